@@ -1,15 +1,17 @@
 #!/usr/bin/env python3
 """Headline benchmark: reads/s through the breakpoint-graph build on a synthetic long-read amplicon BAM.
 
-    python bench.py --gpus 1 --steps K --warmup W [--config cfg3] [--reads N] [--bam-reads M]
+    python bench.py --gpus 1 --steps K --warmup W [--config cfg3] [--reads N] [--dump-outputs DIR] [--full [--bam-reads M]]
 
 One "step" = one full pass of the hot path over the resident batch: decoded records already in HBM ->
 BreakpointGraph objects + *_graph.txt written (Gurobi cycle step skipped), i.e. the contract's timed region.
-Prints ONE JSON line (rank 0) with
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0) with `value` / `ms_per_step` and
   `roofline`      dominant kernel (coral_cigar_scan), HIP-event timed on the launch stream inside the timed steps;
-  `h2d_ms` / `value_incl_h2d`   pinned host -> HBM of the resident arrays, measured once, and the rate with it added;
   `first_build_ms` / `value_cold`   the FIRST build of the process on fresh records (what one `CoRAL.py reconstruct` run pays: library
-                  load, first launches, pinned pools, every per-records one-off), before any warm-up; `value` is the steady state;
+                  load, first launches, pinned pools, every per-records one-off), before any warm-up; `value` is the steady state.
+`--dump-outputs DIR` writes the graphs of the last timed step as DIR/<table>.npy (float64, see dump_outputs) before the line.
+`--full` adds the measurements that take runs of their own, after the timed steps:
+  `h2d_ms` / `value_incl_h2d`   pinned host -> HBM of the resident arrays, measured once, and the rate with it added;
   `decode`        BGZF/BAM decode throughput of the product's GPU decoder (coral_bamgpu_*) on a BAM FILE of the whole workload
                   (--bam-reads 0 = the configuration's read count: 2 M reads, 18.7 GB at config 3); `decode_host` the host pipeline
                   (coral_bam_decode_*) on the first tenth of the same file (a byte range; the whole file would take 17 s);
@@ -44,9 +46,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="cfg3")
     ap.add_argument("--reads", type=int, default=0, help="override the read count of the config (0 = as configured)")
-    ap.add_argument("--cpu-sample", type=int, default=50000, help="reads in the CPU-baseline sample (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure H2D, the BAM decode / end-to-end legs and the CPU baseline "
+                         "(runs of their own; a plain run only sets up, warms up, times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the graphs the last timed step built as DIR/<table>.npy (float64)")
+    ap.add_argument("--cpu-sample", type=int, default=50000, help="--full: reads in the CPU-baseline sample (0 = skip)")
     ap.add_argument("--bam-reads", type=int, default=0,
-                    help="reads of the BAM the decode / end-to-end legs run on (same generator and layout); 0 (default) = the "
+                    help="--full: reads of the BAM the decode / end-to-end legs run on (same generator and layout); 0 (default) = the "
                          "configuration's own read count, i.e. the size the metric is quoted on; -1 = skip those legs")
     ap.add_argument("--backend", default="nccl", help="nccl (= RCCL, default) or gloo (single-GPU rehearsal of N > 1)")
     ap.add_argument("--shared-gpu", action="store_true", help="rehearsal only: every rank uses cuda:0")
@@ -58,6 +65,8 @@ def main():
     ap.add_argument("--dry-launch", action="store_true",
                     help="N > 1 without a launcher: the rank processes only print their RANK / LOCAL_RANK / WORLD_SIZE and exit (CPU test)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without torch.distributed.run: this process becomes the launcher.  Nothing has touched the
@@ -70,9 +79,12 @@ def main():
     if a.dry_launch:
         if os.environ.get("CORAL_BENCH_DRY_FAIL_RANK") == os.environ.get("RANK", "0"):      # (test hook: a rank that dies)
             sys.exit(3)
-        print(json.dumps({"dry_launch": True, "rank": int(os.environ.get("RANK", "0")), "local_rank": int(os.environ.get("LOCAL_RANK", "0")),
-                          "world": int(os.environ.get("WORLD_SIZE", "1")), "master": "%s:%s" % (os.environ.get("MASTER_ADDR"),
-                                                                                                 os.environ.get("MASTER_PORT"))}), flush=True)
+        # ranks 1.. share the launcher's stderr: the line goes out in ONE write (print() issues the text and its newline as two
+        # writes when Python runs unbuffered, and another rank's line could land between them)
+        sys.stdout.write(json.dumps({"dry_launch": True, "rank": int(os.environ.get("RANK", "0")), "local_rank": int(os.environ.get("LOCAL_RANK", "0")),
+                                     "world": int(os.environ.get("WORLD_SIZE", "1")), "master": "%s:%s" % (os.environ.get("MASTER_ADDR"),
+                                                                                                            os.environ.get("MASTER_PORT"))}) + "\n")
+        sys.stdout.flush()
         return
 
     import torch
@@ -118,7 +130,7 @@ def main():
         dr = sharding.shard_records(rec, rank, world, dev)      # world == 1: all records on this GPU
         n_reads_total = cfg.n_reads
     alg_bytes_local = dr.algorithmic_bytes()
-    if not (rank == 0 and a.bam_reads == 0 and a.mode == "shard"):
+    if not (a.full and rank == 0 and a.bam_reads == 0 and a.mode == "shard"):
         rec = None                                                  # (rank 0 keeps the records: they become the BAM file of the legs below)
     torch.cuda.empty_cache()
 
@@ -166,13 +178,15 @@ def main():
     scan_ms_avg = sum(scan_ms) / max(1, len(scan_ms))
     kernels.PROFILE.pop("scan_ms", None)
     b_last = b
-    h2d_ms = measure_h2d(dr) if a.mode == "shard" else None          # every rank uploads its own shard: max over ranks
+    if a.dump_outputs and rank == 0 and b is not None:          # (with --mode samples every rank holds a result)
+        dump_outputs(b, a.dump_outputs)
+    h2d_ms = measure_h2d(dr) if (a.full and a.mode == "shard") else None          # every rank uploads its own shard: max over ranks
     if world > 1 and h2d_ms is not None:
         tt = torch.tensor([h2d_ms], dtype=torch.float64, device=dev if a.backend == "nccl" else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         h2d_ms = float(tt.item())
     legs = None
-    if a.bam_reads >= 0 and a.mode == "shard":
+    if a.full and a.bam_reads >= 0 and a.mode == "shard":
         try:
             legs = bam_legs(a, rank, world, dev, work, rec, cfg.n_reads)
         except Exception as exc:                      # noqa: BLE001 — the headline above must not be lost to a full disk or the like
@@ -216,14 +230,14 @@ def main():
         out["config"]["first_build_phase_ms"] = first_phases
         out["config"]["host_threads"] = {"build": "1 Python thread + %s look-ahead threads + %s helper threads of the interval search" %
                                          (os.environ.get("CORAL_SEARCH_THREADS", "6"), os.environ.get("CORAL_SEARCH_HELPERS", "8" if (os.cpu_count() or 1) >= 16 else "3" if (os.cpu_count() or 1) >= 8 else "1")),
-                                         "decode": "see decode.host_threads"}
+                                         "decode": "see decode.host_threads" if legs and "decode" in legs else "not measured in this run"}
         out["config"]["library"] = _lib.lib().coral_version().decode()
         if h2d_ms is not None:
             out["h2d_ms"] = round(h2d_ms, 1)
             out["value_incl_h2d"] = n_reads_total / (ms_per_step * 1e-3 + h2d_ms * 1e-3)
         if legs:
             out.update(legs)
-        if a.cpu_sample and world == 1:
+        if a.full and a.cpu_sample and world == 1:
             out["cpu_baseline"] = cpu_baseline(a.config, min(a.cpu_sample, cfg.n_reads), work)
         print(json.dumps(out), flush=True)
     if world > 1:
@@ -288,6 +302,59 @@ def launch_ranks(n: int) -> int:
                 p.kill()
     t.join(timeout=10)
     return rc
+
+
+# column layout of the tables dump_outputs writes (chromosomes as global_names.chr_idx, orientations '+' / '-' as +1 / -1, read sets
+# as their sizes; column 0 is the amplicon: the graph's position in the result's lr_graph)
+DUMP_COLUMNS = {
+    "amplicons": ("amplicon", "max_cn", "sequence_edges", "concordant_edges", "discordant_edges", "source_edges"),
+    "amplicon_intervals": ("amplicon", "chr", "start", "end"),
+    "sequence_edges": ("amplicon", "chr", "start", "end", "sr_count", "lr_count", "lr_nc", "size", "cn"),
+    "concordant_edges": ("amplicon", "chr1", "pos1", "o1", "chr2", "pos2", "o2", "sr_count", "lr_count", "reads", "cn"),
+    "discordant_edges": ("amplicon", "chr1", "pos1", "o1", "chr2", "pos2", "o2", "sr_count", "sr_cn", "lr_count", "reads", "cn"),
+    "source_edges": ("amplicon", "chr", "pos", "o", "sr_count", "sr_cn", "lr_cn", "cn"),
+}
+DUMP_MAX_BYTES = 64_000_000          # all files written, .npy headers included
+DUMP_HEADER_BYTES = 1024             # per table: its .npy header (128 bytes for these shapes) + the one row a sampled table keeps
+
+
+def dump_outputs(b, out_dir):
+    """The graphs a caller of the timed path receives (``b.lr_graph`` of the last step) as float64 tables ``out_dir/<name>.npy``,
+    columns as in DUMP_COLUMNS.  Rows are sorted: the order of discordant edges within a graph follows set iteration, which
+    varies with PYTHONHASHSEED, and sorted tables compare row for row between two builds.  A table set above DUMP_MAX_BYTES
+    keeps a fixed, seeded sample of the rows of every table (the same share of each, at least one row, still sorted).  A table
+    without rows is not written (source edges: the graph build, like the reference's, adds none); the per-graph row counts of
+    every table are in amplicons.npy."""
+    import numpy as np
+    from coral_amd.global_names import chr_idx
+    c = lambda name: chr_idx.get(name, -1)
+    o = lambda sign: 1 if sign == "+" else -1
+    rows = {k: [] for k in DUMP_COLUMNS}
+    for k, g in enumerate(b.lr_graph):
+        rows["amplicons"].append([k, g.max_cn, len(g.sequence_edges), len(g.concordant_edges), len(g.discordant_edges),
+                                  len(g.source_edges)])
+        rows["amplicon_intervals"] += [[k, c(ai[0]), ai[1], ai[2]] for ai in g.amplicon_intervals]
+        rows["sequence_edges"] += [[k, c(e[0]), e[1], e[2], e[3], e[5], e[6], e[7], e[8]] for e in g.sequence_edges]
+        rows["concordant_edges"] += [[k, c(e[0]), e[1], o(e[2]), c(e[3]), e[4], o(e[5]), e[6], e[8], len(e[9]), e[10]]
+                                     for e in g.concordant_edges]
+        rows["discordant_edges"] += [[k, c(e[0]), e[1], o(e[2]), c(e[3]), e[4], o(e[5]), e[6], e[8], e[9], len(e[10]), e[11]]
+                                     for e in g.discordant_edges]
+        rows["source_edges"] += [[k, c(e[3]), e[4], o(e[5]), e[6], e[8], e[9], e[10]] for e in g.source_edges]
+    tables = {}
+    for name, cols in DUMP_COLUMNS.items():
+        t = np.asarray(rows[name], dtype=np.float64).reshape(-1, len(cols))
+        tables[name] = t[np.lexsort(t.T[::-1])] if len(t) else t
+    total = sum(t.nbytes for t in tables.values())
+    budget = DUMP_MAX_BYTES - DUMP_HEADER_BYTES * len(tables)
+    if total > budget:
+        rng = np.random.default_rng(0)
+        for name, t in tables.items():
+            keep = max(1, int(len(t) * budget / total)) if len(t) else 0
+            tables[name] = t[np.sort(rng.choice(len(t), keep, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in tables.items():
+        if len(t):
+            np.save(os.path.join(out_dir, name + ".npy"), t)
 
 
 def measure_h2d(dr):
