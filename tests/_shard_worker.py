@@ -1,4 +1,7 @@
-"""Rank body of the world_size-2 gloo test (CPU): sharded graph build with oracle-backed local kernels."""
+"""Rank body of the gloo tests: sharded graph build.  Default (CPU): oracle-backed local kernels.  With ``--device cuda:0``:
+the real HIP kernels, every rank on that one device, and for the BAM leg the GPU byte-range decoder.
+
+usage: _shard_worker.py CASE OUTDIR [BAM] [--device DEV]"""
 import json
 import os
 import sys
@@ -15,19 +18,26 @@ class _Patch:
 def main():
     import torch
     import torch.distributed as dist
-    case, outdir = sys.argv[1], sys.argv[2]
+    args = sys.argv[1:]
+    device = "cpu"
+    if "--device" in args:
+        k = args.index("--device")
+        device = args[k + 1]
+        del args[k:k + 2]
+    case, outdir = args[0], args[1]
     rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
     dist.init_process_group("gloo", rank=rank, world_size=world)
     from coral_amd import sharding, synth
     from coral_amd.breakpoint_graph import graph_text
     from tests.product_check import install_cpu_kernel_fakes
-    install_cpu_kernel_fakes(_Patch())
+    if device == "cpu":
+        install_cpu_kernel_fakes(_Patch())
     cfg, rec = synth.dataset(case, "cpu")
     cn, seeds = os.path.join(outdir, "cn%d.bed" % rank), os.path.join(outdir, "seeds%d.bed" % rank)
     synth.write_cn_bed(cfg, cn)
     synth.write_seed_bed(cfg, seeds)
-    if len(sys.argv) > 3:          # per-rank input: every rank decodes only its byte range of the BAM written by the test
-        dr = sharding.load_bam_sharded(sys.argv[3], rank, world, "cpu", n_threads=2)
+    if len(args) > 2:          # per-rank input: every rank decodes only its byte range of the BAM written by the test
+        dr = sharding.load_bam_sharded(args[2], rank, world, device, n_threads=2)
         assert dr.has_host == (rank == 0)
         if rank == 0:           # unified read-name ids = first appearance over the whole file, as a one-process decode numbers them
             want = rec.materialise_names()
@@ -36,8 +46,10 @@ def main():
             first_seen = list(dict.fromkeys(want[i] for i in ids))
             assert dr.names == first_seen
     else:
-        dr = sharding.shard_records(rec, rank, world, "cpu")
-    if world <= 3:
+        dr = sharding.shard_records(rec, rank, world, device)
+    if world == 1:             # the unsharded run the GPU tests compare with
+        assert dr.n == dr.n_total
+    elif world <= 3:
         assert 0 < dr.n < dr.n_total
     else:                      # many ranks on a small file: a byte range may hold no record start at all
         assert 0 <= dr.n < dr.n_total

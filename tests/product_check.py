@@ -173,7 +173,7 @@ def pair_table_cpu(cols, off, chroms, chr_rank, cutoff=100, min_mapq=20, gap_=10
 # ---- oracle-backed stand-ins for the device kernels (CPU tests of the host logic only) ----------------
 def install_cpu_kernel_fakes(monkeypatch):
     from coral_amd import kernels
-    from oracle.hostrecords import HostRecords
+    from oracle.hostrecords import IS_ALN, HostRecords
     hosts = {}
 
     class _LocalShard:
@@ -210,9 +210,10 @@ def install_cpu_kernel_fakes(monkeypatch):
             mb.append(sum(e - s for s, e in bl)); qi.append(h.infer_read_length(i) or 0)
             b0.append(bl[0][0] if bl else -1); b1.append(bl[-1][1] if bl else -1)
             if h.mapq[i] >= min_mapq:
+                blk_op = np.nonzero(IS_ALN[h.ops(i)[0]])[0]         # CIGAR op index of every block (include/coral_hip.h)
                 for k in range(len(bl) - 1):
                     if abs(bl[k + 1][0] - bl[k][1]) > min_gap:
-                        rows.append((i, k + 1, bl[k][1], bl[k + 1][0], b0[-1], b1[-1]))
+                        rows.append((i, int(blk_op[k + 1]), bl[k][1], bl[k + 1][0], b0[-1], b1[-1]))
         summary = torch.tensor([mb, qi, b0, b1], dtype=torch.int32).t().contiguous().reshape(-1, 4)
         return summary, lambda: torch.tensor(rows, dtype=torch.int64).reshape(-1, 6)
 

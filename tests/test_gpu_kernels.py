@@ -376,3 +376,111 @@ def test_sa_table_error_semantics():
         dict(tid=0, pos=20, cigar=[(M, 50)], name="y")])
     with pytest.raises(ZeroDivisionError):
         build_chimeric_table(DeviceRecords(zero, "cuda:0"))
+
+
+class _Rows:
+    """The fields of a ChimericTable that coral_hash_rows and its stand-in read: device rows (int32 [n, 8]: qs, qe, tid, ra,
+    rb, strand, mapq, nm) and the host columns tid / ra / rb."""
+
+    def __init__(self, tid, ra, rb, device="cuda:0"):
+        self.tid, self.ra, self.rb = (np.asarray(v, dtype=np.int64) for v in (tid, ra, rb))
+        self.n_rows = len(self.tid)
+        rows = np.zeros((self.n_rows, 8), dtype=np.int32)
+        rows[:, 2], rows[:, 3], rows[:, 4] = self.tid, self.ra, self.rb
+        rows[:, 5] = self.ra > self.rb
+        self.dev_rows = torch.from_numpy(rows).to(device)
+
+
+def _hash_rows_stand_in():
+    from tests.product_check import install_cpu_kernel_fakes
+
+    class _Keep(dict):          # records what install_cpu_kernel_fakes would patch in, patches nothing
+        def setattr(self, obj, name, val):
+            self[name] = val
+    k = _Keep()
+    install_cpu_kernel_fakes(k)
+    return k["_hash_rows_local"]
+
+
+def _check_hash_rows(dr, T, seg, has):
+    from coral_amd import kernels
+    got = kernels._hash_rows_local(dr, T, seg, has)
+    want = _hash_rows_stand_in()(dr, T, seg, has)
+    for what, g, w in zip(("cni0", "cni1", "e_key", "e_row"), got, want):
+        assert g.shape == w.shape and np.array_equal(g, w), (what, np.nonzero(g != w)[0][:8] if g.shape == w.shape else (g.shape, w.shape))
+    return got
+
+
+def test_hash_rows_segment_edges():
+    """coral_hash_rows on a hand-made table against its stand-in: ends at start - 1, start, end - 1 and end of adjacent
+    segments and of segments with a gap between them, '-' rows (ra > rb), both ends in one segment (one entry), a contig
+    without segments (-3), a position between segments (-1); then the same rows against an empty segment table."""
+    from coral_amd.records import DeviceRecords
+    dr = DeviceRecords(synth.records_from_alignments([]), "cuda:0")
+    # contig 0: [100, 200) #4, [200, 300) #5 adjacent, gap, [400, 500) #6; contig 1: no segments; contig 2: [0, 50) #0, [60, 61) #1
+    seg = np.array([[0, 100, 200, 4], [0, 200, 300, 5], [0, 400, 500, 6], [2, 0, 50, 0], [2, 60, 61, 1]], dtype=np.int32).T
+    has = np.array([1, 0, 1, 0], dtype=np.int32)
+    edges = [99, 100, 101, 199, 200, 201, 299, 300, 301, 350, 399, 400, 499, 500]
+    tid, ra, rb = [], [], []
+    for a in edges:
+        for b in edges:
+            tid.append(0); ra.append(a); rb.append(b)                      # a > b: '-' rows
+    for a, b in [(0, 0), (0, 49), (49, 50), (50, 60), (59, 60), (60, 60), (60, 61), (61, 70), (10, 5)]:
+        tid.append(2); ra.append(a); rb.append(b)
+    for a, b in [(150, 250), (450, 120), (0, 5)]:
+        tid.append(1); ra.append(a); rb.append(b)                          # contig without segments: -3
+    tid.append(3); ra.append(5); rb.append(1)                               # contig that is not in the CN file at all
+    T = _Rows(tid, ra, rb)
+    c0, c1, e_key, e_row = _check_hash_rows(dr, T, seg, has)
+    assert set(c0.tolist()) == {-3, -1, 0, 1, 4, 5, 6} and (c0 == -3).sum() == 4
+    assert len(e_key) == (c0 >= 0).sum() + ((c1 >= 0) & (c1 != c0)).sum()
+    assert (np.diff(e_key) >= 0).all()
+    none = np.zeros((4, 0), dtype=np.int32)
+    c0, c1, e_key, _ = _check_hash_rows(dr, T, none, has)                 # n_seg = 0, contigs flagged: every end -1
+    assert (c0[T.tid == 0] == -1).all() and len(e_key) == 0
+    c0, _, _, _ = _check_hash_rows(dr, T, none, np.zeros(4, dtype=np.int32))
+    assert (c0 == -3).all()
+
+
+@pytest.mark.parametrize("name", ["tiny_edge", "small", "cfg3_12k"])
+def test_hash_rows_real_tables(name, tmp_path, monkeypatch):
+    """coral_hash_rows on the chimeric tables of real builds, with the CN segments the build itself hands to it (captured from
+    hash_alignment_to_seg), against the stand-in."""
+    from coral_amd import infer_breakpoint_graph as ibg
+    from coral_amd import kernels
+    from coral_amd.records import DeviceRecords
+    cfg, rec = synth.dataset(name, "cpu")
+    cn, seeds = str(tmp_path / "cn.bed"), str(tmp_path / "seeds.bed")
+    synth.write_cn_bed(cfg, cn)
+    synth.write_seed_bed(cfg, seeds)
+    dr = DeviceRecords(rec, "cuda:0")
+    b = ibg.bam_to_breakpoint_nanopore(None, seeds, records=dr)
+    b.read_cns(cn)
+    b.fetch()
+    calls, real = [], kernels.hash_rows
+
+    def keep(dr_, T_, seg_, has_):
+        calls.append((T_, np.array(seg_, copy=True), np.array(has_, copy=True)))
+        return real(dr_, T_, seg_, has_)
+    monkeypatch.setattr(kernels, "hash_rows", keep)
+    b.hash_alignment_to_seg()
+    assert len(calls) == 1                                   # disjoint segments: the path that runs coral_hash_rows
+    T, seg, has = calls[0]
+    assert T is b._chim and seg.shape[0] == 4 and seg.shape[1] > 0
+    c0, c1, e_key, _ = _check_hash_rows(dr, T, seg, has)
+    assert T.n_rows > 50 and (c0 >= 0).sum() > 10 and len(e_key) > 10
+
+
+def test_hash_rows_stable_across_tiles():
+    """300 k rows whose ends fall into a handful of segments: long runs of equal keys over many radix-sort tiles must keep
+    their append order (row, then end)."""
+    from coral_amd.records import DeviceRecords
+    dr = DeviceRecords(synth.records_from_alignments([]), "cuda:0")
+    seg = np.array([[0, 0, 1000, 0], [0, 1000, 2000, 1], [0, 3000, 4000, 2], [1, 0, 500, 0]], dtype=np.int32).T
+    rng = np.random.default_rng(11)
+    n = 300_000
+    tid = rng.integers(0, 2, n)
+    ra, rb = rng.integers(0, 4100, n), rng.integers(0, 4100, n)
+    T = _Rows(tid, ra, rb)
+    c0, c1, e_key, e_row = _check_hash_rows(dr, T, seg, np.array([1, 1], dtype=np.int32))
+    assert len(e_key) > n // 2 and len(np.unique(e_key)) == 4

@@ -2,6 +2,7 @@
 of the per-segment sums.  The merged result must equal the reference golden (== the unsharded result)."""
 import json
 import os
+import signal
 import socket
 import subprocess
 import sys
@@ -77,3 +78,94 @@ def test_rccl_arms_at_world_one():
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "_rccl_world1.py")], env=env, cwd=ROOT, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "rccl world-1 ok" in r.stdout, r.stdout[-2000:] + r.stderr[-3000:]
+
+
+# ---- the same runs with the real HIP kernels: gloo, every rank on cuda:0 -----------------------------------------------
+_FATAL = (134, 139, 124, 137, -6, -11)       # abort, segfault, time limit: nothing more may start on the GPU in this session
+
+
+def _stop_rank(p):
+    """End a rank and everything it started.  ``p`` is the ``timeout`` wrapper, which cannot pass SIGKILL on to the rank: the
+    whole process group goes (each rank is started as the leader of a session of its own), then the wrapper is reaped."""
+    try:
+        os.killpg(p.pid, signal.SIGKILL)
+    except ProcessLookupError:
+        pass
+    p.wait()
+
+
+def _run_ranks_gpu(world, case, outdir, extra=()):
+    """One rank per process, all on cuda:0, each under its own time limit; the ranks are polled and the first that exits
+    non-zero stops the others.  A crash or a time limit ends the whole session (pytest.exit)."""
+    import time
+    os.makedirs(str(outdir), exist_ok=True)
+    port = _free_port()
+    procs, logs = [], []
+    failed = None
+    try:
+        for rank in range(world):
+            env = dict(os.environ, PYTHONHASHSEED="0", RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1",
+                       MASTER_PORT=str(port), OMP_NUM_THREADS="2")
+            log = open(os.path.join(str(outdir), "rank%d.log" % rank), "w")
+            logs.append(log)
+            procs.append(subprocess.Popen(["timeout", "-k", "10", "300", sys.executable, os.path.join(ROOT, "tests", "_shard_worker.py"),
+                                           case, str(outdir)] + list(extra) + ["--device", "cuda:0"],
+                                          env=env, cwd=ROOT, stdout=log, stderr=subprocess.STDOUT, start_new_session=True))
+        while failed is None and any(p.poll() is None for p in procs):
+            failed = next((p for p in procs if p.poll() not in (None, 0)), None)
+            time.sleep(0.2)
+        failed = failed or next((p for p in procs if p.returncode != 0), None)
+    finally:
+        if failed is not None or any(p.poll() is None for p in procs):      # a failure, or the test itself was interrupted
+            for p in procs:
+                _stop_rank(p)
+    for log in logs:
+        log.close()
+    if failed is not None:
+        tails = []
+        for rank, p in enumerate(procs):
+            with open(os.path.join(str(outdir), "rank%d.log" % rank)) as fp:
+                tails.append("--- rank %d (exit %s)\n%s" % (rank, p.returncode, fp.read()[-3000:]))
+        msg = "world %d %s: rank exited with %s\n%s" % (world, case, failed.returncode, "\n".join(tails))
+        if failed.returncode in _FATAL:
+            pytest.exit(msg, returncode=1)
+        pytest.fail(msg)
+    with open(os.path.join(str(outdir), "result.json")) as fp:
+        return json.load(fp)
+
+
+def _check_gpu_run(case, world, golden_dir, tmp_path, extra=()):
+    """The sharded run meets the golden, and its graph files are byte-identical to a one-rank run of the same worker."""
+    res = _run_ranks_gpu(world, case, tmp_path / ("w%d" % world), extra)
+    with open(os.path.join(golden_dir, "e2e_%s.json" % case)) as fp:
+        gold = json.load(fp)
+    assert res["normal_cov"] == gold["A2"]["normal_cov"]
+    assert 0 < res["shard"][1] < res["shard"][2] == gold["n_records"] and res["world"] == world
+    assert sorted(res["files"]) == sorted(gold["files"])
+    for k in res["files"]:
+        compare_graph_text(res["files"][k], gold["files"][k])
+        assert open(str(tmp_path / ("w%d" % world) / ("sh" + k[3:]))).read() == res["files"][k]
+    one = _run_ranks_gpu(1, case, tmp_path / "w1", extra)
+    assert one["world"] == 1 and one["normal_cov"] == res["normal_cov"] and one["large_indel"] == res["large_indel"]
+    assert one["files"] == res["files"]
+    for k in res["files"]:
+        a, b = (open(str(tmp_path / d / ("sh" + k[3:])), "rb").read() for d in ("w%d" % world, "w1"))
+        assert a == b, k
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case,world", [("tiny_edge", 2), ("small", 3)])
+def test_shard_merge_real_kernels(case, world, golden_dir, tmp_path):
+    """In-memory shards on cuda:0, real cigar_scan / segment_coverage / point_cover on every rank, exchange over gloo."""
+    _check_gpu_run(case, world, golden_dir, tmp_path)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case,world", [("tiny_edge", 2)])
+def test_per_rank_bam_decode_real_kernels(case, world, golden_dir, tmp_path):
+    """Every rank decodes its byte range of the BAM with the GPU decoder, then builds with the real kernels."""
+    from coral_amd import bam, synth
+    cfg, rec = synth.dataset(case, "cpu")
+    path = str(tmp_path / "input.bam")
+    bam.write_bam_native(rec, path, seed=7, n_threads=2)
+    _check_gpu_run(case, world, golden_dir, tmp_path, extra=[path])
