@@ -117,6 +117,13 @@ def lib():
     L.coral_bamgpu_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_double)]
     L.coral_bamgpu_close.argtypes = [C.c_void_p]
     L.coral_bgzf_inflate.argtypes = [P, P, C.c_int32, P, P, P]
+    L.coral_bam_decode_range_cov.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P, P, P, C.c_int32, C.c_int32,
+                                             C.POINTER(C.c_void_p)]
+    L.coral_bam_coverage_result.argtypes = [C.c_void_p, C.c_int32, P]
+    L.coral_bamgpu_coverage.argtypes = [C.c_void_p, C.c_int32, P, P, P, C.c_int32, C.c_int32, P]
+    L.coral_bamgpu_coverage_result.argtypes = [C.c_void_p, C.c_int32, P, P]
+    for name in ("coral_bam_decode_range_cov", "coral_bam_coverage_result", "coral_bamgpu_coverage", "coral_bamgpu_coverage_result"):
+        getattr(L, name).restype = C.c_int
     for name in ("coral_bamgpu_open", "coral_bamgpu_start", "coral_bamgpu_next", "coral_bamgpu_emit", "coral_bamgpu_host",
                  "coral_bamgpu_stats", "coral_bamgpu_close", "coral_bgzf_inflate"):
         getattr(L, name).restype = C.c_int

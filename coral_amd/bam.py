@@ -8,10 +8,12 @@ real coordinate-sorted BAM (htslib / pysam are not available offline); it is not
 from __future__ import annotations
 
 import ctypes as C
+import gzip
+import numbers
 import os
 import struct
 import zlib
-from typing import Optional
+from typing import Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -109,6 +111,13 @@ def decode_bam_gpu(path: str, device="cuda:0", n_threads: Optional[int] = None, 
     """The same result as ``decode_bam`` with the inflate and the record parsing on the GPU (csrc/coral_bamgpu.hip): the host
     only reads the file and uploads COMPRESSED bytes; the CIGAR words of the returned Records are a device tensor (they never
     exist in host memory), everything else is host-side as before.  ``batch_bytes``: inflated bytes per batch (0 = the default, 2.52 GiB)."""
+    return _decode_gpu(path, device, n_threads, rank, world, batch_bytes)[0]
+
+
+def _decode_gpu(path: str, device, n_threads: Optional[int], rank: int, world: int, batch_bytes: int, coverage=None, records=True):
+    """decode_bam_gpu; with ``coverage`` = (segments int32 [3][S], quality threshold, read_callback code) the window-coverage
+    request of coral_bamgpu_coverage rides along and its S int64 counts come back as the second result (records: None
+    unless ``records``)."""
     L = _lib.lib()
     dev = torch.device(device)
     if dev.type != "cuda":
@@ -129,6 +138,16 @@ def decode_bam_gpu(path: str, device="cuda:0", n_threads: Optional[int] = None, 
         # still has queued (possibly on the block's previous owner) finish first — once per decode.
         torch.cuda.current_stream(dev).synchronize()
         fail = lambda what, rc: _lib.CoralHipError("%s(%s) failed (%d): %s" % (what, path, rc, L.coral_bam_last_error().decode()))
+        counts = None
+        if coverage is not None:
+            segs, thr, cb = coverage
+            d_segs = torch.from_numpy(np.ascontiguousarray(segs, dtype=np.int32)).to(dev)
+            d_counts = torch.zeros(max(segs.shape[1], 1), dtype=torch.int64, device=dev)
+            torch.cuda.synchronize(dev)
+            S = int(segs.shape[1])
+            rc = L.coral_bamgpu_coverage(h, S, d_segs[0].data_ptr(), d_segs[1].data_ptr(), d_segs[2].data_ptr(), thr, cb, d_counts.data_ptr())
+            if rc != 0:
+                raise fail("coral_bamgpu_coverage", rc)
         rc = L.coral_bamgpu_start(h, base, int(ws_bytes.value))
         if rc != 0:
             raise fail("coral_bamgpu_start", rc)
@@ -148,6 +167,11 @@ def decode_bam_gpu(path: str, device="cuda:0", n_threads: Optional[int] = None, 
             if words:
                 pieces.append(piece[:words])
                 total += words
+        if coverage is not None:
+            counts = np.zeros(S, dtype=np.int64)
+            rc = L.coral_bamgpu_coverage_result(h, S, counts.ctypes.data, stream)
+            if rc != 0:
+                raise fail("coral_bamgpu_coverage_result", rc)
         cigar = torch.cat(pieces) if len(pieces) > 1 else (pieces[0] if pieces else torch.zeros(0, dtype=torch.int32, device=dev))
         del pieces
         dh = C.c_void_p()
@@ -164,11 +188,120 @@ def decode_bam_gpu(path: str, device="cuda:0", n_threads: Optional[int] = None, 
                            nonacgt_records_fetched=int(gst[2]), batch_bytes=int(gst[3]), host_seconds=float(gsecs[1]), read_seconds=float(gsecs[2]),
                            setup_seconds=float(gsecs[3]), waited_for_file_seconds=float(gsecs[4]), waited_for_gpu_seconds=float(gsecs[5]),
                            workspace_bytes=int(ws_bytes.value))
-        return _records_from_handle(L, dh, cigar, total)
+        return (_records_from_handle(L, dh, cigar, total) if records else None), counts
     finally:
         # (close drains the decoder's streams — a byte range may have batches of its overhang still being inflated — and only
         # then the workspace, which those kernels write, is released: `ws` lives until this function returns)
         L.coral_bamgpu_close(h)
+
+
+# ----------------------------------------------------------------------------------------------
+# window coverage with a base-quality threshold (the coverage track of `plot`)
+# ----------------------------------------------------------------------------------------------
+_READ_CALLBACKS = {"nofilter": 0, "all": 1}
+_I32_MAX = (1 << 31) - 1
+
+
+def bam_reference_names(path: str):
+    """Contig names of a BAM file's header, in tid order (read with gzip: BGZF is a series of gzip members)."""
+    with gzip.open(path, "rb") as fp:
+        def take(n):
+            b = fp.read(n)
+            if len(b) != n:
+                raise _lib.CoralHipError("%s: truncated BAM header" % path)
+            return b
+        if take(4) != b"BAM\x01":
+            raise _lib.CoralHipError("%s: not a BAM file" % path)
+        take(struct.unpack("<i", take(4))[0])
+        names = []
+        for _ in range(struct.unpack("<i", take(4))[0]):
+            names.append(take(struct.unpack("<i", take(4))[0]).rstrip(b"\0").decode())
+            take(4)
+        return names
+
+
+def quality_threshold_value(quality_threshold) -> int:
+    """The base-quality threshold as an int in 0..255.  Integer-valued floats (``20.0``: the reference passes a float) are
+    accepted; a fractional value raises ValueError (what pysam does with one is not pinned here)."""
+    if isinstance(quality_threshold, numbers.Integral):
+        v = int(quality_threshold)
+    elif isinstance(quality_threshold, numbers.Real) and float(quality_threshold).is_integer():
+        v = int(quality_threshold)
+    else:
+        raise ValueError("quality_threshold must be an integer in 0..255, got %r" % (quality_threshold,))
+    if not 0 <= v <= 255:
+        raise ValueError("quality_threshold must be an integer in 0..255, got %r" % (quality_threshold,))
+    return v
+
+
+def coverage_segments(windows, ref_names: Sequence[str]):
+    """Windows (chrom, start, stop) -> (segments int32 [3][S]: tid, start, end of the sorted, disjoint pieces the windows are
+    cut into at every start and stop; first, last int64 [W]: window w is the sum of the segments first[w]:last[w])."""
+    tid_of = {c: k for k, c in enumerate(ref_names)}
+    W = len(windows)
+    tid, lo, hi = np.empty(W, dtype=np.int64), np.empty(W, dtype=np.int64), np.empty(W, dtype=np.int64)
+    for k, w in enumerate(windows):
+        if len(w) != 3:
+            raise ValueError("a window is (chrom, start, stop), got %r" % (w,))
+        chrom, a, b = w
+        if chrom not in tid_of:
+            raise ValueError("unknown contig %r" % (chrom,))
+        a, b = int(a), int(b)
+        if a < 0 or b < a:
+            raise ValueError("bad window %r: needs 0 <= start <= stop" % (w,))
+        tid[k], lo[k], hi[k] = tid_of[chrom], min(a, _I32_MAX), min(b, _I32_MAX)
+    key_lo, key_hi = (tid << 32) | lo, (tid << 32) | hi
+    cuts = np.unique(np.concatenate([key_lo, key_hi]))
+    delta = np.zeros(len(cuts) + 1, dtype=np.int64)
+    np.add.at(delta, np.searchsorted(cuts, key_lo), 1)
+    np.add.at(delta, np.searchsorted(cuts, key_hi), -1)
+    covered = np.cumsum(delta)[:max(len(cuts) - 1, 0)] > 0          # piece k = [cuts[k], cuts[k + 1]) lies inside some window
+    keep = covered & ((cuts[:-1] >> 32) == (cuts[1:] >> 32))
+    s_lo, s_hi = cuts[:-1][keep], cuts[1:][keep]
+    segs = np.stack([s_lo >> 32, s_lo & 0xffffffff, s_hi & 0xffffffff]).astype(np.int32).reshape(3, -1)
+    return segs, np.searchsorted(s_lo, key_lo), np.searchsorted(s_lo, key_hi)
+
+
+def window_coverage(path: str, windows: Sequence[Tuple[str, int, int]], quality_threshold=0, read_callback: str = "nofilter",
+                    device="cuda:0", rank: int = 0, world: int = 1, batch_bytes: int = 0, n_threads: Optional[int] = None) -> np.ndarray:
+    """pysam ``AlignmentFile.count_coverage(chrom, start, stop, quality_threshold=..., read_callback=...)`` summed over its four
+    arrays, for every window (chrom, start, stop) of ``windows`` (in that order, may overlap), as exact int64 — counted while
+    the BAM is decoded, the only time SEQ and QUAL are at hand.
+
+    A base counts when its read is on the window's contig (``read_callback='all'``: none of the flags 0x4 | 0x100 | 0x200 |
+    0x400; ``'nofilter'``: every read), has SEQ, it is an aligned base of an M / = / X op (the CG:B,I CIGAR for the
+    placeholder) inside the window, its SEQ code is A, C, G or T, and ``quality_threshold`` is 0 or the read has QUAL (first
+    byte not 0xff; else pysam's query_qualities is None) with QUAL >= the threshold there.  The threshold is an integer in
+    0..255 (``20.0`` is accepted; a fractional value raises ValueError — pysam's own handling of one is not pinned here).  An
+    unknown contig or a window with start < 0 or stop < start raises ValueError.
+
+    The GPU pipeline (csrc/coral_bamgpu.hip: k_bam_cov_plan / k_bam_cov_count per batch) runs on a GPU ``device``; the host
+    pipeline (coral_bam_decode_range_cov) otherwise, or with ``CORAL_BAM_DECODE=cpu``.  With ``world`` > 1 the counts are those
+    of the ``rank``-th byte range; the ranges' counts add up to the whole file's."""
+    thr = quality_threshold_value(quality_threshold)
+    if read_callback not in _READ_CALLBACKS:
+        raise ValueError("read_callback must be 'nofilter' or 'all', got %r" % (read_callback,))
+    cb = _READ_CALLBACKS[read_callback]
+    segs, first, last = coverage_segments(list(windows), bam_reference_names(path))
+    S = segs.shape[1]
+    if n_threads is None:
+        n_threads = default_threads()
+    if torch.device(device).type == "cuda" and os.environ.get("CORAL_BAM_DECODE", "gpu") != "cpu":
+        counts = _decode_gpu(path, device, n_threads, rank, world, batch_bytes, coverage=(segs, thr, cb), records=False)[1]
+    else:
+        L = _lib.lib()
+        h = C.c_void_p()
+        rc = L.coral_bam_decode_range_cov(path.encode(), n_threads, rank, world, S, segs[0].ctypes.data, segs[1].ctypes.data,
+                                          segs[2].ctypes.data, thr, cb, C.byref(h))
+        if rc != 0:
+            raise _lib.CoralHipError("coral_bam_decode_range_cov(%s) failed (%d): %s" % (path, rc, L.coral_bam_last_error().decode()))
+        try:
+            counts = np.zeros(S, dtype=np.int64)
+            _lib.check(L.coral_bam_coverage_result(h, S, counts.ctypes.data), "coral_bam_coverage_result")
+        finally:
+            L.coral_bam_decode_close(h)
+    csum = np.concatenate([[0], np.cumsum(counts, dtype=np.int64)])
+    return (csum[last] - csum[first]).astype(np.int64)
 
 
 def write_bam_native(rec: Records, path: str, seed: int = 0, level: int = 1, n_threads: Optional[int] = None) -> None:
@@ -232,7 +365,7 @@ _NM_PACK = {"c": "<b", "C": "<B", "s": "<h", "S": "<H", "i": "<i", "I": "<I"}
 
 
 def write_bam(rec: Records, path: str, seed: int = 0, long_cigar_as_cg: bool = True, fast_seq: bool = False, *, aux=None,
-              nm_type="i", with_qual: bool = False, block_size: int = 0xff00, empty_block_every: int = 0,
+              nm_type="i", with_qual=False, block_size: int = 0xff00, empty_block_every: int = 0,
               header_comment: str = "") -> None:
     """Serialise ``rec`` as a coordinate-sorted BAM (SEQ = deterministic ACGT with N at the listed non-ACGT
     positions, QUAL absent, tags NM:i and SA:Z; CIGARs with more than 65535 ops go to the CG:B,I tag).
@@ -241,7 +374,7 @@ def write_bam(rec: Records, path: str, seed: int = 0, long_cigar_as_cg: bool = T
       ``aux(i)``        -> (raw tag bytes in FRONT of NM, raw tag bytes BEHIND the last tag) of record i: any SAM aux tags;
       ``nm_type``       one of c C s S i I (htslib stores integers in the smallest type that fits), None (no NM tag), or a
                         callable i -> one of these;
-      ``with_qual``     real QUAL bytes (a hash of the position, 0..60) instead of 0xff;
+      ``with_qual``     real QUAL bytes (a hash of the position, 0..60) instead of 0xff; a callable i -> bool decides per record;
       ``block_size``    payload bytes per BGZF block (small: header, records and tags straddle blocks);
       ``empty_block_every``  an empty BGZF block after every k-th block;
       ``header_comment``     extra @CO text (a long header spans several BGZF blocks)."""
@@ -304,7 +437,7 @@ def write_bam(rec: Records, path: str, seed: int = 0, long_cigar_as_cg: bool = T
         name = names[name_id[i]].encode() + b"\0"
         body = struct.pack("<iiBBHHHiiii", int(tid[i]), int(pos[i]), len(name), int(mapq[i]),
                            _reg2bin(int(pos[i]), int(pos[i]) + max(1, rlen)), len(cig_field), int(flag[i]), l_seq, -1, -1, 0)
-        if with_qual and l_seq:
+        if l_seq and (with_qual(i) if callable(with_qual) else with_qual):
             qual_bytes = ((hash_u32(seed, S_SEQ, torch.arange(l_seq, dtype=torch.int64) + (i + 7) * (1 << 22)) % 61).numpy()
                           .astype(np.uint8).tobytes())
         else:

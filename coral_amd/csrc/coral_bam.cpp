@@ -12,7 +12,8 @@
 //     stage 2 (caller, cheap) hop along the record lengths: record starts of the chunk, hand-over of the record that
 //                             straddles into the next chunk
 //     stage 3 (worker pool)   parse the chunk's records into a per-chunk partial (CIGAR copy + padding, SA tokens, NM,
-//                             non-ACGT scan)
+//                             non-ACGT scan; with a window-coverage request, coral_bam_decode_range_cov, the chunk's
+//                             partial counts per segment, added up in stage 4)
 //     stage 4 (caller)        append the partials in file order; read names -> ids
 // A byte range [rank, world) of the file can be decoded on its own (one process per GPU): the range
 // starts at the first BGZF block at or after its first byte (blocks are found by their magic + BC subfield and a chained
@@ -69,7 +70,7 @@ struct Chunk {
     bool submitted_parse = false;
 };
 
-bool decode_file(const char *path, int n_threads, int rank, int world, Decoded &D) {
+bool decode_file(const char *path, int n_threads, int rank, int world, Decoded &D, const CovTable *cov = nullptr) {
     const auto t_start = std::chrono::steady_clock::now();
     MappedFile f;
     if (!f.open(path, D.error)) return false;
@@ -130,9 +131,10 @@ bool decode_file(const char *path, int n_threads, int rank, int world, Decoded &
         pool.submit([&, c]() {
             Partial &pt = c->part;
             pt.cigar.reserve(c->own / 6 + 64);
+            if (cov) pt.cov.assign(cov->size(), 0);              // the chunk's partial counts, added up in merge()
             for (size_t s : c->starts) {
                 const uint8_t *q = c->buf.data() + s;
-                if (!decode_record(q + 4, rd32(q), ref_id, pt, pt.error)) break;
+                if (!decode_record(q + 4, rd32(q), ref_id, pt, pt.error, cov)) break;
             }
             std::vector<uint8_t>().swap(c->buf);            // SEQ / QUAL bytes are gone from here on
             c->parsed.set();
@@ -141,6 +143,7 @@ bool decode_file(const char *path, int n_threads, int rank, int world, Decoded &
     auto wait = [&](Flag &fl) { while (!fl.get()) if (!pool.help_one()) std::this_thread::yield(); };
 
     D.names.grow(1 << 21);
+    if (cov) D.cov.assign(cov->size(), 0);
     auto merge = [&](Chunk &c) -> bool {
         Partial &pt = c.part;
         if (!pt.error.empty()) { D.error = pt.error; return false; }
@@ -154,6 +157,7 @@ bool decode_file(const char *path, int n_threads, int rank, int world, Decoded &
         for (int32_t cnt : pt.sa_cnt) D.sa_off.push_back(D.sa_off.back() + cnt);
         for (int64_t l : pt.na_rec_local) D.na_rec.push_back(base + l);
         app(D.na_pos, pt.na_pos);
+        for (size_t t = 0; t < pt.cov.size(); ++t) D.cov[t] += pt.cov[t];
         for (const char *s = pt.names.data(), *e = s + pt.names.size(); s < e;) {
             const size_t len = strlen(s);
             D.name_id.push_back(D.names.intern(s, len));
@@ -429,12 +433,12 @@ void coral_bam::set_error(const std::string &msg) { g_bam_err = msg; }
 
 extern "C" const char *coral_bam_last_error(void) { return g_bam_err.c_str(); }
 
-extern "C" int coral_bam_decode_range(const char *path, int32_t n_threads, int32_t rank, int32_t world, void **handle) {
+static int decode_range(const char *path, int32_t n_threads, int32_t rank, int32_t world, const CovTable *cov, void **handle) {
     if (!path || !handle) return CORAL_ERR_ARG;
     Decoded *D = new Decoded();
     bool ok = false;
     try {
-        ok = decode_file(path, n_threads, rank, world, *D);
+        ok = decode_file(path, n_threads, rank, world, *D, cov);
     } catch (const std::exception &e) {          // e.g. bad_alloc on a corrupt size field: never across the C boundary
         D->error = std::string("decoder failed: ") + e.what();
     }
@@ -444,6 +448,30 @@ extern "C" int coral_bam_decode_range(const char *path, int32_t n_threads, int32
         return CORAL_ERR_FORMAT;
     }
     *handle = D;
+    return CORAL_OK;
+}
+
+extern "C" int coral_bam_decode_range(const char *path, int32_t n_threads, int32_t rank, int32_t world, void **handle) {
+    return decode_range(path, n_threads, rank, world, nullptr, handle);
+}
+
+extern "C" int coral_bam_decode_range_cov(const char *path, int32_t n_threads, int32_t rank, int32_t world, int32_t n_seg,
+                                          const int32_t *seg_tid, const int32_t *seg_start, const int32_t *seg_end,
+                                          int32_t quality_threshold, int32_t read_callback, void **handle) {
+    CovTable T;
+    std::string err;
+    if (!make_cov_table(n_seg, seg_tid, seg_start, seg_end, quality_threshold, read_callback, T, err)) {
+        g_bam_err = err;
+        return CORAL_ERR_ARG;
+    }
+    return decode_range(path, n_threads, rank, world, &T, handle);
+}
+
+extern "C" int coral_bam_coverage_result(void *handle, int32_t n_seg, int64_t *counts) {
+    if (!handle || n_seg < 0 || (n_seg > 0 && !counts)) return CORAL_ERR_ARG;
+    Decoded *D = (Decoded *)handle;
+    if ((size_t)n_seg != D->cov.size()) { g_bam_err = "coral_bam_coverage_result: the handle holds no request of this size"; return CORAL_ERR_ARG; }
+    if (n_seg) memcpy(counts, D->cov.data(), (size_t)n_seg * 8);
     return CORAL_OK;
 }
 

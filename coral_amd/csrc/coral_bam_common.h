@@ -45,6 +45,7 @@ struct Decoded {
     // statistics of the decode (coral_bam_decode_stats)
     int64_t compressed_bytes = 0, uncompressed_bytes = 0, n_blocks = 0;
     double seconds = 0.0;
+    std::vector<int64_t> cov;               // window-coverage counts per segment (coral_bam_decode_range_cov)
 };
 
 struct Partial {   // what stage 3 produces for one chunk
@@ -55,6 +56,7 @@ struct Partial {   // what stage 3 produces for one chunk
     std::vector<int64_t> na_rec_local;
     std::vector<int32_t> na_pos;
     std::vector<char> names;                // NUL-separated
+    std::vector<int64_t> cov;               // window-coverage counts of the chunk's records (per segment; empty without a request)
     std::string error;
 };
 
@@ -66,6 +68,81 @@ static const int IS_ALN[16] = {1, 0, 0, 0, 0, 0, 0, 1, 1, 0, 0, 0, 0, 0, 0, 0};
 static const int QRY_ADV[16] = {1, 1, 0, 0, 1, 0, 0, 1, 1, 0, 0, 0, 0, 0, 0, 0};
 
 typedef std::unordered_map<std::string, int> RefIds;
+
+// A window-coverage request (coral_bam_decode_range_cov, coral_bamgpu_coverage): pysam count_coverage summed over the four
+// bases, for n sorted, pairwise disjoint half-open segments (tid, lo, hi) — the caller cuts its (possibly overlapping) windows
+// at every start and stop and sums the segments back.  A base counts when the record is on the segment's contig (with
+// filter_all: none of the flags 0x4 | 0x100 | 0x200 | 0x400), has SEQ, the base is an aligned (M / = / X) base inside the
+// segment, its SEQ code is A, C, G or T, and either threshold is 0 or the record has QUAL (first byte not 0xff) and
+// QUAL >= threshold there.
+struct CovTable {
+    std::vector<int32_t> tid, lo, hi;
+    int32_t threshold = 0;
+    bool filter_all = false;
+    size_t size() const { return tid.size(); }
+    // first segment at or after (t, pos) in (tid, hi) order: tid > t, or tid == t and hi > pos
+    size_t first(int32_t t, int64_t pos, size_t from = 0) const {
+        size_t a = from, b = tid.size();
+        while (a < b) {
+            const size_t m = (a + b) / 2;
+            if (tid[m] < t || (tid[m] == t && hi[m] <= pos)) a = m + 1; else b = m;
+        }
+        return a;
+    }
+};
+
+// Validate a request (sorted by (tid, lo), disjoint, lo <= hi, threshold 0..255) and copy it; false: `err` says why.
+inline bool make_cov_table(int32_t n_seg, const int32_t *tid, const int32_t *lo, const int32_t *hi, int32_t threshold,
+                           int32_t read_callback, CovTable &T, std::string &err) {
+    if (n_seg < 0 || (n_seg > 0 && (!tid || !lo || !hi))) { err = "coverage request: bad segment arrays"; return false; }
+    if (threshold < 0 || threshold > 255) { err = "coverage request: the quality threshold must be 0..255"; return false; }
+    if (read_callback != 0 && read_callback != 1) { err = "coverage request: read_callback must be 0 (nofilter) or 1 (all)"; return false; }
+    for (int32_t k = 0; k < n_seg; ++k) {
+        if (tid[k] < 0 || lo[k] < 0 || hi[k] < lo[k]) { err = "coverage request: bad segment"; return false; }
+        if (k > 0 && (tid[k] < tid[k - 1] || (tid[k] == tid[k - 1] && lo[k] < hi[k - 1]))) {
+            err = "coverage request: segments must be sorted by (tid, start) and disjoint";
+            return false;
+        }
+    }
+    T.tid.assign(tid, tid + n_seg);
+    T.lo.assign(lo, lo + n_seg);
+    T.hi.assign(hi, hi + n_seg);
+    T.threshold = threshold;
+    T.filter_all = read_callback == 1;
+    return true;
+}
+
+// Add one record's counted bases to counts[segment] (host pipeline; ops = the real CIGAR, CG tag already resolved).
+inline void count_record_coverage(const CovTable &T, int32_t refID, int64_t pos, uint32_t flag, uint32_t l_seq, const uint32_t *ops,
+                                  uint32_t n_ops, const uint8_t *seq, const uint8_t *qual, int64_t *counts) {
+    if (refID < 0 || l_seq == 0 || n_ops == 0 || T.size() == 0) return;
+    if (T.filter_all && (flag & 0x704u)) return;
+    const uint32_t thr = (uint32_t)T.threshold;
+    if (thr > 0 && qual[0] == 0xff) return;                // no QUAL: pysam's query_qualities is None
+    size_t s = T.first(refID, pos);
+    int64_t q = 0, r = pos;
+    for (uint32_t k = 0; k < n_ops; ++k) {
+        if (s >= T.size() || T.tid[s] != refID) return;     // no segment left on this contig
+        const uint32_t op = ops[k] & 15, len = ops[k] >> 4;
+        if (IS_ALN[op] && len) {
+            const int64_t r1 = r + len;
+            s = T.first(refID, r, s);
+            for (size_t t = s; t < T.size() && T.tid[t] == refID && T.lo[t] < r1; ++t) {
+                const int64_t a = std::max<int64_t>(r, T.lo[t]), b = std::min<int64_t>(r1, T.hi[t]);
+                int64_t c = 0;
+                for (int64_t x = a; x < b; ++x) {
+                    const uint64_t qi = (uint64_t)(q + (x - r));
+                    if (qi >= l_seq) break;
+                    const uint8_t code = (qi & 1) ? (seq[qi >> 1] & 15) : (seq[qi >> 1] >> 4);
+                    c += (code == 1 || code == 2 || code == 4 || code == 8) && qual[qi] >= thr;
+                }
+                counts[t] += c;
+            }
+        }
+        if (QRY_ADV[op]) q += len;
+        if (REF_ADV[op]) r += len;
+    }
+}
 
 // Tokenise one SA entry "rname,pos,strand,CIGAR,mapQ,NM" into 8 ints + nm.  The CIGAR must be
 // [c5 S] m M [x I | x D] [c3 S]; anything else containing S and M is marked c5 = -2 (the reference raises
@@ -161,7 +238,9 @@ inline bool all_acgt(const uint8_t *seq, uint32_t l_seq) {
 }
 
 // Decode one BAM record (p points at refID, i.e. after block_size) into the partial.
-inline bool decode_record(const uint8_t *p, uint32_t block_size, const RefIds &ref_id, Partial &o, std::string &err) {
+// With `cov`, the record's bases also go into o.cov (sized by the caller).
+inline bool decode_record(const uint8_t *p, uint32_t block_size, const RefIds &ref_id, Partial &o, std::string &err,
+                          const CovTable *cov = nullptr) {
     if (block_size < 32) { err = "record shorter than its fixed fields"; return false; }
     const int32_t refID = (int32_t)rd32(p), pos = (int32_t)rd32(p + 4);
     const uint32_t l_read_name = p[8], mapq = p[9];
@@ -233,6 +312,7 @@ inline bool decode_record(const uint8_t *p, uint32_t block_size, const RefIds &r
         qinf += QRY_ADV[v & 15] ? (v >> 4) : 0;
     }
     o.cigar_len.push_back((int64_t)padded);
+    if (cov) count_record_coverage(*cov, refID, pos, flag, l_seq, dst, n_cigar_op, seq, qual, o.cov.data());
     if ((flag & 4) || n_cigar_op == 0) rlen = 0;                 // htslib bam_endpos
     o.tid.push_back(refID);
     o.pos.push_back(pos);

@@ -18,6 +18,8 @@
 //                   codes, read name and SA text -> compact blobs for the host
 //   worker thread   per batch, a few hundred bytes per record: read names -> ids, SA text -> numeric rows; the rare
 //                   records with non-ACGT bases are gathered whole (k_bam_gather) and handled by the CPU pipeline's own routine.
+//   k_bam_cov_plan / k_bam_cov_count   only with a window-coverage request (coral_bamgpu_coverage): pysam count_coverage with a
+//                   base-quality threshold over the request's segments, read from the batch's SEQ / QUAL before the slot is reused.
 // Batches (64 MiB first, doubling up to 2.52 GiB inflated, coral_bamgpu_open) are double-buffered: while batch k is parsed, batch k + 1 is inflated
 // and k + 2 is read.
 // A record that straddles two batches is carried in front of the next batch's buffer.
@@ -978,6 +980,127 @@ __global__ __launch_bounds__(256) void k_bam_gather(const uint8_t *__restrict__ 
 }
 
 // ---------------------------------------------------------------------------------------------
+// K_cov: window coverage with a base-quality threshold (coral_bamgpu_coverage), counted while SEQ and QUAL are in HBM
+// ---------------------------------------------------------------------------------------------
+#define COV_SLICE 16384ll                // query bases per work item: a 1 Mb read is 62 waves' work, not one wave's
+
+struct CovSegs {                         // the request's sorted, disjoint segments (device arrays of the caller)
+    const int32_t *tid, *lo, *hi;
+    int n;
+};
+
+// first segment at or after (t, pos) in (tid, hi) order, searching [from, n); wave-uniform when its arguments are
+__device__ __forceinline__ int cov_first(const CovSegs &S, int32_t t, long long pos, int from) {
+    int a = from, b = S.n;
+    while (a < b) {
+        const int m = (a + b) >> 1;
+        if (S.tid[m] < t || (S.tid[m] == t && (long long)S.hi[m] <= pos)) a = m + 1; else b = m;
+    }
+    return a;
+}
+
+// one thread per record: how many work items (COV_SLICE query bases each) the record needs; 0 when it is filtered out, has no
+// SEQ, has no QUAL at a threshold above 0, or overlaps no segment.  Slot n_rec gets 0 (the scan's extra entry).
+__global__ __launch_bounds__(256) void k_bam_cov_plan(const uint8_t *__restrict__ buf, long long n_rec, MetaArrays M,
+                                                       const int32_t *__restrict__ end_in, CovSegs S, int threshold, int filter_all,
+                                                       long long *__restrict__ n_items) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > n_rec) return;
+    long long cnt = 0;
+    if (i < n_rec) {
+        const int32_t tid = M.tid[i], l_seq = M.l_seq[i], flag = M.flag[i];
+        if (tid >= 0 && l_seq > 0 && M.n_cigar[i] > 0 && !(filter_all && (flag & 0x704))) {
+            const uint8_t *qual = buf + M.seq_src[i] + ((long long)l_seq + 1) / 2;
+            if (threshold == 0 || qual[0] != 0xff) {
+                const int32_t pos = M.pos[i];
+                // end_in is htslib's bam_endpos: pos + 1 for an unmapped record, whose CIGAR is walked all the same
+                const long long end = (flag & 4) ? (1ll << 40) : (long long)end_in[i];
+                const int s = cov_first(S, tid, pos, 0);
+                if (s < S.n && S.tid[s] == tid && (long long)S.lo[s] < end) cnt = ((long long)l_seq + COV_SLICE - 1) / COV_SLICE;
+            }
+        }
+    }
+    n_items[i] = cnt;
+}
+
+// one wave per work item (grid-stride): the query bases [k * COV_SLICE, (k + 1) * COV_SLICE) of record i.  The wave walks the
+// CIGAR 64 ops at a time (prefix sums of the query / reference advance), and for every aligned op that meets its query range
+// the lanes stride over the op's bases inside each segment, testing the SEQ code and QUAL.  Per-lane counts are reduced in
+// the wave and added with ONE 64-bit atomic per (work item, segment): segments are met in increasing order.
+__global__ __launch_bounds__(256) void k_bam_cov_count(const uint8_t *__restrict__ buf, long long n_rec, MetaArrays M, CovSegs S,
+                                                        int threshold, const long long *__restrict__ item_off,
+                                                        unsigned long long *__restrict__ counts) {
+    const int lane = threadIdx.x & 63;
+    const long long n_waves = ((long long)gridDim.x * blockDim.x) >> 6;
+    const long long total = item_off[n_rec];
+    const uint32_t thr = (uint32_t)threshold;
+    for (long long w = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6; w < total; w += n_waves) {
+        long long a = 0, b = n_rec;                                   // the record: the last i with item_off[i] <= w
+        while (b - a > 1) {
+            const long long m = (a + b) >> 1;
+            if (item_off[m] <= w) a = m; else b = m;
+        }
+        const long long i = a;
+        const int32_t tid = M.tid[i], l_seq = M.l_seq[i], pos = M.pos[i];
+        const int n_ops = M.n_cigar[i];
+        const long long q_lo = (w - item_off[i]) * COV_SLICE, q_hi = min((long long)l_seq, q_lo + COV_SLICE);
+        const uint8_t *ops = buf + M.cig_src[i];
+        const uint8_t *seq = buf + M.seq_src[i];
+        const uint8_t *qual = seq + ((long long)l_seq + 1) / 2;
+        int s = cov_first(S, tid, pos, 0);
+        int cur = -1;                                                  // the segment the lanes' counts belong to
+        uint32_t acc = 0;
+        auto flush = [&]() {
+            long long sum = (long long)acc;
+            for (int d = 32; d > 0; d >>= 1) sum += __shfl_xor(sum, d);
+            if (cur >= 0 && lane == 0 && sum) atomicAdd(counts + cur, (unsigned long long)sum);
+            acc = 0;
+        };
+        long long q_base = 0, r_base = pos;
+        for (int c = 0; c < n_ops && q_base < q_hi; c += WAVE) {
+            if (s >= S.n || S.tid[s] != tid) break;                   // no segment left on this contig
+            const int kk = c + lane;
+            const uint32_t wd = kk < n_ops ? ld32(ops + 4ll * kk) : 15u;
+            const uint32_t op = wd & 15u;
+            const long long len = (long long)(wd >> 4);
+            const long long qa = ((0x193u >> op) & 1u) ? len : 0;     // M I S = X advance the query
+            const long long ra = ((0x18Du >> op) & 1u) ? len : 0;     // M D N = X advance the reference
+            long long qs = qa, rs = ra;
+            for (int d = 1; d < WAVE; d <<= 1) {
+                const long long tq = __shfl_up(qs, d), tr = __shfl_up(rs, d);
+                if (lane >= d) { qs += tq; rs += tr; }
+            }
+            const long long q_op = q_base + qs - qa, r_op = r_base + rs - ra;
+            const bool cand = ((0x181u >> op) & 1u) && len > 0 && q_op < q_hi && q_op + len > q_lo;     // M = X meeting the item
+            unsigned long long m = __ballot(cand);
+            while (m) {
+                const int j = __builtin_ctzll(m);
+                m &= m - 1;
+                const long long oq = __shfl(q_op, j), orf = __shfl(r_op, j), ol = __shfl(len, j);
+                const long long aq = max(oq, q_lo), bq = min(oq + ol, q_hi);
+                const long long r0 = orf + (aq - oq), r1 = orf + (bq - oq);
+                // r0 only grows: the cursor is usually still right (this op ends inside its segment) or one further
+                if (s < S.n && S.tid[s] == tid && (long long)S.hi[s] <= r0)
+                    s = (s + 1 < S.n && S.tid[s + 1] == tid && (long long)S.hi[s + 1] > r0) ? s + 1 : cov_first(S, tid, r0, s + 1);
+                for (int t = s; t < S.n && S.tid[t] == tid && (long long)S.lo[t] < r1; ++t) {
+                    if (t != cur) { flush(); cur = t; }
+                    const long long xa = max(r0, (long long)S.lo[t]), xb = min(r1, (long long)S.hi[t]);
+                    for (long long x = xa + lane; x < xb; x += WAVE) {
+                        const long long qi = aq + (x - r0);                    // < bq <= q_hi <= l_seq
+                        const uint8_t byte = seq[qi >> 1];
+                        const uint32_t code = (qi & 1) ? (byte & 15u) : (uint32_t)(byte >> 4);
+                        acc += (code != 0 && (code & (code - 1)) == 0 && qual[qi] >= thr) ? 1u : 0u;
+                    }
+                }
+            }
+            q_base += __shfl(qs, WAVE - 1);
+            r_base += __shfl(rs, WAVE - 1);
+        }
+        flush();
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
 inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -1062,6 +1185,11 @@ struct GpuDecoder {
     bool worker_stop = false, worker_busy = false;
     std::string worker_error;
     long long cur_carry_pos = 0;
+    // window-coverage request (coral_bamgpu_coverage): segments and counters in the caller's device memory
+    CovSegs cov{nullptr, nullptr, nullptr, 0};
+    int cov_threshold = 0, cov_filter_all = 0;
+    unsigned long long *cov_counts = nullptr;
+    bool cov_set = false;
     // statistics
     double t_open = 0, seconds = 0, host_seconds = 0;
     int64_t fixups = 0, n_batches = 0, na_records = 0;
@@ -1738,6 +1866,23 @@ extern "C" int coral_bamgpu_emit(void *handle, uint32_t *cigar_dst, int64_t *cig
     } else if (hipStreamSynchronize(stream) != hipSuccess) {
         return fail(CORAL_ERR_HIP, "hipStreamSynchronize failed");
     }
+    if (n > 0 && G->cov_set && G->cov.n > 0) {
+        // window coverage of the batch's records, queued before ev_parsed so that the slot is not inflated into while it reads.
+        // The per-record item counts and their offsets use the name / SA length arrays: k_bam_emit has finished with them
+        // (the host copies above synchronised the stream) and the next batch's k_bam_meta comes behind on the same stream.
+        long long *n_items = G->M.name_len, *item_off = G->M.sa_len;
+        hipLaunchKernelGGL(k_bam_cov_plan, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, stream, buf, n, G->M, G->d_end, G->cov,
+                           G->cov_threshold, G->cov_filter_all, n_items);
+        size_t tmp = G->scan_tmp_bytes;
+        if (hipcub::DeviceScan::ExclusiveSum(G->d_scan_tmp, tmp, n_items, item_off, (int)(n + 1), stream) != hipSuccess)
+            return fail(CORAL_ERR_HIP, "scan of the coverage work items failed");
+        // at most one item per record plus one per COV_SLICE bases of SEQ in the batch; 4 waves per workgroup, grid-stride beyond
+        const long long items = n + ((long long)CARRY_CAP + (long long)G->cur.infl_bytes) / COV_SLICE + 1;
+        const unsigned blocks = (unsigned)std::min<long long>((items + 3) / 4, 8192);
+        hipLaunchKernelGGL(k_bam_cov_count, dim3(blocks), dim3(256), 0, stream, buf, n, G->M, G->cov, G->cov_threshold, item_off, G->cov_counts);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return fail(CORAL_ERR_HIP, std::string("window coverage launch failed: ") + hipGetErrorString(e));
+    }
     // this buffer may be inflated into again (batch k + 2) once everything above has run
     if (hipEventRecord(G->ev_parsed[slot], stream) != hipSuccess) return fail(CORAL_ERR_HIP, "hipEventRecord failed");
     {
@@ -1748,6 +1893,50 @@ extern "C" int coral_bamgpu_emit(void *handle, uint32_t *cigar_dst, int64_t *cig
     G->have_cur = false;
     ++G->k;
     if (G->finished) D.seconds = G->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - G->t_start).count();
+    return CORAL_OK;
+}
+
+// Window-coverage request: after open, before start.  seg_* are device arrays of n_seg sorted, disjoint segments; counts is a
+// device array of n_seg int64 the caller has zeroed; both must outlive the decode.  Checked here on a host copy.
+extern "C" int coral_bamgpu_coverage(void *handle, int32_t n_seg, const int32_t *seg_tid, const int32_t *seg_start, const int32_t *seg_end,
+                                     int32_t quality_threshold, int32_t read_callback, int64_t *counts) {
+    GpuDecoder *G = (GpuDecoder *)handle;
+    if (!G || n_seg < 0 || (n_seg > 0 && !counts)) return CORAL_ERR_ARG;
+    if (G->feeder.joinable() || G->cov_set) { set_error("coral_bamgpu_coverage: call it once, after open and before start"); return CORAL_ERR_ARG; }
+    std::vector<int32_t> h((size_t)n_seg * 3);
+    if (n_seg > 0) {
+        if (!seg_tid || !seg_start || !seg_end) return CORAL_ERR_ARG;
+        if (hipMemcpy(h.data(), seg_tid, (size_t)n_seg * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(h.data() + n_seg, seg_start, (size_t)n_seg * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(h.data() + 2 * (size_t)n_seg, seg_end, (size_t)n_seg * 4, hipMemcpyDeviceToHost) != hipSuccess) {
+            set_error("coral_bamgpu_coverage: cannot read the segment table");
+            return CORAL_ERR_HIP;
+        }
+    }
+    CovTable T;
+    std::string err;
+    if (!make_cov_table(n_seg, h.data(), h.data() + n_seg, h.data() + 2 * (size_t)n_seg, quality_threshold, read_callback, T, err)) {
+        set_error(err);
+        return CORAL_ERR_ARG;
+    }
+    G->cov = CovSegs{seg_tid, seg_start, seg_end, (int)n_seg};
+    G->cov_threshold = quality_threshold;
+    G->cov_filter_all = read_callback;
+    G->cov_counts = (unsigned long long *)counts;
+    G->cov_set = true;
+    return CORAL_OK;
+}
+
+// The request's counts, once every batch has been emitted: waits for `stream` and copies the n_seg device counters to `counts` (host).
+extern "C" int coral_bamgpu_coverage_result(void *handle, int32_t n_seg, int64_t *counts, void *stream_) {
+    GpuDecoder *G = (GpuDecoder *)handle;
+    if (!G || !G->cov_set || n_seg != G->cov.n || (n_seg > 0 && !counts)) return CORAL_ERR_ARG;
+    if (!G->finished || G->have_cur) { set_error("coral_bamgpu_coverage_result: the decode is not finished"); return CORAL_ERR_ARG; }
+    if (hipStreamSynchronize((hipStream_t)stream_) != hipSuccess ||
+        (n_seg > 0 && hipMemcpy(counts, G->cov_counts, (size_t)n_seg * 8, hipMemcpyDeviceToHost) != hipSuccess)) {
+        set_error("coral_bamgpu_coverage_result: copy of the counts failed");
+        return CORAL_ERR_HIP;
+    }
     return CORAL_OK;
 }
 

@@ -6,6 +6,10 @@ The reference draws, for every amplified interval of a ``*_graph.txt``, one grey
 reads.  Here all windows of a plot are ONE ``coral_segment_coverage`` launch over the HBM-resident records (the kernel of
 the graph build's A2 / A10 steps: per-record sums from the fused CIGAR scan, CIGAR re-walk only for records straddling a
 window border).  Only the numbers are produced; drawing stays with the reference's matplotlib code.
+
+For a base-quality threshold above 0 (the reference's ``--min_mapq``, which pysam applies per base) the resident records are
+not enough — they hold no QUAL — so ``coverage_track_bam`` / ``CoverageTable`` count the windows while the BAM file is
+decoded (``bam.window_coverage``).
 """
 from __future__ import annotations
 
@@ -88,3 +92,68 @@ def coverage_track(dr, intervals, plot_bounds=None, scan=None):
             out.append((c, s, s + w, int(n_bases[k])))
             k += 1
     return out
+
+
+def plot_windows(intervals, plot_bounds=None):
+    """(chrom, start, stop) of every rectangle of the coverage track, in drawing order."""
+    return [(c, s, s + w) for c, w, st in track_windows(intervals, plot_bounds) for s in st.tolist()]
+
+
+def coverage_track_bam(bam_path, intervals, plot_bounds=None, quality_threshold=0, read_callback="nofilter", device="cuda:0"):
+    """``coverage_track`` straight from a BAM file, for any base-quality threshold (what the reference passes as ``min_mapq``,
+    plot:935) and either read callback: [(chrom, start, stop, bases)], counted while the file is decoded
+    (``bam.window_coverage``).  At threshold 0 with 'nofilter' it equals ``coverage_track`` on the file's records."""
+    from . import bam
+    windows = plot_windows(intervals, plot_bounds)
+    if not windows:
+        return []
+    counts = bam.window_coverage(bam_path, windows, quality_threshold, read_callback, device=device)
+    return [(c, s, e, int(n)) for (c, s, e), n in zip(windows, counts)]
+
+
+def parse_region(region: Optional[str]):
+    """'chr:start-end' -> (chr, start, end) plot bounds, None -> None."""
+    if not region:
+        return None
+    chrom, span = region.split(":")
+    a, b = span.split("-")
+    return chrom, int(a), int(b)
+
+
+class CoverageTable:
+    """A stand-in for the pysam handle the reference's plot code draws the coverage track from (``graph_vis.lr_bamfh``,
+    plot:399-409): every window of one plot is counted in ONE decode of the BAM file, and ``count_coverage`` answers those
+    windows from the table.  Only what was precomputed can be answered: another window, threshold or read callback raises
+    KeyError."""
+
+    def __init__(self, windows, counts, quality_threshold=0, read_callback="nofilter"):
+        from . import bam
+        self.quality_threshold = bam.quality_threshold_value(quality_threshold)
+        self.read_callback = read_callback
+        self._counts = {(c, int(s), int(e)): int(n) for (c, s, e), n in zip(windows, counts)}
+
+    @classmethod
+    def from_bam(cls, bam_path, graph_fn, region=None, min_mapq=0, read_callback="nofilter", device="cuda:0"):
+        """The windows of the plot of ``graph_fn`` (optionally restricted to ``region`` 'chr:start-end'), counted with
+        ``quality_threshold=min_mapq`` as the reference does (plot:935)."""
+        track = coverage_track_bam(bam_path, parse_graph_intervals(graph_fn), parse_region(region), min_mapq, read_callback, device)
+        return cls([(c, s, e) for c, s, e, _ in track], [n for _, _, _, n in track], min_mapq, read_callback)
+
+    def __len__(self):
+        return len(self._counts)
+
+    def count_coverage(self, contig=None, start=None, stop=None, region=None, quality_threshold=15, read_callback="all",
+                       reference=None, end=None):
+        """pysam's signature; answers ([bases], [0], [0], [0]) — the reference only ever sums the four arrays."""
+        from . import bam
+        contig = reference if contig is None else contig
+        stop = end if stop is None else stop
+        if region is not None or contig is None or start is None or stop is None:
+            raise KeyError("CoverageTable answers (contig, start, stop) windows only")
+        if bam.quality_threshold_value(quality_threshold) != self.quality_threshold or read_callback != self.read_callback:
+            raise KeyError("CoverageTable was built for quality_threshold=%d, read_callback=%r"
+                           % (self.quality_threshold, self.read_callback))
+        return ([self._counts[(contig, int(start), int(stop))]], [0], [0], [0])
+
+    def close(self):
+        self._counts = {}

@@ -383,6 +383,20 @@ int coral_bam_write(const char *path, int64_t n_rec, const int32_t *tid, const i
                     const int32_t *nonacgt_pos, const char *const *names, int32_t n_ref, const char *const *ref_names,
                     const int32_t *ref_lens, uint32_t seed, int32_t level, int32_t n_threads);
 const char *coral_bam_last_error(void);
+/* Window coverage counted during the decode — replaces, for the coverage track of `plot`, the per-window
+ * lr_bamfh.count_coverage(chrom, w, w + window, quality_threshold=..., read_callback='nofilter') calls
+ * (/root/reference/src/plot_amplicons.py:399-400, :408-409; threshold from :935): pysam count_coverage summed over its four
+ * arrays, for any base-quality threshold and both read callbacks.  The caller cuts its windows into n_seg sorted (by tid,
+ * start), pairwise disjoint half-open segments (seg_tid, seg_start, seg_end) and sums the segments back into windows.  A
+ * base counts when its record is on the segment's contig (read_callback 1 = 'all': none of the flags 0x704), has SEQ, it is
+ * an aligned base of an M / = / X op (the real CIGAR: CG:B,I for the placeholder) inside the segment, its SEQ code is A, C,
+ * G or T, and quality_threshold (0..255) is 0 or the record has QUAL (first byte not 0xff) with QUAL >= quality_threshold
+ * there.  `decode_range_cov` is coral_bam_decode_range with such a request (each parse task keeps partial counts, added up
+ * in file order); `coverage_result` copies the n_seg int64 counts of the handle. */
+int coral_bam_decode_range_cov(const char *path, int32_t n_threads, int32_t rank, int32_t world, int32_t n_seg,
+                               const int32_t *seg_tid, const int32_t *seg_start, const int32_t *seg_end,
+                               int32_t quality_threshold, int32_t read_callback, void **handle);
+int coral_bam_coverage_result(void *handle, int32_t n_seg, int64_t *counts);
 
 /* ------------------------------------------------------------------------------------------------
  * coral_bamgpu_* — the same decode with the inflate and the record parsing ON THE GPU: the host reads the file and sends
@@ -405,6 +419,12 @@ const char *coral_bam_last_error(void);
  *   stats  stats = batches, segments whose speculative record start was replaced by the exact walk, records fetched
  *          whole for the non-ACGT list, batch capacity; seconds = total wall time, host-side field handling, file reads,
  *          set-up of pinned buffers and streams, time the caller waited for the file feeder, ... for the GPU
+ *   coverage         the window-coverage request of coral_bam_decode_range_cov on the GPU (same segments, same rules;
+ *          /root/reference/src/plot_amplicons.py:399-400, :408-409): after open, before start; seg_* are device arrays,
+ *          `counts` n_seg device int64 the caller zeroes, both live until the decode ends.  Per batch, k_bam_cov_plan +
+ *          k_bam_cov_count read the batch's inflated SEQ / QUAL before the slot is reused (one wave per 16 384 query bases
+ *          of a record, one 64-bit atomic per work item and segment).  Without a request no kernel is added.
+ *   coverage_result  after the last batch: waits for `stream`, copies the n_seg counts to host memory
  * coral_bgzf_inflate: one inflate launch over caller-provided device buffers — desc = n_blocks x {src_off, src_len,
  * dst_off, isize} uint32 (raw DEFLATE streams in `comp`, which must be readable 4096 bytes beyond the last stream);
  * status[b] = 0 or the decoder's error code.
@@ -416,6 +436,9 @@ int coral_bamgpu_next(void *handle, int64_t out[4], void *stream);
 int coral_bamgpu_emit(void *handle, uint32_t *cigar_dst, int64_t *cigar_off_dst, void *stream);
 int coral_bamgpu_host(void *handle, void **decoded);
 int coral_bamgpu_stats(void *handle, int64_t stats[4], double seconds[6]);
+int coral_bamgpu_coverage(void *handle, int32_t n_seg, const int32_t *seg_tid, const int32_t *seg_start, const int32_t *seg_end,
+                          int32_t quality_threshold, int32_t read_callback, int64_t *counts);
+int coral_bamgpu_coverage_result(void *handle, int32_t n_seg, int64_t *counts, void *stream);
 int coral_bamgpu_close(void *handle);
 int coral_bgzf_inflate(const uint8_t *comp, const uint32_t *desc, int32_t n_blocks, uint8_t *out, int32_t *status,
                        void *stream);
