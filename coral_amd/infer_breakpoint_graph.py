@@ -20,6 +20,8 @@ There is no CPU fallback: importing works without a GPU, running needs libcoral_
 """
 from __future__ import annotations
 
+import functools
+import itertools
 import logging
 import math
 import sys
@@ -38,7 +40,7 @@ from .bpcluster import call_breakpoints
 from .breakpoint_graph import BreakpointGraph, compute_cn_lr, output_breakpoint_graph_lr, output_breakpoint_info_lr
 from .chimeric import Candidates, ChimericTable, PairSearch, build_chimeric_table
 from .global_names import chr_idx
-from .lazysets import ReadNameSet, ReadSupportSet
+from .lazysets import LazyDict, ReadNameSet, ReadSupportSet
 
 _ORI = "+-"
 _VERIFY_SET_ORDER = os.environ.get("CORAL_VERIFY_SET_ORDER") == "1"     # tests: cross-check the set replay against real sets
@@ -110,144 +112,59 @@ def rows_by_interval(r_tid, r_pos, r_end, intervals) -> np.ndarray:
     return np.concatenate(parts)
 
 
-class _ChimericAlignments(dict):
+class _ChimericAlignments(LazyDict):
     """``name -> (qint, rint(+cniset), qual, nm)`` exactly as the reference stores it (cp:269, ibg:200-210), over the
-    ChimericTable: the keys (read names, in the reference's insertion order) are created the first time anything but the
-    SIZE is asked for, a value the first time that entry is read.  Every access path of ``dict`` is overridden — including
-    ``__iter__``, so that ``dict(x)`` / ``x.copy()`` / ``{**x}`` take the generic route through ``keys()`` and
-    ``__getitem__`` instead of copying the raw table."""
+    ChimericTable: the keys are the read names in the reference's insertion order, a value is built the first time that
+    entry is read."""
 
     def __init__(self, owner, name_ids, keep=None):
-        super().__init__()
         self._owner = weakref.proxy(owner)      # no reference cycle: the result is freed by reference counting, not by the GC
         self._name_ids = name_ids
         self._keep = keep                       # owner of the memory `name_ids` is a view of
-        self._names_ = None                     # read names in dict order
-        self._index_ = None
-        self._filled = False
-        self._n = len(name_ids)
-        self._made = []                         # keys holding a materialised value
+        self._made = {}                         # key -> the value _make built for it
 
-    # -- lazy parts ---------------------------------------------------------------------------------
-    @property
-    def _names(self):
-        if self._names_ is None:
-            self._names_ = self._owner._names_of(self._name_ids)
-        return self._names_
+    @functools.cached_property
+    def _names(self):                           # read names in dict order
+        return self._owner._names_of(self._name_ids)
 
-    def _fill(self):
-        if not self._filled:
-            self._filled = True
-            dict.update(self, dict.fromkeys(self._names))
-
-    @property
+    @functools.cached_property
     def _index(self):
-        if self._index_ is None:
-            self._index_ = {nm: k for k, nm in enumerate(self._names)}
-        return self._index_
+        return {nm: k for k, nm in enumerate(self._names)}
+
+    def _count(self):
+        return len(self._name_ids)
+
+    def _load(self):
+        return zip(self._names, itertools.repeat(self._PENDING))
 
     def _make(self, key):
         o = self._owner
         T = o._chim
         r = self._index[key]
         if T.failed[r]:
-            return ([], [], [])
-        a, b = int(T.off[r]), int(T.off[r + 1])
-        chroms = o.rec.header_chroms
-        qint = [[int(T.qs[k]), int(T.qe[k])] for k in range(a, b)]
-        rint = []
-        for k in range(a, b):
-            seg = [chroms[T.tid[k]], int(T.ra[k]), int(T.rb[k]), _ORI[T.strand[k]]]
-            if o._hashed:
-                seg.append(o._cniset(k))
-            rint.append(seg)
-        qual = [int(T.mapq[k]) for k in range(a, b)]
-        nm = [float(T.nm[k]) for k in range(a, b)]
-        return (qint, rint, qual, nm)
-
-    # -- dict protocol --------------------------------------------------------------------------------
-    def __len__(self):
-        return dict.__len__(self) if self._filled else self._n
-
-    def __contains__(self, key):
-        self._fill()
-        return dict.__contains__(self, key)
-
-    def __iter__(self):
-        self._fill()
-        return dict.__iter__(self)
-
-    def keys(self):
-        self._fill()
-        return dict.keys(self)
-
-    def __getitem__(self, key):
-        self._fill()
-        v = dict.__getitem__(self, key)
-        if v is None:
-            v = self._make(key)
-            dict.__setitem__(self, key, v)
-            self._made.append(key)
+            v = ([], [], [])
+        else:
+            a, b = int(T.off[r]), int(T.off[r + 1])
+            chroms = o.rec.header_chroms
+            qint = [[int(T.qs[k]), int(T.qe[k])] for k in range(a, b)]
+            rint = []
+            for k in range(a, b):
+                seg = [chroms[T.tid[k]], int(T.ra[k]), int(T.rb[k]), _ORI[T.strand[k]]]
+                if o._hashed:
+                    seg.append(o._cniset(k))
+                rint.append(seg)
+            qual = [int(T.mapq[k]) for k in range(a, b)]
+            nm = [float(T.nm[k]) for k in range(a, b)]
+            v = (qint, rint, qual, nm)
+        self._made[key] = v
         return v
 
-    def get(self, key, default=None):
-        return self[key] if key in self else default
-
-    def items(self):
-        return [(k, self[k]) for k in self.keys()]
-
-    def values(self):
-        return [self[k] for k in self.keys()]
-
-    def __setitem__(self, key, value):
-        self._fill()
-        dict.__setitem__(self, key, value)
-
-    def __delitem__(self, key):
-        self._fill()
-        dict.__delitem__(self, key)
-
-    def pop(self, key, *default):
-        self._fill()
-        if dict.__contains__(self, key):
-            v = self[key]
-            dict.__delitem__(self, key)
-            return v
-        if default:
-            return default[0]
-        raise KeyError(key)
-
-    def setdefault(self, key, default=None):
-        if key not in self:
-            self[key] = default
-        return self[key]
-
-    def update(self, *a, **kw):
-        self._fill()
-        dict.update(self, *a, **kw)
-
-    def copy(self):
-        return dict(self.items())
-
-    def __eq__(self, other):
-        return dict(self.items()) == other
-
-    def __ne__(self, other):
-        return not self.__eq__(other)
-
-    __hash__ = None
-
-    def __repr__(self):
-        return repr(dict(self.items()))
-
-    def __reduce__(self):
-        return (dict, (self.items(),))
-
     def invalidate(self):
-        for k in self._made:
-            if dict.__contains__(self, k):
-                dict.__setitem__(self, k, None)
-        self._made = []
+        """Build again the values made so far, so that they carry the CN-segment sets hash_alignment_to_seg adds (ibg:200-210)."""
+        made, self._made = self._made, {}
+        for key, v in made.items():
+            if dict.get(self, key) is v:        # not replaced or removed since
+                dict.__setitem__(self, key, self._make(key))
 
 
 class _RecordsFile:
@@ -1402,174 +1319,44 @@ class bam_to_breakpoint_nanopore():
         self.lr_bamfh.close()
 
 
-class _LazyIndelAlignments(dict):
+class _LazyIndelAlignments(LazyDict):
     """``large_indel_alignments``: read name -> list of ``[chr, next block start, previous block end, first block start, last
-    block end, mapq]`` (ibg:746-762), names in first-appearance order.  Built from arrays on first use; only ``len()`` is
-    answered without building."""
+    block end, mapq]`` (ibg:746-762), names in first-appearance order, built from arrays on first use."""
 
     def __init__(self, owner, group_name_ids, bounds, tid, nxt, prv, b0, b1, mapq):
-        super().__init__()
         self._src = (weakref.proxy(owner), group_name_ids, bounds, tid, nxt, prv, b0, b1, mapq)
-        self._n = len(group_name_ids)
 
-    def _fill(self):
-        if self._src is not None:
-            o, gids, bounds, tid, nxt, prv, b0, b1, mapq = self._src
-            self._src = None
-            chroms = o.rec.header_chroms
-            rows = list(map(list, zip([chroms[t] for t in tid.tolist()], nxt.tolist(), prv.tolist(), b0.tolist(), b1.tolist(),
-                                      mapq.tolist())))
-            names = o._names_of(gids)
-            bnd = bounds.tolist()
-            dict.update(self, {nm: rows[bnd[k]:bnd[k + 1]] for k, nm in enumerate(names)})
+    def _count(self):
+        return len(self._src[1])
 
-    def __len__(self):
-        return self._n if self._src is not None else dict.__len__(self)
-
-    def __bool__(self):
-        return len(self) > 0
-
-    def __contains__(self, k):
-        self._fill()
-        return dict.__contains__(self, k)
-
-    def __getitem__(self, k):
-        self._fill()
-        return dict.__getitem__(self, k)
-
-    def get(self, k, default=None):
-        self._fill()
-        return dict.get(self, k, default)
-
-    def __iter__(self):
-        self._fill()
-        return dict.__iter__(self)
-
-    def keys(self):
-        self._fill()
-        return dict.keys(self)
-
-    def items(self):
-        self._fill()
-        return dict.items(self)
-
-    def values(self):
-        self._fill()
-        return dict.values(self)
-
-    def __setitem__(self, k, v):
-        self._fill()
-        dict.__setitem__(self, k, v)
-
-    def __delitem__(self, k):
-        self._fill()
-        dict.__delitem__(self, k)
-
-    def setdefault(self, k, default=None):
-        self._fill()
-        return dict.setdefault(self, k, default)
-
-    def pop(self, k, *default):
-        self._fill()
-        return dict.pop(self, k, *default)
-
-    def update(self, *a, **kw):
-        self._fill()
-        dict.update(self, *a, **kw)
-
-    def copy(self):
-        self._fill()
-        return dict(self)
-
-    def __eq__(self, other):
-        self._fill()
-        return dict.__eq__(self, other)
-
-    def __ne__(self, other):
-        return not self.__eq__(other)
-
-    __hash__ = None
-
-    def __repr__(self):
-        self._fill()
-        return dict.__repr__(self)
-
-    def __reduce__(self):
-        self._fill()
-        return (dict, (list(dict.items(self)),))
+    def _load(self):
+        o, gids, bounds, tid, nxt, prv, b0, b1, mapq = self._src
+        self._src = None
+        chroms = o.rec.header_chroms
+        rows = list(map(list, zip([chroms[t] for t in tid.tolist()], nxt.tolist(), prv.tolist(), b0.tolist(), b1.tolist(),
+                                  mapq.tolist())))
+        names = o._names_of(gids)
+        bnd = bounds.tolist()
+        return ((nm, rows[bnd[k]:bnd[k + 1]]) for k, nm in enumerate(names))
 
 
-class _LazyReadLength(dict):
+class _LazyReadLength(LazyDict):
     """``read name -> query length`` for reads with a primary record (ibg:141-143); built from the chimeric table's per-name
     array — which stays on the device until then — on first use."""
 
     def __init__(self, names, table):
-        super().__init__()
-        self._names, self._table, self._done, self._has = names, table, False, None
+        self._names, self._table, self._has = names, table, None
 
-    def _which(self):
+    def _count(self):
         if self._has is None:
             self._has = np.nonzero(self._table.read_length >= 0)[0]
-        return self._has
+        return len(self._has)
 
-    def _fill(self):
-        if not self._done:
-            self._done = True
-            has = self._which()
-            dict.update(self, zip(self._names.take(has), self._table.read_length[has].tolist()))
-            self._table = None
-
-    def __len__(self):
-        return dict.__len__(self) if self._done else len(self._which())
-
-    def __contains__(self, k):
-        self._fill()
-        return dict.__contains__(self, k)
-
-    def __getitem__(self, k):
-        self._fill()
-        return dict.__getitem__(self, k)
-
-    def get(self, k, default=None):
-        self._fill()
-        return dict.get(self, k, default)
-
-    def __iter__(self):
-        self._fill()
-        return dict.__iter__(self)
-
-    def keys(self):
-        self._fill()
-        return dict.keys(self)
-
-    def values(self):
-        self._fill()
-        return dict.values(self)
-
-    def items(self):
-        self._fill()
-        return dict.items(self)
-
-    def __eq__(self, other):
-        self._fill()
-        return dict.__eq__(self, other)
-
-    def __ne__(self, other):
-        return not self.__eq__(other)
-
-    __hash__ = None
-
-    def __repr__(self):
-        self._fill()
-        return dict.__repr__(self)
-
-    def copy(self):
-        self._fill()
-        return dict(self)
-
-    def __reduce__(self):
-        self._fill()
-        return (dict, (list(dict.items(self)),))
+    def _load(self):
+        self._count()
+        has, read_length = self._has, self._table.read_length
+        self._table = self._has = None
+        return zip(self._names.take(has), read_length[has].tolist())
 
 
 class _SegIndexView:

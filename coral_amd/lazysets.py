@@ -1,4 +1,4 @@
-"""Set-valued fields of the object surface, kept as index arrays until somebody looks inside.
+"""Lazy containers of the object surface, kept as index arrays until somebody looks inside.
 
 The reference stores, per breakpoint, the ``set`` of supporting ``(read name, i, j)`` tuples (``new_bp_list[k][-1]`` =
 ``discordant_edges[k][10]``, /root/reference/src/infer_breakpoint_graph.py:330-335, :1000) and, per concordant edge, the
@@ -15,6 +15,10 @@ materialised set is the reference's — the first time an element is asked for. 
 ``set``: CPython's C-level fast paths (``set(x)``, ``s.update(x)``, ``s |= x``) read a subclass's hash table directly and
 would silently see an empty one, whereas a non-``set`` iterable always goes through ``__iter__``.  ``isinstance(x, set)`` is
 therefore False (``isinstance(x, collections.abc.Set)`` is True); ``x.as_set()`` returns the plain ``set``.
+
+``LazyDict`` does the same for the dict-valued fields (``chimeric_alignments``, ``large_indel_alignments``, ``read_length``).
+Those must stay ``dict`` instances, so it IS a subclass of ``dict``, and it overrides every method of ``dict``: each one loads the
+table first and then does what ``dict`` does, so no method can act on the still-empty table underneath.
 """
 from __future__ import annotations
 
@@ -202,3 +206,121 @@ class ReadNameSet(_LazySet):
         if self._set is not None:
             return None
         return np.union1d(self._ids(self._left), self._ids(self._right))
+
+
+class LazyDict(dict):
+    """A ``dict`` whose entries are loaded from arrays the first time anything but its size is asked for.
+
+    A subclass supplies ``_count()``, the size without loading, and ``_load()``, which returns the ``(key, value)`` pairs in
+    the reference's insertion order and drops its sources.  A subclass that builds values one at a time loads ``_PENDING``
+    as the value and supplies ``_make(key)``, which builds it; every path that hands out a value builds the pending ones it
+    would expose first.  After the load the object is its own table, so order and contents after any mutation are those
+    of a plain ``dict`` that was loaded first.  ``copy``, ``|``, ``fromkeys`` and pickling give plain ``dict``s.
+    """
+    _PENDING = object()                 # a value not built yet (``None`` is an ordinary value)
+    _loaded = False
+    _make = None
+
+    def _load_once(self):
+        if not self._loaded:
+            dict.update(self, self._load())
+            self._loaded = True
+        return self
+
+    def _build_value(self, key):
+        """Load, and build the value at ``key`` if it is pending."""
+        if dict.get(self._load_once(), key) is self._PENDING:
+            dict.__setitem__(self, key, self._make(key))
+        return self
+
+    def _build_all(self):
+        """Load, and build every pending value."""
+        self._load_once()
+        if self._make is not None:
+            for key in [k for k, v in dict.items(self) if v is self._PENDING]:
+                dict.__setitem__(self, key, self._make(key))
+        return self
+
+    def __len__(self):
+        return dict.__len__(self) if self._loaded else self._count()
+
+    # __iter__ must stay overridden: CPython's dict(x), {**x} and d.update(x) copy a dict subclass's table directly unless
+    # the type overrides __iter__; with it overridden they go through keys() and __getitem__ like any other mapping.
+    def __iter__(self):
+        return dict.__iter__(self._load_once())
+
+    def __reversed__(self):
+        return dict.__reversed__(self._load_once())
+
+    def __contains__(self, key):
+        return dict.__contains__(self._load_once(), key)
+
+    def keys(self):
+        return dict.keys(self._load_once())
+
+    def values(self):
+        return dict.values(self._build_all())
+
+    def items(self):
+        return dict.items(self._build_all())
+
+    def __getitem__(self, key):
+        return dict.__getitem__(self._build_value(key), key)
+
+    def get(self, key, default=None):
+        return dict.get(self._build_value(key), key, default)
+
+    def setdefault(self, key, default=None):
+        return dict.setdefault(self._build_value(key), key, default)
+
+    def pop(self, key, *default):
+        return dict.pop(self._build_value(key), key, *default)
+
+    def popitem(self):
+        last = next(reversed(self), None)        # the entry popitem() removes; None (nothing to build) when empty
+        return dict.popitem(self._build_value(last))
+
+    def __setitem__(self, key, value):
+        dict.__setitem__(self._load_once(), key, value)
+
+    def __delitem__(self, key):
+        dict.__delitem__(self._load_once(), key)
+
+    def update(self, *args, **kwargs):
+        dict.update(self._load_once(), *args, **kwargs)
+
+    def __ior__(self, other):
+        return dict.__ior__(self._load_once(), other)
+
+    def clear(self):
+        dict.clear(self._load_once())
+
+    def copy(self):
+        return dict(dict.items(self._build_all()))
+
+    def __or__(self, other):
+        return dict.__or__(self.copy(), other)
+
+    def __ror__(self, other):
+        return dict.__ror__(self.copy(), other)
+
+    @classmethod
+    def fromkeys(cls, iterable, value=None):
+        return dict.fromkeys(iterable, value)
+
+    def __eq__(self, other):
+        if isinstance(other, LazyDict):
+            other = other._build_all()
+        return dict.__eq__(self._build_all(), other)
+
+    def __ne__(self, other):
+        eq = self.__eq__(other)
+        return eq if eq is NotImplemented else not eq
+
+    __hash__ = None
+
+    def __repr__(self):
+        return dict.__repr__(self._build_all())
+
+    def __reduce__(self):
+        return (dict, (list(dict.items(self._build_all())),))
