@@ -58,6 +58,10 @@ def build_parser():
     hp.add_argument("--bp_match_cutoff", help="Breakpoint matching cutoff.", type=int, default=100)
     hp.add_argument("--bp_match_cutoff_clustering", help="Crude breakpoint matching cutoff for clustering.", type=int, default=2000)
     hp.add_argument("--device", help="GPU to use (MI355X build only option).", default="cuda:0")
+    ip = sub.add_parser("index", help="Write the BAI index of a sorted bam file (x.bam.bai), from one decode of it.")
+    ip.add_argument("--lr_bam", help="Sorted (long read) bam file.", required=True)
+    ip.add_argument("--index", help="Name of the index file (default: <lr_bam>.bai).")
+    ip.add_argument("--device", help="GPU to use ('cpu': the host pipeline).", default="cuda:0")
     for mode in ("seed", "plot", "cycle2bed"):
         sub.add_parser(mode, help="(reference implementation; not part of the MI355X path)", add_help=False)
     return parser
@@ -104,6 +108,11 @@ def main(argv=None):
         print_args(args)
         from coral_amd import hsr
         return hsr.locate_hsrs(args)
+    if args.mode == "index":
+        from coral_amd import bam
+        out = bam.build_index(args.lr_bam, args.index, device=args.device)
+        print("Wrote %s" % out)
+        return out
     parser.print_help()
     return None
 

@@ -122,6 +122,18 @@ def lib():
     L.coral_bam_coverage_result.argtypes = [C.c_void_p, C.c_int32, P]
     L.coral_bamgpu_coverage.argtypes = [C.c_void_p, C.c_int32, P, P, P, C.c_int32, C.c_int32, P]
     L.coral_bamgpu_coverage_result.argtypes = [C.c_void_p, C.c_int32, P, P]
+    L.coral_bam_decode_range_idx.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
+    L.coral_bam_index_sizes.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+    L.coral_bam_index_fill.argtypes = [C.c_void_p, P, P, P, P, P, C.POINTER(C.c_uint64)]
+    L.coral_bam_decode_spans.argtypes = [C.c_char_p, C.c_int32, C.c_int32, P, P, C.POINTER(C.c_void_p)]
+    L.coral_bam_decode_spans_cov.argtypes = [C.c_char_p, C.c_int32, C.c_int32, P, P, C.c_int32, P, P, P, C.c_int32, C.c_int32,
+                                             C.POINTER(C.c_void_p)]
+    L.coral_bamgpu_open_spans.argtypes = [C.c_char_p, C.c_int32, C.c_int32, P, P, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
+    L.coral_bamgpu_index.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+    L.coral_bamgpu_index_result.argtypes = [C.c_void_p, P]
+    for name in ("coral_bam_decode_range_idx", "coral_bam_index_sizes", "coral_bam_index_fill", "coral_bam_decode_spans",
+                 "coral_bam_decode_spans_cov", "coral_bamgpu_open_spans", "coral_bamgpu_index", "coral_bamgpu_index_result"):
+        getattr(L, name).restype = C.c_int
     for name in ("coral_bam_decode_range_cov", "coral_bam_coverage_result", "coral_bamgpu_coverage", "coral_bamgpu_coverage_result"):
         getattr(L, name).restype = C.c_int
     for name in ("coral_bamgpu_open", "coral_bamgpu_start", "coral_bamgpu_next", "coral_bamgpu_emit", "coral_bamgpu_host",

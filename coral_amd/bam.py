@@ -60,12 +60,81 @@ def decode_bam(path: str, n_threads: Optional[int] = None, rank: int = 0, world:
         L.coral_bam_decode_close(h)
 
 
-def load_bam(path: str, device="cuda:0", n_threads: Optional[int] = None, rank: int = 0, world: int = 1) -> Records:
+def _on_gpu(device) -> bool:
+    return torch.device(device).type == "cuda" and os.environ.get("CORAL_BAM_DECODE", "gpu") != "cpu"
+
+
+def load_bam(path: str, device="cuda:0", n_threads: Optional[int] = None, rank: int = 0, world: int = 1, *, regions=None,
+             index=None) -> Records:
     """The product's way from a BAM file to records: inflate and parse on the GPU (``decode_bam_gpu``) when ``device`` is one;
-    ``CORAL_BAM_DECODE=cpu`` selects the host pipeline (``decode_bam``: same result, CIGAR words in host memory)."""
-    if torch.device(device).type == "cuda" and os.environ.get("CORAL_BAM_DECODE", "gpu") != "cpu":
-        return decode_bam_gpu(path, device, n_threads=n_threads, rank=rank, world=world)
-    return decode_bam(path, n_threads=n_threads, rank=rank, world=world)
+    ``CORAL_BAM_DECODE=cpu`` selects the host pipeline (``decode_bam``: same result, CIGAR words in host memory).
+
+    ``regions`` = [(chrom, start, stop), ...]: only the records pysam's ``fetch`` returns for them (on the contig, ``pos < stop
+    and end > start``), each once, in file order, read-name ids numbered by first appearance among them — through the BAI index
+    ``index`` (a path, an object of ``read_index``, or None for the file next to the BAM, which must then be usable): only the
+    BGZF blocks the index names are read and inflated; records a chunk carries that meet no region are dropped on the host."""
+    if regions is None:
+        if _on_gpu(device):
+            return decode_bam_gpu(path, device, n_threads=n_threads, rank=rank, world=world)
+        return decode_bam(path, n_threads=n_threads, rank=rank, world=world)
+    if world != 1:
+        raise ValueError("a region decode is not sharded (world must be 1)")
+    if index is False:
+        raise ValueError("load_bam(regions=...) needs an index: pass its path, an object of read_index, or None for the file beside the BAM")
+    names = bam_reference_names(path)
+    idx = _usable_index(path, index if index is not None else _index_beside(path, must=True), len(names))
+    reg = _regions_as_tids(regions, names)
+    # (an empty region start == stop keeps, by the rule above, the records that span the point)
+    spans = region_spans(idx, [(t, a, max(b, a + 1)) for t, a, b in reg])
+    rec = _decode_spans(path, spans, device, n_threads, 0)
+    keep = np.zeros(rec.n, dtype=bool)
+    tid, pos, end = rec.tid.numpy(), rec.pos.numpy(), rec.end.numpy()
+    for t, a, b in reg:
+        keep |= (tid == t) & (pos < b) & (end > a)
+    return select_records(rec, keep)
+
+
+def select_records(rec: Records, keep) -> Records:
+    """The records ``rec[keep]`` (boolean mask) in their order: read-name ids renumbered by first appearance, ragged columns
+    re-packed (the CIGAR words on the device they are on)."""
+    keep = np.asarray(keep, dtype=bool)
+    ids = np.nonzero(keep)[0]
+    t = torch.from_numpy
+    take = lambda x: t(np.ascontiguousarray(x.numpy()[ids]))
+
+    def ragged(off, data, width=1):
+        off = off.numpy()
+        lens = off[ids + 1] - off[ids]
+        new_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+        src = np.repeat(off[ids] - new_off[:-1], lens) + np.arange(int(new_off[-1]), dtype=np.int64)
+        return t(new_off), src
+    cigar_off, cig_src = ragged(rec.cigar_off, rec.cigar)
+    cigar = rec.cigar[t(cig_src).to(rec.cigar.device)] if len(cig_src) else rec.cigar[:0]
+    sa_off, sa_src = ragged(rec.sa_off, rec.sa)
+    na_keep = keep[rec.nonacgt_rec.numpy()] if rec.nonacgt_rec.numel() else np.zeros(0, dtype=bool)
+    new_ordinal = np.cumsum(keep) - 1
+    old_ids = rec.name_id.numpy()[ids]
+    uniq, first, inv = np.unique(old_ids, return_index=True, return_inverse=True)
+    order = np.argsort(first, kind="stable")                     # name ids in order of first appearance among the kept
+    rank_of = np.empty(len(uniq), dtype=np.int64)
+    rank_of[order] = np.arange(len(uniq))
+    names = rec.names
+    if isinstance(names, NameTable):
+        old = uniq[order]
+        lens = names.off[old + 1] - names.off[old]
+        off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+        src = np.repeat(names.off[old] - off[:-1], lens) + np.arange(int(off[-1]), dtype=np.int64)
+        names = NameTable(names.blob[src] if len(src) else np.zeros(0, dtype=np.uint8), off)
+    else:
+        all_names = rec.materialise_names()
+        names = [all_names[k] for k in uniq[order]]
+    return Records(n=len(ids), tid=take(rec.tid), pos=take(rec.pos), end=take(rec.end), flag=take(rec.flag), mapq=take(rec.mapq),
+                   qlen=take(rec.qlen), has_seq=take(rec.has_seq), nm=take(rec.nm), name_id=t(rank_of[inv].astype(np.int32)),
+                   n_cigar=take(rec.n_cigar), cigar_off=cigar_off, cigar=cigar, sa_off=sa_off,
+                   sa=t(np.ascontiguousarray(rec.sa.numpy()[sa_src])), sa_nm=t(np.ascontiguousarray(rec.sa_nm.numpy()[sa_src])),
+                   nonacgt_rec=t(new_ordinal[rec.nonacgt_rec.numpy()[na_keep]].astype(np.int64)),
+                   nonacgt_pos=t(np.ascontiguousarray(rec.nonacgt_pos.numpy()[na_keep])), n_names=len(uniq), name_gid=None, names=names,
+                   header_chroms=list(rec.header_chroms), header_lens=list(rec.header_lens))
 
 
 def _records_from_handle(L, h, cigar, cigar_words: int) -> Records:
@@ -114,10 +183,13 @@ def decode_bam_gpu(path: str, device="cuda:0", n_threads: Optional[int] = None, 
     return _decode_gpu(path, device, n_threads, rank, world, batch_bytes)[0]
 
 
-def _decode_gpu(path: str, device, n_threads: Optional[int], rank: int, world: int, batch_bytes: int, coverage=None, records=True):
+def _decode_gpu(path: str, device, n_threads: Optional[int], rank: int, world: int, batch_bytes: int, coverage=None, records=True,
+                spans=None, index=False):
     """decode_bam_gpu; with ``coverage`` = (segments int32 [3][S], quality threshold, read_callback code) the window-coverage
     request of coral_bamgpu_coverage rides along and its S int64 counts come back as the second result (records: None
-    unless ``records``)."""
+    unless ``records``).  ``spans`` (uint64 [K][2] virtual offsets): only the records that start inside them
+    (coral_bamgpu_open_spans).  ``index``: the index request of coral_bamgpu_index rides along; its partial index is the
+    third result."""
     L = _lib.lib()
     dev = torch.device(device)
     if dev.type != "cuda":
@@ -126,10 +198,17 @@ def _decode_gpu(path: str, device, n_threads: Optional[int], rank: int, world: i
     if n_threads is None:
         n_threads = default_threads()
     h, ws_bytes = C.c_void_p(), C.c_int64(0)
-    rc = L.coral_bamgpu_open(path.encode(), n_threads, rank, world, batch_bytes, C.byref(h), C.byref(ws_bytes))
+    if spans is None:
+        rc = L.coral_bamgpu_open(path.encode(), n_threads, rank, world, batch_bytes, C.byref(h), C.byref(ws_bytes))
+    else:
+        sp_beg, sp_end = np.ascontiguousarray(spans[:, 0], dtype=np.uint64), np.ascontiguousarray(spans[:, 1], dtype=np.uint64)
+        rc = L.coral_bamgpu_open_spans(path.encode(), n_threads, len(spans), sp_beg.ctypes.data, sp_end.ctypes.data, batch_bytes,
+                                       C.byref(h), C.byref(ws_bytes))
     if rc != 0:
         raise _lib.CoralHipError("coral_bamgpu_open(%s) failed (%d): %s" % (path, rc, L.coral_bam_last_error().decode()))
     try:
+        if index and L.coral_bamgpu_index(h, C.byref(ws_bytes)) != 0:
+            raise _lib.CoralHipError("coral_bamgpu_index(%s) failed: %s" % (path, L.coral_bam_last_error().decode()))
         ws = torch.empty(int(ws_bytes.value) + 256, dtype=torch.uint8, device=dev)
         base = (ws.data_ptr() + 255) & ~255
         stream = torch.cuda.current_stream(dev).cuda_stream
@@ -172,6 +251,10 @@ def _decode_gpu(path: str, device, n_threads: Optional[int], rank: int, world: i
             rc = L.coral_bamgpu_coverage_result(h, S, counts.ctypes.data, stream)
             if rc != 0:
                 raise fail("coral_bamgpu_coverage_result", rc)
+        if index:
+            rc = L.coral_bamgpu_index_result(h, stream)
+            if rc != 0:
+                raise fail("coral_bamgpu_index_result", rc)
         cigar = torch.cat(pieces) if len(pieces) > 1 else (pieces[0] if pieces else torch.zeros(0, dtype=torch.int32, device=dev))
         del pieces
         dh = C.c_void_p()
@@ -188,7 +271,8 @@ def _decode_gpu(path: str, device, n_threads: Optional[int], rank: int, world: i
                            nonacgt_records_fetched=int(gst[2]), batch_bytes=int(gst[3]), host_seconds=float(gsecs[1]), read_seconds=float(gsecs[2]),
                            setup_seconds=float(gsecs[3]), waited_for_file_seconds=float(gsecs[4]), waited_for_gpu_seconds=float(gsecs[5]),
                            workspace_bytes=int(ws_bytes.value))
-        return (_records_from_handle(L, dh, cigar, total) if records else None), counts
+        partial = _index_partial_from_handle(L, dh) if index else None
+        return (_records_from_handle(L, dh, cigar, total) if records else None), counts, partial
     finally:
         # (close drains the decoder's streams — a byte range may have batches of its overhang still being inflated — and only
         # then the workspace, which those kernels write, is released: `ws` lives until this function returns)
@@ -263,7 +347,8 @@ def coverage_segments(windows, ref_names: Sequence[str]):
 
 
 def window_coverage(path: str, windows: Sequence[Tuple[str, int, int]], quality_threshold=0, read_callback: str = "nofilter",
-                    device="cuda:0", rank: int = 0, world: int = 1, batch_bytes: int = 0, n_threads: Optional[int] = None) -> np.ndarray:
+                    device="cuda:0", rank: int = 0, world: int = 1, batch_bytes: int = 0, n_threads: Optional[int] = None, *,
+                    index=None) -> np.ndarray:
     """pysam ``AlignmentFile.count_coverage(chrom, start, stop, quality_threshold=..., read_callback=...)`` summed over its four
     arrays, for every window (chrom, start, stop) of ``windows`` (in that order, may overlap), as exact int64 — counted while
     the BAM is decoded, the only time SEQ and QUAL are at hand.
@@ -277,17 +362,69 @@ def window_coverage(path: str, windows: Sequence[Tuple[str, int, int]], quality_
 
     The GPU pipeline (csrc/coral_bamgpu.hip: k_bam_cov_plan / k_bam_cov_count per batch) runs on a GPU ``device``; the host
     pipeline (coral_bam_decode_range_cov) otherwise, or with ``CORAL_BAM_DECODE=cpu``.  With ``world`` > 1 the counts are those
-    of the ``rank``-th byte range; the ranges' counts add up to the whole file's."""
+    of the ``rank``-th byte range; the ranges' counts add up to the whole file's.
+
+    ``index``: a BAI index restricts the decode to the BGZF blocks it names for the windows (``region_spans``); the counts are
+    the same.  None (default): the index beside the file (``path + ".bai"`` or ``path[:-4] + ".bai"``) when it is a valid BAI,
+    fits the header and is not older than the BAM, else the whole file as before (``LAST_DECODE["index"]`` says which: the
+    index's path, or None with ``LAST_DECODE["index_skipped"]`` giving the reason an existing file was not used); False:
+    never; a path or an object of ``read_index``: must be usable, or the call raises.  With ``world`` > 1 an index raises
+    ValueError (a region decode is not sharded), unless it is the default one, which is then not looked for."""
     thr = quality_threshold_value(quality_threshold)
     if read_callback not in _READ_CALLBACKS:
         raise ValueError("read_callback must be 'nofilter' or 'all', got %r" % (read_callback,))
     cb = _READ_CALLBACKS[read_callback]
-    segs, first, last = coverage_segments(list(windows), bam_reference_names(path))
+    ref_names = bam_reference_names(path)
+    segs, first, last = coverage_segments(list(windows), ref_names)
     S = segs.shape[1]
     if n_threads is None:
         n_threads = default_threads()
-    if torch.device(device).type == "cuda" and os.environ.get("CORAL_BAM_DECODE", "gpu") != "cpu":
+    idx, skipped = None, None
+    if index is not None and index is not False:
+        if world != 1:
+            raise ValueError("a region decode is not sharded: index and world > 1 do not go together")
+        idx = _usable_index(path, index, len(ref_names))
+    elif index is None and world == 1:
+        beside = _index_beside(path)
+        if beside is not None:
+            try:
+                if os.path.getmtime(beside) < os.path.getmtime(path):
+                    raise _lib.CoralHipError("%s is older than the BAM file" % beside)
+                idx = _usable_index(path, beside, len(ref_names))
+            except (_lib.CoralHipError, OSError) as e:
+                skipped = str(e)
+    if idx is not None:
+        regions = []                                             # the segments, neighbours within one linear-index window joined
+        for t, a, b in segs.T.tolist():
+            if regions and regions[-1][0] == t and a - regions[-1][2] < 16384:
+                regions[-1][2] = b
+            else:
+                regions.append([t, a, b])
+        spans = region_spans(idx, regions)
+        if len(spans) == 0:
+            counts = np.zeros(S, dtype=np.int64)
+            LAST_DECODE.clear()
+            LAST_DECODE.update(seconds=0.0, compressed_bytes=0, uncompressed_bytes=0, blocks=0, threads=int(n_threads))
+        elif _on_gpu(device):
+            counts = _decode_gpu(path, device, n_threads, 0, 1, batch_bytes, coverage=(segs, thr, cb), records=False, spans=spans)[1]
+        else:
+            L = _lib.lib()
+            h = C.c_void_p()
+            sp_beg, sp_end = np.ascontiguousarray(spans[:, 0]), np.ascontiguousarray(spans[:, 1])
+            rc = L.coral_bam_decode_spans_cov(path.encode(), n_threads, len(spans), sp_beg.ctypes.data, sp_end.ctypes.data, S, segs[0].ctypes.data,
+                                              segs[1].ctypes.data, segs[2].ctypes.data, thr, cb, C.byref(h))
+            if rc != 0:
+                raise _lib.CoralHipError("coral_bam_decode_spans_cov(%s) failed (%d): %s" % (path, rc, L.coral_bam_last_error().decode()))
+            try:
+                counts = np.zeros(S, dtype=np.int64)
+                _lib.check(L.coral_bam_coverage_result(h, S, counts.ctypes.data), "coral_bam_coverage_result")
+                _host_stats(L, h, n_threads)
+            finally:
+                L.coral_bam_decode_close(h)
+        LAST_DECODE.update(index=idx.path or "<object>", spans=int(len(spans)))
+    elif _on_gpu(device):
         counts = _decode_gpu(path, device, n_threads, rank, world, batch_bytes, coverage=(segs, thr, cb), records=False)[1]
+        LAST_DECODE.update(index=None, index_skipped=skipped)
     else:
         L = _lib.lib()
         h = C.c_void_p()
@@ -298,10 +435,328 @@ def window_coverage(path: str, windows: Sequence[Tuple[str, int, int]], quality_
         try:
             counts = np.zeros(S, dtype=np.int64)
             _lib.check(L.coral_bam_coverage_result(h, S, counts.ctypes.data), "coral_bam_coverage_result")
+            _host_stats(L, h, n_threads)
+            LAST_DECODE.update(index=None, index_skipped=skipped)
         finally:
             L.coral_bam_decode_close(h)
     csum = np.concatenate([[0], np.cumsum(counts, dtype=np.int64)])
     return (csum[last] - csum[first]).astype(np.int64)
+
+
+# ----------------------------------------------------------------------------------------------
+# BAI index (SAMv1 §5.2): built during a decode, read, queried
+# ----------------------------------------------------------------------------------------------
+_PSEUDO_BIN = 37450
+_NO_OFFSET = np.uint64(0xffffffffffffffff)
+
+
+def _host_stats(L, h, n_threads):
+    st, secs = (C.c_int64 * 3)(), C.c_double(0.0)
+    L.coral_bam_decode_stats(h, st, C.byref(secs))
+    LAST_DECODE.clear()
+    LAST_DECODE.update(seconds=float(secs.value), compressed_bytes=int(st[0]), uncompressed_bytes=int(st[1]), blocks=int(st[2]),
+                       threads=int(n_threads))
+
+
+def _decode_spans(path, spans, device, n_threads, batch_bytes) -> Records:
+    """The records that start inside ``spans`` (uint64 [K][2] virtual offsets), on either pipeline."""
+    if n_threads is None:
+        n_threads = default_threads()
+    if _on_gpu(device) and len(spans):
+        return _decode_gpu(path, device, n_threads, 0, 1, batch_bytes, spans=spans)[0]
+    L = _lib.lib()
+    h = C.c_void_p()
+    sp_beg, sp_end = np.ascontiguousarray(spans[:, 0], dtype=np.uint64), np.ascontiguousarray(spans[:, 1], dtype=np.uint64)
+    rc = L.coral_bam_decode_spans(path.encode(), n_threads, len(spans), sp_beg.ctypes.data, sp_end.ctypes.data, C.byref(h))
+    if rc != 0:
+        raise _lib.CoralHipError("coral_bam_decode_spans(%s) failed (%d): %s" % (path, rc, L.coral_bam_last_error().decode()))
+    try:
+        _host_stats(L, h, n_threads)
+        return _records_from_handle(L, h, None, 0)
+    finally:
+        L.coral_bam_decode_close(h)
+
+
+def _index_partial_from_handle(L, h) -> dict:
+    sz = (C.c_int64 * 4)()
+    _lib.check(L.coral_bam_index_sizes(h, sz), "coral_bam_index_sizes")
+    n_heads, n_lin, n_ref, n_rec = (int(v) for v in sz)
+    key, voff = np.empty(n_heads, dtype=np.int64), np.empty(n_heads, dtype=np.uint64)
+    lin = np.empty(n_lin, dtype=np.uint64)
+    mapped, unmapped = np.empty(n_ref, dtype=np.int64), np.empty(n_ref, dtype=np.int64)
+    sc = (C.c_uint64 * 4)()
+    _lib.check(L.coral_bam_index_fill(h, key.ctypes.data, voff.ctypes.data, lin.ctypes.data, mapped.ctypes.data, unmapped.ctypes.data, sc),
+               "coral_bam_index_fill")
+    return dict(head_key=key, head_voff=voff, lin=lin, n_mapped=mapped, n_unmapped=unmapped, n_records=n_rec, n_no_coor=int(sc[0]),
+                end_voff=int(sc[1]), first_sort=int(sc[2]), last_sort=int(sc[3]))
+
+
+def index_partial(path: str, device="cuda:0", rank: int = 0, world: int = 1, n_threads: Optional[int] = None, batch_bytes: int = 0) -> dict:
+    """What the ``rank``-th of ``world`` byte ranges of the BAM contributes to its BAI index, from one decode with an index
+    request (GPU: coral_bamgpu_index, k_bam_index per batch; host: coral_bam_decode_range_idx).  ``merge_index_partials`` puts
+    consecutive ranges together, ``index_bytes`` writes the file's bytes."""
+    if n_threads is None:
+        n_threads = default_threads()
+    if _on_gpu(device):
+        return _decode_gpu(path, device, n_threads, rank, world, batch_bytes, records=False, index=True)[2]
+    L = _lib.lib()
+    h = C.c_void_p()
+    rc = L.coral_bam_decode_range_idx(path.encode(), n_threads, rank, world, C.byref(h))
+    if rc != 0:
+        raise _lib.CoralHipError("coral_bam_decode_range_idx(%s) failed (%d): %s" % (path, rc, L.coral_bam_last_error().decode()))
+    try:
+        _host_stats(L, h, n_threads)
+        return _index_partial_from_handle(L, h)
+    finally:
+        L.coral_bam_decode_close(h)
+
+
+def merge_index_partials(parts: Sequence[dict]) -> dict:
+    """The partial indexes of consecutive byte ranges (in rank order) as one: a run of equal (tid, bin) that goes on across a
+    boundary is one run, a window takes the smallest offset, counts add up, and the file ends where the last range that holds a
+    record ends.  Raises CoralHipError when the ranges are not in coordinate order among each other."""
+    parts = list(parts)
+    full = [p for p in parts if p["n_records"] > 0]
+    for a, b in zip(full, full[1:]):
+        if b["first_sort"] < a["last_sort"]:
+            raise _lib.CoralHipError("the records are not in coordinate order: no index can be built")
+    key = np.concatenate([p["head_key"] for p in parts])
+    voff = np.concatenate([p["head_voff"] for p in parts])
+    if len(key):
+        new = np.concatenate([[True], key[1:] != key[:-1]])
+        key, voff = key[new], voff[new]
+    last = full[-1] if full else parts[0]
+    return dict(head_key=key, head_voff=voff, lin=np.minimum.reduce([p["lin"] for p in parts]),
+                n_mapped=np.sum([p["n_mapped"] for p in parts], axis=0), n_unmapped=np.sum([p["n_unmapped"] for p in parts], axis=0),
+                n_records=sum(p["n_records"] for p in parts), n_no_coor=sum(p["n_no_coor"] for p in parts), end_voff=last["end_voff"],
+                first_sort=(full[0] if full else parts[0])["first_sort"], last_sort=last["last_sort"])
+
+
+def index_bytes(partial: dict, ref_lens: Sequence[int]) -> bytes:
+    """The BAI file (SAMv1 §5.2) of a whole file's (merged) partial index: per contig its bins in ascending order, each with
+    its chunks in file order, the pseudo-bin 37450 last (first and last offset of the contig, records with and without flag
+    0x4), the linear index up to the last window a record overlaps (a window without records repeats the one in front, leading
+    ones hold 0), and the number of records without coordinates."""
+    key, beg = partial["head_key"], partial["head_voff"]
+    end = np.concatenate([beg[1:], np.array([partial["end_voff"]], dtype=np.uint64)]) if len(beg) else beg
+    placed = key >= 0
+    key, beg, end = key[placed], beg[placed], end[placed]
+    order = np.argsort(key, kind="stable")                       # by (tid, bin); a bin's chunks stay in file order
+    key, beg, end = key[order], beg[order], end[order]
+    tid_of = key >> 16
+    lin_off = np.concatenate([[0], np.cumsum([(max(int(l), 0) >> 14) + 1 for l in ref_lens])]).astype(np.int64)
+    out = [b"BAI\x01", struct.pack("<i", len(ref_lens))]
+    for t in range(len(ref_lens)):
+        a, b = np.searchsorted(tid_of, t), np.searchsorted(tid_of, t, side="right")
+        if a == b:
+            out.append(struct.pack("<ii", 0, 0))
+            continue
+        k, cb, ce = key[a:b] & 0xffff, beg[a:b], end[a:b]
+        cut = np.concatenate([[0], np.nonzero(k[1:] != k[:-1])[0] + 1, [len(k)]])
+        out.append(struct.pack("<i", len(cut)))                  # (the bins + the pseudo-bin)
+        # all bins of the contig as 64-bit words at once: per bin one word (bin number | chunk count << 32), then its chunks
+        n_bins, counts = len(cut) - 1, np.diff(cut)
+        words = np.empty(n_bins + 2 * len(k), dtype="<u8")
+        words[np.arange(n_bins) + 2 * cut[:-1]] = k[cut[:-1]].astype(np.uint64) | (counts.astype(np.uint64) << np.uint64(32))
+        at = 2 * np.arange(len(k)) + np.repeat(np.arange(n_bins), counts) + 1
+        words[at], words[at + 1] = cb, ce
+        out.append(words.tobytes())
+        out.append(struct.pack("<IiQQQQ", _PSEUDO_BIN, 2, int(cb.min()), int(ce.max()), int(partial["n_mapped"][t]), int(partial["n_unmapped"][t])))
+        lin = partial["lin"][lin_off[t]:lin_off[t + 1]].copy()
+        have = np.nonzero(lin != _NO_OFFSET)[0]
+        n_intv = int(have[-1]) + 1 if len(have) else 0
+        lin = lin[:n_intv]
+        src = np.maximum.accumulate(np.where(lin != _NO_OFFSET, np.arange(n_intv), -1))      # the last window with a record at or in front
+        filled = np.where(src >= 0, lin[np.maximum(src, 0)], np.uint64(0)).astype("<u8")
+        out.append(struct.pack("<i", n_intv) + filled.tobytes())
+    out.append(struct.pack("<Q", int(partial["n_no_coor"])))
+    return b"".join(out)
+
+
+def bam_reference_lengths(path: str):
+    with gzip.open(path, "rb") as fp:
+        fp.read(4)
+        fp.read(struct.unpack("<i", fp.read(4))[0])
+        lens = []
+        for _ in range(struct.unpack("<i", fp.read(4))[0]):
+            fp.read(struct.unpack("<i", fp.read(4))[0])
+            lens.append(struct.unpack("<i", fp.read(4))[0])
+        return lens
+
+
+def build_index(path: str, index_path: Optional[str] = None, device="cuda:0", n_threads: Optional[int] = None, batch_bytes: int = 0,
+                world: int = 1) -> str:
+    """Write the BAI index of a coordinate-sorted BAM (default ``path + ".bai"``; to a temporary name first, then renamed) and
+    return its path — what ``samtools index`` does, from one decode of the file: on the GPU pipeline when ``device`` is a GPU
+    (k_bam_index beside the parse of every batch), on the host pipeline otherwise or with ``CORAL_BAM_DECODE=cpu``.  ``world`` >
+    1 decodes that many byte ranges one after the other and merges their partial indexes (the bytes are the same).  A file that
+    is not in coordinate order raises CoralHipError and leaves no index behind.  The bytes are a function of the BAM file alone
+    (spec-conformant; not the sparser file htslib writes, which also folds small bins into their parents)."""
+    bam_reference_names(path)                                    # (a clear error for something that is not a BAM file)
+    parts = [index_partial(path, device, r, world, n_threads, batch_bytes) for r in range(world)]
+    data = index_bytes(merge_index_partials(parts), bam_reference_lengths(path))
+    index_path = index_path or path + ".bai"
+    tmp = "%s.tmp%d" % (index_path, os.getpid())
+    try:
+        with open(tmp, "wb") as fp:
+            fp.write(data)
+        os.replace(tmp, index_path)
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+    return index_path
+
+
+class BamIndex:
+    """A BAI index in memory (``read_index``): per contig ``bins[tid]`` = {bin: uint64 [K][2] chunks (begin, end)} without the
+    pseudo-bin, ``linear[tid]`` = uint64 [n_intv], ``meta[tid]`` = (first offset, last offset, mapped, unmapped) or None, and
+    ``n_no_coor`` (None when the file ends without it)."""
+
+    def __init__(self, bins, linear, meta, n_no_coor, path=None):
+        self.bins, self.linear, self.meta, self.n_no_coor, self.path = bins, linear, meta, n_no_coor, path
+        self.n_ref = len(bins)
+
+
+def read_index(index_path: str) -> BamIndex:
+    """Read any spec-conformant ``.bai`` (SAMv1 §5.2): chunks wherever the writer put them (htslib moves those of sparse bins
+    into a parent bin and merges neighbours), the pseudo-bin and the trailing ``n_no_coor`` present or not, contigs without
+    bins, a linear index shorter than the contig.  A truncated file or one that is not a BAI raises CoralHipError."""
+    try:
+        with open(index_path, "rb") as fp:
+            raw = fp.read()
+    except OSError as e:
+        raise _lib.CoralHipError("cannot read the index %s: %s" % (index_path, e))
+    bad = lambda why: _lib.CoralHipError("%s: %s" % (index_path, why))
+    if raw[:4] != b"BAI\x01":
+        raise bad("not a BAI index")
+    o = [4]
+
+    def take(fmt):
+        n = struct.calcsize(fmt)
+        if o[0] + n > len(raw):
+            raise bad("truncated BAI index")
+        v = struct.unpack_from(fmt, raw, o[0])
+        o[0] += n
+        return v
+
+    def array(count, width):
+        if count < 0 or o[0] + 8 * count * width > len(raw):
+            raise bad("truncated BAI index")
+        a = np.frombuffer(raw, dtype="<u8", count=count * width, offset=o[0]).astype(np.uint64)
+        o[0] += 8 * count * width
+        return a
+    (n_ref,) = take("<i")
+    if n_ref < 0:
+        raise bad("not a BAI index")
+    bins, linear, meta = [], [], []
+    for _ in range(n_ref):
+        (n_bin,) = take("<i")
+        b, m = {}, None
+        for _ in range(n_bin):
+            bin_no, n_chunk = take("<Ii")
+            ch = array(n_chunk, 2).reshape(-1, 2)
+            if bin_no == _PSEUDO_BIN:
+                if n_chunk == 2:
+                    m = tuple(int(v) for v in ch.reshape(-1))
+            elif bin_no > _PSEUDO_BIN:
+                raise bad("bin number %d" % bin_no)
+            else:
+                b[int(bin_no)] = np.concatenate([b[int(bin_no)], ch]) if int(bin_no) in b else ch
+        (n_intv,) = take("<i")
+        bins.append(b)
+        meta.append(m)
+        linear.append(array(n_intv, 1))
+    n_no_coor = None
+    if o[0] + 8 <= len(raw):
+        (n_no_coor,) = take("<Q")
+    if o[0] != len(raw):
+        raise bad("bytes behind the end of the BAI index")
+    return BamIndex(bins, linear, meta, n_no_coor, index_path)
+
+
+def _reg2bins(beg: int, end: int):
+    """SAMv1 §5.3: the bins that may hold a record overlapping [beg, end)."""
+    end -= 1
+    out = [0]
+    for shift, off in ((26, 1), (23, 9), (20, 73), (17, 585), (14, 4681)):
+        out.extend(range(off + (beg >> shift), off + (end >> shift) + 1))
+    return out
+
+
+def region_spans(index: BamIndex, regions) -> np.ndarray:
+    """The query of SAMv1 §5.3 for ALL ``regions`` [(tid, beg, end), ...] at once: the chunks of the bins ``reg2bins(beg, end)``
+    of every region, without those that end at or in front of the linear index's offset for window ``beg >> 14``, merged over
+    all regions into sorted, disjoint spans of virtual offsets uint64 [K][2] (spans that overlap, touch or share a BGZF block
+    become one).  Decoding the records that start inside the spans reaches every record that overlaps a region, each once —
+    two windows whose chunk lists name the same record must not make it count twice."""
+    chunks = []
+    for tid, beg, end in regions:
+        tid, beg, end = int(tid), max(int(beg), 0), min(int(end), 1 << 29)
+        if not 0 <= tid < index.n_ref:
+            raise ValueError("region on contig %d: the index has %d contigs" % (tid, index.n_ref))
+        if end <= beg:
+            continue
+        lin = index.linear[tid]
+        min_off = int(lin[min(beg >> 14, len(lin) - 1)]) if len(lin) else 0
+        b = index.bins[tid]
+        for k in _reg2bins(beg, end) if ((end - beg) >> 14) + 6 < len(b) else [k for k in b if _bin_overlaps(k, beg, end)]:
+            ch = b.get(k)
+            if ch is not None:
+                chunks.append(ch[ch[:, 1] > np.uint64(min_off)])
+    if not chunks:
+        return np.zeros((0, 2), dtype=np.uint64)
+    ch = np.concatenate(chunks)
+    ch = ch[ch[:, 1] > ch[:, 0]]
+    ch = ch[np.argsort(ch[:, 0], kind="stable")]
+    out = []
+    for a, b in ch.tolist():
+        if out and (a >> 16) <= (out[-1][1] >> 16):
+            out[-1][1] = max(out[-1][1], b)
+        else:
+            out.append([a, b])
+    return np.array(out, dtype=np.uint64).reshape(-1, 2)
+
+
+_BIN_LEVELS = ((0, 29), (1, 26), (9, 23), (73, 20), (585, 17), (4681, 14))
+
+
+def _bin_overlaps(k: int, beg: int, end: int) -> bool:
+    for first, shift in reversed(_BIN_LEVELS):
+        if k >= first:
+            lo = (k - first) << shift
+            return lo < end and lo + (1 << shift) > beg
+    return False
+
+
+def _index_beside(path: str, must: bool = False):
+    for cand in (path + ".bai", path[:-4] + ".bai" if path.endswith(".bam") else None):
+        if cand and os.path.exists(cand):
+            return cand
+    if must:
+        raise _lib.CoralHipError("%s has no index beside it (bam.build_index writes one)" % path)
+    return None
+
+
+def _usable_index(path: str, index, n_ref: int) -> BamIndex:
+    idx = index if isinstance(index, BamIndex) else read_index(os.fspath(index))
+    if idx.n_ref != n_ref:
+        raise _lib.CoralHipError("the index %s has %d contigs, the BAM header %d" % (idx.path or "", idx.n_ref, n_ref))
+    return idx
+
+
+def _regions_as_tids(regions, ref_names):
+    tid_of = {c: k for k, c in enumerate(ref_names)}
+    out = []
+    for r in regions:
+        if len(r) != 3:
+            raise ValueError("a region is (chrom, start, stop), got %r" % (r,))
+        chrom, a, b = r
+        if chrom not in tid_of:
+            raise ValueError("unknown contig %r" % (chrom,))
+        if int(a) < 0 or int(b) < int(a):
+            raise ValueError("bad region %r: needs 0 <= start <= stop" % (r,))
+        out.append((tid_of[chrom], int(a), int(b)))
+    return out
 
 
 def write_bam_native(rec: Records, path: str, seed: int = 0, level: int = 1, n_threads: Optional[int] = None) -> None:

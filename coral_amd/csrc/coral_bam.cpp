@@ -64,13 +64,18 @@ struct Chunk {
     size_t own = 0;                           // inflated bytes
     size_t begin = HEADROOM;                  // first byte that matters (HEADROOM - carried bytes)
     std::vector<size_t> starts;               // record starts (offsets into buf)
+    std::vector<uint64_t> ustarts;            // the same starts as offsets in the range's uncompressed stream (index request only)
     Partial part;
     Flag inflated, parsed;
     std::atomic<int> bad{0};
     bool submitted_parse = false;
 };
 
-bool decode_file(const char *path, int n_threads, int rank, int world, Decoded &D, const CovTable *cov = nullptr) {
+// With `span` the range is not the rank-th byte range but the records that start inside [span->beg, span->end) (virtual
+// offsets, e.g. from a BAI index): the first record is at a known place, nothing is searched, and the decode stops in front of
+// the record that starts at or behind span->end.  Spans may be decoded one after the other into the same `D`.
+bool decode_file(const char *path, int n_threads, int rank, int world, Decoded &D, const CovTable *cov = nullptr, const Span *span = nullptr,
+                 bool want_index = false) {
     const auto t_start = std::chrono::steady_clock::now();
     MappedFile f;
     if (!f.open(path, D.error)) return false;
@@ -79,33 +84,67 @@ bool decode_file(const char *path, int n_threads, int rank, int world, Decoded &
     // ---- header (every rank): inflate from block 0 until the reference list is complete
     size_t hdr_bytes = 0;                      // header length in the uncompressed stream
     RefIds ref_id;
-    if (!read_bam_header(f, D, ref_id, &hdr_bytes)) return false;
+    {
+        Decoded H;
+        if (!read_bam_header(f, H, ref_id, &hdr_bytes)) { D.error = H.error; return false; }
+        if (D.ref_names.empty()) { D.ref_names = H.ref_names; D.ref_lens = H.ref_lens; }
+    }
     const int32_t n_ref = (int32_t)D.ref_names.size();
+    if (want_index) D.idx.init(D.ref_lens);
     // ---- block table: the blocks that START inside this rank's byte range, plus an overhang for the last record
     const uint64_t byte_lo = rank == 0 ? 0 : f.size / (uint64_t)world * (uint64_t)rank;
     const uint64_t byte_hi = rank == world - 1 ? f.size : f.size / (uint64_t)world * (uint64_t)(rank + 1);
     uint64_t first = 0;
     if (rank > 0 && !find_block(f, byte_lo, &first)) first = f.size;
+    const uint64_t span_end_block = span ? span->end >> 16 : 0;
+    const uint32_t span_end_off = span ? (uint32_t)(span->end & 0xffff) : 0;
+    if (span) {
+        first = span->beg >> 16;
+        if (span->end < span->beg || first >= f.size) { D.error = "a span of virtual offsets lies outside the file"; return false; }
+    }
     std::vector<Block> blocks;
+    std::vector<uint64_t> ublk;                // offset of every block's first byte in the range's uncompressed stream
     size_t n_own = 0;
     uint64_t own_bytes = 0;                    // uncompressed offset (from this rank's first block) of the next rank's first block
+    uint64_t limit = ~0ull, total_bytes = 0;   // a record that starts at or behind `limit` (uncompressed offset) is not this range's
+    uint64_t table_end = first;                // file offset behind the last block of the table
     for (uint64_t at = first; at < f.size && blocks.size() < n_own + OVERHANG_BLOCKS;) {
         Block b;
         if (!bgzf_header(f.data + at, f.size - at, b)) { D.error = "not a BGZF block"; return false; }
         b.off = at;
-        if (at < byte_hi) { ++n_own; own_bytes += b.isize; }
+        if (span) {
+            if (at == span_end_block) limit = total_bytes + span_end_off;
+            if (at < span_end_block || (at == span_end_block && span_end_off > 0)) { ++n_own; own_bytes += b.isize; }
+        } else if (at < byte_hi) { ++n_own; own_bytes += b.isize; }
+        ublk.push_back(total_bytes);
+        total_bytes += b.isize;
         blocks.push_back(b);
         at += b.csize;
+        table_end = at;
     }
+    if (span && limit == ~0ull && span_end_block < f.size) { D.error = "the end of a span is not the start of a BGZF block"; return false; }
+    // virtual offset of the record that starts at uncompressed offset u; behind the last byte: the block that follows (bgzf_tell)
+    auto voffset = [&](uint64_t u) -> uint64_t {
+        if (u < total_bytes) {
+            const size_t b = (size_t)(std::upper_bound(ublk.begin(), ublk.end(), u) - ublk.begin()) - 1;
+            return (blocks[b].off << 16) | (u - ublk[b]);
+        }
+        const size_t b = (size_t)(std::lower_bound(ublk.begin(), ublk.end(), u) - ublk.begin());
+        return (b < blocks.size() ? blocks[b].off : table_end) << 16;
+    };
     std::vector<std::unique_ptr<Chunk>> chunks;
-    for (size_t b = 0; b < blocks.size(); b += CHUNK_BLOCKS) {
+    for (size_t b = 0; b < blocks.size();) {     // (a span's own blocks end with a chunk: what lies behind is inflated only if needed)
+        size_t e = std::min(blocks.size(), b + CHUNK_BLOCKS);
+        if (span && b < n_own && e > n_own) e = n_own;
         chunks.emplace_back(new Chunk());
         chunks.back()->b0 = b;
-        chunks.back()->b1 = std::min(blocks.size(), b + CHUNK_BLOCKS);
+        chunks.back()->b1 = e;
+        b = e;
     }
     const size_t n_chunks = chunks.size();
     const size_t own_chunks = (n_own + CHUNK_BLOCKS - 1) / CHUNK_BLOCKS;      // chunks holding at least one owned block
-    const bool last_rank = rank == world - 1;
+    const bool last_rank = rank == world - 1 && !span;
+    if (!span && !last_rank) limit = own_bytes;
 
     Pool pool(n_threads);
     const size_t window = (size_t)std::max(4, 3 * n_threads);
@@ -142,12 +181,14 @@ bool decode_file(const char *path, int n_threads, int rank, int world, Decoded &
     };
     auto wait = [&](Flag &fl) { while (!fl.get()) if (!pool.help_one()) std::this_thread::yield(); };
 
-    D.names.grow(1 << 21);
-    if (cov) D.cov.assign(cov->size(), 0);
+    if (D.tid.empty()) D.names.grow(1 << 21);
+    if (cov && D.cov.size() != cov->size()) D.cov.assign(cov->size(), 0);
     auto merge = [&](Chunk &c) -> bool {
         Partial &pt = c.part;
         if (!pt.error.empty()) { D.error = pt.error; return false; }
         const int64_t base = (int64_t)D.tid.size();
+        if (D.idx.on)                          // the index request: records in file order, each with its virtual offset
+            for (size_t j = 0; j < pt.tid.size(); ++j) D.idx.add(pt.tid[j], pt.pos[j], pt.end[j], pt.flag[j], voffset(c.ustarts[j]));
         auto app = [](std::vector<int32_t> &d, const std::vector<int32_t> &s) { d.insert(d.end(), s.begin(), s.end()); };
         app(D.tid, pt.tid); app(D.pos, pt.pos); app(D.end, pt.end); app(D.flag, pt.flag); app(D.mapq, pt.mapq);
         app(D.qlen, pt.qlen); app(D.has_seq, pt.has_seq); app(D.nm, pt.nm); app(D.n_cigar, pt.n_cigar);
@@ -170,11 +211,11 @@ bool decode_file(const char *path, int n_threads, int rank, int world, Decoded &
     // ---- the ordered walk: stage 2 for chunk k, stage 4 for the chunks whose parse is done (in order)
     size_t next_inflate = 0, merged = 0;
     auto top_up = [&](size_t k) {               // beyond the owned chunks only one chunk ahead (the overhang is rarely needed)
-        const size_t upto = std::min(n_chunks, std::max(k + 1, std::min(k + window, own_chunks + 1)));
+        const size_t upto = std::min(n_chunks, std::max(k + 1, std::min(k + window, own_chunks + (span ? 0 : 1))));
         while (next_inflate < upto) submit_inflate(next_inflate++);
     };
-    bool searching = rank > 0;                 // still looking for the first record of the range
-    uint64_t pos = rank == 0 ? hdr_bytes : 0;  // offset (in this rank's uncompressed stream) of the next record start
+    bool searching = rank > 0 && !span;        // still looking for the first record of the range
+    uint64_t pos = span ? (span->beg & 0xffff) : rank == 0 ? hdr_bytes : 0;  // offset (in this rank's uncompressed stream) of the next record start
     std::vector<uint8_t> carry;                // bytes [pos, end of the previous chunk): head of a straddling record
     uint64_t ubase = 0;                        // stream offset of the current chunk's first inflated byte
     bool done = false;
@@ -226,16 +267,17 @@ bool decode_file(const char *path, int n_threads, int rank, int world, Decoded &
             p = (size_t)(pos - u0);
         }
         while (p < nbytes) {
-            if (!last_rank && u0 + p >= own_bytes) { done = true; break; }     // starts in the next rank's range: theirs
+            if (u0 + p >= limit) { done = true; break; }                       // starts in the next rank's range (behind the span): not ours
             if (nbytes - p < 4) break;
             const uint64_t len = 4ull + rd32(base + p);
             if (len < 36) { D.error = "record shorter than its fixed fields"; return false; }
             if (p + len > nbytes) break;                                       // straddles into the next chunk
             c.starts.push_back(c.begin + p);
+            if (want_index) c.ustarts.push_back(u0 + p);
             p += (size_t)len;
         }
         if (!done) {
-            if (!last_rank && u0 + p >= own_bytes) done = true;
+            if (u0 + p >= limit) done = true;
             else if (p < nbytes) carry.assign(base + p, base + nbytes);
         }
         pos = u0 + p;
@@ -260,9 +302,15 @@ bool decode_file(const char *path, int n_threads, int rank, int world, Decoded &
     }
     // inflate tasks that were submitted ahead but never used must finish before the pool (and the chunks) go away
     for (size_t k = 0; k < next_inflate; ++k) wait(chunks[k]->inflated);
-    for (size_t b = 0; b < n_own; ++b) { D.compressed_bytes += blocks[b].csize; D.uncompressed_bytes += blocks[b].isize; }
-    D.n_blocks = (int64_t)n_own;
-    D.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
+    // statistics: the range's own blocks; of a span every block that was inflated (its overhang included)
+    const size_t n_read = span ? (next_inflate ? chunks[next_inflate - 1]->b1 : 0) : n_own;
+    for (size_t b = 0; b < n_read; ++b) { D.compressed_bytes += blocks[b].csize; D.uncompressed_bytes += blocks[b].isize; }
+    D.n_blocks += (int64_t)n_read;
+    if (D.idx.on) {
+        if (D.idx.unsorted) { D.error = "the records are not in coordinate order: no index can be built"; return false; }
+        D.idx.end_voff = voffset(pos);
+    }
+    D.seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
     return true;
 }
 
@@ -433,12 +481,25 @@ void coral_bam::set_error(const std::string &msg) { g_bam_err = msg; }
 
 extern "C" const char *coral_bam_last_error(void) { return g_bam_err.c_str(); }
 
-static int decode_range(const char *path, int32_t n_threads, int32_t rank, int32_t world, const CovTable *cov, void **handle) {
-    if (!path || !handle) return CORAL_ERR_ARG;
+static int decode_range(const char *path, int32_t n_threads, int32_t rank, int32_t world, const CovTable *cov, void **handle,
+                        bool want_index = false, int32_t n_spans = -1, const uint64_t *span_beg = nullptr, const uint64_t *span_end = nullptr) {
+    if (!path || !handle || (n_spans > 0 && (!span_beg || !span_end))) return CORAL_ERR_ARG;
     Decoded *D = new Decoded();
     bool ok = false;
     try {
-        ok = decode_file(path, n_threads, rank, world, *D, cov);
+        if (n_spans < 0) {
+            ok = decode_file(path, n_threads, rank, world, *D, cov, nullptr, want_index);
+        } else {                                 // spans in the given order, into one result (no span: the header only)
+            MappedFile f;
+            RefIds ids;
+            size_t hdr = 0;
+            ok = f.open(path, D->error) && read_bam_header(f, *D, ids, &hdr);
+            if (ok && cov) D->cov.assign(cov->size(), 0);
+            for (int32_t k = 0; k < n_spans && ok; ++k) {
+                const Span sp{span_beg[k], span_end[k]};
+                ok = decode_file(path, n_threads, 0, 1, *D, cov, &sp);
+            }
+        }
     } catch (const std::exception &e) {          // e.g. bad_alloc on a corrupt size field: never across the C boundary
         D->error = std::string("decoder failed: ") + e.what();
     }
@@ -465,6 +526,51 @@ extern "C" int coral_bam_decode_range_cov(const char *path, int32_t n_threads, i
         return CORAL_ERR_ARG;
     }
     return decode_range(path, n_threads, rank, world, &T, handle);
+}
+
+extern "C" int coral_bam_decode_range_idx(const char *path, int32_t n_threads, int32_t rank, int32_t world, void **handle) {
+    return decode_range(path, n_threads, rank, world, nullptr, handle, true);
+}
+
+extern "C" int coral_bam_decode_spans(const char *path, int32_t n_threads, int32_t n_spans, const uint64_t *span_beg,
+                                      const uint64_t *span_end, void **handle) {
+    if (n_spans < 0) return CORAL_ERR_ARG;
+    return decode_range(path, n_threads, 0, 1, nullptr, handle, false, n_spans, span_beg, span_end);
+}
+
+extern "C" int coral_bam_decode_spans_cov(const char *path, int32_t n_threads, int32_t n_spans, const uint64_t *span_beg,
+                                          const uint64_t *span_end, int32_t n_seg, const int32_t *seg_tid, const int32_t *seg_start,
+                                          const int32_t *seg_end, int32_t quality_threshold, int32_t read_callback, void **handle) {
+    CovTable T;
+    std::string err;
+    if (n_spans < 0) return CORAL_ERR_ARG;
+    if (!make_cov_table(n_seg, seg_tid, seg_start, seg_end, quality_threshold, read_callback, T, err)) {
+        g_bam_err = err;
+        return CORAL_ERR_ARG;
+    }
+    return decode_range(path, n_threads, 0, 1, &T, handle, false, n_spans, span_beg, span_end);
+}
+
+extern "C" int coral_bam_index_sizes(void *handle, int64_t sizes[4]) {
+    if (!handle || !sizes) return CORAL_ERR_ARG;
+    const IndexPartial &X = ((Decoded *)handle)->idx;
+    if (!X.on) { g_bam_err = "coral_bam_index_sizes: the handle holds no index request"; return CORAL_ERR_ARG; }
+    sizes[0] = (int64_t)X.head_key.size();
+    sizes[1] = (int64_t)X.lin.size();
+    sizes[2] = (int64_t)X.n_mapped.size();
+    sizes[3] = X.n_rec;
+    return CORAL_OK;
+}
+
+extern "C" int coral_bam_index_fill(void *handle, int64_t *head_key, uint64_t *head_voff, uint64_t *lin, int64_t *n_mapped,
+                                    int64_t *n_unmapped, uint64_t scalars[4]) {
+    if (!handle || !scalars) return CORAL_ERR_ARG;
+    const IndexPartial &X = ((Decoded *)handle)->idx;
+    if (!X.on) { g_bam_err = "coral_bam_index_fill: the handle holds no index request"; return CORAL_ERR_ARG; }
+    auto cp = [](auto *dst, const auto &v) { if (!v.empty() && dst) memcpy(dst, v.data(), v.size() * sizeof(v[0])); };
+    cp(head_key, X.head_key); cp(head_voff, X.head_voff); cp(lin, X.lin); cp(n_mapped, X.n_mapped); cp(n_unmapped, X.n_unmapped);
+    scalars[0] = (uint64_t)X.n_no_coor; scalars[1] = X.end_voff; scalars[2] = X.first_sort; scalars[3] = X.last_sort;
+    return CORAL_OK;
 }
 
 extern "C" int coral_bam_coverage_result(void *handle, int32_t n_seg, int64_t *counts) {

@@ -30,7 +30,87 @@
 namespace coral_bam {
 
 
+// A BAI index request (coral_bam_decode_range_idx, coral_bamgpu_index): what one decode of a byte range contributes to the
+// index of the file (SAMv1 §5.2), in a form that partial results of consecutive byte ranges merge into exactly.
+//   heads     one entry per maximal run of file-consecutive records with the same (tid, bin), in file order: key =
+//             tid * 65536 + reg2bin(beg, end) (-1 for a record without coordinates, which only ends the run in front of it) and
+//             the virtual offset of the run's first record.  A run's chunk ends where the next head starts (the start of the
+//             next record in the file), the file's last run at `end_voff`.
+//   lin       per contig (len >> 14) + 1 windows of 16 384 bases: the smallest virtual offset of a record that overlaps the
+//             window (~0: none).
+//   counts    records per contig with / without flag 0x4 (the pseudo-bin 37450), and records without coordinates.
+// A record is indexed as [beg, end) = [max(pos, 0), bam_endpos) (end = beg + 1 without a reference length, as htslib does).
+// The linear index of a contig has the windows its header length gives; of a record that reaches further (which no aligner
+// writes) the windows behind the last one are folded into the last one — the region query clamps its window the same way, so the
+// record is still found (tests/test_bam_index.py::test_record_past_the_contig_end_is_still_found).
+struct IndexPartial {
+    bool on = false;
+    std::vector<int64_t> head_key;
+    std::vector<uint64_t> head_voff;
+    std::vector<int64_t> lin_off;           // n_ref + 1
+    std::vector<uint64_t> lin;
+    std::vector<int64_t> n_mapped, n_unmapped;
+    int64_t n_no_coor = 0, n_rec = 0;
+    uint64_t end_voff = 0;                  // virtual offset just behind the range's last record (bgzf_tell's rule at the end of the file)
+    uint64_t first_sort = 0, last_sort = 0; // (tid, pos) of the range's first and last record as one sortable word
+    bool unsorted = false;
+
+    void init(const std::vector<int32_t> &ref_lens) {
+        on = true;
+        lin_off.assign(1, 0);
+        for (int32_t l : ref_lens) lin_off.push_back(lin_off.back() + ((int64_t)(l > 0 ? l : 0) >> 14) + 1);
+        lin.assign((size_t)lin_off.back(), ~0ull);
+        n_mapped.assign(ref_lens.size(), 0);
+        n_unmapped.assign(ref_lens.size(), 0);
+    }
+    static uint64_t sort_word(int32_t tid, int32_t pos) {      // records without coordinates sort last
+        return tid < 0 ? ~0ull : ((uint64_t)(uint32_t)tid << 32) | (uint32_t)(pos < 0 ? 0 : pos);
+    }
+    static int reg2bin(int64_t beg, int64_t end) {             // SAMv1 §5.3
+        --end;
+        if (beg >> 14 == end >> 14) return (int)(4681 + (beg >> 14));
+        if (beg >> 17 == end >> 17) return (int)(585 + (beg >> 17));
+        if (beg >> 20 == end >> 20) return (int)(73 + (beg >> 20));
+        if (beg >> 23 == end >> 23) return (int)(9 + (beg >> 23));
+        if (beg >> 26 == end >> 26) return (int)(1 + (beg >> 26));
+        return 0;
+    }
+    void add_head(int64_t key, uint64_t voff) {                // heads of consecutive batches / chunks: a run that goes on is ONE run
+        if (!head_key.empty() && head_key.back() == key) return;
+        head_key.push_back(key);
+        head_voff.push_back(voff);
+    }
+    void note_order(uint64_t first, uint64_t last) {           // a batch / record whose records are sorted among themselves
+        if (n_rec == 0) first_sort = first;
+        else if (first < last_sort) unsorted = true;
+        last_sort = last;
+    }
+    void add(int32_t tid, int32_t pos, int32_t end, int32_t flag, uint64_t voff) {      // host pipeline: records in file order
+        const uint64_t sw = sort_word(tid, pos);
+        note_order(sw, sw);
+        ++n_rec;
+        if (tid < 0 || (size_t)tid >= n_mapped.size()) {
+            ++n_no_coor;
+            add_head(-1, voff);
+            return;
+        }
+        const int64_t b = pos < 0 ? 0 : pos, e = end > b ? end : b + 1;
+        add_head((int64_t)tid * 65536 + reg2bin(b, e), voff);
+        ++((flag & 4) ? n_unmapped : n_mapped)[(size_t)tid];
+        const int64_t nw = lin_off[(size_t)tid + 1] - lin_off[(size_t)tid];
+        const int64_t w0 = std::min(b >> 14, nw - 1), w1 = std::min((e - 1) >> 14, nw - 1);
+        uint64_t *l = lin.data() + lin_off[(size_t)tid];
+        for (int64_t w = w0; w <= w1; ++w) l[w] = std::min(l[w], voff);
+    }
+};
+
+// A span of virtual offsets [beg, end) (coral_bam_decode_spans, coral_bamgpu_open_spans): the records that START in it.
+struct Span {
+    uint64_t beg = 0, end = 0;
+};
+
 struct Decoded {
+    IndexPartial idx;                       // BAI index request (empty without one)
     std::vector<int32_t> tid, pos, end, flag, mapq, qlen, has_seq, nm, name_id, n_cigar;
     std::vector<int64_t> cigar_off{0}, sa_off{0};
     std::vector<uint32_t> cigar;

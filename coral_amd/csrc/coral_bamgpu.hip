@@ -20,6 +20,8 @@
 //                   records with non-ACGT bases are gathered whole (k_bam_gather) and handled by the CPU pipeline's own routine.
 //   k_bam_cov_plan / k_bam_cov_count   only with a window-coverage request (coral_bamgpu_coverage): pysam count_coverage with a
 //                   base-quality threshold over the request's segments, read from the batch's SEQ / QUAL before the slot is reused.
+//   k_bam_index / k_bam_index_compact   only with an index request (coral_bamgpu_index): per record the virtual offset, the UCSC bin
+//                   and the linear-index windows of a BAI index, per batch the heads of the runs of equal (tid, bin).
 // Batches (64 MiB first, doubling up to 2.52 GiB inflated, coral_bamgpu_open) are double-buffered: while batch k is parsed, batch k + 1 is inflated
 // and k + 2 is read.
 // A record that straddles two batches is carried in front of the next batch's buffer.
@@ -1101,6 +1103,135 @@ __global__ __launch_bounds__(256) void k_bam_cov_count(const uint8_t *__restrict
 }
 
 // ---------------------------------------------------------------------------------------------
+// K_index: what a batch contributes to the BAI index of the file (coral_bamgpu_index; IndexPartial in coral_bam_common.h)
+// ---------------------------------------------------------------------------------------------
+struct IndexDev {                        // device arrays of the request, carved from the caller's workspace
+    unsigned long long *lin;             // linear index: smallest virtual offset per (contig, 16 384-base window), ~0 = none
+    long long *lin_off;                  // n_ref + 1: first window of every contig
+    unsigned long long *n_mapped, *n_unmapped, *n_no_coor;      // n_ref, n_ref, 1 counters
+    unsigned long long *state;           // [2]: virtual offset of the position a batch ends at (read by the next batch: the
+                                         // start of the record it carries in), alternating
+    int32_t *unsorted;                   // set when a record sorts in front of its predecessor
+    int n_ref;
+};
+
+// virtual offset of byte `rel` of the batch's inflated bytes: the block that holds it (the last one that starts at or in front
+// of it: an empty block starts where its successor does); behind the batch's last byte the block that follows it (bgzf_tell)
+__device__ __forceinline__ unsigned long long batch_voffset(const BlockDesc *__restrict__ desc, const uint32_t *__restrict__ boff, int n_blocks,
+                                                            unsigned long long file_off, unsigned long long comp_bytes, long long rel,
+                                                            long long infl_bytes) {
+    if (rel < infl_bytes) {
+        int a = 0, b = n_blocks;                                   // the last block with dst_off <= rel
+        while (b - a > 1) {
+            const int m = (a + b) >> 1;
+            if ((long long)desc[m].dst_off <= rel) a = m; else b = m;
+        }
+        return ((file_off + boff[a]) << 16) | (unsigned long long)(rel - (long long)desc[a].dst_off);
+    }
+    int a = 0, b = n_blocks;                                       // the first block with dst_off >= rel
+    while (a < b) {
+        const int m = (a + b) >> 1;
+        if ((long long)desc[m].dst_off < rel) a = m + 1; else b = m;
+    }
+    return (a < n_blocks ? file_off + boff[a] : file_off + comp_bytes) << 16;
+}
+
+__device__ __forceinline__ long long index_key(int32_t tid, int32_t pos, int32_t end, int n_ref, long long *beg_out, long long *end_out) {
+    if (tid < 0 || tid >= n_ref) return -1;
+    const long long b = pos < 0 ? 0 : pos, e = (long long)end > b ? (long long)end : b + 1, l = e - 1;
+    *beg_out = b;
+    *end_out = e;
+    int bin = 0;
+    if (b >> 14 == l >> 14) bin = (int)(4681 + (b >> 14));
+    else if (b >> 17 == l >> 17) bin = (int)(585 + (b >> 17));
+    else if (b >> 20 == l >> 20) bin = (int)(73 + (b >> 20));
+    else if (b >> 23 == l >> 23) bin = (int)(9 + (b >> 23));
+    else if (b >> 26 == l >> 26) bin = (int)(1 + (b >> 26));
+    return (long long)tid * 65536 + bin;
+}
+
+__device__ __forceinline__ unsigned long long index_sort_word(int32_t tid, int32_t pos) {
+    return tid < 0 ? ~0ull : ((unsigned long long)(uint32_t)tid << 32) | (uint32_t)(pos < 0 ? 0 : pos);
+}
+
+// One thread per record (one-wave workgroups: the kernel runs beside the next batch's inflate), thread n_rec for the batch's end.
+// Record i: virtual offset of its first byte (a record carried in from the previous batch: where it STARTED, state[parity]),
+// key = tid * 65536 + bin, head[i] = 1 when the key differs from its predecessor's (record 0 always: the host joins a run that
+// goes on across batches), 64-bit atomicMin into every linear-index window it overlaps, the per-contig counters (one atomic per
+// wave when the wave's records are on one contig), and the order check against its predecessor.
+__global__ __launch_bounds__(WAVE) void k_bam_index(const long long *__restrict__ rec_start, long long n_rec, MetaArrays M,
+                                                    const int32_t *__restrict__ end_in, const BlockDesc *__restrict__ desc,
+                                                    const uint32_t *__restrict__ boff, int n_blocks, unsigned long long file_off,
+                                                    unsigned long long comp_bytes, long long infl_bytes, long long carry_pos, int parity,
+                                                    IndexDev X, unsigned long long *__restrict__ voff_out, long long *__restrict__ key_out,
+                                                    long long *__restrict__ head_out) {
+    const int lane = threadIdx.x & 63;
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i == n_rec) {
+        head_out[i] = 0;                                               // the scan's extra slot
+        // where the batch ends: the start of the record that is carried into the next batch (or still the one carried into this
+        // one: a record may span several batches), or the place just behind the batch's last record
+        X.state[parity ^ 1] = carry_pos < CARRY_CAP ? X.state[parity]
+                                                    : batch_voffset(desc, boff, n_blocks, file_off, comp_bytes, carry_pos - CARRY_CAP, infl_bytes);
+    }
+    const bool valid = i < n_rec;
+    int32_t tid = -1, flag = 0;
+    if (valid) {
+        const long long x = rec_start[i];
+        const unsigned long long voff = x < CARRY_CAP ? X.state[parity]
+                                                      : batch_voffset(desc, boff, n_blocks, file_off, comp_bytes, x - CARRY_CAP, infl_bytes);
+        tid = M.tid[i];
+        flag = M.flag[i];
+        const int32_t pos = M.pos[i];
+        long long b = 0, e = 0;
+        const long long key = index_key(tid, pos, end_in[i], X.n_ref, &b, &e);
+        bool head = true;
+        if (i > 0) {
+            long long pb, pe;
+            const int32_t ptid = M.tid[i - 1], ppos = M.pos[i - 1];
+            head = index_key(ptid, ppos, end_in[i - 1], X.n_ref, &pb, &pe) != key;
+            if (index_sort_word(tid, pos) < index_sort_word(ptid, ppos)) *X.unsorted = 1;
+        }
+        voff_out[i] = voff;
+        key_out[i] = key;
+        head_out[i] = head ? 1 : 0;
+        if (key >= 0) {
+            const long long w_first = X.lin_off[tid], nw = X.lin_off[tid + 1] - w_first;
+            const long long w0 = min(b >> 14, nw - 1), w1 = min((e - 1) >> 14, nw - 1);
+            for (long long w = w0; w <= w1; ++w) atomicMin(X.lin + w_first + w, voff);
+        } else {
+            tid = -1;
+        }
+    }
+    // counters
+    const unsigned long long act = __ballot(valid);
+    if (act == 0ull) return;
+    const int32_t t0 = __shfl(tid, (int)__builtin_ctzll(act));
+    if (__ballot(valid && tid != t0) == 0ull) {
+        const unsigned long long unm = __ballot(valid && (flag & 4));
+        if (lane == (int)__builtin_ctzll(act)) {
+            if (t0 < 0) atomicAdd(X.n_no_coor, (unsigned long long)__popcll(act));
+            else {
+                if (act & ~unm) atomicAdd(X.n_mapped + t0, (unsigned long long)__popcll(act & ~unm));
+                if (unm) atomicAdd(X.n_unmapped + t0, (unsigned long long)__popcll(unm));
+            }
+        }
+    } else if (valid) {
+        atomicAdd(tid < 0 ? X.n_no_coor : (flag & 4) ? X.n_unmapped + tid : X.n_mapped + tid, 1ull);
+    }
+}
+
+// the heads, compacted in file order: head_off = exclusive prefix sum of head
+__global__ __launch_bounds__(WAVE) void k_bam_index_compact(long long n_rec, const long long *__restrict__ head, const long long *__restrict__ head_off,
+                                                            const unsigned long long *__restrict__ voff, const long long *__restrict__ key,
+                                                            unsigned long long *__restrict__ voff_out, long long *__restrict__ key_out) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_rec || !head[i]) return;
+    voff_out[head_off[i]] = voff[i];
+    key_out[head_off[i]] = key[i];
+}
+
+// ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
 inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -1111,7 +1242,17 @@ struct BatchInfo {
     uint64_t ubase = 0;              // offset of the batch's first inflated byte in this range's uncompressed stream
     bool has_limit = false;          // the next byte range begins at or in front of this batch's end:
     long long limit_rel = 0;         //   at this offset from the batch's first inflated byte (negative: in an earlier batch)
-    bool last = false;               // nothing follows
+    bool last = false;               // nothing follows (in this span)
+    int span = 0;                    // span decode: which span the batch belongs to, whether it is the span's first batch and
+    bool span_first = false;         //   where in its first block the span's first record starts
+    uint32_t start_off = 0;
+    bool span_tail = false;          // span decode: the batch ends with the span's last own block; what lies behind is only staged
+                                     //   when the parse of this batch says that the span's last record goes on (span_verdict)
+};
+
+struct SpanDef {                     // a span of virtual offsets, taken apart
+    uint64_t first_block = 0, end_block = 0;
+    uint32_t start_off = 0, end_off = 0;
 };
 
 // what a batch leaves for the host-side worker: read names -> ids, SA text -> rows, non-ACGT records -> positions
@@ -1190,6 +1331,19 @@ struct GpuDecoder {
     int cov_threshold = 0, cov_filter_all = 0;
     unsigned long long *cov_counts = nullptr;
     bool cov_set = false;
+    // span decode (coral_bamgpu_open_spans): the spans are decoded one after the other through the same batches
+    bool span_mode = false;
+    std::vector<SpanDef> spans;
+    int cur_span = 0;                         // the span the caller's thread is parsing
+    std::vector<int> span_verdict;            // per span (under m): 0 = not known yet, 1 = its last record has been parsed,
+                                              //   2 = the record in front of its end goes on behind its last own block
+    // index request (coral_bamgpu_index)
+    bool idx_on = false;
+    IndexDev X{};
+    uint32_t *d_boff[2] = {nullptr, nullptr}; // per block of the slot's batch: its file offset relative to the batch's
+    BlockDesc *d_idesc[2] = {nullptr, nullptr};   // the slot's block table and offsets, kept for k_bam_index: the feeder re-stages
+    uint32_t *d_iboff[2] = {nullptr, nullptr};    //   d_desc / d_boff for batch k + 2 while batch k is still being parsed
+    int idx_parity = 0;
     // statistics
     double t_open = 0, seconds = 0, host_seconds = 0;
     int64_t fixups = 0, n_batches = 0, na_records = 0;
@@ -1268,6 +1422,7 @@ void feeder_main(GpuDecoder *G) {
     long long own_bytes = -1;                 // known once the first block of the next range has been seen
     size_t overhang_left = OVERHANG_BLOCKS;
     int kb = 0, chunk_no = 0;
+    const int n_spans = G->span_mode ? (int)G->spans.size() : 1;
     auto fail = [&](const std::string &msg) {
         std::lock_guard<std::mutex> lk(G->m);
         G->feeder_error = msg;
@@ -1275,110 +1430,146 @@ void feeder_main(GpuDecoder *G) {
         G->cv.notify_all();
     };
     std::vector<BlockDesc> desc;
-    std::vector<uint32_t> crcs;
-    for (;;) {
-        const int slot = kb & 1;
-        if (at >= G->f.size || (own_bytes >= 0 && overhang_left == 0)) break;
-        {   // the slot's device buffers are free once the inflate of batch kb - 2 has run
-            std::unique_lock<std::mutex> lk(G->m);
-            G->cv.wait(lk, [&] { return G->stop || G->inflate_launched >= kb - 1; });
-            if (G->stop) return;
+    std::vector<uint32_t> crcs, boffs;
+    for (int sp = 0; sp < n_spans; ++sp) {
+        const SpanDef S = G->span_mode ? G->spans[(size_t)sp] : SpanDef();
+        bool span_first = G->span_mode;
+        if (G->span_mode) {
+            at = S.first_block;
+            ubase = 0;
+            own_bytes = -1;
+            overhang_left = OVERHANG_BLOCKS;
         }
-        if (kb >= 2 && (hipEventSynchronize(G->ev_infl[slot]) != hipSuccess || hipEventSynchronize(G->ev_crc[slot]) != hipSuccess))
-            return fail("hipEventSynchronize failed in the feeder");
-        // the first batches are small so that the GPU has something to inflate almost at once; then they double up to the cap
-        const uint64_t infl_cap = std::min<uint64_t>(G->infl_cap, G->first_batch << std::min(kb, 20));
-        const uint64_t comp_cap = std::min<uint64_t>(G->comp_cap, std::max<uint64_t>(infl_cap / 2, 1u << 20));
-        BatchInfo bi;
-        bi.file_off = at;
-        bi.ubase = ubase;
-        desc.clear();
-        crcs.clear();
-        uint64_t comp = 0, infl = 0;          // bytes of the batch so far
-        bool full = false;
-        while (!full && at < G->f.size) {
-            // one chunk: read -> walk its whole BGZF blocks -> send them behind what the batch already has
-            const int cs = chunk_no % N_STAGE;
-            if (chunk_no >= N_STAGE && hipEventSynchronize(G->ev_stage[cs]) != hipSuccess) return fail("hipEventSynchronize failed in the feeder");
-            const size_t want = (size_t)std::min<uint64_t>(std::min<uint64_t>(STAGE_BYTES, comp_cap - comp), G->f.size - at);
-            if (want < 28) break;
-            uint8_t *data = G->h_stage[cs];
-            const auto t0 = std::chrono::steady_clock::now();
-            if (!read_range(G->f.fd, at, want, data, G->n_threads)) return fail("reading the BAM file failed");
-            G->t_read += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-            size_t p = 0;
-            while (p < want) {
-                if (desc.size() >= G->max_blocks) { full = true; break; }
-                Block b;
-                if (!bgzf_header(data + p, want - p, b)) {
-                    if (want - p >= 65536 + 26 || at + want >= G->f.size) return fail("not a BGZF block");
-                    if (want < STAGE_BYTES) full = true;           // the block does not fit what is left of the batch
-                    break;                                         // the block continues behind what was read
-                }
-                if (infl + b.isize > infl_cap) { full = true; break; }
-                const bool owned = at + p < G->byte_hi;
-                if (!owned) {
-                    if (own_bytes < 0) own_bytes = (long long)(ubase + infl);
-                    if (overhang_left == 0) { full = true; break; }
-                    --overhang_left;
-                }
-                BlockDesc d;
-                d.src_off = (uint32_t)(comp + p + b.hdr);
-                d.src_len = b.csize - b.hdr - 8;
-                d.dst_off = (uint32_t)infl;
-                d.isize = b.isize;
-                desc.push_back(d);
-                crcs.push_back(rd32(data + p + b.csize - 8));
-                infl += b.isize;
-                p += b.csize;
-                if (owned) { G->D.compressed_bytes += b.csize; G->D.uncompressed_bytes += b.isize; ++G->D.n_blocks; }
+        bool tail_staged = false, overhang_ok = false;
+        for (;;) {
+            const int slot = kb & 1;
+            if (at >= G->f.size || (own_bytes >= 0 && overhang_left == 0)) break;
+            if (tail_staged && !overhang_ok) {
+                // the span's own blocks are on their way.  Its end is a record boundary of the index, so as a rule its last record
+                // ends there too and nothing behind is read; only when the parse finds that record going on is the overhang staged
+                std::unique_lock<std::mutex> lk(G->m);
+                G->cv.wait(lk, [&] { return G->stop || G->span_verdict[(size_t)sp] != 0; });
+                if (G->stop) return;
+                if (G->span_verdict[(size_t)sp] == 1) break;
+                overhang_ok = true;
             }
-            if (p == 0) {
-                if (desc.empty()) return fail("a BGZF block does not fit the batch buffers");
-                break;
+            {   // the slot's device buffers are free once the inflate of batch kb - 2 has run
+                std::unique_lock<std::mutex> lk(G->m);
+                G->cv.wait(lk, [&] { return G->stop || G->inflate_launched >= kb - 1; });
+                if (G->stop) return;
             }
-            if (hipMemcpyAsync(G->d_comp[slot] + comp, data, p, hipMemcpyHostToDevice, G->s_copy) != hipSuccess ||
-                hipEventRecord(G->ev_stage[cs], G->s_copy) != hipSuccess)
-                return fail("host-to-device copy of compressed bytes failed");
-            ++chunk_no;
-            comp += p;
-            at += p;
-            if (comp + 65536 + 26 > comp_cap) full = true;
+            if (kb >= 2 && (hipEventSynchronize(G->ev_infl[slot]) != hipSuccess || hipEventSynchronize(G->ev_crc[slot]) != hipSuccess))
+                return fail("hipEventSynchronize failed in the feeder");
+            // the first batches are small so that the GPU has something to inflate almost at once; then they double up to the cap
+            const uint64_t infl_cap = std::min<uint64_t>(G->infl_cap, G->first_batch << std::min(kb, 20));
+            const uint64_t comp_cap = std::min<uint64_t>(G->comp_cap, std::max<uint64_t>(infl_cap / 2, 1u << 20));
+            BatchInfo bi;
+            bi.file_off = at;
+            bi.ubase = ubase;
+            bi.span = sp;
+            bi.span_first = span_first;
+            bi.start_off = S.start_off;
+            span_first = false;
+            desc.clear();
+            crcs.clear();
+            boffs.clear();
+            uint64_t comp = 0, infl = 0;          // bytes of the batch so far
+            bool full = false;
+            while (!full && at < G->f.size) {
+                // one chunk: read -> walk its whole BGZF blocks -> send them behind what the batch already has
+                const int cs = chunk_no % N_STAGE;
+                if (chunk_no >= N_STAGE && hipEventSynchronize(G->ev_stage[cs]) != hipSuccess) return fail("hipEventSynchronize failed in the feeder");
+                const size_t want = (size_t)std::min<uint64_t>(std::min<uint64_t>(STAGE_BYTES, comp_cap - comp), G->f.size - at);
+                if (want < 28) break;
+                uint8_t *data = G->h_stage[cs];
+                const auto t0 = std::chrono::steady_clock::now();
+                if (!read_range(G->f.fd, at, want, data, G->n_threads)) return fail("reading the BAM file failed");
+                G->t_read += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+                size_t p = 0;
+                while (p < want) {
+                    if (desc.size() >= G->max_blocks) { full = true; break; }
+                    Block b;
+                    if (!bgzf_header(data + p, want - p, b)) {
+                        if (want - p >= 65536 + 26 || at + want >= G->f.size) return fail("not a BGZF block");
+                        if (want < STAGE_BYTES) full = true;           // the block does not fit what is left of the batch
+                        break;                                         // the block continues behind what was read
+                    }
+                    if (infl + b.isize > infl_cap) { full = true; break; }
+                    if (G->span_mode && at + p == S.end_block && own_bytes < 0) own_bytes = (long long)(ubase + infl) + S.end_off;
+                    const bool owned = G->span_mode ? (at + p < S.end_block || (at + p == S.end_block && S.end_off > 0)) : at + p < G->byte_hi;
+                    if (!owned && G->span_mode && !overhang_ok && !desc.empty()) { tail_staged = true; full = true; break; }
+                    // (the batch in front filled up exactly with the span's last own block: this one block alone is the tail batch
+                    // the parse gives its verdict on)
+                    const bool lone_tail = !owned && G->span_mode && !overhang_ok;
+                    if (!owned) {
+                        if (own_bytes < 0) own_bytes = (long long)(ubase + infl);
+                        if (overhang_left == 0) { full = true; break; }
+                        --overhang_left;
+                    }
+                    BlockDesc d;
+                    d.src_off = (uint32_t)(comp + p + b.hdr);
+                    d.src_len = b.csize - b.hdr - 8;
+                    d.dst_off = (uint32_t)infl;
+                    d.isize = b.isize;
+                    desc.push_back(d);
+                    crcs.push_back(rd32(data + p + b.csize - 8));
+                    boffs.push_back((uint32_t)(comp + p));
+                    infl += b.isize;
+                    p += b.csize;
+                    // (of a span every block that is read counts, its overhang included)
+                    if (lone_tail) { tail_staged = true; full = true; }
+                    if (owned || G->span_mode) { G->D.compressed_bytes += b.csize; G->D.uncompressed_bytes += b.isize; ++G->D.n_blocks; }
+                }
+                if (p == 0) {
+                    if (desc.empty()) return fail("a BGZF block does not fit the batch buffers");
+                    break;
+                }
+                if (hipMemcpyAsync(G->d_comp[slot] + comp, data, p, hipMemcpyHostToDevice, G->s_copy) != hipSuccess ||
+                    hipEventRecord(G->ev_stage[cs], G->s_copy) != hipSuccess)
+                    return fail("host-to-device copy of compressed bytes failed");
+                ++chunk_no;
+                comp += p;
+                at += p;
+                if (comp + 65536 + 26 > comp_cap) full = true;
+            }
+            if (desc.empty()) break;
+            bi.n_blocks = (int)desc.size();
+            bi.comp_bytes = comp;
+            bi.infl_bytes = infl;
+            if (own_bytes >= 0) {
+                bi.has_limit = true;
+                bi.limit_rel = own_bytes - (long long)ubase;
+            }
+            ubase += infl;
+            bi.last = at >= G->f.size || (own_bytes >= 0 && overhang_left == 0);
+            bi.span_tail = tail_staged && !overhang_ok;
+            // the block table and the trailer CRCs go through their own pinned buffer (one per batch slot; host and device copies are
+            // free again once the slot's inflate + checksum kernels have run: see the wait at the top of the round)
+            memcpy(G->h_desc[slot], desc.data(), desc.size() * sizeof(BlockDesc));
+            uint32_t *h_crc = reinterpret_cast<uint32_t *>(G->h_desc[slot] + G->max_blocks);
+            memcpy(h_crc, crcs.data(), crcs.size() * 4);
+            if (hipMemcpyAsync(G->d_desc[slot], G->h_desc[slot], desc.size() * sizeof(BlockDesc), hipMemcpyHostToDevice, G->s_copy) != hipSuccess ||
+                hipMemcpyAsync(G->d_crc[slot], h_crc, crcs.size() * 4, hipMemcpyHostToDevice, G->s_copy) != hipSuccess ||
+                (G->idx_on && (memcpy(h_crc + G->max_blocks, boffs.data(), boffs.size() * 4),
+                               hipMemcpyAsync(G->d_boff[slot], h_crc + G->max_blocks, boffs.size() * 4, hipMemcpyHostToDevice, G->s_copy) != hipSuccess)) ||
+                hipEventRecord(G->ev_h2d[slot], G->s_copy) != hipSuccess)
+                return fail("host-to-device copy of a block table failed");
+            {
+                std::lock_guard<std::mutex> lk(G->m);
+                G->staged.push_back(bi);
+            }
+            G->cv.notify_all();
+            // ... and its inflate is enqueued from here as well, as soon as the batch that used this slot's inflated buffer before
+            // (kb - 2) has been parsed: the GPU never waits for the caller's thread to come round
+            {
+                std::unique_lock<std::mutex> lk(G->m);
+                G->cv.wait(lk, [&] { return G->stop || G->emitted >= kb - 1; });
+                if (G->stop) return;
+            }
+            if (!launch_inflate(G, kb, bi)) return fail(G->launch_error);
+            ++kb;
+            if (bi.last) break;
         }
-        if (desc.empty()) break;
-        bi.n_blocks = (int)desc.size();
-        bi.comp_bytes = comp;
-        bi.infl_bytes = infl;
-        if (own_bytes >= 0) {
-            bi.has_limit = true;
-            bi.limit_rel = own_bytes - (long long)ubase;
-        }
-        ubase += infl;
-        bi.last = at >= G->f.size || (own_bytes >= 0 && overhang_left == 0);
-        // the block table and the trailer CRCs go through their own pinned buffer (one per batch slot; host and device copies are
-        // free again once the slot's inflate + checksum kernels have run: see the wait at the top of the round)
-        memcpy(G->h_desc[slot], desc.data(), desc.size() * sizeof(BlockDesc));
-        uint32_t *h_crc = reinterpret_cast<uint32_t *>(G->h_desc[slot] + G->max_blocks);
-        memcpy(h_crc, crcs.data(), crcs.size() * 4);
-        if (hipMemcpyAsync(G->d_desc[slot], G->h_desc[slot], desc.size() * sizeof(BlockDesc), hipMemcpyHostToDevice, G->s_copy) != hipSuccess ||
-            hipMemcpyAsync(G->d_crc[slot], h_crc, crcs.size() * 4, hipMemcpyHostToDevice, G->s_copy) != hipSuccess ||
-            hipEventRecord(G->ev_h2d[slot], G->s_copy) != hipSuccess)
-            return fail("host-to-device copy of a block table failed");
-        {
-            std::lock_guard<std::mutex> lk(G->m);
-            G->staged.push_back(bi);
-        }
-        G->cv.notify_all();
-        // ... and its inflate is enqueued from here as well, as soon as the batch that used this slot's inflated buffer before
-        // (kb - 2) has been parsed: the GPU never waits for the caller's thread to come round
-        {
-            std::unique_lock<std::mutex> lk(G->m);
-            G->cv.wait(lk, [&] { return G->stop || G->emitted >= kb - 1; });
-            if (G->stop) return;
-        }
-        if (!launch_inflate(G, kb, bi)) return fail(G->launch_error);
-        ++kb;
-        if (bi.last) break;
     }
     {
         std::lock_guard<std::mutex> lk(G->m);
@@ -1487,6 +1678,22 @@ bool carve(GpuDecoder *G, void *ws, size_t bytes) {
     G->names_cap = G->sa_cap = (size_t)CARRY_CAP + G->infl_cap;
     G->d_names = (uint8_t *)take(G->names_cap);
     G->d_sa_text = (uint8_t *)take(G->sa_cap);
+    if (G->idx_on) {                           // the index request's own arrays (everything per record re-uses the batch's scratch)
+        const size_t n_ref = G->D.ref_lens.size();
+        for (int i = 0; i < 2; ++i) {
+            G->d_boff[i] = (uint32_t *)take(G->max_blocks * 4);
+            G->d_iboff[i] = (uint32_t *)take(G->max_blocks * 4);
+            G->d_idesc[i] = (BlockDesc *)take(G->max_blocks * sizeof(BlockDesc));
+        }
+        G->X.lin = (unsigned long long *)take(G->D.idx.lin.size() * 8);
+        G->X.lin_off = (long long *)take((n_ref + 1) * 8);
+        G->X.n_mapped = (unsigned long long *)take(n_ref * 8);
+        G->X.n_unmapped = (unsigned long long *)take(n_ref * 8);
+        G->X.n_no_coor = (unsigned long long *)take(8);
+        G->X.state = (unsigned long long *)take(16);
+        G->X.unsorted = (int32_t *)take(4);
+        G->X.n_ref = (int)n_ref;
+    }
     if (ws && used > bytes) return false;
     G->ws_bytes = used;
     return true;
@@ -1505,6 +1712,10 @@ bool launch_inflate(GpuDecoder *G, int kb, const BatchInfo &bi) {
     const int slot = kb & 1;
     HIP_LAUNCH_OK(hipStreamWaitEvent(G->s_infl, G->ev_h2d[slot], 0), "hipStreamWaitEvent");
     if (kb >= 2) HIP_LAUNCH_OK(hipStreamWaitEvent(G->s_infl, G->ev_parsed[slot], 0), "hipStreamWaitEvent");     // the buffer's previous batch has been parsed
+    if (G->idx_on) {    // (behind ev_parsed of batch kb - 2, whose k_bam_index read the copies; in front of ev_infl, which this batch's parse waits for)
+        HIP_LAUNCH_OK(hipMemcpyAsync(G->d_idesc[slot], G->d_desc[slot], (size_t)bi.n_blocks * sizeof(BlockDesc), hipMemcpyDeviceToDevice, G->s_infl), "hipMemcpyAsync");
+        HIP_LAUNCH_OK(hipMemcpyAsync(G->d_iboff[slot], G->d_boff[slot], (size_t)bi.n_blocks * 4, hipMemcpyDeviceToDevice, G->s_infl), "hipMemcpyAsync");
+    }
     const int grid = (bi.n_blocks + INFL_WAVES - 1) / INFL_WAVES;
     hipLaunchKernelGGL(k_bgzf_inflate<0>, dim3(grid), dim3(INFL_WAVES * WAVE), 0, G->s_infl, G->d_comp[slot], G->d_desc[slot], bi.n_blocks,
                        G->d_infl[slot] + CARRY_CAP, G->d_status[slot]);
@@ -1555,8 +1766,8 @@ const char *rec_error_text(int e) {
 // ---------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------
-extern "C" int coral_bamgpu_open(const char *path, int32_t n_threads, int32_t rank, int32_t world, int64_t batch_bytes, void **handle,
-                                 int64_t *workspace_bytes) {
+static int open_decoder(const char *path, int32_t n_threads, int32_t rank, int32_t world, int64_t batch_bytes, void **handle,
+                        int64_t *workspace_bytes, int32_t n_spans, const uint64_t *span_beg, const uint64_t *span_end) {
     if (!path || !handle || !workspace_bytes || world < 1 || rank < 0 || rank >= world) return CORAL_ERR_ARG;
     std::unique_ptr<GpuDecoder> G(new GpuDecoder());
     G->t_start = std::chrono::steady_clock::now();
@@ -1574,6 +1785,26 @@ extern "C" int coral_bamgpu_open(const char *path, int32_t n_threads, int32_t ra
     if (rank > 0 && !find_block(G->f, G->byte_lo, &G->first_block)) G->first_block = G->f.size;
     if (G->first_block >= G->byte_hi) G->first_block = G->f.size;          // no block starts in this range: nothing to do
     G->searching = rank > 0;
+    uint64_t span_bytes = 0;
+    if (n_spans >= 0) {                        // the records that start inside the spans, nothing else
+        G->span_mode = true;
+        G->last_rank = false;
+        for (int32_t k = 0; k < n_spans; ++k) {
+            SpanDef S;
+            S.first_block = span_beg[k] >> 16; S.start_off = (uint32_t)(span_beg[k] & 0xffff);
+            S.end_block = span_end[k] >> 16; S.end_off = (uint32_t)(span_end[k] & 0xffff);
+            if (span_end[k] <= span_beg[k] || S.first_block >= G->f.size || S.end_block > G->f.size || (k > 0 && span_beg[k] < span_end[k - 1])) {
+                set_error("coral_bamgpu_open_spans: the spans must be sorted, disjoint, non-empty and inside the file");
+                return CORAL_ERR_ARG;
+            }
+            span_bytes = std::max(span_bytes, S.end_block - S.first_block + 65536 + (uint64_t)OVERHANG_BLOCKS * 65536 / 4);
+            G->spans.push_back(S);
+        }
+        G->span_verdict.assign(G->spans.size(), 0);
+        G->first_block = G->byte_lo = 0;
+        G->byte_hi = span_bytes;
+        if (n_spans == 0) G->first_block = G->f.size;
+    }
     // batch size: at most `batch_bytes` inflated, no more than the range can need.  Default 2.52 GiB = 6 x 6 912 BGZF blocks of
     // 65 280 bytes (htslib's block size): the inflate kernel keeps 27 one-wave workgroups per CU x 256 CUs resident, blocks of
     // equal size finish in rounds, and a batch that is a whole number of rounds has no part-filled last round; bigger batches
@@ -1600,6 +1831,56 @@ extern "C" int coral_bamgpu_open(const char *path, int32_t n_threads, int32_t ra
     return CORAL_OK;
 }
 
+extern "C" int coral_bamgpu_open(const char *path, int32_t n_threads, int32_t rank, int32_t world, int64_t batch_bytes, void **handle,
+                                 int64_t *workspace_bytes) {
+    return open_decoder(path, n_threads, rank, world, batch_bytes, handle, workspace_bytes, -1, nullptr, nullptr);
+}
+
+// coral_bamgpu_open for the records that start inside n_spans sorted, disjoint spans of virtual offsets (a BAI region query):
+// only the spans' BGZF blocks (and what their last records straddle into) are read, uploaded and inflated; the spans go through
+// the same batches one after the other, and every other call is the same as behind coral_bamgpu_open.
+extern "C" int coral_bamgpu_open_spans(const char *path, int32_t n_threads, int32_t n_spans, const uint64_t *span_beg, const uint64_t *span_end,
+                                       int64_t batch_bytes, void **handle, int64_t *workspace_bytes) {
+    if (n_spans < 0 || (n_spans > 0 && (!span_beg || !span_end))) return CORAL_ERR_ARG;
+    return open_decoder(path, n_threads, 0, 1, batch_bytes, handle, workspace_bytes, n_spans, span_beg, span_end);
+}
+
+// Index request: after open (not open_spans), before start and before the workspace is allocated: *workspace_bytes is the new
+// size (the request's block offsets, linear index and counters).  Per batch k_bam_index + one scan + k_bam_index_compact.
+extern "C" int coral_bamgpu_index(void *handle, int64_t *workspace_bytes) {
+    GpuDecoder *G = (GpuDecoder *)handle;
+    if (!G || !workspace_bytes) return CORAL_ERR_ARG;
+    if (G->feeder.joinable() || G->idx_on || G->span_mode) { set_error("coral_bamgpu_index: call it once, after open and before start, not on a span decode"); return CORAL_ERR_ARG; }
+    G->idx_on = true;
+    G->D.idx.init(G->D.ref_lens);
+    carve(G, nullptr, 0);
+    *workspace_bytes = (int64_t)G->ws_bytes;
+    return CORAL_OK;
+}
+
+// The request's result, once every batch has been emitted: waits for `stream`, takes the linear index and the counters from the
+// device and leaves the partial index in the host-side result (coral_bamgpu_host -> coral_bam_index_sizes / _fill).
+extern "C" int coral_bamgpu_index_result(void *handle, void *stream_) {
+    GpuDecoder *G = (GpuDecoder *)handle;
+    if (!G || !G->idx_on) return CORAL_ERR_ARG;
+    if (!G->finished || G->have_cur) { set_error("coral_bamgpu_index_result: the decode is not finished"); return CORAL_ERR_ARG; }
+    IndexPartial &P = G->D.idx;
+    const size_t n_ref = P.n_mapped.size();
+    unsigned long long state[2] = {0, 0}, no_coor = 0;
+    int32_t unsorted = 0;
+    auto get = [](void *dst, const void *src, size_t bytes) { return bytes == 0 || hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) == hipSuccess; };
+    if (hipStreamSynchronize((hipStream_t)stream_) != hipSuccess || !get(P.lin.data(), G->X.lin, P.lin.size() * 8) ||
+        !get(P.n_mapped.data(), G->X.n_mapped, n_ref * 8) || !get(P.n_unmapped.data(), G->X.n_unmapped, n_ref * 8) ||
+        !get(&no_coor, G->X.n_no_coor, 8) || !get(state, G->X.state, 16) || !get(&unsorted, G->X.unsorted, 4)) {
+        set_error("coral_bamgpu_index_result: copy of the index arrays failed");
+        return CORAL_ERR_HIP;
+    }
+    if (unsorted || P.unsorted) { set_error("the records are not in coordinate order: no index can be built"); return CORAL_ERR_FORMAT; }
+    P.n_no_coor = (int64_t)no_coor;
+    P.end_voff = state[G->idx_parity];
+    return CORAL_OK;
+}
+
 extern "C" int coral_bamgpu_start(void *handle, void *workspace, int64_t workspace_bytes) {
     GpuDecoder *G = (GpuDecoder *)handle;
     if (!G || !workspace || workspace_bytes < (int64_t)G->ws_bytes || (((uintptr_t)workspace) & 255)) return CORAL_ERR_ARG;
@@ -1616,7 +1897,7 @@ extern "C" int coral_bamgpu_start(void *handle, void *workspace, int64_t workspa
         if ((e = hipEventCreateWithFlags(&G->ev_stage[i], hipEventDisableTiming)) != hipSuccess) return bad("hipEventCreate", e);
     }
     for (int i = 0; i < 2; ++i) {
-        if ((e = hipHostMalloc((void **)&G->h_desc[i], up256(G->max_blocks * (sizeof(BlockDesc) + 4)), hipHostMallocDefault)) != hipSuccess) return bad("hipHostMalloc", e);
+        if ((e = hipHostMalloc((void **)&G->h_desc[i], up256(G->max_blocks * (sizeof(BlockDesc) + 8)), hipHostMallocDefault)) != hipSuccess) return bad("hipHostMalloc", e);
         if ((e = hipEventCreateWithFlags(&G->ev_h2d[i], hipEventDisableTiming)) != hipSuccess) return bad("hipEventCreate", e);
         if ((e = hipEventCreateWithFlags(&G->ev_infl[i], hipEventDisableTiming)) != hipSuccess) return bad("hipEventCreate", e);
         if ((e = hipEventCreateWithFlags(&G->ev_crc[i], hipEventDisableTiming)) != hipSuccess) return bad("hipEventCreate", e);
@@ -1632,6 +1913,16 @@ extern "C" int coral_bamgpu_start(void *handle, void *workspace, int64_t workspa
     }
     if ((e = hipStreamCreateWithFlags(&G->s_crc, hipStreamNonBlocking)) != hipSuccess) return bad("hipStreamCreate", e);
     G->t_alloc = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_alloc0).count();
+    if (G->idx_on) {
+        const size_t n_ref = G->D.ref_lens.size();
+        // with nothing in front of the first record (rank 0) the first batch's end state is never read; a later rank's first
+        // record is found by search and must start inside its batch (checked in coral_bamgpu_next)
+        if ((e = hipMemset(G->X.lin, 0xff, G->D.idx.lin.size() * 8)) != hipSuccess || (e = hipMemset(G->X.n_mapped, 0, n_ref * 8)) != hipSuccess ||
+            (e = hipMemset(G->X.n_unmapped, 0, n_ref * 8)) != hipSuccess || (e = hipMemset(G->X.n_no_coor, 0, 8)) != hipSuccess ||
+            (e = hipMemset(G->X.state, 0, 16)) != hipSuccess || (e = hipMemset(G->X.unsorted, 0, 4)) != hipSuccess ||
+            (e = hipMemcpy(G->X.lin_off, G->D.idx.lin_off.data(), (n_ref + 1) * 8, hipMemcpyHostToDevice)) != hipSuccess)
+            return bad("index request set-up", e);
+    }
     G->feeder = std::thread(feeder_main, G);
     G->worker = std::thread(worker_main, G);
     return CORAL_OK;
@@ -1651,19 +1942,47 @@ extern "C" int coral_bamgpu_next(void *handle, int64_t out[4], void *stream_) {
     };
     if (G->finished) return CORAL_OK;
     BatchInfo bi;
-    if (!wait_staged(G, G->k, &bi)) {
-        if (!G->error.empty()) return fail(CORAL_ERR_FORMAT);
-        if (G->carry_len > 0 && !G->searching) { G->error = G->last_rank ? "truncated record at the end of the file" : "a record straddles further than the supported overhang"; return fail(CORAL_ERR_FORMAT); }
-        G->finished = true;
-        return CORAL_OK;
+    for (;;) {
+        if (!wait_staged(G, G->k, &bi)) {
+            if (!G->error.empty()) return fail(CORAL_ERR_FORMAT);
+            if (G->carry_len > 0 && !G->searching) { G->error = G->last_rank ? "truncated record at the end of the file" : "a record straddles further than the supported overhang"; return fail(CORAL_ERR_FORMAT); }
+            G->finished = true;
+            return CORAL_OK;
+        }
+        {   // the feeder enqueues the inflate of a batch right after staging it
+            const int kw = G->k;
+            std::unique_lock<std::mutex> lk(G->m);
+            G->cv.wait(lk, [&] { return G->inflate_launched > kw || !G->feeder_error.empty(); });
+            if (G->inflate_launched <= kw) { G->error = G->feeder_error; return fail(CORAL_ERR_HIP); }
+        }
+        if (!G->span_mode || bi.span >= G->cur_span) break;
+        // a batch of overhang blocks behind a span whose last record has been seen already: nothing to parse, the slot is free
+        // again once its inflate has run
+        const int sl = G->k & 1;
+        if (hipStreamWaitEvent(stream, G->ev_infl[sl], 0) != hipSuccess || hipEventRecord(G->ev_parsed[sl], stream) != hipSuccess) {
+            G->error = "hipEventRecord failed";
+            return fail(CORAL_ERR_HIP);
+        }
+        {
+            std::lock_guard<std::mutex> lk(G->m);
+            ++G->emitted;
+        }
+        G->cv.notify_all();
+        ++G->k;
+    }
+    if (G->span_mode) {
+        if (bi.span > G->cur_span) {             // the span in front ran out of blocks without reaching its end
+            if (G->carry_len > 0) { G->error = "a record straddles further than the supported overhang"; return fail(CORAL_ERR_FORMAT); }
+            G->cur_span = bi.span;
+        }
+        if (bi.span_first) {                     // the span's first record: at a known place, nothing carried, nothing searched
+            G->known_start = CARRY_CAP + (long long)bi.start_off;
+            G->carry_len = 0;
+            G->searching = false;
+        }
     }
     const int kb = G->k, slot = kb & 1;
     uint8_t *buf = G->d_infl[slot];
-    {   // the feeder enqueues the inflate of a batch right after staging it
-        std::unique_lock<std::mutex> lk(G->m);
-        G->cv.wait(lk, [&] { return G->inflate_launched > kb || !G->feeder_error.empty(); });
-        if (G->inflate_launched <= kb) { G->error = G->feeder_error; return fail(CORAL_ERR_HIP); }
-    }
     // this batch's inflate must be complete before the parse kernels read its bytes
     if (hipStreamWaitEvent(stream, G->ev_infl[slot], 0) != hipSuccess) { G->error = "hipStreamWaitEvent failed"; return fail(CORAL_ERR_HIP); }
     const long long data_end = CARRY_CAP + (long long)bi.infl_bytes;
@@ -1713,6 +2032,11 @@ extern "C" int coral_bamgpu_next(void *handle, int64_t out[4], void *stream_) {
         still_searching = !bi.last;
     }
     const long long n_rec = res[0], carry_pos = res[1];
+    if (G->idx_on && G->searching && n_rec > 0 && res[5] < CARRY_CAP) {
+        // (a byte range that found no record start in its first batch and finds one in the bytes kept from it)
+        G->error = "index request: the first record of the byte range does not start in the batch it was found in";
+        return fail(CORAL_ERR_FORMAT);
+    }
     G->cur_carry_pos = carry_pos < data_end ? carry_pos : data_end;
     G->fixups += res[4];
     if (n_rec > (long long)G->rec_cap) { G->error = "more records in a batch than its workspace holds"; return fail(CORAL_ERR_FORMAT); }
@@ -1748,9 +2072,22 @@ extern "C" int coral_bamgpu_next(void *handle, int64_t out[4], void *stream_) {
     }
     // what the next batch starts with
     const bool done = res[2] != 0;
-    if (done) {
-        G->finished = true;
+    // (a span decode goes on with the next span)
+    auto verdict = [&](int v) {
+        if (!G->span_mode) return;
+        {
+            std::lock_guard<std::mutex> lk(G->m);
+            if (G->span_verdict[(size_t)bi.span] == 0) G->span_verdict[(size_t)bi.span] = v;
+        }
+        G->cv.notify_all();
+    };
+    auto range_done = [&]() {
         G->carry_len = 0;
+        verdict(1);
+        if (G->span_mode && G->cur_span + 1 < (int)G->spans.size()) ++G->cur_span; else G->finished = true;
+    };
+    if (done) {
+        range_done();
     } else if (carry_pos < data_end) {
         G->carry_len = data_end - carry_pos;
         if (G->carry_len > CARRY_CAP) { G->error = "a record larger than 64 MiB straddles two batches"; return fail(CORAL_ERR_FORMAT); }
@@ -1761,8 +2098,9 @@ extern "C" int coral_bamgpu_next(void *handle, int64_t out[4], void *stream_) {
     }
     if (bi.last && !done) {
         if (G->carry_len > 0) { G->error = G->last_rank ? "truncated record at the end of the file" : "a record straddles further than the supported overhang"; return fail(CORAL_ERR_FORMAT); }
-        G->finished = true;
+        range_done();
     }
+    if (bi.span_tail && !done) verdict(2);       // the feeder stages what lies behind the span's own blocks
     G->have_cur = true;
     ++G->n_batches;
     out[0] = n_rec;
@@ -1827,6 +2165,10 @@ extern "C" int coral_bamgpu_emit(void *handle, uint32_t *cigar_dst, int64_t *cig
         if (!ok || hipStreamSynchronize(stream) != hipSuccess) return fail(CORAL_ERR_HIP, std::string("copy of the batch's host fields failed: ") + hipGetErrorString(hipGetLastError()));
         G->t_wait_gpu += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_gpu0).count();
         for (long long i = 0; i < n; ++i) has_seq[i] = has_seq[i] > 0 ? 1 : 0;       // (arrived as l_seq)
+        if (G->idx_on) {                          // the batch's first record against the last one of the batch in front (inside a batch: k_bam_index)
+            D.idx.note_order(IndexPartial::sort_word(tid[0], pos[0]), IndexPartial::sort_word(tid[n - 1], pos[n - 1]));
+            D.idx.n_rec += n;
+        }
         if (na_count > 0) {
             // the records with a non-ACGT code, whole, in one gather + one copy (the offset arrays of the scans are free by now)
             J.na_list.resize((size_t)na_count);
@@ -1882,6 +2224,33 @@ extern "C" int coral_bamgpu_emit(void *handle, uint32_t *cigar_dst, int64_t *cig
         hipLaunchKernelGGL(k_bam_cov_count, dim3(blocks), dim3(256), 0, stream, buf, n, G->M, G->cov, G->cov_threshold, item_off, G->cov_counts);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return fail(CORAL_ERR_HIP, std::string("window coverage launch failed: ") + hipGetErrorString(e));
+    }
+    if (G->idx_on) {
+        // the batch's part of the BAI index, behind the coverage kernels on the same stream: every per-record array of the parse
+        // is free by now except the fixed fields and the end positions (the next batch's k_bam_meta comes behind on this stream)
+        unsigned long long *voff = (unsigned long long *)G->d_cig_off, *out_voff = (unsigned long long *)G->M.sa_src;
+        long long *key = G->M.pad_ops, *head = G->d_name_off, *head_off = G->d_sa_off, *out_key = G->M.cig_src;
+        hipLaunchKernelGGL(k_bam_index, dim3((unsigned)((n + 1 + WAVE - 1) / WAVE)), dim3(WAVE), 0, stream, G->d_rec_start, n, G->M, G->d_end,
+                           G->d_idesc[slot], G->d_iboff[slot], G->cur.n_blocks, (unsigned long long)G->cur.file_off, (unsigned long long)G->cur.comp_bytes,
+                           (long long)G->cur.infl_bytes, G->cur_carry_pos, G->idx_parity, G->X, voff, key, head);
+        G->idx_parity ^= 1;
+        long long n_heads = 0;
+        if (n > 0) {
+            size_t tmp = G->scan_tmp_bytes;
+            if (hipcub::DeviceScan::ExclusiveSum(G->d_scan_tmp, tmp, head, head_off, (int)(n + 1), stream) != hipSuccess)
+                return fail(CORAL_ERR_HIP, "scan of the index run heads failed");
+            hipLaunchKernelGGL(k_bam_index_compact, dim3((unsigned)((n + WAVE - 1) / WAVE)), dim3(WAVE), 0, stream, n, head, head_off, voff, key, out_voff, out_key);
+            if (hipMemcpyAsync(&n_heads, head_off + n, 8, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess)
+                return fail(CORAL_ERR_HIP, std::string("index kernels failed: ") + hipGetErrorString(hipGetLastError()));
+            std::vector<long long> hk((size_t)n_heads);
+            std::vector<unsigned long long> hv((size_t)n_heads);
+            if (hipMemcpy(hk.data(), out_key, (size_t)n_heads * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+                hipMemcpy(hv.data(), out_voff, (size_t)n_heads * 8, hipMemcpyDeviceToHost) != hipSuccess)
+                return fail(CORAL_ERR_HIP, "copy of the index run heads failed");
+            for (long long j = 0; j < n_heads; ++j) D.idx.add_head(hk[(size_t)j], hv[(size_t)j]);
+        }
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return fail(CORAL_ERR_HIP, std::string("index launch failed: ") + hipGetErrorString(e));
     }
     // this buffer may be inflated into again (batch k + 2) once everything above has run
     if (hipEventRecord(G->ev_parsed[slot], stream) != hipSuccess) return fail(CORAL_ERR_HIP, "hipEventRecord failed");

@@ -397,6 +397,36 @@ int coral_bam_decode_range_cov(const char *path, int32_t n_threads, int32_t rank
                                const int32_t *seg_tid, const int32_t *seg_start, const int32_t *seg_end,
                                int32_t quality_threshold, int32_t read_callback, void **handle);
 int coral_bam_coverage_result(void *handle, int32_t n_seg, int64_t *counts);
+/* BAI index (SAMv1 5.2) built during the decode, and the decode of the regions such an index names - replaces what the
+ * reference gets from htslib behind pysam: the "Sorted indexed" BAM it opens was indexed by `samtools index`
+ * (hts_idx_push / hts_idx_finish), and every lr_bamfh.count_coverage(chrom, w, w + window, ...) of
+ * /root/reference/src/plot_amplicons.py:399-409 goes through hts_itr_query + bgzf_seek on that index.
+ *   decode_range_idx  coral_bam_decode_range with an index request: besides the records, what the byte range contributes to
+ *          the file's index.  index_sizes -> heads, linear-index windows, contigs, records; index_fill copies
+ *            head_key / head_voff  one entry per maximal run of file-consecutive records with the same (tid, bin), in file
+ *                      order: tid * 65536 + reg2bin(beg, end) (-1: a record without coordinates) and the virtual offset
+ *                      (block file offset << 16 | offset in the inflated block) of the run's first record; a run's chunk
+ *                      ends where the next head starts, the last one at scalars[1]
+ *            lin       per contig (length >> 14) + 1 windows: smallest virtual offset of an overlapping record, ~0 = none
+ *            n_mapped / n_unmapped  records per contig without / with flag 0x4 (pseudo-bin 37450)
+ *            scalars   records without coordinates, virtual offset behind the range's last record (bgzf_tell's rule),
+ *                      (tid, pos) of the first and of the last record as sortable words (order check across ranges)
+ *          A record is indexed as [max(pos, 0), bam_endpos), one base without a reference length; a record that sorts in
+ *          front of its predecessor fails the decode.  Partial results of consecutive byte ranges concatenate (a run that
+ *          goes on across the boundary is one run, windows take the minimum) into the whole file's.
+ *   decode_spans / decode_spans_cov  coral_bam_decode_range / _range_cov for the records that START inside n_spans sorted,
+ *          disjoint spans [span_beg, span_end) of virtual offsets (the chunks of a region query): each span begins at a
+ *          known record start (no search), ends in front of the record at or behind its end, and only its blocks (plus
+ *          what its last record straddles into) are inflated; coral_bam_decode_stats counts the blocks inflated. */
+int coral_bam_decode_range_idx(const char *path, int32_t n_threads, int32_t rank, int32_t world, void **handle);
+int coral_bam_index_sizes(void *handle, int64_t sizes[4]);
+int coral_bam_index_fill(void *handle, int64_t *head_key, uint64_t *head_voff, uint64_t *lin, int64_t *n_mapped,
+                         int64_t *n_unmapped, uint64_t scalars[4]);
+int coral_bam_decode_spans(const char *path, int32_t n_threads, int32_t n_spans, const uint64_t *span_beg,
+                           const uint64_t *span_end, void **handle);
+int coral_bam_decode_spans_cov(const char *path, int32_t n_threads, int32_t n_spans, const uint64_t *span_beg,
+                               const uint64_t *span_end, int32_t n_seg, const int32_t *seg_tid, const int32_t *seg_start,
+                               const int32_t *seg_end, int32_t quality_threshold, int32_t read_callback, void **handle);
 
 /* ------------------------------------------------------------------------------------------------
  * coral_bamgpu_* — the same decode with the inflate and the record parsing ON THE GPU: the host reads the file and sends
@@ -425,6 +455,19 @@ int coral_bam_coverage_result(void *handle, int32_t n_seg, int64_t *counts);
  *          k_bam_cov_count read the batch's inflated SEQ / QUAL before the slot is reused (one wave per 16 384 query bases
  *          of a record, one 64-bit atomic per work item and segment).  Without a request no kernel is added.
  *   coverage_result  after the last batch: waits for `stream`, copies the n_seg counts to host memory
+ *   open_spans       open for coral_bam_decode_spans on the GPU (htslib's hts_itr_query + bgzf_seek behind the reference's
+ *          per-window count_coverage calls): the spans go through the same batches one after the other, each from its known
+ *          first record to the record at or behind its end; only their blocks are read, uploaded and inflated.  A coverage
+ *          request works on it unchanged.  Statistics count every block read.
+ *   index            the index request of coral_bam_decode_range_idx on the GPU (htslib's hts_idx_push during
+ *          `samtools index`): after open, before start and BEFORE the workspace is allocated - *workspace_bytes is the new
+ *          size (block offsets, linear index, counters; everything per record re-uses the batch's scratch).  Per batch
+ *          k_bam_index (one thread per record: virtual offset by binary search of the batch's block table - a record carried
+ *          in from the batch in front keeps the offset it STARTED at -, bin, run heads, 64-bit atomicMin per overlapped
+ *          window, per-contig counters, order check), one scan and k_bam_index_compact; the host joins the runs that go on
+ *          across batches.  Without a request no kernel is added.
+ *   index_result     after the last batch: waits for `stream`, leaves the partial index in the handle of `host`
+ *          (coral_bam_index_sizes / _fill); fails when the records are not in coordinate order
  * coral_bgzf_inflate: one inflate launch over caller-provided device buffers — desc = n_blocks x {src_off, src_len,
  * dst_off, isize} uint32 (raw DEFLATE streams in `comp`, which must be readable 4096 bytes beyond the last stream);
  * status[b] = 0 or the decoder's error code.
@@ -439,6 +482,10 @@ int coral_bamgpu_stats(void *handle, int64_t stats[4], double seconds[6]);
 int coral_bamgpu_coverage(void *handle, int32_t n_seg, const int32_t *seg_tid, const int32_t *seg_start, const int32_t *seg_end,
                           int32_t quality_threshold, int32_t read_callback, int64_t *counts);
 int coral_bamgpu_coverage_result(void *handle, int32_t n_seg, int64_t *counts, void *stream);
+int coral_bamgpu_open_spans(const char *path, int32_t n_threads, int32_t n_spans, const uint64_t *span_beg,
+                            const uint64_t *span_end, int64_t batch_bytes, void **handle, int64_t *workspace_bytes);
+int coral_bamgpu_index(void *handle, int64_t *workspace_bytes);
+int coral_bamgpu_index_result(void *handle, void *stream);
 int coral_bamgpu_close(void *handle);
 int coral_bgzf_inflate(const uint8_t *comp, const uint32_t *desc, int32_t n_blocks, uint8_t *out, int32_t *status,
                        void *stream);
