@@ -4,7 +4,8 @@
     python -m coral_amd.CoRAL reconstruct --lr_bam x.bam --cnv_seed seeds.bed --cn_seg cn.bed --output_prefix out \\
         --skip_cycle_decomp
 
-The `reconstruct` mode and the `hsr` mode (§8(f) item 3) run on the MI355X path; the other modes of the
+The `reconstruct` mode and the `hsr` mode (§8(f) item 3) run on the MI355X path, and so do `index` and `qc`
+(the reference's scripts/report_nanopore_qc.py, from one decode of the aligned BAM); the other modes of the
 reference (seed, plot, cycle2bed) are untouched and are delegated to the reference's own modules when they are
 importable (set CORAL_REFERENCE_SRC to the reference's src/ directory).  The cycle-decomposition step after the graph build is the
 reference's (Gurobi); it runs on the object this module returns.
@@ -62,6 +63,11 @@ def build_parser():
     ip.add_argument("--lr_bam", help="Sorted (long read) bam file.", required=True)
     ip.add_argument("--index", help="Name of the index file (default: <lr_bam>.bai).")
     ip.add_argument("--device", help="GPU to use ('cpu': the host pipeline).", default="cuda:0")
+    qp = sub.add_parser("qc", help="Report read length and base quality statistics of a (long read) bam file.")
+    qp.add_argument("--lr_bam", help="(Long read) bam file.", required=True)
+    qp.add_argument("--output_dir", help="Where to write the summary and the plots.", required=True)
+    qp.add_argument("--device", help="GPU to use ('cpu': the host pipeline).", default="cuda:0")
+    qp.add_argument("--no_plots", help="If specified, write no histogram images.", action='store_true')
     for mode in ("seed", "plot", "cycle2bed"):
         sub.add_parser(mode, help="(reference implementation; not part of the MI355X path)", add_help=False)
     return parser
@@ -86,6 +92,47 @@ def reconstruct_mode(args):
     infer_breakpoint_graph.print_complete_message()
     print("\nCompleted reconstruction.")
     return b2bn
+
+
+def qc_mode(args):
+    """scripts/report_nanopore_qc.py of the reference on the aligned BAM: quality_control_summary.tsv (its lines 70-74), the two
+    histograms (lines 54-68, plain matplotlib) and read_qc.json (counters, summary, base-quality histogram)."""
+    import json
+    from coral_amd import bam
+    qc = bam.read_qc(args.lr_bam, device=args.device)
+    os.makedirs(args.output_dir, exist_ok=True)
+    wrote = [qc.write_summary(os.path.join(args.output_dir, "quality_control_summary.tsv"))]
+    summary = qc.summary()
+    path = os.path.join(args.output_dir, "read_qc.json")
+    with open(path, "w") as fp:
+        json.dump({"counters": qc.counters, "summary": summary, "base_quality_hist": qc.base_quality_hist.tolist()}, fp, indent=1)
+        fp.write("\n")
+    wrote.append(path)
+    plt = None
+    if not args.no_plots:
+        try:
+            import matplotlib
+            matplotlib.use("Agg")
+            import matplotlib.pyplot as plt
+        except ImportError:
+            print("matplotlib is not installed: no histogram images")
+    if plt is not None:
+        for values, label, title, name in (
+                (qc.length, "Mean Sequence Length", "Mean Length of Nanopore Sequences (mean = %s)" % summary["mean_length"], "mean_length_histogram.png"),
+                (qc.mean_qualities(), "Mean Sequence Quality", "Mean Quality of Nanopore Sequences (mean = %s)" % summary["mean_quality"],
+                 "mean_sequence_quality_histogram.png")):
+            plt.figure(figsize=(10, 5))
+            plt.hist(values, bins="auto")
+            plt.xlabel(label)
+            plt.ylabel("Frequency")
+            plt.title(title)
+            path = os.path.join(args.output_dir, name)
+            plt.savefig(path, dpi=300)
+            plt.close()
+            wrote.append(path)
+    for w in wrote:
+        print("Wrote %s" % w)
+    return wrote
 
 
 def main(argv=None):
@@ -113,6 +160,8 @@ def main(argv=None):
         out = bam.build_index(args.lr_bam, args.index, device=args.device)
         print("Wrote %s" % out)
         return out
+    if args.mode == "qc":
+        return qc_mode(args)
     parser.print_help()
     return None
 

@@ -131,6 +131,13 @@ def lib():
     L.coral_bamgpu_open_spans.argtypes = [C.c_char_p, C.c_int32, C.c_int32, P, P, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
     L.coral_bamgpu_index.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
     L.coral_bamgpu_index_result.argtypes = [C.c_void_p, P]
+    L.coral_bam_decode_range_qc.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
+    L.coral_bam_qc_sizes.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+    L.coral_bam_qc_fill.argtypes = [C.c_void_p, P, P, P, P, P, C.POINTER(C.c_int64)]
+    L.coral_bamgpu_qc.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+    L.coral_bamgpu_qc_result.argtypes = [C.c_void_p, P]
+    for name in ("coral_bam_decode_range_qc", "coral_bam_qc_sizes", "coral_bam_qc_fill", "coral_bamgpu_qc", "coral_bamgpu_qc_result"):
+        getattr(L, name).restype = C.c_int
     for name in ("coral_bam_decode_range_idx", "coral_bam_index_sizes", "coral_bam_index_fill", "coral_bam_decode_spans",
                  "coral_bam_decode_spans_cov", "coral_bamgpu_open_spans", "coral_bamgpu_index", "coral_bamgpu_index_result"):
         getattr(L, name).restype = C.c_int

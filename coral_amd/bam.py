@@ -184,7 +184,7 @@ def decode_bam_gpu(path: str, device="cuda:0", n_threads: Optional[int] = None, 
 
 
 def _decode_gpu(path: str, device, n_threads: Optional[int], rank: int, world: int, batch_bytes: int, coverage=None, records=True,
-                spans=None, index=False):
+                spans=None, index=False, qc=False):
     """decode_bam_gpu; with ``coverage`` = (segments int32 [3][S], quality threshold, read_callback code) the window-coverage
     request of coral_bamgpu_coverage rides along and its S int64 counts come back as the second result (records: None
     unless ``records``).  ``spans`` (uint64 [K][2] virtual offsets): only the records that start inside them
@@ -209,6 +209,8 @@ def _decode_gpu(path: str, device, n_threads: Optional[int], rank: int, world: i
     try:
         if index and L.coral_bamgpu_index(h, C.byref(ws_bytes)) != 0:
             raise _lib.CoralHipError("coral_bamgpu_index(%s) failed: %s" % (path, L.coral_bam_last_error().decode()))
+        if qc and L.coral_bamgpu_qc(h, C.byref(ws_bytes)) != 0:
+            raise _lib.CoralHipError("coral_bamgpu_qc(%s) failed: %s" % (path, L.coral_bam_last_error().decode()))
         ws = torch.empty(int(ws_bytes.value) + 256, dtype=torch.uint8, device=dev)
         base = (ws.data_ptr() + 255) & ~255
         stream = torch.cuda.current_stream(dev).cuda_stream
@@ -255,6 +257,10 @@ def _decode_gpu(path: str, device, n_threads: Optional[int], rank: int, world: i
             rc = L.coral_bamgpu_index_result(h, stream)
             if rc != 0:
                 raise fail("coral_bamgpu_index_result", rc)
+        if qc:
+            rc = L.coral_bamgpu_qc_result(h, stream)
+            if rc != 0:
+                raise fail("coral_bamgpu_qc_result", rc)
         cigar = torch.cat(pieces) if len(pieces) > 1 else (pieces[0] if pieces else torch.zeros(0, dtype=torch.int32, device=dev))
         del pieces
         dh = C.c_void_p()
@@ -272,7 +278,8 @@ def _decode_gpu(path: str, device, n_threads: Optional[int], rank: int, world: i
                            setup_seconds=float(gsecs[3]), waited_for_file_seconds=float(gsecs[4]), waited_for_gpu_seconds=float(gsecs[5]),
                            workspace_bytes=int(ws_bytes.value))
         partial = _index_partial_from_handle(L, dh) if index else None
-        return (_records_from_handle(L, dh, cigar, total) if records else None), counts, partial
+        read_qc_ = _read_qc_from_handle(L, dh) if qc else None
+        return (_records_from_handle(L, dh, cigar, total) if records else None), counts, partial, read_qc_
     finally:
         # (close drains the decoder's streams — a byte range may have batches of its overhang still being inflated — and only
         # then the workspace, which those kernels write, is released: `ws` lives until this function returns)
@@ -441,6 +448,115 @@ def window_coverage(path: str, windows: Sequence[Tuple[str, int, int]], quality_
             L.coral_bam_decode_close(h)
     csum = np.concatenate([[0], np.cumsum(counts, dtype=np.int64)])
     return (csum[last] - csum[first]).astype(np.int64)
+
+
+# ----------------------------------------------------------------------------------------------
+# read QC: per-read length and base-quality statistics, counted during the decode
+# ----------------------------------------------------------------------------------------------
+QC_COUNTERS = ("n_records", "n_reads", "n_secondary", "n_supplementary", "n_unmapped", "n_no_seq", "n_no_qual", "total_bases")
+
+
+class ReadQC:
+    """What the reference's scripts/report_nanopore_qc.py looks at, from one decode of the aligned BAM.  One entry per READ (a
+    record with ``flag & 0x900 == 0`` and SEQ: one per FASTQ record the file was aligned from, mapped or not), in file order:
+    ``length`` int32 (``l_seq``, the stored sequence: a hard-clipped primary reports its stored length), ``qual_sum`` int64
+    (sum of the read's QUAL bytes = FASTQ character - 33; -1: the read has no quality, its first QUAL byte is 0xff), ``mapq``
+    and ``flag`` int32.  ``base_quality_hist`` int64 [256] counts every QUAL byte of the reads that have quality.  Counters
+    (``QC_COUNTERS``, also attributes): records, reads, records with flag 0x100 / 0x800, reads with flag 0x4, primary records
+    without SEQ, reads without quality, bases of all reads.  Everything is an integer until ``summary`` divides."""
+
+    def __init__(self, length, qual_sum, mapq, flag, base_quality_hist, counters):
+        self.length = np.ascontiguousarray(length, dtype=np.int32)
+        self.qual_sum = np.ascontiguousarray(qual_sum, dtype=np.int64)
+        self.mapq = np.ascontiguousarray(mapq, dtype=np.int32)
+        self.flag = np.ascontiguousarray(flag, dtype=np.int32)
+        self.base_quality_hist = np.ascontiguousarray(base_quality_hist, dtype=np.int64)
+        self.counters = {k: int(counters[k]) for k in QC_COUNTERS}
+        for k, v in self.counters.items():
+            setattr(self, k, v)
+
+    def mean_qualities(self) -> np.ndarray:
+        """``np.mean(quality)`` of every read that has quality, in file order: qual_sum / length in float64 (the sums are far
+        below 2^53, so this is the mean of the integer array bit for bit)."""
+        have = self.qual_sum >= 0
+        return self.qual_sum[have].astype(np.float64) / self.length[have].astype(np.float64)
+
+    def summary(self) -> dict:
+        """Q25 / Q50 / Q75 (``np.percentile``, the script's lines 70-72) and the mean (lines 58, 66) of the read lengths and of
+        the reads' mean qualities, N50 and the number of bases.  The quality entries are None when no read has quality; a
+        file without any read raises ValueError."""
+        if len(self.length) == 0:
+            raise ValueError("read QC: the file holds no read (no primary record with SEQ): there is nothing to summarise")
+        lengths = self.length.astype(np.int64)
+        out = {"length_Q%d" % q: float(np.percentile(lengths, q)) for q in (25, 50, 75)}
+        out["mean_length"] = float(np.mean(lengths))
+        mq = self.mean_qualities()
+        for q in (25, 50, 75):
+            out["quality_Q%d" % q] = float(np.percentile(mq, q)) if len(mq) else None
+        out["mean_quality"] = float(np.mean(mq)) if len(mq) else None
+        desc = np.sort(lengths)[::-1]
+        out["n50"] = int(desc[np.searchsorted(2 * np.cumsum(desc), int(lengths.sum()))])      # reads this long or longer hold half the bases
+        out["total_bases"] = int(lengths.sum())
+        return out
+
+    def summary_text(self) -> str:
+        """The bytes of the script's ``quality_control_summary.tsv`` (``DataFrame.to_csv(sep='\\t')`` of its frame)."""
+        s = self.summary()
+        if s["mean_quality"] is None:
+            raise ValueError("read QC: no read has base qualities: quality_control_summary.tsv cannot be written")
+        row = lambda name, key: "\t".join([name] + [repr(s["%s_Q%d" % (key, q)]) for q in (25, 50, 75)]) + "\n"
+        return "\tQ25\tQ50\tQ75\n" + row("mean_length", "length") + row("mean_sequence_quality", "quality")
+
+    def write_summary(self, path: str) -> str:
+        text = self.summary_text()
+        with open(path, "w", newline="") as fp:
+            fp.write(text)
+        return path
+
+
+def _read_qc_from_handle(L, h) -> ReadQC:
+    sz = (C.c_int64 * 2)()
+    if L.coral_bam_qc_sizes(h, sz) != 0:
+        raise _lib.CoralHipError("coral_bam_qc_sizes failed: %s" % L.coral_bam_last_error().decode())
+    r = int(sz[1])
+    length, mapq, flag = (np.empty(r, dtype=np.int32) for _ in range(3))
+    qual_sum, hist = np.empty(r, dtype=np.int64), np.zeros(256, dtype=np.int64)
+    cnt = (C.c_int64 * 8)()
+    if L.coral_bam_qc_fill(h, length.ctypes.data, qual_sum.ctypes.data, mapq.ctypes.data, flag.ctypes.data, hist.ctypes.data, cnt) != 0:
+        raise _lib.CoralHipError("coral_bam_qc_fill failed: %s" % L.coral_bam_last_error().decode())
+    return ReadQC(length, qual_sum, mapq, flag, hist, dict(zip(QC_COUNTERS, cnt)))
+
+
+def read_qc(path: str, device="cuda:0", n_threads: Optional[int] = None, rank: int = 0, world: int = 1, batch_bytes: int = 0) -> ReadQC:
+    """Per-read length and base-quality statistics of the BAM (``ReadQC``), counted while it is decoded - the only time QUAL is
+    at hand.  On the GPU pipeline when ``device`` is a GPU (coral_bamgpu_qc: k_bam_qc_plan / k_bam_qc per batch), on the host
+    pipeline with ``device="cpu"`` or ``CORAL_BAM_DECODE=cpu`` (coral_bam_decode_range_qc); the results are identical.  With
+    ``world`` > 1 the result is that of the ``rank``-th byte range; ``merge_read_qc`` joins them."""
+    bam_reference_names(path)                                    # (a clear error for something that is not a BAM file)
+    if n_threads is None:
+        n_threads = default_threads()
+    if _on_gpu(device):
+        return _decode_gpu(path, device, n_threads, rank, world, batch_bytes, records=False, qc=True)[3]
+    L = _lib.lib()
+    h = C.c_void_p()
+    rc = L.coral_bam_decode_range_qc(path.encode(), n_threads, rank, world, C.byref(h))
+    if rc != 0:
+        raise _lib.CoralHipError("coral_bam_decode_range_qc(%s) failed (%d): %s" % (path, rc, L.coral_bam_last_error().decode()))
+    try:
+        _host_stats(L, h, n_threads)
+        return _read_qc_from_handle(L, h)
+    finally:
+        L.coral_bam_decode_close(h)
+
+
+def merge_read_qc(parts: Sequence[ReadQC]) -> ReadQC:
+    """The results of consecutive byte ranges (in rank order) as one: rows concatenated, histograms and counters added."""
+    parts = list(parts)
+    if not parts:
+        raise ValueError("merge_read_qc needs at least one part")
+    cat = lambda k: np.concatenate([getattr(p, k) for p in parts])
+    return ReadQC(cat("length"), cat("qual_sum"), cat("mapq"), cat("flag"), np.sum([p.base_quality_hist for p in parts], axis=0),
+                  {k: sum(p.counters[k] for p in parts) for k in QC_COUNTERS})
 
 
 # ----------------------------------------------------------------------------------------------
@@ -821,7 +937,7 @@ _NM_PACK = {"c": "<b", "C": "<B", "s": "<h", "S": "<H", "i": "<i", "I": "<I"}
 
 def write_bam(rec: Records, path: str, seed: int = 0, long_cigar_as_cg: bool = True, fast_seq: bool = False, *, aux=None,
               nm_type="i", with_qual=False, block_size: int = 0xff00, empty_block_every: int = 0,
-              header_comment: str = "") -> None:
+              header_comment: str = "", qual=None) -> None:
     """Serialise ``rec`` as a coordinate-sorted BAM (SEQ = deterministic ACGT with N at the listed non-ACGT
     positions, QUAL absent, tags NM:i and SA:Z; CIGARs with more than 65535 ops go to the CG:B,I tag).
 
@@ -830,6 +946,8 @@ def write_bam(rec: Records, path: str, seed: int = 0, long_cigar_as_cg: bool = T
       ``nm_type``       one of c C s S i I (htslib stores integers in the smallest type that fits), None (no NM tag), or a
                         callable i -> one of these;
       ``with_qual``     real QUAL bytes (a hash of the position, 0..60) instead of 0xff; a callable i -> bool decides per record;
+      ``qual``          a callable i -> the record's QUAL bytes (any values 0..255, exactly l_seq of them), or None for what
+                        ``with_qual`` says;
       ``block_size``    payload bytes per BGZF block (small: header, records and tags straddle blocks);
       ``empty_block_every``  an empty BGZF block after every k-th block;
       ``header_comment``     extra @CO text (a long header spans several BGZF blocks)."""
@@ -892,7 +1010,12 @@ def write_bam(rec: Records, path: str, seed: int = 0, long_cigar_as_cg: bool = T
         name = names[name_id[i]].encode() + b"\0"
         body = struct.pack("<iiBBHHHiiii", int(tid[i]), int(pos[i]), len(name), int(mapq[i]),
                            _reg2bin(int(pos[i]), int(pos[i]) + max(1, rlen)), len(cig_field), int(flag[i]), l_seq, -1, -1, 0)
-        if l_seq and (with_qual(i) if callable(with_qual) else with_qual):
+        given = qual(i) if qual is not None and l_seq else None
+        if given is not None:
+            qual_bytes = bytes(given)
+            if len(qual_bytes) != l_seq:
+                raise ValueError("write_bam: qual(%d) gave %d bytes for a record of %d bases" % (i, len(qual_bytes), l_seq))
+        elif l_seq and (with_qual(i) if callable(with_qual) else with_qual):
             qual_bytes = ((hash_u32(seed, S_SEQ, torch.arange(l_seq, dtype=torch.int64) + (i + 7) * (1 << 22)) % 61).numpy()
                           .astype(np.uint8).tobytes())
         else:

@@ -75,7 +75,7 @@ struct Chunk {
 // offsets, e.g. from a BAI index): the first record is at a known place, nothing is searched, and the decode stops in front of
 // the record that starts at or behind span->end.  Spans may be decoded one after the other into the same `D`.
 bool decode_file(const char *path, int n_threads, int rank, int world, Decoded &D, const CovTable *cov = nullptr, const Span *span = nullptr,
-                 bool want_index = false) {
+                 bool want_index = false, bool want_qc = false) {
     const auto t_start = std::chrono::steady_clock::now();
     MappedFile f;
     if (!f.open(path, D.error)) return false;
@@ -91,6 +91,7 @@ bool decode_file(const char *path, int n_threads, int rank, int world, Decoded &
     }
     const int32_t n_ref = (int32_t)D.ref_names.size();
     if (want_index) D.idx.init(D.ref_lens);
+    if (want_qc) D.qc.init();
     // ---- block table: the blocks that START inside this rank's byte range, plus an overhang for the last record
     const uint64_t byte_lo = rank == 0 ? 0 : f.size / (uint64_t)world * (uint64_t)rank;
     const uint64_t byte_hi = rank == world - 1 ? f.size : f.size / (uint64_t)world * (uint64_t)(rank + 1);
@@ -171,9 +172,10 @@ bool decode_file(const char *path, int n_threads, int rank, int world, Decoded &
             Partial &pt = c->part;
             pt.cigar.reserve(c->own / 6 + 64);
             if (cov) pt.cov.assign(cov->size(), 0);              // the chunk's partial counts, added up in merge()
+            if (want_qc) pt.qc_hist.assign(256, 0);              // the chunk's partial histogram, likewise
             for (size_t s : c->starts) {
                 const uint8_t *q = c->buf.data() + s;
-                if (!decode_record(q + 4, rd32(q), ref_id, pt, pt.error, cov)) break;
+                if (!decode_record(q + 4, rd32(q), ref_id, pt, pt.error, cov, want_qc)) break;
             }
             std::vector<uint8_t>().swap(c->buf);            // SEQ / QUAL bytes are gone from here on
             c->parsed.set();
@@ -199,6 +201,8 @@ bool decode_file(const char *path, int n_threads, int rank, int world, Decoded &
         for (int64_t l : pt.na_rec_local) D.na_rec.push_back(base + l);
         app(D.na_pos, pt.na_pos);
         for (size_t t = 0; t < pt.cov.size(); ++t) D.cov[t] += pt.cov[t];
+        D.qc.qual_sum.insert(D.qc.qual_sum.end(), pt.qc_sum.begin(), pt.qc_sum.end());
+        for (size_t t = 0; t < pt.qc_hist.size(); ++t) D.qc.hist[t] += pt.qc_hist[t];
         for (const char *s = pt.names.data(), *e = s + pt.names.size(); s < e;) {
             const size_t len = strlen(s);
             D.name_id.push_back(D.names.intern(s, len));
@@ -482,13 +486,14 @@ void coral_bam::set_error(const std::string &msg) { g_bam_err = msg; }
 extern "C" const char *coral_bam_last_error(void) { return g_bam_err.c_str(); }
 
 static int decode_range(const char *path, int32_t n_threads, int32_t rank, int32_t world, const CovTable *cov, void **handle,
-                        bool want_index = false, int32_t n_spans = -1, const uint64_t *span_beg = nullptr, const uint64_t *span_end = nullptr) {
+                        bool want_index = false, int32_t n_spans = -1, const uint64_t *span_beg = nullptr, const uint64_t *span_end = nullptr,
+                        bool want_qc = false) {
     if (!path || !handle || (n_spans > 0 && (!span_beg || !span_end))) return CORAL_ERR_ARG;
     Decoded *D = new Decoded();
     bool ok = false;
     try {
         if (n_spans < 0) {
-            ok = decode_file(path, n_threads, rank, world, *D, cov, nullptr, want_index);
+            ok = decode_file(path, n_threads, rank, world, *D, cov, nullptr, want_index, want_qc);
         } else {                                 // spans in the given order, into one result (no span: the header only)
             MappedFile f;
             RefIds ids;
@@ -532,6 +537,10 @@ extern "C" int coral_bam_decode_range_idx(const char *path, int32_t n_threads, i
     return decode_range(path, n_threads, rank, world, nullptr, handle, true);
 }
 
+extern "C" int coral_bam_decode_range_qc(const char *path, int32_t n_threads, int32_t rank, int32_t world, void **handle) {
+    return decode_range(path, n_threads, rank, world, nullptr, handle, false, -1, nullptr, nullptr, true);
+}
+
 extern "C" int coral_bam_decode_spans(const char *path, int32_t n_threads, int32_t n_spans, const uint64_t *span_beg,
                                       const uint64_t *span_end, void **handle) {
     if (n_spans < 0) return CORAL_ERR_ARG;
@@ -570,6 +579,38 @@ extern "C" int coral_bam_index_fill(void *handle, int64_t *head_key, uint64_t *h
     auto cp = [](auto *dst, const auto &v) { if (!v.empty() && dst) memcpy(dst, v.data(), v.size() * sizeof(v[0])); };
     cp(head_key, X.head_key); cp(head_voff, X.head_voff); cp(lin, X.lin); cp(n_mapped, X.n_mapped); cp(n_unmapped, X.n_unmapped);
     scalars[0] = (uint64_t)X.n_no_coor; scalars[1] = X.end_voff; scalars[2] = X.first_sort; scalars[3] = X.last_sort;
+    return CORAL_OK;
+}
+
+// The read-QC request of a handle (either pipeline): sizes = records, reads; fill = the reads' rows in file order (length,
+// qual_sum with -1 for no quality, mapq, flag), the 256-bin histogram and the counters (QC_N_RECORDS ...).
+extern "C" int coral_bam_qc_sizes(void *handle, int64_t sizes[2]) {
+    if (!handle || !sizes) return CORAL_ERR_ARG;
+    const Decoded *D = (const Decoded *)handle;
+    if (!D->qc.on || D->qc.qual_sum.size() != D->flag.size()) { g_bam_err = "coral_bam_qc_sizes: the handle holds no read-QC request"; return CORAL_ERR_ARG; }
+    int64_t c[QC_N_COUNTERS];
+    QcPartial::counters(D->flag, D->has_seq, D->qlen, D->qc.qual_sum, c);
+    sizes[0] = c[QC_N_RECORDS];
+    sizes[1] = c[QC_N_READS];
+    return CORAL_OK;
+}
+
+extern "C" int coral_bam_qc_fill(void *handle, int32_t *length, int64_t *qual_sum, int32_t *mapq, int32_t *flag, int64_t hist[256],
+                                 int64_t counters[8]) {
+    if (!handle || !hist || !counters) return CORAL_ERR_ARG;
+    const Decoded *D = (const Decoded *)handle;
+    if (!D->qc.on || D->qc.qual_sum.size() != D->flag.size()) { g_bam_err = "coral_bam_qc_fill: the handle holds no read-QC request"; return CORAL_ERR_ARG; }
+    static_assert(QC_N_COUNTERS == 8, "the counters of the C ABI");
+    QcPartial::counters(D->flag, D->has_seq, D->qlen, D->qc.qual_sum, counters);
+    if (counters[QC_N_READS] > 0 && (!length || !qual_sum || !mapq || !flag)) return CORAL_ERR_ARG;
+    size_t r = 0;
+    for (size_t i = 0; i < D->flag.size(); ++i) {
+        const uint32_t l_seq = D->has_seq[i] ? (uint32_t)D->qlen[i] : 0u;
+        if (!qc_is_read((uint32_t)D->flag[i], l_seq)) continue;
+        length[r] = (int32_t)l_seq; qual_sum[r] = D->qc.qual_sum[i]; mapq[r] = D->mapq[i]; flag[r] = D->flag[i];
+        ++r;
+    }
+    memcpy(hist, D->qc.hist, sizeof(D->qc.hist));
     return CORAL_OK;
 }
 

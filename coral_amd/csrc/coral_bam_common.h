@@ -104,6 +104,54 @@ struct IndexPartial {
     }
 };
 
+// A read-QC request (coral_bam_decode_range_qc, coral_bamgpu_qc): per-read length and base-quality statistics, what the
+// reference's scripts/report_nanopore_qc.py computes from the FASTQ the file was aligned from.  The rules both pipelines share:
+//   a READ is a record with flag & 0x900 == 0 (neither secondary nor supplementary) and l_seq > 0, mapped or not;
+//   its QUAL bytes start qc_qual_offset() bytes behind the record's first byte (its block_size field) - the record's OWN
+//   n_cigar_op counts there, not the CG tag's -; a read whose first QUAL byte is 0xff has no quality.
+// Per record: qual_sum = sum of the read's l_seq QUAL bytes, -1 when the record is not a read or has no quality (its length is
+// the l_seq the decode keeps anyway).  hist counts every QUAL byte value of the reads that have quality.  Integers only: the
+// result is the same on either pipeline, for any batch size and any split into byte ranges.
+#ifdef __HIP__
+#define CORAL_QC_HD __host__ __device__
+#else
+#define CORAL_QC_HD
+#endif
+CORAL_QC_HD inline bool qc_is_read(uint32_t flag, uint32_t l_seq) { return (flag & 0x900u) == 0 && l_seq > 0; }
+CORAL_QC_HD inline unsigned long long qc_qual_offset(uint32_t l_read_name, uint32_t n_cigar_op, uint32_t l_seq) {
+    return 36ull + l_read_name + 4ull * n_cigar_op + ((unsigned long long)l_seq + 1) / 2;
+}
+CORAL_QC_HD inline bool qc_has_quality(uint8_t first_qual_byte) { return first_qual_byte != 0xff; }
+
+enum { QC_N_RECORDS = 0, QC_N_READS, QC_N_SECONDARY, QC_N_SUPPLEMENTARY, QC_N_UNMAPPED, QC_N_NO_SEQ, QC_N_NO_QUAL, QC_TOTAL_BASES, QC_N_COUNTERS };
+
+struct QcPartial {
+    bool on = false;
+    std::vector<int64_t> qual_sum;          // per record, in file order
+    int64_t hist[256];
+    void init() {
+        on = true;
+        memset(hist, 0, sizeof(hist));
+    }
+    // the counters of the request from the per-record columns (flag; l_seq = has_seq ? qlen : 0; qual_sum)
+    static void counters(const std::vector<int32_t> &flag, const std::vector<int32_t> &has_seq, const std::vector<int32_t> &qlen,
+                         const std::vector<int64_t> &qual_sum, int64_t c[QC_N_COUNTERS]) {
+        for (int k = 0; k < QC_N_COUNTERS; ++k) c[k] = 0;
+        c[QC_N_RECORDS] = (int64_t)flag.size();
+        for (size_t i = 0; i < flag.size(); ++i) {
+            const uint32_t f = (uint32_t)flag[i], l_seq = has_seq[i] ? (uint32_t)qlen[i] : 0u;
+            c[QC_N_SECONDARY] += (f & 0x100u) != 0;
+            c[QC_N_SUPPLEMENTARY] += (f & 0x800u) != 0;
+            c[QC_N_NO_SEQ] += (f & 0x900u) == 0 && l_seq == 0;
+            if (!qc_is_read(f, l_seq)) continue;
+            ++c[QC_N_READS];
+            c[QC_N_UNMAPPED] += (f & 4u) != 0;
+            c[QC_N_NO_QUAL] += qual_sum[i] < 0;
+            c[QC_TOTAL_BASES] += l_seq;
+        }
+    }
+};
+
 // A span of virtual offsets [beg, end) (coral_bam_decode_spans, coral_bamgpu_open_spans): the records that START in it.
 struct Span {
     uint64_t beg = 0, end = 0;
@@ -111,6 +159,7 @@ struct Span {
 
 struct Decoded {
     IndexPartial idx;                       // BAI index request (empty without one)
+    QcPartial qc;                           // read-QC request (empty without one)
     std::vector<int32_t> tid, pos, end, flag, mapq, qlen, has_seq, nm, name_id, n_cigar;
     std::vector<int64_t> cigar_off{0}, sa_off{0};
     std::vector<uint32_t> cigar;
@@ -137,6 +186,7 @@ struct Partial {   // what stage 3 produces for one chunk
     std::vector<int32_t> na_pos;
     std::vector<char> names;                // NUL-separated
     std::vector<int64_t> cov;               // window-coverage counts of the chunk's records (per segment; empty without a request)
+    std::vector<int64_t> qc_sum, qc_hist;   // read-QC request: qual_sum per record, the chunk's 256-bin histogram (empty without a request)
     std::string error;
 };
 
@@ -319,8 +369,9 @@ inline bool all_acgt(const uint8_t *seq, uint32_t l_seq) {
 
 // Decode one BAM record (p points at refID, i.e. after block_size) into the partial.
 // With `cov`, the record's bases also go into o.cov (sized by the caller).
+// With `qc`, the record's qual_sum goes to o.qc_sum and its QUAL bytes into o.qc_hist (256 bins, sized by the caller).
 inline bool decode_record(const uint8_t *p, uint32_t block_size, const RefIds &ref_id, Partial &o, std::string &err,
-                          const CovTable *cov = nullptr) {
+                          const CovTable *cov = nullptr, bool qc = false) {
     if (block_size < 32) { err = "record shorter than its fixed fields"; return false; }
     const int32_t refID = (int32_t)rd32(p), pos = (int32_t)rd32(p + 4);
     const uint32_t l_read_name = p[8], mapq = p[9];
@@ -333,6 +384,16 @@ inline bool decode_record(const uint8_t *p, uint32_t block_size, const RefIds &r
     const uint8_t *tags = qual + l_seq;
     const uint8_t *endp = p + block_size;
     if (tags > endp || l_read_name == 0) { err = "record fields overrun the record"; return false; }
+    if (qc) {
+        int64_t sum = -1;
+        const uint8_t *q = p - 4 + qc_qual_offset(l_read_name, n_cigar_op, l_seq);
+        if (qc_is_read(flag, l_seq) && qc_has_quality(q[0])) {
+            sum = 0;
+            int64_t *h = o.qc_hist.data();
+            for (uint32_t k = 0; k < l_seq; ++k) { sum += q[k]; ++h[q[k]]; }
+        }
+        o.qc_sum.push_back(sum);
+    }
     // tags: NM, SA, CG
     int32_t nm = 0;
     const char *sa = nullptr;

@@ -22,6 +22,8 @@
 //                   base-quality threshold over the request's segments, read from the batch's SEQ / QUAL before the slot is reused.
 //   k_bam_index / k_bam_index_compact   only with an index request (coral_bamgpu_index): per record the virtual offset, the UCSC bin
 //                   and the linear-index windows of a BAI index, per batch the heads of the runs of equal (tid, bin).
+//   k_bam_qc_plan / k_bam_qc   only with a read-QC request (coral_bamgpu_qc): per read the sum of its QUAL bytes, and the 256-bin
+//                   histogram of all of them, read from the batch's QUAL before the slot is reused.
 // Batches (64 MiB first, doubling up to 2.52 GiB inflated, coral_bamgpu_open) are double-buffered: while batch k is parsed, batch k + 1 is inflated
 // and k + 2 is read.
 // A record that straddles two batches is carried in front of the next batch's buffer.
@@ -1103,6 +1105,109 @@ __global__ __launch_bounds__(256) void k_bam_cov_count(const uint8_t *__restrict
 }
 
 // ---------------------------------------------------------------------------------------------
+// K_qc: per-read base-quality sums and the base-quality histogram (coral_bamgpu_qc; the rules: QcPartial in coral_bam_common.h)
+// ---------------------------------------------------------------------------------------------
+#define QC_SLICE 16384ll                 // QUAL bytes per work item (as COV_SLICE: a 1 Mb read is 62 waves' work)
+#ifndef QC_COPIES
+#define QC_COPIES 4                      // copies of the 256-bin table per wave, interleaved: 4 KiB of LDS (a -DQC_COPIES=1 build is
+#endif                                   // the single table to measure it against)
+
+// One thread per record (one-wave workgroups): qual_sum[i] = 0 for a read with quality (k_bam_qc adds to it), -1 otherwise, and
+// the number of work items its QUAL is cut into.  Slot n_rec gets 0 items (the scan's extra entry).
+__global__ __launch_bounds__(WAVE) void k_bam_qc_plan(const uint8_t *__restrict__ buf, const long long *__restrict__ rec_start, long long n_rec,
+                                                      MetaArrays M, long long *__restrict__ qual_sum, long long *__restrict__ n_items) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > n_rec) return;
+    long long cnt = 0;
+    if (i < n_rec) {
+        const uint32_t l_seq = (uint32_t)M.l_seq[i];
+        bool counted = false;
+        if (qc_is_read((uint32_t)M.flag[i], l_seq)) {
+            const uint8_t *r = buf + rec_start[i];
+            counted = qc_has_quality(r[qc_qual_offset(r[12], ld16(r + 16), l_seq)]);
+        }
+        if (counted) cnt = ((long long)l_seq + QC_SLICE - 1) / QC_SLICE;
+        qual_sum[i] = counted ? 0 : -1;
+    }
+    n_items[i] = cnt;
+}
+
+// One wave per work item (one-wave workgroups, grid-stride): QUAL bytes [k * QC_SLICE, (k + 1) * QC_SLICE) of record i.
+// QUAL begins at any byte address: the wave reads the 16-byte aligned chunks that cover its bytes, lane l the chunks l, l + 64,
+// ... - one load instruction of the wave is 1 KiB of consecutive memory, every cache line is fetched once - and the bytes of the
+// first and the last chunk that are not the item's are masked out.  Sum: v_sad_u8 per dword, reduced in the wave, ONE 64-bit
+// atomic per item.  Histogram: COPIES copies of the 256 bins in LDS, interleaved (bin v of copy c at word v * COPIES + c, lane l
+// uses copy l % COPIES): real QUAL sits on a few values, and lanes that add to the same word are serialised - with the copies
+// side by side, lanes with the same value spread over COPIES words in COPIES different banks.  The workgroup adds its table to the
+// device histogram once, at its end, with 64-bit atomics.  4 KiB of LDS (COPIES = 4): fits beside the inflate launch's 27 x 5.75 KiB
+// of a CU's 160 KiB, as k_bgzf_crc's tables do.
+__global__ __launch_bounds__(WAVE) void k_bam_qc(const uint8_t *__restrict__ buf, const long long *__restrict__ rec_start, long long n_rec,
+                                                 MetaArrays M, const long long *__restrict__ item_off,
+                                                 unsigned long long *__restrict__ qual_sum, unsigned long long *__restrict__ hist) {
+    constexpr int COPIES = QC_COPIES;
+    // (a 32-bit bin cannot overflow: the grid-stride loop gives a workgroup at most ceil(items / 2 048) work items of 16 KiB, and
+    // CARRY_CAP + a batch stay below 4 GiB - under 2^21 bytes per workgroup and launch)
+    __shared__ uint32_t H[256 * COPIES];
+    const int lane = threadIdx.x;
+    for (int k = lane; k < 256 * COPIES; k += WAVE) H[k] = 0;
+    __syncthreads();
+    uint32_t *mine = H + (lane % COPIES);
+    const long long total = item_off[n_rec];
+    for (long long w = blockIdx.x; w < total; w += gridDim.x) {
+        long long a = 0, b = n_rec;                                   // the record: the last i with item_off[i] <= w
+        while (b - a > 1) {
+            const long long m = (a + b) >> 1;
+            if (item_off[m] <= w) a = m; else b = m;
+        }
+        const long long i = a;
+        const uint32_t l_seq = (uint32_t)M.l_seq[i];
+        const uint8_t *r = buf + rec_start[i];
+        const long long q_lo = (w - item_off[i]) * QC_SLICE, q_hi = min((long long)l_seq, q_lo + QC_SLICE);
+        const uint8_t *p = r + qc_qual_offset(r[12], ld16(r + 16), l_seq) + q_lo;
+        const int n = (int)(q_hi - q_lo);                             // 1 .. QC_SLICE
+        const int head = (int)((uintptr_t)p & 15u);
+        const uint4 *chunks = reinterpret_cast<const uint4 *>(p - head);       // (inside the batch buffer: a record starts >= 36 bytes in front of its QUAL)
+        const int n_chunks = (head + n + 15) >> 4;
+        uint32_t acc = 0;
+        for (int c = lane; c < n_chunks; c += WAVE) {
+            const uint4 v = chunks[c];
+            const uint32_t word[4] = {v.x, v.y, v.z, v.w};
+            const int first = c * 16 - head;                          // item-relative index of the chunk's byte 0
+            if (first >= 0 && first + 16 <= n) {
+#pragma unroll
+                for (int d = 0; d < 4; ++d) {
+                    const uint32_t x = word[d];
+                    acc = __builtin_amdgcn_sad_u8(x, 0u, acc);
+                    atomicAdd(mine + (x & 0xffu) * COPIES, 1u);
+                    atomicAdd(mine + ((x >> 8) & 0xffu) * COPIES, 1u);
+                    atomicAdd(mine + ((x >> 16) & 0xffu) * COPIES, 1u);
+                    atomicAdd(mine + (x >> 24) * COPIES, 1u);
+                }
+            } else {                                                  // the item's first or last chunk: byte by byte
+#pragma unroll
+                for (int j = 0; j < 16; ++j) {
+                    const uint32_t q = (word[j >> 2] >> (8 * (j & 3))) & 0xffu;
+                    if (first + j >= 0 && first + j < n) {
+                        acc += q;
+                        atomicAdd(mine + q * COPIES, 1u);
+                    }
+                }
+            }
+        }
+        unsigned long long sum = acc;
+        for (int d = 32; d > 0; d >>= 1) sum += __shfl_xor(sum, d);
+        if (lane == 0) atomicAdd(qual_sum + i, sum);
+    }
+    __syncthreads();
+    for (int v = lane; v < 256; v += WAVE) {
+        unsigned long long t = 0;
+#pragma unroll
+        for (int c = 0; c < COPIES; ++c) t += H[v * COPIES + c];
+        if (t) atomicAdd(hist + v, t);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // K_index: what a batch contributes to the BAI index of the file (coral_bamgpu_index; IndexPartial in coral_bam_common.h)
 // ---------------------------------------------------------------------------------------------
 struct IndexDev {                        // device arrays of the request, carved from the caller's workspace
@@ -1344,6 +1449,13 @@ struct GpuDecoder {
     BlockDesc *d_idesc[2] = {nullptr, nullptr};   // the slot's block table and offsets, kept for k_bam_index: the feeder re-stages
     uint32_t *d_iboff[2] = {nullptr, nullptr};    //   d_desc / d_boff for batch k + 2 while batch k is still being parsed
     int idx_parity = 0;
+    // read-QC request (coral_bamgpu_qc): the batch's qual_sum rows (fetched when the NEXT batch's host fields are: the stream has
+    // been synchronised behind the kernels by then, and that batch's k_bam_qc_plan is queued only afterwards, so one array
+    // does), the device histogram of the whole decode
+    bool qc_on = false;
+    long long *d_qc_sum = nullptr;
+    unsigned long long *d_qc_hist = nullptr;
+    long long qc_pending_n = 0;               // records of the batch whose rows are still on the device
     // statistics
     double t_open = 0, seconds = 0, host_seconds = 0;
     int64_t fixups = 0, n_batches = 0, na_records = 0;
@@ -1694,6 +1806,10 @@ bool carve(GpuDecoder *G, void *ws, size_t bytes) {
         G->X.unsorted = (int32_t *)take(4);
         G->X.n_ref = (int)n_ref;
     }
+    if (G->qc_on) {
+        G->d_qc_sum = (long long *)take(nr * 8);
+        G->d_qc_hist = (unsigned long long *)take(256 * 8);
+    }
     if (ws && used > bytes) return false;
     G->ws_bytes = used;
     return true;
@@ -1881,6 +1997,46 @@ extern "C" int coral_bamgpu_index_result(void *handle, void *stream_) {
     return CORAL_OK;
 }
 
+// Read-QC request: after open (not open_spans), before start and before the workspace is allocated: *workspace_bytes is the new
+// size (one int64 per record of a batch, the histogram).  Per batch k_bam_qc_plan + one scan + k_bam_qc.
+extern "C" int coral_bamgpu_qc(void *handle, int64_t *workspace_bytes) {
+    GpuDecoder *G = (GpuDecoder *)handle;
+    if (!G || !workspace_bytes) return CORAL_ERR_ARG;
+    if (G->feeder.joinable() || G->qc_on || G->span_mode) { set_error("coral_bamgpu_qc: call it once, after open and before start, not on a span decode"); return CORAL_ERR_ARG; }
+    G->qc_on = true;
+    G->D.qc.init();
+    carve(G, nullptr, 0);
+    *workspace_bytes = (int64_t)G->ws_bytes;
+    return CORAL_OK;
+}
+
+// the qual_sum rows of the batch emitted last, if they are still on the device (the caller has synchronised the stream).
+// One array for all batches: that holds only while every emit of a decode and the result call are given the SAME stream:
+// the rows of batch k-1 are complete once batch k's emit has waited for the stream that batch k-1's kernels were queued on.
+static bool qc_collect(GpuDecoder *G) {
+    if (G->qc_pending_n == 0) return true;
+    std::vector<int64_t> &v = G->D.qc.qual_sum;
+    const size_t base = v.size();
+    v.resize(base + (size_t)G->qc_pending_n);
+    const bool ok = hipMemcpy(v.data() + base, G->d_qc_sum, (size_t)G->qc_pending_n * 8, hipMemcpyDeviceToHost) == hipSuccess;
+    G->qc_pending_n = 0;
+    return ok;
+}
+
+// The request's result, once every batch has been emitted: waits for `stream`, takes the last batch's rows and the histogram
+// from the device and leaves them in the host-side result (coral_bamgpu_host -> coral_bam_qc_sizes / _fill).
+extern "C" int coral_bamgpu_qc_result(void *handle, void *stream_) {
+    GpuDecoder *G = (GpuDecoder *)handle;
+    if (!G || !G->qc_on) return CORAL_ERR_ARG;
+    if (!G->finished || G->have_cur) { set_error("coral_bamgpu_qc_result: the decode is not finished"); return CORAL_ERR_ARG; }
+    if (hipStreamSynchronize((hipStream_t)stream_) != hipSuccess || !qc_collect(G) ||
+        hipMemcpy(G->D.qc.hist, G->d_qc_hist, 256 * 8, hipMemcpyDeviceToHost) != hipSuccess) {
+        set_error("coral_bamgpu_qc_result: copy of the read-QC arrays failed");
+        return CORAL_ERR_HIP;
+    }
+    return CORAL_OK;
+}
+
 extern "C" int coral_bamgpu_start(void *handle, void *workspace, int64_t workspace_bytes) {
     GpuDecoder *G = (GpuDecoder *)handle;
     if (!G || !workspace || workspace_bytes < (int64_t)G->ws_bytes || (((uintptr_t)workspace) & 255)) return CORAL_ERR_ARG;
@@ -1923,6 +2079,7 @@ extern "C" int coral_bamgpu_start(void *handle, void *workspace, int64_t workspa
             (e = hipMemcpy(G->X.lin_off, G->D.idx.lin_off.data(), (n_ref + 1) * 8, hipMemcpyHostToDevice)) != hipSuccess)
             return bad("index request set-up", e);
     }
+    if (G->qc_on && (e = hipMemset(G->d_qc_hist, 0, 256 * 8)) != hipSuccess) return bad("read-QC request set-up", e);
     G->feeder = std::thread(feeder_main, G);
     G->worker = std::thread(worker_main, G);
     return CORAL_OK;
@@ -2164,6 +2321,7 @@ extern "C" int coral_bamgpu_emit(void *handle, uint32_t *cigar_dst, int64_t *cig
                   get(J.sa_text.data(), G->d_sa_text, J.sa_text.size()) && get(&na_count, G->d_na_count, 4);
         if (!ok || hipStreamSynchronize(stream) != hipSuccess) return fail(CORAL_ERR_HIP, std::string("copy of the batch's host fields failed: ") + hipGetErrorString(hipGetLastError()));
         G->t_wait_gpu += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_gpu0).count();
+        if (G->qc_on && !qc_collect(G)) return fail(CORAL_ERR_HIP, "copy of the read-QC rows failed");      // (of the batch in front)
         for (long long i = 0; i < n; ++i) has_seq[i] = has_seq[i] > 0 ? 1 : 0;       // (arrived as l_seq)
         if (G->idx_on) {                          // the batch's first record against the last one of the batch in front (inside a batch: k_bam_index)
             D.idx.note_order(IndexPartial::sort_word(tid[0], pos[0]), IndexPartial::sort_word(tid[n - 1], pos[n - 1]));
@@ -2224,6 +2382,25 @@ extern "C" int coral_bamgpu_emit(void *handle, uint32_t *cigar_dst, int64_t *cig
         hipLaunchKernelGGL(k_bam_cov_count, dim3(blocks), dim3(256), 0, stream, buf, n, G->M, G->cov, G->cov_threshold, item_off, G->cov_counts);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return fail(CORAL_ERR_HIP, std::string("window coverage launch failed: ") + hipGetErrorString(e));
+    }
+    if (n > 0 && G->qc_on) {
+        // read QC of the batch's records, behind the coverage kernels on the same stream and, like them, in front of ev_parsed.
+        // Item counts and offsets use the name / SA length arrays again (the coverage kernels in front have finished with them).
+        // Nothing is waited for here: the rows are fetched with the next batch's host fields (behind that emit's stream
+        // synchronisation, which any kernel queued here is in front of), or by coral_bamgpu_qc_result.
+        long long *n_items = G->M.name_len, *item_off = G->M.sa_len;
+        long long *rows = G->d_qc_sum;
+        hipLaunchKernelGGL(k_bam_qc_plan, dim3((unsigned)((n + 1 + WAVE - 1) / WAVE)), dim3(WAVE), 0, stream, buf, G->d_rec_start, n, G->M, rows, n_items);
+        size_t tmp = G->scan_tmp_bytes;
+        if (hipcub::DeviceScan::ExclusiveSum(G->d_scan_tmp, tmp, n_items, item_off, (int)(n + 1), stream) != hipSuccess)
+            return fail(CORAL_ERR_HIP, "scan of the read-QC work items failed");
+        // at most one item per record plus one per QC_SLICE bytes of the batch; one wave per workgroup, grid-stride beyond 8 per CU
+        const long long items = n + ((long long)CARRY_CAP + (long long)G->cur.infl_bytes) / QC_SLICE + 1;
+        const unsigned blocks = (unsigned)std::min<long long>(items, 2048);
+        hipLaunchKernelGGL(k_bam_qc, dim3(blocks), dim3(WAVE), 0, stream, buf, G->d_rec_start, n, G->M, item_off, (unsigned long long *)rows, G->d_qc_hist);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return fail(CORAL_ERR_HIP, std::string("read-QC launch failed: ") + hipGetErrorString(e));
+        G->qc_pending_n = n;
     }
     if (G->idx_on) {
         // the batch's part of the BAI index, behind the coverage kernels on the same stream: every per-record array of the parse

@@ -424,6 +424,20 @@ int coral_bam_index_fill(void *handle, int64_t *head_key, uint64_t *head_voff, u
                          int64_t *n_unmapped, uint64_t scalars[4]);
 int coral_bam_decode_spans(const char *path, int32_t n_threads, int32_t n_spans, const uint64_t *span_beg,
                            const uint64_t *span_end, void **handle);
+/* Read QC counted during the decode - replaces the one pass over every read of the reference's
+ * scripts/report_nanopore_qc.py:35-48 (len(sequence) and np.mean(quality) per read of the FASTQ the file was aligned from)
+ * and feeds its summary, scripts/report_nanopore_qc.py:70-74 (Q25 / Q50 / Q75 of both, quality_control_summary.tsv).
+ *   decode_range_qc  coral_bam_decode_range with a read-QC request.  A READ is a record with flag & 0x900 == 0 and l_seq > 0
+ *          (one per FASTQ record; mapped or not); a read whose first QUAL byte is 0xff has no quality.
+ *   qc_sizes -> records, reads; qc_fill copies, per read in file order, length (l_seq), qual_sum (sum of its QUAL bytes,
+ *          -1 without quality), mapq and flag; hist[256] = count of every QUAL byte value over the reads with quality;
+ *          counters = records, reads, records with flag 0x100, with flag 0x800, reads with flag 0x4, primary records
+ *          without SEQ, reads without quality, bases of all reads.  Integers only: mean quality of a read is
+ *          qual_sum / length on the host.  Results of consecutive byte ranges concatenate / add up. */
+int coral_bam_decode_range_qc(const char *path, int32_t n_threads, int32_t rank, int32_t world, void **handle);
+int coral_bam_qc_sizes(void *handle, int64_t sizes[2]);
+int coral_bam_qc_fill(void *handle, int32_t *length, int64_t *qual_sum, int32_t *mapq, int32_t *flag, int64_t hist[256],
+                      int64_t counters[8]);
 int coral_bam_decode_spans_cov(const char *path, int32_t n_threads, int32_t n_spans, const uint64_t *span_beg,
                                const uint64_t *span_end, int32_t n_seg, const int32_t *seg_tid, const int32_t *seg_start,
                                const int32_t *seg_end, int32_t quality_threshold, int32_t read_callback, void **handle);
@@ -468,6 +482,13 @@ int coral_bam_decode_spans_cov(const char *path, int32_t n_threads, int32_t n_sp
  *          across batches.  Without a request no kernel is added.
  *   index_result     after the last batch: waits for `stream`, leaves the partial index in the handle of `host`
  *          (coral_bam_index_sizes / _fill); fails when the records are not in coordinate order
+ *   qc               the read-QC request of coral_bam_decode_range_qc on the GPU (scripts/report_nanopore_qc.py:35-48 of the
+ *          reference): after open (not open_spans), before start and BEFORE the workspace is allocated - *workspace_bytes
+ *          is the new size.  Per batch k_bam_qc_plan, one scan and k_bam_qc read the batch's QUAL before the slot is reused
+ *          (one wave per 16 384 QUAL bytes of a read, aligned 16-byte loads, one 64-bit atomic per work item, the histogram
+ *          in LDS per workgroup).  Without a request no kernel is added and nothing more is allocated.
+ *   qc_result        after the last batch: waits for `stream`, leaves rows and histogram in the handle of `host`
+ *          (coral_bam_qc_sizes / _fill; scripts/report_nanopore_qc.py:70-74 is computed from them)
  * coral_bgzf_inflate: one inflate launch over caller-provided device buffers — desc = n_blocks x {src_off, src_len,
  * dst_off, isize} uint32 (raw DEFLATE streams in `comp`, which must be readable 4096 bytes beyond the last stream);
  * status[b] = 0 or the decoder's error code.
@@ -486,6 +507,8 @@ int coral_bamgpu_open_spans(const char *path, int32_t n_threads, int32_t n_spans
                             const uint64_t *span_end, int64_t batch_bytes, void **handle, int64_t *workspace_bytes);
 int coral_bamgpu_index(void *handle, int64_t *workspace_bytes);
 int coral_bamgpu_index_result(void *handle, void *stream);
+int coral_bamgpu_qc(void *handle, int64_t *workspace_bytes);
+int coral_bamgpu_qc_result(void *handle, void *stream);
 int coral_bamgpu_close(void *handle);
 int coral_bgzf_inflate(const uint8_t *comp, const uint32_t *desc, int32_t n_blocks, uint8_t *out, int32_t *status,
                        void *stream);

@@ -1,0 +1,319 @@
+"""Per-read length and base-quality statistics counted during the BAM decode (bam.read_qc, the `qc` mode): both pipelines against
+an INDEPENDENT restatement of the reference's scripts/report_nanopore_qc.py in this module.  The BAM is read with gzip + struct,
+and the script's own formulas (len, np.mean of the quality values, np.percentile) are applied to the primary records with SEQ —
+one per FASTQ record the file was aligned from.  (The script itself reads the FASTQ through pysam.FastxFile, which cannot be
+run here: parity with it is not pinned)"""
+import gzip
+import json
+import os
+import struct
+import warnings
+
+import numpy as np
+import pytest
+
+from coral_amd import bam, synth
+
+M, I, D, N, S, H, P, EQ, X = range(9)
+
+
+# ---- the restatement -----------------------------------------------------------------------------------------------------------
+def read_bam(path):
+    """Every record straight from the bytes: flag, mapq, l_seq, QUAL (the record's own n_cigar_op locates it)."""
+    raw = gzip.open(path, "rb").read()
+    assert raw[:4] == b"BAM\x01"
+    o = 8 + struct.unpack_from("<i", raw, 4)[0]
+    n_ref = struct.unpack_from("<i", raw, o)[0]
+    o += 4
+    for _ in range(n_ref):
+        o += 8 + struct.unpack_from("<i", raw, o)[0]
+    recs = []
+    while o < len(raw):
+        bs, _tid, _pos, l_name, mapq, _bin, n_cig, flag, l_seq = struct.unpack_from("<iiiBBHHHi", raw, o)
+        p = o + 36 + l_name + 4 * n_cig + (l_seq + 1) // 2
+        recs.append(dict(flag=flag, mapq=mapq, l_seq=l_seq, n_cig=n_cig, qual=np.frombuffer(raw, dtype=np.uint8, count=l_seq, offset=p)))
+        o += 4 + bs
+    return recs, len(raw)
+
+
+def restate(recs):
+    """What the script collects (lines 35-48) over the reads, plus the counters and the histogram as the issue words them."""
+    reads = [r for r in recs if r["flag"] & 0x900 == 0 and r["l_seq"] > 0]          # `if sequence:`
+    mean_lengths = [r["l_seq"] for r in reads]                                        # len(sequence)
+    with_q = [r for r in reads if r["qual"][0] != 0xFF]
+    mean_qualities = [np.mean(np.array(r["qual"].tolist())) for r in with_q]          # np.mean(np.array([ints]))
+    hist = np.zeros(256, dtype=np.int64)
+    for r in with_q:
+        hist += np.bincount(r["qual"], minlength=256)
+    counters = dict(n_records=len(recs), n_reads=len(reads), n_secondary=sum(1 for r in recs if r["flag"] & 0x100),
+                    n_supplementary=sum(1 for r in recs if r["flag"] & 0x800), n_unmapped=sum(1 for r in reads if r["flag"] & 4),
+                    n_no_seq=sum(1 for r in recs if r["flag"] & 0x900 == 0 and r["l_seq"] == 0), n_no_qual=len(reads) - len(with_q),
+                    total_bases=sum(mean_lengths))
+    return dict(reads=reads, mean_lengths=mean_lengths, mean_qualities=mean_qualities, hist=hist, counters=counters,
+                length=np.array(mean_lengths, dtype=np.int32),
+                qual_sum=np.array([int(r["qual"].astype(np.int64).sum()) if r["qual"][0] != 0xFF else -1 for r in reads], dtype=np.int64),
+                mapq=np.array([r["mapq"] for r in reads], dtype=np.int32), flag=np.array([r["flag"] for r in reads], dtype=np.int32))
+
+
+def restated_summary(want):
+    ml, mq = want["mean_lengths"], want["mean_qualities"]
+    out = {"length_Q%d" % q: float(np.percentile(ml, q)) for q in (25, 50, 75)}
+    out.update({"quality_Q%d" % q: float(np.percentile(mq, q)) for q in (25, 50, 75)})
+    out["mean_length"], out["mean_quality"] = float(np.mean(ml)), float(np.mean(mq))
+    half, run = sum(ml) / 2, 0
+    for ln in sorted(ml, reverse=True):                       # N50: the length at which the longest reads hold half the bases
+        run += ln
+        if run >= half:
+            out["n50"] = ln
+            break
+    out["total_bases"] = sum(ml)
+    return out
+
+
+# ---- test data -----------------------------------------------------------------------------------------------------------------
+LONG_READ = 300_000
+EDGE_QUAL = bytes([0, 93, 200, 254])
+
+
+def odd_records():
+    big = [(M, 3), (I, 1), (D, 2)] * 22000 + [(M, 5)]            # 66001 ops -> CG tag; the record's own n_cigar_op is 2
+    alns = [
+        dict(tid=7, pos=150_000, cigar=[(S, 5), (M, 50), (D, 70), (M, 30)], name="edgeq"),
+        dict(tid=7, pos=150_005, cigar=[(M, 120)], flag=0x100, name="secondary"),
+        dict(tid=7, pos=150_010, cigar=[(H, 50), (M, 100), (H, 30)], flag=0x800, name="supp_hard"),
+        dict(tid=7, pos=150_015, cigar=[(M, 60)], flag=4, name="unmapped", mapq=0),
+        dict(tid=7, pos=150_020, cigar=[(M, 200)], has_seq=0, name="noseq"),
+        dict(tid=7, pos=150_025, cigar=[(M, 90)], name="withq_a", mapq=13),
+        dict(tid=7, pos=150_026, cigar=[(M, 333)], name="noqual"),
+        dict(tid=7, pos=150_027, cigar=[(M, 91)], name="withq_b"),
+    ]
+    alns += [dict(tid=7, pos=150_030 + k, cigar=[(M, ln)], name="len%d" % ln, mapq=20 + k) for k, ln in enumerate((1, 15, 16, 17, 65))]
+    alns += [dict(tid=7, pos=150_070, cigar=big, name="longcigar"),
+             dict(tid=7, pos=150_080, cigar=[(S, 100), (M, LONG_READ - 100)], name="huge"),
+             dict(tid=7, pos=150_090, cigar=[(H, 10), (M, 77)], name="hard_primary")]
+    return synth.records_from_alignments(alns)
+
+
+def make_records(n=500):
+    return synth.merge_sorted(synth.generate(synth.scaled_config("tiny", n), "cpu"), odd_records())
+
+
+def writer_options(rec):
+    names = rec.materialise_names()
+    name_of = lambda i: names[int(rec.name_id[i])]
+    qlen = rec.qlen.numpy()
+
+    def qual(i):
+        nm, n = name_of(i), int(qlen[i])
+        if nm == "edgeq":
+            return (EDGE_QUAL * (n // 4 + 1))[:n]
+        if nm.startswith("len"):
+            return bytes((7 * k + 3) % 94 for k in range(n))
+        if nm == "huge":
+            k = np.arange(n, dtype=np.int64)
+            return ((k * k + 11 * k + 5) % 95).astype(np.uint8).tobytes()
+        return None
+    with_qual = lambda i: name_of(i) != "noqual" and (i % 4 != 2 or name_of(i).startswith("withq"))
+    return dict(qual=qual, with_qual=with_qual)
+
+
+@pytest.fixture(scope="module")
+def case(tmp_path_factory):
+    d = tmp_path_factory.mktemp("readqc")
+    rec = make_records()
+    opts = writer_options(rec)
+    path, small = str(d / "mixed.bam"), str(d / "mixed_small_blocks.bam")
+    bam.write_bam(rec, path, seed=5, fast_seq=True, **opts)
+    bam.write_bam(rec, small, seed=5, fast_seq=True, block_size=1500, empty_block_every=5, **opts)
+    recs, n_bytes = read_bam(path)
+    assert len(recs) == rec.n
+    none = str(d / "no_reads.bam")
+    bam.write_bam(synth.records_from_alignments([dict(tid=7, pos=100, cigar=[(M, 50)], flag=0x100, name="s"),
+                                                 dict(tid=7, pos=200, cigar=[(M, 50)], has_seq=0, name="p"),
+                                                 dict(tid=7, pos=300, cigar=[(H, 5), (M, 50)], flag=0x800, name="t")]), none, with_qual=True)
+    return dict(rec=rec, path=path, small=small, none=none, recs=recs, want=restate(recs), inflated_bytes=n_bytes)
+
+
+def host(path, **kw):
+    return bam.read_qc(path, device="cpu", **kw)
+
+
+def assert_equal(got, want, what=""):
+    for k in ("length", "qual_sum", "mapq", "flag"):
+        a = getattr(got, k)
+        assert a.dtype == want[k].dtype and np.array_equal(a, want[k]), (what, k)
+    assert got.base_quality_hist.dtype == np.int64 and np.array_equal(got.base_quality_hist, want["hist"]), what
+    assert got.counters == want["counters"], what
+    for k, v in want["counters"].items():
+        assert getattr(got, k) == v
+
+
+def assert_same(a, b, what=""):
+    for k in ("length", "qual_sum", "mapq", "flag", "base_quality_hist"):
+        assert np.array_equal(getattr(a, k), getattr(b, k)), (what, k)
+    assert a.counters == b.counters, what
+
+
+# ---- the restatement sees what was planted ---------------------------------------------------------------------------------------
+def test_restatement_reads_the_planted_records(case):
+    recs, want = case["recs"], case["want"]
+    c = want["counters"]
+    assert c["n_secondary"] >= 1 and c["n_supplementary"] >= 1 and c["n_unmapped"] >= 1 and c["n_no_seq"] >= 1
+    assert 50 < c["n_no_qual"] < c["n_reads"] - 100 and c["n_reads"] < c["n_records"]
+    assert {1, 15, 16, 17, 65, 77, LONG_READ} <= set(want["mean_lengths"])
+    assert any(r["n_cig"] == 2 and r["l_seq"] == 88005 for r in recs)                 # the CG-tag record: placeholder CIGAR of 2 ops
+    assert all(want["hist"][v] > 0 for v in (0, 93, 200, 254)) and want["hist"][255] == 0
+    assert case["inflated_bytes"] > 2 * (1 << 20)                                     # several 1 MiB batches
+    i = want["mean_lengths"].index(LONG_READ)
+    assert want["qual_sum"][i] > 10_000_000
+
+
+# ---- host pipeline ---------------------------------------------------------------------------------------------------------------
+def test_host_pipeline_matches_the_restatement(case):
+    got = host(case["path"], n_threads=3)
+    assert_equal(got, case["want"])
+    assert bam.LAST_DECODE["blocks"] > 0 and bam.LAST_DECODE["uncompressed_bytes"] > 0
+
+
+def test_summary_is_bit_equal_to_the_scripts_floats(case):
+    got, want = host(case["path"]).summary(), restated_summary(case["want"])
+    assert set(got) == set(want)
+    for k, v in want.items():
+        assert type(got[k]) is type(v) and got[k] == v, k
+    assert np.array_equal(host(case["path"]).mean_qualities(), np.array(case["want"]["mean_qualities"]))
+
+
+def test_write_summary_is_what_pandas_writes(case, tmp_path):
+    pd = pytest.importorskip("pandas")
+    want = case["want"]
+    ml, mq = want["mean_lengths"], want["mean_qualities"]
+    frame = pd.DataFrame(columns=['Q25', 'Q50', 'Q75'])                                # the script's lines 70-74
+    frame.loc['mean_length'] = [np.percentile(ml, 25), np.percentile(ml, 50), np.percentile(ml, 75)]
+    frame.loc['mean_sequence_quality'] = [np.percentile(mq, 25), np.percentile(mq, 50), np.percentile(mq, 75)]
+    ref = str(tmp_path / "pandas.tsv")
+    frame.to_csv(ref, sep='\t')
+    out = host(case["path"]).write_summary(str(tmp_path / "quality_control_summary.tsv"))
+    assert open(out, "rb").read() == open(ref, "rb").read()
+
+
+def test_write_summary_literal(tmp_path):
+    qc = bam.ReadQC([10, 20, 30, 40], [100, 400, -1, 1200], [60] * 4, [0, 16, 0, 4], np.zeros(256, dtype=np.int64),
+                    dict(n_records=4, n_reads=4, n_secondary=0, n_supplementary=0, n_unmapped=1, n_no_seq=0, n_no_qual=1, total_bases=100))
+    out = qc.write_summary(str(tmp_path / "s.tsv"))
+    assert open(out, "rb").read() == b"\tQ25\tQ50\tQ75\nmean_length\t17.5\t25.0\t32.5\nmean_sequence_quality\t15.0\t20.0\t25.0\n"
+    s = qc.summary()
+    assert s["n50"] == 30 and s["total_bases"] == 100 and s["mean_length"] == 25.0 and s["mean_quality"] == 20.0
+
+
+def test_host_pipeline_ranges_merge_to_the_whole(case):
+    whole = host(case["path"], n_threads=2)
+    for path in (case["path"], case["small"]):
+        parts = [host(path, n_threads=2, rank=r, world=3) for r in range(3)]
+        assert sum(p.n_records > 0 for p in parts) >= 2
+        assert_same(bam.merge_read_qc(parts), whole, path)
+    assert_equal(bam.merge_read_qc([host(case["small"], rank=r, world=3) for r in range(3)]), case["want"])
+
+
+def test_host_pipeline_small_blocks_and_empty_blocks(case):
+    assert_equal(host(case["small"], n_threads=2), case["want"])
+
+
+def test_qc_command_line(case, tmp_path, capsys):
+    from coral_amd import CoRAL
+    d = str(tmp_path / "out")
+    wrote = CoRAL.main(["qc", "--lr_bam", case["path"], "--output_dir", d, "--device", "cpu"])
+    printed = capsys.readouterr().out
+    want = {"quality_control_summary.tsv", "read_qc.json"}
+    try:
+        import matplotlib  # noqa: F401
+        want |= {"mean_length_histogram.png", "mean_sequence_quality_histogram.png"}
+    except ImportError:
+        pass
+    assert set(os.listdir(d)) == want and {os.path.basename(w) for w in wrote} == want
+    assert all(("Wrote %s" % w) in printed for w in wrote)
+    with open(os.path.join(d, "read_qc.json")) as fp:
+        js = json.load(fp)
+    assert js["counters"] == case["want"]["counters"] and js["base_quality_hist"] == case["want"]["hist"].tolist()
+    assert js["summary"] == restated_summary(case["want"])
+    assert open(os.path.join(d, "quality_control_summary.tsv")).read() == host(case["path"]).summary_text()
+    d2 = str(tmp_path / "out2")
+    CoRAL.main(["qc", "--lr_bam", case["path"], "--output_dir", d2, "--device", "cpu", "--no_plots"])
+    assert set(os.listdir(d2)) == {"quality_control_summary.tsv", "read_qc.json"}
+
+
+def test_file_without_reads(case):
+    recs, _ = read_bam(case["none"])
+    got = host(case["none"])
+    assert_equal(got, restate(recs))
+    assert len(got.length) == 0 and got.n_reads == 0 and got.n_records == 3 and got.base_quality_hist.sum() == 0
+    with warnings.catch_warnings():
+        warnings.simplefilter("error")
+        with pytest.raises(ValueError, match="no read"):
+            got.summary()
+        with pytest.raises(ValueError, match="no read"):
+            got.write_summary(os.devnull)
+
+
+def test_write_bam_qual_option_checks_the_length(tmp_path):
+    rec = synth.records_from_alignments([dict(tid=7, pos=100, cigar=[(M, 50)], name="a")])
+    with pytest.raises(ValueError):
+        bam.write_bam(rec, str(tmp_path / "x.bam"), qual=lambda i: b"\x01" * 49)
+
+
+# ---- GPU pipeline ----------------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+def test_gpu_pipeline_matches_host_and_restatement(case):
+    h = host(case["path"], n_threads=2)
+    assert_equal(h, case["want"], "host")
+    for path in (case["path"], case["small"]):
+        for batch in (0, 1 << 20):                # 1 MiB batches: the 300 000-base read and others straddle them
+            got = bam.read_qc(path, device="cuda:0", batch_bytes=batch)
+            assert_equal(got, case["want"], (path, batch))
+            assert_same(got, h, (path, batch))
+            assert bam.LAST_DECODE["where"] == "gpu" and (batch == 0 or bam.LAST_DECODE["batches"] >= 3)
+    assert_equal(bam.read_qc(case["none"], device="cuda:0"), restate(read_bam(case["none"])[0]))
+
+
+@pytest.mark.gpu
+def test_gpu_pipeline_ranges_merge_to_the_whole(case):
+    for path, batch in ((case["path"], 0), (case["small"], 1 << 20)):
+        parts = [bam.read_qc(path, device="cuda:0", rank=r, world=3, batch_bytes=batch) for r in range(3)]
+        assert_equal(bam.merge_read_qc(parts), case["want"], path)
+
+
+RECORD_COLUMNS = ("tid", "pos", "end", "flag", "mapq", "qlen", "has_seq", "nm", "name_id", "n_cigar", "cigar_off", "cigar", "sa_off", "sa",
+                  "sa_nm", "nonacgt_rec", "nonacgt_pos")
+
+
+def assert_same_records(a, b):
+    assert a.n == b.n and a.n_names == b.n_names and a.header_chroms == b.header_chroms
+    for k in RECORD_COLUMNS:
+        assert np.array_equal(getattr(a, k).cpu().numpy(), getattr(b, k).cpu().numpy()), k
+    assert a.materialise_names() == b.materialise_names()
+
+
+@pytest.mark.gpu
+def test_gpu_request_leaves_the_records_alone(case):
+    plain = bam.decode_bam_gpu(case["small"], "cuda:0", batch_bytes=1 << 20)
+    rec, _, _, qc = bam._decode_gpu(case["small"], "cuda:0", None, 0, 1, 1 << 20, qc=True)
+    assert_same_records(rec, plain)
+    assert_equal(qc, case["want"])
+    assert bam._decode_gpu(case["small"], "cuda:0", None, 0, 1, 1 << 20)[3] is None
+
+
+@pytest.mark.gpu
+def test_gpu_three_requests_at_once(case):
+    rec = case["rec"]
+    windows = [("chr8", 149_000, 152_000), ("chr8", 150_000, 150_100), ("chr8", 0, 1 << 28)]
+    segs, first, last = bam.coverage_segments(windows, rec.header_chroms)
+    for batch in (0, 1 << 20):
+        alone_cov = bam._decode_gpu(case["path"], "cuda:0", None, 0, 1, batch, coverage=(segs, 20, 0), records=False)[1]
+        alone_idx = bam._decode_gpu(case["path"], "cuda:0", None, 0, 1, batch, records=False, index=True)[2]
+        plain = bam.decode_bam_gpu(case["path"], "cuda:0", batch_bytes=batch)
+        got_rec, cov, idx, qc = bam._decode_gpu(case["path"], "cuda:0", None, 0, 1, batch, coverage=(segs, 20, 0), index=True, qc=True)
+        assert alone_cov.sum() > 0 and np.array_equal(cov, alone_cov)
+        assert set(idx) == set(alone_idx)
+        for k, v in alone_idx.items():
+            assert np.array_equal(idx[k], v), k
+        assert_same_records(got_rec, plain)
+        assert_equal(qc, case["want"], batch)
