@@ -4,6 +4,9 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
+
+import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libcoral_hip.so")
@@ -16,6 +19,33 @@ class CoralHipError(RuntimeError):
 class coral_records_t(C.Structure):
     _fields_ = [("n_rec", C.c_int64), ("tid", C.c_void_p), ("pos", C.c_void_p), ("end", C.c_void_p),
                 ("flagmq", C.c_void_p), ("n_cigar", C.c_void_p), ("cigar_off", C.c_void_p), ("cigar", C.c_void_p)]
+
+
+class coral_bam_request_t(C.Structure):
+    _fields_ = [("rank", C.c_int32), ("world", C.c_int32), ("n_spans", C.c_int32), ("span_beg", C.c_void_p), ("span_end", C.c_void_p),
+                ("n_seg", C.c_int32), ("seg_tid", C.c_void_p), ("seg_start", C.c_void_p), ("seg_end", C.c_void_p),
+                ("quality_threshold", C.c_int32), ("read_callback", C.c_int32), ("want_index", C.c_int32), ("want_qc", C.c_int32)]
+
+
+def bam_request(rank: int = 0, world: int = 1, spans=None, coverage=None, index: bool = False, qc: bool = False) -> coral_bam_request_t:
+    """The request of a BAM decode: ``spans`` uint64 [K][2] virtual offsets (None: the byte range), ``coverage`` = (segments int32
+    [3][S], quality threshold, read_callback code) or None.  The struct keeps the contiguous arrays it points into alive; the
+    rules are the library's to check."""
+    req = coral_bam_request_t(rank=rank, world=world, n_spans=-1, n_seg=-1, want_index=int(index), want_qc=int(qc))
+    req.arrays = []
+
+    def pointer(a, dtype):
+        req.arrays.append(np.ascontiguousarray(a, dtype=dtype))
+        return req.arrays[-1].ctypes.data
+    if spans is not None:
+        spans = np.asarray(spans, dtype=np.uint64).reshape(-1, 2)
+        req.n_spans, req.span_beg, req.span_end = len(spans), pointer(spans[:, 0], np.uint64), pointer(spans[:, 1], np.uint64)
+    if coverage is not None:
+        segs, req.quality_threshold, req.read_callback = coverage
+        segs = np.asarray(segs, dtype=np.int32).reshape(3, -1)
+        req.n_seg = segs.shape[1]
+        req.seg_tid, req.seg_start, req.seg_end = (pointer(row, np.int32) for row in segs)
+    return req
 
 
 _lib = None
@@ -42,69 +72,46 @@ def lib():
     L.coral_point_cover.argtypes = [R, C.c_int32, P, P, C.c_int32, P, P, C.c_uint32, P]
     L.coral_read_counter.argtypes = [P, C.POINTER(C.c_uint32), P]
     L.coral_first_seen_rows.argtypes = [C.c_int64, C.c_int32, P, P]
-    L.coral_first_seen_rows.restype = C.c_int
     L.coral_bp_pair_table.argtypes = [C.c_int32, C.c_int32, P, P, P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P, P]
-    L.coral_bp_pair_table.restype = C.c_int
     L.coral_search_create.argtypes = [C.c_int64, C.c_int64] + [P] * 9 + [C.c_int64, P, P, P, C.c_int32, P, P, P]
     L.coral_search_create.restype = C.c_void_p
     L.coral_search_free.argtypes = [C.c_void_p]
-    L.coral_search_free.restype = C.c_int
     L.coral_search_error.argtypes = [C.c_void_p]
     L.coral_search_error.restype = C.c_char_p
     PI64, PF64, PI32 = C.POINTER(C.POINTER(C.c_int64)), C.POINTER(C.POINTER(C.c_double)), C.POINTER(C.POINTER(C.c_int32))
     L.coral_search_result.argtypes = [C.c_void_p, C.POINTER(C.c_int64), PI64, C.POINTER(C.c_int64), PI64, C.POINTER(C.c_int64), PI64,
                                       PF64, PI64, PI32]
-    L.coral_search_result.restype = C.c_int
     L.coral_search_step.argtypes = [C.c_void_p] + [C.c_int64] * 5
-    L.coral_search_step.restype = C.c_int
     L.coral_search_prefetch.argtypes = [C.c_void_p] + [C.c_int64] * 5
-    L.coral_search_prefetch.restype = C.c_int
     L.coral_search_params.argtypes = [C.c_void_p, C.c_double, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_int32]
-    L.coral_search_params.restype = C.c_int
     L.coral_search_bfs.argtypes = [C.c_void_p, C.c_int32, P, P, P, P, P, C.c_double, C.c_int64, C.c_int32]
-    L.coral_search_bfs.restype = C.c_int
     L.coral_search_bfs_get.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
-    L.coral_search_bfs_get.restype = C.c_int
     L.coral_search_within.argtypes = [C.c_void_p, C.c_int32, P, P, P]
-    L.coral_search_within.restype = C.c_int
     L.coral_search_between.argtypes = [C.c_void_p, C.c_int64, P] + [C.c_int64] * 6
-    L.coral_search_between.restype = C.c_int
     L.coral_sa_table.argtypes = [C.c_int32, P, P, P, P, C.c_int32, C.c_int32, P, P, P, P, C.c_int64, P, P, P, P, P,
                                  C.POINTER(C.c_int32), P]
-    L.coral_sa_table.restype = C.c_int
     L.coral_sa_last_error.restype = C.c_char_p
     L.coral_hash_rows.argtypes = [C.c_int32, P, C.c_int32, P, P, P, P, P, C.c_int32, P, C.c_int64, P, P, P, P, C.POINTER(C.c_int32), P]
-    L.coral_hash_rows.restype = C.c_int
     L.coral_pyset_batch_create.argtypes = [C.c_int64, P, P, P, C.c_int32, P]
     L.coral_pyset_batch_create.restype = C.c_void_p
     L.coral_pyset_union_order.argtypes = [C.c_void_p, C.c_int32, P, P, C.POINTER(C.c_int32)]
-    L.coral_pyset_union_order.restype = C.c_int
     L.coral_pyset_batch_free.argtypes = [C.c_void_p]
-    L.coral_pyset_batch_free.restype = C.c_int
     L.coral_call_breakpoints.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_int64, C.c_int64, C.c_double,
                                          C.c_int32] + [C.c_void_p] * 10
-    L.coral_call_breakpoints.restype = C.c_int
     L.coral_nm_stats.argtypes = [C.c_int64] + [C.c_void_p] * 8
-    L.coral_nm_stats.restype = C.c_int
     L.coral_reach_create.argtypes = [C.c_int64] + [C.c_void_p] * 6 + [C.c_int64] * 4 + [C.c_void_p, C.c_void_p]
     L.coral_reach_create.restype = C.c_void_p
     L.coral_reach_keys.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    L.coral_reach_keys.restype = C.c_int
     L.coral_concordant_counts.argtypes = [C.c_int32, P, P, P, C.c_int64, P, C.c_int64, C.c_int64, P, P, P]
-    L.coral_concordant_counts.restype = C.c_int
     L.coral_independent_rows.argtypes = [C.c_int32, C.c_int32, P, P, C.c_double]
-    L.coral_independent_rows.restype = C.c_int
     L.coral_cn_solve.argtypes = [C.c_int32, C.c_int32, P, P, P, P, C.c_int32, P, P, C.POINTER(C.c_int32)]
-    L.coral_cn_solve.restype = C.c_int
     L.coral_cluster_first_fit.argtypes = [C.c_int64, P, P, C.c_int64, P, C.POINTER(C.c_int32)]
-    L.coral_cluster_first_fit.restype = C.c_int
     L.coral_bam_decode_open.argtypes = [C.c_char_p, C.c_int32, C.POINTER(C.c_void_p)]
     L.coral_bam_decode_sizes.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
     L.coral_bam_decode_fill.argtypes = [C.c_void_p] + [P] * 21
     L.coral_bam_decode_close.argtypes = [C.c_void_p]
     L.coral_bam_last_error.restype = C.c_char_p
     L.coral_names_unify.argtypes = [C.c_int32, P, P, P, P, P, P, C.POINTER(C.c_int64), C.c_int32]
-    L.coral_names_unify.restype = C.c_int
     L.coral_bam_decode_range.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
     L.coral_bam_decode_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_double)]
     L.coral_bam_write.argtypes = [C.c_char_p, C.c_int64] + [P] * 9 + [P, P, P, P, P, C.c_int64, P, P, P, C.c_int32, P, P, C.c_uint32,
@@ -117,40 +124,18 @@ def lib():
     L.coral_bamgpu_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_double)]
     L.coral_bamgpu_close.argtypes = [C.c_void_p]
     L.coral_bgzf_inflate.argtypes = [P, P, C.c_int32, P, P, P]
-    L.coral_bam_decode_range_cov.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P, P, P, C.c_int32, C.c_int32,
-                                             C.POINTER(C.c_void_p)]
+    Q = C.POINTER(coral_bam_request_t)
+    L.coral_bam_decode_request.argtypes = [C.c_char_p, C.c_int32, Q, C.POINTER(C.c_void_p)]
     L.coral_bam_coverage_result.argtypes = [C.c_void_p, C.c_int32, P]
-    L.coral_bamgpu_coverage.argtypes = [C.c_void_p, C.c_int32, P, P, P, C.c_int32, C.c_int32, P]
-    L.coral_bamgpu_coverage_result.argtypes = [C.c_void_p, C.c_int32, P, P]
-    L.coral_bam_decode_range_idx.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
     L.coral_bam_index_sizes.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
     L.coral_bam_index_fill.argtypes = [C.c_void_p, P, P, P, P, P, C.POINTER(C.c_uint64)]
-    L.coral_bam_decode_spans.argtypes = [C.c_char_p, C.c_int32, C.c_int32, P, P, C.POINTER(C.c_void_p)]
-    L.coral_bam_decode_spans_cov.argtypes = [C.c_char_p, C.c_int32, C.c_int32, P, P, C.c_int32, P, P, P, C.c_int32, C.c_int32,
-                                             C.POINTER(C.c_void_p)]
-    L.coral_bamgpu_open_spans.argtypes = [C.c_char_p, C.c_int32, C.c_int32, P, P, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
-    L.coral_bamgpu_index.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
-    L.coral_bamgpu_index_result.argtypes = [C.c_void_p, P]
-    L.coral_bam_decode_range_qc.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
     L.coral_bam_qc_sizes.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
     L.coral_bam_qc_fill.argtypes = [C.c_void_p, P, P, P, P, P, C.POINTER(C.c_int64)]
-    L.coral_bamgpu_qc.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
-    L.coral_bamgpu_qc_result.argtypes = [C.c_void_p, P]
-    for name in ("coral_bam_decode_range_qc", "coral_bam_qc_sizes", "coral_bam_qc_fill", "coral_bamgpu_qc", "coral_bamgpu_qc_result"):
-        getattr(L, name).restype = C.c_int
-    for name in ("coral_bam_decode_range_idx", "coral_bam_index_sizes", "coral_bam_index_fill", "coral_bam_decode_spans",
-                 "coral_bam_decode_spans_cov", "coral_bamgpu_open_spans", "coral_bamgpu_index", "coral_bamgpu_index_result"):
-        getattr(L, name).restype = C.c_int
-    for name in ("coral_bam_decode_range_cov", "coral_bam_coverage_result", "coral_bamgpu_coverage", "coral_bamgpu_coverage_result"):
-        getattr(L, name).restype = C.c_int
-    for name in ("coral_bamgpu_open", "coral_bamgpu_start", "coral_bamgpu_next", "coral_bamgpu_emit", "coral_bamgpu_host",
-                 "coral_bamgpu_stats", "coral_bamgpu_close", "coral_bgzf_inflate"):
-        getattr(L, name).restype = C.c_int
-    for name in ("coral_bam_decode_open", "coral_bam_decode_sizes", "coral_bam_decode_fill", "coral_bam_decode_close",
-                 "coral_bam_decode_range", "coral_bam_decode_stats", "coral_bam_write"):
-        getattr(L, name).restype = C.c_int
-    for name in ("coral_cigar_scan", "coral_segment_coverage", "coral_point_cover", "coral_read_counter"):
-        getattr(L, name).restype = C.c_int
+    L.coral_bamgpu_open_request.argtypes = [C.c_char_p, C.c_int32, C.c_int64, Q, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
+    L.coral_bamgpu_finish.argtypes = [C.c_void_p, P]
+    with open(os.path.join(os.path.dirname(_HERE), "include", "coral_hip.h")) as fp:
+        for name in re.findall(r"^int (coral_\w+)\(", fp.read(), re.M):      # every prototype of the header that returns int
+            getattr(L, name).restype = C.c_int
     _lib = L
     return L
 
@@ -172,7 +157,6 @@ def check_pyset_replay():
     if _pyset_checked:
         return
     import random
-    import numpy as np
     L = lib()
     rnd = random.Random(12345)
     names = ["read%07d_%d" % (rnd.randrange(10 ** 7), k) for k in range(900)]

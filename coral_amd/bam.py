@@ -7,6 +7,7 @@ real coordinate-sorted BAM (htslib / pysam are not available offline); it is not
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import gzip
 import numbers
@@ -42,22 +43,7 @@ def decode_bam(path: str, n_threads: Optional[int] = None, rank: int = 0, world:
     """Decode the BAM file (or, with ``world`` > 1, the ``rank``-th of ``world`` byte ranges of it: one process per GPU, every
     rank inflates and parses only its share; consecutive ranges neither drop nor repeat a record).  Read-name ids are local
     to the returned records."""
-    L = _lib.lib()
-    if n_threads is None:
-        n_threads = default_threads()
-    h = C.c_void_p()
-    rc = L.coral_bam_decode_range(path.encode(), n_threads, rank, world, C.byref(h))
-    if rc != 0:
-        raise _lib.CoralHipError("coral_bam_decode(%s) failed (%d): %s" % (path, rc, L.coral_bam_last_error().decode()))
-    st, secs = (C.c_int64 * 3)(), C.c_double(0.0)
-    L.coral_bam_decode_stats(h, st, C.byref(secs))
-    LAST_DECODE.clear()
-    LAST_DECODE.update(seconds=float(secs.value), compressed_bytes=int(st[0]), uncompressed_bytes=int(st[1]), blocks=int(st[2]),
-                       threads=int(n_threads))
-    try:
-        return _records_from_handle(L, h, None, 0)
-    finally:
-        L.coral_bam_decode_close(h)
+    return _decode(path, "cpu", n_threads=n_threads, rank=rank, world=world).records
 
 
 def _on_gpu(device) -> bool:
@@ -180,37 +166,68 @@ def decode_bam_gpu(path: str, device="cuda:0", n_threads: Optional[int] = None, 
     """The same result as ``decode_bam`` with the inflate and the record parsing on the GPU (csrc/coral_bamgpu.hip): the host
     only reads the file and uploads COMPRESSED bytes; the CIGAR words of the returned Records are a device tensor (they never
     exist in host memory), everything else is host-side as before.  ``batch_bytes``: inflated bytes per batch (0 = the default, 2.52 GiB)."""
-    return _decode_gpu(path, device, n_threads, rank, world, batch_bytes)[0]
+    if torch.device(device).type != "cuda":
+        raise _lib.CoralHipError("decode_bam_gpu needs a GPU device (the CPU pipeline is decode_bam)")
+    return _decode_gpu(path, device, n_threads, batch_bytes, _lib.bam_request(rank, world), True).records      # (whatever CORAL_BAM_DECODE says)
 
 
-def _decode_gpu(path: str, device, n_threads: Optional[int], rank: int, world: int, batch_bytes: int, coverage=None, records=True,
-                spans=None, index=False, qc=False):
-    """decode_bam_gpu; with ``coverage`` = (segments int32 [3][S], quality threshold, read_callback code) the window-coverage
-    request of coral_bamgpu_coverage rides along and its S int64 counts come back as the second result (records: None
-    unless ``records``).  ``spans`` (uint64 [K][2] virtual offsets): only the records that start inside them
-    (coral_bamgpu_open_spans).  ``index``: the index request of coral_bamgpu_index rides along; its partial index is the
-    third result."""
+DecodeResult = collections.namedtuple("DecodeResult", "records counts index qc")      # what _decode was not asked for is None
+
+
+def _decode(path: str, device, *, n_threads: Optional[int] = None, rank: int = 0, world: int = 1, batch_bytes: int = 0, spans=None,
+            coverage=None, index=False, qc=False, records=True) -> DecodeResult:
+    """One decode of the ``rank``-th of ``world`` byte ranges, or of the records that start inside ``spans`` (uint64 [K][2] virtual
+    offsets), with what rides along: ``coverage`` = (segments int32 [3][S], quality threshold, read_callback code) gives the S
+    int64 ``counts``, ``index`` the partial BAI index, ``qc`` the ``ReadQC``; ``records`` False leaves the Records out.  On the GPU
+    pipeline when ``_on_gpu(device)``, else on the host."""
+    req = _lib.bam_request(rank, world, spans, coverage, index, qc)
+    if _on_gpu(device):
+        return _decode_gpu(path, device, n_threads, batch_bytes, req, records)
+    L = _lib.lib()
+    if n_threads is None:
+        n_threads = default_threads()
+    h = C.c_void_p()
+    rc = L.coral_bam_decode_request(path.encode(), n_threads, C.byref(req), C.byref(h))
+    if rc != 0:
+        raise _lib.CoralHipError("coral_bam_decode_request(%s) failed (%d): %s" % (path, rc, L.coral_bam_last_error().decode()))
+    try:
+        _host_stats(L, h, n_threads)
+        return _result_from_handle(L, h, req, records, None, 0)
+    finally:
+        L.coral_bam_decode_close(h)
+
+
+def _host_stats(L, h, n_threads):
+    st, secs = (C.c_int64 * 3)(), C.c_double(0.0)
+    L.coral_bam_decode_stats(h, st, C.byref(secs))
+    LAST_DECODE.clear()
+    LAST_DECODE.update(seconds=float(secs.value), compressed_bytes=int(st[0]), uncompressed_bytes=int(st[1]), blocks=int(st[2]),
+                       threads=int(n_threads))
+
+
+def _result_from_handle(L, h, req, records: bool, cigar, cigar_words: int) -> DecodeResult:
+    """What ``req`` asked for, read from a decode handle of either pipeline (``cigar``: see _records_from_handle)."""
+    counts = None
+    if req.n_seg >= 0:
+        counts = np.zeros(req.n_seg, dtype=np.int64)
+        _lib.check(L.coral_bam_coverage_result(h, req.n_seg, counts.ctypes.data), "coral_bam_coverage_result")
+    return DecodeResult(_records_from_handle(L, h, cigar, cigar_words) if records else None, counts,
+                        _index_partial_from_handle(L, h) if req.want_index else None, _read_qc_from_handle(L, h) if req.want_qc else None)
+
+
+def _decode_gpu(path: str, device, n_threads: Optional[int], batch_bytes: int, req, records: bool) -> DecodeResult:
+    """The GPU pipeline of _decode: coral_bamgpu_open_request, the batches, coral_bamgpu_finish."""
     L = _lib.lib()
     dev = torch.device(device)
-    if dev.type != "cuda":
-        raise _lib.CoralHipError("decode_bam_gpu needs a GPU device (the CPU pipeline is decode_bam)")
     torch.cuda.set_device(dev)
     if n_threads is None:
         n_threads = default_threads()
+    fail = lambda what, rc: _lib.CoralHipError("%s(%s) failed (%d): %s" % (what, path, rc, L.coral_bam_last_error().decode()))
     h, ws_bytes = C.c_void_p(), C.c_int64(0)
-    if spans is None:
-        rc = L.coral_bamgpu_open(path.encode(), n_threads, rank, world, batch_bytes, C.byref(h), C.byref(ws_bytes))
-    else:
-        sp_beg, sp_end = np.ascontiguousarray(spans[:, 0], dtype=np.uint64), np.ascontiguousarray(spans[:, 1], dtype=np.uint64)
-        rc = L.coral_bamgpu_open_spans(path.encode(), n_threads, len(spans), sp_beg.ctypes.data, sp_end.ctypes.data, batch_bytes,
-                                       C.byref(h), C.byref(ws_bytes))
+    rc = L.coral_bamgpu_open_request(path.encode(), n_threads, batch_bytes, C.byref(req), C.byref(h), C.byref(ws_bytes))
     if rc != 0:
-        raise _lib.CoralHipError("coral_bamgpu_open(%s) failed (%d): %s" % (path, rc, L.coral_bam_last_error().decode()))
+        raise fail("coral_bamgpu_open_request", rc)
     try:
-        if index and L.coral_bamgpu_index(h, C.byref(ws_bytes)) != 0:
-            raise _lib.CoralHipError("coral_bamgpu_index(%s) failed: %s" % (path, L.coral_bam_last_error().decode()))
-        if qc and L.coral_bamgpu_qc(h, C.byref(ws_bytes)) != 0:
-            raise _lib.CoralHipError("coral_bamgpu_qc(%s) failed: %s" % (path, L.coral_bam_last_error().decode()))
         ws = torch.empty(int(ws_bytes.value) + 256, dtype=torch.uint8, device=dev)
         base = (ws.data_ptr() + 255) & ~255
         stream = torch.cuda.current_stream(dev).cuda_stream
@@ -218,17 +235,6 @@ def _decode_gpu(path: str, device, n_threads: Optional[int], rank: int, world: i
         # decoder's feeder thread and its own streams start writing into the workspace at once.  Let whatever the current stream
         # still has queued (possibly on the block's previous owner) finish first — once per decode.
         torch.cuda.current_stream(dev).synchronize()
-        fail = lambda what, rc: _lib.CoralHipError("%s(%s) failed (%d): %s" % (what, path, rc, L.coral_bam_last_error().decode()))
-        counts = None
-        if coverage is not None:
-            segs, thr, cb = coverage
-            d_segs = torch.from_numpy(np.ascontiguousarray(segs, dtype=np.int32)).to(dev)
-            d_counts = torch.zeros(max(segs.shape[1], 1), dtype=torch.int64, device=dev)
-            torch.cuda.synchronize(dev)
-            S = int(segs.shape[1])
-            rc = L.coral_bamgpu_coverage(h, S, d_segs[0].data_ptr(), d_segs[1].data_ptr(), d_segs[2].data_ptr(), thr, cb, d_counts.data_ptr())
-            if rc != 0:
-                raise fail("coral_bamgpu_coverage", rc)
         rc = L.coral_bamgpu_start(h, base, int(ws_bytes.value))
         if rc != 0:
             raise fail("coral_bamgpu_start", rc)
@@ -248,19 +254,9 @@ def _decode_gpu(path: str, device, n_threads: Optional[int], rank: int, world: i
             if words:
                 pieces.append(piece[:words])
                 total += words
-        if coverage is not None:
-            counts = np.zeros(S, dtype=np.int64)
-            rc = L.coral_bamgpu_coverage_result(h, S, counts.ctypes.data, stream)
-            if rc != 0:
-                raise fail("coral_bamgpu_coverage_result", rc)
-        if index:
-            rc = L.coral_bamgpu_index_result(h, stream)
-            if rc != 0:
-                raise fail("coral_bamgpu_index_result", rc)
-        if qc:
-            rc = L.coral_bamgpu_qc_result(h, stream)
-            if rc != 0:
-                raise fail("coral_bamgpu_qc_result", rc)
+        rc = L.coral_bamgpu_finish(h, stream)
+        if rc != 0:
+            raise fail("coral_bamgpu_finish", rc)
         cigar = torch.cat(pieces) if len(pieces) > 1 else (pieces[0] if pieces else torch.zeros(0, dtype=torch.int32, device=dev))
         del pieces
         dh = C.c_void_p()
@@ -277,9 +273,7 @@ def _decode_gpu(path: str, device, n_threads: Optional[int], rank: int, world: i
                            nonacgt_records_fetched=int(gst[2]), batch_bytes=int(gst[3]), host_seconds=float(gsecs[1]), read_seconds=float(gsecs[2]),
                            setup_seconds=float(gsecs[3]), waited_for_file_seconds=float(gsecs[4]), waited_for_gpu_seconds=float(gsecs[5]),
                            workspace_bytes=int(ws_bytes.value))
-        partial = _index_partial_from_handle(L, dh) if index else None
-        read_qc_ = _read_qc_from_handle(L, dh) if qc else None
-        return (_records_from_handle(L, dh, cigar, total) if records else None), counts, partial, read_qc_
+        return _result_from_handle(L, dh, req, records, cigar, total)
     finally:
         # (close drains the decoder's streams — a byte range may have batches of its overhang still being inflated — and only
         # then the workspace, which those kernels write, is released: `ws` lives until this function returns)
@@ -368,7 +362,7 @@ def window_coverage(path: str, windows: Sequence[Tuple[str, int, int]], quality_
     unknown contig or a window with start < 0 or stop < start raises ValueError.
 
     The GPU pipeline (csrc/coral_bamgpu.hip: k_bam_cov_plan / k_bam_cov_count per batch) runs on a GPU ``device``; the host
-    pipeline (coral_bam_decode_range_cov) otherwise, or with ``CORAL_BAM_DECODE=cpu``.  With ``world`` > 1 the counts are those
+    pipeline (coral_bam_decode_request) otherwise, or with ``CORAL_BAM_DECODE=cpu``.  With ``world`` > 1 the counts are those
     of the ``rank``-th byte range; the ranges' counts add up to the whole file's.
 
     ``index``: a BAI index restricts the decode to the BGZF blocks it names for the windows (``region_spans``); the counts are
@@ -400,6 +394,7 @@ def window_coverage(path: str, windows: Sequence[Tuple[str, int, int]], quality_
                 idx = _usable_index(path, beside, len(ref_names))
             except (_lib.CoralHipError, OSError) as e:
                 skipped = str(e)
+    spans = None
     if idx is not None:
         regions = []                                             # the segments, neighbours within one linear-index window joined
         for t, a, b in segs.T.tolist():
@@ -408,44 +403,17 @@ def window_coverage(path: str, windows: Sequence[Tuple[str, int, int]], quality_
             else:
                 regions.append([t, a, b])
         spans = region_spans(idx, regions)
-        if len(spans) == 0:
-            counts = np.zeros(S, dtype=np.int64)
-            LAST_DECODE.clear()
-            LAST_DECODE.update(seconds=0.0, compressed_bytes=0, uncompressed_bytes=0, blocks=0, threads=int(n_threads))
-        elif _on_gpu(device):
-            counts = _decode_gpu(path, device, n_threads, 0, 1, batch_bytes, coverage=(segs, thr, cb), records=False, spans=spans)[1]
-        else:
-            L = _lib.lib()
-            h = C.c_void_p()
-            sp_beg, sp_end = np.ascontiguousarray(spans[:, 0]), np.ascontiguousarray(spans[:, 1])
-            rc = L.coral_bam_decode_spans_cov(path.encode(), n_threads, len(spans), sp_beg.ctypes.data, sp_end.ctypes.data, S, segs[0].ctypes.data,
-                                              segs[1].ctypes.data, segs[2].ctypes.data, thr, cb, C.byref(h))
-            if rc != 0:
-                raise _lib.CoralHipError("coral_bam_decode_spans_cov(%s) failed (%d): %s" % (path, rc, L.coral_bam_last_error().decode()))
-            try:
-                counts = np.zeros(S, dtype=np.int64)
-                _lib.check(L.coral_bam_coverage_result(h, S, counts.ctypes.data), "coral_bam_coverage_result")
-                _host_stats(L, h, n_threads)
-            finally:
-                L.coral_bam_decode_close(h)
-        LAST_DECODE.update(index=idx.path or "<object>", spans=int(len(spans)))
-    elif _on_gpu(device):
-        counts = _decode_gpu(path, device, n_threads, rank, world, batch_bytes, coverage=(segs, thr, cb), records=False)[1]
-        LAST_DECODE.update(index=None, index_skipped=skipped)
+    if spans is not None and len(spans) == 0:
+        counts = np.zeros(S, dtype=np.int64)
+        LAST_DECODE.clear()
+        LAST_DECODE.update(seconds=0.0, compressed_bytes=0, uncompressed_bytes=0, blocks=0, threads=int(n_threads))
     else:
-        L = _lib.lib()
-        h = C.c_void_p()
-        rc = L.coral_bam_decode_range_cov(path.encode(), n_threads, rank, world, S, segs[0].ctypes.data, segs[1].ctypes.data,
-                                          segs[2].ctypes.data, thr, cb, C.byref(h))
-        if rc != 0:
-            raise _lib.CoralHipError("coral_bam_decode_range_cov(%s) failed (%d): %s" % (path, rc, L.coral_bam_last_error().decode()))
-        try:
-            counts = np.zeros(S, dtype=np.int64)
-            _lib.check(L.coral_bam_coverage_result(h, S, counts.ctypes.data), "coral_bam_coverage_result")
-            _host_stats(L, h, n_threads)
-            LAST_DECODE.update(index=None, index_skipped=skipped)
-        finally:
-            L.coral_bam_decode_close(h)
+        counts = _decode(path, device, n_threads=n_threads, rank=rank, world=world, batch_bytes=batch_bytes, spans=spans,
+                         coverage=(segs, thr, cb), records=False).counts
+    if idx is not None:
+        LAST_DECODE.update(index=idx.path or "<object>", spans=int(len(spans)))
+    else:
+        LAST_DECODE.update(index=None, index_skipped=skipped)
     csum = np.concatenate([[0], np.cumsum(counts, dtype=np.int64)])
     return (csum[last] - csum[first]).astype(np.int64)
 
@@ -529,24 +497,11 @@ def _read_qc_from_handle(L, h) -> ReadQC:
 
 def read_qc(path: str, device="cuda:0", n_threads: Optional[int] = None, rank: int = 0, world: int = 1, batch_bytes: int = 0) -> ReadQC:
     """Per-read length and base-quality statistics of the BAM (``ReadQC``), counted while it is decoded - the only time QUAL is
-    at hand.  On the GPU pipeline when ``device`` is a GPU (coral_bamgpu_qc: k_bam_qc_plan / k_bam_qc per batch), on the host
-    pipeline with ``device="cpu"`` or ``CORAL_BAM_DECODE=cpu`` (coral_bam_decode_range_qc); the results are identical.  With
+    at hand.  On the GPU pipeline when ``device`` is a GPU (k_bam_qc_plan / k_bam_qc per batch), on the host
+    pipeline with ``device="cpu"`` or ``CORAL_BAM_DECODE=cpu`` (coral_bam_decode_request); the results are identical.  With
     ``world`` > 1 the result is that of the ``rank``-th byte range; ``merge_read_qc`` joins them."""
     bam_reference_names(path)                                    # (a clear error for something that is not a BAM file)
-    if n_threads is None:
-        n_threads = default_threads()
-    if _on_gpu(device):
-        return _decode_gpu(path, device, n_threads, rank, world, batch_bytes, records=False, qc=True)[3]
-    L = _lib.lib()
-    h = C.c_void_p()
-    rc = L.coral_bam_decode_range_qc(path.encode(), n_threads, rank, world, C.byref(h))
-    if rc != 0:
-        raise _lib.CoralHipError("coral_bam_decode_range_qc(%s) failed (%d): %s" % (path, rc, L.coral_bam_last_error().decode()))
-    try:
-        _host_stats(L, h, n_threads)
-        return _read_qc_from_handle(L, h)
-    finally:
-        L.coral_bam_decode_close(h)
+    return _decode(path, device, n_threads=n_threads, rank=rank, world=world, batch_bytes=batch_bytes, qc=True, records=False).qc
 
 
 def merge_read_qc(parts: Sequence[ReadQC]) -> ReadQC:
@@ -566,31 +521,9 @@ _PSEUDO_BIN = 37450
 _NO_OFFSET = np.uint64(0xffffffffffffffff)
 
 
-def _host_stats(L, h, n_threads):
-    st, secs = (C.c_int64 * 3)(), C.c_double(0.0)
-    L.coral_bam_decode_stats(h, st, C.byref(secs))
-    LAST_DECODE.clear()
-    LAST_DECODE.update(seconds=float(secs.value), compressed_bytes=int(st[0]), uncompressed_bytes=int(st[1]), blocks=int(st[2]),
-                       threads=int(n_threads))
-
-
 def _decode_spans(path, spans, device, n_threads, batch_bytes) -> Records:
-    """The records that start inside ``spans`` (uint64 [K][2] virtual offsets), on either pipeline."""
-    if n_threads is None:
-        n_threads = default_threads()
-    if _on_gpu(device) and len(spans):
-        return _decode_gpu(path, device, n_threads, 0, 1, batch_bytes, spans=spans)[0]
-    L = _lib.lib()
-    h = C.c_void_p()
-    sp_beg, sp_end = np.ascontiguousarray(spans[:, 0], dtype=np.uint64), np.ascontiguousarray(spans[:, 1], dtype=np.uint64)
-    rc = L.coral_bam_decode_spans(path.encode(), n_threads, len(spans), sp_beg.ctypes.data, sp_end.ctypes.data, C.byref(h))
-    if rc != 0:
-        raise _lib.CoralHipError("coral_bam_decode_spans(%s) failed (%d): %s" % (path, rc, L.coral_bam_last_error().decode()))
-    try:
-        _host_stats(L, h, n_threads)
-        return _records_from_handle(L, h, None, 0)
-    finally:
-        L.coral_bam_decode_close(h)
+    """The records that start inside ``spans`` (uint64 [K][2] virtual offsets), on either pipeline (no span: on the host)."""
+    return _decode(path, device if len(spans) else "cpu", n_threads=n_threads, batch_bytes=batch_bytes, spans=spans).records
 
 
 def _index_partial_from_handle(L, h) -> dict:
@@ -609,22 +542,9 @@ def _index_partial_from_handle(L, h) -> dict:
 
 def index_partial(path: str, device="cuda:0", rank: int = 0, world: int = 1, n_threads: Optional[int] = None, batch_bytes: int = 0) -> dict:
     """What the ``rank``-th of ``world`` byte ranges of the BAM contributes to its BAI index, from one decode with an index
-    request (GPU: coral_bamgpu_index, k_bam_index per batch; host: coral_bam_decode_range_idx).  ``merge_index_partials`` puts
+    request (GPU: k_bam_index per batch; host: coral_bam_decode_request).  ``merge_index_partials`` puts
     consecutive ranges together, ``index_bytes`` writes the file's bytes."""
-    if n_threads is None:
-        n_threads = default_threads()
-    if _on_gpu(device):
-        return _decode_gpu(path, device, n_threads, rank, world, batch_bytes, records=False, index=True)[2]
-    L = _lib.lib()
-    h = C.c_void_p()
-    rc = L.coral_bam_decode_range_idx(path.encode(), n_threads, rank, world, C.byref(h))
-    if rc != 0:
-        raise _lib.CoralHipError("coral_bam_decode_range_idx(%s) failed (%d): %s" % (path, rc, L.coral_bam_last_error().decode()))
-    try:
-        _host_stats(L, h, n_threads)
-        return _index_partial_from_handle(L, h)
-    finally:
-        L.coral_bam_decode_close(h)
+    return _decode(path, device, n_threads=n_threads, rank=rank, world=world, batch_bytes=batch_bytes, index=True, records=False).index
 
 
 def merge_index_partials(parts: Sequence[dict]) -> dict:

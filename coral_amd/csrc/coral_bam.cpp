@@ -12,7 +12,7 @@
 //     stage 2 (caller, cheap) hop along the record lengths: record starts of the chunk, hand-over of the record that
 //                             straddles into the next chunk
 //     stage 3 (worker pool)   parse the chunk's records into a per-chunk partial (CIGAR copy + padding, SA tokens, NM,
-//                             non-ACGT scan; with a window-coverage request, coral_bam_decode_range_cov, the chunk's
+//                             non-ACGT scan; with a window-coverage request the chunk's
 //                             partial counts per segment, added up in stage 4)
 //     stage 4 (caller)        append the partials in file order; read names -> ids
 // A byte range [rank, world) of the file can be decoded on its own (one process per GPU): the range
@@ -74,13 +74,14 @@ struct Chunk {
 // With `span` the range is not the rank-th byte range but the records that start inside [span->beg, span->end) (virtual
 // offsets, e.g. from a BAI index): the first record is at a known place, nothing is searched, and the decode stops in front of
 // the record that starts at or behind span->end.  Spans may be decoded one after the other into the same `D`.
-bool decode_file(const char *path, int n_threads, int rank, int world, Decoded &D, const CovTable *cov = nullptr, const Span *span = nullptr,
-                 bool want_index = false, bool want_qc = false) {
+bool decode_file(const char *path, int n_threads, const Request &R, const Span *span, Decoded &D) {
+    const int rank = R.rank, world = R.world;
+    const CovTable *cov = R.cov_table();
+    const bool want_index = R.want_index, want_qc = R.want_qc;
     const auto t_start = std::chrono::steady_clock::now();
     MappedFile f;
     if (!f.open(path, D.error)) return false;
     n_threads = n_threads < 1 ? 1 : (n_threads > 256 ? 256 : n_threads);
-    if (world < 1 || rank < 0 || rank >= world) { D.error = "bad rank / world"; return false; }
     // ---- header (every rank): inflate from block 0 until the reference list is complete
     size_t hdr_bytes = 0;                      // header length in the uncompressed stream
     RefIds ref_id;
@@ -99,10 +100,7 @@ bool decode_file(const char *path, int n_threads, int rank, int world, Decoded &
     if (rank > 0 && !find_block(f, byte_lo, &first)) first = f.size;
     const uint64_t span_end_block = span ? span->end >> 16 : 0;
     const uint32_t span_end_off = span ? (uint32_t)(span->end & 0xffff) : 0;
-    if (span) {
-        first = span->beg >> 16;
-        if (span->end < span->beg || first >= f.size) { D.error = "a span of virtual offsets lies outside the file"; return false; }
-    }
+    if (span) first = span->beg >> 16;
     std::vector<Block> blocks;
     std::vector<uint64_t> ublk;                // offset of every block's first byte in the range's uncompressed stream
     size_t n_own = 0;
@@ -485,79 +483,38 @@ void coral_bam::set_error(const std::string &msg) { g_bam_err = msg; }
 
 extern "C" const char *coral_bam_last_error(void) { return g_bam_err.c_str(); }
 
-static int decode_range(const char *path, int32_t n_threads, int32_t rank, int32_t world, const CovTable *cov, void **handle,
-                        bool want_index = false, int32_t n_spans = -1, const uint64_t *span_beg = nullptr, const uint64_t *span_end = nullptr,
-                        bool want_qc = false) {
-    if (!path || !handle || (n_spans > 0 && (!span_beg || !span_end))) return CORAL_ERR_ARG;
-    Decoded *D = new Decoded();
+extern "C" int coral_bam_decode_request(const char *path, int32_t n_threads, const coral_bam_request_t *req, void **handle) {
+    if (!path || !handle) return CORAL_ERR_ARG;
+    Request R;
+    if (!parse_request(req, R, g_bam_err)) return CORAL_ERR_ARG;
+    std::unique_ptr<Decoded> D(new Decoded());
     bool ok = false;
     try {
-        if (n_spans < 0) {
-            ok = decode_file(path, n_threads, rank, world, *D, cov, nullptr, want_index, want_qc);
+        if (!R.span_mode) {
+            ok = decode_file(path, n_threads, R, nullptr, *D);
         } else {                                 // spans in the given order, into one result (no span: the header only)
             MappedFile f;
             RefIds ids;
             size_t hdr = 0;
             ok = f.open(path, D->error) && read_bam_header(f, *D, ids, &hdr);
-            if (ok && cov) D->cov.assign(cov->size(), 0);
-            for (int32_t k = 0; k < n_spans && ok; ++k) {
-                const Span sp{span_beg[k], span_end[k]};
-                ok = decode_file(path, n_threads, 0, 1, *D, cov, &sp);
-            }
+            if (ok && !spans_inside_file(R, f.size, g_bam_err)) return CORAL_ERR_ARG;
+            if (ok && R.has_cov) D->cov.assign(R.cov.size(), 0);
+            for (size_t k = 0; k < R.spans.size() && ok; ++k) ok = decode_file(path, n_threads, R, &R.spans[k], *D);
         }
     } catch (const std::exception &e) {          // e.g. bad_alloc on a corrupt size field: never across the C boundary
         D->error = std::string("decoder failed: ") + e.what();
     }
     if (!ok) {
         g_bam_err = D->error;
-        delete D;
         return CORAL_ERR_FORMAT;
     }
-    *handle = D;
+    *handle = D.release();
     return CORAL_OK;
 }
 
 extern "C" int coral_bam_decode_range(const char *path, int32_t n_threads, int32_t rank, int32_t world, void **handle) {
-    return decode_range(path, n_threads, rank, world, nullptr, handle);
-}
-
-extern "C" int coral_bam_decode_range_cov(const char *path, int32_t n_threads, int32_t rank, int32_t world, int32_t n_seg,
-                                          const int32_t *seg_tid, const int32_t *seg_start, const int32_t *seg_end,
-                                          int32_t quality_threshold, int32_t read_callback, void **handle) {
-    CovTable T;
-    std::string err;
-    if (!make_cov_table(n_seg, seg_tid, seg_start, seg_end, quality_threshold, read_callback, T, err)) {
-        g_bam_err = err;
-        return CORAL_ERR_ARG;
-    }
-    return decode_range(path, n_threads, rank, world, &T, handle);
-}
-
-extern "C" int coral_bam_decode_range_idx(const char *path, int32_t n_threads, int32_t rank, int32_t world, void **handle) {
-    return decode_range(path, n_threads, rank, world, nullptr, handle, true);
-}
-
-extern "C" int coral_bam_decode_range_qc(const char *path, int32_t n_threads, int32_t rank, int32_t world, void **handle) {
-    return decode_range(path, n_threads, rank, world, nullptr, handle, false, -1, nullptr, nullptr, true);
-}
-
-extern "C" int coral_bam_decode_spans(const char *path, int32_t n_threads, int32_t n_spans, const uint64_t *span_beg,
-                                      const uint64_t *span_end, void **handle) {
-    if (n_spans < 0) return CORAL_ERR_ARG;
-    return decode_range(path, n_threads, 0, 1, nullptr, handle, false, n_spans, span_beg, span_end);
-}
-
-extern "C" int coral_bam_decode_spans_cov(const char *path, int32_t n_threads, int32_t n_spans, const uint64_t *span_beg,
-                                          const uint64_t *span_end, int32_t n_seg, const int32_t *seg_tid, const int32_t *seg_start,
-                                          const int32_t *seg_end, int32_t quality_threshold, int32_t read_callback, void **handle) {
-    CovTable T;
-    std::string err;
-    if (n_spans < 0) return CORAL_ERR_ARG;
-    if (!make_cov_table(n_seg, seg_tid, seg_start, seg_end, quality_threshold, read_callback, T, err)) {
-        g_bam_err = err;
-        return CORAL_ERR_ARG;
-    }
-    return decode_range(path, n_threads, 0, 1, &T, handle, false, n_spans, span_beg, span_end);
+    const coral_bam_request_t q = range_request(rank, world);
+    return coral_bam_decode_request(path, n_threads, &q, handle);
 }
 
 extern "C" int coral_bam_index_sizes(void *handle, int64_t sizes[4]) {

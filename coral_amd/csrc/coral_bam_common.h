@@ -25,12 +25,13 @@
 #include <unordered_map>
 #include <vector>
 
+#include "../../include/coral_hip.h"
 #include "coral_names.h"
 
 namespace coral_bam {
 
 
-// A BAI index request (coral_bam_decode_range_idx, coral_bamgpu_index): what one decode of a byte range contributes to the
+// A BAI index request (want_index of a coral_bam_request_t): what one decode of a byte range contributes to the
 // index of the file (SAMv1 §5.2), in a form that partial results of consecutive byte ranges merge into exactly.
 //   heads     one entry per maximal run of file-consecutive records with the same (tid, bin), in file order: key =
 //             tid * 65536 + reg2bin(beg, end) (-1 for a record without coordinates, which only ends the run in front of it) and
@@ -104,7 +105,7 @@ struct IndexPartial {
     }
 };
 
-// A read-QC request (coral_bam_decode_range_qc, coral_bamgpu_qc): per-read length and base-quality statistics, what the
+// A read-QC request (want_qc of a coral_bam_request_t): per-read length and base-quality statistics, what the
 // reference's scripts/report_nanopore_qc.py computes from the FASTQ the file was aligned from.  The rules both pipelines share:
 //   a READ is a record with flag & 0x900 == 0 (neither secondary nor supplementary) and l_seq > 0, mapped or not;
 //   its QUAL bytes start qc_qual_offset() bytes behind the record's first byte (its block_size field) - the record's OWN
@@ -152,7 +153,7 @@ struct QcPartial {
     }
 };
 
-// A span of virtual offsets [beg, end) (coral_bam_decode_spans, coral_bamgpu_open_spans): the records that START in it.
+// A span of virtual offsets [beg, end) (span_beg / span_end of a coral_bam_request_t): the records that START in it.
 struct Span {
     uint64_t beg = 0, end = 0;
 };
@@ -174,7 +175,7 @@ struct Decoded {
     // statistics of the decode (coral_bam_decode_stats)
     int64_t compressed_bytes = 0, uncompressed_bytes = 0, n_blocks = 0;
     double seconds = 0.0;
-    std::vector<int64_t> cov;               // window-coverage counts per segment (coral_bam_decode_range_cov)
+    std::vector<int64_t> cov;               // window-coverage counts per segment (coral_bam_coverage_result)
 };
 
 struct Partial {   // what stage 3 produces for one chunk
@@ -199,7 +200,7 @@ static const int QRY_ADV[16] = {1, 1, 0, 0, 1, 0, 0, 1, 1, 0, 0, 0, 0, 0, 0, 0};
 
 typedef std::unordered_map<std::string, int> RefIds;
 
-// A window-coverage request (coral_bam_decode_range_cov, coral_bamgpu_coverage): pysam count_coverage summed over the four
+// A window-coverage request (the segments of a coral_bam_request_t): pysam count_coverage summed over the four
 // bases, for n sorted, pairwise disjoint half-open segments (tid, lo, hi) — the caller cuts its (possibly overlapping) windows
 // at every start and stop and sums the segments back.  A base counts when the record is on the segment's contig (with
 // filter_all: none of the flags 0x4 | 0x100 | 0x200 | 0x400), has SEQ, the base is an aligned (M / = / X) base inside the
@@ -240,6 +241,59 @@ inline bool make_cov_table(int32_t n_seg, const int32_t *tid, const int32_t *lo,
     T.threshold = threshold;
     T.filter_all = read_callback == 1;
     return true;
+}
+
+// What one decode is asked for: a coral_bam_request_t, checked and copied (parse_request).  Both pipelines take it.
+struct Request {
+    int32_t rank = 0, world = 1;            // the byte range (0, 1 on a span decode: spans are not sharded)
+    bool span_mode = false;                 // only the records that start inside `spans`
+    std::vector<Span> spans;
+    bool has_cov = false;                   // a window-coverage request (it may have no segment)
+    CovTable cov;
+    bool want_index = false, want_qc = false;
+    const CovTable *cov_table() const { return has_cov ? &cov : nullptr; }
+};
+
+// Every argument rule of a request but one (the spans lie inside the file: spans_inside_file); false: `err` says why.
+inline bool parse_request(const coral_bam_request_t *q, Request &R, std::string &err) {
+    if (!q) { err = "request: null pointer"; return false; }
+    R.want_index = q->want_index != 0;
+    R.want_qc = q->want_qc != 0;
+    if (q->n_spans >= 0) {
+        if (q->n_spans > 0 && (!q->span_beg || !q->span_end)) { err = "request: bad span arrays"; return false; }
+        if (R.want_index || R.want_qc) { err = "request: an index or read-QC request does not go with a span decode"; return false; }
+        for (int32_t k = 0; k < q->n_spans; ++k) {
+            if (q->span_end[k] <= q->span_beg[k] || (k > 0 && q->span_beg[k] < q->span_end[k - 1])) {
+                err = "request: the spans must be sorted, disjoint and non-empty";
+                return false;
+            }
+            R.spans.push_back(Span{q->span_beg[k], q->span_end[k]});
+        }
+        R.span_mode = true;                   // (not sharded: rank 0 of 1 whatever the request says)
+    } else {
+        if (q->world < 1 || q->rank < 0 || q->rank >= q->world) { err = "request: needs world >= 1 and 0 <= rank < world"; return false; }
+        R.rank = q->rank;
+        R.world = q->world;
+    }
+    R.has_cov = q->n_seg >= 0;
+    return !R.has_cov || make_cov_table(q->n_seg, q->seg_tid, q->seg_start, q->seg_end, q->quality_threshold, q->read_callback, R.cov, err);
+}
+
+// The rule that needs the file: every span begins at a block inside the file and ends at one or at the file's end.
+inline bool spans_inside_file(const Request &R, uint64_t file_size, std::string &err) {
+    for (const Span &s : R.spans)
+        if ((s.beg >> 16) >= file_size || (s.end >> 16) > file_size) { err = "request: a span of virtual offsets lies outside the file"; return false; }
+    return true;
+}
+
+// The plain request of the rank-th of `world` byte ranges.
+inline coral_bam_request_t range_request(int32_t rank, int32_t world) {
+    coral_bam_request_t q;
+    memset(&q, 0, sizeof(q));
+    q.rank = rank;
+    q.world = world;
+    q.n_spans = q.n_seg = -1;
+    return q;
 }
 
 // Add one record's counted bases to counts[segment] (host pipeline; ops = the real CIGAR, CG tag already resolved).

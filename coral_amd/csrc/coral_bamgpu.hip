@@ -18,11 +18,11 @@
 //                   codes, read name and SA text -> compact blobs for the host
 //   worker thread   per batch, a few hundred bytes per record: read names -> ids, SA text -> numeric rows; the rare
 //                   records with non-ACGT bases are gathered whole (k_bam_gather) and handled by the CPU pipeline's own routine.
-//   k_bam_cov_plan / k_bam_cov_count   only with a window-coverage request (coral_bamgpu_coverage): pysam count_coverage with a
+//   k_bam_cov_plan / k_bam_cov_count   only with a window-coverage request (coral_bam_request_t): pysam count_coverage with a
 //                   base-quality threshold over the request's segments, read from the batch's SEQ / QUAL before the slot is reused.
-//   k_bam_index / k_bam_index_compact   only with an index request (coral_bamgpu_index): per record the virtual offset, the UCSC bin
+//   k_bam_index / k_bam_index_compact   only with an index request (want_index): per record the virtual offset, the UCSC bin
 //                   and the linear-index windows of a BAI index, per batch the heads of the runs of equal (tid, bin).
-//   k_bam_qc_plan / k_bam_qc   only with a read-QC request (coral_bamgpu_qc): per read the sum of its QUAL bytes, and the 256-bin
+//   k_bam_qc_plan / k_bam_qc   only with a read-QC request (want_qc): per read the sum of its QUAL bytes, and the 256-bin
 //                   histogram of all of them, read from the batch's QUAL before the slot is reused.
 // Batches (64 MiB first, doubling up to 2.52 GiB inflated, coral_bamgpu_open) are double-buffered: while batch k is parsed, batch k + 1 is inflated
 // and k + 2 is read.
@@ -984,11 +984,11 @@ __global__ __launch_bounds__(256) void k_bam_gather(const uint8_t *__restrict__ 
 }
 
 // ---------------------------------------------------------------------------------------------
-// K_cov: window coverage with a base-quality threshold (coral_bamgpu_coverage), counted while SEQ and QUAL are in HBM
+// K_cov: window coverage with a base-quality threshold (the segments of the request), counted while SEQ and QUAL are in HBM
 // ---------------------------------------------------------------------------------------------
 #define COV_SLICE 16384ll                // query bases per work item: a 1 Mb read is 62 waves' work, not one wave's
 
-struct CovSegs {                         // the request's sorted, disjoint segments (device arrays of the caller)
+struct CovSegs {                         // the request's sorted, disjoint segments (device arrays in the workspace)
     const int32_t *tid, *lo, *hi;
     int n;
 };
@@ -1105,7 +1105,7 @@ __global__ __launch_bounds__(256) void k_bam_cov_count(const uint8_t *__restrict
 }
 
 // ---------------------------------------------------------------------------------------------
-// K_qc: per-read base-quality sums and the base-quality histogram (coral_bamgpu_qc; the rules: QcPartial in coral_bam_common.h)
+// K_qc: per-read base-quality sums and the base-quality histogram (want_qc; the rules: QcPartial in coral_bam_common.h)
 // ---------------------------------------------------------------------------------------------
 #define QC_SLICE 16384ll                 // QUAL bytes per work item (as COV_SLICE: a 1 Mb read is 62 waves' work)
 #ifndef QC_COPIES
@@ -1208,7 +1208,7 @@ __global__ __launch_bounds__(WAVE) void k_bam_qc(const uint8_t *__restrict__ buf
 }
 
 // ---------------------------------------------------------------------------------------------
-// K_index: what a batch contributes to the BAI index of the file (coral_bamgpu_index; IndexPartial in coral_bam_common.h)
+// K_index: what a batch contributes to the BAI index of the file (want_index; IndexPartial in coral_bam_common.h)
 // ---------------------------------------------------------------------------------------------
 struct IndexDev {                        // device arrays of the request, carved from the caller's workspace
     unsigned long long *lin;             // linear index: smallest virtual offset per (contig, 16 384-base window), ~0 = none
@@ -1376,7 +1376,8 @@ struct GpuDecoder {
     Decoded D;
     RefIds ref_id;
     size_t hdr_bytes = 0;
-    int rank = 0, world = 1, n_threads = 1, device = 0;
+    Request req;                              // what was asked for (coral_bamgpu_open_request)
+    int n_threads = 1, device = 0;
     uint64_t byte_lo = 0, byte_hi = 0, first_block = 0;
     bool last_rank = true;
     std::string error;
@@ -1431,28 +1432,23 @@ struct GpuDecoder {
     bool worker_stop = false, worker_busy = false;
     std::string worker_error;
     long long cur_carry_pos = 0;
-    // window-coverage request (coral_bamgpu_coverage): segments and counters in the caller's device memory
+    // window-coverage request: segments and counters in the workspace (n = 0 without one)
     CovSegs cov{nullptr, nullptr, nullptr, 0};
-    int cov_threshold = 0, cov_filter_all = 0;
     unsigned long long *cov_counts = nullptr;
-    bool cov_set = false;
-    // span decode (coral_bamgpu_open_spans): the spans are decoded one after the other through the same batches
-    bool span_mode = false;
+    // span decode: the spans are decoded one after the other through the same batches
     std::vector<SpanDef> spans;
     int cur_span = 0;                         // the span the caller's thread is parsing
     std::vector<int> span_verdict;            // per span (under m): 0 = not known yet, 1 = its last record has been parsed,
                                               //   2 = the record in front of its end goes on behind its last own block
-    // index request (coral_bamgpu_index)
-    bool idx_on = false;
+    // index request
     IndexDev X{};
     uint32_t *d_boff[2] = {nullptr, nullptr}; // per block of the slot's batch: its file offset relative to the batch's
     BlockDesc *d_idesc[2] = {nullptr, nullptr};   // the slot's block table and offsets, kept for k_bam_index: the feeder re-stages
     uint32_t *d_iboff[2] = {nullptr, nullptr};    //   d_desc / d_boff for batch k + 2 while batch k is still being parsed
     int idx_parity = 0;
-    // read-QC request (coral_bamgpu_qc): the batch's qual_sum rows (fetched when the NEXT batch's host fields are: the stream has
+    // read-QC request: the batch's qual_sum rows (fetched when the NEXT batch's host fields are: the stream has
     // been synchronised behind the kernels by then, and that batch's k_bam_qc_plan is queued only afterwards, so one array
     // does), the device histogram of the whole decode
-    bool qc_on = false;
     long long *d_qc_sum = nullptr;
     unsigned long long *d_qc_hist = nullptr;
     long long qc_pending_n = 0;               // records of the batch whose rows are still on the device
@@ -1534,7 +1530,7 @@ void feeder_main(GpuDecoder *G) {
     long long own_bytes = -1;                 // known once the first block of the next range has been seen
     size_t overhang_left = OVERHANG_BLOCKS;
     int kb = 0, chunk_no = 0;
-    const int n_spans = G->span_mode ? (int)G->spans.size() : 1;
+    const int n_spans = G->req.span_mode ? (int)G->spans.size() : 1;
     auto fail = [&](const std::string &msg) {
         std::lock_guard<std::mutex> lk(G->m);
         G->feeder_error = msg;
@@ -1544,9 +1540,9 @@ void feeder_main(GpuDecoder *G) {
     std::vector<BlockDesc> desc;
     std::vector<uint32_t> crcs, boffs;
     for (int sp = 0; sp < n_spans; ++sp) {
-        const SpanDef S = G->span_mode ? G->spans[(size_t)sp] : SpanDef();
-        bool span_first = G->span_mode;
-        if (G->span_mode) {
+        const SpanDef S = G->req.span_mode ? G->spans[(size_t)sp] : SpanDef();
+        bool span_first = G->req.span_mode;
+        if (G->req.span_mode) {
             at = S.first_block;
             ubase = 0;
             own_bytes = -1;
@@ -1607,12 +1603,12 @@ void feeder_main(GpuDecoder *G) {
                         break;                                         // the block continues behind what was read
                     }
                     if (infl + b.isize > infl_cap) { full = true; break; }
-                    if (G->span_mode && at + p == S.end_block && own_bytes < 0) own_bytes = (long long)(ubase + infl) + S.end_off;
-                    const bool owned = G->span_mode ? (at + p < S.end_block || (at + p == S.end_block && S.end_off > 0)) : at + p < G->byte_hi;
-                    if (!owned && G->span_mode && !overhang_ok && !desc.empty()) { tail_staged = true; full = true; break; }
+                    if (G->req.span_mode && at + p == S.end_block && own_bytes < 0) own_bytes = (long long)(ubase + infl) + S.end_off;
+                    const bool owned = G->req.span_mode ? (at + p < S.end_block || (at + p == S.end_block && S.end_off > 0)) : at + p < G->byte_hi;
+                    if (!owned && G->req.span_mode && !overhang_ok && !desc.empty()) { tail_staged = true; full = true; break; }
                     // (the batch in front filled up exactly with the span's last own block: this one block alone is the tail batch
                     // the parse gives its verdict on)
-                    const bool lone_tail = !owned && G->span_mode && !overhang_ok;
+                    const bool lone_tail = !owned && G->req.span_mode && !overhang_ok;
                     if (!owned) {
                         if (own_bytes < 0) own_bytes = (long long)(ubase + infl);
                         if (overhang_left == 0) { full = true; break; }
@@ -1630,7 +1626,7 @@ void feeder_main(GpuDecoder *G) {
                     p += b.csize;
                     // (of a span every block that is read counts, its overhang included)
                     if (lone_tail) { tail_staged = true; full = true; }
-                    if (owned || G->span_mode) { G->D.compressed_bytes += b.csize; G->D.uncompressed_bytes += b.isize; ++G->D.n_blocks; }
+                    if (owned || G->req.span_mode) { G->D.compressed_bytes += b.csize; G->D.uncompressed_bytes += b.isize; ++G->D.n_blocks; }
                 }
                 if (p == 0) {
                     if (desc.empty()) return fail("a BGZF block does not fit the batch buffers");
@@ -1662,7 +1658,7 @@ void feeder_main(GpuDecoder *G) {
             memcpy(h_crc, crcs.data(), crcs.size() * 4);
             if (hipMemcpyAsync(G->d_desc[slot], G->h_desc[slot], desc.size() * sizeof(BlockDesc), hipMemcpyHostToDevice, G->s_copy) != hipSuccess ||
                 hipMemcpyAsync(G->d_crc[slot], h_crc, crcs.size() * 4, hipMemcpyHostToDevice, G->s_copy) != hipSuccess ||
-                (G->idx_on && (memcpy(h_crc + G->max_blocks, boffs.data(), boffs.size() * 4),
+                (G->req.want_index && (memcpy(h_crc + G->max_blocks, boffs.data(), boffs.size() * 4),
                                hipMemcpyAsync(G->d_boff[slot], h_crc + G->max_blocks, boffs.size() * 4, hipMemcpyHostToDevice, G->s_copy) != hipSuccess)) ||
                 hipEventRecord(G->ev_h2d[slot], G->s_copy) != hipSuccess)
                 return fail("host-to-device copy of a block table failed");
@@ -1790,7 +1786,7 @@ bool carve(GpuDecoder *G, void *ws, size_t bytes) {
     G->names_cap = G->sa_cap = (size_t)CARRY_CAP + G->infl_cap;
     G->d_names = (uint8_t *)take(G->names_cap);
     G->d_sa_text = (uint8_t *)take(G->sa_cap);
-    if (G->idx_on) {                           // the index request's own arrays (everything per record re-uses the batch's scratch)
+    if (G->req.want_index) {                           // the index request's own arrays (everything per record re-uses the batch's scratch)
         const size_t n_ref = G->D.ref_lens.size();
         for (int i = 0; i < 2; ++i) {
             G->d_boff[i] = (uint32_t *)take(G->max_blocks * 4);
@@ -1806,9 +1802,15 @@ bool carve(GpuDecoder *G, void *ws, size_t bytes) {
         G->X.unsorted = (int32_t *)take(4);
         G->X.n_ref = (int)n_ref;
     }
-    if (G->qc_on) {
+    if (G->req.want_qc) {
         G->d_qc_sum = (long long *)take(nr * 8);
         G->d_qc_hist = (unsigned long long *)take(256 * 8);
+    }
+    if (G->req.has_cov) {                      // the coverage request's segments (tid, lo, hi) and counters
+        const size_t n_seg = G->req.cov.size();
+        int32_t *seg = (int32_t *)take(3 * n_seg * 4);
+        G->cov = CovSegs{seg, seg + n_seg, seg + 2 * n_seg, (int)n_seg};
+        G->cov_counts = (unsigned long long *)take(n_seg * 8);
     }
     if (ws && used > bytes) return false;
     G->ws_bytes = used;
@@ -1828,7 +1830,7 @@ bool launch_inflate(GpuDecoder *G, int kb, const BatchInfo &bi) {
     const int slot = kb & 1;
     HIP_LAUNCH_OK(hipStreamWaitEvent(G->s_infl, G->ev_h2d[slot], 0), "hipStreamWaitEvent");
     if (kb >= 2) HIP_LAUNCH_OK(hipStreamWaitEvent(G->s_infl, G->ev_parsed[slot], 0), "hipStreamWaitEvent");     // the buffer's previous batch has been parsed
-    if (G->idx_on) {    // (behind ev_parsed of batch kb - 2, whose k_bam_index read the copies; in front of ev_infl, which this batch's parse waits for)
+    if (G->req.want_index) {    // (behind ev_parsed of batch kb - 2, whose k_bam_index read the copies; in front of ev_infl, which this batch's parse waits for)
         HIP_LAUNCH_OK(hipMemcpyAsync(G->d_idesc[slot], G->d_desc[slot], (size_t)bi.n_blocks * sizeof(BlockDesc), hipMemcpyDeviceToDevice, G->s_infl), "hipMemcpyAsync");
         HIP_LAUNCH_OK(hipMemcpyAsync(G->d_iboff[slot], G->d_boff[slot], (size_t)bi.n_blocks * 4, hipMemcpyDeviceToDevice, G->s_infl), "hipMemcpyAsync");
     }
@@ -1882,17 +1884,20 @@ const char *rec_error_text(int e) {
 // ---------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------
-static int open_decoder(const char *path, int32_t n_threads, int32_t rank, int32_t world, int64_t batch_bytes, void **handle,
-                        int64_t *workspace_bytes, int32_t n_spans, const uint64_t *span_beg, const uint64_t *span_end) {
-    if (!path || !handle || !workspace_bytes || world < 1 || rank < 0 || rank >= world) return CORAL_ERR_ARG;
+extern "C" int coral_bamgpu_open_request(const char *path, int32_t n_threads, int64_t batch_bytes, const coral_bam_request_t *req, void **handle,
+                                         int64_t *workspace_bytes) {
+    if (!path || !handle || !workspace_bytes) return CORAL_ERR_ARG;
     std::unique_ptr<GpuDecoder> G(new GpuDecoder());
     G->t_start = std::chrono::steady_clock::now();
+    std::string err;
+    if (!parse_request(req, G->req, err)) { set_error(err); return CORAL_ERR_ARG; }
+    const Request &R = G->req;
+    const int32_t rank = R.rank, world = R.world;
     if (!G->f.open(path, G->error) || !read_bam_header(G->f, G->D, G->ref_id, &G->hdr_bytes)) {
         set_error(G->error.empty() ? G->D.error : G->error);
         return CORAL_ERR_FORMAT;
     }
-    G->rank = rank;
-    G->world = world;
+    if (!spans_inside_file(R, G->f.size, err)) { set_error(err); return CORAL_ERR_ARG; }
     G->n_threads = n_threads < 1 ? 1 : (n_threads > 64 ? 64 : n_threads);
     G->last_rank = rank == world - 1;
     G->byte_lo = rank == 0 ? 0 : G->f.size / (uint64_t)world * (uint64_t)rank;
@@ -1901,26 +1906,23 @@ static int open_decoder(const char *path, int32_t n_threads, int32_t rank, int32
     if (rank > 0 && !find_block(G->f, G->byte_lo, &G->first_block)) G->first_block = G->f.size;
     if (G->first_block >= G->byte_hi) G->first_block = G->f.size;          // no block starts in this range: nothing to do
     G->searching = rank > 0;
-    uint64_t span_bytes = 0;
-    if (n_spans >= 0) {                        // the records that start inside the spans, nothing else
-        G->span_mode = true;
+    if (R.span_mode) {                         // the records that start inside the spans, nothing else: only the spans' BGZF blocks
+        uint64_t span_bytes = 0;               // (and what their last records straddle into) are read, uploaded and inflated
         G->last_rank = false;
-        for (int32_t k = 0; k < n_spans; ++k) {
+        for (const Span &sp : R.spans) {
             SpanDef S;
-            S.first_block = span_beg[k] >> 16; S.start_off = (uint32_t)(span_beg[k] & 0xffff);
-            S.end_block = span_end[k] >> 16; S.end_off = (uint32_t)(span_end[k] & 0xffff);
-            if (span_end[k] <= span_beg[k] || S.first_block >= G->f.size || S.end_block > G->f.size || (k > 0 && span_beg[k] < span_end[k - 1])) {
-                set_error("coral_bamgpu_open_spans: the spans must be sorted, disjoint, non-empty and inside the file");
-                return CORAL_ERR_ARG;
-            }
+            S.first_block = sp.beg >> 16; S.start_off = (uint32_t)(sp.beg & 0xffff);
+            S.end_block = sp.end >> 16; S.end_off = (uint32_t)(sp.end & 0xffff);
             span_bytes = std::max(span_bytes, S.end_block - S.first_block + 65536 + (uint64_t)OVERHANG_BLOCKS * 65536 / 4);
             G->spans.push_back(S);
         }
         G->span_verdict.assign(G->spans.size(), 0);
         G->first_block = G->byte_lo = 0;
         G->byte_hi = span_bytes;
-        if (n_spans == 0) G->first_block = G->f.size;
+        if (G->spans.empty()) G->first_block = G->f.size;
     }
+    if (R.want_index) G->D.idx.init(G->D.ref_lens);
+    if (R.want_qc) G->D.qc.init();
     // batch size: at most `batch_bytes` inflated, no more than the range can need.  Default 2.52 GiB = 6 x 6 912 BGZF blocks of
     // 65 280 bytes (htslib's block size): the inflate kernel keeps 27 one-wave workgroups per CU x 256 CUs resident, blocks of
     // equal size finish in rounds, and a batch that is a whole number of rounds has no part-filled last round; bigger batches
@@ -1949,65 +1951,8 @@ static int open_decoder(const char *path, int32_t n_threads, int32_t rank, int32
 
 extern "C" int coral_bamgpu_open(const char *path, int32_t n_threads, int32_t rank, int32_t world, int64_t batch_bytes, void **handle,
                                  int64_t *workspace_bytes) {
-    return open_decoder(path, n_threads, rank, world, batch_bytes, handle, workspace_bytes, -1, nullptr, nullptr);
-}
-
-// coral_bamgpu_open for the records that start inside n_spans sorted, disjoint spans of virtual offsets (a BAI region query):
-// only the spans' BGZF blocks (and what their last records straddle into) are read, uploaded and inflated; the spans go through
-// the same batches one after the other, and every other call is the same as behind coral_bamgpu_open.
-extern "C" int coral_bamgpu_open_spans(const char *path, int32_t n_threads, int32_t n_spans, const uint64_t *span_beg, const uint64_t *span_end,
-                                       int64_t batch_bytes, void **handle, int64_t *workspace_bytes) {
-    if (n_spans < 0 || (n_spans > 0 && (!span_beg || !span_end))) return CORAL_ERR_ARG;
-    return open_decoder(path, n_threads, 0, 1, batch_bytes, handle, workspace_bytes, n_spans, span_beg, span_end);
-}
-
-// Index request: after open (not open_spans), before start and before the workspace is allocated: *workspace_bytes is the new
-// size (the request's block offsets, linear index and counters).  Per batch k_bam_index + one scan + k_bam_index_compact.
-extern "C" int coral_bamgpu_index(void *handle, int64_t *workspace_bytes) {
-    GpuDecoder *G = (GpuDecoder *)handle;
-    if (!G || !workspace_bytes) return CORAL_ERR_ARG;
-    if (G->feeder.joinable() || G->idx_on || G->span_mode) { set_error("coral_bamgpu_index: call it once, after open and before start, not on a span decode"); return CORAL_ERR_ARG; }
-    G->idx_on = true;
-    G->D.idx.init(G->D.ref_lens);
-    carve(G, nullptr, 0);
-    *workspace_bytes = (int64_t)G->ws_bytes;
-    return CORAL_OK;
-}
-
-// The request's result, once every batch has been emitted: waits for `stream`, takes the linear index and the counters from the
-// device and leaves the partial index in the host-side result (coral_bamgpu_host -> coral_bam_index_sizes / _fill).
-extern "C" int coral_bamgpu_index_result(void *handle, void *stream_) {
-    GpuDecoder *G = (GpuDecoder *)handle;
-    if (!G || !G->idx_on) return CORAL_ERR_ARG;
-    if (!G->finished || G->have_cur) { set_error("coral_bamgpu_index_result: the decode is not finished"); return CORAL_ERR_ARG; }
-    IndexPartial &P = G->D.idx;
-    const size_t n_ref = P.n_mapped.size();
-    unsigned long long state[2] = {0, 0}, no_coor = 0;
-    int32_t unsorted = 0;
-    auto get = [](void *dst, const void *src, size_t bytes) { return bytes == 0 || hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) == hipSuccess; };
-    if (hipStreamSynchronize((hipStream_t)stream_) != hipSuccess || !get(P.lin.data(), G->X.lin, P.lin.size() * 8) ||
-        !get(P.n_mapped.data(), G->X.n_mapped, n_ref * 8) || !get(P.n_unmapped.data(), G->X.n_unmapped, n_ref * 8) ||
-        !get(&no_coor, G->X.n_no_coor, 8) || !get(state, G->X.state, 16) || !get(&unsorted, G->X.unsorted, 4)) {
-        set_error("coral_bamgpu_index_result: copy of the index arrays failed");
-        return CORAL_ERR_HIP;
-    }
-    if (unsorted || P.unsorted) { set_error("the records are not in coordinate order: no index can be built"); return CORAL_ERR_FORMAT; }
-    P.n_no_coor = (int64_t)no_coor;
-    P.end_voff = state[G->idx_parity];
-    return CORAL_OK;
-}
-
-// Read-QC request: after open (not open_spans), before start and before the workspace is allocated: *workspace_bytes is the new
-// size (one int64 per record of a batch, the histogram).  Per batch k_bam_qc_plan + one scan + k_bam_qc.
-extern "C" int coral_bamgpu_qc(void *handle, int64_t *workspace_bytes) {
-    GpuDecoder *G = (GpuDecoder *)handle;
-    if (!G || !workspace_bytes) return CORAL_ERR_ARG;
-    if (G->feeder.joinable() || G->qc_on || G->span_mode) { set_error("coral_bamgpu_qc: call it once, after open and before start, not on a span decode"); return CORAL_ERR_ARG; }
-    G->qc_on = true;
-    G->D.qc.init();
-    carve(G, nullptr, 0);
-    *workspace_bytes = (int64_t)G->ws_bytes;
-    return CORAL_OK;
+    const coral_bam_request_t q = range_request(rank, world);
+    return coral_bamgpu_open_request(path, n_threads, batch_bytes, &q, handle, workspace_bytes);
 }
 
 // the qual_sum rows of the batch emitted last, if they are still on the device (the caller has synchronised the stream).
@@ -2023,16 +1968,35 @@ static bool qc_collect(GpuDecoder *G) {
     return ok;
 }
 
-// The request's result, once every batch has been emitted: waits for `stream`, takes the last batch's rows and the histogram
-// from the device and leaves them in the host-side result (coral_bamgpu_host -> coral_bam_qc_sizes / _fill).
-extern "C" int coral_bamgpu_qc_result(void *handle, void *stream_) {
+// Once every batch has been emitted: waits for `stream_` and leaves what was requested in the host-side result
+// (coral_bamgpu_host -> coral_bam_coverage_result, coral_bam_index_sizes / _fill, coral_bam_qc_sizes / _fill).
+extern "C" int coral_bamgpu_finish(void *handle, void *stream_) {
     GpuDecoder *G = (GpuDecoder *)handle;
-    if (!G || !G->qc_on) return CORAL_ERR_ARG;
-    if (!G->finished || G->have_cur) { set_error("coral_bamgpu_qc_result: the decode is not finished"); return CORAL_ERR_ARG; }
-    if (hipStreamSynchronize((hipStream_t)stream_) != hipSuccess || !qc_collect(G) ||
-        hipMemcpy(G->D.qc.hist, G->d_qc_hist, 256 * 8, hipMemcpyDeviceToHost) != hipSuccess) {
-        set_error("coral_bamgpu_qc_result: copy of the read-QC arrays failed");
-        return CORAL_ERR_HIP;
+    if (!G) return CORAL_ERR_ARG;
+    if (!G->finished || G->have_cur) { set_error("coral_bamgpu_finish: the decode is not finished"); return CORAL_ERR_ARG; }
+    const Request &R = G->req;
+    if (!R.has_cov && !R.want_index && !R.want_qc) return CORAL_OK;
+    auto get = [](void *dst, const void *src, size_t bytes) { return bytes == 0 || hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) == hipSuccess; };
+    bool ok = hipStreamSynchronize((hipStream_t)stream_) == hipSuccess;
+    if (ok && R.has_cov) {
+        G->D.cov.assign(R.cov.size(), 0);
+        ok = get(G->D.cov.data(), G->cov_counts, R.cov.size() * 8);
+    }
+    IndexPartial &P = G->D.idx;
+    unsigned long long state[2] = {0, 0}, no_coor = 0;
+    int32_t unsorted = 0;
+    if (ok && R.want_index) {
+        const size_t n_ref = P.n_mapped.size();
+        ok = get(P.lin.data(), G->X.lin, P.lin.size() * 8) && get(P.n_mapped.data(), G->X.n_mapped, n_ref * 8) &&
+             get(P.n_unmapped.data(), G->X.n_unmapped, n_ref * 8) && get(&no_coor, G->X.n_no_coor, 8) && get(state, G->X.state, 16) &&
+             get(&unsorted, G->X.unsorted, 4);
+    }
+    if (ok && R.want_qc) ok = qc_collect(G) && get(G->D.qc.hist, G->d_qc_hist, 256 * 8);
+    if (!ok) { set_error("coral_bamgpu_finish: copy of the requested results failed"); return CORAL_ERR_HIP; }
+    if (unsorted || P.unsorted) { set_error("the records are not in coordinate order: no index can be built"); return CORAL_ERR_FORMAT; }
+    if (R.want_index) {
+        P.n_no_coor = (int64_t)no_coor;
+        P.end_voff = state[G->idx_parity];
     }
     return CORAL_OK;
 }
@@ -2069,7 +2033,7 @@ extern "C" int coral_bamgpu_start(void *handle, void *workspace, int64_t workspa
     }
     if ((e = hipStreamCreateWithFlags(&G->s_crc, hipStreamNonBlocking)) != hipSuccess) return bad("hipStreamCreate", e);
     G->t_alloc = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_alloc0).count();
-    if (G->idx_on) {
+    if (G->req.want_index) {
         const size_t n_ref = G->D.ref_lens.size();
         // with nothing in front of the first record (rank 0) the first batch's end state is never read; a later rank's first
         // record is found by search and must start inside its batch (checked in coral_bamgpu_next)
@@ -2079,7 +2043,16 @@ extern "C" int coral_bamgpu_start(void *handle, void *workspace, int64_t workspa
             (e = hipMemcpy(G->X.lin_off, G->D.idx.lin_off.data(), (n_ref + 1) * 8, hipMemcpyHostToDevice)) != hipSuccess)
             return bad("index request set-up", e);
     }
-    if (G->qc_on && (e = hipMemset(G->d_qc_hist, 0, 256 * 8)) != hipSuccess) return bad("read-QC request set-up", e);
+    if (G->req.want_qc && (e = hipMemset(G->d_qc_hist, 0, 256 * 8)) != hipSuccess) return bad("read-QC request set-up", e);
+    if (G->cov.n > 0) {
+        const CovTable &T = G->req.cov;
+        const size_t b = T.size() * 4;
+        if ((e = hipMemcpy((void *)G->cov.tid, T.tid.data(), b, hipMemcpyHostToDevice)) != hipSuccess ||
+            (e = hipMemcpy((void *)G->cov.lo, T.lo.data(), b, hipMemcpyHostToDevice)) != hipSuccess ||
+            (e = hipMemcpy((void *)G->cov.hi, T.hi.data(), b, hipMemcpyHostToDevice)) != hipSuccess ||
+            (e = hipMemset(G->cov_counts, 0, 2 * b)) != hipSuccess)
+            return bad("coverage request set-up", e);
+    }
     G->feeder = std::thread(feeder_main, G);
     G->worker = std::thread(worker_main, G);
     return CORAL_OK;
@@ -2112,7 +2085,7 @@ extern "C" int coral_bamgpu_next(void *handle, int64_t out[4], void *stream_) {
             G->cv.wait(lk, [&] { return G->inflate_launched > kw || !G->feeder_error.empty(); });
             if (G->inflate_launched <= kw) { G->error = G->feeder_error; return fail(CORAL_ERR_HIP); }
         }
-        if (!G->span_mode || bi.span >= G->cur_span) break;
+        if (!G->req.span_mode || bi.span >= G->cur_span) break;
         // a batch of overhang blocks behind a span whose last record has been seen already: nothing to parse, the slot is free
         // again once its inflate has run
         const int sl = G->k & 1;
@@ -2127,7 +2100,7 @@ extern "C" int coral_bamgpu_next(void *handle, int64_t out[4], void *stream_) {
         G->cv.notify_all();
         ++G->k;
     }
-    if (G->span_mode) {
+    if (G->req.span_mode) {
         if (bi.span > G->cur_span) {             // the span in front ran out of blocks without reaching its end
             if (G->carry_len > 0) { G->error = "a record straddles further than the supported overhang"; return fail(CORAL_ERR_FORMAT); }
             G->cur_span = bi.span;
@@ -2189,7 +2162,7 @@ extern "C" int coral_bamgpu_next(void *handle, int64_t out[4], void *stream_) {
         still_searching = !bi.last;
     }
     const long long n_rec = res[0], carry_pos = res[1];
-    if (G->idx_on && G->searching && n_rec > 0 && res[5] < CARRY_CAP) {
+    if (G->req.want_index && G->searching && n_rec > 0 && res[5] < CARRY_CAP) {
         // (a byte range that found no record start in its first batch and finds one in the bytes kept from it)
         G->error = "index request: the first record of the byte range does not start in the batch it was found in";
         return fail(CORAL_ERR_FORMAT);
@@ -2231,7 +2204,7 @@ extern "C" int coral_bamgpu_next(void *handle, int64_t out[4], void *stream_) {
     const bool done = res[2] != 0;
     // (a span decode goes on with the next span)
     auto verdict = [&](int v) {
-        if (!G->span_mode) return;
+        if (!G->req.span_mode) return;
         {
             std::lock_guard<std::mutex> lk(G->m);
             if (G->span_verdict[(size_t)bi.span] == 0) G->span_verdict[(size_t)bi.span] = v;
@@ -2241,7 +2214,7 @@ extern "C" int coral_bamgpu_next(void *handle, int64_t out[4], void *stream_) {
     auto range_done = [&]() {
         G->carry_len = 0;
         verdict(1);
-        if (G->span_mode && G->cur_span + 1 < (int)G->spans.size()) ++G->cur_span; else G->finished = true;
+        if (G->req.span_mode && G->cur_span + 1 < (int)G->spans.size()) ++G->cur_span; else G->finished = true;
     };
     if (done) {
         range_done();
@@ -2321,9 +2294,9 @@ extern "C" int coral_bamgpu_emit(void *handle, uint32_t *cigar_dst, int64_t *cig
                   get(J.sa_text.data(), G->d_sa_text, J.sa_text.size()) && get(&na_count, G->d_na_count, 4);
         if (!ok || hipStreamSynchronize(stream) != hipSuccess) return fail(CORAL_ERR_HIP, std::string("copy of the batch's host fields failed: ") + hipGetErrorString(hipGetLastError()));
         G->t_wait_gpu += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_gpu0).count();
-        if (G->qc_on && !qc_collect(G)) return fail(CORAL_ERR_HIP, "copy of the read-QC rows failed");      // (of the batch in front)
+        if (G->req.want_qc && !qc_collect(G)) return fail(CORAL_ERR_HIP, "copy of the read-QC rows failed");      // (of the batch in front)
         for (long long i = 0; i < n; ++i) has_seq[i] = has_seq[i] > 0 ? 1 : 0;       // (arrived as l_seq)
-        if (G->idx_on) {                          // the batch's first record against the last one of the batch in front (inside a batch: k_bam_index)
+        if (G->req.want_index) {                          // the batch's first record against the last one of the batch in front (inside a batch: k_bam_index)
             D.idx.note_order(IndexPartial::sort_word(tid[0], pos[0]), IndexPartial::sort_word(tid[n - 1], pos[n - 1]));
             D.idx.n_rec += n;
         }
@@ -2366,28 +2339,28 @@ extern "C" int coral_bamgpu_emit(void *handle, uint32_t *cigar_dst, int64_t *cig
     } else if (hipStreamSynchronize(stream) != hipSuccess) {
         return fail(CORAL_ERR_HIP, "hipStreamSynchronize failed");
     }
-    if (n > 0 && G->cov_set && G->cov.n > 0) {
+    if (n > 0 && G->cov.n > 0) {
         // window coverage of the batch's records, queued before ev_parsed so that the slot is not inflated into while it reads.
         // The per-record item counts and their offsets use the name / SA length arrays: k_bam_emit has finished with them
         // (the host copies above synchronised the stream) and the next batch's k_bam_meta comes behind on the same stream.
         long long *n_items = G->M.name_len, *item_off = G->M.sa_len;
         hipLaunchKernelGGL(k_bam_cov_plan, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, stream, buf, n, G->M, G->d_end, G->cov,
-                           G->cov_threshold, G->cov_filter_all, n_items);
+                           G->req.cov.threshold, (int)G->req.cov.filter_all, n_items);
         size_t tmp = G->scan_tmp_bytes;
         if (hipcub::DeviceScan::ExclusiveSum(G->d_scan_tmp, tmp, n_items, item_off, (int)(n + 1), stream) != hipSuccess)
             return fail(CORAL_ERR_HIP, "scan of the coverage work items failed");
         // at most one item per record plus one per COV_SLICE bases of SEQ in the batch; 4 waves per workgroup, grid-stride beyond
         const long long items = n + ((long long)CARRY_CAP + (long long)G->cur.infl_bytes) / COV_SLICE + 1;
         const unsigned blocks = (unsigned)std::min<long long>((items + 3) / 4, 8192);
-        hipLaunchKernelGGL(k_bam_cov_count, dim3(blocks), dim3(256), 0, stream, buf, n, G->M, G->cov, G->cov_threshold, item_off, G->cov_counts);
+        hipLaunchKernelGGL(k_bam_cov_count, dim3(blocks), dim3(256), 0, stream, buf, n, G->M, G->cov, G->req.cov.threshold, item_off, G->cov_counts);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return fail(CORAL_ERR_HIP, std::string("window coverage launch failed: ") + hipGetErrorString(e));
     }
-    if (n > 0 && G->qc_on) {
+    if (n > 0 && G->req.want_qc) {
         // read QC of the batch's records, behind the coverage kernels on the same stream and, like them, in front of ev_parsed.
         // Item counts and offsets use the name / SA length arrays again (the coverage kernels in front have finished with them).
         // Nothing is waited for here: the rows are fetched with the next batch's host fields (behind that emit's stream
-        // synchronisation, which any kernel queued here is in front of), or by coral_bamgpu_qc_result.
+        // synchronisation, which any kernel queued here is in front of), or by coral_bamgpu_finish.
         long long *n_items = G->M.name_len, *item_off = G->M.sa_len;
         long long *rows = G->d_qc_sum;
         hipLaunchKernelGGL(k_bam_qc_plan, dim3((unsigned)((n + 1 + WAVE - 1) / WAVE)), dim3(WAVE), 0, stream, buf, G->d_rec_start, n, G->M, rows, n_items);
@@ -2402,7 +2375,7 @@ extern "C" int coral_bamgpu_emit(void *handle, uint32_t *cigar_dst, int64_t *cig
         if (e != hipSuccess) return fail(CORAL_ERR_HIP, std::string("read-QC launch failed: ") + hipGetErrorString(e));
         G->qc_pending_n = n;
     }
-    if (G->idx_on) {
+    if (G->req.want_index) {
         // the batch's part of the BAI index, behind the coverage kernels on the same stream: every per-record array of the parse
         // is free by now except the fixed fields and the end positions (the next batch's k_bam_meta comes behind on this stream)
         unsigned long long *voff = (unsigned long long *)G->d_cig_off, *out_voff = (unsigned long long *)G->M.sa_src;
@@ -2439,50 +2412,6 @@ extern "C" int coral_bamgpu_emit(void *handle, uint32_t *cigar_dst, int64_t *cig
     G->have_cur = false;
     ++G->k;
     if (G->finished) D.seconds = G->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - G->t_start).count();
-    return CORAL_OK;
-}
-
-// Window-coverage request: after open, before start.  seg_* are device arrays of n_seg sorted, disjoint segments; counts is a
-// device array of n_seg int64 the caller has zeroed; both must outlive the decode.  Checked here on a host copy.
-extern "C" int coral_bamgpu_coverage(void *handle, int32_t n_seg, const int32_t *seg_tid, const int32_t *seg_start, const int32_t *seg_end,
-                                     int32_t quality_threshold, int32_t read_callback, int64_t *counts) {
-    GpuDecoder *G = (GpuDecoder *)handle;
-    if (!G || n_seg < 0 || (n_seg > 0 && !counts)) return CORAL_ERR_ARG;
-    if (G->feeder.joinable() || G->cov_set) { set_error("coral_bamgpu_coverage: call it once, after open and before start"); return CORAL_ERR_ARG; }
-    std::vector<int32_t> h((size_t)n_seg * 3);
-    if (n_seg > 0) {
-        if (!seg_tid || !seg_start || !seg_end) return CORAL_ERR_ARG;
-        if (hipMemcpy(h.data(), seg_tid, (size_t)n_seg * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(h.data() + n_seg, seg_start, (size_t)n_seg * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(h.data() + 2 * (size_t)n_seg, seg_end, (size_t)n_seg * 4, hipMemcpyDeviceToHost) != hipSuccess) {
-            set_error("coral_bamgpu_coverage: cannot read the segment table");
-            return CORAL_ERR_HIP;
-        }
-    }
-    CovTable T;
-    std::string err;
-    if (!make_cov_table(n_seg, h.data(), h.data() + n_seg, h.data() + 2 * (size_t)n_seg, quality_threshold, read_callback, T, err)) {
-        set_error(err);
-        return CORAL_ERR_ARG;
-    }
-    G->cov = CovSegs{seg_tid, seg_start, seg_end, (int)n_seg};
-    G->cov_threshold = quality_threshold;
-    G->cov_filter_all = read_callback;
-    G->cov_counts = (unsigned long long *)counts;
-    G->cov_set = true;
-    return CORAL_OK;
-}
-
-// The request's counts, once every batch has been emitted: waits for `stream` and copies the n_seg device counters to `counts` (host).
-extern "C" int coral_bamgpu_coverage_result(void *handle, int32_t n_seg, int64_t *counts, void *stream_) {
-    GpuDecoder *G = (GpuDecoder *)handle;
-    if (!G || !G->cov_set || n_seg != G->cov.n || (n_seg > 0 && !counts)) return CORAL_ERR_ARG;
-    if (!G->finished || G->have_cur) { set_error("coral_bamgpu_coverage_result: the decode is not finished"); return CORAL_ERR_ARG; }
-    if (hipStreamSynchronize((hipStream_t)stream_) != hipSuccess ||
-        (n_seg > 0 && hipMemcpy(counts, G->cov_counts, (size_t)n_seg * 8, hipMemcpyDeviceToHost) != hipSuccess)) {
-        set_error("coral_bamgpu_coverage_result: copy of the counts failed");
-        return CORAL_ERR_HIP;
-    }
     return CORAL_OK;
 }
 

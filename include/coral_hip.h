@@ -383,7 +383,30 @@ int coral_bam_write(const char *path, int64_t n_rec, const int32_t *tid, const i
                     const int32_t *nonacgt_pos, const char *const *names, int32_t n_ref, const char *const *ref_names,
                     const int32_t *ref_lens, uint32_t seed, int32_t level, int32_t n_threads);
 const char *coral_bam_last_error(void);
-/* Window coverage counted during the decode — replaces, for the coverage track of `plot`, the per-window
+/* What a decode is asked for besides (or instead of) the records of a byte range.  Host pointers only; the arrays are read
+ * during the open call and not kept.  Every rule is checked by both pipelines alike (CORAL_ERR_ARG, coral_bam_last_error says
+ * why): world >= 1 and 0 <= rank < world; spans sorted, disjoint, non-empty and inside the file; segments sorted by (tid,
+ * start), disjoint, 0 <= start <= end; quality_threshold 0..255; read_callback 0 or 1; no want_index / want_qc on a span
+ * decode.  A span decode is not sharded: rank and world are taken as 0 and 1. */
+typedef struct {
+    int32_t rank, world;                       /* byte range (ignored when n_spans >= 0) */
+    int32_t n_spans;                           /* -1: the byte range; >= 0: only records starting inside these spans */
+    const uint64_t *span_beg, *span_end;       /* virtual offsets, sorted, disjoint, non-empty */
+    int32_t n_seg;                             /* -1: no coverage request; >= 0: sorted, disjoint segments */
+    const int32_t *seg_tid, *seg_start, *seg_end;
+    int32_t quality_threshold, read_callback;
+    int32_t want_index, want_qc;
+} coral_bam_request_t;
+/* coral_bam_decode_range with a request; the results that ride along are read from the handle (of this call, or of
+ * coral_bamgpu_host) with coral_bam_coverage_result, coral_bam_index_sizes / _fill and coral_bam_qc_sizes / _fill.
+ *
+ * Spans (n_spans >= 0) - replaces htslib's hts_itr_query + bgzf_seek behind every lr_bamfh.count_coverage(chrom, w, w + window,
+ * ...) of /root/reference/src/plot_amplicons.py:399-409: the records that START inside n_spans spans [span_beg, span_end) of
+ * virtual offsets (the chunks of a region query).  Each span begins at a known record start (no search), ends in front of the
+ * record at or behind its end, and only its blocks (plus what its last record straddles into) are inflated;
+ * coral_bam_decode_stats counts the blocks inflated.
+ *
+ * Window coverage (n_seg >= 0) - replaces, for the coverage track of `plot`, the per-window
  * lr_bamfh.count_coverage(chrom, w, w + window, quality_threshold=..., read_callback='nofilter') calls
  * (/root/reference/src/plot_amplicons.py:399-400, :408-409; threshold from :935): pysam count_coverage summed over its four
  * arrays, for any base-quality threshold and both read callbacks.  The caller cuts its windows into n_seg sorted (by tid,
@@ -391,18 +414,11 @@ const char *coral_bam_last_error(void);
  * base counts when its record is on the segment's contig (read_callback 1 = 'all': none of the flags 0x704), has SEQ, it is
  * an aligned base of an M / = / X op (the real CIGAR: CG:B,I for the placeholder) inside the segment, its SEQ code is A, C,
  * G or T, and quality_threshold (0..255) is 0 or the record has QUAL (first byte not 0xff) with QUAL >= quality_threshold
- * there.  `decode_range_cov` is coral_bam_decode_range with such a request (each parse task keeps partial counts, added up
- * in file order); `coverage_result` copies the n_seg int64 counts of the handle. */
-int coral_bam_decode_range_cov(const char *path, int32_t n_threads, int32_t rank, int32_t world, int32_t n_seg,
-                               const int32_t *seg_tid, const int32_t *seg_start, const int32_t *seg_end,
-                               int32_t quality_threshold, int32_t read_callback, void **handle);
-int coral_bam_coverage_result(void *handle, int32_t n_seg, int64_t *counts);
-/* BAI index (SAMv1 5.2) built during the decode, and the decode of the regions such an index names - replaces what the
- * reference gets from htslib behind pysam: the "Sorted indexed" BAM it opens was indexed by `samtools index`
- * (hts_idx_push / hts_idx_finish), and every lr_bamfh.count_coverage(chrom, w, w + window, ...) of
- * /root/reference/src/plot_amplicons.py:399-409 goes through hts_itr_query + bgzf_seek on that index.
- *   decode_range_idx  coral_bam_decode_range with an index request: besides the records, what the byte range contributes to
- *          the file's index.  index_sizes -> heads, linear-index windows, contigs, records; index_fill copies
+ * there.  `coverage_result` copies the n_seg int64 counts of the handle.
+ *
+ * BAI index (want_index; SAMv1 5.2) - replaces what the reference gets from htslib behind pysam: the "Sorted indexed" BAM it
+ * opens was indexed by `samtools index` (hts_idx_push / hts_idx_finish).  Besides the records, what the byte range contributes
+ * to the file's index.  index_sizes -> heads, linear-index windows, contigs, records; index_fill copies
  *            head_key / head_voff  one entry per maximal run of file-consecutive records with the same (tid, bin), in file
  *                      order: tid * 65536 + reg2bin(beg, end) (-1: a record without coordinates) and the virtual offset
  *                      (block file offset << 16 | offset in the inflated block) of the run's first record; a run's chunk
@@ -414,33 +430,24 @@ int coral_bam_coverage_result(void *handle, int32_t n_seg, int64_t *counts);
  *          A record is indexed as [max(pos, 0), bam_endpos), one base without a reference length; a record that sorts in
  *          front of its predecessor fails the decode.  Partial results of consecutive byte ranges concatenate (a run that
  *          goes on across the boundary is one run, windows take the minimum) into the whole file's.
- *   decode_spans / decode_spans_cov  coral_bam_decode_range / _range_cov for the records that START inside n_spans sorted,
- *          disjoint spans [span_beg, span_end) of virtual offsets (the chunks of a region query): each span begins at a
- *          known record start (no search), ends in front of the record at or behind its end, and only its blocks (plus
- *          what its last record straddles into) are inflated; coral_bam_decode_stats counts the blocks inflated. */
-int coral_bam_decode_range_idx(const char *path, int32_t n_threads, int32_t rank, int32_t world, void **handle);
-int coral_bam_index_sizes(void *handle, int64_t sizes[4]);
-int coral_bam_index_fill(void *handle, int64_t *head_key, uint64_t *head_voff, uint64_t *lin, int64_t *n_mapped,
-                         int64_t *n_unmapped, uint64_t scalars[4]);
-int coral_bam_decode_spans(const char *path, int32_t n_threads, int32_t n_spans, const uint64_t *span_beg,
-                           const uint64_t *span_end, void **handle);
-/* Read QC counted during the decode - replaces the one pass over every read of the reference's
- * scripts/report_nanopore_qc.py:35-48 (len(sequence) and np.mean(quality) per read of the FASTQ the file was aligned from)
- * and feeds its summary, scripts/report_nanopore_qc.py:70-74 (Q25 / Q50 / Q75 of both, quality_control_summary.tsv).
- *   decode_range_qc  coral_bam_decode_range with a read-QC request.  A READ is a record with flag & 0x900 == 0 and l_seq > 0
- *          (one per FASTQ record; mapped or not); a read whose first QUAL byte is 0xff has no quality.
+ *
+ * Read QC (want_qc) - replaces the one pass over every read of the reference's scripts/report_nanopore_qc.py:35-48
+ * (len(sequence) and np.mean(quality) per read of the FASTQ the file was aligned from) and feeds its summary,
+ * scripts/report_nanopore_qc.py:70-74 (Q25 / Q50 / Q75 of both, quality_control_summary.tsv).  A READ is a record with
+ * flag & 0x900 == 0 and l_seq > 0 (one per FASTQ record; mapped or not); a read whose first QUAL byte is 0xff has no quality.
  *   qc_sizes -> records, reads; qc_fill copies, per read in file order, length (l_seq), qual_sum (sum of its QUAL bytes,
  *          -1 without quality), mapq and flag; hist[256] = count of every QUAL byte value over the reads with quality;
  *          counters = records, reads, records with flag 0x100, with flag 0x800, reads with flag 0x4, primary records
  *          without SEQ, reads without quality, bases of all reads.  Integers only: mean quality of a read is
  *          qual_sum / length on the host.  Results of consecutive byte ranges concatenate / add up. */
-int coral_bam_decode_range_qc(const char *path, int32_t n_threads, int32_t rank, int32_t world, void **handle);
+int coral_bam_decode_request(const char *path, int32_t n_threads, const coral_bam_request_t *req, void **handle);
+int coral_bam_coverage_result(void *handle, int32_t n_seg, int64_t *counts);
+int coral_bam_index_sizes(void *handle, int64_t sizes[4]);
+int coral_bam_index_fill(void *handle, int64_t *head_key, uint64_t *head_voff, uint64_t *lin, int64_t *n_mapped,
+                         int64_t *n_unmapped, uint64_t scalars[4]);
 int coral_bam_qc_sizes(void *handle, int64_t sizes[2]);
 int coral_bam_qc_fill(void *handle, int32_t *length, int64_t *qual_sum, int32_t *mapq, int32_t *flag, int64_t hist[256],
                       int64_t counters[8]);
-int coral_bam_decode_spans_cov(const char *path, int32_t n_threads, int32_t n_spans, const uint64_t *span_beg,
-                               const uint64_t *span_end, int32_t n_seg, const int32_t *seg_tid, const int32_t *seg_start,
-                               const int32_t *seg_end, int32_t quality_threshold, int32_t read_callback, void **handle);
 
 /* ------------------------------------------------------------------------------------------------
  * coral_bamgpu_* — the same decode with the inflate and the record parsing ON THE GPU: the host reads the file and sends
@@ -463,32 +470,23 @@ int coral_bam_decode_spans_cov(const char *path, int32_t n_threads, int32_t n_sp
  *   stats  stats = batches, segments whose speculative record start was replaced by the exact walk, records fetched
  *          whole for the non-ACGT list, batch capacity; seconds = total wall time, host-side field handling, file reads,
  *          set-up of pinned buffers and streams, time the caller waited for the file feeder, ... for the GPU
- *   coverage         the window-coverage request of coral_bam_decode_range_cov on the GPU (same segments, same rules;
- *          /root/reference/src/plot_amplicons.py:399-400, :408-409): after open, before start; seg_* are device arrays,
- *          `counts` n_seg device int64 the caller zeroes, both live until the decode ends.  Per batch, k_bam_cov_plan +
- *          k_bam_cov_count read the batch's inflated SEQ / QUAL before the slot is reused (one wave per 16 384 query bases
- *          of a record, one 64-bit atomic per work item and segment).  Without a request no kernel is added.
- *   coverage_result  after the last batch: waits for `stream`, copies the n_seg counts to host memory
- *   open_spans       open for coral_bam_decode_spans on the GPU (htslib's hts_itr_query + bgzf_seek behind the reference's
- *          per-window count_coverage calls): the spans go through the same batches one after the other, each from its known
- *          first record to the record at or behind its end; only their blocks are read, uploaded and inflated.  A coverage
- *          request works on it unchanged.  Statistics count every block read.
- *   index            the index request of coral_bam_decode_range_idx on the GPU (htslib's hts_idx_push during
- *          `samtools index`): after open, before start and BEFORE the workspace is allocated - *workspace_bytes is the new
- *          size (block offsets, linear index, counters; everything per record re-uses the batch's scratch).  Per batch
- *          k_bam_index (one thread per record: virtual offset by binary search of the batch's block table - a record carried
- *          in from the batch in front keeps the offset it STARTED at -, bin, run heads, 64-bit atomicMin per overlapped
- *          window, per-contig counters, order check), one scan and k_bam_index_compact; the host joins the runs that go on
- *          across batches.  Without a request no kernel is added.
- *   index_result     after the last batch: waits for `stream`, leaves the partial index in the handle of `host`
- *          (coral_bam_index_sizes / _fill); fails when the records are not in coordinate order
- *   qc               the read-QC request of coral_bam_decode_range_qc on the GPU (scripts/report_nanopore_qc.py:35-48 of the
- *          reference): after open (not open_spans), before start and BEFORE the workspace is allocated - *workspace_bytes
- *          is the new size.  Per batch k_bam_qc_plan, one scan and k_bam_qc read the batch's QUAL before the slot is reused
- *          (one wave per 16 384 QUAL bytes of a read, aligned 16-byte loads, one 64-bit atomic per work item, the histogram
- *          in LDS per workgroup).  Without a request no kernel is added and nothing more is allocated.
- *   qc_result        after the last batch: waits for `stream`, leaves rows and histogram in the handle of `host`
- *          (coral_bam_qc_sizes / _fill; scripts/report_nanopore_qc.py:70-74 is computed from them)
+ *   open_request  open with a coral_bam_request_t; *workspace_bytes is final (the requests' own arrays are part of it).
+ *          Spans go through the same batches one after the other, each from its known first record to the record at or
+ *          behind its end; only their blocks are read, uploaded and inflated, and statistics count every block read.
+ *          Without a request no kernel is added and nothing more is allocated.  Per batch, with
+ *            a coverage request  k_bam_cov_plan + k_bam_cov_count read the batch's inflated SEQ / QUAL before the slot is reused
+ *                      (one wave per 16 384 query bases of a record, one 64-bit atomic per work item and segment); segments
+ *                      and counters live in the workspace
+ *            want_index  k_bam_index (one thread per record: virtual offset by binary search of the batch's block table - a
+ *                      record carried in from the batch in front keeps the offset it STARTED at -, bin, run heads, 64-bit
+ *                      atomicMin per overlapped window, per-contig counters, order check), one scan and k_bam_index_compact;
+ *                      the host joins the runs that go on across batches
+ *            want_qc     k_bam_qc_plan, one scan and k_bam_qc read the batch's QUAL before the slot is reused (one wave per
+ *                      16 384 QUAL bytes of a read, aligned 16-byte loads, one 64-bit atomic per work item, the histogram in
+ *                      LDS per workgroup)
+ *   finish        after the last batch (CORAL_ERR_ARG before): waits for `stream` once and leaves what was requested in the
+ *          handle of `host` (coral_bam_coverage_result, coral_bam_index_sizes / _fill, coral_bam_qc_sizes / _fill); fails when
+ *          an index was requested and the records are not in coordinate order; with nothing requested it does nothing
  * coral_bgzf_inflate: one inflate launch over caller-provided device buffers — desc = n_blocks x {src_off, src_len,
  * dst_off, isize} uint32 (raw DEFLATE streams in `comp`, which must be readable 4096 bytes beyond the last stream);
  * status[b] = 0 or the decoder's error code.
@@ -500,15 +498,9 @@ int coral_bamgpu_next(void *handle, int64_t out[4], void *stream);
 int coral_bamgpu_emit(void *handle, uint32_t *cigar_dst, int64_t *cigar_off_dst, void *stream);
 int coral_bamgpu_host(void *handle, void **decoded);
 int coral_bamgpu_stats(void *handle, int64_t stats[4], double seconds[6]);
-int coral_bamgpu_coverage(void *handle, int32_t n_seg, const int32_t *seg_tid, const int32_t *seg_start, const int32_t *seg_end,
-                          int32_t quality_threshold, int32_t read_callback, int64_t *counts);
-int coral_bamgpu_coverage_result(void *handle, int32_t n_seg, int64_t *counts, void *stream);
-int coral_bamgpu_open_spans(const char *path, int32_t n_threads, int32_t n_spans, const uint64_t *span_beg,
-                            const uint64_t *span_end, int64_t batch_bytes, void **handle, int64_t *workspace_bytes);
-int coral_bamgpu_index(void *handle, int64_t *workspace_bytes);
-int coral_bamgpu_index_result(void *handle, void *stream);
-int coral_bamgpu_qc(void *handle, int64_t *workspace_bytes);
-int coral_bamgpu_qc_result(void *handle, void *stream);
+int coral_bamgpu_open_request(const char *path, int32_t n_threads, int64_t batch_bytes, const coral_bam_request_t *req,
+                              void **handle, int64_t *workspace_bytes);
+int coral_bamgpu_finish(void *handle, void *stream);
 int coral_bamgpu_close(void *handle);
 int coral_bgzf_inflate(const uint8_t *comp, const uint32_t *desc, int32_t n_blocks, uint8_t *out, int32_t *status,
                        void *stream);

@@ -1,0 +1,140 @@
+"""The request of a BAM decode (coral_bam_request_t): one struct says what a decode of either pipeline is asked for - a byte
+range or spans, and the window coverage, the BAI index and the read QC that ride along.  Both pipelines parse it with the same
+code (coral_bam_common.h: parse_request), so they accept and refuse the same requests, and what rides along is the same whether it
+is asked for alone or together."""
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from coral_amd import _lib, bam
+from tests.test_read_qc import assert_equal, assert_same, assert_same_records, case  # noqa: F401  (case: the module's fixture)
+
+CORAL_OK, CORAL_ERR_ARG = 0, -1
+WINDOWS = [("chr8", 149_000, 152_000), ("chr8", 150_000, 150_100), ("chr8", 0, 1 << 28)]
+
+
+def segments(case):
+    return bam.coverage_segments(WINDOWS, case["rec"].header_chroms)[0]
+
+
+def assert_same_index(a, b):
+    assert set(a) == set(b)
+    for k, v in b.items():
+        assert np.array_equal(a[k], v), k
+
+
+# ---- host pipeline -------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n_threads", [1, 2])
+def test_host_three_requests_at_once(case, n_threads):
+    segs = segments(case)
+    decode = lambda **kw: bam._decode(case["path"], "cpu", n_threads=n_threads, **kw)
+    alone_cov = decode(coverage=(segs, 20, 0), records=False).counts
+    alone_idx = decode(index=True, records=False).index
+    alone_qc = decode(qc=True, records=False).qc
+    got = decode(coverage=(segs, 20, 0), index=True, qc=True)
+    assert alone_cov.sum() > 0 and np.array_equal(got.counts, alone_cov)
+    assert_same_index(got.index, alone_idx)
+    assert_same(got.qc, alone_qc)
+    assert_equal(got.qc, case["want"])
+    assert_same_records(got.records, bam.decode_bam(case["path"], n_threads=n_threads))
+
+
+def bad_requests(case):
+    """name -> (arguments of _lib.bam_request, a word of the message)"""
+    V = lambda block, off=0: (block << 16) | off
+    size = os.path.getsize(case["path"])
+    assert size > 4000
+    segs = segments(case)
+    assert segs.shape[1] >= 2
+    return {
+        "rank >= world": (dict(rank=2, world=2), "rank"),
+        "spans out of order": (dict(spans=[[V(3000), V(4000)], [V(1000), V(2000)]]), "sorted"),
+        "overlapping spans": (dict(spans=[[V(1000), V(3000)], [V(2000), V(4000)]]), "disjoint"),
+        "an empty span": (dict(spans=[[V(1000, 7), V(1000, 7)]]), "non-empty"),
+        "a span beyond the file": (dict(spans=[[V(size + 5), V(size + 9)]]), "outside the file"),
+        "unsorted segments": (dict(coverage=(segs[:, ::-1], 20, 0)), "sorted"),
+        "quality threshold above 255": (dict(coverage=(segs, 256, 0)), "threshold"),
+        "quality threshold below 0": (dict(coverage=(segs, -1, 0)), "threshold"),
+        "index request with spans": (dict(spans=[[V(1000), V(2000)]], index=True), "span decode"),
+        "read-QC request with spans": (dict(spans=[[V(1000), V(2000)]], qc=True), "span decode"),
+    }
+
+
+def test_host_refuses_bad_requests(case):
+    L = _lib.lib()
+    for name, (kw, word) in bad_requests(case).items():
+        req, h = _lib.bam_request(**kw), C.c_void_p()
+        rc = L.coral_bam_decode_request(case["path"].encode(), 1, C.byref(req), C.byref(h))
+        assert rc == CORAL_ERR_ARG and h.value is None, name
+        assert word in L.coral_bam_last_error().decode(), name
+
+
+# ---- GPU pipeline --------------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+def test_gpu_refuses_the_same_requests(case):
+    L = _lib.lib()
+    for name, (kw, word) in bad_requests(case).items():
+        req, h, ws_bytes = _lib.bam_request(**kw), C.c_void_p(), C.c_int64(0)
+        rc = L.coral_bamgpu_open_request(case["path"].encode(), 1, 0, C.byref(req), C.byref(h), C.byref(ws_bytes))
+        assert rc == CORAL_ERR_ARG and h.value is None and ws_bytes.value == 0, name
+        assert word in L.coral_bam_last_error().decode(), name
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("batch", [0, 1 << 20])
+def test_gpu_coverage_from_the_workspace_equals_host(case, batch):
+    segs = segments(case)
+    S = segs.shape[1]
+    want = bam._decode(case["path"], "cpu", coverage=(segs, 20, 0), records=False).counts
+    bam.decode_bam_gpu(case["path"], "cuda:0", batch_bytes=batch)
+    plain_bytes = bam.LAST_DECODE["workspace_bytes"]
+    got = bam._decode(case["path"], "cuda:0", batch_bytes=batch, coverage=(segs, 20, 0), records=False)
+    assert want.sum() > 0 and got.counts.dtype == np.int64 and np.array_equal(got.counts, want)
+    assert bam.LAST_DECODE["where"] == "gpu" and (batch == 0 or bam.LAST_DECODE["batches"] >= 3)
+    up256 = lambda n: (n + 255) & ~255
+    assert bam.LAST_DECODE["workspace_bytes"] == plain_bytes + up256(3 * S * 4) + up256(S * 8)      # segments and counters live there
+    if batch == 0:                                               # an empty table: an empty result, nothing more in the workspace
+        none = bam._decode(case["path"], "cuda:0", coverage=(np.zeros((3, 0), dtype=np.int32), 20, 0), records=False)
+        assert none.counts.dtype == np.int64 and none.counts.shape == (0,) and none.records is None
+        assert bam.LAST_DECODE["workspace_bytes"] == plain_bytes
+
+
+@pytest.mark.gpu
+def test_gpu_finish_before_the_last_batch_is_refused(case):
+    """A state check, on a decode that then goes on to its end: the refusals change nothing."""
+    L = _lib.lib()
+    segs = segments(case)
+    want = bam._decode(case["path"], "cpu", coverage=(segs, 20, 0), records=False).counts
+    dev = torch.device("cuda:0")
+    torch.cuda.set_device(dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    req, h, ws_bytes = _lib.bam_request(coverage=(segs, 20, 0)), C.c_void_p(), C.c_int64(0)
+    assert L.coral_bamgpu_open_request(case["path"].encode(), 2, 1 << 20, C.byref(req), C.byref(h), C.byref(ws_bytes)) == CORAL_OK
+    try:
+        ws = torch.empty(int(ws_bytes.value) + 256, dtype=torch.uint8, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        assert L.coral_bamgpu_start(h, (ws.data_ptr() + 255) & ~255, int(ws_bytes.value)) == CORAL_OK
+
+        def refused():
+            return L.coral_bamgpu_finish(h, stream) == CORAL_ERR_ARG and "not finished" in L.coral_bam_last_error().decode()
+        assert refused()                                         # no batch has been parsed
+        out, batches, pieces = (C.c_int64 * 4)(), 0, []
+        while True:
+            assert L.coral_bamgpu_next(h, out, stream) == CORAL_OK
+            if not out[2]:
+                break
+            assert refused()                                     # a batch is between next and emit
+            pieces.append(torch.empty(max(int(out[1]), 1), dtype=torch.int32, device=dev))
+            assert L.coral_bamgpu_emit(h, pieces[-1].data_ptr(), None, stream) == CORAL_OK
+            batches += 1
+        assert batches >= 3
+        assert L.coral_bamgpu_finish(h, stream) == CORAL_OK
+        dh, counts = C.c_void_p(), np.zeros(segs.shape[1], dtype=np.int64)
+        assert L.coral_bamgpu_host(h, C.byref(dh)) == CORAL_OK
+        assert L.coral_bam_coverage_result(dh, len(counts), counts.ctypes.data) == CORAL_OK
+        assert np.array_equal(counts, want)
+    finally:
+        assert L.coral_bamgpu_close(h) == CORAL_OK

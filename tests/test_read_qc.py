@@ -295,10 +295,10 @@ def assert_same_records(a, b):
 @pytest.mark.gpu
 def test_gpu_request_leaves_the_records_alone(case):
     plain = bam.decode_bam_gpu(case["small"], "cuda:0", batch_bytes=1 << 20)
-    rec, _, _, qc = bam._decode_gpu(case["small"], "cuda:0", None, 0, 1, 1 << 20, qc=True)
-    assert_same_records(rec, plain)
-    assert_equal(qc, case["want"])
-    assert bam._decode_gpu(case["small"], "cuda:0", None, 0, 1, 1 << 20)[3] is None
+    got = bam._decode(case["small"], "cuda:0", batch_bytes=1 << 20, qc=True)
+    assert_same_records(got.records, plain)
+    assert_equal(got.qc, case["want"])
+    assert bam._decode(case["small"], "cuda:0", batch_bytes=1 << 20).qc is None
 
 
 @pytest.mark.gpu
@@ -307,10 +307,10 @@ def test_gpu_three_requests_at_once(case):
     windows = [("chr8", 149_000, 152_000), ("chr8", 150_000, 150_100), ("chr8", 0, 1 << 28)]
     segs, first, last = bam.coverage_segments(windows, rec.header_chroms)
     for batch in (0, 1 << 20):
-        alone_cov = bam._decode_gpu(case["path"], "cuda:0", None, 0, 1, batch, coverage=(segs, 20, 0), records=False)[1]
-        alone_idx = bam._decode_gpu(case["path"], "cuda:0", None, 0, 1, batch, records=False, index=True)[2]
+        alone_cov = bam._decode(case["path"], "cuda:0", batch_bytes=batch, coverage=(segs, 20, 0), records=False).counts
+        alone_idx = bam._decode(case["path"], "cuda:0", batch_bytes=batch, records=False, index=True).index
         plain = bam.decode_bam_gpu(case["path"], "cuda:0", batch_bytes=batch)
-        got_rec, cov, idx, qc = bam._decode_gpu(case["path"], "cuda:0", None, 0, 1, batch, coverage=(segs, 20, 0), index=True, qc=True)
+        got_rec, cov, idx, qc = bam._decode(case["path"], "cuda:0", batch_bytes=batch, coverage=(segs, 20, 0), index=True, qc=True)
         assert alone_cov.sum() > 0 and np.array_equal(cov, alone_cov)
         assert set(idx) == set(alone_idx)
         for k, v in alone_idx.items():
