@@ -4,8 +4,9 @@
     python -m coral_amd.CoRAL reconstruct --lr_bam x.bam --cnv_seed seeds.bed --cn_seg cn.bed --output_prefix out \\
         --skip_cycle_decomp
 
-The `reconstruct` mode and the `hsr` mode (§8(f) item 3) run on the MI355X path, and so do `index` and `qc`
-(the reference's scripts/report_nanopore_qc.py, from one decode of the aligned BAM); the other modes of the
+The `reconstruct` mode and the `hsr` mode (§8(f) item 3) run on the MI355X path, and so do `index`, `qc`
+(the reference's scripts/report_nanopore_qc.py, from one decode of the aligned BAM) and `pileup` (the bases per position of
+regions, pysam's count_coverage as a table); the other modes of the
 reference (seed, plot, cycle2bed) are untouched and are delegated to the reference's own modules when they are
 importable (set CORAL_REFERENCE_SRC to the reference's src/ directory).  The cycle-decomposition step after the graph build is the
 reference's (Gurobi); it runs on the object this module returns.
@@ -68,6 +69,16 @@ def build_parser():
     qp.add_argument("--output_dir", help="Where to write the summary and the plots.", required=True)
     qp.add_argument("--device", help="GPU to use ('cpu': the host pipeline).", default="cuda:0")
     qp.add_argument("--no_plots", help="If specified, write no histogram images.", action='store_true')
+    pp = sub.add_parser("pileup", help="Count the A, C, G and T bases at every position of regions of a (long read) bam file.")
+    pp.add_argument("--lr_bam", help="Sorted (long read) bam file.", required=True)
+    where = pp.add_mutually_exclusive_group(required=True)
+    where.add_argument("--region", help="chr:start-stop (0-based, half-open); may be given several times.", action="append")
+    where.add_argument("--bed", help="Bed file of regions.")
+    pp.add_argument("--min_base_quality", help="Count only bases of at least this quality.", type=int, default=0)
+    pp.add_argument("--read_callback", help="'all' leaves out unmapped, secondary, QC-fail and duplicate reads.",
+                    choices=("all", "nofilter"), default="nofilter")
+    pp.add_argument("--output", help="Name of the output file (tab-separated).", required=True)
+    pp.add_argument("--device", help="GPU to use ('cpu': the host pipeline).", default="cuda:0")
     for mode in ("seed", "plot", "cycle2bed"):
         sub.add_parser(mode, help="(reference implementation; not part of the MI355X path)", add_help=False)
     return parser
@@ -135,6 +146,30 @@ def qc_mode(args):
     return wrote
 
 
+def pileup_mode(args):
+    """chrom, pos (0-based), A, C, G, T of every position of the regions whose depth is above 0, in region order."""
+    from coral_amd import bam
+    if args.bed:
+        with open(args.bed) as fp:
+            rows = [ln.split() for ln in fp if ln.strip() and not ln.startswith(("#", "track", "browser"))]
+        regions = [(r[0], int(r[1]), int(r[2])) for r in rows]
+    else:
+        regions = []
+        for text in args.region:
+            chrom, span = text.rsplit(":", 1)
+            a, b = span.replace(",", "").split("-")
+            regions.append((chrom, int(a), int(b)))
+    p = bam.pileup(args.lr_bam, regions, args.min_base_quality, args.read_callback, device=args.device)
+    with open(args.output, "w") as fp:
+        fp.write("chrom\tpos\tA\tC\tG\tT\n")
+        for chrom, a, b in p.regions:
+            counts = p.counts(chrom, a, b)
+            for k in counts.sum(axis=0).nonzero()[0].tolist():
+                fp.write("%s\t%d\t%d\t%d\t%d\t%d\n" % ((chrom, a + k) + tuple(counts[:, k].tolist())))
+    print("Wrote %s" % args.output)
+    return args.output
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     if argv and argv[0] in ("seed", "plot", "cycle2bed"):
@@ -162,6 +197,8 @@ def main(argv=None):
         return out
     if args.mode == "qc":
         return qc_mode(args)
+    if args.mode == "pileup":
+        return pileup_mode(args)
     parser.print_help()
     return None
 

@@ -24,14 +24,16 @@ class coral_records_t(C.Structure):
 class coral_bam_request_t(C.Structure):
     _fields_ = [("rank", C.c_int32), ("world", C.c_int32), ("n_spans", C.c_int32), ("span_beg", C.c_void_p), ("span_end", C.c_void_p),
                 ("n_seg", C.c_int32), ("seg_tid", C.c_void_p), ("seg_start", C.c_void_p), ("seg_end", C.c_void_p),
-                ("quality_threshold", C.c_int32), ("read_callback", C.c_int32), ("want_index", C.c_int32), ("want_qc", C.c_int32)]
+                ("quality_threshold", C.c_int32), ("read_callback", C.c_int32), ("want_index", C.c_int32), ("want_qc", C.c_int32),
+                ("per_base", C.c_int32)]
 
 
-def bam_request(rank: int = 0, world: int = 1, spans=None, coverage=None, index: bool = False, qc: bool = False) -> coral_bam_request_t:
+def bam_request(rank: int = 0, world: int = 1, spans=None, coverage=None, index: bool = False, qc: bool = False,
+                per_base: bool = False) -> coral_bam_request_t:
     """The request of a BAM decode: ``spans`` uint64 [K][2] virtual offsets (None: the byte range), ``coverage`` = (segments int32
-    [3][S], quality threshold, read_callback code) or None.  The struct keeps the contiguous arrays it points into alive; the
-    rules are the library's to check."""
-    req = coral_bam_request_t(rank=rank, world=world, n_spans=-1, n_seg=-1, want_index=int(index), want_qc=int(qc))
+    [3][S], quality threshold, read_callback code) or None, ``per_base``: the coverage as the table per position and base (the
+    pileup).  The struct keeps the contiguous arrays it points into alive; the rules are the library's to check."""
+    req = coral_bam_request_t(rank=rank, world=world, n_spans=-1, n_seg=-1, want_index=int(index), want_qc=int(qc), per_base=int(per_base))
     req.arrays = []
 
     def pointer(a, dtype):
@@ -127,6 +129,7 @@ def lib():
     Q = C.POINTER(coral_bam_request_t)
     L.coral_bam_decode_request.argtypes = [C.c_char_p, C.c_int32, Q, C.POINTER(C.c_void_p)]
     L.coral_bam_coverage_result.argtypes = [C.c_void_p, C.c_int32, P]
+    L.coral_bam_pileup_result.argtypes = [C.c_void_p, C.c_int64, P]
     L.coral_bam_index_sizes.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
     L.coral_bam_index_fill.argtypes = [C.c_void_p, P, P, P, P, P, C.POINTER(C.c_uint64)]
     L.coral_bam_qc_sizes.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]

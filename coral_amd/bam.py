@@ -7,6 +7,7 @@ real coordinate-sorted BAM (htslib / pysam are not available offline); it is not
 """
 from __future__ import annotations
 
+import array
 import collections
 import ctypes as C
 import gzip
@@ -171,16 +172,20 @@ def decode_bam_gpu(path: str, device="cuda:0", n_threads: Optional[int] = None, 
     return _decode_gpu(path, device, n_threads, batch_bytes, _lib.bam_request(rank, world), True).records      # (whatever CORAL_BAM_DECODE says)
 
 
-DecodeResult = collections.namedtuple("DecodeResult", "records counts index qc")      # what _decode was not asked for is None
+class DecodeResult(collections.namedtuple("DecodeResult", "records counts index qc")):
+    """What _decode returns; what it was not asked for is None.  It unpacks as these four; the table of a pileup request
+    (uint32 [positions][4]) is the attribute ``pileup``."""
+    pileup = None
 
 
 def _decode(path: str, device, *, n_threads: Optional[int] = None, rank: int = 0, world: int = 1, batch_bytes: int = 0, spans=None,
-            coverage=None, index=False, qc=False, records=True) -> DecodeResult:
+            coverage=None, index=False, qc=False, records=True, per_base=False) -> DecodeResult:
     """One decode of the ``rank``-th of ``world`` byte ranges, or of the records that start inside ``spans`` (uint64 [K][2] virtual
     offsets), with what rides along: ``coverage`` = (segments int32 [3][S], quality threshold, read_callback code) gives the S
-    int64 ``counts``, ``index`` the partial BAI index, ``qc`` the ``ReadQC``; ``records`` False leaves the Records out.  On the GPU
-    pipeline when ``_on_gpu(device)``, else on the host."""
-    req = _lib.bam_request(rank, world, spans, coverage, index, qc)
+    int64 ``counts``, ``index`` the partial BAI index, ``qc`` the ``ReadQC``; ``records`` False leaves the Records out.  With
+    ``per_base`` the coverage is counted per position and base: ``pileup`` is the uint32 table [positions of the segments, in
+    segment order][A, C, G, T] and ``counts`` its sums per segment.  On the GPU pipeline when ``_on_gpu(device)``, else on the host."""
+    req = _lib.bam_request(rank, world, spans, coverage, index, qc, per_base)
     if _on_gpu(device):
         return _decode_gpu(path, device, n_threads, batch_bytes, req, records)
     L = _lib.lib()
@@ -211,8 +216,17 @@ def _result_from_handle(L, h, req, records: bool, cigar, cigar_words: int) -> De
     if req.n_seg >= 0:
         counts = np.zeros(req.n_seg, dtype=np.int64)
         _lib.check(L.coral_bam_coverage_result(h, req.n_seg, counts.ctypes.data), "coral_bam_coverage_result")
-    return DecodeResult(_records_from_handle(L, h, cigar, cigar_words) if records else None, counts,
-                        _index_partial_from_handle(L, h) if req.want_index else None, _read_qc_from_handle(L, h) if req.want_qc else None)
+    table = None
+    if req.per_base:
+        seg_start, seg_end = req.arrays[-2], req.arrays[-1]      # (bam_request puts the segment rows last)
+        n_pos = int((seg_end.astype(np.int64) - seg_start).sum())
+        table = np.zeros((n_pos, 4), dtype=np.uint32)
+        if L.coral_bam_pileup_result(h, n_pos, table.ctypes.data) != 0:
+            raise _lib.CoralHipError("coral_bam_pileup_result failed: %s" % L.coral_bam_last_error().decode())
+    res = DecodeResult(_records_from_handle(L, h, cigar, cigar_words) if records else None, counts,
+                       _index_partial_from_handle(L, h) if req.want_index else None, _read_qc_from_handle(L, h) if req.want_qc else None)
+    res.pileup = table
+    return res
 
 
 def _decode_gpu(path: str, device, n_threads: Optional[int], batch_bytes: int, req, records: bool) -> DecodeResult:
@@ -380,18 +394,28 @@ def window_coverage(path: str, windows: Sequence[Tuple[str, int, int]], quality_
     S = segs.shape[1]
     if n_threads is None:
         n_threads = default_threads()
+    res = _decode_segments(path, segs, thr, cb, device, rank, world, batch_bytes, n_threads, index, len(ref_names), False)
+    counts = res.counts if res is not None else np.zeros(S, dtype=np.int64)
+    csum = np.concatenate([[0], np.cumsum(counts, dtype=np.int64)])
+    return (csum[last] - csum[first]).astype(np.int64)
+
+
+def _decode_segments(path, segs, thr, cb, device, rank, world, batch_bytes, n_threads, index, n_ref, per_base):
+    """The decode behind ``window_coverage`` and ``pileup``: the coverage request of ``segs``, through the BAI index ``index`` (the
+    rules of ``window_coverage``) when there is one.  None when the index names no block for the segments: nothing was decoded
+    and every count is 0.  ``LAST_DECODE`` says which index was used."""
     idx, skipped = None, None
     if index is not None and index is not False:
         if world != 1:
             raise ValueError("a region decode is not sharded: index and world > 1 do not go together")
-        idx = _usable_index(path, index, len(ref_names))
+        idx = _usable_index(path, index, n_ref)
     elif index is None and world == 1:
         beside = _index_beside(path)
         if beside is not None:
             try:
                 if os.path.getmtime(beside) < os.path.getmtime(path):
                     raise _lib.CoralHipError("%s is older than the BAM file" % beside)
-                idx = _usable_index(path, beside, len(ref_names))
+                idx = _usable_index(path, beside, n_ref)
             except (_lib.CoralHipError, OSError) as e:
                 skipped = str(e)
     spans = None
@@ -403,19 +427,135 @@ def window_coverage(path: str, windows: Sequence[Tuple[str, int, int]], quality_
             else:
                 regions.append([t, a, b])
         spans = region_spans(idx, regions)
+    res = None
     if spans is not None and len(spans) == 0:
-        counts = np.zeros(S, dtype=np.int64)
         LAST_DECODE.clear()
         LAST_DECODE.update(seconds=0.0, compressed_bytes=0, uncompressed_bytes=0, blocks=0, threads=int(n_threads))
     else:
-        counts = _decode(path, device, n_threads=n_threads, rank=rank, world=world, batch_bytes=batch_bytes, spans=spans,
-                         coverage=(segs, thr, cb), records=False).counts
+        res = _decode(path, device, n_threads=n_threads, rank=rank, world=world, batch_bytes=batch_bytes, spans=spans,
+                      coverage=(segs, thr, cb), records=False, per_base=per_base)
     if idx is not None:
         LAST_DECODE.update(index=idx.path or "<object>", spans=int(len(spans)))
     else:
         LAST_DECODE.update(index=None, index_skipped=skipped)
-    csum = np.concatenate([[0], np.cumsum(counts, dtype=np.int64)])
-    return (csum[last] - csum[first]).astype(np.int64)
+    return res
+
+
+# ----------------------------------------------------------------------------------------------
+# pileup: the bases per position (A / C / G / T), counted during the decode
+# ----------------------------------------------------------------------------------------------
+PILEUP_MAX_POSITIONS = 1 << 28
+
+
+class Pileup:
+    """pysam ``count_coverage`` itself - the four per-position arrays - for the regions of one decode (``pileup``): a stand-in for
+    the reference's ``lr_bamfh`` that answers ANY window inside the loaded regions, at any resolution.  ``regions`` = the merged
+    regions [(chrom, start, stop)] in (contig, start) order, ``table`` uint32 [positions of the regions, in that order][A, C, G, T]."""
+
+    def __init__(self, regions, table, quality_threshold=0, read_callback="nofilter"):
+        self.regions = [(c, int(a), int(b)) for c, a, b in regions]
+        self.quality_threshold = quality_threshold_value(quality_threshold)
+        self.read_callback = read_callback
+        self.table = np.ascontiguousarray(table, dtype=np.uint32).reshape(-1, 4)
+        self._off = np.concatenate([[0], np.cumsum([b - a for _, a, b in self.regions])]).astype(np.int64)
+        if int(self._off[-1]) != len(self.table):
+            raise ValueError("Pileup: the regions hold %d positions, the table %d" % (int(self._off[-1]), len(self.table)))
+
+    def _rows(self, chrom, start, stop):
+        start, stop = int(start), int(stop)
+        if stop >= start:
+            for k, (c, a, b) in enumerate(self.regions):
+                if c == chrom and a <= start and stop <= b:
+                    return self.table[self._off[k] + start - a:self._off[k] + stop - a]
+        raise KeyError("%s:%d-%d is not inside one loaded region" % (chrom, start, stop))
+
+    def counts(self, chrom, start, stop) -> np.ndarray:
+        """int64 [4][stop - start]: the counted A, C, G and T bases at every position of [start, stop).  KeyError when the range
+        is not inside one loaded region."""
+        return np.ascontiguousarray(self._rows(chrom, start, stop).T, dtype=np.int64)
+
+    def depth(self, chrom, start, stop) -> np.ndarray:
+        """int64 [stop - start]: the sum over the four bases."""
+        return self._rows(chrom, start, stop).sum(axis=1, dtype=np.int64)
+
+    def count_coverage(self, contig, start=None, stop=None, region=None, quality_threshold=15, read_callback="all"):
+        """pysam's signature and defaults: four ``array.array('L')`` (A, C, G, T) of ``stop - start`` counts.  ``region`` is a
+        samtools region string ('chr:start-stop', 1-based, inclusive).  ValueError when the threshold or the callback is not
+        what was counted, KeyError when the range is not inside one loaded region."""
+        if quality_threshold_value(quality_threshold) != self.quality_threshold or read_callback != self.read_callback:
+            raise ValueError("this Pileup was counted with quality_threshold=%d, read_callback=%r"
+                             % (self.quality_threshold, self.read_callback))
+        if region is not None:
+            contig, span = region.rsplit(":", 1)
+            a, b = span.replace(",", "").split("-")
+            start, stop = int(a) - 1, int(b)
+        if contig is None or start is None or stop is None:
+            raise KeyError("Pileup answers (contig, start, stop) ranges only")
+        return tuple(array.array("L", row.tolist()) for row in self.counts(contig, start, stop))
+
+    def close(self):
+        self.regions, self.table, self._off = [], np.zeros((0, 4), dtype=np.uint32), np.zeros(1, dtype=np.int64)
+
+
+def pileup_regions(regions, ref_names: Sequence[str]):
+    """Regions (chrom, start, stop), which may overlap or touch -> (the merged, non-empty regions in (contig, start) order,
+    their segments int32 [3][S]).  Argument errors as ``window_coverage``."""
+    reg = sorted((t, min(a, _I32_MAX), min(b, _I32_MAX)) for t, a, b in _regions_as_tids(regions, ref_names))
+    merged = []
+    for t, a, b in reg:
+        if a == b:
+            continue
+        if merged and merged[-1][0] == t and a <= merged[-1][2]:
+            merged[-1][2] = max(merged[-1][2], b)
+        else:
+            merged.append([t, a, b])
+    segs = np.array(merged, dtype=np.int32).reshape(-1, 3).T.copy()
+    return [(ref_names[t], a, b) for t, a, b in merged], segs
+
+
+def pileup(path: str, regions: Sequence[Tuple[str, int, int]], quality_threshold=0, read_callback: str = "nofilter", device="cuda:0",
+           rank: int = 0, world: int = 1, batch_bytes: int = 0, n_threads: Optional[int] = None, *, index=None) -> Pileup:
+    """pysam ``count_coverage`` per position and base for ``regions`` [(chrom, start, stop)] (they may overlap or touch and are
+    merged; at most 2^28 positions in all), counted while the BAM is decoded.  The counting rule, ``quality_threshold``,
+    ``read_callback``, ``index``, ``rank`` / ``world`` and the choice of the pipeline are ``window_coverage``'s: a base that
+    counts there adds 1 to its position's A, C, G or T here (GPU: k_bam_cov_plan / k_bam_pileup per batch).  With ``world`` > 1
+    the table is that of the ``rank``-th byte range; ``merge_pileups`` adds them."""
+    thr = quality_threshold_value(quality_threshold)
+    if read_callback not in _READ_CALLBACKS:
+        raise ValueError("read_callback must be 'nofilter' or 'all', got %r" % (read_callback,))
+    ref_names = bam_reference_names(path)
+    merged, segs = pileup_regions(list(regions), ref_names)
+    n_pos = sum(b - a for _, a, b in merged)
+    if n_pos > PILEUP_MAX_POSITIONS:
+        raise ValueError("the regions hold %d positions: a pileup takes at most 2^28" % n_pos)
+    if n_threads is None:
+        n_threads = default_threads()
+    res = _decode_segments(path, segs, thr, _READ_CALLBACKS[read_callback], device, rank, world, batch_bytes, n_threads, index,
+                           len(ref_names), True)
+    return Pileup(merged, res.pileup if res is not None else np.zeros((n_pos, 4), dtype=np.uint32), thr, read_callback)
+
+
+def merge_pileups(parts: Sequence[Pileup]) -> Pileup:
+    """The tables of byte ranges decoded by several ranks, added.  The parts must hold the same regions, counted alike."""
+    parts = list(parts)
+    if not parts:
+        raise ValueError("merge_pileups needs at least one part")
+    first = parts[0]
+    total = first.table.astype(np.uint64)
+    for p in parts[1:]:
+        if p.regions != first.regions or p.quality_threshold != first.quality_threshold or p.read_callback != first.read_callback:
+            raise ValueError("merge_pileups: the parts do not hold the same regions, threshold and read callback")
+        total += p.table
+    if total.size and int(total.max()) > 0xffffffff:
+        raise ValueError("merge_pileups: a count does not fit 32 bits")
+    return Pileup(first.regions, total.astype(np.uint32), first.quality_threshold, first.read_callback)
+
+
+def count_coverage(path: str, contig: str, start: int, stop: int, quality_threshold=15, read_callback: str = "all", **kw):
+    """``pysam.AlignmentFile(path).count_coverage(contig, start, stop, quality_threshold, read_callback)`` in one call: four
+    ``array.array('L')``.  Keywords as ``pileup`` (device, index, ...)."""
+    p = pileup(path, [(contig, start, stop)], quality_threshold, read_callback, **kw)
+    return p.count_coverage(contig, start, stop, quality_threshold=quality_threshold, read_callback=read_callback)
 
 
 # ----------------------------------------------------------------------------------------------

@@ -169,11 +169,11 @@ bool decode_file(const char *path, int n_threads, const Request &R, const Span *
         pool.submit([&, c]() {
             Partial &pt = c->part;
             pt.cigar.reserve(c->own / 6 + 64);
-            if (cov) pt.cov.assign(cov->size(), 0);              // the chunk's partial counts, added up in merge()
+            if (cov && !cov->per_base) pt.cov.assign(cov->size(), 0);    // the chunk's partial counts, added up in merge()
             if (want_qc) pt.qc_hist.assign(256, 0);              // the chunk's partial histogram, likewise
             for (size_t s : c->starts) {
                 const uint8_t *q = c->buf.data() + s;
-                if (!decode_record(q + 4, rd32(q), ref_id, pt, pt.error, cov, want_qc)) break;
+                if (!decode_record(q + 4, rd32(q), ref_id, pt, pt.error, cov, want_qc, D.pileup.data())) break;
             }
             std::vector<uint8_t>().swap(c->buf);            // SEQ / QUAL bytes are gone from here on
             c->parsed.set();
@@ -183,6 +183,10 @@ bool decode_file(const char *path, int n_threads, const Request &R, const Span *
 
     if (D.tid.empty()) D.names.grow(1 << 21);
     if (cov && D.cov.size() != cov->size()) D.cov.assign(cov->size(), 0);
+    if (cov && cov->per_base && !D.has_pileup) {                 // one table for the decode (a span decode comes here once per span)
+        D.pileup.assign((size_t)(4 * cov->n_pos()), 0);
+        D.has_pileup = true;
+    }
     auto merge = [&](Chunk &c) -> bool {
         Partial &pt = c.part;
         if (!pt.error.empty()) { D.error = pt.error; return false; }
@@ -499,6 +503,7 @@ extern "C" int coral_bam_decode_request(const char *path, int32_t n_threads, con
             ok = f.open(path, D->error) && read_bam_header(f, *D, ids, &hdr);
             if (ok && !spans_inside_file(R, f.size, g_bam_err)) return CORAL_ERR_ARG;
             if (ok && R.has_cov) D->cov.assign(R.cov.size(), 0);
+            if (ok && R.cov.per_base) { D->pileup.assign((size_t)(4 * R.cov.n_pos()), 0); D->has_pileup = true; }
             for (size_t k = 0; k < R.spans.size() && ok; ++k) ok = decode_file(path, n_threads, R, &R.spans[k], *D);
         }
     } catch (const std::exception &e) {          // e.g. bad_alloc on a corrupt size field: never across the C boundary
@@ -508,6 +513,7 @@ extern "C" int coral_bam_decode_request(const char *path, int32_t n_threads, con
         g_bam_err = D->error;
         return CORAL_ERR_FORMAT;
     }
+    if (D->has_pileup) pileup_segment_sums(R.cov, D->pileup.data(), D->cov);
     *handle = D.release();
     return CORAL_OK;
 }
@@ -576,6 +582,14 @@ extern "C" int coral_bam_coverage_result(void *handle, int32_t n_seg, int64_t *c
     Decoded *D = (Decoded *)handle;
     if ((size_t)n_seg != D->cov.size()) { g_bam_err = "coral_bam_coverage_result: the handle holds no request of this size"; return CORAL_ERR_ARG; }
     if (n_seg) memcpy(counts, D->cov.data(), (size_t)n_seg * 8);
+    return CORAL_OK;
+}
+
+extern "C" int coral_bam_pileup_result(void *handle, int64_t n_pos, uint32_t *counts) {
+    if (!handle || n_pos < 0 || (n_pos > 0 && !counts)) return CORAL_ERR_ARG;
+    Decoded *D = (Decoded *)handle;
+    if (!D->has_pileup || (uint64_t)n_pos * 4 != D->pileup.size()) { g_bam_err = "coral_bam_pileup_result: the handle holds no pileup request of this size"; return CORAL_ERR_ARG; }
+    if (n_pos) memcpy(counts, D->pileup.data(), (size_t)n_pos * 16);
     return CORAL_OK;
 }
 

@@ -176,6 +176,8 @@ struct Decoded {
     int64_t compressed_bytes = 0, uncompressed_bytes = 0, n_blocks = 0;
     double seconds = 0.0;
     std::vector<int64_t> cov;               // window-coverage counts per segment (coral_bam_coverage_result)
+    bool has_pileup = false;                // a pileup request (per_base of a coral_bam_request_t; it may hold no position)
+    std::vector<uint32_t> pileup;           // its table [positions in segment order][A, C, G, T] (coral_bam_pileup_result)
 };
 
 struct Partial {   // what stage 3 produces for one chunk
@@ -206,11 +208,24 @@ typedef std::unordered_map<std::string, int> RefIds;
 // filter_all: none of the flags 0x4 | 0x100 | 0x200 | 0x400), has SEQ, the base is an aligned (M / = / X) base inside the
 // segment, its SEQ code is A, C, G or T, and either threshold is 0 or the record has QUAL (first byte not 0xff) and
 // QUAL >= threshold there.
+// A pileup request (per_base of the request) is the same rule split by position and base: a counted base adds 1 to
+// table[(seg_off[segment] + position - lo[segment]) * 4 + b], b = 0..3 for the SEQ codes 1, 2, 4, 8 (A, C, G, T); the
+// per-segment counts of such a request are the sums of the table (pileup_segment_sums), not counted on their own.
+const int64_t PILEUP_MAX_POSITIONS = 1ll << 28;     // 4 x 2^28 counters: int32-indexable, a table of at most 4 GiB
+
+CORAL_QC_HD inline bool pileup_base(uint32_t code, uint32_t *b) {      // SEQ code -> column of the table; false: not A, C, G or T
+    *b = (code >> 1) - (code >> 3);                           // 1, 2, 4, 8 -> 0, 1, 2, 3
+    return code != 0 && (code & (code - 1)) == 0;
+}
+
 struct CovTable {
     std::vector<int32_t> tid, lo, hi;
     int32_t threshold = 0;
     bool filter_all = false;
+    bool per_base = false;
+    std::vector<int64_t> seg_off;           // per_base: positions in front of every segment, n + 1 entries
     size_t size() const { return tid.size(); }
+    int64_t n_pos() const { return seg_off.empty() ? 0 : seg_off.back(); }
     // first segment at or after (t, pos) in (tid, hi) order: tid > t, or tid == t and hi > pos
     size_t first(int32_t t, int64_t pos, size_t from = 0) const {
         size_t a = from, b = tid.size();
@@ -276,7 +291,26 @@ inline bool parse_request(const coral_bam_request_t *q, Request &R, std::string 
         R.world = q->world;
     }
     R.has_cov = q->n_seg >= 0;
-    return !R.has_cov || make_cov_table(q->n_seg, q->seg_tid, q->seg_start, q->seg_end, q->quality_threshold, q->read_callback, R.cov, err);
+    if (q->per_base != 0 && !R.has_cov) { err = "pileup request: per_base needs segments (n_seg >= 0)"; return false; }
+    if (R.has_cov && !make_cov_table(q->n_seg, q->seg_tid, q->seg_start, q->seg_end, q->quality_threshold, q->read_callback, R.cov, err)) return false;
+    if (q->per_base != 0) {
+        CovTable &T = R.cov;
+        T.per_base = true;
+        T.seg_off.assign(1, 0);
+        for (size_t k = 0; k < T.size(); ++k) T.seg_off.push_back(T.seg_off.back() + ((int64_t)T.hi[k] - T.lo[k]));
+        if (T.n_pos() > PILEUP_MAX_POSITIONS) { err = "pileup request: the segments hold more than 2^28 positions"; return false; }
+    }
+    return true;
+}
+
+// The per-segment counts of a pileup request: the sums of the table over every segment's positions and the four bases.
+inline void pileup_segment_sums(const CovTable &T, const uint32_t *table, std::vector<int64_t> &counts) {
+    counts.assign(T.size(), 0);
+    for (size_t t = 0; t < T.size(); ++t) {
+        int64_t c = 0;
+        for (int64_t k = 4 * T.seg_off[t]; k < 4 * T.seg_off[t + 1]; ++k) c += table[k];
+        counts[t] = c;
+    }
 }
 
 // The rule that needs the file: every span begins at a block inside the file and ends at one or at the file's end.
@@ -296,9 +330,10 @@ inline coral_bam_request_t range_request(int32_t rank, int32_t world) {
     return q;
 }
 
-// Add one record's counted bases to counts[segment] (host pipeline; ops = the real CIGAR, CG tag already resolved).
+// Add one record's counted bases to counts[segment] or, for a pileup request (T.per_base), to `table` - shared by the
+// threads that parse chunks, hence the atomic add (host pipeline; ops = the real CIGAR, CG tag already resolved).
 inline void count_record_coverage(const CovTable &T, int32_t refID, int64_t pos, uint32_t flag, uint32_t l_seq, const uint32_t *ops,
-                                  uint32_t n_ops, const uint8_t *seq, const uint8_t *qual, int64_t *counts) {
+                                  uint32_t n_ops, const uint8_t *seq, const uint8_t *qual, int64_t *counts, uint32_t *table = nullptr) {
     if (refID < 0 || l_seq == 0 || n_ops == 0 || T.size() == 0) return;
     if (T.filter_all && (flag & 0x704u)) return;
     const uint32_t thr = (uint32_t)T.threshold;
@@ -318,9 +353,12 @@ inline void count_record_coverage(const CovTable &T, int32_t refID, int64_t pos,
                     const uint64_t qi = (uint64_t)(q + (x - r));
                     if (qi >= l_seq) break;
                     const uint8_t code = (qi & 1) ? (seq[qi >> 1] & 15) : (seq[qi >> 1] >> 4);
-                    c += (code == 1 || code == 2 || code == 4 || code == 8) && qual[qi] >= thr;
+                    uint32_t b;
+                    const bool counted = pileup_base(code, &b) && qual[qi] >= thr;
+                    c += counted;
+                    if (counted && T.per_base) __atomic_fetch_add(table + 4 * (T.seg_off[t] + (x - T.lo[t])) + b, 1u, __ATOMIC_RELAXED);
                 }
-                counts[t] += c;
+                if (!T.per_base) counts[t] += c;
             }
         }
         if (QRY_ADV[op]) q += len;
@@ -422,10 +460,10 @@ inline bool all_acgt(const uint8_t *seq, uint32_t l_seq) {
 }
 
 // Decode one BAM record (p points at refID, i.e. after block_size) into the partial.
-// With `cov`, the record's bases also go into o.cov (sized by the caller).
+// With `cov`, the record's bases also go into o.cov (sized by the caller) or, for a pileup request, into `pileup` (the decode's table).
 // With `qc`, the record's qual_sum goes to o.qc_sum and its QUAL bytes into o.qc_hist (256 bins, sized by the caller).
 inline bool decode_record(const uint8_t *p, uint32_t block_size, const RefIds &ref_id, Partial &o, std::string &err,
-                          const CovTable *cov = nullptr, bool qc = false) {
+                          const CovTable *cov = nullptr, bool qc = false, uint32_t *pileup = nullptr) {
     if (block_size < 32) { err = "record shorter than its fixed fields"; return false; }
     const int32_t refID = (int32_t)rd32(p), pos = (int32_t)rd32(p + 4);
     const uint32_t l_read_name = p[8], mapq = p[9];
@@ -507,7 +545,7 @@ inline bool decode_record(const uint8_t *p, uint32_t block_size, const RefIds &r
         qinf += QRY_ADV[v & 15] ? (v >> 4) : 0;
     }
     o.cigar_len.push_back((int64_t)padded);
-    if (cov) count_record_coverage(*cov, refID, pos, flag, l_seq, dst, n_cigar_op, seq, qual, o.cov.data());
+    if (cov) count_record_coverage(*cov, refID, pos, flag, l_seq, dst, n_cigar_op, seq, qual, o.cov.data(), pileup);
     if ((flag & 4) || n_cigar_op == 0) rlen = 0;                 // htslib bam_endpos
     o.tid.push_back(refID);
     o.pos.push_back(pos);

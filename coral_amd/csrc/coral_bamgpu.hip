@@ -18,6 +18,7 @@
 //                   codes, read name and SA text -> compact blobs for the host
 //   worker thread   per batch, a few hundred bytes per record: read names -> ids, SA text -> numeric rows; the rare
 //                   records with non-ACGT bases are gathered whole (k_bam_gather) and handled by the CPU pipeline's own routine.
+//   k_bam_pileup   only with a pileup request (per_base): k_bam_cov_count's work items, one 32-bit atomic per counted base
 //   k_bam_cov_plan / k_bam_cov_count   only with a window-coverage request (coral_bam_request_t): pysam count_coverage with a
 //                   base-quality threshold over the request's segments, read from the batch's SEQ / QUAL before the slot is reused.
 //   k_bam_index / k_bam_index_compact   only with an index request (want_index): per record the virtual offset, the UCSC bin
@@ -1104,6 +1105,74 @@ __global__ __launch_bounds__(256) void k_bam_cov_count(const uint8_t *__restrict
     }
 }
 
+// K_pileup: the coverage request split by position and base (per_base of the request; the rule: CovTable in coral_bam_common.h).
+// The work items and the CIGAR walk are k_bam_cov_count's (k_bam_cov_plan sizes them); what differs is the inner loop: every
+// counted base is one no-return 32-bit atomic at table[(seg_off[t] + x - lo[t]) * 4 + b].  There is nothing to reduce: the 64
+// lanes of a stride are 64 different positions, so a wave never collides with itself - only different records at the same
+// position do.  One wave per workgroup (grid-stride), no LDS: it fits beside resident inflate waves.
+__global__ __launch_bounds__(WAVE) void k_bam_pileup(const uint8_t *__restrict__ buf, long long n_rec, MetaArrays M, CovSegs S,
+                                                     const long long *__restrict__ seg_off, int threshold,
+                                                     const long long *__restrict__ item_off, uint32_t *__restrict__ table) {
+    const int lane = threadIdx.x;
+    const long long total = item_off[n_rec];
+    const uint32_t thr = (uint32_t)threshold;
+    for (long long w = blockIdx.x; w < total; w += gridDim.x) {
+        long long a = 0, b = n_rec;                                   // the record: the last i with item_off[i] <= w
+        while (b - a > 1) {
+            const long long m = (a + b) >> 1;
+            if (item_off[m] <= w) a = m; else b = m;
+        }
+        const long long i = a;
+        const int32_t tid = M.tid[i], l_seq = M.l_seq[i], pos = M.pos[i];
+        const int n_ops = M.n_cigar[i];
+        const long long q_lo = (w - item_off[i]) * COV_SLICE, q_hi = min((long long)l_seq, q_lo + COV_SLICE);
+        const uint8_t *ops = buf + M.cig_src[i];
+        const uint8_t *seq = buf + M.seq_src[i];
+        const uint8_t *qual = seq + ((long long)l_seq + 1) / 2;
+        int s = cov_first(S, tid, pos, 0);
+        long long q_base = 0, r_base = pos;
+        for (int c = 0; c < n_ops && q_base < q_hi; c += WAVE) {
+            if (s >= S.n || S.tid[s] != tid) break;                   // no segment left on this contig
+            const int kk = c + lane;
+            const uint32_t wd = kk < n_ops ? ld32(ops + 4ll * kk) : 15u;
+            const uint32_t op = wd & 15u;
+            const long long len = (long long)(wd >> 4);
+            const long long qa = ((0x193u >> op) & 1u) ? len : 0;     // M I S = X advance the query
+            const long long ra = ((0x18Du >> op) & 1u) ? len : 0;     // M D N = X advance the reference
+            long long qs = qa, rs = ra;
+            for (int d = 1; d < WAVE; d <<= 1) {
+                const long long tq = __shfl_up(qs, d), tr = __shfl_up(rs, d);
+                if (lane >= d) { qs += tq; rs += tr; }
+            }
+            const long long q_op = q_base + qs - qa, r_op = r_base + rs - ra;
+            const bool cand = ((0x181u >> op) & 1u) && len > 0 && q_op < q_hi && q_op + len > q_lo;     // M = X meeting the item
+            unsigned long long m = __ballot(cand);
+            while (m) {
+                const int j = __builtin_ctzll(m);
+                m &= m - 1;
+                const long long oq = __shfl(q_op, j), orf = __shfl(r_op, j), ol = __shfl(len, j);
+                const long long aq = max(oq, q_lo), bq = min(oq + ol, q_hi);
+                const long long r0 = orf + (aq - oq), r1 = orf + (bq - oq);
+                if (s < S.n && S.tid[s] == tid && (long long)S.hi[s] <= r0)
+                    s = (s + 1 < S.n && S.tid[s + 1] == tid && (long long)S.hi[s + 1] > r0) ? s + 1 : cov_first(S, tid, r0, s + 1);
+                for (int t = s; t < S.n && S.tid[t] == tid && (long long)S.lo[t] < r1; ++t) {
+                    const long long lo = S.lo[t], xa = max(r0, lo), xb = min(r1, (long long)S.hi[t]);
+                    const long long row0 = 4 * (seg_off[t] - lo);                  // lo <= x < hi: 4 * x + row0 lies in the segment's rows
+                    for (long long x = xa + lane; x < xb; x += WAVE) {
+                        const long long qi = aq + (x - r0);                    // < bq <= q_hi <= l_seq
+                        const uint8_t byte = seq[qi >> 1];
+                        const uint32_t code = (qi & 1) ? (byte & 15u) : (uint32_t)(byte >> 4);
+                        uint32_t col;
+                        if (pileup_base(code, &col) && qual[qi] >= thr) atomicAdd(table + (row0 + 4 * x + col), 1u);
+                    }
+                }
+            }
+            q_base += __shfl(qs, WAVE - 1);
+            r_base += __shfl(rs, WAVE - 1);
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // K_qc: per-read base-quality sums and the base-quality histogram (want_qc; the rules: QcPartial in coral_bam_common.h)
 // ---------------------------------------------------------------------------------------------
@@ -1435,6 +1504,9 @@ struct GpuDecoder {
     // window-coverage request: segments and counters in the workspace (n = 0 without one)
     CovSegs cov{nullptr, nullptr, nullptr, 0};
     unsigned long long *cov_counts = nullptr;
+    // pileup request (per_base): the segments' prefix offsets and the table [positions][4], in the workspace as well
+    long long *pile_off = nullptr;
+    uint32_t *pile = nullptr;
     // span decode: the spans are decoded one after the other through the same batches
     std::vector<SpanDef> spans;
     int cur_span = 0;                         // the span the caller's thread is parsing
@@ -1811,6 +1883,10 @@ bool carve(GpuDecoder *G, void *ws, size_t bytes) {
         int32_t *seg = (int32_t *)take(3 * n_seg * 4);
         G->cov = CovSegs{seg, seg + n_seg, seg + 2 * n_seg, (int)n_seg};
         G->cov_counts = (unsigned long long *)take(n_seg * 8);
+        if (G->req.cov.per_base) {
+            G->pile_off = (long long *)take((n_seg + 1) * 8);
+            G->pile = (uint32_t *)take((size_t)G->req.cov.n_pos() * 16);
+        }
     }
     if (ws && used > bytes) return false;
     G->ws_bytes = used;
@@ -1978,9 +2054,15 @@ extern "C" int coral_bamgpu_finish(void *handle, void *stream_) {
     if (!R.has_cov && !R.want_index && !R.want_qc) return CORAL_OK;
     auto get = [](void *dst, const void *src, size_t bytes) { return bytes == 0 || hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) == hipSuccess; };
     bool ok = hipStreamSynchronize((hipStream_t)stream_) == hipSuccess;
-    if (ok && R.has_cov) {
+    if (ok && R.has_cov && !R.cov.per_base) {
         G->D.cov.assign(R.cov.size(), 0);
         ok = get(G->D.cov.data(), G->cov_counts, R.cov.size() * 8);
+    }
+    if (ok && R.cov.per_base) {                // the table, and the counts per segment as its sums
+        G->D.pileup.assign((size_t)R.cov.n_pos() * 4, 0);
+        G->D.has_pileup = true;
+        ok = get(G->D.pileup.data(), G->pile, (size_t)R.cov.n_pos() * 16);
+        if (ok) pileup_segment_sums(R.cov, G->D.pileup.data(), G->D.cov);
     }
     IndexPartial &P = G->D.idx;
     unsigned long long state[2] = {0, 0}, no_coor = 0;
@@ -2052,6 +2134,9 @@ extern "C" int coral_bamgpu_start(void *handle, void *workspace, int64_t workspa
             (e = hipMemcpy((void *)G->cov.hi, T.hi.data(), b, hipMemcpyHostToDevice)) != hipSuccess ||
             (e = hipMemset(G->cov_counts, 0, 2 * b)) != hipSuccess)
             return bad("coverage request set-up", e);
+        if (T.per_base && ((e = hipMemcpy(G->pile_off, T.seg_off.data(), (T.size() + 1) * 8, hipMemcpyHostToDevice)) != hipSuccess ||
+                           (T.n_pos() > 0 && (e = hipMemset(G->pile, 0, (size_t)T.n_pos() * 16)) != hipSuccess)))
+            return bad("pileup request set-up", e);
     }
     G->feeder = std::thread(feeder_main, G);
     G->worker = std::thread(worker_main, G);
@@ -2352,7 +2437,11 @@ extern "C" int coral_bamgpu_emit(void *handle, uint32_t *cigar_dst, int64_t *cig
         // at most one item per record plus one per COV_SLICE bases of SEQ in the batch; 4 waves per workgroup, grid-stride beyond
         const long long items = n + ((long long)CARRY_CAP + (long long)G->cur.infl_bytes) / COV_SLICE + 1;
         const unsigned blocks = (unsigned)std::min<long long>((items + 3) / 4, 8192);
-        hipLaunchKernelGGL(k_bam_cov_count, dim3(blocks), dim3(256), 0, stream, buf, n, G->M, G->cov, G->req.cov.threshold, item_off, G->cov_counts);
+        if (G->req.cov.per_base)               // one wave per workgroup, grid-stride beyond 32 per CU
+            hipLaunchKernelGGL(k_bam_pileup, dim3((unsigned)std::min<long long>(items, 8192)), dim3(WAVE), 0, stream, buf, n, G->M, G->cov, G->pile_off,
+                               G->req.cov.threshold, item_off, G->pile);
+        else
+            hipLaunchKernelGGL(k_bam_cov_count, dim3(blocks), dim3(256), 0, stream, buf, n, G->M, G->cov, G->req.cov.threshold, item_off, G->cov_counts);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return fail(CORAL_ERR_HIP, std::string("window coverage launch failed: ") + hipGetErrorString(e));
     }

@@ -387,7 +387,8 @@ const char *coral_bam_last_error(void);
  * during the open call and not kept.  Every rule is checked by both pipelines alike (CORAL_ERR_ARG, coral_bam_last_error says
  * why): world >= 1 and 0 <= rank < world; spans sorted, disjoint, non-empty and inside the file; segments sorted by (tid,
  * start), disjoint, 0 <= start <= end; quality_threshold 0..255; read_callback 0 or 1; no want_index / want_qc on a span
- * decode.  A span decode is not sharded: rank and world are taken as 0 and 1. */
+ * decode; per_base only with segments (n_seg >= 0) of at most 2^28 positions in all.  A span decode is not sharded: rank and
+ * world are taken as 0 and 1. */
 typedef struct {
     int32_t rank, world;                       /* byte range (ignored when n_spans >= 0) */
     int32_t n_spans;                           /* -1: the byte range; >= 0: only records starting inside these spans */
@@ -396,9 +397,11 @@ typedef struct {
     const int32_t *seg_tid, *seg_start, *seg_end;
     int32_t quality_threshold, read_callback;
     int32_t want_index, want_qc;
+    int32_t per_base;                          /* 0: counts per segment; else: the table per position and base (pileup) */
 } coral_bam_request_t;
 /* coral_bam_decode_range with a request; the results that ride along are read from the handle (of this call, or of
- * coral_bamgpu_host) with coral_bam_coverage_result, coral_bam_index_sizes / _fill and coral_bam_qc_sizes / _fill.
+ * coral_bamgpu_host) with coral_bam_coverage_result, coral_bam_pileup_result, coral_bam_index_sizes / _fill and
+ * coral_bam_qc_sizes / _fill.
  *
  * Spans (n_spans >= 0) - replaces htslib's hts_itr_query + bgzf_seek behind every lr_bamfh.count_coverage(chrom, w, w + window,
  * ...) of /root/reference/src/plot_amplicons.py:399-409: the records that START inside n_spans spans [span_beg, span_end) of
@@ -415,6 +418,15 @@ typedef struct {
  * an aligned base of an M / = / X op (the real CIGAR: CG:B,I for the placeholder) inside the segment, its SEQ code is A, C,
  * G or T, and quality_threshold (0..255) is 0 or the record has QUAL (first byte not 0xff) with QUAL >= quality_threshold
  * there.  `coverage_result` copies the n_seg int64 counts of the handle.
+ *
+ * Pileup (per_base != 0, with segments) - replaces lr_bamfh.count_coverage(chrom, start, stop, ...) itself, the four per-position
+ * arrays the reference sums at once (/root/reference/src/infer_breakpoint_graph.py:130-133,
+ * /root/reference/src/plot_amplicons.py:399-409): the same rule split by position and base.  A counted base adds 1 to
+ * counts[p][b], p = the position's place among the positions of all segments in segment order, b = 0..3 for the SEQ codes 1,
+ * 2, 4, 8 (A, C, G, T).  The segments may hold at most 2^28 positions in all (4 x 2^28 counters stay int32-indexable, the
+ * table is at most 4 GiB).  `pileup_result` copies the uint32 [n_pos][4] table; n_pos must be the sum of the segment lengths.
+ * `coverage_result` stays valid and returns the sums of the table per segment: one result, not two rules.  Allowed on a span
+ * decode, as coverage is; tables of byte ranges add up.
  *
  * BAI index (want_index; SAMv1 5.2) - replaces what the reference gets from htslib behind pysam: the "Sorted indexed" BAM it
  * opens was indexed by `samtools index` (hts_idx_push / hts_idx_finish).  Besides the records, what the byte range contributes
@@ -442,6 +454,7 @@ typedef struct {
  *          qual_sum / length on the host.  Results of consecutive byte ranges concatenate / add up. */
 int coral_bam_decode_request(const char *path, int32_t n_threads, const coral_bam_request_t *req, void **handle);
 int coral_bam_coverage_result(void *handle, int32_t n_seg, int64_t *counts);
+int coral_bam_pileup_result(void *handle, int64_t n_pos, uint32_t *counts);
 int coral_bam_index_sizes(void *handle, int64_t sizes[4]);
 int coral_bam_index_fill(void *handle, int64_t *head_key, uint64_t *head_voff, uint64_t *lin, int64_t *n_mapped,
                          int64_t *n_unmapped, uint64_t scalars[4]);
@@ -477,6 +490,10 @@ int coral_bam_qc_fill(void *handle, int32_t *length, int64_t *qual_sum, int32_t 
  *            a coverage request  k_bam_cov_plan + k_bam_cov_count read the batch's inflated SEQ / QUAL before the slot is reused
  *                      (one wave per 16 384 query bases of a record, one 64-bit atomic per work item and segment); segments
  *                      and counters live in the workspace
+ *            per_base  k_bam_cov_plan + k_bam_pileup instead (the same work items in one-wave workgroups; one no-return
+ *                      32-bit atomic per counted base, no reduction: the 64 lanes of a stride are 64 different positions);
+ *                      the segments' prefix offsets (int64 [n_seg + 1]) and the uint32 [n_pos][4] table live in the workspace
+ *                      too, zeroed by `start`
  *            want_index  k_bam_index (one thread per record: virtual offset by binary search of the batch's block table - a
  *                      record carried in from the batch in front keeps the offset it STARTED at -, bin, run heads, 64-bit
  *                      atomicMin per overlapped window, per-contig counters, order check), one scan and k_bam_index_compact;
@@ -485,7 +502,8 @@ int coral_bam_qc_fill(void *handle, int32_t *length, int64_t *qual_sum, int32_t 
  *                      16 384 QUAL bytes of a read, aligned 16-byte loads, one 64-bit atomic per work item, the histogram in
  *                      LDS per workgroup)
  *   finish        after the last batch (CORAL_ERR_ARG before): waits for `stream` once and leaves what was requested in the
- *          handle of `host` (coral_bam_coverage_result, coral_bam_index_sizes / _fill, coral_bam_qc_sizes / _fill); fails when
+ *          handle of `host` (coral_bam_coverage_result, coral_bam_pileup_result - the table is copied and summed per segment
+ *          here -, coral_bam_index_sizes / _fill, coral_bam_qc_sizes / _fill); fails when
  *          an index was requested and the records are not in coordinate order; with nothing requested it does nothing
  * coral_bgzf_inflate: one inflate launch over caller-provided device buffers — desc = n_blocks x {src_off, src_len,
  * dst_off, isize} uint32 (raw DEFLATE streams in `comp`, which must be readable 4096 bytes beyond the last stream);
