@@ -18,13 +18,14 @@
 //                   codes, read name and SA text -> compact blobs for the host
 //   worker thread   per batch, a few hundred bytes per record: read names -> ids, SA text -> numeric rows; the rare
 //                   records with non-ACGT bases are gathered whole (k_bam_gather) and handled by the CPU pipeline's own routine.
-//   k_bam_pileup   only with a pileup request (per_base): k_bam_cov_count's work items, one 32-bit atomic per counted base
-//   k_bam_cov_plan / k_bam_cov_count   only with a window-coverage request (coral_bam_request_t): pysam count_coverage with a
-//                   base-quality threshold over the request's segments, read from the batch's SEQ / QUAL before the slot is reused.
-//   k_bam_index / k_bam_index_compact   only with an index request (want_index): per record the virtual offset, the UCSC bin
-//                   and the linear-index windows of a BAI index, per batch the heads of the runs of equal (tid, bin).
-//   k_bam_qc_plan / k_bam_qc   only with a read-QC request (want_qc): per read the sum of its QUAL bytes, and the 256-bin
-//                   histogram of all of them, read from the batch's QUAL before the slot is reused.
+// Requests that ride along a decode (coral_bam_request_t), each queued per batch before the slot is reused:
+//   k_bam_cov_plan + k_bam_cov_count   window coverage: pysam count_coverage with a base-quality threshold over the segments
+//   k_bam_cov_plan + k_bam_pileup      the same split by position and base (per_base): one 32-bit atomic per counted base
+//                   (both kernels are cov_walk, the one CIGAR walk that applies the coverage rule, with a sink each)
+//   k_bam_qc_plan + k_bam_qc           read QC: per read the sum of its QUAL bytes, and the 256-bin histogram of all of them
+//   k_bam_index + k_bam_index_compact  index: per record the virtual offset, the UCSC bin and the linear-index windows of a
+//                   BAI index, per batch the heads of the runs of equal (tid, bin)
+// Host: one struct per request (carve / start / batch / finish); what it may borrow of the parse's scratch: struct Borrowed.
 // Batches (64 MiB first, doubling up to 2.52 GiB inflated, coral_bamgpu_open) are double-buffered: while batch k is parsed, batch k + 1 is inflated
 // and k + 2 is read.
 // A record that straddles two batches is carried in front of the next batch's buffer.
@@ -1028,31 +1029,86 @@ __global__ __launch_bounds__(256) void k_bam_cov_plan(const uint8_t *__restrict_
     n_items[i] = cnt;
 }
 
-// one wave per work item (grid-stride): the query bases [k * COV_SLICE, (k + 1) * COV_SLICE) of record i.  The wave walks the
-// CIGAR 64 ops at a time (prefix sums of the query / reference advance), and for every aligned op that meets its query range
-// the lanes stride over the op's bases inside each segment, testing the SEQ code and QUAL.  Per-lane counts are reduced in
-// the wave and added with ONE 64-bit atomic per (work item, segment): segments are met in increasing order.
+// the record of work item w: the last i with item_off[i] <= w (item_off: the exclusive sums of n_rec + 1 item counts)
+__device__ __forceinline__ long long item_record(const long long *__restrict__ item_off, long long n_rec, long long w) {
+    long long a = 0, b = n_rec;
+    while (b - a > 1) {
+        const long long m = (a + b) >> 1;
+        if (item_off[m] <= w) a = m; else b = m;
+    }
+    return a;
+}
+
+// The CIGAR walk of one work item, the query bases [q_lo, q_hi) of record i, for both coverage kernels: the coverage rule
+// (CovTable in coral_bam_common.h) is applied here and nowhere else on the device.  The wave walks the CIGAR 64 ops at a time
+// (prefix sums of the query / reference advance), and for every aligned op that meets the query range the lanes stride over the
+// op's bases inside each segment, testing the SEQ code and QUAL.  What becomes of a counted base is the sink's business:
+//   segment(t, lo)   wave-uniform, in front of the bases of an op inside segment t (lo = S.lo[t]); segments are met in
+//                    increasing order, the same one again for every further op inside it
+//   base(x, col)     per lane: the base at reference position x counts, col = 0..3 for A, C, G, T
+template <class Segment, class Base>
+__device__ __forceinline__ void cov_walk(const uint8_t *__restrict__ buf, const MetaArrays &M, const CovSegs &S, uint32_t thr, long long i,
+                                         long long q_lo, long long q_hi, int lane, Segment segment, Base base) {
+    const int32_t tid = M.tid[i], l_seq = M.l_seq[i], pos = M.pos[i];
+    const int n_ops = M.n_cigar[i];
+    const uint8_t *ops = buf + M.cig_src[i];
+    const uint8_t *seq = buf + M.seq_src[i];
+    const uint8_t *qual = seq + ((long long)l_seq + 1) / 2;
+    int s = cov_first(S, tid, pos, 0);
+    long long q_base = 0, r_base = pos;
+    for (int c = 0; c < n_ops && q_base < q_hi; c += WAVE) {
+        if (s >= S.n || S.tid[s] != tid) break;                   // no segment left on this contig
+        const int kk = c + lane;
+        const uint32_t wd = kk < n_ops ? ld32(ops + 4ll * kk) : 15u;
+        const uint32_t op = wd & 15u;
+        const long long len = (long long)(wd >> 4);
+        const long long qa = ((0x193u >> op) & 1u) ? len : 0;     // M I S = X advance the query
+        const long long ra = ((0x18Du >> op) & 1u) ? len : 0;     // M D N = X advance the reference
+        long long qs = qa, rs = ra;
+        for (int d = 1; d < WAVE; d <<= 1) {
+            const long long tq = __shfl_up(qs, d), tr = __shfl_up(rs, d);
+            if (lane >= d) { qs += tq; rs += tr; }
+        }
+        const long long q_op = q_base + qs - qa, r_op = r_base + rs - ra;
+        const bool cand = ((0x181u >> op) & 1u) && len > 0 && q_op < q_hi && q_op + len > q_lo;     // M = X meeting the item
+        unsigned long long m = __ballot(cand);
+        while (m) {
+            const int j = __builtin_ctzll(m);
+            m &= m - 1;
+            const long long oq = __shfl(q_op, j), orf = __shfl(r_op, j), ol = __shfl(len, j);
+            const long long aq = max(oq, q_lo), bq = min(oq + ol, q_hi);
+            const long long r0 = orf + (aq - oq), r1 = orf + (bq - oq);
+            // r0 only grows: the cursor is usually still right (this op ends inside its segment) or one further
+            if (s < S.n && S.tid[s] == tid && (long long)S.hi[s] <= r0)
+                s = (s + 1 < S.n && S.tid[s + 1] == tid && (long long)S.hi[s + 1] > r0) ? s + 1 : cov_first(S, tid, r0, s + 1);
+            for (int t = s; t < S.n && S.tid[t] == tid && (long long)S.lo[t] < r1; ++t) {
+                const long long lo = S.lo[t], xa = max(r0, lo), xb = min(r1, (long long)S.hi[t]);
+                segment(t, lo);
+                for (long long x = xa + lane; x < xb; x += WAVE) {
+                    const long long qi = aq + (x - r0);                    // < bq <= q_hi <= l_seq
+                    const uint8_t byte = seq[qi >> 1];
+                    const uint32_t code = (qi & 1) ? (byte & 15u) : (uint32_t)(byte >> 4);
+                    uint32_t col;
+                    if (pileup_base(code, &col) && qual[qi] >= thr) base(x, col);
+                }
+            }
+        }
+        q_base += __shfl(qs, WAVE - 1);
+        r_base += __shfl(rs, WAVE - 1);
+    }
+}
+
+// one wave per work item (grid-stride): the query bases [k * COV_SLICE, (k + 1) * COV_SLICE) of record i.  The counting sink:
+// per-lane counts, reduced in the wave and added with ONE 64-bit atomic per (work item, segment).
 __global__ __launch_bounds__(256) void k_bam_cov_count(const uint8_t *__restrict__ buf, long long n_rec, MetaArrays M, CovSegs S,
                                                         int threshold, const long long *__restrict__ item_off,
                                                         unsigned long long *__restrict__ counts) {
     const int lane = threadIdx.x & 63;
     const long long n_waves = ((long long)gridDim.x * blockDim.x) >> 6;
     const long long total = item_off[n_rec];
-    const uint32_t thr = (uint32_t)threshold;
     for (long long w = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6; w < total; w += n_waves) {
-        long long a = 0, b = n_rec;                                   // the record: the last i with item_off[i] <= w
-        while (b - a > 1) {
-            const long long m = (a + b) >> 1;
-            if (item_off[m] <= w) a = m; else b = m;
-        }
-        const long long i = a;
-        const int32_t tid = M.tid[i], l_seq = M.l_seq[i], pos = M.pos[i];
-        const int n_ops = M.n_cigar[i];
-        const long long q_lo = (w - item_off[i]) * COV_SLICE, q_hi = min((long long)l_seq, q_lo + COV_SLICE);
-        const uint8_t *ops = buf + M.cig_src[i];
-        const uint8_t *seq = buf + M.seq_src[i];
-        const uint8_t *qual = seq + ((long long)l_seq + 1) / 2;
-        int s = cov_first(S, tid, pos, 0);
+        const long long i = item_record(item_off, n_rec, w);
+        const long long q_lo = (w - item_off[i]) * COV_SLICE, q_hi = min((long long)M.l_seq[i], q_lo + COV_SLICE);
         int cur = -1;                                                  // the segment the lanes' counts belong to
         uint32_t acc = 0;
         auto flush = [&]() {
@@ -1061,115 +1117,27 @@ __global__ __launch_bounds__(256) void k_bam_cov_count(const uint8_t *__restrict
             if (cur >= 0 && lane == 0 && sum) atomicAdd(counts + cur, (unsigned long long)sum);
             acc = 0;
         };
-        long long q_base = 0, r_base = pos;
-        for (int c = 0; c < n_ops && q_base < q_hi; c += WAVE) {
-            if (s >= S.n || S.tid[s] != tid) break;                   // no segment left on this contig
-            const int kk = c + lane;
-            const uint32_t wd = kk < n_ops ? ld32(ops + 4ll * kk) : 15u;
-            const uint32_t op = wd & 15u;
-            const long long len = (long long)(wd >> 4);
-            const long long qa = ((0x193u >> op) & 1u) ? len : 0;     // M I S = X advance the query
-            const long long ra = ((0x18Du >> op) & 1u) ? len : 0;     // M D N = X advance the reference
-            long long qs = qa, rs = ra;
-            for (int d = 1; d < WAVE; d <<= 1) {
-                const long long tq = __shfl_up(qs, d), tr = __shfl_up(rs, d);
-                if (lane >= d) { qs += tq; rs += tr; }
-            }
-            const long long q_op = q_base + qs - qa, r_op = r_base + rs - ra;
-            const bool cand = ((0x181u >> op) & 1u) && len > 0 && q_op < q_hi && q_op + len > q_lo;     // M = X meeting the item
-            unsigned long long m = __ballot(cand);
-            while (m) {
-                const int j = __builtin_ctzll(m);
-                m &= m - 1;
-                const long long oq = __shfl(q_op, j), orf = __shfl(r_op, j), ol = __shfl(len, j);
-                const long long aq = max(oq, q_lo), bq = min(oq + ol, q_hi);
-                const long long r0 = orf + (aq - oq), r1 = orf + (bq - oq);
-                // r0 only grows: the cursor is usually still right (this op ends inside its segment) or one further
-                if (s < S.n && S.tid[s] == tid && (long long)S.hi[s] <= r0)
-                    s = (s + 1 < S.n && S.tid[s + 1] == tid && (long long)S.hi[s + 1] > r0) ? s + 1 : cov_first(S, tid, r0, s + 1);
-                for (int t = s; t < S.n && S.tid[t] == tid && (long long)S.lo[t] < r1; ++t) {
-                    if (t != cur) { flush(); cur = t; }
-                    const long long xa = max(r0, (long long)S.lo[t]), xb = min(r1, (long long)S.hi[t]);
-                    for (long long x = xa + lane; x < xb; x += WAVE) {
-                        const long long qi = aq + (x - r0);                    // < bq <= q_hi <= l_seq
-                        const uint8_t byte = seq[qi >> 1];
-                        const uint32_t code = (qi & 1) ? (byte & 15u) : (uint32_t)(byte >> 4);
-                        acc += (code != 0 && (code & (code - 1)) == 0 && qual[qi] >= thr) ? 1u : 0u;
-                    }
-                }
-            }
-            q_base += __shfl(qs, WAVE - 1);
-            r_base += __shfl(rs, WAVE - 1);
-        }
+        cov_walk(buf, M, S, (uint32_t)threshold, i, q_lo, q_hi, lane, [&](int t, long long) { if (t != cur) { flush(); cur = t; } },
+                 [&](long long, uint32_t) { ++acc; });
         flush();
     }
 }
 
-// K_pileup: the coverage request split by position and base (per_base of the request; the rule: CovTable in coral_bam_common.h).
-// The work items and the CIGAR walk are k_bam_cov_count's (k_bam_cov_plan sizes them); what differs is the inner loop: every
-// counted base is one no-return 32-bit atomic at table[(seg_off[t] + x - lo[t]) * 4 + b].  There is nothing to reduce: the 64
-// lanes of a stride are 64 different positions, so a wave never collides with itself - only different records at the same
-// position do.  One wave per workgroup (grid-stride), no LDS: it fits beside resident inflate waves.
+// K_pileup (per_base of the request): k_bam_cov_count's work items and walk with the table sink: every counted base is one
+// no-return 32-bit atomic at table[(seg_off[t] + x - lo[t]) * 4 + col].  There is nothing to reduce: the 64 lanes of a stride are
+// 64 different positions, so a wave never collides with itself - only different records at the same position do.  One wave per
+// workgroup (grid-stride), no LDS: it fits beside resident inflate waves.
 __global__ __launch_bounds__(WAVE) void k_bam_pileup(const uint8_t *__restrict__ buf, long long n_rec, MetaArrays M, CovSegs S,
                                                      const long long *__restrict__ seg_off, int threshold,
                                                      const long long *__restrict__ item_off, uint32_t *__restrict__ table) {
     const int lane = threadIdx.x;
     const long long total = item_off[n_rec];
-    const uint32_t thr = (uint32_t)threshold;
     for (long long w = blockIdx.x; w < total; w += gridDim.x) {
-        long long a = 0, b = n_rec;                                   // the record: the last i with item_off[i] <= w
-        while (b - a > 1) {
-            const long long m = (a + b) >> 1;
-            if (item_off[m] <= w) a = m; else b = m;
-        }
-        const long long i = a;
-        const int32_t tid = M.tid[i], l_seq = M.l_seq[i], pos = M.pos[i];
-        const int n_ops = M.n_cigar[i];
-        const long long q_lo = (w - item_off[i]) * COV_SLICE, q_hi = min((long long)l_seq, q_lo + COV_SLICE);
-        const uint8_t *ops = buf + M.cig_src[i];
-        const uint8_t *seq = buf + M.seq_src[i];
-        const uint8_t *qual = seq + ((long long)l_seq + 1) / 2;
-        int s = cov_first(S, tid, pos, 0);
-        long long q_base = 0, r_base = pos;
-        for (int c = 0; c < n_ops && q_base < q_hi; c += WAVE) {
-            if (s >= S.n || S.tid[s] != tid) break;                   // no segment left on this contig
-            const int kk = c + lane;
-            const uint32_t wd = kk < n_ops ? ld32(ops + 4ll * kk) : 15u;
-            const uint32_t op = wd & 15u;
-            const long long len = (long long)(wd >> 4);
-            const long long qa = ((0x193u >> op) & 1u) ? len : 0;     // M I S = X advance the query
-            const long long ra = ((0x18Du >> op) & 1u) ? len : 0;     // M D N = X advance the reference
-            long long qs = qa, rs = ra;
-            for (int d = 1; d < WAVE; d <<= 1) {
-                const long long tq = __shfl_up(qs, d), tr = __shfl_up(rs, d);
-                if (lane >= d) { qs += tq; rs += tr; }
-            }
-            const long long q_op = q_base + qs - qa, r_op = r_base + rs - ra;
-            const bool cand = ((0x181u >> op) & 1u) && len > 0 && q_op < q_hi && q_op + len > q_lo;     // M = X meeting the item
-            unsigned long long m = __ballot(cand);
-            while (m) {
-                const int j = __builtin_ctzll(m);
-                m &= m - 1;
-                const long long oq = __shfl(q_op, j), orf = __shfl(r_op, j), ol = __shfl(len, j);
-                const long long aq = max(oq, q_lo), bq = min(oq + ol, q_hi);
-                const long long r0 = orf + (aq - oq), r1 = orf + (bq - oq);
-                if (s < S.n && S.tid[s] == tid && (long long)S.hi[s] <= r0)
-                    s = (s + 1 < S.n && S.tid[s + 1] == tid && (long long)S.hi[s + 1] > r0) ? s + 1 : cov_first(S, tid, r0, s + 1);
-                for (int t = s; t < S.n && S.tid[t] == tid && (long long)S.lo[t] < r1; ++t) {
-                    const long long lo = S.lo[t], xa = max(r0, lo), xb = min(r1, (long long)S.hi[t]);
-                    const long long row0 = 4 * (seg_off[t] - lo);                  // lo <= x < hi: 4 * x + row0 lies in the segment's rows
-                    for (long long x = xa + lane; x < xb; x += WAVE) {
-                        const long long qi = aq + (x - r0);                    // < bq <= q_hi <= l_seq
-                        const uint8_t byte = seq[qi >> 1];
-                        const uint32_t code = (qi & 1) ? (byte & 15u) : (uint32_t)(byte >> 4);
-                        uint32_t col;
-                        if (pileup_base(code, &col) && qual[qi] >= thr) atomicAdd(table + (row0 + 4 * x + col), 1u);
-                    }
-                }
-            }
-            q_base += __shfl(qs, WAVE - 1);
-            r_base += __shfl(rs, WAVE - 1);
-        }
+        const long long i = item_record(item_off, n_rec, w);
+        const long long q_lo = (w - item_off[i]) * COV_SLICE, q_hi = min((long long)M.l_seq[i], q_lo + COV_SLICE);
+        long long row0 = 0;                                            // lo <= x < hi: 4 * x + row0 lies in the segment's rows
+        cov_walk(buf, M, S, (uint32_t)threshold, i, q_lo, q_hi, lane, [&](int t, long long lo) { row0 = 4 * (seg_off[t] - lo); },
+                 [&](long long x, uint32_t col) { atomicAdd(table + (row0 + 4 * x + col), 1u); });
     }
 }
 
@@ -1223,12 +1191,7 @@ __global__ __launch_bounds__(WAVE) void k_bam_qc(const uint8_t *__restrict__ buf
     uint32_t *mine = H + (lane % COPIES);
     const long long total = item_off[n_rec];
     for (long long w = blockIdx.x; w < total; w += gridDim.x) {
-        long long a = 0, b = n_rec;                                   // the record: the last i with item_off[i] <= w
-        while (b - a > 1) {
-            const long long m = (a + b) >> 1;
-            if (item_off[m] <= w) a = m; else b = m;
-        }
-        const long long i = a;
+        const long long i = item_record(item_off, n_rec, w);
         const uint32_t l_seq = (uint32_t)M.l_seq[i];
         const uint8_t *r = buf + rec_start[i];
         const long long q_lo = (w - item_off[i]) * QC_SLICE, q_hi = min((long long)l_seq, q_lo + QC_SLICE);
@@ -1440,6 +1403,148 @@ struct HostJob {
     std::vector<uint8_t> na_raw;
 };
 
+struct Carver {                      // hands the workspace out in 256-byte steps (p == 0: only the size is counted)
+    uintptr_t p;
+    size_t used = 0;
+    void *operator()(size_t n) { used += up256(n); return (void *)(p + used - up256(n)); }
+};
+
+inline bool dev_get(void *dst, const void *src, size_t bytes) { return bytes == 0 || hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) == hipSuccess; }
+
+// The per-record scratch of the parse that a request may WRITE, built in emit.  Why that is safe:
+// - k_bam_emit has finished with every array named here: the batch's host copies synchronised the stream behind it.
+// - The requests are queued on the caller's stream in the order coverage, read QC, index, so each runs behind the one in front.
+//   Coverage and read QC use the same two arrays in turn.
+// - The index goes last because its out_key is M.cig_src, which the coverage walk reads.  What every request only READS: the
+//   fixed fields of M (tid .. n_cigar, seq_src), the record starts and the end positions.
+// - All of it is queued in front of ev_parsed and of the next batch's k_bam_meta, which refills the arrays on the same stream.
+struct GpuDecoder;
+struct Borrowed {
+    long long *items, *item_off;                        // coverage, then read QC (M.name_len, M.sa_len)
+    unsigned long long *voff, *out_voff;                // index (d_cig_off, M.sa_src)
+    long long *key, *head, *head_off, *out_key;         // index (M.pad_ops, d_name_off, d_sa_off, M.cig_src)
+};
+
+inline bool launched(const char *what, std::string &err) {      // behind a request's launches
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) err = std::string(what) + " launch failed: " + hipGetErrorString(e);
+    return e == hipSuccess;
+}
+
+struct CovRequest {                  // window coverage; with per_base the table of a pileup request instead of the counters
+    bool active = false;
+    const CovTable *T = nullptr;     // the request's segments, threshold and callback (Request::cov)
+    CovSegs segs{nullptr, nullptr, nullptr, 0};          // segments and counters in the workspace (n = 0: nothing to count)
+    unsigned long long *counts = nullptr;
+    long long *pile_off = nullptr;   // per_base: the segments' prefix offsets and the table [positions][4]
+    uint32_t *pile = nullptr;
+    void carve(Carver &take) {
+        if (!active) return;
+        const size_t n_seg = T->size();
+        int32_t *seg = (int32_t *)take(3 * n_seg * 4);
+        segs = CovSegs{seg, seg + n_seg, seg + 2 * n_seg, (int)n_seg};
+        counts = (unsigned long long *)take(n_seg * 8);
+        if (!T->per_base) return;
+        pile_off = (long long *)take((n_seg + 1) * 8);
+        pile = (uint32_t *)take((size_t)T->n_pos() * 16);
+    }
+    const char *start(hipError_t &e) const {             // nullptr, or what failed with `e`
+        if (segs.n == 0) return nullptr;
+        const size_t b = T->size() * 4;
+        if ((e = hipMemcpy((void *)segs.tid, T->tid.data(), b, hipMemcpyHostToDevice)) != hipSuccess ||
+            (e = hipMemcpy((void *)segs.lo, T->lo.data(), b, hipMemcpyHostToDevice)) != hipSuccess ||
+            (e = hipMemcpy((void *)segs.hi, T->hi.data(), b, hipMemcpyHostToDevice)) != hipSuccess || (e = hipMemset(counts, 0, 2 * b)) != hipSuccess)
+            return "coverage request set-up";
+        if (T->per_base && ((e = hipMemcpy(pile_off, T->seg_off.data(), (T->size() + 1) * 8, hipMemcpyHostToDevice)) != hipSuccess ||
+                            (T->n_pos() > 0 && (e = hipMemset(pile, 0, (size_t)T->n_pos() * 16)) != hipSuccess)))
+            return "pileup request set-up";
+        return nullptr;
+    }
+    bool batch(GpuDecoder *G, hipStream_t stream, const Borrowed &S, std::string &err) const;      // (behind GpuDecoder)
+    bool finish(Decoded &D) const {
+        if (!active) return true;
+        if (!T->per_base) { D.cov.assign(T->size(), 0); return dev_get(D.cov.data(), counts, T->size() * 8); }
+        D.pileup.assign((size_t)T->n_pos() * 4, 0);      // the table, and the counts per segment as its sums
+        D.has_pileup = true;
+        if (!dev_get(D.pileup.data(), pile, (size_t)T->n_pos() * 16)) return false;
+        pileup_segment_sums(*T, D.pileup.data(), D.cov);
+        return true;
+    }
+};
+
+struct QcRequest {
+    bool active = false;
+    long long *rows = nullptr;                // the batch's qual_sum rows: one array for all batches (collect)
+    unsigned long long *hist = nullptr;       // the device histogram of the whole decode
+    long long pending_n = 0;                  // records of the batch whose rows are still on the device
+    void carve(Carver &take, size_t nr) {
+        if (!active) return;
+        rows = (long long *)take(nr * 8);
+        hist = (unsigned long long *)take(256 * 8);
+    }
+    const char *start(hipError_t &e) const { return active && (e = hipMemset(hist, 0, 256 * 8)) != hipSuccess ? "read-QC request set-up" : nullptr; }
+    bool batch(GpuDecoder *G, hipStream_t stream, const Borrowed &S, std::string &err);
+    // The rows of the batch emitted last, if they are still on the device (the caller has synchronised the stream).  One array
+    // for all batches: that holds only while every emit of a decode and the result call are given the SAME stream: the rows of
+    // batch k-1 are complete once batch k's emit has waited for the stream that batch k-1's kernels were queued on, and batch
+    // k's k_bam_qc_plan is queued only afterwards.
+    bool collect(std::vector<int64_t> &v) {
+        if (pending_n == 0) return true;
+        const size_t base = v.size();
+        v.resize(base + (size_t)pending_n);
+        const bool ok = hipMemcpy(v.data() + base, rows, (size_t)pending_n * 8, hipMemcpyDeviceToHost) == hipSuccess;
+        pending_n = 0;
+        return ok;
+    }
+    bool finish(QcPartial &Q) { return !active || (collect(Q.qual_sum) && dev_get(Q.hist, hist, 256 * 8)); }
+};
+
+struct IndexRequest {
+    bool active = false;
+    IndexDev X{};
+    uint32_t *boff[2] = {nullptr, nullptr};       // per block of the slot's batch: its file offset relative to the batch's
+    BlockDesc *kept_desc[2] = {nullptr, nullptr}; // the slot's block table and offsets, kept for k_bam_index: the feeder re-stages
+    uint32_t *kept_boff[2] = {nullptr, nullptr};  //   d_desc / boff for batch k + 2 while batch k is still being parsed
+    int parity = 0;                               // which X.state the next batch reads
+    void carve(Carver &take, size_t max_blocks, const IndexPartial &P) {      // (everything per record re-uses the batch's scratch)
+        if (!active) return;
+        const size_t n_ref = P.n_mapped.size();
+        for (int i = 0; i < 2; ++i) {
+            boff[i] = (uint32_t *)take(max_blocks * 4);
+            kept_boff[i] = (uint32_t *)take(max_blocks * 4);
+            kept_desc[i] = (BlockDesc *)take(max_blocks * sizeof(BlockDesc));
+        }
+        X.lin = (unsigned long long *)take(P.lin.size() * 8); X.lin_off = (long long *)take((n_ref + 1) * 8);
+        X.n_mapped = (unsigned long long *)take(n_ref * 8); X.n_unmapped = (unsigned long long *)take(n_ref * 8);
+        X.n_no_coor = (unsigned long long *)take(8); X.state = (unsigned long long *)take(16); X.unsorted = (int32_t *)take(4);
+        X.n_ref = (int)n_ref;
+    }
+    // with nothing in front of the first record (rank 0) the first batch's end state is never read; a later rank's first
+    // record is found by search and must start inside its batch (checked in coral_bamgpu_next)
+    const char *start(const IndexPartial &P, hipError_t &e) const {
+        const size_t n_ref = (size_t)X.n_ref;
+        const bool ok = !active || ((e = hipMemset(X.lin, 0xff, P.lin.size() * 8)) == hipSuccess && (e = hipMemset(X.n_mapped, 0, n_ref * 8)) == hipSuccess &&
+                                    (e = hipMemset(X.n_unmapped, 0, n_ref * 8)) == hipSuccess && (e = hipMemset(X.n_no_coor, 0, 8)) == hipSuccess &&
+                                    (e = hipMemset(X.state, 0, 16)) == hipSuccess && (e = hipMemset(X.unsorted, 0, 4)) == hipSuccess &&
+                                    (e = hipMemcpy(X.lin_off, P.lin_off.data(), (n_ref + 1) * 8, hipMemcpyHostToDevice)) == hipSuccess);
+        return ok ? nullptr : "index request set-up";
+    }
+    bool batch(GpuDecoder *G, hipStream_t stream, const Borrowed &S, std::string &err);
+    // false: a copy failed.  Sets P.unsorted when the device saw the order broken; it stays set: no index can be built
+    bool finish(IndexPartial &P) const {
+        if (!active) return true;
+        const size_t n_ref = (size_t)X.n_ref;
+        unsigned long long state[2] = {0, 0}, no_coor = 0;
+        int32_t dev_unsorted = 0;
+        if (!(dev_get(P.lin.data(), X.lin, P.lin.size() * 8) && dev_get(P.n_mapped.data(), X.n_mapped, n_ref * 8) && dev_get(P.n_unmapped.data(), X.n_unmapped, n_ref * 8) &&
+              dev_get(&no_coor, X.n_no_coor, 8) && dev_get(state, X.state, 16) && dev_get(&dev_unsorted, X.unsorted, 4)))
+            return false;
+        if (dev_unsorted) P.unsorted = true;
+        if (!P.unsorted) { P.n_no_coor = (int64_t)no_coor; P.end_voff = state[parity]; }
+        return true;
+    }
+};
+
 struct GpuDecoder {
     MappedFile f;
     Decoded D;
@@ -1501,33 +1606,27 @@ struct GpuDecoder {
     bool worker_stop = false, worker_busy = false;
     std::string worker_error;
     long long cur_carry_pos = 0;
-    // window-coverage request: segments and counters in the workspace (n = 0 without one)
-    CovSegs cov{nullptr, nullptr, nullptr, 0};
-    unsigned long long *cov_counts = nullptr;
-    // pileup request (per_base): the segments' prefix offsets and the table [positions][4], in the workspace as well
-    long long *pile_off = nullptr;
-    uint32_t *pile = nullptr;
+    // the requests that ride along
+    CovRequest cov;
+    QcRequest qc;
+    IndexRequest idx;
     // span decode: the spans are decoded one after the other through the same batches
     std::vector<SpanDef> spans;
     int cur_span = 0;                         // the span the caller's thread is parsing
     std::vector<int> span_verdict;            // per span (under m): 0 = not known yet, 1 = its last record has been parsed,
                                               //   2 = the record in front of its end goes on behind its last own block
-    // index request
-    IndexDev X{};
-    uint32_t *d_boff[2] = {nullptr, nullptr}; // per block of the slot's batch: its file offset relative to the batch's
-    BlockDesc *d_idesc[2] = {nullptr, nullptr};   // the slot's block table and offsets, kept for k_bam_index: the feeder re-stages
-    uint32_t *d_iboff[2] = {nullptr, nullptr};    //   d_desc / d_boff for batch k + 2 while batch k is still being parsed
-    int idx_parity = 0;
-    // read-QC request: the batch's qual_sum rows (fetched when the NEXT batch's host fields are: the stream has
-    // been synchronised behind the kernels by then, and that batch's k_bam_qc_plan is queued only afterwards, so one array
-    // does), the device histogram of the whole decode
-    long long *d_qc_sum = nullptr;
-    unsigned long long *d_qc_hist = nullptr;
-    long long qc_pending_n = 0;               // records of the batch whose rows are still on the device
     // statistics
     double t_open = 0, seconds = 0, host_seconds = 0;
     int64_t fixups = 0, n_batches = 0, na_records = 0;
     std::chrono::steady_clock::time_point t_start;
+
+    // work items of `slice` bytes in the batch between next() and emit(): at most one per record plus one per slice
+    long long max_items(long long slice) const { return cur_n_rec + ((long long)CARRY_CAP + (long long)cur.infl_bytes) / slice + 1; }
+    // exclusive sums of that batch's n + 1 per-record counts (scan inputs, work items, index run heads)
+    bool scan(hipStream_t stream, long long *in, long long *out) {
+        size_t tmp = scan_tmp_bytes;
+        return hipcub::DeviceScan::ExclusiveSum(d_scan_tmp, tmp, in, out, (int)(cur_n_rec + 1), stream) == hipSuccess;
+    }
 
     ~GpuDecoder() {
         {
@@ -1563,14 +1662,67 @@ struct GpuDecoder {
     }
 };
 
-#define HIP_OK(call, what)                                                                  \
-    do {                                                                                    \
-        hipError_t e_ = (call);                                                             \
-        if (e_ != hipSuccess) {                                                             \
-            G->error = std::string(what) + ": " + hipGetErrorString(e_);                    \
-            return false;                                                                   \
-        }                                                                                   \
-    } while (0)
+// queued before ev_parsed so that the slot is not inflated into while the kernels read its SEQ and QUAL
+bool CovRequest::batch(GpuDecoder *G, hipStream_t stream, const Borrowed &S, std::string &err) const {
+    const long long n = G->cur_n_rec;
+    const uint8_t *buf = G->d_infl[G->k & 1];
+    if (n == 0 || segs.n == 0) return true;
+    hipLaunchKernelGGL(k_bam_cov_plan, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, stream, buf, n, G->M, G->d_end, segs, T->threshold,
+                       (int)T->filter_all, S.items);
+    if (!G->scan(stream, S.items, S.item_off)) { err = "scan of the coverage work items failed"; return false; }
+    const long long items = G->max_items(COV_SLICE);
+    if (T->per_base)                 // one wave per workgroup, grid-stride beyond 32 per CU
+        hipLaunchKernelGGL(k_bam_pileup, dim3((unsigned)std::min<long long>(items, 8192)), dim3(WAVE), 0, stream, buf, n, G->M, segs, pile_off,
+                           T->threshold, S.item_off, pile);
+    else                             // 4 waves per workgroup, grid-stride beyond
+        hipLaunchKernelGGL(k_bam_cov_count, dim3((unsigned)std::min<long long>((items + 3) / 4, 8192)), dim3(256), 0, stream, buf, n, G->M, segs,
+                           T->threshold, S.item_off, counts);
+    return launched("window coverage", err);
+}
+
+// Nothing is waited for here: the rows are fetched with the next batch's host fields (behind that emit's stream
+// synchronisation, which any kernel queued here is in front of), or by coral_bamgpu_finish.
+bool QcRequest::batch(GpuDecoder *G, hipStream_t stream, const Borrowed &S, std::string &err) {
+    const long long n = G->cur_n_rec;
+    const uint8_t *buf = G->d_infl[G->k & 1];
+    if (n == 0 || !active) return true;
+    hipLaunchKernelGGL(k_bam_qc_plan, dim3((unsigned)((n + 1 + WAVE - 1) / WAVE)), dim3(WAVE), 0, stream, buf, G->d_rec_start, n, G->M, rows, S.items);
+    if (!G->scan(stream, S.items, S.item_off)) { err = "scan of the read-QC work items failed"; return false; }
+    // one wave per workgroup, grid-stride beyond 8 per CU
+    hipLaunchKernelGGL(k_bam_qc, dim3((unsigned)std::min<long long>(G->max_items(QC_SLICE), 2048)), dim3(WAVE), 0, stream, buf, G->d_rec_start, n, G->M, S.item_off,
+                       (unsigned long long *)rows, hist);
+    if (!launched("read-QC", err)) return false;
+    pending_n = n;
+    return true;
+}
+
+// the batch's part of the index; also for a batch without records: the end state it leaves is the next batch's start
+bool IndexRequest::batch(GpuDecoder *G, hipStream_t stream, const Borrowed &S, std::string &err) {
+    const long long n = G->cur_n_rec;
+    if (!active) return true;
+    hipLaunchKernelGGL(k_bam_index, dim3((unsigned)((n + 1 + WAVE - 1) / WAVE)), dim3(WAVE), 0, stream, G->d_rec_start, n, G->M, G->d_end, kept_desc[G->k & 1],
+                       kept_boff[G->k & 1], G->cur.n_blocks, (unsigned long long)G->cur.file_off, (unsigned long long)G->cur.comp_bytes,
+                       (long long)G->cur.infl_bytes, G->cur_carry_pos, parity, X, S.voff, S.key, S.head);
+    parity ^= 1;
+    long long n_heads = 0;
+    if (n > 0) {
+        if (!G->scan(stream, S.head, S.head_off)) { err = "scan of the index run heads failed"; return false; }
+        hipLaunchKernelGGL(k_bam_index_compact, dim3((unsigned)((n + WAVE - 1) / WAVE)), dim3(WAVE), 0, stream, n, S.head, S.head_off, S.voff, S.key, S.out_voff,
+                           S.out_key);
+        if (hipMemcpyAsync(&n_heads, S.head_off + n, 8, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) {
+            err = std::string("index kernels failed: ") + hipGetErrorString(hipGetLastError());
+            return false;
+        }
+        std::vector<long long> hk((size_t)n_heads);
+        std::vector<unsigned long long> hv((size_t)n_heads);
+        if (!dev_get(hk.data(), S.out_key, (size_t)n_heads * 8) || !dev_get(hv.data(), S.out_voff, (size_t)n_heads * 8)) {
+            err = "copy of the index run heads failed";
+            return false;
+        }
+        for (long long j = 0; j < n_heads; ++j) G->D.idx.add_head(hk[(size_t)j], hv[(size_t)j]);
+    }
+    return launched("index", err);
+}
 
 // parallel pread of [off, off + n) into dst
 bool read_range(int fd, uint64_t off, size_t n, uint8_t *dst, int n_threads) {
@@ -1730,8 +1882,8 @@ void feeder_main(GpuDecoder *G) {
             memcpy(h_crc, crcs.data(), crcs.size() * 4);
             if (hipMemcpyAsync(G->d_desc[slot], G->h_desc[slot], desc.size() * sizeof(BlockDesc), hipMemcpyHostToDevice, G->s_copy) != hipSuccess ||
                 hipMemcpyAsync(G->d_crc[slot], h_crc, crcs.size() * 4, hipMemcpyHostToDevice, G->s_copy) != hipSuccess ||
-                (G->req.want_index && (memcpy(h_crc + G->max_blocks, boffs.data(), boffs.size() * 4),
-                               hipMemcpyAsync(G->d_boff[slot], h_crc + G->max_blocks, boffs.size() * 4, hipMemcpyHostToDevice, G->s_copy) != hipSuccess)) ||
+                (G->idx.active && (memcpy(h_crc + G->max_blocks, boffs.data(), boffs.size() * 4),
+                               hipMemcpyAsync(G->idx.boff[slot], h_crc + G->max_blocks, boffs.size() * 4, hipMemcpyHostToDevice, G->s_copy) != hipSuccess)) ||
                 hipEventRecord(G->ev_h2d[slot], G->s_copy) != hipSuccess)
                 return fail("host-to-device copy of a block table failed");
             {
@@ -1821,13 +1973,7 @@ void worker_main(GpuDecoder *G) {
 
 // Lays the device workspace out (ws == nullptr: only its size is computed, the pointers stay meaningless).
 bool carve(GpuDecoder *G, void *ws, size_t bytes) {
-    const uintptr_t p = (uintptr_t)ws;
-    size_t used = 0;
-    auto take = [&](size_t n) -> void * {
-        void *q = (void *)(p + used);
-        used += up256(n);
-        return q;
-    };
+    Carver take{(uintptr_t)ws};
     for (int i = 0; i < 2; ++i) {
         G->d_comp[i] = (uint8_t *)take(G->comp_cap + COMP_SLACK);
         G->d_infl[i] = (uint8_t *)take((size_t)CARRY_CAP + G->infl_cap + COMP_SLACK);
@@ -1858,38 +2004,11 @@ bool carve(GpuDecoder *G, void *ws, size_t bytes) {
     G->names_cap = G->sa_cap = (size_t)CARRY_CAP + G->infl_cap;
     G->d_names = (uint8_t *)take(G->names_cap);
     G->d_sa_text = (uint8_t *)take(G->sa_cap);
-    if (G->req.want_index) {                           // the index request's own arrays (everything per record re-uses the batch's scratch)
-        const size_t n_ref = G->D.ref_lens.size();
-        for (int i = 0; i < 2; ++i) {
-            G->d_boff[i] = (uint32_t *)take(G->max_blocks * 4);
-            G->d_iboff[i] = (uint32_t *)take(G->max_blocks * 4);
-            G->d_idesc[i] = (BlockDesc *)take(G->max_blocks * sizeof(BlockDesc));
-        }
-        G->X.lin = (unsigned long long *)take(G->D.idx.lin.size() * 8);
-        G->X.lin_off = (long long *)take((n_ref + 1) * 8);
-        G->X.n_mapped = (unsigned long long *)take(n_ref * 8);
-        G->X.n_unmapped = (unsigned long long *)take(n_ref * 8);
-        G->X.n_no_coor = (unsigned long long *)take(8);
-        G->X.state = (unsigned long long *)take(16);
-        G->X.unsorted = (int32_t *)take(4);
-        G->X.n_ref = (int)n_ref;
-    }
-    if (G->req.want_qc) {
-        G->d_qc_sum = (long long *)take(nr * 8);
-        G->d_qc_hist = (unsigned long long *)take(256 * 8);
-    }
-    if (G->req.has_cov) {                      // the coverage request's segments (tid, lo, hi) and counters
-        const size_t n_seg = G->req.cov.size();
-        int32_t *seg = (int32_t *)take(3 * n_seg * 4);
-        G->cov = CovSegs{seg, seg + n_seg, seg + 2 * n_seg, (int)n_seg};
-        G->cov_counts = (unsigned long long *)take(n_seg * 8);
-        if (G->req.cov.per_base) {
-            G->pile_off = (long long *)take((n_seg + 1) * 8);
-            G->pile = (uint32_t *)take((size_t)G->req.cov.n_pos() * 16);
-        }
-    }
-    if (ws && used > bytes) return false;
-    G->ws_bytes = used;
+    G->idx.carve(take, G->max_blocks, G->D.idx);
+    G->qc.carve(take, nr);
+    G->cov.carve(take);
+    if (ws && take.used > bytes) return false;
+    G->ws_bytes = take.used;
     return true;
 }
 
@@ -1906,9 +2025,9 @@ bool launch_inflate(GpuDecoder *G, int kb, const BatchInfo &bi) {
     const int slot = kb & 1;
     HIP_LAUNCH_OK(hipStreamWaitEvent(G->s_infl, G->ev_h2d[slot], 0), "hipStreamWaitEvent");
     if (kb >= 2) HIP_LAUNCH_OK(hipStreamWaitEvent(G->s_infl, G->ev_parsed[slot], 0), "hipStreamWaitEvent");     // the buffer's previous batch has been parsed
-    if (G->req.want_index) {    // (behind ev_parsed of batch kb - 2, whose k_bam_index read the copies; in front of ev_infl, which this batch's parse waits for)
-        HIP_LAUNCH_OK(hipMemcpyAsync(G->d_idesc[slot], G->d_desc[slot], (size_t)bi.n_blocks * sizeof(BlockDesc), hipMemcpyDeviceToDevice, G->s_infl), "hipMemcpyAsync");
-        HIP_LAUNCH_OK(hipMemcpyAsync(G->d_iboff[slot], G->d_boff[slot], (size_t)bi.n_blocks * 4, hipMemcpyDeviceToDevice, G->s_infl), "hipMemcpyAsync");
+    if (G->idx.active) {    // (behind ev_parsed of batch kb - 2, whose k_bam_index read the copies; in front of ev_infl, which this batch's parse waits for)
+        HIP_LAUNCH_OK(hipMemcpyAsync(G->idx.kept_desc[slot], G->d_desc[slot], (size_t)bi.n_blocks * sizeof(BlockDesc), hipMemcpyDeviceToDevice, G->s_infl), "hipMemcpyAsync");
+        HIP_LAUNCH_OK(hipMemcpyAsync(G->idx.kept_boff[slot], G->idx.boff[slot], (size_t)bi.n_blocks * 4, hipMemcpyDeviceToDevice, G->s_infl), "hipMemcpyAsync");
     }
     const int grid = (bi.n_blocks + INFL_WAVES - 1) / INFL_WAVES;
     hipLaunchKernelGGL(k_bgzf_inflate<0>, dim3(grid), dim3(INFL_WAVES * WAVE), 0, G->s_infl, G->d_comp[slot], G->d_desc[slot], bi.n_blocks,
@@ -1997,8 +2116,10 @@ extern "C" int coral_bamgpu_open_request(const char *path, int32_t n_threads, in
         G->byte_hi = span_bytes;
         if (G->spans.empty()) G->first_block = G->f.size;
     }
-    if (R.want_index) G->D.idx.init(G->D.ref_lens);
-    if (R.want_qc) G->D.qc.init();
+    G->cov.active = R.has_cov;
+    G->cov.T = &G->req.cov;
+    if ((G->idx.active = R.want_index)) G->D.idx.init(G->D.ref_lens);
+    if ((G->qc.active = R.want_qc)) G->D.qc.init();
     // batch size: at most `batch_bytes` inflated, no more than the range can need.  Default 2.52 GiB = 6 x 6 912 BGZF blocks of
     // 65 280 bytes (htslib's block size): the inflate kernel keeps 27 one-wave workgroups per CU x 256 CUs resident, blocks of
     // equal size finish in rounds, and a batch that is a whole number of rounds has no part-filled last round; bigger batches
@@ -2031,55 +2152,18 @@ extern "C" int coral_bamgpu_open(const char *path, int32_t n_threads, int32_t ra
     return coral_bamgpu_open_request(path, n_threads, batch_bytes, &q, handle, workspace_bytes);
 }
 
-// the qual_sum rows of the batch emitted last, if they are still on the device (the caller has synchronised the stream).
-// One array for all batches: that holds only while every emit of a decode and the result call are given the SAME stream:
-// the rows of batch k-1 are complete once batch k's emit has waited for the stream that batch k-1's kernels were queued on.
-static bool qc_collect(GpuDecoder *G) {
-    if (G->qc_pending_n == 0) return true;
-    std::vector<int64_t> &v = G->D.qc.qual_sum;
-    const size_t base = v.size();
-    v.resize(base + (size_t)G->qc_pending_n);
-    const bool ok = hipMemcpy(v.data() + base, G->d_qc_sum, (size_t)G->qc_pending_n * 8, hipMemcpyDeviceToHost) == hipSuccess;
-    G->qc_pending_n = 0;
-    return ok;
-}
-
 // Once every batch has been emitted: waits for `stream_` and leaves what was requested in the host-side result
 // (coral_bamgpu_host -> coral_bam_coverage_result, coral_bam_index_sizes / _fill, coral_bam_qc_sizes / _fill).
 extern "C" int coral_bamgpu_finish(void *handle, void *stream_) {
     GpuDecoder *G = (GpuDecoder *)handle;
     if (!G) return CORAL_ERR_ARG;
     if (!G->finished || G->have_cur) { set_error("coral_bamgpu_finish: the decode is not finished"); return CORAL_ERR_ARG; }
-    const Request &R = G->req;
-    if (!R.has_cov && !R.want_index && !R.want_qc) return CORAL_OK;
-    auto get = [](void *dst, const void *src, size_t bytes) { return bytes == 0 || hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) == hipSuccess; };
-    bool ok = hipStreamSynchronize((hipStream_t)stream_) == hipSuccess;
-    if (ok && R.has_cov && !R.cov.per_base) {
-        G->D.cov.assign(R.cov.size(), 0);
-        ok = get(G->D.cov.data(), G->cov_counts, R.cov.size() * 8);
+    if (!G->cov.active && !G->qc.active && !G->idx.active) return CORAL_OK;
+    if (hipStreamSynchronize((hipStream_t)stream_) != hipSuccess || !G->cov.finish(G->D) || !G->idx.finish(G->D.idx) || !G->qc.finish(G->D.qc)) {
+        set_error("coral_bamgpu_finish: copy of the requested results failed");
+        return CORAL_ERR_HIP;
     }
-    if (ok && R.cov.per_base) {                // the table, and the counts per segment as its sums
-        G->D.pileup.assign((size_t)R.cov.n_pos() * 4, 0);
-        G->D.has_pileup = true;
-        ok = get(G->D.pileup.data(), G->pile, (size_t)R.cov.n_pos() * 16);
-        if (ok) pileup_segment_sums(R.cov, G->D.pileup.data(), G->D.cov);
-    }
-    IndexPartial &P = G->D.idx;
-    unsigned long long state[2] = {0, 0}, no_coor = 0;
-    int32_t unsorted = 0;
-    if (ok && R.want_index) {
-        const size_t n_ref = P.n_mapped.size();
-        ok = get(P.lin.data(), G->X.lin, P.lin.size() * 8) && get(P.n_mapped.data(), G->X.n_mapped, n_ref * 8) &&
-             get(P.n_unmapped.data(), G->X.n_unmapped, n_ref * 8) && get(&no_coor, G->X.n_no_coor, 8) && get(state, G->X.state, 16) &&
-             get(&unsorted, G->X.unsorted, 4);
-    }
-    if (ok && R.want_qc) ok = qc_collect(G) && get(G->D.qc.hist, G->d_qc_hist, 256 * 8);
-    if (!ok) { set_error("coral_bamgpu_finish: copy of the requested results failed"); return CORAL_ERR_HIP; }
-    if (unsorted || P.unsorted) { set_error("the records are not in coordinate order: no index can be built"); return CORAL_ERR_FORMAT; }
-    if (R.want_index) {
-        P.n_no_coor = (int64_t)no_coor;
-        P.end_voff = state[G->idx_parity];
-    }
+    if (G->D.idx.unsorted) { set_error("the records are not in coordinate order: no index can be built"); return CORAL_ERR_FORMAT; }
     return CORAL_OK;
 }
 
@@ -2115,29 +2199,8 @@ extern "C" int coral_bamgpu_start(void *handle, void *workspace, int64_t workspa
     }
     if ((e = hipStreamCreateWithFlags(&G->s_crc, hipStreamNonBlocking)) != hipSuccess) return bad("hipStreamCreate", e);
     G->t_alloc = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_alloc0).count();
-    if (G->req.want_index) {
-        const size_t n_ref = G->D.ref_lens.size();
-        // with nothing in front of the first record (rank 0) the first batch's end state is never read; a later rank's first
-        // record is found by search and must start inside its batch (checked in coral_bamgpu_next)
-        if ((e = hipMemset(G->X.lin, 0xff, G->D.idx.lin.size() * 8)) != hipSuccess || (e = hipMemset(G->X.n_mapped, 0, n_ref * 8)) != hipSuccess ||
-            (e = hipMemset(G->X.n_unmapped, 0, n_ref * 8)) != hipSuccess || (e = hipMemset(G->X.n_no_coor, 0, 8)) != hipSuccess ||
-            (e = hipMemset(G->X.state, 0, 16)) != hipSuccess || (e = hipMemset(G->X.unsorted, 0, 4)) != hipSuccess ||
-            (e = hipMemcpy(G->X.lin_off, G->D.idx.lin_off.data(), (n_ref + 1) * 8, hipMemcpyHostToDevice)) != hipSuccess)
-            return bad("index request set-up", e);
-    }
-    if (G->req.want_qc && (e = hipMemset(G->d_qc_hist, 0, 256 * 8)) != hipSuccess) return bad("read-QC request set-up", e);
-    if (G->cov.n > 0) {
-        const CovTable &T = G->req.cov;
-        const size_t b = T.size() * 4;
-        if ((e = hipMemcpy((void *)G->cov.tid, T.tid.data(), b, hipMemcpyHostToDevice)) != hipSuccess ||
-            (e = hipMemcpy((void *)G->cov.lo, T.lo.data(), b, hipMemcpyHostToDevice)) != hipSuccess ||
-            (e = hipMemcpy((void *)G->cov.hi, T.hi.data(), b, hipMemcpyHostToDevice)) != hipSuccess ||
-            (e = hipMemset(G->cov_counts, 0, 2 * b)) != hipSuccess)
-            return bad("coverage request set-up", e);
-        if (T.per_base && ((e = hipMemcpy(G->pile_off, T.seg_off.data(), (T.size() + 1) * 8, hipMemcpyHostToDevice)) != hipSuccess ||
-                           (T.n_pos() > 0 && (e = hipMemset(G->pile, 0, (size_t)T.n_pos() * 16)) != hipSuccess)))
-            return bad("pileup request set-up", e);
-    }
+    const char *what;
+    if ((what = G->idx.start(G->D.idx, e)) || (what = G->qc.start(e)) || (what = G->cov.start(e))) return bad(what, e);
     G->feeder = std::thread(feeder_main, G);
     G->worker = std::thread(worker_main, G);
     return CORAL_OK;
@@ -2247,7 +2310,7 @@ extern "C" int coral_bamgpu_next(void *handle, int64_t out[4], void *stream_) {
         still_searching = !bi.last;
     }
     const long long n_rec = res[0], carry_pos = res[1];
-    if (G->req.want_index && G->searching && n_rec > 0 && res[5] < CARRY_CAP) {
+    if (G->idx.active && G->searching && n_rec > 0 && res[5] < CARRY_CAP) {
         // (a byte range that found no record start in its first batch and finds one in the bytes kept from it)
         G->error = "index request: the first record of the byte range does not start in the batch it was found in";
         return fail(CORAL_ERR_FORMAT);
@@ -2265,12 +2328,9 @@ extern "C" int coral_bamgpu_next(void *handle, int64_t out[4], void *stream_) {
         (void)hipMemsetAsync(G->d_error, 0, 4, stream);
         const long long waves = n_rec + 1;
         hipLaunchKernelGGL(k_bam_meta, dim3((unsigned)waves), dim3(WAVE), 0, stream, buf, G->d_rec_start, n_rec, G->M, G->d_error);
-        size_t tmp = G->scan_tmp_bytes;
-        (void)hipcub::DeviceScan::ExclusiveSum(G->d_scan_tmp, tmp, G->M.pad_ops, G->d_cig_off, (int)(n_rec + 1), stream);
-        tmp = G->scan_tmp_bytes;
-        (void)hipcub::DeviceScan::ExclusiveSum(G->d_scan_tmp, tmp, G->M.name_len, G->d_name_off, (int)(n_rec + 1), stream);
-        tmp = G->scan_tmp_bytes;
-        (void)hipcub::DeviceScan::ExclusiveSum(G->d_scan_tmp, tmp, G->M.sa_len, G->d_sa_off, (int)(n_rec + 1), stream);
+        (void)G->scan(stream, G->M.pad_ops, G->d_cig_off);
+        (void)G->scan(stream, G->M.name_len, G->d_name_off);
+        (void)G->scan(stream, G->M.sa_len, G->d_sa_off);
         long long totals[3] = {0, 0, 0};
         int32_t rec_err = 0;
         if (hipMemcpyAsync(&totals[0], G->d_cig_off + n_rec, 8, hipMemcpyDeviceToHost, stream) != hipSuccess ||
@@ -2379,9 +2439,9 @@ extern "C" int coral_bamgpu_emit(void *handle, uint32_t *cigar_dst, int64_t *cig
                   get(J.sa_text.data(), G->d_sa_text, J.sa_text.size()) && get(&na_count, G->d_na_count, 4);
         if (!ok || hipStreamSynchronize(stream) != hipSuccess) return fail(CORAL_ERR_HIP, std::string("copy of the batch's host fields failed: ") + hipGetErrorString(hipGetLastError()));
         G->t_wait_gpu += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_gpu0).count();
-        if (G->req.want_qc && !qc_collect(G)) return fail(CORAL_ERR_HIP, "copy of the read-QC rows failed");      // (of the batch in front)
+        if (!G->qc.collect(D.qc.qual_sum)) return fail(CORAL_ERR_HIP, "copy of the read-QC rows failed");      // (of the batch in front)
         for (long long i = 0; i < n; ++i) has_seq[i] = has_seq[i] > 0 ? 1 : 0;       // (arrived as l_seq)
-        if (G->req.want_index) {                          // the batch's first record against the last one of the batch in front (inside a batch: k_bam_index)
+        if (G->idx.active) {                              // the batch's first record against the last one of the batch in front (inside a batch: k_bam_index)
             D.idx.note_order(IndexPartial::sort_word(tid[0], pos[0]), IndexPartial::sort_word(tid[n - 1], pos[n - 1]));
             D.idx.n_rec += n;
         }
@@ -2424,73 +2484,9 @@ extern "C" int coral_bamgpu_emit(void *handle, uint32_t *cigar_dst, int64_t *cig
     } else if (hipStreamSynchronize(stream) != hipSuccess) {
         return fail(CORAL_ERR_HIP, "hipStreamSynchronize failed");
     }
-    if (n > 0 && G->cov.n > 0) {
-        // window coverage of the batch's records, queued before ev_parsed so that the slot is not inflated into while it reads.
-        // The per-record item counts and their offsets use the name / SA length arrays: k_bam_emit has finished with them
-        // (the host copies above synchronised the stream) and the next batch's k_bam_meta comes behind on the same stream.
-        long long *n_items = G->M.name_len, *item_off = G->M.sa_len;
-        hipLaunchKernelGGL(k_bam_cov_plan, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, stream, buf, n, G->M, G->d_end, G->cov,
-                           G->req.cov.threshold, (int)G->req.cov.filter_all, n_items);
-        size_t tmp = G->scan_tmp_bytes;
-        if (hipcub::DeviceScan::ExclusiveSum(G->d_scan_tmp, tmp, n_items, item_off, (int)(n + 1), stream) != hipSuccess)
-            return fail(CORAL_ERR_HIP, "scan of the coverage work items failed");
-        // at most one item per record plus one per COV_SLICE bases of SEQ in the batch; 4 waves per workgroup, grid-stride beyond
-        const long long items = n + ((long long)CARRY_CAP + (long long)G->cur.infl_bytes) / COV_SLICE + 1;
-        const unsigned blocks = (unsigned)std::min<long long>((items + 3) / 4, 8192);
-        if (G->req.cov.per_base)               // one wave per workgroup, grid-stride beyond 32 per CU
-            hipLaunchKernelGGL(k_bam_pileup, dim3((unsigned)std::min<long long>(items, 8192)), dim3(WAVE), 0, stream, buf, n, G->M, G->cov, G->pile_off,
-                               G->req.cov.threshold, item_off, G->pile);
-        else
-            hipLaunchKernelGGL(k_bam_cov_count, dim3(blocks), dim3(256), 0, stream, buf, n, G->M, G->cov, G->req.cov.threshold, item_off, G->cov_counts);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(CORAL_ERR_HIP, std::string("window coverage launch failed: ") + hipGetErrorString(e));
-    }
-    if (n > 0 && G->req.want_qc) {
-        // read QC of the batch's records, behind the coverage kernels on the same stream and, like them, in front of ev_parsed.
-        // Item counts and offsets use the name / SA length arrays again (the coverage kernels in front have finished with them).
-        // Nothing is waited for here: the rows are fetched with the next batch's host fields (behind that emit's stream
-        // synchronisation, which any kernel queued here is in front of), or by coral_bamgpu_finish.
-        long long *n_items = G->M.name_len, *item_off = G->M.sa_len;
-        long long *rows = G->d_qc_sum;
-        hipLaunchKernelGGL(k_bam_qc_plan, dim3((unsigned)((n + 1 + WAVE - 1) / WAVE)), dim3(WAVE), 0, stream, buf, G->d_rec_start, n, G->M, rows, n_items);
-        size_t tmp = G->scan_tmp_bytes;
-        if (hipcub::DeviceScan::ExclusiveSum(G->d_scan_tmp, tmp, n_items, item_off, (int)(n + 1), stream) != hipSuccess)
-            return fail(CORAL_ERR_HIP, "scan of the read-QC work items failed");
-        // at most one item per record plus one per QC_SLICE bytes of the batch; one wave per workgroup, grid-stride beyond 8 per CU
-        const long long items = n + ((long long)CARRY_CAP + (long long)G->cur.infl_bytes) / QC_SLICE + 1;
-        const unsigned blocks = (unsigned)std::min<long long>(items, 2048);
-        hipLaunchKernelGGL(k_bam_qc, dim3(blocks), dim3(WAVE), 0, stream, buf, G->d_rec_start, n, G->M, item_off, (unsigned long long *)rows, G->d_qc_hist);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(CORAL_ERR_HIP, std::string("read-QC launch failed: ") + hipGetErrorString(e));
-        G->qc_pending_n = n;
-    }
-    if (G->req.want_index) {
-        // the batch's part of the BAI index, behind the coverage kernels on the same stream: every per-record array of the parse
-        // is free by now except the fixed fields and the end positions (the next batch's k_bam_meta comes behind on this stream)
-        unsigned long long *voff = (unsigned long long *)G->d_cig_off, *out_voff = (unsigned long long *)G->M.sa_src;
-        long long *key = G->M.pad_ops, *head = G->d_name_off, *head_off = G->d_sa_off, *out_key = G->M.cig_src;
-        hipLaunchKernelGGL(k_bam_index, dim3((unsigned)((n + 1 + WAVE - 1) / WAVE)), dim3(WAVE), 0, stream, G->d_rec_start, n, G->M, G->d_end,
-                           G->d_idesc[slot], G->d_iboff[slot], G->cur.n_blocks, (unsigned long long)G->cur.file_off, (unsigned long long)G->cur.comp_bytes,
-                           (long long)G->cur.infl_bytes, G->cur_carry_pos, G->idx_parity, G->X, voff, key, head);
-        G->idx_parity ^= 1;
-        long long n_heads = 0;
-        if (n > 0) {
-            size_t tmp = G->scan_tmp_bytes;
-            if (hipcub::DeviceScan::ExclusiveSum(G->d_scan_tmp, tmp, head, head_off, (int)(n + 1), stream) != hipSuccess)
-                return fail(CORAL_ERR_HIP, "scan of the index run heads failed");
-            hipLaunchKernelGGL(k_bam_index_compact, dim3((unsigned)((n + WAVE - 1) / WAVE)), dim3(WAVE), 0, stream, n, head, head_off, voff, key, out_voff, out_key);
-            if (hipMemcpyAsync(&n_heads, head_off + n, 8, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess)
-                return fail(CORAL_ERR_HIP, std::string("index kernels failed: ") + hipGetErrorString(hipGetLastError()));
-            std::vector<long long> hk((size_t)n_heads);
-            std::vector<unsigned long long> hv((size_t)n_heads);
-            if (hipMemcpy(hk.data(), out_key, (size_t)n_heads * 8, hipMemcpyDeviceToHost) != hipSuccess ||
-                hipMemcpy(hv.data(), out_voff, (size_t)n_heads * 8, hipMemcpyDeviceToHost) != hipSuccess)
-                return fail(CORAL_ERR_HIP, "copy of the index run heads failed");
-            for (long long j = 0; j < n_heads; ++j) D.idx.add_head(hk[(size_t)j], hv[(size_t)j]);
-        }
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(CORAL_ERR_HIP, std::string("index launch failed: ") + hipGetErrorString(e));
-    }
+    const Borrowed S{G->M.name_len, G->M.sa_len, (unsigned long long *)G->d_cig_off, (unsigned long long *)G->M.sa_src, G->M.pad_ops, G->d_name_off, G->d_sa_off, G->M.cig_src};
+    std::string err;
+    if (!G->cov.batch(G, stream, S, err) || !G->qc.batch(G, stream, S, err) || !G->idx.batch(G, stream, S, err)) return fail(CORAL_ERR_HIP, err);
     // this buffer may be inflated into again (batch k + 2) once everything above has run
     if (hipEventRecord(G->ev_parsed[slot], stream) != hipSuccess) return fail(CORAL_ERR_HIP, "hipEventRecord failed");
     {

@@ -292,6 +292,19 @@ def test_table_equals_restatement(case, pipe, thr, cb):
     assert p.quality_threshold == thr and p.read_callback == cb
 
 
+@pytest.mark.parametrize("cb", CALLBACKS)
+@pytest.mark.parametrize("thr", THRESHOLDS)
+@pytest.mark.parametrize("pipe", PIPELINES)
+def test_counts_equal_restatement_sums(case, pipe, thr, cb):
+    """The counting request on its own (no table): one walk serves both results, so the counters face the same shapes as the table."""
+    got = bam._decode(case["path"], DEVICE[pipe], coverage=(segment_array(), thr, CB_CODE[cb]), records=False)
+    want = restated_table(case["bases"][(thr, cb)], SEGMENTS)
+    off = np.concatenate([[0], np.cumsum([hi - lo for _, lo, hi in SEGMENTS])])
+    assert got.pileup is None and got.counts.dtype == np.int64
+    # (no case is empty: test_restatement_reads_the_planted_records asserts counted bases at every threshold, 255 included)
+    assert got.counts.tolist() == [int(want[a:b].sum()) for a, b in zip(off, off[1:])] and want.sum() > 0
+
+
 @pytest.mark.parametrize("pipe", PIPELINES)
 def test_depth_equals_window_coverage(case, pipe):
     windows = [("chr8", 150_020, 150_045), ("chr8", 150_100, 150_101), ("chr8", 150_021, 150_400), ("chr8", HOT_POS + 3, HOT_POS + 150),
