@@ -5,8 +5,9 @@
         --skip_cycle_decomp
 
 The `reconstruct` mode and the `hsr` mode (§8(f) item 3) run on the MI355X path, and so do `index`, `qc`
-(the reference's scripts/report_nanopore_qc.py, from one decode of the aligned BAM) and `pileup` (the bases per position of
-regions, pysam's count_coverage as a table); the other modes of the
+(the reference's scripts/report_nanopore_qc.py, from one decode of the aligned BAM), `pileup` (the bases per position of
+regions, pysam's count_coverage as a table) and `depth` (read depth per fixed-size bin of every contig, the table a copy-number
+caller starts from); the other modes of the
 reference (seed, plot, cycle2bed) are untouched and are delegated to the reference's own modules when they are
 importable (set CORAL_REFERENCE_SRC to the reference's src/ directory).  The cycle-decomposition step after the graph build is the
 reference's (Gurobi); it runs on the object this module returns.
@@ -79,6 +80,15 @@ def build_parser():
                     choices=("all", "nofilter"), default="nofilter")
     pp.add_argument("--output", help="Name of the output file (tab-separated).", required=True)
     pp.add_argument("--device", help="GPU to use ('cpu': the host pipeline).", default="cuda:0")
+    dp = sub.add_parser("depth", help="Sum read depth into fixed-size bins along every contig of a (long read) bam file.")
+    dp.add_argument("--lr_bam", help="(Long read) bam file.", required=True)
+    dp.add_argument("--output", help="Name of the output file (tab-separated, CNVkit's .cnn columns).", required=True)
+    dp.add_argument("--bin_size", help="Bases per bin.", type=int, default=1000)
+    dp.add_argument("--min_mapq", help="Leave out reads of a lower mapping quality.", type=int, default=0)
+    dp.add_argument("--exclude_flags", help="Leave out reads with any of these flag bits (default: unmapped, secondary, QC-fail, duplicate).",
+                    type=int, default=0x704)
+    dp.add_argument("--no_deletions", help="If specified, deleted reference bases (D) do not count as covered.", action='store_true')
+    dp.add_argument("--device", help="GPU to use ('cpu': the host pipeline).", default="cuda:0")
     for mode in ("seed", "plot", "cycle2bed"):
         sub.add_parser(mode, help="(reference implementation; not part of the MI355X path)", add_help=False)
     return parser
@@ -170,6 +180,15 @@ def pileup_mode(args):
     return args.output
 
 
+def depth_mode(args):
+    """chromosome, start, end, gene, depth, log2, reads of every bin, in header order (bam.BinnedDepth.write)."""
+    from coral_amd import bam
+    d = bam.binned_depth(args.lr_bam, args.bin_size, args.min_mapq, args.exclude_flags, not args.no_deletions, device=args.device)
+    d.write(args.output)
+    print("Wrote %s (%d bins)" % (args.output, d.n_bins))
+    return args.output
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     if argv and argv[0] in ("seed", "plot", "cycle2bed"):
@@ -199,6 +218,8 @@ def main(argv=None):
         return qc_mode(args)
     if args.mode == "pileup":
         return pileup_mode(args)
+    if args.mode == "depth":
+        return depth_mode(args)
     parser.print_help()
     return None
 

@@ -25,16 +25,19 @@ class coral_bam_request_t(C.Structure):
     _fields_ = [("rank", C.c_int32), ("world", C.c_int32), ("n_spans", C.c_int32), ("span_beg", C.c_void_p), ("span_end", C.c_void_p),
                 ("n_seg", C.c_int32), ("seg_tid", C.c_void_p), ("seg_start", C.c_void_p), ("seg_end", C.c_void_p),
                 ("quality_threshold", C.c_int32), ("read_callback", C.c_int32), ("want_index", C.c_int32), ("want_qc", C.c_int32),
-                ("per_base", C.c_int32)]
+                ("per_base", C.c_int32), ("depth_bin", C.c_int32), ("depth_min_mapq", C.c_int32), ("depth_exclude_flags", C.c_int32),
+                ("depth_count_deletions", C.c_int32)]
 
 
 def bam_request(rank: int = 0, world: int = 1, spans=None, coverage=None, index: bool = False, qc: bool = False,
-                per_base: bool = False) -> coral_bam_request_t:
+                per_base: bool = False, depth=None) -> coral_bam_request_t:
     """The request of a BAM decode: ``spans`` uint64 [K][2] virtual offsets (None: the byte range), ``coverage`` = (segments int32
     [3][S], quality threshold, read_callback code) or None, ``per_base``: the coverage as the table per position and base (the
-    pileup).  The struct keeps the contiguous arrays it points into alive; the rules are the library's to check."""
+    pileup), ``depth`` = (bin size, min_mapq, exclude_flags, count_deletions) or None: the binned-depth request.  The struct keeps the contiguous arrays it points into alive; the rules are the library's to check."""
     req = coral_bam_request_t(rank=rank, world=world, n_spans=-1, n_seg=-1, want_index=int(index), want_qc=int(qc), per_base=int(per_base))
     req.arrays = []
+    if depth is not None:
+        req.depth_bin, req.depth_min_mapq, req.depth_exclude_flags, req.depth_count_deletions = (int(v) for v in depth)
 
     def pointer(a, dtype):
         req.arrays.append(np.ascontiguousarray(a, dtype=dtype))
@@ -134,6 +137,8 @@ def lib():
     L.coral_bam_index_fill.argtypes = [C.c_void_p, P, P, P, P, P, C.POINTER(C.c_uint64)]
     L.coral_bam_qc_sizes.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
     L.coral_bam_qc_fill.argtypes = [C.c_void_p, P, P, P, P, P, C.POINTER(C.c_int64)]
+    L.coral_bam_depth_sizes.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+    L.coral_bam_depth_fill.argtypes = [C.c_void_p, P, P, P]
     L.coral_bamgpu_open_request.argtypes = [C.c_char_p, C.c_int32, C.c_int64, Q, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
     L.coral_bamgpu_finish.argtypes = [C.c_void_p, P]
     with open(os.path.join(os.path.dirname(_HERE), "include", "coral_hip.h")) as fp:

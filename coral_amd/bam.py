@@ -174,18 +174,21 @@ def decode_bam_gpu(path: str, device="cuda:0", n_threads: Optional[int] = None, 
 
 class DecodeResult(collections.namedtuple("DecodeResult", "records counts index qc")):
     """What _decode returns; what it was not asked for is None.  It unpacks as these four; the table of a pileup request
-    (uint32 [positions][4]) is the attribute ``pileup``."""
+    (uint32 [positions][4]) is the attribute ``pileup``, the result of a binned-depth request the attribute ``depth``
+    (bin_off int64 [contigs + 1], bases and reads int64 [bins])."""
     pileup = None
+    depth = None
 
 
 def _decode(path: str, device, *, n_threads: Optional[int] = None, rank: int = 0, world: int = 1, batch_bytes: int = 0, spans=None,
-            coverage=None, index=False, qc=False, records=True, per_base=False) -> DecodeResult:
+            coverage=None, index=False, qc=False, records=True, per_base=False, depth=None) -> DecodeResult:
     """One decode of the ``rank``-th of ``world`` byte ranges, or of the records that start inside ``spans`` (uint64 [K][2] virtual
     offsets), with what rides along: ``coverage`` = (segments int32 [3][S], quality threshold, read_callback code) gives the S
     int64 ``counts``, ``index`` the partial BAI index, ``qc`` the ``ReadQC``; ``records`` False leaves the Records out.  With
     ``per_base`` the coverage is counted per position and base: ``pileup`` is the uint32 table [positions of the segments, in
-    segment order][A, C, G, T] and ``counts`` its sums per segment.  On the GPU pipeline when ``_on_gpu(device)``, else on the host."""
-    req = _lib.bam_request(rank, world, spans, coverage, index, qc, per_base)
+    segment order][A, C, G, T] and ``counts`` its sums per segment.  ``depth`` = (bin size, min_mapq, exclude_flags,
+    count_deletions) gives the binned-depth tables (``binned_depth``).  On the GPU pipeline when ``_on_gpu(device)``, else on the host."""
+    req = _lib.bam_request(rank, world, spans, coverage, index, qc, per_base, depth)
     if _on_gpu(device):
         return _decode_gpu(path, device, n_threads, batch_bytes, req, records)
     L = _lib.lib()
@@ -226,6 +229,14 @@ def _result_from_handle(L, h, req, records: bool, cigar, cigar_words: int) -> De
     res = DecodeResult(_records_from_handle(L, h, cigar, cigar_words) if records else None, counts,
                        _index_partial_from_handle(L, h) if req.want_index else None, _read_qc_from_handle(L, h) if req.want_qc else None)
     res.pileup = table
+    if req.depth_bin:
+        sz = (C.c_int64 * 2)()
+        if L.coral_bam_depth_sizes(h, sz) != 0:
+            raise _lib.CoralHipError("coral_bam_depth_sizes failed: %s" % L.coral_bam_last_error().decode())
+        bin_off, bases, reads = np.zeros(int(sz[0]) + 1, dtype=np.int64), np.zeros(int(sz[1]), dtype=np.int64), np.zeros(int(sz[1]), dtype=np.int64)
+        if L.coral_bam_depth_fill(h, bin_off.ctypes.data, bases.ctypes.data, reads.ctypes.data) != 0:
+            raise _lib.CoralHipError("coral_bam_depth_fill failed: %s" % L.coral_bam_last_error().decode())
+        res.depth = (bin_off, bases, reads)
     return res
 
 
@@ -652,6 +663,122 @@ def merge_read_qc(parts: Sequence[ReadQC]) -> ReadQC:
     cat = lambda k: np.concatenate([getattr(p, k) for p in parts])
     return ReadQC(cat("length"), cat("qual_sum"), cat("mapq"), cat("flag"), np.sum([p.base_quality_hist for p in parts], axis=0),
                   {k: sum(p.counters[k] for p in parts) for k in QC_COUNTERS})
+
+
+# ----------------------------------------------------------------------------------------------
+# binned depth: read depth per fixed-size bin of every contig, counted during the decode
+# ----------------------------------------------------------------------------------------------
+DEPTH_MAX_BINS = 1 << 28
+
+
+class BinnedDepth:
+    """Read depth summed into bins of ``bin_size`` bases along every contig of the header - the per-bin table a copy-number
+    caller starts from (the reference's scripts/call_cnvs.sh runs CNVkit for it).  ``chroms`` / ``lengths``: the header's
+    contigs; contig c has ceil(length / bin_size) bins, the last one ending at the contig's length.  ``bases(c)``: reference
+    positions of the bin covered by M / = / X ops (and D ops with ``count_deletions``), summed over the records that take part
+    (``flag & exclude_flags == 0`` and ``mapq >= min_mapq``); ``reads(c)``: such records that start in the bin.  int64, exact."""
+
+    def __init__(self, chroms, lengths, bin_size, min_mapq, exclude_flags, count_deletions, bin_off, bases, reads):
+        self.chroms, self.lengths = list(chroms), [max(int(l), 0) for l in lengths]
+        self.bin_size, self.min_mapq, self.exclude_flags, self.count_deletions = int(bin_size), int(min_mapq), int(exclude_flags), bool(count_deletions)
+        self.bin_off = np.ascontiguousarray(bin_off, dtype=np.int64)
+        self.all_bases = np.ascontiguousarray(bases, dtype=np.int64)
+        self.all_reads = np.ascontiguousarray(reads, dtype=np.int64)
+        want = np.concatenate([[0], np.cumsum([(l + self.bin_size - 1) // self.bin_size for l in self.lengths], dtype=np.int64)])
+        if not np.array_equal(self.bin_off, want) or len(self.all_bases) != want[-1] or len(self.all_reads) != want[-1]:
+            raise ValueError("BinnedDepth: the tables do not fit the contigs and the bin size")
+        self._tid = {c: k for k, c in enumerate(self.chroms)}
+
+    @property
+    def params(self):
+        return (self.bin_size, self.min_mapq, self.exclude_flags, self.count_deletions)
+
+    @property
+    def n_bins(self) -> int:
+        return int(self.bin_off[-1])
+
+    def _rows(self, chrom):
+        if chrom not in self._tid:
+            raise KeyError("unknown contig %r" % (chrom,))
+        t = self._tid[chrom]
+        return slice(int(self.bin_off[t]), int(self.bin_off[t + 1])), self.lengths[t]
+
+    def bases(self, chrom) -> np.ndarray:
+        return self.all_bases[self._rows(chrom)[0]]
+
+    def reads(self, chrom) -> np.ndarray:
+        return self.all_reads[self._rows(chrom)[0]]
+
+    def bins(self, chrom):
+        """(starts, ends) int64 of the contig's bins; the last bin ends at the contig's length."""
+        rows, length = self._rows(chrom)
+        starts = np.arange(rows.stop - rows.start, dtype=np.int64) * self.bin_size
+        return starts, np.minimum(starts + self.bin_size, length)
+
+    def mean_depth(self, chrom) -> np.ndarray:
+        """bases / bin length as float64 (the short last bin divided by its own length)."""
+        starts, ends = self.bins(chrom)
+        return self.bases(chrom).astype(np.float64) / (ends - starts).astype(np.float64)
+
+    def write(self, path: str) -> str:
+        """Tab-separated, one row per bin in header order, with the columns CNVkit documents for its .cnn files: chromosome,
+        start, end, gene ('-'), depth (the mean depth), log2 (log2 of the depth; -20 for a depth of 0), plus reads."""
+        with open(path, "w", newline="") as fp:
+            fp.write("chromosome\tstart\tend\tgene\tdepth\tlog2\treads\n")
+            for c in self.chroms:
+                (starts, ends), depth, reads = self.bins(c), self.mean_depth(c), self.reads(c)
+                log2 = np.full(len(depth), -20.0)
+                np.log2(depth, out=log2, where=depth > 0)
+                fp.write("".join("%s\t%d\t%d\t-\t%r\t%r\t%d\n" % (c, a, b, d, l, r)
+                                 for a, b, d, l, r in zip(starts.tolist(), ends.tolist(), depth.tolist(), log2.tolist(), reads.tolist())))
+        return path
+
+
+def depth_parameters(bin_size, min_mapq, exclude_flags, count_deletions):
+    """The parameters of a binned-depth request as ints, or ValueError: bin_size >= 1, min_mapq 0..255, exclude_flags 0..0xffff."""
+    for name, v in (("bin_size", bin_size), ("min_mapq", min_mapq), ("exclude_flags", exclude_flags)):
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+            raise ValueError("%s must be an integer, got %r" % (name, v))
+    if not 1 <= bin_size <= _I32_MAX:
+        raise ValueError("bin_size must be at least 1, got %r" % (bin_size,))
+    if not 0 <= min_mapq <= 255:
+        raise ValueError("min_mapq must be in 0..255, got %r" % (min_mapq,))
+    if not 0 <= exclude_flags <= 0xffff:
+        raise ValueError("exclude_flags must be in 0..0xffff, got %r" % (exclude_flags,))
+    return int(bin_size), int(min_mapq), int(exclude_flags), 1 if count_deletions else 0
+
+
+def binned_depth(path: str, bin_size: int = 1000, min_mapq: int = 0, exclude_flags: int = 0x704, count_deletions: bool = True,
+                 device="cuda:0", rank: int = 0, world: int = 1, batch_bytes: int = 0, n_threads: Optional[int] = None) -> BinnedDepth:
+    """Read depth per bin of ``bin_size`` bases along every contig (``BinnedDepth``), counted while the BAM is decoded: only the
+    fixed fields and the CIGAR of a record are looked at, so a file without SEQ or QUAL serves as well.  A record takes part
+    when it has a contig, a position and a CIGAR, ``flag & exclude_flags == 0`` and ``mapq >= min_mapq``; M / = / X ops (and D
+    ops with ``count_deletions``) add their reference positions inside the contig to ``bases``, the record's start adds 1 to
+    ``reads``.  The defaults are meant to be ``samtools bedcov``'s (what CNVkit's WGS coverage runs); parity with samtools or
+    CNVkit is not pinned here, the rule is.  Bad parameters, or more than 2^28 bins, raise ValueError before
+    anything is decoded.  GPU pipeline (k_bam_depth per batch) on a GPU ``device``, host pipeline with ``device="cpu"`` or
+    ``CORAL_BAM_DECODE=cpu``; identical results.  With ``world`` > 1 the tables are those of the ``rank``-th byte range;
+    ``merge_binned_depth`` adds them."""
+    params = depth_parameters(bin_size, min_mapq, exclude_flags, count_deletions)
+    chroms, lengths = bam_reference_names(path), bam_reference_lengths(path)
+    n_bins = sum((max(l, 0) + params[0] - 1) // params[0] for l in lengths)
+    if n_bins > DEPTH_MAX_BINS:
+        raise ValueError("bins of %d bases make %d bins of this header: a binned-depth request takes at most 2^28" % (params[0], n_bins))
+    res = _decode(path, device, n_threads=n_threads, rank=rank, world=world, batch_bytes=batch_bytes, records=False, depth=params)
+    return BinnedDepth(chroms, lengths, *params, *res.depth)
+
+
+def merge_binned_depth(parts: Sequence[BinnedDepth]) -> BinnedDepth:
+    """The tables of byte ranges decoded by several ranks, added.  The parts must have the same header and parameters."""
+    parts = list(parts)
+    if not parts:
+        raise ValueError("merge_binned_depth needs at least one part")
+    first = parts[0]
+    for p in parts[1:]:
+        if p.params != first.params or p.chroms != first.chroms or p.lengths != first.lengths:
+            raise ValueError("merge_binned_depth: the parts do not have the same header and parameters")
+    return BinnedDepth(first.chroms, first.lengths, *first.params, first.bin_off, np.sum([p.all_bases for p in parts], axis=0),
+                       np.sum([p.all_reads for p in parts], axis=0))
 
 
 # ----------------------------------------------------------------------------------------------

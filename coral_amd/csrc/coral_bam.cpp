@@ -93,6 +93,11 @@ bool decode_file(const char *path, int n_threads, const Request &R, const Span *
     const int32_t n_ref = (int32_t)D.ref_names.size();
     if (want_index) D.idx.init(D.ref_lens);
     if (want_qc) D.qc.init();
+    if (R.depth_bin > 0) {                     // (never on a span decode: this is the decode's one call)
+        if (!D.depth.init(R.depth_bin, R.depth_min_mapq, R.depth_exclude_flags, R.depth_count_deletions, D.ref_lens, D.error)) { D.bad_request = true; return false; }
+        D.depth.zero_tables();
+    }
+    DepthPartial *depth = D.depth.on ? &D.depth : nullptr;
     // ---- block table: the blocks that START inside this rank's byte range, plus an overhang for the last record
     const uint64_t byte_lo = rank == 0 ? 0 : f.size / (uint64_t)world * (uint64_t)rank;
     const uint64_t byte_hi = rank == world - 1 ? f.size : f.size / (uint64_t)world * (uint64_t)(rank + 1);
@@ -173,7 +178,7 @@ bool decode_file(const char *path, int n_threads, const Request &R, const Span *
             if (want_qc) pt.qc_hist.assign(256, 0);              // the chunk's partial histogram, likewise
             for (size_t s : c->starts) {
                 const uint8_t *q = c->buf.data() + s;
-                if (!decode_record(q + 4, rd32(q), ref_id, pt, pt.error, cov, want_qc, D.pileup.data())) break;
+                if (!decode_record(q + 4, rd32(q), ref_id, pt, pt.error, cov, want_qc, D.pileup.data(), depth)) break;
             }
             std::vector<uint8_t>().swap(c->buf);            // SEQ / QUAL bytes are gone from here on
             c->parsed.set();
@@ -511,7 +516,7 @@ extern "C" int coral_bam_decode_request(const char *path, int32_t n_threads, con
     }
     if (!ok) {
         g_bam_err = D->error;
-        return CORAL_ERR_FORMAT;
+        return D->bad_request ? CORAL_ERR_ARG : CORAL_ERR_FORMAT;
     }
     if (D->has_pileup) pileup_segment_sums(R.cov, D->pileup.data(), D->cov);
     *handle = D.release();
@@ -574,6 +579,29 @@ extern "C" int coral_bam_qc_fill(void *handle, int32_t *length, int64_t *qual_su
         ++r;
     }
     memcpy(hist, D->qc.hist, sizeof(D->qc.hist));
+    return CORAL_OK;
+}
+
+// The binned-depth request of a handle (either pipeline): sizes = contigs, bins; fill = bin_off (n_ref + 1) and the two tables.
+extern "C" int coral_bam_depth_sizes(void *handle, int64_t sizes[2]) {
+    if (!handle || !sizes) return CORAL_ERR_ARG;
+    const DepthPartial &P = ((Decoded *)handle)->depth;
+    if (!P.on) { g_bam_err = "coral_bam_depth_sizes: the handle holds no binned-depth request"; return CORAL_ERR_ARG; }
+    sizes[0] = (int64_t)P.len.size();
+    sizes[1] = P.n_bins();
+    return CORAL_OK;
+}
+
+extern "C" int coral_bam_depth_fill(void *handle, int64_t *bin_off, int64_t *bases, int64_t *reads) {
+    if (!handle || !bin_off) return CORAL_ERR_ARG;
+    const DepthPartial &P = ((Decoded *)handle)->depth;
+    if (!P.on || (int64_t)P.bases.size() != P.n_bins()) { g_bam_err = "coral_bam_depth_fill: the handle holds no binned-depth request"; return CORAL_ERR_ARG; }
+    if (P.n_bins() > 0 && (!bases || !reads)) return CORAL_ERR_ARG;
+    memcpy(bin_off, P.bin_off.data(), P.bin_off.size() * 8);
+    if (P.n_bins() > 0) {
+        memcpy(bases, P.bases.data(), P.bases.size() * 8);
+        memcpy(reads, P.reads.data(), P.reads.size() * 8);
+    }
     return CORAL_OK;
 }
 

@@ -153,6 +153,77 @@ struct QcPartial {
     }
 };
 
+// A binned-depth request (depth_bin > 0 of a coral_bam_request_t): read depth summed into fixed-size bins along every contig of
+// the header, the one pass over the alignments behind the reference's scripts/call_cnvs.sh:12-17 (cnvkit.py batch --seq-method
+// wgs: CNVkit's `coverage`).  Contig t of length LN[t] has ceil(LN[t] / bin) bins (none for a length of 0), bin_off is their
+// exclusive prefix sum in tid order.  The rules both pipelines share:
+//   a record TAKES PART when 0 <= tid < n_ref, pos >= 0, its real CIGAR (CG:B,I for the placeholder) has an op,
+//   flag & exclude_flags == 0 and mapq >= min_mapq (depth_takes_part); SEQ and QUAL are not looked at, and flag 0x4 only
+//   matters through exclude_flags;
+//   bases[bin_off[tid] + x / bin] += 1 for every reference position x < LN[tid] covered by an M, = or X op, and by a D op with
+//   count_deletions (depth_counts_op); N, I, S, H, P and zero-length ops add nothing; positions at or behind LN[tid] are dropped;
+//   reads[bin_off[tid] + pos / bin] += 1 for every record that takes part and has pos < LN[tid].
+// int64, exact: the tables do not depend on scheduling, batch size or rank count, and tables of byte ranges add up.
+const int64_t DEPTH_MAX_BINS = 1ll << 28;
+
+CORAL_QC_HD inline bool depth_takes_part(int32_t tid, int32_t pos, uint32_t n_ops, uint32_t flag, uint32_t mapq, int32_t n_ref,
+                                         uint32_t exclude_flags, uint32_t min_mapq) {
+    return tid >= 0 && tid < n_ref && pos >= 0 && n_ops > 0 && (flag & exclude_flags) == 0 && mapq >= min_mapq;
+}
+CORAL_QC_HD inline bool depth_counts_op(uint32_t op, bool count_deletions) {      // M = X, and D on request
+    return ((0x181u >> op) & 1u) != 0 || (op == 2u && count_deletions);
+}
+
+struct DepthPartial {
+    bool on = false;
+    int32_t bin = 0, min_mapq = 0, exclude_flags = 0;
+    bool count_deletions = false;
+    std::vector<int32_t> len;               // LN per contig (a negative one counts as 0)
+    std::vector<int64_t> bin_off;           // n_ref + 1
+    std::vector<int64_t> bases, reads;      // n_bins each (filled by the decode)
+    int64_t n_bins() const { return bin_off.empty() ? 0 : bin_off.back(); }
+    // the bins of the header's contigs; false (nothing allocated): more than 2^28 of them
+    bool init(int32_t bin_, int32_t min_mapq_, int32_t exclude_, bool count_del, const std::vector<int32_t> &ref_lens, std::string &err) {
+        bin = bin_; min_mapq = min_mapq_; exclude_flags = exclude_; count_deletions = count_del;
+        len.clear();
+        bin_off.assign(1, 0);
+        for (int32_t l : ref_lens) {
+            len.push_back(l > 0 ? l : 0);
+            bin_off.push_back(bin_off.back() + ((int64_t)len.back() + bin - 1) / bin);
+        }
+        if (n_bins() > DEPTH_MAX_BINS) { err = "binned-depth request: the contigs hold more than 2^28 bins of this size"; return false; }
+        on = true;
+        return true;
+    }
+    void zero_tables() {
+        bases.assign((size_t)n_bins(), 0);
+        reads.assign((size_t)n_bins(), 0);
+    }
+    // One record into the tables (host pipeline; ops = the real CIGAR, CG tag already resolved).  The tables are shared by the
+    // threads that parse chunks, hence the relaxed atomic adds: one per op and bin it covers.
+    void add(int32_t tid, int32_t pos, uint32_t flag, uint32_t mapq, const uint32_t *ops, uint32_t n_ops) {
+        if (!depth_takes_part(tid, pos, n_ops, flag, mapq, (int32_t)len.size(), (uint32_t)exclude_flags, (uint32_t)min_mapq)) return;
+        const int64_t ln = len[(size_t)tid];
+        if (pos >= ln) return;
+        int64_t *b = bases.data() + bin_off[(size_t)tid];
+        __atomic_fetch_add(reads.data() + bin_off[(size_t)tid] + pos / bin, (int64_t)1, __ATOMIC_RELAXED);
+        int64_t r = pos;
+        for (uint32_t k = 0; k < n_ops && r < ln; ++k) {
+            const uint32_t op = ops[k] & 15;
+            const int64_t l = ops[k] >> 4;
+            if (depth_counts_op(op, count_deletions)) {
+                const int64_t e = std::min(r + l, ln);
+                for (int64_t x = r; x < e;) {
+                    const int64_t nx = std::min(e, (x / bin + 1) * bin);
+                    __atomic_fetch_add(b + x / bin, nx - x, __ATOMIC_RELAXED);
+                    x = nx;
+                }
+            }
+            if ((0x18Du >> op) & 1u) r += l;      // M D N = X advance the reference
+        }
+    }
+};
+
 // A span of virtual offsets [beg, end) (span_beg / span_end of a coral_bam_request_t): the records that START in it.
 struct Span {
     uint64_t beg = 0, end = 0;
@@ -161,6 +232,7 @@ struct Span {
 struct Decoded {
     IndexPartial idx;                       // BAI index request (empty without one)
     QcPartial qc;                           // read-QC request (empty without one)
+    DepthPartial depth;                     // binned-depth request (empty without one)
     std::vector<int32_t> tid, pos, end, flag, mapq, qlen, has_seq, nm, name_id, n_cigar;
     std::vector<int64_t> cigar_off{0}, sa_off{0};
     std::vector<uint32_t> cigar;
@@ -172,6 +244,7 @@ struct Decoded {
     std::vector<std::string> ref_names;
     std::vector<int32_t> ref_lens;
     std::string error;
+    bool bad_request = false;               // `error` is about the request, not the file (a rule that needs the header)
     // statistics of the decode (coral_bam_decode_stats)
     int64_t compressed_bytes = 0, uncompressed_bytes = 0, n_blocks = 0;
     double seconds = 0.0;
@@ -266,6 +339,8 @@ struct Request {
     bool has_cov = false;                   // a window-coverage request (it may have no segment)
     CovTable cov;
     bool want_index = false, want_qc = false;
+    int32_t depth_bin = 0, depth_min_mapq = 0, depth_exclude_flags = 0;      // a binned-depth request (depth_bin > 0; the bins need the header: DepthPartial::init)
+    bool depth_count_deletions = false;
     const CovTable *cov_table() const { return has_cov ? &cov : nullptr; }
 };
 
@@ -274,6 +349,17 @@ inline bool parse_request(const coral_bam_request_t *q, Request &R, std::string 
     if (!q) { err = "request: null pointer"; return false; }
     R.want_index = q->want_index != 0;
     R.want_qc = q->want_qc != 0;
+    if (q->depth_bin < 0) { err = "binned-depth request: depth_bin must be >= 1 (0: no request)"; return false; }
+    if (q->depth_bin > 0) {
+        if (q->depth_min_mapq < 0 || q->depth_min_mapq > 255) { err = "binned-depth request: min_mapq must be 0..255"; return false; }
+        if (q->depth_exclude_flags < 0 || q->depth_exclude_flags > 0xffff) { err = "binned-depth request: exclude_flags must be 0..0xffff"; return false; }
+        if (q->depth_count_deletions != 0 && q->depth_count_deletions != 1) { err = "binned-depth request: count_deletions must be 0 or 1"; return false; }
+        if (q->n_spans >= 0) { err = "request: a binned-depth request does not go with a span decode"; return false; }
+        R.depth_bin = q->depth_bin;
+        R.depth_min_mapq = q->depth_min_mapq;
+        R.depth_exclude_flags = q->depth_exclude_flags;
+        R.depth_count_deletions = q->depth_count_deletions != 0;
+    }
     if (q->n_spans >= 0) {
         if (q->n_spans > 0 && (!q->span_beg || !q->span_end)) { err = "request: bad span arrays"; return false; }
         if (R.want_index || R.want_qc) { err = "request: an index or read-QC request does not go with a span decode"; return false; }
@@ -462,8 +548,9 @@ inline bool all_acgt(const uint8_t *seq, uint32_t l_seq) {
 // Decode one BAM record (p points at refID, i.e. after block_size) into the partial.
 // With `cov`, the record's bases also go into o.cov (sized by the caller) or, for a pileup request, into `pileup` (the decode's table).
 // With `qc`, the record's qual_sum goes to o.qc_sum and its QUAL bytes into o.qc_hist (256 bins, sized by the caller).
+// With `depth`, the record goes into the tables of the binned-depth request (the decode's, shared by the parse tasks).
 inline bool decode_record(const uint8_t *p, uint32_t block_size, const RefIds &ref_id, Partial &o, std::string &err,
-                          const CovTable *cov = nullptr, bool qc = false, uint32_t *pileup = nullptr) {
+                          const CovTable *cov = nullptr, bool qc = false, uint32_t *pileup = nullptr, DepthPartial *depth = nullptr) {
     if (block_size < 32) { err = "record shorter than its fixed fields"; return false; }
     const int32_t refID = (int32_t)rd32(p), pos = (int32_t)rd32(p + 4);
     const uint32_t l_read_name = p[8], mapq = p[9];
@@ -546,6 +633,7 @@ inline bool decode_record(const uint8_t *p, uint32_t block_size, const RefIds &r
     }
     o.cigar_len.push_back((int64_t)padded);
     if (cov) count_record_coverage(*cov, refID, pos, flag, l_seq, dst, n_cigar_op, seq, qual, o.cov.data(), pileup);
+    if (depth) depth->add(refID, pos, flag, mapq, dst, n_cigar_op);
     if ((flag & 4) || n_cigar_op == 0) rlen = 0;                 // htslib bam_endpos
     o.tid.push_back(refID);
     o.pos.push_back(pos);

@@ -25,6 +25,7 @@
 //   k_bam_qc_plan + k_bam_qc           read QC: per read the sum of its QUAL bytes, and the 256-bin histogram of all of them
 //   k_bam_index + k_bam_index_compact  index: per record the virtual offset, the UCSC bin and the linear-index windows of a
 //                   BAI index, per batch the heads of the runs of equal (tid, bin)
+//   k_bam_depth     binned depth: per record one walk of its CIGAR, one 64-bit atomic per run of lanes in the same bin
 // Host: one struct per request (carve / start / batch / finish); what it may borrow of the parse's scratch: struct Borrowed.
 // Batches (64 MiB first, doubling up to 2.52 GiB inflated, coral_bamgpu_open) are double-buffered: while batch k is parsed, batch k + 1 is inflated
 // and k + 2 is read.
@@ -1369,6 +1370,89 @@ __global__ __launch_bounds__(WAVE) void k_bam_index_compact(long long n_rec, con
 }
 
 // ---------------------------------------------------------------------------------------------
+// K_depth: whole-genome binned read depth (depth_bin of the request; the rules: DepthPartial in coral_bam_common.h)
+// ---------------------------------------------------------------------------------------------
+struct DepthDev {                        // device arrays of the request, carved from the caller's workspace
+    long long *bin_off;                  // n_ref + 1: first bin of every contig
+    int32_t *len;                        // n_ref: LN (>= 0)
+    unsigned long long *bases, *reads;   // n_bins each
+    int n_ref;
+    uint32_t bin, min_mapq, exclude_flags;
+    int count_deletions;
+};
+
+// `key` does not decrease from lane to lane: the sum of `v` over every run of equal keys, in the run's first lane (a segmented
+// suffix sum by doubling; the other lanes of a run hold partial sums).
+__device__ __forceinline__ uint32_t depth_run_sum(uint32_t key, uint32_t v, int lane) {
+    for (int d = 1; d < WAVE; d <<= 1) {
+        const uint32_t tv = __shfl_down(v, d), tk = __shfl_down(key, d);
+        if (lane + d < WAVE && tk == key) v += tv;
+    }
+    return v;
+}
+
+// One wave per record (grid-stride), one-wave workgroups without LDS: it fits beside resident inflate waves.
+// Only the fixed fields and the real CIGAR (M.cig_src / M.n_cigar: the CG tag is resolved) are read.  The wave takes 64 ops at a
+// time; the wave prefix sum of the reference advance gives every lane its op's interval [a, e), clipped to the contig - so no bin
+// at or behind ceil(LN / bin) is ever addressed.  Ops come in increasing reference order, hence the lanes' bins do not decrease:
+//   first bin   every lane adds the part of its op inside the op's first bin b0; lanes with the same b0 are summed in the wave
+//               (an op that is not counted joins the run with 0) and the run's first lane issues ONE no-return 64-bit atomic;
+//   last bin    the same for the part inside the op's last bin b1, for the ops that cross a bin edge (rare unless bin is small);
+//   in between  the whole bins b0 + 1 .. b1 - 1 of such an op get `bin` each, 64 bins per step of the wave.
+// A run's sum fits 32 bits: the positions one record covers are disjoint, so a bin gets at most `bin` from it.
+// Atomics per record: the bins it touches (at most twice each) plus its 64-op chunks - not its ops.
+__global__ __launch_bounds__(WAVE) void k_bam_depth(const uint8_t *__restrict__ buf, long long n_rec, MetaArrays M, DepthDev X) {
+    const int lane = threadIdx.x;
+    const uint32_t bin = X.bin;
+    for (long long i = blockIdx.x; i < n_rec; i += gridDim.x) {
+        const int32_t tid = M.tid[i], pos = M.pos[i];
+        const int n_ops = M.n_cigar[i];
+        if (!depth_takes_part(tid, pos, (uint32_t)n_ops, (uint32_t)M.flag[i], (uint32_t)M.mapq[i], X.n_ref, X.exclude_flags, X.min_mapq)) continue;
+        const long long ln = X.len[tid];
+        if (pos >= ln) continue;                                       // (so ln >= 1 below)
+        const long long bo = X.bin_off[tid];
+        unsigned long long *bases = X.bases + bo;
+        if (lane == 0) atomicAdd(X.reads + bo + (uint32_t)pos / bin, 1ull);
+        const uint8_t *ops = buf + M.cig_src[i];
+        long long r_base = pos;
+        for (int c = 0; c < n_ops && r_base < ln; c += WAVE) {
+            const int kk = c + lane;
+            const uint32_t wd = kk < n_ops ? ld32(ops + 4ll * kk) : 15u;
+            const uint32_t op = wd & 15u;
+            const long long len = (long long)(wd >> 4);
+            const long long ra = ((0x18Du >> op) & 1u) ? len : 0;     // M D N = X advance the reference
+            long long rs = ra;
+            for (int d = 1; d < WAVE; d <<= 1) {
+                const long long t = __shfl_up(rs, d);
+                if (lane >= d) rs += t;
+            }
+            const uint32_t a = (uint32_t)min(r_base + rs - ra, ln), e = (uint32_t)min(r_base + rs, ln);      // 0 <= a <= e <= LN
+            const bool counted = depth_counts_op(op, X.count_deletions != 0) && e > a;
+            const uint32_t b0 = min(a, (uint32_t)ln - 1u) / bin, b1 = (max(e, 1u) - 1u) / bin;               // counted: b0 <= b1 < the contig's bins
+            const unsigned long long edge = ((unsigned long long)b0 + 1ull) * bin;
+            const uint32_t first = counted ? (uint32_t)(min((unsigned long long)e, edge) - a) : 0u;
+            const uint32_t last = counted && b1 > b0 ? (uint32_t)(e - (unsigned long long)b1 * bin) : 0u;
+            {
+                const uint32_t sum = depth_run_sum(b0, first, lane), prev = __shfl_up(b0, 1);
+                if ((lane == 0 || prev != b0) && sum) atomicAdd(bases + b0, (unsigned long long)sum);
+            }
+            if (__ballot(last != 0u) != 0ull) {
+                const uint32_t sum = depth_run_sum(b1, last, lane), prev = __shfl_up(b1, 1);
+                if ((lane == 0 || prev != b1) && sum) atomicAdd(bases + b1, (unsigned long long)sum);
+                unsigned long long m = __ballot(counted && b1 > b0 + 1u);
+                while (m) {
+                    const int j = __builtin_ctzll(m);
+                    m &= m - 1;
+                    const uint32_t k0 = __shfl(b0, j) + 1u, k1 = __shfl(b1, j);
+                    for (uint32_t k = k0 + (uint32_t)lane; k < k1; k += WAVE) atomicAdd(bases + k, (unsigned long long)bin);
+                }
+            }
+            r_base += __shfl(rs, WAVE - 1);
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
 inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -1413,9 +1497,10 @@ inline bool dev_get(void *dst, const void *src, size_t bytes) { return bytes == 
 
 // The per-record scratch of the parse that a request may WRITE, built in emit.  Why that is safe:
 // - k_bam_emit has finished with every array named here: the batch's host copies synchronised the stream behind it.
-// - The requests are queued on the caller's stream in the order coverage, read QC, index, so each runs behind the one in front.
+// - The requests are queued on the caller's stream in the order coverage, read QC, binned depth, index, so each runs behind the
+//   one in front.  Binned depth borrows nothing; it reads M.cig_src.
 //   Coverage and read QC use the same two arrays in turn.
-// - The index goes last because its out_key is M.cig_src, which the coverage walk reads.  What every request only READS: the
+// - The index goes last because its out_key is M.cig_src, which the coverage and the depth walk read.  What every request only READS: the
 //   fixed fields of M (tid .. n_cigar, seq_src), the record starts and the end positions.
 // - All of it is queued in front of ev_parsed and of the next batch's k_bam_meta, which refills the arrays on the same stream.
 struct GpuDecoder;
@@ -1545,6 +1630,38 @@ struct IndexRequest {
     }
 };
 
+struct DepthRequest {                // binned depth: bin_off, the contig lengths and the two int64 tables in the workspace
+    bool active = false;
+    DepthDev X{};
+    size_t n_bins = 0;
+    void carve(Carver &take, const DepthPartial &P) {
+        if (!active) return;
+        const size_t n_ref = P.len.size();
+        n_bins = (size_t)P.n_bins();
+        X.bin_off = (long long *)take((n_ref + 1) * 8);
+        X.len = (int32_t *)take(n_ref * 4);
+        X.bases = (unsigned long long *)take(n_bins * 8);
+        X.reads = (unsigned long long *)take(n_bins * 8);
+        X.n_ref = (int)n_ref;
+        X.bin = (uint32_t)P.bin; X.min_mapq = (uint32_t)P.min_mapq; X.exclude_flags = (uint32_t)P.exclude_flags;
+        X.count_deletions = P.count_deletions ? 1 : 0;
+    }
+    const char *start(const DepthPartial &P, hipError_t &e) const {
+        if (!active) return nullptr;
+        const size_t n_ref = (size_t)X.n_ref;
+        const bool ok = (e = hipMemcpy(X.bin_off, P.bin_off.data(), (n_ref + 1) * 8, hipMemcpyHostToDevice)) == hipSuccess &&
+                        (n_ref == 0 || (e = hipMemcpy(X.len, P.len.data(), n_ref * 4, hipMemcpyHostToDevice)) == hipSuccess) &&
+                        (n_bins == 0 || ((e = hipMemset(X.bases, 0, n_bins * 8)) == hipSuccess && (e = hipMemset(X.reads, 0, n_bins * 8)) == hipSuccess));
+        return ok ? nullptr : "binned-depth request set-up";
+    }
+    bool batch(GpuDecoder *G, hipStream_t stream, std::string &err) const;
+    bool finish(DepthPartial &P) const {
+        if (!active) return true;
+        P.zero_tables();
+        return dev_get(P.bases.data(), X.bases, n_bins * 8) && dev_get(P.reads.data(), X.reads, n_bins * 8);
+    }
+};
+
 struct GpuDecoder {
     MappedFile f;
     Decoded D;
@@ -1610,6 +1727,7 @@ struct GpuDecoder {
     CovRequest cov;
     QcRequest qc;
     IndexRequest idx;
+    DepthRequest depth;
     // span decode: the spans are decoded one after the other through the same batches
     std::vector<SpanDef> spans;
     int cur_span = 0;                         // the span the caller's thread is parsing
@@ -1694,6 +1812,15 @@ bool QcRequest::batch(GpuDecoder *G, hipStream_t stream, const Borrowed &S, std:
     if (!launched("read-QC", err)) return false;
     pending_n = n;
     return true;
+}
+
+// reads the slot's CIGAR bytes (M.cig_src: in front of the index request, which borrows that array)
+bool DepthRequest::batch(GpuDecoder *G, hipStream_t stream, std::string &err) const {
+    const long long n = G->cur_n_rec;
+    if (n == 0 || !active || n_bins == 0) return true;
+    // one wave per workgroup, grid-stride beyond 32 per CU
+    hipLaunchKernelGGL(k_bam_depth, dim3((unsigned)std::min<long long>(n, 8192)), dim3(WAVE), 0, stream, G->d_infl[G->k & 1], n, G->M, X);
+    return launched("binned depth", err);
 }
 
 // the batch's part of the index; also for a batch without records: the end state it leaves is the next batch's start
@@ -2007,6 +2134,7 @@ bool carve(GpuDecoder *G, void *ws, size_t bytes) {
     G->idx.carve(take, G->max_blocks, G->D.idx);
     G->qc.carve(take, nr);
     G->cov.carve(take);
+    G->depth.carve(take, G->D.depth);
     if (ws && take.used > bytes) return false;
     G->ws_bytes = take.used;
     return true;
@@ -2120,6 +2248,10 @@ extern "C" int coral_bamgpu_open_request(const char *path, int32_t n_threads, in
     G->cov.T = &G->req.cov;
     if ((G->idx.active = R.want_index)) G->D.idx.init(G->D.ref_lens);
     if ((G->qc.active = R.want_qc)) G->D.qc.init();
+    if (R.depth_bin > 0) {                     // the rule that needs the header: at most 2^28 bins (refused here, nothing allocated)
+        if (!G->D.depth.init(R.depth_bin, R.depth_min_mapq, R.depth_exclude_flags, R.depth_count_deletions, G->D.ref_lens, err)) { set_error(err); return CORAL_ERR_ARG; }
+        G->depth.active = true;
+    }
     // batch size: at most `batch_bytes` inflated, no more than the range can need.  Default 2.52 GiB = 6 x 6 912 BGZF blocks of
     // 65 280 bytes (htslib's block size): the inflate kernel keeps 27 one-wave workgroups per CU x 256 CUs resident, blocks of
     // equal size finish in rounds, and a batch that is a whole number of rounds has no part-filled last round; bigger batches
@@ -2153,13 +2285,15 @@ extern "C" int coral_bamgpu_open(const char *path, int32_t n_threads, int32_t ra
 }
 
 // Once every batch has been emitted: waits for `stream_` and leaves what was requested in the host-side result
-// (coral_bamgpu_host -> coral_bam_coverage_result, coral_bam_index_sizes / _fill, coral_bam_qc_sizes / _fill).
+// (coral_bamgpu_host -> coral_bam_coverage_result, coral_bam_index_sizes / _fill, coral_bam_qc_sizes / _fill,
+// coral_bam_depth_sizes / _fill).
 extern "C" int coral_bamgpu_finish(void *handle, void *stream_) {
     GpuDecoder *G = (GpuDecoder *)handle;
     if (!G) return CORAL_ERR_ARG;
     if (!G->finished || G->have_cur) { set_error("coral_bamgpu_finish: the decode is not finished"); return CORAL_ERR_ARG; }
-    if (!G->cov.active && !G->qc.active && !G->idx.active) return CORAL_OK;
-    if (hipStreamSynchronize((hipStream_t)stream_) != hipSuccess || !G->cov.finish(G->D) || !G->idx.finish(G->D.idx) || !G->qc.finish(G->D.qc)) {
+    if (!G->cov.active && !G->qc.active && !G->idx.active && !G->depth.active) return CORAL_OK;
+    if (hipStreamSynchronize((hipStream_t)stream_) != hipSuccess || !G->cov.finish(G->D) || !G->idx.finish(G->D.idx) || !G->qc.finish(G->D.qc) ||
+        !G->depth.finish(G->D.depth)) {
         set_error("coral_bamgpu_finish: copy of the requested results failed");
         return CORAL_ERR_HIP;
     }
@@ -2200,7 +2334,7 @@ extern "C" int coral_bamgpu_start(void *handle, void *workspace, int64_t workspa
     if ((e = hipStreamCreateWithFlags(&G->s_crc, hipStreamNonBlocking)) != hipSuccess) return bad("hipStreamCreate", e);
     G->t_alloc = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_alloc0).count();
     const char *what;
-    if ((what = G->idx.start(G->D.idx, e)) || (what = G->qc.start(e)) || (what = G->cov.start(e))) return bad(what, e);
+    if ((what = G->idx.start(G->D.idx, e)) || (what = G->qc.start(e)) || (what = G->cov.start(e)) || (what = G->depth.start(G->D.depth, e))) return bad(what, e);
     G->feeder = std::thread(feeder_main, G);
     G->worker = std::thread(worker_main, G);
     return CORAL_OK;
@@ -2486,7 +2620,8 @@ extern "C" int coral_bamgpu_emit(void *handle, uint32_t *cigar_dst, int64_t *cig
     }
     const Borrowed S{G->M.name_len, G->M.sa_len, (unsigned long long *)G->d_cig_off, (unsigned long long *)G->M.sa_src, G->M.pad_ops, G->d_name_off, G->d_sa_off, G->M.cig_src};
     std::string err;
-    if (!G->cov.batch(G, stream, S, err) || !G->qc.batch(G, stream, S, err) || !G->idx.batch(G, stream, S, err)) return fail(CORAL_ERR_HIP, err);
+    if (!G->cov.batch(G, stream, S, err) || !G->qc.batch(G, stream, S, err) || !G->depth.batch(G, stream, err) || !G->idx.batch(G, stream, S, err))
+        return fail(CORAL_ERR_HIP, err);
     // this buffer may be inflated into again (batch k + 2) once everything above has run
     if (hipEventRecord(G->ev_parsed[slot], stream) != hipSuccess) return fail(CORAL_ERR_HIP, "hipEventRecord failed");
     {

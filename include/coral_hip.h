@@ -387,8 +387,10 @@ const char *coral_bam_last_error(void);
  * during the open call and not kept.  Every rule is checked by both pipelines alike (CORAL_ERR_ARG, coral_bam_last_error says
  * why): world >= 1 and 0 <= rank < world; spans sorted, disjoint, non-empty and inside the file; segments sorted by (tid,
  * start), disjoint, 0 <= start <= end; quality_threshold 0..255; read_callback 0 or 1; no want_index / want_qc on a span
- * decode; per_base only with segments (n_seg >= 0) of at most 2^28 positions in all.  A span decode is not sharded: rank and
- * world are taken as 0 and 1. */
+ * decode; per_base only with segments (n_seg >= 0) of at most 2^28 positions in all; depth_bin >= 0, and with depth_bin > 0:
+ * depth_min_mapq 0..255, depth_exclude_flags 0..0xffff, depth_count_deletions 0 or 1, no span decode, at most 2^28 bins over
+ * the header's contigs (checked once the header is read: refused before anything is decoded or allocated).  A span decode is
+ * not sharded: rank and world are taken as 0 and 1. */
 typedef struct {
     int32_t rank, world;                       /* byte range (ignored when n_spans >= 0) */
     int32_t n_spans;                           /* -1: the byte range; >= 0: only records starting inside these spans */
@@ -398,10 +400,12 @@ typedef struct {
     int32_t quality_threshold, read_callback;
     int32_t want_index, want_qc;
     int32_t per_base;                          /* 0: counts per segment; else: the table per position and base (pileup) */
+    int32_t depth_bin;                         /* 0: no binned-depth request; >= 1: the bin size */
+    int32_t depth_min_mapq, depth_exclude_flags, depth_count_deletions;
 } coral_bam_request_t;
 /* coral_bam_decode_range with a request; the results that ride along are read from the handle (of this call, or of
- * coral_bamgpu_host) with coral_bam_coverage_result, coral_bam_pileup_result, coral_bam_index_sizes / _fill and
- * coral_bam_qc_sizes / _fill.
+ * coral_bamgpu_host) with coral_bam_coverage_result, coral_bam_pileup_result, coral_bam_index_sizes / _fill,
+ * coral_bam_qc_sizes / _fill and coral_bam_depth_sizes / _fill.
  *
  * Spans (n_spans >= 0) - replaces htslib's hts_itr_query + bgzf_seek behind every lr_bamfh.count_coverage(chrom, w, w + window,
  * ...) of /root/reference/src/plot_amplicons.py:399-409: the records that START inside n_spans spans [span_beg, span_end) of
@@ -451,7 +455,21 @@ typedef struct {
  *          -1 without quality), mapq and flag; hist[256] = count of every QUAL byte value over the reads with quality;
  *          counters = records, reads, records with flag 0x100, with flag 0x800, reads with flag 0x4, primary records
  *          without SEQ, reads without quality, bases of all reads.  Integers only: mean quality of a read is
- *          qual_sum / length on the host.  Results of consecutive byte ranges concatenate / add up. */
+ *          qual_sum / length on the host.  Results of consecutive byte ranges concatenate / add up.
+ *
+ * Binned depth (depth_bin > 0) - replaces the one pass over the alignments behind the reference's scripts/call_cnvs.sh:12-17
+ * (cnvkit.py batch --seq-method wgs; CNVkit's `coverage` sums depth into fixed-size bins along every contig), which yields the
+ * --cn_seg file `seed` and `reconstruct` need; segmentation and normalisation stay the CN caller's.  Contig t of the header, of
+ * length LN[t], has ceil(LN[t] / depth_bin) bins (a length of 0: none); bin_off is their exclusive prefix sum in tid order,
+ * n_bins = bin_off[n_ref] <= 2^28.  A record takes part when 0 <= tid < n_ref, pos >= 0, its real CIGAR (CG:B,I for the
+ * placeholder) has an op, flag & depth_exclude_flags == 0 and mapq >= depth_min_mapq; SEQ and QUAL are not looked at, and a
+ * record with flag 0x4 that is not excluded has its CIGAR walked all the same.
+ *   bases[bin_off[tid] + x / depth_bin] += 1 for every reference position x < LN[tid] covered by an M, = or X op, and by a D op
+ *          when depth_count_deletions is 1; N, I, S, H, P and zero-length ops add nothing, positions at or behind LN[tid] are
+ *          dropped; position arithmetic is 64-bit.
+ *   reads[bin_off[tid] + pos / depth_bin] += 1 for every record that takes part and has pos < LN[tid].
+ *   depth_sizes -> n_ref, n_bins; depth_fill copies bin_off (n_ref + 1 int64) and the two int64 tables (n_bins each).  Exact
+ *          integers, independent of scheduling, batch size and rank count; tables of byte ranges add up. */
 int coral_bam_decode_request(const char *path, int32_t n_threads, const coral_bam_request_t *req, void **handle);
 int coral_bam_coverage_result(void *handle, int32_t n_seg, int64_t *counts);
 int coral_bam_pileup_result(void *handle, int64_t n_pos, uint32_t *counts);
@@ -461,6 +479,8 @@ int coral_bam_index_fill(void *handle, int64_t *head_key, uint64_t *head_voff, u
 int coral_bam_qc_sizes(void *handle, int64_t sizes[2]);
 int coral_bam_qc_fill(void *handle, int32_t *length, int64_t *qual_sum, int32_t *mapq, int32_t *flag, int64_t hist[256],
                       int64_t counters[8]);
+int coral_bam_depth_sizes(void *handle, int64_t sizes[2]);
+int coral_bam_depth_fill(void *handle, int64_t *bin_off, int64_t *bases, int64_t *reads);
 
 /* ------------------------------------------------------------------------------------------------
  * coral_bamgpu_* — the same decode with the inflate and the record parsing ON THE GPU: the host reads the file and sends
@@ -501,9 +521,13 @@ int coral_bam_qc_fill(void *handle, int32_t *length, int64_t *qual_sum, int32_t 
  *            want_qc     k_bam_qc_plan, one scan and k_bam_qc read the batch's QUAL before the slot is reused (one wave per
  *                      16 384 QUAL bytes of a read, aligned 16-byte loads, one 64-bit atomic per work item, the histogram in
  *                      LDS per workgroup)
+ *            depth_bin   k_bam_depth walks the batch's CIGARs before the slot is reused (one wave per record in one-wave
+ *                      workgroups without LDS, 64 ops at a time; lanes that hit the same bin are summed in the wave and the
+ *                      run's head issues one no-return 64-bit atomic, an op that spans whole bins is spread over them by
+ *                      the wave); bin_off, the contig lengths and the two int64 tables live in the workspace, zeroed by `start`
  *   finish        after the last batch (CORAL_ERR_ARG before): waits for `stream` once and leaves what was requested in the
  *          handle of `host` (coral_bam_coverage_result, coral_bam_pileup_result - the table is copied and summed per segment
- *          here -, coral_bam_index_sizes / _fill, coral_bam_qc_sizes / _fill); fails when
+ *          here -, coral_bam_index_sizes / _fill, coral_bam_qc_sizes / _fill, coral_bam_depth_sizes / _fill); fails when
  *          an index was requested and the records are not in coordinate order; with nothing requested it does nothing
  * coral_bgzf_inflate: one inflate launch over caller-provided device buffers — desc = n_blocks x {src_off, src_len,
  * dst_off, isize} uint32 (raw DEFLATE streams in `comp`, which must be readable 4096 bytes beyond the last stream);

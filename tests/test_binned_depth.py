@@ -1,0 +1,462 @@
+"""Whole-genome binned read depth counted during the BAM decode (bam.binned_depth, the `depth` mode): both pipelines against an
+INDEPENDENT restatement of the rule in this module.  The BAM is read with gzip + struct, the CG tag resolved, the CIGAR walked in
+plain Python and both tables filled with np.add.at.  Everything is exact integer equality.  (Neither samtools bedcov nor CNVkit
+can be run here: parity with them is not pinned; what is pinned is the rule.)"""
+import ctypes as C
+import gzip
+import math
+import struct
+
+import numpy as np
+import pytest
+import torch
+
+from coral_amd import _lib, bam, synth
+from coral_amd import CoRAL
+
+M, I, D, N, S, H, P, EQ, X = range(9)
+PIPELINES = ["host", pytest.param("gpu", marks=pytest.mark.gpu)]
+DEVICE = {"host": "cpu", "gpu": "cuda:0"}
+CORAL_OK, CORAL_ERR_ARG = 0, -1
+BIN_SIZES = (1, 7, 1000, 1 << 20)              # the last one is larger than every contig
+MIN_MAPQS = (0, 20, 255)
+EXCLUDES = (0, 0x704, 0x904)
+# the header: a length that is a multiple of 7 and of 1000, one that is of neither, an empty contig, one no read touches, a long one
+CHROMS = ["even", "odd", "empty", "untouched", "long"]
+LENGTHS = [7000, 5003, 0, 3000, 200_003]
+HOT_POS, HOT_LEN, HOT_DEPTH = 2000, 200, 2000
+MAPQ_CYCLE = (0, 19, 20, 255)
+
+
+@pytest.fixture(autouse=True)
+def _pipeline_by_device(monkeypatch):
+    monkeypatch.delenv("CORAL_BAM_DECODE", raising=False)
+
+
+# ---- the restatement -----------------------------------------------------------------------------------------------------------
+def read_bam(path):
+    """(ref names, ref lengths, [record dicts]) straight from the bytes: tid, pos, flag, mapq, name, l_seq, the first QUAL byte and
+    the real CIGAR (CG:B,I for the placeholder) as (op, len) pairs."""
+    raw = gzip.open(path, "rb").read()
+    assert raw[:4] == b"BAM\x01"
+    o = 8 + struct.unpack_from("<i", raw, 4)[0]
+    refs, lens = [], []
+    n_ref = struct.unpack_from("<i", raw, o)[0]
+    o += 4
+    for _ in range(n_ref):
+        ln = struct.unpack_from("<i", raw, o)[0]
+        refs.append(raw[o + 4:o + 4 + ln - 1].decode())
+        lens.append(struct.unpack_from("<i", raw, o + 4 + ln)[0])
+        o += 8 + ln
+    recs = []
+    while o < len(raw):
+        bs, tid, pos, l_name, mapq, _bin, n_cig, flag, l_seq = struct.unpack_from("<iiiBBHHHi", raw, o)
+        name = raw[o + 36:o + 36 + l_name - 1].decode()
+        p = o + 36 + l_name
+        ops = list(struct.unpack_from("<%dI" % n_cig, raw, p))
+        p += 4 * n_cig + (l_seq + 1) // 2
+        qual0 = raw[p] if l_seq else None
+        p += l_seq
+        end = o + 4 + bs
+        while p < end:                                    # tags: only CG:B,I matters here
+            key, ty = raw[p:p + 2], chr(raw[p + 2])
+            p += 3
+            if ty in "AcC":
+                p += 1
+            elif ty in "sS":
+                p += 2
+            elif ty in "iIf":
+                p += 4
+            elif ty in "ZH":
+                p = raw.index(b"\0", p) + 1
+            else:
+                sub, cnt = chr(raw[p]), struct.unpack_from("<I", raw, p + 1)[0]
+                size = {"c": 1, "C": 1, "s": 2, "S": 2}.get(sub, 4)
+                if key == b"CG" and sub == "I" and len(ops) == 2 and ops[0] & 15 == S and ops[0] >> 4 == l_seq and ops[1] & 15 == N:
+                    ops = list(struct.unpack_from("<%dI" % cnt, raw, p + 5))
+                p += 5 + size * cnt
+        recs.append(dict(tid=tid, pos=pos, flag=flag, mapq=mapq, name=name, l_seq=l_seq, qual0=qual0, ops=[(w & 15, w >> 4) for w in ops]))
+        o = end
+    return refs, lens, recs
+
+
+def covered_positions(rec, length):
+    """(positions of the M / = / X ops, positions of the D ops) of one record, below the contig's length."""
+    aligned, deleted = [np.zeros(0, dtype=np.int64)], [np.zeros(0, dtype=np.int64)]
+    ref = rec["pos"]
+    for op, ln in rec["ops"]:
+        if op in (M, EQ, X, D) and ln and ref < length:
+            (deleted if op == D else aligned).append(np.arange(ref, min(ref + ln, length), dtype=np.int64))
+        ref += ln if op in (M, D, N, EQ, X) else 0
+    return np.concatenate(aligned), np.concatenate(deleted)
+
+
+class Restatement:
+    """The rule of the issue, restated: the two int64 tables for any parameters (cached: both pipelines ask for the same ones)."""
+
+    def __init__(self, path):
+        self.refs, self.lens, self.recs = read_bam(path)
+        self.lens = [max(l, 0) for l in self.lens]
+        n_ref = len(self.refs)
+        self.candidates = [r for r in self.recs if 0 <= r["tid"] < n_ref and r["pos"] >= 0 and len(r["ops"]) >= 1]
+        self.covered = [covered_positions(r, self.lens[r["tid"]]) for r in self.candidates]
+        self.cache = {}
+
+    def bin_off(self, bin_size):
+        return np.concatenate([[0], np.cumsum([-(-l // bin_size) for l in self.lens])]).astype(np.int64)
+
+    def tables(self, bin_size, min_mapq, exclude_flags, count_deletions):
+        key = (bin_size, min_mapq, exclude_flags, bool(count_deletions))
+        if key not in self.cache:
+            off = self.bin_off(bin_size)
+            bases, reads = np.zeros(off[-1], dtype=np.int64), np.zeros(off[-1], dtype=np.int64)
+            where, starts = [np.zeros(0, dtype=np.int64)], []
+            for r, (aligned, deleted) in zip(self.candidates, self.covered):
+                if r["flag"] & exclude_flags or r["mapq"] < min_mapq:
+                    continue
+                where.append(off[r["tid"]] + aligned // bin_size)
+                if count_deletions:
+                    where.append(off[r["tid"]] + deleted // bin_size)
+                if r["pos"] < self.lens[r["tid"]]:
+                    starts.append(off[r["tid"]] + r["pos"] // bin_size)
+            np.add.at(bases, np.concatenate(where), 1)
+            np.add.at(reads, np.array(starts, dtype=np.int64), 1)
+            self.cache[key] = (off, bases, reads)
+        return self.cache[key]
+
+
+# ---- test data -----------------------------------------------------------------------------------------------------------------
+def many_ops(n):
+    """A CIGAR of exactly n >= 16 ops: leading H and S, every op of M I D N S H P = X, zero-length ops in between."""
+    cycle = [(M, 5), (I, 2), (M, 0), (D, 3), (EQ, 4), (X, 1), (I, 0), (N, 7), (P, 2), (M, 6), (D, 0)]
+    ops = [(H, 3), (S, 4)]
+    while len(ops) < n - 3:
+        ops.append(cycle[(len(ops) - 2) % len(cycle)])
+    return ops + [(M, 9), (S, 2), (H, 1)]
+
+
+def odd_records(with_no_seq):
+    alns = [
+        # contig "even" (7000 = 7 x 1000): bin edges, ops that cross several bins, the flags, reads at and past the contig's end
+        dict(tid=0, pos=0, cigar=[(M, 1000)], name="ends_on_edge"),
+        dict(tid=0, pos=1, cigar=[(M, 998)], name="ends_before_edge"),
+        dict(tid=0, pos=2, cigar=[(M, 999)], name="ends_after_edge"),
+        dict(tid=0, pos=500, cigar=[(S, 2), (M, 3500)], name="long_m", mapq=0),
+        dict(tid=0, pos=600, cigar=[(M, 10), (D, 2500), (M, 10)], name="long_d", mapq=19),
+        dict(tid=0, pos=700, cigar=[(M, 300)], flag=0x4, name="unmapped", mapq=20),
+        dict(tid=0, pos=710, cigar=[(M, 300)], flag=0x100, name="secondary", mapq=255),
+        dict(tid=0, pos=720, cigar=[(M, 150), (D, 5), (M, 150)], flag=0x200, name="qcfail", mapq=20),
+        dict(tid=0, pos=730, cigar=[(M, 300)], flag=0x400, name="duplicate", mapq=19),
+        dict(tid=0, pos=740, cigar=[(M, 300)], flag=0x800, name="supplementary", mapq=255),
+        dict(tid=0, pos=750, cigar=[(M, 300)], flag=0x10, name="reverse", mapq=0),
+        dict(tid=0, pos=760, cigar=[], name="no_cigar"),
+        dict(tid=0, pos=6900, cigar=[(M, 40), (D, 30), (M, 230)], name="past_the_end"),
+        dict(tid=0, pos=6999, cigar=[(M, 1)], name="last_base"),
+        dict(tid=0, pos=7000, cigar=[(M, 50)], name="starts_at_the_end"),
+        dict(tid=0, pos=7100, cigar=[(M, 50)], name="starts_behind_the_end"),
+        # contig "odd" (5003): the CIGAR lengths around the 64-op chunk, the stack of reads in one bin, the short last bin
+        dict(tid=1, pos=10, cigar=[(M, 50)], name="ops1"),
+        dict(tid=1, pos=100, cigar=many_ops(63), name="ops63", mapq=19),
+        dict(tid=1, pos=110, cigar=many_ops(64), name="ops64", mapq=20),
+        dict(tid=1, pos=120, cigar=many_ops(65), name="ops65", mapq=255),
+        dict(tid=1, pos=130, cigar=many_ops(128), name="ops128", mapq=0),
+        dict(tid=1, pos=140, cigar=many_ops(129), name="ops129"),
+        dict(tid=1, pos=150, cigar=[(M, 80)], name="noqual"),
+    ]
+    if with_no_seq:
+        alns.append(dict(tid=1, pos=160, cigar=[(M, 200), (D, 7), (M, 30)], has_seq=0, name="noseq"))
+    alns += [dict(tid=1, pos=HOT_POS, cigar=[(M, HOT_LEN)], name="hot%d" % k, mapq=MAPQ_CYCLE[k % 4]) for k in range(HOT_DEPTH)]
+    alns += [
+        dict(tid=1, pos=4990, cigar=[(M, 5), (N, 4), (M, 10)], name="short_last_bin"),
+        dict(tid=2, pos=0, cigar=[(M, 10)], name="on_the_empty_contig"),
+        # contig "long": the CIGAR in the CG tag, one M op over 100 000 positions, reads large enough to straddle batches
+        dict(tid=4, pos=5, cigar=many_ops(66001), name="longcigar", mapq=20),
+        dict(tid=4, pos=100, cigar=[(S, 3), (M, 100_000), (I, 5), (M, 50)], name="m100k"),
+    ]
+    alns += [dict(tid=4, pos=1000 + 7000 * k, cigar=[(M, 150_000)], name="bulk%d" % k, mapq=MAPQ_CYCLE[k % 4]) for k in range(6)]
+    alns.append(dict(tid=-1, pos=-1, cigar=[], flag=0x4, name="no_coordinates"))
+    rec = synth.records_from_alignments(alns)
+    rec.header_chroms, rec.header_lens = list(CHROMS), list(LENGTHS)
+    return rec
+
+
+@pytest.fixture(scope="module")
+def case(tmp_path_factory):
+    d = tmp_path_factory.mktemp("binned_depth")
+    out = dict(dir=d)
+    for key, with_no_seq in (("odd", True), ("acgt", False)):
+        rec = odd_records(with_no_seq)
+        names = rec.materialise_names()
+        path = str(d / (key + ".bam"))
+        bam.write_bam(rec, path, seed=5, fast_seq=True, with_qual=lambda i: names[int(rec.name_id[i])] != "noqual" and i % 3 != 1)
+        out[key] = path
+    raw = gzip.open(out["odd"], "rb").read()
+    out["small"] = str(d / "odd_small_blocks.bam")
+    with open(out["small"], "wb") as fp:
+        for blk in bam._bgzf_blocks(raw, block_size=1500, empty_block_every=5):
+            fp.write(blk)
+    out["want"] = Restatement(out["odd"])
+    # a header with long contigs (the human genome's) for the limit on the number of bins
+    out["genome"] = str(d / "genome.bam")
+    bam.write_bam(synth.records_from_alignments([dict(tid=0, pos=100, cigar=[(M, 50)])]), out["genome"])
+    return out
+
+
+def equal_to_restatement(got, case, bin_size, min_mapq, exclude_flags, count_deletions):
+    off, bases, reads = case["want"].tables(bin_size, min_mapq, exclude_flags, count_deletions)
+    assert got.all_bases.dtype == np.int64 and got.all_reads.dtype == np.int64
+    assert np.array_equal(got.bin_off, off) and got.n_bins == off[-1]
+    assert np.array_equal(got.all_reads, reads)
+    assert np.array_equal(got.all_bases, bases)
+    return bases, reads
+
+
+# ---- the restatement itself sees what was planted ------------------------------------------------------------------------------
+def test_restatement_reads_the_planted_records(case):
+    want = case["want"]
+    by_name = {r["name"]: r for r in want.recs}
+    assert want.refs == CHROMS and want.lens == LENGTHS
+    assert [len(by_name[k]["ops"]) for k in ("ops1", "ops63", "ops64", "ops65", "ops128", "ops129", "longcigar")] == [1, 63, 64, 65, 128, 129, 66001]
+    for k in ("ops63", "ops64", "ops65", "ops128", "ops129", "longcigar"):
+        assert {op for op, _ in by_name[k]["ops"]} == set(range(9)) and any(ln == 0 for _, ln in by_name[k]["ops"])
+    assert {by_name[k]["flag"] for k in ("unmapped", "secondary", "qcfail", "duplicate", "supplementary", "reverse")} == {0x4, 0x100, 0x200, 0x400, 0x800, 0x10}
+    assert {r["mapq"] for r in want.recs} >= {0, 19, 20, 255}
+    assert by_name["noseq"]["l_seq"] == 0 and by_name["noqual"]["l_seq"] == 80 and by_name["noqual"]["qual0"] == 0xFF and by_name["ends_on_edge"]["qual0"] != 0xFF
+    assert sum(r["name"].startswith("hot") for r in want.recs) == HOT_DEPTH and by_name["no_coordinates"]["tid"] == -1
+    off, bases, reads = want.tables(1000, 0, 0, True)
+    assert off.tolist() == [0, 7, 13, 13, 16, 217]
+    assert reads[off[1] + 2] == HOT_DEPTH and bases[off[1] + 2] == HOT_DEPTH * HOT_LEN          # the stack, in one bin
+    assert bases[off[3]:off[4]].sum() == 0 and reads[off[3]:off[4]].sum() == 0                    # the contig no read touches
+    assert bases[off[1] + 5] == 3 and reads[off[1] + 5] == 0                                      # the short last bin: [5000, 5003)
+    # the last bin of "even" holds what lies below 7000 of "past_the_end" and "last_base"; the reads at and behind 7000 are not counted
+    assert bases[off[0] + 6] == 40 + 30 + 30 + 1 and reads[off[0] + 6] == 2
+    # every parameter bites on this file
+    totals = {k: want.tables(1000, *k)[1].sum() for k in ((0, 0, True), (20, 0, True), (255, 0, True), (0, 0x704, True), (0, 0x904, True), (0, 0, False))}
+    assert len(set(totals.values())) == 6 and all(v > 0 for v in totals.values())
+    assert want.tables(1, 0, 0, True)[1].max() >= HOT_DEPTH and want.tables(1 << 20, 0, 0, True)[0][-1] == 4
+
+
+# ---- 1. the tables -------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("count_deletions", [True, False])
+@pytest.mark.parametrize("bin_size", BIN_SIZES)
+@pytest.mark.parametrize("pipe", PIPELINES)
+def test_tables_equal_restatement(case, pipe, bin_size, count_deletions):
+    for min_mapq in MIN_MAPQS:
+        for exclude in EXCLUDES:
+            got = bam.binned_depth(case["odd"], bin_size, min_mapq, exclude, count_deletions, device=DEVICE[pipe], n_threads=3)
+            bases, _ = equal_to_restatement(got, case, bin_size, min_mapq, exclude, count_deletions)
+            assert bases.sum() > 0 and got.params == (bin_size, min_mapq, exclude, count_deletions)
+            assert got.chroms == CHROMS and got.lengths == LENGTHS
+
+
+@pytest.mark.parametrize("pipe", PIPELINES)
+def test_defaults_and_accessors(case, pipe):
+    got = bam.binned_depth(case["odd"], device=DEVICE[pipe])
+    assert got.params == (1000, 0, 0x704, True)
+    off, bases, reads = case["want"].tables(1000, 0, 0x704, True)
+    for t, c in enumerate(CHROMS):
+        assert np.array_equal(got.bases(c), bases[off[t]:off[t + 1]]) and np.array_equal(got.reads(c), reads[off[t]:off[t + 1]])
+        starts, ends = got.bins(c)
+        assert len(starts) == off[t + 1] - off[t] and (len(starts) == 0 or (starts[0] == 0 and ends[-1] == LENGTHS[t]))
+        assert np.array_equal(got.mean_depth(c), got.bases(c) / (ends - starts)) and got.mean_depth(c).dtype == np.float64
+    assert got.bins("odd")[1].tolist() == [1000, 2000, 3000, 4000, 5000, 5003] and len(got.bases("empty")) == 0
+    assert got.mean_depth("odd")[5] == got.bases("odd")[5] / 3.0                              # the short last bin by its own length
+    with pytest.raises(KeyError):
+        got.bases("chrNope")
+
+
+# ---- 2. / 3. independent cross-checks against the coverage rule ----------------------------------------------------------------
+@pytest.mark.parametrize("pipe", PIPELINES)
+def test_bases_equal_window_coverage(case, pipe):
+    """Every record of this file has SEQ, only A / C / G / T and a CIGAR of its query length: window coverage at threshold 0 counts
+    what binned depth counts without deletions."""
+    for b in (7, 1000):
+        windows = [(c, a, min(a + b, l)) for c, l in zip(CHROMS, LENGTHS) for a in range(0, l, b)]
+        for exclude, cb in ((0, "nofilter"), (0x704, "all")):
+            got = bam.binned_depth(case["acgt"], b, 0, exclude, False, device=DEVICE[pipe])
+            cov = bam.window_coverage(case["acgt"], windows, 0, cb, device=DEVICE[pipe], index=False)
+            assert cov.sum() > HOT_DEPTH * HOT_LEN and np.array_equal(got.all_bases, cov)
+
+
+@pytest.mark.parametrize("pipe", PIPELINES)
+def test_bin_size_one_equals_pileup_depth(case, pipe):
+    got = bam.binned_depth(case["acgt"], 1, 0, 0, False, device=DEVICE[pipe])
+    regions = [(c, 0, l) for c, l in zip(CHROMS, LENGTHS) if l]
+    p = bam.pileup(case["acgt"], regions, 0, "nofilter", device=DEVICE[pipe], index=False)
+    for c, a, b in regions:
+        assert np.array_equal(got.bases(c), p.depth(c, a, b))
+    assert got.all_bases.max() >= HOT_DEPTH
+
+
+# ---- 4. / 5. / 6. batches, byte ranges, pipelines --------------------------------------------------------------------------------
+@pytest.mark.parametrize("pipe", PIPELINES)
+def test_batch_boundaries(case, pipe):
+    """1 MiB batches (the smallest there are) over small BGZF blocks: records straddle batches."""
+    one = bam.binned_depth(case["small"], 7, 20, 0x704, True, device=DEVICE[pipe])
+    equal_to_restatement(one, case, 7, 20, 0x704, True)
+    many = bam.binned_depth(case["small"], 7, 20, 0x704, True, device=DEVICE[pipe], batch_bytes=1 << 16, n_threads=2)
+    if pipe == "gpu":
+        assert bam.LAST_DECODE["where"] == "gpu" and bam.LAST_DECODE["batches"] >= 2
+    assert np.array_equal(many.all_bases, one.all_bases) and np.array_equal(many.all_reads, one.all_reads)
+
+
+@pytest.mark.parametrize("world", [2, 3])
+@pytest.mark.parametrize("pipe", PIPELINES)
+def test_byte_ranges_add_up(case, pipe, world):
+    parts = [bam.binned_depth(case["small"], 1000, 0, 0x704, True, device=DEVICE[pipe], rank=r, world=world, batch_bytes=1 << 16) for r in range(world)]
+    assert sum(int(p.all_reads.sum()) > 0 for p in parts) >= 2
+    merged = bam.merge_binned_depth(parts)
+    equal_to_restatement(merged, case, 1000, 0, 0x704, True)
+    assert merged.params == parts[0].params and merged.chroms == CHROMS
+
+
+def test_merge_refuses_differing_parts(case):
+    a = bam.binned_depth(case["odd"], 1000, device="cpu")
+    for other in (bam.binned_depth(case["odd"], 999, device="cpu"), bam.binned_depth(case["odd"], 1000, 1, device="cpu"),
+                  bam.binned_depth(case["odd"], 1000, 0, 0x904, device="cpu"), bam.binned_depth(case["odd"], 1000, count_deletions=False, device="cpu"),
+                  bam.binned_depth(case["genome"], 1 << 20, device="cpu")):
+        with pytest.raises(ValueError):
+            bam.merge_binned_depth([a, other])
+    with pytest.raises(ValueError):
+        bam.merge_binned_depth([])
+    assert np.array_equal(bam.merge_binned_depth([a]).all_bases, a.all_bases)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("bin_size,count_deletions", [(1, True), (7, False), (1000, True)])
+def test_gpu_equals_host(case, bin_size, count_deletions):
+    host = bam.binned_depth(case["odd"], bin_size, 19, 0x10, count_deletions, device="cpu")
+    got = bam.binned_depth(case["odd"], bin_size, 19, 0x10, count_deletions, device="cuda:0")
+    assert bam.LAST_DECODE["where"] == "gpu"
+    assert np.array_equal(got.bin_off, host.bin_off) and np.array_equal(got.all_bases, host.all_bases) and np.array_equal(got.all_reads, host.all_reads)
+    assert host.all_bases.sum() > 0
+
+
+def test_cpu_pipeline_by_environment(case, monkeypatch):
+    monkeypatch.setenv("CORAL_BAM_DECODE", "cpu")
+    got = bam.binned_depth(case["odd"], 1000, 20, 0x704, True, device="cuda:0")
+    assert bam.LAST_DECODE.get("where") != "gpu"
+    equal_to_restatement(got, case, 1000, 20, 0x704, True)
+
+
+# ---- 7. with the other requests -------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("pipe", PIPELINES)
+def test_every_request_in_one_decode(case, pipe):
+    segs = np.array([(0, 400, 1200), (1, 0, 5003), (4, 90, 3000)], dtype=np.int32).T.copy()
+    depth = (7, 20, 0x704, 1)
+    decode = lambda **kw: bam._decode(case["odd"], DEVICE[pipe], n_threads=2, **kw)
+    alone = decode(depth=depth, records=False)
+    alone_cov, alone_idx, alone_qc = decode(coverage=(segs, 0, 1), records=False).counts, decode(index=True, records=False).index, decode(qc=True, records=False).qc
+    got = decode(depth=depth, coverage=(segs, 0, 1), index=True, qc=True)
+    off, bases, reads = case["want"].tables(7, 20, 0x704, True)
+    for res in (alone, got):
+        assert np.array_equal(res.depth[0], off) and np.array_equal(res.depth[1], bases) and np.array_equal(res.depth[2], reads)
+    assert alone_cov.sum() > 0 and np.array_equal(got.counts, alone_cov)
+    assert set(got.index) == set(alone_idx) and all(np.array_equal(got.index[k], v) for k, v in alone_idx.items())
+    for k in ("length", "qual_sum", "mapq", "flag", "base_quality_hist"):
+        assert np.array_equal(getattr(got.qc, k), getattr(alone_qc, k)), k
+    assert got.qc.counters == alone_qc.counters and got.records.n == len(case["want"].recs)
+    assert alone.records is None and alone.counts is None and alone.index is None and alone.qc is None and decode(records=False).depth is None
+
+
+# ---- 8. argument rules, equal on both pipelines --------------------------------------------------------------------------------
+def bad_requests(case):
+    """name -> (file, arguments of _lib.bam_request, a word of the message)"""
+    return {
+        "depth_bin < 0": (case["odd"], dict(depth=(-1, 0, 0, 1)), "depth_bin"),
+        "min_mapq < 0": (case["odd"], dict(depth=(1000, -1, 0, 1)), "min_mapq"),
+        "min_mapq > 255": (case["odd"], dict(depth=(1000, 256, 0, 1)), "min_mapq"),
+        "exclude_flags < 0": (case["odd"], dict(depth=(1000, 0, -1, 1)), "exclude_flags"),
+        "exclude_flags > 0xffff": (case["odd"], dict(depth=(1000, 0, 0x10000, 1)), "exclude_flags"),
+        "count_deletions = 2": (case["odd"], dict(depth=(1000, 0, 0, 2)), "count_deletions"),
+        "more than 2^28 bins": (case["genome"], dict(depth=(1, 0, 0, 1)), "2^28 bins"),
+        "on a span decode": (case["odd"], dict(depth=(1000, 0, 0, 1), spans=[[0, 1 << 16]]), "span decode"),
+    }
+
+
+def test_host_refuses_bad_requests(case):
+    L = _lib.lib()
+    for name, (path, kw, word) in bad_requests(case).items():
+        req, h = _lib.bam_request(**kw), C.c_void_p()
+        assert L.coral_bam_decode_request(path.encode(), 1, C.byref(req), C.byref(h)) == CORAL_ERR_ARG and h.value is None, name
+        assert word in L.coral_bam_last_error().decode(), name
+    # larger bins are a legal request on the long header, and the handle answers
+    req, h = _lib.bam_request(depth=(1000, 0, 0, 1)), C.c_void_p()
+    assert L.coral_bam_decode_request(case["genome"].encode(), 2, C.byref(req), C.byref(h)) == CORAL_OK
+    try:
+        sz = (C.c_int64 * 2)()
+        assert L.coral_bam_depth_sizes(h, sz) == CORAL_OK and sz[0] == 25 and sz[1] == sum(-(-l // 1000) for l in synth.CHR_SIZES)
+    finally:
+        L.coral_bam_decode_close(h)
+    req, h = _lib.bam_request(), C.c_void_p()                                         # a handle without the request holds no table
+    assert L.coral_bam_decode_request(case["odd"].encode(), 2, C.byref(req), C.byref(h)) == CORAL_OK
+    try:
+        sz, off = (C.c_int64 * 2)(), np.zeros(6, dtype=np.int64)
+        assert L.coral_bam_depth_sizes(h, sz) == CORAL_ERR_ARG and "no binned-depth request" in L.coral_bam_last_error().decode()
+        assert L.coral_bam_depth_fill(h, off.ctypes.data, None, None) == CORAL_ERR_ARG
+    finally:
+        L.coral_bam_decode_close(h)
+
+
+@pytest.mark.gpu
+def test_gpu_refuses_the_same_requests(case):
+    L = _lib.lib()
+    torch.cuda.set_device(torch.device("cuda:0"))
+    for name, (path, kw, word) in bad_requests(case).items():
+        req, h, ws_bytes = _lib.bam_request(**kw), C.c_void_p(), C.c_int64(0)
+        rc = L.coral_bamgpu_open_request(path.encode(), 1, 0, C.byref(req), C.byref(h), C.byref(ws_bytes))
+        assert rc == CORAL_ERR_ARG and h.value is None and ws_bytes.value == 0, name            # refused at open: nothing to allocate
+        assert word in L.coral_bam_last_error().decode(), name
+
+
+@pytest.mark.gpu
+def test_gpu_workspace_grows_by_the_tables(case):
+    up256 = lambda n: (n + 255) & ~255
+    bam.decode_bam_gpu(case["odd"], "cuda:0")
+    plain = bam.LAST_DECODE["workspace_bytes"]
+    n_ref = len(CHROMS)
+    for b in (7, 1000):
+        got = bam.binned_depth(case["odd"], b, device="cuda:0")
+        assert bam.LAST_DECODE["workspace_bytes"] == plain + up256((n_ref + 1) * 8) + up256(n_ref * 4) + 2 * up256(got.n_bins * 8)
+    bam._decode(case["odd"], "cuda:0", index=True, qc=True, records=False)            # unchanged without the request
+    other = bam.LAST_DECODE["workspace_bytes"]
+    bam.decode_bam_gpu(case["odd"], "cuda:0")
+    assert bam.LAST_DECODE["workspace_bytes"] == plain < other
+
+
+@pytest.mark.parametrize("kw", [dict(bin_size=0), dict(bin_size=-5), dict(bin_size=2.5), dict(bin_size=1 << 31), dict(min_mapq=-1), dict(min_mapq=256),
+                                dict(exclude_flags=-1), dict(exclude_flags=0x10000), dict(min_mapq="20")])
+def test_bad_parameters_raise_before_anything_is_decoded(kw):
+    with pytest.raises(ValueError):
+        bam.binned_depth("/no/such/file.bam", device="cpu", **kw)
+
+
+def test_too_many_bins_raise_value_error(case):
+    with pytest.raises(ValueError):
+        bam.binned_depth(case["genome"], 1, device="cpu")
+    with pytest.raises(OSError):
+        bam.binned_depth(str(case["dir"] / "missing.bam"), device="cpu")
+
+
+# ---- 9. the command line ---------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("flags,params", [([], (1000, 0, 0x704, True)),
+                                          (["--bin_size", "7", "--min_mapq", "20", "--exclude_flags", "2308", "--no_deletions"], (7, 20, 0x904, False))])
+@pytest.mark.parametrize("pipe", PIPELINES)
+def test_cli_writes_the_bins(case, pipe, tmp_path, flags, params):
+    off, bases, reads = case["want"].tables(*params)
+    out = str(tmp_path / "bins.cnn")
+    assert CoRAL.main(["depth", "--lr_bam", case["odd"], "--output", out, "--device", DEVICE[pipe]] + flags) == out
+    lines = open(out).read().split("\n")
+    assert lines[0] == "chromosome\tstart\tend\tgene\tdepth\tlog2\treads" and lines[-1] == ""
+    rows = [ln.split("\t") for ln in lines[1:-1]]
+    assert len(rows) == off[-1]
+    k, zeros = 0, 0
+    for t, c in enumerate(CHROMS):
+        for j in range(off[t + 1] - off[t]):
+            chrom, start, end, gene, depth, log2, n_reads = rows[k]
+            assert (chrom, int(start), int(end), gene) == (c, j * params[0], min((j + 1) * params[0], LENGTHS[t]), "-")
+            assert float(depth) == bases[k] / (int(end) - int(start)) and int(n_reads) == reads[k]
+            assert float(log2) == (math.log2(float(depth)) if bases[k] else -20.0)
+            zeros += bases[k] == 0
+            k += 1
+    assert zeros > 0 and k - zeros > 10
