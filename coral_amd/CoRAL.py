@@ -28,6 +28,22 @@ def print_args(args_dict):
     print()
 
 
+def add_filter_arguments(p):
+    """--filter_*: the record filter of the decode (bam.RecordFilter), what `samtools view -q / -f / -F` and a length test in
+    front of the file would do; integers in any base, 0 = no test."""
+    any_int = lambda x: int(x, 0)
+    p.add_argument("--filter_min_mapq", help="Drop reads of a lower mapping quality while the bam file is decoded.", type=any_int, default=0)
+    p.add_argument("--filter_min_length", help="Drop reads with a shorter stored sequence.", type=any_int, default=0)
+    p.add_argument("--filter_require_flags", help="Drop reads that lack any of these flag bits.", type=any_int, default=0)
+    p.add_argument("--filter_exclude_flags", help="Drop reads with any of these flag bits.", type=any_int, default=0)
+
+
+def record_filter_of(args):
+    """The bam.RecordFilter of an argument object (one without the --filter_* attributes: no filter)."""
+    from coral_amd import bam
+    return bam.record_filter_from_args(args)
+
+
 def build_parser():
     parser = argparse.ArgumentParser(description="Long-read amplicon reconstruction pipeline and associated utilities.")
     sub = parser.add_subparsers(dest="mode", help="Select mode.")
@@ -89,6 +105,8 @@ def build_parser():
                     type=int, default=0x704)
     dp.add_argument("--no_deletions", help="If specified, deleted reference bases (D) do not count as covered.", action='store_true')
     dp.add_argument("--device", help="GPU to use ('cpu': the host pipeline).", default="cuda:0")
+    for p in (rp, hp, qp, pp, dp):
+        add_filter_arguments(p)
     for mode in ("seed", "plot", "cycle2bed"):
         sub.add_parser(mode, help="(reference implementation; not part of the MI355X path)", add_help=False)
     return parser
@@ -120,7 +138,7 @@ def qc_mode(args):
     histograms (lines 54-68, plain matplotlib) and read_qc.json (counters, summary, base-quality histogram)."""
     import json
     from coral_amd import bam
-    qc = bam.read_qc(args.lr_bam, device=args.device)
+    qc = bam.read_qc(args.lr_bam, device=args.device, record_filter=record_filter_of(args))
     os.makedirs(args.output_dir, exist_ok=True)
     wrote = [qc.write_summary(os.path.join(args.output_dir, "quality_control_summary.tsv"))]
     summary = qc.summary()
@@ -169,7 +187,7 @@ def pileup_mode(args):
             chrom, span = text.rsplit(":", 1)
             a, b = span.replace(",", "").split("-")
             regions.append((chrom, int(a), int(b)))
-    p = bam.pileup(args.lr_bam, regions, args.min_base_quality, args.read_callback, device=args.device)
+    p = bam.pileup(args.lr_bam, regions, args.min_base_quality, args.read_callback, device=args.device, record_filter=record_filter_of(args))
     with open(args.output, "w") as fp:
         fp.write("chrom\tpos\tA\tC\tG\tT\n")
         for chrom, a, b in p.regions:
@@ -183,7 +201,8 @@ def pileup_mode(args):
 def depth_mode(args):
     """chromosome, start, end, gene, depth, log2, reads of every bin, in header order (bam.BinnedDepth.write)."""
     from coral_amd import bam
-    d = bam.binned_depth(args.lr_bam, args.bin_size, args.min_mapq, args.exclude_flags, not args.no_deletions, device=args.device)
+    d = bam.binned_depth(args.lr_bam, args.bin_size, args.min_mapq, args.exclude_flags, not args.no_deletions, device=args.device,
+                         record_filter=record_filter_of(args))
     d.write(args.output)
     print("Wrote %s (%d bins)" % (args.output, d.n_bins))
     return args.output

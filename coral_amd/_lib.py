@@ -26,18 +26,22 @@ class coral_bam_request_t(C.Structure):
                 ("n_seg", C.c_int32), ("seg_tid", C.c_void_p), ("seg_start", C.c_void_p), ("seg_end", C.c_void_p),
                 ("quality_threshold", C.c_int32), ("read_callback", C.c_int32), ("want_index", C.c_int32), ("want_qc", C.c_int32),
                 ("per_base", C.c_int32), ("depth_bin", C.c_int32), ("depth_min_mapq", C.c_int32), ("depth_exclude_flags", C.c_int32),
-                ("depth_count_deletions", C.c_int32)]
+                ("depth_count_deletions", C.c_int32), ("keep_min_mapq", C.c_int32), ("keep_min_seq_length", C.c_int32),
+                ("keep_require_flags", C.c_int32), ("keep_exclude_flags", C.c_int32)]
 
 
 def bam_request(rank: int = 0, world: int = 1, spans=None, coverage=None, index: bool = False, qc: bool = False,
-                per_base: bool = False, depth=None) -> coral_bam_request_t:
+                per_base: bool = False, depth=None, keep=None) -> coral_bam_request_t:
     """The request of a BAM decode: ``spans`` uint64 [K][2] virtual offsets (None: the byte range), ``coverage`` = (segments int32
     [3][S], quality threshold, read_callback code) or None, ``per_base``: the coverage as the table per position and base (the
-    pileup), ``depth`` = (bin size, min_mapq, exclude_flags, count_deletions) or None: the binned-depth request.  The struct keeps the contiguous arrays it points into alive; the rules are the library's to check."""
+    pileup), ``depth`` = (bin size, min_mapq, exclude_flags, count_deletions) or None: the binned-depth request, ``keep`` = (min_mapq, min_seq_length, require_flags, exclude_flags) (a
+    ``bam.RecordFilter`` is one) or None: the record filter.  The struct keeps the contiguous arrays it points into alive; the rules are the library's to check."""
     req = coral_bam_request_t(rank=rank, world=world, n_spans=-1, n_seg=-1, want_index=int(index), want_qc=int(qc), per_base=int(per_base))
     req.arrays = []
     if depth is not None:
         req.depth_bin, req.depth_min_mapq, req.depth_exclude_flags, req.depth_count_deletions = (int(v) for v in depth)
+    if keep is not None:
+        req.keep_min_mapq, req.keep_min_seq_length, req.keep_require_flags, req.keep_exclude_flags = (int(v) for v in keep)
 
     def pointer(a, dtype):
         req.arrays.append(np.ascontiguousarray(a, dtype=dtype))

@@ -40,11 +40,49 @@ def default_threads() -> int:
 LAST_DECODE = {}      # statistics of the last decode_bam call (bench.py): seconds, compressed / uncompressed bytes, threads
 
 
-def decode_bam(path: str, n_threads: Optional[int] = None, rank: int = 0, world: int = 1) -> Records:
+class RecordFilter(collections.namedtuple("RecordFilter", "min_mapq min_seq_length require_flags exclude_flags")):
+    """Which records a decode keeps (``record_filter=`` of every decode here): ``mapq >= min_mapq`` (samtools view -q), ``l_seq >=
+    min_seq_length`` (the stored sequence; a record without SEQ has length 0), ``flag & require_flags == require_flags`` (-f) and
+    ``flag & exclude_flags == 0`` (-F).  Every result of a filtered decode is that of the same call on a BAM file that holds only
+    the kept records, in the same order; a dropped record costs nothing behind the decode's boundary walk.  The reference's
+    preparation step ``samtools view -h | awk 'length($10) > 1000' | samtools view -bSq 25`` is ``RecordFilter(25, 1001)``.
+    ValueError for values outside 0..255, 0..2^29, 0..0xffff, 0..0xffff."""
+    __slots__ = ()
+
+    def __new__(cls, min_mapq=0, min_seq_length=0, require_flags=0, exclude_flags=0):
+        for name, v, top in (("min_mapq", min_mapq, 255), ("min_seq_length", min_seq_length, 1 << 29),
+                             ("require_flags", require_flags, 0xffff), ("exclude_flags", exclude_flags, 0xffff)):
+            if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+                raise ValueError("%s must be an integer, got %r" % (name, v))
+            if not 0 <= v <= top:
+                raise ValueError("%s must be in 0..%d, got %r" % (name, top, v))
+        return super().__new__(cls, int(min_mapq), int(min_seq_length), int(require_flags), int(exclude_flags))
+
+    @property
+    def active(self) -> bool:
+        return any(self)
+
+
+def _as_filter(record_filter) -> Optional[RecordFilter]:
+    """None, a RecordFilter or a 4-tuple -> a checked RecordFilter, or None when it keeps everything."""
+    if record_filter is None:
+        return None
+    f = record_filter if isinstance(record_filter, RecordFilter) else RecordFilter(*record_filter)
+    return f if f.active else None
+
+
+def record_filter_from_args(args) -> RecordFilter:
+    """The RecordFilter of a command line's argument object (--filter_min_mapq, --filter_min_length, --filter_require_flags,
+    --filter_exclude_flags of CoRAL.py); an object without these attributes gives the filter that keeps everything."""
+    return RecordFilter(getattr(args, "filter_min_mapq", 0), getattr(args, "filter_min_length", 0),
+                        getattr(args, "filter_require_flags", 0), getattr(args, "filter_exclude_flags", 0))
+
+
+def decode_bam(path: str, n_threads: Optional[int] = None, rank: int = 0, world: int = 1, *, record_filter=None) -> Records:
     """Decode the BAM file (or, with ``world`` > 1, the ``rank``-th of ``world`` byte ranges of it: one process per GPU, every
     rank inflates and parses only its share; consecutive ranges neither drop nor repeat a record).  Read-name ids are local
-    to the returned records."""
-    return _decode(path, "cpu", n_threads=n_threads, rank=rank, world=world).records
+    to the returned records.  ``record_filter``: a ``RecordFilter`` - only the records it keeps."""
+    return _decode(path, "cpu", n_threads=n_threads, rank=rank, world=world, record_filter=record_filter).records
 
 
 def _on_gpu(device) -> bool:
@@ -52,18 +90,21 @@ def _on_gpu(device) -> bool:
 
 
 def load_bam(path: str, device="cuda:0", n_threads: Optional[int] = None, rank: int = 0, world: int = 1, *, regions=None,
-             index=None) -> Records:
+             index=None, record_filter=None) -> Records:
     """The product's way from a BAM file to records: inflate and parse on the GPU (``decode_bam_gpu``) when ``device`` is one;
     ``CORAL_BAM_DECODE=cpu`` selects the host pipeline (``decode_bam``: same result, CIGAR words in host memory).
 
     ``regions`` = [(chrom, start, stop), ...]: only the records pysam's ``fetch`` returns for them (on the contig, ``pos < stop
     and end > start``), each once, in file order, read-name ids numbered by first appearance among them — through the BAI index
     ``index`` (a path, an object of ``read_index``, or None for the file next to the BAM, which must then be usable): only the
-    BGZF blocks the index names are read and inflated; records a chunk carries that meet no region are dropped on the host."""
+    BGZF blocks the index names are read and inflated; records a chunk carries that meet no region are dropped on the host.
+
+    ``record_filter``: a ``RecordFilter`` - the result is that of a file holding only the records it keeps (dropped inside the
+    decode; with ``regions`` the region test runs on the host afterwards, on the kept records)."""
     if regions is None:
         if _on_gpu(device):
-            return decode_bam_gpu(path, device, n_threads=n_threads, rank=rank, world=world)
-        return decode_bam(path, n_threads=n_threads, rank=rank, world=world)
+            return decode_bam_gpu(path, device, n_threads=n_threads, rank=rank, world=world, record_filter=record_filter)
+        return decode_bam(path, n_threads=n_threads, rank=rank, world=world, record_filter=record_filter)
     if world != 1:
         raise ValueError("a region decode is not sharded (world must be 1)")
     if index is False:
@@ -73,7 +114,7 @@ def load_bam(path: str, device="cuda:0", n_threads: Optional[int] = None, rank: 
     reg = _regions_as_tids(regions, names)
     # (an empty region start == stop keeps, by the rule above, the records that span the point)
     spans = region_spans(idx, [(t, a, max(b, a + 1)) for t, a, b in reg])
-    rec = _decode_spans(path, spans, device, n_threads, 0)
+    rec = _decode_spans(path, spans, device, n_threads, 0, record_filter)
     keep = np.zeros(rec.n, dtype=bool)
     tid, pos, end = rec.tid.numpy(), rec.pos.numpy(), rec.end.numpy()
     for t, a, b in reg:
@@ -163,13 +204,14 @@ def _records_from_handle(L, h, cigar, cigar_words: int) -> Records:
 
 
 def decode_bam_gpu(path: str, device="cuda:0", n_threads: Optional[int] = None, rank: int = 0, world: int = 1,
-                   batch_bytes: int = 0) -> Records:
+                   batch_bytes: int = 0, *, record_filter=None) -> Records:
     """The same result as ``decode_bam`` with the inflate and the record parsing on the GPU (csrc/coral_bamgpu.hip): the host
     only reads the file and uploads COMPRESSED bytes; the CIGAR words of the returned Records are a device tensor (they never
-    exist in host memory), everything else is host-side as before.  ``batch_bytes``: inflated bytes per batch (0 = the default, 2.52 GiB)."""
+    exist in host memory), everything else is host-side as before.  ``batch_bytes``: inflated bytes per batch (0 = the default, 2.52 GiB).
+    ``record_filter``: a ``RecordFilter`` (k_bam_keep / k_bam_keep_compact per batch, in front of the record parse)."""
     if torch.device(device).type != "cuda":
         raise _lib.CoralHipError("decode_bam_gpu needs a GPU device (the CPU pipeline is decode_bam)")
-    return _decode_gpu(path, device, n_threads, batch_bytes, _lib.bam_request(rank, world), True).records      # (whatever CORAL_BAM_DECODE says)
+    return _decode_gpu(path, device, n_threads, batch_bytes, _lib.bam_request(rank, world, keep=_as_filter(record_filter)), True).records      # (whatever CORAL_BAM_DECODE says)
 
 
 class DecodeResult(collections.namedtuple("DecodeResult", "records counts index qc")):
@@ -181,14 +223,15 @@ class DecodeResult(collections.namedtuple("DecodeResult", "records counts index 
 
 
 def _decode(path: str, device, *, n_threads: Optional[int] = None, rank: int = 0, world: int = 1, batch_bytes: int = 0, spans=None,
-            coverage=None, index=False, qc=False, records=True, per_base=False, depth=None) -> DecodeResult:
+            coverage=None, index=False, qc=False, records=True, per_base=False, depth=None, record_filter=None) -> DecodeResult:
     """One decode of the ``rank``-th of ``world`` byte ranges, or of the records that start inside ``spans`` (uint64 [K][2] virtual
     offsets), with what rides along: ``coverage`` = (segments int32 [3][S], quality threshold, read_callback code) gives the S
     int64 ``counts``, ``index`` the partial BAI index, ``qc`` the ``ReadQC``; ``records`` False leaves the Records out.  With
     ``per_base`` the coverage is counted per position and base: ``pileup`` is the uint32 table [positions of the segments, in
     segment order][A, C, G, T] and ``counts`` its sums per segment.  ``depth`` = (bin size, min_mapq, exclude_flags,
-    count_deletions) gives the binned-depth tables (``binned_depth``).  On the GPU pipeline when ``_on_gpu(device)``, else on the host."""
-    req = _lib.bam_request(rank, world, spans, coverage, index, qc, per_base, depth)
+    count_deletions) gives the binned-depth tables (``binned_depth``).  ``record_filter``: a ``RecordFilter``; every result is
+    then that of a file holding only the kept records.  On the GPU pipeline when ``_on_gpu(device)``, else on the host."""
+    req = _lib.bam_request(rank, world, spans, coverage, index, qc, per_base, depth, keep=_as_filter(record_filter))
     if _on_gpu(device):
         return _decode_gpu(path, device, n_threads, batch_bytes, req, records)
     L = _lib.lib()
@@ -374,7 +417,7 @@ def coverage_segments(windows, ref_names: Sequence[str]):
 
 def window_coverage(path: str, windows: Sequence[Tuple[str, int, int]], quality_threshold=0, read_callback: str = "nofilter",
                     device="cuda:0", rank: int = 0, world: int = 1, batch_bytes: int = 0, n_threads: Optional[int] = None, *,
-                    index=None) -> np.ndarray:
+                    index=None, record_filter=None) -> np.ndarray:
     """pysam ``AlignmentFile.count_coverage(chrom, start, stop, quality_threshold=..., read_callback=...)`` summed over its four
     arrays, for every window (chrom, start, stop) of ``windows`` (in that order, may overlap), as exact int64 — counted while
     the BAM is decoded, the only time SEQ and QUAL are at hand.
@@ -395,7 +438,9 @@ def window_coverage(path: str, windows: Sequence[Tuple[str, int, int]], quality_
     fits the header and is not older than the BAM, else the whole file as before (``LAST_DECODE["index"]`` says which: the
     index's path, or None with ``LAST_DECODE["index_skipped"]`` giving the reason an existing file was not used); False:
     never; a path or an object of ``read_index``: must be usable, or the call raises.  With ``world`` > 1 an index raises
-    ValueError (a region decode is not sharded), unless it is the default one, which is then not looked for."""
+    ValueError (a region decode is not sharded), unless it is the default one, which is then not looked for.
+
+    ``record_filter``: a ``RecordFilter`` - only the records it keeps are counted."""
     thr = quality_threshold_value(quality_threshold)
     if read_callback not in _READ_CALLBACKS:
         raise ValueError("read_callback must be 'nofilter' or 'all', got %r" % (read_callback,))
@@ -405,13 +450,13 @@ def window_coverage(path: str, windows: Sequence[Tuple[str, int, int]], quality_
     S = segs.shape[1]
     if n_threads is None:
         n_threads = default_threads()
-    res = _decode_segments(path, segs, thr, cb, device, rank, world, batch_bytes, n_threads, index, len(ref_names), False)
+    res = _decode_segments(path, segs, thr, cb, device, rank, world, batch_bytes, n_threads, index, len(ref_names), False, record_filter)
     counts = res.counts if res is not None else np.zeros(S, dtype=np.int64)
     csum = np.concatenate([[0], np.cumsum(counts, dtype=np.int64)])
     return (csum[last] - csum[first]).astype(np.int64)
 
 
-def _decode_segments(path, segs, thr, cb, device, rank, world, batch_bytes, n_threads, index, n_ref, per_base):
+def _decode_segments(path, segs, thr, cb, device, rank, world, batch_bytes, n_threads, index, n_ref, per_base, record_filter=None):
     """The decode behind ``window_coverage`` and ``pileup``: the coverage request of ``segs``, through the BAI index ``index`` (the
     rules of ``window_coverage``) when there is one.  None when the index names no block for the segments: nothing was decoded
     and every count is 0.  ``LAST_DECODE`` says which index was used."""
@@ -444,7 +489,7 @@ def _decode_segments(path, segs, thr, cb, device, rank, world, batch_bytes, n_th
         LAST_DECODE.update(seconds=0.0, compressed_bytes=0, uncompressed_bytes=0, blocks=0, threads=int(n_threads))
     else:
         res = _decode(path, device, n_threads=n_threads, rank=rank, world=world, batch_bytes=batch_bytes, spans=spans,
-                      coverage=(segs, thr, cb), records=False, per_base=per_base)
+                      coverage=(segs, thr, cb), records=False, per_base=per_base, record_filter=record_filter)
     if idx is not None:
         LAST_DECODE.update(index=idx.path or "<object>", spans=int(len(spans)))
     else:
@@ -525,12 +570,14 @@ def pileup_regions(regions, ref_names: Sequence[str]):
 
 
 def pileup(path: str, regions: Sequence[Tuple[str, int, int]], quality_threshold=0, read_callback: str = "nofilter", device="cuda:0",
-           rank: int = 0, world: int = 1, batch_bytes: int = 0, n_threads: Optional[int] = None, *, index=None) -> Pileup:
+           rank: int = 0, world: int = 1, batch_bytes: int = 0, n_threads: Optional[int] = None, *, index=None,
+           record_filter=None) -> Pileup:
     """pysam ``count_coverage`` per position and base for ``regions`` [(chrom, start, stop)] (they may overlap or touch and are
     merged; at most 2^28 positions in all), counted while the BAM is decoded.  The counting rule, ``quality_threshold``,
     ``read_callback``, ``index``, ``rank`` / ``world`` and the choice of the pipeline are ``window_coverage``'s: a base that
     counts there adds 1 to its position's A, C, G or T here (GPU: k_bam_cov_plan / k_bam_pileup per batch).  With ``world`` > 1
-    the table is that of the ``rank``-th byte range; ``merge_pileups`` adds them."""
+    the table is that of the ``rank``-th byte range; ``merge_pileups`` adds them.  ``record_filter``: a ``RecordFilter`` - only
+    the records it keeps are counted."""
     thr = quality_threshold_value(quality_threshold)
     if read_callback not in _READ_CALLBACKS:
         raise ValueError("read_callback must be 'nofilter' or 'all', got %r" % (read_callback,))
@@ -542,7 +589,7 @@ def pileup(path: str, regions: Sequence[Tuple[str, int, int]], quality_threshold
     if n_threads is None:
         n_threads = default_threads()
     res = _decode_segments(path, segs, thr, _READ_CALLBACKS[read_callback], device, rank, world, batch_bytes, n_threads, index,
-                           len(ref_names), True)
+                           len(ref_names), True, record_filter)
     return Pileup(merged, res.pileup if res is not None else np.zeros((n_pos, 4), dtype=np.uint32), thr, read_callback)
 
 
@@ -564,7 +611,7 @@ def merge_pileups(parts: Sequence[Pileup]) -> Pileup:
 
 def count_coverage(path: str, contig: str, start: int, stop: int, quality_threshold=15, read_callback: str = "all", **kw):
     """``pysam.AlignmentFile(path).count_coverage(contig, start, stop, quality_threshold, read_callback)`` in one call: four
-    ``array.array('L')``.  Keywords as ``pileup`` (device, index, ...)."""
+    ``array.array('L')``.  Keywords as ``pileup`` (device, index, record_filter, ...)."""
     p = pileup(path, [(contig, start, stop)], quality_threshold, read_callback, **kw)
     return p.count_coverage(contig, start, stop, quality_threshold=quality_threshold, read_callback=read_callback)
 
@@ -646,13 +693,16 @@ def _read_qc_from_handle(L, h) -> ReadQC:
     return ReadQC(length, qual_sum, mapq, flag, hist, dict(zip(QC_COUNTERS, cnt)))
 
 
-def read_qc(path: str, device="cuda:0", n_threads: Optional[int] = None, rank: int = 0, world: int = 1, batch_bytes: int = 0) -> ReadQC:
+def read_qc(path: str, device="cuda:0", n_threads: Optional[int] = None, rank: int = 0, world: int = 1, batch_bytes: int = 0, *,
+            record_filter=None) -> ReadQC:
     """Per-read length and base-quality statistics of the BAM (``ReadQC``), counted while it is decoded - the only time QUAL is
     at hand.  On the GPU pipeline when ``device`` is a GPU (k_bam_qc_plan / k_bam_qc per batch), on the host
     pipeline with ``device="cpu"`` or ``CORAL_BAM_DECODE=cpu`` (coral_bam_decode_request); the results are identical.  With
-    ``world`` > 1 the result is that of the ``rank``-th byte range; ``merge_read_qc`` joins them."""
+    ``world`` > 1 the result is that of the ``rank``-th byte range; ``merge_read_qc`` joins them.  ``record_filter``: a
+    ``RecordFilter`` - the statistics (``n_records`` included) are those of the records it keeps."""
     bam_reference_names(path)                                    # (a clear error for something that is not a BAM file)
-    return _decode(path, device, n_threads=n_threads, rank=rank, world=world, batch_bytes=batch_bytes, qc=True, records=False).qc
+    return _decode(path, device, n_threads=n_threads, rank=rank, world=world, batch_bytes=batch_bytes, qc=True, records=False,
+                   record_filter=record_filter).qc
 
 
 def merge_read_qc(parts: Sequence[ReadQC]) -> ReadQC:
@@ -749,7 +799,8 @@ def depth_parameters(bin_size, min_mapq, exclude_flags, count_deletions):
 
 
 def binned_depth(path: str, bin_size: int = 1000, min_mapq: int = 0, exclude_flags: int = 0x704, count_deletions: bool = True,
-                 device="cuda:0", rank: int = 0, world: int = 1, batch_bytes: int = 0, n_threads: Optional[int] = None) -> BinnedDepth:
+                 device="cuda:0", rank: int = 0, world: int = 1, batch_bytes: int = 0, n_threads: Optional[int] = None, *,
+                 record_filter=None) -> BinnedDepth:
     """Read depth per bin of ``bin_size`` bases along every contig (``BinnedDepth``), counted while the BAM is decoded: only the
     fixed fields and the CIGAR of a record are looked at, so a file without SEQ or QUAL serves as well.  A record takes part
     when it has a contig, a position and a CIGAR, ``flag & exclude_flags == 0`` and ``mapq >= min_mapq``; M / = / X ops (and D
@@ -758,13 +809,15 @@ def binned_depth(path: str, bin_size: int = 1000, min_mapq: int = 0, exclude_fla
     CNVkit is not pinned here, the rule is.  Bad parameters, or more than 2^28 bins, raise ValueError before
     anything is decoded.  GPU pipeline (k_bam_depth per batch) on a GPU ``device``, host pipeline with ``device="cpu"`` or
     ``CORAL_BAM_DECODE=cpu``; identical results.  With ``world`` > 1 the tables are those of the ``rank``-th byte range;
-    ``merge_binned_depth`` adds them."""
+    ``merge_binned_depth`` adds them.  ``record_filter``: a ``RecordFilter``, applied in front of (and so together with)
+    ``min_mapq`` / ``exclude_flags``."""
     params = depth_parameters(bin_size, min_mapq, exclude_flags, count_deletions)
     chroms, lengths = bam_reference_names(path), bam_reference_lengths(path)
     n_bins = sum((max(l, 0) + params[0] - 1) // params[0] for l in lengths)
     if n_bins > DEPTH_MAX_BINS:
         raise ValueError("bins of %d bases make %d bins of this header: a binned-depth request takes at most 2^28" % (params[0], n_bins))
-    res = _decode(path, device, n_threads=n_threads, rank=rank, world=world, batch_bytes=batch_bytes, records=False, depth=params)
+    res = _decode(path, device, n_threads=n_threads, rank=rank, world=world, batch_bytes=batch_bytes, records=False, depth=params,
+                  record_filter=record_filter)
     return BinnedDepth(chroms, lengths, *params, *res.depth)
 
 
@@ -788,9 +841,10 @@ _PSEUDO_BIN = 37450
 _NO_OFFSET = np.uint64(0xffffffffffffffff)
 
 
-def _decode_spans(path, spans, device, n_threads, batch_bytes) -> Records:
+def _decode_spans(path, spans, device, n_threads, batch_bytes, record_filter=None) -> Records:
     """The records that start inside ``spans`` (uint64 [K][2] virtual offsets), on either pipeline (no span: on the host)."""
-    return _decode(path, device if len(spans) else "cpu", n_threads=n_threads, batch_bytes=batch_bytes, spans=spans).records
+    return _decode(path, device if len(spans) else "cpu", n_threads=n_threads, batch_bytes=batch_bytes, spans=spans,
+                   record_filter=record_filter).records
 
 
 def _index_partial_from_handle(L, h) -> dict:

@@ -77,7 +77,7 @@ struct Chunk {
 bool decode_file(const char *path, int n_threads, const Request &R, const Span *span, Decoded &D) {
     const int rank = R.rank, world = R.world;
     const CovTable *cov = R.cov_table();
-    const bool want_index = R.want_index, want_qc = R.want_qc;
+    const bool want_index = R.want_index, want_qc = R.want_qc, filtered = R.keep.active();
     const auto t_start = std::chrono::steady_clock::now();
     MappedFile f;
     if (!f.open(path, D.error)) return false;
@@ -178,6 +178,7 @@ bool decode_file(const char *path, int n_threads, const Request &R, const Span *
             if (want_qc) pt.qc_hist.assign(256, 0);              // the chunk's partial histogram, likewise
             for (size_t s : c->starts) {
                 const uint8_t *q = c->buf.data() + s;
+                if (filtered && !keep_record_at(q, R.keep)) continue;      // dropped: no field, no tag, no counter sees it
                 if (!decode_record(q + 4, rd32(q), ref_id, pt, pt.error, cov, want_qc, D.pileup.data(), depth)) break;
             }
             std::vector<uint8_t>().swap(c->buf);            // SEQ / QUAL bytes are gone from here on

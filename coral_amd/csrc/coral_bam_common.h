@@ -224,6 +224,27 @@ struct DepthPartial {
     }
 };
 
+// A record filter (keep_* of a coral_bam_request_t): which records a decode keeps - samtools view -q / -f / -F and the length
+// test of the reference's preparation step (scripts/align_nanopore_reads.sh:42-44), decided from the record's fixed fields
+// alone.  A record is kept when all four tests hold; all-zero keeps everything (the filter is then not active: no work is added).
+// The length is the fixed field l_seq: a record without SEQ has length 0, where awk sees `*` with length 1 - both fail any
+// threshold of 2 or more.  Every result of a filtered decode is that of a file holding only the kept records; a dropped record
+// is looked at no further than its fixed fields (its tags are not walked, so a malformed tag in it is not an error).
+struct KeepRule {
+    uint32_t min_mapq = 0, min_seq_length = 0, require_flags = 0, exclude_flags = 0;
+    bool active() const { return (min_mapq | min_seq_length | require_flags | exclude_flags) != 0; }
+};
+CORAL_QC_HD inline bool keep_record(uint32_t mapq, uint32_t flag, uint32_t l_seq, uint32_t min_mapq, uint32_t min_seq_length,
+                                    uint32_t require_flags, uint32_t exclude_flags) {
+    return mapq >= min_mapq && l_seq >= min_seq_length && (flag & require_flags) == require_flags && (flag & exclude_flags) == 0;
+}
+// the same on a record's bytes (r points at block_size, which must be >= 32)
+inline bool keep_record_at(const uint8_t *r, const KeepRule &K) {
+    uint16_t flag; uint32_t l_seq;
+    memcpy(&flag, r + 18, 2); memcpy(&l_seq, r + 20, 4);
+    return keep_record(r[13], flag, l_seq, K.min_mapq, K.min_seq_length, K.require_flags, K.exclude_flags);
+}
+
 // A span of virtual offsets [beg, end) (span_beg / span_end of a coral_bam_request_t): the records that START in it.
 struct Span {
     uint64_t beg = 0, end = 0;
@@ -341,6 +362,7 @@ struct Request {
     bool want_index = false, want_qc = false;
     int32_t depth_bin = 0, depth_min_mapq = 0, depth_exclude_flags = 0;      // a binned-depth request (depth_bin > 0; the bins need the header: DepthPartial::init)
     bool depth_count_deletions = false;
+    KeepRule keep;                          // the record filter (not active: every record is kept)
     const CovTable *cov_table() const { return has_cov ? &cov : nullptr; }
 };
 
@@ -375,6 +397,16 @@ inline bool parse_request(const coral_bam_request_t *q, Request &R, std::string 
         if (q->world < 1 || q->rank < 0 || q->rank >= q->world) { err = "request: needs world >= 1 and 0 <= rank < world"; return false; }
         R.rank = q->rank;
         R.world = q->world;
+    }
+    if (q->keep_min_mapq < 0 || q->keep_min_mapq > 255) { err = "record filter: keep_min_mapq must be 0..255"; return false; }
+    if (q->keep_min_seq_length < 0 || q->keep_min_seq_length > (1 << 29)) { err = "record filter: keep_min_seq_length must be 0..2^29"; return false; }
+    if (q->keep_require_flags < 0 || q->keep_require_flags > 0xffff) { err = "record filter: keep_require_flags must be 0..0xffff"; return false; }
+    if (q->keep_exclude_flags < 0 || q->keep_exclude_flags > 0xffff) { err = "record filter: keep_exclude_flags must be 0..0xffff"; return false; }
+    R.keep.min_mapq = (uint32_t)q->keep_min_mapq; R.keep.min_seq_length = (uint32_t)q->keep_min_seq_length;
+    R.keep.require_flags = (uint32_t)q->keep_require_flags; R.keep.exclude_flags = (uint32_t)q->keep_exclude_flags;
+    if (R.keep.active() && R.want_index) {
+        err = "request: a record filter does not go with an index request (the virtual offsets of a file that holds only the kept records do not exist)";
+        return false;
     }
     R.has_cov = q->n_seg >= 0;
     if (q->per_base != 0 && !R.has_cov) { err = "pileup request: per_base needs segments (n_seg >= 0)"; return false; }

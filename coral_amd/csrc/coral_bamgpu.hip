@@ -12,6 +12,8 @@
 //   k_bam_verify    one workgroup: follows the chain of segment landings from the batch's KNOWN first record; a segment
 //                   whose guess is not on the chain is re-walked exactly, so record boundaries never rest on a heuristic
 //   k_bam_starts    record start offsets, in file order
+//   k_bam_keep + scan + k_bam_keep_compact   only with a record filter (keep_* of the request): the starts of the kept records,
+//                   in order, in a second array - everything below sees only those
 //   k_bam_meta      one wave per record: fixed fields, tag walk (NM, SA, CG), sizes of what the record contributes
 //   (hipcub scans)  offsets of CIGAR ops (padded to 4), read-name bytes and SA text
 //   k_bam_emit      one wave per record: CIGAR -> padded SoA op array (+ reference / query lengths), SEQ scan for non-ACGT
@@ -798,6 +800,33 @@ __global__ void k_bam_starts(const uint8_t *__restrict__ buf, int seg0, int n_se
     }
 }
 
+enum { REC_ERR_SHORT = 1, REC_ERR_FIELDS = 2, REC_ERR_TAG_B = 3, REC_ERR_TAG_TYPE = 4, REC_ERR_TAG_OVERRUN = 5 };
+
+// ---------------------------------------------------------------------------------------------
+// K_keep: the record filter (keep_* of the request; KeepRule / keep_record in coral_bam_common.h), between the boundary walk
+// and k_bam_meta.  One thread per record in one-wave workgroups (they run beside the inflate launch): the
+// three fixed fields decide, keep[i] = 0 / 1 (slot n_rec: the scan's extra 0).  After one exclusive scan, k_bam_keep_compact
+// writes the kept starts in order into a second array - not in place: record i's slot may be another thread's source.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(WAVE) void k_bam_keep(const uint8_t *__restrict__ buf, const long long *__restrict__ rec_start, long long n_rec,
+                                                   KeepRule K, long long *__restrict__ keep, int32_t *__restrict__ error) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > n_rec) return;
+    long long k = 0;
+    if (i < n_rec) {
+        const uint8_t *r = buf + rec_start[i];
+        if (ld32(r) < 32) atomicMax(error, (int)REC_ERR_SHORT);          // (the boundary walk has refused it already)
+        else k = keep_record(r[13], ld16(r + 18), ld32(r + 20), K.min_mapq, K.min_seq_length, K.require_flags, K.exclude_flags) ? 1 : 0;
+    }
+    keep[i] = k;
+}
+
+__global__ __launch_bounds__(WAVE) void k_bam_keep_compact(const long long *__restrict__ rec_start, long long n_rec, const long long *__restrict__ keep,
+                                                           const long long *__restrict__ keep_off, long long *__restrict__ kept_start) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_rec && keep[i]) kept_start[keep_off[i]] = rec_start[i];
+}
+
 // ---------------------------------------------------------------------------------------------
 // K_meta: one wave per record
 // ---------------------------------------------------------------------------------------------
@@ -806,8 +835,6 @@ struct MetaArrays {
     long long *cig_src, *seq_src, *sa_src;                         // buffer offsets
     long long *pad_ops, *name_len, *sa_len;                        // scan inputs (n + 1 entries, the last one 0)
 };
-
-enum { REC_ERR_SHORT = 1, REC_ERR_FIELDS = 2, REC_ERR_TAG_B = 3, REC_ERR_TAG_TYPE = 4, REC_ERR_TAG_OVERRUN = 5 };
 
 __global__ __launch_bounds__(256) void k_bam_meta(const uint8_t *__restrict__ buf, const long long *__restrict__ rec_start, long long n_rec,
                                                    MetaArrays M, int32_t *__restrict__ error) {
@@ -1682,6 +1709,8 @@ struct GpuDecoder {
     uint32_t *d_crc[2] = {nullptr, nullptr};
     int32_t *d_status[2] = {nullptr, nullptr};
     long long *d_seg_first = nullptr, *d_seg_land = nullptr, *d_seg_base = nullptr, *d_result = nullptr, *d_rec_start = nullptr;
+    long long *d_rec_all = nullptr;           // every record start of the batch (k_bam_starts).  d_rec_start is what everything behind
+                                              // reads: the same array, or with an active record filter a second one (the kept starts)
     int32_t *d_seg_count = nullptr, *d_seg_valid = nullptr, *d_error = nullptr, *d_na_list = nullptr, *d_na_count = nullptr;
     MetaArrays M{};
     long long *d_cig_off = nullptr, *d_name_off = nullptr, *d_sa_off = nullptr;
@@ -2117,7 +2146,8 @@ bool carve(GpuDecoder *G, void *ws, size_t bytes) {
     G->d_result = (long long *)take(64);
     G->d_error = (int32_t *)take(16);
     G->d_na_count = (int32_t *)take(16);
-    G->d_rec_start = (long long *)take(nr * 8);
+    G->d_rec_start = G->d_rec_all = (long long *)take(nr * 8);
+    if (G->req.keep.active()) G->d_rec_start = (long long *)take(nr * 8);      // the kept starts (k_bam_keep_compact)
     G->M.tid = (int32_t *)take(nr * 4); G->M.pos = (int32_t *)take(nr * 4); G->M.flag = (int32_t *)take(nr * 4);
     G->M.mapq = (int32_t *)take(nr * 4); G->M.l_seq = (int32_t *)take(nr * 4); G->M.nm = (int32_t *)take(nr * 4);
     G->M.n_cigar = (int32_t *)take(nr * 4);
@@ -2443,7 +2473,8 @@ extern "C" int coral_bamgpu_next(void *handle, int64_t out[4], void *stream_) {
         res[2] = 0;
         still_searching = !bi.last;
     }
-    const long long n_rec = res[0], carry_pos = res[1];
+    long long n_rec = res[0];
+    const long long carry_pos = res[1];
     if (G->idx.active && G->searching && n_rec > 0 && res[5] < CARRY_CAP) {
         // (a byte range that found no record start in its first batch and finds one in the bytes kept from it)
         G->error = "index request: the first record of the byte range does not start in the batch it was found in";
@@ -2458,8 +2489,32 @@ extern "C" int coral_bamgpu_next(void *handle, int64_t out[4], void *stream_) {
     G->cur_ops = G->cur_name_bytes = G->cur_sa_bytes = 0;
     if (n_rec > 0) {
         hipLaunchKernelGGL(k_bam_starts, dim3((n_seg + WAVE - 1) / WAVE), dim3(WAVE), 0, stream, buf, seg0, n_seg, G->d_seg_first, G->d_seg_count, G->d_seg_valid,
-                           G->d_seg_base, G->d_rec_start);
+                           G->d_seg_base, G->d_rec_all);
         (void)hipMemsetAsync(G->d_error, 0, 4, stream);
+    }
+    if (n_rec > 0 && G->req.keep.active()) {
+        // The record filter: from here on the batch's records are the kept ones.  Everything above (carry_pos, done, the span
+        // verdicts: byte positions of the walk) has not seen and does not see the kept count.  The flags and their offsets borrow
+        // two arrays k_bam_meta and the scans behind it refill (M.pad_ops, d_cig_off); the kept count comes back on its own
+        // (8 bytes + the error word): k_bam_meta's launch and the three scans are sized by it.
+        long long *keep = G->M.pad_ops, *keep_off = G->d_cig_off;
+        const unsigned grid = (unsigned)((n_rec + 1 + WAVE - 1) / WAVE);
+        hipLaunchKernelGGL(k_bam_keep, dim3(grid), dim3(WAVE), 0, stream, buf, G->d_rec_all, n_rec, G->req.keep, keep, G->d_error);
+        (void)G->scan(stream, keep, keep_off);                   // (over cur_n_rec + 1 = every record of the walk + the extra slot)
+        hipLaunchKernelGGL(k_bam_keep_compact, dim3(grid), dim3(WAVE), 0, stream, G->d_rec_all, n_rec, keep, keep_off, G->d_rec_start);
+        long long n_kept = 0;
+        int32_t rec_err = 0;
+        if (hipMemcpyAsync(&n_kept, keep_off + n_rec, 8, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+            hipMemcpyAsync(&rec_err, G->d_error, 4, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) {
+            G->error = std::string("record filter failed: ") + hipGetErrorString(hipGetLastError());
+            return fail(CORAL_ERR_HIP);
+        }
+        if (rec_err) { G->error = rec_error_text(rec_err); return fail(CORAL_ERR_FORMAT); }
+        if (n_kept < 0 || n_kept > n_rec) { G->error = "record filter: the kept count is out of range"; return fail(CORAL_ERR_HIP); }
+        n_rec = n_kept;
+        G->cur_n_rec = n_rec;
+    }
+    if (n_rec > 0) {
         const long long waves = n_rec + 1;
         hipLaunchKernelGGL(k_bam_meta, dim3((unsigned)waves), dim3(WAVE), 0, stream, buf, G->d_rec_start, n_rec, G->M, G->d_error);
         (void)G->scan(stream, G->M.pad_ops, G->d_cig_off);
@@ -2587,11 +2642,20 @@ extern "C" int coral_bamgpu_emit(void *handle, uint32_t *cigar_dst, int64_t *cig
                 hipMemcpy(starts.data(), G->d_rec_start, (size_t)n * 8, hipMemcpyDeviceToHost) != hipSuccess)
                 return fail(CORAL_ERR_HIP, "copy of the non-ACGT list failed");
             std::sort(J.na_list.begin(), J.na_list.end());
+            // a record ends where the next one starts - unless a record filter dropped that one: then its block_size says where
+            std::vector<uint32_t> own_size;
+            if (G->req.keep.active()) {
+                own_size.resize((size_t)na_count);
+                for (int32_t j = 0; j < na_count; ++j)
+                    if (hipMemcpy(&own_size[(size_t)j], buf + starts[(size_t)J.na_list[(size_t)j]], 4, hipMemcpyDeviceToHost) != hipSuccess)
+                        return fail(CORAL_ERR_HIP, "copy of the non-ACGT list failed");
+            }
             std::vector<long long> src((size_t)na_count), dst((size_t)na_count), len((size_t)na_count);
             J.na_off.assign((size_t)na_count + 1, 0);
             for (int32_t j = 0; j < na_count; ++j) {
                 const int32_t li = J.na_list[(size_t)j];
-                const long long rec_end = li + 1 < n ? starts[(size_t)li + 1] : G->cur_carry_pos;
+                const long long rec_end = !own_size.empty() ? starts[(size_t)li] + 4 + (long long)own_size[(size_t)j]
+                                          : li + 1 < n ? starts[(size_t)li + 1] : G->cur_carry_pos;
                 src[(size_t)j] = starts[(size_t)li] + 4;
                 len[(size_t)j] = rec_end - starts[(size_t)li] - 4;
                 dst[(size_t)j] = J.na_off[(size_t)j];

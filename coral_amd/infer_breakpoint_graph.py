@@ -1494,9 +1494,10 @@ def reconstruct_graph(args):
     for arg in sys.argv:
         commandstring += ('"{}" '.format(arg) if ' ' in arg else "{} ".format(arg))
     logging.info(_t() + commandstring)
-    from .bam import load_bam
+    from .bam import load_bam, record_filter_from_args
     from .records import DeviceRecords
-    records = DeviceRecords(load_bam(args.lr_bam, getattr(args, "device", "cuda:0")), getattr(args, "device", "cuda:0"))
+    records = DeviceRecords(load_bam(args.lr_bam, getattr(args, "device", "cuda:0"), record_filter=record_filter_from_args(args)),
+                            getattr(args, "device", "cuda:0"))
     return build_graph_from_records(records, args.cnv_seed, args.cn_seg, args.output_prefix, args.min_bp_support,
                                     args.output_bp, gc_policy=getattr(args, "gc_policy", "pause"))
 

@@ -99,16 +99,18 @@ def plot_windows(intervals, plot_bounds=None):
     return [(c, s, s + w) for c, w, st in track_windows(intervals, plot_bounds) for s in st.tolist()]
 
 
-def coverage_track_bam(bam_path, intervals, plot_bounds=None, quality_threshold=0, read_callback="nofilter", device="cuda:0", index=None):
+def coverage_track_bam(bam_path, intervals, plot_bounds=None, quality_threshold=0, read_callback="nofilter", device="cuda:0", index=None, *,
+                       record_filter=None):
     """``coverage_track`` straight from a BAM file, for any base-quality threshold (what the reference passes as ``min_mapq``,
     plot:935) and either read callback: [(chrom, start, stop, bases)], counted while the file is decoded
     (``bam.window_coverage``).  At threshold 0 with 'nofilter' it equals ``coverage_track`` on the file's records.  ``index``: as
-    in ``bam.window_coverage`` — with a BAI index beside the file only the plot's regions are decoded."""
+    in ``bam.window_coverage`` — with a BAI index beside the file only the plot's regions are decoded.  ``record_filter``: a
+    ``bam.RecordFilter`` - only the records it keeps are counted."""
     from . import bam
     windows = plot_windows(intervals, plot_bounds)
     if not windows:
         return []
-    counts = bam.window_coverage(bam_path, windows, quality_threshold, read_callback, device=device, index=index)
+    counts = bam.window_coverage(bam_path, windows, quality_threshold, read_callback, device=device, index=index, record_filter=record_filter)
     return [(c, s, e, int(n)) for (c, s, e), n in zip(windows, counts)]
 
 
@@ -134,10 +136,11 @@ class CoverageTable:
         self._counts = {(c, int(s), int(e)): int(n) for (c, s, e), n in zip(windows, counts)}
 
     @classmethod
-    def from_bam(cls, bam_path, graph_fn, region=None, min_mapq=0, read_callback="nofilter", device="cuda:0", index=None):
+    def from_bam(cls, bam_path, graph_fn, region=None, min_mapq=0, read_callback="nofilter", device="cuda:0", index=None, *, record_filter=None):
         """The windows of the plot of ``graph_fn`` (optionally restricted to ``region`` 'chr:start-end'), counted with
         ``quality_threshold=min_mapq`` as the reference does (plot:935)."""
-        track = coverage_track_bam(bam_path, parse_graph_intervals(graph_fn), parse_region(region), min_mapq, read_callback, device, index)
+        track = coverage_track_bam(bam_path, parse_graph_intervals(graph_fn), parse_region(region), min_mapq, read_callback, device, index,
+                                   record_filter=record_filter)
         return cls([(c, s, e) for c, s, e, _ in track], [n for _, _, _, n in track], min_mapq, read_callback)
 
     def __len__(self):

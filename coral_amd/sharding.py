@@ -151,19 +151,20 @@ def _gather_to_rank0(dr, buf: np.ndarray):
 LAST_LOAD = {}      # timings of the last load_bam_sharded call on this rank (bench.py): decode, gather, merge seconds
 
 
-def load_bam_sharded(path: str, rank: int, world: int, device, group=None, n_threads=None):
+def load_bam_sharded(path: str, rank: int, world: int, device, group=None, n_threads=None, record_filter=None):
     """Per-rank input: decode the rank's byte range of the BAM, upload only that shard, and gather — once — the per-record
     host fields and the read names to rank 0 (which unifies the range-local name ids).  Returns DeviceRecords; its host
     mirrors describe the whole file on rank 0 and are absent elsewhere.
 
     What travels: per rank ONE buffer of fixed-width columns + one read-name blob + its offsets (``HostMirrors.pack``) — no
     pickling, no text joins; rank 0 maps the columns in place and joins the name tables natively (``coral_names_unify``), so
-    names stay bytes until something asks for a ``str``."""
+    names stay bytes until something asks for a ``str``.  ``record_filter``: a ``bam.RecordFilter``; every rank drops the
+    records of its own byte range inside its decode."""
     import time
     from . import bam
     from .records import DeviceRecords, HostMirrors
     t0 = time.perf_counter()
-    rec = bam.load_bam(path, device, n_threads=n_threads, rank=rank, world=world)
+    rec = bam.load_bam(path, device, n_threads=n_threads, rank=rank, world=world, record_filter=record_filter)
     stats = dict(bam.LAST_DECODE)
     t1 = time.perf_counter()
     LAST_LOAD.clear()

@@ -389,8 +389,9 @@ const char *coral_bam_last_error(void);
  * start), disjoint, 0 <= start <= end; quality_threshold 0..255; read_callback 0 or 1; no want_index / want_qc on a span
  * decode; per_base only with segments (n_seg >= 0) of at most 2^28 positions in all; depth_bin >= 0, and with depth_bin > 0:
  * depth_min_mapq 0..255, depth_exclude_flags 0..0xffff, depth_count_deletions 0 or 1, no span decode, at most 2^28 bins over
- * the header's contigs (checked once the header is read: refused before anything is decoded or allocated).  A span decode is
- * not sharded: rank and world are taken as 0 and 1. */
+ * the header's contigs (checked once the header is read: refused before anything is decoded or allocated); keep_min_mapq
+ * 0..255, keep_min_seq_length 0..2^29, keep_require_flags and keep_exclude_flags 0..0xffff, and no active record filter together
+ * with want_index.  A span decode is not sharded: rank and world are taken as 0 and 1. */
 typedef struct {
     int32_t rank, world;                       /* byte range (ignored when n_spans >= 0) */
     int32_t n_spans;                           /* -1: the byte range; >= 0: only records starting inside these spans */
@@ -402,6 +403,11 @@ typedef struct {
     int32_t per_base;                          /* 0: counts per segment; else: the table per position and base (pileup) */
     int32_t depth_bin;                         /* 0: no binned-depth request; >= 1: the bin size */
     int32_t depth_min_mapq, depth_exclude_flags, depth_count_deletions;
+    /* the record filter: all four 0 = none.  A record is kept when all four tests hold. */
+    int32_t keep_min_mapq;                     /* 0..255    keep when mapq >= it               (samtools view -q) */
+    int32_t keep_min_seq_length;               /* 0..2^29   keep when l_seq >= it              (awk 'length($10) > 1000': 1001) */
+    int32_t keep_require_flags;                /* 0..0xffff keep when (flag & it) == it        (samtools view -f) */
+    int32_t keep_exclude_flags;                /* 0..0xffff keep when (flag & it) == 0         (samtools view -F) */
 } coral_bam_request_t;
 /* coral_bam_decode_range with a request; the results that ride along are read from the handle (of this call, or of
  * coral_bamgpu_host) with coral_bam_coverage_result, coral_bam_pileup_result, coral_bam_index_sizes / _fill,
@@ -469,7 +475,21 @@ typedef struct {
  *          dropped; position arithmetic is 64-bit.
  *   reads[bin_off[tid] + pos / depth_bin] += 1 for every record that takes part and has pos < LN[tid].
  *   depth_sizes -> n_ref, n_bins; depth_fill copies bin_off (n_ref + 1 int64) and the two int64 tables (n_bins each).  Exact
- *          integers, independent of scheduling, batch size and rank count; tables of byte ranges add up. */
+ *          integers, independent of scheduling, batch size and rank count; tables of byte ranges add up.
+ *
+ * Record filter (any keep_* field non-zero) - replaces the single-threaded trip through SAM text between aligning and sorting
+ * in the reference's scripts/align_nanopore_reads.sh:42-44 (samtools view -h | awk 'length($10) > 1000 || $1 ~ /^@/' |
+ * samtools view -bSq 25: keep_min_mapq 25, keep_min_seq_length 1001).  A record is kept when mapq >= keep_min_mapq, l_seq >=
+ * keep_min_seq_length, (flag & keep_require_flags) == keep_require_flags and (flag & keep_exclude_flags) == 0.  l_seq is the
+ * fixed field: a record without SEQ has length 0, where awk sees `*` with length 1 - both fail any threshold of 2 or more.
+ *   Every result of a filtered decode equals the result of the same request on a BAM file that holds only the kept records, in
+ *   the same order: the records (read-name ids numbered by first appearance among the kept records), the non-ACGT list, window
+ *   coverage, pileup, read QC including its `records` counter, and binned depth - for byte ranges (rank / world) and for span
+ *   decodes.  Exception: coral_bam_decode_stats and coral_bamgpu_stats go on counting the bytes and blocks actually read.
+ *   A dropped record is validated only as far as the boundary walk and its fixed fields go (block_size >= 32): its tags are
+ *   not walked, so a malformed tag in a dropped record is not an error, in either pipeline.  depth_min_mapq and
+ *   depth_exclude_flags stay and apply on top of the filter (a logical AND).  Not together with want_index: the virtual
+ *   offsets of a file that does not exist mean nothing. */
 int coral_bam_decode_request(const char *path, int32_t n_threads, const coral_bam_request_t *req, void **handle);
 int coral_bam_coverage_result(void *handle, int32_t n_seg, int64_t *counts);
 int coral_bam_pileup_result(void *handle, int64_t n_pos, uint32_t *counts);
@@ -525,6 +545,11 @@ int coral_bam_depth_fill(void *handle, int64_t *bin_off, int64_t *bases, int64_t
  *                      workgroups without LDS, 64 ops at a time; lanes that hit the same bin are summed in the wave and the
  *                      run's head issues one no-return 64-bit atomic, an op that spans whole bins is spread over them by
  *                      the wave); bin_off, the contig lengths and the two int64 tables live in the workspace, zeroed by `start`
+ *            keep_*      (an active record filter) k_bam_keep (one thread per record in one-wave workgroups: 0 / 1 from the fixed
+ *                      fields), one scan and k_bam_keep_compact (the kept record starts, in order, into a second array of
+ *                      record starts in the workspace) between the boundary walk and the record parse; the kept count is read
+ *                      back (8 bytes per batch) and is the batch's record count from there on: out[0] of `next`.  A batch
+ *                      whose records are all dropped is pending with out[0] = out[1] = 0 and must be emitted like any other
  *   finish        after the last batch (CORAL_ERR_ARG before): waits for `stream` once and leaves what was requested in the
  *          handle of `host` (coral_bam_coverage_result, coral_bam_pileup_result - the table is copied and summed per segment
  *          here -, coral_bam_index_sizes / _fill, coral_bam_qc_sizes / _fill, coral_bam_depth_sizes / _fill); fails when
