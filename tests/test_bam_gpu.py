@@ -12,7 +12,7 @@ import pytest
 import torch
 
 from coral_amd import bam, synth, _lib
-from tests.test_bam_io import FIELDS, _concat, _odd, assert_same
+from tests.decode_support import assert_same_records as assert_same, concat_records as _concat, odd_io_records as _odd
 
 pytestmark = pytest.mark.gpu
 

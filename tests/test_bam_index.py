@@ -2,21 +2,19 @@
 region-restricted decode behind bam.window_coverage(index=...) and bam.load_bam(regions=...).
 
 The index bytes are compared with an INDEPENDENT restatement in this module: the BAM is walked with zlib + struct, BGZF block
-by BGZF block, so every record's virtual offset comes from block boundaries found here, and the rules of SAMv1 §5 are applied
-to them without either decoder.  Region decodes are compared with the whole-file decode, filtered here."""
-import bisect
+by BGZF block, by tests/bamfile.py, so every record's virtual offset comes from block boundaries found there, and the rules of
+SAMv1 §5 are applied to them here without either decoder.  Region decodes are compared with the whole-file decode, filtered here."""
 import os
 import struct
-import zlib
 
 import numpy as np
 import pytest
 
 from coral_amd import _lib, bam, plot_coverage, synth
-from tests.test_bam_io import FIELDS
-from tests.test_window_coverage import _plot_case, host as host_coverage, make_windows, odd_records, oracle_coverage, read_bam, with_qual
+from tests.bamfile import D, EQ, I, M, N, S, X, oracle_coverage, read_bam, read_bam_bgzf
+from tests.decode_support import (RECORD_FIELDS as FIELDS, coverage_odd_records as odd_records, coverage_windows as make_windows, cpu,  # noqa: F401
+                                  host_window_coverage as host_coverage, plot_case as _plot_case, with_qual)
 
-M, I, D, N, S, H, P, EQ, X = range(9)
 PSEUDO = 37450
 NO_COOR_TID = 25                        # one behind the last contig while the records are merged and sorted
 
@@ -31,66 +29,15 @@ def reg2bin(beg, end):
 
 # ---- the restatement --------------------------------------------------------------------------------------------------------
 def walk_bam(path):
-    """(ref lengths, records [dict(tid, pos, end, flag, voff)] in file order, virtual offset behind the last record)."""
-    raw = open(path, "rb").read()
-    blocks, data, at = [], bytearray(), 0           # (file offset, first inflated byte)
-    while at < len(raw):
-        assert raw[at:at + 4] == b"\x1f\x8b\x08\x04"
-        xlen = struct.unpack_from("<H", raw, at + 10)[0]
-        bsize = None
-        x = at + 12
-        while x < at + 12 + xlen:
-            si, slen = raw[x:x + 2], struct.unpack_from("<H", raw, x + 2)[0]
-            if si == b"BC":
-                bsize = struct.unpack_from("<H", raw, x + 4)[0]
-            x += 4 + slen
-        blocks.append((at, len(data)))
-        data += zlib.decompress(raw[at + 12 + xlen:at + bsize + 1 - 8], -15)
-        at += bsize + 1
-    starts = [u for _, u in blocks]
-
-    def voffset(u):
-        if u < len(data):                            # the block that holds byte u (an empty block holds none)
-            b = bisect.bisect_right(starts, u) - 1
-            return (blocks[b][0] << 16) | (u - blocks[b][1])
-        b = bisect.bisect_left(starts, u)            # behind the last byte: the block that follows the last byte
-        return (blocks[b][0] if b < len(blocks) else len(raw)) << 16
-    assert data[:4] == b"BAM\x01"
-    o = 8 + struct.unpack_from("<i", data, 4)[0]
-    n_ref = struct.unpack_from("<i", data, o)[0]
-    o += 4
-    lens = []
-    for _ in range(n_ref):
-        ln = struct.unpack_from("<i", data, o)[0]
-        lens.append(struct.unpack_from("<i", data, o + 4 + ln)[0])
-        o += 8 + ln
+    """(ref lengths, records [dict(tid, pos, end, flag, voff)] in file order, virtual offset behind the last record): the records
+    of tests/bamfile.py, read BGZF block by BGZF block, with the end of SAMv1 section 5 (a placed read covers at least one base)."""
+    parsed = read_bam_bgzf(path)
     recs = []
-    while o < len(data):
-        bs, tid, pos, l_name, _mq, _bin, n_cig, flag, l_seq = struct.unpack_from("<iiiBBHHHi", data, o)
-        p = o + 36 + l_name
-        ops = np.frombuffer(data, dtype="<u4", count=n_cig, offset=p)
-        p += 4 * n_cig + (l_seq + 1) // 2 + l_seq
-        end_rec = o + 4 + bs
-        while p < end_rec:                           # tags: only CG:B,I matters
-            key, ty = bytes(data[p:p + 2]), chr(data[p + 2])
-            p += 3
-            if ty in "AcC":
-                p += 1
-            elif ty in "sS":
-                p += 2
-            elif ty in "iIf":
-                p += 4
-            elif ty in "ZH":
-                p = data.index(b"\0", p) + 1
-            else:
-                sub, cnt = chr(data[p]), struct.unpack_from("<I", data, p + 1)[0]
-                if key == b"CG" and sub == "I" and n_cig == 2 and ops[0] & 15 == S and ops[0] >> 4 == l_seq and ops[1] & 15 == N:
-                    ops = np.frombuffer(data, dtype="<u4", count=cnt, offset=p + 5)
-                p += 5 + {"c": 1, "C": 1, "s": 2, "S": 2}.get(sub, 4) * cnt
-        rlen = 0 if (flag & 4) or len(ops) == 0 else int((ops >> 4)[np.isin(ops & 15, (M, D, N, EQ, X))].sum())
-        recs.append(dict(tid=tid, pos=pos, end=pos + max(rlen, 1), flag=flag, voff=voffset(o)))
-        o = end_rec
-    return lens, recs, voffset(o)
+    for r in parsed.recs:
+        ops = r["ops"]
+        rlen = 0 if (r["flag"] & 4) or len(ops) == 0 else int((ops >> 4)[np.isin(ops & 15, (M, D, N, EQ, X))].sum())
+        recs.append(dict(tid=r["tid"], pos=r["pos"], end=r["pos"] + max(rlen, 1), flag=r["flag"], voff=r["voff"]))
+    return parsed.lens, recs, parsed.end_voff
 
 
 def restated_index(path):
@@ -173,11 +120,6 @@ def case(tmp_path_factory):
     whole = bam.decode_bam(small, n_threads=2)
     assert whole.n == rec.n
     return dict(dir=d, rec=rec, small=small, plain=plain, whole=whole, walked=walk_bam(small), blocks=bam.LAST_DECODE["blocks"])
-
-
-@pytest.fixture()
-def cpu(monkeypatch):
-    monkeypatch.setenv("CORAL_BAM_DECODE", "cpu")
 
 
 def index_bytes(path, device, **kw):
@@ -429,6 +371,7 @@ def coverage_checks(case, device, thresholds=(0, 7, 20), **kw):
     bam.build_index(path, device=device)
     windows = make_windows(case["rec"])
     parsed = read_bam(path)
+    parsed = (parsed.refs, parsed.recs)
     for thr in thresholds:
         for cb in ("nofilter", "all"):
             plain = bam.window_coverage(path, windows, thr, cb, device=device, index=False, **kw)

@@ -28,13 +28,11 @@ import numpy as np
 import pytest
 
 from coral_amd import _lib, bam, synth
-from tests.test_bam_io import assert_same
+from tests.bamfile import M, bgzf_blocks
+from tests.decode_support import DEVICE, PIPELINES, _pipeline_by_device, assert_same_records as assert_same  # noqa: F401
 
-M = 0
 SEG = 128 << 10                                # SEG_BYTES of coral_bamgpu.hip
 BATCH = 16 * 0xff00                            # inflated bytes of a batch of batch_bytes = 1 << 20 (16 whole BGZF blocks)
-PIPELINES = ["host", pytest.param("gpu", marks=pytest.mark.gpu)]
-DEVICE = {"host": "cpu", "gpu": "cuda:0"}
 DECOY_FILES = ("tail_tags", "tail_rejoins", "tail_zeros")
 FILES = DECOY_FILES + ("edges", "long")
 SMALL_BATCH = {"tail_tags": 1 << 20, "tail_rejoins": 1 << 20, "tail_zeros": 1 << 20, "edges": 1 << 20, "long": 2 << 20}
@@ -47,11 +45,6 @@ assert len(DECOY) == 64
 
 _HEADER_TEXT = "@HD\tVN:1.6\tSO:coordinate\n" + "".join("@SQ\tSN:%s\tLN:%d\n" % cl for cl in zip(synth.CHROMS, synth.CHR_SIZES))
 HEADER_BYTES = 12 + len(_HEADER_TEXT) + sum(len(c) + 9 for c in synth.CHROMS)      # what write_bam puts in front of the first record
-
-
-@pytest.fixture(autouse=True)
-def _pipeline_by_device(monkeypatch):
-    monkeypatch.delenv("CORAL_BAM_DECODE", raising=False)
 
 
 # ---- the restatement -----------------------------------------------------------------------------------------------------------
@@ -444,13 +437,8 @@ def test_decode_gives_the_records_back(kind, pipeline, case):
 def _linear(path, voff):
     """Virtual offsets -> offsets in the uncompressed stream (the twin's blocks compress differently; ~0 stays)."""
     data = open(path, "rb").read()
-    at, cum, table = 0, 0, {}
-    while at < len(data):
-        table[at] = cum
-        size = struct.unpack_from("<H", data, at + 16)[0] + 1
-        cum += struct.unpack_from("<I", data, at + size - 4)[0]
-        at += size
-    table[at] = cum
+    table = {at: u for at, u, _ in bgzf_blocks(data)}
+    table[len(data)] = sum(n for _, _, n in bgzf_blocks(data))
     return [v if v == 0xffffffffffffffff else table[v >> 16] + (v & 0xffff) for v in np.asarray(voff, dtype=np.uint64).tolist()]
 
 

@@ -10,10 +10,15 @@ import pytest
 import torch
 
 from coral_amd import _lib, bam
-from tests.test_read_qc import assert_equal, assert_same, assert_same_records, case  # noqa: F401  (case: the module's fixture)
+from tests.decode_support import (CORAL_ERR_ARG, CORAL_OK, assert_qc_equals_restatement as assert_equal, assert_same_qc as assert_same,
+                                  assert_same_records, gpu_decode_started, gpu_open_only, read_qc_case)
 
-CORAL_OK, CORAL_ERR_ARG = 0, -1
 WINDOWS = [("chr8", 149_000, 152_000), ("chr8", 150_000, 150_100), ("chr8", 0, 1 << 28)]
+
+
+@pytest.fixture(scope="module")
+def case(tmp_path_factory):
+    return read_qc_case(tmp_path_factory.mktemp("bam_request"))
 
 
 def segments(case):
@@ -77,10 +82,9 @@ def test_host_refuses_bad_requests(case):
 def test_gpu_refuses_the_same_requests(case):
     L = _lib.lib()
     for name, (kw, word) in bad_requests(case).items():
-        req, h, ws_bytes = _lib.bam_request(**kw), C.c_void_p(), C.c_int64(0)
-        rc = L.coral_bamgpu_open_request(case["path"].encode(), 1, 0, C.byref(req), C.byref(h), C.byref(ws_bytes))
-        assert rc == CORAL_ERR_ARG and h.value is None and ws_bytes.value == 0, name
-        assert word in L.coral_bam_last_error().decode(), name
+        rc, h, ws_bytes, message = gpu_open_only(case["path"], **kw)
+        assert rc == CORAL_ERR_ARG and h is None and ws_bytes == 0, name
+        assert word in message, name
 
 
 @pytest.mark.gpu
@@ -108,27 +112,20 @@ def test_gpu_finish_before_the_last_batch_is_refused(case):
     L = _lib.lib()
     segs = segments(case)
     want = bam._decode(case["path"], "cpu", coverage=(segs, 20, 0), records=False).counts
-    dev = torch.device("cuda:0")
-    torch.cuda.set_device(dev)
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    req, h, ws_bytes = _lib.bam_request(coverage=(segs, 20, 0)), C.c_void_p(), C.c_int64(0)
-    assert L.coral_bamgpu_open_request(case["path"].encode(), 2, 1 << 20, C.byref(req), C.byref(h), C.byref(ws_bytes)) == CORAL_OK
-    try:
-        ws = torch.empty(int(ws_bytes.value) + 256, dtype=torch.uint8, device=dev)
-        torch.cuda.current_stream(dev).synchronize()
-        assert L.coral_bamgpu_start(h, (ws.data_ptr() + 255) & ~255, int(ws_bytes.value)) == CORAL_OK
+    with gpu_decode_started(case["path"], 2, 1 << 20, coverage=(segs, 20, 0)) as d:
+        h, stream = d.h, d.stream
 
         def refused():
             return L.coral_bamgpu_finish(h, stream) == CORAL_ERR_ARG and "not finished" in L.coral_bam_last_error().decode()
         assert refused()                                         # no batch has been parsed
-        out, batches, pieces = (C.c_int64 * 4)(), 0, []
+        out, batches = (C.c_int64 * 4)(), 0
         while True:
             assert L.coral_bamgpu_next(h, out, stream) == CORAL_OK
             if not out[2]:
                 break
             assert refused()                                     # a batch is between next and emit
-            pieces.append(torch.empty(max(int(out[1]), 1), dtype=torch.int32, device=dev))
-            assert L.coral_bamgpu_emit(h, pieces[-1].data_ptr(), None, stream) == CORAL_OK
+            d.pieces.append(torch.empty(max(int(out[1]), 1), dtype=torch.int32, device=d.dev))
+            assert L.coral_bamgpu_emit(h, d.pieces[-1].data_ptr(), None, stream) == CORAL_OK
             batches += 1
         assert batches >= 3
         assert L.coral_bamgpu_finish(h, stream) == CORAL_OK
@@ -136,5 +133,3 @@ def test_gpu_finish_before_the_last_batch_is_refused(case):
         assert L.coral_bamgpu_host(h, C.byref(dh)) == CORAL_OK
         assert L.coral_bam_coverage_result(dh, len(counts), counts.ctypes.data) == CORAL_OK
         assert np.array_equal(counts, want)
-    finally:
-        assert L.coral_bamgpu_close(h) == CORAL_OK

@@ -5,16 +5,17 @@ htslib stores integer tags in the smallest type that fits (NM as C / S, rarely I
 s2 / de:f / rl (+ MD:Z, basecaller MM:Z and ML:B:C arrays), QUAL is real, the hg38 header has 3,366 contigs and spans several BGZF
 blocks.  No htslib-written file exists here (parity with htslib itself stays unpinned), so these tests cover the SPEC: the files are
 written by the pure-Python writer with every aux type the SAM specification defines, and the expected values come from an
-INDEPENDENT read of the same file in this module (gzip module + struct), not from either decoder.
+INDEPENDENT read of the same file by tests/bamfile.py (gzip module + struct), not from either decoder.
 The host decoder runs here on the CPU; the `gpu` twins run the GPU decoder on the same files.
 """
-import gzip
 import struct
 
 import numpy as np
 import pytest
 
 from coral_amd import bam, synth
+from tests.bamfile import read_bam
+from tests.decode_support import RECORD_FIELDS as FIELDS, assert_same_records as assert_same
 
 REF_ADV = (1, 0, 1, 1, 0, 0, 0, 1, 1)
 QRY_ADV = (1, 1, 0, 0, 1, 0, 0, 1, 1)
@@ -22,70 +23,25 @@ _INT = {"c": ("<b", 1), "C": ("<B", 1), "s": ("<h", 2), "S": ("<H", 2), "i": ("<
 
 
 # ---------------------------------------------------------------------------------------------
-# independent reader: gzip (BGZF is multi-member gzip, empty members included) + struct
+# independent reader: tests/bamfile.py (gzip + struct), and what a decoder has to derive from its records
 # ---------------------------------------------------------------------------------------------
 def parse_bam(path):
-    raw = gzip.open(path, "rb").read()
-    assert raw[:4] == b"BAM\x01"
-    l_text = struct.unpack_from("<i", raw, 4)[0]
-    o = 8 + l_text
-    n_ref = struct.unpack_from("<i", raw, o)[0]
-    o += 4
-    refs = []
-    for _ in range(n_ref):
-        ln = struct.unpack_from("<i", raw, o)[0]
-        refs.append((raw[o + 4:o + 4 + ln - 1].decode(), struct.unpack_from("<i", raw, o + 4 + ln)[0]))
-        o += 8 + ln
+    parsed = read_bam(path)
     recs = []
-    while o < len(raw):
-        bs, tid, pos, l_name, mapq, _bin, n_cig, flag, l_seq = struct.unpack_from("<iiiBBHHHi", raw, o)
-        end = o + 4 + bs
-        q = o + 36
-        name = raw[q:q + l_name - 1].decode()
-        q += l_name
-        cig = np.frombuffer(raw, dtype="<u4", count=n_cig, offset=q).copy()
-        q += 4 * n_cig + (l_seq + 1) // 2
-        qual = raw[q:q + l_seq]
-        q += l_seq
-        tags = []
-        while q < end:
-            key, ty = raw[q:q + 2].decode(), chr(raw[q + 2])
-            q += 3
-            if ty == "A":
-                val, q = chr(raw[q]), q + 1
-            elif ty in _INT:
-                val, q = struct.unpack_from(_INT[ty][0], raw, q)[0], q + _INT[ty][1]
-            elif ty == "f":
-                val, q = struct.unpack_from("<f", raw, q)[0], q + 4
-            elif ty in "ZH":
-                z = raw.index(b"\0", q)
-                val, q = raw[q:z].decode(), z + 1
-            elif ty == "B":
-                sub, cnt = chr(raw[q]), struct.unpack_from("<I", raw, q + 1)[0]
-                fmt, es = (("<f", 4) if sub == "f" else _INT[sub])
-                val = np.frombuffer(raw, dtype=np.dtype(fmt), count=cnt, offset=q + 5).copy()
-                q += 5 + es * cnt
-            else:
-                raise AssertionError("tag type %r" % ty)
-            tags.append((key, ty, val))
-        assert q == end
-        d = dict(tags_list=tags, tid=tid, pos=pos, mapq=mapq, flag=flag, l_seq=l_seq, name=name, qual=qual)
-        by = {k: (t, v) for k, t, v in reversed(tags)}                       # first occurrence wins (htslib bam_aux_get)
-        if "CG" in by and n_cig == 2 and (cig[0] & 15) == 4 and (cig[0] >> 4) == l_seq and (cig[1] & 15) == 3:
-            cig = by["CG"][1].astype("<u4")
-        d["cigar"] = cig
-        op, ln = (cig & 15).astype(int), (cig >> 4).astype(np.int64)
+    for r in parsed.recs:
+        d = dict(r, tags_list=r["tags"], cigar=r["ops"])
+        by = {k: (t, v) for k, t, v in reversed(r["tags"])}                  # first occurrence wins (htslib bam_aux_get)
+        op, ln = (d["cigar"] & 15).astype(int), (d["cigar"] >> 4).astype(np.int64)
         rlen = int(sum(l for o_, l in zip(op, ln) if o_ < 9 and REF_ADV[o_]))
         qinf = int(sum(l for o_, l in zip(op, ln) if o_ < 9 and QRY_ADV[o_]))
-        if (flag & 4) or len(cig) == 0:
+        if (r["flag"] & 4) or len(d["cigar"]) == 0:
             rlen = 0
-        d["end"] = pos + (rlen if rlen > 0 else 1)
-        d["qlen"] = l_seq if l_seq > 0 else qinf
+        d["end"] = r["pos"] + (rlen if rlen > 0 else 1)
+        d["qlen"] = r["l_seq"] if r["l_seq"] > 0 else qinf
         d["nm"] = int(by["NM"][1]) if "NM" in by and by["NM"][0] in _INT else 0
         d["sa"] = by["SA"][1] if "SA" in by and by["SA"][0] == "Z" else None
         recs.append(d)
-        o = end
-    return refs, recs
+    return list(zip(parsed.refs, parsed.lens)), recs
 
 
 def check_against_independent_read(rec, path):
@@ -206,7 +162,6 @@ def test_host_decoder_on_spec_shaped_files(case, tmp_path):
         want_nm = np.where(np.arange(rec.n) % 4 == 0, 0, rec.nm.numpy())
         assert np.array_equal(got.nm.numpy(), want_nm)
     else:                      # the extra tags, the NM type, QUAL and the block layout change nothing
-        from tests.test_bam_io import assert_same
         assert_same(bam.decode_bam(plain, n_threads=2), got)
     # byte ranges of the same file (what ranks of an N-GPU run decode) partition the records
     parts = [bam.decode_bam(path, n_threads=2, rank=r, world=3) for r in range(3)]
@@ -238,7 +193,6 @@ def test_gpu_decoder_on_spec_shaped_files(case, tmp_path):
     path = str(tmp_path / (case + ".bam"))
     rec, plain = write_case(case, path)
     host = bam.decode_bam(path, n_threads=3)
-    from tests.test_bam_io import FIELDS
     for batch in (0, 1 << 16, 40000):          # whole file in one batch; batches smaller than the 60 kB ML array: records and tags straddle
         got = bam.decode_bam_gpu(path, "cuda:0", batch_bytes=batch)
         torch.cuda.synchronize()

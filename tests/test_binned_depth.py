@@ -1,11 +1,10 @@
 """Whole-genome binned read depth counted during the BAM decode (bam.binned_depth, the `depth` mode): both pipelines against an
-INDEPENDENT restatement of the rule in this module.  The BAM is read with gzip + struct, the CG tag resolved, the CIGAR walked in
-plain Python and both tables filled with np.add.at.  Everything is exact integer equality.  (Neither samtools bedcov nor CNVkit
-can be run here: parity with them is not pinned; what is pinned is the rule.)"""
+INDEPENDENT restatement of the rule in this module.  The BAM is read with gzip + struct and the CG tag resolved by
+tests/bamfile.py, the CIGAR walked in plain Python and both tables filled with np.add.at.  Everything is exact integer equality.
+(Neither samtools bedcov nor CNVkit can be run here: parity with them is not pinned; what is pinned is the rule.)"""
 import ctypes as C
 import gzip
 import math
-import struct
 
 import numpy as np
 import pytest
@@ -13,11 +12,9 @@ import torch
 
 from coral_amd import _lib, bam, synth
 from coral_amd import CoRAL
+from tests.bamfile import D, EQ, I, M, N, S, X, many_ops, pairs, read_bam as _read_bam
+from tests.decode_support import CORAL_ERR_ARG, CORAL_OK, DEVICE, PIPELINES, _pipeline_by_device, gpu_open_only  # noqa: F401
 
-M, I, D, N, S, H, P, EQ, X = range(9)
-PIPELINES = ["host", pytest.param("gpu", marks=pytest.mark.gpu)]
-DEVICE = {"host": "cpu", "gpu": "cuda:0"}
-CORAL_OK, CORAL_ERR_ARG = 0, -1
 BIN_SIZES = (1, 7, 1000, 1 << 20)              # the last one is larger than every contig
 MIN_MAPQS = (0, 20, 255)
 EXCLUDES = (0, 0x704, 0x904)
@@ -28,56 +25,12 @@ HOT_POS, HOT_LEN, HOT_DEPTH = 2000, 200, 2000
 MAPQ_CYCLE = (0, 19, 20, 255)
 
 
-@pytest.fixture(autouse=True)
-def _pipeline_by_device(monkeypatch):
-    monkeypatch.delenv("CORAL_BAM_DECODE", raising=False)
-
-
 # ---- the restatement -----------------------------------------------------------------------------------------------------------
 def read_bam(path):
-    """(ref names, ref lengths, [record dicts]) straight from the bytes: tid, pos, flag, mapq, name, l_seq, the first QUAL byte and
-    the real CIGAR (CG:B,I for the placeholder) as (op, len) pairs."""
-    raw = gzip.open(path, "rb").read()
-    assert raw[:4] == b"BAM\x01"
-    o = 8 + struct.unpack_from("<i", raw, 4)[0]
-    refs, lens = [], []
-    n_ref = struct.unpack_from("<i", raw, o)[0]
-    o += 4
-    for _ in range(n_ref):
-        ln = struct.unpack_from("<i", raw, o)[0]
-        refs.append(raw[o + 4:o + 4 + ln - 1].decode())
-        lens.append(struct.unpack_from("<i", raw, o + 4 + ln)[0])
-        o += 8 + ln
-    recs = []
-    while o < len(raw):
-        bs, tid, pos, l_name, mapq, _bin, n_cig, flag, l_seq = struct.unpack_from("<iiiBBHHHi", raw, o)
-        name = raw[o + 36:o + 36 + l_name - 1].decode()
-        p = o + 36 + l_name
-        ops = list(struct.unpack_from("<%dI" % n_cig, raw, p))
-        p += 4 * n_cig + (l_seq + 1) // 2
-        qual0 = raw[p] if l_seq else None
-        p += l_seq
-        end = o + 4 + bs
-        while p < end:                                    # tags: only CG:B,I matters here
-            key, ty = raw[p:p + 2], chr(raw[p + 2])
-            p += 3
-            if ty in "AcC":
-                p += 1
-            elif ty in "sS":
-                p += 2
-            elif ty in "iIf":
-                p += 4
-            elif ty in "ZH":
-                p = raw.index(b"\0", p) + 1
-            else:
-                sub, cnt = chr(raw[p]), struct.unpack_from("<I", raw, p + 1)[0]
-                size = {"c": 1, "C": 1, "s": 2, "S": 2}.get(sub, 4)
-                if key == b"CG" and sub == "I" and len(ops) == 2 and ops[0] & 15 == S and ops[0] >> 4 == l_seq and ops[1] & 15 == N:
-                    ops = list(struct.unpack_from("<%dI" % cnt, raw, p + 5))
-                p += 5 + size * cnt
-        recs.append(dict(tid=tid, pos=pos, flag=flag, mapq=mapq, name=name, l_seq=l_seq, qual0=qual0, ops=[(w & 15, w >> 4) for w in ops]))
-        o = end
-    return refs, lens, recs
+    """(ref names, ref lengths, [record dicts]): the records of tests/bamfile.py with the first QUAL byte and the CIGAR as
+    (op, len) pairs."""
+    parsed = _read_bam(path)
+    return parsed.refs, parsed.lens, [dict(r, qual0=int(r["qual"][0]) if r["l_seq"] else None, ops=pairs(r["ops"])) for r in parsed.recs]
 
 
 def covered_positions(rec, length):
@@ -126,15 +79,6 @@ class Restatement:
 
 
 # ---- test data -----------------------------------------------------------------------------------------------------------------
-def many_ops(n):
-    """A CIGAR of exactly n >= 16 ops: leading H and S, every op of M I D N S H P = X, zero-length ops in between."""
-    cycle = [(M, 5), (I, 2), (M, 0), (D, 3), (EQ, 4), (X, 1), (I, 0), (N, 7), (P, 2), (M, 6), (D, 0)]
-    ops = [(H, 3), (S, 4)]
-    while len(ops) < n - 3:
-        ops.append(cycle[(len(ops) - 2) % len(cycle)])
-    return ops + [(M, 9), (S, 2), (H, 1)]
-
-
 def odd_records(with_no_seq):
     alns = [
         # contig "even" (7000 = 7 x 1000): bin edges, ops that cross several bins, the flags, reads at and past the contig's end
@@ -403,10 +347,9 @@ def test_gpu_refuses_the_same_requests(case):
     L = _lib.lib()
     torch.cuda.set_device(torch.device("cuda:0"))
     for name, (path, kw, word) in bad_requests(case).items():
-        req, h, ws_bytes = _lib.bam_request(**kw), C.c_void_p(), C.c_int64(0)
-        rc = L.coral_bamgpu_open_request(path.encode(), 1, 0, C.byref(req), C.byref(h), C.byref(ws_bytes))
-        assert rc == CORAL_ERR_ARG and h.value is None and ws_bytes.value == 0, name            # refused at open: nothing to allocate
-        assert word in L.coral_bam_last_error().decode(), name
+        rc, h, ws_bytes, message = gpu_open_only(path, **kw)
+        assert rc == CORAL_ERR_ARG and h is None and ws_bytes == 0, name            # refused at open: nothing to allocate
+        assert word in message, name
 
 
 @pytest.mark.gpu

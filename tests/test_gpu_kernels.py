@@ -4,12 +4,12 @@ import pytest
 import torch
 
 from coral_amd import synth
+from tests.bamfile import D, EQ, H, I, M, N, P, S, X
 
 pytestmark = pytest.mark.gpu
 
 
 def _odd_records():
-    M, I, D, N, S, H, P, EQ, X = range(9)
     alns = [
         dict(tid=0, pos=100, cigar=[(S, 5), (M, 50), (D, 700), (M, 20), (I, 3), (M, 10)], name="a"),
         dict(tid=0, pos=120, cigar=[(D, 4), (M, 30), (N, 900), (EQ, 10), (X, 2), (EQ, 5), (H, 7)], name="b"),   # leading D, N gap, =/X
@@ -30,7 +30,6 @@ def _adversarial_records(seed=5, n=160):
     """Random CIGARs built to sit on the gap filter's edges: D/N runs whose sums hover around min_gap / 2 and min_gap,
     runs of non-aligned ops longer than one and two lanes (4 and 8 ops), placed across quad, chunk (256 ops) and batch
     (2048 ops) boundaries, records that end in D/N/S, and records without any aligned op."""
-    M, I, D, N, S, H, P, EQ, X = range(9)
     rng = np.random.default_rng(seed)
     alns, pos = [], 1000
     for r in range(n):
@@ -133,7 +132,6 @@ def test_cigar_scan_record_shapes():
     from coral_amd import kernels
     from coral_amd.records import DeviceRecords
     from oracle.hostrecords import HostRecords
-    M, I, D, N, S, H, P, EQ, X = range(9)
     rng = np.random.default_rng(3)
     alns, pos = [], 50
 

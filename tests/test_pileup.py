@@ -1,7 +1,7 @@
 """Bases per position (A / C / G / T) counted during the BAM decode (bam.pileup, the `pileup` mode): both pipelines against an
-INDEPENDENT restatement of the counting rule in this module.  The BAM is read with gzip + struct, the CG tag resolved, the CIGAR
-walked in plain Python and [positions][4] built per segment.  (pysam's own count_coverage cannot be run here: parity with it is
-not pinned; what is pinned is the rule.)"""
+INDEPENDENT restatement of the counting rule in this module.  The BAM is read with gzip + struct and the CG tag resolved by
+tests/bamfile.py, the CIGAR walked in plain Python and [positions][4] built per segment.  (pysam's own count_coverage cannot be
+run here: parity with it is not pinned; what is pinned is the rule.)"""
 import array
 import ctypes as C
 import gzip
@@ -9,75 +9,24 @@ import struct
 
 import numpy as np
 import pytest
-import torch
 
 from coral_amd import _lib, bam, synth
 from coral_amd import CoRAL
+from tests.bamfile import D, EQ, H, I, M, N, S, X, many_ops, pairs, read_bam as _read_bam
+from tests.decode_support import CORAL_ERR_ARG, CORAL_OK, DEVICE, PIPELINES, _pipeline_by_device, gpu_decode, gpu_open_only  # noqa: F401
 
-M, I, D, N, S, H, P, EQ, X = range(9)
 THRESHOLDS = (0, 1, 15, 255)
 CALLBACKS = ("nofilter", "all")
 CB_CODE = {"nofilter": 0, "all": 1}
-PIPELINES = ["host", pytest.param("gpu", marks=pytest.mark.gpu)]
-DEVICE = {"host": "cpu", "gpu": "cuda:0"}
-CORAL_OK, CORAL_ERR_ARG = 0, -1
 COLUMN = {1: 0, 2: 1, 4: 2, 8: 3}
 EDGE_QUAL = bytes([0, 14, 15, 254])
 
 
-@pytest.fixture(autouse=True)
-def _pipeline_by_device(monkeypatch):
-    monkeypatch.delenv("CORAL_BAM_DECODE", raising=False)
-
-
 # ---- the restatement -----------------------------------------------------------------------------------------------------------
 def read_bam(path):
-    """(ref names, [record dicts]) straight from the bytes: tid, pos, flag, name, the real CIGAR (CG:B,I for the placeholder)
-    as (op, len) pairs, SEQ codes, QUAL."""
-    raw = gzip.open(path, "rb").read()
-    assert raw[:4] == b"BAM\x01"
-    o = 8 + struct.unpack_from("<i", raw, 4)[0]
-    refs = []
-    n_ref = struct.unpack_from("<i", raw, o)[0]
-    o += 4
-    for _ in range(n_ref):
-        ln = struct.unpack_from("<i", raw, o)[0]
-        refs.append(raw[o + 4:o + 4 + ln - 1].decode())
-        o += 8 + ln
-    recs = []
-    while o < len(raw):
-        bs, tid, pos, l_name, _mapq, _bin, n_cig, flag, l_seq = struct.unpack_from("<iiiBBHHHi", raw, o)
-        name = raw[o + 36:o + 36 + l_name - 1].decode()
-        p = o + 36 + l_name
-        ops = list(struct.unpack_from("<%dI" % n_cig, raw, p))
-        p += 4 * n_cig
-        packed = np.frombuffer(raw, dtype=np.uint8, count=(l_seq + 1) // 2, offset=p)
-        codes = np.empty(2 * len(packed), dtype=np.uint8)
-        codes[0::2], codes[1::2] = packed >> 4, packed & 15
-        p += (l_seq + 1) // 2
-        qual = np.frombuffer(raw, dtype=np.uint8, count=l_seq, offset=p)
-        p += l_seq
-        end = o + 4 + bs
-        while p < end:                                    # tags: only CG:B,I matters here
-            key, ty = raw[p:p + 2], chr(raw[p + 2])
-            p += 3
-            if ty in "AcC":
-                p += 1
-            elif ty in "sS":
-                p += 2
-            elif ty in "iIf":
-                p += 4
-            elif ty in "ZH":
-                p = raw.index(b"\0", p) + 1
-            else:
-                sub, cnt = chr(raw[p]), struct.unpack_from("<I", raw, p + 1)[0]
-                size = {"c": 1, "C": 1, "s": 2, "S": 2}.get(sub, 4)
-                if key == b"CG" and sub == "I" and len(ops) == 2 and ops[0] & 15 == S and ops[0] >> 4 == l_seq and ops[1] & 15 == N:
-                    ops = list(struct.unpack_from("<%dI" % cnt, raw, p + 5))
-                p += 5 + size * cnt
-        recs.append(dict(tid=tid, pos=pos, flag=flag, name=name, ops=[(w & 15, w >> 4) for w in ops], codes=codes[:l_seq], qual=qual))
-        o = end
-    return refs, recs
+    """(ref names, [record dicts]): the records of tests/bamfile.py with the CIGAR as (op, len) pairs."""
+    parsed = _read_bam(path)
+    return parsed.refs, [dict(r, ops=pairs(r["ops"])) for r in parsed.recs]
 
 
 def counted_bases(parsed, threshold, read_callback):
@@ -122,15 +71,6 @@ def restated_table(bases, segments):
 
 
 # ---- test data -----------------------------------------------------------------------------------------------------------------
-def many_ops(n):
-    """A CIGAR of exactly n ops: leading H and S, every op of M I D N S H P = X, zero-length ops in between."""
-    cycle = [(M, 5), (I, 2), (M, 0), (D, 3), (EQ, 4), (X, 1), (I, 0), (N, 7), (P, 2), (M, 6), (D, 0)]
-    ops = [(H, 3), (S, 4)]
-    while len(ops) < n - 3:
-        ops.append(cycle[(len(ops) - 2) % len(cycle)])
-    return ops + [(M, 9), (S, 2), (H, 1)]
-
-
 HOT_POS, HOT_LEN, HOT_DEPTH = 500_000, 200, 2000
 
 
@@ -435,38 +375,18 @@ def test_host_refuses_bad_requests(case):
 def test_gpu_refuses_the_same_requests(case):
     L = _lib.lib()
     for name, (kw, word) in bad_requests().items():
-        req, h, ws_bytes = _lib.bam_request(**kw), C.c_void_p(), C.c_int64(0)
-        rc = L.coral_bamgpu_open_request(case["path"].encode(), 1, 0, C.byref(req), C.byref(h), C.byref(ws_bytes))
-        assert rc == CORAL_ERR_ARG and h.value is None and ws_bytes.value == 0, name
-        assert word in L.coral_bam_last_error().decode(), name
+        rc, h, ws_bytes, message = gpu_open_only(case["path"], **kw)
+        assert rc == CORAL_ERR_ARG and h is None and ws_bytes == 0, name
+        assert word in message, name
     # a wrong n_pos, on the handle of a GPU decode
     segs = segment_array()
     n_pos = int((segs[2].astype(np.int64) - segs[1]).sum())
-    dev = torch.device("cuda:0")
-    torch.cuda.set_device(dev)
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    req, h, ws_bytes = _lib.bam_request(coverage=(segs, 0, 0), per_base=True), C.c_void_p(), C.c_int64(0)
-    assert L.coral_bamgpu_open_request(case["path"].encode(), 2, 0, C.byref(req), C.byref(h), C.byref(ws_bytes)) == CORAL_OK
-    try:
-        ws = torch.empty(int(ws_bytes.value) + 256, dtype=torch.uint8, device=dev)
-        torch.cuda.current_stream(dev).synchronize()
-        assert L.coral_bamgpu_start(h, (ws.data_ptr() + 255) & ~255, int(ws_bytes.value)) == CORAL_OK
-        out, pieces = (C.c_int64 * 4)(), []
-        while True:
-            assert L.coral_bamgpu_next(h, out, stream) == CORAL_OK
-            if not out[2]:
-                break
-            pieces.append(torch.empty(max(int(out[1]), 1), dtype=torch.int32, device=dev))
-            assert L.coral_bamgpu_emit(h, pieces[-1].data_ptr(), None, stream) == CORAL_OK
-        assert L.coral_bamgpu_finish(h, stream) == CORAL_OK
-        dh, table = C.c_void_p(), np.zeros((n_pos + 1, 4), dtype=np.uint32)
-        assert L.coral_bamgpu_host(h, C.byref(dh)) == CORAL_OK
+    with gpu_decode(case["path"], coverage=(segs, 0, 0), per_base=True) as d:
+        table = np.zeros((n_pos + 1, 4), dtype=np.uint32)
         for wrong in (n_pos - 1, n_pos + 1, 0):
-            assert L.coral_bam_pileup_result(dh, wrong, table.ctypes.data) == CORAL_ERR_ARG
-        assert L.coral_bam_pileup_result(dh, n_pos, table.ctypes.data) == CORAL_OK
+            assert L.coral_bam_pileup_result(d.dh, wrong, table.ctypes.data) == CORAL_ERR_ARG
+        assert L.coral_bam_pileup_result(d.dh, n_pos, table.ctypes.data) == CORAL_OK
         assert np.array_equal(table[:n_pos], restated_table(case["bases"][(0, "nofilter")], SEGMENTS))
-    finally:
-        assert L.coral_bamgpu_close(h) == CORAL_OK
 
 
 @pytest.mark.parametrize("regions,thr,cb", [

@@ -1,58 +1,27 @@
 """Per-read length and base-quality statistics counted during the BAM decode (bam.read_qc, the `qc` mode): both pipelines against
-an INDEPENDENT restatement of the reference's scripts/report_nanopore_qc.py in this module.  The BAM is read with gzip + struct,
-and the script's own formulas (len, np.mean of the quality values, np.percentile) are applied to the primary records with SEQ —
-one per FASTQ record the file was aligned from.  (The script itself reads the FASTQ through pysam.FastxFile, which cannot be
-run here: parity with it is not pinned)"""
-import gzip
+an INDEPENDENT restatement of the reference's scripts/report_nanopore_qc.py: restate_read_qc, which tests/test_bam_request.py
+checks against as well and which therefore lives next to the reader in tests/bamfile.py, and restated_summary here.  The BAM is
+read with gzip + struct in tests/bamfile.py, and the script's own formulas (len, np.mean of the quality values, np.percentile)
+are applied to the primary records with SEQ — one per FASTQ record the file was aligned from.  (The script itself reads the
+FASTQ through pysam.FastxFile, which cannot be run here: parity with it is not pinned)"""
 import json
 import os
-import struct
 import warnings
 
 import numpy as np
 import pytest
 
 from coral_amd import bam, synth
-
-M, I, D, N, S, H, P, EQ, X = range(9)
+from tests.bamfile import M, read_bam as _read_bam, restate_read_qc as restate
+from tests.decode_support import (LONG_READ, assert_qc_equals_restatement as assert_equal, assert_same_qc as assert_same, assert_same_records,
+                                  read_qc_case)
 
 
 # ---- the restatement -----------------------------------------------------------------------------------------------------------
 def read_bam(path):
-    """Every record straight from the bytes: flag, mapq, l_seq, QUAL (the record's own n_cigar_op locates it)."""
-    raw = gzip.open(path, "rb").read()
-    assert raw[:4] == b"BAM\x01"
-    o = 8 + struct.unpack_from("<i", raw, 4)[0]
-    n_ref = struct.unpack_from("<i", raw, o)[0]
-    o += 4
-    for _ in range(n_ref):
-        o += 8 + struct.unpack_from("<i", raw, o)[0]
-    recs = []
-    while o < len(raw):
-        bs, _tid, _pos, l_name, mapq, _bin, n_cig, flag, l_seq = struct.unpack_from("<iiiBBHHHi", raw, o)
-        p = o + 36 + l_name + 4 * n_cig + (l_seq + 1) // 2
-        recs.append(dict(flag=flag, mapq=mapq, l_seq=l_seq, n_cig=n_cig, qual=np.frombuffer(raw, dtype=np.uint8, count=l_seq, offset=p)))
-        o += 4 + bs
-    return recs, len(raw)
-
-
-def restate(recs):
-    """What the script collects (lines 35-48) over the reads, plus the counters and the histogram as the issue words them."""
-    reads = [r for r in recs if r["flag"] & 0x900 == 0 and r["l_seq"] > 0]          # `if sequence:`
-    mean_lengths = [r["l_seq"] for r in reads]                                        # len(sequence)
-    with_q = [r for r in reads if r["qual"][0] != 0xFF]
-    mean_qualities = [np.mean(np.array(r["qual"].tolist())) for r in with_q]          # np.mean(np.array([ints]))
-    hist = np.zeros(256, dtype=np.int64)
-    for r in with_q:
-        hist += np.bincount(r["qual"], minlength=256)
-    counters = dict(n_records=len(recs), n_reads=len(reads), n_secondary=sum(1 for r in recs if r["flag"] & 0x100),
-                    n_supplementary=sum(1 for r in recs if r["flag"] & 0x800), n_unmapped=sum(1 for r in reads if r["flag"] & 4),
-                    n_no_seq=sum(1 for r in recs if r["flag"] & 0x900 == 0 and r["l_seq"] == 0), n_no_qual=len(reads) - len(with_q),
-                    total_bases=sum(mean_lengths))
-    return dict(reads=reads, mean_lengths=mean_lengths, mean_qualities=mean_qualities, hist=hist, counters=counters,
-                length=np.array(mean_lengths, dtype=np.int32),
-                qual_sum=np.array([int(r["qual"].astype(np.int64).sum()) if r["qual"][0] != 0xFF else -1 for r in reads], dtype=np.int64),
-                mapq=np.array([r["mapq"] for r in reads], dtype=np.int32), flag=np.array([r["flag"] for r in reads], dtype=np.int32))
+    """(every record straight from the bytes, the length of the inflated stream)"""
+    parsed = _read_bam(path)
+    return parsed.recs, parsed.n_bytes
 
 
 def restated_summary(want):
@@ -70,88 +39,13 @@ def restated_summary(want):
     return out
 
 
-# ---- test data -----------------------------------------------------------------------------------------------------------------
-LONG_READ = 300_000
-EDGE_QUAL = bytes([0, 93, 200, 254])
-
-
-def odd_records():
-    big = [(M, 3), (I, 1), (D, 2)] * 22000 + [(M, 5)]            # 66001 ops -> CG tag; the record's own n_cigar_op is 2
-    alns = [
-        dict(tid=7, pos=150_000, cigar=[(S, 5), (M, 50), (D, 70), (M, 30)], name="edgeq"),
-        dict(tid=7, pos=150_005, cigar=[(M, 120)], flag=0x100, name="secondary"),
-        dict(tid=7, pos=150_010, cigar=[(H, 50), (M, 100), (H, 30)], flag=0x800, name="supp_hard"),
-        dict(tid=7, pos=150_015, cigar=[(M, 60)], flag=4, name="unmapped", mapq=0),
-        dict(tid=7, pos=150_020, cigar=[(M, 200)], has_seq=0, name="noseq"),
-        dict(tid=7, pos=150_025, cigar=[(M, 90)], name="withq_a", mapq=13),
-        dict(tid=7, pos=150_026, cigar=[(M, 333)], name="noqual"),
-        dict(tid=7, pos=150_027, cigar=[(M, 91)], name="withq_b"),
-    ]
-    alns += [dict(tid=7, pos=150_030 + k, cigar=[(M, ln)], name="len%d" % ln, mapq=20 + k) for k, ln in enumerate((1, 15, 16, 17, 65))]
-    alns += [dict(tid=7, pos=150_070, cigar=big, name="longcigar"),
-             dict(tid=7, pos=150_080, cigar=[(S, 100), (M, LONG_READ - 100)], name="huge"),
-             dict(tid=7, pos=150_090, cigar=[(H, 10), (M, 77)], name="hard_primary")]
-    return synth.records_from_alignments(alns)
-
-
-def make_records(n=500):
-    return synth.merge_sorted(synth.generate(synth.scaled_config("tiny", n), "cpu"), odd_records())
-
-
-def writer_options(rec):
-    names = rec.materialise_names()
-    name_of = lambda i: names[int(rec.name_id[i])]
-    qlen = rec.qlen.numpy()
-
-    def qual(i):
-        nm, n = name_of(i), int(qlen[i])
-        if nm == "edgeq":
-            return (EDGE_QUAL * (n // 4 + 1))[:n]
-        if nm.startswith("len"):
-            return bytes((7 * k + 3) % 94 for k in range(n))
-        if nm == "huge":
-            k = np.arange(n, dtype=np.int64)
-            return ((k * k + 11 * k + 5) % 95).astype(np.uint8).tobytes()
-        return None
-    with_qual = lambda i: name_of(i) != "noqual" and (i % 4 != 2 or name_of(i).startswith("withq"))
-    return dict(qual=qual, with_qual=with_qual)
-
-
 @pytest.fixture(scope="module")
 def case(tmp_path_factory):
-    d = tmp_path_factory.mktemp("readqc")
-    rec = make_records()
-    opts = writer_options(rec)
-    path, small = str(d / "mixed.bam"), str(d / "mixed_small_blocks.bam")
-    bam.write_bam(rec, path, seed=5, fast_seq=True, **opts)
-    bam.write_bam(rec, small, seed=5, fast_seq=True, block_size=1500, empty_block_every=5, **opts)
-    recs, n_bytes = read_bam(path)
-    assert len(recs) == rec.n
-    none = str(d / "no_reads.bam")
-    bam.write_bam(synth.records_from_alignments([dict(tid=7, pos=100, cigar=[(M, 50)], flag=0x100, name="s"),
-                                                 dict(tid=7, pos=200, cigar=[(M, 50)], has_seq=0, name="p"),
-                                                 dict(tid=7, pos=300, cigar=[(H, 5), (M, 50)], flag=0x800, name="t")]), none, with_qual=True)
-    return dict(rec=rec, path=path, small=small, none=none, recs=recs, want=restate(recs), inflated_bytes=n_bytes)
+    return read_qc_case(tmp_path_factory.mktemp("readqc"))
 
 
 def host(path, **kw):
     return bam.read_qc(path, device="cpu", **kw)
-
-
-def assert_equal(got, want, what=""):
-    for k in ("length", "qual_sum", "mapq", "flag"):
-        a = getattr(got, k)
-        assert a.dtype == want[k].dtype and np.array_equal(a, want[k]), (what, k)
-    assert got.base_quality_hist.dtype == np.int64 and np.array_equal(got.base_quality_hist, want["hist"]), what
-    assert got.counters == want["counters"], what
-    for k, v in want["counters"].items():
-        assert getattr(got, k) == v
-
-
-def assert_same(a, b, what=""):
-    for k in ("length", "qual_sum", "mapq", "flag", "base_quality_hist"):
-        assert np.array_equal(getattr(a, k), getattr(b, k)), (what, k)
-    assert a.counters == b.counters, what
 
 
 # ---- the restatement sees what was planted ---------------------------------------------------------------------------------------
@@ -279,17 +173,6 @@ def test_gpu_pipeline_ranges_merge_to_the_whole(case):
     for path, batch in ((case["path"], 0), (case["small"], 1 << 20)):
         parts = [bam.read_qc(path, device="cuda:0", rank=r, world=3, batch_bytes=batch) for r in range(3)]
         assert_equal(bam.merge_read_qc(parts), case["want"], path)
-
-
-RECORD_COLUMNS = ("tid", "pos", "end", "flag", "mapq", "qlen", "has_seq", "nm", "name_id", "n_cigar", "cigar_off", "cigar", "sa_off", "sa",
-                  "sa_nm", "nonacgt_rec", "nonacgt_pos")
-
-
-def assert_same_records(a, b):
-    assert a.n == b.n and a.n_names == b.n_names and a.header_chroms == b.header_chroms
-    for k in RECORD_COLUMNS:
-        assert np.array_equal(getattr(a, k).cpu().numpy(), getattr(b, k).cpu().numpy()), k
-    assert a.materialise_names() == b.materialise_names()
 
 
 @pytest.mark.gpu

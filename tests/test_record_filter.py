@@ -3,24 +3,19 @@ the result of the same request on a BAM file that holds only the kept records, i
 batches, byte ranges and a batch whose records are all dropped.  The oracles are the unfiltered decode masked in numpy
 (select_records) and a second file written from the kept records.  Everything is exact equality."""
 import ctypes as C
-import gzip
 import json
 import os
-import struct
 
 import numpy as np
 import pytest
 import torch
 
 from coral_amd import CoRAL, _lib, bam, synth
+from tests.bamfile import D, EQ, I, M, N, S, X, read_bam
+from tests.decode_support import (CORAL_ERR_ARG, CORAL_OK, DEVICE, PIPELINES, _pipeline_by_device, assert_same_qc,  # noqa: F401
+                                  assert_same_records as assert_same, concat_records as concat, gpu_open_only)
 
-M, I, D, N, S, H, P, EQ, X = range(9)
-PIPELINES = ["host", pytest.param("gpu", marks=pytest.mark.gpu)]
-DEVICE = {"host": "cpu", "gpu": "cuda:0"}
-CORAL_OK, CORAL_ERR_ARG = 0, -1
 CHROMS, LENGTHS = ["ctgA", "ctgB", "ctgC"], [400_000, 300_000, 350_000]
-FIELDS = ("tid", "pos", "end", "flag", "mapq", "qlen", "has_seq", "nm", "name_id", "n_cigar", "cigar_off", "cigar", "sa_off", "sa", "sa_nm",
-          "nonacgt_rec", "nonacgt_pos")
 BLOCK = 1500                                   # payload bytes per BGZF block: nearly every record straddles blocks
 BATCH = 1 << 20                                # the smallest batch the GPU pipeline cuts (whatever smaller value is asked for)
 N_REC = 320
@@ -32,25 +27,11 @@ FILTERS = {
 }
 
 
-@pytest.fixture(autouse=True)
-def _pipeline_by_device(monkeypatch):
-    monkeypatch.delenv("CORAL_BAM_DECODE", raising=False)
-
-
 def mask_of(rec, f):
     """The rule, in numpy, on the columns of an unfiltered decode."""
     flag, mapq = rec.flag.numpy(), rec.mapq.numpy()
     l_seq = rec.has_seq.numpy() * rec.qlen.numpy()
     return (mapq >= f.min_mapq) & (l_seq >= f.min_seq_length) & ((flag & f.require_flags) == f.require_flags) & ((flag & f.exclude_flags) == 0)
-
-
-def assert_same(a, b):
-    assert a.n == b.n
-    for k in FIELDS:
-        x, y = getattr(a, k).cpu().numpy(), getattr(b, k).cpu().numpy()
-        assert x.shape == y.shape and np.array_equal(x, y), k
-    assert a.n_names == b.n_names and a.materialise_names() == b.materialise_names()
-    assert a.header_chroms == b.header_chroms and a.header_lens == b.header_lens
 
 
 # ---- test data -----------------------------------------------------------------------------------------------------------------
@@ -127,18 +108,7 @@ def quality(rec):
 
 def stream_layout(path):
     """(start, end) of every record in the file's uncompressed stream."""
-    raw = gzip.open(path, "rb").read()
-    o = 8 + struct.unpack_from("<i", raw, 4)[0]
-    n_ref = struct.unpack_from("<i", raw, o)[0]
-    o += 4
-    for _ in range(n_ref):
-        o += 8 + struct.unpack_from("<i", raw, o)[0]
-    out = []
-    while o < len(raw):
-        e = o + 4 + struct.unpack_from("<i", raw, o)[0]
-        out.append((o, e))
-        o = e
-    return out
+    return [(r["start"], r["start"] + r["size"]) for r in read_bam(path).recs]
 
 
 @pytest.fixture(scope="module")
@@ -208,12 +178,6 @@ def test_regions_with_a_filter(case, pipe):
 
 
 # ---- 2. the file of the kept records -------------------------------------------------------------------------------------------
-def assert_same_qc(a, b):
-    for k in ("length", "qual_sum", "mapq", "flag", "base_quality_hist"):
-        assert np.array_equal(getattr(a, k), getattr(b, k)), k
-    assert a.counters == b.counters
-
-
 @pytest.mark.parametrize("pipe", PIPELINES)
 def test_results_equal_those_of_the_file_of_kept_records(case, pipe):
     dev = DEVICE[pipe]
@@ -312,23 +276,6 @@ def test_a_batch_whose_records_are_all_dropped(run_case):
 
 
 # ---- 5. byte ranges ------------------------------------------------------------------------------------------------------------
-def concat(parts):
-    """Records of consecutive byte ranges put together again (read-name ids are local to a range: compare by name)."""
-    out = {}
-    for k in FIELDS:
-        if k not in ("cigar_off", "sa_off", "nonacgt_rec", "name_id"):
-            out[k] = np.concatenate([getattr(p, k).cpu().numpy() for p in parts])
-    out["n_cigar_padded"] = np.concatenate([np.diff(p.cigar_off.cpu().numpy()) for p in parts])
-    out["sa_count"] = np.concatenate([np.diff(p.sa_off.cpu().numpy()) for p in parts])
-    base, na = 0, []
-    for p in parts:
-        na.append(p.nonacgt_rec.cpu().numpy() + base)
-        base += p.n
-    out["nonacgt_rec"] = np.concatenate(na)
-    out["names"] = [p.names[i] for p in parts for i in p.name_id.tolist()]
-    return out
-
-
 @pytest.mark.parametrize("pipe", PIPELINES)
 def test_byte_ranges_with_a_filter(case, pipe):
     dev = DEVICE[pipe]
@@ -427,16 +374,13 @@ def test_gpu_refuses_the_same_filters(case):
     L = _lib.lib()
     torch.cuda.set_device(torch.device("cuda:0"))
     for name, (kw, word) in BAD_REQUESTS.items():
-        req, h, ws_bytes = _lib.bam_request(**kw), C.c_void_p(), C.c_int64(0)
-        rc = L.coral_bamgpu_open_request(case["A"].encode(), 1, 0, C.byref(req), C.byref(h), C.byref(ws_bytes))
-        assert rc == CORAL_ERR_ARG and h.value is None and ws_bytes.value == 0, name
-        assert word in L.coral_bam_last_error().decode(), name
+        rc, h, ws_bytes, message = gpu_open_only(case["A"], **kw)
+        assert rc == CORAL_ERR_ARG and h is None and ws_bytes == 0, name
+        assert word in message, name
     sizes = {}
     for key, keep in (("none", None), ("zero", (0, 0, 0, 0)), ("active", (20, 0, 0, 0))):   # open only: no GPU work
-        req, h, ws_bytes = _lib.bam_request(keep=keep), C.c_void_p(), C.c_int64(0)
-        assert L.coral_bamgpu_open_request(case["A"].encode(), 1, 0, C.byref(req), C.byref(h), C.byref(ws_bytes)) == CORAL_OK
-        L.coral_bamgpu_close(h)
-        sizes[key] = ws_bytes.value
+        rc, _, sizes[key], _ = gpu_open_only(case["A"], keep=keep)
+        assert rc == CORAL_OK
     assert sizes["none"] == sizes["zero"] < sizes["active"]                                   # the second array of record starts
 
 

@@ -1,150 +1,27 @@
 """Window coverage with a base-quality threshold, counted during the BAM decode (bam.window_coverage, the coverage track of
-`plot` at any --min_mapq): both pipelines against an INDEPENDENT restatement of pysam count_coverage in this module (the BAM
-is read with gzip + struct, CIGAR / SEQ / QUAL walked per record), and against the plot goldens at threshold 0."""
-import gzip
-import json
-import os
-import struct
-
+`plot` at any --min_mapq): both pipelines against an INDEPENDENT restatement of pysam count_coverage (oracle_coverage, which
+tests/test_bam_index.py checks against as well and which therefore lives next to the reader in tests/bamfile.py: the BAM is
+read there with gzip + struct, CIGAR / SEQ / QUAL walked per record), and against the plot goldens at threshold 0."""
 import numpy as np
 import pytest
 
 from coral_amd import bam, plot_coverage, synth
+from tests.bamfile import D, I, M, S, oracle_coverage, read_bam as _read_bam
+from tests.decode_support import (coverage_odd_records as odd_records, coverage_windows as make_windows, host_window_coverage as host,
+                                  plot_case as _plot_case, with_qual)
 
-M, I, D, N, S, H, P, EQ, X = range(9)
 THRESHOLDS = (0, 1, 7, 20, 30, 61, 255)
 CALLBACKS = ("nofilter", "all")
 
 
-# ---- the oracle: pysam AlignmentFile.count_coverage, summed over the four bases -------------------------------------------
 def read_bam(path):
-    """[(ref names), [record dicts]] straight from the bytes: tid, pos, flag, ops (the CG:B,I CIGAR for the placeholder),
-    SEQ codes, QUAL."""
-    raw = gzip.open(path, "rb").read()
-    assert raw[:4] == b"BAM\x01"
-    o = 8 + struct.unpack_from("<i", raw, 4)[0]
-    refs = []
-    n_ref = struct.unpack_from("<i", raw, o)[0]
-    o += 4
-    for _ in range(n_ref):
-        ln = struct.unpack_from("<i", raw, o)[0]
-        refs.append(raw[o + 4:o + 4 + ln - 1].decode())
-        o += 8 + ln
-    recs = []
-    while o < len(raw):
-        bs, tid, pos, l_name, _mapq, _bin, n_cig, flag, l_seq = struct.unpack_from("<iiiBBHHHi", raw, o)
-        p = o + 36 + l_name
-        ops = np.frombuffer(raw, dtype="<u4", count=n_cig, offset=p).copy()
-        p += 4 * n_cig
-        packed = np.frombuffer(raw, dtype=np.uint8, count=(l_seq + 1) // 2, offset=p)
-        codes = np.empty(2 * len(packed), dtype=np.uint8)
-        codes[0::2], codes[1::2] = packed >> 4, packed & 15
-        p += (l_seq + 1) // 2
-        qual = np.frombuffer(raw, dtype=np.uint8, count=l_seq, offset=p)
-        p += l_seq
-        end = o + 4 + bs
-        while p < end:                                    # tags: only CG:B,I matters here
-            key, ty = raw[p:p + 2], chr(raw[p + 2])
-            p += 3
-            if ty in "AcC":
-                p += 1
-            elif ty in "sS":
-                p += 2
-            elif ty in "iIf":
-                p += 4
-            elif ty in "ZH":
-                p = raw.index(b"\0", p) + 1
-            else:
-                sub, cnt = chr(raw[p]), struct.unpack_from("<I", raw, p + 1)[0]
-                size = {"c": 1, "C": 1, "s": 2, "S": 2}.get(sub, 4)
-                if key == b"CG" and sub == "I" and len(ops) == 2 and ops[0] & 15 == S and ops[0] >> 4 == l_seq and ops[1] & 15 == N:
-                    ops = np.frombuffer(raw, dtype="<u4", count=cnt, offset=p + 5).copy()
-                p += 5 + size * cnt
-        recs.append(dict(tid=tid, pos=pos, flag=flag, ops=ops, codes=codes[:l_seq], qual=qual))
-        o = end
-    return refs, recs
-
-
-def oracle_coverage(parsed, windows, threshold, read_callback):
-    """For every window: #(read, qpos, refpos) with the read on the contig (and, with 'all', none of the flags 0x704), SEQ
-    present, (qpos, refpos) an aligned pair of an M / = / X op inside the window, SEQ code A/C/G/T, and threshold 0 or QUAL
-    present (first byte not 0xff) and QUAL[qpos] >= threshold."""
-    refs, recs = parsed
-    hits = {}
-    for r in recs:
-        if r["tid"] < 0 or len(r["codes"]) == 0 or (read_callback == "all" and r["flag"] & 0x704):
-            continue
-        if threshold > 0 and r["qual"][0] == 0xFF:
-            continue
-        q, ref, qs, rs = 0, r["pos"], [], []
-        for w in r["ops"]:
-            op, ln = int(w & 15), int(w >> 4)
-            if op in (M, EQ, X):
-                qs.append(np.arange(q, q + ln))
-                rs.append(np.arange(ref, ref + ln))
-            q += ln if op in (M, I, S, EQ, X) else 0
-            ref += ln if op in (M, D, N, EQ, X) else 0
-        if not qs:
-            continue
-        qp, rp = np.concatenate(qs), np.concatenate(rs)
-        keep = qp < len(r["codes"])
-        qp, rp = qp[keep], rp[keep]
-        c = r["codes"][qp]
-        ok = (c == 1) | (c == 2) | (c == 4) | (c == 8)
-        if threshold > 0:
-            ok &= r["qual"][qp] >= threshold
-        hits.setdefault(r["tid"], []).append(rp[ok])
-    hits = {t: np.sort(np.concatenate(v)) for t, v in hits.items()}
-    out = []
-    for chrom, a, b in windows:
-        h = hits.get(refs.index(chrom), np.zeros(0, dtype=np.int64))
-        out.append(int(np.searchsorted(h, b) - np.searchsorted(h, a)))
-    return np.array(out, dtype=np.int64)
-
-
-# ---- test data ---------------------------------------------------------------------------------------------------------------
-def odd_records():
-    """Hand-written records: the flags the 'all' callback drops, no SEQ, N bases, an unmapped read with a CIGAR, a CIGAR of
-    more than 65 535 ops (CG tag), soft / hard clips, =, X, D, N."""
-    big = [(M, 3), (I, 1), (D, 2)] * 22000 + [(M, 5)]            # 66001 ops -> CG tag
-    return synth.records_from_alignments([
-        dict(tid=7, pos=150_000, cigar=[(S, 5), (M, 50), (D, 70), (M, 20), (I, 3), (M, 10)], name="a", nonacgt=[150_001, 150_140]),
-        dict(tid=7, pos=150_010, cigar=[(H, 9), (EQ, 10), (X, 2), (N, 90), (M, 30), (H, 7)], name="b", flag=0x10),
-        dict(tid=7, pos=150_020, cigar=[(M, 60)], flag=4, name="c"),
-        dict(tid=7, pos=150_030, cigar=[(M, 200)], has_seq=0, flag=256, name="a"),
-        dict(tid=7, pos=150_040, cigar=[(M, 120)], flag=256, name="d"),
-        dict(tid=7, pos=150_050, cigar=[(M, 80), (I, 4), (M, 40)], flag=0x400, name="e", nonacgt=[150_060]),
-        dict(tid=7, pos=150_060, cigar=[(S, 3), (M, 90)], flag=0x200, name="f"),
-        dict(tid=7, pos=150_070, cigar=big, name="long"),
-        dict(tid=7, pos=400_000, cigar=[(M, 500)], flag=0x800, name="g"),
-        dict(tid=24, pos=16000, cigar=[(M, 500)], name="mito"),
-    ])
+    """(ref names, [record dicts]) as oracle_coverage takes them"""
+    parsed = _read_bam(path)
+    return parsed.refs, parsed.recs
 
 
 def make_records(n=700):
     return synth.merge_sorted(synth.generate(synth.scaled_config("tiny", n), "cpu"), odd_records())
-
-
-def make_windows(rec, seed=3):
-    """Random windows where the reads are (overlapping ones included), the plot's own window shape, windows at both ends of
-    chr8 and chrM, a window on a contig without reads, empty windows."""
-    rng = np.random.default_rng(seed)
-    tid, pos, end = (getattr(rec, k).numpy() for k in ("tid", "pos", "end"))
-    chroms, lens = rec.header_chroms, rec.header_lens
-    out = []
-    for k in rng.choice(rec.n, 60):
-        a = int(pos[k]) + int(rng.integers(-300, 300))
-        out.append((chroms[tid[k]], max(a, 0), max(a, 0) + int(rng.choice([1, 37, 150, 1000, 25_000]))))
-    out += [("chr8", 150_000 + 150 * k, 150_000 + 150 * (k + 1)) for k in range(8)]
-    out += [("chr8", 150_000, 151_000), ("chr8", 150_100, 150_250), ("chr8", 150_100, 150_250)]     # overlapping, repeated
-    out += [("chr8", 0, 1000), ("chr8", lens[7] - 1000, lens[7]), ("chrM", 0, 10), ("chrM", lens[24] - 5, lens[24])]
-    out += [("chr3", 1000, 500_000), ("chr8", 150_090, 150_090), ("chrM", 16_100, 16_100)]
-    assert chroms[7] == "chr8" and chroms[24] == "chrM"
-    return out
-
-
-def with_qual(i):
-    return i % 3 != 1                 # QUAL on two records in three, absent (0xff) on the rest
 
 
 @pytest.fixture(scope="module")
@@ -158,18 +35,6 @@ def case(tmp_path_factory):
     parsed = read_bam(path)
     assert len(parsed[1]) == rec.n
     return dict(rec=rec, path=path, small=small, parsed=parsed, windows=make_windows(rec))
-
-
-def host(path, windows, thr, cb, **kw):
-    old = os.environ.get("CORAL_BAM_DECODE")
-    os.environ["CORAL_BAM_DECODE"] = "cpu"
-    try:
-        return bam.window_coverage(path, windows, thr, cb, device="cpu", **kw)
-    finally:
-        if old is None:
-            del os.environ["CORAL_BAM_DECODE"]
-        else:
-            os.environ["CORAL_BAM_DECODE"] = old
 
 
 # ---- the oracle itself sees what was planted -----------------------------------------------------------------------------------
@@ -241,19 +106,6 @@ def test_segments_cover_exactly_the_windows():
 
 
 # ---- the plot's coverage track -------------------------------------------------------------------------------------------------
-def _plot_case(golden_dir, name, tmp_path):
-    with open(os.path.join(golden_dir, "plotcov_%s.json" % name)) as fp:
-        gold = json.load(fp)
-    _, rec = synth.dataset(gold["config"], "cpu")
-    with open(os.path.join(golden_dir, "e2e_%s.json" % gold["config"])) as fp:
-        text = json.load(fp)["files"][gold["graph_file"]]
-    graph = str(tmp_path / "g_graph.txt")
-    with open(graph, "w") as fp:
-        fp.write(text)
-    want = [(c, a + k * w, a + k * w + w, tot) for c, a, w, totals in gold["tracks"] for k, tot in enumerate(totals)]
-    return gold, rec, graph, want
-
-
 @pytest.mark.parametrize("name", ["tiny", "tiny_region", "tiny_edge_region", "ultra"])
 def test_coverage_track_bam_equals_plot_goldens(name, golden_dir, tmp_path, monkeypatch):
     monkeypatch.setenv("CORAL_BAM_DECODE", "cpu")
