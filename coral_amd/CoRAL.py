@@ -7,7 +7,7 @@
 The `reconstruct` mode and the `hsr` mode (§8(f) item 3) run on the MI355X path, and so do `index`, `qc`
 (the reference's scripts/report_nanopore_qc.py, from one decode of the aligned BAM), `pileup` (the bases per position of
 regions, pysam's count_coverage as a table) and `depth` (read depth per fixed-size bin of every contig, the table a copy-number
-caller starts from); the other modes of the
+caller starts from) and `fastq` (selected reads as FASTQ, by regions or read names); the other modes of the
 reference (seed, plot, cycle2bed) are untouched and are delegated to the reference's own modules when they are
 importable (set CORAL_REFERENCE_SRC to the reference's src/ directory).  The cycle-decomposition step after the graph build is the
 reference's (Gurobi); it runs on the object this module returns.
@@ -105,7 +105,15 @@ def build_parser():
                     type=int, default=0x704)
     dp.add_argument("--no_deletions", help="If specified, deleted reference bases (D) do not count as covered.", action='store_true')
     dp.add_argument("--device", help="GPU to use ('cpu': the host pipeline).", default="cuda:0")
-    for p in (rp, hp, qp, pp, dp):
+    fp = sub.add_parser("fastq", help="Write selected reads of a (long read) bam file as FASTQ, from one decode of it.")
+    fp.add_argument("--lr_bam", help="(Long read) bam file.", required=True)
+    fp.add_argument("--region", help="chr:start-stop (0-based, half-open): only reads that overlap it; may be given several times.", action="append")
+    fp.add_argument("--names_file", help="File of read names, one per line: only these reads.")
+    fp.add_argument("--reads_exclude_flags", help="Leave out records with any of these flag bits (default: secondary, supplementary).",
+                    type=lambda x: int(x, 0), default=0x900)
+    fp.add_argument("--output", help="Name of the FASTQ file.", required=True)
+    fp.add_argument("--device", help="GPU to use ('cpu': the host pipeline).", default="cuda:0")
+    for p in (rp, hp, qp, pp, dp, fp):
         add_filter_arguments(p)
     for mode in ("seed", "plot", "cycle2bed"):
         sub.add_parser(mode, help="(reference implementation; not part of the MI355X path)", add_help=False)
@@ -208,6 +216,26 @@ def depth_mode(args):
     return args.output
 
 
+def fastq_mode(args):
+    """The selected reads as FASTQ (bam.extract_reads): by regions, by names, both (intersected) or neither (every read)."""
+    from coral_amd import bam
+    regions = None
+    if args.region:
+        regions = []
+        for text in args.region:
+            chrom, span = text.rsplit(":", 1)
+            a, b = span.replace(",", "").split("-")
+            regions.append((chrom, int(a), int(b)))
+    names = None
+    if args.names_file:
+        with open(args.names_file) as fp:
+            names = [ln.strip() for ln in fp if ln.strip()]
+    reads = bam.extract_reads(args.lr_bam, regions, names, args.reads_exclude_flags, device=args.device, record_filter=record_filter_of(args))
+    reads.write(args.output)
+    print("Wrote %s (%d reads)" % (args.output, reads.n))
+    return args.output
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     if argv and argv[0] in ("seed", "plot", "cycle2bed"):
@@ -239,6 +267,8 @@ def main(argv=None):
         return pileup_mode(args)
     if args.mode == "depth":
         return depth_mode(args)
+    if args.mode == "fastq":
+        return fastq_mode(args)
     parser.print_help()
     return None
 

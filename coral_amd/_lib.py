@@ -26,16 +26,19 @@ class coral_bam_request_t(C.Structure):
                 ("n_seg", C.c_int32), ("seg_tid", C.c_void_p), ("seg_start", C.c_void_p), ("seg_end", C.c_void_p),
                 ("quality_threshold", C.c_int32), ("read_callback", C.c_int32), ("want_index", C.c_int32), ("want_qc", C.c_int32),
                 ("per_base", C.c_int32), ("depth_bin", C.c_int32), ("depth_min_mapq", C.c_int32), ("depth_exclude_flags", C.c_int32),
-                ("depth_count_deletions", C.c_int32), ("keep_min_mapq", C.c_int32), ("keep_min_seq_length", C.c_int32),
+                ("depth_count_deletions", C.c_int32), ("want_reads", C.c_int32), ("reads_exclude_flags", C.c_int32),
+                ("reads_n_seg", C.c_int32), ("reads_seg_tid", C.c_void_p), ("reads_seg_start", C.c_void_p), ("reads_seg_end", C.c_void_p),
+                ("reads_n_names", C.c_int32), ("reads_names", C.c_void_p), ("reads_name_off", C.c_void_p), ("keep_min_mapq", C.c_int32), ("keep_min_seq_length", C.c_int32),
                 ("keep_require_flags", C.c_int32), ("keep_exclude_flags", C.c_int32)]
 
 
 def bam_request(rank: int = 0, world: int = 1, spans=None, coverage=None, index: bool = False, qc: bool = False,
-                per_base: bool = False, depth=None, keep=None) -> coral_bam_request_t:
+                per_base: bool = False, depth=None, keep=None, reads=None) -> coral_bam_request_t:
     """The request of a BAM decode: ``spans`` uint64 [K][2] virtual offsets (None: the byte range), ``coverage`` = (segments int32
     [3][S], quality threshold, read_callback code) or None, ``per_base``: the coverage as the table per position and base (the
     pileup), ``depth`` = (bin size, min_mapq, exclude_flags, count_deletions) or None: the binned-depth request, ``keep`` = (min_mapq, min_seq_length, require_flags, exclude_flags) (a
-    ``bam.RecordFilter`` is one) or None: the record filter.  The struct keeps the contiguous arrays it points into alive; the rules are the library's to check."""
+    ``bam.RecordFilter`` is one) or None: the record filter, ``reads`` = (exclude_flags, segments int32 [3][S] or None, names = a list
+    of bytes or None) or None: the reads request (no segment / no name: no such limit).  The struct keeps the contiguous arrays it points into alive; the rules are the library's to check."""
     req = coral_bam_request_t(rank=rank, world=world, n_spans=-1, n_seg=-1, want_index=int(index), want_qc=int(qc), per_base=int(per_base))
     req.arrays = []
     if depth is not None:
@@ -46,6 +49,18 @@ def bam_request(rank: int = 0, world: int = 1, spans=None, coverage=None, index:
     def pointer(a, dtype):
         req.arrays.append(np.ascontiguousarray(a, dtype=dtype))
         return req.arrays[-1].ctypes.data
+    if reads is not None:                    # (in front of the coverage request: its segment rows stay the last arrays)
+        exclude_flags, segs, names = reads
+        req.want_reads, req.reads_exclude_flags = 1, int(exclude_flags)
+        if segs is not None:
+            segs = np.asarray(segs, dtype=np.int32).reshape(3, -1)
+            req.reads_n_seg = segs.shape[1]
+            req.reads_seg_tid, req.reads_seg_start, req.reads_seg_end = (pointer(row, np.int32) for row in segs)
+        if names is not None:
+            names = [bytes(nm) for nm in names]
+            req.reads_n_names = len(names)
+            req.reads_names = pointer(np.frombuffer(b"".join(names) + b"\0", dtype=np.uint8), np.uint8)
+            req.reads_name_off = pointer(np.concatenate([[0], np.cumsum([len(nm) for nm in names], dtype=np.int64)]), np.int64)
     if spans is not None:
         spans = np.asarray(spans, dtype=np.uint64).reshape(-1, 2)
         req.n_spans, req.span_beg, req.span_end = len(spans), pointer(spans[:, 0], np.uint64), pointer(spans[:, 1], np.uint64)
@@ -143,6 +158,8 @@ def lib():
     L.coral_bam_qc_fill.argtypes = [C.c_void_p, P, P, P, P, P, C.POINTER(C.c_int64)]
     L.coral_bam_depth_sizes.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
     L.coral_bam_depth_fill.argtypes = [C.c_void_p, P, P, P]
+    L.coral_bam_reads_sizes.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+    L.coral_bam_reads_fill.argtypes = [C.c_void_p, P, P]
     L.coral_bamgpu_open_request.argtypes = [C.c_char_p, C.c_int32, C.c_int64, Q, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
     L.coral_bamgpu_finish.argtypes = [C.c_void_p, P]
     with open(os.path.join(os.path.dirname(_HERE), "include", "coral_hip.h")) as fp:

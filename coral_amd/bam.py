@@ -217,21 +217,24 @@ def decode_bam_gpu(path: str, device="cuda:0", n_threads: Optional[int] = None, 
 class DecodeResult(collections.namedtuple("DecodeResult", "records counts index qc")):
     """What _decode returns; what it was not asked for is None.  It unpacks as these four; the table of a pileup request
     (uint32 [positions][4]) is the attribute ``pileup``, the result of a binned-depth request the attribute ``depth``
-    (bin_off int64 [contigs + 1], bases and reads int64 [bins])."""
+    (bin_off int64 [contigs + 1], bases and reads int64 [bins]), the result of a reads request the attribute ``reads`` (text uint8,
+    offsets int64 [records + 1])."""
     pileup = None
     depth = None
+    reads = None
 
 
 def _decode(path: str, device, *, n_threads: Optional[int] = None, rank: int = 0, world: int = 1, batch_bytes: int = 0, spans=None,
-            coverage=None, index=False, qc=False, records=True, per_base=False, depth=None, record_filter=None) -> DecodeResult:
+            coverage=None, index=False, qc=False, records=True, per_base=False, depth=None, record_filter=None, reads=None) -> DecodeResult:
     """One decode of the ``rank``-th of ``world`` byte ranges, or of the records that start inside ``spans`` (uint64 [K][2] virtual
     offsets), with what rides along: ``coverage`` = (segments int32 [3][S], quality threshold, read_callback code) gives the S
     int64 ``counts``, ``index`` the partial BAI index, ``qc`` the ``ReadQC``; ``records`` False leaves the Records out.  With
     ``per_base`` the coverage is counted per position and base: ``pileup`` is the uint32 table [positions of the segments, in
     segment order][A, C, G, T] and ``counts`` its sums per segment.  ``depth`` = (bin size, min_mapq, exclude_flags,
-    count_deletions) gives the binned-depth tables (``binned_depth``).  ``record_filter``: a ``RecordFilter``; every result is
+    count_deletions) gives the binned-depth tables (``binned_depth``), ``reads`` = (exclude_flags, segments or None, sorted names or
+    None) the FASTQ text of the selected records (``extract_reads``).  ``record_filter``: a ``RecordFilter``; every result is
     then that of a file holding only the kept records.  On the GPU pipeline when ``_on_gpu(device)``, else on the host."""
-    req = _lib.bam_request(rank, world, spans, coverage, index, qc, per_base, depth, keep=_as_filter(record_filter))
+    req = _lib.bam_request(rank, world, spans, coverage, index, qc, per_base, depth, keep=_as_filter(record_filter), reads=reads)
     if _on_gpu(device):
         return _decode_gpu(path, device, n_threads, batch_bytes, req, records)
     L = _lib.lib()
@@ -280,6 +283,14 @@ def _result_from_handle(L, h, req, records: bool, cigar, cigar_words: int) -> De
         if L.coral_bam_depth_fill(h, bin_off.ctypes.data, bases.ctypes.data, reads.ctypes.data) != 0:
             raise _lib.CoralHipError("coral_bam_depth_fill failed: %s" % L.coral_bam_last_error().decode())
         res.depth = (bin_off, bases, reads)
+    if req.want_reads:
+        sz = (C.c_int64 * 2)()
+        if L.coral_bam_reads_sizes(h, sz) != 0:
+            raise _lib.CoralHipError("coral_bam_reads_sizes failed: %s" % L.coral_bam_last_error().decode())
+        text, offsets = np.zeros(int(sz[1]), dtype=np.uint8), np.zeros(int(sz[0]) + 1, dtype=np.int64)
+        if L.coral_bam_reads_fill(h, text.ctypes.data, offsets.ctypes.data) != 0:
+            raise _lib.CoralHipError("coral_bam_reads_fill failed: %s" % L.coral_bam_last_error().decode())
+        res.reads = (text, offsets)
     return res
 
 
@@ -832,6 +843,118 @@ def merge_binned_depth(parts: Sequence[BinnedDepth]) -> BinnedDepth:
             raise ValueError("merge_binned_depth: the parts do not have the same header and parameters")
     return BinnedDepth(first.chroms, first.lengths, *first.params, first.bin_off, np.sum([p.all_bases for p in parts], axis=0),
                        np.sum([p.all_reads for p in parts], axis=0))
+
+
+# ----------------------------------------------------------------------------------------------
+# reads: the selected records as FASTQ text, written during the decode
+# ----------------------------------------------------------------------------------------------
+class Reads:
+    """FASTQ text of the reads one decode selected (``extract_reads``): ``text`` uint8, the records `@name\\nSEQ\\n+\\nQUAL\\n` one
+    after the other in file order, ``offsets`` int64 [n + 1] where each starts, ``n`` their number.  Iterating yields (name, seq,
+    qual) as str."""
+
+    def __init__(self, text=None, offsets=None):
+        self.text = np.ascontiguousarray(text if text is not None else np.zeros(0, dtype=np.uint8), dtype=np.uint8)
+        self.offsets = np.ascontiguousarray(offsets if offsets is not None else np.zeros(1, dtype=np.int64), dtype=np.int64)
+        if len(self.offsets) < 1 or int(self.offsets[0]) != 0 or int(self.offsets[-1]) != len(self.text):
+            raise ValueError("Reads: the offsets do not fit the text")
+        self.n = len(self.offsets) - 1
+
+    def __len__(self):
+        return self.n
+
+    def __iter__(self):
+        raw, off = self.text.tobytes(), self.offsets.tolist()
+        for a, b in zip(off, off[1:]):
+            name, seq, _, qual = raw[a:b - 1].decode("latin-1").split("\n")      # (a name holds no line end: its bytes are printable)
+            yield name[1:], seq, qual
+
+    def names(self):
+        raw, off = self.text.tobytes(), self.offsets.tolist()
+        return [raw[a + 1:raw.index(b"\n", a)].decode("latin-1") for a in off[:-1]]
+
+    def write(self, path: str) -> str:
+        with open(path, "wb") as fp:
+            fp.write(self.text.tobytes())
+        return path
+
+
+def merge_reads(parts: Sequence[Reads]) -> Reads:
+    """The results of consecutive byte ranges (in rank order) as one: the texts concatenated."""
+    parts = list(parts)
+    if not parts:
+        raise ValueError("merge_reads needs at least one part")
+    base = np.concatenate([[0], np.cumsum([len(p.text) for p in parts])]).astype(np.int64)
+    return Reads(np.concatenate([p.text for p in parts]),
+                 np.concatenate([np.zeros(1, dtype=np.int64)] + [p.offsets[1:] + b for p, b in zip(parts, base)]))
+
+
+def extract_reads(path: str, regions=None, names=None, exclude_flags: int = 0x900, device="cuda:0", n_threads: Optional[int] = None,
+                  rank: int = 0, world: int = 1, batch_bytes: int = 0, *, index=None, record_filter=None) -> Reads:
+    """The reads of the BAM file as FASTQ (``Reads``), written while it is decoded - the only time SEQ and QUAL are at hand: what
+    ``samtools view x.bam region... | samtools fastq`` or ``samtools view -N names.txt`` get from a second pass over the file.
+
+    A record is written when it has SEQ, ``flag & exclude_flags == 0`` (default 0x900: one record per read - a hard-clipped
+    supplementary holds only a part of it), with ``regions`` [(chrom, start, stop)] (they may overlap or touch and are merged):
+    it is on a region's contig and ``[pos, end)`` meets the region (a record with flag 0x4: ``[pos, pos + 1)``), with ``names``
+    (str or bytes): its read name is one of them.  Regions and names intersect; neither: every read.  An empty ``regions`` or
+    ``names`` list selects nothing, and the file is not opened.  Text of a record: ``@name``, SEQ ("=ACMGRSVTWYHKDBN"), ``+``,
+    QUAL (min(q, 93) + 33; '"' throughout when the record has no QUAL); a record with flag 0x10 is reverse-complemented back to
+    the orientation it was sequenced in, its QUAL reversed.  The quality-1 default, the clamp at 93 and the 0x900 default are
+    meant to be ``samtools fastq``'s; parity with samtools is not pinned here, the rule is.
+
+    GPU pipeline (k_bam_reads_plan / k_bam_reads_emit per batch) on a GPU ``device``, host pipeline with ``device="cpu"`` or
+    ``CORAL_BAM_DECODE=cpu``; identical bytes.  With regions, a BAI index (``index``: the rules of ``window_coverage``) restricts
+    the decode to the BGZF blocks it names; with names only, or neither, the byte range (``rank`` of ``world``) is decoded and
+    ``merge_reads`` joins the ranges.  ``record_filter``: a ``RecordFilter``, applied first.  The whole result lives in host
+    memory: meant for the reads of an amplicon, not for every read of a 2 M-read file."""
+    if isinstance(exclude_flags, bool) or not isinstance(exclude_flags, numbers.Integral) or not 0 <= exclude_flags <= 0xffff:
+        raise ValueError("exclude_flags must be an integer in 0..0xffff, got %r" % (exclude_flags,))
+    if names is not None:
+        names = sorted(set(nm.encode("latin-1") if isinstance(nm, str) else bytes(nm) for nm in names))
+        for nm in names:
+            if not 1 <= len(nm) <= 254:
+                raise ValueError("a read name has 1..254 bytes, got %r" % (nm,))
+    if (regions is not None and len(list(regions)) == 0) or (names is not None and len(names) == 0):
+        return Reads()
+    if n_threads is None:
+        n_threads = default_threads()
+    if regions is None:
+        res = _decode(path, device, n_threads=n_threads, rank=rank, world=world, batch_bytes=batch_bytes, records=False,
+                      record_filter=record_filter, reads=(exclude_flags, None, names))
+        return Reads(*res.reads)
+    ref_names = bam_reference_names(path)
+    _, segs = pileup_regions(list(regions), ref_names)
+    if segs.shape[1] == 0:                                       # only empty regions
+        return Reads()
+    idx, skipped = None, None
+    if index is not None and index is not False:
+        if world != 1:
+            raise ValueError("a region decode is not sharded: index and world > 1 do not go together")
+        idx = _usable_index(path, index, len(ref_names))
+    elif index is None and world == 1:
+        beside = _index_beside(path)
+        if beside is not None:
+            try:
+                if os.path.getmtime(beside) < os.path.getmtime(path):
+                    raise _lib.CoralHipError("%s is older than the BAM file" % beside)
+                idx = _usable_index(path, beside, len(ref_names))
+            except (_lib.CoralHipError, OSError) as e:
+                skipped = str(e)
+    spans = region_spans(idx, segs.T.tolist()) if idx is not None else None
+    if spans is not None and len(spans) == 0:
+        LAST_DECODE.clear()
+        LAST_DECODE.update(seconds=0.0, compressed_bytes=0, uncompressed_bytes=0, blocks=0, threads=int(n_threads))
+        out = Reads()
+    else:
+        res = _decode(path, device, n_threads=n_threads, rank=rank, world=world, batch_bytes=batch_bytes, spans=spans, records=False,
+                      record_filter=record_filter, reads=(exclude_flags, segs, names))
+        out = Reads(*res.reads)
+    if idx is not None:
+        LAST_DECODE.update(index=idx.path or "<object>", spans=int(len(spans)))
+    else:
+        LAST_DECODE.update(index=None, index_skipped=skipped)
+    return out
 
 
 # ----------------------------------------------------------------------------------------------

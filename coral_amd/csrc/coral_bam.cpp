@@ -13,7 +13,8 @@
 //                             straddles into the next chunk
 //     stage 3 (worker pool)   parse the chunk's records into a per-chunk partial (CIGAR copy + padding, SA tokens, NM,
 //                             non-ACGT scan; with a window-coverage request the chunk's
-//                             partial counts per segment, added up in stage 4)
+//                             partial counts per segment, added up in stage 4; with a reads request the
+//                             FASTQ text of the chunk's written records, concatenated in stage 4)
 //     stage 4 (caller)        append the partials in file order; read names -> ids
 // A byte range [rank, world) of the file can be decoded on its own (one process per GPU): the range
 // starts at the first BGZF block at or after its first byte (blocks are found by their magic + BC subfield and a chained
@@ -98,6 +99,8 @@ bool decode_file(const char *path, int n_threads, const Request &R, const Span *
         D.depth.zero_tables();
     }
     DepthPartial *depth = D.depth.on ? &D.depth : nullptr;
+    const ReadsRule *reads = R.reads.on ? &R.reads : nullptr;
+    if (reads) D.has_reads = true;
     // ---- block table: the blocks that START inside this rank's byte range, plus an overhang for the last record
     const uint64_t byte_lo = rank == 0 ? 0 : f.size / (uint64_t)world * (uint64_t)rank;
     const uint64_t byte_hi = rank == world - 1 ? f.size : f.size / (uint64_t)world * (uint64_t)(rank + 1);
@@ -180,6 +183,11 @@ bool decode_file(const char *path, int n_threads, const Request &R, const Span *
                 const uint8_t *q = c->buf.data() + s;
                 if (filtered && !keep_record_at(q, R.keep)) continue;      // dropped: no field, no tag, no counter sees it
                 if (!decode_record(q + 4, rd32(q), ref_id, pt, pt.error, cov, want_qc, D.pileup.data(), depth)) break;
+                if (reads && reads->written(q, pt.end.back())) {      // the reads request: the chunk's text, concatenated in merge()
+                    const size_t at = pt.reads_text.size();
+                    reads_append_text(q, pt.reads_text);
+                    pt.reads_len.push_back((int64_t)(pt.reads_text.size() - at));
+                }
             }
             std::vector<uint8_t>().swap(c->buf);            // SEQ / QUAL bytes are gone from here on
             c->parsed.set();
@@ -211,6 +219,8 @@ bool decode_file(const char *path, int n_threads, const Request &R, const Span *
         for (size_t t = 0; t < pt.cov.size(); ++t) D.cov[t] += pt.cov[t];
         D.qc.qual_sum.insert(D.qc.qual_sum.end(), pt.qc_sum.begin(), pt.qc_sum.end());
         for (size_t t = 0; t < pt.qc_hist.size(); ++t) D.qc.hist[t] += pt.qc_hist[t];
+        D.reads_text.insert(D.reads_text.end(), pt.reads_text.begin(), pt.reads_text.end());
+        for (int64_t l : pt.reads_len) D.reads_off.push_back(D.reads_off.back() + l);
         for (const char *s = pt.names.data(), *e = s + pt.names.size(); s < e;) {
             const size_t len = strlen(s);
             D.name_id.push_back(D.names.intern(s, len));
@@ -510,6 +520,7 @@ extern "C" int coral_bam_decode_request(const char *path, int32_t n_threads, con
             if (ok && !spans_inside_file(R, f.size, g_bam_err)) return CORAL_ERR_ARG;
             if (ok && R.has_cov) D->cov.assign(R.cov.size(), 0);
             if (ok && R.cov.per_base) { D->pileup.assign((size_t)(4 * R.cov.n_pos()), 0); D->has_pileup = true; }
+            if (ok && R.reads.on) D->has_reads = true;
             for (size_t k = 0; k < R.spans.size() && ok; ++k) ok = decode_file(path, n_threads, R, &R.spans[k], *D);
         }
     } catch (const std::exception &e) {          // e.g. bad_alloc on a corrupt size field: never across the C boundary
@@ -603,6 +614,26 @@ extern "C" int coral_bam_depth_fill(void *handle, int64_t *bin_off, int64_t *bas
         memcpy(bases, P.bases.data(), P.bases.size() * 8);
         memcpy(reads, P.reads.data(), P.reads.size() * 8);
     }
+    return CORAL_OK;
+}
+
+// The reads request of a handle (either pipeline): sizes = records written, text bytes; fill = the text and the n + 1 offsets.
+extern "C" int coral_bam_reads_sizes(void *handle, int64_t sizes[2]) {
+    if (!handle || !sizes) return CORAL_ERR_ARG;
+    const Decoded *D = (const Decoded *)handle;
+    if (!D->has_reads) { g_bam_err = "coral_bam_reads_sizes: the handle holds no reads request"; return CORAL_ERR_ARG; }
+    sizes[0] = (int64_t)D->reads_off.size() - 1;
+    sizes[1] = (int64_t)D->reads_text.size();
+    return CORAL_OK;
+}
+
+extern "C" int coral_bam_reads_fill(void *handle, uint8_t *text, int64_t *rec_off) {
+    if (!handle || !rec_off) return CORAL_ERR_ARG;
+    const Decoded *D = (const Decoded *)handle;
+    if (!D->has_reads || D->reads_off.back() != (int64_t)D->reads_text.size()) { g_bam_err = "coral_bam_reads_fill: the handle holds no reads request"; return CORAL_ERR_ARG; }
+    if (!D->reads_text.empty() && !text) return CORAL_ERR_ARG;
+    if (!D->reads_text.empty()) memcpy(text, D->reads_text.data(), D->reads_text.size());
+    memcpy(rec_off, D->reads_off.data(), D->reads_off.size() * 8);
     return CORAL_OK;
 }
 

@@ -245,6 +245,107 @@ inline bool keep_record_at(const uint8_t *r, const KeepRule &K) {
     return keep_record(r[13], flag, l_seq, K.min_mapq, K.min_seq_length, K.require_flags, K.exclude_flags);
 }
 
+// A reads request (want_reads of a coral_bam_request_t): the selected records as FASTQ text, what the reference's workflow gets
+// from `samtools view x.bam region... | samtools fastq` or `samtools view -N names.txt` in a second pass over the file (its own
+// scripts start and end at FASTQ: scripts/align_nanopore_reads.sh, scripts/report_nanopore_qc.py).  The rules both pipelines share:
+//   a record is WRITTEN when l_seq > 0, flag & exclude_flags == 0 (reads_takes_part), with segments: tid >= 0 and
+//   [pos, bam_endpos) - [pos, pos + 1) with flag 0x4, which is what bam_endpos gives - meets a non-empty segment
+//   (reads_meets_segment), with names: its read name without the NUL is in the sorted list (reads_name_listed: exact binary
+//   search, bytes compared, nothing hashed).  Segments and names intersect; neither: every read.
+//   Its text is `@` name `\n` SEQ `\n+\n` QUAL `\n`: 2 l_seq + l_read_name + 5 bytes (reads_text_bytes; l_read_name counts
+//   the NUL).  SEQ characters are READS_SEQ_CHARS[code], QUAL characters min(q, 93) + 33; a record whose first QUAL byte is
+//   0xff gets l_seq times '"' (quality 1).  With flag 0x10 the read is restored to the orientation it was sequenced in: SEQ
+//   reversed and complemented - the complement of a 4-bit code is its bit reversal, so = and N stay - and QUAL reversed.
+//   Nothing is appended to the name; records come in file order.  Bytes only: identical on either pipeline, for any batch size,
+//   and texts of byte ranges concatenate.
+#define READS_SEQ_CHARS "=ACMGRSVTWYHKDBN"
+const int64_t READS_SLICE = 16384;          // bases per work item of the GPU pipeline (as COV_SLICE and QC_SLICE)
+
+CORAL_QC_HD inline bool reads_takes_part(uint32_t flag, uint32_t l_seq, uint32_t exclude_flags) { return l_seq > 0 && (flag & exclude_flags) == 0; }
+CORAL_QC_HD inline uint32_t reads_complement(uint32_t code) {      // A <-> T, C <-> G, M <-> K, ...: the four bits reversed
+    return ((code & 1u) << 3) | ((code & 2u) << 1) | ((code & 4u) >> 1) | ((code & 8u) >> 3);
+}
+CORAL_QC_HD inline uint8_t reads_seq_char(uint32_t code, bool reverse) { return (uint8_t)READS_SEQ_CHARS[reverse ? reads_complement(code & 15u) : (code & 15u)]; }
+CORAL_QC_HD inline uint8_t reads_qual_char(uint32_t q) { return (uint8_t)((q < 93u ? q : 93u) + 33u); }
+CORAL_QC_HD inline long long reads_text_bytes(uint32_t l_seq, uint32_t l_read_name) { return 2ll * l_seq + l_read_name + 5; }
+// characters of the codes 8 * half .. 8 * half + 7 (complemented first with `reverse`) as one little-endian word
+CORAL_QC_HD constexpr unsigned long long reads_char_table(int half, bool reverse) {
+    unsigned long long w = 0;
+    for (int k = 0; k < 8; ++k) {
+        const unsigned c = (unsigned)(8 * half + k);
+        const unsigned r = ((c & 1u) << 3) | ((c & 2u) << 1) | ((c & 4u) >> 1) | ((c & 8u) >> 3);
+        w |= (unsigned long long)(unsigned char)READS_SEQ_CHARS[reverse ? r : c] << (8 * k);
+    }
+    return w;
+}
+// [pos, end) meets a non-empty one of the n sorted, disjoint segments (tid, lo, hi)
+CORAL_QC_HD inline bool reads_meets_segment(const int32_t *tid, const int32_t *lo, const int32_t *hi, int n, int32_t t, long long pos, long long end) {
+    if (t < 0) return false;
+    int a = 0, b = n;
+    while (a < b) {                            // first segment with tid > t, or tid == t and hi > pos
+        const int m = (a + b) >> 1;
+        if (tid[m] < t || (tid[m] == t && (long long)hi[m] <= pos)) a = m + 1; else b = m;
+    }
+    for (; a < n && tid[a] == t && (long long)lo[a] < end; ++a)
+        if (hi[a] > lo[a]) return true;
+    return false;
+}
+// `name` (len bytes, no NUL) is one of the n names blob[off[k] .. off[k + 1]), sorted ascending by their bytes, then by length
+CORAL_QC_HD inline bool reads_name_listed(const uint8_t *blob, const int64_t *off, long long n, const uint8_t *name, uint32_t len) {
+    long long a = 0, b = n;
+    while (a < b) {
+        const long long m = (a + b) >> 1;
+        const uint8_t *s = blob + off[m];
+        const uint32_t sl = (uint32_t)(off[m + 1] - off[m]), common = sl < len ? sl : len;
+        int c = 0;
+        for (uint32_t k = 0; k < common && c == 0; ++k) c = (int)s[k] - (int)name[k];
+        if (c == 0) c = sl < len ? -1 : sl > len ? 1 : 0;
+        if (c == 0) return true;
+        if (c < 0) a = m + 1; else b = m;
+    }
+    return false;
+}
+
+struct ReadsRule {                          // the request, checked and copied (parse_request)
+    bool on = false;
+    uint32_t exclude_flags = 0;
+    std::vector<int32_t> tid, lo, hi;       // no segment: no region limit
+    std::vector<uint8_t> names;             // no name: no name limit
+    std::vector<int64_t> name_off;          // n + 1
+    long long n_names() const { return name_off.empty() ? 0 : (long long)name_off.size() - 1; }
+    // the whole rule on a record's bytes (r points at block_size; end = bam_endpos of the record)
+    bool written(const uint8_t *r, int32_t end) const {
+        uint16_t flag; uint32_t l_seq; int32_t t, pos;
+        memcpy(&t, r + 4, 4); memcpy(&pos, r + 8, 4); memcpy(&flag, r + 18, 2); memcpy(&l_seq, r + 20, 4);
+        if (!reads_takes_part(flag, l_seq, exclude_flags)) return false;
+        if (!tid.empty() && !reads_meets_segment(tid.data(), lo.data(), hi.data(), (int)tid.size(), t, pos, end)) return false;
+        return n_names() == 0 || reads_name_listed(names.data(), name_off.data(), n_names(), r + 36, (uint32_t)r[12] - 1u);
+    }
+};
+
+// the text of one record (r points at block_size; its fields have been checked to lie inside it), appended to `out`
+inline void reads_append_text(const uint8_t *r, std::vector<uint8_t> &out) {
+    uint16_t flag, n_cigar_op; uint32_t l_seq;
+    memcpy(&n_cigar_op, r + 16, 2); memcpy(&flag, r + 18, 2); memcpy(&l_seq, r + 20, 4);
+    const uint32_t l_read_name = r[12];
+    const bool reverse = (flag & 0x10u) != 0;
+    const uint8_t *seq = r + 36 + l_read_name + 4ull * n_cigar_op, *qual = seq + ((size_t)l_seq + 1) / 2;
+    const size_t at = out.size();
+    out.resize(at + (size_t)reads_text_bytes(l_seq, l_read_name));
+    uint8_t *w = out.data() + at;
+    *w++ = '@';
+    memcpy(w, r + 36, l_read_name - 1); w += l_read_name - 1;
+    *w++ = '\n';
+    for (uint32_t j = 0; j < l_seq; ++j) {
+        const uint32_t s = reverse ? l_seq - 1 - j : j;
+        *w++ = reads_seq_char((s & 1) ? (seq[s >> 1] & 15u) : (uint32_t)(seq[s >> 1] >> 4), reverse);
+    }
+    *w++ = '\n'; *w++ = '+'; *w++ = '\n';
+    const bool has_qual = qual[0] != 0xff;
+    for (uint32_t j = 0; j < l_seq; ++j) *w++ = has_qual ? reads_qual_char(qual[reverse ? l_seq - 1 - j : j]) : (uint8_t)'"';
+    *w++ = '\n';
+}
+
 // A span of virtual offsets [beg, end) (span_beg / span_end of a coral_bam_request_t): the records that START in it.
 struct Span {
     uint64_t beg = 0, end = 0;
@@ -272,6 +373,9 @@ struct Decoded {
     std::vector<int64_t> cov;               // window-coverage counts per segment (coral_bam_coverage_result)
     bool has_pileup = false;                // a pileup request (per_base of a coral_bam_request_t; it may hold no position)
     std::vector<uint32_t> pileup;           // its table [positions in segment order][A, C, G, T] (coral_bam_pileup_result)
+    bool has_reads = false;                 // a reads request (it may have written no record)
+    std::vector<uint8_t> reads_text;        // its FASTQ text, the written records in file order (coral_bam_reads_fill)
+    std::vector<int64_t> reads_off{0};      // where every written record starts in it, n + 1 entries
 };
 
 struct Partial {   // what stage 3 produces for one chunk
@@ -284,6 +388,8 @@ struct Partial {   // what stage 3 produces for one chunk
     std::vector<char> names;                // NUL-separated
     std::vector<int64_t> cov;               // window-coverage counts of the chunk's records (per segment; empty without a request)
     std::vector<int64_t> qc_sum, qc_hist;   // read-QC request: qual_sum per record, the chunk's 256-bin histogram (empty without a request)
+    std::vector<uint8_t> reads_text;        // reads request: the text of the chunk's written records and its length per written record
+    std::vector<int64_t> reads_len;
     std::string error;
 };
 
@@ -362,6 +468,7 @@ struct Request {
     bool want_index = false, want_qc = false;
     int32_t depth_bin = 0, depth_min_mapq = 0, depth_exclude_flags = 0;      // a binned-depth request (depth_bin > 0; the bins need the header: DepthPartial::init)
     bool depth_count_deletions = false;
+    ReadsRule reads;                        // a reads request (reads.on)
     KeepRule keep;                          // the record filter (not active: every record is kept)
     const CovTable *cov_table() const { return has_cov ? &cov : nullptr; }
 };
@@ -381,6 +488,42 @@ inline bool parse_request(const coral_bam_request_t *q, Request &R, std::string 
         R.depth_min_mapq = q->depth_min_mapq;
         R.depth_exclude_flags = q->depth_exclude_flags;
         R.depth_count_deletions = q->depth_count_deletions != 0;
+    }
+    if (q->want_reads != 0) {
+        ReadsRule &W = R.reads;
+        if (q->want_reads != 1) { err = "reads request: want_reads must be 0 or 1"; return false; }
+        if (R.want_index) { err = "request: want_reads does not go with want_index (an index request decodes every record of the file, a reads request a selection)"; return false; }
+        if (q->reads_exclude_flags < 0 || q->reads_exclude_flags > 0xffff) { err = "reads request: reads_exclude_flags must be 0..0xffff"; return false; }
+        if (q->reads_n_seg < 0 || (q->reads_n_seg > 0 && (!q->reads_seg_tid || !q->reads_seg_start || !q->reads_seg_end))) { err = "reads request: bad reads_seg arrays"; return false; }
+        for (int32_t k = 0; k < q->reads_n_seg; ++k) {
+            const int32_t *t = q->reads_seg_tid, *lo = q->reads_seg_start, *hi = q->reads_seg_end;
+            if (t[k] < 0 || lo[k] < 0 || hi[k] < lo[k]) { err = "reads request: bad segment in reads_seg"; return false; }
+            if (k > 0 && (t[k] < t[k - 1] || (t[k] == t[k - 1] && lo[k] < hi[k - 1]))) { err = "reads request: the reads_seg segments must be sorted by (tid, start) and disjoint"; return false; }
+        }
+        if (q->reads_n_names < 0 || (q->reads_n_names > 0 && (!q->reads_names || !q->reads_name_off))) { err = "reads request: bad reads_names arrays"; return false; }
+        for (int32_t k = 0; k < q->reads_n_names; ++k) {
+            const int64_t *o = q->reads_name_off;
+            const int64_t len = o[k + 1] - o[k];
+            if (o[k] < 0 || len < 1 || len > 254) { err = "reads request: every name of reads_names must have 1..254 bytes"; return false; }
+            if (k > 0) {                       // strictly ascending: by bytes, a prefix in front of what it is a prefix of
+                const int64_t pl = o[k] - o[k - 1];
+                const int c = memcmp(q->reads_names + o[k - 1], q->reads_names + o[k], (size_t)std::min(pl, len));
+                if (c > 0 || (c == 0 && pl >= len)) { err = "reads request: reads_names must be sorted ascending (bytes, then length) without duplicates"; return false; }
+            }
+        }
+        W.on = true;
+        W.exclude_flags = (uint32_t)q->reads_exclude_flags;
+        if (q->reads_n_seg > 0) {
+            W.tid.assign(q->reads_seg_tid, q->reads_seg_tid + q->reads_n_seg);
+            W.lo.assign(q->reads_seg_start, q->reads_seg_start + q->reads_n_seg);
+            W.hi.assign(q->reads_seg_end, q->reads_seg_end + q->reads_n_seg);
+        }
+        if (q->reads_n_names > 0) {
+            W.name_off.assign(q->reads_name_off, q->reads_name_off + q->reads_n_names + 1);
+            W.names.assign(q->reads_names + W.name_off.front(), q->reads_names + W.name_off.back());
+            const int64_t first = W.name_off.front();
+            for (int64_t &o : W.name_off) o -= first;
+        }
     }
     if (q->n_spans >= 0) {
         if (q->n_spans > 0 && (!q->span_beg || !q->span_end)) { err = "request: bad span arrays"; return false; }

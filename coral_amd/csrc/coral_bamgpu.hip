@@ -28,6 +28,8 @@
 //   k_bam_index + k_bam_index_compact  index: per record the virtual offset, the UCSC bin and the linear-index windows of a
 //                   BAI index, per batch the heads of the runs of equal (tid, bin)
 //   k_bam_depth     binned depth: per record one walk of its CIGAR, one 64-bit atomic per run of lanes in the same bin
+//   k_bam_reads_plan + k_bam_reads_emit   reads: the selected records as FASTQ text (nibbles -> ASCII, reverse strand mirrored
+//                   and complemented), scattered to scanned offsets of a per-batch buffer the host collects one batch later
 // Host: one struct per request (carve / start / batch / finish); what it may borrow of the parse's scratch: struct Borrowed.
 // Batches (64 MiB first, doubling up to 2.52 GiB inflated, coral_bamgpu_open) are double-buffered: while batch k is parsed, batch k + 1 is inflated
 // and k + 2 is read.
@@ -1268,6 +1270,159 @@ __global__ __launch_bounds__(WAVE) void k_bam_qc(const uint8_t *__restrict__ buf
 }
 
 // ---------------------------------------------------------------------------------------------
+// K_reads: the selected records as FASTQ text (want_reads; the rules: ReadsRule and reads_* in coral_bam_common.h)
+// ---------------------------------------------------------------------------------------------
+struct ReadsDev {                        // the request's device arrays, carved from the caller's workspace
+    const int32_t *tid, *lo, *hi;        // the segments (n_seg = 0: no region limit)
+    const uint8_t *names;                // the sorted names as one blob and n_names + 1 offsets (n_names = 0: no name limit)
+    const int64_t *name_off;
+    int n_seg;
+    long long n_names;
+    uint32_t exclude_flags;
+};
+
+// One thread per record (one-wave workgroups: they run beside the inflate launch): the rule, from the fixed
+// fields k_bam_meta left, the end position k_bam_emit left and the name behind the record's fixed fields.  out_len[i] = bytes of
+// the record's text, n_items[i] = its work items of READS_SLICE bases; both 0 when the record is not written, and in slot n_rec
+// (the scans' extra entry).
+__global__ __launch_bounds__(WAVE) void k_bam_reads_plan(const uint8_t *__restrict__ buf, const long long *__restrict__ rec_start, long long n_rec,
+                                                         MetaArrays M, const int32_t *__restrict__ end_in, ReadsDev X,
+                                                         long long *__restrict__ out_len, long long *__restrict__ n_items) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > n_rec) return;
+    long long bytes = 0, items = 0;
+    if (i < n_rec) {
+        const uint32_t l_seq = (uint32_t)M.l_seq[i];
+        const uint8_t *r = buf + rec_start[i];
+        const uint32_t l_read_name = r[12];
+        bool w = l_read_name > 0 && reads_takes_part((uint32_t)M.flag[i], l_seq, X.exclude_flags);
+        if (w && X.n_seg > 0) w = reads_meets_segment(X.tid, X.lo, X.hi, X.n_seg, M.tid[i], M.pos[i], end_in[i]);
+        if (w && X.n_names > 0) w = reads_name_listed(X.names, X.name_off, X.n_names, r + 36, l_read_name - 1u);
+        if (w) {
+            bytes = reads_text_bytes(l_seq, l_read_name);
+            items = ((long long)l_seq + READS_SLICE - 1) / READS_SLICE;
+        }
+    }
+    out_len[i] = bytes;
+    n_items[i] = items;
+}
+
+// The 16 bytes buf[p .. p + 16) for any p, from the two aligned 16-byte chunks that cover them (the second one is the first one
+// of the lane that makes the next 16 characters: the same or the next cache line, served by the L1).  A chunk that does not lie
+// inside [0, buf_bytes) reads as zeros: only the windows of an item's edge chunks reach outside the record, with bytes that are
+// not used.
+__device__ __forceinline__ uint4 reads_window(const uint8_t *__restrict__ buf, long long p, long long buf_bytes) {
+    const long long base = p & ~15ll;
+    uint4 lo = make_uint4(0u, 0u, 0u, 0u), hi = lo;
+    if (base >= 0 && base + 16 <= buf_bytes) lo = *reinterpret_cast<const uint4 *>(buf + base);
+    if (base + 16 >= 0 && base + 32 <= buf_bytes) hi = *reinterpret_cast<const uint4 *>(buf + base + 16);
+    const uint32_t sh = (uint32_t)(p & 15);
+    uint32_t d0 = lo.x, d1 = lo.y, d2 = lo.z, d3 = lo.w, d4 = hi.x, d5 = hi.y, d6 = hi.z, d7 = hi.w;
+    if (sh & 8u) { d0 = d2; d1 = d3; d2 = d4; d3 = d5; d4 = d6; d5 = d7; }
+    if (sh & 4u) { d0 = d1; d1 = d2; d2 = d3; d3 = d4; d4 = d5; }
+    const uint32_t bs = (sh & 3u) * 8u;
+    return make_uint4(__builtin_amdgcn_alignbit(d1, d0, bs), __builtin_amdgcn_alignbit(d2, d1, bs), __builtin_amdgcn_alignbit(d3, d2, bs),
+                      __builtin_amdgcn_alignbit(d4, d3, bs));
+}
+
+__device__ __forceinline__ uint4 reads_mirror(uint4 v) {      // the 16 bytes in reverse order
+    return make_uint4(__builtin_bswap32(v.w), __builtin_bswap32(v.z), __builtin_bswap32(v.y), __builtin_bswap32(v.x));
+}
+
+// 16 characters of SEQ.  Forward: of the bases s0 .. s0 + 15, in that order; reverse: of the same bases from s0 + 15 down to s0,
+// complemented.  The nine bytes that hold the bases are read as one big-endian number N whose nibble k (from the top) is base
+// s0 + k - shifted by one nibble when s0 is odd -, so that character t is the table entry of nibble t (forward) or 15 - t
+// (reverse): mirroring the indices is all a reverse-strand record costs.  s0 may be negative or reach behind l_seq in an item's
+// edge chunks; those characters are not stored.
+template <bool REV>
+__device__ __forceinline__ uint4 reads_seq_chunk(const uint8_t *__restrict__ buf, long long seq_at, long long s0, long long buf_bytes) {
+    constexpr unsigned long long T_LO = reads_char_table(0, REV), T_HI = reads_char_table(1, REV);
+    const uint4 v = reads_window(buf, seq_at + (s0 >> 1), buf_bytes);
+    unsigned long long N = ((unsigned long long)__builtin_bswap32(v.x) << 32) | __builtin_bswap32(v.y);
+    if (s0 & 1) N = (N << 4) | ((v.z & 0xffu) >> 4);
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int t = 0; t < 16; ++t) {
+        const uint32_t code = (uint32_t)(N >> (REV ? 4 * t : 60 - 4 * t)) & 15u;
+        const uint32_t c = (uint32_t)(((code & 8u) ? T_HI : T_LO) >> ((code & 7u) * 8u)) & 0xffu;
+        w[t >> 2] |= c << (8 * (t & 3));
+    }
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+__device__ __forceinline__ uint32_t reads_qual_word(uint32_t x) {      // min(q, 93) + 33 on each of the four bytes
+    uint32_t r = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) r |= (uint32_t)reads_qual_char((x >> (8 * k)) & 0xffu) << (8 * k);
+    return r;
+}
+
+// One run of an item's output: the characters [a, b) of a field (SEQ or QUAL) whose character 0 lies at out[origin].  Lane l takes
+// the 16-byte aligned chunks l, l + 64, ... of the output that the run touches: one store instruction of the wave is 1 KiB of
+// consecutive memory.  A chunk that lies inside the run is ONE aligned 16-byte store; the run's first and last chunk, which it may
+// share with a neighbouring item or field, are stored byte by byte, only the run's own bytes.  make(j0) gives the characters
+// j0 .. j0 + 15 of the field.
+template <class Make>
+__device__ __forceinline__ void reads_run(uint8_t *__restrict__ out, long long origin, long long a, long long b, int lane, Make make) {
+    const long long c0 = (origin + a) >> 4, c1 = (origin + b - 1) >> 4;
+    for (long long c = c0 + lane; c <= c1; c += WAVE) {
+        const long long j0 = 16 * c - origin;
+        const uint4 v = make(j0);
+        if (j0 >= a && j0 + 16 <= b) {
+            *reinterpret_cast<uint4 *>(out + 16 * c) = v;
+        } else {
+            const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int t = 0; t < 16; ++t)
+                if (j0 + t >= a && j0 + t < b) out[16 * c + t] = (uint8_t)(w[t >> 2] >> (8 * (t & 3)));
+        }
+    }
+}
+
+// One wave per work item (one-wave workgroups, grid-stride, no LDS): the bases [k * READS_SLICE, (k + 1) * READS_SLICE) of a
+// written record - their SEQ characters and their QUAL characters, two runs of the record's text at out_off[i].  Item 0 also
+// writes what is not a base: `@`, the name, and the three line ends.  With flag 0x10 character j of either field comes from base
+// l_seq - 1 - j: the source window of a chunk is the mirrored one, read once - no second pass.  Every output byte has exactly
+// one writer (the items of a record split [0, l_seq), the records split the text): no atomics.
+__global__ __launch_bounds__(WAVE) void k_bam_reads_emit(const uint8_t *__restrict__ buf, long long buf_bytes, const long long *__restrict__ rec_start,
+                                                         long long n_rec, MetaArrays M, const long long *__restrict__ item_off,
+                                                         const long long *__restrict__ out_off, uint8_t *__restrict__ out) {
+    const int lane = threadIdx.x;
+    const long long total = item_off[n_rec];
+    for (long long w = blockIdx.x; w < total; w += gridDim.x) {
+        const long long i = item_record(item_off, n_rec, w);
+        const long long l_seq = (long long)(uint32_t)M.l_seq[i];
+        const long long rs = rec_start[i];
+        const uint8_t *r = buf + rs;
+        const long long l_read_name = r[12];
+        const bool rev = (ld16(r + 18) & 0x10u) != 0;
+        const long long seq_at = M.seq_src[i], qual_at = seq_at + (l_seq + 1) / 2;
+        const bool has_qual = buf[qual_at] != 0xff;
+        const long long at = out_off[i];
+        const long long seq_origin = at + l_read_name + 1, qual_origin = seq_origin + l_seq + 3;
+        const long long k = w - item_off[i], a = k * READS_SLICE, b = min(l_seq, a + READS_SLICE);
+        if (k == 0) {
+            uint8_t *o = out + at;
+            for (long long j = lane; j < l_read_name - 1; j += WAVE) o[1 + j] = r[36 + j];
+            if (lane == 0) {
+                o[0] = '@';
+                o[l_read_name] = '\n';
+                out[seq_origin + l_seq] = '\n'; out[seq_origin + l_seq + 1] = '+'; out[seq_origin + l_seq + 2] = '\n';
+                out[qual_origin + l_seq] = '\n';
+            }
+        }
+        if (rev) reads_run(out, seq_origin, a, b, lane, [&](long long j0) { return reads_seq_chunk<true>(buf, seq_at, l_seq - 16 - j0, buf_bytes); });
+        else reads_run(out, seq_origin, a, b, lane, [&](long long j0) { return reads_seq_chunk<false>(buf, seq_at, j0, buf_bytes); });
+        reads_run(out, qual_origin, a, b, lane, [&](long long j0) {
+            if (!has_qual) return make_uint4(0x22222222u, 0x22222222u, 0x22222222u, 0x22222222u);
+            uint4 v = reads_window(buf, qual_at + (rev ? l_seq - 16 - j0 : j0), buf_bytes);
+            if (rev) v = reads_mirror(v);
+            return make_uint4(reads_qual_word(v.x), reads_qual_word(v.y), reads_qual_word(v.z), reads_qual_word(v.w));
+        });
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // K_index: what a batch contributes to the BAI index of the file (want_index; IndexPartial in coral_bam_common.h)
 // ---------------------------------------------------------------------------------------------
 struct IndexDev {                        // device arrays of the request, carved from the caller's workspace
@@ -1524,15 +1679,19 @@ inline bool dev_get(void *dst, const void *src, size_t bytes) { return bytes == 
 
 // The per-record scratch of the parse that a request may WRITE, built in emit.  Why that is safe:
 // - k_bam_emit has finished with every array named here: the batch's host copies synchronised the stream behind it.
-// - The requests are queued on the caller's stream in the order coverage, read QC, binned depth, index, so each runs behind the
-//   one in front.  Binned depth borrows nothing; it reads M.cig_src.
-//   Coverage and read QC use the same two arrays in turn.
+// - The requests are queued on the caller's stream in the order reads, coverage, read QC, binned depth, index, so each runs
+//   behind the one in front.  Binned depth borrows nothing; it reads M.cig_src.
+//   Reads, coverage and read QC use the same two arrays (items, item_off) in turn.  Reads also borrows out_len / out_off, which
+//   nothing behind it but the index uses (and that never rides with it); it has read them back before it returns (its offsets)
+//   and its k_bam_reads_emit, which reads out_off, runs in front of whatever is queued later.  Because M.name_len is `items`,
+//   the reads kernels take a record's l_read_name from its bytes.
 // - The index goes last because its out_key is M.cig_src, which the coverage and the depth walk read.  What every request only READS: the
 //   fixed fields of M (tid .. n_cigar, seq_src), the record starts and the end positions.
 // - All of it is queued in front of ev_parsed and of the next batch's k_bam_meta, which refills the arrays on the same stream.
 struct GpuDecoder;
 struct Borrowed {
-    long long *items, *item_off;                        // coverage, then read QC (M.name_len, M.sa_len)
+    long long *items, *item_off;                        // reads, then coverage, then read QC (M.name_len, M.sa_len)
+    long long *out_len, *out_off;                       // reads (M.pad_ops, d_cig_off)
     unsigned long long *voff, *out_voff;                // index (d_cig_off, M.sa_src)
     long long *key, *head, *head_off, *out_key;         // index (M.pad_ops, d_name_off, d_sa_off, M.cig_src)
 };
@@ -1689,6 +1848,57 @@ struct DepthRequest {                // binned depth: bin_off, the contig length
     }
 };
 
+struct ReadsRequest {                // FASTQ text of the selected records
+    bool active = false;
+    const ReadsRule *R = nullptr;    // the request (Request::reads)
+    ReadsDev X{};
+    uint8_t *text = nullptr;         // the batch's text: one buffer for all batches (collect)
+    size_t text_cap = 0, buf_bytes = 0;
+    long long pending_bytes = 0;     // text of the batch emitted last that is still on the device
+    // The output buffer is sized by a bound, not by a count: a record of l bases and a name field of n bytes (NUL included) takes
+    // at least 36 + n + 1.5 l bytes of the batch (block_size, the fixed fields, the name, SEQ, QUAL) and its text 2 l + n + 5, and
+    // 2 l + n + 5 <= 4/3 (36 + n + 1.5 l) = 48 + 4/3 n + 2 l.  So the text of all records of a batch fits 4/3 of the batch's bytes,
+    // the carried ones included (+ 256: the division's remainder and room to spare).
+    void carve(Carver &take, size_t batch_cap) {
+        if (!active) return;
+        buf_bytes = up256(batch_cap + COMP_SLACK);                 // (what d_infl[slot] really has: reads_window's guard)
+        const size_t n_seg = R->tid.size(), n_names = (size_t)R->n_names();
+        int32_t *seg = (int32_t *)take(3 * n_seg * 4);
+        uint8_t *names = (uint8_t *)take(R->names.size());
+        int64_t *off = (int64_t *)take((n_names + 1) * 8);
+        X = ReadsDev{seg, seg + n_seg, seg + 2 * n_seg, names, off, (int)n_seg, (long long)n_names, R->exclude_flags};
+        text_cap = batch_cap / 3 * 4 + 256;
+        text = (uint8_t *)take(text_cap);
+    }
+    const char *start(hipError_t &e) const {
+        if (!active) return nullptr;
+        const size_t b = (size_t)X.n_seg * 4;
+        const bool ok = (b == 0 || ((e = hipMemcpy((void *)X.tid, R->tid.data(), b, hipMemcpyHostToDevice)) == hipSuccess &&
+                                    (e = hipMemcpy((void *)X.lo, R->lo.data(), b, hipMemcpyHostToDevice)) == hipSuccess &&
+                                    (e = hipMemcpy((void *)X.hi, R->hi.data(), b, hipMemcpyHostToDevice)) == hipSuccess)) &&
+                        (X.n_names == 0 || ((e = hipMemcpy((void *)X.names, R->names.data(), R->names.size(), hipMemcpyHostToDevice)) == hipSuccess &&
+                                            (e = hipMemcpy((void *)X.name_off, R->name_off.data(), R->name_off.size() * 8, hipMemcpyHostToDevice)) == hipSuccess));
+        return ok ? nullptr : "reads request set-up";
+    }
+    bool batch(GpuDecoder *G, hipStream_t stream, const Borrowed &S, std::string &err);
+    // The text of the batch emitted last, if it is still on the device (the caller has synchronised the stream).  One buffer for
+    // all batches: QcRequest::collect's argument, under the same condition - every emit of a decode and the result call are
+    // given the SAME stream.
+    bool collect(Decoded &D) {
+        if (pending_bytes == 0) return true;
+        const size_t base = D.reads_text.size();
+        D.reads_text.resize(base + (size_t)pending_bytes);
+        const bool ok = hipMemcpy(D.reads_text.data() + base, text, (size_t)pending_bytes, hipMemcpyDeviceToHost) == hipSuccess;
+        pending_bytes = 0;
+        return ok;
+    }
+    bool finish(Decoded &D) {
+        if (!active) return true;
+        D.has_reads = true;
+        return collect(D);
+    }
+};
+
 struct GpuDecoder {
     MappedFile f;
     Decoded D;
@@ -1757,6 +1967,7 @@ struct GpuDecoder {
     QcRequest qc;
     IndexRequest idx;
     DepthRequest depth;
+    ReadsRequest reads;
     // span decode: the spans are decoded one after the other through the same batches
     std::vector<SpanDef> spans;
     int cur_span = 0;                         // the span the caller's thread is parsing
@@ -1840,6 +2051,39 @@ bool QcRequest::batch(GpuDecoder *G, hipStream_t stream, const Borrowed &S, std:
                        (unsigned long long *)rows, hist);
     if (!launched("read-QC", err)) return false;
     pending_n = n;
+    return true;
+}
+
+// The reads request goes FIRST behind the batch's host copies: it waits for its own totals (16 bytes: no read-back of the batch
+// lies behind these kernels, so they are a small copy of their own, as k_bam_keep_compact's count is), and in front of the other
+// requests that wait is only for its plan kernel and two scans.  The text itself is not waited for (collect).
+bool ReadsRequest::batch(GpuDecoder *G, hipStream_t stream, const Borrowed &S, std::string &err) {
+    if (!active) return true;
+    if (!collect(G->D)) { err = "copy of the reads text failed"; return false; }      // (of the batch in front: its kernels have run, ours are not queued yet)
+    const long long n = G->cur_n_rec;
+    if (n == 0) return true;
+    const uint8_t *buf = G->d_infl[G->k & 1];
+    hipLaunchKernelGGL(k_bam_reads_plan, dim3((unsigned)((n + 1 + WAVE - 1) / WAVE)), dim3(WAVE), 0, stream, buf, G->d_rec_start, n, G->M, G->d_end, X,
+                       S.out_len, S.items);
+    if (!G->scan(stream, S.out_len, S.out_off) || !G->scan(stream, S.items, S.item_off)) { err = "scan of the reads work items failed"; return false; }
+    std::vector<long long> off((size_t)n + 1);
+    long long items = 0;
+    if (hipMemcpyAsync(off.data(), S.out_off, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+        hipMemcpyAsync(&items, S.item_off + n, 8, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) {
+        err = std::string("reads plan failed: ") + hipGetErrorString(hipGetLastError());
+        return false;
+    }
+    const long long bytes = off[(size_t)n];
+    if (bytes < 0 || (size_t)bytes > text_cap || items < 0) { err = "reads request: the batch's text does not fit its buffer"; return false; }
+    if (bytes == 0) return true;                     // no record of the batch is written: nothing more is queued
+    const int64_t base = G->D.reads_off.back();
+    for (long long i = 0; i < n; ++i)
+        if (off[(size_t)i + 1] > off[(size_t)i]) G->D.reads_off.push_back(base + off[(size_t)i + 1]);
+    // one wave per workgroup, grid-stride beyond 8 per CU
+    hipLaunchKernelGGL(k_bam_reads_emit, dim3((unsigned)std::min<long long>(items, 2048)), dim3(WAVE), 0, stream, buf, (long long)buf_bytes, G->d_rec_start, n,
+                       G->M, S.item_off, S.out_off, text);
+    if (!launched("reads", err)) return false;
+    pending_bytes = bytes;
     return true;
 }
 
@@ -2165,6 +2409,7 @@ bool carve(GpuDecoder *G, void *ws, size_t bytes) {
     G->qc.carve(take, nr);
     G->cov.carve(take);
     G->depth.carve(take, G->D.depth);
+    G->reads.carve(take, (size_t)CARRY_CAP + G->infl_cap);
     if (ws && take.used > bytes) return false;
     G->ws_bytes = take.used;
     return true;
@@ -2278,6 +2523,8 @@ extern "C" int coral_bamgpu_open_request(const char *path, int32_t n_threads, in
     G->cov.T = &G->req.cov;
     if ((G->idx.active = R.want_index)) G->D.idx.init(G->D.ref_lens);
     if ((G->qc.active = R.want_qc)) G->D.qc.init();
+    G->reads.active = R.reads.on;
+    G->reads.R = &G->req.reads;
     if (R.depth_bin > 0) {                     // the rule that needs the header: at most 2^28 bins (refused here, nothing allocated)
         if (!G->D.depth.init(R.depth_bin, R.depth_min_mapq, R.depth_exclude_flags, R.depth_count_deletions, G->D.ref_lens, err)) { set_error(err); return CORAL_ERR_ARG; }
         G->depth.active = true;
@@ -2316,14 +2563,14 @@ extern "C" int coral_bamgpu_open(const char *path, int32_t n_threads, int32_t ra
 
 // Once every batch has been emitted: waits for `stream_` and leaves what was requested in the host-side result
 // (coral_bamgpu_host -> coral_bam_coverage_result, coral_bam_index_sizes / _fill, coral_bam_qc_sizes / _fill,
-// coral_bam_depth_sizes / _fill).
+// coral_bam_depth_sizes / _fill, coral_bam_reads_sizes / _fill).
 extern "C" int coral_bamgpu_finish(void *handle, void *stream_) {
     GpuDecoder *G = (GpuDecoder *)handle;
     if (!G) return CORAL_ERR_ARG;
     if (!G->finished || G->have_cur) { set_error("coral_bamgpu_finish: the decode is not finished"); return CORAL_ERR_ARG; }
-    if (!G->cov.active && !G->qc.active && !G->idx.active && !G->depth.active) return CORAL_OK;
+    if (!G->cov.active && !G->qc.active && !G->idx.active && !G->depth.active && !G->reads.active) return CORAL_OK;
     if (hipStreamSynchronize((hipStream_t)stream_) != hipSuccess || !G->cov.finish(G->D) || !G->idx.finish(G->D.idx) || !G->qc.finish(G->D.qc) ||
-        !G->depth.finish(G->D.depth)) {
+        !G->depth.finish(G->D.depth) || !G->reads.finish(G->D)) {
         set_error("coral_bamgpu_finish: copy of the requested results failed");
         return CORAL_ERR_HIP;
     }
@@ -2364,7 +2611,7 @@ extern "C" int coral_bamgpu_start(void *handle, void *workspace, int64_t workspa
     if ((e = hipStreamCreateWithFlags(&G->s_crc, hipStreamNonBlocking)) != hipSuccess) return bad("hipStreamCreate", e);
     G->t_alloc = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_alloc0).count();
     const char *what;
-    if ((what = G->idx.start(G->D.idx, e)) || (what = G->qc.start(e)) || (what = G->cov.start(e)) || (what = G->depth.start(G->D.depth, e))) return bad(what, e);
+    if ((what = G->idx.start(G->D.idx, e)) || (what = G->qc.start(e)) || (what = G->cov.start(e)) || (what = G->depth.start(G->D.depth, e)) || (what = G->reads.start(e))) return bad(what, e);
     G->feeder = std::thread(feeder_main, G);
     G->worker = std::thread(worker_main, G);
     return CORAL_OK;
@@ -2682,9 +2929,9 @@ extern "C" int coral_bamgpu_emit(void *handle, uint32_t *cigar_dst, int64_t *cig
     } else if (hipStreamSynchronize(stream) != hipSuccess) {
         return fail(CORAL_ERR_HIP, "hipStreamSynchronize failed");
     }
-    const Borrowed S{G->M.name_len, G->M.sa_len, (unsigned long long *)G->d_cig_off, (unsigned long long *)G->M.sa_src, G->M.pad_ops, G->d_name_off, G->d_sa_off, G->M.cig_src};
+    const Borrowed S{G->M.name_len, G->M.sa_len, G->M.pad_ops, G->d_cig_off, (unsigned long long *)G->d_cig_off, (unsigned long long *)G->M.sa_src, G->M.pad_ops, G->d_name_off, G->d_sa_off, G->M.cig_src};
     std::string err;
-    if (!G->cov.batch(G, stream, S, err) || !G->qc.batch(G, stream, S, err) || !G->depth.batch(G, stream, err) || !G->idx.batch(G, stream, S, err))
+    if (!G->reads.batch(G, stream, S, err) || !G->cov.batch(G, stream, S, err) || !G->qc.batch(G, stream, S, err) || !G->depth.batch(G, stream, err) || !G->idx.batch(G, stream, S, err))
         return fail(CORAL_ERR_HIP, err);
     // this buffer may be inflated into again (batch k + 2) once everything above has run
     if (hipEventRecord(G->ev_parsed[slot], stream) != hipSuccess) return fail(CORAL_ERR_HIP, "hipEventRecord failed");

@@ -391,7 +391,9 @@ const char *coral_bam_last_error(void);
  * depth_min_mapq 0..255, depth_exclude_flags 0..0xffff, depth_count_deletions 0 or 1, no span decode, at most 2^28 bins over
  * the header's contigs (checked once the header is read: refused before anything is decoded or allocated); keep_min_mapq
  * 0..255, keep_min_seq_length 0..2^29, keep_require_flags and keep_exclude_flags 0..0xffff, and no active record filter together
- * with want_index.  A span decode is not sharded: rank and world are taken as 0 and 1. */
+ * with want_index; want_reads 0 or 1, and with want_reads = 1: reads_exclude_flags 0..0xffff, reads_seg under the rules of the
+ * coverage segments, reads_names of 1..254 bytes each, strictly ascending, and no want_index.  A span decode is not sharded:
+ * rank and world are taken as 0 and 1. */
 typedef struct {
     int32_t rank, world;                       /* byte range (ignored when n_spans >= 0) */
     int32_t n_spans;                           /* -1: the byte range; >= 0: only records starting inside these spans */
@@ -403,6 +405,14 @@ typedef struct {
     int32_t per_base;                          /* 0: counts per segment; else: the table per position and base (pileup) */
     int32_t depth_bin;                         /* 0: no binned-depth request; >= 1: the bin size */
     int32_t depth_min_mapq, depth_exclude_flags, depth_count_deletions;
+    /* the reads request: want_reads 0 = none */
+    int32_t want_reads;                        /* 1: the selected records as FASTQ text (coral_bam_reads_sizes / _fill) */
+    int32_t reads_exclude_flags;               /* 0..0xffff  written only when (flag & it) == 0 */
+    int32_t reads_n_seg;                       /* 0: no region limit; else sorted, disjoint segments, the coverage segments' rules */
+    const int32_t *reads_seg_tid, *reads_seg_start, *reads_seg_end;
+    int32_t reads_n_names;                     /* 0: no name limit; else names of 1..254 bytes, sorted ascending by their bytes */
+    const uint8_t *reads_names;                /*    (memcmp, then length), no duplicates: one blob ...                        */
+    const int64_t *reads_name_off;             /*    ... and reads_n_names + 1 offsets into it                                 */
     /* the record filter: all four 0 = none.  A record is kept when all four tests hold. */
     int32_t keep_min_mapq;                     /* 0..255    keep when mapq >= it               (samtools view -q) */
     int32_t keep_min_seq_length;               /* 0..2^29   keep when l_seq >= it              (awk 'length($10) > 1000': 1001) */
@@ -489,7 +499,22 @@ typedef struct {
  *   A dropped record is validated only as far as the boundary walk and its fixed fields go (block_size >= 32): its tags are
  *   not walked, so a malformed tag in a dropped record is not an error, in either pipeline.  depth_min_mapq and
  *   depth_exclude_flags stay and apply on top of the filter (a logical AND).  Not together with want_index: the virtual
- *   offsets of a file that does not exist mean nothing. */
+ *   offsets of a file that does not exist mean nothing.
+ *
+ * Reads (want_reads = 1) - replaces the second pass over the file that the reference's workflow makes to get at the reads behind
+ * an amplicon: `samtools view x.bam region... | samtools fastq`, or `samtools view -N names.txt` when the supporting alignment
+ * is a hard-clipped supplementary and the whole read sits at its primary record elsewhere (its scripts start and end at FASTQ:
+ * scripts/align_nanopore_reads.sh, scripts/report_nanopore_qc.py).  A record is WRITTEN when l_seq > 0, (flag &
+ * reads_exclude_flags) == 0, with segments: tid >= 0 and [pos, bam_endpos) - [pos, pos + 1) with flag 0x4 - meets a non-empty
+ * segment, with names: its read name (without the NUL) is in the list, found by an exact binary search.  Segments and names
+ * intersect; neither means every read.  An active record filter acts first.  The text of a written record is exactly
+ *   `@` name `\n` SEQ `\n+\n` QUAL `\n`          (2 l_seq + l_read_name + 5 bytes)
+ * with SEQ characters "=ACMGRSVTWYHKDBN"[code], QUAL characters min(q, 93) + 33, l_seq times `"` (quality 1) for a record whose
+ * first QUAL byte is 0xff; with flag 0x10 SEQ is reversed and complemented (the complement of a 4-bit code is its bit reversal)
+ * and QUAL reversed, so the read has the orientation it was sequenced in.  Nothing is appended to the name; records come in
+ * file order.  Allowed on byte ranges (the texts of consecutive ranges concatenate) and on span decodes, not with want_index.
+ *   reads_sizes -> records written, text bytes; reads_fill copies the text and the n + 1 int64 offsets of the records in it.
+ *   The whole result lives in host memory: meant for the reads of an amplicon, not for a whole 2 M-read file. */
 int coral_bam_decode_request(const char *path, int32_t n_threads, const coral_bam_request_t *req, void **handle);
 int coral_bam_coverage_result(void *handle, int32_t n_seg, int64_t *counts);
 int coral_bam_pileup_result(void *handle, int64_t n_pos, uint32_t *counts);
@@ -501,6 +526,8 @@ int coral_bam_qc_fill(void *handle, int32_t *length, int64_t *qual_sum, int32_t 
                       int64_t counters[8]);
 int coral_bam_depth_sizes(void *handle, int64_t sizes[2]);
 int coral_bam_depth_fill(void *handle, int64_t *bin_off, int64_t *bases, int64_t *reads);
+int coral_bam_reads_sizes(void *handle, int64_t sizes[2]);
+int coral_bam_reads_fill(void *handle, uint8_t *text, int64_t *rec_off);
 
 /* ------------------------------------------------------------------------------------------------
  * coral_bamgpu_* — the same decode with the inflate and the record parsing ON THE GPU: the host reads the file and sends
@@ -550,9 +577,16 @@ int coral_bam_depth_fill(void *handle, int64_t *bin_off, int64_t *bases, int64_t
  *                      record starts in the workspace) between the boundary walk and the record parse; the kept count is read
  *                      back (8 bytes per batch) and is the batch's record count from there on: out[0] of `next`.  A batch
  *                      whose records are all dropped is pending with out[0] = out[1] = 0 and must be emitted like any other
+ *            want_reads  k_bam_reads_plan (one thread per record in one-wave workgroups: the rule, the record's text bytes and its
+ *                      work items of 16 384 bases), two scans and k_bam_reads_emit (one wave per work item in at most 2 048
+ *                      one-wave workgroups without LDS: a lane makes 16 consecutive output characters from the nibbles / QUAL
+ *                      bytes that cover them, mirrored for flag 0x10; aligned 16-byte stores inside an item, bytes at its two
+ *                      edges; no atomics) write the batch's text into a buffer of the workspace (4/3 of a batch + 256 bytes),
+ *                      which is copied to the host once the next batch's emit has synchronised the stream; the segments and the
+ *                      name list live in the workspace too.  The totals come back on their own (16 bytes per batch)
  *   finish        after the last batch (CORAL_ERR_ARG before): waits for `stream` once and leaves what was requested in the
  *          handle of `host` (coral_bam_coverage_result, coral_bam_pileup_result - the table is copied and summed per segment
- *          here -, coral_bam_index_sizes / _fill, coral_bam_qc_sizes / _fill, coral_bam_depth_sizes / _fill); fails when
+ *          here -, coral_bam_index_sizes / _fill, coral_bam_qc_sizes / _fill, coral_bam_depth_sizes / _fill, coral_bam_reads_sizes / _fill); fails when
  *          an index was requested and the records are not in coordinate order; with nothing requested it does nothing
  * coral_bgzf_inflate: one inflate launch over caller-provided device buffers — desc = n_blocks x {src_off, src_len,
  * dst_off, isize} uint32 (raw DEFLATE streams in `comp`, which must be readable 4096 bytes beyond the last stream);
