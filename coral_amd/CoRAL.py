@@ -7,7 +7,8 @@
 The `reconstruct` mode and the `hsr` mode (§8(f) item 3) run on the MI355X path, and so do `index`, `qc`
 (the reference's scripts/report_nanopore_qc.py, from one decode of the aligned BAM), `pileup` (the bases per position of
 regions, pysam's count_coverage as a table) and `depth` (read depth per fixed-size bin of every contig, the table a copy-number
-caller starts from) and `fastq` (selected reads as FASTQ, by regions or read names); the other modes of the
+caller starts from), `fastq` (selected reads as FASTQ, by regions or read names) and `view` (the same selection as a BAM file of
+the records themselves, with its index on request); the other modes of the
 reference (seed, plot, cycle2bed) are untouched and are delegated to the reference's own modules when they are
 importable (set CORAL_REFERENCE_SRC to the reference's src/ directory).  The cycle-decomposition step after the graph build is the
 reference's (Gurobi); it runs on the object this module returns.
@@ -113,7 +114,17 @@ def build_parser():
                     type=lambda x: int(x, 0), default=0x900)
     fp.add_argument("--output", help="Name of the FASTQ file.", required=True)
     fp.add_argument("--device", help="GPU to use ('cpu': the host pipeline).", default="cuda:0")
-    for p in (rp, hp, qp, pp, dp, fp):
+    vp = sub.add_parser("view", help="Write selected records of a (long read) bam file as a BAM file, from one decode of it.")
+    vp.add_argument("--lr_bam", help="(Long read) bam file.", required=True)
+    vp.add_argument("--region", help="chr:start-stop (0-based, half-open): only records that overlap it; may be given several times.", action="append")
+    vp.add_argument("--names_file", help="File of read names, one per line: only the records of these reads.")
+    vp.add_argument("--reads_exclude_flags", help="Leave out records with any of these flag bits (default: none).",
+                    type=lambda x: int(x, 0), default=0)
+    vp.add_argument("--level", help="Compression level of the BAM file, 0..9.", type=int, default=1)
+    vp.add_argument("--index", help="If specified, also write the BAI index (<output>.bai).", action='store_true')
+    vp.add_argument("--output", help="Name of the BAM file.", required=True)
+    vp.add_argument("--device", help="GPU to use ('cpu': the host pipeline).", default="cuda:0")
+    for p in (rp, hp, qp, pp, dp, fp, vp):
         add_filter_arguments(p)
     for mode in ("seed", "plot", "cycle2bed"):
         sub.add_parser(mode, help="(reference implementation; not part of the MI355X path)", add_help=False)
@@ -216,9 +227,8 @@ def depth_mode(args):
     return args.output
 
 
-def fastq_mode(args):
-    """The selected reads as FASTQ (bam.extract_reads): by regions, by names, both (intersected) or neither (every read)."""
-    from coral_amd import bam
+def selection_of(args):
+    """(regions, names) of the --region and --names_file arguments; None where there is none."""
     regions = None
     if args.region:
         regions = []
@@ -230,9 +240,29 @@ def fastq_mode(args):
     if args.names_file:
         with open(args.names_file) as fp:
             names = [ln.strip() for ln in fp if ln.strip()]
+    return regions, names
+
+
+def fastq_mode(args):
+    """The selected reads as FASTQ (bam.extract_reads): by regions, by names, both (intersected) or neither (every read)."""
+    from coral_amd import bam
+    regions, names = selection_of(args)
     reads = bam.extract_reads(args.lr_bam, regions, names, args.reads_exclude_flags, device=args.device, record_filter=record_filter_of(args))
     reads.write(args.output)
     print("Wrote %s (%d reads)" % (args.output, reads.n))
+    return args.output
+
+
+def view_mode(args):
+    """The selected records as a BAM file (bam.extract_records + RecordBytes.write): the selection of `fastq`, the records
+    themselves - alignments, tags and all - under the source's header, with the BAI index on request."""
+    from coral_amd import bam
+    regions, names = selection_of(args)
+    rec = bam.extract_records(args.lr_bam, regions, names, args.reads_exclude_flags, device=args.device, record_filter=record_filter_of(args))
+    if rec.header is None:                                       # an empty names file: nothing was decoded
+        rec.header = bam.bam_header_bytes(args.lr_bam)
+    rec.write(args.output, level=args.level, index=args.index)
+    print("Wrote %s (%d records)" % (args.output, rec.n))
     return args.output
 
 
@@ -269,6 +299,8 @@ def main(argv=None):
         return depth_mode(args)
     if args.mode == "fastq":
         return fastq_mode(args)
+    if args.mode == "view":
+        return view_mode(args)
     parser.print_help()
     return None
 

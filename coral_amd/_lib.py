@@ -38,7 +38,8 @@ def bam_request(rank: int = 0, world: int = 1, spans=None, coverage=None, index:
     [3][S], quality threshold, read_callback code) or None, ``per_base``: the coverage as the table per position and base (the
     pileup), ``depth`` = (bin size, min_mapq, exclude_flags, count_deletions) or None: the binned-depth request, ``keep`` = (min_mapq, min_seq_length, require_flags, exclude_flags) (a
     ``bam.RecordFilter`` is one) or None: the record filter, ``reads`` = (exclude_flags, segments int32 [3][S] or None, names = a list
-    of bytes or None) or None: the reads request (no segment / no name: no such limit).  The struct keeps the contiguous arrays it points into alive; the rules are the library's to check."""
+    of bytes or None[, mode]) or None: the reads request (no segment / no name: no such limit; mode 1, the default: FASTQ text,
+    2: the records' own bytes).  The struct keeps the contiguous arrays it points into alive; the rules are the library's to check."""
     req = coral_bam_request_t(rank=rank, world=world, n_spans=-1, n_seg=-1, want_index=int(index), want_qc=int(qc), per_base=int(per_base))
     req.arrays = []
     if depth is not None:
@@ -50,8 +51,8 @@ def bam_request(rank: int = 0, world: int = 1, spans=None, coverage=None, index:
         req.arrays.append(np.ascontiguousarray(a, dtype=dtype))
         return req.arrays[-1].ctypes.data
     if reads is not None:                    # (in front of the coverage request: its segment rows stay the last arrays)
-        exclude_flags, segs, names = reads
-        req.want_reads, req.reads_exclude_flags = 1, int(exclude_flags)
+        exclude_flags, segs, names = reads[:3]
+        req.want_reads, req.reads_exclude_flags = (int(reads[3]) if len(reads) > 3 else 1), int(exclude_flags)
         if segs is not None:
             segs = np.asarray(segs, dtype=np.int32).reshape(3, -1)
             req.reads_n_seg = segs.shape[1]
@@ -160,6 +161,7 @@ def lib():
     L.coral_bam_depth_fill.argtypes = [C.c_void_p, P, P, P]
     L.coral_bam_reads_sizes.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
     L.coral_bam_reads_fill.argtypes = [C.c_void_p, P, P]
+    L.coral_bgzf_write.argtypes = [C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int32, C.c_int32, C.c_int32]
     L.coral_bamgpu_open_request.argtypes = [C.c_char_p, C.c_int32, C.c_int64, Q, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
     L.coral_bamgpu_finish.argtypes = [C.c_void_p, P]
     with open(os.path.join(os.path.dirname(_HERE), "include", "coral_hip.h")) as fp:

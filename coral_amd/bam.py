@@ -217,8 +217,8 @@ def decode_bam_gpu(path: str, device="cuda:0", n_threads: Optional[int] = None, 
 class DecodeResult(collections.namedtuple("DecodeResult", "records counts index qc")):
     """What _decode returns; what it was not asked for is None.  It unpacks as these four; the table of a pileup request
     (uint32 [positions][4]) is the attribute ``pileup``, the result of a binned-depth request the attribute ``depth``
-    (bin_off int64 [contigs + 1], bases and reads int64 [bins]), the result of a reads request the attribute ``reads`` (text uint8,
-    offsets int64 [records + 1])."""
+    (bin_off int64 [contigs + 1], bases and reads int64 [bins]), the result of a reads request the attribute ``reads`` (text - in
+    mode 2 the records' bytes - uint8, offsets int64 [records + 1])."""
     pileup = None
     depth = None
     reads = None
@@ -232,7 +232,7 @@ def _decode(path: str, device, *, n_threads: Optional[int] = None, rank: int = 0
     ``per_base`` the coverage is counted per position and base: ``pileup`` is the uint32 table [positions of the segments, in
     segment order][A, C, G, T] and ``counts`` its sums per segment.  ``depth`` = (bin size, min_mapq, exclude_flags,
     count_deletions) gives the binned-depth tables (``binned_depth``), ``reads`` = (exclude_flags, segments or None, sorted names or
-    None) the FASTQ text of the selected records (``extract_reads``).  ``record_filter``: a ``RecordFilter``; every result is
+    None[, mode]) the FASTQ text of the selected records (``extract_reads``) or, with mode 2, their own bytes (``extract_records``).  ``record_filter``: a ``RecordFilter``; every result is
     then that of a file holding only the kept records.  On the GPU pipeline when ``_on_gpu(device)``, else on the host."""
     req = _lib.bam_request(rank, world, spans, coverage, index, qc, per_base, depth, keep=_as_filter(record_filter), reads=reads)
     if _on_gpu(device):
@@ -908,6 +908,14 @@ def extract_reads(path: str, regions=None, names=None, exclude_flags: int = 0x90
     the decode to the BGZF blocks it names; with names only, or neither, the byte range (``rank`` of ``world``) is decoded and
     ``merge_reads`` joins the ranges.  ``record_filter``: a ``RecordFilter``, applied first.  The whole result lives in host
     memory: meant for the reads of an amplicon, not for every read of a 2 M-read file."""
+    got = _selected(1, path, regions, names, exclude_flags, device, n_threads, rank, world, batch_bytes, index, record_filter)
+    return Reads(*got) if got is not None else Reads()
+
+
+def _selected(mode: int, path, regions, names, exclude_flags, device, n_threads, rank, world, batch_bytes, index, record_filter):
+    """What ``extract_reads`` (mode 1) and ``extract_records`` (mode 2) share: the argument rules, the index use and the decode ->
+    (bytes uint8, offsets int64 [n + 1]) of the reads request, or None for a selection that is empty before any record is decoded
+    (an empty list: the file is not opened)."""
     if isinstance(exclude_flags, bool) or not isinstance(exclude_flags, numbers.Integral) or not 0 <= exclude_flags <= 0xffff:
         raise ValueError("exclude_flags must be an integer in 0..0xffff, got %r" % (exclude_flags,))
     if names is not None:
@@ -916,17 +924,17 @@ def extract_reads(path: str, regions=None, names=None, exclude_flags: int = 0x90
             if not 1 <= len(nm) <= 254:
                 raise ValueError("a read name has 1..254 bytes, got %r" % (nm,))
     if (regions is not None and len(list(regions)) == 0) or (names is not None and len(names) == 0):
-        return Reads()
+        return None
     if n_threads is None:
         n_threads = default_threads()
     if regions is None:
         res = _decode(path, device, n_threads=n_threads, rank=rank, world=world, batch_bytes=batch_bytes, records=False,
-                      record_filter=record_filter, reads=(exclude_flags, None, names))
-        return Reads(*res.reads)
+                      record_filter=record_filter, reads=(exclude_flags, None, names, mode))
+        return res.reads
     ref_names = bam_reference_names(path)
     _, segs = pileup_regions(list(regions), ref_names)
     if segs.shape[1] == 0:                                       # only empty regions
-        return Reads()
+        return None
     idx, skipped = None, None
     if index is not None and index is not False:
         if world != 1:
@@ -945,16 +953,116 @@ def extract_reads(path: str, regions=None, names=None, exclude_flags: int = 0x90
     if spans is not None and len(spans) == 0:
         LAST_DECODE.clear()
         LAST_DECODE.update(seconds=0.0, compressed_bytes=0, uncompressed_bytes=0, blocks=0, threads=int(n_threads))
-        out = Reads()
+        out = None
     else:
         res = _decode(path, device, n_threads=n_threads, rank=rank, world=world, batch_bytes=batch_bytes, spans=spans, records=False,
-                      record_filter=record_filter, reads=(exclude_flags, segs, names))
-        out = Reads(*res.reads)
+                      record_filter=record_filter, reads=(exclude_flags, segs, names, mode))
+        out = res.reads
     if idx is not None:
         LAST_DECODE.update(index=idx.path or "<object>", spans=int(len(spans)))
     else:
         LAST_DECODE.update(index=None, index_skipped=skipped)
     return out
+
+
+# ----------------------------------------------------------------------------------------------
+# records: the selected records' own bytes, and the BAM file around them
+# ----------------------------------------------------------------------------------------------
+def bam_header_bytes(path: str) -> bytes:
+    """The inflated bytes of a BAM file in front of its first record, verbatim: magic, header text, contig names and lengths
+    (read with gzip, as ``bam_reference_names`` reads them)."""
+    with gzip.open(path, "rb") as fp:
+        out = []
+
+        def take(n):
+            b = fp.read(n)
+            if len(b) != n:
+                raise _lib.CoralHipError("%s: truncated BAM header" % path)
+            out.append(b)
+            return b
+        if take(4) != b"BAM\x01":
+            raise _lib.CoralHipError("%s: not a BAM file" % path)
+        take(struct.unpack("<i", take(4))[0])
+        for _ in range(struct.unpack("<i", take(4))[0]):
+            take(struct.unpack("<i", take(4))[0])
+            take(4)
+        return b"".join(out)
+
+
+class RecordBytes:
+    """The records one decode selected (``extract_records``) as they stand in the source's inflated stream: ``data`` uint8, per
+    record its block_size word and the block_size bytes behind it, in file order; ``offsets`` int64 [n + 1] where each starts;
+    ``n`` their number; ``header`` the source's inflated bytes in front of its first record (None where the file was never opened:
+    an empty ``regions`` or ``names`` list)."""
+
+    def __init__(self, data=None, offsets=None, header: Optional[bytes] = None):
+        self.data = np.ascontiguousarray(data if data is not None else np.zeros(0, dtype=np.uint8), dtype=np.uint8)
+        self.offsets = np.ascontiguousarray(offsets if offsets is not None else np.zeros(1, dtype=np.int64), dtype=np.int64)
+        if len(self.offsets) < 1 or int(self.offsets[0]) != 0 or int(self.offsets[-1]) != len(self.data):
+            raise ValueError("RecordBytes: the offsets do not fit the data")
+        self.n = len(self.offsets) - 1
+        self.header = None if header is None else bytes(header)
+
+    def __len__(self):
+        return self.n
+
+    def names(self):
+        raw = self.data.tobytes()
+        return [raw[a + 36:a + 36 + raw[a + 12] - 1].decode("latin-1") for a in self.offsets[:-1].tolist()]
+
+    def write(self, path: str, level: int = 1, index: bool = False, n_threads: Optional[int] = None) -> str:
+        """The header and the records as a BGZF / BAM file (coral_bgzf_write: blocks of at most 0xff00 bytes, the header in
+        blocks of its own, the EOF block last; ``level`` 0..9; the bytes do not depend on ``n_threads``).  ``index``: also its
+        BAI index beside it (``build_index`` of the file written, host pipeline; the records must be in coordinate order, as
+        those of a sorted source are)."""
+        if self.header is None:
+            raise ValueError("RecordBytes.write needs the source's header (bam_header_bytes)")
+        if isinstance(level, bool) or not isinstance(level, numbers.Integral) or not 0 <= level <= 9:
+            raise ValueError("level must be an integer in 0..9, got %r" % (level,))
+        L = _lib.lib()
+        head = np.frombuffer(self.header, dtype=np.uint8)
+        parts = (C.c_void_p * 2)(head.ctypes.data, self.data.ctypes.data if len(self.data) else None)
+        sizes = (C.c_int64 * 2)(len(head), len(self.data))
+        rc = L.coral_bgzf_write(os.fsencode(path), parts, sizes, 2, int(level), n_threads or default_threads())
+        if rc != 0:
+            raise _lib.CoralHipError("coral_bgzf_write(%s) failed (%d): %s" % (path, rc, L.coral_bam_last_error().decode()))
+        if index:
+            build_index(path, device="cpu")
+        return path
+
+
+def merge_record_bytes(parts: Sequence[RecordBytes]) -> RecordBytes:
+    """The results of consecutive byte ranges (in rank order) as one: the bytes concatenated.  The parts are of one file: their
+    headers must be equal."""
+    parts = list(parts)
+    if not parts:
+        raise ValueError("merge_record_bytes needs at least one part")
+    if any(p.header != parts[0].header for p in parts[1:]):
+        raise ValueError("merge_record_bytes: the parts have different headers")
+    base = np.concatenate([[0], np.cumsum([len(p.data) for p in parts])]).astype(np.int64)
+    return RecordBytes(np.concatenate([p.data for p in parts]),
+                       np.concatenate([np.zeros(1, dtype=np.int64)] + [p.offsets[1:] + b for p, b in zip(parts, base)]), parts[0].header)
+
+
+def extract_records(path: str, regions=None, names=None, exclude_flags: int = 0, device="cuda:0", n_threads: Optional[int] = None,
+                    rank: int = 0, world: int = 1, batch_bytes: int = 0, *, index=None, record_filter=None) -> RecordBytes:
+    """The selected records of the BAM file as raw BAM record bytes (``RecordBytes``), copied out while it is decoded; with
+    ``RecordBytes.write`` what ``samtools view -b x.bam region... > amp.bam && samtools index amp.bam`` gets from a second pass.
+
+    The arguments, the index use and the empty-selection shortcuts are ``extract_reads``'s, and so is the rule but for one
+    condition: a record is written when ``flag & exclude_flags == 0`` (default 0: nothing is left out), with ``regions``: it is
+    on a region's contig and ``[pos, end)`` meets the region (flag 0x4: ``[pos, pos + 1)``), with ``names``: its read name is
+    listed - SEQ is NOT required: a record without SEQ is still a record.  ``record_filter`` acts first.  Every written record
+    is ``4 + block_size`` bytes, byte for byte the source's (a CIGAR in a CG:B,I tag stays there), in file order.
+
+    GPU pipeline (k_bam_reads_plan / k_bam_reads_copy per batch) on a GPU ``device``, host pipeline with ``device="cpu"`` or
+    ``CORAL_BAM_DECODE=cpu``; identical bytes.  ``merge_record_bytes`` joins byte ranges.  The whole result lives in host memory:
+    meant for the records of an amplicon, not for a whole 2 M-read file; nothing is streamed to disk."""
+    regions, names = (None if x is None else list(x) for x in (regions, names))
+    got = _selected(2, path, regions, names, exclude_flags, device, n_threads, rank, world, batch_bytes, index, record_filter)
+    if got is None and (regions == [] or names == []):
+        return RecordBytes()                                     # (the file was not opened: no header)
+    return RecordBytes(*(got if got is not None else (None, None)), header=bam_header_bytes(path))
 
 
 # ----------------------------------------------------------------------------------------------

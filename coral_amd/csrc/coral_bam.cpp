@@ -14,7 +14,8 @@
 //     stage 3 (worker pool)   parse the chunk's records into a per-chunk partial (CIGAR copy + padding, SA tokens, NM,
 //                             non-ACGT scan; with a window-coverage request the chunk's
 //                             partial counts per segment, added up in stage 4; with a reads request the
-//                             FASTQ text of the chunk's written records, concatenated in stage 4)
+//                             FASTQ text - or, with want_reads = 2, the own bytes - of the chunk's written records,
+//                             concatenated in stage 4)
 //     stage 4 (caller)        append the partials in file order; read names -> ids
 // A byte range [rank, world) of the file can be decoded on its own (one process per GPU): the range
 // starts at the first BGZF block at or after its first byte (blocks are found by their magic + BC subfield and a chained
@@ -185,7 +186,8 @@ bool decode_file(const char *path, int n_threads, const Request &R, const Span *
                 if (!decode_record(q + 4, rd32(q), ref_id, pt, pt.error, cov, want_qc, D.pileup.data(), depth)) break;
                 if (reads && reads->written(q, pt.end.back())) {      // the reads request: the chunk's text, concatenated in merge()
                     const size_t at = pt.reads_text.size();
-                    reads_append_text(q, pt.reads_text);
+                    if (reads->mode == READS_AS_RECORDS) reads_append_record(q, pt.reads_text);
+                    else reads_append_text(q, pt.reads_text);
                     pt.reads_len.push_back((int64_t)(pt.reads_text.size() - at));
                 }
             }
@@ -617,7 +619,8 @@ extern "C" int coral_bam_depth_fill(void *handle, int64_t *bin_off, int64_t *bas
     return CORAL_OK;
 }
 
-// The reads request of a handle (either pipeline): sizes = records written, text bytes; fill = the text and the n + 1 offsets.
+// The reads request of a handle (either pipeline): sizes = records written, text bytes; fill = the text and the n + 1 offsets
+// (want_reads = 2: the records' own bytes in place of the text).
 extern "C" int coral_bam_reads_sizes(void *handle, int64_t sizes[2]) {
     if (!handle || !sizes) return CORAL_ERR_ARG;
     const Decoded *D = (const Decoded *)handle;
@@ -769,5 +772,53 @@ extern "C" int coral_bam_write(const char *path, int64_t n_rec, const int32_t *t
     ok = ok && fwrite(EOF_BLOCK, 1, 28, fp) == 28;
     ok = (fclose(fp) == 0) && ok;
     if (!ok) { g_bam_err = "writing the BAM file failed"; return CORAL_ERR_FORMAT; }
+    return CORAL_OK;
+}
+
+// `n_parts` byte strings -> one BGZF file (the writer behind bam.RecordBytes.write: part 0 the BAM header, part 1 the records).
+// Every part is cut into blocks of at most 0xff00 input bytes and starts a block of its own, so the header ends a block as
+// htslib's does and the first record's virtual offset has a zero low half; an empty part makes no block.  The blocks are shared
+// out over n_threads as tasks of BGZF_TASK_BLOCKS consecutive blocks of one part, deflated independently of each other (the
+// bytes do not depend on n_threads) and written in order; the 28-byte EOF block goes last.
+extern "C" int coral_bgzf_write(const char *path, const uint8_t *const *parts, const int64_t *part_bytes, int32_t n_parts, int32_t level,
+                                int32_t n_threads) {
+    if (!path) { g_bam_err = "coral_bgzf_write: no path"; return CORAL_ERR_ARG; }
+    if (level < 0 || level > 9) { g_bam_err = "coral_bgzf_write: level must be 0..9"; return CORAL_ERR_ARG; }
+    if (n_parts < 0 || (n_parts > 0 && (!parts || !part_bytes))) { g_bam_err = "coral_bgzf_write: n_parts must be >= 0, with the parts and their sizes"; return CORAL_ERR_ARG; }
+    struct Task { const uint8_t *in; size_t n; };
+    const size_t BGZF_TASK_BLOCKS = 16, task_bytes = BGZF_TASK_BLOCKS * 0xff00;
+    std::vector<Task> tasks;
+    for (int32_t k = 0; k < n_parts; ++k) {
+        if (part_bytes[k] < 0 || (part_bytes[k] > 0 && !parts[k])) { g_bam_err = "coral_bgzf_write: bad part"; return CORAL_ERR_ARG; }
+        for (size_t at = 0, n = (size_t)part_bytes[k]; at < n; at += task_bytes) tasks.push_back(Task{parts[k] + at, std::min(task_bytes, n - at)});
+    }
+    FILE *fp = fopen(path, "wb");
+    if (!fp) { g_bam_err = std::string("cannot create ") + path; return CORAL_ERR_ARG; }
+    const int nt = n_threads < 1 ? 1 : (n_threads > 64 ? 64 : n_threads);
+    const size_t n_tasks = tasks.size();
+    bool ok = true;
+    for (size_t wave = 0; wave < n_tasks && ok; wave += 4 * (size_t)nt) {
+        const size_t w1 = std::min(n_tasks, wave + 4 * (size_t)nt);
+        std::vector<std::vector<uint8_t>> outs(w1 - wave);
+        std::atomic<size_t> next{wave};
+        std::atomic<bool> bad{false};
+        auto work = [&]() {
+            for (;;) {
+                const size_t t = next.fetch_add(1);
+                if (t >= w1) return;
+                if (!bgzf_compress(tasks[t].in, tasks[t].n, level, outs[t - wave])) bad = true;
+            }
+        };
+        std::vector<std::thread> th;
+        for (int t = 1; t < nt && (size_t)t < w1 - wave; ++t) th.emplace_back(work);
+        work();
+        for (auto &t : th) t.join();
+        ok = !bad;
+        for (auto &o : outs) ok = ok && fwrite(o.data(), 1, o.size(), fp) == o.size();
+    }
+    static const uint8_t EOF_BLOCK[28] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0, 0x1b, 0, 0x03, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    ok = ok && fwrite(EOF_BLOCK, 1, 28, fp) == 28;
+    ok = (fclose(fp) == 0) && ok;
+    if (!ok) { g_bam_err = std::string("writing ") + path + " failed"; return CORAL_ERR_FORMAT; }
     return CORAL_OK;
 }

@@ -258,10 +258,20 @@ inline bool keep_record_at(const uint8_t *r, const KeepRule &K) {
 //   reversed and complemented - the complement of a 4-bit code is its bit reversal, so = and N stay - and QUAL reversed.
 //   Nothing is appended to the name; records come in file order.  Bytes only: identical on either pipeline, for any batch size,
 //   and texts of byte ranges concatenate.
+// want_reads = 2 (READS_AS_RECORDS) selects by the same rule without the l_seq condition - a record without SEQ is still a record -
+// and writes, instead of text, the record's own bytes: its block_size word and the block_size bytes behind it, as they stand in the
+// inflated stream (reads_record_bytes; a CIGAR kept in a CG:B,I tag stays there).  The GPU pipeline copies them in work items of
+// READS_COPY_SLICE bytes.
 #define READS_SEQ_CHARS "=ACMGRSVTWYHKDBN"
 const int64_t READS_SLICE = 16384;          // bases per work item of the GPU pipeline (as COV_SLICE and QC_SLICE)
 
-CORAL_QC_HD inline bool reads_takes_part(uint32_t flag, uint32_t l_seq, uint32_t exclude_flags) { return l_seq > 0 && (flag & exclude_flags) == 0; }
+const int READS_AS_FASTQ = 1, READS_AS_RECORDS = 2;      // the values of want_reads
+const int64_t READS_COPY_SLICE = 32768;     // record bytes per work item of the GPU pipeline in mode 2 (what a FASTQ item writes)
+
+CORAL_QC_HD inline bool reads_takes_part(uint32_t flag, uint32_t l_seq, uint32_t exclude_flags, int mode = READS_AS_FASTQ) {
+    return (mode == READS_AS_RECORDS || l_seq > 0) && (flag & exclude_flags) == 0;
+}
+CORAL_QC_HD inline long long reads_record_bytes(uint32_t block_size) { return 4ll + block_size; }
 CORAL_QC_HD inline uint32_t reads_complement(uint32_t code) {      // A <-> T, C <-> G, M <-> K, ...: the four bits reversed
     return ((code & 1u) << 3) | ((code & 2u) << 1) | ((code & 4u) >> 1) | ((code & 8u) >> 3);
 }
@@ -308,6 +318,7 @@ CORAL_QC_HD inline bool reads_name_listed(const uint8_t *blob, const int64_t *of
 
 struct ReadsRule {                          // the request, checked and copied (parse_request)
     bool on = false;
+    int mode = READS_AS_FASTQ;              // READS_AS_FASTQ: the text; READS_AS_RECORDS: the records' own bytes
     uint32_t exclude_flags = 0;
     std::vector<int32_t> tid, lo, hi;       // no segment: no region limit
     std::vector<uint8_t> names;             // no name: no name limit
@@ -317,7 +328,7 @@ struct ReadsRule {                          // the request, checked and copied (
     bool written(const uint8_t *r, int32_t end) const {
         uint16_t flag; uint32_t l_seq; int32_t t, pos;
         memcpy(&t, r + 4, 4); memcpy(&pos, r + 8, 4); memcpy(&flag, r + 18, 2); memcpy(&l_seq, r + 20, 4);
-        if (!reads_takes_part(flag, l_seq, exclude_flags)) return false;
+        if (!reads_takes_part(flag, l_seq, exclude_flags, mode)) return false;
         if (!tid.empty() && !reads_meets_segment(tid.data(), lo.data(), hi.data(), (int)tid.size(), t, pos, end)) return false;
         return n_names() == 0 || reads_name_listed(names.data(), name_off.data(), n_names(), r + 36, (uint32_t)r[12] - 1u);
     }
@@ -344,6 +355,15 @@ inline void reads_append_text(const uint8_t *r, std::vector<uint8_t> &out) {
     const bool has_qual = qual[0] != 0xff;
     for (uint32_t j = 0; j < l_seq; ++j) *w++ = has_qual ? reads_qual_char(qual[reverse ? l_seq - 1 - j : j]) : (uint8_t)'"';
     *w++ = '\n';
+}
+
+// the bytes of one record as they stand (r points at block_size), appended to `out`: what want_reads = 2 writes
+inline void reads_append_record(const uint8_t *r, std::vector<uint8_t> &out) {
+    uint32_t block_size;
+    memcpy(&block_size, r, 4);
+    const size_t at = out.size(), n = (size_t)reads_record_bytes(block_size);
+    out.resize(at + n);
+    memcpy(out.data() + at, r, n);
 }
 
 // A span of virtual offsets [beg, end) (span_beg / span_end of a coral_bam_request_t): the records that START in it.
@@ -374,7 +394,7 @@ struct Decoded {
     bool has_pileup = false;                // a pileup request (per_base of a coral_bam_request_t; it may hold no position)
     std::vector<uint32_t> pileup;           // its table [positions in segment order][A, C, G, T] (coral_bam_pileup_result)
     bool has_reads = false;                 // a reads request (it may have written no record)
-    std::vector<uint8_t> reads_text;        // its FASTQ text, the written records in file order (coral_bam_reads_fill)
+    std::vector<uint8_t> reads_text;        // its FASTQ text (want_reads = 2: the records' bytes), the written records in file order (coral_bam_reads_fill)
     std::vector<int64_t> reads_off{0};      // where every written record starts in it, n + 1 entries
 };
 
@@ -388,7 +408,7 @@ struct Partial {   // what stage 3 produces for one chunk
     std::vector<char> names;                // NUL-separated
     std::vector<int64_t> cov;               // window-coverage counts of the chunk's records (per segment; empty without a request)
     std::vector<int64_t> qc_sum, qc_hist;   // read-QC request: qual_sum per record, the chunk's 256-bin histogram (empty without a request)
-    std::vector<uint8_t> reads_text;        // reads request: the text of the chunk's written records and its length per written record
+    std::vector<uint8_t> reads_text;        // reads request: the text (or bytes) of the chunk's written records and its length per written record
     std::vector<int64_t> reads_len;
     std::string error;
 };
@@ -491,7 +511,7 @@ inline bool parse_request(const coral_bam_request_t *q, Request &R, std::string 
     }
     if (q->want_reads != 0) {
         ReadsRule &W = R.reads;
-        if (q->want_reads != 1) { err = "reads request: want_reads must be 0 or 1"; return false; }
+        if (q->want_reads != READS_AS_FASTQ && q->want_reads != READS_AS_RECORDS) { err = "reads request: want_reads must be 0, 1 or 2"; return false; }
         if (R.want_index) { err = "request: want_reads does not go with want_index (an index request decodes every record of the file, a reads request a selection)"; return false; }
         if (q->reads_exclude_flags < 0 || q->reads_exclude_flags > 0xffff) { err = "reads request: reads_exclude_flags must be 0..0xffff"; return false; }
         if (q->reads_n_seg < 0 || (q->reads_n_seg > 0 && (!q->reads_seg_tid || !q->reads_seg_start || !q->reads_seg_end))) { err = "reads request: bad reads_seg arrays"; return false; }
@@ -512,6 +532,7 @@ inline bool parse_request(const coral_bam_request_t *q, Request &R, std::string 
             }
         }
         W.on = true;
+        W.mode = q->want_reads;
         W.exclude_flags = (uint32_t)q->reads_exclude_flags;
         if (q->reads_n_seg > 0) {
             W.tid.assign(q->reads_seg_tid, q->reads_seg_tid + q->reads_n_seg);

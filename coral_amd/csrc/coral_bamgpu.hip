@@ -30,6 +30,7 @@
 //   k_bam_depth     binned depth: per record one walk of its CIGAR, one 64-bit atomic per run of lanes in the same bin
 //   k_bam_reads_plan + k_bam_reads_emit   reads: the selected records as FASTQ text (nibbles -> ASCII, reverse strand mirrored
 //                   and complemented), scattered to scanned offsets of a per-batch buffer the host collects one batch later
+//   k_bam_reads_copy   reads, want_reads = 2: the selected records' own bytes, gathered to the same scanned offsets
 // Host: one struct per request (carve / start / batch / finish); what it may borrow of the parse's scratch: struct Borrowed.
 // Batches (64 MiB first, doubling up to 2.52 GiB inflated, coral_bamgpu_open) are double-buffered: while batch k is parsed, batch k + 1 is inflated
 // and k + 2 is read.
@@ -1279,12 +1280,14 @@ struct ReadsDev {                        // the request's device arrays, carved 
     int n_seg;
     long long n_names;
     uint32_t exclude_flags;
+    int mode;                            // READS_AS_FASTQ or READS_AS_RECORDS
 };
 
 // One thread per record (one-wave workgroups: they run beside the inflate launch): the rule, from the fixed
 // fields k_bam_meta left, the end position k_bam_emit left and the name behind the record's fixed fields.  out_len[i] = bytes of
 // the record's text, n_items[i] = its work items of READS_SLICE bases; both 0 when the record is not written, and in slot n_rec
-// (the scans' extra entry).
+// (the scans' extra entry).  In mode READS_AS_RECORDS a record without SEQ takes part too, out_len[i] is the record's own size,
+// 4 + block_size, and its work items are slices of READS_COPY_SLICE of those bytes.
 __global__ __launch_bounds__(WAVE) void k_bam_reads_plan(const uint8_t *__restrict__ buf, const long long *__restrict__ rec_start, long long n_rec,
                                                          MetaArrays M, const int32_t *__restrict__ end_in, ReadsDev X,
                                                          long long *__restrict__ out_len, long long *__restrict__ n_items) {
@@ -1295,10 +1298,13 @@ __global__ __launch_bounds__(WAVE) void k_bam_reads_plan(const uint8_t *__restri
         const uint32_t l_seq = (uint32_t)M.l_seq[i];
         const uint8_t *r = buf + rec_start[i];
         const uint32_t l_read_name = r[12];
-        bool w = l_read_name > 0 && reads_takes_part((uint32_t)M.flag[i], l_seq, X.exclude_flags);
+        bool w = l_read_name > 0 && reads_takes_part((uint32_t)M.flag[i], l_seq, X.exclude_flags, X.mode);
         if (w && X.n_seg > 0) w = reads_meets_segment(X.tid, X.lo, X.hi, X.n_seg, M.tid[i], M.pos[i], end_in[i]);
         if (w && X.n_names > 0) w = reads_name_listed(X.names, X.name_off, X.n_names, r + 36, l_read_name - 1u);
-        if (w) {
+        if (w && X.mode == READS_AS_RECORDS) {
+            bytes = reads_record_bytes(ld32(r));
+            items = (bytes + READS_COPY_SLICE - 1) / READS_COPY_SLICE;
+        } else if (w) {
             bytes = reads_text_bytes(l_seq, l_read_name);
             items = ((long long)l_seq + READS_SLICE - 1) / READS_SLICE;
         }
@@ -1419,6 +1425,25 @@ __global__ __launch_bounds__(WAVE) void k_bam_reads_emit(const uint8_t *__restri
             if (rev) v = reads_mirror(v);
             return make_uint4(reads_qual_word(v.x), reads_qual_word(v.y), reads_qual_word(v.z), reads_qual_word(v.w));
         });
+    }
+}
+
+// One wave per work item (one-wave workgroups, grid-stride, no LDS), mode READS_AS_RECORDS: the bytes [k * READS_COPY_SLICE,
+// (k + 1) * READS_COPY_SLICE) of a written record - block_size word first - go from buf + rec_start[i] to out + out_off[i] as
+// they stand.  Source and destination have byte alignments of their own: a lane takes an aligned 16-byte chunk of the OUTPUT,
+// filled from the two aligned source chunks that cover it (reads_window) and stored as one uint4; the item's first and last
+// chunk, which it may share with the neighbouring item or record, are stored byte by byte, only the item's own bytes
+// (reads_run).  Every output byte has exactly one writer (the items split the record, the records split the output): no atomics.
+__global__ __launch_bounds__(WAVE) void k_bam_reads_copy(const uint8_t *__restrict__ buf, long long buf_bytes, const long long *__restrict__ rec_start,
+                                                         long long n_rec, const long long *__restrict__ item_off,
+                                                         const long long *__restrict__ out_off, uint8_t *__restrict__ out) {
+    const int lane = threadIdx.x;
+    const long long total = item_off[n_rec];
+    for (long long w = blockIdx.x; w < total; w += gridDim.x) {
+        const long long i = item_record(item_off, n_rec, w);
+        const long long rs = rec_start[i], at = out_off[i], bytes = out_off[i + 1] - at;
+        const long long a = (w - item_off[i]) * READS_COPY_SLICE, b = min(bytes, a + READS_COPY_SLICE);
+        reads_run(out, at, a, b, lane, [&](long long j0) { return reads_window(buf, rs + j0, buf_bytes); });
     }
 }
 
@@ -1848,7 +1873,7 @@ struct DepthRequest {                // binned depth: bin_off, the contig length
     }
 };
 
-struct ReadsRequest {                // FASTQ text of the selected records
+struct ReadsRequest {                // FASTQ text, or the own bytes (R->mode), of the selected records
     bool active = false;
     const ReadsRule *R = nullptr;    // the request (Request::reads)
     ReadsDev X{};
@@ -1858,7 +1883,8 @@ struct ReadsRequest {                // FASTQ text of the selected records
     // The output buffer is sized by a bound, not by a count: a record of l bases and a name field of n bytes (NUL included) takes
     // at least 36 + n + 1.5 l bytes of the batch (block_size, the fixed fields, the name, SEQ, QUAL) and its text 2 l + n + 5, and
     // 2 l + n + 5 <= 4/3 (36 + n + 1.5 l) = 48 + 4/3 n + 2 l.  So the text of all records of a batch fits 4/3 of the batch's bytes,
-    // the carried ones included (+ 256: the division's remainder and room to spare).
+    // the carried ones included (+ 256: the division's remainder and room to spare).  In mode READS_AS_RECORDS the written bytes
+    // are a part of the batch's own: one batch's capacity + 256.
     void carve(Carver &take, size_t batch_cap) {
         if (!active) return;
         buf_bytes = up256(batch_cap + COMP_SLACK);                 // (what d_infl[slot] really has: reads_window's guard)
@@ -1866,8 +1892,8 @@ struct ReadsRequest {                // FASTQ text of the selected records
         int32_t *seg = (int32_t *)take(3 * n_seg * 4);
         uint8_t *names = (uint8_t *)take(R->names.size());
         int64_t *off = (int64_t *)take((n_names + 1) * 8);
-        X = ReadsDev{seg, seg + n_seg, seg + 2 * n_seg, names, off, (int)n_seg, (long long)n_names, R->exclude_flags};
-        text_cap = batch_cap / 3 * 4 + 256;
+        X = ReadsDev{seg, seg + n_seg, seg + 2 * n_seg, names, off, (int)n_seg, (long long)n_names, R->exclude_flags, R->mode};
+        text_cap = (R->mode == READS_AS_RECORDS ? batch_cap : batch_cap / 3 * 4) + 256;
         text = (uint8_t *)take(text_cap);
     }
     const char *start(hipError_t &e) const {
@@ -2080,8 +2106,11 @@ bool ReadsRequest::batch(GpuDecoder *G, hipStream_t stream, const Borrowed &S, s
     for (long long i = 0; i < n; ++i)
         if (off[(size_t)i + 1] > off[(size_t)i]) G->D.reads_off.push_back(base + off[(size_t)i + 1]);
     // one wave per workgroup, grid-stride beyond 8 per CU
-    hipLaunchKernelGGL(k_bam_reads_emit, dim3((unsigned)std::min<long long>(items, 2048)), dim3(WAVE), 0, stream, buf, (long long)buf_bytes, G->d_rec_start, n,
-                       G->M, S.item_off, S.out_off, text);
+    const dim3 grid((unsigned)std::min<long long>(items, 2048));
+    if (X.mode == READS_AS_RECORDS)
+        hipLaunchKernelGGL(k_bam_reads_copy, grid, dim3(WAVE), 0, stream, buf, (long long)buf_bytes, G->d_rec_start, n, S.item_off, S.out_off, text);
+    else
+        hipLaunchKernelGGL(k_bam_reads_emit, grid, dim3(WAVE), 0, stream, buf, (long long)buf_bytes, G->d_rec_start, n, G->M, S.item_off, S.out_off, text);
     if (!launched("reads", err)) return false;
     pending_bytes = bytes;
     return true;

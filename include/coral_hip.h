@@ -391,8 +391,8 @@ const char *coral_bam_last_error(void);
  * depth_min_mapq 0..255, depth_exclude_flags 0..0xffff, depth_count_deletions 0 or 1, no span decode, at most 2^28 bins over
  * the header's contigs (checked once the header is read: refused before anything is decoded or allocated); keep_min_mapq
  * 0..255, keep_min_seq_length 0..2^29, keep_require_flags and keep_exclude_flags 0..0xffff, and no active record filter together
- * with want_index; want_reads 0 or 1, and with want_reads = 1: reads_exclude_flags 0..0xffff, reads_seg under the rules of the
- * coverage segments, reads_names of 1..254 bytes each, strictly ascending, and no want_index.  A span decode is not sharded:
+ * with want_index; want_reads 0, 1 or 2, and with want_reads = 1 or 2: reads_exclude_flags 0..0xffff, reads_seg under the rules of
+ * the coverage segments, reads_names of 1..254 bytes each, strictly ascending, and no want_index.  A span decode is not sharded:
  * rank and world are taken as 0 and 1. */
 typedef struct {
     int32_t rank, world;                       /* byte range (ignored when n_spans >= 0) */
@@ -406,7 +406,7 @@ typedef struct {
     int32_t depth_bin;                         /* 0: no binned-depth request; >= 1: the bin size */
     int32_t depth_min_mapq, depth_exclude_flags, depth_count_deletions;
     /* the reads request: want_reads 0 = none */
-    int32_t want_reads;                        /* 1: the selected records as FASTQ text (coral_bam_reads_sizes / _fill) */
+    int32_t want_reads;                        /* 1: the selected records as FASTQ text, 2: as their own bytes (coral_bam_reads_sizes / _fill) */
     int32_t reads_exclude_flags;               /* 0..0xffff  written only when (flag & it) == 0 */
     int32_t reads_n_seg;                       /* 0: no region limit; else sorted, disjoint segments, the coverage segments' rules */
     const int32_t *reads_seg_tid, *reads_seg_start, *reads_seg_end;
@@ -514,7 +514,20 @@ typedef struct {
  * and QUAL reversed, so the read has the orientation it was sequenced in.  Nothing is appended to the name; records come in
  * file order.  Allowed on byte ranges (the texts of consecutive ranges concatenate) and on span decodes, not with want_index.
  *   reads_sizes -> records written, text bytes; reads_fill copies the text and the n + 1 int64 offsets of the records in it.
- *   The whole result lives in host memory: meant for the reads of an amplicon, not for a whole 2 M-read file. */
+ *   The whole result lives in host memory: meant for the reads of an amplicon, not for a whole 2 M-read file.
+ *
+ * Records (want_reads = 2) - the same selection with the alignments kept: what `samtools view -b x.bam region... > amp.bam`
+ * gets from a second pass, for a genome browser or any tool that reads BAM.  reads_exclude_flags, reads_seg_*, reads_names /
+ * reads_name_off and the keep_* filter mean what they mean for want_reads = 1, with the same validation.  A record is WRITTEN
+ * when (flag & reads_exclude_flags) == 0, with segments: tid >= 0 and [pos, bam_endpos) - [pos, pos + 1) with flag 0x4 - meets
+ * a non-empty segment, with names: its name is listed.  Unlike FASTQ, l_seq > 0 is NOT required: a record without SEQ is still
+ * a record.  An active record filter acts first.  The output is 4 + block_size bytes per written record - its block_size word
+ * and the block_size bytes behind it, byte for byte the source's inflated stream (a CIGAR carried in a CG:B,I tag is copied as
+ * it is) - one record after the other in file order.  Allowed on byte ranges (the outputs of consecutive ranges concatenate)
+ * and on span decodes, not with want_index.
+ *   reads_sizes -> records written, total bytes; reads_fill copies the bytes and the n + 1 int64 offsets of the records.
+ *   The whole result lives in host memory: meant for the records of an amplicon, not for a whole 2 M-read file; nothing is
+ *   streamed to disk.  coral_bgzf_write puts a header and such bytes into a BGZF / BAM file. */
 int coral_bam_decode_request(const char *path, int32_t n_threads, const coral_bam_request_t *req, void **handle);
 int coral_bam_coverage_result(void *handle, int32_t n_seg, int64_t *counts);
 int coral_bam_pileup_result(void *handle, int64_t n_pos, uint32_t *counts);
@@ -528,6 +541,13 @@ int coral_bam_depth_sizes(void *handle, int64_t sizes[2]);
 int coral_bam_depth_fill(void *handle, int64_t *bin_off, int64_t *bases, int64_t *reads);
 int coral_bam_reads_sizes(void *handle, int64_t sizes[2]);
 int coral_bam_reads_fill(void *handle, uint8_t *text, int64_t *rec_off);
+/* n_parts byte strings (for a BAM file: the inflated header, then record bytes) -> one BGZF file at `path`.  Each part is deflated
+ * into blocks of at most 0xff00 input bytes and starts a new block (the header ends a block, as htslib's does, so the first
+ * record's virtual offset has a zero low half); an empty part makes no block; level 0..9; the blocks are shared out over
+ * n_threads (< 1: one) and the bytes do not depend on it; the 28-byte EOF block goes last.  CORAL_ERR_ARG: level outside 0..9,
+ * n_parts < 0, a missing array or part, a path that cannot be created; CORAL_ERR_FORMAT: the write failed. */
+int coral_bgzf_write(const char *path, const uint8_t *const *parts, const int64_t *part_bytes, int32_t n_parts, int32_t level,
+                     int32_t n_threads);
 
 /* ------------------------------------------------------------------------------------------------
  * coral_bamgpu_* — the same decode with the inflate and the record parsing ON THE GPU: the host reads the file and sends
@@ -583,7 +603,11 @@ int coral_bam_reads_fill(void *handle, uint8_t *text, int64_t *rec_off);
  *                      bytes that cover them, mirrored for flag 0x10; aligned 16-byte stores inside an item, bytes at its two
  *                      edges; no atomics) write the batch's text into a buffer of the workspace (4/3 of a batch + 256 bytes),
  *                      which is copied to the host once the next batch's emit has synchronised the stream; the segments and the
- *                      name list live in the workspace too.  The totals come back on their own (16 bytes per batch)
+ *                      name list live in the workspace too.  The totals come back on their own (16 bytes per batch).
+ *                      want_reads = 2: the plan gives 4 + block_size per written record and work items of 32 768 record bytes,
+ *                      and k_bam_reads_copy takes k_bam_reads_emit's place (same launch shape: a lane stores one aligned
+ *                      16-byte chunk of the output, filled from the two aligned source chunks that cover it; bytes at an
+ *                      item's two edges; no LDS, no atomics); the buffer is one batch + 256 bytes
  *   finish        after the last batch (CORAL_ERR_ARG before): waits for `stream` once and leaves what was requested in the
  *          handle of `host` (coral_bam_coverage_result, coral_bam_pileup_result - the table is copied and summed per segment
  *          here -, coral_bam_index_sizes / _fill, coral_bam_qc_sizes / _fill, coral_bam_depth_sizes / _fill, coral_bam_reads_sizes / _fill); fails when
