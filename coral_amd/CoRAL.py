@@ -7,8 +7,9 @@
 The `reconstruct` mode and the `hsr` mode (§8(f) item 3) run on the MI355X path, and so do `index`, `qc`
 (the reference's scripts/report_nanopore_qc.py, from one decode of the aligned BAM), `pileup` (the bases per position of
 regions, pysam's count_coverage as a table) and `depth` (read depth per fixed-size bin of every contig, the table a copy-number
-caller starts from), `fastq` (selected reads as FASTQ, by regions or read names) and `view` (the same selection as a BAM file of
-the records themselves, with its index on request); the other modes of the
+caller starts from), `fastq` (selected reads as FASTQ, by regions or read names), `view` (the same selection as a BAM file of
+the records themselves, with its index on request) and `sort` (the kept records in coordinate order as a BAM file, with its
+index on request: lines 42-50 of the reference's scripts/align_nanopore_reads.sh from one decode); the other modes of the
 reference (seed, plot, cycle2bed) are untouched and are delegated to the reference's own modules when they are
 importable (set CORAL_REFERENCE_SRC to the reference's src/ directory).  The cycle-decomposition step after the graph build is the
 reference's (Gurobi); it runs on the object this module returns.
@@ -124,7 +125,15 @@ def build_parser():
     vp.add_argument("--index", help="If specified, also write the BAI index (<output>.bai).", action='store_true')
     vp.add_argument("--output", help="Name of the BAM file.", required=True)
     vp.add_argument("--device", help="GPU to use ('cpu': the host pipeline).", default="cuda:0")
-    for p in (rp, hp, qp, pp, dp, fp, vp):
+    sp = sub.add_parser("sort", help="Write the records of a (long read) bam file in coordinate order as a BAM file, from one decode of it.")
+    sp.add_argument("--lr_bam", help="(Long read) bam file, in any order.", required=True)
+    sp.add_argument("--reads_exclude_flags", help="Leave out records with any of these flag bits (default: none).",
+                    type=lambda x: int(x, 0), default=0)
+    sp.add_argument("--level", help="Compression level of the BAM file, 0..9.", type=int, default=1)
+    sp.add_argument("--index", help="If specified, also write the BAI index (<output>.bai).", action='store_true')
+    sp.add_argument("--output", help="Name of the sorted BAM file.", required=True)
+    sp.add_argument("--device", help="GPU to use ('cpu': the host pipeline).", default="cuda:0")
+    for p in (rp, hp, qp, pp, dp, fp, vp, sp):
         add_filter_arguments(p)
     for mode in ("seed", "plot", "cycle2bed"):
         sub.add_parser(mode, help="(reference implementation; not part of the MI355X path)", add_help=False)
@@ -266,6 +275,16 @@ def view_mode(args):
     return args.output
 
 
+def sort_mode(args):
+    """The records in coordinate order as a BAM file (bam.sort_bam): `samtools view -bq ... | samtools sort | samtools index`,
+    with the --filter_* arguments as the view's tests."""
+    from coral_amd import bam
+    out = bam.sort_bam(args.lr_bam, args.output, index=args.index, level=args.level, record_filter=record_filter_of(args),
+                       exclude_flags=args.reads_exclude_flags, device=args.device)
+    print("Wrote %s" % out)
+    return out
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     if argv and argv[0] in ("seed", "plot", "cycle2bed"):
@@ -301,6 +320,8 @@ def main(argv=None):
         return fastq_mode(args)
     if args.mode == "view":
         return view_mode(args)
+    if args.mode == "sort":
+        return sort_mode(args)
     parser.print_help()
     return None
 

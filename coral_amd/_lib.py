@@ -38,10 +38,13 @@ def bam_request(rank: int = 0, world: int = 1, spans=None, coverage=None, index:
     [3][S], quality threshold, read_callback code) or None, ``per_base``: the coverage as the table per position and base (the
     pileup), ``depth`` = (bin size, min_mapq, exclude_flags, count_deletions) or None: the binned-depth request, ``keep`` = (min_mapq, min_seq_length, require_flags, exclude_flags) (a
     ``bam.RecordFilter`` is one) or None: the record filter, ``reads`` = (exclude_flags, segments int32 [3][S] or None, names = a list
-    of bytes or None[, mode]) or None: the reads request (no segment / no name: no such limit; mode 1, the default: FASTQ text,
-    2: the records' own bytes).  The struct keeps the contiguous arrays it points into alive; the rules are the library's to check."""
+    of bytes or None[, mode[, order]]) or None: the reads request (no segment / no name: no such limit; mode 1, the default: FASTQ
+    text, 2: the records' own bytes; order 0, the default: file order, 1: coordinate order - not a field of the struct but the
+    ``reads_order`` argument of the _ordered entry points, kept as the attribute ``reads_order``).  The struct keeps the contiguous
+    arrays it points into alive; the rules are the library's to check."""
     req = coral_bam_request_t(rank=rank, world=world, n_spans=-1, n_seg=-1, want_index=int(index), want_qc=int(qc), per_base=int(per_base))
     req.arrays = []
+    req.reads_order = int(reads[4]) if reads is not None and len(reads) > 4 else 0
     if depth is not None:
         req.depth_bin, req.depth_min_mapq, req.depth_exclude_flags, req.depth_count_deletions = (int(v) for v in depth)
     if keep is not None:
@@ -164,6 +167,9 @@ def lib():
     L.coral_bgzf_write.argtypes = [C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int32, C.c_int32, C.c_int32]
     L.coral_bamgpu_open_request.argtypes = [C.c_char_p, C.c_int32, C.c_int64, Q, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
     L.coral_bamgpu_finish.argtypes = [C.c_void_p, P]
+    L.coral_bam_decode_request_ordered.argtypes = [C.c_char_p, C.c_int32, Q, C.c_int32, C.POINTER(C.c_void_p)]
+    L.coral_bamgpu_open_request_ordered.argtypes = [C.c_char_p, C.c_int32, C.c_int64, Q, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
+    L.coral_bam_records_merge.argtypes = [C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64), P, P, C.c_int32]
     with open(os.path.join(os.path.dirname(_HERE), "include", "coral_hip.h")) as fp:
         for name in re.findall(r"^int (coral_\w+)\(", fp.read(), re.M):      # every prototype of the header that returns int
             getattr(L, name).restype = C.c_int

@@ -241,7 +241,10 @@ def _decode(path: str, device, *, n_threads: Optional[int] = None, rank: int = 0
     if n_threads is None:
         n_threads = default_threads()
     h = C.c_void_p()
-    rc = L.coral_bam_decode_request(path.encode(), n_threads, C.byref(req), C.byref(h))
+    if req.reads_order:
+        rc = L.coral_bam_decode_request_ordered(path.encode(), n_threads, C.byref(req), req.reads_order, C.byref(h))
+    else:
+        rc = L.coral_bam_decode_request(path.encode(), n_threads, C.byref(req), C.byref(h))
     if rc != 0:
         raise _lib.CoralHipError("coral_bam_decode_request(%s) failed (%d): %s" % (path, rc, L.coral_bam_last_error().decode()))
     try:
@@ -303,7 +306,10 @@ def _decode_gpu(path: str, device, n_threads: Optional[int], batch_bytes: int, r
         n_threads = default_threads()
     fail = lambda what, rc: _lib.CoralHipError("%s(%s) failed (%d): %s" % (what, path, rc, L.coral_bam_last_error().decode()))
     h, ws_bytes = C.c_void_p(), C.c_int64(0)
-    rc = L.coral_bamgpu_open_request(path.encode(), n_threads, batch_bytes, C.byref(req), C.byref(h), C.byref(ws_bytes))
+    if req.reads_order:
+        rc = L.coral_bamgpu_open_request_ordered(path.encode(), n_threads, batch_bytes, C.byref(req), req.reads_order, C.byref(h), C.byref(ws_bytes))
+    else:
+        rc = L.coral_bamgpu_open_request(path.encode(), n_threads, batch_bytes, C.byref(req), C.byref(h), C.byref(ws_bytes))
     if rc != 0:
         raise fail("coral_bamgpu_open_request", rc)
     try:
@@ -912,10 +918,10 @@ def extract_reads(path: str, regions=None, names=None, exclude_flags: int = 0x90
     return Reads(*got) if got is not None else Reads()
 
 
-def _selected(mode: int, path, regions, names, exclude_flags, device, n_threads, rank, world, batch_bytes, index, record_filter):
+def _selected(mode: int, path, regions, names, exclude_flags, device, n_threads, rank, world, batch_bytes, index, record_filter, order: int = 0):
     """What ``extract_reads`` (mode 1) and ``extract_records`` (mode 2) share: the argument rules, the index use and the decode ->
     (bytes uint8, offsets int64 [n + 1]) of the reads request, or None for a selection that is empty before any record is decoded
-    (an empty list: the file is not opened)."""
+    (an empty list: the file is not opened).  ``order`` 1 (mode 2 only): the records in coordinate order."""
     if isinstance(exclude_flags, bool) or not isinstance(exclude_flags, numbers.Integral) or not 0 <= exclude_flags <= 0xffff:
         raise ValueError("exclude_flags must be an integer in 0..0xffff, got %r" % (exclude_flags,))
     if names is not None:
@@ -929,7 +935,7 @@ def _selected(mode: int, path, regions, names, exclude_flags, device, n_threads,
         n_threads = default_threads()
     if regions is None:
         res = _decode(path, device, n_threads=n_threads, rank=rank, world=world, batch_bytes=batch_bytes, records=False,
-                      record_filter=record_filter, reads=(exclude_flags, None, names, mode))
+                      record_filter=record_filter, reads=(exclude_flags, None, names, mode, order))
         return res.reads
     ref_names = bam_reference_names(path)
     _, segs = pileup_regions(list(regions), ref_names)
@@ -956,7 +962,7 @@ def _selected(mode: int, path, regions, names, exclude_flags, device, n_threads,
         out = None
     else:
         res = _decode(path, device, n_threads=n_threads, rank=rank, world=world, batch_bytes=batch_bytes, spans=spans, records=False,
-                      record_filter=record_filter, reads=(exclude_flags, segs, names, mode))
+                      record_filter=record_filter, reads=(exclude_flags, segs, names, mode, order))
         out = res.reads
     if idx is not None:
         LAST_DECODE.update(index=idx.path or "<object>", spans=int(len(spans)))
@@ -989,13 +995,45 @@ def bam_header_bytes(path: str) -> bytes:
         return b"".join(out)
 
 
+_RECORD_ORDERS = {"file": 0, "coordinate": 1}
+
+
+def sorted_header_bytes(header: bytes) -> bytes:
+    """The inflated BAM header ``header`` (``bam_header_bytes``) saying that the records are in coordinate order: the ``SO:``
+    value of the text's ``@HD`` line becomes ``coordinate``, an ``@HD`` line without ``SO:`` gets ``\tSO:coordinate`` appended, a
+    text without ``@HD`` (an empty one too) gets ``@HD\tVN:1.6\tSO:coordinate\n`` in front; ``l_text`` follows, and everything
+    behind the text (the contigs) stays byte for byte."""
+    header = bytes(header)
+    if len(header) < 8 or header[:4] != b"BAM\x01":
+        raise ValueError("sorted_header_bytes: not the inflated header of a BAM file")
+    l_text = struct.unpack_from("<i", header, 4)[0]
+    if l_text < 0 or 8 + l_text > len(header):
+        raise ValueError("sorted_header_bytes: l_text reaches behind the header")
+    text, rest = header[8:8 + l_text], header[8 + l_text:]
+    if text[:3] == b"@HD" and text[3:4] in (b"\t", b"\n", b""):
+        end = text.find(b"\n") if b"\n" in text else len(text)
+        fields = text[:end].split(b"\t")
+        if any(f.startswith(b"SO:") for f in fields[1:]):
+            fields = fields[:1] + [b"SO:coordinate" if f.startswith(b"SO:") else f for f in fields[1:]]
+        else:
+            fields.append(b"SO:coordinate")
+        text = b"\t".join(fields) + text[end:]
+    else:
+        text = b"@HD\tVN:1.6\tSO:coordinate\n" + text
+    return header[:4] + struct.pack("<i", len(text)) + text + rest
+
+
 class RecordBytes:
     """The records one decode selected (``extract_records``) as they stand in the source's inflated stream: ``data`` uint8, per
-    record its block_size word and the block_size bytes behind it, in file order; ``offsets`` int64 [n + 1] where each starts;
-    ``n`` their number; ``header`` the source's inflated bytes in front of its first record (None where the file was never opened:
-    an empty ``regions`` or ``names`` list)."""
+    record its block_size word and the block_size bytes behind it, in file order - or, with ``order`` "coordinate", sorted;
+    ``offsets`` int64 [n + 1] where each starts; ``n`` their number; ``header`` the source's inflated bytes in front of its first
+    record (None where the file was never opened: an empty ``regions`` or ``names`` list), for coordinate order rewritten by
+    ``sorted_header_bytes``; ``order`` "file" or "coordinate"."""
 
-    def __init__(self, data=None, offsets=None, header: Optional[bytes] = None):
+    def __init__(self, data=None, offsets=None, header: Optional[bytes] = None, order: str = "file"):
+        if order not in _RECORD_ORDERS:
+            raise ValueError("order must be 'file' or 'coordinate', got %r" % (order,))
+        self.order = order
         self.data = np.ascontiguousarray(data if data is not None else np.zeros(0, dtype=np.uint8), dtype=np.uint8)
         self.offsets = np.ascontiguousarray(offsets if offsets is not None else np.zeros(1, dtype=np.int64), dtype=np.int64)
         if len(self.offsets) < 1 or int(self.offsets[0]) != 0 or int(self.offsets[-1]) != len(self.data):
@@ -1039,13 +1077,42 @@ def merge_record_bytes(parts: Sequence[RecordBytes]) -> RecordBytes:
         raise ValueError("merge_record_bytes needs at least one part")
     if any(p.header != parts[0].header for p in parts[1:]):
         raise ValueError("merge_record_bytes: the parts have different headers")
+    if any(p.order != parts[0].order for p in parts[1:]):
+        raise ValueError("merge_record_bytes: the parts have different orders")
+    if parts[0].order != "file" and len(parts) > 1:
+        raise ValueError("merge_record_bytes: sorted parts do not concatenate to a sorted whole (merge_sorted_record_bytes)")
     base = np.concatenate([[0], np.cumsum([len(p.data) for p in parts])]).astype(np.int64)
     return RecordBytes(np.concatenate([p.data for p in parts]),
-                       np.concatenate([np.zeros(1, dtype=np.int64)] + [p.offsets[1:] + b for p, b in zip(parts, base)]), parts[0].header)
+                       np.concatenate([np.zeros(1, dtype=np.int64)] + [p.offsets[1:] + b for p, b in zip(parts, base)]), parts[0].header,
+                       parts[0].order)
+
+
+def merge_sorted_record_bytes(parts: Sequence[RecordBytes], n_threads: Optional[int] = None) -> RecordBytes:
+    """The coordinate-ordered results of consecutive byte ranges (in rank order) as one sorted whole: the native stable k-way
+    merge (coral_bam_records_merge) with the parts as runs, so records with equal keys stay in file order.  The parts are of
+    one file: their headers must be equal."""
+    parts = list(parts)
+    if not parts:
+        raise ValueError("merge_sorted_record_bytes needs at least one part")
+    if any(p.order != "coordinate" for p in parts):
+        raise ValueError("merge_sorted_record_bytes: every part must be in coordinate order")
+    if any(p.header != parts[0].header for p in parts[1:]):
+        raise ValueError("merge_sorted_record_bytes: the parts have different headers")
+    L = _lib.lib()
+    k = len(parts)
+    data = (C.c_void_p * k)(*[p.data.ctypes.data if len(p.data) else None for p in parts])
+    off = (C.c_void_p * k)(*[p.offsets.ctypes.data for p in parts])
+    n = (C.c_int64 * k)(*[p.n for p in parts])
+    out = np.zeros(sum(len(p.data) for p in parts), dtype=np.uint8)
+    out_off = np.zeros(sum(p.n for p in parts) + 1, dtype=np.int64)
+    rc = L.coral_bam_records_merge(k, data, off, n, out.ctypes.data if len(out) else None, out_off.ctypes.data, n_threads or default_threads())
+    if rc != 0:
+        raise _lib.CoralHipError("coral_bam_records_merge failed (%d): %s" % (rc, L.coral_bam_last_error().decode()))
+    return RecordBytes(out, out_off, parts[0].header, "coordinate")
 
 
 def extract_records(path: str, regions=None, names=None, exclude_flags: int = 0, device="cuda:0", n_threads: Optional[int] = None,
-                    rank: int = 0, world: int = 1, batch_bytes: int = 0, *, index=None, record_filter=None) -> RecordBytes:
+                    rank: int = 0, world: int = 1, batch_bytes: int = 0, *, index=None, record_filter=None, order: str = "file") -> RecordBytes:
     """The selected records of the BAM file as raw BAM record bytes (``RecordBytes``), copied out while it is decoded; with
     ``RecordBytes.write`` what ``samtools view -b x.bam region... > amp.bam && samtools index amp.bam`` gets from a second pass.
 
@@ -1057,12 +1124,35 @@ def extract_records(path: str, regions=None, names=None, exclude_flags: int = 0,
 
     GPU pipeline (k_bam_reads_plan / k_bam_reads_copy per batch) on a GPU ``device``, host pipeline with ``device="cpu"`` or
     ``CORAL_BAM_DECODE=cpu``; identical bytes.  ``merge_record_bytes`` joins byte ranges.  The whole result lives in host memory:
-    meant for the records of an amplicon, not for a whole 2 M-read file; nothing is streamed to disk."""
+    meant for the records of an amplicon, not for a whole 2 M-read file; nothing is streamed to disk.
+
+    ``order="coordinate"``: the written records sorted during the same decode, ascending by ``(tid, pos, reverse strand)`` with
+    ``tid = -1`` last and records of equal key in file order - what ``samtools sort`` does in a pass of its own.  On the GPU each
+    batch is sorted on the device (k_bam_sort_keys, hipcub's radix sort, k_bam_sort_permute, k_bam_reads_copy_sorted) and the
+    batches' runs are merged on the host; the host pipeline sorts what it wrote.  The result carries ``sorted_header_bytes`` of
+    the source's header; ``merge_sorted_record_bytes`` joins byte ranges.  It lives in host memory, about twice its size while
+    the runs are merged."""
+    if order not in _RECORD_ORDERS:
+        raise ValueError("order must be 'file' or 'coordinate', got %r" % (order,))
     regions, names = (None if x is None else list(x) for x in (regions, names))
-    got = _selected(2, path, regions, names, exclude_flags, device, n_threads, rank, world, batch_bytes, index, record_filter)
+    got = _selected(2, path, regions, names, exclude_flags, device, n_threads, rank, world, batch_bytes, index, record_filter,
+                    _RECORD_ORDERS[order])
     if got is None and (regions == [] or names == []):
-        return RecordBytes()                                     # (the file was not opened: no header)
-    return RecordBytes(*(got if got is not None else (None, None)), header=bam_header_bytes(path))
+        return RecordBytes(order=order)                          # (the file was not opened: no header)
+    header = bam_header_bytes(path)
+    return RecordBytes(*(got if got is not None else (None, None)), header=sorted_header_bytes(header) if order == "coordinate" else header,
+                       order=order)
+
+
+def sort_bam(path: str, output: str, *, index: bool = True, level: int = 1, record_filter=None, exclude_flags: int = 0, device="cuda:0",
+             n_threads: Optional[int] = None, batch_bytes: int = 0) -> str:
+    """``path``'s records - those that pass ``record_filter`` and ``exclude_flags`` - in coordinate order as the BAM file
+    ``output``, with its BAI index beside it (``index``): ``samtools view -b -q ... | samtools sort | samtools index`` from one
+    decode (``extract_records(order="coordinate")`` and ``RecordBytes.write``).  Returns ``output``.  The result lives in host
+    memory, about twice its size while the batches' runs are merged; runs are not spilled to disk."""
+    rec = extract_records(path, None, None, exclude_flags, device=device, n_threads=n_threads, batch_bytes=batch_bytes, index=False,
+                          record_filter=record_filter, order="coordinate")
+    return rec.write(output, level=level, index=index, n_threads=n_threads)
 
 
 # ----------------------------------------------------------------------------------------------

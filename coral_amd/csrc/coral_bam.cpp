@@ -40,6 +40,7 @@
 #include <functional>
 #include <memory>
 #include <mutex>
+#include <queue>
 #include <string>
 #include <thread>
 #include <unordered_map>
@@ -505,10 +506,36 @@ void coral_bam::set_error(const std::string &msg) { g_bam_err = msg; }
 
 extern "C" const char *coral_bam_last_error(void) { return g_bam_err.c_str(); }
 
+// The written records of a records request in coordinate order (host pipeline: the parity partner of the GPU path, not a fast
+// path): a stable sort of the records by reads_sort_key, then the bytes gathered in that order.
+static void sort_written_records(Decoded &D) {
+    const size_t n = D.reads_off.size() - 1;
+    std::vector<unsigned long long> key(n);
+    std::vector<size_t> order(n);
+    for (size_t k = 0; k < n; ++k) { key[k] = reads_sort_key_at(D.reads_text.data() + D.reads_off[k]); order[k] = k; }
+    if (std::is_sorted(key.begin(), key.end())) return;
+    std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return key[a] < key[b]; });
+    std::vector<uint8_t> text(D.reads_text.size());
+    std::vector<int64_t> off(1, 0);
+    off.reserve(n + 1);
+    for (size_t k = 0; k < n; ++k) {
+        const int64_t a = D.reads_off[order[k]], len = D.reads_off[order[k] + 1] - a;
+        memcpy(text.data() + off.back(), D.reads_text.data() + a, (size_t)len);
+        off.push_back(off.back() + len);
+    }
+    D.reads_text.swap(text);
+    D.reads_off.swap(off);
+}
+
 extern "C" int coral_bam_decode_request(const char *path, int32_t n_threads, const coral_bam_request_t *req, void **handle) {
+    return coral_bam_decode_request_ordered(path, n_threads, req, READS_ORDER_FILE, handle);
+}
+
+extern "C" int coral_bam_decode_request_ordered(const char *path, int32_t n_threads, const coral_bam_request_t *req, int32_t reads_order,
+                                                void **handle) {
     if (!path || !handle) return CORAL_ERR_ARG;
     Request R;
-    if (!parse_request(req, R, g_bam_err)) return CORAL_ERR_ARG;
+    if (!parse_request(req, R, g_bam_err) || !set_reads_order(R, reads_order, g_bam_err)) return CORAL_ERR_ARG;
     std::unique_ptr<Decoded> D(new Decoded());
     bool ok = false;
     try {
@@ -533,6 +560,7 @@ extern "C" int coral_bam_decode_request(const char *path, int32_t n_threads, con
         return D->bad_request ? CORAL_ERR_ARG : CORAL_ERR_FORMAT;
     }
     if (D->has_pileup) pileup_segment_sums(R.cov, D->pileup.data(), D->cov);
+    if (R.reads.order == READS_ORDER_COORDINATE) sort_written_records(*D);
     *handle = D.release();
     return CORAL_OK;
 }
@@ -621,6 +649,48 @@ extern "C" int coral_bam_depth_fill(void *handle, int64_t *bin_off, int64_t *bas
 
 // The reads request of a handle (either pipeline): sizes = records written, text bytes; fill = the text and the n + 1 offsets
 // (want_reads = 2: the records' own bytes in place of the text).
+// Stable k-way merge of sorted runs of raw records (include/coral_hip.h): first the order - a heap of the runs' heads by (key,
+// run), so a tie goes to the earlier run - and the output offsets, then the bytes, copied by n_threads workers that each take a
+// stretch of consecutive output records.
+extern "C" int coral_bam_records_merge(int32_t n_runs, const uint8_t *const *data, const int64_t *const *off, const int64_t *n,
+                                       uint8_t *out_data, int64_t *out_off, int32_t n_threads) {
+    if (n_runs < 0 || !out_off || (n_runs > 0 && (!data || !off || !n))) { g_bam_err = "coral_bam_records_merge: bad arguments"; return CORAL_ERR_ARG; }
+    int64_t total = 0;
+    for (int32_t r = 0; r < n_runs; ++r) {
+        if (n[r] < 0 || !off[r] || (n[r] > 0 && !data[r])) { g_bam_err = "coral_bam_records_merge: bad run"; return CORAL_ERR_ARG; }
+        for (int64_t k = 0; k < n[r]; ++k)
+            if (off[r][k] < 0 || off[r][k + 1] - off[r][k] < 20) { g_bam_err = "coral_bam_records_merge: a record is shorter than its key fields (bad offsets)"; return CORAL_ERR_ARG; }
+        total += n[r];
+    }
+    struct Head { unsigned long long key; int32_t run; };
+    auto later = [](const Head &a, const Head &b) { return a.key != b.key ? a.key > b.key : a.run > b.run; };
+    std::priority_queue<Head, std::vector<Head>, decltype(later)> heads(later);
+    std::vector<int64_t> at((size_t)n_runs, 0);
+    for (int32_t r = 0; r < n_runs; ++r)
+        if (n[r] > 0) heads.push(Head{reads_sort_key_at(data[r] + off[r][0]), r});
+    std::vector<const uint8_t *> src((size_t)total);
+    out_off[0] = 0;
+    for (int64_t j = 0; j < total; ++j) {
+        const int32_t r = heads.top().run;
+        heads.pop();
+        const int64_t k = at[(size_t)r]++;
+        src[(size_t)j] = data[r] + off[r][k];
+        out_off[j + 1] = out_off[j] + (off[r][k + 1] - off[r][k]);
+        if (k + 1 < n[r]) heads.push(Head{reads_sort_key_at(data[r] + off[r][k + 1]), r});
+    }
+    if (total > 0 && !out_data) { g_bam_err = "coral_bam_records_merge: no output buffer"; return CORAL_ERR_ARG; }
+    const int64_t nt = std::max<int64_t>(1, std::min<int64_t>({(int64_t)n_threads, (int64_t)64, total}));
+    auto copy = [&](int64_t t) {
+        for (int64_t j = total * t / nt, e = total * (t + 1) / nt; j < e; ++j)
+            memcpy(out_data + out_off[j], src[(size_t)j], (size_t)(out_off[j + 1] - out_off[j]));
+    };
+    std::vector<std::thread> workers;
+    for (int64_t t = 1; t < nt; ++t) workers.emplace_back(copy, t);
+    copy(0);
+    for (auto &w : workers) w.join();
+    return CORAL_OK;
+}
+
 extern "C" int coral_bam_reads_sizes(void *handle, int64_t sizes[2]) {
     if (!handle || !sizes) return CORAL_ERR_ARG;
     const Decoded *D = (const Decoded *)handle;

@@ -272,6 +272,14 @@ CORAL_QC_HD inline bool reads_takes_part(uint32_t flag, uint32_t l_seq, uint32_t
     return (mode == READS_AS_RECORDS || l_seq > 0) && (flag & exclude_flags) == 0;
 }
 CORAL_QC_HD inline long long reads_record_bytes(uint32_t block_size) { return 4ll + block_size; }
+// The order of a coordinate-ordered records request (reads_order = 1; want_reads = 2 only): ascending by this key, records with
+// equal keys in their input order (stable).  tid = -1 becomes 0xffffffff - records without coordinates go last -, and at an equal
+// position the forward strand comes before the reverse strand: the order `samtools sort` documents.  It refines
+// IndexPartial::sort_word, so a file written in this order can always be indexed.
+const int READS_ORDER_FILE = 0, READS_ORDER_COORDINATE = 1;      // the values of reads_order
+CORAL_QC_HD inline unsigned long long reads_sort_key(int32_t tid, int32_t pos, uint32_t flag) {
+    return ((unsigned long long)(uint32_t)tid << 32) | ((unsigned long long)((uint32_t)pos + 1u) << 1) | ((flag >> 4) & 1u);
+}
 CORAL_QC_HD inline uint32_t reads_complement(uint32_t code) {      // A <-> T, C <-> G, M <-> K, ...: the four bits reversed
     return ((code & 1u) << 3) | ((code & 2u) << 1) | ((code & 4u) >> 1) | ((code & 8u) >> 3);
 }
@@ -319,6 +327,7 @@ CORAL_QC_HD inline bool reads_name_listed(const uint8_t *blob, const int64_t *of
 struct ReadsRule {                          // the request, checked and copied (parse_request)
     bool on = false;
     int mode = READS_AS_FASTQ;              // READS_AS_FASTQ: the text; READS_AS_RECORDS: the records' own bytes
+    int order = READS_ORDER_FILE;           // READS_ORDER_COORDINATE (mode READS_AS_RECORDS only): sorted by reads_sort_key, stable
     uint32_t exclude_flags = 0;
     std::vector<int32_t> tid, lo, hi;       // no segment: no region limit
     std::vector<uint8_t> names;             // no name: no name limit
@@ -333,6 +342,13 @@ struct ReadsRule {                          // the request, checked and copied (
         return n_names() == 0 || reads_name_listed(names.data(), name_off.data(), n_names(), r + 36, (uint32_t)r[12] - 1u);
     }
 };
+
+// reads_sort_key of a record's bytes (r points at block_size): tid at +4, pos at +8, flag at +18
+inline unsigned long long reads_sort_key_at(const uint8_t *r) {
+    int32_t tid, pos; uint16_t flag;
+    memcpy(&tid, r + 4, 4); memcpy(&pos, r + 8, 4); memcpy(&flag, r + 18, 2);
+    return reads_sort_key(tid, pos, flag);
+}
 
 // the text of one record (r points at block_size; its fields have been checked to lie inside it), appended to `out`
 inline void reads_append_text(const uint8_t *r, std::vector<uint8_t> &out) {
@@ -396,6 +412,7 @@ struct Decoded {
     bool has_reads = false;                 // a reads request (it may have written no record)
     std::vector<uint8_t> reads_text;        // its FASTQ text (want_reads = 2: the records' bytes), the written records in file order (coral_bam_reads_fill)
     std::vector<int64_t> reads_off{0};      // where every written record starts in it, n + 1 entries
+    std::vector<int64_t> reads_runs;        // coordinate order, GPU pipeline: the written record each batch's sorted run begins at
 };
 
 struct Partial {   // what stage 3 produces for one chunk
@@ -492,6 +509,17 @@ struct Request {
     KeepRule keep;                          // the record filter (not active: every record is kept)
     const CovTable *cov_table() const { return has_cov ? &cov : nullptr; }
 };
+
+// The reads_order argument of the _ordered entry points, behind parse_request: 0 or 1, and 1 only with want_reads = 2.
+inline bool set_reads_order(Request &R, int32_t reads_order, std::string &err) {
+    if (reads_order != READS_ORDER_FILE && reads_order != READS_ORDER_COORDINATE) { err = "reads request: reads_order must be 0 (file order) or 1 (coordinate order)"; return false; }
+    if (reads_order == READS_ORDER_COORDINATE && !(R.reads.on && R.reads.mode == READS_AS_RECORDS)) {
+        err = "reads request: reads_order = 1 sorts records: it needs want_reads = 2";
+        return false;
+    }
+    R.reads.order = reads_order;
+    return true;
+}
 
 // Every argument rule of a request but one (the spans lie inside the file: spans_inside_file); false: `err` says why.
 inline bool parse_request(const coral_bam_request_t *q, Request &R, std::string &err) {

@@ -1447,6 +1447,47 @@ __global__ __launch_bounds__(WAVE) void k_bam_reads_copy(const uint8_t *__restri
     }
 }
 
+// Coordinate order (reads_order = 1 of a records request): between the plan and the scans the batch's records are sorted by
+// reads_sort_key - hipcub's radix sort of (key, ordinal), stable, so records with equal keys keep their file order - and
+// everything behind works on sorted positions: position j holds record ord[j].  All three kernels are one-wave workgroups
+// (DESIGN.md §10 (vi)).
+// One thread per record: its key from the fixed fields k_bam_meta left, and its ordinal.
+__global__ __launch_bounds__(WAVE) void k_bam_sort_keys(long long n_rec, MetaArrays M, unsigned long long *__restrict__ key, uint32_t *__restrict__ ord) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_rec) return;
+    key[i] = reads_sort_key(M.tid[i], M.pos[i], (uint32_t)M.flag[i]);
+    ord[i] = (uint32_t)i;
+}
+
+// One thread per sorted position: the plan's out_len / n_items of the record that sorts there (0 for a record that is not
+// written, wherever it sorts); slot n_rec, the scans' extra entry, is 0.
+__global__ __launch_bounds__(WAVE) void k_bam_sort_permute(long long n_rec, const uint32_t *__restrict__ ord, const long long *__restrict__ out_len,
+                                                           const long long *__restrict__ n_items, long long *__restrict__ sorted_len,
+                                                           long long *__restrict__ sorted_items) {
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j > n_rec) return;
+    const long long i = j < n_rec ? (long long)ord[j] : n_rec;
+    sorted_len[j] = j < n_rec ? out_len[i] : 0;
+    sorted_items[j] = j < n_rec ? n_items[i] : 0;
+}
+
+// k_bam_reads_copy for sorted positions (same launch shape, same work items of READS_COPY_SLICE bytes): item_off / out_off are
+// the scans over the PERMUTED arrays, so work item w belongs to sorted position j, whose bytes come from record ord[j].  Every
+// output byte still has exactly one writer (the items split the record, the sorted positions split the output): no atomics.
+__global__ __launch_bounds__(WAVE) void k_bam_reads_copy_sorted(const uint8_t *__restrict__ buf, long long buf_bytes, const long long *__restrict__ rec_start,
+                                                                long long n_rec, const uint32_t *__restrict__ ord,
+                                                                const long long *__restrict__ item_off, const long long *__restrict__ out_off,
+                                                                uint8_t *__restrict__ out) {
+    const int lane = threadIdx.x;
+    const long long total = item_off[n_rec];
+    for (long long w = blockIdx.x; w < total; w += gridDim.x) {
+        const long long j = item_record(item_off, n_rec, w);
+        const long long rs = rec_start[ord[j]], at = out_off[j], bytes = out_off[j + 1] - at;
+        const long long a = (w - item_off[j]) * READS_COPY_SLICE, b = min(bytes, a + READS_COPY_SLICE);
+        reads_run(out, at, a, b, lane, [&](long long j0) { return reads_window(buf, rs + j0, buf_bytes); });
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // K_index: what a batch contributes to the BAI index of the file (want_index; IndexPartial in coral_bam_common.h)
 // ---------------------------------------------------------------------------------------------
@@ -1880,13 +1921,26 @@ struct ReadsRequest {                // FASTQ text, or the own bytes (R->mode), 
     uint8_t *text = nullptr;         // the batch's text: one buffer for all batches (collect)
     size_t text_cap = 0, buf_bytes = 0;
     long long pending_bytes = 0;     // text of the batch emitted last that is still on the device
+    // coordinate order (R->order): the sort's double buffers of keys and ordinals, the permuted plan arrays and hipcub's
+    // temporary storage - carved only for such a request
+    unsigned long long *sort_key[2] = {nullptr, nullptr};
+    uint32_t *sort_ord[2] = {nullptr, nullptr};
+    long long *sorted_len = nullptr, *sorted_items = nullptr;
+    void *sort_tmp = nullptr;
+    size_t sort_tmp_bytes = 0;
+    bool ordered() const { return active && R->order == READS_ORDER_COORDINATE; }
     // The output buffer is sized by a bound, not by a count: a record of l bases and a name field of n bytes (NUL included) takes
     // at least 36 + n + 1.5 l bytes of the batch (block_size, the fixed fields, the name, SEQ, QUAL) and its text 2 l + n + 5, and
     // 2 l + n + 5 <= 4/3 (36 + n + 1.5 l) = 48 + 4/3 n + 2 l.  So the text of all records of a batch fits 4/3 of the batch's bytes,
     // the carried ones included (+ 256: the division's remainder and room to spare).  In mode READS_AS_RECORDS the written bytes
     // are a part of the batch's own: one batch's capacity + 256.
-    void carve(Carver &take, size_t batch_cap) {
+    void carve(Carver &take, size_t batch_cap, size_t nr) {
         if (!active) return;
+        if (ordered()) {
+            for (int i = 0; i < 2; ++i) { sort_key[i] = (unsigned long long *)take(nr * 8); sort_ord[i] = (uint32_t *)take(nr * 4); }
+            sorted_len = (long long *)take(nr * 8); sorted_items = (long long *)take(nr * 8);
+            sort_tmp = take(sort_tmp_bytes);
+        }
         buf_bytes = up256(batch_cap + COMP_SLACK);                 // (what d_infl[slot] really has: reads_window's guard)
         const size_t n_seg = R->tid.size(), n_names = (size_t)R->n_names();
         int32_t *seg = (int32_t *)take(3 * n_seg * 4);
@@ -1918,10 +1972,28 @@ struct ReadsRequest {                // FASTQ text, or the own bytes (R->mode), 
         pending_bytes = 0;
         return ok;
     }
-    bool finish(Decoded &D) {
+    // Coordinate order: every batch left one sorted run (D.reads_runs: the written record it begins at); more than one run goes
+    // through the host's stable k-way merge, run order = batch order, and the runs are freed.
+    bool finish(Decoded &D, int n_threads) {
         if (!active) return true;
         D.has_reads = true;
-        return collect(D);
+        if (!collect(D)) return false;
+        if (!ordered() || D.reads_runs.size() < 2) return true;
+        const size_t n_runs = D.reads_runs.size(), n_rec = D.reads_off.size() - 1;
+        std::vector<const uint8_t *> data(n_runs, D.reads_text.data());
+        std::vector<const int64_t *> off(n_runs);
+        std::vector<int64_t> n(n_runs);
+        for (size_t r = 0; r < n_runs; ++r) {
+            off[r] = D.reads_off.data() + D.reads_runs[r];
+            n[r] = (r + 1 < n_runs ? D.reads_runs[r + 1] : (int64_t)n_rec) - D.reads_runs[r];
+        }
+        std::vector<uint8_t> text(D.reads_text.size());
+        std::vector<int64_t> merged(n_rec + 1);
+        if (coral_bam_records_merge((int32_t)n_runs, data.data(), off.data(), n.data(), text.data(), merged.data(), n_threads) != CORAL_OK) return false;
+        D.reads_text.swap(text);
+        D.reads_off.swap(merged);
+        D.reads_runs.assign(1, 0);
+        return true;
     }
 };
 
@@ -2091,7 +2163,23 @@ bool ReadsRequest::batch(GpuDecoder *G, hipStream_t stream, const Borrowed &S, s
     const uint8_t *buf = G->d_infl[G->k & 1];
     hipLaunchKernelGGL(k_bam_reads_plan, dim3((unsigned)((n + 1 + WAVE - 1) / WAVE)), dim3(WAVE), 0, stream, buf, G->d_rec_start, n, G->M, G->d_end, X,
                        S.out_len, S.items);
-    if (!G->scan(stream, S.out_len, S.out_off) || !G->scan(stream, S.items, S.item_off)) { err = "scan of the reads work items failed"; return false; }
+    const uint32_t *ord = nullptr;                   // coordinate order: sorted position -> record of the batch
+    if (ordered()) {
+        hipLaunchKernelGGL(k_bam_sort_keys, dim3((unsigned)((n + WAVE - 1) / WAVE)), dim3(WAVE), 0, stream, n, G->M, sort_key[0], sort_ord[0]);
+        hipcub::DoubleBuffer<unsigned long long> keys(sort_key[0], sort_key[1]);
+        hipcub::DoubleBuffer<uint32_t> ords(sort_ord[0], sort_ord[1]);
+        size_t need = 0, tmp = sort_tmp_bytes;           // (the storage was sized for the largest batch: checked, not assumed)
+        if (hipcub::DeviceRadixSort::SortPairs(nullptr, need, keys, ords, (int)n, 0, 64, stream) != hipSuccess || need > sort_tmp_bytes ||
+            hipcub::DeviceRadixSort::SortPairs(sort_tmp, tmp, keys, ords, (int)n, 0, 64, stream) != hipSuccess) {
+            err = "sort of the reads keys failed";
+            return false;
+        }
+        ord = ords.Current();
+        hipLaunchKernelGGL(k_bam_sort_permute, dim3((unsigned)((n + 1 + WAVE - 1) / WAVE)), dim3(WAVE), 0, stream, n, ord, S.out_len, S.items, sorted_len,
+                           sorted_items);
+        if (!G->scan(stream, sorted_len, S.out_off) || !G->scan(stream, sorted_items, S.item_off)) { err = "scan of the sorted reads work items failed"; return false; }
+        G->D.reads_runs.push_back((int64_t)G->D.reads_off.size() - 1);      // this batch's run begins behind what is written
+    } else if (!G->scan(stream, S.out_len, S.out_off) || !G->scan(stream, S.items, S.item_off)) { err = "scan of the reads work items failed"; return false; }
     std::vector<long long> off((size_t)n + 1);
     long long items = 0;
     if (hipMemcpyAsync(off.data(), S.out_off, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, stream) != hipSuccess ||
@@ -2107,7 +2195,9 @@ bool ReadsRequest::batch(GpuDecoder *G, hipStream_t stream, const Borrowed &S, s
         if (off[(size_t)i + 1] > off[(size_t)i]) G->D.reads_off.push_back(base + off[(size_t)i + 1]);
     // one wave per workgroup, grid-stride beyond 8 per CU
     const dim3 grid((unsigned)std::min<long long>(items, 2048));
-    if (X.mode == READS_AS_RECORDS)
+    if (ord)
+        hipLaunchKernelGGL(k_bam_reads_copy_sorted, grid, dim3(WAVE), 0, stream, buf, (long long)buf_bytes, G->d_rec_start, n, ord, S.item_off, S.out_off, text);
+    else if (X.mode == READS_AS_RECORDS)
         hipLaunchKernelGGL(k_bam_reads_copy, grid, dim3(WAVE), 0, stream, buf, (long long)buf_bytes, G->d_rec_start, n, S.item_off, S.out_off, text);
     else
         hipLaunchKernelGGL(k_bam_reads_emit, grid, dim3(WAVE), 0, stream, buf, (long long)buf_bytes, G->d_rec_start, n, G->M, S.item_off, S.out_off, text);
@@ -2438,7 +2528,7 @@ bool carve(GpuDecoder *G, void *ws, size_t bytes) {
     G->qc.carve(take, nr);
     G->cov.carve(take);
     G->depth.carve(take, G->D.depth);
-    G->reads.carve(take, (size_t)CARRY_CAP + G->infl_cap);
+    G->reads.carve(take, (size_t)CARRY_CAP + G->infl_cap, nr);
     if (ws && take.used > bytes) return false;
     G->ws_bytes = take.used;
     return true;
@@ -2513,11 +2603,16 @@ const char *rec_error_text(int e) {
 // ---------------------------------------------------------------------------------------------
 extern "C" int coral_bamgpu_open_request(const char *path, int32_t n_threads, int64_t batch_bytes, const coral_bam_request_t *req, void **handle,
                                          int64_t *workspace_bytes) {
+    return coral_bamgpu_open_request_ordered(path, n_threads, batch_bytes, req, READS_ORDER_FILE, handle, workspace_bytes);
+}
+
+extern "C" int coral_bamgpu_open_request_ordered(const char *path, int32_t n_threads, int64_t batch_bytes, const coral_bam_request_t *req,
+                                                 int32_t reads_order, void **handle, int64_t *workspace_bytes) {
     if (!path || !handle || !workspace_bytes) return CORAL_ERR_ARG;
     std::unique_ptr<GpuDecoder> G(new GpuDecoder());
     G->t_start = std::chrono::steady_clock::now();
     std::string err;
-    if (!parse_request(req, G->req, err)) { set_error(err); return CORAL_ERR_ARG; }
+    if (!parse_request(req, G->req, err) || !set_reads_order(G->req, reads_order, err)) { set_error(err); return CORAL_ERR_ARG; }
     const Request &R = G->req;
     const int32_t rank = R.rank, world = R.world;
     if (!G->f.open(path, G->error) || !read_bam_header(G->f, G->D, G->ref_id, &G->hdr_bytes)) {
@@ -2576,6 +2671,16 @@ extern "C" int coral_bamgpu_open_request(const char *path, int32_t n_threads, in
     size_t tmp = 0;
     (void)hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, (long long *)nullptr, (long long *)nullptr, (int)std::min<size_t>(G->rec_cap + 1, 0x7fffffff));
     G->scan_tmp_bytes = tmp + 256;
+    if (G->reads.ordered()) {                  // the sort's temporary storage, queried once for the largest batch, as the scan's is
+        hipcub::DoubleBuffer<unsigned long long> keys(nullptr, nullptr);
+        hipcub::DoubleBuffer<uint32_t> ords(nullptr, nullptr);
+        size_t sort_tmp = 0;
+        if (hipcub::DeviceRadixSort::SortPairs(nullptr, sort_tmp, keys, ords, (int)std::min<size_t>(G->rec_cap + 1, 0x7fffffff), 0, 64) != hipSuccess) {
+            set_error("coral_bamgpu_open_request_ordered: the size of the sort's temporary storage could not be queried");
+            return CORAL_ERR_HIP;
+        }
+        G->reads.sort_tmp_bytes = sort_tmp + 256;
+    }
     carve(G.get(), nullptr, 0);
     if (const char *fb = getenv("CORAL_BAMGPU_FIRST_BATCH")) G->first_batch = std::max<uint64_t>(1u << 20, strtoull(fb, nullptr, 10));      // tuning
     G->known_start = CARRY_CAP + (long long)(rank == 0 ? G->hdr_bytes : 0);
@@ -2599,7 +2704,7 @@ extern "C" int coral_bamgpu_finish(void *handle, void *stream_) {
     if (!G->finished || G->have_cur) { set_error("coral_bamgpu_finish: the decode is not finished"); return CORAL_ERR_ARG; }
     if (!G->cov.active && !G->qc.active && !G->idx.active && !G->depth.active && !G->reads.active) return CORAL_OK;
     if (hipStreamSynchronize((hipStream_t)stream_) != hipSuccess || !G->cov.finish(G->D) || !G->idx.finish(G->D.idx) || !G->qc.finish(G->D.qc) ||
-        !G->depth.finish(G->D.depth) || !G->reads.finish(G->D)) {
+        !G->depth.finish(G->D.depth) || !G->reads.finish(G->D, G->n_threads)) {
         set_error("coral_bamgpu_finish: copy of the requested results failed");
         return CORAL_ERR_HIP;
     }

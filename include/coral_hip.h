@@ -548,6 +548,25 @@ int coral_bam_reads_fill(void *handle, uint8_t *text, int64_t *rec_off);
  * n_parts < 0, a missing array or part, a path that cannot be created; CORAL_ERR_FORMAT: the write failed. */
 int coral_bgzf_write(const char *path, const uint8_t *const *parts, const int64_t *part_bytes, int32_t n_parts, int32_t level,
                      int32_t n_threads);
+/* Records in coordinate order - what `samtools sort` does in a pass of its own (the reference's
+ * scripts/align_nanopore_reads.sh:49), here inside the decode.  coral_bam_decode_request_ordered is coral_bam_decode_request
+ * with reads_order: 0 = file order (what coral_bam_decode_request asks for), 1 = the written records of a want_reads = 2
+ * request ascending by
+ *   key = (uint64)(uint32)tid << 32 | (uint64)(uint32)(pos + 1) << 1 | (flag >> 4 & 1)
+ * - tid = -1 is 0xffffffff: records without coordinates last; at an equal position forward strand first -, records with equal
+ * keys in their input order (stable).  CORAL_ERR_ARG: reads_order outside 0..1, or 1 without want_reads = 2.  The result is read
+ * with coral_bam_reads_sizes / _fill as before, in final order.  A byte range or span decode sorts what it selects; the sorted
+ * results of consecutive ranges are joined by coral_bam_records_merge (rank order = run order).
+ * coral_bam_records_merge: a stable k-way merge of n_runs sorted runs of raw records by the same key, read from the records'
+ * bytes (tid at +4, pos at +8, flag at +18).  Record k of run r is data[r][off[r][k] .. off[r][k + 1]), n[r] records; on a tie
+ * the earlier run wins, inside a run the order stays.  out_off gets sum(n) + 1 offsets (the first 0), out_data the bytes
+ * (out_off[sum(n)] of them = the runs' bytes; the caller sizes it).  The order and the offsets are computed first, then the
+ * bytes are copied by n_threads workers (< 1: one): they do not depend on n_threads.  CORAL_ERR_ARG: n_runs < 0, a missing
+ * array, a negative count, offsets that decrease. */
+int coral_bam_decode_request_ordered(const char *path, int32_t n_threads, const coral_bam_request_t *req, int32_t reads_order,
+                                     void **handle);
+int coral_bam_records_merge(int32_t n_runs, const uint8_t *const *data, const int64_t *const *off, const int64_t *n,
+                            uint8_t *out_data, int64_t *out_off, int32_t n_threads);
 
 /* ------------------------------------------------------------------------------------------------
  * coral_bamgpu_* — the same decode with the inflate and the record parsing ON THE GPU: the host reads the file and sends
@@ -608,6 +627,13 @@ int coral_bgzf_write(const char *path, const uint8_t *const *parts, const int64_
  *                      and k_bam_reads_copy takes k_bam_reads_emit's place (same launch shape: a lane stores one aligned
  *                      16-byte chunk of the output, filled from the two aligned source chunks that cover it; bytes at an
  *                      item's two edges; no LDS, no atomics); the buffer is one batch + 256 bytes
+ *                      reads_order = 1 (coral_bamgpu_open_request_ordered): between the plan and the scans k_bam_sort_keys (one
+ *                      thread per record: reads_sort_key and the record's ordinal), hipcub's stable radix sort of (key,
+ *                      ordinal) and k_bam_sort_permute (the plan's lengths and item counts in sorted order); the scans run
+ *                      over the permuted arrays and k_bam_reads_copy_sorted, k_bam_reads_copy with the source record looked up
+ *                      through the permutation, writes the batch's records sorted: one sorted run per batch.  The sort's
+ *                      arrays (40 bytes per record of a batch + hipcub's temporary storage) are carved only for such a
+ *                      request.  `finish` merges the runs (coral_bam_records_merge) when there is more than one
  *   finish        after the last batch (CORAL_ERR_ARG before): waits for `stream` once and leaves what was requested in the
  *          handle of `host` (coral_bam_coverage_result, coral_bam_pileup_result - the table is copied and summed per segment
  *          here -, coral_bam_index_sizes / _fill, coral_bam_qc_sizes / _fill, coral_bam_depth_sizes / _fill, coral_bam_reads_sizes / _fill); fails when
@@ -625,6 +651,8 @@ int coral_bamgpu_host(void *handle, void **decoded);
 int coral_bamgpu_stats(void *handle, int64_t stats[4], double seconds[6]);
 int coral_bamgpu_open_request(const char *path, int32_t n_threads, int64_t batch_bytes, const coral_bam_request_t *req,
                               void **handle, int64_t *workspace_bytes);
+int coral_bamgpu_open_request_ordered(const char *path, int32_t n_threads, int64_t batch_bytes, const coral_bam_request_t *req,
+                                      int32_t reads_order, void **handle, int64_t *workspace_bytes);
 int coral_bamgpu_finish(void *handle, void *stream);
 int coral_bamgpu_close(void *handle);
 int coral_bgzf_inflate(const uint8_t *comp, const uint32_t *desc, int32_t n_blocks, uint8_t *out, int32_t *status,
