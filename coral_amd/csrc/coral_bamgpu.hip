@@ -148,6 +148,9 @@ struct DevWaveT {
         return v;
     }
     __device__ __forceinline__ bool input_exhausted() const { return win + idx > last_dw + 4; }
+    __device__ __forceinline__ bool input_overrun(long long dwords, int bc) const {
+        return 32 * (base_dw + (int)dwords) - bc > 8 * (stream_off + stream_len);
+    }
     __device__ __forceinline__ uint8_t *ring_at(uint32_t av) const { return ring + (av & RING_MASK); }
     // completed 256-byte lines ring -> global memory (the block's first line may start inside a line: byte stores there);
     // never beyond the block's last byte
@@ -189,7 +192,10 @@ _Pragma("clang loop unroll(disable) vectorize(disable) interleave(disable)")
     // lenv, distv: the same value in every lane (vector registers)
     __device__ __forceinline__ void match(uint32_t lenv, uint32_t distv) {
         const uint32_t av = vec((uint32_t)a);
-        const uint32_t room = vec((uint32_t)(aend - a));              // (a <= aend + 255; as unsigned a huge room then, `over` is raised by drain)
+        // one byte more than the block may still take: a match that does not fit leaves `a` behind aend, which drain() turns into
+        // `over` (cut to what fits, it would end the block at exactly its size and pass for a good one); the byte goes to the ring
+        // only.  (a <= aend + 255; behind aend the room is 0 or, as unsigned, huge, and `over` is raised all the same)
+        const uint32_t room = vec((uint32_t)(aend - a) + 1u);
         const uint32_t far_back = distv > av - (uint32_t)a0 ? 1u : 0u;    // reaches in front of the block's output: corrupt
         badv |= far_back;
         lenv = far_back ? 0u : (lenv < room ? lenv : room);

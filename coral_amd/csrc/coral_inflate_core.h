@@ -79,7 +79,11 @@ CORAL_HD uint32_t dist_entry(uint32_t d, uint32_t nbits) {
 //   bool     copy_stored(long long dwords, uint32_t n)   n raw bytes, starting `dwords` dwords into the input window, to the output
 //   uint32_t reset_input_after_stored(long long dwords, uint32_t n)   restart the window behind those bytes; returns the bits
 //                                     to drop from the first dword of the new window (device windows are dword-aligned)
-//   bool     input_exhausted()        more input pulled than the stream holds (corrupt data)
+//   bool     input_exhausted()        more input pulled than the stream holds (corrupt data); coarse, the bit buffer reads ahead
+//   bool     input_overrun(long long dwords, int bc)   exact, once per stream: the bits consumed (`dwords` dwords into the window
+//                                     less `bc` still in the bit buffer) lie beyond the stream's last byte.  Optional: a backend
+//                                     that does not know where its stream ends leaves it out and gets the coarse check alone
+//                                     (the device backend and the host backend of the tests both have it)
 //   int      produced()               output bytes so far;   int capacity()
 //   void     add_count(uint32_t *c)   atomic / plain increment of a table counter
 //   void     fence()                  order table writes of all lanes before later reads
@@ -89,6 +93,11 @@ CORAL_HD uint32_t dist_entry(uint32_t d, uint32_t nbits) {
 #else
 #define W_FOR_LANES(w, lane) for (int lane = 0; lane < WAVE_LANES; ++lane)
 #endif
+
+template <class X>
+CORAL_HD auto input_overrun_of(X &w, long long dwords, int bc, int) -> decltype(w.input_overrun(dwords, bc)) { return w.input_overrun(dwords, bc); }
+template <class X>
+CORAL_HD bool input_overrun_of(X &, long long, int, long) { return false; }
 
 template <class W>
 struct Inflater {
@@ -474,6 +483,9 @@ struct Inflater {
             if (w.input_exhausted()) return ERR_INPUT;
             if (last) break;
         }
+        // the bit buffer reads up to 8 bytes ahead: a stream cut inside its last bytes (a short stored block, an end-of-block code)
+        // must not be completed by whatever follows it in memory
+        if (input_overrun_of(w, dwords, bc, 0)) return ERR_INPUT;
         return w.produced() == w.capacity() ? OK : ERR_SHORT;
     }
 };

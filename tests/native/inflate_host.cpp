@@ -79,6 +79,7 @@ struct HostWaveT {
         return v;
     }
     bool input_exhausted() const { return win0 + 4 * pulled > src_len + 8; }
+    bool input_overrun(long long dwords, int bc) const { return 8 * win0 + 32 * dwords - bc > 8 * src_len; }
     // the vector loop's backend operations, with the device backend's error behaviour: nothing is tested per symbol — a bad
     // length / distance is clamped and remembered, output beyond the capacity is dropped and raises `over`
     bool over = false, bad_ = false;

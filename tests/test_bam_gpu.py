@@ -12,39 +12,12 @@ import pytest
 import torch
 
 from coral_amd import bam, synth, _lib
-from tests.decode_support import assert_same_records as assert_same, concat_records as _concat, odd_io_records as _odd
+from tests.decode_support import assert_same_records as assert_same, concat_records as _concat, inflate_on_gpu as _inflate_on_gpu, odd_io_records as _odd
 
 pytestmark = pytest.mark.gpu
 
 
 from tests.deflate_streams import streams as _streams
-
-
-def _inflate_on_gpu(pairs, pad=0):
-    """One coral_bgzf_inflate launch over all streams (stream k starts `pad + k % 4` bytes after the previous one: every
-    alignment of input and output occurs)."""
-    L = _lib.lib()
-    comp, desc, o_in, o_out = bytearray(), [], 0, 0
-    for k, (c, d) in enumerate(pairs):
-        gap = pad + (k % 4)
-        comp += b"\xaa" * gap
-        o_in += gap
-        o_out += k % 3
-        desc.append((o_in, len(c), o_out, len(d)))
-        comp += c
-        o_in += len(c)
-        o_out += len(d)
-    comp += bytes(4096)
-    dev = "cuda:0"
-    t_comp = torch.frombuffer(bytearray(comp), dtype=torch.uint8).to(dev)
-    t_desc = torch.tensor(desc, dtype=torch.int64).to(torch.int32).contiguous().to(dev)      # (values < 2^31)
-    t_out = torch.full((o_out + 64,), 0x55, dtype=torch.uint8, device=dev)
-    t_status = torch.full((len(pairs),), -1, dtype=torch.int32, device=dev)
-    rc = L.coral_bgzf_inflate(t_comp.data_ptr(), t_desc.data_ptr(), len(pairs), t_out.data_ptr(), t_status.data_ptr(),
-                              torch.cuda.current_stream().cuda_stream)
-    assert rc == 0, L.coral_bam_last_error()
-    torch.cuda.synchronize()
-    return t_out.cpu().numpy().tobytes(), t_status.cpu().tolist(), desc
 
 
 def test_inflate_kernel_equals_zlib():

@@ -90,3 +90,45 @@ def test_core_survives_corrupt_streams(inflate):
         comp = zlib.compress(os.urandom(3000), 6)[2:-4]
         rc, got = inflate(comp[:cut], 3000)
         assert rc != 0
+
+
+# ---- hand-built streams (tests/deflate_streams.py: Deflate): what no compressor writes
+@pytest.fixture(scope="module")
+def built():
+    from tests import deflate_streams as ds
+    return ds.dynamic_streams(), ds.rejected_streams(), ds.incomplete_streams()
+
+
+def test_hand_built_streams_reach_their_edges(built):
+    """Every case asserts from the header and the lengths it wrote that it holds what it is named after (a repeat op that really
+    crosses the literal / distance boundary, a code that really is longer than the table, ...), and the set as a whole covers
+    every length and distance symbol on both decode paths with every extra-bit pattern."""
+    from tests.deflate_streams import check_coverage
+    valid, rejected, incomplete = built
+    for case in valid:
+        case["edge"]()
+    check_coverage(valid)
+    names = [c["name"] for c in valid] + [r[0] for r in rejected] + [r[0] for r in incomplete if r[0].endswith("accepted")]
+    assert len(set(names)) == len(names)
+    assert sum(1 for n in names if n.startswith("cut_after_")) == 40
+
+
+def test_core_decodes_hand_built_streams(inflate, built):
+    for case in built[0]:
+        assert inflate(case["comp"], len(case["text"])) == (0, case["text"]), case["name"]
+
+
+def test_core_rejects_hand_built_streams(inflate, built):
+    """(the fixture asserts that nothing is written beyond the declared size)"""
+    for name, comp, size in built[1]:
+        rc, got = inflate(comp, size)
+        assert rc != 0 and len(got) <= size, name
+
+
+def test_core_takes_incomplete_codes_whose_unused_patterns_do_not_occur(inflate, built):
+    """Inflater::build: 'Incomplete codes are accepted; their unused patterns decode to "bad code"' — zlib refuses the header."""
+    for name, comp, want in built[2]:
+        if name.endswith("accepted"):
+            assert inflate(comp, len(want)) == (0, want), name
+        else:
+            assert inflate(comp, want)[0] != 0, name
