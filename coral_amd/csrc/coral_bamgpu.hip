@@ -20,18 +20,15 @@
 //                   codes, read name and SA text -> compact blobs for the host
 //   worker thread   per batch, a few hundred bytes per record: read names -> ids, SA text -> numeric rows; the rare
 //                   records with non-ACGT bases are gathered whole (k_bam_gather) and handled by the CPU pipeline's own routine.
-// Requests that ride along a decode (coral_bam_request_t), each queued per batch before the slot is reused:
-//   k_bam_cov_plan + k_bam_cov_count   window coverage: pysam count_coverage with a base-quality threshold over the segments
-//   k_bam_cov_plan + k_bam_pileup      the same split by position and base (per_base): one 32-bit atomic per counted base
-//                   (both kernels are cov_walk, the one CIGAR walk that applies the coverage rule, with a sink each)
-//   k_bam_qc_plan + k_bam_qc           read QC: per read the sum of its QUAL bytes, and the 256-bin histogram of all of them
-//   k_bam_index + k_bam_index_compact  index: per record the virtual offset, the UCSC bin and the linear-index windows of a
-//                   BAI index, per batch the heads of the runs of equal (tid, bin)
-//   k_bam_depth     binned depth: per record one walk of its CIGAR, one 64-bit atomic per run of lanes in the same bin
-//   k_bam_reads_plan + k_bam_reads_emit   reads: the selected records as FASTQ text (nibbles -> ASCII, reverse strand mirrored
-//                   and complemented), scattered to scanned offsets of a per-batch buffer the host collects one batch later
-//   k_bam_reads_copy   reads, want_reads = 2: the selected records' own bytes, gathered to the same scanned offsets
-// Host: one struct per request (carve / start / batch / finish); what it may borrow of the parse's scratch: struct Borrowed.
+// Requests that ride along a decode (coral_bam_request_t), each queued per batch before the slot is reused; one header each
+// (kernels, device structs and the host-side struct), listed once, in stream order, at each_request:
+//   coral_bamgpu_reads.h   reads: the selected records as FASTQ text or as their own bytes, in file or coordinate order
+//   coral_bamgpu_cov.h     window coverage: pysam count_coverage with a base-quality threshold; per_base: the pileup table
+//   coral_bamgpu_qc.h      read QC: per read the sum of its QUAL bytes, and the 256-bin histogram of all of them
+//   coral_bamgpu_depth.h   binned depth: one walk of each record's CIGAR into two tables of fixed-size bins
+//   coral_bamgpu_index.h   index: what the batch contributes to a BAI index
+// Every request has open / carve / start / batch / finish; batch sees the batch as a `Batch` and may overwrite the parse's dead
+// per-record arrays, handed to it as a `Scratch` (coral_bamgpu_common.h).
 // Batches (64 MiB first, doubling up to 2.52 GiB inflated, coral_bamgpu_open) are double-buffered: while batch k is parsed, batch k + 1 is inflated
 // and k + 2 is read.
 // A record that straddles two batches is carried in front of the next batch's buffer.
@@ -40,6 +37,8 @@
 // same first-record / last-record rule as coral_bam_decode_range, so consecutive ranges neither drop nor repeat a record.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
+
+#include <array>
 
 #include "../../include/coral_hip.h"
 #include "coral_bam_common.h"
@@ -65,6 +64,8 @@ struct BlockDesc {
     uint32_t dst_off;     // first output byte, relative to the batch's first inflated byte
     uint32_t isize;
 };
+
+#include "coral_bamgpu_common.h"
 
 // ---------------------------------------------------------------------------------------------
 // K_inflate
@@ -619,9 +620,6 @@ __global__ __launch_bounds__(WAVE) void k_bgzf_crc(const uint8_t *__restrict__ o
 // ---------------------------------------------------------------------------------------------
 // record boundaries
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t ld32(const uint8_t *p) { uint32_t v; __builtin_memcpy(&v, p, 4); return v; }
-__device__ __forceinline__ uint32_t ld16(const uint8_t *p) { uint16_t v; __builtin_memcpy(&v, p, 2); return v; }
-
 // the plausibility test of coral_bam.cpp (plausible_record), on device memory
 __device__ __forceinline__ bool plausible(const uint8_t *buf, long long q, long long data_end, int n_ref, long long *len) {
     const long long n = data_end - q;
@@ -809,8 +807,6 @@ __global__ void k_bam_starts(const uint8_t *__restrict__ buf, int seg0, int n_se
     }
 }
 
-enum { REC_ERR_SHORT = 1, REC_ERR_FIELDS = 2, REC_ERR_TAG_B = 3, REC_ERR_TAG_TYPE = 4, REC_ERR_TAG_OVERRUN = 5 };
-
 // ---------------------------------------------------------------------------------------------
 // K_keep: the record filter (keep_* of the request; KeepRule / keep_record in coral_bam_common.h), between the boundary walk
 // and k_bam_meta.  One thread per record in one-wave workgroups (they run beside the inflate launch): the
@@ -839,12 +835,6 @@ __global__ __launch_bounds__(WAVE) void k_bam_keep_compact(const long long *__re
 // ---------------------------------------------------------------------------------------------
 // K_meta: one wave per record
 // ---------------------------------------------------------------------------------------------
-struct MetaArrays {
-    int32_t *tid, *pos, *flag, *mapq, *l_seq, *nm, *n_cigar;       // what the host mirrors need (+ end, qlen from k_bam_emit)
-    long long *cig_src, *seq_src, *sa_src;                         // buffer offsets
-    long long *pad_ops, *name_len, *sa_len;                        // scan inputs (n + 1 entries, the last one 0)
-};
-
 __global__ __launch_bounds__(256) void k_bam_meta(const uint8_t *__restrict__ buf, const long long *__restrict__ rec_start, long long n_rec,
                                                    MetaArrays M, int32_t *__restrict__ error) {
     const int lane = threadIdx.x & 63;
@@ -1023,708 +1013,17 @@ __global__ __launch_bounds__(256) void k_bam_gather(const uint8_t *__restrict__ 
 }
 
 // ---------------------------------------------------------------------------------------------
-// K_cov: window coverage with a base-quality threshold (the segments of the request), counted while SEQ and QUAL are in HBM
+// the requests that ride along, in stream order (each_request)
 // ---------------------------------------------------------------------------------------------
-#define COV_SLICE 16384ll                // query bases per work item: a 1 Mb read is 62 waves' work, not one wave's
-
-struct CovSegs {                         // the request's sorted, disjoint segments (device arrays in the workspace)
-    const int32_t *tid, *lo, *hi;
-    int n;
-};
-
-// first segment at or after (t, pos) in (tid, hi) order, searching [from, n); wave-uniform when its arguments are
-__device__ __forceinline__ int cov_first(const CovSegs &S, int32_t t, long long pos, int from) {
-    int a = from, b = S.n;
-    while (a < b) {
-        const int m = (a + b) >> 1;
-        if (S.tid[m] < t || (S.tid[m] == t && (long long)S.hi[m] <= pos)) a = m + 1; else b = m;
-    }
-    return a;
-}
-
-// one thread per record: how many work items (COV_SLICE query bases each) the record needs; 0 when it is filtered out, has no
-// SEQ, has no QUAL at a threshold above 0, or overlaps no segment.  Slot n_rec gets 0 (the scan's extra entry).
-__global__ __launch_bounds__(256) void k_bam_cov_plan(const uint8_t *__restrict__ buf, long long n_rec, MetaArrays M,
-                                                       const int32_t *__restrict__ end_in, CovSegs S, int threshold, int filter_all,
-                                                       long long *__restrict__ n_items) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i > n_rec) return;
-    long long cnt = 0;
-    if (i < n_rec) {
-        const int32_t tid = M.tid[i], l_seq = M.l_seq[i], flag = M.flag[i];
-        if (tid >= 0 && l_seq > 0 && M.n_cigar[i] > 0 && !(filter_all && (flag & 0x704))) {
-            const uint8_t *qual = buf + M.seq_src[i] + ((long long)l_seq + 1) / 2;
-            if (threshold == 0 || qual[0] != 0xff) {
-                const int32_t pos = M.pos[i];
-                // end_in is htslib's bam_endpos: pos + 1 for an unmapped record, whose CIGAR is walked all the same
-                const long long end = (flag & 4) ? (1ll << 40) : (long long)end_in[i];
-                const int s = cov_first(S, tid, pos, 0);
-                if (s < S.n && S.tid[s] == tid && (long long)S.lo[s] < end) cnt = ((long long)l_seq + COV_SLICE - 1) / COV_SLICE;
-            }
-        }
-    }
-    n_items[i] = cnt;
-}
-
-// the record of work item w: the last i with item_off[i] <= w (item_off: the exclusive sums of n_rec + 1 item counts)
-__device__ __forceinline__ long long item_record(const long long *__restrict__ item_off, long long n_rec, long long w) {
-    long long a = 0, b = n_rec;
-    while (b - a > 1) {
-        const long long m = (a + b) >> 1;
-        if (item_off[m] <= w) a = m; else b = m;
-    }
-    return a;
-}
-
-// The CIGAR walk of one work item, the query bases [q_lo, q_hi) of record i, for both coverage kernels: the coverage rule
-// (CovTable in coral_bam_common.h) is applied here and nowhere else on the device.  The wave walks the CIGAR 64 ops at a time
-// (prefix sums of the query / reference advance), and for every aligned op that meets the query range the lanes stride over the
-// op's bases inside each segment, testing the SEQ code and QUAL.  What becomes of a counted base is the sink's business:
-//   segment(t, lo)   wave-uniform, in front of the bases of an op inside segment t (lo = S.lo[t]); segments are met in
-//                    increasing order, the same one again for every further op inside it
-//   base(x, col)     per lane: the base at reference position x counts, col = 0..3 for A, C, G, T
-template <class Segment, class Base>
-__device__ __forceinline__ void cov_walk(const uint8_t *__restrict__ buf, const MetaArrays &M, const CovSegs &S, uint32_t thr, long long i,
-                                         long long q_lo, long long q_hi, int lane, Segment segment, Base base) {
-    const int32_t tid = M.tid[i], l_seq = M.l_seq[i], pos = M.pos[i];
-    const int n_ops = M.n_cigar[i];
-    const uint8_t *ops = buf + M.cig_src[i];
-    const uint8_t *seq = buf + M.seq_src[i];
-    const uint8_t *qual = seq + ((long long)l_seq + 1) / 2;
-    int s = cov_first(S, tid, pos, 0);
-    long long q_base = 0, r_base = pos;
-    for (int c = 0; c < n_ops && q_base < q_hi; c += WAVE) {
-        if (s >= S.n || S.tid[s] != tid) break;                   // no segment left on this contig
-        const int kk = c + lane;
-        const uint32_t wd = kk < n_ops ? ld32(ops + 4ll * kk) : 15u;
-        const uint32_t op = wd & 15u;
-        const long long len = (long long)(wd >> 4);
-        const long long qa = ((0x193u >> op) & 1u) ? len : 0;     // M I S = X advance the query
-        const long long ra = ((0x18Du >> op) & 1u) ? len : 0;     // M D N = X advance the reference
-        long long qs = qa, rs = ra;
-        for (int d = 1; d < WAVE; d <<= 1) {
-            const long long tq = __shfl_up(qs, d), tr = __shfl_up(rs, d);
-            if (lane >= d) { qs += tq; rs += tr; }
-        }
-        const long long q_op = q_base + qs - qa, r_op = r_base + rs - ra;
-        const bool cand = ((0x181u >> op) & 1u) && len > 0 && q_op < q_hi && q_op + len > q_lo;     // M = X meeting the item
-        unsigned long long m = __ballot(cand);
-        while (m) {
-            const int j = __builtin_ctzll(m);
-            m &= m - 1;
-            const long long oq = __shfl(q_op, j), orf = __shfl(r_op, j), ol = __shfl(len, j);
-            const long long aq = max(oq, q_lo), bq = min(oq + ol, q_hi);
-            const long long r0 = orf + (aq - oq), r1 = orf + (bq - oq);
-            // r0 only grows: the cursor is usually still right (this op ends inside its segment) or one further
-            if (s < S.n && S.tid[s] == tid && (long long)S.hi[s] <= r0)
-                s = (s + 1 < S.n && S.tid[s + 1] == tid && (long long)S.hi[s + 1] > r0) ? s + 1 : cov_first(S, tid, r0, s + 1);
-            for (int t = s; t < S.n && S.tid[t] == tid && (long long)S.lo[t] < r1; ++t) {
-                const long long lo = S.lo[t], xa = max(r0, lo), xb = min(r1, (long long)S.hi[t]);
-                segment(t, lo);
-                for (long long x = xa + lane; x < xb; x += WAVE) {
-                    const long long qi = aq + (x - r0);                    // < bq <= q_hi <= l_seq
-                    const uint8_t byte = seq[qi >> 1];
-                    const uint32_t code = (qi & 1) ? (byte & 15u) : (uint32_t)(byte >> 4);
-                    uint32_t col;
-                    if (pileup_base(code, &col) && qual[qi] >= thr) base(x, col);
-                }
-            }
-        }
-        q_base += __shfl(qs, WAVE - 1);
-        r_base += __shfl(rs, WAVE - 1);
-    }
-}
-
-// one wave per work item (grid-stride): the query bases [k * COV_SLICE, (k + 1) * COV_SLICE) of record i.  The counting sink:
-// per-lane counts, reduced in the wave and added with ONE 64-bit atomic per (work item, segment).
-__global__ __launch_bounds__(256) void k_bam_cov_count(const uint8_t *__restrict__ buf, long long n_rec, MetaArrays M, CovSegs S,
-                                                        int threshold, const long long *__restrict__ item_off,
-                                                        unsigned long long *__restrict__ counts) {
-    const int lane = threadIdx.x & 63;
-    const long long n_waves = ((long long)gridDim.x * blockDim.x) >> 6;
-    const long long total = item_off[n_rec];
-    for (long long w = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6; w < total; w += n_waves) {
-        const long long i = item_record(item_off, n_rec, w);
-        const long long q_lo = (w - item_off[i]) * COV_SLICE, q_hi = min((long long)M.l_seq[i], q_lo + COV_SLICE);
-        int cur = -1;                                                  // the segment the lanes' counts belong to
-        uint32_t acc = 0;
-        auto flush = [&]() {
-            long long sum = (long long)acc;
-            for (int d = 32; d > 0; d >>= 1) sum += __shfl_xor(sum, d);
-            if (cur >= 0 && lane == 0 && sum) atomicAdd(counts + cur, (unsigned long long)sum);
-            acc = 0;
-        };
-        cov_walk(buf, M, S, (uint32_t)threshold, i, q_lo, q_hi, lane, [&](int t, long long) { if (t != cur) { flush(); cur = t; } },
-                 [&](long long, uint32_t) { ++acc; });
-        flush();
-    }
-}
-
-// K_pileup (per_base of the request): k_bam_cov_count's work items and walk with the table sink: every counted base is one
-// no-return 32-bit atomic at table[(seg_off[t] + x - lo[t]) * 4 + col].  There is nothing to reduce: the 64 lanes of a stride are
-// 64 different positions, so a wave never collides with itself - only different records at the same position do.  One wave per
-// workgroup (grid-stride), no LDS: it fits beside resident inflate waves.
-__global__ __launch_bounds__(WAVE) void k_bam_pileup(const uint8_t *__restrict__ buf, long long n_rec, MetaArrays M, CovSegs S,
-                                                     const long long *__restrict__ seg_off, int threshold,
-                                                     const long long *__restrict__ item_off, uint32_t *__restrict__ table) {
-    const int lane = threadIdx.x;
-    const long long total = item_off[n_rec];
-    for (long long w = blockIdx.x; w < total; w += gridDim.x) {
-        const long long i = item_record(item_off, n_rec, w);
-        const long long q_lo = (w - item_off[i]) * COV_SLICE, q_hi = min((long long)M.l_seq[i], q_lo + COV_SLICE);
-        long long row0 = 0;                                            // lo <= x < hi: 4 * x + row0 lies in the segment's rows
-        cov_walk(buf, M, S, (uint32_t)threshold, i, q_lo, q_hi, lane, [&](int t, long long lo) { row0 = 4 * (seg_off[t] - lo); },
-                 [&](long long x, uint32_t col) { atomicAdd(table + (row0 + 4 * x + col), 1u); });
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// K_qc: per-read base-quality sums and the base-quality histogram (want_qc; the rules: QcPartial in coral_bam_common.h)
-// ---------------------------------------------------------------------------------------------
-#define QC_SLICE 16384ll                 // QUAL bytes per work item (as COV_SLICE: a 1 Mb read is 62 waves' work)
-#ifndef QC_COPIES
-#define QC_COPIES 4                      // copies of the 256-bin table per wave, interleaved: 4 KiB of LDS (a -DQC_COPIES=1 build is
-#endif                                   // the single table to measure it against)
-
-// One thread per record (one-wave workgroups): qual_sum[i] = 0 for a read with quality (k_bam_qc adds to it), -1 otherwise, and
-// the number of work items its QUAL is cut into.  Slot n_rec gets 0 items (the scan's extra entry).
-__global__ __launch_bounds__(WAVE) void k_bam_qc_plan(const uint8_t *__restrict__ buf, const long long *__restrict__ rec_start, long long n_rec,
-                                                      MetaArrays M, long long *__restrict__ qual_sum, long long *__restrict__ n_items) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i > n_rec) return;
-    long long cnt = 0;
-    if (i < n_rec) {
-        const uint32_t l_seq = (uint32_t)M.l_seq[i];
-        bool counted = false;
-        if (qc_is_read((uint32_t)M.flag[i], l_seq)) {
-            const uint8_t *r = buf + rec_start[i];
-            counted = qc_has_quality(r[qc_qual_offset(r[12], ld16(r + 16), l_seq)]);
-        }
-        if (counted) cnt = ((long long)l_seq + QC_SLICE - 1) / QC_SLICE;
-        qual_sum[i] = counted ? 0 : -1;
-    }
-    n_items[i] = cnt;
-}
-
-// One wave per work item (one-wave workgroups, grid-stride): QUAL bytes [k * QC_SLICE, (k + 1) * QC_SLICE) of record i.
-// QUAL begins at any byte address: the wave reads the 16-byte aligned chunks that cover its bytes, lane l the chunks l, l + 64,
-// ... - one load instruction of the wave is 1 KiB of consecutive memory, every cache line is fetched once - and the bytes of the
-// first and the last chunk that are not the item's are masked out.  Sum: v_sad_u8 per dword, reduced in the wave, ONE 64-bit
-// atomic per item.  Histogram: COPIES copies of the 256 bins in LDS, interleaved (bin v of copy c at word v * COPIES + c, lane l
-// uses copy l % COPIES): real QUAL sits on a few values, and lanes that add to the same word are serialised - with the copies
-// side by side, lanes with the same value spread over COPIES words in COPIES different banks.  The workgroup adds its table to the
-// device histogram once, at its end, with 64-bit atomics.  4 KiB of LDS (COPIES = 4): fits beside the inflate launch's 27 x 5.75 KiB
-// of a CU's 160 KiB, as k_bgzf_crc's tables do.
-__global__ __launch_bounds__(WAVE) void k_bam_qc(const uint8_t *__restrict__ buf, const long long *__restrict__ rec_start, long long n_rec,
-                                                 MetaArrays M, const long long *__restrict__ item_off,
-                                                 unsigned long long *__restrict__ qual_sum, unsigned long long *__restrict__ hist) {
-    constexpr int COPIES = QC_COPIES;
-    // (a 32-bit bin cannot overflow: the grid-stride loop gives a workgroup at most ceil(items / 2 048) work items of 16 KiB, and
-    // CARRY_CAP + a batch stay below 4 GiB - under 2^21 bytes per workgroup and launch)
-    __shared__ uint32_t H[256 * COPIES];
-    const int lane = threadIdx.x;
-    for (int k = lane; k < 256 * COPIES; k += WAVE) H[k] = 0;
-    __syncthreads();
-    uint32_t *mine = H + (lane % COPIES);
-    const long long total = item_off[n_rec];
-    for (long long w = blockIdx.x; w < total; w += gridDim.x) {
-        const long long i = item_record(item_off, n_rec, w);
-        const uint32_t l_seq = (uint32_t)M.l_seq[i];
-        const uint8_t *r = buf + rec_start[i];
-        const long long q_lo = (w - item_off[i]) * QC_SLICE, q_hi = min((long long)l_seq, q_lo + QC_SLICE);
-        const uint8_t *p = r + qc_qual_offset(r[12], ld16(r + 16), l_seq) + q_lo;
-        const int n = (int)(q_hi - q_lo);                             // 1 .. QC_SLICE
-        const int head = (int)((uintptr_t)p & 15u);
-        const uint4 *chunks = reinterpret_cast<const uint4 *>(p - head);       // (inside the batch buffer: a record starts >= 36 bytes in front of its QUAL)
-        const int n_chunks = (head + n + 15) >> 4;
-        uint32_t acc = 0;
-        for (int c = lane; c < n_chunks; c += WAVE) {
-            const uint4 v = chunks[c];
-            const uint32_t word[4] = {v.x, v.y, v.z, v.w};
-            const int first = c * 16 - head;                          // item-relative index of the chunk's byte 0
-            if (first >= 0 && first + 16 <= n) {
-#pragma unroll
-                for (int d = 0; d < 4; ++d) {
-                    const uint32_t x = word[d];
-                    acc = __builtin_amdgcn_sad_u8(x, 0u, acc);
-                    atomicAdd(mine + (x & 0xffu) * COPIES, 1u);
-                    atomicAdd(mine + ((x >> 8) & 0xffu) * COPIES, 1u);
-                    atomicAdd(mine + ((x >> 16) & 0xffu) * COPIES, 1u);
-                    atomicAdd(mine + (x >> 24) * COPIES, 1u);
-                }
-            } else {                                                  // the item's first or last chunk: byte by byte
-#pragma unroll
-                for (int j = 0; j < 16; ++j) {
-                    const uint32_t q = (word[j >> 2] >> (8 * (j & 3))) & 0xffu;
-                    if (first + j >= 0 && first + j < n) {
-                        acc += q;
-                        atomicAdd(mine + q * COPIES, 1u);
-                    }
-                }
-            }
-        }
-        unsigned long long sum = acc;
-        for (int d = 32; d > 0; d >>= 1) sum += __shfl_xor(sum, d);
-        if (lane == 0) atomicAdd(qual_sum + i, sum);
-    }
-    __syncthreads();
-    for (int v = lane; v < 256; v += WAVE) {
-        unsigned long long t = 0;
-#pragma unroll
-        for (int c = 0; c < COPIES; ++c) t += H[v * COPIES + c];
-        if (t) atomicAdd(hist + v, t);
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// K_reads: the selected records as FASTQ text (want_reads; the rules: ReadsRule and reads_* in coral_bam_common.h)
-// ---------------------------------------------------------------------------------------------
-struct ReadsDev {                        // the request's device arrays, carved from the caller's workspace
-    const int32_t *tid, *lo, *hi;        // the segments (n_seg = 0: no region limit)
-    const uint8_t *names;                // the sorted names as one blob and n_names + 1 offsets (n_names = 0: no name limit)
-    const int64_t *name_off;
-    int n_seg;
-    long long n_names;
-    uint32_t exclude_flags;
-    int mode;                            // READS_AS_FASTQ or READS_AS_RECORDS
-};
-
-// One thread per record (one-wave workgroups: they run beside the inflate launch): the rule, from the fixed
-// fields k_bam_meta left, the end position k_bam_emit left and the name behind the record's fixed fields.  out_len[i] = bytes of
-// the record's text, n_items[i] = its work items of READS_SLICE bases; both 0 when the record is not written, and in slot n_rec
-// (the scans' extra entry).  In mode READS_AS_RECORDS a record without SEQ takes part too, out_len[i] is the record's own size,
-// 4 + block_size, and its work items are slices of READS_COPY_SLICE of those bytes.
-__global__ __launch_bounds__(WAVE) void k_bam_reads_plan(const uint8_t *__restrict__ buf, const long long *__restrict__ rec_start, long long n_rec,
-                                                         MetaArrays M, const int32_t *__restrict__ end_in, ReadsDev X,
-                                                         long long *__restrict__ out_len, long long *__restrict__ n_items) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i > n_rec) return;
-    long long bytes = 0, items = 0;
-    if (i < n_rec) {
-        const uint32_t l_seq = (uint32_t)M.l_seq[i];
-        const uint8_t *r = buf + rec_start[i];
-        const uint32_t l_read_name = r[12];
-        bool w = l_read_name > 0 && reads_takes_part((uint32_t)M.flag[i], l_seq, X.exclude_flags, X.mode);
-        if (w && X.n_seg > 0) w = reads_meets_segment(X.tid, X.lo, X.hi, X.n_seg, M.tid[i], M.pos[i], end_in[i]);
-        if (w && X.n_names > 0) w = reads_name_listed(X.names, X.name_off, X.n_names, r + 36, l_read_name - 1u);
-        if (w && X.mode == READS_AS_RECORDS) {
-            bytes = reads_record_bytes(ld32(r));
-            items = (bytes + READS_COPY_SLICE - 1) / READS_COPY_SLICE;
-        } else if (w) {
-            bytes = reads_text_bytes(l_seq, l_read_name);
-            items = ((long long)l_seq + READS_SLICE - 1) / READS_SLICE;
-        }
-    }
-    out_len[i] = bytes;
-    n_items[i] = items;
-}
-
-// The 16 bytes buf[p .. p + 16) for any p, from the two aligned 16-byte chunks that cover them (the second one is the first one
-// of the lane that makes the next 16 characters: the same or the next cache line, served by the L1).  A chunk that does not lie
-// inside [0, buf_bytes) reads as zeros: only the windows of an item's edge chunks reach outside the record, with bytes that are
-// not used.
-__device__ __forceinline__ uint4 reads_window(const uint8_t *__restrict__ buf, long long p, long long buf_bytes) {
-    const long long base = p & ~15ll;
-    uint4 lo = make_uint4(0u, 0u, 0u, 0u), hi = lo;
-    if (base >= 0 && base + 16 <= buf_bytes) lo = *reinterpret_cast<const uint4 *>(buf + base);
-    if (base + 16 >= 0 && base + 32 <= buf_bytes) hi = *reinterpret_cast<const uint4 *>(buf + base + 16);
-    const uint32_t sh = (uint32_t)(p & 15);
-    uint32_t d0 = lo.x, d1 = lo.y, d2 = lo.z, d3 = lo.w, d4 = hi.x, d5 = hi.y, d6 = hi.z, d7 = hi.w;
-    if (sh & 8u) { d0 = d2; d1 = d3; d2 = d4; d3 = d5; d4 = d6; d5 = d7; }
-    if (sh & 4u) { d0 = d1; d1 = d2; d2 = d3; d3 = d4; d4 = d5; }
-    const uint32_t bs = (sh & 3u) * 8u;
-    return make_uint4(__builtin_amdgcn_alignbit(d1, d0, bs), __builtin_amdgcn_alignbit(d2, d1, bs), __builtin_amdgcn_alignbit(d3, d2, bs),
-                      __builtin_amdgcn_alignbit(d4, d3, bs));
-}
-
-__device__ __forceinline__ uint4 reads_mirror(uint4 v) {      // the 16 bytes in reverse order
-    return make_uint4(__builtin_bswap32(v.w), __builtin_bswap32(v.z), __builtin_bswap32(v.y), __builtin_bswap32(v.x));
-}
-
-// 16 characters of SEQ.  Forward: of the bases s0 .. s0 + 15, in that order; reverse: of the same bases from s0 + 15 down to s0,
-// complemented.  The nine bytes that hold the bases are read as one big-endian number N whose nibble k (from the top) is base
-// s0 + k - shifted by one nibble when s0 is odd -, so that character t is the table entry of nibble t (forward) or 15 - t
-// (reverse): mirroring the indices is all a reverse-strand record costs.  s0 may be negative or reach behind l_seq in an item's
-// edge chunks; those characters are not stored.
-template <bool REV>
-__device__ __forceinline__ uint4 reads_seq_chunk(const uint8_t *__restrict__ buf, long long seq_at, long long s0, long long buf_bytes) {
-    constexpr unsigned long long T_LO = reads_char_table(0, REV), T_HI = reads_char_table(1, REV);
-    const uint4 v = reads_window(buf, seq_at + (s0 >> 1), buf_bytes);
-    unsigned long long N = ((unsigned long long)__builtin_bswap32(v.x) << 32) | __builtin_bswap32(v.y);
-    if (s0 & 1) N = (N << 4) | ((v.z & 0xffu) >> 4);
-    uint32_t w[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-    for (int t = 0; t < 16; ++t) {
-        const uint32_t code = (uint32_t)(N >> (REV ? 4 * t : 60 - 4 * t)) & 15u;
-        const uint32_t c = (uint32_t)(((code & 8u) ? T_HI : T_LO) >> ((code & 7u) * 8u)) & 0xffu;
-        w[t >> 2] |= c << (8 * (t & 3));
-    }
-    return make_uint4(w[0], w[1], w[2], w[3]);
-}
-
-__device__ __forceinline__ uint32_t reads_qual_word(uint32_t x) {      // min(q, 93) + 33 on each of the four bytes
-    uint32_t r = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) r |= (uint32_t)reads_qual_char((x >> (8 * k)) & 0xffu) << (8 * k);
-    return r;
-}
-
-// One run of an item's output: the characters [a, b) of a field (SEQ or QUAL) whose character 0 lies at out[origin].  Lane l takes
-// the 16-byte aligned chunks l, l + 64, ... of the output that the run touches: one store instruction of the wave is 1 KiB of
-// consecutive memory.  A chunk that lies inside the run is ONE aligned 16-byte store; the run's first and last chunk, which it may
-// share with a neighbouring item or field, are stored byte by byte, only the run's own bytes.  make(j0) gives the characters
-// j0 .. j0 + 15 of the field.
-template <class Make>
-__device__ __forceinline__ void reads_run(uint8_t *__restrict__ out, long long origin, long long a, long long b, int lane, Make make) {
-    const long long c0 = (origin + a) >> 4, c1 = (origin + b - 1) >> 4;
-    for (long long c = c0 + lane; c <= c1; c += WAVE) {
-        const long long j0 = 16 * c - origin;
-        const uint4 v = make(j0);
-        if (j0 >= a && j0 + 16 <= b) {
-            *reinterpret_cast<uint4 *>(out + 16 * c) = v;
-        } else {
-            const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int t = 0; t < 16; ++t)
-                if (j0 + t >= a && j0 + t < b) out[16 * c + t] = (uint8_t)(w[t >> 2] >> (8 * (t & 3)));
-        }
-    }
-}
-
-// One wave per work item (one-wave workgroups, grid-stride, no LDS): the bases [k * READS_SLICE, (k + 1) * READS_SLICE) of a
-// written record - their SEQ characters and their QUAL characters, two runs of the record's text at out_off[i].  Item 0 also
-// writes what is not a base: `@`, the name, and the three line ends.  With flag 0x10 character j of either field comes from base
-// l_seq - 1 - j: the source window of a chunk is the mirrored one, read once - no second pass.  Every output byte has exactly
-// one writer (the items of a record split [0, l_seq), the records split the text): no atomics.
-__global__ __launch_bounds__(WAVE) void k_bam_reads_emit(const uint8_t *__restrict__ buf, long long buf_bytes, const long long *__restrict__ rec_start,
-                                                         long long n_rec, MetaArrays M, const long long *__restrict__ item_off,
-                                                         const long long *__restrict__ out_off, uint8_t *__restrict__ out) {
-    const int lane = threadIdx.x;
-    const long long total = item_off[n_rec];
-    for (long long w = blockIdx.x; w < total; w += gridDim.x) {
-        const long long i = item_record(item_off, n_rec, w);
-        const long long l_seq = (long long)(uint32_t)M.l_seq[i];
-        const long long rs = rec_start[i];
-        const uint8_t *r = buf + rs;
-        const long long l_read_name = r[12];
-        const bool rev = (ld16(r + 18) & 0x10u) != 0;
-        const long long seq_at = M.seq_src[i], qual_at = seq_at + (l_seq + 1) / 2;
-        const bool has_qual = buf[qual_at] != 0xff;
-        const long long at = out_off[i];
-        const long long seq_origin = at + l_read_name + 1, qual_origin = seq_origin + l_seq + 3;
-        const long long k = w - item_off[i], a = k * READS_SLICE, b = min(l_seq, a + READS_SLICE);
-        if (k == 0) {
-            uint8_t *o = out + at;
-            for (long long j = lane; j < l_read_name - 1; j += WAVE) o[1 + j] = r[36 + j];
-            if (lane == 0) {
-                o[0] = '@';
-                o[l_read_name] = '\n';
-                out[seq_origin + l_seq] = '\n'; out[seq_origin + l_seq + 1] = '+'; out[seq_origin + l_seq + 2] = '\n';
-                out[qual_origin + l_seq] = '\n';
-            }
-        }
-        if (rev) reads_run(out, seq_origin, a, b, lane, [&](long long j0) { return reads_seq_chunk<true>(buf, seq_at, l_seq - 16 - j0, buf_bytes); });
-        else reads_run(out, seq_origin, a, b, lane, [&](long long j0) { return reads_seq_chunk<false>(buf, seq_at, j0, buf_bytes); });
-        reads_run(out, qual_origin, a, b, lane, [&](long long j0) {
-            if (!has_qual) return make_uint4(0x22222222u, 0x22222222u, 0x22222222u, 0x22222222u);
-            uint4 v = reads_window(buf, qual_at + (rev ? l_seq - 16 - j0 : j0), buf_bytes);
-            if (rev) v = reads_mirror(v);
-            return make_uint4(reads_qual_word(v.x), reads_qual_word(v.y), reads_qual_word(v.z), reads_qual_word(v.w));
-        });
-    }
-}
-
-// One wave per work item (one-wave workgroups, grid-stride, no LDS), mode READS_AS_RECORDS: the bytes [k * READS_COPY_SLICE,
-// (k + 1) * READS_COPY_SLICE) of a written record - block_size word first - go from buf + rec_start[i] to out + out_off[i] as
-// they stand.  Source and destination have byte alignments of their own: a lane takes an aligned 16-byte chunk of the OUTPUT,
-// filled from the two aligned source chunks that cover it (reads_window) and stored as one uint4; the item's first and last
-// chunk, which it may share with the neighbouring item or record, are stored byte by byte, only the item's own bytes
-// (reads_run).  Every output byte has exactly one writer (the items split the record, the records split the output): no atomics.
-__global__ __launch_bounds__(WAVE) void k_bam_reads_copy(const uint8_t *__restrict__ buf, long long buf_bytes, const long long *__restrict__ rec_start,
-                                                         long long n_rec, const long long *__restrict__ item_off,
-                                                         const long long *__restrict__ out_off, uint8_t *__restrict__ out) {
-    const int lane = threadIdx.x;
-    const long long total = item_off[n_rec];
-    for (long long w = blockIdx.x; w < total; w += gridDim.x) {
-        const long long i = item_record(item_off, n_rec, w);
-        const long long rs = rec_start[i], at = out_off[i], bytes = out_off[i + 1] - at;
-        const long long a = (w - item_off[i]) * READS_COPY_SLICE, b = min(bytes, a + READS_COPY_SLICE);
-        reads_run(out, at, a, b, lane, [&](long long j0) { return reads_window(buf, rs + j0, buf_bytes); });
-    }
-}
-
-// Coordinate order (reads_order = 1 of a records request): between the plan and the scans the batch's records are sorted by
-// reads_sort_key - hipcub's radix sort of (key, ordinal), stable, so records with equal keys keep their file order - and
-// everything behind works on sorted positions: position j holds record ord[j].  All three kernels are one-wave workgroups
-// (DESIGN.md §10 (vi)).
-// One thread per record: its key from the fixed fields k_bam_meta left, and its ordinal.
-__global__ __launch_bounds__(WAVE) void k_bam_sort_keys(long long n_rec, MetaArrays M, unsigned long long *__restrict__ key, uint32_t *__restrict__ ord) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_rec) return;
-    key[i] = reads_sort_key(M.tid[i], M.pos[i], (uint32_t)M.flag[i]);
-    ord[i] = (uint32_t)i;
-}
-
-// One thread per sorted position: the plan's out_len / n_items of the record that sorts there (0 for a record that is not
-// written, wherever it sorts); slot n_rec, the scans' extra entry, is 0.
-__global__ __launch_bounds__(WAVE) void k_bam_sort_permute(long long n_rec, const uint32_t *__restrict__ ord, const long long *__restrict__ out_len,
-                                                           const long long *__restrict__ n_items, long long *__restrict__ sorted_len,
-                                                           long long *__restrict__ sorted_items) {
-    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j > n_rec) return;
-    const long long i = j < n_rec ? (long long)ord[j] : n_rec;
-    sorted_len[j] = j < n_rec ? out_len[i] : 0;
-    sorted_items[j] = j < n_rec ? n_items[i] : 0;
-}
-
-// k_bam_reads_copy for sorted positions (same launch shape, same work items of READS_COPY_SLICE bytes): item_off / out_off are
-// the scans over the PERMUTED arrays, so work item w belongs to sorted position j, whose bytes come from record ord[j].  Every
-// output byte still has exactly one writer (the items split the record, the sorted positions split the output): no atomics.
-__global__ __launch_bounds__(WAVE) void k_bam_reads_copy_sorted(const uint8_t *__restrict__ buf, long long buf_bytes, const long long *__restrict__ rec_start,
-                                                                long long n_rec, const uint32_t *__restrict__ ord,
-                                                                const long long *__restrict__ item_off, const long long *__restrict__ out_off,
-                                                                uint8_t *__restrict__ out) {
-    const int lane = threadIdx.x;
-    const long long total = item_off[n_rec];
-    for (long long w = blockIdx.x; w < total; w += gridDim.x) {
-        const long long j = item_record(item_off, n_rec, w);
-        const long long rs = rec_start[ord[j]], at = out_off[j], bytes = out_off[j + 1] - at;
-        const long long a = (w - item_off[j]) * READS_COPY_SLICE, b = min(bytes, a + READS_COPY_SLICE);
-        reads_run(out, at, a, b, lane, [&](long long j0) { return reads_window(buf, rs + j0, buf_bytes); });
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// K_index: what a batch contributes to the BAI index of the file (want_index; IndexPartial in coral_bam_common.h)
-// ---------------------------------------------------------------------------------------------
-struct IndexDev {                        // device arrays of the request, carved from the caller's workspace
-    unsigned long long *lin;             // linear index: smallest virtual offset per (contig, 16 384-base window), ~0 = none
-    long long *lin_off;                  // n_ref + 1: first window of every contig
-    unsigned long long *n_mapped, *n_unmapped, *n_no_coor;      // n_ref, n_ref, 1 counters
-    unsigned long long *state;           // [2]: virtual offset of the position a batch ends at (read by the next batch: the
-                                         // start of the record it carries in), alternating
-    int32_t *unsorted;                   // set when a record sorts in front of its predecessor
-    int n_ref;
-};
-
-// virtual offset of byte `rel` of the batch's inflated bytes: the block that holds it (the last one that starts at or in front
-// of it: an empty block starts where its successor does); behind the batch's last byte the block that follows it (bgzf_tell)
-__device__ __forceinline__ unsigned long long batch_voffset(const BlockDesc *__restrict__ desc, const uint32_t *__restrict__ boff, int n_blocks,
-                                                            unsigned long long file_off, unsigned long long comp_bytes, long long rel,
-                                                            long long infl_bytes) {
-    if (rel < infl_bytes) {
-        int a = 0, b = n_blocks;                                   // the last block with dst_off <= rel
-        while (b - a > 1) {
-            const int m = (a + b) >> 1;
-            if ((long long)desc[m].dst_off <= rel) a = m; else b = m;
-        }
-        return ((file_off + boff[a]) << 16) | (unsigned long long)(rel - (long long)desc[a].dst_off);
-    }
-    int a = 0, b = n_blocks;                                       // the first block with dst_off >= rel
-    while (a < b) {
-        const int m = (a + b) >> 1;
-        if ((long long)desc[m].dst_off < rel) a = m + 1; else b = m;
-    }
-    return (a < n_blocks ? file_off + boff[a] : file_off + comp_bytes) << 16;
-}
-
-__device__ __forceinline__ long long index_key(int32_t tid, int32_t pos, int32_t end, int n_ref, long long *beg_out, long long *end_out) {
-    if (tid < 0 || tid >= n_ref) return -1;
-    const long long b = pos < 0 ? 0 : pos, e = (long long)end > b ? (long long)end : b + 1, l = e - 1;
-    *beg_out = b;
-    *end_out = e;
-    int bin = 0;
-    if (b >> 14 == l >> 14) bin = (int)(4681 + (b >> 14));
-    else if (b >> 17 == l >> 17) bin = (int)(585 + (b >> 17));
-    else if (b >> 20 == l >> 20) bin = (int)(73 + (b >> 20));
-    else if (b >> 23 == l >> 23) bin = (int)(9 + (b >> 23));
-    else if (b >> 26 == l >> 26) bin = (int)(1 + (b >> 26));
-    return (long long)tid * 65536 + bin;
-}
-
-__device__ __forceinline__ unsigned long long index_sort_word(int32_t tid, int32_t pos) {
-    return tid < 0 ? ~0ull : ((unsigned long long)(uint32_t)tid << 32) | (uint32_t)(pos < 0 ? 0 : pos);
-}
-
-// One thread per record (one-wave workgroups: the kernel runs beside the next batch's inflate), thread n_rec for the batch's end.
-// Record i: virtual offset of its first byte (a record carried in from the previous batch: where it STARTED, state[parity]),
-// key = tid * 65536 + bin, head[i] = 1 when the key differs from its predecessor's (record 0 always: the host joins a run that
-// goes on across batches), 64-bit atomicMin into every linear-index window it overlaps, the per-contig counters (one atomic per
-// wave when the wave's records are on one contig), and the order check against its predecessor.
-__global__ __launch_bounds__(WAVE) void k_bam_index(const long long *__restrict__ rec_start, long long n_rec, MetaArrays M,
-                                                    const int32_t *__restrict__ end_in, const BlockDesc *__restrict__ desc,
-                                                    const uint32_t *__restrict__ boff, int n_blocks, unsigned long long file_off,
-                                                    unsigned long long comp_bytes, long long infl_bytes, long long carry_pos, int parity,
-                                                    IndexDev X, unsigned long long *__restrict__ voff_out, long long *__restrict__ key_out,
-                                                    long long *__restrict__ head_out) {
-    const int lane = threadIdx.x & 63;
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i == n_rec) {
-        head_out[i] = 0;                                               // the scan's extra slot
-        // where the batch ends: the start of the record that is carried into the next batch (or still the one carried into this
-        // one: a record may span several batches), or the place just behind the batch's last record
-        X.state[parity ^ 1] = carry_pos < CARRY_CAP ? X.state[parity]
-                                                    : batch_voffset(desc, boff, n_blocks, file_off, comp_bytes, carry_pos - CARRY_CAP, infl_bytes);
-    }
-    const bool valid = i < n_rec;
-    int32_t tid = -1, flag = 0;
-    if (valid) {
-        const long long x = rec_start[i];
-        const unsigned long long voff = x < CARRY_CAP ? X.state[parity]
-                                                      : batch_voffset(desc, boff, n_blocks, file_off, comp_bytes, x - CARRY_CAP, infl_bytes);
-        tid = M.tid[i];
-        flag = M.flag[i];
-        const int32_t pos = M.pos[i];
-        long long b = 0, e = 0;
-        const long long key = index_key(tid, pos, end_in[i], X.n_ref, &b, &e);
-        bool head = true;
-        if (i > 0) {
-            long long pb, pe;
-            const int32_t ptid = M.tid[i - 1], ppos = M.pos[i - 1];
-            head = index_key(ptid, ppos, end_in[i - 1], X.n_ref, &pb, &pe) != key;
-            if (index_sort_word(tid, pos) < index_sort_word(ptid, ppos)) *X.unsorted = 1;
-        }
-        voff_out[i] = voff;
-        key_out[i] = key;
-        head_out[i] = head ? 1 : 0;
-        if (key >= 0) {
-            const long long w_first = X.lin_off[tid], nw = X.lin_off[tid + 1] - w_first;
-            const long long w0 = min(b >> 14, nw - 1), w1 = min((e - 1) >> 14, nw - 1);
-            for (long long w = w0; w <= w1; ++w) atomicMin(X.lin + w_first + w, voff);
-        } else {
-            tid = -1;
-        }
-    }
-    // counters
-    const unsigned long long act = __ballot(valid);
-    if (act == 0ull) return;
-    const int32_t t0 = __shfl(tid, (int)__builtin_ctzll(act));
-    if (__ballot(valid && tid != t0) == 0ull) {
-        const unsigned long long unm = __ballot(valid && (flag & 4));
-        if (lane == (int)__builtin_ctzll(act)) {
-            if (t0 < 0) atomicAdd(X.n_no_coor, (unsigned long long)__popcll(act));
-            else {
-                if (act & ~unm) atomicAdd(X.n_mapped + t0, (unsigned long long)__popcll(act & ~unm));
-                if (unm) atomicAdd(X.n_unmapped + t0, (unsigned long long)__popcll(unm));
-            }
-        }
-    } else if (valid) {
-        atomicAdd(tid < 0 ? X.n_no_coor : (flag & 4) ? X.n_unmapped + tid : X.n_mapped + tid, 1ull);
-    }
-}
-
-// the heads, compacted in file order: head_off = exclusive prefix sum of head
-__global__ __launch_bounds__(WAVE) void k_bam_index_compact(long long n_rec, const long long *__restrict__ head, const long long *__restrict__ head_off,
-                                                            const unsigned long long *__restrict__ voff, const long long *__restrict__ key,
-                                                            unsigned long long *__restrict__ voff_out, long long *__restrict__ key_out) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_rec || !head[i]) return;
-    voff_out[head_off[i]] = voff[i];
-    key_out[head_off[i]] = key[i];
-}
-
-// ---------------------------------------------------------------------------------------------
-// K_depth: whole-genome binned read depth (depth_bin of the request; the rules: DepthPartial in coral_bam_common.h)
-// ---------------------------------------------------------------------------------------------
-struct DepthDev {                        // device arrays of the request, carved from the caller's workspace
-    long long *bin_off;                  // n_ref + 1: first bin of every contig
-    int32_t *len;                        // n_ref: LN (>= 0)
-    unsigned long long *bases, *reads;   // n_bins each
-    int n_ref;
-    uint32_t bin, min_mapq, exclude_flags;
-    int count_deletions;
-};
-
-// `key` does not decrease from lane to lane: the sum of `v` over every run of equal keys, in the run's first lane (a segmented
-// suffix sum by doubling; the other lanes of a run hold partial sums).
-__device__ __forceinline__ uint32_t depth_run_sum(uint32_t key, uint32_t v, int lane) {
-    for (int d = 1; d < WAVE; d <<= 1) {
-        const uint32_t tv = __shfl_down(v, d), tk = __shfl_down(key, d);
-        if (lane + d < WAVE && tk == key) v += tv;
-    }
-    return v;
-}
-
-// One wave per record (grid-stride), one-wave workgroups without LDS: it fits beside resident inflate waves.
-// Only the fixed fields and the real CIGAR (M.cig_src / M.n_cigar: the CG tag is resolved) are read.  The wave takes 64 ops at a
-// time; the wave prefix sum of the reference advance gives every lane its op's interval [a, e), clipped to the contig - so no bin
-// at or behind ceil(LN / bin) is ever addressed.  Ops come in increasing reference order, hence the lanes' bins do not decrease:
-//   first bin   every lane adds the part of its op inside the op's first bin b0; lanes with the same b0 are summed in the wave
-//               (an op that is not counted joins the run with 0) and the run's first lane issues ONE no-return 64-bit atomic;
-//   last bin    the same for the part inside the op's last bin b1, for the ops that cross a bin edge (rare unless bin is small);
-//   in between  the whole bins b0 + 1 .. b1 - 1 of such an op get `bin` each, 64 bins per step of the wave.
-// A run's sum fits 32 bits: the positions one record covers are disjoint, so a bin gets at most `bin` from it.
-// Atomics per record: the bins it touches (at most twice each) plus its 64-op chunks - not its ops.
-__global__ __launch_bounds__(WAVE) void k_bam_depth(const uint8_t *__restrict__ buf, long long n_rec, MetaArrays M, DepthDev X) {
-    const int lane = threadIdx.x;
-    const uint32_t bin = X.bin;
-    for (long long i = blockIdx.x; i < n_rec; i += gridDim.x) {
-        const int32_t tid = M.tid[i], pos = M.pos[i];
-        const int n_ops = M.n_cigar[i];
-        if (!depth_takes_part(tid, pos, (uint32_t)n_ops, (uint32_t)M.flag[i], (uint32_t)M.mapq[i], X.n_ref, X.exclude_flags, X.min_mapq)) continue;
-        const long long ln = X.len[tid];
-        if (pos >= ln) continue;                                       // (so ln >= 1 below)
-        const long long bo = X.bin_off[tid];
-        unsigned long long *bases = X.bases + bo;
-        if (lane == 0) atomicAdd(X.reads + bo + (uint32_t)pos / bin, 1ull);
-        const uint8_t *ops = buf + M.cig_src[i];
-        long long r_base = pos;
-        for (int c = 0; c < n_ops && r_base < ln; c += WAVE) {
-            const int kk = c + lane;
-            const uint32_t wd = kk < n_ops ? ld32(ops + 4ll * kk) : 15u;
-            const uint32_t op = wd & 15u;
-            const long long len = (long long)(wd >> 4);
-            const long long ra = ((0x18Du >> op) & 1u) ? len : 0;     // M D N = X advance the reference
-            long long rs = ra;
-            for (int d = 1; d < WAVE; d <<= 1) {
-                const long long t = __shfl_up(rs, d);
-                if (lane >= d) rs += t;
-            }
-            const uint32_t a = (uint32_t)min(r_base + rs - ra, ln), e = (uint32_t)min(r_base + rs, ln);      // 0 <= a <= e <= LN
-            const bool counted = depth_counts_op(op, X.count_deletions != 0) && e > a;
-            const uint32_t b0 = min(a, (uint32_t)ln - 1u) / bin, b1 = (max(e, 1u) - 1u) / bin;               // counted: b0 <= b1 < the contig's bins
-            const unsigned long long edge = ((unsigned long long)b0 + 1ull) * bin;
-            const uint32_t first = counted ? (uint32_t)(min((unsigned long long)e, edge) - a) : 0u;
-            const uint32_t last = counted && b1 > b0 ? (uint32_t)(e - (unsigned long long)b1 * bin) : 0u;
-            {
-                const uint32_t sum = depth_run_sum(b0, first, lane), prev = __shfl_up(b0, 1);
-                if ((lane == 0 || prev != b0) && sum) atomicAdd(bases + b0, (unsigned long long)sum);
-            }
-            if (__ballot(last != 0u) != 0ull) {
-                const uint32_t sum = depth_run_sum(b1, last, lane), prev = __shfl_up(b1, 1);
-                if ((lane == 0 || prev != b1) && sum) atomicAdd(bases + b1, (unsigned long long)sum);
-                unsigned long long m = __ballot(counted && b1 > b0 + 1u);
-                while (m) {
-                    const int j = __builtin_ctzll(m);
-                    m &= m - 1;
-                    const uint32_t k0 = __shfl(b0, j) + 1u, k1 = __shfl(b1, j);
-                    for (uint32_t k = k0 + (uint32_t)lane; k < k1; k += WAVE) atomicAdd(bases + k, (unsigned long long)bin);
-                }
-            }
-            r_base += __shfl(rs, WAVE - 1);
-        }
-    }
-}
+#include "coral_bamgpu_reads.h"
+#include "coral_bamgpu_cov.h"
+#include "coral_bamgpu_qc.h"
+#include "coral_bamgpu_depth.h"
+#include "coral_bamgpu_index.h"
 
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-struct BatchInfo {
-    int n_blocks = 0;
-    uint64_t file_off = 0, comp_bytes = 0, infl_bytes = 0;
-    uint64_t ubase = 0;              // offset of the batch's first inflated byte in this range's uncompressed stream
-    bool has_limit = false;          // the next byte range begins at or in front of this batch's end:
-    long long limit_rel = 0;         //   at this offset from the batch's first inflated byte (negative: in an earlier batch)
-    bool last = false;               // nothing follows (in this span)
-    int span = 0;                    // span decode: which span the batch belongs to, whether it is the span's first batch and
-    bool span_first = false;         //   where in its first block the span's first record starts
-    uint32_t start_off = 0;
-    bool span_tail = false;          // span decode: the batch ends with the span's last own block; what lies behind is only staged
-                                     //   when the parse of this batch says that the span's last record goes on (span_verdict)
-};
-
 struct SpanDef {                     // a span of virtual offsets, taken apart
     uint64_t first_block = 0, end_block = 0;
     uint32_t start_off = 0, end_off = 0;
@@ -1739,268 +1038,6 @@ struct HostJob {
     std::vector<int32_t> na_list;    // (sorted) batch-local ordinals of the records with a non-ACGT code
     std::vector<long long> na_off;   // their bytes in na_raw (n + 1 offsets); a record = its bytes behind block_size
     std::vector<uint8_t> na_raw;
-};
-
-struct Carver {                      // hands the workspace out in 256-byte steps (p == 0: only the size is counted)
-    uintptr_t p;
-    size_t used = 0;
-    void *operator()(size_t n) { used += up256(n); return (void *)(p + used - up256(n)); }
-};
-
-inline bool dev_get(void *dst, const void *src, size_t bytes) { return bytes == 0 || hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) == hipSuccess; }
-
-// The per-record scratch of the parse that a request may WRITE, built in emit.  Why that is safe:
-// - k_bam_emit has finished with every array named here: the batch's host copies synchronised the stream behind it.
-// - The requests are queued on the caller's stream in the order reads, coverage, read QC, binned depth, index, so each runs
-//   behind the one in front.  Binned depth borrows nothing; it reads M.cig_src.
-//   Reads, coverage and read QC use the same two arrays (items, item_off) in turn.  Reads also borrows out_len / out_off, which
-//   nothing behind it but the index uses (and that never rides with it); it has read them back before it returns (its offsets)
-//   and its k_bam_reads_emit, which reads out_off, runs in front of whatever is queued later.  Because M.name_len is `items`,
-//   the reads kernels take a record's l_read_name from its bytes.
-// - The index goes last because its out_key is M.cig_src, which the coverage and the depth walk read.  What every request only READS: the
-//   fixed fields of M (tid .. n_cigar, seq_src), the record starts and the end positions.
-// - All of it is queued in front of ev_parsed and of the next batch's k_bam_meta, which refills the arrays on the same stream.
-struct GpuDecoder;
-struct Borrowed {
-    long long *items, *item_off;                        // reads, then coverage, then read QC (M.name_len, M.sa_len)
-    long long *out_len, *out_off;                       // reads (M.pad_ops, d_cig_off)
-    unsigned long long *voff, *out_voff;                // index (d_cig_off, M.sa_src)
-    long long *key, *head, *head_off, *out_key;         // index (M.pad_ops, d_name_off, d_sa_off, M.cig_src)
-};
-
-inline bool launched(const char *what, std::string &err) {      // behind a request's launches
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) err = std::string(what) + " launch failed: " + hipGetErrorString(e);
-    return e == hipSuccess;
-}
-
-struct CovRequest {                  // window coverage; with per_base the table of a pileup request instead of the counters
-    bool active = false;
-    const CovTable *T = nullptr;     // the request's segments, threshold and callback (Request::cov)
-    CovSegs segs{nullptr, nullptr, nullptr, 0};          // segments and counters in the workspace (n = 0: nothing to count)
-    unsigned long long *counts = nullptr;
-    long long *pile_off = nullptr;   // per_base: the segments' prefix offsets and the table [positions][4]
-    uint32_t *pile = nullptr;
-    void carve(Carver &take) {
-        if (!active) return;
-        const size_t n_seg = T->size();
-        int32_t *seg = (int32_t *)take(3 * n_seg * 4);
-        segs = CovSegs{seg, seg + n_seg, seg + 2 * n_seg, (int)n_seg};
-        counts = (unsigned long long *)take(n_seg * 8);
-        if (!T->per_base) return;
-        pile_off = (long long *)take((n_seg + 1) * 8);
-        pile = (uint32_t *)take((size_t)T->n_pos() * 16);
-    }
-    const char *start(hipError_t &e) const {             // nullptr, or what failed with `e`
-        if (segs.n == 0) return nullptr;
-        const size_t b = T->size() * 4;
-        if ((e = hipMemcpy((void *)segs.tid, T->tid.data(), b, hipMemcpyHostToDevice)) != hipSuccess ||
-            (e = hipMemcpy((void *)segs.lo, T->lo.data(), b, hipMemcpyHostToDevice)) != hipSuccess ||
-            (e = hipMemcpy((void *)segs.hi, T->hi.data(), b, hipMemcpyHostToDevice)) != hipSuccess || (e = hipMemset(counts, 0, 2 * b)) != hipSuccess)
-            return "coverage request set-up";
-        if (T->per_base && ((e = hipMemcpy(pile_off, T->seg_off.data(), (T->size() + 1) * 8, hipMemcpyHostToDevice)) != hipSuccess ||
-                            (T->n_pos() > 0 && (e = hipMemset(pile, 0, (size_t)T->n_pos() * 16)) != hipSuccess)))
-            return "pileup request set-up";
-        return nullptr;
-    }
-    bool batch(GpuDecoder *G, hipStream_t stream, const Borrowed &S, std::string &err) const;      // (behind GpuDecoder)
-    bool finish(Decoded &D) const {
-        if (!active) return true;
-        if (!T->per_base) { D.cov.assign(T->size(), 0); return dev_get(D.cov.data(), counts, T->size() * 8); }
-        D.pileup.assign((size_t)T->n_pos() * 4, 0);      // the table, and the counts per segment as its sums
-        D.has_pileup = true;
-        if (!dev_get(D.pileup.data(), pile, (size_t)T->n_pos() * 16)) return false;
-        pileup_segment_sums(*T, D.pileup.data(), D.cov);
-        return true;
-    }
-};
-
-struct QcRequest {
-    bool active = false;
-    long long *rows = nullptr;                // the batch's qual_sum rows: one array for all batches (collect)
-    unsigned long long *hist = nullptr;       // the device histogram of the whole decode
-    long long pending_n = 0;                  // records of the batch whose rows are still on the device
-    void carve(Carver &take, size_t nr) {
-        if (!active) return;
-        rows = (long long *)take(nr * 8);
-        hist = (unsigned long long *)take(256 * 8);
-    }
-    const char *start(hipError_t &e) const { return active && (e = hipMemset(hist, 0, 256 * 8)) != hipSuccess ? "read-QC request set-up" : nullptr; }
-    bool batch(GpuDecoder *G, hipStream_t stream, const Borrowed &S, std::string &err);
-    // The rows of the batch emitted last, if they are still on the device (the caller has synchronised the stream).  One array
-    // for all batches: that holds only while every emit of a decode and the result call are given the SAME stream: the rows of
-    // batch k-1 are complete once batch k's emit has waited for the stream that batch k-1's kernels were queued on, and batch
-    // k's k_bam_qc_plan is queued only afterwards.
-    bool collect(std::vector<int64_t> &v) {
-        if (pending_n == 0) return true;
-        const size_t base = v.size();
-        v.resize(base + (size_t)pending_n);
-        const bool ok = hipMemcpy(v.data() + base, rows, (size_t)pending_n * 8, hipMemcpyDeviceToHost) == hipSuccess;
-        pending_n = 0;
-        return ok;
-    }
-    bool finish(QcPartial &Q) { return !active || (collect(Q.qual_sum) && dev_get(Q.hist, hist, 256 * 8)); }
-};
-
-struct IndexRequest {
-    bool active = false;
-    IndexDev X{};
-    uint32_t *boff[2] = {nullptr, nullptr};       // per block of the slot's batch: its file offset relative to the batch's
-    BlockDesc *kept_desc[2] = {nullptr, nullptr}; // the slot's block table and offsets, kept for k_bam_index: the feeder re-stages
-    uint32_t *kept_boff[2] = {nullptr, nullptr};  //   d_desc / boff for batch k + 2 while batch k is still being parsed
-    int parity = 0;                               // which X.state the next batch reads
-    void carve(Carver &take, size_t max_blocks, const IndexPartial &P) {      // (everything per record re-uses the batch's scratch)
-        if (!active) return;
-        const size_t n_ref = P.n_mapped.size();
-        for (int i = 0; i < 2; ++i) {
-            boff[i] = (uint32_t *)take(max_blocks * 4);
-            kept_boff[i] = (uint32_t *)take(max_blocks * 4);
-            kept_desc[i] = (BlockDesc *)take(max_blocks * sizeof(BlockDesc));
-        }
-        X.lin = (unsigned long long *)take(P.lin.size() * 8); X.lin_off = (long long *)take((n_ref + 1) * 8);
-        X.n_mapped = (unsigned long long *)take(n_ref * 8); X.n_unmapped = (unsigned long long *)take(n_ref * 8);
-        X.n_no_coor = (unsigned long long *)take(8); X.state = (unsigned long long *)take(16); X.unsorted = (int32_t *)take(4);
-        X.n_ref = (int)n_ref;
-    }
-    // with nothing in front of the first record (rank 0) the first batch's end state is never read; a later rank's first
-    // record is found by search and must start inside its batch (checked in coral_bamgpu_next)
-    const char *start(const IndexPartial &P, hipError_t &e) const {
-        const size_t n_ref = (size_t)X.n_ref;
-        const bool ok = !active || ((e = hipMemset(X.lin, 0xff, P.lin.size() * 8)) == hipSuccess && (e = hipMemset(X.n_mapped, 0, n_ref * 8)) == hipSuccess &&
-                                    (e = hipMemset(X.n_unmapped, 0, n_ref * 8)) == hipSuccess && (e = hipMemset(X.n_no_coor, 0, 8)) == hipSuccess &&
-                                    (e = hipMemset(X.state, 0, 16)) == hipSuccess && (e = hipMemset(X.unsorted, 0, 4)) == hipSuccess &&
-                                    (e = hipMemcpy(X.lin_off, P.lin_off.data(), (n_ref + 1) * 8, hipMemcpyHostToDevice)) == hipSuccess);
-        return ok ? nullptr : "index request set-up";
-    }
-    bool batch(GpuDecoder *G, hipStream_t stream, const Borrowed &S, std::string &err);
-    // false: a copy failed.  Sets P.unsorted when the device saw the order broken; it stays set: no index can be built
-    bool finish(IndexPartial &P) const {
-        if (!active) return true;
-        const size_t n_ref = (size_t)X.n_ref;
-        unsigned long long state[2] = {0, 0}, no_coor = 0;
-        int32_t dev_unsorted = 0;
-        if (!(dev_get(P.lin.data(), X.lin, P.lin.size() * 8) && dev_get(P.n_mapped.data(), X.n_mapped, n_ref * 8) && dev_get(P.n_unmapped.data(), X.n_unmapped, n_ref * 8) &&
-              dev_get(&no_coor, X.n_no_coor, 8) && dev_get(state, X.state, 16) && dev_get(&dev_unsorted, X.unsorted, 4)))
-            return false;
-        if (dev_unsorted) P.unsorted = true;
-        if (!P.unsorted) { P.n_no_coor = (int64_t)no_coor; P.end_voff = state[parity]; }
-        return true;
-    }
-};
-
-struct DepthRequest {                // binned depth: bin_off, the contig lengths and the two int64 tables in the workspace
-    bool active = false;
-    DepthDev X{};
-    size_t n_bins = 0;
-    void carve(Carver &take, const DepthPartial &P) {
-        if (!active) return;
-        const size_t n_ref = P.len.size();
-        n_bins = (size_t)P.n_bins();
-        X.bin_off = (long long *)take((n_ref + 1) * 8);
-        X.len = (int32_t *)take(n_ref * 4);
-        X.bases = (unsigned long long *)take(n_bins * 8);
-        X.reads = (unsigned long long *)take(n_bins * 8);
-        X.n_ref = (int)n_ref;
-        X.bin = (uint32_t)P.bin; X.min_mapq = (uint32_t)P.min_mapq; X.exclude_flags = (uint32_t)P.exclude_flags;
-        X.count_deletions = P.count_deletions ? 1 : 0;
-    }
-    const char *start(const DepthPartial &P, hipError_t &e) const {
-        if (!active) return nullptr;
-        const size_t n_ref = (size_t)X.n_ref;
-        const bool ok = (e = hipMemcpy(X.bin_off, P.bin_off.data(), (n_ref + 1) * 8, hipMemcpyHostToDevice)) == hipSuccess &&
-                        (n_ref == 0 || (e = hipMemcpy(X.len, P.len.data(), n_ref * 4, hipMemcpyHostToDevice)) == hipSuccess) &&
-                        (n_bins == 0 || ((e = hipMemset(X.bases, 0, n_bins * 8)) == hipSuccess && (e = hipMemset(X.reads, 0, n_bins * 8)) == hipSuccess));
-        return ok ? nullptr : "binned-depth request set-up";
-    }
-    bool batch(GpuDecoder *G, hipStream_t stream, std::string &err) const;
-    bool finish(DepthPartial &P) const {
-        if (!active) return true;
-        P.zero_tables();
-        return dev_get(P.bases.data(), X.bases, n_bins * 8) && dev_get(P.reads.data(), X.reads, n_bins * 8);
-    }
-};
-
-struct ReadsRequest {                // FASTQ text, or the own bytes (R->mode), of the selected records
-    bool active = false;
-    const ReadsRule *R = nullptr;    // the request (Request::reads)
-    ReadsDev X{};
-    uint8_t *text = nullptr;         // the batch's text: one buffer for all batches (collect)
-    size_t text_cap = 0, buf_bytes = 0;
-    long long pending_bytes = 0;     // text of the batch emitted last that is still on the device
-    // coordinate order (R->order): the sort's double buffers of keys and ordinals, the permuted plan arrays and hipcub's
-    // temporary storage - carved only for such a request
-    unsigned long long *sort_key[2] = {nullptr, nullptr};
-    uint32_t *sort_ord[2] = {nullptr, nullptr};
-    long long *sorted_len = nullptr, *sorted_items = nullptr;
-    void *sort_tmp = nullptr;
-    size_t sort_tmp_bytes = 0;
-    bool ordered() const { return active && R->order == READS_ORDER_COORDINATE; }
-    // The output buffer is sized by a bound, not by a count: a record of l bases and a name field of n bytes (NUL included) takes
-    // at least 36 + n + 1.5 l bytes of the batch (block_size, the fixed fields, the name, SEQ, QUAL) and its text 2 l + n + 5, and
-    // 2 l + n + 5 <= 4/3 (36 + n + 1.5 l) = 48 + 4/3 n + 2 l.  So the text of all records of a batch fits 4/3 of the batch's bytes,
-    // the carried ones included (+ 256: the division's remainder and room to spare).  In mode READS_AS_RECORDS the written bytes
-    // are a part of the batch's own: one batch's capacity + 256.
-    void carve(Carver &take, size_t batch_cap, size_t nr) {
-        if (!active) return;
-        if (ordered()) {
-            for (int i = 0; i < 2; ++i) { sort_key[i] = (unsigned long long *)take(nr * 8); sort_ord[i] = (uint32_t *)take(nr * 4); }
-            sorted_len = (long long *)take(nr * 8); sorted_items = (long long *)take(nr * 8);
-            sort_tmp = take(sort_tmp_bytes);
-        }
-        buf_bytes = up256(batch_cap + COMP_SLACK);                 // (what d_infl[slot] really has: reads_window's guard)
-        const size_t n_seg = R->tid.size(), n_names = (size_t)R->n_names();
-        int32_t *seg = (int32_t *)take(3 * n_seg * 4);
-        uint8_t *names = (uint8_t *)take(R->names.size());
-        int64_t *off = (int64_t *)take((n_names + 1) * 8);
-        X = ReadsDev{seg, seg + n_seg, seg + 2 * n_seg, names, off, (int)n_seg, (long long)n_names, R->exclude_flags, R->mode};
-        text_cap = (R->mode == READS_AS_RECORDS ? batch_cap : batch_cap / 3 * 4) + 256;
-        text = (uint8_t *)take(text_cap);
-    }
-    const char *start(hipError_t &e) const {
-        if (!active) return nullptr;
-        const size_t b = (size_t)X.n_seg * 4;
-        const bool ok = (b == 0 || ((e = hipMemcpy((void *)X.tid, R->tid.data(), b, hipMemcpyHostToDevice)) == hipSuccess &&
-                                    (e = hipMemcpy((void *)X.lo, R->lo.data(), b, hipMemcpyHostToDevice)) == hipSuccess &&
-                                    (e = hipMemcpy((void *)X.hi, R->hi.data(), b, hipMemcpyHostToDevice)) == hipSuccess)) &&
-                        (X.n_names == 0 || ((e = hipMemcpy((void *)X.names, R->names.data(), R->names.size(), hipMemcpyHostToDevice)) == hipSuccess &&
-                                            (e = hipMemcpy((void *)X.name_off, R->name_off.data(), R->name_off.size() * 8, hipMemcpyHostToDevice)) == hipSuccess));
-        return ok ? nullptr : "reads request set-up";
-    }
-    bool batch(GpuDecoder *G, hipStream_t stream, const Borrowed &S, std::string &err);
-    // The text of the batch emitted last, if it is still on the device (the caller has synchronised the stream).  One buffer for
-    // all batches: QcRequest::collect's argument, under the same condition - every emit of a decode and the result call are
-    // given the SAME stream.
-    bool collect(Decoded &D) {
-        if (pending_bytes == 0) return true;
-        const size_t base = D.reads_text.size();
-        D.reads_text.resize(base + (size_t)pending_bytes);
-        const bool ok = hipMemcpy(D.reads_text.data() + base, text, (size_t)pending_bytes, hipMemcpyDeviceToHost) == hipSuccess;
-        pending_bytes = 0;
-        return ok;
-    }
-    // Coordinate order: every batch left one sorted run (D.reads_runs: the written record it begins at); more than one run goes
-    // through the host's stable k-way merge, run order = batch order, and the runs are freed.
-    bool finish(Decoded &D, int n_threads) {
-        if (!active) return true;
-        D.has_reads = true;
-        if (!collect(D)) return false;
-        if (!ordered() || D.reads_runs.size() < 2) return true;
-        const size_t n_runs = D.reads_runs.size(), n_rec = D.reads_off.size() - 1;
-        std::vector<const uint8_t *> data(n_runs, D.reads_text.data());
-        std::vector<const int64_t *> off(n_runs);
-        std::vector<int64_t> n(n_runs);
-        for (size_t r = 0; r < n_runs; ++r) {
-            off[r] = D.reads_off.data() + D.reads_runs[r];
-            n[r] = (r + 1 < n_runs ? D.reads_runs[r + 1] : (int64_t)n_rec) - D.reads_runs[r];
-        }
-        std::vector<uint8_t> text(D.reads_text.size());
-        std::vector<int64_t> merged(n_rec + 1);
-        if (coral_bam_records_merge((int32_t)n_runs, data.data(), off.data(), n.data(), text.data(), merged.data(), n_threads) != CORAL_OK) return false;
-        D.reads_text.swap(text);
-        D.reads_off.swap(merged);
-        D.reads_runs.assign(1, 0);
-        return true;
-    }
 };
 
 struct GpuDecoder {
@@ -2054,7 +1091,7 @@ struct GpuDecoder {
     bool searching = false, finished = false;
     long long known_start = 0;                // buffer offset of the first record of batch k (CARRY_CAP-based)
     long long carry_len = 0;                  // bytes carried in front of batch k
-    // the batch between next() and emit()
+    // the batch between next() and emit() (cur: from the moment next() takes it from the feeder)
     BatchInfo cur;
     long long cur_n_rec = 0, cur_ops = 0, cur_name_bytes = 0, cur_sa_bytes = 0;
     bool have_cur = false;
@@ -2066,12 +1103,12 @@ struct GpuDecoder {
     bool worker_stop = false, worker_busy = false;
     std::string worker_error;
     long long cur_carry_pos = 0;
-    // the requests that ride along
+    // the requests that ride along (each_request)
+    ReadsRequest reads;
     CovRequest cov;
     QcRequest qc;
-    IndexRequest idx;
     DepthRequest depth;
-    ReadsRequest reads;
+    IndexRequest idx;
     // span decode: the spans are decoded one after the other through the same batches
     std::vector<SpanDef> spans;
     int cur_span = 0;                         // the span the caller's thread is parsing
@@ -2082,13 +1119,10 @@ struct GpuDecoder {
     int64_t fixups = 0, n_batches = 0, na_records = 0;
     std::chrono::steady_clock::time_point t_start;
 
-    // work items of `slice` bytes in the batch between next() and emit(): at most one per record plus one per slice
-    long long max_items(long long slice) const { return cur_n_rec + ((long long)CARRY_CAP + (long long)cur.infl_bytes) / slice + 1; }
-    // exclusive sums of that batch's n + 1 per-record counts (scan inputs, work items, index run heads)
-    bool scan(hipStream_t stream, long long *in, long long *out) {
-        size_t tmp = scan_tmp_bytes;
-        return hipcub::DeviceScan::ExclusiveSum(d_scan_tmp, tmp, in, out, (int)(cur_n_rec + 1), stream) == hipSuccess;
-    }
+    Caps caps() const { return Caps{max_blocks, rec_cap + 1, (size_t)CARRY_CAP + infl_cap}; }
+    Scratch scratch() const { return Scratch{{M.pad_ops, M.name_len, M.sa_len, M.sa_src, d_cig_off, d_name_off, d_sa_off}}; }
+    // the batch between next() and emit()
+    Batch batch(hipStream_t stream) { return Batch{stream, k & 1, d_infl[k & 1], d_rec_start, cur_n_rec, M, d_end, cur, cur_carry_pos, d_scan_tmp, scan_tmp_bytes, D}; }
 
     ~GpuDecoder() {
         {
@@ -2124,129 +1158,14 @@ struct GpuDecoder {
     }
 };
 
-// queued before ev_parsed so that the slot is not inflated into while the kernels read its SEQ and QUAL
-bool CovRequest::batch(GpuDecoder *G, hipStream_t stream, const Borrowed &S, std::string &err) const {
-    const long long n = G->cur_n_rec;
-    const uint8_t *buf = G->d_infl[G->k & 1];
-    if (n == 0 || segs.n == 0) return true;
-    hipLaunchKernelGGL(k_bam_cov_plan, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, stream, buf, n, G->M, G->d_end, segs, T->threshold,
-                       (int)T->filter_all, S.items);
-    if (!G->scan(stream, S.items, S.item_off)) { err = "scan of the coverage work items failed"; return false; }
-    const long long items = G->max_items(COV_SLICE);
-    if (T->per_base)                 // one wave per workgroup, grid-stride beyond 32 per CU
-        hipLaunchKernelGGL(k_bam_pileup, dim3((unsigned)std::min<long long>(items, 8192)), dim3(WAVE), 0, stream, buf, n, G->M, segs, pile_off,
-                           T->threshold, S.item_off, pile);
-    else                             // 4 waves per workgroup, grid-stride beyond
-        hipLaunchKernelGGL(k_bam_cov_count, dim3((unsigned)std::min<long long>((items + 3) / 4, 8192)), dim3(256), 0, stream, buf, n, G->M, segs,
-                           T->threshold, S.item_off, counts);
-    return launched("window coverage", err);
-}
-
-// Nothing is waited for here: the rows are fetched with the next batch's host fields (behind that emit's stream
-// synchronisation, which any kernel queued here is in front of), or by coral_bamgpu_finish.
-bool QcRequest::batch(GpuDecoder *G, hipStream_t stream, const Borrowed &S, std::string &err) {
-    const long long n = G->cur_n_rec;
-    const uint8_t *buf = G->d_infl[G->k & 1];
-    if (n == 0 || !active) return true;
-    hipLaunchKernelGGL(k_bam_qc_plan, dim3((unsigned)((n + 1 + WAVE - 1) / WAVE)), dim3(WAVE), 0, stream, buf, G->d_rec_start, n, G->M, rows, S.items);
-    if (!G->scan(stream, S.items, S.item_off)) { err = "scan of the read-QC work items failed"; return false; }
-    // one wave per workgroup, grid-stride beyond 8 per CU
-    hipLaunchKernelGGL(k_bam_qc, dim3((unsigned)std::min<long long>(G->max_items(QC_SLICE), 2048)), dim3(WAVE), 0, stream, buf, G->d_rec_start, n, G->M, S.item_off,
-                       (unsigned long long *)rows, hist);
-    if (!launched("read-QC", err)) return false;
-    pending_n = n;
-    return true;
-}
-
-// The reads request goes FIRST behind the batch's host copies: it waits for its own totals (16 bytes: no read-back of the batch
-// lies behind these kernels, so they are a small copy of their own, as k_bam_keep_compact's count is), and in front of the other
-// requests that wait is only for its plan kernel and two scans.  The text itself is not waited for (collect).
-bool ReadsRequest::batch(GpuDecoder *G, hipStream_t stream, const Borrowed &S, std::string &err) {
-    if (!active) return true;
-    if (!collect(G->D)) { err = "copy of the reads text failed"; return false; }      // (of the batch in front: its kernels have run, ours are not queued yet)
-    const long long n = G->cur_n_rec;
-    if (n == 0) return true;
-    const uint8_t *buf = G->d_infl[G->k & 1];
-    hipLaunchKernelGGL(k_bam_reads_plan, dim3((unsigned)((n + 1 + WAVE - 1) / WAVE)), dim3(WAVE), 0, stream, buf, G->d_rec_start, n, G->M, G->d_end, X,
-                       S.out_len, S.items);
-    const uint32_t *ord = nullptr;                   // coordinate order: sorted position -> record of the batch
-    if (ordered()) {
-        hipLaunchKernelGGL(k_bam_sort_keys, dim3((unsigned)((n + WAVE - 1) / WAVE)), dim3(WAVE), 0, stream, n, G->M, sort_key[0], sort_ord[0]);
-        hipcub::DoubleBuffer<unsigned long long> keys(sort_key[0], sort_key[1]);
-        hipcub::DoubleBuffer<uint32_t> ords(sort_ord[0], sort_ord[1]);
-        size_t need = 0, tmp = sort_tmp_bytes;           // (the storage was sized for the largest batch: checked, not assumed)
-        if (hipcub::DeviceRadixSort::SortPairs(nullptr, need, keys, ords, (int)n, 0, 64, stream) != hipSuccess || need > sort_tmp_bytes ||
-            hipcub::DeviceRadixSort::SortPairs(sort_tmp, tmp, keys, ords, (int)n, 0, 64, stream) != hipSuccess) {
-            err = "sort of the reads keys failed";
-            return false;
-        }
-        ord = ords.Current();
-        hipLaunchKernelGGL(k_bam_sort_permute, dim3((unsigned)((n + 1 + WAVE - 1) / WAVE)), dim3(WAVE), 0, stream, n, ord, S.out_len, S.items, sorted_len,
-                           sorted_items);
-        if (!G->scan(stream, sorted_len, S.out_off) || !G->scan(stream, sorted_items, S.item_off)) { err = "scan of the sorted reads work items failed"; return false; }
-        G->D.reads_runs.push_back((int64_t)G->D.reads_off.size() - 1);      // this batch's run begins behind what is written
-    } else if (!G->scan(stream, S.out_len, S.out_off) || !G->scan(stream, S.items, S.item_off)) { err = "scan of the reads work items failed"; return false; }
-    std::vector<long long> off((size_t)n + 1);
-    long long items = 0;
-    if (hipMemcpyAsync(off.data(), S.out_off, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, stream) != hipSuccess ||
-        hipMemcpyAsync(&items, S.item_off + n, 8, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) {
-        err = std::string("reads plan failed: ") + hipGetErrorString(hipGetLastError());
-        return false;
-    }
-    const long long bytes = off[(size_t)n];
-    if (bytes < 0 || (size_t)bytes > text_cap || items < 0) { err = "reads request: the batch's text does not fit its buffer"; return false; }
-    if (bytes == 0) return true;                     // no record of the batch is written: nothing more is queued
-    const int64_t base = G->D.reads_off.back();
-    for (long long i = 0; i < n; ++i)
-        if (off[(size_t)i + 1] > off[(size_t)i]) G->D.reads_off.push_back(base + off[(size_t)i + 1]);
-    // one wave per workgroup, grid-stride beyond 8 per CU
-    const dim3 grid((unsigned)std::min<long long>(items, 2048));
-    if (ord)
-        hipLaunchKernelGGL(k_bam_reads_copy_sorted, grid, dim3(WAVE), 0, stream, buf, (long long)buf_bytes, G->d_rec_start, n, ord, S.item_off, S.out_off, text);
-    else if (X.mode == READS_AS_RECORDS)
-        hipLaunchKernelGGL(k_bam_reads_copy, grid, dim3(WAVE), 0, stream, buf, (long long)buf_bytes, G->d_rec_start, n, S.item_off, S.out_off, text);
-    else
-        hipLaunchKernelGGL(k_bam_reads_emit, grid, dim3(WAVE), 0, stream, buf, (long long)buf_bytes, G->d_rec_start, n, G->M, S.item_off, S.out_off, text);
-    if (!launched("reads", err)) return false;
-    pending_bytes = bytes;
-    return true;
-}
-
-// reads the slot's CIGAR bytes (M.cig_src: in front of the index request, which borrows that array)
-bool DepthRequest::batch(GpuDecoder *G, hipStream_t stream, std::string &err) const {
-    const long long n = G->cur_n_rec;
-    if (n == 0 || !active || n_bins == 0) return true;
-    // one wave per workgroup, grid-stride beyond 32 per CU
-    hipLaunchKernelGGL(k_bam_depth, dim3((unsigned)std::min<long long>(n, 8192)), dim3(WAVE), 0, stream, G->d_infl[G->k & 1], n, G->M, X);
-    return launched("binned depth", err);
-}
-
-// the batch's part of the index; also for a batch without records: the end state it leaves is the next batch's start
-bool IndexRequest::batch(GpuDecoder *G, hipStream_t stream, const Borrowed &S, std::string &err) {
-    const long long n = G->cur_n_rec;
-    if (!active) return true;
-    hipLaunchKernelGGL(k_bam_index, dim3((unsigned)((n + 1 + WAVE - 1) / WAVE)), dim3(WAVE), 0, stream, G->d_rec_start, n, G->M, G->d_end, kept_desc[G->k & 1],
-                       kept_boff[G->k & 1], G->cur.n_blocks, (unsigned long long)G->cur.file_off, (unsigned long long)G->cur.comp_bytes,
-                       (long long)G->cur.infl_bytes, G->cur_carry_pos, parity, X, S.voff, S.key, S.head);
-    parity ^= 1;
-    long long n_heads = 0;
-    if (n > 0) {
-        if (!G->scan(stream, S.head, S.head_off)) { err = "scan of the index run heads failed"; return false; }
-        hipLaunchKernelGGL(k_bam_index_compact, dim3((unsigned)((n + WAVE - 1) / WAVE)), dim3(WAVE), 0, stream, n, S.head, S.head_off, S.voff, S.key, S.out_voff,
-                           S.out_key);
-        if (hipMemcpyAsync(&n_heads, S.head_off + n, 8, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) {
-            err = std::string("index kernels failed: ") + hipGetErrorString(hipGetLastError());
-            return false;
-        }
-        std::vector<long long> hk((size_t)n_heads);
-        std::vector<unsigned long long> hv((size_t)n_heads);
-        if (!dev_get(hk.data(), S.out_key, (size_t)n_heads * 8) || !dev_get(hv.data(), S.out_voff, (size_t)n_heads * 8)) {
-            err = "copy of the index run heads failed";
-            return false;
-        }
-        for (long long j = 0; j < n_heads; ++j) G->D.idx.add_head(hk[(size_t)j], hv[(size_t)j]);
-    }
-    return launched("index", err);
+// The five requests, named once, in the order their kernels are queued per batch; open, carve, start and finish go through the
+// same list.  Reads goes first: it alone waits for a read-back of its own (its offsets and totals), which is then a wait for its
+// plan kernel and two scans only.  f says whether to go on; each_request says whether f did for all five.
+// Only the active ones are visited, unless `all` (open, which is what activates them).
+template <class F>
+bool each_request(GpuDecoder *G, F f, bool all = false) {
+    auto go = [&](auto &r) { return !(all || r.active) || f(r); };
+    return go(G->reads) && go(G->cov) && go(G->qc) && go(G->depth) && go(G->idx);
 }
 
 // parallel pread of [off, off + n) into dst
@@ -2530,11 +1449,7 @@ bool carve(GpuDecoder *G, void *ws, size_t bytes) {
     G->names_cap = G->sa_cap = (size_t)CARRY_CAP + G->infl_cap;
     G->d_names = (uint8_t *)take(G->names_cap);
     G->d_sa_text = (uint8_t *)take(G->sa_cap);
-    G->idx.carve(take, G->max_blocks, G->D.idx);
-    G->qc.carve(take, nr);
-    G->cov.carve(take);
-    G->depth.carve(take, G->D.depth);
-    G->reads.carve(take, (size_t)CARRY_CAP + G->infl_cap, nr);
+    each_request(G, [&](auto &r) { r.carve(take, G->caps(), G->D); return true; });
     if (ws && take.used > bytes) return false;
     G->ws_bytes = take.used;
     return true;
@@ -2591,15 +1506,240 @@ bool wait_staged(GpuDecoder *G, int kb, BatchInfo *bi) {
     return true;
 }
 
-const char *rec_error_text(int e) {
-    switch (e) {
-        case REC_ERR_SHORT: return "record shorter than its fixed fields";
-        case REC_ERR_FIELDS: return "record fields overrun the record";
-        case REC_ERR_TAG_B: return "truncated B tag";
-        case REC_ERR_TAG_TYPE: return "unknown tag type";
-        case REC_ERR_TAG_OVERRUN: return "tag overruns the record";
+int fail(int code, const std::string &msg) { set_error(msg); return code; }
+int failed(GpuDecoder *G, int code, std::string msg) { G->error = std::move(msg); return code; }      // (coral_bamgpu_next reports G->error)
+
+// Batch k is done with its slot: the buffer may be inflated into again (batch k + 2) once everything queued on `stream` so far has
+// run.  On to batch k + 1.
+bool release_slot(GpuDecoder *G, hipStream_t stream) {
+    if (hipEventRecord(G->ev_parsed[G->k & 1], stream) != hipSuccess) return false;
+    {
+        std::lock_guard<std::mutex> lk(G->m);
+        ++G->emitted;
     }
-    return "malformed record";
+    G->cv.notify_all();
+    ++G->k;
+    return true;
+}
+
+const char *cut_short(const GpuDecoder *G) { return G->last_rank ? "truncated record at the end of the file" : "a record straddles further than the supported overhang"; }
+
+// ---- the steps of coral_bamgpu_next, in its order: each returns CORAL_OK, or a code with G->error set -------------------------
+// Batch k once it is staged and its inflate queued; batches of overhang blocks behind a span that is done are skipped.
+// When no batch is left the decode is finished (G->finished).
+int take_staged_batch(GpuDecoder *G, hipStream_t stream) {
+    BatchInfo &bi = G->cur;
+    for (;;) {
+        if (!wait_staged(G, G->k, &bi)) {
+            if (!G->error.empty()) return CORAL_ERR_FORMAT;
+            if (G->carry_len > 0 && !G->searching) return failed(G, CORAL_ERR_FORMAT, cut_short(G));
+            G->finished = true;
+            return CORAL_OK;
+        }
+        {   // the feeder enqueues the inflate of a batch right after staging it
+            const int kw = G->k;
+            std::unique_lock<std::mutex> lk(G->m);
+            G->cv.wait(lk, [&] { return G->inflate_launched > kw || !G->feeder_error.empty(); });
+            if (G->inflate_launched <= kw) return failed(G, CORAL_ERR_HIP, G->feeder_error);
+        }
+        if (!G->req.span_mode || bi.span >= G->cur_span) break;
+        // a batch of overhang blocks behind a span whose last record has been seen already: nothing to parse, the slot is free
+        // again once its inflate has run
+        if (hipStreamWaitEvent(stream, G->ev_infl[G->k & 1], 0) != hipSuccess || !release_slot(G, stream)) return failed(G, CORAL_ERR_HIP, "hipEventRecord failed");
+    }
+    if (G->req.span_mode) {
+        if (bi.span > G->cur_span) {             // the span in front ran out of blocks without reaching its end
+            if (G->carry_len > 0) return failed(G, CORAL_ERR_FORMAT, "a record straddles further than the supported overhang");
+            G->cur_span = bi.span;
+        }
+        if (bi.span_first) {                     // the span's first record: at a known place, nothing carried, nothing searched
+            G->known_start = CARRY_CAP + (long long)bi.start_off;
+            G->carry_len = 0;
+            G->searching = false;
+        }
+    }
+    return CORAL_OK;
+}
+
+// The batch's record boundaries (k_bam_find, k_bam_verify) and the status of its blocks; what the walk found becomes the batch
+// between next() and emit() (G->cur, cur_n_rec, cur_carry_pos), and k_bam_starts is queued.  carry_pos: where the walk's last whole
+// record ends; done: the byte range (or span) has no further record.
+int walk_boundaries(GpuDecoder *G, hipStream_t stream, long long &carry_pos, bool &done) {
+    const BatchInfo &bi = G->cur;
+    const int slot = G->k & 1;
+    uint8_t *buf = G->d_infl[slot];
+    // this batch's inflate must be complete before the parse kernels read its bytes
+    if (hipStreamWaitEvent(stream, G->ev_infl[slot], 0) != hipSuccess) return failed(G, CORAL_ERR_HIP, "hipStreamWaitEvent failed");
+    const long long data_end = CARRY_CAP + (long long)bi.infl_bytes;
+    const long long begin = G->searching ? (long long)CARRY_CAP - G->carry_len : std::min(G->known_start, data_end);
+    const long long limit = (G->last_rank || !bi.has_limit) ? (1ll << 62) : (long long)CARRY_CAP + bi.limit_rel;
+    const int seg0 = (int)(begin / SEG_BYTES);
+    const int n_seg = (int)((data_end + SEG_BYTES - 1) / SEG_BYTES) - seg0;
+    const int n_ref = (int)G->D.ref_names.size();
+    long long res[6] = {0, 0, 0, 0, 0, 0};
+    if (n_seg > 0) {
+        hipLaunchKernelGGL(k_bam_find, dim3(n_seg), dim3(WAVE), 0, stream, buf, begin, data_end, limit, n_ref, seg0, n_seg, G->d_seg_first,
+                           G->d_seg_land, G->d_seg_count, G->d_seg_valid);
+        hipLaunchKernelGGL(k_bam_verify, dim3(1), dim3(WAVE), 0, stream, buf, G->searching ? -1ll : G->known_start, begin, data_end, limit, seg0, n_seg,
+                           G->d_seg_first, G->d_seg_land, G->d_seg_count, G->d_seg_valid, G->d_seg_base, G->d_result);
+        const auto t_gpu0 = std::chrono::steady_clock::now();
+        const bool synced = hipMemcpyAsync(res, G->d_result, sizeof(res), hipMemcpyDeviceToHost, stream) == hipSuccess && hipStreamSynchronize(stream) == hipSuccess;
+        G->t_wait_gpu += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_gpu0).count();
+        if (!synced) return failed(G, CORAL_ERR_HIP, std::string("record walk failed: ") + hipGetErrorString(hipGetLastError()));
+    } else {
+        res[1] = G->known_start;
+        if (hipStreamSynchronize(stream) != hipSuccess) return failed(G, CORAL_ERR_HIP, "hipStreamSynchronize failed");
+    }
+    // every block of the batch must have inflated cleanly and have the checksum of its trailer
+    if (hipEventSynchronize(G->ev_crc[slot]) != hipSuccess) return failed(G, CORAL_ERR_HIP, "hipEventSynchronize failed");
+    std::vector<int32_t> st((size_t)bi.n_blocks);
+    if (hipMemcpy(st.data(), G->d_status[slot], st.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return failed(G, CORAL_ERR_HIP, "hipMemcpy failed");
+    int32_t status_bad = 0;
+    for (int32_t s : st) if (s != 0) { status_bad = s; break; }
+    if (status_bad == ERR_CRC) return failed(G, CORAL_ERR_FORMAT, "CRC32 of an inflated BGZF block differs from the one in its trailer");
+    if (status_bad) return failed(G, CORAL_ERR_FORMAT, "inflate failed (corrupt BGZF block), code " + std::to_string(status_bad));
+    if (res[3] == 1) return failed(G, CORAL_ERR_FORMAT, "record shorter than its fixed fields");
+    bool still_searching = false;
+    if (res[3] == 2) {
+        // no confirmed record start in what this byte range has seen so far (the chained check needs three records in a row): keep
+        // the bytes and look again with the next batch behind them, as the host pipeline does; at the end of the range it simply
+        // has no record of its own (it lies inside one record of the previous range)
+        if (data_end - begin > CARRY_CAP) return failed(G, CORAL_ERR_FORMAT, "no record start found in 64 MiB at the beginning of the byte range");
+        res[0] = 0;
+        res[1] = bi.last ? data_end : begin;
+        res[2] = 0;
+        still_searching = !bi.last;
+    }
+    const long long n_rec = res[0];
+    carry_pos = res[1];
+    done = res[2] != 0;
+    // (a byte range that found no record start in its first batch and finds one in the bytes kept from it)
+    if (G->idx.active && G->searching && n_rec > 0 && res[5] < CARRY_CAP)
+        return failed(G, CORAL_ERR_FORMAT, "index request: the first record of the byte range does not start in the batch it was found in");
+    G->cur_carry_pos = std::min(carry_pos, data_end);
+    G->fixups += res[4];
+    if (n_rec > (long long)G->rec_cap) return failed(G, CORAL_ERR_FORMAT, "more records in a batch than its workspace holds");
+    G->searching = still_searching;
+    G->cur_n_rec = n_rec;
+    G->cur_ops = G->cur_name_bytes = G->cur_sa_bytes = 0;
+    if (n_rec > 0) {
+        hipLaunchKernelGGL(k_bam_starts, dim3((n_seg + WAVE - 1) / WAVE), dim3(WAVE), 0, stream, buf, seg0, n_seg, G->d_seg_first, G->d_seg_count, G->d_seg_valid,
+                           G->d_seg_base, G->d_rec_all);
+        (void)hipMemsetAsync(G->d_error, 0, 4, stream);
+    }
+    return CORAL_OK;
+}
+
+// The record filter: from here on the batch's records are the kept ones.  Everything in front (carry_pos, done, the span
+// verdicts: byte positions of the walk) has not seen and does not see the kept count.  The flags and their offsets borrow
+// two arrays k_bam_meta and the scans behind it refill (M.pad_ops, d_cig_off); the kept count comes back on its own
+// (8 bytes + the error word): k_bam_meta's launch and the three scans are sized by it.
+int filter_records(GpuDecoder *G, hipStream_t stream) {
+    const long long n_rec = G->cur_n_rec;
+    if (n_rec == 0 || !G->req.keep.active()) return CORAL_OK;
+    long long *keep = G->M.pad_ops, *keep_off = G->d_cig_off, n_kept = 0;
+    const unsigned grid = (unsigned)((n_rec + 1 + WAVE - 1) / WAVE);
+    hipLaunchKernelGGL(k_bam_keep, dim3(grid), dim3(WAVE), 0, stream, G->d_infl[G->k & 1], G->d_rec_all, n_rec, G->req.keep, keep, G->d_error);
+    // (over every record of the walk + the extra slot)
+    if (!G->batch(stream).scan(keep, keep_off)) return failed(G, CORAL_ERR_HIP, "scan of the record filter's flags failed");
+    hipLaunchKernelGGL(k_bam_keep_compact, dim3(grid), dim3(WAVE), 0, stream, G->d_rec_all, n_rec, keep, keep_off, G->d_rec_start);
+    if (const int rc = fetch_sync(stream, {{&n_kept, keep_off + n_rec, 8}}, G->d_error, "record filter", G->error)) return rc;
+    if (n_kept < 0 || n_kept > n_rec) return failed(G, CORAL_ERR_HIP, "record filter: the kept count is out of range");
+    G->cur_n_rec = n_kept;
+    return CORAL_OK;
+}
+
+// k_bam_meta and the three scans: the sizes of what the batch contributes (cur_ops, cur_name_bytes, cur_sa_bytes)
+int parse_meta(GpuDecoder *G, hipStream_t stream) {
+    const long long n_rec = G->cur_n_rec;
+    if (n_rec == 0) return CORAL_OK;
+    hipLaunchKernelGGL(k_bam_meta, dim3((unsigned)(n_rec + 1)), dim3(WAVE), 0, stream, G->d_infl[G->k & 1], G->d_rec_start, n_rec, G->M, G->d_error);
+    const Batch B = G->batch(stream);
+    if (!B.scan(G->M.pad_ops, G->d_cig_off)) return failed(G, CORAL_ERR_HIP, "scan of the CIGAR op counts failed");
+    if (!B.scan(G->M.name_len, G->d_name_off)) return failed(G, CORAL_ERR_HIP, "scan of the read-name lengths failed");
+    if (!B.scan(G->M.sa_len, G->d_sa_off)) return failed(G, CORAL_ERR_HIP, "scan of the SA text lengths failed");
+    return fetch_sync(stream, {{&G->cur_ops, G->d_cig_off + n_rec, 8}, {&G->cur_name_bytes, G->d_name_off + n_rec, 8}, {&G->cur_sa_bytes, G->d_sa_off + n_rec, 8}},
+                      G->d_error, "record parse", G->error);
+}
+
+// what the next batch starts with: the bytes carried over or the place of its first record, and the span's verdict for the feeder
+int advance_carry(GpuDecoder *G, long long carry_pos, bool done) {
+    const BatchInfo &bi = G->cur;
+    const long long data_end = CARRY_CAP + (long long)bi.infl_bytes;
+    // (a span decode goes on with the next span)
+    auto verdict = [&](int v) {
+        if (!G->req.span_mode) return;
+        {
+            std::lock_guard<std::mutex> lk(G->m);
+            if (G->span_verdict[(size_t)bi.span] == 0) G->span_verdict[(size_t)bi.span] = v;
+        }
+        G->cv.notify_all();
+    };
+    auto range_done = [&]() {
+        G->carry_len = 0;
+        verdict(1);
+        if (G->req.span_mode && G->cur_span + 1 < (int)G->spans.size()) ++G->cur_span; else G->finished = true;
+    };
+    if (done) {
+        range_done();
+    } else if (carry_pos < data_end) {
+        G->carry_len = data_end - carry_pos;
+        if (G->carry_len > CARRY_CAP) return failed(G, CORAL_ERR_FORMAT, "a record larger than 64 MiB straddles two batches");
+        G->known_start = CARRY_CAP - G->carry_len;
+    } else {
+        G->carry_len = 0;
+        G->known_start = CARRY_CAP + (carry_pos - data_end);
+    }
+    if (bi.last && !done) {
+        if (G->carry_len > 0) return failed(G, CORAL_ERR_FORMAT, cut_short(G));
+        range_done();
+    }
+    if (bi.span_tail && !done) verdict(2);     // the feeder stages what lies behind the span's own blocks
+    return CORAL_OK;
+}
+
+// The records of the job with a non-ACGT code, whole, in one gather + one copy (the offset arrays of the scans are free by now).
+int fetch_nonacgt(GpuDecoder *G, hipStream_t stream, HostJob &J, int32_t na_count) {
+    const uint8_t *buf = G->d_infl[G->k & 1];
+    const long long n = J.n;
+    J.na_list.resize((size_t)na_count);
+    std::vector<long long> starts((size_t)n);
+    if (hipMemcpy(J.na_list.data(), G->d_na_list, (size_t)na_count * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(starts.data(), G->d_rec_start, (size_t)n * 8, hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(CORAL_ERR_HIP, "copy of the non-ACGT list failed");
+    std::sort(J.na_list.begin(), J.na_list.end());
+    // a record ends where the next one starts - unless a record filter dropped that one: then its block_size says where
+    std::vector<uint32_t> own_size;
+    if (G->req.keep.active()) {
+        own_size.resize((size_t)na_count);
+        for (int32_t j = 0; j < na_count; ++j)
+            if (hipMemcpy(&own_size[(size_t)j], buf + starts[(size_t)J.na_list[(size_t)j]], 4, hipMemcpyDeviceToHost) != hipSuccess)
+                return fail(CORAL_ERR_HIP, "copy of the non-ACGT list failed");
+    }
+    std::vector<long long> src((size_t)na_count), dst((size_t)na_count), len((size_t)na_count);
+    J.na_off.assign((size_t)na_count + 1, 0);
+    for (int32_t j = 0; j < na_count; ++j) {
+        const int32_t li = J.na_list[(size_t)j];
+        const long long rec_end = !own_size.empty() ? starts[(size_t)li] + 4 + (long long)own_size[(size_t)j]
+                                  : li + 1 < n ? starts[(size_t)li + 1] : G->cur_carry_pos;
+        src[(size_t)j] = starts[(size_t)li] + 4;
+        len[(size_t)j] = rec_end - starts[(size_t)li] - 4;
+        dst[(size_t)j] = J.na_off[(size_t)j];
+        J.na_off[(size_t)j + 1] = J.na_off[(size_t)j] + len[(size_t)j];
+    }
+    const long long total = J.na_off[(size_t)na_count];
+    J.na_raw.resize((size_t)total);
+    if ((size_t)total > G->names_cap) return fail(CORAL_ERR_FORMAT, "records with non-ACGT bases exceed the batch workspace");
+    if (hipMemcpy(G->d_cig_off, src.data(), (size_t)na_count * 8, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(G->d_name_off, dst.data(), (size_t)na_count * 8, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(G->d_sa_off, len.data(), (size_t)na_count * 8, hipMemcpyHostToDevice) != hipSuccess)
+        return fail(CORAL_ERR_HIP, "upload of the non-ACGT gather list failed");
+    hipLaunchKernelGGL(k_bam_gather, dim3((unsigned)na_count), dim3(WAVE), 0, stream, buf, G->d_cig_off, G->d_name_off, G->d_sa_off, (int)na_count,
+                       G->d_names);
+    if (hipMemcpyAsync(J.na_raw.data(), G->d_names, (size_t)total, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess)
+        return fail(CORAL_ERR_HIP, "copy of the records with non-ACGT bases failed");
+    G->na_records += na_count;
+    return CORAL_OK;
 }
 
 }  // namespace
@@ -2649,16 +1789,6 @@ extern "C" int coral_bamgpu_open_request_ordered(const char *path, int32_t n_thr
         G->byte_hi = span_bytes;
         if (G->spans.empty()) G->first_block = G->f.size;
     }
-    G->cov.active = R.has_cov;
-    G->cov.T = &G->req.cov;
-    if ((G->idx.active = R.want_index)) G->D.idx.init(G->D.ref_lens);
-    if ((G->qc.active = R.want_qc)) G->D.qc.init();
-    G->reads.active = R.reads.on;
-    G->reads.R = &G->req.reads;
-    if (R.depth_bin > 0) {                     // the rule that needs the header: at most 2^28 bins (refused here, nothing allocated)
-        if (!G->D.depth.init(R.depth_bin, R.depth_min_mapq, R.depth_exclude_flags, R.depth_count_deletions, G->D.ref_lens, err)) { set_error(err); return CORAL_ERR_ARG; }
-        G->depth.active = true;
-    }
     // batch size: at most `batch_bytes` inflated, no more than the range can need.  Default 2.52 GiB = 6 x 6 912 BGZF blocks of
     // 65 280 bytes (htslib's block size): the inflate kernel keeps 27 one-wave workgroups per CU x 256 CUs resident, blocks of
     // equal size finish in rounds, and a batch that is a whole number of rounds has no part-filled last round; bigger batches
@@ -2677,16 +1807,8 @@ extern "C" int coral_bamgpu_open_request_ordered(const char *path, int32_t n_thr
     size_t tmp = 0;
     (void)hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, (long long *)nullptr, (long long *)nullptr, (int)std::min<size_t>(G->rec_cap + 1, 0x7fffffff));
     G->scan_tmp_bytes = tmp + 256;
-    if (G->reads.ordered()) {                  // the sort's temporary storage, queried once for the largest batch, as the scan's is
-        hipcub::DoubleBuffer<unsigned long long> keys(nullptr, nullptr);
-        hipcub::DoubleBuffer<uint32_t> ords(nullptr, nullptr);
-        size_t sort_tmp = 0;
-        if (hipcub::DeviceRadixSort::SortPairs(nullptr, sort_tmp, keys, ords, (int)std::min<size_t>(G->rec_cap + 1, 0x7fffffff), 0, 64) != hipSuccess) {
-            set_error("coral_bamgpu_open_request_ordered: the size of the sort's temporary storage could not be queried");
-            return CORAL_ERR_HIP;
-        }
-        G->reads.sort_tmp_bytes = sort_tmp + 256;
-    }
+    int rc = CORAL_OK;                         // what rides along: each request takes its part of R (and what of it needs the header or the capacities)
+    if (!each_request(G.get(), [&](auto &r) { return (rc = r.open(R, G->caps(), G->D, err)) == CORAL_OK; }, true)) { set_error(err); return rc; }
     carve(G.get(), nullptr, 0);
     if (const char *fb = getenv("CORAL_BAMGPU_FIRST_BATCH")) G->first_batch = std::max<uint64_t>(1u << 20, strtoull(fb, nullptr, 10));      // tuning
     G->known_start = CARRY_CAP + (long long)(rank == 0 ? G->hdr_bytes : 0);
@@ -2708,9 +1830,8 @@ extern "C" int coral_bamgpu_finish(void *handle, void *stream_) {
     GpuDecoder *G = (GpuDecoder *)handle;
     if (!G) return CORAL_ERR_ARG;
     if (!G->finished || G->have_cur) { set_error("coral_bamgpu_finish: the decode is not finished"); return CORAL_ERR_ARG; }
-    if (!G->cov.active && !G->qc.active && !G->idx.active && !G->depth.active && !G->reads.active) return CORAL_OK;
-    if (hipStreamSynchronize((hipStream_t)stream_) != hipSuccess || !G->cov.finish(G->D) || !G->idx.finish(G->D.idx) || !G->qc.finish(G->D.qc) ||
-        !G->depth.finish(G->D.depth) || !G->reads.finish(G->D, G->n_threads)) {
+    if (each_request(G, [](auto &) { return false; })) return CORAL_OK;      // nothing rides along
+    if (hipStreamSynchronize((hipStream_t)stream_) != hipSuccess || !each_request(G, [&](auto &r) { return r.finish(G->D, G->n_threads); })) {
         set_error("coral_bamgpu_finish: copy of the requested results failed");
         return CORAL_ERR_HIP;
     }
@@ -2750,8 +1871,8 @@ extern "C" int coral_bamgpu_start(void *handle, void *workspace, int64_t workspa
     }
     if ((e = hipStreamCreateWithFlags(&G->s_crc, hipStreamNonBlocking)) != hipSuccess) return bad("hipStreamCreate", e);
     G->t_alloc = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_alloc0).count();
-    const char *what;
-    if ((what = G->idx.start(G->D.idx, e)) || (what = G->qc.start(e)) || (what = G->cov.start(e)) || (what = G->depth.start(G->D.depth, e)) || (what = G->reads.start(e))) return bad(what, e);
+    const char *what = nullptr;
+    if (!each_request(G, [&](auto &r) { return !(what = r.start(G->D, e)); })) return bad(what, e);
     G->feeder = std::thread(feeder_main, G);
     G->worker = std::thread(worker_main, G);
     return CORAL_OK;
@@ -2765,196 +1886,19 @@ extern "C" int coral_bamgpu_next(void *handle, int64_t out[4], void *stream_) {
     if (!G || !out) return CORAL_ERR_ARG;
     out[0] = out[1] = out[2] = out[3] = 0;
     if (G->have_cur) { set_error("coral_bamgpu_next: the previous batch has not been emitted"); return CORAL_ERR_ARG; }
-    auto fail = [&](int code) {
-        set_error(G->error);
-        return code;
-    };
     if (G->finished) return CORAL_OK;
-    BatchInfo bi;
-    for (;;) {
-        if (!wait_staged(G, G->k, &bi)) {
-            if (!G->error.empty()) return fail(CORAL_ERR_FORMAT);
-            if (G->carry_len > 0 && !G->searching) { G->error = G->last_rank ? "truncated record at the end of the file" : "a record straddles further than the supported overhang"; return fail(CORAL_ERR_FORMAT); }
-            G->finished = true;
-            return CORAL_OK;
-        }
-        {   // the feeder enqueues the inflate of a batch right after staging it
-            const int kw = G->k;
-            std::unique_lock<std::mutex> lk(G->m);
-            G->cv.wait(lk, [&] { return G->inflate_launched > kw || !G->feeder_error.empty(); });
-            if (G->inflate_launched <= kw) { G->error = G->feeder_error; return fail(CORAL_ERR_HIP); }
-        }
-        if (!G->req.span_mode || bi.span >= G->cur_span) break;
-        // a batch of overhang blocks behind a span whose last record has been seen already: nothing to parse, the slot is free
-        // again once its inflate has run
-        const int sl = G->k & 1;
-        if (hipStreamWaitEvent(stream, G->ev_infl[sl], 0) != hipSuccess || hipEventRecord(G->ev_parsed[sl], stream) != hipSuccess) {
-            G->error = "hipEventRecord failed";
-            return fail(CORAL_ERR_HIP);
-        }
-        {
-            std::lock_guard<std::mutex> lk(G->m);
-            ++G->emitted;
-        }
-        G->cv.notify_all();
-        ++G->k;
-    }
-    if (G->req.span_mode) {
-        if (bi.span > G->cur_span) {             // the span in front ran out of blocks without reaching its end
-            if (G->carry_len > 0) { G->error = "a record straddles further than the supported overhang"; return fail(CORAL_ERR_FORMAT); }
-            G->cur_span = bi.span;
-        }
-        if (bi.span_first) {                     // the span's first record: at a known place, nothing carried, nothing searched
-            G->known_start = CARRY_CAP + (long long)bi.start_off;
-            G->carry_len = 0;
-            G->searching = false;
-        }
-    }
-    const int kb = G->k, slot = kb & 1;
-    uint8_t *buf = G->d_infl[slot];
-    // this batch's inflate must be complete before the parse kernels read its bytes
-    if (hipStreamWaitEvent(stream, G->ev_infl[slot], 0) != hipSuccess) { G->error = "hipStreamWaitEvent failed"; return fail(CORAL_ERR_HIP); }
-    const long long data_end = CARRY_CAP + (long long)bi.infl_bytes;
-    const long long begin = G->searching ? (long long)CARRY_CAP - G->carry_len : std::min(G->known_start, data_end);
-    const long long limit = (G->last_rank || !bi.has_limit) ? (1ll << 62) : (long long)CARRY_CAP + bi.limit_rel;
-    const int seg0 = (int)(begin / SEG_BYTES);
-    const int n_seg = (int)((data_end + SEG_BYTES - 1) / SEG_BYTES) - seg0;
-    const int n_ref = (int)G->D.ref_names.size();
-    long long res[6] = {0, 0, 0, 0, 0, 0};
-    if (n_seg > 0) {
-        hipLaunchKernelGGL(k_bam_find, dim3(n_seg), dim3(WAVE), 0, stream, buf, begin, data_end, limit, n_ref, seg0, n_seg, G->d_seg_first,
-                           G->d_seg_land, G->d_seg_count, G->d_seg_valid);
-        hipLaunchKernelGGL(k_bam_verify, dim3(1), dim3(WAVE), 0, stream, buf, G->searching ? -1ll : G->known_start, begin, data_end, limit, seg0, n_seg,
-                           G->d_seg_first, G->d_seg_land, G->d_seg_count, G->d_seg_valid, G->d_seg_base, G->d_result);
-    }
-    int32_t status_bad = 0;
-    if (n_seg > 0) {
-        const auto t_gpu0 = std::chrono::steady_clock::now();
-        const bool synced = hipMemcpyAsync(res, G->d_result, sizeof(res), hipMemcpyDeviceToHost, stream) == hipSuccess && hipStreamSynchronize(stream) == hipSuccess;
-        G->t_wait_gpu += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_gpu0).count();
-        if (!synced) {
-            G->error = std::string("record walk failed: ") + hipGetErrorString(hipGetLastError());
-            return fail(CORAL_ERR_HIP);
-        }
-    } else {
-        res[1] = G->known_start;
-        if (hipStreamSynchronize(stream) != hipSuccess) { G->error = "hipStreamSynchronize failed"; return fail(CORAL_ERR_HIP); }
-    }
-    {   // every block of the batch must have inflated cleanly and have the checksum of its trailer
-        if (hipEventSynchronize(G->ev_crc[slot]) != hipSuccess) { G->error = "hipEventSynchronize failed"; return fail(CORAL_ERR_HIP); }
-        std::vector<int32_t> st((size_t)bi.n_blocks);
-        if (hipMemcpy(st.data(), G->d_status[slot], st.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) { G->error = "hipMemcpy failed"; return fail(CORAL_ERR_HIP); }
-        for (int32_t s : st) if (s != 0) { status_bad = s; break; }
-        if (status_bad == ERR_CRC) { G->error = "CRC32 of an inflated BGZF block differs from the one in its trailer"; return fail(CORAL_ERR_FORMAT); }
-        if (status_bad) { G->error = "inflate failed (corrupt BGZF block), code " + std::to_string(status_bad); return fail(CORAL_ERR_FORMAT); }
-    }
-    if (res[3] == 1) { G->error = "record shorter than its fixed fields"; return fail(CORAL_ERR_FORMAT); }
-    bool still_searching = false;
-    if (res[3] == 2) {
-        // no confirmed record start in what this byte range has seen so far (the chained check needs three records in a row): keep
-        // the bytes and look again with the next batch behind them, as the host pipeline does; at the end of the range it simply
-        // has no record of its own (it lies inside one record of the previous range)
-        if (data_end - begin > CARRY_CAP) { G->error = "no record start found in 64 MiB at the beginning of the byte range"; return fail(CORAL_ERR_FORMAT); }
-        res[0] = 0;
-        res[1] = bi.last ? data_end : begin;
-        res[2] = 0;
-        still_searching = !bi.last;
-    }
-    long long n_rec = res[0];
-    const long long carry_pos = res[1];
-    if (G->idx.active && G->searching && n_rec > 0 && res[5] < CARRY_CAP) {
-        // (a byte range that found no record start in its first batch and finds one in the bytes kept from it)
-        G->error = "index request: the first record of the byte range does not start in the batch it was found in";
-        return fail(CORAL_ERR_FORMAT);
-    }
-    G->cur_carry_pos = carry_pos < data_end ? carry_pos : data_end;
-    G->fixups += res[4];
-    if (n_rec > (long long)G->rec_cap) { G->error = "more records in a batch than its workspace holds"; return fail(CORAL_ERR_FORMAT); }
-    G->searching = still_searching;
-    G->cur = bi;
-    G->cur_n_rec = n_rec;
-    G->cur_ops = G->cur_name_bytes = G->cur_sa_bytes = 0;
-    if (n_rec > 0) {
-        hipLaunchKernelGGL(k_bam_starts, dim3((n_seg + WAVE - 1) / WAVE), dim3(WAVE), 0, stream, buf, seg0, n_seg, G->d_seg_first, G->d_seg_count, G->d_seg_valid,
-                           G->d_seg_base, G->d_rec_all);
-        (void)hipMemsetAsync(G->d_error, 0, 4, stream);
-    }
-    if (n_rec > 0 && G->req.keep.active()) {
-        // The record filter: from here on the batch's records are the kept ones.  Everything above (carry_pos, done, the span
-        // verdicts: byte positions of the walk) has not seen and does not see the kept count.  The flags and their offsets borrow
-        // two arrays k_bam_meta and the scans behind it refill (M.pad_ops, d_cig_off); the kept count comes back on its own
-        // (8 bytes + the error word): k_bam_meta's launch and the three scans are sized by it.
-        long long *keep = G->M.pad_ops, *keep_off = G->d_cig_off;
-        const unsigned grid = (unsigned)((n_rec + 1 + WAVE - 1) / WAVE);
-        hipLaunchKernelGGL(k_bam_keep, dim3(grid), dim3(WAVE), 0, stream, buf, G->d_rec_all, n_rec, G->req.keep, keep, G->d_error);
-        (void)G->scan(stream, keep, keep_off);                   // (over cur_n_rec + 1 = every record of the walk + the extra slot)
-        hipLaunchKernelGGL(k_bam_keep_compact, dim3(grid), dim3(WAVE), 0, stream, G->d_rec_all, n_rec, keep, keep_off, G->d_rec_start);
-        long long n_kept = 0;
-        int32_t rec_err = 0;
-        if (hipMemcpyAsync(&n_kept, keep_off + n_rec, 8, hipMemcpyDeviceToHost, stream) != hipSuccess ||
-            hipMemcpyAsync(&rec_err, G->d_error, 4, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) {
-            G->error = std::string("record filter failed: ") + hipGetErrorString(hipGetLastError());
-            return fail(CORAL_ERR_HIP);
-        }
-        if (rec_err) { G->error = rec_error_text(rec_err); return fail(CORAL_ERR_FORMAT); }
-        if (n_kept < 0 || n_kept > n_rec) { G->error = "record filter: the kept count is out of range"; return fail(CORAL_ERR_HIP); }
-        n_rec = n_kept;
-        G->cur_n_rec = n_rec;
-    }
-    if (n_rec > 0) {
-        const long long waves = n_rec + 1;
-        hipLaunchKernelGGL(k_bam_meta, dim3((unsigned)waves), dim3(WAVE), 0, stream, buf, G->d_rec_start, n_rec, G->M, G->d_error);
-        (void)G->scan(stream, G->M.pad_ops, G->d_cig_off);
-        (void)G->scan(stream, G->M.name_len, G->d_name_off);
-        (void)G->scan(stream, G->M.sa_len, G->d_sa_off);
-        long long totals[3] = {0, 0, 0};
-        int32_t rec_err = 0;
-        if (hipMemcpyAsync(&totals[0], G->d_cig_off + n_rec, 8, hipMemcpyDeviceToHost, stream) != hipSuccess ||
-            hipMemcpyAsync(&totals[1], G->d_name_off + n_rec, 8, hipMemcpyDeviceToHost, stream) != hipSuccess ||
-            hipMemcpyAsync(&totals[2], G->d_sa_off + n_rec, 8, hipMemcpyDeviceToHost, stream) != hipSuccess ||
-            hipMemcpyAsync(&rec_err, G->d_error, 4, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) {
-            G->error = std::string("record parse failed: ") + hipGetErrorString(hipGetLastError());
-            return fail(CORAL_ERR_HIP);
-        }
-        if (rec_err) { G->error = rec_error_text(rec_err); return fail(CORAL_ERR_FORMAT); }
-        G->cur_ops = totals[0];
-        G->cur_name_bytes = totals[1];
-        G->cur_sa_bytes = totals[2];
-    }
-    // what the next batch starts with
-    const bool done = res[2] != 0;
-    // (a span decode goes on with the next span)
-    auto verdict = [&](int v) {
-        if (!G->req.span_mode) return;
-        {
-            std::lock_guard<std::mutex> lk(G->m);
-            if (G->span_verdict[(size_t)bi.span] == 0) G->span_verdict[(size_t)bi.span] = v;
-        }
-        G->cv.notify_all();
-    };
-    auto range_done = [&]() {
-        G->carry_len = 0;
-        verdict(1);
-        if (G->req.span_mode && G->cur_span + 1 < (int)G->spans.size()) ++G->cur_span; else G->finished = true;
-    };
-    if (done) {
-        range_done();
-    } else if (carry_pos < data_end) {
-        G->carry_len = data_end - carry_pos;
-        if (G->carry_len > CARRY_CAP) { G->error = "a record larger than 64 MiB straddles two batches"; return fail(CORAL_ERR_FORMAT); }
-        G->known_start = CARRY_CAP - G->carry_len;
-    } else {
-        G->carry_len = 0;
-        G->known_start = CARRY_CAP + (carry_pos - data_end);
-    }
-    if (bi.last && !done) {
-        if (G->carry_len > 0) { G->error = G->last_rank ? "truncated record at the end of the file" : "a record straddles further than the supported overhang"; return fail(CORAL_ERR_FORMAT); }
-        range_done();
-    }
-    if (bi.span_tail && !done) verdict(2);       // the feeder stages what lies behind the span's own blocks
+    long long carry_pos = 0;
+    bool done = false;
+    int rc = take_staged_batch(G, stream);
+    if (rc == CORAL_OK && G->finished) return CORAL_OK;
+    if (rc == CORAL_OK) rc = walk_boundaries(G, stream, carry_pos, done);
+    if (rc == CORAL_OK) rc = filter_records(G, stream);
+    if (rc == CORAL_OK) rc = parse_meta(G, stream);
+    if (rc == CORAL_OK) rc = advance_carry(G, carry_pos, done);
+    if (rc != CORAL_OK) { set_error(G->error); return rc; }
     G->have_cur = true;
     ++G->n_batches;
-    out[0] = n_rec;
+    out[0] = G->cur_n_rec;
     out[1] = G->cur_ops;
     out[2] = 1;
     return CORAL_OK;
@@ -2967,14 +1911,11 @@ extern "C" int coral_bamgpu_emit(void *handle, uint32_t *cigar_dst, int64_t *cig
     hipStream_t stream = (hipStream_t)stream_;
     GpuDecoder *G = (GpuDecoder *)handle;
     if (!G || !G->have_cur) return CORAL_ERR_ARG;
-    auto fail = [&](int code, const std::string &msg) {
-        set_error(msg);
-        return code;
-    };
     const int kb = G->k, slot = kb & 1;
     uint8_t *buf = G->d_infl[slot];
     const long long n = G->cur_n_rec;
     Decoded &D = G->D;
+    std::string err;
     if (n > 0) {
         if (G->cur_ops > 0 && !cigar_dst) return CORAL_ERR_ARG;
         (void)hipMemsetAsync(G->d_na_count, 0, 4, stream);
@@ -3021,46 +1962,8 @@ extern "C" int coral_bamgpu_emit(void *handle, uint32_t *cigar_dst, int64_t *cig
             D.idx.note_order(IndexPartial::sort_word(tid[0], pos[0]), IndexPartial::sort_word(tid[n - 1], pos[n - 1]));
             D.idx.n_rec += n;
         }
-        if (na_count > 0) {
-            // the records with a non-ACGT code, whole, in one gather + one copy (the offset arrays of the scans are free by now)
-            J.na_list.resize((size_t)na_count);
-            std::vector<long long> starts((size_t)n);
-            if (hipMemcpy(J.na_list.data(), G->d_na_list, (size_t)na_count * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-                hipMemcpy(starts.data(), G->d_rec_start, (size_t)n * 8, hipMemcpyDeviceToHost) != hipSuccess)
-                return fail(CORAL_ERR_HIP, "copy of the non-ACGT list failed");
-            std::sort(J.na_list.begin(), J.na_list.end());
-            // a record ends where the next one starts - unless a record filter dropped that one: then its block_size says where
-            std::vector<uint32_t> own_size;
-            if (G->req.keep.active()) {
-                own_size.resize((size_t)na_count);
-                for (int32_t j = 0; j < na_count; ++j)
-                    if (hipMemcpy(&own_size[(size_t)j], buf + starts[(size_t)J.na_list[(size_t)j]], 4, hipMemcpyDeviceToHost) != hipSuccess)
-                        return fail(CORAL_ERR_HIP, "copy of the non-ACGT list failed");
-            }
-            std::vector<long long> src((size_t)na_count), dst((size_t)na_count), len((size_t)na_count);
-            J.na_off.assign((size_t)na_count + 1, 0);
-            for (int32_t j = 0; j < na_count; ++j) {
-                const int32_t li = J.na_list[(size_t)j];
-                const long long rec_end = !own_size.empty() ? starts[(size_t)li] + 4 + (long long)own_size[(size_t)j]
-                                          : li + 1 < n ? starts[(size_t)li + 1] : G->cur_carry_pos;
-                src[(size_t)j] = starts[(size_t)li] + 4;
-                len[(size_t)j] = rec_end - starts[(size_t)li] - 4;
-                dst[(size_t)j] = J.na_off[(size_t)j];
-                J.na_off[(size_t)j + 1] = J.na_off[(size_t)j] + len[(size_t)j];
-            }
-            const long long total = J.na_off[(size_t)na_count];
-            J.na_raw.resize((size_t)total);
-            if ((size_t)total > G->names_cap) return fail(CORAL_ERR_FORMAT, "records with non-ACGT bases exceed the batch workspace");
-            if (hipMemcpy(G->d_cig_off, src.data(), (size_t)na_count * 8, hipMemcpyHostToDevice) != hipSuccess ||
-                hipMemcpy(G->d_name_off, dst.data(), (size_t)na_count * 8, hipMemcpyHostToDevice) != hipSuccess ||
-                hipMemcpy(G->d_sa_off, len.data(), (size_t)na_count * 8, hipMemcpyHostToDevice) != hipSuccess)
-                return fail(CORAL_ERR_HIP, "upload of the non-ACGT gather list failed");
-            hipLaunchKernelGGL(k_bam_gather, dim3((unsigned)na_count), dim3(WAVE), 0, stream, buf, G->d_cig_off, G->d_name_off, G->d_sa_off, (int)na_count,
-                               G->d_names);
-            if (hipMemcpyAsync(J.na_raw.data(), G->d_names, (size_t)total, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess)
-                return fail(CORAL_ERR_HIP, "copy of the records with non-ACGT bases failed");
-            G->na_records += na_count;
-        }
+        if (na_count > 0)
+            if (const int rc = fetch_nonacgt(G, stream, J, na_count)) return rc;
         {
             std::lock_guard<std::mutex> lk(G->wm);
             G->jobs.push_back(std::move(job));
@@ -3069,19 +1972,11 @@ extern "C" int coral_bamgpu_emit(void *handle, uint32_t *cigar_dst, int64_t *cig
     } else if (hipStreamSynchronize(stream) != hipSuccess) {
         return fail(CORAL_ERR_HIP, "hipStreamSynchronize failed");
     }
-    const Borrowed S{G->M.name_len, G->M.sa_len, G->M.pad_ops, G->d_cig_off, (unsigned long long *)G->d_cig_off, (unsigned long long *)G->M.sa_src, G->M.pad_ops, G->d_name_off, G->d_sa_off, G->M.cig_src};
-    std::string err;
-    if (!G->reads.batch(G, stream, S, err) || !G->cov.batch(G, stream, S, err) || !G->qc.batch(G, stream, S, err) || !G->depth.batch(G, stream, err) || !G->idx.batch(G, stream, S, err))
-        return fail(CORAL_ERR_HIP, err);
-    // this buffer may be inflated into again (batch k + 2) once everything above has run
-    if (hipEventRecord(G->ev_parsed[slot], stream) != hipSuccess) return fail(CORAL_ERR_HIP, "hipEventRecord failed");
-    {
-        std::lock_guard<std::mutex> lk(G->m);
-        ++G->emitted;
-    }
-    G->cv.notify_all();
+    // what rides along, each with the parse's scratch to itself; all of it in front of ev_parsed
+    const Batch B = G->batch(stream);
+    if (!each_request(G, [&](auto &r) { return r.batch(B, G->scratch(), err); })) return fail(CORAL_ERR_HIP, err);
+    if (!release_slot(G, stream)) return fail(CORAL_ERR_HIP, "hipEventRecord failed");
     G->have_cur = false;
-    ++G->k;
     if (G->finished) D.seconds = G->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - G->t_start).count();
     return CORAL_OK;
 }

@@ -10,8 +10,8 @@ import pytest
 import torch
 
 from coral_amd import _lib, bam
-from tests.decode_support import (CORAL_ERR_ARG, CORAL_OK, assert_qc_equals_restatement as assert_equal, assert_same_qc as assert_same,
-                                  assert_same_records, gpu_decode_started, gpu_open_only, read_qc_case)
+from tests.decode_support import (CORAL_ERR_ARG, CORAL_OK, DEVICE, PIPELINES, assert_qc_equals_restatement as assert_equal,
+                                  assert_same_qc as assert_same, assert_same_records, gpu_decode_started, gpu_open_only, read_qc_case)
 
 WINDOWS = [("chr8", 149_000, 152_000), ("chr8", 150_000, 150_100), ("chr8", 0, 1 << 28)]
 
@@ -75,6 +75,71 @@ def test_host_refuses_bad_requests(case):
         rc = L.coral_bam_decode_request(case["path"].encode(), 1, C.byref(req), C.byref(h))
         assert rc == CORAL_ERR_ARG and h.value is None, name
         assert word in L.coral_bam_last_error().decode(), name
+
+
+# ---- every request that may ride together, in one decode ----------------------------------------------------------------------
+PILE_WINDOWS = [("chr8", 149_000, 152_000), ("chr8", 150_000, 150_100), ("chr8", 440_000, 451_000)]      # (the last: the 300 kb read's end)
+DEPTH = (1000, 0, 0x704, 1)
+SORTED_RECORDS = (0, None, None, 2, 1)                           # every record's own bytes, in coordinate order
+
+
+def maximal_sets(case):
+    """The two largest sets of requests one decode accepts -> (name -> each request's own arguments, records wanted).  The reads
+    request does not ride with the index, counts and pileup are the two forms of the one coverage request."""
+    chroms = case["rec"].header_chroms
+    pile_segs = bam.coverage_segments(PILE_WINDOWS, chroms)[0]
+    return [(dict(counts=dict(coverage=(segments(case), 20, 0)), qc=dict(qc=True), depth=dict(depth=DEPTH), index=dict(index=True)), True),
+            (dict(reads=dict(reads=SORTED_RECORDS), pileup=dict(coverage=(pile_segs, 20, 0), per_base=True), qc=dict(qc=True),
+                  depth=dict(depth=DEPTH)), False)]
+
+
+def assert_same_result(got, want, name, what):
+    if name in ("counts", "pileup"):
+        assert want.counts.sum() > 0 and np.array_equal(got.counts, want.counts), what
+    if name == "pileup":
+        assert got.pileup.dtype == want.pileup.dtype and np.array_equal(got.pileup, want.pileup), what
+    if name == "qc":
+        assert_same(got.qc, want.qc, what)
+    if name == "index":
+        assert_same_index(got.index, want.index)
+    if name in ("depth", "reads"):
+        a, b = getattr(got, name), getattr(want, name)
+        assert len(a) == len(b) and len(b[-1]) > 0, what
+        for x, y in zip(a, b):
+            assert x.dtype == y.dtype and np.array_equal(x, y), what
+    if name == "records":
+        assert_same_records(got.records, want.records)
+
+
+@pytest.fixture(scope="module")
+def host_alone(case):
+    """Every request of the two sets decoded alone on the host pipeline, once."""
+    out = {"records": bam._decode(case["path"], "cpu", n_threads=2)}
+    for requests, _ in maximal_sets(case):
+        for name, kw in requests.items():
+            if name not in out:
+                out[name] = bam._decode(case["path"], "cpu", n_threads=2, records=False, **kw)
+    return out
+
+
+@pytest.mark.parametrize("pipe", PIPELINES)
+def test_maximal_request_sets_equal_each_request_alone(case, host_alone, pipe):
+    """What rides along shares the per-record scratch of the parse; a result must not depend on what else rides.  Each of the two
+    maximal sets in one decode: every result bit-equal to that request decoded alone on the same pipeline, and to the host's."""
+    for batch in ((0, 1 << 20) if pipe == "gpu" else (0,)):
+        decode = lambda **kw: bam._decode(case["path"], DEVICE[pipe], n_threads=2, batch_bytes=batch, **kw)
+        alone = dict(host_alone) if pipe == "host" else {"records": decode()}
+        for requests, records in maximal_sets(case):
+            together = decode(records=records, **{k: v for kw in requests.values() for k, v in kw.items()})
+            if pipe == "gpu":
+                assert bam.LAST_DECODE["where"] == "gpu" and (batch == 0 or bam.LAST_DECODE["batches"] >= 3)
+            for name, kw in list(requests.items()) + ([("records", {})] if records else []):
+                if name not in alone:
+                    alone[name] = decode(records=False, **kw)
+                what = "%s, batch_bytes %d, with %s" % (name, batch, "+".join(requests))
+                assert_same_result(together, alone[name], name, what)
+                assert_same_result(together, host_alone[name], name, what + " (host)")
+            assert (together.records is None) == (not records)
 
 
 # ---- GPU pipeline --------------------------------------------------------------------------------------------------------------
