@@ -123,6 +123,7 @@ def build_parser():
                     type=lambda x: int(x, 0), default=0)
     vp.add_argument("--level", help="Compression level of the BAM file, 0..9.", type=int, default=1)
     vp.add_argument("--index", help="If specified, also write the BAI index (<output>.bai).", action='store_true')
+    vp.add_argument("--gpu_compress", help="Deflate the BAM file's BGZF blocks on the GPU (--device; cuda:0 with --device cpu) instead of on the host; --level must be 1.", action='store_true')
     vp.add_argument("--output", help="Name of the BAM file.", required=True)
     vp.add_argument("--device", help="GPU to use ('cpu': the host pipeline).", default="cuda:0")
     sp = sub.add_parser("sort", help="Write the records of a (long read) bam file in coordinate order as a BAM file, from one decode of it.")
@@ -131,6 +132,7 @@ def build_parser():
                     type=lambda x: int(x, 0), default=0)
     sp.add_argument("--level", help="Compression level of the BAM file, 0..9.", type=int, default=1)
     sp.add_argument("--index", help="If specified, also write the BAI index (<output>.bai).", action='store_true')
+    sp.add_argument("--gpu_compress", help="Deflate the BAM file's BGZF blocks on the GPU (--device; cuda:0 with --device cpu) instead of on the host; --level must be 1.", action='store_true')
     sp.add_argument("--output", help="Name of the sorted BAM file.", required=True)
     sp.add_argument("--device", help="GPU to use ('cpu': the host pipeline).", default="cuda:0")
     for p in (rp, hp, qp, pp, dp, fp, vp, sp):
@@ -262,6 +264,13 @@ def fastq_mode(args):
     return args.output
 
 
+def write_device_of(args):
+    """--gpu_compress: where `view` and `sort` deflate their output (RecordBytes.write's device)."""
+    if not args.gpu_compress:
+        return "cpu"
+    return "cuda:0" if args.device == "cpu" else args.device
+
+
 def view_mode(args):
     """The selected records as a BAM file (bam.extract_records + RecordBytes.write): the selection of `fastq`, the records
     themselves - alignments, tags and all - under the source's header, with the BAI index on request."""
@@ -270,7 +279,7 @@ def view_mode(args):
     rec = bam.extract_records(args.lr_bam, regions, names, args.reads_exclude_flags, device=args.device, record_filter=record_filter_of(args))
     if rec.header is None:                                       # an empty names file: nothing was decoded
         rec.header = bam.bam_header_bytes(args.lr_bam)
-    rec.write(args.output, level=args.level, index=args.index)
+    rec.write(args.output, level=args.level, index=args.index, device=write_device_of(args))
     print("Wrote %s (%d records)" % (args.output, rec.n))
     return args.output
 
@@ -280,7 +289,7 @@ def sort_mode(args):
     with the --filter_* arguments as the view's tests."""
     from coral_amd import bam
     out = bam.sort_bam(args.lr_bam, args.output, index=args.index, level=args.level, record_filter=record_filter_of(args),
-                       exclude_flags=args.reads_exclude_flags, device=args.device)
+                       exclude_flags=args.reads_exclude_flags, device=args.device, write_device=write_device_of(args))
     print("Wrote %s" % out)
     return out
 

@@ -170,6 +170,15 @@ def lib():
     L.coral_bam_decode_request_ordered.argtypes = [C.c_char_p, C.c_int32, Q, C.c_int32, C.POINTER(C.c_void_p)]
     L.coral_bamgpu_open_request_ordered.argtypes = [C.c_char_p, C.c_int32, C.c_int64, Q, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
     L.coral_bam_records_merge.argtypes = [C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64), P, P, C.c_int32]
+    L.coral_bgzf_deflate.argtypes = [P, P, C.c_int32, P, P, P, C.c_int64, P]
+    L.coral_bgzf_pack.argtypes = [P, P, C.c_int32, P, P, P, C.c_int64, P]
+    L.coral_bgzf_write_gpu.argtypes = [C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int32, P, C.c_int64, P]
+    for name in ("coral_bgzf_deflate_scratch_bytes", "coral_bgzf_pack_scratch_bytes"):
+        getattr(L, name).argtypes = [C.c_int32]
+        getattr(L, name).restype = C.c_int64
+    for name in ("coral_bgzf_write_gpu_workspace_bytes", "coral_bgzf_write_gpu_workspace_min_bytes"):
+        getattr(L, name).argtypes = []
+        getattr(L, name).restype = C.c_int64
     with open(os.path.join(os.path.dirname(_HERE), "include", "coral_hip.h")) as fp:
         for name in re.findall(r"^int (coral_\w+)\(", fp.read(), re.M):      # every prototype of the header that returns int
             getattr(L, name).restype = C.c_int

@@ -1048,11 +1048,17 @@ class RecordBytes:
         raw = self.data.tobytes()
         return [raw[a + 36:a + 36 + raw[a + 12] - 1].decode("latin-1") for a in self.offsets[:-1].tolist()]
 
-    def write(self, path: str, level: int = 1, index: bool = False, n_threads: Optional[int] = None) -> str:
+    def write(self, path: str, level: int = 1, index: bool = False, n_threads: Optional[int] = None, device="cpu",
+              workspace_bytes: Optional[int] = None) -> str:
         """The header and the records as a BGZF / BAM file (coral_bgzf_write: blocks of at most 0xff00 bytes, the header in
         blocks of its own, the EOF block last; ``level`` 0..9; the bytes do not depend on ``n_threads``).  ``index``: also its
         BAI index beside it (``build_index`` of the file written, host pipeline; the records must be in coordinate order, as
-        those of a sorted source are)."""
+        those of a sorted source are).
+
+        With a GPU ``device`` the same blocks are deflated there (coral_bgzf_write_gpu: k_bgzf_deflate, k_bgzf_pack): the same
+        cuts, so the same inflated bytes per block, other compressed bytes.  The GPU compressor has one setting: ``level`` must
+        be 1.  ``workspace_bytes``: device memory for the call (default: what it asks for; less means smaller chunks, the same
+        file)."""
         if self.header is None:
             raise ValueError("RecordBytes.write needs the source's header (bam_header_bytes)")
         if isinstance(level, bool) or not isinstance(level, numbers.Integral) or not 0 <= level <= 9:
@@ -1061,12 +1067,74 @@ class RecordBytes:
         head = np.frombuffer(self.header, dtype=np.uint8)
         parts = (C.c_void_p * 2)(head.ctypes.data, self.data.ctypes.data if len(self.data) else None)
         sizes = (C.c_int64 * 2)(len(head), len(self.data))
-        rc = L.coral_bgzf_write(os.fsencode(path), parts, sizes, 2, int(level), n_threads or default_threads())
-        if rc != 0:
-            raise _lib.CoralHipError("coral_bgzf_write(%s) failed (%d): %s" % (path, rc, L.coral_bam_last_error().decode()))
+        if torch.device(device).type == "cuda":
+            if level != 1:
+                raise ValueError("the GPU compressor has one setting: level must be 1 with a GPU device, got %r" % (level,))
+            _bgzf_write_gpu(path, parts, sizes, 2, device, workspace_bytes)
+        else:
+            rc = L.coral_bgzf_write(os.fsencode(path), parts, sizes, 2, int(level), n_threads or default_threads())
+            if rc != 0:
+                raise _lib.CoralHipError("coral_bgzf_write(%s) failed (%d): %s" % (path, rc, L.coral_bam_last_error().decode()))
         if index:
             build_index(path, device="cpu")
         return path
+
+
+def _bgzf_write_gpu(path, parts, sizes, n_parts: int, device, workspace_bytes: Optional[int] = None) -> None:
+    """coral_bgzf_write_gpu with its workspace as a torch uint8 tensor on ``device``, as the decode's is."""
+    L = _lib.lib()
+    dev = torch.device(device)
+    torch.cuda.set_device(dev)
+    ws_bytes = int(L.coral_bgzf_write_gpu_workspace_bytes()) if workspace_bytes is None else int(workspace_bytes)
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    stream = torch.cuda.current_stream(dev)
+    rc = L.coral_bgzf_write_gpu(os.fsencode(path), parts, sizes, n_parts, ws.data_ptr(), ws_bytes, stream.cuda_stream)
+    stream.synchronize()                                  # (the call has waited already; `ws` is released behind it)
+    if rc != 0:
+        raise _lib.CoralHipError("coral_bgzf_write_gpu(%s) failed (%d): %s" % (path, rc, L.coral_bam_last_error().decode()))
+
+
+_BGZF_SLOT = 65536
+
+
+def bgzf_compress(data, device="cuda:0") -> bytes:
+    """``data`` (bytes, or a uint8 array) as BGZF: one member per 0xff00 bytes, made on the GPU (coral_bgzf_deflate,
+    coral_bgzf_pack: one wave per member, dynamic Huffman or stored, whichever is smaller), and the 28-byte EOF block.
+    ``gzip.decompress`` of the result is ``data``; the bytes depend on ``data`` alone.  The thin public face of the kernel:
+    everything stays in torch tensors on ``device``, 1 024 blocks at a time."""
+    L = _lib.lib()
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise ValueError("bgzf_compress runs on a GPU device, got %r" % (device,))
+    raw = np.frombuffer(bytes(data), dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+    torch.cuda.set_device(dev)
+    stream = torch.cuda.current_stream(dev)
+    out = []
+    per_call = 1024
+    for at in range(0, len(raw), per_call * 0xff00):
+        piece = raw[at:at + per_call * 0xff00]
+        n = (len(piece) + 0xff00 - 1) // 0xff00
+        desc = np.zeros((n, 4), dtype=np.uint32)
+        desc[:, 0] = np.arange(n, dtype=np.uint32) * 0xff00
+        desc[:, 1] = np.minimum(0xff00, len(piece) - desc[:, 0].astype(np.int64))
+        desc[:, 2] = np.arange(n, dtype=np.uint32) * _BGZF_SLOT
+        t_in = torch.from_numpy(piece.copy()).to(dev)
+        t_desc = torch.from_numpy(desc.view(np.int32)).to(dev)
+        slots = torch.empty(n * _BGZF_SLOT, dtype=torch.uint8, device=dev)
+        packed = torch.empty(n * _BGZF_SLOT, dtype=torch.uint8, device=dev)
+        member = torch.empty(n, dtype=torch.int32, device=dev)
+        off = torch.empty(n + 1, dtype=torch.int32, device=dev)
+        scratch = torch.empty(int(L.coral_bgzf_deflate_scratch_bytes(n)), dtype=torch.uint8, device=dev)
+        tmp = torch.empty(max(int(L.coral_bgzf_pack_scratch_bytes(n)), 1), dtype=torch.uint8, device=dev)
+        rc = L.coral_bgzf_deflate(t_in.data_ptr(), t_desc.data_ptr(), n, slots.data_ptr(), member.data_ptr(), scratch.data_ptr(), scratch.numel(),
+                                  stream.cuda_stream)
+        if rc == 0:
+            rc = L.coral_bgzf_pack(slots.data_ptr(), member.data_ptr(), n, packed.data_ptr(), off.data_ptr(), tmp.data_ptr(), tmp.numel(), stream.cuda_stream)
+        if rc != 0:
+            raise _lib.CoralHipError("bgzf_compress failed (%d): %s" % (rc, L.coral_bam_last_error().decode()))
+        total = int(off[n].item())
+        out.append(packed[:total].cpu().numpy().tobytes())
+    return b"".join(out) + _BGZF_EMPTY
 
 
 def merge_record_bytes(parts: Sequence[RecordBytes]) -> RecordBytes:
@@ -1145,14 +1213,15 @@ def extract_records(path: str, regions=None, names=None, exclude_flags: int = 0,
 
 
 def sort_bam(path: str, output: str, *, index: bool = True, level: int = 1, record_filter=None, exclude_flags: int = 0, device="cuda:0",
-             n_threads: Optional[int] = None, batch_bytes: int = 0) -> str:
+             n_threads: Optional[int] = None, batch_bytes: int = 0, write_device=None) -> str:
     """``path``'s records - those that pass ``record_filter`` and ``exclude_flags`` - in coordinate order as the BAM file
     ``output``, with its BAI index beside it (``index``): ``samtools view -b -q ... | samtools sort | samtools index`` from one
     decode (``extract_records(order="coordinate")`` and ``RecordBytes.write``).  Returns ``output``.  The result lives in host
-    memory, about twice its size while the batches' runs are merged; runs are not spilled to disk."""
+    memory, about twice its size while the batches' runs are merged; runs are not spilled to disk.  ``write_device``: where the
+    output's BGZF blocks are deflated (``RecordBytes.write``'s ``device``; None: on the host, as before)."""
     rec = extract_records(path, None, None, exclude_flags, device=device, n_threads=n_threads, batch_bytes=batch_bytes, index=False,
                           record_filter=record_filter, order="coordinate")
-    return rec.write(output, level=level, index=index, n_threads=n_threads)
+    return rec.write(output, level=level, index=index, n_threads=n_threads, device="cpu" if write_device is None else write_device)
 
 
 # ----------------------------------------------------------------------------------------------

@@ -1020,6 +1020,7 @@ __global__ __launch_bounds__(256) void k_bam_gather(const uint8_t *__restrict__ 
 #include "coral_bamgpu_qc.h"
 #include "coral_bamgpu_depth.h"
 #include "coral_bamgpu_index.h"
+#include "coral_bamgpu_deflate.h"        // (no request of the decode: the BGZF writer's kernels, coral_bgzf_deflate / _write_gpu)
 
 // ---------------------------------------------------------------------------------------------
 // host side
@@ -2043,4 +2044,52 @@ extern "C" int coral_bgzf_inflate(const uint8_t *comp, const uint32_t *desc, int
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { set_error(std::string("k_bgzf_inflate: ") + hipGetErrorString(e)); return CORAL_ERR_HIP; }
     return CORAL_OK;
+}
+
+// One deflate launch on caller-provided buffers, the counterpart of coral_bgzf_inflate (tests; tools/bench_bgzf_deflate.py;
+// bam.bgzf_compress).  The descriptors are read back once to refuse what the kernel must not be given.
+extern "C" int64_t coral_bgzf_deflate_scratch_bytes(int32_t n_blocks) { return (int64_t)deflate_scratch_bytes(n_blocks); }
+
+extern "C" int coral_bgzf_deflate(const uint8_t *in, const uint32_t *desc, int32_t n_blocks, uint8_t *out, uint32_t *member_bytes, void *scratch,
+                                  int64_t scratch_bytes, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (n_blocks < 0 || (n_blocks > 0 && (!in || !desc || !out || !member_bytes || !scratch))) { set_error("coral_bgzf_deflate: a missing array"); return CORAL_ERR_ARG; }
+    if (n_blocks == 0) return CORAL_OK;
+    if (scratch_bytes < (int64_t)deflate_scratch_bytes(n_blocks)) { set_error("coral_bgzf_deflate: scratch is shorter than coral_bgzf_deflate_scratch_bytes"); return CORAL_ERR_ARG; }
+    std::vector<uint32_t> h((size_t)n_blocks * 4);
+    hipError_t e = hipMemcpyAsync(h.data(), desc, h.size() * 4, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) { set_error(std::string("coral_bgzf_deflate: ") + hipGetErrorString(e)); return CORAL_ERR_HIP; }
+    for (int32_t b = 0; b < n_blocks; ++b) {
+        if (h[4 * (size_t)b + 1] > (uint32_t)coral_deflate::BLOCK_MAX) { set_error("coral_bgzf_deflate: a block of more than 0xff00 bytes"); return CORAL_ERR_ARG; }
+        if (h[4 * (size_t)b + 2] & 3u) { set_error("coral_bgzf_deflate: dst_off must be a multiple of 4"); return CORAL_ERR_ARG; }
+    }
+    if (((uintptr_t)out & 3u) != 0) { set_error("coral_bgzf_deflate: out must be 4-byte aligned"); return CORAL_ERR_ARG; }
+    e = launch_deflate(in, desc, n_blocks, out, member_bytes, scratch, stream);
+    if (e != hipSuccess) { set_error(std::string("k_bgzf_deflate: ") + hipGetErrorString(e)); return CORAL_ERR_HIP; }
+    return CORAL_OK;
+}
+
+extern "C" int64_t coral_bgzf_pack_scratch_bytes(int32_t n_blocks) { return (int64_t)pack_tmp_bytes(n_blocks); }
+
+extern "C" int coral_bgzf_pack(const uint8_t *slots, const uint32_t *member_bytes, int32_t n_blocks, uint8_t *packed, uint32_t *offsets, void *scratch,
+                               int64_t scratch_bytes, void *stream_) {
+    if (n_blocks < 0 || n_blocks > 16384 || !offsets || (n_blocks > 0 && (!slots || !member_bytes || !packed || !scratch))) { set_error("coral_bgzf_pack: a missing array, or more than 16 384 blocks"); return CORAL_ERR_ARG; }
+    if ((((uintptr_t)slots | (uintptr_t)packed) & 15u) != 0) { set_error("coral_bgzf_pack: slots and packed must be 16-byte aligned"); return CORAL_ERR_ARG; }
+    hipError_t e;
+    if (n_blocks == 0) e = hipMemsetAsync(offsets, 0, 4, (hipStream_t)stream_);
+    else {
+        if (scratch_bytes < (int64_t)pack_tmp_bytes(n_blocks)) { set_error("coral_bgzf_pack: scratch is shorter than coral_bgzf_pack_scratch_bytes"); return CORAL_ERR_ARG; }
+        e = launch_pack(slots, member_bytes, n_blocks, packed, offsets, scratch, (size_t)scratch_bytes, (hipStream_t)stream_);
+    }
+    if (e != hipSuccess) { set_error(std::string("k_bgzf_pack: ") + hipGetErrorString(e)); return CORAL_ERR_HIP; }
+    return CORAL_OK;
+}
+
+extern "C" int64_t coral_bgzf_write_gpu_workspace_bytes(void) { return (int64_t)write_gpu_workspace_bytes(DEFL_CHUNK_BLOCKS); }
+extern "C" int64_t coral_bgzf_write_gpu_workspace_min_bytes(void) { return (int64_t)write_gpu_workspace_bytes(1); }
+
+extern "C" int coral_bgzf_write_gpu(const char *path, const uint8_t *const *parts, const int64_t *part_bytes, int32_t n_parts, void *workspace,
+                                    int64_t workspace_bytes, void *stream) {
+    return bgzf_write_gpu(path, parts, part_bytes, n_parts, workspace, workspace_bytes, (hipStream_t)stream);
 }

@@ -658,6 +658,49 @@ int coral_bamgpu_close(void *handle);
 int coral_bgzf_inflate(const uint8_t *comp, const uint32_t *desc, int32_t n_blocks, uint8_t *out, int32_t *status,
                        void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * BGZF blocks made ON THE GPU - replaces what the reference's workflow gets from htslib's bgzf_write + zlib deflate when
+ * `samtools view -b` / `samtools sort` write their output (/root/reference/scripts/align_nanopore_reads.sh:44, :49).  One
+ * 64-lane wave turns one input block of at most 0xff00 bytes into one complete BGZF member (k_bgzf_deflate,
+ * coral_deflate_core.h): the 18-byte header with BSIZE, ONE raw DEFLATE block - dynamic Huffman, or stored when the dynamic
+ * stream would not be smaller than len + 5 bytes, so a member is never longer than len + 31 bytes -, CRC-32 and ISIZE.  An
+ * empty block gives a valid empty member (31 bytes).  There is one setting, no levels.  A member's bytes are a function of its
+ * block's bytes alone: not of the launch, the chunking, the alignment of source or slot, or the run.  They inflate with any
+ * DEFLATE decoder; they are NOT zlib's or htslib's bytes.  The library allocates no device memory.
+ *
+ * coral_bgzf_deflate: one launch over caller-provided device buffers, the counterpart of coral_bgzf_inflate.  desc = n_blocks x
+ *   {src_off, src_len <= 0xff00, dst_off, 0} uint32 on the device: the block is in[src_off .. src_off + src_len) (any byte
+ *   alignment; nothing outside it is read), its member goes to out + dst_off, a slot of 65 536 bytes all of which may be
+ *   written (out 4-byte aligned, dst_off a multiple of 4; slots must not overlap), and member_bytes[b] is the member's
+ *   length.  scratch: coral_bgzf_deflate_scratch_bytes(n_blocks) bytes of device memory (4-byte aligned), the tokens between
+ *   the compressor's two passes, 261 120 bytes per workgroup of the launch (at most 2 048).  The descriptors are read back
+ *   once (the call waits for `stream` up to there); the launch itself is asynchronous.  n_blocks = 0 is a no-op.
+ *   CORAL_ERR_ARG: n_blocks < 0, a missing array, src_len > 0xff00, a misaligned dst_off or out, short scratch.
+ * coral_bgzf_pack: members in slots at the fixed stride (member b at slots + b * 65 536, member_bytes[b] long) -> one contiguous
+ *   byte string: offsets[0 .. n_blocks] (uint32, device) is the exclusive scan of the lengths (offsets[n_blocks]: all bytes),
+ *   packed gets the members one behind the other.  slots and packed 16-byte aligned; at most 16 384 blocks per call;
+ *   scratch: coral_bgzf_pack_scratch_bytes(n_blocks) bytes (hipcub's temporary storage).  Asynchronous on `stream`.
+ * coral_bgzf_write_gpu: coral_bgzf_write's contract with the blocks made on the current device: every part is cut at 0xff00
+ *   bytes and starts a block of its own, an empty part makes no block, the 28-byte EOF block goes last.  The parts are host
+ *   memory; chunks of consecutive blocks go up through two pinned buffers (allocated and freed by the call), each chunk is
+ *   deflated and packed on the device, and only the packed bytes come back, written in order.  workspace: device memory,
+ *   coral_bgzf_write_gpu_workspace_bytes() for chunks of 1 024 blocks (about 0.44 GiB, more than half of it tokens); a smaller one, down
+ *   to coral_bgzf_write_gpu_workspace_min_bytes() (one block per chunk), only makes the chunks smaller - the file's bytes do not
+ *   depend on it.  The call returns when the file is closed; nothing of it is left on `stream`.
+ *   CORAL_ERR_ARG: no path, n_parts < 0, a missing array or part, no or too small a workspace, a path that cannot be created;
+ *   CORAL_ERR_HIP: a HIP call failed; CORAL_ERR_FORMAT: the write failed.
+ * ------------------------------------------------------------------------------------------------ */
+int coral_bgzf_deflate(const uint8_t *in, const uint32_t *desc, int32_t n_blocks, uint8_t *out, uint32_t *member_bytes,
+                       void *scratch, int64_t scratch_bytes, void *stream);
+int64_t coral_bgzf_deflate_scratch_bytes(int32_t n_blocks);
+int coral_bgzf_pack(const uint8_t *slots, const uint32_t *member_bytes, int32_t n_blocks, uint8_t *packed, uint32_t *offsets,
+                    void *scratch, int64_t scratch_bytes, void *stream);
+int64_t coral_bgzf_pack_scratch_bytes(int32_t n_blocks);
+int coral_bgzf_write_gpu(const char *path, const uint8_t *const *parts, const int64_t *part_bytes, int32_t n_parts,
+                         void *workspace, int64_t workspace_bytes, void *stream);
+int64_t coral_bgzf_write_gpu_workspace_bytes(void);
+int64_t coral_bgzf_write_gpu_workspace_min_bytes(void);
+
 #ifdef __cplusplus
 }
 #endif
