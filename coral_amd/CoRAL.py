@@ -113,6 +113,8 @@ def build_parser():
     fp.add_argument("--names_file", help="File of read names, one per line: only these reads.")
     fp.add_argument("--reads_exclude_flags", help="Leave out records with any of these flag bits (default: secondary, supplementary).",
                     type=lambda x: int(x, 0), default=0x900)
+    fp.add_argument("--stream", help="Write each batch's text to the file while the input is decoded on the GPU (--device; cuda:0 with --device cpu): "
+                    "bounded host memory, for every read of a file of any size.", action='store_true')
     fp.add_argument("--output", help="Name of the FASTQ file.", required=True)
     fp.add_argument("--device", help="GPU to use ('cpu': the host pipeline).", default="cuda:0")
     vp = sub.add_parser("view", help="Write selected records of a (long read) bam file as a BAM file, from one decode of it.")
@@ -124,6 +126,8 @@ def build_parser():
     vp.add_argument("--level", help="Compression level of the BAM file, 0..9.", type=int, default=1)
     vp.add_argument("--index", help="If specified, also write the BAI index (<output>.bai).", action='store_true')
     vp.add_argument("--gpu_compress", help="Deflate the BAM file's BGZF blocks on the GPU (--device; cuda:0 with --device cpu) instead of on the host; --level must be 1.", action='store_true')
+    vp.add_argument("--stream", help="Write the BAM file while the input is decoded, its BGZF blocks deflated on the GPU (--device; cuda:0 with --device cpu): "
+                    "bounded host memory, for a file of any size; implies --gpu_compress and --level 1.", action='store_true')
     vp.add_argument("--output", help="Name of the BAM file.", required=True)
     vp.add_argument("--device", help="GPU to use ('cpu': the host pipeline).", default="cuda:0")
     sp = sub.add_parser("sort", help="Write the records of a (long read) bam file in coordinate order as a BAM file, from one decode of it.")
@@ -258,6 +262,11 @@ def fastq_mode(args):
     """The selected reads as FASTQ (bam.extract_reads): by regions, by names, both (intersected) or neither (every read)."""
     from coral_amd import bam
     regions, names = selection_of(args)
+    if args.stream:
+        n, _ = bam.extract_reads(args.lr_bam, regions, names, args.reads_exclude_flags, device="cuda:0" if args.device == "cpu" else args.device,
+                                 record_filter=record_filter_of(args), output=args.output)
+        print("Wrote %s (%d reads)" % (args.output, n))
+        return args.output
     reads = bam.extract_reads(args.lr_bam, regions, names, args.reads_exclude_flags, device=args.device, record_filter=record_filter_of(args))
     reads.write(args.output)
     print("Wrote %s (%d reads)" % (args.output, reads.n))
@@ -276,6 +285,13 @@ def view_mode(args):
     themselves - alignments, tags and all - under the source's header, with the BAI index on request."""
     from coral_amd import bam
     regions, names = selection_of(args)
+    if args.stream:                                              # (bam.view_bam: the same bytes, never whole in host memory)
+        if args.level != 1:
+            raise ValueError("--stream deflates on the GPU, which has one setting: --level must be 1, got %r" % (args.level,))
+        st = bam.view_bam(args.lr_bam, args.output, regions, names, args.reads_exclude_flags, record_filter=record_filter_of(args), index=args.index,
+                          device="cuda:0" if args.device == "cpu" else args.device)
+        print("Wrote %s (%d records)" % (args.output, st.records))
+        return args.output
     rec = bam.extract_records(args.lr_bam, regions, names, args.reads_exclude_flags, device=args.device, record_filter=record_filter_of(args))
     if rec.header is None:                                       # an empty names file: nothing was decoded
         rec.header = bam.bam_header_bytes(args.lr_bam)

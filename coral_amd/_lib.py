@@ -169,7 +169,11 @@ def lib():
     L.coral_bamgpu_finish.argtypes = [C.c_void_p, P]
     L.coral_bam_decode_request_ordered.argtypes = [C.c_char_p, C.c_int32, Q, C.c_int32, C.POINTER(C.c_void_p)]
     L.coral_bamgpu_open_request_ordered.argtypes = [C.c_char_p, C.c_int32, C.c_int64, Q, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
-    L.coral_bam_records_merge.argtypes = [C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64), P, P, C.c_int32]
+    L.coral_bamgpu_open_request_to_file.argtypes = [C.c_char_p, C.c_int32, C.c_int64, Q, C.c_char_p, P, C.c_int64, C.c_int32, C.POINTER(C.c_void_p),
+                                                    C.POINTER(C.c_int64)]
+    L.coral_bamgpu_open_request_to_text.argtypes = [C.c_char_p, C.c_int32, C.c_int64, Q, C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
+    L.coral_bamgpu_sink_stats.argtypes =[C.c_void_p, C.POINTER(C.c_int64)]
+    L.coral_bam_records_merge.argtypes =[C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64), P, P, C.c_int32]
     L.coral_bgzf_deflate.argtypes = [P, P, C.c_int32, P, P, P, C.c_int64, P]
     L.coral_bgzf_pack.argtypes = [P, P, C.c_int32, P, P, P, C.c_int64, P]
     L.coral_bgzf_write_gpu.argtypes = [C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int32, P, C.c_int64, P]

@@ -225,7 +225,8 @@ class DecodeResult(collections.namedtuple("DecodeResult", "records counts index 
 
 
 def _decode(path: str, device, *, n_threads: Optional[int] = None, rank: int = 0, world: int = 1, batch_bytes: int = 0, spans=None,
-            coverage=None, index=False, qc=False, records=True, per_base=False, depth=None, record_filter=None, reads=None) -> DecodeResult:
+            coverage=None, index=False, qc=False, records=True, per_base=False, depth=None, record_filter=None, reads=None,
+            sink=None) -> DecodeResult:
     """One decode of the ``rank``-th of ``world`` byte ranges, or of the records that start inside ``spans`` (uint64 [K][2] virtual
     offsets), with what rides along: ``coverage`` = (segments int32 [3][S], quality threshold, read_callback code) gives the S
     int64 ``counts``, ``index`` the partial BAI index, ``qc`` the ``ReadQC``; ``records`` False leaves the Records out.  With
@@ -233,10 +234,15 @@ def _decode(path: str, device, *, n_threads: Optional[int] = None, rank: int = 0
     segment order][A, C, G, T] and ``counts`` its sums per segment.  ``depth`` = (bin size, min_mapq, exclude_flags,
     count_deletions) gives the binned-depth tables (``binned_depth``), ``reads`` = (exclude_flags, segments or None, sorted names or
     None[, mode]) the FASTQ text of the selected records (``extract_reads``) or, with mode 2, their own bytes (``extract_records``).  ``record_filter``: a ``RecordFilter``; every result is
-    then that of a file holding only the kept records.  On the GPU pipeline when ``_on_gpu(device)``, else on the host."""
+    then that of a file holding only the kept records.  On the GPU pipeline when ``_on_gpu(device)``, else on the host.
+    ``sink`` = (output path, inflated header, chunk_blocks): the records of a mode-2 reads request go to that BAM file while the
+    decode runs (GPU pipeline only, whatever CORAL_BAM_DECODE says); ``reads`` is then (records, bytes, file bytes, members).
+    ``sink`` = (output path, None, 0): the FASTQ text of a mode-1 request goes to that plain file, batch by batch."""
     req = _lib.bam_request(rank, world, spans, coverage, index, qc, per_base, depth, keep=_as_filter(record_filter), reads=reads)
-    if _on_gpu(device):
-        return _decode_gpu(path, device, n_threads, batch_bytes, req, records)
+    if sink is not None and torch.device(device).type != "cuda":
+        raise ValueError("a decode that writes its records to a file runs on a GPU device, got %r" % (device,))
+    if _on_gpu(device) or sink is not None:
+        return _decode_gpu(path, device, n_threads, batch_bytes, req, records, sink)
     L = _lib.lib()
     if n_threads is None:
         n_threads = default_threads()
@@ -262,8 +268,9 @@ def _host_stats(L, h, n_threads):
                        threads=int(n_threads))
 
 
-def _result_from_handle(L, h, req, records: bool, cigar, cigar_words: int) -> DecodeResult:
-    """What ``req`` asked for, read from a decode handle of either pipeline (``cigar``: see _records_from_handle)."""
+def _result_from_handle(L, h, req, records: bool, cigar, cigar_words: int, reads_on_host: bool = True) -> DecodeResult:
+    """What ``req`` asked for, read from a decode handle of either pipeline (``cigar``: see _records_from_handle); not the reads
+    request's result when it went to a file (``reads_on_host`` False)."""
     counts = None
     if req.n_seg >= 0:
         counts = np.zeros(req.n_seg, dtype=np.int64)
@@ -286,7 +293,7 @@ def _result_from_handle(L, h, req, records: bool, cigar, cigar_words: int) -> De
         if L.coral_bam_depth_fill(h, bin_off.ctypes.data, bases.ctypes.data, reads.ctypes.data) != 0:
             raise _lib.CoralHipError("coral_bam_depth_fill failed: %s" % L.coral_bam_last_error().decode())
         res.depth = (bin_off, bases, reads)
-    if req.want_reads:
+    if req.want_reads and reads_on_host:
         sz = (C.c_int64 * 2)()
         if L.coral_bam_reads_sizes(h, sz) != 0:
             raise _lib.CoralHipError("coral_bam_reads_sizes failed: %s" % L.coral_bam_last_error().decode())
@@ -297,8 +304,8 @@ def _result_from_handle(L, h, req, records: bool, cigar, cigar_words: int) -> De
     return res
 
 
-def _decode_gpu(path: str, device, n_threads: Optional[int], batch_bytes: int, req, records: bool) -> DecodeResult:
-    """The GPU pipeline of _decode: coral_bamgpu_open_request, the batches, coral_bamgpu_finish."""
+def _decode_gpu(path: str, device, n_threads: Optional[int], batch_bytes: int, req, records: bool, sink=None) -> DecodeResult:
+    """The GPU pipeline of _decode: coral_bamgpu_open_request (with ``sink``: _to_file), the batches, coral_bamgpu_finish."""
     L = _lib.lib()
     dev = torch.device(device)
     torch.cuda.set_device(dev)
@@ -306,7 +313,15 @@ def _decode_gpu(path: str, device, n_threads: Optional[int], batch_bytes: int, r
         n_threads = default_threads()
     fail = lambda what, rc: _lib.CoralHipError("%s(%s) failed (%d): %s" % (what, path, rc, L.coral_bam_last_error().decode()))
     h, ws_bytes = C.c_void_p(), C.c_int64(0)
-    if req.reads_order:
+    if sink is not None:
+        out_path, header, chunk_blocks = sink
+    if sink is not None and header is None:
+        rc = L.coral_bamgpu_open_request_to_text(path.encode(), n_threads, batch_bytes, C.byref(req), os.fsencode(out_path), C.byref(h), C.byref(ws_bytes))
+    elif sink is not None:
+        head = np.frombuffer(bytes(header), dtype=np.uint8)
+        rc = L.coral_bamgpu_open_request_to_file(path.encode(), n_threads, batch_bytes, C.byref(req), os.fsencode(out_path),
+                                                 head.ctypes.data if len(head) else None, len(head), int(chunk_blocks), C.byref(h), C.byref(ws_bytes))
+    elif req.reads_order:
         rc = L.coral_bamgpu_open_request_ordered(path.encode(), n_threads, batch_bytes, C.byref(req), req.reads_order, C.byref(h), C.byref(ws_bytes))
     else:
         rc = L.coral_bamgpu_open_request(path.encode(), n_threads, batch_bytes, C.byref(req), C.byref(h), C.byref(ws_bytes))
@@ -358,6 +373,12 @@ def _decode_gpu(path: str, device, n_threads: Optional[int], batch_bytes: int, r
                            nonacgt_records_fetched=int(gst[2]), batch_bytes=int(gst[3]), host_seconds=float(gsecs[1]), read_seconds=float(gsecs[2]),
                            setup_seconds=float(gsecs[3]), waited_for_file_seconds=float(gsecs[4]), waited_for_gpu_seconds=float(gsecs[5]),
                            workspace_bytes=int(ws_bytes.value))
+        if sink is not None:                                     # (nothing of the reads request is on the host: coral_bam_reads_fill refuses)
+            sst = (C.c_int64 * 4)()
+            _lib.check(L.coral_bamgpu_sink_stats(h, sst), "coral_bamgpu_sink_stats")
+            res = _result_from_handle(L, dh, req, records, cigar, total, reads_on_host=False)
+            res.reads = tuple(int(v) for v in sst)
+            return res
         return _result_from_handle(L, dh, req, records, cigar, total)
     finally:
         # (close drains the decoder's streams — a byte range may have batches of its overhang still being inflated — and only
@@ -896,7 +917,7 @@ def merge_reads(parts: Sequence[Reads]) -> Reads:
 
 
 def extract_reads(path: str, regions=None, names=None, exclude_flags: int = 0x900, device="cuda:0", n_threads: Optional[int] = None,
-                  rank: int = 0, world: int = 1, batch_bytes: int = 0, *, index=None, record_filter=None) -> Reads:
+                  rank: int = 0, world: int = 1, batch_bytes: int = 0, *, index=None, record_filter=None, output: Optional[str] = None):
     """The reads of the BAM file as FASTQ (``Reads``), written while it is decoded - the only time SEQ and QUAL are at hand: what
     ``samtools view x.bam region... | samtools fastq`` or ``samtools view -N names.txt`` get from a second pass over the file.
 
@@ -913,15 +934,30 @@ def extract_reads(path: str, regions=None, names=None, exclude_flags: int = 0x90
     ``CORAL_BAM_DECODE=cpu``; identical bytes.  With regions, a BAI index (``index``: the rules of ``window_coverage``) restricts
     the decode to the BGZF blocks it names; with names only, or neither, the byte range (``rank`` of ``world``) is decoded and
     ``merge_reads`` joins the ranges.  ``record_filter``: a ``RecordFilter``, applied first.  The whole result lives in host
-    memory: meant for the reads of an amplicon, not for every read of a 2 M-read file."""
-    got = _selected(1, path, regions, names, exclude_flags, device, n_threads, rank, world, batch_bytes, index, record_filter)
-    return Reads(*got) if got is not None else Reads()
+    memory: meant for the reads of an amplicon.  For every read of a 2 M-read file give ``output``: each batch's text is written
+    to that file where it would be appended to the result (coral_bamgpu_open_request_to_text; a GPU ``device``, the whole file:
+    ``world`` 1), nothing is kept, and the call returns ``(records, bytes)``; the file's bytes are those of ``Reads.write``."""
+    if output is None:
+        got = _selected(1, path, regions, names, exclude_flags, device, n_threads, rank, world, batch_bytes, index, record_filter)
+        return Reads(*got) if got is not None else Reads()
+    if torch.device(device).type != "cuda":
+        raise ValueError("extract_reads(output=...) writes during a GPU decode, got device %r; the host path is extract_reads(...).write(...)" % (device,))
+    if (rank, world) != (0, 1):
+        raise ValueError("extract_reads(output=...) writes one file: byte ranges (world > 1) do not go with it")
+    regions, names = (None if x is None else list(x) for x in (regions, names))
+    got = _selected(1, path, regions, names, exclude_flags, device, n_threads, 0, 1, batch_bytes, index, record_filter, sink=(output, None, 0))
+    if got is None:                                              # nothing was decoded: an empty file
+        open(output, "wb").close()
+        return 0, 0
+    return int(got[0]), int(got[1])
 
 
-def _selected(mode: int, path, regions, names, exclude_flags, device, n_threads, rank, world, batch_bytes, index, record_filter, order: int = 0):
-    """What ``extract_reads`` (mode 1) and ``extract_records`` (mode 2) share: the argument rules, the index use and the decode ->
-    (bytes uint8, offsets int64 [n + 1]) of the reads request, or None for a selection that is empty before any record is decoded
-    (an empty list: the file is not opened).  ``order`` 1 (mode 2 only): the records in coordinate order."""
+def _selected(mode: int, path, regions, names, exclude_flags, device, n_threads, rank, world, batch_bytes, index, record_filter, order: int = 0,
+              sink=None):
+    """What ``extract_reads`` (mode 1), ``extract_records`` (mode 2) and ``view_bam`` (mode 2 with ``sink``, see _decode) share: the
+    argument rules, the index use and the decode -> (bytes uint8, offsets int64 [n + 1]) of the reads request - with ``sink``
+    its four counts -, or None for a selection that is empty before any record is decoded (an empty list: the file is not
+    opened).  ``order`` 1 (mode 2 only): the records in coordinate order."""
     if isinstance(exclude_flags, bool) or not isinstance(exclude_flags, numbers.Integral) or not 0 <= exclude_flags <= 0xffff:
         raise ValueError("exclude_flags must be an integer in 0..0xffff, got %r" % (exclude_flags,))
     if names is not None:
@@ -935,7 +971,7 @@ def _selected(mode: int, path, regions, names, exclude_flags, device, n_threads,
         n_threads = default_threads()
     if regions is None:
         res = _decode(path, device, n_threads=n_threads, rank=rank, world=world, batch_bytes=batch_bytes, records=False,
-                      record_filter=record_filter, reads=(exclude_flags, None, names, mode, order))
+                      record_filter=record_filter, reads=(exclude_flags, None, names, mode, order), sink=sink)
         return res.reads
     ref_names = bam_reference_names(path)
     _, segs = pileup_regions(list(regions), ref_names)
@@ -962,7 +998,7 @@ def _selected(mode: int, path, regions, names, exclude_flags, device, n_threads,
         out = None
     else:
         res = _decode(path, device, n_threads=n_threads, rank=rank, world=world, batch_bytes=batch_bytes, spans=spans, records=False,
-                      record_filter=record_filter, reads=(exclude_flags, segs, names, mode, order))
+                      record_filter=record_filter, reads=(exclude_flags, segs, names, mode, order), sink=sink)
         out = res.reads
     if idx is not None:
         LAST_DECODE.update(index=idx.path or "<object>", spans=int(len(spans)))
@@ -1192,7 +1228,7 @@ def extract_records(path: str, regions=None, names=None, exclude_flags: int = 0,
 
     GPU pipeline (k_bam_reads_plan / k_bam_reads_copy per batch) on a GPU ``device``, host pipeline with ``device="cpu"`` or
     ``CORAL_BAM_DECODE=cpu``; identical bytes.  ``merge_record_bytes`` joins byte ranges.  The whole result lives in host memory:
-    meant for the records of an amplicon, not for a whole 2 M-read file; nothing is streamed to disk.
+    meant for the records of an amplicon; ``view_bam`` streams the same selection of a whole 2 M-read file to disk.
 
     ``order="coordinate"``: the written records sorted during the same decode, ascending by ``(tid, pos, reverse strand)`` with
     ``tid = -1`` last and records of equal key in file order - what ``samtools sort`` does in a pass of its own.  On the GPU each
@@ -1210,6 +1246,51 @@ def extract_records(path: str, regions=None, names=None, exclude_flags: int = 0,
     header = bam_header_bytes(path)
     return RecordBytes(*(got if got is not None else (None, None)), header=sorted_header_bytes(header) if order == "coordinate" else header,
                        order=order)
+
+
+ViewStats = collections.namedtuple("ViewStats", "records bytes file_bytes")
+
+
+def view_bam(path: str, output: str, regions=None, names=None, exclude_flags: int = 0, *, record_filter=None, index: bool = False, bam_index=None,
+             device="cuda:0", n_threads: Optional[int] = None, batch_bytes: int = 0, chunk_blocks: int = 0) -> ViewStats:
+    """``samtools view -b`` of a file of any size: the selected records of ``path`` as the BAM file ``output``, written WHILE the
+    file is decoded.  Each batch's records are copied out of the inflated batch and deflated where they are, in HBM
+    (k_bam_reads_copy_shifted, k_bgzf_chunk_desc, k_bgzf_deflate, k_bgzf_pack; coral_bamgpu_open_request_to_file): uncompressed
+    record bytes never cross PCIe, compressed ones once, and host memory is bounded by two pinned chunks whatever the output's
+    size.  Returns ``ViewStats(records, bytes, file_bytes)``: records written, their inflated bytes, the size of ``output``.
+
+    Selection (``regions``, ``names``, ``exclude_flags``), ``record_filter`` and the index use (``bam_index`` is
+    ``extract_records``'s ``index``) are exactly ``extract_records``'s, and ``output`` is byte for byte
+    ``extract_records(...).write(output, device=gpu)``: the source's header in blocks of its own, the records in file order cut
+    at 0xff00 bytes, the EOF block; the bytes do not depend on ``batch_bytes``, on ``chunk_blocks`` (blocks per deflate launch:
+    0 = 1 024, at most 16 384) or on the run.  An empty ``regions`` or ``names`` list writes header + EOF without a decode.
+    ``index``: also ``output``'s BAI index beside it (``build_index`` of the file written, host pipeline, as
+    ``RecordBytes.write``).  It needs a GPU ``device``: the host path is ``extract_records(...).write(...)``.  On an exception
+    the partial output is removed.  Coordinate order is ``sort_bam``, which is not streamed."""
+    if torch.device(device).type != "cuda":
+        raise ValueError("view_bam streams through a GPU device, got %r; the host path is extract_records(...).write(...)" % (device,))
+    if isinstance(chunk_blocks, bool) or not isinstance(chunk_blocks, numbers.Integral) or not 0 <= chunk_blocks <= 16384:
+        raise ValueError("chunk_blocks must be an integer in 0..16384 (0: 1 024), got %r" % (chunk_blocks,))
+    if isinstance(batch_bytes, bool) or not isinstance(batch_bytes, numbers.Integral) or batch_bytes < 0:
+        raise ValueError("batch_bytes must be an integer >= 0, got %r" % (batch_bytes,))
+    regions, names = (None if x is None else list(x) for x in (regions, names))
+    header = bam_header_bytes(path)
+    stat_of = lambda p: (lambda st: (st.st_ino, st.st_size, st.st_mtime_ns))(os.stat(p)) if os.path.exists(p) else None
+    before = stat_of(output)                                     # (an argument error leaves a file that was there alone)
+    try:
+        got = _selected(2, path, regions, names, exclude_flags, device, n_threads, 0, 1, batch_bytes, bam_index, record_filter,
+                        sink=(output, header, chunk_blocks))
+        if got is None:                                          # nothing was decoded: header + EOF, the same members
+            head = np.frombuffer(header, dtype=np.uint8)
+            _bgzf_write_gpu(output, (C.c_void_p * 1)(head.ctypes.data), (C.c_int64 * 1)(len(head)), 1, device)
+            got = (0, 0, os.path.getsize(output), 0)
+        if index:
+            build_index(output, device="cpu")
+    except BaseException:
+        if stat_of(output) not in (None, before):
+            os.remove(output)
+        raise
+    return ViewStats(int(got[0]), int(got[1]), int(got[2]))
 
 
 def sort_bam(path: str, output: str, *, index: bool = True, level: int = 1, record_filter=None, exclude_flags: int = 0, device="cuda:0",

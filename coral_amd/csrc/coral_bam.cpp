@@ -695,14 +695,15 @@ extern "C" int coral_bam_reads_sizes(void *handle, int64_t sizes[2]) {
     if (!handle || !sizes) return CORAL_ERR_ARG;
     const Decoded *D = (const Decoded *)handle;
     if (!D->has_reads) { g_bam_err = "coral_bam_reads_sizes: the handle holds no reads request"; return CORAL_ERR_ARG; }
-    sizes[0] = (int64_t)D->reads_off.size() - 1;
-    sizes[1] = (int64_t)D->reads_text.size();
+    sizes[0] = D->reads_to_file ? D->reads_file_records : (int64_t)D->reads_off.size() - 1;
+    sizes[1] = D->reads_to_file ? D->reads_file_bytes : (int64_t)D->reads_text.size();
     return CORAL_OK;
 }
 
 extern "C" int coral_bam_reads_fill(void *handle, uint8_t *text, int64_t *rec_off) {
     if (!handle || !rec_off) return CORAL_ERR_ARG;
     const Decoded *D = (const Decoded *)handle;
+    if (D->reads_to_file) { g_bam_err = "coral_bam_reads_fill: the records were written to a file, none is kept (coral_bamgpu_open_request_to_file)"; return CORAL_ERR_ARG; }
     if (!D->has_reads || D->reads_off.back() != (int64_t)D->reads_text.size()) { g_bam_err = "coral_bam_reads_fill: the handle holds no reads request"; return CORAL_ERR_ARG; }
     if (!D->reads_text.empty() && !text) return CORAL_ERR_ARG;
     if (!D->reads_text.empty()) memcpy(text, D->reads_text.data(), D->reads_text.size());

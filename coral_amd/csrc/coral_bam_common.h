@@ -413,6 +413,8 @@ struct Decoded {
     std::vector<uint8_t> reads_text;        // its FASTQ text (want_reads = 2: the records' bytes), the written records in file order (coral_bam_reads_fill)
     std::vector<int64_t> reads_off{0};      // where every written record starts in it, n + 1 entries
     std::vector<int64_t> reads_runs;        // coordinate order, GPU pipeline: the written record each batch's sorted run begins at
+    bool reads_to_file = false;             // GPU pipeline, coral_bamgpu_open_request_to_file: the records went to a file; nothing of them
+    int64_t reads_file_records = 0, reads_file_bytes = 0;      //   is kept here but their number and their inflated bytes
 };
 
 struct Partial {   // what stage 3 produces for one chunk

@@ -1020,7 +1020,8 @@ __global__ __launch_bounds__(256) void k_bam_gather(const uint8_t *__restrict__ 
 #include "coral_bamgpu_qc.h"
 #include "coral_bamgpu_depth.h"
 #include "coral_bamgpu_index.h"
-#include "coral_bamgpu_deflate.h"        // (no request of the decode: the BGZF writer's kernels, coral_bgzf_deflate / _write_gpu)
+#include "coral_bamgpu_deflate.h"        // (no request of the decode: the BGZF writer's kernels, coral_bgzf_deflate / _write_gpu, and the
+                                         //  file sink of a records request - coral_bamgpu_reads.h has included it for that)
 
 // ---------------------------------------------------------------------------------------------
 // host side
@@ -1753,14 +1754,34 @@ extern "C" int coral_bamgpu_open_request(const char *path, int32_t n_threads, in
     return coral_bamgpu_open_request_ordered(path, n_threads, batch_bytes, req, READS_ORDER_FILE, handle, workspace_bytes);
 }
 
-extern "C" int coral_bamgpu_open_request_ordered(const char *path, int32_t n_threads, int64_t batch_bytes, const coral_bam_request_t *req,
-                                                 int32_t reads_order, void **handle, int64_t *workspace_bytes) {
+namespace {
+// The file a records request writes to (coral_bamgpu_open_request_to_file); none: the request's result stays on the host.
+// (as_text: the plain FASTQ file of coral_bamgpu_open_request_to_text - no header, no chunks)
+struct SinkArgs { const char *out_path; const uint8_t *header; int64_t header_bytes; int32_t chunk_blocks; bool as_text; };
+
+// What the open entry points share: the older calls are this one without a sink.
+int open_decoder(const char *path, int32_t n_threads, int64_t batch_bytes, const coral_bam_request_t *req, int32_t reads_order, const SinkArgs *to_file,
+                 void **handle, int64_t *workspace_bytes) {
     if (!path || !handle || !workspace_bytes) return CORAL_ERR_ARG;
     std::unique_ptr<GpuDecoder> G(new GpuDecoder());
     G->t_start = std::chrono::steady_clock::now();
     std::string err;
     if (!parse_request(req, G->req, err) || !set_reads_order(G->req, reads_order, err)) { set_error(err); return CORAL_ERR_ARG; }
     const Request &R = G->req;
+    if (to_file && to_file->as_text) {
+        const char *me = "coral_bamgpu_open_request_to_text: ";
+        if (!(R.reads.on && R.reads.mode == READS_AS_FASTQ)) return fail(CORAL_ERR_ARG, std::string(me) + "a text file takes FASTQ: it needs want_reads = 1");
+        if (R.rank != 0 || R.world != 1) return fail(CORAL_ERR_ARG, std::string(me) + "byte ranges do not share a file: rank 0 of world 1");
+        if (!to_file->out_path) return fail(CORAL_ERR_ARG, std::string(me) + "no output path");
+    } else if (to_file) {
+        const char *me = "coral_bamgpu_open_request_to_file: ";
+        if (!(R.reads.on && R.reads.mode == READS_AS_RECORDS)) return fail(CORAL_ERR_ARG, std::string(me) + "a file takes records: it needs want_reads = 2");
+        if (R.reads.order != READS_ORDER_FILE) return fail(CORAL_ERR_ARG, std::string(me) + "records are streamed in file order: reads_order must be 0");
+        if (R.rank != 0 || R.world != 1) return fail(CORAL_ERR_ARG, std::string(me) + "byte ranges do not share a file: rank 0 of world 1");
+        if (!to_file->out_path) return fail(CORAL_ERR_ARG, std::string(me) + "no output path");
+        if (!to_file->header || to_file->header_bytes <= 0) return fail(CORAL_ERR_ARG, std::string(me) + "no header to write");
+        if (to_file->chunk_blocks < 0 || to_file->chunk_blocks > 16384) return fail(CORAL_ERR_ARG, std::string(me) + "chunk_blocks must be 0 (1 024) .. 16 384");
+    }
     const int32_t rank = R.rank, world = R.world;
     if (!G->f.open(path, G->error) || !read_bam_header(G->f, G->D, G->ref_id, &G->hdr_bytes)) {
         set_error(G->error.empty() ? G->D.error : G->error);
@@ -1808,6 +1829,19 @@ extern "C" int coral_bamgpu_open_request_ordered(const char *path, int32_t n_thr
     size_t tmp = 0;
     (void)hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, (long long *)nullptr, (long long *)nullptr, (int)std::min<size_t>(G->rec_cap + 1, 0x7fffffff));
     G->scan_tmp_bytes = tmp + 256;
+    if (to_file && to_file->as_text) {
+        TextSink &S = G->reads.text_sink;
+        S.on = true;
+        S.path = to_file->out_path;
+        if (!(S.fp = fopen(to_file->out_path, "wb"))) return fail(CORAL_ERR_ARG, std::string("cannot create ") + to_file->out_path);
+    } else if (to_file) {                      // (last: nothing is created for a request that is refused)
+        RecordSink &S = G->reads.sink;
+        S.on = true;
+        S.path = to_file->out_path;
+        S.header.assign(to_file->header, to_file->header + to_file->header_bytes);
+        S.chunk = to_file->chunk_blocks > 0 ? (size_t)to_file->chunk_blocks : DEFL_CHUNK_BLOCKS;
+        if (!(S.fp = fopen(to_file->out_path, "wb"))) return fail(CORAL_ERR_ARG, std::string("cannot create ") + to_file->out_path);
+    }
     int rc = CORAL_OK;                         // what rides along: each request takes its part of R (and what of it needs the header or the capacities)
     if (!each_request(G.get(), [&](auto &r) { return (rc = r.open(R, G->caps(), G->D, err)) == CORAL_OK; }, true)) { set_error(err); return rc; }
     carve(G.get(), nullptr, 0);
@@ -1815,6 +1849,42 @@ extern "C" int coral_bamgpu_open_request_ordered(const char *path, int32_t n_thr
     G->known_start = CARRY_CAP + (long long)(rank == 0 ? G->hdr_bytes : 0);
     *workspace_bytes = (int64_t)G->ws_bytes;
     *handle = G.release();
+    return CORAL_OK;
+}
+}  // namespace
+
+extern "C" int coral_bamgpu_open_request_ordered(const char *path, int32_t n_threads, int64_t batch_bytes, const coral_bam_request_t *req,
+                                                 int32_t reads_order, void **handle, int64_t *workspace_bytes) {
+    return open_decoder(path, n_threads, batch_bytes, req, reads_order, nullptr, handle, workspace_bytes);
+}
+
+// The records of a want_reads = 2 request, in file order, as a BGZF / BAM file written while the decode runs (RecordSink).
+extern "C" int coral_bamgpu_open_request_to_file(const char *path, int32_t n_threads, int64_t batch_bytes, const coral_bam_request_t *req,
+                                                 const char *out_path, const uint8_t *header, int64_t header_bytes, int32_t chunk_blocks,
+                                                 void **handle, int64_t *workspace_bytes) {
+    const SinkArgs to_file{out_path, header, header_bytes, chunk_blocks, false};
+    return open_decoder(path, n_threads, batch_bytes, req, READS_ORDER_FILE, &to_file, handle, workspace_bytes);
+}
+
+// The FASTQ text of a want_reads = 1 request as a plain file written while the decode runs (TextSink).
+extern "C" int coral_bamgpu_open_request_to_text(const char *path, int32_t n_threads, int64_t batch_bytes, const coral_bam_request_t *req,
+                                                 const char *out_path, void **handle, int64_t *workspace_bytes) {
+    const SinkArgs to_file{out_path, nullptr, 0, 0, true};
+    return open_decoder(path, n_threads, batch_bytes, req, READS_ORDER_FILE, &to_file, handle, workspace_bytes);
+}
+
+// records written, their inflated bytes, bytes of the file so far, BGZF members in it (after `finish`: the whole file, EOF block included)
+extern "C" int coral_bamgpu_sink_stats(void *handle, int64_t out[4]) {
+    GpuDecoder *G = (GpuDecoder *)handle;
+    if (!G || !out) return CORAL_ERR_ARG;
+    if (G->reads.text_sink.on) {               // (a text file: its bytes are the text's, and it has no members)
+        const TextSink &T = G->reads.text_sink;
+        out[0] = T.records; out[1] = T.bytes; out[2] = T.bytes; out[3] = 0;
+        return CORAL_OK;
+    }
+    const RecordSink &S = G->reads.sink;
+    if (!S.on) { set_error("coral_bamgpu_sink_stats: the handle writes to no file"); return CORAL_ERR_ARG; }
+    out[0] = S.records; out[1] = S.bytes; out[2] = S.file_bytes; out[3] = S.members;
     return CORAL_OK;
 }
 
@@ -1833,7 +1903,7 @@ extern "C" int coral_bamgpu_finish(void *handle, void *stream_) {
     if (!G->finished || G->have_cur) { set_error("coral_bamgpu_finish: the decode is not finished"); return CORAL_ERR_ARG; }
     if (each_request(G, [](auto &) { return false; })) return CORAL_OK;      // nothing rides along
     if (hipStreamSynchronize((hipStream_t)stream_) != hipSuccess || !each_request(G, [&](auto &r) { return r.finish(G->D, G->n_threads); })) {
-        set_error("coral_bamgpu_finish: copy of the requested results failed");
+        set_error(G->reads.sink.error.empty() ? "coral_bamgpu_finish: copy of the requested results failed" : G->reads.sink.error);
         return CORAL_ERR_HIP;
     }
     if (G->D.idx.unsorted) { set_error("the records are not in coordinate order: no index can be built"); return CORAL_ERR_FORMAT; }
@@ -1873,7 +1943,7 @@ extern "C" int coral_bamgpu_start(void *handle, void *workspace, int64_t workspa
     if ((e = hipStreamCreateWithFlags(&G->s_crc, hipStreamNonBlocking)) != hipSuccess) return bad("hipStreamCreate", e);
     G->t_alloc = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_alloc0).count();
     const char *what = nullptr;
-    if (!each_request(G, [&](auto &r) { return !(what = r.start(G->D, e)); })) return bad(what, e);
+    if (!each_request(G, [&](auto &r) { return !(what = r.start(G->D, e)); })) return G->reads.sink.error.empty() ? bad(what, e) : fail(CORAL_ERR_HIP, G->reads.sink.error);
     G->feeder = std::thread(feeder_main, G);
     G->worker = std::thread(worker_main, G);
     return CORAL_OK;

@@ -1,11 +1,13 @@
 // coral_bamgpu_deflate.h - BGZF blocks made ON THE GPU (included by coral_bamgpu.hip, behind coral_bamgpu_reads.h): the writers
 // behind bam.RecordBytes.write(device=...) and bam.sort_bam(write_device=...) deflate on the device instead of calling zlib on
-// the host (coral_bgzf_write).  Nothing here touches the decode pipeline, its workspace or its kernels.
+// the host (coral_bgzf_write).  The writers touch nothing of the decode pipeline; RecordSink, at the end, is the one piece that
+// does: the file a records request streams to (coral_bamgpu_open_request_to_file), with its arrays in the decode's workspace.
 //
 //   k_bgzf_deflate  one wave per input block of at most 0xff00 bytes: one complete BGZF member (header with BSIZE, one dynamic or
 //                   stored DEFLATE block, CRC-32, ISIZE) into the block's 64 KiB slot - coral_deflate_core.h, the device backend
 //   k_bgzf_pack     hipcub's scan over the member lengths, then one wave per member: the fixed-stride slots gathered into one
 //                   contiguous byte string with reads_window / reads_run (coral_bamgpu_reads.h)
+//   k_bgzf_chunk_desc  the descriptors of a chunk of consecutive 0xff00-byte blocks, made on the device (RecordSink)
 //
 // Replaces what the reference's workflow gets from `samtools view -b` / `samtools sort` when they write their output
 // (/root/reference/scripts/align_nanopore_reads.sh:44, :49: htslib's bgzf_write + zlib deflate).
@@ -241,3 +243,161 @@ inline int bgzf_write_gpu(const char *path, const uint8_t *const *parts, const i
     if (!io_ok) { set_error(std::string("writing ") + path + " failed"); return CORAL_ERR_FORMAT; }
     return CORAL_OK;
 }
+
+// ---- the file sink of a records request (coral_bamgpu_open_request_to_file; ReadsRequest in coral_bamgpu_reads.h) ---------------
+// The descriptors of one chunk, made where they are read: block k of n_blocks is in[k * 0xff00 ..) with 0xff00 bytes (the last
+// one: last_len), its member goes to slot k.
+__global__ __launch_bounds__(WAVE) void k_bgzf_chunk_desc(BlockDesc *__restrict__ desc, int n_blocks, uint32_t last_len) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n_blocks) return;
+    desc[k] = BlockDesc{(uint32_t)k * (uint32_t)coral_deflate::BLOCK_MAX, k == n_blocks - 1 ? last_len : (uint32_t)coral_deflate::BLOCK_MAX,
+                        (uint32_t)k * (uint32_t)coral_deflate::SLOT_BYTES, 0u};
+}
+
+// A BGZF file that grows while the decode runs: the header at `start`, per batch the full 0xff00-byte blocks of the records
+// written so far (the rest, the carry, waits at the front of the request's buffer for the next batch), at `finish` the carry, if
+// any, and the EOF block.  The cuts run through the concatenation of all batches, so the file is coral_bgzf_write_gpu's of the
+// two parts (header, all record bytes).  Chunks of at most `chunk` blocks go through k_bgzf_chunk_desc, k_bgzf_deflate and
+// k_bgzf_pack on the sink's own stream; a chunk's total comes back first (4 bytes), then exactly its packed bytes into one of two
+// pinned buffers, and it is written while the chunk behind it is on the device.  A chunk that was launched last stays in flight
+// when a batch ends: it is taken in by the next batch's first chunk, or by `finish`.
+// A failure leaves the file without the EOF block (readers see it truncated); the destructor closes it.
+struct RecordSink {
+    bool on = false;
+    std::string path, error;
+    std::vector<uint8_t> header;
+    size_t chunk = DEFL_CHUNK_BLOCKS;
+    FILE *fp = nullptr;
+    // device memory (carved by the request) and what the sink owns: its stream, events and pinned buffers
+    uint8_t *slots = nullptr, *packed = nullptr;
+    BlockDesc *desc = nullptr;
+    uint32_t *member = nullptr, *off = nullptr;
+    void *tokens = nullptr, *tmp = nullptr;
+    hipStream_t s = nullptr;
+    hipEvent_t ev_copied = nullptr, ev_moved = nullptr, ev_total = nullptr, ev_out = nullptr;
+    uint8_t *h_out[2] = {nullptr, nullptr};
+    uint32_t *h_total = nullptr;
+    bool moved = false;                  // ev_moved has been recorded: the next batch's copy waits for it
+    long long carry = 0;                 // bytes at the front of the buffer that belong to the next block
+    int launched_blocks = 0;             // blocks of the chunk in flight (0: none)
+    size_t n_chunks = 0;                 // chunks launched so far (chunk c comes back through h_out[c & 1])
+    int64_t records = 0, bytes = 0, file_bytes = 0, members = 0;
+
+    bool fail(const std::string &what) { if (error.empty()) error = "record sink: " + what; return false; }
+    bool ok(hipError_t e, const char *what) { return e == hipSuccess || fail(std::string(what) + ": " + hipGetErrorString(e)); }
+
+    void carve(Carver &take) {
+        slots = (uint8_t *)take(chunk * coral_deflate::SLOT_BYTES);
+        packed = (uint8_t *)take(chunk * coral_deflate::SLOT_BYTES);
+        desc = (BlockDesc *)take(chunk * sizeof(BlockDesc));
+        member = (uint32_t *)take(chunk * 4);
+        off = (uint32_t *)take((chunk + 1) * 4);
+        tokens = take(deflate_scratch_bytes((long long)chunk));
+        tmp = take(DEFL_SCAN_TMP);
+    }
+    bool start() {
+        bool good = ok(hipStreamCreateWithFlags(&s, hipStreamNonBlocking), "hipStreamCreate") &&
+                    ok(hipHostMalloc((void **)&h_total, 256, hipHostMallocDefault), "hipHostMalloc");
+        for (hipEvent_t *e : {&ev_copied, &ev_moved, &ev_total, &ev_out}) good = good && ok(hipEventCreateWithFlags(e, hipEventDisableTiming), "hipEventCreate");
+        for (int i = 0; i < 2 && good; ++i) good = ok(hipHostMalloc((void **)&h_out[i], chunk * coral_deflate::SLOT_BYTES, hipHostMallocDefault), "hipHostMalloc");
+        return good;
+    }
+    // The chunk in flight: its total, then its packed bytes into its pinned buffer.  n = 0: there is none.
+    bool take_in(uint8_t *&data, size_t &n) {
+        n = 0;
+        if (launched_blocks == 0) return true;
+        const size_t nb = (size_t)launched_blocks;
+        launched_blocks = 0;
+        if (!ok(hipEventSynchronize(ev_total), "hipEventSynchronize")) return false;
+        const size_t total = *h_total;
+        if (total < nb * 26 || total > nb * (size_t)coral_deflate::MEMBER_MAX) return fail("the packed chunk has an impossible size");
+        data = h_out[(n_chunks - 1) & 1];
+        if (!ok(hipMemcpyAsync(data, packed, total, hipMemcpyDeviceToHost, s), "hipMemcpyAsync") || !ok(hipEventRecord(ev_out, s), "hipEventRecord")) return false;
+        n = total;
+        members += (int64_t)nb;
+        return true;
+    }
+    bool write_out(const uint8_t *data, size_t n) {      // (behind take_in: the bytes are on their way)
+        if (n == 0) return true;
+        if (!ok(hipEventSynchronize(ev_out), "hipEventSynchronize")) return false;
+        if (fwrite(data, 1, n, fp) != n) return fail("writing " + path + " failed");
+        file_bytes += (int64_t)n;
+        return true;
+    }
+    // n_blocks <= chunk blocks at `in` (device; the last one last_len bytes), queued on the sink's stream behind what is there; the
+    // chunk in front comes back and is written while this one runs.
+    bool submit(const uint8_t *in, int n_blocks, uint32_t last_len) {
+        uint8_t *data = nullptr;
+        size_t n = 0;
+        if (!take_in(data, n)) return false;                         // (its copy is queued in front of this chunk's pack: `packed` is free)
+        hipLaunchKernelGGL(k_bgzf_chunk_desc, dim3((unsigned)((n_blocks + WAVE - 1) / WAVE)), dim3(WAVE), 0, s, desc, n_blocks, last_len);
+        if (!ok(hipGetLastError(), "k_bgzf_chunk_desc") ||
+            !ok(launch_deflate(in, (const uint32_t *)desc, n_blocks, slots, member, tokens, s), "k_bgzf_deflate") ||
+            !ok(launch_pack(slots, member, n_blocks, packed, off, tmp, DEFL_SCAN_TMP, s), "k_bgzf_pack") ||
+            !ok(hipMemcpyAsync(h_total, off + n_blocks, 4, hipMemcpyDeviceToHost, s), "hipMemcpyAsync") || !ok(hipEventRecord(ev_total, s), "hipEventRecord"))
+            return false;
+        launched_blocks = n_blocks;
+        ++n_chunks;
+        return write_out(data, n);
+    }
+    // `n` bytes at `in` as whole blocks, the last one shorter when n is no multiple of 0xff00, in chunks
+    bool submit_all(const uint8_t *in, size_t n) {
+        const size_t nb = (n + coral_deflate::BLOCK_MAX - 1) / coral_deflate::BLOCK_MAX;
+        for (size_t c0 = 0; c0 < nb; c0 += chunk) {
+            const size_t k = std::min(chunk, nb - c0);
+            const size_t last = c0 + k == nb ? n - (nb - 1) * coral_deflate::BLOCK_MAX : (size_t)coral_deflate::BLOCK_MAX;
+            if (!submit(in + c0 * coral_deflate::BLOCK_MAX, (int)k, (uint32_t)last)) return false;
+        }
+        return true;
+    }
+    // The header, through `buf` (the request's buffer, cap bytes; nothing else uses it yet): it ends a block.
+    bool write_header(uint8_t *buf, size_t cap) {
+        const size_t piece = std::min(chunk, cap / coral_deflate::BLOCK_MAX) * coral_deflate::BLOCK_MAX;
+        for (size_t at = 0; at < header.size(); at += piece) {
+            const size_t n = std::min(piece, header.size() - at);
+            if (!ok(hipMemcpyAsync(buf, header.data() + at, n, hipMemcpyHostToDevice, s), "hipMemcpyAsync") || !submit_all(buf, n)) return false;
+        }
+        moved = true;                                // (the first batch's copy waits for the header's deflate, which reads `buf`)
+        return ok(hipEventRecord(ev_moved, s), "hipEventRecord");
+    }
+    // One batch: `n` new bytes stand at buf + carry, written by a kernel on `stream`.  Its full blocks are deflated, the rest moves
+    // to the front (source and destination cannot overlap: the tail is shorter than one block, and at least one block lies in
+    // front of it).
+    bool batch(uint8_t *buf, long long n, long long n_records, hipStream_t stream) {
+        if (!ok(hipEventRecord(ev_copied, stream), "hipEventRecord") || !ok(hipStreamWaitEvent(s, ev_copied, 0), "hipStreamWaitEvent")) return false;
+        const long long total = carry + n, n_full = total / coral_deflate::BLOCK_MAX, tail = total - n_full * coral_deflate::BLOCK_MAX;
+        if (n_full > 0 && !submit_all(buf, (size_t)(n_full * coral_deflate::BLOCK_MAX))) return false;
+        if (n_full > 0 && tail > 0 && !ok(hipMemcpyAsync(buf, buf + n_full * coral_deflate::BLOCK_MAX, (size_t)tail, hipMemcpyDeviceToDevice, s), "hipMemcpyAsync")) return false;
+        if (!ok(hipEventRecord(ev_moved, s), "hipEventRecord")) return false;
+        moved = true;
+        carry = tail;
+        records += n_records;
+        bytes += n;
+        return true;
+    }
+    // The next batch's copy kernel on `stream` writes behind the carry: behind the tail move, and behind the deflate that read the buffer.
+    bool wait_moved(hipStream_t stream) { return !moved || ok(hipStreamWaitEvent(stream, ev_moved, 0), "hipStreamWaitEvent"); }
+    bool finish(uint8_t *buf) {
+        if (carry > 0 && !submit_all(buf, (size_t)carry)) return false;
+        carry = 0;
+        uint8_t *data = nullptr;
+        size_t n = 0;
+        if (!take_in(data, n) || !write_out(data, n)) return false;
+        static const uint8_t EOF_BLOCK[28] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0, 0x1b, 0, 0x03, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        bool good = fwrite(EOF_BLOCK, 1, 28, fp) == 28;
+        good = (fclose(fp) == 0) && good;
+        fp = nullptr;
+        if (!good) return fail("writing " + path + " failed");
+        file_bytes += 28;
+        ++members;
+        return true;
+    }
+    ~RecordSink() {
+        if (s) (void)hipStreamSynchronize(s);        // (its kernels work in the caller's workspace, which is about to be released)
+        if (fp) fclose(fp);
+        for (hipEvent_t e : {ev_copied, ev_moved, ev_total, ev_out}) if (e) (void)hipEventDestroy(e);
+        for (int i = 0; i < 2; ++i) if (h_out[i]) (void)hipHostFree(h_out[i]);
+        if (h_total) (void)hipHostFree(h_total);
+        if (s) (void)hipStreamDestroy(s);
+    }
+};

@@ -2,6 +2,8 @@
 //   k_bam_reads_plan + k_bam_reads_emit   the selected records as FASTQ text (nibbles -> ASCII, reverse strand mirrored
 //                   and complemented), scattered to scanned offsets of a per-batch buffer the host collects one batch later
 //   k_bam_reads_copy   want_reads = 2: the selected records' own bytes, gathered to the same scanned offsets
+//   k_bam_reads_copy_shifted   the same into a buffer whose head holds bytes carried over: a request that writes to a file
+//                   (RecordSink in coral_bamgpu_deflate.h; TextSink, below, is the plain file of a FASTQ request)
 //   k_bam_sort_keys + k_bam_sort_permute + k_bam_reads_copy_sorted   reads_order = 1: the same bytes in coordinate order
 // Kernels, device structs and the host-side request in one place; included by coral_bamgpu.hip inside its anonymous namespace
 // (once, behind coral_bamgpu_common.h), not a header of its own.
@@ -183,6 +185,23 @@ __global__ __launch_bounds__(WAVE) void k_bam_reads_copy(const uint8_t *__restri
     }
 }
 
+// k_bam_reads_copy for a request that writes to a file (RecordSink): the batch's records land `shift` bytes into `out`, behind the
+// bytes the batch in front left for this one's first block.  The shift goes into the origin, not into the pointer: reads_run
+// stores aligned 16-byte chunks relative to `out`, which stays 16-byte aligned; the chunk the carried bytes share with the
+// batch's first record is one of reads_run's edge chunks, stored byte by byte.
+__global__ __launch_bounds__(WAVE) void k_bam_reads_copy_shifted(const uint8_t *__restrict__ buf, long long buf_bytes, const long long *__restrict__ rec_start,
+                                                                 long long n_rec, const long long *__restrict__ item_off,
+                                                                 const long long *__restrict__ out_off, long long shift, uint8_t *__restrict__ out) {
+    const int lane = threadIdx.x;
+    const long long total = item_off[n_rec];
+    for (long long w = blockIdx.x; w < total; w += gridDim.x) {
+        const long long i = item_record(item_off, n_rec, w);
+        const long long rs = rec_start[i], at = out_off[i], bytes = out_off[i + 1] - at;
+        const long long a = (w - item_off[i]) * READS_COPY_SLICE, b = min(bytes, a + READS_COPY_SLICE);
+        reads_run(out, at + shift, a, b, lane, [&](long long j0) { return reads_window(buf, rs + j0, buf_bytes); });
+    }
+}
+
 // Coordinate order (reads_order = 1 of a records request): between the plan and the scans the batch's records are sorted by
 // reads_sort_key - hipcub's radix sort of (key, ordinal), stable, so records with equal keys keep their file order - and
 // everything behind works on sorted positions: position j holds record ord[j].  All three kernels are one-wave workgroups
@@ -224,9 +243,36 @@ __global__ __launch_bounds__(WAVE) void k_bam_reads_copy_sorted(const uint8_t *_
     }
 }
 
+#include "coral_bamgpu_deflate.h"      // RecordSink; its kernels use reads_window / reads_run above
+
 // ---- host side: the request's lifecycle (each_request in coral_bamgpu.hip, which calls all but open only when `active`) ---------
+// The plain file a FASTQ request writes to (coral_bamgpu_open_request_to_text): each batch's text goes there where `collect` would
+// append it to the host-side result - no compression, no carry.  A failure leaves what was written; the destructor closes the file.
+struct TextSink {
+    bool on = false;
+    std::string path;
+    FILE *fp = nullptr;
+    std::vector<uint8_t> host;           // one batch's text on its way to the file
+    int64_t records = 0, bytes = 0;
+    bool write(const void *dev, long long &pending) {
+        host.resize((size_t)pending);
+        const bool ok = dev_get(host.data(), dev, host.size()) && fwrite(host.data(), 1, host.size(), fp) == host.size();
+        bytes += pending;
+        pending = 0;
+        return ok;
+    }
+    bool finish() {
+        const bool ok = fclose(fp) == 0;
+        fp = nullptr;
+        return ok;
+    }
+    ~TextSink() { if (fp) fclose(fp); }
+};
+
 struct ReadsRequest {                // FASTQ text, or the own bytes (R->mode), of the selected records
     bool active = false;
+    RecordSink sink;                 // sink.on (coral_bamgpu_open_request_to_file): the records go to a BGZF file, not to the host-side result
+    TextSink text_sink;              // text_sink.on (coral_bamgpu_open_request_to_text): the FASTQ text goes to a plain file
     const ReadsRule *R = nullptr;    // the request (Request::reads)
     ReadsDev X{};
     uint8_t *text = nullptr;         // the batch's text: one buffer for all batches (collect)
@@ -243,6 +289,10 @@ struct ReadsRequest {                // FASTQ text, or the own bytes (R->mode), 
     int open(const Request &Q, const Caps &C, Decoded &, std::string &err) {
         active = Q.reads.on;
         R = &Q.reads;
+        if (sink.on) {
+            sink.chunk = std::min(sink.chunk, C.batch_cap / coral_deflate::BLOCK_MAX + 2);      // (no batch can fill more)
+            if (pack_tmp_bytes((int)sink.chunk) > DEFL_SCAN_TMP) { err = "coral_bamgpu_open_request_to_file: hipcub asks for more temporary storage than reserved"; return CORAL_ERR_HIP; }
+        }
         if (!ordered()) return CORAL_OK;
         // the sort's temporary storage, queried once for the largest batch, as the scan's is
         hipcub::DoubleBuffer<unsigned long long> keys(nullptr, nullptr);
@@ -258,7 +308,8 @@ struct ReadsRequest {                // FASTQ text, or the own bytes (R->mode), 
     // at least 36 + n + 1.5 l bytes of the batch (block_size, the fixed fields, the name, SEQ, QUAL) and its text 2 l + n + 5, and
     // 2 l + n + 5 <= 4/3 (36 + n + 1.5 l) = 48 + 4/3 n + 2 l.  So the text of all records of a batch fits 4/3 of the batch's bytes,
     // the carried ones included (+ 256: the division's remainder and room to spare).  In mode READS_AS_RECORDS the written bytes
-    // are a part of the batch's own: one batch's capacity + 256.
+    // are a part of the batch's own: one batch's capacity + 256.  With a sink: + 0xff00 for the bytes carried in front, and the
+    // sink's own arrays - only then.
     void carve(Carver &take, const Caps &C, const Decoded &) {
         if (ordered()) {
             for (int i = 0; i < 2; ++i) { sort_key[i] = (unsigned long long *)take(C.rec_slots * 8); sort_ord[i] = (uint32_t *)take(C.rec_slots * 4); }
@@ -272,16 +323,19 @@ struct ReadsRequest {                // FASTQ text, or the own bytes (R->mode), 
         int64_t *off = (int64_t *)take((n_names + 1) * 8);
         X = ReadsDev{seg, seg + n_seg, seg + 2 * n_seg, names, off, (int)n_seg, (long long)n_names, R->exclude_flags, R->mode};
         text_cap = (R->mode == READS_AS_RECORDS ? C.batch_cap : C.batch_cap / 3 * 4) + 256;
-        text = (uint8_t *)take(text_cap);
+        text = (uint8_t *)take(text_cap + (sink.on ? (size_t)coral_deflate::BLOCK_MAX : 0));
+        if (sink.on) sink.carve(take);
     }
-    const char *start(const Decoded &, hipError_t &e) const {
+    const char *start(const Decoded &, hipError_t &e) {
         const size_t b = (size_t)X.n_seg * 4;
         const bool ok = (b == 0 || ((e = hipMemcpy((void *)X.tid, R->tid.data(), b, hipMemcpyHostToDevice)) == hipSuccess &&
                                     (e = hipMemcpy((void *)X.lo, R->lo.data(), b, hipMemcpyHostToDevice)) == hipSuccess &&
                                     (e = hipMemcpy((void *)X.hi, R->hi.data(), b, hipMemcpyHostToDevice)) == hipSuccess)) &&
                         (X.n_names == 0 || ((e = hipMemcpy((void *)X.names, R->names.data(), R->names.size(), hipMemcpyHostToDevice)) == hipSuccess &&
                                             (e = hipMemcpy((void *)X.name_off, R->name_off.data(), R->name_off.size() * 8, hipMemcpyHostToDevice)) == hipSuccess));
-        return ok ? nullptr : "reads request set-up";
+        if (!ok) return "reads request set-up";
+        if (sink.on && !(sink.start() && sink.write_header(text, text_cap))) { e = hipGetLastError(); return "record sink set-up"; }
+        return nullptr;
     }
     // It waits for its own totals (16 bytes: no read-back of the batch lies behind these kernels, so they are a small copy of their
     // own, as k_bam_keep_compact's count is).  The text itself is not waited for (collect).
@@ -314,9 +368,22 @@ struct ReadsRequest {                // FASTQ text, or the own bytes (R->mode), 
         const long long bytes = off[(size_t)n];
         if (bytes < 0 || (size_t)bytes > text_cap || items < 0) { err = "reads request: the batch's text does not fit its buffer"; return false; }
         if (bytes == 0) return true;                     // no record of the batch is written: nothing more is queued
+        if (sink.on) {                                   // to the file: behind the carried bytes, and nothing for the host-side result
+            long long written = 0;
+            for (long long i = 0; i < n; ++i) written += off[(size_t)i + 1] > off[(size_t)i];
+            if (!sink.wait_moved(B.stream)) { err = sink.error; return false; }
+            hipLaunchKernelGGL(k_bam_reads_copy_shifted, dim3((unsigned)std::min<long long>(items, 2048)), dim3(WAVE), 0, B.stream, B.buf, (long long)buf_bytes,
+                               B.rec_start, n, item_off, out_off, sink.carry, text);
+            if (!launched("reads", err)) return false;
+            if (!sink.batch(text, bytes, written, B.stream)) { err = sink.error; return false; }
+            return true;
+        }
         const int64_t base = B.D.reads_off.back();
         for (long long i = 0; i < n; ++i)
-            if (off[(size_t)i + 1] > off[(size_t)i]) B.D.reads_off.push_back(base + off[(size_t)i + 1]);
+            if (off[(size_t)i + 1] > off[(size_t)i]) {
+                if (text_sink.on) ++text_sink.records;
+                else B.D.reads_off.push_back(base + off[(size_t)i + 1]);
+            }
         // one wave per workgroup, grid-stride beyond 8 per CU
         const dim3 grid((unsigned)std::min<long long>(items, 2048));
         if (ord)
@@ -332,12 +399,25 @@ struct ReadsRequest {                // FASTQ text, or the own bytes (R->mode), 
     // The text of the batch emitted last, if it is still on the device (the caller has synchronised the stream).  One buffer for
     // all batches: QcRequest::collect's argument, under the same condition - every emit of a decode and the result call are
     // given the SAME stream.
-    bool collect(Decoded &D) { return collect_pending(D.reads_text, text, pending_bytes); }
+    bool collect(Decoded &D) { return text_sink.on ? text_sink.write(text, pending_bytes) : collect_pending(D.reads_text, text, pending_bytes); }
     // Coordinate order: every batch left one sorted run (D.reads_runs: the written record it begins at); more than one run goes
     // through the host's stable k-way merge, run order = batch order, and the runs are freed.
     bool finish(Decoded &D, int n_threads) {
         D.has_reads = true;
+        if (sink.on) {
+            if (!sink.finish(text)) return false;
+            D.reads_to_file = true;
+            D.reads_file_records = sink.records;
+            D.reads_file_bytes = sink.bytes;
+            return true;
+        }
         if (!collect(D)) return false;
+        if (text_sink.on) {
+            D.reads_to_file = true;
+            D.reads_file_records = text_sink.records;
+            D.reads_file_bytes = text_sink.bytes;
+            return text_sink.finish();
+        }
         if (!ordered() || D.reads_runs.size() < 2) return true;
         const size_t n_runs = D.reads_runs.size(), n_rec = D.reads_off.size() - 1;
         std::vector<const uint8_t *> data(n_runs, D.reads_text.data());

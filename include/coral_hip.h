@@ -514,7 +514,8 @@ typedef struct {
  * and QUAL reversed, so the read has the orientation it was sequenced in.  Nothing is appended to the name; records come in
  * file order.  Allowed on byte ranges (the texts of consecutive ranges concatenate) and on span decodes, not with want_index.
  *   reads_sizes -> records written, text bytes; reads_fill copies the text and the n + 1 int64 offsets of the records in it.
- *   The whole result lives in host memory: meant for the reads of an amplicon, not for a whole 2 M-read file.
+ *   The whole result lives in host memory: meant for the reads of an amplicon; for every read of a 2 M-read file the GPU
+ *   pipeline writes the same text to a file batch by batch: coral_bamgpu_open_request_to_text.
  *
  * Records (want_reads = 2) - the same selection with the alignments kept: what `samtools view -b x.bam region... > amp.bam`
  * gets from a second pass, for a genome browser or any tool that reads BAM.  reads_exclude_flags, reads_seg_*, reads_names /
@@ -526,8 +527,9 @@ typedef struct {
  * it is) - one record after the other in file order.  Allowed on byte ranges (the outputs of consecutive ranges concatenate)
  * and on span decodes, not with want_index.
  *   reads_sizes -> records written, total bytes; reads_fill copies the bytes and the n + 1 int64 offsets of the records.
- *   The whole result lives in host memory: meant for the records of an amplicon, not for a whole 2 M-read file; nothing is
- *   streamed to disk.  coral_bgzf_write puts a header and such bytes into a BGZF / BAM file. */
+ *   The whole result lives in host memory: meant for the records of an amplicon.  coral_bgzf_write puts a header and such bytes
+ *   into a BGZF / BAM file.  For a whole 2 M-read file the GPU pipeline streams the same records to disk in bounded host
+ *   memory: coral_bamgpu_open_request_to_file. */
 int coral_bam_decode_request(const char *path, int32_t n_threads, const coral_bam_request_t *req, void **handle);
 int coral_bam_coverage_result(void *handle, int32_t n_seg, int64_t *counts);
 int coral_bam_pileup_result(void *handle, int64_t n_pos, uint32_t *counts);
@@ -638,6 +640,33 @@ int coral_bam_records_merge(int32_t n_runs, const uint8_t *const *data, const in
  *          handle of `host` (coral_bam_coverage_result, coral_bam_pileup_result - the table is copied and summed per segment
  *          here -, coral_bam_index_sizes / _fill, coral_bam_qc_sizes / _fill, coral_bam_depth_sizes / _fill, coral_bam_reads_sizes / _fill); fails when
  *          an index was requested and the records are not in coordinate order; with nothing requested it does nothing
+ *   open_request_to_file  open_request for a want_reads = 2 request in file order whose records go to the BGZF / BAM file
+ *          `out_path` WHILE the decode runs, deflated where they are: uncompressed record bytes never leave the device, and the
+ *          host keeps two pinned buffers of one chunk whatever the file's size.  The file is exactly coral_bgzf_write_gpu's of
+ *          the two parts (header, all written record bytes): each part cut at 0xff00 bytes, the header ending a block, no empty
+ *          member, the EOF block last; its bytes do not depend on batch_bytes, chunk_blocks or the run.  `header`: the inflated
+ *          header to write (`header_bytes` > 0); chunk_blocks: blocks per deflate launch, 0 = 1 024, at most 16 384.  Spans are
+ *          allowed.  `start` creates the sink's stream and pinned buffers and deflates the header.  Per batch, behind the plan's
+ *          read-back: k_bam_reads_copy_shifted puts the batch's records behind the `carry` (< 0xff00) bytes the batch in front
+ *          left at the head of the buffer (0xff00 bytes larger for that), the full blocks go in chunks through
+ *          k_bgzf_chunk_desc (descriptors made on the device), k_bgzf_deflate and k_bgzf_pack on the sink's stream - behind an
+ *          event recorded after the copy kernel, so the slot's reuse does not wait for them -, the tail moves to the front
+ *          (device to device), and the next batch's copy kernel waits for an event behind that move.  A chunk's packed bytes
+ *          come back once (4 bytes for their number first) and are written while the next chunk is on the device.  A batch that
+ *          writes nothing queues nothing.  `finish` deflates the carry as the last block (none when it is 0), writes the EOF
+ *          block and closes the file.  The slots, packed bytes, tokens, descriptors, lengths, offsets and scan storage of one
+ *          chunk are part of *workspace_bytes only for such a request.  Nothing is kept on the host: coral_bam_reads_sizes gives
+ *          records written and their inflated bytes, coral_bam_reads_fill is CORAL_ERR_ARG.  On any failure the file is left
+ *          without the EOF block (readers see it truncated); `close` closes it.
+ *          CORAL_ERR_ARG: want_reads other than 2, world above 1, no out_path, no header, chunk_blocks outside 0..16 384, a
+ *          path that cannot be created (and every refusal of open_request).
+ *   open_request_to_text  the same for FASTQ: open_request for a want_reads = 1 request whose text goes to the plain file
+ *          `out_path` - each batch's text is written where it would be appended to the host-side result (one batch later, once
+ *          the next emit or `finish` has synchronised the stream); no compression, no carry, nothing new in the workspace.  The
+ *          bytes are those coral_bam_reads_fill would give.  reads_sizes / reads_fill as for open_request_to_file; `finish`
+ *          closes the file.  CORAL_ERR_ARG: want_reads other than 1, world above 1, no out_path, a path that cannot be created.
+ *   sink_stats  of such a handle: out = records written, their inflated bytes, bytes of the file, BGZF members in it (after
+ *          `finish`: the whole file, header and EOF members included; a text file: its bytes twice and 0)
  * coral_bgzf_inflate: one inflate launch over caller-provided device buffers — desc = n_blocks x {src_off, src_len,
  * dst_off, isize} uint32 (raw DEFLATE streams in `comp`, which must be readable 4096 bytes beyond the last stream);
  * status[b] = 0 or the decoder's error code.
@@ -653,6 +682,12 @@ int coral_bamgpu_open_request(const char *path, int32_t n_threads, int64_t batch
                               void **handle, int64_t *workspace_bytes);
 int coral_bamgpu_open_request_ordered(const char *path, int32_t n_threads, int64_t batch_bytes, const coral_bam_request_t *req,
                                       int32_t reads_order, void **handle, int64_t *workspace_bytes);
+int coral_bamgpu_open_request_to_file(const char *path, int32_t n_threads, int64_t batch_bytes, const coral_bam_request_t *req,
+                                      const char *out_path, const uint8_t *header, int64_t header_bytes, int32_t chunk_blocks,
+                                      void **handle, int64_t *workspace_bytes);
+int coral_bamgpu_open_request_to_text(const char *path, int32_t n_threads, int64_t batch_bytes, const coral_bam_request_t *req,
+                                      const char *out_path, void **handle, int64_t *workspace_bytes);
+int coral_bamgpu_sink_stats(void *handle, int64_t out[4]);
 int coral_bamgpu_finish(void *handle, void *stream);
 int coral_bamgpu_close(void *handle);
 int coral_bgzf_inflate(const uint8_t *comp, const uint32_t *desc, int32_t n_blocks, uint8_t *out, int32_t *status,
