@@ -120,6 +120,12 @@ def lib():
                                  C.POINTER(C.c_int32), P]
     L.coral_sa_last_error.restype = C.c_char_p
     L.coral_hash_rows.argtypes = [C.c_int32, P, C.c_int32, P, P, P, P, P, C.c_int32, P, C.c_int64, P, P, P, P, C.POINTER(C.c_int32), P]
+    L.coral_segment_coverage_host.argtypes = [R, P, C.c_int32, P, P, P, P]
+    L.coral_hash_rows_host.argtypes = [C.c_int32, P, C.c_int32, P, P, C.c_int32, P, P, P, P, C.POINTER(C.c_int32), P]
+    L.coral_point_cover_host.argtypes = [R, C.c_int32, P, P, C.c_int32, C.c_uint32, P, P, C.POINTER(C.c_uint32), P]
+    L.coral_query_arena_release.argtypes = []
+    L.coral_sa_table_async.argtypes = [C.c_int32, P, P, P, P, C.c_int32, C.c_int32, P, P, P, P, C.c_int64, P, P, P, P, C.c_int32, C.c_int32,
+                                       C.c_int32, C.c_int32, C.c_int32, P, P, P, P, P, C.POINTER(C.c_int32), P]
     L.coral_pyset_batch_create.argtypes = [C.c_int64, P, P, P, C.c_int32, P]
     L.coral_pyset_batch_create.restype = C.c_void_p
     L.coral_pyset_union_order.argtypes = [C.c_void_p, C.c_int32, P, P, C.POINTER(C.c_int32)]

@@ -343,6 +343,8 @@ class bam_to_breakpoint_nanopore():
         overlap with the scan.  What fetch() would raise is kept and raised there."""
         trace = os.environ.get("CORAL_TRACE_OPEN") == "1"
         t0 = time.perf_counter()
+        if getattr(self.rec, "has_host", False):
+            kernels.sa_table_early(self.rec)          # one GPU: table kernels and table copy in front of the scan (see there)
         self.scan()
         t1 = time.perf_counter()
         try:

@@ -9,6 +9,8 @@ any number of shards.
 from __future__ import annotations
 
 import ctypes as C
+import os
+import weakref
 from typing import List, Sequence, Tuple
 
 import numpy as np
@@ -125,6 +127,37 @@ def cigar_scan(dr, min_gap: int = 600, min_mapq: int = 20, gap_cap: int = 1 << 1
     return ScanResult(summary, pending=gather)
 
 
+def _native_queries(dr) -> bool:
+    """segment_coverage, hash_rows and point_cover as one native call each (coral_*_host: arguments staged through the
+    library's pinned arena, everything queued on the records' stream, one or two host waits) and sa_table as one chain without
+    inner waits (coral_sa_table_async).  One GPU only: with sharded
+    records the local results stay device tensors for the collectives.  CORAL_DEVICE_QUERIES=legacy forces the torch-side
+    path (differential tests, A/B measurements)."""
+    return dr.device.type == "cuda" and dr.world == 1 and os.environ.get("CORAL_DEVICE_QUERIES", "native") != "legacy"
+
+
+def _query_failed(what: str, rc: int):
+    return _lib.CoralHipError("%s failed (%d): %s" % (what, rc, _lib.lib().coral_sa_last_error().decode()))
+
+
+class _Lease:
+    """Pinned buffers of one query result, returned to the pool when the result goes away."""
+
+    def __init__(self, device, bufs):
+        self.device, self._bufs = device, list(bufs)
+
+    def close(self):
+        for buf in self._bufs:
+            _PinnedPool.release(self.device, buf)
+        self._bufs = []
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:          # noqa: BLE001 — interpreter shutdown
+            pass
+
+
 def _disjoint_batches(segs: np.ndarray) -> List[np.ndarray]:
     """Split segment indices into batches that are sorted by (tid, start) and pairwise disjoint."""
     order = np.lexsort((segs[:, 1], segs[:, 0]))
@@ -177,11 +210,20 @@ def segment_coverage(dr, scan: ScanResult, segs: Sequence[Tuple[int, int, int]],
     sg = np.asarray(segs, dtype=np.int64).reshape(S, 3)
     if dr.world > 1 and not _worker:
         sharding.command(dr, sharding.CMD_COVERAGE, payload=sg)
-    out = _coverage_local(dr, scan, sg)
-    if dr.world > 1:
-        out = sharding.allreduce_sum(dr, out)
-    o = out.cpu().numpy()
-    n_reads, n_bases = o[0].copy(), o[1].copy()
+    if _native_queries(dr):
+        sg = np.ascontiguousarray(sg)
+        n_reads, n_bases = np.empty(S, dtype=np.int64), np.empty(S, dtype=np.int64)
+        rs = dr.c_struct()
+        rc = _lib.lib().coral_segment_coverage_host(C.byref(rs), scan.summary.data_ptr(), S, sg.ctypes.data, n_reads.ctypes.data,
+                                                    n_bases.ctypes.data, dr.stream())
+        if rc != 0:
+            raise _query_failed("coral_segment_coverage_host", rc)
+    else:
+        out = _coverage_local(dr, scan, sg)
+        if dr.world > 1:
+            out = sharding.allreduce_sum(dr, out)
+        o = out.cpu().numpy()
+        n_reads, n_bases = o[0].copy(), o[1].copy()
     if len(dr.h_nonacgt_rec):
         # aligned non-ACGT bases inside each segment: two binary searches per segment in the (contig, position)-sorted list of
         # those bases (sorted once per records object) instead of a pass over the list per segment
@@ -213,6 +255,28 @@ def _points_local(dr, uniq: np.ndarray, pair_cap: int) -> torch.Tensor:
         if k <= pair_cap:
             return pairs[:k]
         pair_cap = 1 << int(np.ceil(np.log2(k + 1)))
+
+
+def _point_cover_host(dr, uniq: np.ndarray, pair_cap: int):
+    """coral_point_cover_host on one GPU: (record ordinals int32 [k] in (point, record) order — a view of a leased pinned
+    buffer —, bounds int64 [len(uniq) + 1], the lease).  Too small a pair_cap: launched again with room for all pairs."""
+    L = _lib.lib()
+    t = np.ascontiguousarray(uniq[:, 0], dtype=np.int32)
+    p = np.ascontiguousarray(uniq[:, 1], dtype=np.int32)
+    bounds = np.empty(len(uniq) + 1, dtype=np.int64)
+    rs = dr.c_struct()
+    n = C.c_uint32(0)
+    while True:
+        buf = _PinnedPool.lease(dr.device, 4 * pair_cap)
+        rc = L.coral_point_cover_host(C.byref(rs), len(uniq), t.ctypes.data, p.ctypes.data, dr.max_span, pair_cap, buf.data_ptr(),
+                                      bounds.ctypes.data, C.byref(n), dr.stream())
+        if rc == 0:
+            break
+        _PinnedPool.release(dr.device, buf)
+        if rc != -3:
+            raise _query_failed("coral_point_cover_host", rc)
+        pair_cap = 1 << int(np.ceil(np.log2(int(n.value) + 1)))
+    return buf[:4 * int(n.value)].view(torch.int32).numpy(), bounds, _Lease(dr.device, [buf])
 
 
 class PointCover:
@@ -251,6 +315,11 @@ def point_cover(dr, points: Sequence[Tuple[int, int]], pair_cap: int = 0, _worke
     else:
         uniq, inverse = np.unique(pts, axis=0, return_inverse=True)
     inverse = inverse.reshape(-1)
+    if _native_queries(dr):
+        rec, b, keep = _point_cover_host(dr, uniq, pair_cap)
+        if len(rec) > pair_cap // 2 or len(rec) < pair_cap // 8:
+            dr._pair_cap_hint = max(1 << 16, 1 << int(np.ceil(np.log2(2 * len(rec) + 2))))
+        return PointCover(rec, b[:-1][inverse], b[1:][inverse], keep)
     pairs = _points_local(dr, uniq, pair_cap) + dr.lo                # record ordinal -> global
     if pairs.numel() > pair_cap // 2 or pairs.numel() < pair_cap // 8:
         dr._pair_cap_hint = max(1 << 16, 1 << int(np.ceil(np.log2(2 * pairs.numel() + 2))))
@@ -372,15 +441,106 @@ def _sa_table_local(dr):
     (cols int64[8, n_rows], off int64[n_reads + 1], name_id, failed, read_length (device int32, or a host array), pairs int32[2 * n_rows, 8], device rows,
     staging): the host arrays live in ``staging``'s pinned buffers; everything but ``pairs`` has landed on return, ``pairs``
     after ``staging.wait("pairs")``."""
+    if _native_queries(dr):
+        pending = dr.__dict__.pop("_sa_pending", None)            # (made by sa_table_early, in front of the CIGAR scan)
+        if isinstance(pending, Exception):
+            raise pending
+        return pending if pending is not None else _sa_table_collect(dr, _sa_table_queue(dr))
     d = dr.sa_device_arrays()
     if dr.device.type != "cuda":
         return _sa_table_on_current_stream(dr, d)
-    # on a stream of its own: the table kernels are tiny and have three host round trips, the CIGAR scan launched just before
-    # on the records' stream keeps the GPU busy meanwhile
+    # on a stream of its own: the table kernels are tiny and have three host round trips
     side = _side_stream(dr.device, "table")
     side.wait_stream(torch.cuda.current_stream(dr.device))
     with torch.cuda.stream(side):
         return _sa_table_on_current_stream(dr, d)
+
+
+def sa_table_early(dr):
+    """Build the table of ``sa_table(dr)`` now and keep it for the next ``sa_table(dr)`` call.  A build calls this in FRONT of
+    the CIGAR scan: the scan fills every wave slot of the GPU for its whole run, so whatever is queued behind its launch, on
+    any stream, starts when it ends — the table kernels and the copy kernels that bring the table to the host alike (measured:
+    the chain began 2.7 ms after it was queued; queued in front of the scan with only the counts waited for, the counts were
+    there at once and the table's copy then took those 2.7 ms).  In front of the scan the chain takes 0.5 ms and the copy 0.6,
+    and the host logic that needs the table runs beside the scan instead of behind it.  Nothing happens on the legacy path,
+    with sharded records or on a CPU; what the table raises is kept and raised by ``sa_table``."""
+    if _native_queries(dr) and dr.has_host:
+        try:
+            dr._sa_pending = _sa_table_collect(dr, _sa_table_queue(dr))
+        except Exception as exc:                      # noqa: BLE001 — re-raised where the table is asked for
+            dr._sa_pending = exc
+
+
+def _sa_table_queue(dr, cutoff=100, min_mapq=20, gap_=100, gap_mapq=10):
+    """coral_sa_table_async on the table stream: everything is queued, nothing waited for.  The stream waits for the upload of
+    the SA arrays only (once per records object), not for what is queued on the records' stream."""
+    L = _lib.lib()
+    dev = dr.device
+    d = dr.sa_device_arrays()
+    side = _side_stream(dev, "table")
+    if getattr(dr, "_sa_ready", None) is not None:
+        side.wait_event(dr._sa_ready)
+    n_sa = dr.n_sa
+    cap = max(n_sa, 1)
+    q = dict(n_sa=n_sa, counts=_PinnedPool.lease(dev, 16))
+    with torch.cuda.stream(side):
+        if getattr(dr, "_chr_rank_dev", None) is None:          # a property of the header: uploaded once per records object
+            dr._chr_rank_dev = torch.from_numpy(np.ascontiguousarray(dr.chr_rank, dtype=np.int32)).to(dev)
+        ws_bytes = max(1 << 20, 104 * cap + 8 * dr.n_names + (8 << 20))
+        q["rows"] = torch.empty((cap, 8), dtype=torch.int32, device=dev)
+        q["off"] = torch.empty(cap + 1, dtype=torch.int32, device=dev)
+        q["rl"] = torch.empty(max(dr.n_names, 1), dtype=torch.int32, device=dev)
+        q["pairs"] = torch.empty((2 * cap, 8), dtype=torch.int32, device=dev)
+        q["cols"] = torch.empty(8 * cap, dtype=torch.int64, device=dev)
+        q["off_w"] = torch.empty(cap + 1, dtype=torch.int64, device=dev)
+        q["name_w"] = torch.empty(cap, dtype=torch.int64, device=dev)
+        q["failed_b"] = torch.empty(cap, dtype=torch.bool, device=dev)
+        counts = q["counts"][:16].view(torch.int32)
+        while True:
+            q["ws"] = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)          # (kept until the chain is through)
+            rc = L.coral_sa_table_async(dr.n_total, d["tid"].data_ptr(), d["flagmq"].data_ptr(), d["qlen"].data_ptr(), d["name"].data_ptr(),
+                                        dr.n_names, n_sa, d["sa"].data_ptr(), d["sa_nm"].data_ptr(), d["sa_rec"].data_ptr(),
+                                        q["ws"].data_ptr(), ws_bytes, q["rows"].data_ptr(), q["off"].data_ptr(), q["rl"].data_ptr(),
+                                        dr._chr_rank_dev.data_ptr(), len(dr.chr_rank), cutoff, min_mapq, gap_, gap_mapq,
+                                        q["pairs"].data_ptr(), q["cols"].data_ptr(), q["off_w"].data_ptr(), q["name_w"].data_ptr(),
+                                        q["failed_b"].data_ptr(), C.cast(counts.data_ptr(), C.POINTER(C.c_int32)), dr.stream())
+            if rc != -3:
+                break
+            ws_bytes = (int(counts[0]) + 1) << 20
+        if rc != 0:
+            _PinnedPool.release(dev, q["counts"])
+            raise _query_failed("coral_sa_table_async", rc)
+        q["done"] = torch.cuda.Event()
+        q["done"].record(side)
+    return q
+
+
+def _sa_table_collect(dr, q):
+    """The ONE wait for the counts of a queued coral_sa_table_async, the reference's errors, then the exact-size copies: the
+    table (already in the host's layout: eight int64 columns, offsets, name ids, failed flags) first, the pairs behind it."""
+    import sys
+    import time
+    t0 = time.perf_counter()
+    q["done"].synchronize()
+    n_reads, n_rows, err, _ = (int(v) for v in q["counts"][:16].view(torch.int32))
+    _PinnedPool.release(dr.device, q["counts"])
+    if err == 3:
+        raise KeyError("SA CIGAR shape outside SM/MS/SMS/SMD/MDS/SMDS/SMI/MIS/SMIS")        # cp:255
+    if err == 4:
+        raise ZeroDivisionError("float division by zero")                                # cp:268
+    if err != 0 or not (0 <= n_reads <= q["n_sa"] and 0 <= n_rows <= q["n_sa"]):
+        raise _lib.CoralHipError("coral_sa_table_async: counts %r beyond their bounds" % ((n_reads, n_rows, err),))
+    t1 = time.perf_counter()
+    with torch.cuda.stream(_side_stream(dr.device, "table")):
+        st = Staged(dr)
+        h = st.start("table", dict(cols=q["cols"][:8 * n_rows].view(8, n_rows), off=q["off_w"][:n_reads + 1], name=q["name_w"][:n_reads],
+                                   failed=q["failed_b"][:n_reads]))
+        hp = st.start("pairs", dict(pairs=q["pairs"][:2 * n_rows]))
+        st.wait("table")
+    if os.environ.get("CORAL_TRACE_OPEN") == "1":
+        sys.stderr.write("  sa_table: wait for the counts %.1f ms, copies + wait for the table %.1f ms\n" % (
+            (t1 - t0) * 1e3, (time.perf_counter() - t1) * 1e3))
+    return h["cols"], h["off"], h["name"], h["failed"], q["rl"][:dr.n_names], hp["pairs"], q["rows"][:n_rows], st
 
 
 def _sa_table_on_current_stream(dr, d):
@@ -494,5 +654,30 @@ def _hash_rows_local(dr, T, seg: np.ndarray, tid_has_segs: np.ndarray):
             e_row[:k].to(torch.int64).cpu().numpy())
 
 
+def _hash_rows_host(dr, T, seg: np.ndarray, tid_has_segs: np.ndarray):
+    """coral_hash_rows_host: the same four int64 arrays as ``_hash_rows_local``, written by the device (already widened) into ONE
+    leased pinned buffer; the arrays are views of it, and the buffer goes back to the pool when the last of them is gone."""
+    n_rows = T.n_rows
+    rows = T.dev_rows
+    assert rows is not None and rows.shape == (n_rows, 8) and rows.dtype == torch.int32 and rows.is_contiguous()
+    if n_rows == 0:
+        return tuple(np.zeros(0, dtype=np.int64) for _ in range(4))
+    sg = np.ascontiguousarray(seg, dtype=np.int32)
+    has = np.ascontiguousarray(tid_has_segs, dtype=np.int32)
+    buf = _PinnedPool.lease(dr.device, 8 * 6 * n_rows)
+    whole = buf[:8 * 6 * n_rows].numpy()
+    weakref.finalize(whole, _PinnedPool.release, dr.device, buf).atexit = False          # (at exit the pool goes away anyway)
+    c0, c1, e_key, e_row = (whole[8 * a * n_rows:8 * b * n_rows].view(np.int64) for a, b in ((0, 1), (1, 2), (2, 4), (4, 6)))
+    n_ent = C.c_int32(0)
+    rc = _lib.lib().coral_hash_rows_host(n_rows, rows.data_ptr(), sg.shape[1], sg.ctypes.data, has.ctypes.data, len(has), c0.ctypes.data,
+                                         c1.ctypes.data, e_key.ctypes.data, e_row.ctypes.data, C.byref(n_ent), dr.stream())
+    if rc != 0:
+        raise _query_failed("coral_hash_rows_host", rc)
+    k = int(n_ent.value)
+    return c0, c1, e_key[:k], e_row[:k]
+
+
 def hash_rows(dr, T, seg, tid_has_segs):
+    if _native_queries(dr):
+        return _hash_rows_host(dr, T, seg, tid_has_segs)
     return _hash_rows_local(dr, T, seg, tid_has_segs)

@@ -256,6 +256,10 @@ class DeviceRecords:
                                 name=up(self.h_name_id), sa=up(sa.astype(np.int32)),
                                 sa_nm=up(self.h_sa_nm if len(self.h_sa_nm) else np.zeros(1, dtype=np.int32)),
                                 sa_rec=up(sa_rec if len(sa_rec) else np.zeros(1, dtype=np.int32)))
+            if self.device.type == "cuda":
+                # what a stream other than the uploading one waits for before it reads these arrays (kernels._sa_table_local)
+                self._sa_ready = torch.cuda.Event()
+                self._sa_ready.record(torch.cuda.current_stream(self.device))
         return self._sa_dev
 
     def stream(self) -> int:

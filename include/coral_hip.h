@@ -12,7 +12,8 @@
  *   - `stream` is a hipStream_t passed as void* (NULL = default stream); launches are asynchronous
  *     unless a function says it returns a value read back from the device;
  *   - return value 0 = success, negative = error (see coral_last_error());
- *   - the library allocates nothing on the device: the caller owns all buffers and workspaces;
+ *   - the library allocates nothing on the device: the caller owns all buffers and workspaces (the one exception is the
+ *     query arena of the coral_*_host calls, see there);
  *   - results are integers and order-free (atomics only ever add integers), so they are bit-exact and
  *     independent of wave scheduling; compacted lists are returned unordered together with a sort key
  *     (record ordinal, within-record index) that defines the reference's iteration order.
@@ -149,6 +150,62 @@ int coral_hash_rows(int32_t n_rows, const int32_t *rows, int32_t n_seg, const in
                     const int32_t *seg_end, const int32_t *seg_idx, const int32_t *tid_has_segs, int32_t n_tid,
                     void *workspace, int64_t workspace_bytes, int32_t *cni0, int32_t *cni1, int64_t *e_key, int32_t *e_row,
                     int32_t *n_ent, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * coral_*_host — the three short device queries of a graph build as ONE call each: host arguments in, host results out.
+ *
+ * Unlike the entry points above, these own their device scratch: a per-device query arena of the library (one pinned host
+ * block, one device block, behind a mutex) that grows when a call needs more and is reused otherwise, so a query in steady
+ * state allocates nothing.  A call stages its arguments through the pinned block, queues everything on `stream`, copies the
+ * result back and returns after its last wait; nothing it returns points into the arena.  Results that can be large are
+ * written straight into the caller's buffers (page-locked ones keep the copies asynchronous).  Errors: coral_sa_last_error().
+ * coral_query_arena_release frees the arenas of all devices (tests, unload); the next query allocates again.
+ *
+ * coral_segment_coverage_host: coral_segment_coverage for n_seg half-open segments segs int64[n_seg][3] = (contig id, start,
+ *   end) in ANY order, overlapping or not: they are split into batches of sorted, pairwise disjoint segments (first fit in
+ *   (contig, start) order), all batches are uploaded with one copy, launched one after the other and fetched with one copy
+ *   and ONE wait.  n_reads / n_bases int64[n_seg] (host) are set, in the caller's order.
+ * coral_hash_rows_host: coral_hash_rows with the segment table seg int32[4][n_seg] (contig, start, end, index; sorted by
+ *   (contig, start), disjoint) and tid_has_segs int32[n_tid] on the HOST; cni0 / cni1 int64[n_rows] and the first *n_ent of
+ *   e_key / e_row int64[2 * n_rows] are written to the caller's host buffers, already widened.  Two waits: the entry count,
+ *   then exactly that many entries.
+ * coral_point_cover_host: coral_point_cover for n_pts host points sorted by (contig, position), distinct, followed by a
+ *   device sort of the pairs: rec_out int32[<= pair_cap] (host) = the record ordinals in (point, record) order, bounds
+ *   int64[n_pts + 1] (host) = the first pair of every point (bounds[n_pts] = *n_pairs).  More pairs than pair_cap:
+ *   CORAL_ERR_CAPACITY with *n_pairs = the count needed, nothing else written.  Two waits: the count, then the pairs.
+ * ------------------------------------------------------------------------------------------------ */
+int coral_segment_coverage_host(const coral_records_t *rec, const int32_t *summary /* device [n_rec][4] */, int32_t n_seg,
+                                const int64_t *segs, int64_t *n_reads, int64_t *n_bases, void *stream);
+int coral_hash_rows_host(int32_t n_rows, const int32_t *rows /* device */, int32_t n_seg, const int32_t *seg,
+                         const int32_t *tid_has_segs, int32_t n_tid, int64_t *cni0, int64_t *cni1, int64_t *e_key,
+                         int64_t *e_row, int32_t *n_ent, void *stream);
+int coral_point_cover_host(const coral_records_t *rec, int32_t n_pts, const int32_t *pt_tid, const int32_t *pt_pos,
+                           int32_t max_span, uint32_t pair_cap, int32_t *rec_out, int64_t *bounds, uint32_t *n_pairs,
+                           void *stream);
+int coral_query_arena_release(void);
+
+/* ------------------------------------------------------------------------------------------------
+ * coral_sa_table_async — coral_sa_table and coral_bp_pair_table as one chain on `stream` WITHOUT a host wait (coral_sa_table has
+ * three): the call returns when the chain is queued.  The numbers of groups, reads and rows stay in device memory for the
+ * kernels that need them; grids, sorts and scans are sized by n_sa, which bounds all of them.  Inputs and workspace rule as
+ * coral_sa_table (too small: CORAL_ERR_CAPACITY at once, counts[0] = MiB needed, nothing queued); chr_rank int32[n_tid] (device)
+ * and the four thresholds as coral_bp_pair_table.
+ *   device outputs, capacities by n_sa: out_rows int32[n_sa][8], out_off int32[n_sa + 1] (entries behind the last read =
+ *           the number of rows), out_read_length int32[n_names], pairs int32[2 * n_sa][8] (slots of the first n_rows rows
+ *           written), and the table in the host's layout, ready for exact-size copies: cols int64[8][n_rows] (column
+ *           stride = the number of rows found: the first 8 * n_rows words of a buffer of 8 * n_sa), off_w int64[n_sa + 1],
+ *           name_w int64[n_sa], failed_b uint8[n_sa] (0 / 1)
+ *   counts  PAGE-LOCKED host int32[4], written by a copy at the end of the chain (valid once `stream` has passed it):
+ *           n_reads, n_rows, error code (0; 3 = SA CIGAR outside the nine shapes: CORAL_ERR_FORMAT of coral_sa_table, KeyError
+ *           in the reference; 4 = zero-length query interval: CORAL_ERR_ZERODIV, ZeroDivisionError; with both in a table: 4,
+ *           as coral_sa_table), n_groups.  With an error code the other outputs hold nothing to be used.
+ * ------------------------------------------------------------------------------------------------ */
+int coral_sa_table_async(int32_t n_rec, const int32_t *rec_tid, const int32_t *rec_flagmq, const int32_t *rec_qlen,
+                         const int32_t *rec_name, int32_t n_names, int32_t n_sa, const int32_t *sa, const int32_t *sa_nm,
+                         const int32_t *sa_rec, void *workspace, int64_t workspace_bytes, int32_t *out_rows, int32_t *out_off,
+                         int32_t *out_read_length, const int32_t *chr_rank, int32_t n_tid, int32_t min_bp_match_cutoff,
+                         int32_t min_mapq, int32_t gap_, int32_t gap_mapq, int32_t *pairs, int64_t *cols, int64_t *off_w,
+                         int64_t *name_w, uint8_t *failed_b, int32_t *counts, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * coral_bp_pair_table — the breakpoint candidate of EVERY pair of local alignments of every chimeric read (K4).
