@@ -81,6 +81,19 @@ __device__ __forceinline__ void parse_row(const int32_t *__restrict__ f, int nm,
     o.rb = fwd ? pos1 + al - 2 : pos1 - 1;
 }
 
+// The error field of a table: 0 = none, else ~(2 * ordinal + (code == 4)) of the FIRST offending read, where ordinal is the
+// read's first SA row in file order - the key the reads are sorted by, i.e. the reference's dict order, in which fetch()
+// walks the reads and raises at the first one that offends (ibg:163-173).  A read offends with one code only (an unknown
+// shape ends it at once), ordinal < 2^31, and the complement turns "smallest ordinal" into an unsigned atomicMax over a
+// field that starts at zero.
+__device__ __forceinline__ void sa_report(int32_t *__restrict__ err, int ordinal, int code) {
+    atomicMax(reinterpret_cast<unsigned int *>(err), ~(2u * (unsigned int)ordinal + (code == 4 ? 1u : 0u)));
+}
+// the code (3: unknown SA CIGAR shape, 4: zero-length query interval) of an error field, 0 for none
+__host__ __device__ __forceinline__ int sa_error_code(int32_t field) {
+    return field == 0 ? 0 : ((~(unsigned int)field & 1u) ? 4 : 3);
+}
+
 // one read (group g of the name-sorted SA rows): de-duplicate, check, parse and sort its rows
 __device__ __forceinline__ void group_process_one(int g, const int32_t *__restrict__ gstart, const int32_t *__restrict__ keys,
                                                   const int32_t *__restrict__ vals, const int32_t *__restrict__ sa,
@@ -118,15 +131,16 @@ __device__ __forceinline__ void group_process_one(int g, const int32_t *__restri
     }
     for (int j = 0; j < nk; ++j) {
         const int32_t *f = sa + 8ll * kept_idx[j];
-        if (f[3] == -2) { atomicMax(err, 3); return; }                       // unknown shape: KeyError in the reference
+        if (f[3] == -2) { sa_report(err, vals[a], 3); return; }               // unknown shape: KeyError in the reference
         if ((f[3] <= 0 && f[6] <= 0) || f[4] <= 0) { g_failed[g] = 1; return; }   // no S or no M: ([], [], [])
     }
     // parse + stable insertion sort by (qs, qe) (cp:263), in place in the group's slots of tmp_rows
     ParsedRow *__restrict__ rows = reinterpret_cast<ParsedRow *>(tmp_rows + 8ll * a);
+    bool zero_len = false;
     for (int j = 0; j < nk; ++j) {
         ParsedRow p;
         parse_row(sa + 8ll * kept_idx[j], sa_nm[kept_idx[j]], rl, p);
-        if (p.qe == p.qs) atomicMax(err, 4);                                  // ZeroDivisionError at cp:268
+        zero_len |= p.qe == p.qs;                                             // ZeroDivisionError at cp:268
         int k = j;
         while (k > 0) {
             const ParsedRow q = rows[k - 1];
@@ -136,6 +150,7 @@ __device__ __forceinline__ void group_process_one(int g, const int32_t *__restri
         }
         rows[k] = p;
     }
+    if (zero_len) sa_report(err, vals[a], 4);
     n_kept[g] = nk;
 }
 
@@ -267,6 +282,7 @@ extern "C" int coral_sa_table(int32_t n_rec, const int32_t *rec_tid, const int32
     if (n_rec > 0) hipLaunchKernelGGL(k_first_primary, dim3((n_rec + B - 1) / B), dim3(B), 0, s, n_rec, rec_tid, rec_flagmq, rec_name, first_primary);
     // first_primary values of 0x7f7f7f7f mean "none": normalise to INVALID_KEY and produce read_length
     hipError_t e = hipSuccess;
+    if (out_off) (void)hipMemsetAsync(out_off, 0, sizeof(int32_t), s);      // a table without reads still has its one offset
     if (n_names > 0) hipLaunchKernelGGL(k_read_length, dim3((n_names + B - 1) / B), dim3(B), 0, s, n_names, first_primary, rec_qlen, out_read_length);
     if (n_sa == 0) {
         e = hipStreamSynchronize(s);
@@ -310,8 +326,9 @@ extern "C" int coral_sa_table(int32_t n_rec, const int32_t *rec_tid, const int32
     if (e == hipSuccess) e = hipMemcpyAsync(&n_rows, off + n_groups, sizeof(int32_t), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) return sa_err(CORAL_ERR_HIP, hipGetErrorString(e));
-    if (h[0] == 3) return sa_err(CORAL_ERR_FORMAT, "sa_table: SA CIGAR shape outside SM/MS/SMS/SMD/MDS/SMDS/SMI/MIS/SMIS");
-    if (h[0] == 4) return sa_err(CORAL_ERR_ZERODIV, "sa_table: zero-length query interval (ZeroDivisionError in the reference)");
+    const int code = sa_error_code(h[0]);                // of the first offending read in table order
+    if (code == 3) return sa_err(CORAL_ERR_FORMAT, "sa_table: SA CIGAR shape outside SM/MS/SMS/SMD/MDS/SMDS/SMI/MIS/SMIS");
+    if (code == 4) return sa_err(CORAL_ERR_ZERODIV, "sa_table: zero-length query interval (ZeroDivisionError in the reference)");
     const int n_reads = h[1];
     if (n_reads > 0) {
         hipLaunchKernelGGL(k_scatter, dim3((n_reads + B - 1) / B), dim3(B), 0, s, n_reads, g_sorted, off, gstart, keys_s, n_kept,
@@ -763,8 +780,8 @@ extern "C" int coral_point_cover_host(const coral_records_t *rec, int32_t n_pts,
 
 // ---- coral_sa_table_async ----------------------------------------------------------------------
 // coral_sa_table + coral_bp_pair_table as ONE chain on the stream, without a host wait at all: the number of groups, of reads
-// and of rows stay in device memory (d_cnt = n_reads, n_rows, error code, n_groups) and the kernels that need them read them
-// there; grids, the second sort and the scan are sized by n_sa, which bounds all three.  The call returns when the chain is
+// and of rows stay in device memory (d_cnt = n_reads, n_rows, error field of sa_report - its code when the chain ends -, n_groups) and the kernels that need them
+// read them there; grids, the second sort and the scan are sized by n_sa, which bounds all three.  The call returns when the chain is
 // queued; the caller puts other work behind it (the CIGAR scan of a build) and looks at the counts when its stream is through.
 __global__ void k_group_starts_n(int n, const int32_t *__restrict__ head, const int32_t *__restrict__ gid_incl,
                                  int32_t *__restrict__ gstart, int32_t *__restrict__ d_cnt) {
@@ -804,12 +821,15 @@ __global__ void k_scatter_n(int cap, int32_t *__restrict__ d_cnt, const int32_t 
 
 // The table in the layout the host logic reads: the eight columns of the rows one after the other (column stride = the
 // number of rows) and the per-read arrays, all widened to int64 (failed: one byte, 0 / 1).
-__global__ void k_table_host_layout(int cap, const int32_t *__restrict__ d_cnt, const int32_t *__restrict__ rows,
+// The last kernel of the chain also turns the error field of sa_report into the code the caller reads (d_cnt[2] = 0, 3 or 4:
+// no other thread of this kernel looks at it).
+__global__ void k_table_host_layout(int cap, int32_t *__restrict__ d_cnt, const int32_t *__restrict__ rows,
                                     const int32_t *__restrict__ off, const int32_t *__restrict__ name, const int32_t *__restrict__ failed,
                                     long long *__restrict__ cols, long long *__restrict__ off_w, long long *__restrict__ name_w,
                                     uint8_t *__restrict__ failed_b) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     const int n_reads = d_cnt[0] < cap ? d_cnt[0] : cap, n_rows = d_cnt[1] < cap ? d_cnt[1] : cap;
+    if (i == 0) d_cnt[2] = sa_error_code(d_cnt[2]);
     if (i < n_rows) {
         const int4 lo = reinterpret_cast<const int4 *>(rows)[2ll * i], hi = reinterpret_cast<const int4 *>(rows)[2ll * i + 1];
         const int v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
@@ -913,6 +933,7 @@ extern "C" int coral_sa_table_async(int32_t n_rec, const int32_t *rec_tid, const
                            reinterpret_cast<long long *>(name_w), failed_b);
     } else {
         QUERY_HIP(hipMemsetAsync(d_cnt, 0, 4 * sizeof(int32_t), s));
+        if (off_w) QUERY_HIP(hipMemsetAsync(off_w, 0, sizeof(int64_t), s));      // a table without reads still has its one offset
     }
     QUERY_HIP(hipGetLastError());
     QUERY_HIP(hipMemcpyAsync(counts, d_cnt, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, s));      // lands when the stream gets there

@@ -127,7 +127,8 @@ int coral_point_cover(const coral_records_t *rec, int32_t n_pts, const int32_t *
  *           out_read_length int32[n_names] (-1 = no primary seen);  counts (HOST) = {n_reads, n_rows}
  * `workspace` is device scratch; when it is too small the call returns CORAL_ERR_CAPACITY with counts[0] = MiB needed.
  * Errors mirror the reference: CORAL_ERR_FORMAT = SA CIGAR outside the nine shapes (KeyError, cp:255),
- * CORAL_ERR_ZERODIV = zero-length query interval (ZeroDivisionError, cp:268).  Synchronises `stream`.
+ * CORAL_ERR_ZERODIV = zero-length query interval (ZeroDivisionError, cp:268); when several reads offend, the error is that
+ * of the first of them in table order (the reference walks its dict and raises there).  Synchronises `stream`.
  * ------------------------------------------------------------------------------------------------ */
 int coral_sa_table(int32_t n_rec, const int32_t *rec_tid, const int32_t *rec_flagmq, const int32_t *rec_qlen,
                    const int32_t *rec_name, int32_t n_names, int32_t n_sa, const int32_t *sa, const int32_t *sa_nm,
@@ -197,8 +198,8 @@ int coral_query_arena_release(void);
  *           name_w int64[n_sa], failed_b uint8[n_sa] (0 / 1)
  *   counts  PAGE-LOCKED host int32[4], written by a copy at the end of the chain (valid once `stream` has passed it):
  *           n_reads, n_rows, error code (0; 3 = SA CIGAR outside the nine shapes: CORAL_ERR_FORMAT of coral_sa_table, KeyError
- *           in the reference; 4 = zero-length query interval: CORAL_ERR_ZERODIV, ZeroDivisionError; with both in a table: 4,
- *           as coral_sa_table), n_groups.  With an error code the other outputs hold nothing to be used.
+ *           in the reference; 4 = zero-length query interval: CORAL_ERR_ZERODIV, ZeroDivisionError; with several offending
+ *           reads in a table: the code of the first of them in table order, as coral_sa_table), n_groups.  With an error code the other outputs hold nothing to be used.
  * ------------------------------------------------------------------------------------------------ */
 int coral_sa_table_async(int32_t n_rec, const int32_t *rec_tid, const int32_t *rec_flagmq, const int32_t *rec_qlen,
                          const int32_t *rec_name, int32_t n_names, int32_t n_sa, const int32_t *sa, const int32_t *sa_nm,

@@ -170,6 +170,49 @@ def pair_table_cpu(cols, off, chroms, chr_rank, cutoff=100, min_mapq=20, gap_=10
     return pairs
 
 
+def device_sa_table(rec, device="cuda:0"):
+    """The SA table of ``rec`` on the GPU as a build makes it - sa_table_early in front of the CIGAR scan, sa_table behind it -
+    on the driver that CORAL_DEVICE_QUERIES selects; every array copied out of the staging buffers."""
+    from coral_amd import kernels
+    from coral_amd.records import DeviceRecords
+    dr = DeviceRecords(rec, device)
+    kernels.sa_table_early(dr)          # as a build does: the table in front of the scan, sa_table hands it out
+    kernels.cigar_scan(dr)
+    cols, off, name, failed, rl, pairs, rows, st = kernels.sa_table(dr)
+    assert getattr(dr, "_sa_pending", None) is None
+    st.wait("pairs")
+    out = dict(cols=np.array(cols, copy=True), off=np.array(off, copy=True), name=np.array(name, copy=True), failed=np.array(failed, copy=True),
+               read_length=rl.cpu().numpy(), pairs=np.array(pairs, copy=True), rows=rows.cpu().numpy())
+    st.close()
+    return out
+
+
+def oracle_sa_table(h, chr_rank):
+    """The oracle's fetch() over the records object ``h`` (what fetch() reads, plus ``chroms``), its per-read Python lists turned
+    into the arrays of the product's wrapper: (cols int64 [8, n_rows], off, name id per read, failed, read_length per name id,
+    pair table).  What fetch() raises, this raises."""
+    from oracle import coral_oracle as O
+    ob = O.OracleGraphBuild.__new__(O.OracleGraphBuild)
+    ob.rec, ob.read_length, ob.chimeric_alignments, ob.nm_stats = h, {}, {}, [0.0, 0.0, 0]
+    ob.fetch()
+    name_id_of = {nm: k for k, nm in enumerate(h.names)}
+    tid_of = {c: k for k, c in enumerate(h.chroms)}
+    rows, off, names, failed = [], [0], [], []
+    for rn, ca in ob.chimeric_alignments.items():
+        names.append(name_id_of[rn])
+        failed.append(len(ca) == 3)
+        if len(ca) == 4:
+            for q, ri, mq, nmr in zip(*ca):
+                rows.append([q[0], q[1], tid_of[ri[0]], ri[1], ri[2], 0 if ri[3] == "+" else 1, mq, int(round(nmr * (q[1] - q[0])))])
+        off.append(len(rows))
+    rl = np.full(len(h.names), -1, dtype=np.int64)
+    for rn, v in ob.read_length.items():
+        rl[name_id_of[rn]] = v
+    cols = np.ascontiguousarray(np.array(rows, dtype=np.int64).reshape(-1, 8).T)          # [8, n_rows], as the product's wrapper
+    return (cols, np.array(off, dtype=np.int64), np.array(names, dtype=np.int64),
+            np.array(failed, dtype=bool), rl, pair_table_cpu(cols, off, h.chroms, chr_rank))
+
+
 # ---- oracle-backed stand-ins for the device kernels (CPU tests of the host logic only) ----------------
 def install_cpu_kernel_fakes(monkeypatch):
     from coral_amd import kernels
@@ -239,7 +282,6 @@ def install_cpu_kernel_fakes(monkeypatch):
 
     def sa_table_local(dr):
         """coral_sa_table stand-in: the oracle's fetch() (string SA entries, per-read Python lists) turned into arrays."""
-        from oracle import coral_oracle as O
 
         class _WholeFile:          # the host mirrors of the whole file (the product builds the SA table from them too)
             n, header_chroms = dr.n_total, dr.header_chroms
@@ -248,26 +290,7 @@ def install_cpu_kernel_fakes(monkeypatch):
             cigar_off, cigar = np.zeros(dr.n_total + 1, dtype=np.int64), np.zeros(0, dtype=np.int32)
             nonacgt_rec, nonacgt_pos = dr.h_nonacgt_rec, dr.h_nonacgt_pos
             materialise_names = staticmethod(lambda: dr.names)
-        h = HostRecords(_WholeFile)
-        ob = O.OracleGraphBuild.__new__(O.OracleGraphBuild)
-        ob.rec, ob.read_length, ob.chimeric_alignments, ob.nm_stats = h, {}, {}, [0.0, 0.0, 0]
-        ob.fetch()
-        name_id_of = {nm: k for k, nm in enumerate(h.names)}
-        tid_of = {c: k for k, c in enumerate(h.chroms)}
-        rows, off, names, failed = [], [0], [], []
-        for rn, ca in ob.chimeric_alignments.items():
-            names.append(name_id_of[rn])
-            failed.append(len(ca) == 3)
-            if len(ca) == 4:
-                for q, ri, mq, nmr in zip(*ca):
-                    rows.append([q[0], q[1], tid_of[ri[0]], ri[1], ri[2], 0 if ri[3] == "+" else 1, mq, int(round(nmr * (q[1] - q[0])))])
-            off.append(len(rows))
-        rl = np.full(len(h.names), -1, dtype=np.int64)
-        for rn, v in ob.read_length.items():
-            rl[name_id_of[rn]] = v
-        cols = np.ascontiguousarray(np.array(rows, dtype=np.int64).reshape(-1, 8).T)          # [8, n_rows], as the product's wrapper
-        return (cols, np.array(off, dtype=np.int64), np.array(names, dtype=np.int64),
-                np.array(failed, dtype=bool), rl, pair_table_cpu(cols, off, h.chroms, dr.chr_rank), None, None)
+        return oracle_sa_table(HostRecords(_WholeFile), dr.chr_rank) + (None, None)
 
     def hash_rows_local(dr, T, seg, tid_has_segs):
         """coral_hash_rows stand-in: point queries by linear search over the segment table (the reference's IntervalTree

@@ -11,6 +11,7 @@ import torch
 
 from coral_amd import synth
 from tests.bamfile import D, EQ, I, M, S
+from tests.product_check import device_sa_table as _sa_table
 from tests.test_gpu_kernel_geometry import _crossing_src, _probe_targets, _records_around_segments, _seg_table
 from tests.test_gpu_kernels import _Rows
 
@@ -242,21 +243,6 @@ def test_point_cover_small_call_after_large_call(mixed, monkeypatch):
 
 
 # ---- SA table ------------------------------------------------------------------------------------------------------------------
-def _sa_table(rec):
-    from coral_amd import kernels
-    from coral_amd.records import DeviceRecords
-    dr = DeviceRecords(rec, "cuda:0")
-    kernels.sa_table_early(dr)          # as a build does: the table in front of the scan, sa_table hands it out
-    kernels.cigar_scan(dr)
-    cols, off, name, failed, rl, pairs, rows, st = kernels.sa_table(dr)
-    assert getattr(dr, "_sa_pending", None) is None
-    st.wait("pairs")
-    out = dict(cols=np.array(cols, copy=True), off=np.array(off, copy=True), name=np.array(name, copy=True), failed=np.array(failed, copy=True),
-               read_length=rl.cpu().numpy(), pairs=np.array(pairs, copy=True), rows=rows.cpu().numpy())
-    st.close()
-    return out
-
-
 def _plain(k, name=None):
     return dict(tid=0, pos=100 + k, cigar=[(M, 50)], name=name or "plain%d" % k)
 
@@ -307,10 +293,12 @@ def test_sa_table_equals_legacy(case, monkeypatch):
 
 def test_sa_table_errors_equal_legacy(monkeypatch):
     """The two error shapes raise what they raised: KeyError for an SA CIGAR outside the nine shapes, ZeroDivisionError for a
-    zero-length query interval - and ZeroDivisionError when a table holds both."""
+    zero-length query interval.  A table that holds both raises what its first offending read raises: the reference walks the
+    reads in dict order and stops there, and in [bad, zero] the read with the unknown shape comes first - KeyError, on both
+    drivers (tests/test_sa_table_reference.py has the other orders)."""
     bad = dict(tid=0, pos=10, cigar=[(S, 5), (M, 50)], name="x", sa=[(0, 500, 0, -2, 40, 0, 0, 60, 1)])
     zero = dict(tid=0, pos=11, cigar=[(S, 5), (M, 50)], name="z", sa=[(0, 500, 0, 54, 1, 0, 0, 60, 1)])
-    for alns, exc in (([bad, _plain(20)], KeyError), ([zero, _plain(20)], ZeroDivisionError), ([bad, zero, _plain(20)], ZeroDivisionError)):
+    for alns, exc in (([bad, _plain(20)], KeyError), ([zero, _plain(20)], ZeroDivisionError), ([bad, zero, _plain(20)], KeyError)):
         rec = synth.records_from_alignments(alns)
         for mode in (None, "legacy"):
             if mode:
