@@ -103,6 +103,11 @@ def lib():
     L.coral_bp_pair_table.argtypes = [C.c_int32, C.c_int32, P, P, P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P, P]
     L.coral_search_create.argtypes = [C.c_int64, C.c_int64] + [P] * 9 + [C.c_int64, P, P, P, C.c_int32, P, P, P]
     L.coral_search_create.restype = C.c_void_p
+    L.coral_search_create_early.argtypes = [C.c_int64, C.c_int64] + [P] * 7 + [C.c_int32]
+    L.coral_search_create_early.restype = C.c_void_p
+    L.coral_search_attach.argtypes = [C.c_void_p, P, P, P, C.c_int64, P, P, P, P, P, P]
+    L.coral_search_shutdown.argtypes = []
+    L.coral_search_stats.argtypes = [C.c_void_p, P, C.c_int32]
     L.coral_search_free.argtypes = [C.c_void_p]
     L.coral_search_error.argtypes = [C.c_void_p]
     L.coral_search_error.restype = C.c_char_p
@@ -192,6 +197,10 @@ def lib():
     with open(os.path.join(os.path.dirname(_HERE), "include", "coral_hip.h")) as fp:
         for name in re.findall(r"^int (coral_\w+)\(", fp.read(), re.M):      # every prototype of the header that returns int
             getattr(L, name).restype = C.c_int
+    # the interval search keeps its threads for the life of the process: join them before the interpreter is torn down, so
+    # that none sleeps in the library while it goes (handles still alive then compute their steps themselves)
+    import atexit
+    atexit.register(L.coral_search_shutdown)
     _lib = L
     return L
 

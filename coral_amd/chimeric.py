@@ -168,25 +168,59 @@ class PairSearch:
     replayed as CPython sets, the runs of neighbouring segments, and alignment2bp / alignment2bp_l as a FILTER over the pair
     table the GPU built once (coral_bp_pair_table).  Every method returns ``Candidates`` with ``read`` = name id."""
 
-    def __init__(self, T: ChimericTable, read_hash: np.ndarray, e_key: np.ndarray, e_row: np.ndarray, seg_off, seg_start, seg_end):
+    def __init__(self, T: ChimericTable, read_hash=None, e_key=None, e_row=None, seg_off=None, seg_start=None, seg_end=None,
+                 n_tid=None):
+        """With the table alone (and ``n_tid``, the number of contigs): the early half of the handle
+        (coral_search_create_early) — what needs the chimeric table and the pair table only, so a build can make it on a thread
+        while its CIGAR scan runs; ``attach`` brings the rest.  With every argument: both halves at once."""
         import ctypes as C
         from . import _lib
         self._C, self._lib, self._L = C, _lib, _lib.lib()
+        self._h = None
+        self.params = None                            # (kept by the build for a handle it gave its parameters ahead of the search)
+        self.early = read_hash is None                # made in two parts
         i64 = lambda a: np.ascontiguousarray(a, dtype=np.int64)
         if T.staging is not None:
             T.staging.wait("pairs")                   # the pair table's device -> host copy ran beside the CIGAR scan
+        if n_tid is None:
+            n_tid = len(seg_off) - 1
         # the handle borrows these arrays: keep them alive (and unchanged in place) for its lifetime
-        self._keep = [T, i64(T.off), i64(T.read), i64(T.tid), i64(T.ra), i64(T.rb), T.cni0, T.cni1, i64(read_hash), i64(T.name_id),
-                      i64(e_key), i64(e_row), np.ascontiguousarray(T.pairs, dtype=np.int32), i64(seg_off), i64(seg_start), i64(seg_end)]
-        assert T.cni0.dtype == np.int64 and T.cni1.dtype == np.int64 and T.cni0.flags.c_contiguous and T.cni1.flags.c_contiguous
+        self._T = T
+        self._keep = [T, i64(T.off), i64(T.read), i64(T.tid), i64(T.ra), i64(T.rb), i64(T.name_id), np.ascontiguousarray(T.pairs, dtype=np.int32)]
         k = self._keep[1:]
-        assert k[11].shape == (2 * T.n_rows, 8), "pair table must hold two slots per table row"
+        assert k[6].shape == (2 * T.n_rows, 8), "pair table must hold two slots per table row"
         ptr = lambda a: a.ctypes.data
-        self._h = self._L.coral_search_create(T.n_reads, T.n_rows, ptr(k[0]), ptr(k[1]), ptr(k[2]), ptr(k[3]), ptr(k[4]), ptr(k[5]),
-                                              ptr(k[6]), ptr(k[7]), ptr(k[8]), len(k[9]), ptr(k[9]), ptr(k[10]), ptr(k[11]),
-                                              len(k[12]) - 1, ptr(k[12]), ptr(k[13]), ptr(k[14]))
+        self.n_tid = int(n_tid)
+        self._h = self._L.coral_search_create_early(T.n_reads, T.n_rows, ptr(k[0]), ptr(k[1]), ptr(k[2]), ptr(k[3]), ptr(k[4]), ptr(k[5]),
+                                                    ptr(k[6]), self.n_tid)
         if not self._h:
-            raise _lib.CoralHipError("coral_search_create failed")
+            raise _lib.CoralHipError("coral_search_create_early failed")
+        if read_hash is not None:
+            self.attach(read_hash, e_key, e_row, seg_off, seg_start, seg_end)
+
+    def attach(self, read_hash, e_key, e_row, seg_off, seg_start, seg_end) -> np.ndarray:
+        """The second half (coral_search_attach), once the table's cni0 / cni1 and the inverted index exist.  Returns int64
+        [n_tid]: per contig the first table row with cni0 != -3, or -1."""
+        T = self._T
+        i64 = lambda a: np.ascontiguousarray(a, dtype=np.int64)
+        assert T.cni0.dtype == np.int64 and T.cni1.dtype == np.int64 and T.cni0.flags.c_contiguous and T.cni1.flags.c_contiguous
+        k = [T.cni0, T.cni1, i64(read_hash), i64(e_key), i64(e_row), i64(seg_off), i64(seg_start), i64(seg_end)]
+        assert len(k[5]) == self.n_tid + 1 and len(k[2]) == T.n_reads and len(k[3]) == len(k[4])
+        first = np.empty(max(self.n_tid, 1), dtype=np.int64)
+        self._keep += k
+        ptr = lambda a: a.ctypes.data
+        rc = self._L.coral_search_attach(self._h, ptr(k[0]), ptr(k[1]), ptr(k[2]), len(k[3]), ptr(k[3]), ptr(k[4]), ptr(k[5]), ptr(k[6]),
+                                         ptr(k[7]), ptr(first))
+        if rc != 0:
+            raise self._lib.CoralHipError("coral_search_attach failed (%d): %s" % (rc, self._L.coral_search_error(self._h).decode()))
+        return first[:self.n_tid]
+
+    def stats(self) -> dict:
+        """Counters of the handle (coral_search_stats)."""
+        out = np.zeros(8, dtype=np.int64)
+        self._lib.check(self._L.coral_search_stats(self._h, out.ctypes.data, len(out)), "coral_search_stats")
+        return dict(zip(("attached", "fill_ready_at_attach", "queued", "queued_before_bfs", "inline_steps", "workers", "helpers"),
+                        (int(v) for v in out[:7])))
 
     def close(self):
         if self._h:

@@ -21,6 +21,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <unistd.h>
 
 #include <algorithm>
 #include <array>
@@ -70,13 +71,26 @@ struct StepResult {
     std::vector<int64_t> order_off;                       // [n_groups + 1]
     std::vector<Calls> calls;                             // per run
     // the same, flattened for one-shot retrieval (coral_search_result): see the header for the layout of `meta`
+    // Only coral_search_result reads them (the step-by-step path of the Python side; coral_search_bfs reads `calls`), so they
+    // are built there, on demand (ensure_flat), and not at the end of every step: `order` from the runs' own lists.
     std::vector<int64_t> meta, sup;
     std::vector<double> stats;
+    std::vector<std::vector<int32_t>> order_parts;        // per run, as the step left them
+    std::mutex flat_m;                                    // a second caller of coral_search_result waits for the first
+    bool flat_done = false;
     double t_phase[4] = {0, 0, 0, 0};                      // CORAL_SEARCH_PROFILE: reach, union, candidates, calls (seconds, wall)
     void clear() {
         rc = CORAL_OK; err[0] = 0;
         groups.clear(); cand.clear(); order.clear(); order_off.assign(1, 0); calls.clear();
-        meta.assign(1, 0); sup.clear(); stats.clear();
+        meta.assign(1, 0); sup.clear(); stats.clear(); order_parts.clear();
+        flat_done = false;
+    }
+    void ensure_flat() {
+        std::lock_guard<std::mutex> lk(flat_m);
+        if (flat_done) return;
+        order.clear();
+        for (const auto &part : order_parts) order.insert(order.end(), part.begin(), part.end());
+        flatten();
     }
     void flatten() {
         const size_t ng = groups.size() / 4;
@@ -97,19 +111,27 @@ struct StepResult {
                 stats.insert(stats.end(), c.stats.begin() + 6 * (size_t)k, c.stats.begin() + 6 * (size_t)k + 6);
             }
         }
+        flat_done = true;
     }
 };
 
-struct Scratch {                                          // per thread
+// Per thread, and a thread of the process-wide set serves one handle after another.  `seen[r] == stamp` means "read r was
+// expanded in THIS step": every step, whichever handle it belongs to, first takes a stamp that no earlier step of this thread
+// has used (++stamp; on wrap-around the marks are wiped), so a mark left by a step of another handle of equal n_reads (with
+// another n_reads the array is made anew) carries an older stamp and reads as "not seen".  Nothing else outlives a step.
+struct Scratch {
     std::vector<uint32_t> seen;                           // per read: stamp of the step that expanded it
     uint32_t stamp = 0;
     std::vector<char> used;
 };
 
+struct Search;
+
 struct Entry {                                            // one (possibly pending) step in the cache
     std::mutex m;
     std::condition_variable cv;
     bool done = false, taken = false;                     // taken: some thread is computing it
+    Search *owner = nullptr;                              // its handle (a worker touches it only while the handle counts it as in flight)
     StepResult res;
     int64_t key[5];
     double t_queued = 0, t_start = 0, t_end = 0;          // CORAL_SEARCH_PROFILE=2: when it was asked for / computed
@@ -124,18 +146,28 @@ struct KeyHash {
     }
 };
 
+void pin_thread(std::thread &t, const std::vector<int> &cpus) {
+    if (cpus.empty()) return;
+    cpu_set_t set;
+    CPU_ZERO(&set);
+    for (int c : cpus) if (c < CPU_SETSIZE) CPU_SET(c, &set);
+    (void)pthread_setaffinity_np(t.native_handle(), sizeof(set), &set);
+}
+
 // A small work-sharing pool: a caller hands in a batch of tasks, helps to run tasks (its own or another caller's) while it
 // waits, and returns when its batch is done.  Several steps may be computed at once (one per look-ahead thread), each handing
-// in its batches; the helpers sleep on a condition variable between batches.
+// in its batches; the helpers sleep on a condition variable between batches.  The helpers belong to the process (Threads):
+// grow() adds some, shutdown() joins them all, and a batch handed in while none exists is run by its caller alone.
 struct TaskPool {
     struct Task { std::function<void()> *fn; std::atomic<int> *left; };
     std::mutex m;
     std::condition_variable cv;
     std::deque<Task> q;
     bool stop = false;
-    std::vector<std::thread> th;
-    explicit TaskPool(int n) {
-        for (int k = 0; k < n; ++k)
+    std::vector<std::thread> th;                          // (grow / shutdown: under Threads::life)
+    std::atomic<int> n_alive{0};
+    void grow(int n, const std::vector<int> &cpus) {
+        while ((int)th.size() < n) {
             th.emplace_back([this]() {
                 for (;;) {
                     Task t;
@@ -150,14 +182,21 @@ struct TaskPool {
                     t.left->fetch_sub(1, std::memory_order_acq_rel);
                 }
             });
+            pin_thread(th.back(), cpus);
+            n_alive.fetch_add(1);
+        }
     }
-    ~TaskPool() {
+    void shutdown() {                                     // (tasks still queued are run by the callers that wait for them)
         {
             std::lock_guard<std::mutex> lk(m);
             stop = true;
         }
         cv.notify_all();
         for (auto &x : th) x.join();
+        th.clear();
+        n_alive.store(0);
+        std::lock_guard<std::mutex> lk(m);
+        stop = false;
     }
     void run(std::vector<std::function<void()>> &tasks) {
         if (tasks.empty()) return;
@@ -187,8 +226,53 @@ struct TaskPool {
 
 struct BfsOut;
 
+// Storage of a handle's pack: int32, NOT initialised (the fill writes every element), and handed from one handle to the next
+// through a one-slot store of the process — a fresh 17 MB block per build costs its page faults and a pass of zeroes, which
+// is more than the fill itself.  coral_search_shutdown empties the slot.
+struct PackBuf {
+    int32_t *p = nullptr;
+    size_t cap = 0;
+    static std::mutex &slot_m() { static std::mutex m; return m; }
+    static PackBuf &slot() { static PackBuf s; return s; }
+    PackBuf() = default;
+    PackBuf(const PackBuf &) = delete;
+    PackBuf &operator=(const PackBuf &) = delete;
+    int32_t *data() { return p; }
+    const int32_t *data() const { return p; }
+    void release() { free(p); p = nullptr; cap = 0; }
+    bool resize(size_t n) {                               // (once per handle)
+        release();
+        {
+            std::lock_guard<std::mutex> lk(slot_m());
+            PackBuf &s = slot();
+            if (s.p && s.cap >= n && s.cap / 2 <= n + (1u << 18)) { p = s.p; cap = s.cap; s.p = nullptr; s.cap = 0; return true; }
+        }
+        p = (int32_t *)malloc(std::max<size_t>(n, 1) * sizeof(int32_t));
+        cap = p ? std::max<size_t>(n, 1) : 0;
+        return p != nullptr;
+    }
+    void give_back() {                                    // to the slot if it is bigger than what the slot holds
+        if (!p) return;
+        std::lock_guard<std::mutex> lk(slot_m());
+        PackBuf &s = slot();
+        if (cap > s.cap) std::swap(p, s.p), std::swap(cap, s.cap);
+    }
+    static void drop_slot() {
+        std::lock_guard<std::mutex> lk(slot_m());
+        slot().release();
+    }
+    ~PackBuf() { release(); }
+};
+
 struct Search {
-    std::unique_ptr<TaskPool> pool;                       // helpers of big steps (coral_search_params: with the look-ahead threads)
+    int32_t n_threads = 0, n_helpers = 0;                // what coral_search_params asked of the process's search threads
+    bool use_pool = false;                                // big steps are split over the helper pool
+    int inflight = 0;                                     // entries of this handle that a worker holds (guarded by Threads::m)
+    bool attached = false;                                // coral_search_attach ran: steps may be asked for
+    std::vector<std::thread> fill_threads;                // coral_search_create_early: the pack fill of a big table
+    std::atomic<int> fill_left{0};                        // ... and how many of its pieces are still to do
+    const int64_t *row_tid = nullptr;
+    int64_t stat_fill_ready = 0, stat_queued = 0, stat_queued_at_bfs = -1;       // coral_search_stats
     size_t chunk_cap = 9, chunk_reads = 1000;              // stage B of a step: at most chunk_cap chunks per run, of >= chunk_reads reads
     std::shared_ptr<BfsOut> bfs;                          // result of the last coral_search_bfs
     int64_t n_reads = 0, n_rows = 0, n_ent = 0;
@@ -197,22 +281,18 @@ struct Search {
     int32_t n_tid = 0;
     const int64_t *seg_off = nullptr, *seg_start = nullptr, *seg_end = nullptr;      // CN segments per contig, file order; end inclusive
     std::vector<int64_t> pack_off;                        // per read: index of its record in `pack` (in int32 units)
-    std::vector<int32_t> pack;
+    PackBuf pack;
     // parameters of the build (coral_search_params)
     double min_cluster_cutoff = 3.0, accept_floor = 3.0;
     int64_t max_seq_len = 2000000, bp_distance_cutoff = 2000, match_cutoff = 100;
     // synchronous calls (within / between / inline steps) use these
     Scratch main_scratch;
     StepResult main_result;
-    const StepResult *current = nullptr;                  // what coral_search_result / coral_search_calls describe
+    StepResult *current = nullptr;                        // what coral_search_result / coral_search_calls describe
     std::shared_ptr<Entry> current_entry;
-    // look-ahead
-    std::vector<std::thread> workers;
+    // look-ahead: the cache is the handle's; the queue and the threads are the process's (Threads)
     std::mutex qm;
-    std::condition_variable qcv;
-    std::deque<std::shared_ptr<Entry>> queue;
     std::unordered_map<std::array<int64_t, 5>, std::shared_ptr<Entry>, KeyHash> cache;
-    bool stop = false;
     char err[256] = "";
     // CORAL_SEARCH_PROFILE=1: seconds per phase and work counters over all steps, printed when the handle is freed
     bool profile = false, profile_steps = false;
@@ -221,6 +301,77 @@ struct Search {
     double t_reach = 0, t_union = 0, t_cand = 0, t_call = 0, t_wait = 0;
     long long n_steps = 0, n_visit = 0, n_adds = 0, n_keys = 0, n_union_items = 0, n_cand = 0, n_inline = 0;
 };
+
+// The search threads of the process: the look-ahead workers with their queue, and the helper pool.  The first
+// coral_search_params with n_threads > 0 starts them, every later handle finds them there (a handle that asks for more makes
+// the set grow), coral_search_shutdown joins them, and the next handle that wants them starts them again.  A queue entry
+// names its handle; coral_search_free takes the handle's entries out of the queue and waits for those a worker holds, so no
+// thread is joined when a handle goes.  After a fork the child has none of these threads and may have inherited the locks
+// in any state: it sees that the pid differs and starts over with a set of its own (the inherited one is left alone).
+struct Threads;
+void worker_main(Threads *G);
+std::vector<int> cpus_of_my_node();
+
+struct Threads {
+    pid_t pid = 0;
+    std::mutex life;                                      // grow / shutdown, one at a time
+    std::mutex m;                                         // queue, stop, every handle's `inflight`
+    std::condition_variable cv, idle_cv;
+    std::deque<std::shared_ptr<Entry>> queue;
+    bool stop = false;
+    std::vector<std::thread> workers;                     // (under `life`)
+    std::atomic<int> n_workers{0};
+    TaskPool helpers;
+    std::vector<int> cpus;                                // NUMA node of the thread that started the first one
+    bool cpus_known = false;
+
+    void ensure(int want_workers, int want_helpers) {
+        if (n_workers.load() >= want_workers && helpers.n_alive.load() >= want_helpers) return;
+        std::lock_guard<std::mutex> lk(life);
+        if (!cpus_known) { cpus = cpus_of_my_node(); cpus_known = true; }
+        while ((int)workers.size() < want_workers) {
+            workers.emplace_back(worker_main, this);
+            pin_thread(workers.back(), cpus);
+            n_workers.fetch_add(1);
+        }
+        helpers.grow(want_helpers, cpus);
+    }
+    void shutdown() {
+        std::lock_guard<std::mutex> lk(life);
+        {
+            std::lock_guard<std::mutex> lq(m);
+            stop = true;
+            queue.clear();                                // (their handles compute them themselves when they are asked for)
+        }
+        cv.notify_all();
+        for (std::thread &t : workers) t.join();
+        workers.clear();
+        n_workers.store(0);
+        helpers.shutdown();
+        std::lock_guard<std::mutex> lq(m);
+        stop = false;
+    }
+};
+
+std::atomic<Threads *> g_threads{nullptr};
+
+Threads *threads_if_any() {                               // the process's set, if this process has made one
+    Threads *G = g_threads.load(std::memory_order_acquire);
+    return (G && G->pid == getpid()) ? G : nullptr;
+}
+
+Threads &threads() {
+    for (;;) {
+        Threads *G = g_threads.load(std::memory_order_acquire);
+        if (G && G->pid == getpid()) return *G;
+        Threads *fresh = new Threads();                   // (never deleted: a thread may still be leaving it at exit)
+        fresh->pid = getpid();
+        if (g_threads.compare_exchange_strong(G, fresh)) return *fresh;
+        delete fresh;
+    }
+}
+
+inline TaskPool *helper_pool(const Search &S) { return S.use_pool ? &threads().helpers : nullptr; }
 
 inline const int32_t *rec_of(const Search &S, int64_t r) { return S.pack.data() + S.pack_off[(size_t)r]; }
 inline const PackedRow *rows_of(const int32_t *rec) { return reinterpret_cast<const PackedRow *>(rec + 2); }
@@ -296,6 +447,7 @@ void run_calls(const Search &S, const int64_t *cand, int64_t n, Calls &c) {
 
 void compute_step(Search &S, Scratch &T, const int64_t key[5], StepResult &R) {
     const int64_t tid = key[0], s = key[1], e = key[2], si = key[3], ei = key[4];
+    TaskPool *const pool = helper_pool(S);
     R.clear();
     auto fail = [&](int rc, const char *msg) { R.rc = rc; snprintf(R.err, sizeof(R.err), "%s", msg); };
     if (tid < 0 || tid >= S.n_tid) return fail(CORAL_ERR_ARG, "search_step: contig id out of range");
@@ -417,11 +569,11 @@ void compute_step(Search &S, Scratch &T, const int64_t key[5], StepResult &R) {
     int64_t reads_in_sets = 0;
     for (size_t g = 0; g < n_runs; ++g)
         for (int32_t k : plan[g].keys) reads_in_sets += (int64_t)sets[(size_t)k].used;
-    const bool pooled = S.pool && reads_in_sets >= S.par_min_reads;
+    const bool pooled = pool && reads_in_sets >= S.par_min_reads;
     if (pooled && n_runs > 1) {
         std::vector<std::function<void()>> tasks;
         for (size_t g = 0; g < n_runs; ++g) tasks.emplace_back([&, g]() { stage_a(g); });
-        S.pool->run(tasks);
+        pool->run(tasks);
     } else {
         for (size_t g = 0; g < n_runs; ++g) stage_a(g);
     }
@@ -451,7 +603,7 @@ void compute_step(Search &S, Scratch &T, const int64_t key[5], StepResult &R) {
                 Scratch sc;                                  // (pairs_between only uses the `used` marks: a few bytes)
                 stage_b(chunks[c], sc);
             });
-        S.pool->run(tasks);
+        pool->run(tasks);
     } else {
         for (Chunk &ch : chunks) stage_b(ch, T);
     }
@@ -472,8 +624,7 @@ void compute_step(Search &S, Scratch &T, const int64_t key[5], StepResult &R) {
         }
     }
     for (size_t g = 0; g < n_runs; ++g) {
-        R.order.insert(R.order.end(), order_of[g].begin(), order_of[g].end());
-        R.order_off.push_back((int64_t)R.order.size());
+        R.order_off.push_back(R.order_off.back() + (int64_t)order_of[g].size());
         const int64_t gr[4] = {plan[g].t, plan[g].b0, plan[g].b1, at[g + 1] - at[g]};
         R.groups.insert(R.groups.end(), gr, gr + 4);
     }
@@ -485,14 +636,14 @@ void compute_step(Search &S, Scratch &T, const int64_t key[5], StepResult &R) {
         if (pooled && n_big > 1) {
             std::vector<std::function<void()>> tasks;
             for (size_t g = 0; g < n_runs; ++g) tasks.emplace_back([&, g]() { run_calls(S, R.cand.data() + 13 * at[g], at[g + 1] - at[g], R.calls[g]); });
-            S.pool->run(tasks);
+            pool->run(tasks);
         } else {
             for (size_t g = 0; g < n_runs; ++g) run_calls(S, R.cand.data() + 13 * at[g], at[g + 1] - at[g], R.calls[g]);
         }
     }
     const double t_u = tB0 - tA0, t_c = t2 - tB0;
     (void)tC0;
-    R.flatten();
+    R.order_parts = std::move(order_of);                 // (`order`, `meta`, `sup`, `stats`: StepResult::ensure_flat, when asked for)
     if (S.profile) {
         const double t3 = now_s();
         R.t_phase[0] = t1 - t0; R.t_phase[1] = t_u; R.t_phase[2] = t_c; R.t_phase[3] = t3 - t2;
@@ -530,30 +681,41 @@ std::vector<int> cpus_of_my_node() {
     return out;
 }
 
-void worker_main(Search *S) {
-    Scratch T;
+void worker_main(Threads *G) {
+    Scratch T;                                            // (serves every handle in turn: see Scratch)
     for (;;) {
         std::shared_ptr<Entry> e;
+        Search *S;
         {
-            std::unique_lock<std::mutex> lk(S->qm);
-            S->qcv.wait(lk, [&] { return S->stop || !S->queue.empty(); });
-            if (S->stop) return;
-            e = S->queue.front();
-            S->queue.pop_front();
+            std::unique_lock<std::mutex> lk(G->m);
+            G->cv.wait(lk, [&] { return G->stop || !G->queue.empty(); });
+            if (G->stop) return;
+            e = G->queue.front();
+            G->queue.pop_front();
+            S = e->owner;
+            ++S->inflight;                               // from here to the decrement below coral_search_free waits for us
         }
-        {
-            std::lock_guard<std::mutex> lk(e->m);
-            if (e->taken) continue;                      // the caller got there first and computes it itself
-            e->taken = true;
-        }
-        e->t_start = now_s();
-        compute_step(*S, T, e->key, e->res);
-        e->t_end = now_s();
+        bool mine;
         {
             std::lock_guard<std::mutex> lk(e->m);
-            e->done = true;
+            mine = !e->taken;                            // (else the caller got there first and computes it itself)
+            if (mine) e->taken = true;
         }
-        e->cv.notify_all();
+        if (mine) {
+            e->t_start = now_s();
+            compute_step(*S, T, e->key, e->res);
+            e->t_end = now_s();
+            {
+                std::lock_guard<std::mutex> lk(e->m);
+                e->done = true;
+            }
+            e->cv.notify_all();
+        }
+        {
+            std::lock_guard<std::mutex> lk(G->m);
+            --S->inflight;                               // (the handle may be gone the moment the lock is released)
+        }
+        G->idle_cv.notify_all();
     }
 }
 
@@ -933,21 +1095,22 @@ struct BfsRun {
 };
 }  // namespace
 
-extern "C" void *coral_search_create(int64_t n_reads, int64_t n_rows, const int64_t *off, const int64_t *row_read,
-                                     const int64_t *row_tid, const int64_t *ra, const int64_t *rb, const int64_t *cni0,
-                                     const int64_t *cni1, const int64_t *read_hash, const int64_t *read_name, int64_t n_ent,
-                                     const int64_t *e_key, const int64_t *e_row, const int32_t *pairs, int32_t n_tid,
-                                     const int64_t *seg_off, const int64_t *seg_start, const int64_t *seg_end) {
-    if (n_reads < 0 || n_rows < 0 || n_ent < 0 || n_tid < 0 || !off || !seg_off) return nullptr;
-    if (n_rows > 0 && (!row_read || !row_tid || !ra || !rb || !cni0 || !cni1 || !pairs)) return nullptr;
-    if (n_reads > 0 && (!read_hash || !read_name)) return nullptr;
-    if (n_ent > 0 && (!e_key || !e_row)) return nullptr;
+// The part of a handle that needs the chimeric table and the pair table only: both are on the host while the build still
+// waits for its CIGAR scan, so the 2 + 12 ints per row of the pack are laid out and filled then, off the build's critical
+// path.  The offsets are computed here; a big table's records are filled on threads of the handle's own, which this call does
+// not wait for (coral_search_attach and coral_search_free do).  The two CN-segment fields of a row come with attach.
+extern "C" void *coral_search_create_early(int64_t n_reads, int64_t n_rows, const int64_t *off, const int64_t *row_read,
+                                           const int64_t *row_tid, const int64_t *ra, const int64_t *rb, const int64_t *read_name,
+                                           const int32_t *pairs, int32_t n_tid) {
+    if (n_reads < 0 || n_rows < 0 || n_tid < 0 || !off) return nullptr;
+    if (n_rows > 0 && (!row_read || !row_tid || !ra || !rb || !pairs)) return nullptr;
+    if (n_reads > 0 && !read_name) return nullptr;
     Search *S = new Search();
-    S->n_reads = n_reads; S->n_rows = n_rows; S->n_ent = n_ent;
-    S->off = off; S->row_read = row_read; S->read_hash = read_hash; S->read_name = read_name; S->e_key = e_key; S->e_row = e_row;
-    S->pairs = pairs; S->n_tid = n_tid; S->seg_off = seg_off; S->seg_start = seg_start; S->seg_end = seg_end;
+    S->n_reads = n_reads; S->n_rows = n_rows;
+    S->off = off; S->row_read = row_read; S->row_tid = row_tid; S->read_name = read_name;
+    S->pairs = pairs; S->n_tid = n_tid;
     S->pack_off.resize((size_t)n_reads);
-    {   // offsets first (2 + 12 ints per row), then the records are filled in parallel: 16 MB at 2 M reads, on the build's critical path
+    {
         int64_t at = 0;
         for (int64_t r = 0; r < n_reads; ++r) {
             const int64_t base = off[r], n = off[r + 1] - base;
@@ -955,8 +1118,8 @@ extern "C" void *coral_search_create(int64_t n_reads, int64_t n_rows, const int6
             S->pack_off[(size_t)r] = at;
             at += 2 + 12 * n;
         }
-        S->pack.resize((size_t)at);
-        auto fill = [&](int64_t r0, int64_t r1) {
+        if (!S->pack.resize((size_t)at)) { delete S; return nullptr; }
+        auto fill = [S, off, row_tid, ra, rb, pairs](int64_t r0, int64_t r1) {
             for (int64_t r = r0; r < r1; ++r) {
                 const int64_t base = off[r], n = off[r + 1] - base;
                 int32_t *w = S->pack.data() + S->pack_off[(size_t)r];
@@ -964,18 +1127,18 @@ extern "C" void *coral_search_create(int64_t n_reads, int64_t n_rows, const int6
                 *w++ = (int32_t)base;
                 for (int64_t k = base; k < base + n; ++k) {
                     const int32_t *adj = pairs + 8 * (2 * k);
-                    const int32_t v[12] = {(int32_t)row_tid[k], (int32_t)ra[k], (int32_t)rb[k], (int32_t)cni0[k], (int32_t)cni1[k],
+                    const int32_t v[12] = {(int32_t)row_tid[k], (int32_t)ra[k], (int32_t)rb[k], -1, -1,
                                            pairs[8 * (2 * k + 1) + 5], adj[0], adj[1], adj[2], adj[3], adj[4], adj[5]};
                     memcpy(w, v, sizeof(v));
                     w += 12;
                 }
             }
+            S->fill_left.fetch_sub(1, std::memory_order_acq_rel);
         };
         const int nt = n_reads >= 40000 ? 4 : 1;
-        std::vector<std::thread> th;
-        for (int t = 1; t < nt; ++t) th.emplace_back(fill, n_reads * t / nt, n_reads * (t + 1) / nt);
-        fill(0, n_reads / nt);
-        for (auto &x : th) x.join();
+        S->fill_left.store(nt);
+        if (nt == 1) fill(0, n_reads);
+        else for (int t = 0; t < nt; ++t) S->fill_threads.emplace_back(fill, n_reads * t / nt, n_reads * (t + 1) / nt);
     }
     const char *pe = getenv("CORAL_SEARCH_PROFILE");
     S->profile = pe && (pe[0] == '1' || pe[0] == '2');
@@ -986,12 +1149,117 @@ extern "C" void *coral_search_create(int64_t n_reads, int64_t n_rows, const int6
     return S;
 }
 
+namespace {
+void wait_fill(Search &S) {
+    for (std::thread &t : S.fill_threads) t.join();
+    S.fill_threads.clear();
+}
+
+int not_attached(Search &S, const char *what) {
+    snprintf(S.err, sizeof(S.err), "%s: the handle is not attached (coral_search_attach)", what);
+    return CORAL_ERR_ARG;
+}
+}  // namespace
+
+// The rest of a handle, once hash_alignment_to_seg has its results: waits for the pack fill, writes the CN-segment indices of
+// both ends into every packed row (a big table in pieces: on the helper threads when the process has some, else on threads of
+// its own) and, in the same pass, finds per contig the first table row with cni0 != -3 (first_row_of_tid int64[n_tid], -1:
+// none; may be null) — the order in which hash_alignment_to_seg's dict meets the contigs.
+extern "C" int coral_search_attach(void *h, const int64_t *cni0, const int64_t *cni1, const int64_t *read_hash, int64_t n_ent,
+                                   const int64_t *e_key, const int64_t *e_row, const int64_t *seg_off, const int64_t *seg_start,
+                                   const int64_t *seg_end, int64_t *first_row_of_tid) {
+    if (!h) return CORAL_ERR_ARG;
+    Search &S = *(Search *)h;
+    auto bad = [&](const char *msg) { snprintf(S.err, sizeof(S.err), "search_attach: %s", msg); return CORAL_ERR_ARG; };
+    if (S.attached) return bad("attached already");
+    if (n_ent < 0 || !seg_off) return bad("bad argument");
+    if (S.n_rows > 0 && (!cni0 || !cni1)) return bad("null CN-segment indices");
+    if (S.n_reads > 0 && !read_hash) return bad("null read hashes");
+    if (n_ent > 0 && (!e_key || !e_row)) return bad("null inverted index");
+    S.stat_fill_ready = S.fill_left.load(std::memory_order_acquire) == 0 ? 1 : 0;
+    wait_fill(S);
+    S.read_hash = read_hash; S.n_ent = n_ent; S.e_key = e_key; S.e_row = e_row;
+    S.seg_off = seg_off; S.seg_start = seg_start; S.seg_end = seg_end;
+    const int64_t n_reads = S.n_reads, n_rows = S.n_rows, n_tid = S.n_tid;
+    // (the pass touches every cache line of the pack, 17 MB at 2 M reads, and it is on the build's critical path: as many pieces
+    // as there are helpers to take them; the first rows are a minimum over the pieces, so their number does not show)
+    Threads *const G = threads_if_any();
+    const int n_help = G ? G->helpers.n_alive.load() : 0;
+    const int pieces = n_reads >= 40000 ? std::max(4, std::min(n_help + 1, 16)) : 1;
+    std::vector<std::vector<int64_t>> first((size_t)pieces, std::vector<int64_t>((size_t)n_tid, -1));
+    auto patch = [&](int p) {
+        const int64_t r0 = n_reads * p / pieces, r1 = n_reads * (p + 1) / pieces;
+        std::vector<int64_t> &fr = first[(size_t)p];
+        auto see = [&](int64_t k) {
+            const int64_t t = S.row_tid[k];
+            if (cni0[k] != -3 && t >= 0 && t < n_tid && fr[(size_t)t] < 0) fr[(size_t)t] = k;
+        };
+        // (rows that belong to no read — in front of the first read's, behind the last read's — still count for the contigs)
+        if (p == 0) for (int64_t k = 0, e = n_reads > 0 ? S.off[0] : n_rows; k < e; ++k) see(k);
+        for (int64_t r = r0; r < r1; ++r) {
+            const int64_t base = S.off[r], n = S.off[r + 1] - base;
+            PackedRow *w = reinterpret_cast<PackedRow *>(S.pack.data() + S.pack_off[(size_t)r] + 2);
+            for (int64_t k = 0; k < n; ++k) {
+                w[k].cni0 = (int32_t)cni0[base + k];
+                w[k].cni1 = (int32_t)cni1[base + k];
+                see(base + k);
+            }
+        }
+        if (p == pieces - 1 && n_reads > 0) for (int64_t k = S.off[n_reads]; k < n_rows; ++k) see(k);
+    };
+    if (pieces == 1) {
+        patch(0);
+    } else {
+        if (n_help > 0) {
+            std::vector<std::function<void()>> tasks;
+            for (int p = 0; p < pieces; ++p) tasks.emplace_back([&, p]() { patch(p); });
+            G->helpers.run(tasks);
+        } else {
+            std::vector<std::thread> th;
+            for (int p = 1; p < pieces; ++p) th.emplace_back(patch, p);
+            patch(0);
+            for (auto &x : th) x.join();
+        }
+    }
+    if (first_row_of_tid)
+        for (int64_t t = 0; t < n_tid; ++t) {
+            int64_t best = -1;
+            for (int p = 0; p < pieces; ++p) {
+                const int64_t v = first[(size_t)p][(size_t)t];
+                if (v >= 0 && (best < 0 || v < best)) best = v;
+            }
+            first_row_of_tid[t] = best;
+        }
+    S.attached = true;
+    return CORAL_OK;
+}
+
+extern "C" int coral_search_free(void *h);
+
+extern "C" void *coral_search_create(int64_t n_reads, int64_t n_rows, const int64_t *off, const int64_t *row_read,
+                                     const int64_t *row_tid, const int64_t *ra, const int64_t *rb, const int64_t *cni0,
+                                     const int64_t *cni1, const int64_t *read_hash, const int64_t *read_name, int64_t n_ent,
+                                     const int64_t *e_key, const int64_t *e_row, const int32_t *pairs, int32_t n_tid,
+                                     const int64_t *seg_off, const int64_t *seg_start, const int64_t *seg_end) {
+    if (n_reads < 0 || n_rows < 0 || n_ent < 0 || n_tid < 0 || !off || !seg_off) return nullptr;
+    if (n_rows > 0 && (!row_read || !row_tid || !ra || !rb || !cni0 || !cni1 || !pairs)) return nullptr;
+    if (n_reads > 0 && (!read_hash || !read_name)) return nullptr;
+    if (n_ent > 0 && (!e_key || !e_row)) return nullptr;
+    void *h = coral_search_create_early(n_reads, n_rows, off, row_read, row_tid, ra, rb, read_name, pairs, n_tid);
+    if (!h) return nullptr;
+    if (coral_search_attach(h, cni0, cni1, read_hash, n_ent, e_key, e_row, seg_off, seg_start, seg_end, nullptr) != CORAL_OK) {
+        coral_search_free(h);
+        return nullptr;
+    }
+    return h;
+}
+
 // Parameters of the build + the number of look-ahead threads (0 = every step is computed by the caller).
 extern "C" int coral_search_params(void *h, double min_cluster_cutoff, int64_t max_seq_len, int64_t bp_distance_cutoff,
                                    int64_t match_cutoff, double accept_floor, int32_t n_threads) {
     if (!h || bp_distance_cutoff <= 0 || n_threads < 0 || n_threads > 64) return CORAL_ERR_ARG;
     Search &S = *(Search *)h;
-    if (!S.workers.empty() || !S.cache.empty()) return CORAL_ERR_ARG;          // set once, before the first step
+    if (S.n_threads > 0 || !S.cache.empty()) return CORAL_ERR_ARG;             // set once, before the first step
     S.min_cluster_cutoff = min_cluster_cutoff; S.max_seq_len = max_seq_len; S.bp_distance_cutoff = bp_distance_cutoff;
     S.match_cutoff = match_cutoff; S.accept_floor = accept_floor;
     if (n_threads > 0) {
@@ -1001,30 +1269,37 @@ extern "C" int coral_search_params(void *h, double min_cluster_cutoff, int64_t m
         if (const char *e = getenv("CORAL_SEARCH_HELPERS")) helpers = std::max(0, std::min(15, atoi(e)));
         if (const char *e = getenv("CORAL_SEARCH_CHUNK")) S.chunk_reads = (size_t)std::max(200, atoi(e));
         S.chunk_cap = (size_t)std::max(8, helpers + 1);
-        if (helpers > 0) S.pool.reset(new TaskPool(helpers));
+        S.n_threads = n_threads;
+        S.n_helpers = helpers;
+        S.use_pool = helpers > 0;
+        // the process's threads: started by the first handle that wants some, found there by every later one.  (How a step
+        // is cut into pieces depends on the handle's own numbers above, never on how many threads exist.)
+        threads().ensure(n_threads, helpers);
     }
-    const std::vector<int> cpus = n_threads > 0 ? cpus_of_my_node() : std::vector<int>();
-    for (int32_t k = 0; k < n_threads; ++k) {
-        S.workers.emplace_back(worker_main, &S);
-        if (!cpus.empty()) {
-            cpu_set_t set;
-            CPU_ZERO(&set);
-            for (int c : cpus) if (c < CPU_SETSIZE) CPU_SET(c, &set);
-            (void)pthread_setaffinity_np(S.workers.back().native_handle(), sizeof(set), &set);
-        }
-    }
+    return CORAL_OK;
+}
+
+// Joins the process's search threads (idempotent).  Handles stay valid: a step that was queued is computed by its caller,
+// and the next prefetch of a handle with n_threads > 0 starts the threads again.
+extern "C" int coral_search_shutdown(void) {
+    if (Threads *G = threads_if_any()) G->shutdown();
+    PackBuf::drop_slot();
     return CORAL_OK;
 }
 
 extern "C" int coral_search_free(void *h) {
     if (!h) return CORAL_OK;
     Search &S = *(Search *)h;
-    {
-        std::lock_guard<std::mutex> lk(S.qm);
-        S.stop = true;
-    }
-    S.qcv.notify_all();
-    for (std::thread &t : S.workers) t.join();
+    wait_fill(S);
+    if (S.n_threads > 0)
+        if (Threads *G = threads_if_any()) {
+            // no thread is joined: what is still queued for this handle is dropped, what a worker holds is waited for
+            std::unique_lock<std::mutex> lk(G->m);
+            auto &q = G->queue;
+            q.erase(std::remove_if(q.begin(), q.end(), [&](const std::shared_ptr<Entry> &e) { return e->owner == &S; }), q.end());
+            G->idle_cv.wait(lk, [&] { return S.inflight == 0; });
+        }
+    S.pack.give_back();                                   // (the next handle's pack: PackBuf)
     if (S.profile)
         fprintf(stderr, "coral_search: %lld steps (%lld computed by the caller, waited %.2f ms)  reach %.2f ms (visit rows %lld, set adds %lld, "
                 "keys %lld)  union %.2f ms (%lld items)  candidates %.2f ms (%lld)  calls %.2f ms\n",
@@ -1040,22 +1315,47 @@ extern "C" const char *coral_search_error(void *h) { return h ? ((Search *)h)->e
 extern "C" int coral_search_prefetch(void *h, int64_t tid, int64_t s, int64_t e, int64_t si, int64_t ei) {
     if (!h) return CORAL_ERR_ARG;
     Search &S = *(Search *)h;
-    if (S.workers.empty()) return CORAL_OK;
+    if (!S.attached) return not_attached(S, "search_prefetch");
+    if (S.n_threads == 0) return CORAL_OK;
     const std::array<int64_t, 5> key = {tid, s, e, si, ei};
+    std::shared_ptr<Entry> ent;
+    {
+        std::lock_guard<std::mutex> lk(S.qm);
+        if (S.cache.find(key) != S.cache.end()) return CORAL_OK;
+        ent = std::make_shared<Entry>();
+        memcpy(ent->key, key.data(), sizeof(ent->key));
+        ent->owner = &S;
+        ent->t_queued = now_s();
+        S.cache.emplace(key, ent);
+        ++S.stat_queued;
+    }
+    Threads &G = threads();
+    G.ensure(S.n_threads, S.n_helpers);                  // (there since coral_search_params, unless shut down or forked since)
+    {
+        std::lock_guard<std::mutex> lk(G.m);
+        G.queue.push_back(ent);
+    }
+    G.cv.notify_one();
+    return CORAL_OK;
+}
+
+// Counters of a handle, for tests and traces: out[0] attached, out[1] the pack fill was complete when coral_search_attach
+// began, out[2] steps queued in all, out[3] steps already queued when the last coral_search_bfs began (-1: none yet), out[4]
+// steps computed by the caller, out[5] / out[6] look-ahead and helper threads alive in the process.
+extern "C" int coral_search_stats(void *h, int64_t *out, int32_t n_out) {
+    if (!h || !out || n_out < 7) return CORAL_ERR_ARG;
+    Search &S = *(Search *)h;
+    Threads *G = threads_if_any();
     std::lock_guard<std::mutex> lk(S.qm);
-    if (S.cache.find(key) != S.cache.end()) return CORAL_OK;
-    auto ent = std::make_shared<Entry>();
-    memcpy(ent->key, key.data(), sizeof(ent->key));
-    ent->t_queued = now_s();
-    S.cache.emplace(key, ent);
-    S.queue.push_back(ent);
-    S.qcv.notify_one();
+    out[0] = S.attached ? 1 : 0; out[1] = S.stat_fill_ready; out[2] = S.stat_queued; out[3] = S.stat_queued_at_bfs;
+    out[4] = S.n_inline; out[5] = G ? G->n_workers.load() : 0; out[6] = G ? G->helpers.n_alive.load() : 0;
     return CORAL_OK;
 }
 
 extern "C" int coral_search_step(void *h, int64_t tid, int64_t s, int64_t e, int64_t si, int64_t ei) {
     if (!h) return CORAL_ERR_ARG;
     Search &S = *(Search *)h;
+    if (!S.attached) return not_attached(S, "search_step");
     const std::array<int64_t, 5> key = {tid, s, e, si, ei};
     std::shared_ptr<Entry> ent;
     {
@@ -1089,7 +1389,7 @@ extern "C" int coral_search_step(void *h, int64_t tid, int64_t s, int64_t e, int
             fprintf(stderr, "  step contig %lld [%lld, %lld]: queued %.2f ms before it was asked for, compute %.2f ms (%s), asked -> ready %.2f ms; "
                     "%zu runs, %zu candidates, %zu reads in the runs; reach %.2f union %.2f candidates %.2f calls %.2f ms\n", (long long)key[0], (long long)key[1], (long long)key[2],
                     (t_ask - ent->t_queued) * 1e3, (ent->t_end - ent->t_start) * 1e3, ent->who == 0 ? "caller" : "worker", (now_s() - t_ask) * 1e3,
-                    ent->res.groups.size() / 4, ent->res.cand.size() / 13, ent->res.order.size(), ent->res.t_phase[0] * 1e3, ent->res.t_phase[1] * 1e3,
+                    ent->res.groups.size() / 4, ent->res.cand.size() / 13, (size_t)ent->res.order_off.back(),ent->res.t_phase[0] * 1e3, ent->res.t_phase[1] * 1e3,
                     ent->res.t_phase[2] * 1e3, ent->res.t_phase[3] * 1e3);
         S.current_entry = ent;
         S.current = &ent->res;
@@ -1107,7 +1407,8 @@ extern "C" int coral_search_result(void *h, int64_t *n_meta, const int64_t **met
                                    int64_t *n_sup, const int64_t **sup, const double **stats, const int64_t **order_off,
                                    const int32_t **order) {
     if (!h || !n_meta || !meta || !n_cand || !cand || !n_sup || !sup || !stats) return CORAL_ERR_ARG;
-    const StepResult &R = *((Search *)h)->current;
+    StepResult &R = *((Search *)h)->current;
+    R.ensure_flat();                                      // (built for the first caller that asks; a step alone does not need them)
     *n_meta = (int64_t)R.meta.size();
     *meta = R.meta.data();
     *n_cand = (int64_t)R.cand.size() / 13;
@@ -1126,11 +1427,12 @@ extern "C" int coral_search_result(void *h, int64_t *n_meta, const int64_t **met
 extern "C" int coral_search_within(void *h, int32_t n_int, const int64_t *int_tid, const int64_t *int_start, const int64_t *int_end) {
     if (!h || n_int < 0 || (n_int > 0 && (!int_tid || !int_start || !int_end))) return CORAL_ERR_ARG;
     Search &S = *(Search *)h;
+    if (!S.attached) return not_attached(S, "search_within");
     StepResult &R = S.main_result;
     R.clear();
     S.current = &R;
     S.current_entry.reset();
-    std::vector<std::vector<int32_t>> by_tid((size_t)S.n_tid);              // interval indices per contig, list order kept
+    std::vector<std::vector<int32_t>> by_tid((size_t)S.n_tid);             // interval indices per contig, list order kept
     for (int32_t k = 0; k < n_int; ++k)
         if (int_tid[k] >= 0 && int_tid[k] < S.n_tid) by_tid[(size_t)int_tid[k]].push_back(k);
     auto first_interval = [&](const PackedRow &w) -> int32_t {
@@ -1171,7 +1473,8 @@ extern "C" int coral_search_within(void *h, int32_t n_int, const int64_t *int_ti
         return ok;
     };
     bool contigs_ok = true;
-    const int pieces = (S.pool && S.n_reads >= 4 * S.par_min_reads) ? 4 : 1;
+    TaskPool *const pool = helper_pool(S);
+    const int pieces = (pool && S.n_reads >= 4 * S.par_min_reads) ? 4 : 1;
     if (pieces == 1) {
         contigs_ok = scan_reads(0, S.n_reads, R.cand);
     } else {
@@ -1180,7 +1483,7 @@ extern "C" int coral_search_within(void *h, int32_t n_int, const int64_t *int_ti
         std::vector<std::function<void()>> tasks;
         for (int c = 0; c < pieces; ++c)
             tasks.emplace_back([&, c]() { okv[(size_t)c] = scan_reads(S.n_reads * c / pieces, S.n_reads * (c + 1) / pieces, part[(size_t)c]); });
-        S.pool->run(tasks);
+        pool->run(tasks);
         for (int c = 0; c < pieces; ++c) {
             contigs_ok &= okv[(size_t)c] != 0;
             R.cand.insert(R.cand.end(), part[(size_t)c].begin(), part[(size_t)c].end());
@@ -1200,6 +1503,7 @@ extern "C" int coral_search_between(void *h, int64_t n_sel, const int32_t *reads
                                     int64_t s2, int64_t e2) {
     if (!h || n_sel < 0 || (n_sel > 0 && !reads)) return CORAL_ERR_ARG;
     Search &S = *(Search *)h;
+    if (!S.attached) return not_attached(S, "search_between");
     StepResult &R = S.main_result;
     R.clear();
     S.current = &R;
@@ -1225,6 +1529,11 @@ extern "C" int coral_search_bfs(void *h, int32_t n_seed, const int64_t *iv, cons
                                 int32_t log_level) {
     if (!h || n_seed < 0 || (n_seed > 0 && !iv) || !seg_cn || !seg_ix || !chr_rank || !tid_has_rows) return CORAL_ERR_ARG;
     Search &S = *(Search *)h;
+    if (!S.attached) return not_attached(S, "search_bfs");
+    {
+        std::lock_guard<std::mutex> lk(S.qm);
+        S.stat_queued_at_bfs = S.stat_queued;
+    }
     S.bfs = std::make_shared<BfsOut>();
     BfsOut &O = *S.bfs;
     for (int32_t k = 0; k < n_seed; ++k) {

@@ -233,6 +233,7 @@ class bam_to_breakpoint_nanopore():
         self.ccid2id = dict()
         self.new_bp_list = []
         self._search_ctx: Optional[PairSearch] = None      # native side of the interval search (coral_search_*)
+        self._cn_col, self._seg_tab = {}, None             # read_cns: the CN column per chromosome, the search's segment tables
         self.new_bp_stats = []
         self.new_bp_ccids = []
         self.source_edges = []
@@ -270,6 +271,7 @@ class bam_to_breakpoint_nanopore():
         """Parse the CN segments and estimate the normal long-read coverage (ibg:75-136)."""
         self.cns_intervals, self.log2_cn = [], []
         tree: Dict[str, list] = {}
+        cn_col: Dict[str, list] = {}                      # the CN values of cns_intervals_by_chr, as plain columns
         idx = 0
         with open(cns, 'r') as fp:
             for line in fp:
@@ -279,6 +281,7 @@ class bam_to_breakpoint_nanopore():
                 self.cns_intervals.append([s[0], int(s[1]), int(s[2]) - 1])
                 if s[0] not in tree:
                     tree[s[0]] = []
+                    cn_col[s[0]] = []
                     self.cns_intervals_by_chr[s[0]] = []
                     idx = 0
                 tree[s[0]].append((int(s[1]), int(s[2]), idx))
@@ -286,9 +289,11 @@ class bam_to_breakpoint_nanopore():
                 if cns.endswith(".cns"):
                     self.cns_intervals_by_chr[s[0]].append([s[0], int(s[1]), int(s[2]) - 1, 2 * (2 ** float(s[4]))])
                     self.log2_cn.append(float(s[4]))
+                    cn_col[s[0]].append(self.cns_intervals_by_chr[s[0]][-1][3])
                 elif cns.endswith(".bed"):
                     self.cns_intervals_by_chr[s[0]].append([s[0], int(s[1]), int(s[2]) - 1, float(s[3])])
                     self.log2_cn.append(np.log2(float(s[3]) / 2.0))
+                    cn_col[s[0]].append(self.cns_intervals_by_chr[s[0]][-1][3])
                 else:
                     sys.stderr.write(cns + "\n")
                     sys.stderr.write("Invalid cn_seg file format!\n")
@@ -298,6 +303,8 @@ class bam_to_breakpoint_nanopore():
             o = np.argsort(st, kind="stable")
             disjoint = bool((en[o][:-1] <= st[o][1:]).all())
             self.cns_tree[c] = (st, en, ix, o, disjoint)
+        self._cn_col, self._seg_tab = cn_col, None
+        self._seg_tables()                                # the search's view of the segments, once per build
         logging.debug(_t() + "Total num LR copy number segments: %d." % (len(self.log2_cn)))
         order = np.argsort(self.log2_cn)
         im = int(len(order) / 2.4)
@@ -336,6 +343,117 @@ class bam_to_breakpoint_nanopore():
         assert (hits.sum(1) <= 1).all()
         return np.where(hits.any(1), ix[np.argmax(hits, 1)], -1)
 
+    def _seg_tables(self):
+        """The CN segments as the native search takes them, contig by contig in header order, file order inside a contig:
+        (seg_off int64 [n_tid + 1], seg_start, seg_end (inclusive), seg_cn float64, seg_ix = the reference's per-chromosome
+        index) — the rows of ``cns_intervals_by_chr`` as read_cns read them, from the columns it kept (``cns_tree``, the CN
+        column).  read_cns builds them, once per build; ``cns_intervals_by_chr`` is not written to after it."""
+        if self._seg_tab is not None:
+            return self._seg_tab
+        chroms = self.rec.header_chroms
+        tree, cn_col = self.cns_tree, self._cn_col
+        seg_off = np.zeros(len(chroms) + 1, dtype=np.int64)
+        st, en, cn, ix = [], [], [], []
+        for t, c in enumerate(chroms):
+            seg_off[t + 1] = seg_off[t] + len(cn_col.get(c, ()))
+            if c in tree:
+                assert len(cn_col[c]) == len(tree[c][0]) == len(self.cns_intervals_by_chr[c]), "CN segment file of an unknown format"
+                st.append(tree[c][0])
+                en.append(tree[c][1] - 1)
+                cn.append(np.asarray(cn_col[c], dtype=np.float64))
+                ix.append(np.asarray(tree[c][2], dtype=np.int64))
+        cat = lambda parts, dt: np.concatenate(parts) if parts else np.zeros(0, dtype=dt)
+        self._seg_tab = (seg_off, cat(st, np.int64), cat(en, np.int64), cat(cn, np.float64), cat(ix, np.int64))
+        return self._seg_tab
+
+    # ---- the early half of the native search ---------------------------------------------------
+    def _start_early_search(self, T):
+        """The part of the search handle that needs the chimeric table and the pair table only (PairSearch with the table
+        alone: offsets, 17 MB of packed rows at 2 M reads) is made on a thread of its own while the CIGAR scan runs, instead
+        of in front of the search.  Only where the threaded search will be used.  The thread waits for the staged copy of the
+        pair table itself (an event of the copy stream: any thread may wait for it).  It refers to the table and its own
+        result only: whatever becomes of this object, the arrays the native call reads stay alive until it returns, and a
+        handle nobody takes is freed with the thread's result."""
+        if os.environ.get("CORAL_SEARCH_EARLY", "1") == "0" or _VERIFY_SET_ORDER:
+            return
+        if len(T.name_id) < int(os.environ.get("CORAL_SEARCH_MIN_READS", "20000")):
+            return
+        import threading
+        box, n_tid = {}, len(self.rec.header_chroms)
+
+        def early():
+            try:
+                box["search"] = PairSearch(T, n_tid=n_tid)
+            except Exception as exc:                  # noqa: BLE001 — _search() makes the handle itself then, and raises what that raises
+                box["error"] = exc
+        th = threading.Thread(target=early, name="coral-search-early")
+        th.start()
+        self._search_early = (th, box)
+
+    def _take_early_search(self) -> Optional[PairSearch]:
+        job, self._search_early = getattr(self, "_search_early", None), None
+        if job is None:
+            return None
+        job[0].join()
+        return job[1].pop("search", None)
+
+    def _drop_early_search(self):
+        """Error paths (fetch() raises, the build is given up): no thread left in a native call, the early handle freed."""
+        S = self._take_early_search()
+        if S is not None:
+            S.close()
+
+    def __del__(self):
+        try:
+            self._drop_early_search()
+        except Exception:                             # noqa: BLE001 — interpreter shutdown
+            pass
+
+    def _search_params(self):
+        # a few thousand chimeric reads: a step costs less than handing it to another thread
+        small = len(self._chim.read) < int(os.environ.get("CORAL_SEARCH_MIN_READS", "20000"))
+        n_threads = 0 if (_VERIFY_SET_ORDER or small) else int(os.environ.get("CORAL_SEARCH_THREADS", "6"))
+        floor = max(self.normal_cov * self.min_bp_cov_factor, 3.0)
+        return (self.min_cluster_cutoff, self.max_seq_len, self.max_breakpoint_distance_cutoff, self.min_bp_match_cutoff_, floor, n_threads)
+
+    def _attach_early_search(self):
+        """hash_alignment_to_seg, as soon as cni0 / cni1 and the inverted index exist: the early handle gets its second half
+        and the build's parameters, and the steps of the seed intervals are asked for at once — the workers compute them while
+        this thread finishes hash_alignment_to_seg and the search's prelude.  Returns the first row of every contig among the
+        rows with CN segments (coral_search_attach finds them in its pass over the rows), or None without an early handle."""
+        t0 = time.perf_counter()
+        S = self._take_early_search()
+        if S is None:
+            return None
+        t1 = time.perf_counter()
+        try:
+            seg_off, seg_start, seg_end, _, _ = self._seg_tables()
+            first = S.attach(self._read_hashes(), self._e_key, self._e_row, seg_off, seg_start, seg_end)
+            S.params = self._search_params()
+            S.set_params(*S.params)
+        except BaseException:
+            S.close()
+            raise
+        if os.environ.get("CORAL_TRACE_OPEN") == "1":
+            sys.stderr.write("hash_alignment_to_seg: early search handle: waited %.2f ms for its thread, attach + parameters %.2f ms, "
+                             "pack %s when attach began\n" % ((t1 - t0) * 1e3, (time.perf_counter() - t1) * 1e3,
+                                                             "filled" if S.stats()["fill_ready_at_attach"] else "still being filled"))
+        if self._search_ctx is not None:
+            self._search_ctx.close()
+        self._search_ctx = S
+        present = np.nonzero(first >= 0)[0]
+        self._seg_tids = [int(t) for t in present[np.argsort(first[present], kind="stable")]]
+        # the seeds as find_amplicon_intervals will snap them (on copies: it snaps its own again, to the same coordinates, so
+        # its requests find these entries)
+        for iv in self.amplicon_intervals:
+            iv = list(iv)
+            try:
+                self._snap_seed(iv)
+            except (KeyError, IndexError):            # the reference's errors on a seed off the CN segments:
+                break                                 # find_amplicon_intervals meets the same seed and raises there
+            self._prefetch_interval(iv[0], iv[1], iv[2], search=S)        # (an error of the native call is an error here too)
+        return first
+
     # ---- A3 ----------------------------------------------------------------------------------
     def launch_record_kernels(self):
         """Issue the two passes that depend on the records alone before any host logic runs: the fused CIGAR scan (launched
@@ -363,6 +481,8 @@ class bam_to_breakpoint_nanopore():
             th = threading.Thread(target=hashes, name="coral-name-hashes")
             th.start()
             T._hash_job = (th, box)
+        if isinstance(T, ChimericTable):
+            self._start_early_search(T)
         if trace:
             sys.stderr.write("launch_record_kernels: scan issue %.1f ms, chimeric table %.1f ms\n" % ((t1 - t0) * 1e3, (time.perf_counter() - t1) * 1e3))
 
@@ -375,9 +495,13 @@ class bam_to_breakpoint_nanopore():
         if T is None:
             T = build_chimeric_table(self.rec)
         self._chim = T
-        T.finish_nm_stats()                           # (started with the table kernels; raises what the reference raises at ibg:154)
-        if T.n_mapq60_plain == 0:
-            raise ZeroDivisionError("float division by zero")                # ibg:159
+        try:
+            T.finish_nm_stats()                       # (started with the table kernels; raises what the reference raises at ibg:154)
+            if T.n_mapq60_plain == 0:
+                raise ZeroDivisionError("float division by zero")            # ibg:159
+        except Exception:
+            self._drop_early_search()                 # (the build ends here: the early half of the search handle goes with it)
+            raise
         s0, s1 = T.nm_sum, T.nm_sum_sq                                        # sequential adds, as the reference
         mean = s0 / T.n_mapq60_plain
         self.nm_stats = [mean, math.sqrt(s1 / T.n_mapq60_plain - mean ** 2), T.n_mapq60_plain]
@@ -445,28 +569,36 @@ class bam_to_breakpoint_nanopore():
             o = np.argsort(key, kind="stable")
             self._e_row, self._e_key = ent_row[o], key[o]
         self._hashed = True
+        # cni0 / cni1 and the inverted index exist (either branch): the early search handle is completed and the seeds' steps
+        # start on the workers before the rest of this function runs
+        first = self._attach_early_search()
         self.chimeric_alignments.invalidate()
-        rows = np.nonzero(T.cni0 != -3)[0]
-        kt = T.tid[rows]
-        present = np.nonzero(np.bincount(kt, minlength=n_tid))[0] if len(kt) else np.zeros(0, dtype=np.int64)
-        first_at = {int(t): int(np.argmax(kt == t)) for t in present}
-        self._seg_tids = sorted(first_at, key=first_at.get)                       # dict key order of ibg:201-202
+        if first is None:
+            rows = np.nonzero(T.cni0 != -3)[0]
+            kt = T.tid[rows]
+            present = np.nonzero(np.bincount(kt, minlength=n_tid))[0] if len(kt) else np.zeros(0, dtype=np.int64)
+            first_at = {int(t): int(np.argmax(kt == t)) for t in present}
+            self._seg_tids = sorted(first_at, key=first_at.get)                   # dict key order of ibg:201-202
         self.chimeric_alignments_seg = _SegIndexView(self)
 
     # ---- A5 ----------------------------------------------------------------------------------
-    def find_amplicon_intervals(self):
+    def _snap_seed(self, iv):
+        """One seed interval moved onto its CN segments, in place (ibg:343-360)."""
         by = self.cns_intervals_by_chr
+        c = iv[0]
+        lcni = self.pos2cni(c, iv[1])[0]
+        rcni = self.pos2cni(c, iv[2])[0]
+        iv[1] = by[c][lcni][1]
+        if self.pos2cni(c, by[c][lcni][1] - self.interval_delta):
+            iv[1] = by[c][lcni][1] - self.interval_delta
+        iv[2] = by[c][rcni][2]
+        if self.pos2cni(c, by[c][rcni][2] + self.interval_delta):
+            iv[2] = by[c][rcni][2] + self.interval_delta
+
+    def find_amplicon_intervals(self):
         logging.debug(_t() + "Updating seed amplicon intervals according to CN segments.")
         for iv in self.amplicon_intervals:
-            c = iv[0]
-            lcni = self.pos2cni(c, iv[1])[0]
-            rcni = self.pos2cni(c, iv[2])[0]
-            iv[1] = by[c][lcni][1]
-            if self.pos2cni(c, by[c][lcni][1] - self.interval_delta):
-                iv[1] = by[c][lcni][1] - self.interval_delta
-            iv[2] = by[c][rcni][2]
-            if self.pos2cni(c, by[c][rcni][2] + self.interval_delta):
-                iv[2] = by[c][rcni][2] + self.interval_delta
+            self._snap_seed(iv)
         ccid = 0
         _lib.check_pyset_replay()            # once per process: the set replay must match this interpreter's sets
         if not _VERIFY_SET_ORDER and os.environ.get("CORAL_SEARCH_BFS", "native") != "python" and not self.new_bp_list and \
@@ -490,12 +622,9 @@ class bam_to_breakpoint_nanopore():
         reference's containers here: interval lists, new_bp_list rows with lazy support sets, the connections dict in its
         insertion order, and the log lines in the order the reference emits them."""
         chroms = self.rec.header_chroms
-        by = self.cns_intervals_by_chr
         S = self._search()
         n_tid = len(chroms)
-        seg_cn = np.fromiter((float(v[3]) for c in chroms for v in by.get(c, ())), dtype=np.float64)
-        seg_ix = np.concatenate([np.asarray(self.cns_tree[c][2], dtype=np.int64) if c in self.cns_tree else np.zeros(0, dtype=np.int64)
-                                 for c in chroms]) if n_tid else np.zeros(0, dtype=np.int64)
+        _, _, _, seg_cn, seg_ix = self._seg_tables()
         assert len(seg_ix) == len(seg_cn)
         has = np.zeros(max(n_tid, 1), dtype=np.uint8)
         has[list(self._seg_tids)] = 1
@@ -676,27 +805,28 @@ class bam_to_breakpoint_nanopore():
 
     def _search(self) -> PairSearch:
         """Native side of the interval search over this build's chimeric table (created after hash_alignment_to_seg)."""
-        if self._search_ctx is None:
-            chroms = self.rec.header_chroms
-            by = self.cns_intervals_by_chr
-            seg_off = np.zeros(len(chroms) + 1, dtype=np.int64)
-            for t, c in enumerate(chroms):
-                seg_off[t + 1] = seg_off[t] + len(by.get(c, ()))
-            seg_start = np.fromiter((v[1] for c in chroms for v in by.get(c, ())), dtype=np.int64, count=int(seg_off[-1]))
-            seg_end = np.fromiter((v[2] for c in chroms for v in by.get(c, ())), dtype=np.int64, count=int(seg_off[-1]))
-            self._search_ctx = PairSearch(self._chim, self._read_hashes(), self._e_key, self._e_row, seg_off, seg_start, seg_end)
-            # a few thousand chimeric reads: a step costs less than handing it to another thread
-            small = len(self._chim.read) < int(os.environ.get("CORAL_SEARCH_MIN_READS", "20000"))
-            n_threads = 0 if (_VERIFY_SET_ORDER or small) else int(os.environ.get("CORAL_SEARCH_THREADS", "6"))
-            floor = max(self.normal_cov * self.min_bp_cov_factor, 3.0)
-            self._search_ctx.set_params(self.min_cluster_cutoff, self.max_seq_len, self.max_breakpoint_distance_cutoff,
-                                        self.min_bp_match_cutoff_, floor, n_threads)
-        return self._search_ctx
+        S = self._search_ctx
+        if S is not None and S.params is not None:
+            # the early handle (hash_alignment_to_seg gave it the parameters of that moment): the one to use unless a
+            # parameter was changed since
+            early, S.params = S.params, None
+            if early != self._search_params():
+                S.close()
+                S = self._search_ctx = None
+        if S is None:
+            self._drop_early_search()                     # (one that hash_alignment_to_seg never saw)
+            seg_off, seg_start, seg_end, _, _ = self._seg_tables()
+            S = self._search_ctx = PairSearch(self._chim, self._read_hashes(), self._e_key, self._e_row, seg_off, seg_start, seg_end)
+            S.set_params(*self._search_params())
+        return S
 
     def _prefetch_step(self, idx):
         """Tell the native search that interval ``idx`` will be searched: its step (a pure function of the coordinates) is
         computed ahead on a worker thread while this thread does the order-dependent part of earlier steps."""
         chrom, s, e = self.amplicon_intervals[idx][:3]
+        self._prefetch_interval(chrom, s, e)
+
+    def _prefetch_interval(self, chrom, s, e, search=None):
         try:
             si = self.pos2cni(chrom, s)[0]
             ei = self.pos2cni(chrom, e)[0]
@@ -704,7 +834,7 @@ class bam_to_breakpoint_nanopore():
             return
         tid = self._tid_of[chrom]
         if tid in self._seg_tids:
-            self._search().prefetch(tid, s, e, si, ei)
+            (search if search is not None else self._search()).prefetch(tid, s, e, si, ei)
 
     def _search_step(self, chrom, s, e):
         """The part of one step of the interval search that is a pure function of the interval's coordinates (ibg:362-434):

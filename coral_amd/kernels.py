@@ -416,12 +416,13 @@ class Staged:
         return out
 
     def wait(self, name: str):
-        ev = self.events.pop(name, None)
+        ev = self.events.get(name)                        # (kept until it has landed: a second thread that asks meanwhile waits too)
         if ev is not None:
             ev.synchronize()
+            self.events.pop(name, None)
 
     def close(self):
-        for ev in self.events.values():
+        for ev in list(self.events.values()):             # (a waiter on another thread may take its event out meanwhile)
             ev.synchronize()
         self.events = {}
         for buf in self._leases:

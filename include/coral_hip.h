@@ -255,7 +255,29 @@ int coral_bp_pair_table(int32_t n_reads, int32_t n_rows, const int32_t *off, con
  *   stats double[6 per call], sup int64[n_sup];
  *   order_off int64[n_groups + 1] / order int32[] = the reads of every run in iteration order (table indices).
  * CORAL_ERR_FORMAT: a candidate touches a contig outside chr1..22,X,Y,M (KeyError at bu:293 in the reference).
+ *
+ * A handle can be made in two parts.  coral_search_create_early takes what exists before hash_alignment_to_seg (table rows,
+ * name ids, pair table, number of contigs), lays out the per-read pack and starts filling it without waiting (a big table on
+ * threads of the handle's own).  coral_search_attach then brings the CN-segment indices, read hashes, inverted index and CN
+ * segments, waits for the fill, writes the indices into the pack and reports in first_row_of_tid int64[n_tid] (may be null)
+ * the first table row with cni0 != -3 per contig (-1: none).  coral_search_create is the two in a row.  Until it is attached
+ * a handle answers step / prefetch / within / between / bfs with CORAL_ERR_ARG; coral_search_free is always allowed.
+ *
+ * The look-ahead threads and the helper threads of big steps belong to the PROCESS: the first coral_search_params with
+ * n_threads > 0 starts them, later handles share them (asking for more makes the set grow; results never depend on the
+ * count), coral_search_free joins nothing — it drops the handle's queued steps and waits for those being computed.
+ * coral_search_shutdown joins the threads (idempotent; a later prefetch starts them again; after fork() the child starts
+ * its own).  coral_search_stats: out int64[>= 7] = attached, pack fill complete when attach began, steps queued in all, steps
+ * already queued when the last coral_search_bfs began (-1: none), steps computed by the caller, look-ahead / helper threads alive.
  * ------------------------------------------------------------------------------------------------ */
+void *coral_search_create_early(int64_t n_reads, int64_t n_rows, const int64_t *off, const int64_t *row_read,
+                                const int64_t *row_tid, const int64_t *ra, const int64_t *rb, const int64_t *read_name,
+                                const int32_t *pairs, int32_t n_tid);
+int coral_search_attach(void *handle, const int64_t *cni0, const int64_t *cni1, const int64_t *read_hash, int64_t n_ent,
+                        const int64_t *e_key, const int64_t *e_row, const int64_t *seg_off, const int64_t *seg_start,
+                        const int64_t *seg_end, int64_t *first_row_of_tid);
+int coral_search_shutdown(void);
+int coral_search_stats(void *handle, int64_t *out, int32_t n_out);
 void *coral_search_create(int64_t n_reads, int64_t n_rows, const int64_t *off, const int64_t *row_read, const int64_t *row_tid,
                           const int64_t *ra, const int64_t *rb, const int64_t *cni0, const int64_t *cni1,
                           const int64_t *read_hash, const int64_t *read_name, int64_t n_ent, const int64_t *e_key,

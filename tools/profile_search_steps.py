@@ -40,7 +40,7 @@ def timed(obj, name, label=None):
 
 from coral_amd import kernels, chimeric
 B = ibg.bam_to_breakpoint_nanopore
-for nm in ("_find_intervals_native", "_merge_intervals", "_search", "_coverage", "_add_clustered"):
+for nm in ("_find_intervals_native", "_merge_intervals", "_search", "_attach_early_search", "_coverage", "_add_clustered"):
     timed(B, nm)
 timed(chimeric.PairSearch, "bfs", "PairSearch.bfs (native call + copies)")
 timed(chimeric.PairSearch, "within", "PairSearch.within")
