@@ -498,10 +498,20 @@ def _checked(x, nu, w_inv, w_lin, w_log, A):
         # ends with status "unknown" there and keeps its last iterate (bg:565-568); say so instead of passing silently
         logging.warning("CN assignment did not converge (relative KKT residual %.3g); the CN column is the last iterate."
                         % solve_cn_lr.last_residual)
+    # The program is not convex in general (w_log = -0.5 on sequence and source edges): the term of edge j is convex where
+    # c_j = w_log_j + 2 w_inv_j / x_j = h_j x_j² > 0.  With every c_j > 0 the point lies in a box on which the whole objective
+    # is convex; otherwise only a second-order test says what it is (tests/cn_reference.py::certificate).  O(n), no linear algebra.
+    c = (w_log + 2.0 * w_inv / x)[~free] if n else np.empty(0)
+    solve_cn_lr.last_min_curvature = float(np.min(c)) if len(c) else float("inf")
+    if not solve_cn_lr.last_min_curvature > 0:
+        j = int(np.nonzero(~free)[0][int(np.argmin(c))])
+        logging.debug("CN assignment: the answer lies outside the convex box (edge %d: w_log + 2 w_inv / x = %.3g)."
+                      % (j, solve_cn_lr.last_min_curvature))
     return x
 
 
 solve_cn_lr.last_residual = 0.0
+solve_cn_lr.last_min_curvature = float("inf")
 
 
 def compute_cn_lr(g, normal_cov_lr):

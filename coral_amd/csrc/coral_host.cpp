@@ -351,7 +351,11 @@ extern "C" int coral_names_unify(int32_t n_pieces, const int64_t *n_names, const
 
 // ---------------------------------------------------------------------------------------------
 // coral_cn_solve — the CN assignment of one amplicon graph: argmin Σ w_inv/x + w_lin·x − w_log·log x  s.t.  A x = 0, x > 0,
-// started at x = 1 (the convex program compute_cn_lr hands to cvxopt.solvers.cp, /root/reference/src/breakpoint_graph.py:495-606).
+// started at x = 1 (the program compute_cn_lr hands to cvxopt.solvers.cp, the reference's src/breakpoint_graph.py:495-606).
+// Not convex in general: a sequence or source edge has w_log = -0.5, its curvature h = w_log/x² + 2 w_inv/x³ is negative once
+// x > 4 w_inv.  Convex on the box {x_j < 2 w_inv_j / |w_log_j|} of those edges; that the point returned is a minimum, and the one
+// every start reaches, is certified by tests/test_cn_solver.py against a 50-digit solve, not by this iteration,
+// which descends on the norm of the KKT residual and not on the objective.
 // Infeasible-start Newton on the KKT system with a backtracking search on the KKT residual — the iteration of
 // coral_amd/breakpoint_graph.py:solve_cn_lr statement by statement (same formulas, same stopping rules), on the sparse balance
 // matrix (an edge touches at most two nodes: a column of A has at most two non-zeros), so that an iteration costs tens of

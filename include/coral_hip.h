@@ -404,11 +404,13 @@ int coral_concordant_counts(int32_t n_edges, const int64_t *pt_begin, const int6
 int coral_independent_rows(int32_t m, int32_t n, const double *A, uint8_t *keep, double tol);
 
 /* coral_cn_solve — HOST function: the CN assignment of one amplicon graph,  argmin Σ w_inv/x + w_lin·x − w_log·log x  s.t.
- * A x = 0, x > 0,  started at x = 1 — the convex program compute_cn_lr gives to cvxopt.solvers.cp
- * (/root/reference/src/breakpoint_graph.py:495-606; one variable per edge, one balance row per interior node).  A double[p][n]
- * row-major with linearly independent rows.  Infeasible-start Newton with a backtracking search on the KKT residual, until the
- * relative step is below 1e-13.  Returns 0 (x[n] and nu[p] filled, *n_iter = iterations), 1 = the reduced Newton system was singular
- * (the caller takes its general path), negative = bad arguments.  CN parity against cvxopt itself is unpinned. */
+ * A x = 0, x > 0,  started at x = 1 — the program compute_cn_lr gives to cvxopt.solvers.cp (the reference's
+ * src/breakpoint_graph.py:495-606; one variable per edge, one balance row per interior node).  Not convex in general (w_log = -0.5
+ * on sequence and source edges); convex on the box x_j < 2 w_inv_j / |w_log_j| for those edges, and that the answer is a minimum
+ * is certified by tests/test_cn_solver.py against a 50-digit solve.  A double[p][n] row-major with linearly
+ * independent rows.  Infeasible-start Newton with a backtracking search on the KKT residual, until the relative step is below
+ * 1e-13.  Returns 0 (x[n] and nu[p] filled, *n_iter = iterations), 1 = the reduced Newton system was singular (the caller takes
+ * its general path), negative = bad arguments.  CN parity against cvxopt itself is unpinned. */
 int coral_cn_solve(int32_t n, int32_t p, const double *w_inv, const double *w_lin, const double *w_log, const double *A,
                    int32_t max_iter, double *x, double *nu /* [p]: the multipliers of the balance rows */, int32_t *n_iter);
 
