@@ -121,6 +121,17 @@ def lib():
     L.coral_search_bfs_get.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
     L.coral_search_within.argtypes = [C.c_void_p, C.c_int32, P, P, P]
     L.coral_search_between.argtypes = [C.c_void_p, C.c_int64, P] + [C.c_int64] * 6
+    L.coral_smalldel_pass.argtypes = [C.c_int64, P, C.c_int64, P, P, P, P, P, C.c_int32, P, C.c_double, C.c_int64, C.c_int64, C.c_double]
+    L.coral_smalldel_pass.restype = C.c_void_p
+    L.coral_tail_result_free.argtypes = [C.c_void_p]
+    L.coral_tail_result_free.restype = None
+    L.coral_tail_result_rc.argtypes = [C.c_void_p]
+    L.coral_tail_result_error.argtypes = [C.c_void_p]
+    L.coral_tail_result_error.restype = C.c_char_p
+    L.coral_tail_result_get.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
+    L.coral_search_tail_prefetch.argtypes = [C.c_void_p, C.c_int32, P, C.c_int64, P, C.c_int64, P, P, P, P, P]
+    L.coral_search_tail_collect.argtypes = [C.c_void_p, C.c_int32, C.c_int32, P, C.c_int64, P, C.c_int64, P, P, P, P, P, C.POINTER(C.c_void_p)]
+    L.coral_search_tail_stats.argtypes = [C.c_void_p, P]
     L.coral_sa_table.argtypes = [C.c_int32, P, P, P, P, C.c_int32, C.c_int32, P, P, P, P, C.c_int64, P, P, P, P, P,
                                  C.POINTER(C.c_int32), P]
     L.coral_sa_last_error.restype = C.c_char_p

@@ -163,6 +163,62 @@ def first_interval_overlap(T: ChimericTable, intervals: Sequence[Tuple[int, int,
     return io
 
 
+def tail_result(res) -> dict:
+    """Copies of a native tail result (coral_tail_result_get): ``cands`` (Candidates), ``called`` = (cluster sizes, calls) as
+    bpcluster.call_breakpoints returns them, and for the small-deletion pass ``groups`` = (name id per group, bounds, tid, nxt,
+    prv, b0, b1, mapq) — the arguments of large_indel_alignments."""
+    import ctypes as C
+    from . import _lib
+    L = _lib.lib()
+
+    def get(which, ty, dtype):
+        ptr, n = C.c_void_p(), C.c_int64(0)
+        _lib.check(L.coral_tail_result_get(res, which, C.byref(ptr), C.byref(n)), "coral_tail_result_get")
+        if not n.value:
+            return np.zeros(0, dtype=dtype)
+        return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ty)), shape=(n.value,)).copy()
+    i64, i32 = (C.c_int64, np.int64), (C.c_int32, np.int32)
+    rows = get(0, *i64).reshape(-1, 13)
+    cols = np.ascontiguousarray(rows.T)
+    cands = Candidates(**{k: cols[j] for j, k in enumerate(Candidates.FIELDS)})
+    sizes = get(1, *i32).tolist()
+    head, p1, p2 = (get(w, *i64).tolist() for w in (2, 3, 4))
+    stats, flags = get(5, C.c_double, np.float64), get(6, *i32).tolist()
+    sup_off, sup_idx = get(7, *i64).tolist(), get(8, *i64)
+    calls = []
+    for k in range(len(head)):
+        st = stats[6 * k:6 * k + 6].tolist()
+        if flags[k] & 1:
+            st[2] = 0                                     # the reference's ValueError branch stores the integer 0
+        if flags[k] & 2:
+            st[3] = 0
+        calls.append((head[k], p1[k], p2[k], sup_idx[sup_off[k]:sup_off[k + 1]], st))
+    out = dict(cands=cands, called=(sizes, calls))
+    grows = get(11, *i64).reshape(-1, 6)
+    if len(grows):
+        g = np.ascontiguousarray(grows.T)
+        out["groups"] = (get(9, *i64), get(10, *i64), g[0], g[1], g[2], g[3], g[4], g[5])
+    return out
+
+
+def smalldel_pass(gaps, cols, intervals, min_cluster_cutoff, bp_distance_cutoff, match_cutoff, accept_floor) -> dict:
+    """coral_smalldel_pass, synchronously, without a search handle: gap rows + record columns (h_tid, h_pos, h_end, h_name_id,
+    h_mapq) + [(tid, start, end)] -> ``tail_result``."""
+    from . import _lib
+    L = _lib.lib()
+    iv, gaps, cols = PairSearch._tail_args(intervals, gaps, cols)
+    res = L.coral_smalldel_pass(len(gaps), gaps.ctypes.data, len(cols[0]), *[c.ctypes.data for c in cols], len(iv), iv.ctypes.data,
+                                float(min_cluster_cutoff), int(bp_distance_cutoff), int(match_cutoff), float(accept_floor))
+    if not res:
+        raise _lib.CoralHipError("coral_smalldel_pass: out of memory")
+    try:
+        if L.coral_tail_result_rc(res) != 0:
+            raise _lib.CoralHipError("coral_smalldel_pass failed: %s" % L.coral_tail_result_error(res).decode())
+        return tail_result(res)
+    finally:
+        L.coral_tail_result_free(res)
+
+
 class PairSearch:
     """Native side of the interval search over one chimeric table (csrc/coral_search.cpp): the reach sets of ibg:369-384
     replayed as CPython sets, the runs of neighbouring segments, and alignment2bp / alignment2bp_l as a FILTER over the pair
@@ -224,8 +280,9 @@ class PairSearch:
 
     def close(self):
         if self._h:
-            self._L.coral_search_free(self._h)
+            self._L.coral_search_free(self._h)            # (drops queued tail jobs, waits for those in flight)
             self._h = None
+        self._tail_keep = None
 
     __del__ = close
 
@@ -299,9 +356,11 @@ class PairSearch:
         self._check(self._L.coral_search_step(self._h, int(tid), int(s), int(e), int(si), int(ei)), "coral_search_step")
         return self._result(want_orders)
 
-    def bfs(self, seeds, seg_cn, seg_ix, chr_rank, tid_has_rows, cn_gain, interval_delta, log_level):
+    def bfs(self, seeds, seg_cn, seg_ix, chr_rank, tid_has_rows, cn_gain, interval_delta, log_level, on_intervals=None):
         """The whole interval search in one native call (coral_search_bfs).  ``seeds`` int64 [n, 4] = contig id, start, end, ccid.
-        Returns {which: numpy array} of coral_search_bfs_get (copies) — see include/coral_hip.h."""
+        Returns {which: numpy array} of coral_search_bfs_get (copies) — see include/coral_hip.h.  ``on_intervals(rows)`` is
+        called with the interval rows (which = 0) before the other arrays are copied: what depends on the intervals alone
+        (tail_prefetch) starts then."""
         C = self._C
         i64, f64 = (lambda a: np.ascontiguousarray(a, dtype=np.int64)), (lambda a: np.ascontiguousarray(a, dtype=np.float64))
         seeds, seg_cn, seg_ix = i64(seeds).reshape(-1, 4), f64(seg_cn), i64(seg_ix)
@@ -322,7 +381,63 @@ class PairSearch:
             ty = C.c_double if which == 3 else C.c_int64
             out[which] = (np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ty)), shape=(n.value,)).copy() if n.value else
                           np.zeros(0, dtype=np.float64 if which == 3 else np.int64))
+            if which == 0 and on_intervals is not None:
+                on_intervals(out[0])
         return out
+
+    # -- the candidates behind the search, asked for ahead (coral_search_tail_*) -----------------------
+    @staticmethod
+    def _tail_args(intervals, gaps, cols):
+        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+        iv = np.ascontiguousarray(np.asarray(intervals, dtype=np.int64).reshape(-1, 3))
+        if gaps is None:
+            return iv, None, None
+        gaps = np.ascontiguousarray(gaps, dtype=np.int64).reshape(-1, 6)
+        cols = tuple(i32(c) for c in cols)
+        assert len(cols) == 5 and all(len(c) == len(cols[0]) for c in cols)
+        return iv, gaps, cols
+
+    def tail_prefetch(self, intervals, gaps, cols):
+        """Have the small-deletion pass over ``gaps`` (ScanResult.gaps, already on the host) and ``within`` of ``intervals``,
+        each with its breakpoint calls, computed on the look-ahead threads.  ``cols`` = (h_tid, h_pos, h_end, h_name_id,
+        h_mapq).  The arrays are kept alive here until both jobs were collected or the handle is closed."""
+        iv, gaps, cols = self._tail_args(intervals, gaps, cols)
+        self._tail_keep = (gaps, cols)
+        self._tail_left = {0, 1}
+        self._lib.check(self._L.coral_search_tail_prefetch(self._h, len(iv), iv.ctypes.data, len(gaps), gaps.ctypes.data, len(cols[0]),
+                                                           *[c.ctypes.data for c in cols]), "coral_search_tail_prefetch")
+
+    def _tail_collect(self, which, iv, gaps, cols):
+        C = self._C
+        res = C.c_void_p()
+        if which == 0:
+            args = [len(gaps), gaps.ctypes.data, len(cols[0])] + [c.ctypes.data for c in cols]
+        else:
+            args = [0, None, 0, None, None, None, None, None]
+        self._check(self._L.coral_search_tail_collect(self._h, which, len(iv), iv.ctypes.data, *args, C.byref(res)), "coral_search_tail_collect")
+        out = tail_result(res)
+        left = getattr(self, "_tail_left", None)
+        if left:
+            left.discard(which)
+            if not left:
+                self._tail_keep = None                    # both jobs collected: nothing native refers to the arrays any more
+        return out
+
+    def tail_smalldel(self, intervals, gaps, cols):
+        """The small-deletion pass (coral_smalldel_pass) for ``intervals``: the job asked for ahead when its key and arrays are
+        these, else computed now.  Returns what ``tail_result`` returns."""
+        iv, g, c = self._tail_args(intervals, gaps, cols)
+        return self._tail_collect(0, iv, g, c)
+
+    def tail_within(self, intervals):
+        """``within(intervals)`` and its breakpoint calls: the job asked for ahead when its key is this list, else computed now."""
+        iv, _, _ = self._tail_args(intervals, None, None)
+        return self._tail_collect(1, iv, None, None)
+
+    def tail_stats(self) -> dict:
+        out = np.zeros(4, dtype=np.int64)
+        self._lib.check(self._L.coral_search_tail_stats(self._h, out.ctypes.data), "coral_search_tail_stats")
+        return dict(zip(("queued", "served", "on_demand", "served_by_caller"), (int(v) for v in out)))
 
     def within(self, intervals) -> Candidates:
         """alignment2bp_l (bu:129-186) of every chimeric read, dict order, against [(tid, start, end)]."""

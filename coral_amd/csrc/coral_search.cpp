@@ -14,6 +14,9 @@
 // computed AHEAD on worker threads as soon as the caller knows an interval will be searched (coral_search_prefetch); the
 // order-dependent rest of the search (addbp, interval refinement) then finds the result ready (coral_search_step).
 // coral_search_within is the pair filter for alignment2bp_l over all chimeric reads (find_breakpoints, ibg:676-690).
+// What follows the search — that filter and the small-deletion pass over the CIGAR scan's gap rows (ibg:721-802), each with
+// its breakpoint calls — is pure as well, a function of the merged interval list: coral_search_tail_prefetch queues both on
+// the same threads the moment the search returns, coral_search_tail_collect serves them (end of this file).
 #include <math.h>
 #include <pthread.h>
 #include <sched.h>
@@ -32,6 +35,7 @@
 #include <functional>
 #include <memory>
 #include <mutex>
+#include <new>
 #include <thread>
 #include <unordered_map>
 #include <vector>
@@ -127,7 +131,32 @@ struct Scratch {
 
 struct Search;
 
-struct Entry {                                            // one (possibly pending) step in the cache
+// The two jobs behind a finished search (coral_search_tail_prefetch): the small-deletion pass over the scan's gap rows and the
+// pair filter of find_breakpoints, each with its breakpoint calls — pure functions of the merged interval list.
+struct TailArgs {                                         // borrowed host arrays of the small-deletion pass
+    int64_t n_gap = 0, n_rec = 0;
+    const int64_t *gaps = nullptr;                        // [n_gap][6]
+    const int32_t *h_tid = nullptr, *h_pos = nullptr, *h_end = nullptr, *h_name = nullptr, *h_mapq = nullptr;
+    bool operator==(const TailArgs &o) const {
+        return n_gap == o.n_gap && n_rec == o.n_rec && gaps == o.gaps && h_tid == o.h_tid && h_pos == o.h_pos && h_end == o.h_end &&
+               h_name == o.h_name && h_mapq == o.h_mapq;
+    }
+};
+
+struct TailResult {
+    int rc = CORAL_OK;
+    char err[200] = "";
+    std::vector<int64_t> cand;                            // [n][13], as StepResult::cand
+    Calls calls;                                          // coral_call_breakpoints on them, sub-cluster counter advancing
+    std::vector<int64_t> grp_name, bounds, rows;          // small deletions: name id per group, [G + 1], [n][6] tid nxt prv b0 b1 mapq
+    double t_phase[3] = {0, 0, 0};                        // CORAL_SEARCH_PROFILE=2: selection / filter, grouping, calls (seconds)
+};
+
+struct Entry {                                            // one (possibly pending) step in the cache, or one tail job
+    int kind = 0;                                         // 0 a step, 1 the small-deletion pass, 2 the pair filter over all reads
+    std::vector<int64_t> tail_iv;                         // [n_int][3]: the key of a tail job
+    TailArgs tail_args;
+    TailResult tail;
     std::mutex m;
     std::condition_variable cv;
     bool done = false, taken = false;                     // taken: some thread is computing it
@@ -293,6 +322,8 @@ struct Search {
     // look-ahead: the cache is the handle's; the queue and the threads are the process's (Threads)
     std::mutex qm;
     std::unordered_map<std::array<int64_t, 5>, std::shared_ptr<Entry>, KeyHash> cache;
+    std::shared_ptr<Entry> tail_job[2], tail_out[2];      // [0] small deletions, [1] pair filter: asked ahead / last collected (under qm)
+    int64_t stat_tail[4] = {0, 0, 0, 0};                  // jobs queued, served from a queued job, computed on demand, of the served: by the caller
     char err[256] = "";
     // CORAL_SEARCH_PROFILE=1: seconds per phase and work counters over all steps, printed when the handle is freed
     bool profile = false, profile_steps = false;
@@ -431,7 +462,8 @@ inline bool pairs_between(const Search &S, Scratch &T, std::vector<int64_t> &can
     return ok;
 }
 
-void run_calls(const Search &S, const int64_t *cand, int64_t n, Calls &c) {
+void run_calls_with(double min_cluster_cutoff, int64_t bp_distance_cutoff, int64_t match_cutoff, double accept_floor, int32_t advance,
+                    const int64_t *cand, int64_t n, Calls &c) {
     c = Calls();
     if (n == 0) return;
     const int64_t *ptr[13];
@@ -440,9 +472,13 @@ void run_calls(const Search &S, const int64_t *cand, int64_t n, Calls &c) {
     c.cluster_size.resize((size_t)n); c.flags.resize((size_t)n);
     c.head.resize((size_t)n); c.p1.resize((size_t)n); c.p2.resize((size_t)n);
     c.sup_off.resize((size_t)n + 1); c.sup_idx.resize((size_t)n); c.stats.resize(6 * (size_t)n);
-    coral_call_breakpoints(n, ptr, stride, S.min_cluster_cutoff, S.bp_distance_cutoff, S.match_cutoff, S.accept_floor, 0,
+    coral_call_breakpoints(n, ptr, stride, min_cluster_cutoff, bp_distance_cutoff, match_cutoff, accept_floor, advance,
                            &c.n_clusters, c.cluster_size.data(), &c.n_calls, c.head.data(), c.p1.data(), c.p2.data(), c.stats.data(),
                            c.flags.data(), c.sup_off.data(), c.sup_idx.data());
+}
+
+void run_calls(const Search &S, const int64_t *cand, int64_t n, Calls &c) {
+    run_calls_with(S.min_cluster_cutoff, S.bp_distance_cutoff, S.match_cutoff, S.accept_floor, 0, cand, n, c);
 }
 
 void compute_step(Search &S, Scratch &T, const int64_t key[5], StepResult &R) {
@@ -681,6 +717,8 @@ std::vector<int> cpus_of_my_node() {
     return out;
 }
 
+void compute_tail(const Search &S, Entry &e);
+
 void worker_main(Threads *G) {
     Scratch T;                                            // (serves every handle in turn: see Scratch)
     for (;;) {
@@ -703,7 +741,8 @@ void worker_main(Threads *G) {
         }
         if (mine) {
             e->t_start = now_s();
-            compute_step(*S, T, e->key, e->res);
+            if (e->kind == 0) compute_step(*S, T, e->key, e->res);
+            else compute_tail(*S, *e);
             e->t_end = now_s();
             {
                 std::lock_guard<std::mutex> lk(e->m);
@@ -1423,22 +1462,20 @@ extern "C" int coral_search_result(void *h, int64_t *n_meta, const int64_t **met
 
 // alignment2bp_l (bu:129-186) of every chimeric read, in table (= dict) order, against the interval list: both alignments of
 // a pair must have the SAME first overlapping interval (interval_overlap_l, bu:37-44) and either change strand or fail the
-// collinearity test.  Result: one group with all candidates (coral_search_result).
-extern "C" int coral_search_within(void *h, int32_t n_int, const int64_t *int_tid, const int64_t *int_start, const int64_t *int_end) {
-    if (!h || n_int < 0 || (n_int > 0 && (!int_tid || !int_start || !int_end))) return CORAL_ERR_ARG;
-    Search &S = *(Search *)h;
-    if (!S.attached) return not_attached(S, "search_within");
-    StepResult &R = S.main_result;
-    R.clear();
-    S.current = &R;
-    S.current_entry.reset();
+// collinearity test.  The candidates are appended to `cand`; false: one of them touches a contig outside chr1..22,X,Y,M.
+// Reads the handle only, so a look-ahead thread may run it (tail jobs) while the caller is elsewhere.
+namespace {
+bool within_compute(const Search &S, int32_t n_int, const int64_t *int_tid, int64_t stride, const int64_t *int_start,
+                    const int64_t *int_end, std::vector<int64_t> &cand) {
     std::vector<std::vector<int32_t>> by_tid((size_t)S.n_tid);             // interval indices per contig, list order kept
-    for (int32_t k = 0; k < n_int; ++k)
-        if (int_tid[k] >= 0 && int_tid[k] < S.n_tid) by_tid[(size_t)int_tid[k]].push_back(k);
+    for (int32_t k = 0; k < n_int; ++k) {
+        const int64_t t = int_tid[k * stride];
+        if (t >= 0 && t < S.n_tid) by_tid[(size_t)t].push_back(k);
+    }
     auto first_interval = [&](const PackedRow &w) -> int32_t {
         if (w.tid < 0 || w.tid >= S.n_tid) return -1;
         for (int32_t k : by_tid[(size_t)w.tid])
-            if (w.ra <= int_end[k] && int_start[k] <= w.rb) return k;
+            if (w.ra <= int_end[k * stride] && int_start[k * stride] <= w.rb) return k;
         return -1;
     };
     // reads in table (= dict) order; big tables are cut into consecutive ranges of reads filtered on the handle's task pool, each
@@ -1476,7 +1513,7 @@ extern "C" int coral_search_within(void *h, int32_t n_int, const int64_t *int_ti
     TaskPool *const pool = helper_pool(S);
     const int pieces = (pool && S.n_reads >= 4 * S.par_min_reads) ? 4 : 1;
     if (pieces == 1) {
-        contigs_ok = scan_reads(0, S.n_reads, R.cand);
+        contigs_ok = scan_reads(0, S.n_reads, cand);
     } else {
         std::vector<std::vector<int64_t>> part((size_t)pieces);
         std::vector<char> okv((size_t)pieces, 1);
@@ -1486,9 +1523,23 @@ extern "C" int coral_search_within(void *h, int32_t n_int, const int64_t *int_ti
         pool->run(tasks);
         for (int c = 0; c < pieces; ++c) {
             contigs_ok &= okv[(size_t)c] != 0;
-            R.cand.insert(R.cand.end(), part[(size_t)c].begin(), part[(size_t)c].end());
+            cand.insert(cand.end(), part[(size_t)c].begin(), part[(size_t)c].end());
         }
     }
+    return contigs_ok;
+}
+}  // namespace
+
+// Result: one group with all candidates (coral_search_result).
+extern "C" int coral_search_within(void *h, int32_t n_int, const int64_t *int_tid, const int64_t *int_start, const int64_t *int_end) {
+    if (!h || n_int < 0 || (n_int > 0 && (!int_tid || !int_start || !int_end))) return CORAL_ERR_ARG;
+    Search &S = *(Search *)h;
+    if (!S.attached) return not_attached(S, "search_within");
+    StepResult &R = S.main_result;
+    R.clear();
+    S.current = &R;
+    S.current_entry.reset();
+    const bool contigs_ok = within_compute(S, n_int, int_tid, 1, int_start, int_end, R.cand);
     const int64_t g[4] = {-1, -1, -1, (int64_t)(R.cand.size() / 13)};
     R.groups.insert(R.groups.end(), g, g + 4);
     R.order_off.push_back(0);
@@ -1604,4 +1655,289 @@ extern "C" int coral_search_bfs_get(void *h, int32_t which, const void **ptr, in
         case 11: return give(O.events);
         default: return CORAL_ERR_ARG;
     }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Behind the search: the candidates of find_smalldel_breakpoints (ibg:721-802) and of find_breakpoints (ibg:676-718) with their
+// breakpoint calls.  Both are pure functions of the merged interval list and of arrays that exist the moment the search
+// returns, so a build asks for them then (coral_search_tail_prefetch) and the look-ahead threads compute them while the
+// caller turns the search's result into its containers; addbp and the connection updates stay with the caller.
+// ---------------------------------------------------------------------------------------------
+namespace {
+// Large deletions inside single records (ibg:721-802) from the gap rows of coral_cigar_scan, int64 [n_gap][6] = record, op
+// index, previous block end, next block start, first block start, last block end, sorted by (record, op index):
+//   selection (ibg:750-766, Appendix A Q11): interval by interval in list order, the rows in their own order inside an interval,
+//     a record overlaps by the htslib rule  pos < e + 1 and end > s;  a record in two intervals is taken twice.  Nothing is
+//     assumed about the intervals (unsorted, overlapping, empty ones are all fine);
+//   grouping (ibg:746-762): by read-name id in order of first appearance among the selected rows (the reference's dict), stable
+//     inside a group; a row's index in its group is the candidate's i = j (ibg:772);
+//   candidates: c1 = c2 = contig, p1 = next block start, p2 = min(previous block end, next block start) (the aliasing swap,
+//     Appendix A Q7), o1 = '-', o2 = '+', gap = swapped = 0, mapq a = b = -1;
+//   then coral_call_breakpoints with the sub-cluster counter advancing (ibg:777-802).
+void smalldel_compute(const TailArgs &A, int32_t n_int, const int64_t *iv, double min_cluster_cutoff, int64_t bp_distance_cutoff,
+                      int64_t match_cutoff, double accept_floor, TailResult &R) {
+    auto fail = [&](const char *msg) { R.rc = CORAL_ERR_ARG; snprintf(R.err, sizeof(R.err), "smalldel: %s", msg); };
+    R.bounds.assign(1, 0);
+    if (A.n_gap < 0 || A.n_rec < 0 || n_int < 0 || (A.n_gap > 0 && (!A.gaps || !A.h_tid || !A.h_pos || !A.h_end || !A.h_name || !A.h_mapq)) ||
+        (n_int > 0 && !iv))
+        return fail("bad argument");
+    for (int64_t k = 0; k < A.n_gap; ++k)
+        if (A.gaps[6 * k] < 0 || A.gaps[6 * k] >= A.n_rec) return fail("record ordinal out of range");
+    // (the records of the rows lie anywhere among millions: their three columns are gathered once, next to each other, and every
+    // interval then passes over that)
+    const double t0 = now_s();
+    struct Span { int32_t tid, pos, end, name, mapq; };
+    std::vector<Span> span((size_t)A.n_gap);
+    for (int64_t k = 0; k < A.n_gap; ++k) {
+        const int64_t rec = A.gaps[6 * k];
+        span[(size_t)k] = Span{A.h_tid[rec], A.h_pos[rec], A.h_end[rec], A.h_name[rec], A.h_mapq[rec]};
+    }
+    std::vector<int64_t> sel;
+    for (int32_t q = 0; q < n_int; ++q) {
+        const int64_t t = iv[3 * q], s = iv[3 * q + 1], e = iv[3 * q + 2];
+        for (int64_t k = 0; k < A.n_gap; ++k) {
+            const Span &w = span[(size_t)k];
+            if (w.tid == t && w.pos < e + 1 && w.end > s) sel.push_back(k);
+        }
+    }
+    const size_t n = sel.size();
+    R.t_phase[0] = now_s() - t0;
+    if (n == 0) return;
+    if (n >= ((size_t)1 << 30)) return fail("too many selected rows");
+    // name id -> group, groups numbered by first appearance: an open-addressing table of at least twice the rows
+    size_t cap = 64;
+    while (cap < 2 * n) cap <<= 1;
+    std::vector<int32_t> slot_name(cap), slot_grp(cap, -1);
+    std::vector<int32_t> grp(n);
+    for (size_t q = 0; q < n; ++q) {
+        const int32_t name = span[(size_t)sel[q]].name;
+        size_t at = ((uint64_t)(uint32_t)name * 0x9E3779B97F4A7C15ull >> 32) & (cap - 1);
+        while (slot_grp[at] >= 0 && slot_name[at] != name) at = (at + 1) & (cap - 1);
+        if (slot_grp[at] < 0) {
+            slot_name[at] = name;
+            slot_grp[at] = (int32_t)R.grp_name.size();
+            R.grp_name.push_back(name);
+        }
+        grp[q] = slot_grp[at];
+    }
+    const size_t n_grp = R.grp_name.size();
+    R.bounds.assign(n_grp + 1, 0);
+    for (size_t q = 0; q < n; ++q) ++R.bounds[(size_t)grp[q] + 1];
+    for (size_t g = 0; g < n_grp; ++g) R.bounds[g + 1] += R.bounds[g];
+    std::vector<int64_t> at(R.bounds.begin(), R.bounds.end() - 1);
+    R.cand.resize(13 * n);
+    R.rows.resize(6 * n);
+    for (size_t q = 0; q < n; ++q) {                                        // (a counting sort by group: stable)
+        const int64_t *g = A.gaps + 6 * sel[q];
+        const Span &sp = span[(size_t)sel[q]];
+        const int64_t prv = g[2], nxt = g[3], tid = sp.tid;
+        const size_t w = (size_t)at[(size_t)grp[q]]++;
+        const int64_t k_in = (int64_t)w - R.bounds[(size_t)grp[q]];
+        const int64_t c[13] = {tid, nxt, 1, tid, prv < nxt ? prv : nxt, 0, sp.name, k_in, k_in, 0, 0, -1, -1};
+        memcpy(R.cand.data() + 13 * w, c, sizeof(c));
+        const int64_t row[6] = {tid, nxt, prv, g[4], g[5], sp.mapq};
+        memcpy(R.rows.data() + 6 * w, row, sizeof(row));
+    }
+    R.t_phase[1] = now_s() - t0 - R.t_phase[0];
+    run_calls_with(min_cluster_cutoff, bp_distance_cutoff, match_cutoff, accept_floor, 1, R.cand.data(), (int64_t)n, R.calls);
+    R.t_phase[2] = now_s() - t0 - R.t_phase[0] - R.t_phase[1];
+}
+
+void compute_tail(const Search &S, Entry &e) {
+    TailResult &R = e.tail;
+    const int32_t n_int = (int32_t)(e.tail_iv.size() / 3);
+    const int64_t *iv = e.tail_iv.data();
+    if (e.kind == 1) {
+        smalldel_compute(e.tail_args, n_int, iv, S.min_cluster_cutoff, S.bp_distance_cutoff, S.match_cutoff, S.accept_floor, R);
+        return;
+    }
+    const double t0 = now_s();
+    const bool contigs_ok = within_compute(S, n_int, iv, 3, iv + 1, iv + 2, R.cand);
+    R.t_phase[0] = now_s() - t0;
+    if (!contigs_ok) {
+        R.rc = CORAL_ERR_FORMAT;
+        snprintf(R.err, sizeof(R.err), "search_within: contig outside chr1..22,X,Y,M");
+        return;
+    }
+    run_calls_with(S.min_cluster_cutoff, S.bp_distance_cutoff, S.match_cutoff, S.accept_floor, 1, R.cand.data(), (int64_t)(R.cand.size() / 13),
+                   R.calls);
+    R.t_phase[2] = now_s() - t0 - R.t_phase[0];
+}
+
+// a queued job nobody will ask for any more: a worker that meets it skips it
+void retire(const std::shared_ptr<Entry> &e) {
+    if (!e) return;
+    std::lock_guard<std::mutex> lk(e->m);
+    e->taken = true;
+}
+}  // namespace
+
+// The small-deletion pass on its own, synchronously, with no handle and no thread.  Returns a result to be read with
+// coral_tail_result_* and freed with coral_tail_result_free (null: out of memory).
+extern "C" void *coral_smalldel_pass(int64_t n_gap, const int64_t *gaps, int64_t n_rec, const int32_t *h_tid, const int32_t *h_pos,
+                                     const int32_t *h_end, const int32_t *h_name_id, const int32_t *h_mapq, int32_t n_int, const int64_t *iv,
+                                     double min_cluster_cutoff, int64_t bp_distance_cutoff, int64_t match_cutoff, double accept_floor) {
+    TailResult *R = new (std::nothrow) TailResult();
+    if (!R) return nullptr;
+    TailArgs A;
+    A.n_gap = n_gap; A.n_rec = n_rec; A.gaps = gaps;
+    A.h_tid = h_tid; A.h_pos = h_pos; A.h_end = h_end; A.h_name = h_name_id; A.h_mapq = h_mapq;
+    if (bp_distance_cutoff <= 0) { R->rc = CORAL_ERR_ARG; snprintf(R->err, sizeof(R->err), "smalldel: bad cluster distance"); R->bounds.assign(1, 0); }
+    else smalldel_compute(A, n_int, iv, min_cluster_cutoff, bp_distance_cutoff, match_cutoff, accept_floor, *R);
+    return R;
+}
+
+extern "C" void coral_tail_result_free(void *result) { delete (TailResult *)result; }
+extern "C" int coral_tail_result_rc(const void *result) { return result ? ((const TailResult *)result)->rc : CORAL_ERR_ARG; }
+extern "C" const char *coral_tail_result_error(const void *result) { return result ? ((const TailResult *)result)->err : "null result"; }
+
+// Arrays of a tail result (owned by it); which =
+//   0 candidates int64[n][13]   1 cluster sizes int32[]   2 / 3 / 4 per call: head candidate, p1, p2 int64[]   5 statistics double[n][6]
+//   6 flags int32[]   7 support offsets int64[calls + 1]   8 support indices int64[]   (1 - 8 as coral_call_breakpoints)
+//   9 small deletions: name id per group int64[G]   10 group bounds int64[G + 1]   11 rows int64[n][6] = contig, next block start,
+//     previous block end, first block start, last block end, mapq (ibg:746-762), grouped like the candidates
+extern "C" int coral_tail_result_get(const void *result, int32_t which, const void **ptr, int64_t *n) {
+    if (!result || !ptr || !n) return CORAL_ERR_ARG;
+    const TailResult &R = *(const TailResult *)result;
+    const Calls &c = R.calls;
+    auto give = [&](const auto &v, size_t len) { *ptr = v.data(); *n = (int64_t)len; return CORAL_OK; };
+    const size_t nc = (size_t)c.n_calls;
+    switch (which) {
+        case 0: return give(R.cand, R.cand.size());
+        case 1: return give(c.cluster_size, (size_t)c.n_clusters);
+        case 2: return give(c.head, nc);
+        case 3: return give(c.p1, nc);
+        case 4: return give(c.p2, nc);
+        case 5: return give(c.stats, 6 * nc);
+        case 6: return give(c.flags, nc);
+        case 7: return give(c.sup_off, c.sup_off.empty() ? 0 : nc + 1);
+        case 8: return give(c.sup_idx, (c.sup_off.empty() || nc == 0) ? 0 : (size_t)c.sup_off[nc]);
+        case 9: return give(R.grp_name, R.grp_name.size());
+        case 10: return give(R.bounds, R.bounds.size());
+        case 11: return give(R.rows, R.rows.size());
+        default: return CORAL_ERR_ARG;
+    }
+}
+
+// Ask for both tail jobs of the interval list iv int64[n_int][3] = contig id, start, end (copied); the other arrays are borrowed
+// until the jobs have been collected or the handle freed.  Returns at once; a handle without look-ahead threads does nothing
+// (its collectors compute on demand).  A job asked for earlier and never collected is retired.
+extern "C" int coral_search_tail_prefetch(void *h, int32_t n_int, const int64_t *iv, int64_t n_gap, const int64_t *gaps, int64_t n_rec,
+                                          const int32_t *h_tid, const int32_t *h_pos, const int32_t *h_end, const int32_t *h_name_id,
+                                          const int32_t *h_mapq) {
+    if (!h || n_int < 0 || (n_int > 0 && !iv) || n_gap < 0 || n_rec < 0) return CORAL_ERR_ARG;
+    Search &S = *(Search *)h;
+    if (!S.attached) return not_attached(S, "search_tail_prefetch");
+    if (S.n_threads == 0) return CORAL_OK;
+    std::shared_ptr<Entry> ent[2];
+    for (int w = 0; w < 2; ++w) {
+        ent[w] = std::make_shared<Entry>();
+        ent[w]->kind = 1 + w;
+        ent[w]->owner = &S;
+        ent[w]->tail_iv.assign(iv, iv + 3 * (size_t)n_int);
+        ent[w]->t_queued = now_s();
+    }
+    TailArgs &A = ent[0]->tail_args;
+    A.n_gap = n_gap; A.n_rec = n_rec; A.gaps = gaps;
+    A.h_tid = h_tid; A.h_pos = h_pos; A.h_end = h_end; A.h_name = h_name_id; A.h_mapq = h_mapq;
+    {
+        std::lock_guard<std::mutex> lk(S.qm);
+        for (int w = 0; w < 2; ++w) {
+            retire(S.tail_job[w]);
+            S.tail_job[w] = ent[w];
+            ++S.stat_tail[0];
+        }
+    }
+    Threads &G = threads();
+    G.ensure(S.n_threads, S.n_helpers);
+    {
+        std::lock_guard<std::mutex> lk(G.m);
+        G.queue.push_back(ent[1]);                       // (the pair filter first: the longer of the two)
+        G.queue.push_back(ent[0]);
+    }
+    G.cv.notify_all();
+    return CORAL_OK;
+}
+
+// Collect a tail job: which = 0 the small-deletion pass, 1 the pair filter of find_breakpoints.  When the arguments are those
+// of a job asked for ahead (the interval list value for value; for 0 also the same arrays) that job is waited for — or
+// computed here if no thread has begun it; with any other arguments, or without a job, the result is computed here and now.
+// *result (coral_tail_result_*) belongs to the handle until the next collect of the same kind or coral_search_free.
+extern "C" int coral_search_tail_collect(void *h, int32_t which, int32_t n_int, const int64_t *iv, int64_t n_gap, const int64_t *gaps,
+                                         int64_t n_rec, const int32_t *h_tid, const int32_t *h_pos, const int32_t *h_end,
+                                         const int32_t *h_name_id, const int32_t *h_mapq, const void **result) {
+    if (!h || !result || which < 0 || which > 1 || n_int < 0 || (n_int > 0 && !iv)) return CORAL_ERR_ARG;
+    Search &S = *(Search *)h;
+    if (!S.attached) return not_attached(S, "search_tail_collect");
+    TailArgs A;
+    if (which == 0) {
+        A.n_gap = n_gap; A.n_rec = n_rec; A.gaps = gaps;
+        A.h_tid = h_tid; A.h_pos = h_pos; A.h_end = h_end; A.h_name = h_name_id; A.h_mapq = h_mapq;
+    }
+    std::shared_ptr<Entry> ent;
+    {
+        std::lock_guard<std::mutex> lk(S.qm);
+        std::shared_ptr<Entry> &job = S.tail_job[which];
+        if (job && job->tail_iv.size() == 3 * (size_t)n_int && std::equal(job->tail_iv.begin(), job->tail_iv.end(), iv) &&
+            (which == 1 || job->tail_args == A))
+            ent = std::move(job);
+        else
+            retire(job);                                 // (asked for with other arguments: nobody will collect it)
+        job.reset();
+        S.tail_out[which].reset();
+    }
+    const bool served = (bool)ent;
+    bool mine = true;
+    if (served) {
+        std::lock_guard<std::mutex> lk(ent->m);
+        mine = !ent->taken;                              // still queued: do it here, the worker will skip it
+        ent->taken = true;
+    } else {
+        ent = std::make_shared<Entry>();
+        ent->kind = 1 + which;
+        ent->owner = &S;
+        ent->tail_iv.assign(iv, iv + 3 * (size_t)n_int);
+        ent->tail_args = A;
+        ent->taken = true;
+    }
+    {
+        std::lock_guard<std::mutex> lk(S.qm);
+        ++S.stat_tail[served ? 1 : 2];
+        if (served && mine) ++S.stat_tail[3];
+    }
+    const double t_ask = now_s();
+    if (mine) {
+        ent->who = 0;
+        ent->t_start = t_ask;
+        compute_tail(S, *ent);
+        ent->t_end = now_s();
+        std::lock_guard<std::mutex> lk(ent->m);
+        ent->done = true;
+    } else {
+        std::unique_lock<std::mutex> lk(ent->m);
+        ent->cv.wait(lk, [&] { return ent->done; });
+    }
+    if (S.profile_steps)
+        fprintf(stderr, "  tail %s: %s, %d intervals, %lld gap rows -> %zu candidates, %d calls; began %.2f ms after it was queued, compute %.2f ms (%s), "
+                "asked -> ready %.2f ms; selection %.2f grouping %.2f calls %.2f ms\n", which == 0 ? "small deletions" : "within", served ? "asked for ahead" : "on demand", (int)n_int,
+                (long long)ent->tail_args.n_gap, ent->tail.cand.size() / 13, (int)ent->tail.calls.n_calls,
+                served ? (ent->t_start - ent->t_queued) * 1e3 : 0.0, (ent->t_end - ent->t_start) * 1e3, ent->who == 0 ? "caller" : "worker",
+                (now_s() - t_ask) * 1e3, ent->tail.t_phase[0] * 1e3, ent->tail.t_phase[1] * 1e3, ent->tail.t_phase[2] * 1e3);
+    {
+        std::lock_guard<std::mutex> lk(S.qm);
+        S.tail_out[which] = ent;
+    }
+    *result = &ent->tail;
+    if (ent->tail.rc != CORAL_OK) snprintf(S.err, sizeof(S.err), "%s", ent->tail.err);
+    return ent->tail.rc;
+}
+
+// out int64[4] = tail jobs queued, collects served by a queued job, collects computed on demand (no job, or other arguments),
+// and of the served ones those the caller computed itself because no thread had begun them.
+extern "C" int coral_search_tail_stats(void *h, int64_t *out) {
+    if (!h || !out) return CORAL_ERR_ARG;
+    Search &S = *(Search *)h;
+    std::lock_guard<std::mutex> lk(S.qm);
+    for (int k = 0; k < 4; ++k) out[k] = S.stat_tail[k];
+    return CORAL_OK;
 }

@@ -84,6 +84,35 @@ def interval_exclusive(a, lst):
     return hit, parts
 
 
+def _merge_plan(ivs):
+    """How ibg:236-319 merges ``ivs`` ([chr, start, end, ...]): (order, srt, runs) — the indices sorted by (chromosome rank,
+    start), the intervals in that order and the (first, last) positions in ``srt`` of every run of two or more neighbours
+    that are adjacent or overlapping.  Nothing is modified."""
+    order = sorted(range(len(ivs)), key=lambda i: (chr_idx[ivs[i][0]], ivs[i][1]))
+    srt = [ivs[i] for i in order]
+    runs, first = [], 0
+    for k in range(len(srt) - 1):
+        if not (interval_adjacent(srt[k + 1], srt[k]) or interval_overlap(srt[k], srt[k + 1])):
+            if k > first:
+                runs.append((first, k))
+            first = k + 1
+    if srt and first < len(srt) - 1:
+        runs.append((first, len(srt) - 1))
+    return order, srt, runs
+
+
+def merged_coordinates(ivs) -> list:
+    """[(chr, start, end)] of the list _merge_intervals will leave, in its order — a function of the intervals' coordinates
+    alone (connections and component labels do not enter): a run keeps its first interval's start (a Q2 bool start included) and
+    takes the end of its LAST interval, as the reference does, not the largest end."""
+    _, srt, runs = _merge_plan(ivs)
+    end_of, gone = {}, set()
+    for a, b in runs:
+        end_of[a] = srt[b][2]
+        gone.update(range(a + 1, b + 1))
+    return [(iv[0], iv[1], end_of.get(k, iv[2])) for k, iv in enumerate(srt) if k not in gone]
+
+
 def rows_by_interval(r_tid, r_pos, r_end, intervals) -> np.ndarray:
     """Indices of the records (contig, pos, end) overlapping each interval (tid, start, end inclusive) by the htslib rule
     ``pos < e + 1 and end > s`` — interval by interval in list order, records in their own order within an interval, a record
@@ -233,6 +262,7 @@ class bam_to_breakpoint_nanopore():
         self.ccid2id = dict()
         self.new_bp_list = []
         self._search_ctx: Optional[PairSearch] = None      # native side of the interval search (coral_search_*)
+        self._tail: Optional[PairSearch] = None            # ... when its tail jobs are this build's to collect (_issue_tail)
         self._cn_col, self._seg_tab = {}, None             # read_cns: the CN column per chromosome, the search's segment tables
         self.new_bp_stats = []
         self.new_bp_ccids = []
@@ -631,9 +661,16 @@ class bam_to_breakpoint_nanopore():
         seeds = [[self._tid_of[iv[0]], int(iv[1]), int(iv[2]), int(iv[3])] for iv in self.amplicon_intervals]
         log = logging.getLogger()
         level = 2 if log.isEnabledFor(logging.DEBUG) else 1 if log.isEnabledFor(logging.WARNING) else 0
-        R = S.bfs(seeds, seg_cn, seg_ix, self.rec.chr_rank, has, self.cn_gain, self.interval_delta, level)
-        iv = R[0].reshape(-1, 5).tolist()
-        self.amplicon_intervals = [[chroms[t], bool(s) if isb else s, e, cc] for t, s, e, cc, isb in iv]
+        def intervals_known(rows):
+            iv = rows.reshape(-1, 5).tolist()
+            self.amplicon_intervals = [[chroms[t], bool(s) if isb else s, e, cc] for t, s, e, cc, isb in iv]
+            self._issue_tail(S)
+        self._tail = None
+        self._start_gap_fetch()
+        try:
+            R = S.bfs(seeds, seg_cn, seg_ix, self.rec.chr_rank, has, self.cn_gain, self.interval_delta, level, on_intervals=intervals_known)
+        finally:
+            self._join_gap_fetch()
         names = self.rec.names
         bp, meta, stats = R[1].reshape(-1, 11), R[2].reshape(-1, 4).tolist(), R[3].reshape(-1, 6)
         chunks, c_read, c_i, c_j = R[4].reshape(-1, 2).tolist(), R[5], R[6], R[7]
@@ -672,19 +709,59 @@ class bam_to_breakpoint_nanopore():
                 elif ty == 4:
                     logging.debug(_t() + "\t\tAdded new interval %s to the amplicon interval list." % [chroms[a], bool(b) if d else b, c, -1])
 
+    def _tail_wanted(self) -> bool:
+        return os.environ.get("CORAL_TAIL_PREFETCH", "1") != "0" and getattr(self.rec, "world", 1) == 1
+
+    def _start_gap_fetch(self):
+        """The scan's gap rows are brought to the host — the wait for their staged copy, the widening to int64, the sort by
+        (record, op index): ScanResult.gaps — on a thread of their own while coral_search_bfs runs (the native call holds no
+        interpreter lock), so the tail prefetch finds them there.  Only for a scan that was launched already; an error is
+        met again, and raised, by whoever asks for the rows next."""
+        sc = self._scan
+        if not self._tail_wanted() or sc is None or getattr(sc, "_gaps", None) is not None:
+            return
+        import threading
+
+        def fetch():
+            try:
+                sc.gaps
+            except Exception:                         # noqa: BLE001 — see above
+                pass
+        self._gap_job = threading.Thread(target=fetch, name="coral-gap-rows")
+        self._gap_job.start()
+
+    def _join_gap_fetch(self):
+        job, self._gap_job = getattr(self, "_gap_job", None), None
+        if job is not None:
+            job.join()
+
+    def _tail_inputs(self):
+        """(gap rows, record columns) of the small-deletion pass; the scan's staged copy of the rows is waited for here."""
+        self._join_gap_fetch()
+        dr = self.rec
+        return self.scan().gaps, (dr.h_tid, dr.h_pos, dr.h_end, dr.h_name_id, dr.h_mapq)
+
+    def _issue_tail(self, S: PairSearch):
+        """The moment the search's intervals are known: the candidates of find_smalldel_breakpoints and find_breakpoints with
+        their breakpoint calls are pure functions of the MERGED interval coordinates (merged_coordinates: no connection, no
+        label enters), the scan's gap rows, the record columns and the tables the search handle holds — so they are asked for
+        now (coral_search_tail_prefetch) and computed on the search's idle threads while this thread builds new_bp_list, the
+        connections and runs _merge_intervals.  Whatever the two phases later ask for is keyed by their own interval list: a
+        list other than the one predicted here is simply computed then.  CORAL_TAIL_PREFETCH=0, several ranks and the
+        step-by-step search keep the numpy path."""
+        if not self._tail_wanted():
+            return
+        self._tail = S
+        try:
+            ivs = [(self._tid_of[c], int(s), int(e)) for c, s, e in merged_coordinates(self.amplicon_intervals)]
+        except KeyError:                                  # a contig outside chr1..22,X,Y,M: _merge_intervals raises it
+            return
+        gaps, cols = self._tail_inputs()
+        S.tail_prefetch(ivs, gaps, cols)
+
     def _merge_intervals(self):
         """Sort, merge adjacent / overlapping intervals, remap connections, relabel components (ibg:236-319)."""
-        ivs = self.amplicon_intervals
-        order = sorted(range(len(ivs)), key=lambda i: (chr_idx[ivs[i][0]], ivs[i][1]))
-        srt = [ivs[i] for i in order]
-        runs, first = [], 0
-        for k in range(len(srt) - 1):
-            if not (interval_adjacent(srt[k + 1], srt[k]) or interval_overlap(srt[k], srt[k + 1])):
-                if k > first:
-                    runs.append((first, k))
-                first = k + 1
-        if srt and first < len(srt) - 1:
-            runs.append((first, len(srt) - 1))
+        order, srt, runs = _merge_plan(self.amplicon_intervals)
         conn = self.amplicon_interval_connections
         for a, b in reversed(runs):
             srt[a][2] = srt[b][2]
@@ -1077,9 +1154,15 @@ class bam_to_breakpoint_nanopore():
                         queue.append(nai)
                         self._prefetch_step(nai)
 
-    def _add_clustered(self, cands: Candidates):
-        """Tail shared by find_breakpoints and find_smalldel_breakpoints (ibg:691-718, ibg:775-802)."""
-        for bp, support, st in self._call_breakpoints(cands, advance_subcluster=True):
+    def _tail_search(self) -> Optional[PairSearch]:
+        """The search handle whose tail jobs this build may collect (_issue_tail), or None: the numpy / synchronous path."""
+        S = getattr(self, "_tail", None)
+        return S if S is not None and S is self._search_ctx and S._h else None
+
+    def _add_clustered(self, cands: Candidates, called=None):
+        """Tail shared by find_breakpoints and find_smalldel_breakpoints (ibg:691-718, ibg:775-802).  ``called``: the
+        candidates' breakpoint calls when they were computed ahead."""
+        for bp, support, st in self._call_breakpoints(cands, advance_subcluster=True, called=called):
             io1 = interval_overlap_l([bp[0], bp[1], bp[1]], self.amplicon_intervals)
             io2 = interval_overlap_l([bp[3], bp[4], bp[4]], self.amplicon_intervals)
             if io1 >= 0 and io2 >= 0:
@@ -1091,6 +1174,16 @@ class bam_to_breakpoint_nanopore():
     def find_smalldel_breakpoints(self):
         """Large deletions inside single alignment records (ibg:721-802), from the gap rows of coral_cigar_scan."""
         dr = self.rec
+        S = self._tail_search()
+        if S is not None:
+            # one native pass (coral_smalldel_pass), usually computed already on a look-ahead thread of the search
+            ivs = [(self._tid_of[iv[0]], int(iv[1]), int(iv[2])) for iv in self.amplicon_intervals]
+            res = S.tail_smalldel(ivs, *self._tail_inputs())
+            if "groups" in res:
+                self.large_indel_alignments = _LazyIndelAlignments(self, *res["groups"])
+            logging.info(_t() + "Fetched %d reads with large indels in CIGAR." % (len(self.large_indel_alignments)))
+            self._add_clustered(res["cands"], res["called"])
+            return
         sc = self.scan()
         g = sc.gaps
         parts = []
@@ -1130,8 +1223,13 @@ class bam_to_breakpoint_nanopore():
     # ---- A7 ----------------------------------------------------------------------------------
     def find_breakpoints(self):
         """Breakpoints from chimeric alignments inside the amplicon intervals (ibg:676-718)."""
-        T = self._chim
         ivs = [(self._tid_of[iv[0]], iv[1], iv[2]) for iv in self.amplicon_intervals]
+        S = self._tail_search()
+        if S is not None:
+            res = S.tail_within(ivs)                      # the same filter + its calls, asked for when the search returned
+            logging.debug(_t() + "Found %d reads with new breakpoints." % (len(res["cands"])))
+            self._add_clustered(res["cands"], res["called"])
+            return
         cands = self._search().within(ivs)              # alignment2bp_l as a filter over the pair table (cutoffs 100 / 20 / 100 / 10)
         logging.debug(_t() + "Found %d reads with new breakpoints." % (len(cands)))
         self._add_clustered(cands)

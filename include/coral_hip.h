@@ -317,6 +317,53 @@ int coral_search_bfs(void *handle, int32_t n_seed, const int64_t *iv, const doub
 int coral_search_bfs_get(void *handle, int32_t which, const void **ptr, int64_t *n);
 
 /* ------------------------------------------------------------------------------------------------
+ * The candidates behind the search — HOST functions (no device work, no HIP call on any thread).
+ *
+ * coral_smalldel_pass: find_smalldel_breakpoints up to its breakpoint calls
+ * (infer_breakpoint_graph.py:721-802 of the reference) in one pass.  gaps int64[n_gap][6] = record ordinal, op index,
+ * previous block end, next block start, first block start, last block end of the record, sorted by (record, op index) — the
+ * gap rows of coral_cigar_scan; h_tid / h_pos / h_end / h_name_id / h_mapq int32[n_rec] the record columns; iv
+ * int64[n_int][3] = contig id, start, end (inclusive) in list order, NOT assumed sorted or disjoint.
+ *   Selection (ibg:750-766): interval by interval in list order, rows in their own order inside an interval; a record
+ *   overlaps when pos < e + 1 and end > s; a record inside two intervals is taken twice (Appendix A Q11).
+ *   Grouping (ibg:746-762): by read-name id in order of first appearance among the selected rows, stable inside a group;
+ *   k_in = the row's index in its group.
+ *   Candidates (ibg:772): c1 = c2 = contig, p1 = next block start, p2 = min(previous block end, next block start) (the
+ *   aliasing swap, Q7), o1 = 1, o2 = 0, read = name id, i = j = k_in, gap = swapped = 0, mapq a = mapq b = -1;
+ *   then coral_call_breakpoints with advance_subcluster = 1 and the given cutoffs and floor (ibg:777-802).
+ * Synchronous, needs no handle and starts no thread.  The result is read with coral_tail_result_get (which = 0 candidates
+ * int64[n][13]; 1 cluster sizes int32; 2 / 3 / 4 head, p1, p2 per call; 5 statistics double[calls][6]; 6 flags int32; 7 / 8
+ * support offsets and indices — 1..8 as coral_call_breakpoints; 9 name id per group; 10 group bounds int64[G + 1]; 11 rows
+ * int64[n][6] = contig, next block start, previous block end, first block start, last block end, mapq in the candidates'
+ * order — what large_indel_alignments holds), coral_tail_result_rc / _error, and freed with coral_tail_result_free.
+ *
+ * coral_search_tail_prefetch(handle, intervals, gap rows + record columns): returns at once; queues on the process's
+ * look-ahead threads (a) the pass above with the handle's parameters and (b) coral_search_within of the same intervals
+ * followed by coral_call_breakpoints with advance_subcluster = 1 (find_breakpoints, ibg:676-718).  The interval list is
+ * copied and is the jobs' key; the other arrays are borrowed until the jobs were collected or the handle freed.
+ * coral_search_tail_collect(which = 0 small deletions, 1 within): with arguments equal to the key of a queued job (and, for
+ * 0, the same arrays) it waits for that job, or computes it itself if no thread has begun it; with any other arguments, or
+ * with no job, it computes here and now — results never depend on the prefetch.  *result belongs to the handle until the
+ * next collect of the same kind.  A handle without threads queues nothing and computes on demand.  coral_search_free drops
+ * queued tail jobs and waits for those in flight, as for steps.  coral_search_tail_stats: out int64[4] = jobs queued,
+ * collects served by a queued job, collects computed on demand, served ones the caller computed itself.
+ * ------------------------------------------------------------------------------------------------ */
+void *coral_smalldel_pass(int64_t n_gap, const int64_t *gaps, int64_t n_rec, const int32_t *h_tid, const int32_t *h_pos,
+                          const int32_t *h_end, const int32_t *h_name_id, const int32_t *h_mapq, int32_t n_int, const int64_t *iv,
+                          double min_cluster_cutoff, int64_t bp_distance_cutoff, int64_t match_cutoff, double accept_floor);
+void coral_tail_result_free(void *result);
+int coral_tail_result_rc(const void *result);
+const char *coral_tail_result_error(const void *result);
+int coral_tail_result_get(const void *result, int32_t which, const void **ptr, int64_t *n);
+int coral_search_tail_prefetch(void *handle, int32_t n_int, const int64_t *iv, int64_t n_gap, const int64_t *gaps, int64_t n_rec,
+                               const int32_t *h_tid, const int32_t *h_pos, const int32_t *h_end, const int32_t *h_name_id,
+                               const int32_t *h_mapq);
+int coral_search_tail_collect(void *handle, int32_t which, int32_t n_int, const int64_t *iv, int64_t n_gap, const int64_t *gaps,
+                              int64_t n_rec, const int32_t *h_tid, const int32_t *h_pos, const int32_t *h_end,
+                              const int32_t *h_name_id, const int32_t *h_mapq, const void **result);
+int coral_search_tail_stats(void *handle, int64_t *out);
+
+/* ------------------------------------------------------------------------------------------------
  * coral_read_counter — copy a device counter to the host (synchronises `stream`).
  * ------------------------------------------------------------------------------------------------ */
 int coral_read_counter(const uint32_t *dev_counter, uint32_t *host_value, void *stream);

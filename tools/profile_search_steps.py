@@ -44,6 +44,12 @@ for nm in ("_find_intervals_native", "_merge_intervals", "_search", "_attach_ear
     timed(B, nm)
 timed(chimeric.PairSearch, "bfs", "PairSearch.bfs (native call + copies)")
 timed(chimeric.PairSearch, "within", "PairSearch.within")
+# the candidates behind the search (coral_search_tail_*): issuing the two jobs, then collecting each
+timed(B, "_issue_tail", "tail: issue (gap rows + prefetch)")
+timed(chimeric.PairSearch, "tail_smalldel", "tail: collect small deletions")
+timed(chimeric.PairSearch, "tail_within", "tail: collect within")
+for nm in ("find_smalldel_breakpoints", "find_breakpoints"):
+    timed(B, nm)
 for nm in ("segment_coverage", "point_cover", "_coverage_local", "_points_local", "hash_rows", "sa_table"):
     timed(kernels, nm, "kernels." + nm)
 timed(ibg, "call_breakpoints", "call_breakpoints")
