@@ -137,6 +137,9 @@ def build_parser():
     sp.add_argument("--level", help="Compression level of the BAM file, 0..9.", type=int, default=1)
     sp.add_argument("--index", help="If specified, also write the BAI index (<output>.bai).", action='store_true')
     sp.add_argument("--gpu_compress", help="Deflate the BAM file's BGZF blocks on the GPU (--device; cuda:0 with --device cpu) instead of on the host; --level must be 1.", action='store_true')
+    sp.add_argument("--stream", help="Spill each batch's sorted run to disk and merge the runs on the GPU (--device; cuda:0 with --device cpu): "
+                    "bounded host memory, for a file of any size; implies --gpu_compress and --level 1.", action='store_true')
+    sp.add_argument("--tmp_dir", help="With --stream: directory of the spill file <output's name>.runs.tmp (default: the output's directory).")
     sp.add_argument("--output", help="Name of the sorted BAM file.", required=True)
     sp.add_argument("--device", help="GPU to use ('cpu': the host pipeline).", default="cuda:0")
     for p in (rp, hp, qp, pp, dp, fp, vp, sp):
@@ -304,6 +307,15 @@ def sort_mode(args):
     """The records in coordinate order as a BAM file (bam.sort_bam): `samtools view -bq ... | samtools sort | samtools index`,
     with the --filter_* arguments as the view's tests."""
     from coral_amd import bam
+    if args.tmp_dir is not None and not args.stream:
+        raise ValueError("--tmp_dir names the spill file's directory: it goes with --stream")
+    if args.stream:                                              # (bam.sort_bam_stream: the same bytes, never whole in host memory)
+        if args.level != 1:
+            raise ValueError("--stream deflates on the GPU, which has one setting: --level must be 1, got %r" % (args.level,))
+        st = bam.sort_bam_stream(args.lr_bam, args.output, index=args.index, record_filter=record_filter_of(args), exclude_flags=args.reads_exclude_flags,
+                                 device="cuda:0" if args.device == "cpu" else args.device, tmp_dir=args.tmp_dir)
+        print("Wrote %s (%d records, %d runs)" % (args.output, st.records, st.runs))
+        return args.output
     out = bam.sort_bam(args.lr_bam, args.output, index=args.index, level=args.level, record_filter=record_filter_of(args),
                        exclude_flags=args.reads_exclude_flags, device=args.device, write_device=write_device_of(args))
     print("Wrote %s" % out)

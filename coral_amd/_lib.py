@@ -195,6 +195,13 @@ def lib():
                                                     C.POINTER(C.c_int64)]
     L.coral_bamgpu_open_request_to_text.argtypes = [C.c_char_p, C.c_int32, C.c_int64, Q, C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
     L.coral_bamgpu_sink_stats.argtypes =[C.c_void_p, C.POINTER(C.c_int64)]
+    L.coral_bamgpu_open_request_to_runs.argtypes = [C.c_char_p, C.c_int32, C.c_int64, Q, C.c_char_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
+    L.coral_bamgpu_run_table.argtypes = [C.c_void_p, C.c_int64, P, C.POINTER(C.c_int64)]
+    L.coral_bamgpu_merge_workspace_bytes.argtypes = [C.c_void_p, C.c_int64]
+    L.coral_bamgpu_merge_workspace_bytes.restype = C.c_int64
+    L.coral_bamgpu_merge_runs.argtypes = [C.c_void_p, C.c_char_p, P, C.c_int64, P, C.c_int64, C.c_int64, P]
+    L.coral_bamgpu_merge_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_double)]
+    L.coral_merge_plan.argtypes = [C.c_int32, P, P, P, C.c_int64, C.c_int64, C.c_int64, P, P, P, C.POINTER(C.c_int64)]
     L.coral_bam_records_merge.argtypes =[C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64), P, P, C.c_int32]
     L.coral_bgzf_deflate.argtypes = [P, P, C.c_int32, P, P, P, C.c_int64, P]
     L.coral_bgzf_pack.argtypes = [P, P, C.c_int32, P, P, P, C.c_int64, P]

@@ -14,6 +14,7 @@ import gzip
 import numbers
 import os
 import struct
+import time
 import zlib
 from typing import Optional, Sequence, Tuple
 
@@ -1266,7 +1267,7 @@ def view_bam(path: str, output: str, regions=None, names=None, exclude_flags: in
     0 = 1 024, at most 16 384) or on the run.  An empty ``regions`` or ``names`` list writes header + EOF without a decode.
     ``index``: also ``output``'s BAI index beside it (``build_index`` of the file written, host pipeline, as
     ``RecordBytes.write``).  It needs a GPU ``device``: the host path is ``extract_records(...).write(...)``.  On an exception
-    the partial output is removed.  Coordinate order is ``sort_bam``, which is not streamed."""
+    the partial output is removed.  Coordinate order is ``sort_bam`` and, streamed, ``sort_bam_stream``."""
     if torch.device(device).type != "cuda":
         raise ValueError("view_bam streams through a GPU device, got %r; the host path is extract_records(...).write(...)" % (device,))
     if isinstance(chunk_blocks, bool) or not isinstance(chunk_blocks, numbers.Integral) or not 0 <= chunk_blocks <= 16384:
@@ -1294,15 +1295,147 @@ def view_bam(path: str, output: str, regions=None, names=None, exclude_flags: in
 
 
 def sort_bam(path: str, output: str, *, index: bool = True, level: int = 1, record_filter=None, exclude_flags: int = 0, device="cuda:0",
-             n_threads: Optional[int] = None, batch_bytes: int = 0, write_device=None) -> str:
+             n_threads: Optional[int] = None, batch_bytes: int = 0, write_device=None, stream: bool = False) -> str:
     """``path``'s records - those that pass ``record_filter`` and ``exclude_flags`` - in coordinate order as the BAM file
     ``output``, with its BAI index beside it (``index``): ``samtools view -b -q ... | samtools sort | samtools index`` from one
     decode (``extract_records(order="coordinate")`` and ``RecordBytes.write``).  Returns ``output``.  The result lives in host
-    memory, about twice its size while the batches' runs are merged; runs are not spilled to disk.  ``write_device``: where the
-    output's BGZF blocks are deflated (``RecordBytes.write``'s ``device``; None: on the host, as before)."""
+    memory, about twice its size while the batches' runs are merged.  ``write_device``: where the output's BGZF blocks are
+    deflated (``RecordBytes.write``'s ``device``; None: on the host, as before).
+
+    ``stream=True``: ``sort_bam_stream`` - the runs are spilled to disk and merged on the GPU, in bounded host memory, for a file
+    of any size; the same bytes as ``write_device=device``.  The GPU compressor has one setting (``level`` must be 1), and a GPU
+    ``write_device`` other than ``device`` is refused."""
+    if stream:
+        if level != 1:
+            raise ValueError("a streamed sort deflates on the GPU, which has one setting: level must be 1, got %r" % (level,))
+        if write_device is not None and torch.device(write_device).type == "cuda" and torch.device(write_device) != torch.device(device):
+            raise ValueError("a streamed sort deflates where it decodes: write_device %r is not device %r" % (write_device, device))
+        sort_bam_stream(path, output, index=index, record_filter=record_filter, exclude_flags=exclude_flags, device=device, n_threads=n_threads,
+                        batch_bytes=batch_bytes)
+        return output
     rec = extract_records(path, None, None, exclude_flags, device=device, n_threads=n_threads, batch_bytes=batch_bytes, index=False,
                           record_filter=record_filter, order="coordinate")
     return rec.write(output, level=level, index=index, n_threads=n_threads, device="cpu" if write_device is None else write_device)
+
+
+SortStats = collections.namedtuple("SortStats", "records bytes file_bytes runs spill_bytes")
+LAST_SORT_STREAM = {}                                            # what the last sort_bam_stream did: coral_bamgpu_merge_stats and the two phases' seconds
+_ERR_NAMES = {-1: "CORAL_ERR_ARG", -2: "CORAL_ERR_HIP", -3: "CORAL_ERR_CAPACITY", -4: "CORAL_ERR_FORMAT"}
+
+
+def _size_argument(name: str, value, upper: Optional[int] = None, zero: str = "the default") -> int:
+    if isinstance(value, bool) or not isinstance(value, numbers.Integral) or value < 0 or (upper is not None and value > upper):
+        raise ValueError("%s must be an integer %s (0: %s), got %r" % (name, ">= 0" if upper is None else "in 0..%d" % upper, zero, value))
+    return int(value)
+
+
+def sort_bam_stream(path: str, output: str, *, index: bool = True, record_filter=None, exclude_flags: int = 0, device="cuda:0",
+                    n_threads: Optional[int] = None, batch_bytes: int = 0, chunk_blocks: int = 0, stage_bytes: int = 0, tmp_dir=None) -> SortStats:
+    """``samtools view -b ... | samtools sort | samtools index`` of a file of any size: ``sort_bam``'s output, byte for byte that of
+    ``extract_records(order="coordinate", ...).write(output, device=gpu)``, made in two phases in which uncompressed record
+    bytes exist only in HBM.
+
+    Phase 1, while the file is decoded (coral_bamgpu_open_request_to_runs): every batch is sorted on the device as for
+    ``order="coordinate"``, and its sorted records are deflated where they are and appended to the spill file
+    ``<tmp_dir or output's directory>/<output's name>.runs.tmp`` as one run of BGZF members.  Per written record 12 bytes come
+    back to the host: its sort key and its length.  Phase 2 (coral_bamgpu_merge_runs): one stable radix sort of all keys on the
+    device gives the final order; in steps of at most ``stage_bytes`` inflated source bytes (0: one batch's capacity) the runs'
+    members are read, inflated on the device (k_bgzf_inflate, k_bgzf_crc), gathered in final order (k_bam_merge_copy) and
+    deflated into ``output`` behind the sorted header (``sorted_header_bytes``), cut at 0xff00 bytes as every writer here cuts.
+    Host memory is bounded by 16 bytes per written record and a few pinned buffers, whatever the output's size; device memory
+    by the decode's workspace plus about 52 bytes per record and three times ``stage_bytes``; the spill file is about as large
+    as the output.  Fewer than 2^31 records.  A record whose source blocks do not fit ``stage_bytes`` raises (CORAL_ERR_CAPACITY).
+
+    ``batch_bytes`` and ``chunk_blocks`` are ``view_bam``'s; the output's bytes depend on none of the three sizes.  ``index``:
+    also the BAI index beside ``output`` (``build_index`` of the file written, host pipeline).  The spill file is removed on
+    success and on any exception; on an exception the partial output is removed too.  It needs a GPU ``device``: the host path
+    is ``sort_bam``.  Returns ``SortStats(records, bytes, file_bytes, runs, spill_bytes)``."""
+    if torch.device(device).type != "cuda":
+        raise ValueError("sort_bam_stream streams through a GPU device, got %r; the host path is sort_bam" % (device,))
+    chunk_blocks = _size_argument("chunk_blocks", chunk_blocks, 16384, "1 024")
+    batch_bytes = _size_argument("batch_bytes", batch_bytes)
+    stage_bytes = _size_argument("stage_bytes", stage_bytes, 0xf0000000, "one batch's capacity")
+    if isinstance(exclude_flags, bool) or not isinstance(exclude_flags, numbers.Integral) or not 0 <= exclude_flags <= 0xffff:
+        raise ValueError("exclude_flags must be an integer in 0..0xffff, got %r" % (exclude_flags,))
+    if tmp_dir is not None and not os.path.isdir(tmp_dir):
+        raise ValueError("tmp_dir %r is not a directory" % (tmp_dir,))
+    record_filter = _as_filter(record_filter)
+    spill = os.path.join(os.fspath(tmp_dir) if tmp_dir is not None else os.path.dirname(os.path.abspath(output)), os.path.basename(output) + ".runs.tmp")
+    header = np.frombuffer(sorted_header_bytes(bam_header_bytes(path)), dtype=np.uint8)
+    L = _lib.lib()
+    dev = torch.device(device)
+    torch.cuda.set_device(dev)
+    if n_threads is None:
+        n_threads = default_threads()
+    fail = lambda what, rc: _lib.CoralHipError("%s(%s) failed (%d, %s): %s" % (what, path, rc, _ERR_NAMES.get(rc, "?"), L.coral_bam_last_error().decode()))
+    stat_of = lambda p: (lambda st: (st.st_ino, st.st_size, st.st_mtime_ns))(os.stat(p)) if os.path.exists(p) else None
+    before = stat_of(output)                                     # (an argument error leaves a file that was there alone)
+    req = _lib.bam_request(keep=record_filter, reads=(exclude_flags, None, None, 2, 1))
+    h, ws_bytes = C.c_void_p(), C.c_int64(0)
+    try:
+        rc = L.coral_bamgpu_open_request_to_runs(path.encode(), n_threads, batch_bytes, C.byref(req), os.fsencode(spill), chunk_blocks, C.byref(h), C.byref(ws_bytes))
+        if rc != 0:
+            raise fail("coral_bamgpu_open_request_to_runs", rc)
+        t0 = time.perf_counter()
+        ws = torch.empty(int(ws_bytes.value) + 256, dtype=torch.uint8, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        torch.cuda.current_stream(dev).synchronize()             # (as _decode_gpu: the workspace may be a recycled block)
+        rc = L.coral_bamgpu_start(h, (ws.data_ptr() + 255) & ~255, int(ws_bytes.value))
+        if rc != 0:
+            raise fail("coral_bamgpu_start", rc)
+        out = (C.c_int64 * 4)()
+        batches, piece = 0, None
+        while True:
+            rc = L.coral_bamgpu_next(h, out, stream)
+            if rc != 0:
+                raise fail("coral_bamgpu_next", rc)
+            if not out[2]:
+                break
+            piece = torch.empty(max(int(out[1]), 1), dtype=torch.int32, device=dev)      # (the decode's CIGAR ops: not kept)
+            rc = L.coral_bamgpu_emit(h, piece.data_ptr(), None, stream)
+            if rc != 0:
+                raise fail("coral_bamgpu_emit", rc)
+            batches += 1
+        rc = L.coral_bamgpu_finish(h, stream)
+        if rc != 0:
+            raise fail("coral_bamgpu_finish", rc)
+        del piece
+        t1 = time.perf_counter()
+        counts = (C.c_int64 * 3)()
+        _lib.check(L.coral_bamgpu_run_table(h, 0, None, counts), "coral_bamgpu_run_table")
+        ws2_bytes = int(L.coral_bamgpu_merge_workspace_bytes(h, stage_bytes))
+        if ws2_bytes < 0:
+            raise fail("coral_bamgpu_merge_workspace_bytes", ws2_bytes)
+        ws2 = torch.empty(ws2_bytes + 256, dtype=torch.uint8, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        rc = L.coral_bamgpu_merge_runs(h, os.fsencode(output), header.ctypes.data, len(header), (ws2.data_ptr() + 255) & ~255, ws2_bytes, stage_bytes, stream)
+        if rc != 0:
+            raise fail("coral_bamgpu_merge_runs", rc)
+        st, secs = (C.c_int64 * 8)(), (C.c_double * 8)()
+        _lib.check(L.coral_bamgpu_merge_stats(h, st, secs), "coral_bamgpu_merge_stats")
+        LAST_SORT_STREAM.clear()
+        LAST_SORT_STREAM.update(batches=batches, runs=int(counts[0]), phase1_seconds=t1 - t0, phase2_seconds=float(secs[0]), order_seconds=float(secs[1]),
+                                read_seconds=float(secs[2]), inflate_wait_seconds=float(secs[3]), inflate_gpu_seconds=float(secs[4]),
+                                copy_gpu_seconds=float(secs[5]), sink_seconds=float(secs[6]), steps=int(st[0]), spill_members_inflated=int(st[1]),
+                                edge_members_inflated_twice=int(st[2]), members=int(st[6]), workspace_bytes=int(ws_bytes.value), merge_workspace_bytes=ws2_bytes)
+        stats = SortStats(int(st[3]), int(st[4]), int(st[5]), int(counts[0]), int(st[7]))
+        L.coral_bamgpu_close(h)                                  # (drains the streams; only then the workspaces go)
+        h = C.c_void_p()
+        if index:
+            build_index(output, device="cpu")
+    except BaseException:
+        if h:
+            L.coral_bamgpu_close(h)
+            h = C.c_void_p()
+        if stat_of(output) not in (None, before):
+            os.remove(output)
+        raise
+    finally:
+        if h:
+            L.coral_bamgpu_close(h)
+        if os.path.exists(spill):
+            os.remove(spill)
+    return stats
 
 
 # ----------------------------------------------------------------------------------------------

@@ -49,6 +49,7 @@
 #include "../../include/coral_hip.h"
 
 #include "coral_bam_common.h"
+#include "coral_merge_plan.h"
 
 using namespace coral_bam;
 
@@ -688,6 +689,27 @@ extern "C" int coral_bam_records_merge(int32_t n_runs, const uint8_t *const *dat
     for (int64_t t = 1; t < nt; ++t) workers.emplace_back(copy, t);
     copy(0);
     for (auto &w : workers) w.join();
+    return CORAL_OK;
+}
+
+// The step plan of the streamed sort's merge (coral_merge_plan.h) on its own: counts = {steps, parts}; with step_j (steps + 1),
+// step_part (steps + 1) and parts (rows of run, first block, block count, staging base) given, of the capacities max_steps /
+// max_parts, the plan itself.
+extern "C" int coral_merge_plan(int32_t n_runs, const int64_t *run_records, const uint32_t *len, const uint32_t *perm, int64_t stage_bytes,
+                                int64_t max_steps, int64_t max_parts, int64_t *step_j, int64_t *step_part, int64_t *parts, int64_t counts[2]) {
+    if (!counts) { g_bam_err = "coral_merge_plan: no counts"; return CORAL_ERR_ARG; }
+    counts[0] = counts[1] = 0;
+    coral_merge::Plan plan;
+    if (const int rc = coral_merge::plan_steps(n_runs, run_records, len, perm, stage_bytes, plan, g_bam_err)) return rc;
+    counts[0] = plan.n_steps();
+    counts[1] = (int64_t)plan.parts.size();
+    if (!step_j && !step_part && !parts) return CORAL_OK;
+    if (!step_j || !step_part || (counts[1] > 0 && !parts)) { g_bam_err = "coral_merge_plan: a missing output array"; return CORAL_ERR_ARG; }
+    if (max_steps < counts[0] || max_parts < counts[1]) { g_bam_err = "coral_merge_plan: the output arrays are too short (counts holds the sizes)"; return CORAL_ERR_CAPACITY; }
+    memcpy(step_j, plan.step_j.data(), plan.step_j.size() * 8);
+    memcpy(step_part, plan.step_part.data(), plan.step_part.size() * 8);
+    static_assert(sizeof(coral_merge::Part) == 32, "a part is four int64");
+    if (counts[1] > 0) memcpy(parts, plan.parts.data(), plan.parts.size() * sizeof(coral_merge::Part));
     return CORAL_OK;
 }
 

@@ -23,6 +23,7 @@
 // Requests that ride along a decode (coral_bam_request_t), each queued per batch before the slot is reused; one header each
 // (kernels, device structs and the host-side struct), listed once, in stream order, at each_request:
 //   coral_bamgpu_reads.h   reads: the selected records as FASTQ text or as their own bytes, in file or coordinate order
+//   coral_bamgpu_merge.h   (with the reads request) the streamed coordinate sort: sorted runs to a spill file, merged on the device
 //   coral_bamgpu_cov.h     window coverage: pysam count_coverage with a base-quality threshold; per_base: the pileup table
 //   coral_bamgpu_qc.h      read QC: per read the sum of its QUAL bytes, and the 256-bin histogram of all of them
 //   coral_bamgpu_depth.h   binned depth: one walk of each record's CIGAR into two tables of fixed-size bins
@@ -1757,7 +1758,8 @@ extern "C" int coral_bamgpu_open_request(const char *path, int32_t n_threads, in
 namespace {
 // The file a records request writes to (coral_bamgpu_open_request_to_file); none: the request's result stays on the host.
 // (as_text: the plain FASTQ file of coral_bamgpu_open_request_to_text - no header, no chunks)
-struct SinkArgs { const char *out_path; const uint8_t *header; int64_t header_bytes; int32_t chunk_blocks; bool as_text; };
+// (as_runs: the spill file of coral_bamgpu_open_request_to_runs - no header, one sorted run per batch)
+struct SinkArgs { const char *out_path; const uint8_t *header; int64_t header_bytes; int32_t chunk_blocks; bool as_text; bool as_runs = false; };
 
 // What the open entry points share: the older calls are this one without a sink.
 int open_decoder(const char *path, int32_t n_threads, int64_t batch_bytes, const coral_bam_request_t *req, int32_t reads_order, const SinkArgs *to_file,
@@ -1773,6 +1775,12 @@ int open_decoder(const char *path, int32_t n_threads, int64_t batch_bytes, const
         if (!(R.reads.on && R.reads.mode == READS_AS_FASTQ)) return fail(CORAL_ERR_ARG, std::string(me) + "a text file takes FASTQ: it needs want_reads = 1");
         if (R.rank != 0 || R.world != 1) return fail(CORAL_ERR_ARG, std::string(me) + "byte ranges do not share a file: rank 0 of world 1");
         if (!to_file->out_path) return fail(CORAL_ERR_ARG, std::string(me) + "no output path");
+    } else if (to_file && to_file->as_runs) {
+        const char *me = "coral_bamgpu_open_request_to_runs: ";
+        if (!(R.reads.on && R.reads.mode == READS_AS_RECORDS)) return fail(CORAL_ERR_ARG, std::string(me) + "runs are made of records: it needs want_reads = 2");
+        if (R.rank != 0 || R.world != 1) return fail(CORAL_ERR_ARG, std::string(me) + "byte ranges do not share a spill file: rank 0 of world 1");
+        if (!to_file->out_path) return fail(CORAL_ERR_ARG, std::string(me) + "no spill path");
+        if (to_file->chunk_blocks < 0 || to_file->chunk_blocks > 16384) return fail(CORAL_ERR_ARG, std::string(me) + "chunk_blocks must be 0 (1 024) .. 16 384");
     } else if (to_file) {
         const char *me = "coral_bamgpu_open_request_to_file: ";
         if (!(R.reads.on && R.reads.mode == READS_AS_RECORDS)) return fail(CORAL_ERR_ARG, std::string(me) + "a file takes records: it needs want_reads = 2");
@@ -1838,9 +1846,16 @@ int open_decoder(const char *path, int32_t n_threads, int64_t batch_bytes, const
         RecordSink &S = G->reads.sink;
         S.on = true;
         S.path = to_file->out_path;
-        S.header.assign(to_file->header, to_file->header + to_file->header_bytes);
+        if (!to_file->as_runs) S.header.assign(to_file->header, to_file->header + to_file->header_bytes);
         S.chunk = to_file->chunk_blocks > 0 ? (size_t)to_file->chunk_blocks : DEFL_CHUNK_BLOCKS;
         if (!(S.fp = fopen(to_file->out_path, "wb"))) return fail(CORAL_ERR_ARG, std::string("cannot create ") + to_file->out_path);
+        if (to_file->as_runs) {
+            MergeRuns &M = G->reads.merge;
+            M.on = true;
+            M.spill_path = to_file->out_path;
+            M.chunk = S.chunk;
+            M.default_stage = (int64_t)std::min<size_t>(G->caps().batch_cap, (size_t)MERGE_STAGE_MAX);
+        }
     }
     int rc = CORAL_OK;                         // what rides along: each request takes its part of R (and what of it needs the header or the capacities)
     if (!each_request(G.get(), [&](auto &r) { return (rc = r.open(R, G->caps(), G->D, err)) == CORAL_OK; }, true)) { set_error(err); return rc; }
@@ -1871,6 +1886,78 @@ extern "C" int coral_bamgpu_open_request_to_text(const char *path, int32_t n_thr
                                                  const char *out_path, void **handle, int64_t *workspace_bytes) {
     const SinkArgs to_file{out_path, nullptr, 0, 0, true};
     return open_decoder(path, n_threads, batch_bytes, req, READS_ORDER_FILE, &to_file, handle, workspace_bytes);
+}
+
+// The streamed coordinate sort, phase 1 (coral_bamgpu_merge.h): an ordered want_reads = 2 request whose batches' sorted runs go
+// to the spill file `spill_path` while the decode runs; coral_bamgpu_merge_runs, after `finish`, is phase 2.
+extern "C" int coral_bamgpu_open_request_to_runs(const char *path, int32_t n_threads, int64_t batch_bytes, const coral_bam_request_t *req,
+                                                 const char *spill_path, int32_t chunk_blocks, void **handle, int64_t *workspace_bytes) {
+    SinkArgs to_runs{spill_path, nullptr, 0, chunk_blocks, false};
+    to_runs.as_runs = true;
+    if (req && req->want_reads != READS_AS_RECORDS) return fail(CORAL_ERR_ARG, "coral_bamgpu_open_request_to_runs: runs are made of records: it needs want_reads = 2");
+    return open_decoder(path, n_threads, batch_bytes, req, READS_ORDER_COORDINATE, &to_runs, handle, workspace_bytes);
+}
+
+namespace {
+MergeRuns *merge_of(void *handle, const char *me, bool finished) {
+    GpuDecoder *G = (GpuDecoder *)handle;
+    if (!G || !G->reads.merge.on) { set_error(std::string(me) + ": the handle was not opened by coral_bamgpu_open_request_to_runs"); return nullptr; }
+    if (finished && !(G->finished && !G->have_cur && G->D.reads_to_file)) { set_error(std::string(me) + ": the decode is not finished (coral_bamgpu_finish)"); return nullptr; }
+    return &G->reads.merge;
+}
+}  // namespace
+
+// counts = runs, written records, bytes of the spill file; table (may be NULL; max_runs rows of first record, records, inflated
+// bytes, file offset): the runs in batch order
+extern "C" int coral_bamgpu_run_table(void *handle, int64_t max_runs, int64_t *table, int64_t counts[3]) {
+    MergeRuns *M = merge_of(handle, "coral_bamgpu_run_table", true);
+    if (!M || !counts) return CORAL_ERR_ARG;
+    counts[0] = (int64_t)M->runs.size(); counts[1] = M->n_records(); counts[2] = M->spill_bytes;
+    if (!table) return CORAL_OK;
+    if (max_runs < counts[0]) return fail(CORAL_ERR_CAPACITY, "coral_bamgpu_run_table: the table is too short (counts[0] holds the size)");
+    for (size_t r = 0; r < M->runs.size(); ++r) {
+        const MergeRuns::Run &R = M->runs[r];
+        table[4 * r] = R.first; table[4 * r + 1] = R.n; table[4 * r + 2] = R.bytes; table[4 * r + 3] = R.file_off;
+    }
+    return CORAL_OK;
+}
+
+// device memory coral_bamgpu_merge_runs needs for this handle's runs and `stage_bytes` (0: one batch's capacity); negative: an error code
+extern "C" int64_t coral_bamgpu_merge_workspace_bytes(void *handle, int64_t stage_bytes) {
+    MergeRuns *M = merge_of(handle, "coral_bamgpu_merge_workspace_bytes", true);
+    if (!M) return CORAL_ERR_ARG;
+    std::string err;
+    const int64_t got = M->workspace_bytes(stage_bytes, err);
+    if (got < 0) set_error(err);
+    return got;
+}
+
+extern "C" int coral_bamgpu_merge_runs(void *handle, const char *out_path, const uint8_t *header, int64_t header_bytes, void *workspace,
+                                       int64_t workspace_bytes, int64_t stage_bytes, void *stream) {
+    const char *me = "coral_bamgpu_merge_runs";
+    MergeRuns *M = merge_of(handle, me, true);
+    if (!M) return CORAL_ERR_ARG;
+    if (!out_path) return fail(CORAL_ERR_ARG, std::string(me) + ": no output path");
+    if (!header || header_bytes <= 0) return fail(CORAL_ERR_ARG, std::string(me) + ": no header to write");
+    const int rc = M->merge(out_path, header, header_bytes, workspace, workspace_bytes, stage_bytes, (hipStream_t)stream);
+    if (rc != CORAL_OK) set_error(M->error.empty() ? std::string(me) + " failed" : M->error);
+    return rc;
+}
+
+// after coral_bamgpu_merge_runs.  stats: [0] steps, [1] spill members inflated, [2] of them members a step shared with the one
+// in front (inflated twice), [3] records written, [4] their bytes, [5] bytes of the output, [6] its BGZF members, [7] bytes of
+// the spill file; seconds: [0] the call, [1] the order (upload, sort, scans, plan), [2] reading the spill file, [3] waiting for
+// upload + inflate + checksums, [4] of that the two kernels on the device, [5] k_bam_merge_copy on the device, [6] the sink
+// (queueing the copy, waiting for deflated chunks, writing them), [7] 0
+extern "C" int coral_bamgpu_merge_stats(void *handle, int64_t stats[8], double seconds[8]) {
+    MergeRuns *M = merge_of(handle, "coral_bamgpu_merge_stats", true);
+    if (!M || !stats || !seconds) return CORAL_ERR_ARG;
+    if (!M->merged) return fail(CORAL_ERR_ARG, "coral_bamgpu_merge_stats: no merge has succeeded on this handle");
+    stats[0] = M->steps; stats[1] = M->blocks; stats[2] = M->blocks_twice; stats[3] = M->out_records; stats[4] = M->out_bytes;
+    stats[5] = M->out_file_bytes; stats[6] = M->out_members; stats[7] = M->spill_bytes;
+    seconds[0] = M->t_total; seconds[1] = M->t_order; seconds[2] = M->t_read; seconds[3] = M->t_inflate_wait; seconds[4] = M->t_inflate_gpu;
+    seconds[5] = M->t_copy_gpu; seconds[6] = M->t_sink; seconds[7] = 0;
+    return CORAL_OK;
 }
 
 // records written, their inflated bytes, bytes of the file so far, BGZF members in it (after `finish`: the whole file, EOF block included)

@@ -375,6 +375,30 @@ struct RecordSink {
         bytes += n;
         return true;
     }
+    // One sorted run of a spill file (coral_bamgpu_open_request_to_runs): `n` bytes stand at buf, offset 0, written by a kernel on
+    // `stream`.  ALL of them are deflated now, a short last block included: a run is a whole number of members and shares none.
+    bool run(uint8_t *buf, long long n, long long n_records, hipStream_t stream) {
+        if (!ok(hipEventRecord(ev_copied, stream), "hipEventRecord") || !ok(hipStreamWaitEvent(s, ev_copied, 0), "hipStreamWaitEvent")) return false;
+        if (n > 0 && !submit_all(buf, (size_t)n)) return false;
+        if (!ok(hipEventRecord(ev_moved, s), "hipEventRecord")) return false;
+        moved = true;
+        records += n_records;
+        bytes += n;
+        return true;
+    }
+    // The chunk in flight, if any, comes back and is written: file_bytes is then where the next member will start.
+    bool flush() {
+        uint8_t *data = nullptr;
+        size_t n = 0;
+        return take_in(data, n) && write_out(data, n);
+    }
+    // The end of a file without an EOF block (a spill file is members only).
+    bool close_plain() {
+        if (!flush()) return false;
+        const bool good = fclose(fp) == 0;
+        fp = nullptr;
+        return good || fail("writing " + path + " failed");
+    }
     // The next batch's copy kernel on `stream` writes behind the carry: behind the tail move, and behind the deflate that read the buffer.
     bool wait_moved(hipStream_t stream) { return !moved || ok(hipStreamWaitEvent(stream, ev_moved, 0), "hipStreamWaitEvent"); }
     bool finish(uint8_t *buf) {

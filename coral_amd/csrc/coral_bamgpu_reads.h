@@ -5,6 +5,7 @@
 //   k_bam_reads_copy_shifted   the same into a buffer whose head holds bytes carried over: a request that writes to a file
 //                   (RecordSink in coral_bamgpu_deflate.h; TextSink, below, is the plain file of a FASTQ request)
 //   k_bam_sort_keys + k_bam_sort_permute + k_bam_reads_copy_sorted   reads_order = 1: the same bytes in coordinate order
+//                   (with MergeRuns, coral_bamgpu_merge.h: every batch's sorted run goes to a spill file, merged on the device later)
 // Kernels, device structs and the host-side request in one place; included by coral_bamgpu.hip inside its anonymous namespace
 // (once, behind coral_bamgpu_common.h), not a header of its own.
 
@@ -244,6 +245,7 @@ __global__ __launch_bounds__(WAVE) void k_bam_reads_copy_sorted(const uint8_t *_
 }
 
 #include "coral_bamgpu_deflate.h"      // RecordSink; its kernels use reads_window / reads_run above
+#include "coral_bamgpu_merge.h"        // MergeRuns: the streamed coordinate sort (sorted runs to a spill file, merged on the device)
 
 // ---- host side: the request's lifecycle (each_request in coral_bamgpu.hip, which calls all but open only when `active`) ---------
 // The plain file a FASTQ request writes to (coral_bamgpu_open_request_to_text): each batch's text goes there where `collect` would
@@ -273,6 +275,7 @@ struct ReadsRequest {                // FASTQ text, or the own bytes (R->mode), 
     bool active = false;
     RecordSink sink;                 // sink.on (coral_bamgpu_open_request_to_file): the records go to a BGZF file, not to the host-side result
     TextSink text_sink;              // text_sink.on (coral_bamgpu_open_request_to_text): the FASTQ text goes to a plain file
+    MergeRuns merge;                 // merge.on (coral_bamgpu_open_request_to_runs; with sink.on): every batch's sorted run goes to the spill file
     const ReadsRule *R = nullptr;    // the request (Request::reads)
     ReadsDev X{};
     uint8_t *text = nullptr;         // the batch's text: one buffer for all batches (collect)
@@ -334,7 +337,7 @@ struct ReadsRequest {                // FASTQ text, or the own bytes (R->mode), 
                         (X.n_names == 0 || ((e = hipMemcpy((void *)X.names, R->names.data(), R->names.size(), hipMemcpyHostToDevice)) == hipSuccess &&
                                             (e = hipMemcpy((void *)X.name_off, R->name_off.data(), R->name_off.size() * 8, hipMemcpyHostToDevice)) == hipSuccess));
         if (!ok) return "reads request set-up";
-        if (sink.on && !(sink.start() && sink.write_header(text, text_cap))) { e = hipGetLastError(); return "record sink set-up"; }
+        if (sink.on && !(sink.start() && (merge.on || sink.write_header(text, text_cap)))) { e = hipGetLastError(); return "record sink set-up"; }      // (a spill file has no header)
         return nullptr;
     }
     // It waits for its own totals (16 bytes: no read-back of the batch lies behind these kernels, so they are a small copy of their
@@ -343,10 +346,11 @@ struct ReadsRequest {                // FASTQ text, or the own bytes (R->mode), 
     bool batch(const Batch &B, Scratch S, std::string &err) {
         if (!collect(B.D)) { err = "copy of the reads text failed"; return false; }      // (of the batch in front: its kernels have run, ours are not queued yet)
         const long long n = B.n_rec;
-        if (n == 0) return true;
+        if (n == 0) return !merge.on || spill_run(B, {0}, {}, 0, 0, 0, nullptr, nullptr, nullptr, err);      // (an empty run)
         auto [out_len, n_items, out_off, item_off] = S.take<4>();
         hipLaunchKernelGGL(k_bam_reads_plan, dim3((unsigned)((n + 1 + WAVE - 1) / WAVE)), dim3(WAVE), 0, B.stream, B.buf, B.rec_start, n, B.M, B.end, X, out_len, n_items);
         const uint32_t *ord = nullptr;                   // coordinate order: sorted position -> record of the batch
+        const unsigned long long *sorted_key = nullptr;  // and the keys in that order
         if (ordered()) {
             hipLaunchKernelGGL(k_bam_sort_keys, dim3((unsigned)((n + WAVE - 1) / WAVE)), dim3(WAVE), 0, B.stream, n, B.M, sort_key[0], sort_ord[0]);
             hipcub::DoubleBuffer<unsigned long long> keys(sort_key[0], sort_key[1]);
@@ -358,12 +362,21 @@ struct ReadsRequest {                // FASTQ text, or the own bytes (R->mode), 
                 return false;
             }
             ord = ords.Current();
+            sorted_key = keys.Current();
             hipLaunchKernelGGL(k_bam_sort_permute, dim3((unsigned)((n + 1 + WAVE - 1) / WAVE)), dim3(WAVE), 0, B.stream, n, ord, out_len, n_items, sorted_len, sorted_items);
             if (!B.scan(sorted_len, out_off) || !B.scan(sorted_items, item_off)) { err = "scan of the sorted reads work items failed"; return false; }
             B.D.reads_runs.push_back((int64_t)B.D.reads_off.size() - 1);      // this batch's run begins behind what is written
         } else if (!B.scan(out_len, out_off) || !B.scan(n_items, item_off)) { err = "scan of the reads work items failed"; return false; }
         std::vector<long long> off((size_t)n + 1);
         long long items = 0;
+        if (merge.on) {                                  // a run of the spill file: the offsets, and the sorted keys with them
+            std::vector<unsigned long long> run_keys((size_t)n);
+            if (fetch_sync(B.stream, {{off.data(), out_off, (size_t)(n + 1) * 8}, {&items, item_off + n, 8}, {run_keys.data(), sorted_key, (size_t)n * 8}}, nullptr, "reads plan", err) != CORAL_OK)
+                return false;
+            const long long run_bytes = off[(size_t)n];
+            if (run_bytes < 0 || (size_t)run_bytes > text_cap || items < 0) { err = "reads request: the batch's text does not fit its buffer"; return false; }
+            return spill_run(B, off, run_keys, n, run_bytes, items, ord, item_off, out_off, err);
+        }
         if (fetch_sync(B.stream, {{off.data(), out_off, (size_t)(n + 1) * 8}, {&items, item_off + n, 8}}, nullptr, "reads plan", err) != CORAL_OK) return false;
         const long long bytes = off[(size_t)n];
         if (bytes < 0 || (size_t)bytes > text_cap || items < 0) { err = "reads request: the batch's text does not fit its buffer"; return false; }
@@ -396,6 +409,21 @@ struct ReadsRequest {                // FASTQ text, or the own bytes (R->mode), 
         pending_bytes = bytes;
         return true;
     }
+    // One batch of a streamed sort: the sorted copy at offset 0 of the sink's buffer - a run never shares a block with another -,
+    // all of its blocks deflated right away, and what the merge needs of it kept (MergeRuns::add_run).  The chunk in flight is
+    // written first, so that the file's size is where the run begins.
+    bool spill_run(const Batch &B, const std::vector<long long> &off, const std::vector<unsigned long long> &run_keys, long long n, long long bytes, long long items,
+                   const uint32_t *ord, const long long *item_off, const long long *out_off, std::string &err) {
+        if (!sink.flush()) { err = sink.error; return false; }
+        if (!merge.add_run(off, run_keys, n, sink.file_bytes)) { err = merge.error; return false; }
+        if (bytes == 0) return true;
+        if (!sink.wait_moved(B.stream)) { err = sink.error; return false; }
+        hipLaunchKernelGGL(k_bam_reads_copy_sorted, dim3((unsigned)std::min<long long>(items, 2048)), dim3(WAVE), 0, B.stream, B.buf, (long long)buf_bytes, B.rec_start, n, ord,
+                           item_off, out_off, text);
+        if (!launched("reads", err)) return false;
+        if (!sink.run(text, bytes, merge.runs.back().n, B.stream)) { err = sink.error; return false; }
+        return true;
+    }
     // The text of the batch emitted last, if it is still on the device (the caller has synchronised the stream).  One buffer for
     // all batches: QcRequest::collect's argument, under the same condition - every emit of a decode and the result call are
     // given the SAME stream.
@@ -404,6 +432,14 @@ struct ReadsRequest {                // FASTQ text, or the own bytes (R->mode), 
     // through the host's stable k-way merge, run order = batch order, and the runs are freed.
     bool finish(Decoded &D, int n_threads) {
         D.has_reads = true;
+        if (merge.on) {                  // the spill file ends with its last run's last member: no EOF block
+            if (!sink.close_plain()) return false;
+            merge.spill_bytes = sink.file_bytes;
+            D.reads_to_file = true;
+            D.reads_file_records = sink.records;
+            D.reads_file_bytes = sink.bytes;
+            return true;
+        }
         if (sink.on) {
             if (!sink.finish(text)) return false;
             D.reads_to_file = true;

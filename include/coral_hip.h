@@ -794,6 +794,48 @@ int coral_bam_records_merge(int32_t n_runs, const uint8_t *const *data, const in
  *          the next emit or `finish` has synchronised the stream); no compression, no carry, nothing new in the workspace.  The
  *          bytes are those coral_bam_reads_fill would give.  reads_sizes / reads_fill as for open_request_to_file; `finish`
  *          closes the file.  CORAL_ERR_ARG: want_reads other than 1, world above 1, no out_path, a path that cannot be created.
+ *   open_request_to_runs / merge_runs  the streamed coordinate sort (coral_bamgpu_merge.h, coral_merge_plan.h), in two phases in
+ *          both of which uncompressed record bytes exist only in device memory.
+ *          Phase 1, open_request_to_runs: open_request_ordered with reads_order = 1 for a want_reads = 2 request whose batches'
+ *          sorted runs go to the spill file `spill_path` WHILE the decode runs.  Per batch the plan, the key sort, the permute
+ *          and the two scans run as for an ordered request; k_bam_reads_copy_sorted puts the sorted records at offset 0 of the
+ *          sink's buffer and ALL of their blocks are deflated right away (k_bgzf_chunk_desc, k_bgzf_deflate, k_bgzf_pack in
+ *          chunks of chunk_blocks), a short last one included: every run is a whole number of BGZF members, every member but a
+ *          run's last holds 0xff00 bytes, no run shares a member.  The spill file has no header and no EOF block - members only;
+ *          a batch that writes nothing leaves an empty run.  The chunk in flight is written before a run begins (its file
+ *          offset is then known).  Per written record its 8-byte key and its length come back, in sorted order: the host keeps 12
+ *          bytes per written record (16 while coral_bamgpu_merge_runs uploads the keys: the order's 4 bytes join them, then the
+ *          keys are freed), a table of the runs and the sink's two pinned chunks - not the records.  The workspace is that of an
+ *          ordered request plus the sink's arrays.  coral_bam_reads_sizes gives records and bytes, coral_bam_reads_fill is
+ *          CORAL_ERR_ARG, sink_stats describes the spill file.  CORAL_ERR_ARG: want_reads other than 2, world above 1, no
+ *          spill_path, chunk_blocks outside 0..16 384, a path that cannot be created (and every refusal of open_request).
+ *          run_table (after `finish`): counts = runs, written records, bytes of the spill file; table (NULL, or max_runs rows):
+ *          per run its first record, records, inflated bytes, file offset.
+ *          Phase 2, merge_runs, after `finish` on the same handle, with a workspace of its own of merge_workspace_bytes(handle,
+ *          stage_bytes) bytes (256-byte aligned; a negative value is an error code; the record count is only known by then).
+ *          Once: the keys go up in run-major order, one stable hipcub radix sort of (key, global ordinal) - a tie goes to the
+ *          earlier run, inside a run to the earlier record: coral_bam_records_merge's rule -, k_bam_merge_lens (the lengths and
+ *          work items of READS_COPY_SLICE bytes in final order), three scans, and the order comes back.  The host plans steps
+ *          (coral_merge_plan): the longest stretch of whole records whose sources fit stage_bytes (0: one batch's capacity; at
+ *          most 0xf0000000); every run gives a contiguous range of its records, rounded outwards to its 0xff00-byte blocks; a
+ *          block two steps share is read and inflated twice; a record whose own blocks do not fit: CORAL_ERR_CAPACITY, nothing
+ *          created.  Per step the members go spill file -> one of two pinned pieces (rewritten only after its upload has
+ *          completed) -> device -> k_bgzf_inflate + k_bgzf_crc into the staging buffer (refilled only behind an event recorded
+ *          after the copy kernel that read it); the status words are waited for; k_bam_merge_copy (k_bam_reads_copy_sorted's
+ *          launch shape) gathers the step's records in final order behind the carry of a second file sink - behind its
+ *          wait_moved -, which cuts the concatenation of all steps at 0xff00 bytes: `out_path` is coral_bgzf_write_gpu's of the
+ *          two parts (header, all records in order), byte for byte.  The reader is synchronous; the sink deflates and writes
+ *          beside the next step.  Device memory: about 52 bytes per record, three times stage_bytes (staging, the members, the
+ *          sink's buffer) and the sink's arrays.  Fewer than 2^31 records.  A short read, a bad magic, a member reaching behind
+ *          its run, a member that does not inflate to its block or fails its CRC-32: CORAL_ERR_FORMAT, and the output is
+ *          removed (as after any failure behind its creation).  The library allocates no device memory.
+ *          merge_stats (after a merge): stats = steps, spill members inflated, of them members shared with the step in front,
+ *          records written, their bytes, bytes of the output, its members, bytes of the spill file; seconds = the call, the order,
+ *          reading the spill, waiting for upload + inflate + checksums, of that the kernels, k_bam_merge_copy, the sink, 0.
+ *   coral_merge_plan  the step plan alone (host only): run_records[n_runs], len[N] (run-major), perm[N] (final position ->
+ *          run-major ordinal; it must keep every run's records in their order: CORAL_ERR_ARG otherwise) -> counts = steps,
+ *          parts; with the three arrays given (capacities max_steps, max_parts; too short: CORAL_ERR_CAPACITY) step_j[steps + 1],
+ *          step_part[steps + 1] and parts[parts][4] = run, first block, block count, staging base, per step in run order.
  *   sink_stats  of such a handle: out = records written, their inflated bytes, bytes of the file, BGZF members in it (after
  *          `finish`: the whole file, header and EOF members included; a text file: its bytes twice and 0)
  * coral_bgzf_inflate: one inflate launch over caller-provided device buffers — desc = n_blocks x {src_off, src_len,
@@ -817,6 +859,15 @@ int coral_bamgpu_open_request_to_file(const char *path, int32_t n_threads, int64
 int coral_bamgpu_open_request_to_text(const char *path, int32_t n_threads, int64_t batch_bytes, const coral_bam_request_t *req,
                                       const char *out_path, void **handle, int64_t *workspace_bytes);
 int coral_bamgpu_sink_stats(void *handle, int64_t out[4]);
+int coral_bamgpu_open_request_to_runs(const char *path, int32_t n_threads, int64_t batch_bytes, const coral_bam_request_t *req,
+                                      const char *spill_path, int32_t chunk_blocks, void **handle, int64_t *workspace_bytes);
+int coral_bamgpu_run_table(void *handle, int64_t max_runs, int64_t *table, int64_t counts[3]);
+int64_t coral_bamgpu_merge_workspace_bytes(void *handle, int64_t stage_bytes);
+int coral_bamgpu_merge_runs(void *handle, const char *out_path, const uint8_t *header, int64_t header_bytes, void *workspace,
+                            int64_t workspace_bytes, int64_t stage_bytes, void *stream);
+int coral_bamgpu_merge_stats(void *handle, int64_t stats[8], double seconds[8]);
+int coral_merge_plan(int32_t n_runs, const int64_t *run_records, const uint32_t *len, const uint32_t *perm, int64_t stage_bytes,
+                     int64_t max_steps, int64_t max_parts, int64_t *step_j, int64_t *step_part, int64_t *parts, int64_t counts[2]);
 int coral_bamgpu_finish(void *handle, void *stream);
 int coral_bamgpu_close(void *handle);
 int coral_bgzf_inflate(const uint8_t *comp, const uint32_t *desc, int32_t n_blocks, uint8_t *out, int32_t *status,

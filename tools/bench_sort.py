@@ -10,10 +10,15 @@ median of `runs` interleaved runs:
 as wall time and as HIP-event time on the caller's stream.  The line also holds the host wall time of coral_bam_records_merge over
 the runs of a `--batch_bytes` decode (runs = batches; with the default batch the file is one run and nothing is merged), as its
 share of that decode's wall time, and the wall time of bam.sort_bam (level 1, with the index).  One JSON line.
-    python tools/bench_sort.py [runs] [--bam PATH] [--batch_bytes N] [--kernels-only file|coordinate] [--decode-only]
+    python tools/bench_sort.py [runs] [--bam PATH] [--batch_bytes N] [--kernels-only file|coordinate] [--decode-only] [--stream]
 --kernels-only: one decode with the request in that order and nothing else (the leg to run under rocprofv3 --kernel-trace
                 --stats: k_bam_reads_copy of `file` against k_bam_reads_copy_sorted of `coordinate` on the same bytes).
---decode-only:  only the `decode` leg (runs on a checkout without the feature: the yardstick for "no request costs nothing")."""
+--decode-only:  only the `decode` leg (runs on a checkout without the feature: the yardstick for "no request costs nothing").
+--stream:       the streamed sort (bam.sort_bam_stream) against the in-memory one (bam.sort_bam(write_device=gpu)), both without
+                the index, `runs` times each, interleaved, every run in a fresh child process so that its peak resident set
+                (VmHWM) is its own: wall time, the two phases, phase 2 split into order / read / inflate / copy / sink,
+                spill size against output size, the edge members inflated twice, peak host RSS of both paths; the outputs
+                must be equal byte for byte.  --batch_bytes and --stage_bytes are passed on (0: the defaults)."""
 import argparse
 import json
 import os
@@ -35,6 +40,10 @@ ap.add_argument("--bam", default="")
 ap.add_argument("--batch_bytes", type=int, default=64 << 20)
 ap.add_argument("--kernels-only", choices=("file", "coordinate"), default=None)
 ap.add_argument("--decode-only", action="store_true")
+ap.add_argument("--stream", action="store_true")
+ap.add_argument("--stream-leg", choices=("memory", "stream"), default=None, help=argparse.SUPPRESS)
+ap.add_argument("--stage_bytes", type=int, default=0)
+ap.add_argument("--out", default="", help=argparse.SUPPRESS)
 args = ap.parse_args()
 
 d = tempfile.mkdtemp(prefix="coral_sort_")
@@ -56,6 +65,59 @@ if not os.path.exists(path):
     del src, take
     print("shuffled BAM written: %.1f MB in %.1f s" % (os.path.getsize(path) / 1e6, time.perf_counter() - t0), file=sys.stderr, flush=True)
 dev = "cuda:0"
+
+if args.stream_leg:                                     # one run in this (fresh) process: its peak RSS is the leg's own
+    def peak_rss_MB():                                  # VmHWM: of this program alone (ru_maxrss would carry the parent's over the exec)
+        with open("/proc/self/status") as fp:
+            return round(next(int(ln.split()[1]) for ln in fp if ln.startswith("VmHWM:")) / 1024, 1)
+    batch = args.batch_bytes if args.batch_bytes != (64 << 20) else 0
+    t0 = time.perf_counter()
+    if args.stream_leg == "stream":
+        st = bam.sort_bam_stream(path, args.out, index=False, device=dev, batch_bytes=batch, stage_bytes=args.stage_bytes)
+        extra = dict(bam.LAST_SORT_STREAM, records=st.records, bytes=st.bytes, spill_bytes=st.spill_bytes)
+    else:
+        bam.sort_bam(path, args.out, index=False, device=dev, write_device=dev, batch_bytes=batch)
+        extra = {"batches": bam.LAST_DECODE.get("batches")}
+    wall = time.perf_counter() - t0
+    print(json.dumps(dict(extra, leg=args.stream_leg, wall_s=round(wall, 4), peak_rss_MB=peak_rss_MB(),
+                          file_bytes=os.path.getsize(args.out))))
+    os.rmdir(d)
+    sys.exit(0)
+
+if args.stream:
+    import hashlib
+    import subprocess
+    runs = {"memory": [], "stream": []}
+    digest = {}
+    for r in range(args.runs):
+        for leg in runs:                                # interleaved; a fresh child each (this process never touches the GPU)
+            out = os.path.join(d, leg + ".bam")
+            done = subprocess.run([sys.executable, os.path.abspath(__file__), "--bam", path, "--stream-leg", leg, "--out", out, "--batch_bytes", str(args.batch_bytes),
+                                   "--stage_bytes", str(args.stage_bytes)], capture_output=True, text=True, timeout=900)
+            if done.returncode != 0:
+                sys.exit("leg %s failed (%d): %s" % (leg, done.returncode, done.stderr[-2000:]))
+            runs[leg].append(json.loads(done.stdout.strip().splitlines()[-1]))
+            with open(out, "rb") as fp:
+                h = hashlib.sha256()
+                for piece in iter(lambda: fp.read(1 << 24), b""):
+                    h.update(piece)
+                digest[leg] = h.hexdigest()
+            os.remove(out)
+        assert digest["memory"] == digest["stream"], "the streamed sort's file differs from the in-memory sort's"
+    med = lambda leg, k: round(statistics.median(x[k] for x in runs[leg]), 4)
+    keys = ("phase1_seconds", "phase2_seconds", "order_seconds", "read_seconds", "inflate_wait_seconds", "inflate_gpu_seconds", "copy_gpu_seconds", "sink_seconds")
+    last = runs["stream"][-1]
+    print(json.dumps({"tool": "bench_sort --stream", "bam_MB": round(os.path.getsize(path) / 1e6, 1), "runs": args.runs, "records": last["records"],
+                      "record_bytes": last["bytes"], "output_bytes": last["file_bytes"], "spill_bytes": last["spill_bytes"],
+                      "spill_over_output": round(last["spill_bytes"] / last["file_bytes"], 4), "sorted_runs": last["runs"], "steps": last["steps"],
+                      "spill_members_inflated": last["spill_members_inflated"], "edge_members_inflated_twice": last["edge_members_inflated_twice"],
+                      "workspace_MB": round(last["workspace_bytes"] / 2 ** 20, 1), "merge_workspace_MB": round(last["merge_workspace_bytes"] / 2 ** 20, 1),
+                      "median": {"memory": {"wall_s": med("memory", "wall_s"), "peak_rss_MB": med("memory", "peak_rss_MB")},
+                                 "stream": dict({"wall_s": med("stream", "wall_s"), "peak_rss_MB": med("stream", "peak_rss_MB")}, **{k: med("stream", k) for k in keys})},
+                      "identical_bytes": True, "all_runs": runs}))
+    import shutil
+    shutil.rmtree(d, ignore_errors=True)
+    sys.exit(0)
 
 if args.decode_only:
     extract = None
