@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import array
 import collections
+import contextlib
 import ctypes as C
 import gzip
 import numbers
@@ -22,6 +23,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .decode_session import BamFile, DecodeSession, Runs, TextFile
 from .names import NameTable
 from .synth import Records, hash_u32, S_SEQ, sa_entry_string
 
@@ -236,9 +238,9 @@ def _decode(path: str, device, *, n_threads: Optional[int] = None, rank: int = 0
     count_deletions) gives the binned-depth tables (``binned_depth``), ``reads`` = (exclude_flags, segments or None, sorted names or
     None[, mode]) the FASTQ text of the selected records (``extract_reads``) or, with mode 2, their own bytes (``extract_records``).  ``record_filter``: a ``RecordFilter``; every result is
     then that of a file holding only the kept records.  On the GPU pipeline when ``_on_gpu(device)``, else on the host.
-    ``sink`` = (output path, inflated header, chunk_blocks): the records of a mode-2 reads request go to that BAM file while the
-    decode runs (GPU pipeline only, whatever CORAL_BAM_DECODE says); ``reads`` is then (records, bytes, file bytes, members).
-    ``sink`` = (output path, None, 0): the FASTQ text of a mode-1 request goes to that plain file, batch by batch."""
+    ``sink`` = BamFile(output path, inflated header, chunk_blocks): the records of a mode-2 reads request go to that BAM file while
+    the decode runs (GPU pipeline only, whatever CORAL_BAM_DECODE says); ``reads`` is then (records, bytes, file bytes, members).
+    ``sink`` = TextFile(output path): the FASTQ text of a mode-1 request goes to that plain file, batch by batch."""
     req = _lib.bam_request(rank, world, spans, coverage, index, qc, per_base, depth, keep=_as_filter(record_filter), reads=reads)
     if sink is not None and torch.device(device).type != "cuda":
         raise ValueError("a decode that writes its records to a file runs on a GPU device, got %r" % (device,))
@@ -306,85 +308,21 @@ def _result_from_handle(L, h, req, records: bool, cigar, cigar_words: int, reads
 
 
 def _decode_gpu(path: str, device, n_threads: Optional[int], batch_bytes: int, req, records: bool, sink=None) -> DecodeResult:
-    """The GPU pipeline of _decode: coral_bamgpu_open_request (with ``sink``: _to_file), the batches, coral_bamgpu_finish."""
-    L = _lib.lib()
-    dev = torch.device(device)
-    torch.cuda.set_device(dev)
+    """The GPU pipeline of _decode: one DecodeSession (``sink``: where the reads request's result goes instead of the host).  The
+    CIGAR words stay on the device only when ``records`` asks for them."""
     if n_threads is None:
         n_threads = default_threads()
-    fail = lambda what, rc: _lib.CoralHipError("%s(%s) failed (%d): %s" % (what, path, rc, L.coral_bam_last_error().decode()))
-    h, ws_bytes = C.c_void_p(), C.c_int64(0)
-    if sink is not None:
-        out_path, header, chunk_blocks = sink
-    if sink is not None and header is None:
-        rc = L.coral_bamgpu_open_request_to_text(path.encode(), n_threads, batch_bytes, C.byref(req), os.fsencode(out_path), C.byref(h), C.byref(ws_bytes))
-    elif sink is not None:
-        head = np.frombuffer(bytes(header), dtype=np.uint8)
-        rc = L.coral_bamgpu_open_request_to_file(path.encode(), n_threads, batch_bytes, C.byref(req), os.fsencode(out_path),
-                                                 head.ctypes.data if len(head) else None, len(head), int(chunk_blocks), C.byref(h), C.byref(ws_bytes))
-    elif req.reads_order:
-        rc = L.coral_bamgpu_open_request_ordered(path.encode(), n_threads, batch_bytes, C.byref(req), req.reads_order, C.byref(h), C.byref(ws_bytes))
-    else:
-        rc = L.coral_bamgpu_open_request(path.encode(), n_threads, batch_bytes, C.byref(req), C.byref(h), C.byref(ws_bytes))
-    if rc != 0:
-        raise fail("coral_bamgpu_open_request", rc)
-    try:
-        ws = torch.empty(int(ws_bytes.value) + 256, dtype=torch.uint8, device=dev)
-        base = (ws.data_ptr() + 255) & ~255
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        # `ws` may be a recycled block of torch's caching allocator: that is ordered only against the allocating stream, while the
-        # decoder's feeder thread and its own streams start writing into the workspace at once.  Let whatever the current stream
-        # still has queued (possibly on the block's previous owner) finish first — once per decode.
-        torch.cuda.current_stream(dev).synchronize()
-        rc = L.coral_bamgpu_start(h, base, int(ws_bytes.value))
-        if rc != 0:
-            raise fail("coral_bamgpu_start", rc)
-        pieces, total = [], 0
-        out = (C.c_int64 * 4)()
-        while True:
-            rc = L.coral_bamgpu_next(h, out, stream)
-            if rc != 0:
-                raise fail("coral_bamgpu_next", rc)
-            if not out[2]:
-                break
-            words = int(out[1])
-            piece = torch.empty(max(words, 1), dtype=torch.int32, device=dev)
-            rc = L.coral_bamgpu_emit(h, piece.data_ptr(), None, stream)
-            if rc != 0:
-                raise fail("coral_bamgpu_emit", rc)
-            if words:
-                pieces.append(piece[:words])
-                total += words
-        rc = L.coral_bamgpu_finish(h, stream)
-        if rc != 0:
-            raise fail("coral_bamgpu_finish", rc)
-        cigar = torch.cat(pieces) if len(pieces) > 1 else (pieces[0] if pieces else torch.zeros(0, dtype=torch.int32, device=dev))
-        del pieces
-        dh = C.c_void_p()
-        rc = L.coral_bamgpu_host(h, C.byref(dh))
-        if rc != 0:
-            raise fail("coral_bamgpu_host", rc)
-        st, secs = (C.c_int64 * 3)(), C.c_double(0.0)
-        L.coral_bam_decode_stats(dh, st, C.byref(secs))
-        gst, gsecs = (C.c_int64 * 4)(), (C.c_double * 6)()
-        L.coral_bamgpu_stats(h, gst, gsecs)
+    with DecodeSession(path, req, device=device, n_threads=n_threads, batch_bytes=batch_bytes, sink=sink) as s:
+        s.start()
+        s.run(keep=records)
+        dh = s.finish()
+        cigar = s.cigar() if records else None
         LAST_DECODE.clear()
-        LAST_DECODE.update(seconds=float(gsecs[0]), compressed_bytes=int(st[0]), uncompressed_bytes=int(st[1]), blocks=int(st[2]),
-                           threads=int(n_threads), where="gpu", batches=int(gst[0]), rewalked_segments=int(gst[1]),
-                           nonacgt_records_fetched=int(gst[2]), batch_bytes=int(gst[3]), host_seconds=float(gsecs[1]), read_seconds=float(gsecs[2]),
-                           setup_seconds=float(gsecs[3]), waited_for_file_seconds=float(gsecs[4]), waited_for_gpu_seconds=float(gsecs[5]),
-                           workspace_bytes=int(ws_bytes.value))
+        LAST_DECODE.update(s.stats())
+        res = _result_from_handle(s.L, dh, req, records, cigar, cigar.numel() if records else 0, reads_on_host=sink is None)
         if sink is not None:                                     # (nothing of the reads request is on the host: coral_bam_reads_fill refuses)
-            sst = (C.c_int64 * 4)()
-            _lib.check(L.coral_bamgpu_sink_stats(h, sst), "coral_bamgpu_sink_stats")
-            res = _result_from_handle(L, dh, req, records, cigar, total, reads_on_host=False)
-            res.reads = tuple(int(v) for v in sst)
-            return res
-        return _result_from_handle(L, dh, req, records, cigar, total)
-    finally:
-        # (close drains the decoder's streams — a byte range may have batches of its overhang still being inflated — and only
-        # then the workspace, which those kernels write, is released: `ws` lives until this function returns)
-        L.coral_bamgpu_close(h)
+            res.reads = s.sink_stats()
+        return res
 
 
 # ----------------------------------------------------------------------------------------------
@@ -946,7 +884,7 @@ def extract_reads(path: str, regions=None, names=None, exclude_flags: int = 0x90
     if (rank, world) != (0, 1):
         raise ValueError("extract_reads(output=...) writes one file: byte ranges (world > 1) do not go with it")
     regions, names = (None if x is None else list(x) for x in (regions, names))
-    got = _selected(1, path, regions, names, exclude_flags, device, n_threads, 0, 1, batch_bytes, index, record_filter, sink=(output, None, 0))
+    got = _selected(1, path, regions, names, exclude_flags, device, n_threads, 0, 1, batch_bytes, index, record_filter, sink=TextFile(output))
     if got is None:                                              # nothing was decoded: an empty file
         open(output, "wb").close()
         return 0, 0
@@ -959,8 +897,7 @@ def _selected(mode: int, path, regions, names, exclude_flags, device, n_threads,
     argument rules, the index use and the decode -> (bytes uint8, offsets int64 [n + 1]) of the reads request - with ``sink``
     its four counts -, or None for a selection that is empty before any record is decoded (an empty list: the file is not
     opened).  ``order`` 1 (mode 2 only): the records in coordinate order."""
-    if isinstance(exclude_flags, bool) or not isinstance(exclude_flags, numbers.Integral) or not 0 <= exclude_flags <= 0xffff:
-        raise ValueError("exclude_flags must be an integer in 0..0xffff, got %r" % (exclude_flags,))
+    _exclude_flags_argument(exclude_flags)
     if names is not None:
         names = sorted(set(nm.encode("latin-1") if isinstance(nm, str) else bytes(nm) for nm in names))
         for nm in names:
@@ -1270,27 +1207,19 @@ def view_bam(path: str, output: str, regions=None, names=None, exclude_flags: in
     the partial output is removed.  Coordinate order is ``sort_bam`` and, streamed, ``sort_bam_stream``."""
     if torch.device(device).type != "cuda":
         raise ValueError("view_bam streams through a GPU device, got %r; the host path is extract_records(...).write(...)" % (device,))
-    if isinstance(chunk_blocks, bool) or not isinstance(chunk_blocks, numbers.Integral) or not 0 <= chunk_blocks <= 16384:
-        raise ValueError("chunk_blocks must be an integer in 0..16384 (0: 1 024), got %r" % (chunk_blocks,))
-    if isinstance(batch_bytes, bool) or not isinstance(batch_bytes, numbers.Integral) or batch_bytes < 0:
-        raise ValueError("batch_bytes must be an integer >= 0, got %r" % (batch_bytes,))
+    chunk_blocks = _size_argument("chunk_blocks", chunk_blocks, 16384, "1 024")
+    batch_bytes = _size_argument("batch_bytes", batch_bytes, zero=None)
     regions, names = (None if x is None else list(x) for x in (regions, names))
     header = bam_header_bytes(path)
-    stat_of = lambda p: (lambda st: (st.st_ino, st.st_size, st.st_mtime_ns))(os.stat(p)) if os.path.exists(p) else None
-    before = stat_of(output)                                     # (an argument error leaves a file that was there alone)
-    try:
+    with _output_guard(output):
         got = _selected(2, path, regions, names, exclude_flags, device, n_threads, 0, 1, batch_bytes, bam_index, record_filter,
-                        sink=(output, header, chunk_blocks))
+                        sink=BamFile(output, header, chunk_blocks))
         if got is None:                                          # nothing was decoded: header + EOF, the same members
             head = np.frombuffer(header, dtype=np.uint8)
             _bgzf_write_gpu(output, (C.c_void_p * 1)(head.ctypes.data), (C.c_int64 * 1)(len(head)), 1, device)
             got = (0, 0, os.path.getsize(output), 0)
         if index:
             build_index(output, device="cpu")
-    except BaseException:
-        if stat_of(output) not in (None, before):
-            os.remove(output)
-        raise
     return ViewStats(int(got[0]), int(got[1]), int(got[2]))
 
 
@@ -1323,10 +1252,31 @@ LAST_SORT_STREAM = {}                                            # what the last
 _ERR_NAMES = {-1: "CORAL_ERR_ARG", -2: "CORAL_ERR_HIP", -3: "CORAL_ERR_CAPACITY", -4: "CORAL_ERR_FORMAT"}
 
 
-def _size_argument(name: str, value, upper: Optional[int] = None, zero: str = "the default") -> int:
+def _size_argument(name: str, value, upper: Optional[int] = None, zero: Optional[str] = "the default") -> int:
+    """``zero``: what 0 stands for in the message (None: the message does not say)."""
     if isinstance(value, bool) or not isinstance(value, numbers.Integral) or value < 0 or (upper is not None and value > upper):
-        raise ValueError("%s must be an integer %s (0: %s), got %r" % (name, ">= 0" if upper is None else "in 0..%d" % upper, zero, value))
+        raise ValueError("%s must be an integer %s%s, got %r" % (name, ">= 0" if upper is None else "in 0..%d" % upper,
+                                                                 "" if zero is None else " (0: %s)" % zero, value))
     return int(value)
+
+
+def _exclude_flags_argument(exclude_flags) -> None:
+    if isinstance(exclude_flags, bool) or not isinstance(exclude_flags, numbers.Integral) or not 0 <= exclude_flags <= 0xffff:
+        raise ValueError("exclude_flags must be an integer in 0..0xffff, got %r" % (exclude_flags,))
+
+
+@contextlib.contextmanager
+def _output_guard(output):
+    """Around the writing of the file ``output``: a partial output is removed on any exception, while a file that was there and
+    that nothing has touched - an argument error came first - is left alone."""
+    stat_of = lambda p: (lambda st: (st.st_ino, st.st_size, st.st_mtime_ns))(os.stat(p)) if os.path.exists(p) else None
+    before = stat_of(output)
+    try:
+        yield
+    except BaseException:
+        if stat_of(output) not in (None, before):
+            os.remove(output)
+        raise
 
 
 def sort_bam_stream(path: str, output: str, *, index: bool = True, record_filter=None, exclude_flags: int = 0, device="cuda:0",
@@ -1355,84 +1305,43 @@ def sort_bam_stream(path: str, output: str, *, index: bool = True, record_filter
     chunk_blocks = _size_argument("chunk_blocks", chunk_blocks, 16384, "1 024")
     batch_bytes = _size_argument("batch_bytes", batch_bytes)
     stage_bytes = _size_argument("stage_bytes", stage_bytes, 0xf0000000, "one batch's capacity")
-    if isinstance(exclude_flags, bool) or not isinstance(exclude_flags, numbers.Integral) or not 0 <= exclude_flags <= 0xffff:
-        raise ValueError("exclude_flags must be an integer in 0..0xffff, got %r" % (exclude_flags,))
+    _exclude_flags_argument(exclude_flags)
     if tmp_dir is not None and not os.path.isdir(tmp_dir):
         raise ValueError("tmp_dir %r is not a directory" % (tmp_dir,))
     record_filter = _as_filter(record_filter)
     spill = os.path.join(os.fspath(tmp_dir) if tmp_dir is not None else os.path.dirname(os.path.abspath(output)), os.path.basename(output) + ".runs.tmp")
     header = np.frombuffer(sorted_header_bytes(bam_header_bytes(path)), dtype=np.uint8)
-    L = _lib.lib()
-    dev = torch.device(device)
-    torch.cuda.set_device(dev)
     if n_threads is None:
         n_threads = default_threads()
-    fail = lambda what, rc: _lib.CoralHipError("%s(%s) failed (%d, %s): %s" % (what, path, rc, _ERR_NAMES.get(rc, "?"), L.coral_bam_last_error().decode()))
-    stat_of = lambda p: (lambda st: (st.st_ino, st.st_size, st.st_mtime_ns))(os.stat(p)) if os.path.exists(p) else None
-    before = stat_of(output)                                     # (an argument error leaves a file that was there alone)
     req = _lib.bam_request(keep=record_filter, reads=(exclude_flags, None, None, 2, 1))
-    h, ws_bytes = C.c_void_p(), C.c_int64(0)
     try:
-        rc = L.coral_bamgpu_open_request_to_runs(path.encode(), n_threads, batch_bytes, C.byref(req), os.fsencode(spill), chunk_blocks, C.byref(h), C.byref(ws_bytes))
-        if rc != 0:
-            raise fail("coral_bamgpu_open_request_to_runs", rc)
-        t0 = time.perf_counter()
-        ws = torch.empty(int(ws_bytes.value) + 256, dtype=torch.uint8, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        torch.cuda.current_stream(dev).synchronize()             # (as _decode_gpu: the workspace may be a recycled block)
-        rc = L.coral_bamgpu_start(h, (ws.data_ptr() + 255) & ~255, int(ws_bytes.value))
-        if rc != 0:
-            raise fail("coral_bamgpu_start", rc)
-        out = (C.c_int64 * 4)()
-        batches, piece = 0, None
-        while True:
-            rc = L.coral_bamgpu_next(h, out, stream)
-            if rc != 0:
-                raise fail("coral_bamgpu_next", rc)
-            if not out[2]:
-                break
-            piece = torch.empty(max(int(out[1]), 1), dtype=torch.int32, device=dev)      # (the decode's CIGAR ops: not kept)
-            rc = L.coral_bamgpu_emit(h, piece.data_ptr(), None, stream)
-            if rc != 0:
-                raise fail("coral_bamgpu_emit", rc)
-            batches += 1
-        rc = L.coral_bamgpu_finish(h, stream)
-        if rc != 0:
-            raise fail("coral_bamgpu_finish", rc)
-        del piece
-        t1 = time.perf_counter()
-        counts = (C.c_int64 * 3)()
-        _lib.check(L.coral_bamgpu_run_table(h, 0, None, counts), "coral_bamgpu_run_table")
-        ws2_bytes = int(L.coral_bamgpu_merge_workspace_bytes(h, stage_bytes))
-        if ws2_bytes < 0:
-            raise fail("coral_bamgpu_merge_workspace_bytes", ws2_bytes)
-        ws2 = torch.empty(ws2_bytes + 256, dtype=torch.uint8, device=dev)
-        torch.cuda.current_stream(dev).synchronize()
-        rc = L.coral_bamgpu_merge_runs(h, os.fsencode(output), header.ctypes.data, len(header), (ws2.data_ptr() + 255) & ~255, ws2_bytes, stage_bytes, stream)
-        if rc != 0:
-            raise fail("coral_bamgpu_merge_runs", rc)
-        st, secs = (C.c_int64 * 8)(), (C.c_double * 8)()
-        _lib.check(L.coral_bamgpu_merge_stats(h, st, secs), "coral_bamgpu_merge_stats")
-        LAST_SORT_STREAM.clear()
-        LAST_SORT_STREAM.update(batches=batches, runs=int(counts[0]), phase1_seconds=t1 - t0, phase2_seconds=float(secs[0]), order_seconds=float(secs[1]),
-                                read_seconds=float(secs[2]), inflate_wait_seconds=float(secs[3]), inflate_gpu_seconds=float(secs[4]),
-                                copy_gpu_seconds=float(secs[5]), sink_seconds=float(secs[6]), steps=int(st[0]), spill_members_inflated=int(st[1]),
-                                edge_members_inflated_twice=int(st[2]), members=int(st[6]), workspace_bytes=int(ws_bytes.value), merge_workspace_bytes=ws2_bytes)
-        stats = SortStats(int(st[3]), int(st[4]), int(st[5]), int(counts[0]), int(st[7]))
-        L.coral_bamgpu_close(h)                                  # (drains the streams; only then the workspaces go)
-        h = C.c_void_p()
-        if index:
-            build_index(output, device="cpu")
-    except BaseException:
-        if h:
-            L.coral_bamgpu_close(h)
-            h = C.c_void_p()
-        if stat_of(output) not in (None, before):
-            os.remove(output)
-        raise
+        with _output_guard(output):
+            with DecodeSession(path, req, device=device, n_threads=n_threads, batch_bytes=batch_bytes, sink=Runs(spill, chunk_blocks),
+                               error_names=_ERR_NAMES) as s:
+                L, t0 = s.L, time.perf_counter()
+                s.start()
+                s.run(keep=False)                                # (the decode's CIGAR ops: not kept)
+                s.finish()
+                t1 = time.perf_counter()
+                counts = (C.c_int64 * 3)()
+                _lib.check(L.coral_bamgpu_run_table(s.h, 0, None, counts), "coral_bamgpu_run_table")
+                ws2_bytes = int(L.coral_bamgpu_merge_workspace_bytes(s.h, stage_bytes))
+                if ws2_bytes < 0:
+                    raise s.fail("coral_bamgpu_merge_workspace_bytes", ws2_bytes)
+                rc = L.coral_bamgpu_merge_runs(s.h, os.fsencode(output), header.ctypes.data, len(header), s.workspace(ws2_bytes), ws2_bytes, stage_bytes, s.stream)
+                if rc != 0:
+                    raise s.fail("coral_bamgpu_merge_runs", rc)
+                st, secs = (C.c_int64 * 8)(), (C.c_double * 8)()
+                _lib.check(L.coral_bamgpu_merge_stats(s.h, st, secs), "coral_bamgpu_merge_stats")
+                LAST_SORT_STREAM.clear()
+                LAST_SORT_STREAM.update(batches=s.batches, runs=int(counts[0]), phase1_seconds=t1 - t0, phase2_seconds=float(secs[0]), order_seconds=float(secs[1]),
+                                        read_seconds=float(secs[2]), inflate_wait_seconds=float(secs[3]), inflate_gpu_seconds=float(secs[4]),
+                                        copy_gpu_seconds=float(secs[5]), sink_seconds=float(secs[6]), steps=int(st[0]), spill_members_inflated=int(st[1]),
+                                        edge_members_inflated_twice=int(st[2]), members=int(st[6]), workspace_bytes=s.ws_bytes, merge_workspace_bytes=ws2_bytes)
+                stats = SortStats(int(st[3]), int(st[4]), int(st[5]), int(counts[0]), int(st[7]))
+            if index:                                            # (the handle is closed: the output is whole)
+                build_index(output, device="cpu")
     finally:
-        if h:
-            L.coral_bamgpu_close(h)
         if os.path.exists(spill):
             os.remove(spill)
     return stats

@@ -2,16 +2,15 @@
 driven through the C ABI, and the test data that more than one module decodes.  (The plain-Python reader the expectations come
 from is tests/bamfile.py, which imports nothing from here or from coral_amd.)"""
 import contextlib
-import ctypes as C
 import json
 import os
-import types
 
 import numpy as np
 import pytest
 import torch
 
 from coral_amd import _lib, bam, synth
+from coral_amd.decode_session import DecodeSession, open_handle
 from tests.bamfile import D, EQ, H, I, M, N, S, X, read_bam, restate_read_qc
 
 PIPELINES = ["host", pytest.param("gpu", marks=pytest.mark.gpu)]
@@ -91,56 +90,32 @@ def _ok(L, step, rc):
     assert rc == CORAL_OK, "%s: %d, %s" % (step, rc, L.coral_bam_last_error().decode())
 
 
-def gpu_open_only(path, n_threads=1, batch_bytes=0, **request):
-    """coral_bamgpu_open_request alone (no GPU work) -> (rc, handle, ws_bytes, message); a handle that was granted is closed."""
-    L = _lib.lib()
-    req, h, ws_bytes = _lib.bam_request(**request), C.c_void_p(), C.c_int64(0)
-    rc = L.coral_bamgpu_open_request(path.encode(), n_threads, batch_bytes, C.byref(req), C.byref(h), C.byref(ws_bytes))
+def gpu_open_only(path, n_threads=1, batch_bytes=0, sink=None, **request):
+    """decode_session.open_handle alone (no GPU work) -> (rc, handle, ws_bytes, message); a handle that was granted is closed."""
+    L, req = _lib.lib(), _lib.bam_request(**request)
+    rc, h, ws_bytes = open_handle(L, path, n_threads, batch_bytes, req, sink)
     message = L.coral_bam_last_error().decode()
     if h.value is not None:
         L.coral_bamgpu_close(h)
-    return rc, h.value, ws_bytes.value, message
+    return rc, h.value, ws_bytes, message
 
 
 @contextlib.contextmanager
-def gpu_decode_started(path, n_threads=2, batch_bytes=0, **request):
-    """A GPU decode opened and started, closed on every way out.  Yields L, h (the decoder handle), stream, dev, ws_bytes and
-    pieces (the CIGAR piece tensors: the caller appends, they and the workspace live until the decoder is closed).  The order
-    is that of bam._decode_gpu: the workspace may be a recycled block that the current stream still writes, so that stream is
-    drained before the decoder's own streams start on it, and close drains the decoder before the tensors go."""
-    L = _lib.lib()
-    dev = torch.device("cuda:0")
-    torch.cuda.set_device(dev)
-    req, h, ws_bytes = _lib.bam_request(**request), C.c_void_p(), C.c_int64(0)
-    _ok(L, "open_request", L.coral_bamgpu_open_request(path.encode(), n_threads, batch_bytes, C.byref(req), C.byref(h), C.byref(ws_bytes)))
-    d = types.SimpleNamespace(L=L, h=h, dev=dev, stream=torch.cuda.current_stream(dev).cuda_stream, ws_bytes=int(ws_bytes.value), pieces=[])
-    ws = None
-    try:
-        ws = torch.empty(d.ws_bytes + 256, dtype=torch.uint8, device=dev)
-        torch.cuda.current_stream(dev).synchronize()
-        _ok(L, "start", L.coral_bamgpu_start(h, (ws.data_ptr() + 255) & ~255, d.ws_bytes))
+def gpu_decode_started(path, n_threads=2, batch_bytes=0, sink=None, **request):
+    """A GPU decode opened and started, closed on every way out: yields the DecodeSession (L, h, stream, dev, ws_bytes, pieces;
+    its rules are the class's), on which the caller steps next() / emit()."""
+    with DecodeSession(path, _lib.bam_request(**request), device="cuda:0", n_threads=n_threads, batch_bytes=batch_bytes, sink=sink) as d:
+        d.start()
         yield d
-    finally:
-        assert L.coral_bamgpu_close(h) == CORAL_OK
-        del ws                                      # (not before: the decoder's kernels write it until close has drained them)
 
 
 @contextlib.contextmanager
-def gpu_decode(path, n_threads=2, batch_bytes=0, **request):
-    """A whole GPU decode: every batch parsed and emitted, finished; yields what gpu_decode_started yields plus dh (the host
+def gpu_decode(path, n_threads=2, batch_bytes=0, sink=None, **request):
+    """A whole GPU decode: every batch parsed and emitted, finished; yields what gpu_decode_started yields, with dh (the host
     handle that the coral_bam_*_result calls take) and batches."""
-    with gpu_decode_started(path, n_threads, batch_bytes, **request) as d:
-        L, out, d.batches = d.L, (C.c_int64 * 4)(), 0
-        while True:
-            _ok(L, "next", L.coral_bamgpu_next(d.h, out, d.stream))
-            if not out[2]:
-                break
-            d.pieces.append(torch.empty(max(int(out[1]), 1), dtype=torch.int32, device=d.dev))
-            _ok(L, "emit", L.coral_bamgpu_emit(d.h, d.pieces[-1].data_ptr(), None, d.stream))
-            d.batches += 1
-        _ok(L, "finish", L.coral_bamgpu_finish(d.h, d.stream))
-        d.dh = C.c_void_p()
-        _ok(L, "host", L.coral_bamgpu_host(d.h, C.byref(d.dh)))
+    with gpu_decode_started(path, n_threads, batch_bytes, sink, **request) as d:
+        d.run()
+        d.finish()
         yield d
 
 

@@ -7,7 +7,6 @@ import os
 
 import numpy as np
 import pytest
-import torch
 
 from coral_amd import _lib, bam
 from tests.decode_support import (CORAL_ERR_ARG, CORAL_OK, DEVICE, PIPELINES, assert_qc_equals_restatement as assert_equal,
@@ -183,18 +182,10 @@ def test_gpu_finish_before_the_last_batch_is_refused(case):
         def refused():
             return L.coral_bamgpu_finish(h, stream) == CORAL_ERR_ARG and "not finished" in L.coral_bam_last_error().decode()
         assert refused()                                         # no batch has been parsed
-        out, batches = (C.c_int64 * 4)(), 0
-        while True:
-            assert L.coral_bamgpu_next(h, out, stream) == CORAL_OK
-            if not out[2]:
-                break
+        while d.next() is not None:
             assert refused()                                     # a batch is between next and emit
-            d.pieces.append(torch.empty(max(int(out[1]), 1), dtype=torch.int32, device=d.dev))
-            assert L.coral_bamgpu_emit(h, d.pieces[-1].data_ptr(), None, stream) == CORAL_OK
-            batches += 1
-        assert batches >= 3
-        assert L.coral_bamgpu_finish(h, stream) == CORAL_OK
-        dh, counts = C.c_void_p(), np.zeros(segs.shape[1], dtype=np.int64)
-        assert L.coral_bamgpu_host(h, C.byref(dh)) == CORAL_OK
+            d.emit()
+        assert d.batches >= 3
+        dh, counts = d.finish(), np.zeros(segs.shape[1], dtype=np.int64)
         assert L.coral_bam_coverage_result(dh, len(counts), counts.ctypes.data) == CORAL_OK
         assert np.array_equal(counts, want)

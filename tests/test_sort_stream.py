@@ -11,15 +11,14 @@ import ctypes as C
 import gzip
 import os
 import struct
-import types
 
 import numpy as np
 import pytest
-import torch
 
 from coral_amd import CoRAL, _lib, bam
+from coral_amd.decode_session import Runs
 from tests.bamfile import bgzf_blocks, parse, read_bam
-from tests.decode_support import CORAL_ERR_ARG, CORAL_OK, _ok, assert_same_records, gpu_open_only
+from tests.decode_support import CORAL_ERR_ARG, CORAL_OK, _ok, assert_same_records, gpu_decode, gpu_open_only
 from tests.test_extract_reads import write_raw
 from tests.test_extract_records import EOF_BLOCK, SMALL_BATCH, SMALLEST, bytes_of, gunzip, selected
 from tests.test_merge_plan import plan, smallest_stage
@@ -89,51 +88,24 @@ def plan_inputs(runs):
 # ---- the C ABI: phase 1 alone, and the merge on its handle ---------------------------------------------------------------------------
 @contextlib.contextmanager
 def runs_decode(path, spill, batch_bytes=SMALL_BATCH, chunk_blocks=0, exclude_flags=0, record_filter=None):
-    """open_request_to_runs, the batches and `finish`; yields L, h, stream, dev, dh, the run table (rows of first record, records,
-    inflated bytes, file offset) and counts (runs, records, spill bytes).  Closed on every way out, the workspace behind that."""
-    L = _lib.lib()
-    dev = torch.device(GPU)
-    torch.cuda.set_device(dev)
-    req = _lib.bam_request(keep=record_filter, reads=(exclude_flags, None, None, 2))
-    h, ws_bytes = C.c_void_p(), C.c_int64(0)
-    _ok(L, "open_request_to_runs", L.coral_bamgpu_open_request_to_runs(path.encode(), 2, batch_bytes, C.byref(req), os.fsencode(spill), chunk_blocks, C.byref(h), C.byref(ws_bytes)))
-    d = types.SimpleNamespace(L=L, h=h, dev=dev, stream=torch.cuda.current_stream(dev).cuda_stream, ws_bytes=int(ws_bytes.value), keep=[])
-    ws = None
-    try:
-        ws = torch.empty(d.ws_bytes + 256, dtype=torch.uint8, device=dev)
-        torch.cuda.current_stream(dev).synchronize()
-        _ok(L, "start", L.coral_bamgpu_start(h, (ws.data_ptr() + 255) & ~255, d.ws_bytes))
-        out = (C.c_int64 * 4)()
-        while True:
-            _ok(L, "next", L.coral_bamgpu_next(h, out, d.stream))
-            if not out[2]:
-                break
-            d.keep.append(torch.empty(max(int(out[1]), 1), dtype=torch.int32, device=dev))
-            _ok(L, "emit", L.coral_bamgpu_emit(h, d.keep[-1].data_ptr(), None, d.stream))
-        _ok(L, "finish", L.coral_bamgpu_finish(h, d.stream))
-        d.dh = C.c_void_p()
-        _ok(L, "host", L.coral_bamgpu_host(h, C.byref(d.dh)))
-        counts = (C.c_int64 * 3)()
-        _ok(L, "run_table", L.coral_bamgpu_run_table(h, 0, None, counts))
+    """open_request_to_runs, the batches and `finish`; yields the DecodeSession (L, h, stream, dev, dh) with the run table (rows of
+    first record, records, inflated bytes, file offset) and counts (runs, records, spill bytes).  Closed on every way out."""
+    with gpu_decode(path, 2, batch_bytes, Runs(spill, chunk_blocks), keep=record_filter, reads=(exclude_flags, None, None, 2)) as d:
+        L, counts = d.L, (C.c_int64 * 3)()
+        _ok(L, "run_table", L.coral_bamgpu_run_table(d.h, 0, None, counts))
         table = np.full((counts[0] + 1, 4), -1, dtype=np.int64)
-        _ok(L, "run_table", L.coral_bamgpu_run_table(h, counts[0], table.ctypes.data, counts))
+        _ok(L, "run_table", L.coral_bamgpu_run_table(d.h, counts[0], table.ctypes.data, counts))
         assert table[-1].tolist() == [-1] * 4
         d.table, d.counts = table[:-1], [int(c) for c in counts]
         yield d
-    finally:
-        assert L.coral_bamgpu_close(h) == CORAL_OK
-        del ws
 
 
 def merge_runs(d, out, header, stage_bytes=0):
     L = d.L
     need = int(L.coral_bamgpu_merge_workspace_bytes(d.h, stage_bytes))
     assert need > 0, L.coral_bam_last_error().decode()
-    ws2 = torch.empty(need + 256, dtype=torch.uint8, device=d.dev)
-    torch.cuda.current_stream(d.dev).synchronize()
     head = np.frombuffer(header, dtype=np.uint8)
-    rc = L.coral_bamgpu_merge_runs(d.h, os.fsencode(out), head.ctypes.data, len(head), (ws2.data_ptr() + 255) & ~255, need, stage_bytes, d.stream)
-    d.keep.append(ws2)                                           # (until close)
+    rc = L.coral_bamgpu_merge_runs(d.h, os.fsencode(out), head.ctypes.data, len(head), d.workspace(need), need, stage_bytes, d.stream)
     return rc, L.coral_bam_last_error().decode()
 
 

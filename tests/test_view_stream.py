@@ -13,8 +13,9 @@ import pytest
 import torch  # noqa: F401
 
 from coral_amd import CoRAL, _lib, bam, synth
+from coral_amd.decode_session import BamFile, TextFile, open_handle
 from tests.bamfile import bgzf_blocks, parse, read_bam
-from tests.decode_support import CORAL_ERR_ARG, CORAL_OK, _ok, _pipeline_by_device, assert_same_records  # noqa: F401
+from tests.decode_support import CORAL_ERR_ARG, CORAL_OK, _ok, _pipeline_by_device, assert_same_records, gpu_decode_started  # noqa: F401
 from tests.test_extract_reads import fastq_of, patch_codes, qual_of, write_raw
 from tests.test_extract_records import EOF_BLOCK, REGIONS, SMALL_BATCH, SMALLEST, edge_record, more_alignments, want_records
 
@@ -302,40 +303,19 @@ def view_of(src, out, *args, **kw):
 # ---- 8. nothing is kept on the host (the C ABI) ----------------------------------------------------------------------------------
 def open_to_file(path, out_path, header, chunk_blocks=0, batch_bytes=SMALL_BATCH, **request):
     """coral_bamgpu_open_request_to_file alone -> (rc, handle, ws_bytes, message, the request - it owns the arrays)."""
-    L = _lib.lib()
-    req, h, ws_bytes = _lib.bam_request(**request), C.c_void_p(), C.c_int64(0)
-    head = None if header is None else np.frombuffer(header, dtype=np.uint8)
-    rc = L.coral_bamgpu_open_request_to_file(path.encode(), 2, batch_bytes, C.byref(req), None if out_path is None else os.fsencode(out_path),
-                                             None if head is None else head.ctypes.data, 0 if head is None else len(head), chunk_blocks,
-                                             C.byref(h), C.byref(ws_bytes))
-    return rc, h, int(ws_bytes.value), L.coral_bam_last_error().decode(), (req, head)
+    L, req = _lib.lib(), _lib.bam_request(**request)
+    rc, h, ws_bytes = open_handle(L, path, 2, batch_bytes, req, BamFile(out_path, header, chunk_blocks))
+    return rc, h, ws_bytes, L.coral_bam_last_error().decode(), req
 
 
 @pytest.mark.gpu
 def test_the_c_abi_keeps_nothing_on_the_host(case, tmp_path):
     L, out = _lib.lib(), str(tmp_path / "abi.bam")
     names = sorted({"huge", "z", name_of_size(BLOCK + 1)})
-    rc, h, ws_bytes, message, keep = open_to_file(case["path"], out, case["header"], 2, reads=(0, None, [n.encode() for n in names], 2))
-    assert rc == CORAL_OK, message
-    dev = torch.device(GPU)
-    torch.cuda.set_device(dev)
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    ws = torch.empty(ws_bytes + 256, dtype=torch.uint8, device=dev)
-    torch.cuda.current_stream(dev).synchronize()
-    pieces = []
-    try:
-        _ok(L, "start", L.coral_bamgpu_start(h, (ws.data_ptr() + 255) & ~255, ws_bytes))
-        nxt = (C.c_int64 * 4)()
-        while True:
-            _ok(L, "next", L.coral_bamgpu_next(h, nxt, stream))
-            if not nxt[2]:
-                break
-            pieces.append(torch.empty(max(int(nxt[1]), 1), dtype=torch.int32, device=dev))
-            _ok(L, "emit", L.coral_bamgpu_emit(h, pieces[-1].data_ptr(), None, stream))
+    with gpu_decode_started(case["path"], 2, SMALL_BATCH, BamFile(out, case["header"], 2), reads=(0, None, [n.encode() for n in names], 2)) as d:
+        d.run()
         assert read_file(out)[-28:] != EOF_BLOCK                 # not before `finish`
-        _ok(L, "finish", L.coral_bamgpu_finish(h, stream))
-        dh = C.c_void_p()
-        _ok(L, "host", L.coral_bamgpu_host(h, C.byref(dh)))
+        dh, h = d.finish(), d.h
         blobs = want_records(case, None, set(names))[1]
         sz, stats = (C.c_int64 * 2)(), (C.c_int64 * 4)()
         _ok(L, "reads_sizes", L.coral_bam_reads_sizes(dh, sz))
@@ -346,9 +326,6 @@ def test_the_c_abi_keeps_nothing_on_the_host(case, tmp_path):
         raw = read_file(out)
         assert list(stats) == [3, int(sz[1]), len(raw), len(members(raw))]
         assert gzip.decompress(raw) == case["header"] + b"".join(blobs)
-    finally:
-        assert L.coral_bamgpu_close(h) == CORAL_OK
-        del ws
 
 
 # ---- 9. refusals at open (no GPU work) -------------------------------------------------------------------------------------------
@@ -456,8 +433,7 @@ def test_fastq_output_argument_rules(case, tmp_path):
     L = _lib.lib()
     for request, out_path, word in ((dict(reads=(0, None, None, 2)), out, "want_reads"), (dict(), out, "want_reads"), (dict(reads=(0, None, None, 1), world=2), out, "world"),
                                     (dict(reads=(0, None, None, 1)), None, "path"), (dict(reads=(0, None, None, 1)), str(tmp_path / "no_dir" / "x"), "cannot create")):
-        req, h, ws_bytes = _lib.bam_request(**request), C.c_void_p(), C.c_int64(0)
-        rc = L.coral_bamgpu_open_request_to_text(case["path"].encode(), 1, 0, C.byref(req), None if out_path is None else os.fsencode(out_path), C.byref(h), C.byref(ws_bytes))
+        rc, h, ws_bytes = open_handle(L, case["path"], 1, 0, _lib.bam_request(**request), TextFile(out_path))
         assert rc == CORAL_ERR_ARG and h.value is None and word in L.coral_bam_last_error().decode(), (request, L.coral_bam_last_error().decode())
     assert not os.path.exists(out)
     a = CoRAL.build_parser().parse_args(["fastq", "--lr_bam", "x.bam", "--output", "o.fastq", "--stream"])
