@@ -9,7 +9,8 @@ The `reconstruct` mode and the `hsr` mode (§8(f) item 3) run on
 regions, pysam's count_coverage as a table) and `depth` (read depth per fixed-size bin of every contig, the table a copy-number
 caller starts from), `fastq` (selected reads as FASTQ, by regions or read names), `view` (the same selection as a BAM file of
 the records themselves, with its index on request) and `sort` (the kept records in coordinate order as a BAM file, with its
-index on request: lines 42-50 of the reference's scripts/align_nanopore_reads.sh from one decode); the other modes of the
+index on request: lines 42-50 of the reference's scripts/align_nanopore_reads.sh from one decode) and `import` (the mapper's
+SAM text as the BAM file `sort` opens: line 38 of that script); the other modes of the
 reference (seed, plot, cycle2bed) are untouched and are delegated to the reference's own modules when they are
 importable (set CORAL_REFERENCE_SRC to the reference's src/ directory).  The cycle-decomposition step after the graph build is the
 reference's (Gurobi); it runs on the object this module returns.
@@ -142,7 +143,15 @@ def build_parser():
     sp.add_argument("--tmp_dir", help="With --stream: directory of the spill file <output's name>.runs.tmp (default: the output's directory).")
     sp.add_argument("--output", help="Name of the sorted BAM file.", required=True)
     sp.add_argument("--device", help="GPU to use ('cpu': the host pipeline).", default="cuda:0")
-    for p in (rp, hp, qp, pp, dp, fp, vp, sp):
+    mp = sub.add_parser("import", help="Write a mapper's SAM text as a BAM file, its records encoded on the GPU.")
+    mp.add_argument("--sam", help="SAM text; '-' reads standard input, so that the mapper pipes into it.", required=True)
+    mp.add_argument("--output", help="Name of the BAM file.", required=True)
+    mp.add_argument("--level", help="With --device cpu: compression level of the BAM file, 0..9 (the GPU path deflates on the device at its one setting).",
+                    type=int, default=1)
+    mp.add_argument("--gpu_compress", help="With --device cpu: deflate the BAM file's BGZF blocks on the GPU (cuda:0) instead of on the host; --level must be 1.",
+                    action='store_true')
+    mp.add_argument("--device", help="GPU to use ('cpu': the host's rule book, one thread, the whole text in memory).", default="cuda:0")
+    for p in (rp, hp, qp, pp, dp, fp, vp, sp, mp):
         add_filter_arguments(p)
     for mode in ("seed", "plot", "cycle2bed"):
         sub.add_parser(mode, help="(reference implementation; not part of the MI355X path)", add_help=False)
@@ -322,6 +331,17 @@ def sort_mode(args):
     return out
 
 
+def import_mode(args):
+    """The mapper's SAM text as a BAM file (bam.import_sam): `winnowmap ... | samtools view -bS > x.bam`, line 38 of the
+    reference's scripts/align_nanopore_reads.sh, with the --filter_* arguments as a view's tests."""
+    from coral_amd import bam
+    on_gpu = args.device != "cpu"
+    st = bam.import_sam(args.sam, args.output, record_filter=record_filter_of(args), device=args.device, level=1 if on_gpu else args.level,
+                        write_device=None if on_gpu or not args.gpu_compress else "cuda:0")
+    print("Wrote %s (%d records of %d lines, %d dropped)" % (args.output, st.records, st.lines, st.dropped))
+    return args.output
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     if argv and argv[0] in ("seed", "plot", "cycle2bed"):
@@ -359,6 +379,8 @@ def main(argv=None):
         return view_mode(args)
     if args.mode == "sort":
         return sort_mode(args)
+    if args.mode == "import":
+        return import_mode(args)
     parser.print_help()
     return None
 

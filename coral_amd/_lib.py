@@ -206,6 +206,12 @@ def lib():
     L.coral_bgzf_deflate.argtypes = [P, P, C.c_int32, P, P, P, C.c_int64, P]
     L.coral_bgzf_pack.argtypes = [P, P, C.c_int32, P, P, P, C.c_int64, P]
     L.coral_bgzf_write_gpu.argtypes = [C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int32, P, C.c_int64, P]
+    L.coral_sam_header.argtypes = [P, C.c_int64, C.POINTER(C.c_int64), P, P, P, P]
+    L.coral_sam_encode.argtypes = [P, C.c_int64, C.c_int64, P, P, P, C.c_int32, C.c_int32, P, P, C.c_int64, C.POINTER(C.c_int64)]
+    L.coral_samgpu_import.argtypes = [C.c_int32, P, C.c_int64, C.c_int64, C.c_char_p, P, C.c_int64, P, P, P, C.c_int32, C.c_int32, P, C.c_int64, C.c_int32,
+                                      P, C.c_int64, P, C.POINTER(C.c_int64), C.POINTER(C.c_double)]
+    L.coral_samgpu_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64]
+    L.coral_samgpu_workspace_bytes.restype = C.c_int64
     for name in ("coral_bgzf_deflate_scratch_bytes", "coral_bgzf_pack_scratch_bytes"):
         getattr(L, name).argtypes = [C.c_int32]
         getattr(L, name).restype = C.c_int64

@@ -1348,6 +1348,158 @@ def sort_bam_stream(path: str, output: str, *, index: bool = True, record_filter
 
 
 # ----------------------------------------------------------------------------------------------
+# import: a mapper's SAM text as a BAM file (coral_sam_core.h: htslib's sam_parse1 + bam_write1)
+# ----------------------------------------------------------------------------------------------
+ImportStats = collections.namedtuple("ImportStats", "lines records dropped text_bytes bytes file_bytes members batches seconds")
+LAST_IMPORT = {}                                                 # what the last import_sam on a GPU did: coral_samgpu_import's seconds and fix-ups
+
+
+class SamHeader(collections.namedtuple("SamHeader", "bam names name_off slots n_ref n_slots text_bytes n_lines")):
+    """What coral_sam_header makes of a SAM text's leading ``@`` lines: ``bam`` the inflated BAM header (uint8), the contig table
+    (``names`` back to back, ``name_off`` int64 [n_ref + 1], ``slots`` uint32 [n_slots]), and how many bytes and lines of the
+    text the header is."""
+
+
+def _sam_header(text) -> SamHeader:
+    L = _lib.lib()
+    buf = np.frombuffer(bytes(text), dtype=np.uint8)
+    sizes = (C.c_int64 * 6)()
+    rc = L.coral_sam_header(buf.ctypes.data if len(buf) else None, len(buf), sizes, None, None, None, None)
+    if rc != 0:
+        raise _sam_error("coral_sam_header", rc)
+    bam, names = np.zeros(int(sizes[0]), dtype=np.uint8), np.zeros(int(sizes[2]) + 1, dtype=np.uint8)
+    name_off, slots = np.zeros(int(sizes[1]) + 1, dtype=np.int64), np.zeros(int(sizes[3]) + 1, dtype=np.uint32)
+    rc = L.coral_sam_header(buf.ctypes.data if len(buf) else None, len(buf), sizes, bam.ctypes.data, names.ctypes.data, name_off.ctypes.data, slots.ctypes.data)
+    if rc != 0:
+        raise _sam_error("coral_sam_header", rc)
+    return SamHeader(bam, names, name_off, slots, int(sizes[1]), int(sizes[3]), int(sizes[4]), int(sizes[5]))
+
+
+def _sam_error(what: str, rc: int) -> _lib.CoralHipError:
+    """The library's refusal as an exception; ``code`` is the C return value (-4, CORAL_ERR_FORMAT, for a refused line)."""
+    e = _lib.CoralHipError("%s failed (%d, %s): %s" % (what, rc, _ERR_NAMES.get(rc, "?"), _lib.lib().coral_bam_last_error().decode()))
+    e.code = rc
+    return e
+
+
+def sam_header_bytes(text) -> bytes:
+    """The inflated BAM header (magic, ``l_text``, the text verbatim without a NUL, ``n_ref``, the contigs of the ``@SQ`` lines in
+    their order) of a SAM text: ``text`` is bytes or str, and only its leading ``@`` lines count.  No ``@PG`` line is added."""
+    return _sam_header(text.encode() if isinstance(text, str) else text).bam.tobytes()
+
+
+def _read_sam_head(fd: int):
+    """Reads ``fd`` until the header's end is in sight -> (all bytes read, bytes of the header): the header ends in front of the
+    first line that does not begin with ``@``, or with the text."""
+    buf, at = bytearray(), 0                                     # at: the first line start not yet judged
+    while True:
+        while at < len(buf) and buf[at] == 0x40:
+            nl = buf.find(b"\n", at)
+            if nl < 0:
+                break
+            at = nl + 1
+        if at < len(buf) and buf[at] != 0x40:
+            return bytes(buf), at
+        chunk = os.read(fd, 1 << 20)
+        if not chunk:
+            return bytes(buf), len(buf)
+        buf += chunk
+
+
+def sam_encode(text, header: SamHeader, record_filter=None, first_line: int = 1):
+    """The host's rule book (coral_sam_encode): the whole record lines ``text`` (bytes) under ``header`` -> (record bytes uint8,
+    lines, records written, records dropped).  One thread; a refused line raises with ``code`` -4 and the line's number, counted
+    from ``first_line``."""
+    L = _lib.lib()
+    keep = np.array(tuple(_as_filter(record_filter) or RecordFilter()), dtype=np.int32)
+    buf = np.frombuffer(bytes(text), dtype=np.uint8)
+    n_lines = int((buf == 10).sum()) + 1
+    out = np.empty(2 * len(buf) + 36 * n_lines + 64, dtype=np.uint8)
+    counts = (C.c_int64 * 6)()
+    rc = L.coral_sam_encode(buf.ctypes.data if len(buf) else None, len(buf), int(first_line), header.names.ctypes.data, header.name_off.ctypes.data,
+                            header.slots.ctypes.data, header.n_ref, header.n_slots, keep.ctypes.data, out.ctypes.data, len(out), counts)
+    if rc != 0:
+        raise _sam_error("coral_sam_encode", rc)
+    return out[:int(counts[3])], int(counts[0]), int(counts[1]), int(counts[2])
+
+
+def import_sam(path, output: str, *, record_filter=None, device="cuda:0", batch_bytes: int = 0, chunk_blocks: int = 0, level: int = 1,
+               write_device=None) -> ImportStats:
+    """``samtools view -bS`` behind a long-read mapper: the SAM text ``path`` (``"-"``: standard input, so that the mapper pipes
+    into it; a file descriptor is taken as it is) as the BAM file ``output``.  The rules are htslib's sam_parse1 + bam_write1 as
+    coral_sam_core.h states them; a line they refuse raises ``CoralHipError`` with ``code`` -4 (CORAL_ERR_FORMAT) and the 1-based
+    line number and the field in its text - of several bad lines the lowest one -, and ``output`` is removed.
+
+    On a GPU ``device`` (coral_samgpu_import) a feeder thread reads the text into pinned buffers of ``batch_bytes`` (0: 128 MiB);
+    per batch k_sam_lines, k_sam_size, a scan and k_sam_encode make the records in HBM, and the record sink of ``view_bam``
+    deflates them where they are (``chunk_blocks`` blocks per launch, 0: 1 024): the text goes up once and only compressed bytes
+    come back.  A line longer than ``batch_bytes`` raises with ``code`` -3 (CORAL_ERR_CAPACITY).  ``level`` and ``write_device``
+    have no meaning there: the GPU compressor has one setting.
+
+    ``device="cpu"``: the same rules on one host thread (coral_sam_header, coral_sam_encode) with the whole text and all records
+    in host memory, written by ``coral_bgzf_write`` at ``level``, or deflated on the GPU ``write_device``.
+
+    The file is laid out as every writer here lays out (header, records): each part cut at 0xff00 bytes, the header ending a
+    block, the EOF block last, no ``@PG`` line added.  Its bytes depend on the text and the filter alone - not on
+    ``batch_bytes``, ``chunk_blocks`` or the run; the GPU path's file is ``coral_bgzf_write_gpu``'s of the host path's two parts.
+    ``record_filter``: lines it drops write nothing.  Mapper order cannot be indexed: ``sort_bam_stream`` is the next step.
+    Returns ``ImportStats(lines, records, dropped, text_bytes, bytes, file_bytes, members, batches, seconds)``."""
+    on_gpu = torch.device(device).type == "cuda"
+    chunk_blocks = _size_argument("chunk_blocks", chunk_blocks, 16384, "1 024")
+    batch_bytes = _size_argument("batch_bytes", batch_bytes, 1 << 30, "128 MiB")
+    if isinstance(level, bool) or not isinstance(level, numbers.Integral) or not 0 <= level <= 9:
+        raise ValueError("level must be an integer in 0..9, got %r" % (level,))
+    keep = np.array(tuple(_as_filter(record_filter) or RecordFilter()), dtype=np.int32)
+    L = _lib.lib()
+    t0 = time.perf_counter()
+    own = not isinstance(path, int)
+    fd = (0 if path == "-" else os.open(path, os.O_RDONLY)) if own else path
+    try:
+        head, n_head = _read_sam_head(fd)
+        H = _sam_header(head[:n_head])
+        lead = head[n_head:]
+        with _output_guard(output):
+            if not on_gpu:
+                pieces = [lead]
+                while True:
+                    chunk = os.read(fd, 1 << 24)
+                    if not chunk:
+                        break
+                    pieces.append(chunk)
+                text = b"".join(pieces)
+                del pieces
+                data, lines, written, dropped = sam_encode(text, H, record_filter, H.n_lines + 1)
+                rb = RecordBytes(data, np.array([0, len(data)], dtype=np.int64), header=H.bam.tobytes())
+                rb.write(output, level=level, device="cpu" if write_device is None else write_device)
+                size = os.path.getsize(output)
+                blocks = lambda n: (n + 0xfeff) // 0xff00
+                return ImportStats(lines, written, dropped, len(text), len(data), size, blocks(len(H.bam)) + blocks(len(data)) + 1, 1, time.perf_counter() - t0)
+            dev = torch.device(device)
+            torch.cuda.set_device(dev)
+            ws_bytes = int(L.coral_samgpu_workspace_bytes(batch_bytes, chunk_blocks, H.n_ref, H.n_slots, int(H.name_off[-1])))
+            if ws_bytes < 0:
+                raise _sam_error("coral_samgpu_workspace_bytes", ws_bytes)
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            stream = torch.cuda.current_stream(dev)
+            stream.synchronize()                                 # (DecodeSession's rule 1: the block may be a recycled one)
+            lead_a = np.frombuffer(lead, dtype=np.uint8)
+            stats, secs = (C.c_int64 * 9)(), (C.c_double * 4)()
+            rc = L.coral_samgpu_import(fd, lead_a.ctypes.data if len(lead_a) else None, len(lead_a), H.n_lines + 1, os.fsencode(output), H.bam.ctypes.data, len(H.bam),
+                                       H.names.ctypes.data, H.name_off.ctypes.data, H.slots.ctypes.data, H.n_ref, H.n_slots, keep.ctypes.data, batch_bytes,
+                                       chunk_blocks, ws.data_ptr(), ws_bytes, stream.cuda_stream, stats, secs)
+            stream.synchronize()                                 # (the call has waited already; `ws` is released behind it)
+            if rc != 0:
+                raise _sam_error("coral_samgpu_import(%s)" % (path,), rc)
+            LAST_IMPORT.clear()
+            LAST_IMPORT.update(seconds=float(secs[0]), feeder_wait_seconds=float(secs[1]), size_kernel_seconds=float(secs[2]), encode_kernel_seconds=float(secs[3]),
+                               float_fixups=int(stats[8]), workspace_bytes=ws_bytes)
+            return ImportStats(*(int(stats[k]) for k in range(8)), time.perf_counter() - t0)
+    finally:
+        if own and fd != 0:
+            os.close(fd)
+
+
+# ----------------------------------------------------------------------------------------------
 # BAI index (SAMv1 §5.2): built during a decode, read, queried
 # ----------------------------------------------------------------------------------------------
 _PSEUDO_BIN = 37450

@@ -39,12 +39,20 @@
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
+#include <errno.h>
+#include <unistd.h>
+
 #include <array>
+#include <chrono>
+#include <condition_variable>
+#include <mutex>
+#include <thread>
 
 #include "../../include/coral_hip.h"
 #include "coral_bam_common.h"
 #include "coral_crc32.h"
 #include "coral_inflate_core.h"
+#include "coral_sam_host.h"              // (coral_bamgpu_sam.h, included inside the namespace below, is its device side)
 
 using namespace coral_bam;
 
@@ -1023,6 +1031,7 @@ __global__ __launch_bounds__(256) void k_bam_gather(const uint8_t *__restrict__ 
 #include "coral_bamgpu_index.h"
 #include "coral_bamgpu_deflate.h"        // (no request of the decode: the BGZF writer's kernels, coral_bgzf_deflate / _write_gpu, and the
                                          //  file sink of a records request - coral_bamgpu_reads.h has included it for that)
+#include "coral_bamgpu_sam.h"            // (no request of the decode either: `import`, SAM text -> records -> the same file sink)
 
 // ---------------------------------------------------------------------------------------------
 // host side
@@ -2241,6 +2250,17 @@ extern "C" int coral_bgzf_pack(const uint8_t *slots, const uint32_t *member_byte
     }
     if (e != hipSuccess) { set_error(std::string("k_bgzf_pack: ") + hipGetErrorString(e)); return CORAL_ERR_HIP; }
     return CORAL_OK;
+}
+
+extern "C" int64_t coral_samgpu_workspace_bytes(int64_t batch_bytes, int32_t chunk_blocks, int32_t n_ref, int32_t n_slots, int64_t names_bytes) {
+    return samgpu_workspace_bytes(batch_bytes, chunk_blocks, n_ref, n_slots, names_bytes);
+}
+
+extern "C" int coral_samgpu_import(int32_t fd, const uint8_t *lead, int64_t lead_bytes, int64_t first_line, const char *out_path, const uint8_t *bam, int64_t bam_bytes,
+                                   const uint8_t *names, const int64_t *name_off, const uint32_t *slots, int32_t n_ref, int32_t n_slots, const int32_t *keep,
+                                   int64_t batch_bytes, int32_t chunk_blocks, void *workspace, int64_t workspace_bytes, void *stream, int64_t *stats, double *seconds) {
+    return samgpu_import(fd, lead, lead_bytes, first_line, out_path, bam, bam_bytes, names, name_off, slots, n_ref, n_slots, keep, batch_bytes, chunk_blocks, workspace,
+                         workspace_bytes, (hipStream_t)stream, stats, seconds);
 }
 
 extern "C" int64_t coral_bgzf_write_gpu_workspace_bytes(void) { return (int64_t)write_gpu_workspace_bytes(DEFL_CHUNK_BLOCKS); }

@@ -916,6 +916,54 @@ int coral_bgzf_write_gpu(const char *path, const uint8_t *const *parts, const in
 int64_t coral_bgzf_write_gpu_workspace_bytes(void);
 int64_t coral_bgzf_write_gpu_workspace_min_bytes(void);
 
+/* ------------------------------------------------------------------------------------------------
+ * SAM text -> BAM records (`import`): what `samtools view -bS` does to a mapper's output, by the rules of htslib's sam_parse1 +
+ * bam_write1 as coral_sam_core.h states them.  The header is the text's leading '@' lines; a record line has 11 fields and its
+ * tags; a line ends at '\n', the text's last one at the text's end too.
+ *
+ * coral_sam_header: text[0, text_bytes) begins with the header (it may hold more: the header ends in front of the first line
+ *   that does not begin with '@').  sizes[0..5] = bytes of the inflated BAM header (magic, l_text, the text verbatim, n_ref, per
+ *   @SQ line l_name, name + NUL, l_ref), n_ref, bytes of all names, slots of the contig table, bytes of the header's text, its
+ *   lines.  With bam / names / name_off / slots given (all four, of those sizes; name_off: n_ref + 1) they are filled: the
+ *   names back to back without NUL, where each starts, and an open-addressing table (a power of two of slots, 1 + the contig
+ *   or 0, linear probing from FNV-1a of the name) - the contig table of the two calls below.
+ *   CORAL_ERR_FORMAT: an @SQ line without SN / LN, a bad LN, a name given twice.
+ * coral_sam_encode: the whole lines of text[0, text_bytes), the first of which is line `first_line` (1-based) of the file ->
+ *   their records back to back at out (out_cap bytes; out == NULL: validated and counted only).  keep[4] = min_mapq,
+ *   min_seq_length, require_flags, exclude_flags: the record filter (a dropped line writes nothing).  counts[0..5] = lines,
+ *   records written, records dropped, record bytes, and on a refusal its line number and field (coral_sam_core.h: Field).
+ *   One thread; this is the rule book the device is compared against, and `import` with device "cpu".
+ *   CORAL_ERR_FORMAT: a refused line - the lowest one; the error text names the line and the field; CORAL_ERR_CAPACITY: out
+ *   is too short (2 * text_bytes + 36 * lines always suffices).
+ * coral_samgpu_import: the lines that fd delivers (a file or a pipe, read to its end; never seeked), in front of them the
+ *   lead_bytes bytes at lead (what the caller read behind the header), as the BAM file out_path: the header `bam` in blocks of
+ *   its own, all records cut at 0xff00 bytes, the EOF block - coral_bgzf_write_gpu's file of the two parts (header, records).
+ *   first_line: the file's line number of the first of them.  A feeder thread reads into two pinned buffers of batch_bytes
+ *   (0: 128 MiB; the call allocates and frees them), each batch is cut at its last '\n' and the partial line leads the next
+ *   one.  Per batch, on `stream`: k_sam_lines (newlines -> line starts), k_sam_size (one wave per line: fields, checks, filter,
+ *   bytes), a scan, k_sam_encode (one wave per line: the record at its offset), and the record sink of
+ *   coral_bamgpu_open_request_to_file deflates the bytes where they are (chunk_blocks blocks per launch, 0: 1 024).  'f' values
+ *   outside the exact fast path of the device come back as (text offset, output offset), are converted with strtof from the
+ *   pinned text and scattered in before the batch goes to the sink.  The file's bytes depend on the text and the filter alone.
+ *   workspace: coral_samgpu_workspace_bytes(batch_bytes, chunk_blocks) bytes of device memory, n_ref / n_slots being those of
+ *   the contig table; the library allocates none.  stats[0..8] = lines, records written, records dropped, text bytes, record
+ *   bytes, file bytes, members, batches, float fix-ups; seconds[0..3] = all, waiting for the feeder, the two per-line kernels
+ *   (from events, summed over the batches).  Nothing is left on `stream` when the call returns.
+ *   CORAL_ERR_FORMAT: a refused line, as coral_sam_encode (the same line and field), or a failed write; CORAL_ERR_CAPACITY: a
+ *   line longer than batch_bytes, or more float fix-ups in a batch than batch_bytes / 64; the output file is removed on any error.
+ * ------------------------------------------------------------------------------------------------ */
+int coral_sam_header(const uint8_t *text, int64_t text_bytes, int64_t *sizes, uint8_t *bam, uint8_t *names, int64_t *name_off,
+                     uint32_t *slots);
+int coral_sam_encode(const uint8_t *text, int64_t text_bytes, int64_t first_line, const uint8_t *names, const int64_t *name_off,
+                     const uint32_t *slots, int32_t n_ref, int32_t n_slots, const int32_t *keep, uint8_t *out, int64_t out_cap,
+                     int64_t *counts);
+int coral_samgpu_import(int32_t fd, const uint8_t *lead, int64_t lead_bytes, int64_t first_line, const char *out_path,
+                        const uint8_t *bam, int64_t bam_bytes, const uint8_t *names, const int64_t *name_off,
+                        const uint32_t *slots, int32_t n_ref, int32_t n_slots, const int32_t *keep, int64_t batch_bytes,
+                        int32_t chunk_blocks, void *workspace, int64_t workspace_bytes, void *stream, int64_t *stats,
+                        double *seconds);
+int64_t coral_samgpu_workspace_bytes(int64_t batch_bytes, int32_t chunk_blocks, int32_t n_ref, int32_t n_slots, int64_t names_bytes);
+
 #ifdef __cplusplus
 }
 #endif
