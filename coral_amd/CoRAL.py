@@ -10,7 +10,8 @@ regions, pysam's count_coverage as a table) and `depth` (read depth per fixed-si
 caller starts from), `fastq` (selected reads as FASTQ, by regions or read names), `view` (the same selection as a BAM file of
 the records themselves, with its index on request) and `sort` (the kept records in coordinate order as a BAM file, with its
 index on request: lines 42-50 of the reference's scripts/align_nanopore_reads.sh from one decode) and `import` (the mapper's
-SAM text as the BAM file `sort` opens: line 38 of that script); the other modes of the
+SAM text as the BAM file `sort` opens: line 38 of that script) and `cnv` (the .cns of segmented copy number and the seed
+intervals that `reconstruct` starts from: scripts/call_cnvs.sh and the seed mode, from the binned depth); the other modes of the
 reference (seed, plot, cycle2bed) are untouched and are delegated to the reference's own modules when they are
 importable (set CORAL_REFERENCE_SRC to the reference's src/ directory).  The cycle-decomposition step after the graph build is the
 reference's (Gurobi); it runs on the object this module returns.
@@ -151,7 +152,23 @@ def build_parser():
     mp.add_argument("--gpu_compress", help="With --device cpu: deflate the BAM file's BGZF blocks on the GPU (cuda:0) instead of on the host; --level must be 1.",
                     action='store_true')
     mp.add_argument("--device", help="GPU to use ('cpu': the host's rule book, one thread, the whole text in memory).", default="cuda:0")
-    for p in (rp, hp, qp, pp, dp, fp, vp, sp, mp):
+    cp = sub.add_parser("cnv", help="Call segmented copy number (.cns) and seed intervals from a sorted bam file or its binned depth.")
+    source = cp.add_mutually_exclusive_group(required=True)
+    source.add_argument("--lr_bam", help="Sorted (long read) bam file.")
+    source.add_argument("--depth", help="Binned-depth table written by the depth mode, in place of the bam file.")
+    cp.add_argument("--output", help="Name of the output file (CNVkit's .cns columns).", required=True)
+    cp.add_argument("--reference_cnn", help="Binned-depth table of a normal sample with the same bins (the depth mode's output).")
+    cp.add_argument("--bin_size", help="Bases per bin (with --lr_bam).", type=int, default=1000)
+    cp.add_argument("--levels", help="Dyadic scales of the Haar segmenter, 1..20.", type=int, default=5)
+    cp.add_argument("--fdr_q", help="False discovery rate of the breakpoint test, in (0, 1).", type=float, default=1e-4)
+    cp.add_argument("--seeds", help="Also write the CNV seed intervals (the reference's seed mode) to this bed file; needs --centromeres.")
+    cp.add_argument("--centromeres", help="Centromere bed file (chrom, start, end, band; a p row and a q row per contig).")
+    cp.add_argument("--chrom_sizes", help="Two-column file of contig lengths for --seeds (default: the bam file's header, or the depth table).")
+    cp.add_argument("--gain", help="Minimum CN of a seed segment.", type=float, default=6.0)
+    cp.add_argument("--min_seed_size", help="Minimum summed length of a seed.", type=int, default=99999)
+    cp.add_argument("--max_seg_gap", help="Maximum gap between the segments of one seed.", type=int, default=300001)
+    cp.add_argument("--device", help="GPU to use ('cpu': the host backend).", default="cuda:0")
+    for p in (rp, hp, qp, pp, dp, fp, vp, sp, mp, cp):
         add_filter_arguments(p)
     for mode in ("seed", "plot", "cycle2bed"):
         sub.add_parser(mode, help="(reference implementation; not part of the MI355X path)", add_help=False)
@@ -342,6 +359,34 @@ def import_mode(args):
     return args.output
 
 
+def cnv_mode(args):
+    """The .cns of segmented copy number (cnv.segment_depth on the binned depth) and, with --seeds, the seed bed of the reference's
+    seed mode (cnv.find_seeds): what scripts/call_cnvs.sh and `CoRAL.py seed` make for `reconstruct`."""
+    from coral_amd import bam, cnv
+    if not 1 <= args.levels <= 20:
+        raise ValueError("--levels must be in 1..20, got %r" % (args.levels,))
+    if not 0.0 < args.fdr_q < 1.0:
+        raise ValueError("--fdr_q must lie in (0, 1), got %r" % (args.fdr_q,))
+    if args.seeds and not args.centromeres:
+        raise ValueError("--seeds needs --centromeres: a bed file of the centromeres' p and q rows (none is shipped)")
+    if args.seeds and not args.output.endswith(".cns"):
+        raise ValueError("--seeds reads --output back as a .cns: its name must end in .cns, got %r" % (args.output,))
+    reference = bam.BinnedDepth.read(args.reference_cnn) if args.reference_cnn else None
+    if args.depth:
+        depth = bam.BinnedDepth.read(args.depth)
+    else:
+        depth = bam.binned_depth(args.lr_bam, args.bin_size, device=args.device, record_filter=record_filter_of(args))
+    seg = cnv.segment_depth(depth, reference, args.levels, args.fdr_q, device=args.device)
+    seg.write(args.output)
+    print("Wrote %s (%d segments of %d bins)" % (args.output, len(seg), seg.counts.get("kept", 0)))
+    if args.seeds:
+        sizes = args.chrom_sizes if args.chrom_sizes else dict(zip(depth.chroms, depth.lengths))
+        seeds = cnv.find_seeds(args.output, args.centromeres, sizes, args.gain, args.min_seed_size, args.max_seg_gap)
+        cnv.write_seeds(seeds, args.seeds)
+        print("Wrote %s (%d seeds)" % (args.seeds, len(seeds)))
+    return args.output
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     if argv and argv[0] in ("seed", "plot", "cycle2bed"):
@@ -381,6 +426,8 @@ def main(argv=None):
         return sort_mode(args)
     if args.mode == "import":
         return import_mode(args)
+    if args.mode == "cnv":
+        return cnv_mode(args)
     parser.print_help()
     return None
 

@@ -212,6 +212,14 @@ def lib():
                                       P, C.c_int64, P, C.POINTER(C.c_int64), C.POINTER(C.c_double)]
     L.coral_samgpu_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64]
     L.coral_samgpu_workspace_bytes.restype = C.c_int64
+    L.coral_cn_log2_q16.argtypes = [C.c_uint64]
+    L.coral_cn_log2_q16.restype = C.c_int32
+    L.coral_cn_fdr_cut.argtypes = [P, C.c_int64, C.c_int64, C.c_double, C.c_double]
+    L.coral_cn_fdr_cut.restype = C.c_int64
+    L.coral_cn_segment_host.argtypes = [C.c_int32, P, P, C.c_int64, P, P, P, C.c_int32, C.c_double, C.c_int64] + [P] * 7
+    L.coral_cn_segment_gpu.argtypes = [C.c_int32] + L.coral_cn_segment_host.argtypes + [P, C.c_int64, P, P]
+    L.coral_cn_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64]
+    L.coral_cn_workspace_bytes.restype = C.c_int64
     for name in ("coral_bgzf_deflate_scratch_bytes", "coral_bgzf_pack_scratch_bytes"):
         getattr(L, name).argtypes = [C.c_int32]
         getattr(L, name).restype = C.c_int64

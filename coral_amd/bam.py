@@ -760,6 +760,47 @@ class BinnedDepth:
                                  for a, b, d, l, r in zip(starts.tolist(), ends.tolist(), depth.tolist(), log2.tolist(), reads.tolist())))
         return path
 
+    @classmethod
+    def read(cls, path: str, bin_size: Optional[int] = None) -> "BinnedDepth":
+        """The table ``write`` wrote, back as a ``BinnedDepth``: contigs in the file's order (a contig without bins is not in
+        the file), a contig's length = the end of its last bin, ``bases`` = depth * the bin's length, rounded (exact below
+        2^52).  ``bin_size``: taken from the first bin that is not its contig's last - or, where every contig has one bin, the
+        longest bin - unless given.  What the file does not say (min_mapq, exclude_flags, count_deletions) is the defaults'.
+        ValueError: other columns, bins that are not ``write``'s."""
+        chroms, rows = [], {}
+        with open(path) as fp:
+            head = fp.readline().rstrip("\n").split("\t")
+            if head[:5] != ["chromosome", "start", "end", "gene", "depth"]:
+                raise ValueError("%s: not a binned-depth table (columns %r)" % (path, head))
+            reads_at = head.index("reads") if "reads" in head else -1
+            for line in fp:
+                s = line.rstrip("\n").split("\t")
+                if len(s) < 5:
+                    continue
+                if s[0] not in rows:
+                    chroms.append(s[0])
+                    rows[s[0]] = []
+                rows[s[0]].append((int(s[1]), int(s[2]), float(s[4]), int(s[reads_at]) if reads_at >= 0 else 0))
+        if bin_size is None:
+            inner = [r[1] - r[0] for c in chroms for r in rows[c][:-1]]
+            bin_size = inner[0] if inner else max([r[1] - r[0] for c in chroms for r in rows[c]], default=1)
+        bin_size = int(bin_size)
+        if bin_size < 1:
+            raise ValueError("bin_size must be at least 1, got %r" % (bin_size,))
+        lengths, bases, reads = [], [], []
+        for c in chroms:
+            length = rows[c][-1][1]
+            for k, (a, b, d, r) in enumerate(rows[c]):
+                if a != k * bin_size or b != min(a + bin_size, length):
+                    raise ValueError("%s: bin %s:%d-%d is not bin %d of bins of %d bases" % (path, c, a, b, k, bin_size))
+                bases.append(int(round(d * (b - a))))
+                reads.append(r)
+            if len(rows[c]) != (length + bin_size - 1) // bin_size:
+                raise ValueError("%s: contig %s does not end with its last bin" % (path, c))
+            lengths.append(length)
+        bin_off = np.concatenate([[0], np.cumsum([len(rows[c]) for c in chroms], dtype=np.int64)]).astype(np.int64)
+        return cls(chroms, lengths, bin_size, 0, 0x704, True, bin_off, np.array(bases, dtype=np.int64), np.array(reads, dtype=np.int64))
+
 
 def depth_parameters(bin_size, min_mapq, exclude_flags, count_deletions):
     """The parameters of a binned-depth request as ints, or ValueError: bin_size >= 1, min_mapq 0..255, exclude_flags 0..0xffff."""
@@ -1931,3 +1972,9 @@ def write_bam(rec: Records, path: str, seed: int = 0, long_cigar_as_cg: bool = T
     with open(path, "wb") as fp:
         for blk in _bgzf_blocks(bytes(out), block_size=block_size, empty_block_every=empty_block_every):
             fp.write(blk)
+
+
+# ----------------------------------------------------------------------------------------------
+# copy number from the binned depth: coral_amd/cnv.py, at hand here beside binned_depth
+# ----------------------------------------------------------------------------------------------
+from .cnv import CopyNumberSegments, call_copy_number, find_seeds, segment_depth, write_seeds      # noqa: E402,F401

@@ -964,6 +964,51 @@ int coral_samgpu_import(int32_t fd, const uint8_t *lead, int64_t lead_bytes, int
                         double *seconds);
 int64_t coral_samgpu_workspace_bytes(int64_t batch_bytes, int32_t chunk_blocks, int32_t n_ref, int32_t n_slots, int64_t names_bytes);
 
+/* ------------------------------------------------------------------------------------------------
+ * Copy number from binned depth (`cnv`): a deterministic Haar-wavelet segmenter after HaarSeg (Ben-Yaacov & Eldar 2008), in
+ * place of the segmentation of `cnvkit.py batch` in the reference's scripts/call_cnvs.sh.  Parity with CNVkit is not claimed;
+ * the rule (coral_cn_core.h) is what both backends compute, exactly:
+ *   table     n_contigs contigs; contig c has the bins bin_off[c] .. bin_off[c + 1] of bin_size bases, ceil(lengths[c] /
+ *             bin_size) of them; bases[b] int64 per bin; ref_bases: the same bins of a normal sample, or NULL; centre[c] != 0:
+ *             a centring contig.  At most 2^28 bins.
+ *   mask      a bin is a candidate when it has the full bin size and bases > 0 (with ref_bases: and ref_bases > 0).  C = the
+ *             lower median of bases over the candidate bins of the centring contigs (C_ref: of ref_bases over the same bins).
+ *             A candidate is kept when bases * 32 >= C (and ref_bases * 32 >= C_ref).  No candidate to centre on: no rows.
+ *   signal    s = L(bases) - L(C) [- (L(ref_bases) - L(C_ref))], L = coral_cn_log2_q16: e = the top bit of x, m = x << (63 - e),
+ *             16 times m * m -> one bit (1 and m = hi when hi >= 2^63, else 0 and m = hi << 1 | lo >> 63), L = e << 16 | bits.
+ *   detail    per contig over its n kept bins x, mirror-padded (x[j] = x[-j-1], x[j] = x[2n-1-j]): for level l = 1..levels,
+ *             h = 2^l <= n, c_h[k] = sum x[k..k+h-1] - sum x[k-h..k-1], k = 1..n-1, c_h[0] = c_h[n] = 0; k is a peak when
+ *             c[k] > 0, c[k] > c[k-1], c[k] >= c[k+1], or the mirrored test for c[k] < 0.
+ *   noise     d = the lower median of |c_1[k]|, k = 1..n-1; sigma = 1.4826 * d / sqrt(2).
+ *   cut       coral_cn_fdr_cut on a (contig, level)'s peak magnitudes, descending: p_i = erfc(m_i / (sqrt(2h) * sigma *
+ *             sqrt(2))), the largest 1-based i with p_i <= q * i / M gives the cut m_i (INT64_MAX: none; sigma == 0: 1, every
+ *             peak).  The one floating-point step; a host function for both backends.
+ *   unify     levels in rising order; a peak of at least its cut is added unless the set of the earlier levels holds a
+ *             breakpoint within 2^(l-1) kept bins.
+ *   rows      each contig's kept bins cut at the breakpoints (k starts a segment), in order: contig, start of the first bin,
+ *             end of the last, probes = bins, sum_s = the sum of s (log2 = sum_s / (probes * 65536)), sum_bases.
+ * counts[0..4] (8 entries) = rows, kept bins, C, C_ref, breakpoints.
+ * coral_cn_segment_host: one thread, host arrays.  coral_cn_segment_gpu: the same arrays go up to `device`; kernels k_cn_* /
+ *   k_haar_* and hipcub scans and radix sorts on `stream` in `workspace` (device memory, coral_cn_workspace_bytes; the
+ *   library allocates none), three host waits in all (noise and peak counts, sorted magnitudes, rows); nothing is left on
+ *   `stream`.  seconds[0..5] (or NULL) = upload, centre + signal + compaction + prefix sums, noise, the levels' peaks and
+ *   sorts, the cuts on the host, unify + rows + download (from events).  Identical rows and counts.
+ *   CORAL_ERR_ARG: a missing array, bins that do not fit the contigs, levels outside 1..20, fdr_q outside (0, 1), too small a
+ *   workspace; CORAL_ERR_CAPACITY: more rows than row_cap - counts[0] then holds a row_cap that suffices.
+ * ------------------------------------------------------------------------------------------------ */
+int32_t coral_cn_log2_q16(uint64_t x);
+int64_t coral_cn_fdr_cut(const int64_t *mags_desc, int64_t n_peaks, int64_t h, double sigma, double q);
+int coral_cn_segment_host(int32_t n_contigs, const int64_t *bin_off, const int64_t *lengths, int64_t bin_size, const int64_t *bases,
+                          const int64_t *ref_bases, const uint8_t *centre, int32_t levels, double fdr_q, int64_t row_cap,
+                          int32_t *row_contig, int64_t *row_start, int64_t *row_end, int64_t *row_probes, int64_t *row_sum_s,
+                          int64_t *row_sum_bases, int64_t *counts);
+int coral_cn_segment_gpu(int32_t device, int32_t n_contigs, const int64_t *bin_off, const int64_t *lengths, int64_t bin_size,
+                         const int64_t *bases, const int64_t *ref_bases, const uint8_t *centre, int32_t levels, double fdr_q,
+                         int64_t row_cap, int32_t *row_contig, int64_t *row_start, int64_t *row_end, int64_t *row_probes,
+                         int64_t *row_sum_s, int64_t *row_sum_bases, int64_t *counts, void *workspace, int64_t workspace_bytes,
+                         void *stream, double *seconds);
+int64_t coral_cn_workspace_bytes(int64_t n_bins, int32_t n_contigs, int32_t levels, int32_t has_reference, int64_t row_cap);
+
 #ifdef __cplusplus
 }
 #endif
