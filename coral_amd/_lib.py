@@ -26,10 +26,16 @@ class coral_bam_request_t(C.Structure):
                 ("n_seg", C.c_int32), ("seg_tid", C.c_void_p), ("seg_start", C.c_void_p), ("seg_end", C.c_void_p),
                 ("quality_threshold", C.c_int32), ("read_callback", C.c_int32), ("want_index", C.c_int32), ("want_qc", C.c_int32),
                 ("per_base", C.c_int32), ("depth_bin", C.c_int32), ("depth_min_mapq", C.c_int32), ("depth_exclude_flags", C.c_int32),
-                ("depth_count_deletions", C.c_int32), ("want_reads", C.c_int32), ("reads_exclude_flags", C.c_int32),
+                ("depth_count_deletions", C.c_int32), ("want_reads", C.c_int32), ("reads_order", C.c_int32), ("reads_exclude_flags", C.c_int32),
                 ("reads_n_seg", C.c_int32), ("reads_seg_tid", C.c_void_p), ("reads_seg_start", C.c_void_p), ("reads_seg_end", C.c_void_p),
                 ("reads_n_names", C.c_int32), ("reads_names", C.c_void_p), ("reads_name_off", C.c_void_p), ("keep_min_mapq", C.c_int32), ("keep_min_seq_length", C.c_int32),
                 ("keep_require_flags", C.c_int32), ("keep_exclude_flags", C.c_int32)]
+
+
+SINK_HOST, SINK_TEXT, SINK_BAM, SINK_RUNS = range(4)         # CORAL_SINK_*: coral_bam_sink_t.kind
+
+class coral_bam_sink_t(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("path", C.c_char_p), ("header", C.c_void_p), ("header_bytes", C.c_int64), ("chunk_blocks", C.c_int32)]
 
 
 def bam_request(rank: int = 0, world: int = 1, spans=None, coverage=None, index: bool = False, qc: bool = False,
@@ -39,12 +45,10 @@ def bam_request(rank: int = 0, world: int = 1, spans=None, coverage=None, index:
     pileup), ``depth`` = (bin size, min_mapq, exclude_flags, count_deletions) or None: the binned-depth request, ``keep`` = (min_mapq, min_seq_length, require_flags, exclude_flags) (a
     ``bam.RecordFilter`` is one) or None: the record filter, ``reads`` = (exclude_flags, segments int32 [3][S] or None, names = a list
     of bytes or None[, mode[, order]]) or None: the reads request (no segment / no name: no such limit; mode 1, the default: FASTQ
-    text, 2: the records' own bytes; order 0, the default: file order, 1: coordinate order - not a field of the struct but the
-    ``reads_order`` argument of the _ordered entry points, kept as the attribute ``reads_order``).  The struct keeps the contiguous
+    text, 2: the records' own bytes; order 0, the default: file order, 1: coordinate order).  The struct keeps the contiguous
     arrays it points into alive; the rules are the library's to check."""
     req = coral_bam_request_t(rank=rank, world=world, n_spans=-1, n_seg=-1, want_index=int(index), want_qc=int(qc), per_base=int(per_base))
     req.arrays = []
-    req.reads_order = int(reads[4]) if reads is not None and len(reads) > 4 else 0
     if depth is not None:
         req.depth_bin, req.depth_min_mapq, req.depth_exclude_flags, req.depth_count_deletions = (int(v) for v in depth)
     if keep is not None:
@@ -56,6 +60,7 @@ def bam_request(rank: int = 0, world: int = 1, spans=None, coverage=None, index:
     if reads is not None:                    # (in front of the coverage request: its segment rows stay the last arrays)
         exclude_flags, segs, names = reads[:3]
         req.want_reads, req.reads_exclude_flags = (int(reads[3]) if len(reads) > 3 else 1), int(exclude_flags)
+        req.reads_order = int(reads[4]) if len(reads) > 4 else 0
         if segs is not None:
             segs = np.asarray(segs, dtype=np.int32).reshape(3, -1)
             req.reads_n_seg = segs.shape[1]
@@ -166,7 +171,6 @@ def lib():
     L.coral_bam_decode_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_double)]
     L.coral_bam_write.argtypes = [C.c_char_p, C.c_int64] + [P] * 9 + [P, P, P, P, P, C.c_int64, P, P, P, C.c_int32, P, P, C.c_uint32,
                                                                         C.c_int32, C.c_int32]
-    L.coral_bamgpu_open.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
     L.coral_bamgpu_start.argtypes = [C.c_void_p, P, C.c_int64]
     L.coral_bamgpu_next.argtypes = [C.c_void_p, C.POINTER(C.c_int64), P]
     L.coral_bamgpu_emit.argtypes = [C.c_void_p, P, P, P]
@@ -187,15 +191,9 @@ def lib():
     L.coral_bam_reads_sizes.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
     L.coral_bam_reads_fill.argtypes = [C.c_void_p, P, P]
     L.coral_bgzf_write.argtypes = [C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int32, C.c_int32, C.c_int32]
-    L.coral_bamgpu_open_request.argtypes = [C.c_char_p, C.c_int32, C.c_int64, Q, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
+    L.coral_bamgpu_open_request.argtypes = [C.c_char_p, C.c_int32, C.c_int64, Q, C.POINTER(coral_bam_sink_t), C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
     L.coral_bamgpu_finish.argtypes = [C.c_void_p, P]
-    L.coral_bam_decode_request_ordered.argtypes = [C.c_char_p, C.c_int32, Q, C.c_int32, C.POINTER(C.c_void_p)]
-    L.coral_bamgpu_open_request_ordered.argtypes = [C.c_char_p, C.c_int32, C.c_int64, Q, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
-    L.coral_bamgpu_open_request_to_file.argtypes = [C.c_char_p, C.c_int32, C.c_int64, Q, C.c_char_p, P, C.c_int64, C.c_int32, C.POINTER(C.c_void_p),
-                                                    C.POINTER(C.c_int64)]
-    L.coral_bamgpu_open_request_to_text.argtypes = [C.c_char_p, C.c_int32, C.c_int64, Q, C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
     L.coral_bamgpu_sink_stats.argtypes =[C.c_void_p, C.POINTER(C.c_int64)]
-    L.coral_bamgpu_open_request_to_runs.argtypes = [C.c_char_p, C.c_int32, C.c_int64, Q, C.c_char_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
     L.coral_bamgpu_run_table.argtypes = [C.c_void_p, C.c_int64, P, C.POINTER(C.c_int64)]
     L.coral_bamgpu_merge_workspace_bytes.argtypes = [C.c_void_p, C.c_int64]
     L.coral_bamgpu_merge_workspace_bytes.restype = C.c_int64

@@ -250,10 +250,7 @@ def _decode(path: str, device, *, n_threads: Optional[int] = None, rank: int = 0
     if n_threads is None:
         n_threads = default_threads()
     h = C.c_void_p()
-    if req.reads_order:
-        rc = L.coral_bam_decode_request_ordered(path.encode(), n_threads, C.byref(req), req.reads_order, C.byref(h))
-    else:
-        rc = L.coral_bam_decode_request(path.encode(), n_threads, C.byref(req), C.byref(h))
+    rc = L.coral_bam_decode_request(path.encode(), n_threads, C.byref(req), C.byref(h))
     if rc != 0:
         raise _lib.CoralHipError("coral_bam_decode_request(%s) failed (%d): %s" % (path, rc, L.coral_bam_last_error().decode()))
     try:
@@ -437,36 +434,49 @@ def _decode_segments(path, segs, thr, cb, device, rank, world, batch_bytes, n_th
     """The decode behind ``window_coverage`` and ``pileup``: the coverage request of ``segs``, through the BAI index ``index`` (the
     rules of ``window_coverage``) when there is one.  None when the index names no block for the segments: nothing was decoded
     and every count is 0.  ``LAST_DECODE`` says which index was used."""
-    idx, skipped = None, None
-    if index is not None and index is not False:
-        if world != 1:
-            raise ValueError("a region decode is not sharded: index and world > 1 do not go together")
-        idx = _usable_index(path, index, n_ref)
-    elif index is None and world == 1:
-        beside = _index_beside(path)
-        if beside is not None:
-            try:
-                if os.path.getmtime(beside) < os.path.getmtime(path):
-                    raise _lib.CoralHipError("%s is older than the BAM file" % beside)
-                idx = _usable_index(path, beside, n_ref)
-            except (_lib.CoralHipError, OSError) as e:
-                skipped = str(e)
-    spans = None
-    if idx is not None:
-        regions = []                                             # the segments, neighbours within one linear-index window joined
+    idx, skipped = _index_choice(path, index, world, n_ref)
+    regions = []
+    if idx is not None:                                          # the segments, neighbours within one linear-index window joined
         for t, a, b in segs.T.tolist():
             if regions and regions[-1][0] == t and a - regions[-1][2] < 16384:
                 regions[-1][2] = b
             else:
                 regions.append([t, a, b])
-        spans = region_spans(idx, regions)
+    return _decode_regions(idx, skipped, regions, n_threads, lambda spans: _decode(
+        path, device, n_threads=n_threads, rank=rank, world=world, batch_bytes=batch_bytes, spans=spans, coverage=(segs, thr, cb), records=False,
+        per_base=per_base, record_filter=record_filter))
+
+
+def _index_choice(path, index, world, n_ref):
+    """Which BAI index a region decode of ``path`` uses, under the rules of ``window_coverage``: a given one (a path or an object
+    of ``read_index``) must be usable and does not go with ``world`` > 1; None looks beside the file, unless ``world`` > 1, and
+    takes what it finds when it is usable and not older than the BAM; False: none -> (the index or None, the reason an existing
+    index beside the file was skipped or None)."""
+    if index is not None and index is not False:
+        if world != 1:
+            raise ValueError("a region decode is not sharded: index and world > 1 do not go together")
+        return _usable_index(path, index, n_ref), None
+    beside = _index_beside(path) if index is None and world == 1 else None
+    if beside is None:
+        return None, None
+    try:
+        if os.path.getmtime(beside) < os.path.getmtime(path):
+            raise _lib.CoralHipError("%s is older than the BAM file" % beside)
+        return _usable_index(path, beside, n_ref), None
+    except (_lib.CoralHipError, OSError) as e:
+        return None, str(e)
+
+
+def _decode_regions(idx, skipped, regions, n_threads, decode):
+    """``decode(spans)`` for the spans the index ``idx`` names for ``regions`` (no index: ``decode(None)``, the whole file) -> its
+    result, or None when the index names no block: nothing is decoded then.  Either way ``LAST_DECODE`` says which index was used."""
+    spans = region_spans(idx, regions) if idx is not None else None
     res = None
     if spans is not None and len(spans) == 0:
         LAST_DECODE.clear()
         LAST_DECODE.update(seconds=0.0, compressed_bytes=0, uncompressed_bytes=0, blocks=0, threads=int(n_threads))
     else:
-        res = _decode(path, device, n_threads=n_threads, rank=rank, world=world, batch_bytes=batch_bytes, spans=spans,
-                      coverage=(segs, thr, cb), records=False, per_base=per_base, record_filter=record_filter)
+        res = decode(spans)
     if idx is not None:
         LAST_DECODE.update(index=idx.path or "<object>", spans=int(len(spans)))
     else:
@@ -915,7 +925,7 @@ def extract_reads(path: str, regions=None, names=None, exclude_flags: int = 0x90
     the decode to the BGZF blocks it names; with names only, or neither, the byte range (``rank`` of ``world``) is decoded and
     ``merge_reads`` joins the ranges.  ``record_filter``: a ``RecordFilter``, applied first.  The whole result lives in host
     memory: meant for the reads of an amplicon.  For every read of a 2 M-read file give ``output``: each batch's text is written
-    to that file where it would be appended to the result (coral_bamgpu_open_request_to_text; a GPU ``device``, the whole file:
+    to that file where it would be appended to the result (the CORAL_SINK_TEXT sink of coral_bamgpu_open_request; a GPU ``device``, the whole file:
     ``world`` 1), nothing is kept, and the call returns ``(records, bytes)``; the file's bytes are those of ``Reads.write``."""
     if output is None:
         got = _selected(1, path, regions, names, exclude_flags, device, n_threads, rank, world, batch_bytes, index, record_filter)
@@ -956,34 +966,11 @@ def _selected(mode: int, path, regions, names, exclude_flags, device, n_threads,
     _, segs = pileup_regions(list(regions), ref_names)
     if segs.shape[1] == 0:                                       # only empty regions
         return None
-    idx, skipped = None, None
-    if index is not None and index is not False:
-        if world != 1:
-            raise ValueError("a region decode is not sharded: index and world > 1 do not go together")
-        idx = _usable_index(path, index, len(ref_names))
-    elif index is None and world == 1:
-        beside = _index_beside(path)
-        if beside is not None:
-            try:
-                if os.path.getmtime(beside) < os.path.getmtime(path):
-                    raise _lib.CoralHipError("%s is older than the BAM file" % beside)
-                idx = _usable_index(path, beside, len(ref_names))
-            except (_lib.CoralHipError, OSError) as e:
-                skipped = str(e)
-    spans = region_spans(idx, segs.T.tolist()) if idx is not None else None
-    if spans is not None and len(spans) == 0:
-        LAST_DECODE.clear()
-        LAST_DECODE.update(seconds=0.0, compressed_bytes=0, uncompressed_bytes=0, blocks=0, threads=int(n_threads))
-        out = None
-    else:
-        res = _decode(path, device, n_threads=n_threads, rank=rank, world=world, batch_bytes=batch_bytes, spans=spans, records=False,
-                      record_filter=record_filter, reads=(exclude_flags, segs, names, mode, order), sink=sink)
-        out = res.reads
-    if idx is not None:
-        LAST_DECODE.update(index=idx.path or "<object>", spans=int(len(spans)))
-    else:
-        LAST_DECODE.update(index=None, index_skipped=skipped)
-    return out
+    idx, skipped = _index_choice(path, index, world, len(ref_names))
+    res = _decode_regions(idx, skipped, segs.T.tolist(), n_threads, lambda spans: _decode(     # (the segments as they are: none joined)
+        path, device, n_threads=n_threads, rank=rank, world=world, batch_bytes=batch_bytes, spans=spans, records=False, record_filter=record_filter,
+        reads=(exclude_flags, segs, names, mode, order), sink=sink))
+    return None if res is None else res.reads
 
 
 # ----------------------------------------------------------------------------------------------
@@ -1234,7 +1221,7 @@ def view_bam(path: str, output: str, regions=None, names=None, exclude_flags: in
              device="cuda:0", n_threads: Optional[int] = None, batch_bytes: int = 0, chunk_blocks: int = 0) -> ViewStats:
     """``samtools view -b`` of a file of any size: the selected records of ``path`` as the BAM file ``output``, written WHILE the
     file is decoded.  Each batch's records are copied out of the inflated batch and deflated where they are, in HBM
-    (k_bam_reads_copy_shifted, k_bgzf_chunk_desc, k_bgzf_deflate, k_bgzf_pack; coral_bamgpu_open_request_to_file): uncompressed
+    (k_bam_reads_copy_shifted, k_bgzf_chunk_desc, k_bgzf_deflate, k_bgzf_pack; the CORAL_SINK_BAM sink of coral_bamgpu_open_request): uncompressed
     record bytes never cross PCIe, compressed ones once, and host memory is bounded by two pinned chunks whatever the output's
     size.  Returns ``ViewStats(records, bytes, file_bytes)``: records written, their inflated bytes, the size of ``output``.
 
@@ -1326,7 +1313,7 @@ def sort_bam_stream(path: str, output: str, *, index: bool = True, record_filter
     ``extract_records(order="coordinate", ...).write(output, device=gpu)``, made in two phases in which uncompressed record
     bytes exist only in HBM.
 
-    Phase 1, while the file is decoded (coral_bamgpu_open_request_to_runs): every batch is sorted on the device as for
+    Phase 1, while the file is decoded (the CORAL_SINK_RUNS sink of coral_bamgpu_open_request): every batch is sorted on the device as for
     ``order="coordinate"``, and its sorted records are deflated where they are and appended to the spill file
     ``<tmp_dir or output's directory>/<output's name>.runs.tmp`` as one run of BGZF members.  Per written record 12 bytes come
     back to the host: its sort key and its length.  Phase 2 (coral_bamgpu_merge_runs): one stable radix sort of all keys on the

@@ -529,14 +529,9 @@ static void sort_written_records(Decoded &D) {
 }
 
 extern "C" int coral_bam_decode_request(const char *path, int32_t n_threads, const coral_bam_request_t *req, void **handle) {
-    return coral_bam_decode_request_ordered(path, n_threads, req, READS_ORDER_FILE, handle);
-}
-
-extern "C" int coral_bam_decode_request_ordered(const char *path, int32_t n_threads, const coral_bam_request_t *req, int32_t reads_order,
-                                                void **handle) {
     if (!path || !handle) return CORAL_ERR_ARG;
     Request R;
-    if (!parse_request(req, R, g_bam_err) || !set_reads_order(R, reads_order, g_bam_err)) return CORAL_ERR_ARG;
+    if (!parse_request(req, R, g_bam_err)) return CORAL_ERR_ARG;
     std::unique_ptr<Decoded> D(new Decoded());
     bool ok = false;
     try {
@@ -717,15 +712,15 @@ extern "C" int coral_bam_reads_sizes(void *handle, int64_t sizes[2]) {
     if (!handle || !sizes) return CORAL_ERR_ARG;
     const Decoded *D = (const Decoded *)handle;
     if (!D->has_reads) { g_bam_err = "coral_bam_reads_sizes: the handle holds no reads request"; return CORAL_ERR_ARG; }
-    sizes[0] = D->reads_to_file ? D->reads_file_records : (int64_t)D->reads_off.size() - 1;
-    sizes[1] = D->reads_to_file ? D->reads_file_bytes : (int64_t)D->reads_text.size();
+    sizes[0] = D->reads_in_file ? D->reads_file_records : (int64_t)D->reads_off.size() - 1;
+    sizes[1] = D->reads_in_file ? D->reads_file_bytes : (int64_t)D->reads_text.size();
     return CORAL_OK;
 }
 
 extern "C" int coral_bam_reads_fill(void *handle, uint8_t *text, int64_t *rec_off) {
     if (!handle || !rec_off) return CORAL_ERR_ARG;
     const Decoded *D = (const Decoded *)handle;
-    if (D->reads_to_file) { g_bam_err = "coral_bam_reads_fill: the records were written to a file, none is kept (coral_bamgpu_open_request_to_file)"; return CORAL_ERR_ARG; }
+    if (D->reads_in_file) { g_bam_err = "coral_bam_reads_fill: the records were written to a file, none is kept (a file sink of coral_bamgpu_open_request)"; return CORAL_ERR_ARG; }
     if (!D->has_reads || D->reads_off.back() != (int64_t)D->reads_text.size()) { g_bam_err = "coral_bam_reads_fill: the handle holds no reads request"; return CORAL_ERR_ARG; }
     if (!D->reads_text.empty() && !text) return CORAL_ERR_ARG;
     if (!D->reads_text.empty()) memcpy(text, D->reads_text.data(), D->reads_text.size());

@@ -413,7 +413,7 @@ struct Decoded {
     std::vector<uint8_t> reads_text;        // its FASTQ text (want_reads = 2: the records' bytes), the written records in file order (coral_bam_reads_fill)
     std::vector<int64_t> reads_off{0};      // where every written record starts in it, n + 1 entries
     std::vector<int64_t> reads_runs;        // coordinate order, GPU pipeline: the written record each batch's sorted run begins at
-    bool reads_to_file = false;             // GPU pipeline, coral_bamgpu_open_request_to_file: the records went to a file; nothing of them
+    bool reads_in_file = false;             // GPU pipeline with a file sink (coral_bam_sink_t): the records went to a file; nothing of them
     int64_t reads_file_records = 0, reads_file_bytes = 0;      //   is kept here but their number and their inflated bytes
 };
 
@@ -512,17 +512,6 @@ struct Request {
     const CovTable *cov_table() const { return has_cov ? &cov : nullptr; }
 };
 
-// The reads_order argument of the _ordered entry points, behind parse_request: 0 or 1, and 1 only with want_reads = 2.
-inline bool set_reads_order(Request &R, int32_t reads_order, std::string &err) {
-    if (reads_order != READS_ORDER_FILE && reads_order != READS_ORDER_COORDINATE) { err = "reads request: reads_order must be 0 (file order) or 1 (coordinate order)"; return false; }
-    if (reads_order == READS_ORDER_COORDINATE && !(R.reads.on && R.reads.mode == READS_AS_RECORDS)) {
-        err = "reads request: reads_order = 1 sorts records: it needs want_reads = 2";
-        return false;
-    }
-    R.reads.order = reads_order;
-    return true;
-}
-
 // Every argument rule of a request but one (the spans lie inside the file: spans_inside_file); false: `err` says why.
 inline bool parse_request(const coral_bam_request_t *q, Request &R, std::string &err) {
     if (!q) { err = "request: null pointer"; return false; }
@@ -612,6 +601,12 @@ inline bool parse_request(const coral_bam_request_t *q, Request &R, std::string 
         for (size_t k = 0; k < T.size(); ++k) T.seg_off.push_back(T.seg_off.back() + ((int64_t)T.hi[k] - T.lo[k]));
         if (T.n_pos() > PILEUP_MAX_POSITIONS) { err = "pileup request: the segments hold more than 2^28 positions"; return false; }
     }
+    if (q->reads_order != READS_ORDER_FILE && q->reads_order != READS_ORDER_COORDINATE) { err = "reads request: reads_order must be 0 (file order) or 1 (coordinate order)"; return false; }
+    if (q->reads_order == READS_ORDER_COORDINATE && !(R.reads.on && R.reads.mode == READS_AS_RECORDS)) {
+        err = "reads request: reads_order = 1 sorts records: it needs want_reads = 2";
+        return false;
+    }
+    R.reads.order = q->reads_order;
     return true;
 }
 

@@ -30,7 +30,7 @@
 //   coral_bamgpu_index.h   index: what the batch contributes to a BAI index
 // Every request has open / carve / start / batch / finish; batch sees the batch as a `Batch` and may overwrite the parse's dead
 // per-record arrays, handed to it as a `Scratch` (coral_bamgpu_common.h).
-// Batches (64 MiB first, doubling up to 2.52 GiB inflated, coral_bamgpu_open) are double-buffered: while batch k is parsed, batch k + 1 is inflated
+// Batches (64 MiB first, doubling up to 2.52 GiB inflated, coral_bamgpu_open_request) are double-buffered: while batch k is parsed, batch k + 1 is inflated
 // and k + 2 is read.
 // A record that straddles two batches is carried in front of the next batch's buffer.
 //
@@ -1759,46 +1759,42 @@ int fetch_nonacgt(GpuDecoder *G, hipStream_t stream, HostJob &J, int32_t na_coun
 // ---------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------
-extern "C" int coral_bamgpu_open_request(const char *path, int32_t n_threads, int64_t batch_bytes, const coral_bam_request_t *req, void **handle,
-                                         int64_t *workspace_bytes) {
-    return coral_bamgpu_open_request_ordered(path, n_threads, batch_bytes, req, READS_ORDER_FILE, handle, workspace_bytes);
-}
-
 namespace {
-// The file a records request writes to (coral_bamgpu_open_request_to_file); none: the request's result stays on the host.
-// (as_text: the plain FASTQ file of coral_bamgpu_open_request_to_text - no header, no chunks)
-// (as_runs: the spill file of coral_bamgpu_open_request_to_runs - no header, one sorted run per batch)
-struct SinkArgs { const char *out_path; const uint8_t *header; int64_t header_bytes; int32_t chunk_blocks; bool as_text; bool as_runs = false; };
+// What a sink kind asks of the request and of the coral_bam_sink_t, in the order it is checked: the want_reads and reads_order
+// it takes, rank 0 of world 1, a path, a header (BAM), chunk_blocks 0..16 384 (BAM, RUNS).  CORAL_SINK_HOST asks for nothing.
+struct SinkRule { int32_t kind; const char *name; int32_t mode; const char *mode_text; int32_t order; const char *order_text, *file, *path; bool header, chunks; };
+const SinkRule SINK_RULES[] = {
+    {CORAL_SINK_TEXT, "text", READS_AS_FASTQ, "a text file takes FASTQ: it needs want_reads = 1", READS_ORDER_FILE, "", "file", "output path", false, false},
+    {CORAL_SINK_BAM, "BAM", READS_AS_RECORDS, "a file takes records: it needs want_reads = 2", READS_ORDER_FILE, "records are streamed in file order: reads_order must be 0",
+     "file", "output path", true, true},
+    {CORAL_SINK_RUNS, "runs", READS_AS_RECORDS, "runs are made of records: it needs want_reads = 2", READS_ORDER_COORDINATE, "runs are sorted: reads_order must be 1",
+     "spill file", "spill path", false, true}};
 
-// What the open entry points share: the older calls are this one without a sink.
-int open_decoder(const char *path, int32_t n_threads, int64_t batch_bytes, const coral_bam_request_t *req, int32_t reads_order, const SinkArgs *to_file,
-                 void **handle, int64_t *workspace_bytes) {
+int check_sink(const Request &R, const coral_bam_sink_t &S) {
+    if (S.kind == CORAL_SINK_HOST) return CORAL_OK;
+    const SinkRule *K = std::find_if(std::begin(SINK_RULES), std::end(SINK_RULES), [&](const SinkRule &k) { return k.kind == S.kind; });
+    if (K == std::end(SINK_RULES)) return fail(CORAL_ERR_ARG, "coral_bamgpu_open_request: unknown sink kind " + std::to_string(S.kind));
+    const std::string me = std::string("coral_bamgpu_open_request (") + K->name + " sink): ";
+    if (!(R.reads.on && R.reads.mode == K->mode)) return fail(CORAL_ERR_ARG, me + K->mode_text);
+    if (R.reads.order != K->order) return fail(CORAL_ERR_ARG, me + K->order_text);
+    if (R.rank != 0 || R.world != 1) return fail(CORAL_ERR_ARG, me + "byte ranges do not share a " + K->file + ": rank 0 of world 1");
+    if (!S.path) return fail(CORAL_ERR_ARG, me + "no " + K->path);
+    if (K->header && (!S.header || S.header_bytes <= 0)) return fail(CORAL_ERR_ARG, me + "no header to write");
+    if (K->chunks && (S.chunk_blocks < 0 || S.chunk_blocks > 16384)) return fail(CORAL_ERR_ARG, me + "chunk_blocks must be 0 (1 024) .. 16 384");
+    return CORAL_OK;
+}
+}  // namespace
+
+extern "C" int coral_bamgpu_open_request(const char *path, int32_t n_threads, int64_t batch_bytes, const coral_bam_request_t *req, const coral_bam_sink_t *sink,
+                                         void **handle, int64_t *workspace_bytes) {
     if (!path || !handle || !workspace_bytes) return CORAL_ERR_ARG;
     std::unique_ptr<GpuDecoder> G(new GpuDecoder());
     G->t_start = std::chrono::steady_clock::now();
     std::string err;
-    if (!parse_request(req, G->req, err) || !set_reads_order(G->req, reads_order, err)) { set_error(err); return CORAL_ERR_ARG; }
+    if (!parse_request(req, G->req, err)) { set_error(err); return CORAL_ERR_ARG; }
     const Request &R = G->req;
-    if (to_file && to_file->as_text) {
-        const char *me = "coral_bamgpu_open_request_to_text: ";
-        if (!(R.reads.on && R.reads.mode == READS_AS_FASTQ)) return fail(CORAL_ERR_ARG, std::string(me) + "a text file takes FASTQ: it needs want_reads = 1");
-        if (R.rank != 0 || R.world != 1) return fail(CORAL_ERR_ARG, std::string(me) + "byte ranges do not share a file: rank 0 of world 1");
-        if (!to_file->out_path) return fail(CORAL_ERR_ARG, std::string(me) + "no output path");
-    } else if (to_file && to_file->as_runs) {
-        const char *me = "coral_bamgpu_open_request_to_runs: ";
-        if (!(R.reads.on && R.reads.mode == READS_AS_RECORDS)) return fail(CORAL_ERR_ARG, std::string(me) + "runs are made of records: it needs want_reads = 2");
-        if (R.rank != 0 || R.world != 1) return fail(CORAL_ERR_ARG, std::string(me) + "byte ranges do not share a spill file: rank 0 of world 1");
-        if (!to_file->out_path) return fail(CORAL_ERR_ARG, std::string(me) + "no spill path");
-        if (to_file->chunk_blocks < 0 || to_file->chunk_blocks > 16384) return fail(CORAL_ERR_ARG, std::string(me) + "chunk_blocks must be 0 (1 024) .. 16 384");
-    } else if (to_file) {
-        const char *me = "coral_bamgpu_open_request_to_file: ";
-        if (!(R.reads.on && R.reads.mode == READS_AS_RECORDS)) return fail(CORAL_ERR_ARG, std::string(me) + "a file takes records: it needs want_reads = 2");
-        if (R.reads.order != READS_ORDER_FILE) return fail(CORAL_ERR_ARG, std::string(me) + "records are streamed in file order: reads_order must be 0");
-        if (R.rank != 0 || R.world != 1) return fail(CORAL_ERR_ARG, std::string(me) + "byte ranges do not share a file: rank 0 of world 1");
-        if (!to_file->out_path) return fail(CORAL_ERR_ARG, std::string(me) + "no output path");
-        if (!to_file->header || to_file->header_bytes <= 0) return fail(CORAL_ERR_ARG, std::string(me) + "no header to write");
-        if (to_file->chunk_blocks < 0 || to_file->chunk_blocks > 16384) return fail(CORAL_ERR_ARG, std::string(me) + "chunk_blocks must be 0 (1 024) .. 16 384");
-    }
+    const coral_bam_sink_t to = sink ? *sink : coral_bam_sink_t{CORAL_SINK_HOST, nullptr, nullptr, 0, 0};
+    if (const int refused = check_sink(R, to)) return refused;
     const int32_t rank = R.rank, world = R.world;
     if (!G->f.open(path, G->error) || !read_bam_header(G->f, G->D, G->ref_id, &G->hdr_bytes)) {
         set_error(G->error.empty() ? G->D.error : G->error);
@@ -1846,26 +1842,28 @@ int open_decoder(const char *path, int32_t n_threads, int64_t batch_bytes, const
     size_t tmp = 0;
     (void)hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, (long long *)nullptr, (long long *)nullptr, (int)std::min<size_t>(G->rec_cap + 1, 0x7fffffff));
     G->scan_tmp_bytes = tmp + 256;
-    if (to_file && to_file->as_text) {
-        TextSink &S = G->reads.text_sink;
-        S.on = true;
-        S.path = to_file->out_path;
-        if (!(S.fp = fopen(to_file->out_path, "wb"))) return fail(CORAL_ERR_ARG, std::string("cannot create ") + to_file->out_path);
-    } else if (to_file) {                      // (last: nothing is created for a request that is refused)
-        RecordSink &S = G->reads.sink;
-        S.on = true;
-        S.path = to_file->out_path;
-        if (!to_file->as_runs) S.header.assign(to_file->header, to_file->header + to_file->header_bytes);
-        S.chunk = to_file->chunk_blocks > 0 ? (size_t)to_file->chunk_blocks : DEFL_CHUNK_BLOCKS;
-        if (!(S.fp = fopen(to_file->out_path, "wb"))) return fail(CORAL_ERR_ARG, std::string("cannot create ") + to_file->out_path);
-        if (to_file->as_runs) {
-            MergeRuns &M = G->reads.merge;
-            M.on = true;
-            M.spill_path = to_file->out_path;
-            M.chunk = S.chunk;
-            M.default_stage = (int64_t)std::min<size_t>(G->caps().batch_cap, (size_t)MERGE_STAGE_MAX);
+    ReadsRequest &W = G->reads;                // where the reads request's result goes (last: nothing is created for a request that is refused)
+    FILE **fp = nullptr;
+    switch (W.dest = to.kind) {
+    case CORAL_SINK_TEXT:
+        W.text_sink.path = to.path;
+        fp = &W.text_sink.fp;
+        break;
+    case CORAL_SINK_BAM:
+        W.sink.header.assign(to.header, to.header + to.header_bytes);
+        [[fallthrough]];
+    case CORAL_SINK_RUNS:
+        W.sink.path = to.path;
+        W.sink.chunk = to.chunk_blocks > 0 ? (size_t)to.chunk_blocks : DEFL_CHUNK_BLOCKS;
+        fp = &W.sink.fp;
+        if (to.kind == CORAL_SINK_RUNS) {
+            W.merge.spill_path = to.path;
+            W.merge.chunk = W.sink.chunk;
+            W.merge.default_stage = (int64_t)std::min<size_t>(G->caps().batch_cap, (size_t)MERGE_STAGE_MAX);
         }
+        break;
     }
+    if (fp && !(*fp = fopen(to.path, "wb"))) return fail(CORAL_ERR_ARG, std::string("cannot create ") + to.path);
     int rc = CORAL_OK;                         // what rides along: each request takes its part of R (and what of it needs the header or the capacities)
     if (!each_request(G.get(), [&](auto &r) { return (rc = r.open(R, G->caps(), G->D, err)) == CORAL_OK; }, true)) { set_error(err); return rc; }
     carve(G.get(), nullptr, 0);
@@ -1875,43 +1873,12 @@ int open_decoder(const char *path, int32_t n_threads, int64_t batch_bytes, const
     *handle = G.release();
     return CORAL_OK;
 }
-}  // namespace
-
-extern "C" int coral_bamgpu_open_request_ordered(const char *path, int32_t n_threads, int64_t batch_bytes, const coral_bam_request_t *req,
-                                                 int32_t reads_order, void **handle, int64_t *workspace_bytes) {
-    return open_decoder(path, n_threads, batch_bytes, req, reads_order, nullptr, handle, workspace_bytes);
-}
-
-// The records of a want_reads = 2 request, in file order, as a BGZF / BAM file written while the decode runs (RecordSink).
-extern "C" int coral_bamgpu_open_request_to_file(const char *path, int32_t n_threads, int64_t batch_bytes, const coral_bam_request_t *req,
-                                                 const char *out_path, const uint8_t *header, int64_t header_bytes, int32_t chunk_blocks,
-                                                 void **handle, int64_t *workspace_bytes) {
-    const SinkArgs to_file{out_path, header, header_bytes, chunk_blocks, false};
-    return open_decoder(path, n_threads, batch_bytes, req, READS_ORDER_FILE, &to_file, handle, workspace_bytes);
-}
-
-// The FASTQ text of a want_reads = 1 request as a plain file written while the decode runs (TextSink).
-extern "C" int coral_bamgpu_open_request_to_text(const char *path, int32_t n_threads, int64_t batch_bytes, const coral_bam_request_t *req,
-                                                 const char *out_path, void **handle, int64_t *workspace_bytes) {
-    const SinkArgs to_file{out_path, nullptr, 0, 0, true};
-    return open_decoder(path, n_threads, batch_bytes, req, READS_ORDER_FILE, &to_file, handle, workspace_bytes);
-}
-
-// The streamed coordinate sort, phase 1 (coral_bamgpu_merge.h): an ordered want_reads = 2 request whose batches' sorted runs go
-// to the spill file `spill_path` while the decode runs; coral_bamgpu_merge_runs, after `finish`, is phase 2.
-extern "C" int coral_bamgpu_open_request_to_runs(const char *path, int32_t n_threads, int64_t batch_bytes, const coral_bam_request_t *req,
-                                                 const char *spill_path, int32_t chunk_blocks, void **handle, int64_t *workspace_bytes) {
-    SinkArgs to_runs{spill_path, nullptr, 0, chunk_blocks, false};
-    to_runs.as_runs = true;
-    if (req && req->want_reads != READS_AS_RECORDS) return fail(CORAL_ERR_ARG, "coral_bamgpu_open_request_to_runs: runs are made of records: it needs want_reads = 2");
-    return open_decoder(path, n_threads, batch_bytes, req, READS_ORDER_COORDINATE, &to_runs, handle, workspace_bytes);
-}
 
 namespace {
 MergeRuns *merge_of(void *handle, const char *me, bool finished) {
     GpuDecoder *G = (GpuDecoder *)handle;
-    if (!G || !G->reads.merge.on) { set_error(std::string(me) + ": the handle was not opened by coral_bamgpu_open_request_to_runs"); return nullptr; }
-    if (finished && !(G->finished && !G->have_cur && G->D.reads_to_file)) { set_error(std::string(me) + ": the decode is not finished (coral_bamgpu_finish)"); return nullptr; }
+    if (!G || G->reads.dest != CORAL_SINK_RUNS) { set_error(std::string(me) + ": the handle was not opened by coral_bamgpu_open_request (runs sink)"); return nullptr; }
+    if (finished && !(G->finished && !G->have_cur && G->D.reads_in_file)) { set_error(std::string(me) + ": the decode is not finished (coral_bamgpu_finish)"); return nullptr; }
     return &G->reads.merge;
 }
 }  // namespace
@@ -1973,21 +1940,10 @@ extern "C" int coral_bamgpu_merge_stats(void *handle, int64_t stats[8], double s
 extern "C" int coral_bamgpu_sink_stats(void *handle, int64_t out[4]) {
     GpuDecoder *G = (GpuDecoder *)handle;
     if (!G || !out) return CORAL_ERR_ARG;
-    if (G->reads.text_sink.on) {               // (a text file: its bytes are the text's, and it has no members)
-        const TextSink &T = G->reads.text_sink;
-        out[0] = T.records; out[1] = T.bytes; out[2] = T.bytes; out[3] = 0;
-        return CORAL_OK;
-    }
-    const RecordSink &S = G->reads.sink;
-    if (!S.on) { set_error("coral_bamgpu_sink_stats: the handle writes to no file"); return CORAL_ERR_ARG; }
-    out[0] = S.records; out[1] = S.bytes; out[2] = S.file_bytes; out[3] = S.members;
+    if (G->reads.dest == CORAL_SINK_HOST) { set_error("coral_bamgpu_sink_stats: the handle writes to no file"); return CORAL_ERR_ARG; }
+    const std::array<int64_t, 4> counts = G->reads.file_counts();
+    std::copy(counts.begin(), counts.end(), out);
     return CORAL_OK;
-}
-
-extern "C" int coral_bamgpu_open(const char *path, int32_t n_threads, int32_t rank, int32_t world, int64_t batch_bytes, void **handle,
-                                 int64_t *workspace_bytes) {
-    const coral_bam_request_t q = range_request(rank, world);
-    return coral_bamgpu_open_request(path, n_threads, batch_bytes, &q, handle, workspace_bytes);
 }
 
 // Once every batch has been emitted: waits for `stream_` and leaves what was requested in the host-side result
@@ -1999,7 +1955,7 @@ extern "C" int coral_bamgpu_finish(void *handle, void *stream_) {
     if (!G->finished || G->have_cur) { set_error("coral_bamgpu_finish: the decode is not finished"); return CORAL_ERR_ARG; }
     if (each_request(G, [](auto &) { return false; })) return CORAL_OK;      // nothing rides along
     if (hipStreamSynchronize((hipStream_t)stream_) != hipSuccess || !each_request(G, [&](auto &r) { return r.finish(G->D, G->n_threads); })) {
-        set_error(G->reads.sink.error.empty() ? "coral_bamgpu_finish: copy of the requested results failed" : G->reads.sink.error);
+        set_error(G->reads.sink_error().empty() ? "coral_bamgpu_finish: copy of the requested results failed" : G->reads.sink_error());
         return CORAL_ERR_HIP;
     }
     if (G->D.idx.unsorted) { set_error("the records are not in coordinate order: no index can be built"); return CORAL_ERR_FORMAT; }
@@ -2039,7 +1995,7 @@ extern "C" int coral_bamgpu_start(void *handle, void *workspace, int64_t workspa
     if ((e = hipStreamCreateWithFlags(&G->s_crc, hipStreamNonBlocking)) != hipSuccess) return bad("hipStreamCreate", e);
     G->t_alloc = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_alloc0).count();
     const char *what = nullptr;
-    if (!each_request(G, [&](auto &r) { return !(what = r.start(G->D, e)); })) return G->reads.sink.error.empty() ? bad(what, e) : fail(CORAL_ERR_HIP, G->reads.sink.error);
+    if (!each_request(G, [&](auto &r) { return !(what = r.start(G->D, e)); })) return G->reads.sink_error().empty() ? bad(what, e) : fail(CORAL_ERR_HIP, G->reads.sink_error());
     G->feeder = std::thread(feeder_main, G);
     G->worker = std::thread(worker_main, G);
     return CORAL_OK;

@@ -1,7 +1,7 @@
 // coral_bamgpu_deflate.h - BGZF blocks made ON THE GPU (included by coral_bamgpu.hip, behind coral_bamgpu_reads.h): the writers
 // behind bam.RecordBytes.write(device=...) and bam.sort_bam(write_device=...) deflate on the device instead of calling zlib on
 // the host (coral_bgzf_write).  The writers touch nothing of the decode pipeline; RecordSink, at the end, is the one piece that
-// does: the file a records request streams to (coral_bamgpu_open_request_to_file), with its arrays in the decode's workspace.
+// does: the file a records request streams to (CORAL_SINK_BAM of coral_bamgpu_open_request), with its arrays in the decode's workspace.
 //
 //   k_bgzf_deflate  one wave per input block of at most 0xff00 bytes: one complete BGZF member (header with BSIZE, one dynamic or
 //                   stored DEFLATE block, CRC-32, ISIZE) into the block's 64 KiB slot - coral_deflate_core.h, the device backend
@@ -244,7 +244,7 @@ inline int bgzf_write_gpu(const char *path, const uint8_t *const *parts, const i
     return CORAL_OK;
 }
 
-// ---- the file sink of a records request (coral_bamgpu_open_request_to_file; ReadsRequest in coral_bamgpu_reads.h) ---------------
+// ---- the file sink of a records request (CORAL_SINK_BAM; ReadsRequest in coral_bamgpu_reads.h) -----------------------------------
 // The descriptors of one chunk, made where they are read: block k of n_blocks is in[k * 0xff00 ..) with 0xff00 bytes (the last
 // one: last_len), its member goes to slot k.
 __global__ __launch_bounds__(WAVE) void k_bgzf_chunk_desc(BlockDesc *__restrict__ desc, int n_blocks, uint32_t last_len) {
@@ -263,7 +263,6 @@ __global__ __launch_bounds__(WAVE) void k_bgzf_chunk_desc(BlockDesc *__restrict_
 // when a batch ends: it is taken in by the next batch's first chunk, or by `finish`.
 // A failure leaves the file without the EOF block (readers see it truncated); the destructor closes it.
 struct RecordSink {
-    bool on = false;
     std::string path, error;
     std::vector<uint8_t> header;
     size_t chunk = DEFL_CHUNK_BLOCKS;
@@ -375,7 +374,7 @@ struct RecordSink {
         bytes += n;
         return true;
     }
-    // One sorted run of a spill file (coral_bamgpu_open_request_to_runs): `n` bytes stand at buf, offset 0, written by a kernel on
+    // One sorted run of a spill file (CORAL_SINK_RUNS): `n` bytes stand at buf, offset 0, written by a kernel on
     // `stream`.  ALL of them are deflated now, a short last block included: a run is a whole number of members and shares none.
     bool run(uint8_t *buf, long long n, long long n_records, hipStream_t stream) {
         if (!ok(hipEventRecord(ev_copied, stream), "hipEventRecord") || !ok(hipStreamWaitEvent(s, ev_copied, 0), "hipStreamWaitEvent")) return false;

@@ -1,7 +1,7 @@
-// coral_bamgpu_merge.h — the streamed coordinate sort of the GPU BAM decoder (coral_bamgpu_open_request_to_runs,
-// coral_bamgpu_merge_runs; bam.sort_bam_stream): sorted runs spilled to disk while the decode runs, merged on the device.
+// coral_bamgpu_merge.h — the streamed coordinate sort of the GPU BAM decoder (the CORAL_SINK_RUNS sink of
+// coral_bamgpu_open_request, coral_bamgpu_merge_runs; bam.sort_bam_stream): sorted runs spilled to disk while the decode runs, merged on the device.
 // In both phases uncompressed record bytes exist only in HBM.
-//   phase 1   ReadsRequest (coral_bamgpu_reads.h) with `merge.on`: every batch is sorted as for reads_order = 1, its sorted copy
+//   phase 1   ReadsRequest (coral_bamgpu_reads.h) with dest = CORAL_SINK_RUNS: every batch is sorted as for reads_order = 1, its sorted copy
 //             goes to offset 0 of the sink's buffer and ALL of it is deflated (RecordSink::run): one run of the spill file, a
 //             whole number of BGZF members, every one but the run's last of 0xff00 bytes.  No header, no EOF block.  What comes
 //             back per written record: its 8-byte key and its length - MergeRuns below, 12 bytes per record.
@@ -82,7 +82,6 @@ __global__ __launch_bounds__(WAVE) void k_bam_merge_copy(const uint8_t *__restri
 // ---- host side --------------------------------------------------------------------------------------------------------------------
 struct MergeRuns {
     struct Run { int64_t first = 0, n = 0, bytes = 0, file_off = 0; };
-    bool on = false;
     std::string spill_path, error;
     size_t chunk = DEFL_CHUNK_BLOCKS;
     int64_t default_stage = 0;               // one batch's capacity: no record of a run is longer
@@ -285,7 +284,6 @@ struct MergeRuns {
         t_order = since(t_order0);
 
         // ---- the output: header first, in blocks of its own ----------------------------------------------------------------------------
-        out.on = true;
         out.path = out_path;
         out.header.assign(header, header + header_bytes);
         if (!(out.fp = fopen(out_path, "wb"))) return bad(CORAL_ERR_ARG, std::string("cannot create ") + out_path);

@@ -248,10 +248,9 @@ __global__ __launch_bounds__(WAVE) void k_bam_reads_copy_sorted(const uint8_t *_
 #include "coral_bamgpu_merge.h"        // MergeRuns: the streamed coordinate sort (sorted runs to a spill file, merged on the device)
 
 // ---- host side: the request's lifecycle (each_request in coral_bamgpu.hip, which calls all but open only when `active`) ---------
-// The plain file a FASTQ request writes to (coral_bamgpu_open_request_to_text): each batch's text goes there where `collect` would
+// The plain file a FASTQ request writes to (CORAL_SINK_TEXT): each batch's text goes there where `collect` would
 // append it to the host-side result - no compression, no carry.  A failure leaves what was written; the destructor closes the file.
 struct TextSink {
-    bool on = false;
     std::string path;
     FILE *fp = nullptr;
     std::vector<uint8_t> host;           // one batch's text on its way to the file
@@ -273,9 +272,10 @@ struct TextSink {
 
 struct ReadsRequest {                // FASTQ text, or the own bytes (R->mode), of the selected records
     bool active = false;
-    RecordSink sink;                 // sink.on (coral_bamgpu_open_request_to_file): the records go to a BGZF file, not to the host-side result
-    TextSink text_sink;              // text_sink.on (coral_bamgpu_open_request_to_text): the FASTQ text goes to a plain file
-    MergeRuns merge;                 // merge.on (coral_bamgpu_open_request_to_runs; with sink.on): every batch's sorted run goes to the spill file
+    int dest = CORAL_SINK_HOST;      // where the result goes (coral_bam_sink_t::kind, set by the open call): the host-side result, or
+    TextSink text_sink;              //   CORAL_SINK_TEXT: the FASTQ text goes to a plain file
+    RecordSink sink;                 //   CORAL_SINK_BAM: the records go to a BGZF file; CORAL_SINK_RUNS: to the spill file, where
+    MergeRuns merge;                 //   every batch's sorted run is kept track of for the merge
     const ReadsRule *R = nullptr;    // the request (Request::reads)
     ReadsDev X{};
     uint8_t *text = nullptr;         // the batch's text: one buffer for all batches (collect)
@@ -289,19 +289,27 @@ struct ReadsRequest {                // FASTQ text, or the own bytes (R->mode), 
     void *sort_tmp = nullptr;
     size_t sort_tmp_bytes = 0;
     bool ordered() const { return active && R->order == READS_ORDER_COORDINATE; }
+    bool deflates() const { return dest == CORAL_SINK_BAM || dest == CORAL_SINK_RUNS; }      // `sink` is in use
+    // What went to the file so far - records, their bytes, the file's bytes, its BGZF members (a text file: its bytes are the
+    // text's, and it has no members) -, and why the sink failed, if it did.
+    std::array<int64_t, 4> file_counts() const {
+        if (dest == CORAL_SINK_TEXT) return {text_sink.records, text_sink.bytes, text_sink.bytes, 0};
+        return {sink.records, sink.bytes, sink.file_bytes, sink.members};
+    }
+    const std::string &sink_error() const { return sink.error; }
     int open(const Request &Q, const Caps &C, Decoded &, std::string &err) {
         active = Q.reads.on;
         R = &Q.reads;
-        if (sink.on) {
+        if (deflates()) {
             sink.chunk = std::min(sink.chunk, C.batch_cap / coral_deflate::BLOCK_MAX + 2);      // (no batch can fill more)
-            if (pack_tmp_bytes((int)sink.chunk) > DEFL_SCAN_TMP) { err = "coral_bamgpu_open_request_to_file: hipcub asks for more temporary storage than reserved"; return CORAL_ERR_HIP; }
+            if (pack_tmp_bytes((int)sink.chunk) > DEFL_SCAN_TMP) { err = "coral_bamgpu_open_request (file sink): hipcub asks for more temporary storage than reserved"; return CORAL_ERR_HIP; }
         }
         if (!ordered()) return CORAL_OK;
         // the sort's temporary storage, queried once for the largest batch, as the scan's is
         hipcub::DoubleBuffer<unsigned long long> keys(nullptr, nullptr);
         hipcub::DoubleBuffer<uint32_t> ords(nullptr, nullptr);
         if (hipcub::DeviceRadixSort::SortPairs(nullptr, sort_tmp_bytes, keys, ords, (int)std::min<size_t>(C.rec_slots, 0x7fffffff), 0, 64) != hipSuccess) {
-            err = "coral_bamgpu_open_request_ordered: the size of the sort's temporary storage could not be queried";
+            err = "coral_bamgpu_open_request (reads_order = 1): the size of the sort's temporary storage could not be queried";
             return CORAL_ERR_HIP;
         }
         sort_tmp_bytes += 256;
@@ -326,8 +334,8 @@ struct ReadsRequest {                // FASTQ text, or the own bytes (R->mode), 
         int64_t *off = (int64_t *)take((n_names + 1) * 8);
         X = ReadsDev{seg, seg + n_seg, seg + 2 * n_seg, names, off, (int)n_seg, (long long)n_names, R->exclude_flags, R->mode};
         text_cap = (R->mode == READS_AS_RECORDS ? C.batch_cap : C.batch_cap / 3 * 4) + 256;
-        text = (uint8_t *)take(text_cap + (sink.on ? (size_t)coral_deflate::BLOCK_MAX : 0));
-        if (sink.on) sink.carve(take);
+        text = (uint8_t *)take(text_cap + (deflates() ? (size_t)coral_deflate::BLOCK_MAX : 0));
+        if (deflates()) sink.carve(take);
     }
     const char *start(const Decoded &, hipError_t &e) {
         const size_t b = (size_t)X.n_seg * 4;
@@ -337,7 +345,7 @@ struct ReadsRequest {                // FASTQ text, or the own bytes (R->mode), 
                         (X.n_names == 0 || ((e = hipMemcpy((void *)X.names, R->names.data(), R->names.size(), hipMemcpyHostToDevice)) == hipSuccess &&
                                             (e = hipMemcpy((void *)X.name_off, R->name_off.data(), R->name_off.size() * 8, hipMemcpyHostToDevice)) == hipSuccess));
         if (!ok) return "reads request set-up";
-        if (sink.on && !(sink.start() && (merge.on || sink.write_header(text, text_cap)))) { e = hipGetLastError(); return "record sink set-up"; }      // (a spill file has no header)
+        if (deflates() && !(sink.start() && (dest == CORAL_SINK_RUNS || sink.write_header(text, text_cap)))) { e = hipGetLastError(); return "record sink set-up"; }      // (a spill file has no header)
         return nullptr;
     }
     // It waits for its own totals (16 bytes: no read-back of the batch lies behind these kernels, so they are a small copy of their
@@ -346,7 +354,7 @@ struct ReadsRequest {                // FASTQ text, or the own bytes (R->mode), 
     bool batch(const Batch &B, Scratch S, std::string &err) {
         if (!collect(B.D)) { err = "copy of the reads text failed"; return false; }      // (of the batch in front: its kernels have run, ours are not queued yet)
         const long long n = B.n_rec;
-        if (n == 0) return !merge.on || spill_run(B, {0}, {}, 0, 0, 0, nullptr, nullptr, nullptr, err);      // (an empty run)
+        if (n == 0) return dest != CORAL_SINK_RUNS || spill_run(B, {0}, {}, 0, 0, 0, nullptr, nullptr, nullptr, err);      // (an empty run)
         auto [out_len, n_items, out_off, item_off] = S.take<4>();
         hipLaunchKernelGGL(k_bam_reads_plan, dim3((unsigned)((n + 1 + WAVE - 1) / WAVE)), dim3(WAVE), 0, B.stream, B.buf, B.rec_start, n, B.M, B.end, X, out_len, n_items);
         const uint32_t *ord = nullptr;                   // coordinate order: sorted position -> record of the batch
@@ -368,20 +376,17 @@ struct ReadsRequest {                // FASTQ text, or the own bytes (R->mode), 
             B.D.reads_runs.push_back((int64_t)B.D.reads_off.size() - 1);      // this batch's run begins behind what is written
         } else if (!B.scan(out_len, out_off) || !B.scan(n_items, item_off)) { err = "scan of the reads work items failed"; return false; }
         std::vector<long long> off((size_t)n + 1);
+        std::vector<unsigned long long> run_keys(dest == CORAL_SINK_RUNS ? (size_t)n : 0);      // a run of the spill file: the sorted keys come with the offsets
         long long items = 0;
-        if (merge.on) {                                  // a run of the spill file: the offsets, and the sorted keys with them
-            std::vector<unsigned long long> run_keys((size_t)n);
-            if (fetch_sync(B.stream, {{off.data(), out_off, (size_t)(n + 1) * 8}, {&items, item_off + n, 8}, {run_keys.data(), sorted_key, (size_t)n * 8}}, nullptr, "reads plan", err) != CORAL_OK)
-                return false;
-            const long long run_bytes = off[(size_t)n];
-            if (run_bytes < 0 || (size_t)run_bytes > text_cap || items < 0) { err = "reads request: the batch's text does not fit its buffer"; return false; }
-            return spill_run(B, off, run_keys, n, run_bytes, items, ord, item_off, out_off, err);
-        }
-        if (fetch_sync(B.stream, {{off.data(), out_off, (size_t)(n + 1) * 8}, {&items, item_off + n, 8}}, nullptr, "reads plan", err) != CORAL_OK) return false;
+        const int rc = dest == CORAL_SINK_RUNS
+            ? fetch_sync(B.stream, {{off.data(), out_off, (size_t)(n + 1) * 8}, {&items, item_off + n, 8}, {run_keys.data(), sorted_key, (size_t)n * 8}}, nullptr, "reads plan", err)
+            : fetch_sync(B.stream, {{off.data(), out_off, (size_t)(n + 1) * 8}, {&items, item_off + n, 8}}, nullptr, "reads plan", err);
+        if (rc != CORAL_OK) return false;
         const long long bytes = off[(size_t)n];
         if (bytes < 0 || (size_t)bytes > text_cap || items < 0) { err = "reads request: the batch's text does not fit its buffer"; return false; }
+        if (dest == CORAL_SINK_RUNS) return spill_run(B, off, run_keys, n, bytes, items, ord, item_off, out_off, err);
         if (bytes == 0) return true;                     // no record of the batch is written: nothing more is queued
-        if (sink.on) {                                   // to the file: behind the carried bytes, and nothing for the host-side result
+        if (dest == CORAL_SINK_BAM) {                    // to the file: behind the carried bytes, and nothing for the host-side result
             long long written = 0;
             for (long long i = 0; i < n; ++i) written += off[(size_t)i + 1] > off[(size_t)i];
             if (!sink.wait_moved(B.stream)) { err = sink.error; return false; }
@@ -394,7 +399,7 @@ struct ReadsRequest {                // FASTQ text, or the own bytes (R->mode), 
         const int64_t base = B.D.reads_off.back();
         for (long long i = 0; i < n; ++i)
             if (off[(size_t)i + 1] > off[(size_t)i]) {
-                if (text_sink.on) ++text_sink.records;
+                if (dest == CORAL_SINK_TEXT) ++text_sink.records;
                 else B.D.reads_off.push_back(base + off[(size_t)i + 1]);
             }
         // one wave per workgroup, grid-stride beyond 8 per CU
@@ -427,33 +432,32 @@ struct ReadsRequest {                // FASTQ text, or the own bytes (R->mode), 
     // The text of the batch emitted last, if it is still on the device (the caller has synchronised the stream).  One buffer for
     // all batches: QcRequest::collect's argument, under the same condition - every emit of a decode and the result call are
     // given the SAME stream.
-    bool collect(Decoded &D) { return text_sink.on ? text_sink.write(text, pending_bytes) : collect_pending(D.reads_text, text, pending_bytes); }
-    // Coordinate order: every batch left one sorted run (D.reads_runs: the written record it begins at); more than one run goes
-    // through the host's stable k-way merge, run order = batch order, and the runs are freed.
+    bool collect(Decoded &D) { return dest == CORAL_SINK_TEXT ? text_sink.write(text, pending_bytes) : collect_pending(D.reads_text, text, pending_bytes); }
+    // A file is closed in its own way; what all three leave in the host-side result is the same.
     bool finish(Decoded &D, int n_threads) {
         D.has_reads = true;
-        if (merge.on) {                  // the spill file ends with its last run's last member: no EOF block
+        switch (dest) {
+        case CORAL_SINK_RUNS:            // the spill file ends with its last run's last member: no EOF block
             if (!sink.close_plain()) return false;
             merge.spill_bytes = sink.file_bytes;
-            D.reads_to_file = true;
-            D.reads_file_records = sink.records;
-            D.reads_file_bytes = sink.bytes;
-            return true;
-        }
-        if (sink.on) {
+            break;
+        case CORAL_SINK_BAM:
             if (!sink.finish(text)) return false;
-            D.reads_to_file = true;
-            D.reads_file_records = sink.records;
-            D.reads_file_bytes = sink.bytes;
-            return true;
+            break;
+        case CORAL_SINK_TEXT:
+            if (!collect(D) || !text_sink.finish()) return false;
+            break;
+        default:
+            return collect(D) && merge_host_runs(D, n_threads);
         }
-        if (!collect(D)) return false;
-        if (text_sink.on) {
-            D.reads_to_file = true;
-            D.reads_file_records = text_sink.records;
-            D.reads_file_bytes = text_sink.bytes;
-            return text_sink.finish();
-        }
+        D.reads_in_file = true;          // nothing is kept here but the number of records and their inflated bytes
+        D.reads_file_records = file_counts()[0];
+        D.reads_file_bytes = file_counts()[1];
+        return true;
+    }
+    // Coordinate order: every batch left one sorted run (D.reads_runs: the written record it begins at); more than one run goes
+    // through the host's stable k-way merge, run order = batch order, and the runs are freed.
+    bool merge_host_runs(Decoded &D, int n_threads) {
         if (!ordered() || D.reads_runs.size() < 2) return true;
         const size_t n_runs = D.reads_runs.size(), n_rec = D.reads_off.size() - 1;
         std::vector<const uint8_t *> data(n_runs, D.reads_text.data());

@@ -293,7 +293,6 @@ inline int samgpu_import(int32_t fd, const uint8_t *lead, int64_t lead_bytes, in
     const auto t_all = std::chrono::steady_clock::now();
 
     RecordSink sink;
-    sink.on = true;
     sink.path = out_path;
     sink.header.assign(bam, bam + bam_bytes);
     sink.chunk = sam_chunk(chunk_blocks);

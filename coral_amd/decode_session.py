@@ -1,4 +1,4 @@
-"""The one driver of the GPU BAM decoder (csrc/coral_bamgpu.hip): which of its open entry points a request goes to, and the
+"""The one driver of the GPU BAM decoder (csrc/coral_bamgpu.hip): the sink descriptor its open call is given, and the
 call sequence on the handle - open, workspace, start, next / emit per batch, finish, host, close."""
 from __future__ import annotations
 
@@ -18,25 +18,25 @@ Runs = collections.namedtuple("Runs", "spill_path chunk_blocks")              # 
 
 
 def open_handle(L, path, n_threads, batch_bytes, req, sink=None):
-    """The coral_bamgpu_open_request* entry point that ``sink`` (None, TextFile, BamFile, Runs) and ``req.reads_order`` select ->
-    (rc, handle, workspace_bytes); no GPU work.  The arguments go through as they are (a None path or header as NULL), and a
-    refusal is returned, not raised: coral_bam_last_error() has its text.  ``req`` must outlive the handle."""
+    """coral_bamgpu_open_request with the coral_bam_sink_t that ``sink`` (None, TextFile, BamFile, Runs) stands for -> (rc, handle,
+    workspace_bytes); no GPU work.  The arguments go through as they are (a None path or header as NULL), and a refusal is
+    returned, not raised: coral_bam_last_error() has its text.  A Runs sink puts ``req`` in coordinate order (the library's runs
+    sink takes no other).  ``req`` must outlive the handle."""
     h, ws_bytes = C.c_void_p(), C.c_int64(0)
-    common, out = (path.encode(), n_threads, batch_bytes, C.byref(req)), (C.byref(h), C.byref(ws_bytes))
     fs = lambda p: None if p is None else os.fsencode(p)
-    if sink is None and req.reads_order:
-        rc = L.coral_bamgpu_open_request_ordered(*common, req.reads_order, *out)
-    elif sink is None:
-        rc = L.coral_bamgpu_open_request(*common, *out)
+    if sink is None:
+        to = None
     elif isinstance(sink, TextFile):
-        rc = L.coral_bamgpu_open_request_to_text(*common, fs(sink.path), *out)
+        to = _lib.coral_bam_sink_t(_lib.SINK_TEXT, fs(sink.path))
     elif isinstance(sink, BamFile):
-        head = np.frombuffer(bytes(b"" if sink.header is None else sink.header), dtype=np.uint8)       # (the library copies it)
-        rc = L.coral_bamgpu_open_request_to_file(*common, fs(sink.path), head.ctypes.data if len(head) else None, len(head), int(sink.chunk_blocks), *out)
+        head = np.frombuffer(bytes(b"" if sink.header is None else sink.header), dtype=np.uint8)       # (alive until the return; the library copies it)
+        to = _lib.coral_bam_sink_t(_lib.SINK_BAM, fs(sink.path), head.ctypes.data if len(head) else None, len(head), int(sink.chunk_blocks))
     elif isinstance(sink, Runs):
-        rc = L.coral_bamgpu_open_request_to_runs(*common, fs(sink.spill_path), int(sink.chunk_blocks), *out)
+        req.reads_order = 1                                      # (runs are sorted runs: what the sink means, said where the library reads it)
+        to = _lib.coral_bam_sink_t(_lib.SINK_RUNS, fs(sink.spill_path), chunk_blocks=int(sink.chunk_blocks))
     else:
         raise TypeError("sink must be None, a TextFile, a BamFile or a Runs, got %r" % (sink,))
+    rc = L.coral_bamgpu_open_request(path.encode(), n_threads, batch_bytes, C.byref(req), to, C.byref(h), C.byref(ws_bytes))
     return rc, h, int(ws_bytes.value)
 
 
@@ -69,7 +69,7 @@ class DecodeSession:
         self.h, self.stream, self.dh, self.pieces, self.words, self.batches, self._held = None, None, None, [], [], 0, []
         rc, h, self.ws_bytes = open_handle(self.L, path, self.n_threads, batch_bytes, req, sink)
         if rc != 0:
-            raise self.fail("coral_bamgpu_open_request" + ("_to_runs" if isinstance(sink, Runs) else ""), rc)
+            raise self.fail("coral_bamgpu_open_request", rc)
         self.h = h
 
     # ---- the two device operations ------------------------------------------------------------------------------------------

@@ -521,8 +521,8 @@ const char *coral_bam_last_error(void);
  * the header's contigs (checked once the header is read: refused before anything is decoded or allocated); keep_min_mapq
  * 0..255, keep_min_seq_length 0..2^29, keep_require_flags and keep_exclude_flags 0..0xffff, and no active record filter together
  * with want_index; want_reads 0, 1 or 2, and with want_reads = 1 or 2: reads_exclude_flags 0..0xffff, reads_seg under the rules of
- * the coverage segments, reads_names of 1..254 bytes each, strictly ascending, and no want_index.  A span decode is not sharded:
- * rank and world are taken as 0 and 1. */
+ * the coverage segments, reads_names of 1..254 bytes each, strictly ascending, and no want_index; reads_order 0 or 1, and 1 only
+ * with want_reads = 2.  A span decode is not sharded: rank and world are taken as 0 and 1. */
 typedef struct {
     int32_t rank, world;                       /* byte range (ignored when n_spans >= 0) */
     int32_t n_spans;                           /* -1: the byte range; >= 0: only records starting inside these spans */
@@ -536,6 +536,10 @@ typedef struct {
     int32_t depth_min_mapq, depth_exclude_flags, depth_count_deletions;
     /* the reads request: want_reads 0 = none */
     int32_t want_reads;                        /* 1: the selected records as FASTQ text, 2: as their own bytes (coral_bam_reads_sizes / _fill) */
+    int32_t reads_order;                       /* 0: file order; 1: the written records of a want_reads = 2 request ascending by
+                                                *    key = (uint64)(uint32)tid << 32 | (uint64)(uint32)(pos + 1) << 1 | (flag >> 4 & 1)
+                                                *    - tid = -1 is 0xffffffff: records without coordinates last; at an equal position
+                                                *    forward strand first -, records with equal keys in their input order (stable) */
     int32_t reads_exclude_flags;               /* 0..0xffff  written only when (flag & it) == 0 */
     int32_t reads_n_seg;                       /* 0: no region limit; else sorted, disjoint segments, the coverage segments' rules */
     const int32_t *reads_seg_tid, *reads_seg_start, *reads_seg_end;
@@ -644,7 +648,7 @@ typedef struct {
  * file order.  Allowed on byte ranges (the texts of consecutive ranges concatenate) and on span decodes, not with want_index.
  *   reads_sizes -> records written, text bytes; reads_fill copies the text and the n + 1 int64 offsets of the records in it.
  *   The whole result lives in host memory: meant for the reads of an amplicon; for every read of a 2 M-read file the GPU
- *   pipeline writes the same text to a file batch by batch: coral_bamgpu_open_request_to_text.
+ *   pipeline writes the same text to a file batch by batch: the CORAL_SINK_TEXT sink of coral_bamgpu_open_request.
  *
  * Records (want_reads = 2) - the same selection with the alignments kept: what `samtools view -b x.bam region... > amp.bam`
  * gets from a second pass, for a genome browser or any tool that reads BAM.  reads_exclude_flags, reads_seg_*, reads_names /
@@ -658,7 +662,7 @@ typedef struct {
  *   reads_sizes -> records written, total bytes; reads_fill copies the bytes and the n + 1 int64 offsets of the records.
  *   The whole result lives in host memory: meant for the records of an amplicon.  coral_bgzf_write puts a header and such bytes
  *   into a BGZF / BAM file.  For a whole 2 M-read file the GPU pipeline streams the same records to disk in bounded host
- *   memory: coral_bamgpu_open_request_to_file. */
+ *   memory: the CORAL_SINK_BAM sink of coral_bamgpu_open_request (CORAL_SINK_RUNS: in coordinate order, for coral_bamgpu_merge_runs). */
 int coral_bam_decode_request(const char *path, int32_t n_threads, const coral_bam_request_t *req, void **handle);
 int coral_bam_coverage_result(void *handle, int32_t n_seg, int64_t *counts);
 int coral_bam_pileup_result(void *handle, int64_t n_pos, uint32_t *counts);
@@ -680,13 +684,9 @@ int coral_bam_reads_fill(void *handle, uint8_t *text, int64_t *rec_off);
 int coral_bgzf_write(const char *path, const uint8_t *const *parts, const int64_t *part_bytes, int32_t n_parts, int32_t level,
                      int32_t n_threads);
 /* Records in coordinate order - what `samtools sort` does in a pass of its own (the reference's
- * scripts/align_nanopore_reads.sh:49), here inside the decode.  coral_bam_decode_request_ordered is coral_bam_decode_request
- * with reads_order: 0 = file order (what coral_bam_decode_request asks for), 1 = the written records of a want_reads = 2
- * request ascending by
- *   key = (uint64)(uint32)tid << 32 | (uint64)(uint32)(pos + 1) << 1 | (flag >> 4 & 1)
- * - tid = -1 is 0xffffffff: records without coordinates last; at an equal position forward strand first -, records with equal
- * keys in their input order (stable).  CORAL_ERR_ARG: reads_order outside 0..1, or 1 without want_reads = 2.  The result is read
- * with coral_bam_reads_sizes / _fill as before, in final order.  A byte range or span decode sorts what it selects; the sorted
+ * scripts/align_nanopore_reads.sh:49), here inside the decode: reads_order = 1 of the request (its key and
+ * tie rule stand at the field).  CORAL_ERR_ARG: reads_order outside 0..1, or 1 without want_reads = 2.  The result is read with
+ * coral_bam_reads_sizes / _fill as in file order, in final order.  A byte range or span decode sorts what it selects; the sorted
  * results of consecutive ranges are joined by coral_bam_records_merge (rank order = run order).
  * coral_bam_records_merge: a stable k-way merge of n_runs sorted runs of raw records by the same key, read from the records'
  * bytes (tid at +4, pos at +8, flag at +18).  Record k of run r is data[r][off[r][k] .. off[r][k + 1]), n[r] records; on a tie
@@ -694,8 +694,6 @@ int coral_bgzf_write(const char *path, const uint8_t *const *parts, const int64_
  * (out_off[sum(n)] of them = the runs' bytes; the caller sizes it).  The order and the offsets are computed first, then the
  * bytes are copied by n_threads workers (< 1: one): they do not depend on n_threads.  CORAL_ERR_ARG: n_runs < 0, a missing
  * array, a negative count, offsets that decrease. */
-int coral_bam_decode_request_ordered(const char *path, int32_t n_threads, const coral_bam_request_t *req, int32_t reads_order,
-                                     void **handle);
 int coral_bam_records_merge(int32_t n_runs, const uint8_t *const *data, const int64_t *const *off, const int64_t *n,
                             uint8_t *out_data, int64_t *out_off, int32_t n_threads);
 
@@ -720,7 +718,9 @@ int coral_bam_records_merge(int32_t n_runs, const uint8_t *const *data, const in
  *   stats  stats = batches, segments whose speculative record start was replaced by the exact walk, records fetched
  *          whole for the non-ACGT list, batch capacity; seconds = total wall time, host-side field handling, file reads,
  *          set-up of pinned buffers and streams, time the caller waited for the file feeder, ... for the GPU
- *   open_request  open with a coral_bam_request_t; *workspace_bytes is final (the requests' own arrays are part of it).
+ *   open_request  open with a coral_bam_request_t and a coral_bam_sink_t: where the reads request's result goes (NULL, or kind
+ *          CORAL_SINK_HOST with the other fields ignored: it stays in host memory; the other kinds below; an unknown kind is
+ *          CORAL_ERR_ARG); *workspace_bytes is final (the requests' own arrays are part of it).
  *          Spans go through the same batches one after the other, each from its known first record to the record at or
  *          behind its end; only their blocks are read, uploaded and inflated, and statistics count every block read.
  *          Without a request no kernel is added and nothing more is allocated.  Per batch, with
@@ -758,7 +758,7 @@ int coral_bam_records_merge(int32_t n_runs, const uint8_t *const *data, const in
  *                      and k_bam_reads_copy takes k_bam_reads_emit's place (same launch shape: a lane stores one aligned
  *                      16-byte chunk of the output, filled from the two aligned source chunks that cover it; bytes at an
  *                      item's two edges; no LDS, no atomics); the buffer is one batch + 256 bytes
- *                      reads_order = 1 (coral_bamgpu_open_request_ordered): between the plan and the scans k_bam_sort_keys (one
+ *                      reads_order = 1 of the request: between the plan and the scans k_bam_sort_keys (one
  *                      thread per record: reads_sort_key and the record's ordinal), hipcub's stable radix sort of (key,
  *                      ordinal) and k_bam_sort_permute (the plan's lengths and item counts in sorted order); the scans run
  *                      over the permuted arrays and k_bam_reads_copy_sorted, k_bam_reads_copy with the source record looked up
@@ -769,8 +769,8 @@ int coral_bam_records_merge(int32_t n_runs, const uint8_t *const *data, const in
  *          handle of `host` (coral_bam_coverage_result, coral_bam_pileup_result - the table is copied and summed per segment
  *          here -, coral_bam_index_sizes / _fill, coral_bam_qc_sizes / _fill, coral_bam_depth_sizes / _fill, coral_bam_reads_sizes / _fill); fails when
  *          an index was requested and the records are not in coordinate order; with nothing requested it does nothing
- *   open_request_to_file  open_request for a want_reads = 2 request in file order whose records go to the BGZF / BAM file
- *          `out_path` WHILE the decode runs, deflated where they are: uncompressed record bytes never leave the device, and the
+ *   CORAL_SINK_BAM  open_request for a want_reads = 2 request in file order (reads_order = 0) whose records go to the BGZF / BAM
+ *          file `path` of the sink WHILE the decode runs, deflated where they are: uncompressed record bytes never leave the device, and the
  *          host keeps two pinned buffers of one chunk whatever the file's size.  The file is exactly coral_bgzf_write_gpu's of
  *          the two parts (header, all written record bytes): each part cut at 0xff00 bytes, the header ending a block, no empty
  *          member, the EOF block last; its bytes do not depend on batch_bytes, chunk_blocks or the run.  `header`: the inflated
@@ -787,17 +787,18 @@ int coral_bam_records_merge(int32_t n_runs, const uint8_t *const *data, const in
  *          chunk are part of *workspace_bytes only for such a request.  Nothing is kept on the host: coral_bam_reads_sizes gives
  *          records written and their inflated bytes, coral_bam_reads_fill is CORAL_ERR_ARG.  On any failure the file is left
  *          without the EOF block (readers see it truncated); `close` closes it.
- *          CORAL_ERR_ARG: want_reads other than 2, world above 1, no out_path, no header, chunk_blocks outside 0..16 384, a
- *          path that cannot be created (and every refusal of open_request).
- *   open_request_to_text  the same for FASTQ: open_request for a want_reads = 1 request whose text goes to the plain file
- *          `out_path` - each batch's text is written where it would be appended to the host-side result (one batch later, once
+ *          CORAL_ERR_ARG: want_reads other than 2, reads_order other than 0, world above 1, no path, no header,
+ *          chunk_blocks outside 0..16 384, a path that cannot be created (and every refusal of a request).  No file is created
+ *          by an open that is refused.
+ *   CORAL_SINK_TEXT  the same for FASTQ: open_request for a want_reads = 1 request whose text goes to the plain file
+ *          `path` of the sink (header and chunk_blocks are ignored) - each batch's text is written where it would be appended to the host-side result (one batch later, once
  *          the next emit or `finish` has synchronised the stream); no compression, no carry, nothing new in the workspace.  The
- *          bytes are those coral_bam_reads_fill would give.  reads_sizes / reads_fill as for open_request_to_file; `finish`
- *          closes the file.  CORAL_ERR_ARG: want_reads other than 1, world above 1, no out_path, a path that cannot be created.
- *   open_request_to_runs / merge_runs  the streamed coordinate sort (coral_bamgpu_merge.h, coral_merge_plan.h), in two phases in
+ *          bytes are those coral_bam_reads_fill would give.  reads_sizes / reads_fill as for CORAL_SINK_BAM; `finish`
+ *          closes the file.  CORAL_ERR_ARG: want_reads other than 1, world above 1, no path, a path that cannot be created.
+ *   CORAL_SINK_RUNS / merge_runs  the streamed coordinate sort (coral_bamgpu_merge.h, coral_merge_plan.h), in two phases in
  *          both of which uncompressed record bytes exist only in device memory.
- *          Phase 1, open_request_to_runs: open_request_ordered with reads_order = 1 for a want_reads = 2 request whose batches'
- *          sorted runs go to the spill file `spill_path` WHILE the decode runs.  Per batch the plan, the key sort, the permute
+ *          Phase 1, CORAL_SINK_RUNS: open_request for a want_reads = 2 request with reads_order = 1 whose batches' sorted runs go
+ *          to the spill file `path` of the sink (header is ignored) WHILE the decode runs.  Per batch the plan, the key sort, the permute
  *          and the two scans run as for an ordered request; k_bam_reads_copy_sorted puts the sorted records at offset 0 of the
  *          sink's buffer and ALL of their blocks are deflated right away (k_bgzf_chunk_desc, k_bgzf_deflate, k_bgzf_pack in
  *          chunks of chunk_blocks), a short last one included: every run is a whole number of BGZF members, every member but a
@@ -807,8 +808,8 @@ int coral_bam_records_merge(int32_t n_runs, const uint8_t *const *data, const in
  *          bytes per written record (16 while coral_bamgpu_merge_runs uploads the keys: the order's 4 bytes join them, then the
  *          keys are freed), a table of the runs and the sink's two pinned chunks - not the records.  The workspace is that of an
  *          ordered request plus the sink's arrays.  coral_bam_reads_sizes gives records and bytes, coral_bam_reads_fill is
- *          CORAL_ERR_ARG, sink_stats describes the spill file.  CORAL_ERR_ARG: want_reads other than 2, world above 1, no
- *          spill_path, chunk_blocks outside 0..16 384, a path that cannot be created (and every refusal of open_request).
+ *          CORAL_ERR_ARG, sink_stats describes the spill file.  CORAL_ERR_ARG: want_reads other than 2, reads_order other than 1,
+ *          world above 1, no path, chunk_blocks outside 0..16 384, a path that cannot be created (and every refusal of open_request).
  *          run_table (after `finish`): counts = runs, written records, bytes of the spill file; table (NULL, or max_runs rows):
  *          per run its first record, records, inflated bytes, file offset.
  *          Phase 2, merge_runs, after `finish` on the same handle, with a workspace of its own of merge_workspace_bytes(handle,
@@ -842,25 +843,22 @@ int coral_bam_records_merge(int32_t n_runs, const uint8_t *const *data, const in
  * dst_off, isize} uint32 (raw DEFLATE streams in `comp`, which must be readable 4096 bytes beyond the last stream);
  * status[b] = 0 or the decoder's error code.
  * ------------------------------------------------------------------------------------------------ */
-int coral_bamgpu_open(const char *path, int32_t n_threads, int32_t rank, int32_t world, int64_t batch_bytes, void **handle,
-                      int64_t *workspace_bytes);
+enum { CORAL_SINK_HOST = 0, CORAL_SINK_TEXT = 1, CORAL_SINK_BAM = 2, CORAL_SINK_RUNS = 3 };
+typedef struct {
+    int32_t kind;                              /* CORAL_SINK_*: where the reads request's result goes */
+    const char *path;                          /* TEXT, BAM, RUNS: the file to create */
+    const uint8_t *header;                     /* BAM: the inflated header to write, copied by the open call ... */
+    int64_t header_bytes;                      /*      ... and its length, > 0 */
+    int32_t chunk_blocks;                      /* BAM, RUNS: blocks per deflate launch, 0 = 1 024, at most 16 384 */
+} coral_bam_sink_t;
 int coral_bamgpu_start(void *handle, void *workspace, int64_t workspace_bytes);
 int coral_bamgpu_next(void *handle, int64_t out[4], void *stream);
 int coral_bamgpu_emit(void *handle, uint32_t *cigar_dst, int64_t *cigar_off_dst, void *stream);
 int coral_bamgpu_host(void *handle, void **decoded);
 int coral_bamgpu_stats(void *handle, int64_t stats[4], double seconds[6]);
 int coral_bamgpu_open_request(const char *path, int32_t n_threads, int64_t batch_bytes, const coral_bam_request_t *req,
-                              void **handle, int64_t *workspace_bytes);
-int coral_bamgpu_open_request_ordered(const char *path, int32_t n_threads, int64_t batch_bytes, const coral_bam_request_t *req,
-                                      int32_t reads_order, void **handle, int64_t *workspace_bytes);
-int coral_bamgpu_open_request_to_file(const char *path, int32_t n_threads, int64_t batch_bytes, const coral_bam_request_t *req,
-                                      const char *out_path, const uint8_t *header, int64_t header_bytes, int32_t chunk_blocks,
-                                      void **handle, int64_t *workspace_bytes);
-int coral_bamgpu_open_request_to_text(const char *path, int32_t n_threads, int64_t batch_bytes, const coral_bam_request_t *req,
-                                      const char *out_path, void **handle, int64_t *workspace_bytes);
+                              const coral_bam_sink_t *sink, void **handle, int64_t *workspace_bytes);
 int coral_bamgpu_sink_stats(void *handle, int64_t out[4]);
-int coral_bamgpu_open_request_to_runs(const char *path, int32_t n_threads, int64_t batch_bytes, const coral_bam_request_t *req,
-                                      const char *spill_path, int32_t chunk_blocks, void **handle, int64_t *workspace_bytes);
 int coral_bamgpu_run_table(void *handle, int64_t max_runs, int64_t *table, int64_t counts[3]);
 int64_t coral_bamgpu_merge_workspace_bytes(void *handle, int64_t stage_bytes);
 int coral_bamgpu_merge_runs(void *handle, const char *out_path, const uint8_t *header, int64_t header_bytes, void *workspace,
@@ -942,7 +940,7 @@ int64_t coral_bgzf_write_gpu_workspace_min_bytes(void);
  *   (0: 128 MiB; the call allocates and frees them), each batch is cut at its last '\n' and the partial line leads the next
  *   one.  Per batch, on `stream`: k_sam_lines (newlines -> line starts), k_sam_size (one wave per line: fields, checks, filter,
  *   bytes), a scan, k_sam_encode (one wave per line: the record at its offset), and the record sink of
- *   coral_bamgpu_open_request_to_file deflates the bytes where they are (chunk_blocks blocks per launch, 0: 1 024).  'f' values
+ *   the CORAL_SINK_BAM sink of coral_bamgpu_open_request deflates the bytes where they are (chunk_blocks blocks per launch, 0: 1 024).  'f' values
  *   outside the exact fast path of the device come back as (text offset, output offset), are converted with strtof from the
  *   pinned text and scattered in before the batch goes to the sink.  The file's bytes depend on the text and the filter alone.
  *   workspace: coral_samgpu_workspace_bytes(batch_bytes, chunk_blocks) bytes of device memory, n_ref / n_slots being those of

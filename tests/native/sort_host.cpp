@@ -1,5 +1,5 @@
 // Stand-alone host build of the host BAM pipeline (coral_amd/csrc/coral_bam.cpp with the shared rules of coral_bam_common.h) for a
-// sanitizer run of the coordinate order (reads_order = 1 of coral_bam_decode_request_ordered) and of coral_bam_records_merge:
+// sanitizer run of the coordinate order (reads_order = 1 of a coral_bam_request_t) and of coral_bam_records_merge:
 // decodes a BAM file in coordinate order - whole, and as 3 byte ranges whose sorted results are merged (the bytes must be equal
 // and in key order) -, merges with 1 and 4 threads (equal bytes), and runs the merge's edge shapes: no run, one run, an empty run
 // between two others, a tie between runs, the refused arguments.
@@ -13,7 +13,8 @@ struct Got { std::vector<uint8_t> data; std::vector<int64_t> off; };
 static Got records(const char *path, coral_bam_request_t q, int order) {
     void *h = nullptr;
     q.want_reads = 2;
-    const int rc = coral_bam_decode_request_ordered(path, 3, &q, order, &h);
+    q.reads_order = order;
+    const int rc = coral_bam_decode_request(path, 3, &q, &h);
     if (rc != CORAL_OK) { fprintf(stderr, "decode of %s failed (%d): %s\n", path, rc, coral_bam_last_error()); exit(2); }
     int64_t sz[2];
     if (coral_bam_reads_sizes(h, sz) != CORAL_OK) exit(3);
@@ -101,9 +102,11 @@ int main(int argc, char **argv) {
     void *h = nullptr;
     coral_bam_request_t q = range_request(0, 1);
     q.want_reads = 2;
-    if (coral_bam_decode_request_ordered(argv[1], 1, &q, 2, &h) != CORAL_ERR_ARG || !strstr(coral_bam_last_error(), "reads_order")) return 14;
+    q.reads_order = 2;
+    if (coral_bam_decode_request(argv[1], 1, &q, &h) != CORAL_ERR_ARG || !strstr(coral_bam_last_error(), "reads_order")) return 14;
     q.want_reads = 1;
-    if (coral_bam_decode_request_ordered(argv[1], 1, &q, 1, &h) != CORAL_ERR_ARG || !strstr(coral_bam_last_error(), "reads_order")) return 15;
+    q.reads_order = 1;
+    if (coral_bam_decode_request(argv[1], 1, &q, &h) != CORAL_ERR_ARG || !strstr(coral_bam_last_error(), "reads_order")) return 15;
     printf("ok\n");
     return 0;
 }

@@ -455,6 +455,35 @@ def test_stale_or_invalid_index_falls_back_and_explicit_ones_raise(case, cpu, tm
     assert np.array_equal(parts[0] + parts[1], want)
 
 
+def test_both_region_decodes_choose_the_same_index(case, cpu, tmp_path):
+    """window_coverage (the coverage request, neighbouring segments joined) and extract_records (the reads request, segments as they
+    are) share one rule for the index of a region decode and leave the same account of it in LAST_DECODE."""
+    import shutil
+    path, regions = str(tmp_path / "p.bam"), [("chr8", 1_300_000, 1_300_500)]
+    shutil.copyfile(case["plain"], path)
+
+    def both(**kw):
+        left = []
+        for call in (bam.window_coverage, bam.extract_records):
+            call(path, regions, device="cpu", **kw)
+            left.append((bam.LAST_DECODE["index"], bam.LAST_DECODE.get("index_skipped"), bam.LAST_DECODE.get("spans")))
+        assert left[0] == left[1], (kw, left)
+        return left[0]
+    assert both() == (None, None, None)                                           # no index beside the file
+    bam.build_index(path, device="cpu")
+    used = both()
+    assert used[:2] == (path + ".bai", None) and used[2] >= 1                     # an index beside the file
+    assert both(index=False) == (None, None, None)
+    assert both(world=2) == (None, None, None)                                    # the default one is not looked for
+    os.utime(path + ".bai", (1, 1))                                               # an index older than the file
+    skipped = both()
+    assert skipped[0] is None and "older" in skipped[1] and skipped[2] is None
+    assert both(index=False) == (None, None, None) and both(world=2) == (None, None, None)
+    for call in (bam.window_coverage, bam.extract_records):                       # a given index does not go with a sharded decode
+        with pytest.raises(ValueError, match="not sharded"):
+            call(path, regions, device="cpu", index=path + ".bai", world=2)
+
+
 def test_cli_index_subcommand(case, cpu, tmp_path, capsys):
     from coral_amd import CoRAL
     out = CoRAL.main(["index", "--lr_bam", case["plain"], "--index", str(tmp_path / "cli.bai"), "--device", "cpu"])

@@ -239,6 +239,28 @@ def test_integration_md_calls_match_the_header():
     assert "MAX_SEGS" not in doc
 
 
+def test_ctypes_structs_match_the_header(tmp_path):
+    """coral_amd/_lib.py: the structs that cross the ABI by pointer have the compiler's size and field offsets
+    (tests/native/abi_layout_host.cpp prints them from include/coral_hip.h), field for field in the header's order."""
+    import subprocess
+    from coral_amd import _lib
+    exe = str(tmp_path / "abi_layout_host")
+    subprocess.run(["g++", "-std=c++17", os.path.join(ROOT, "tests/native/abi_layout_host.cpp"), "-o", exe], check=True, cwd=ROOT)
+    printed = {}
+    for line in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.splitlines():
+        struct, field, value = line.split()
+        printed.setdefault(struct, []).append((field, int(value)))
+    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "coral_hip.h")).read(), flags=re.S)
+    for T in (_lib.coral_bam_request_t, _lib.coral_bam_sink_t):
+        name = T.__name__
+        want = [("sizeof", ctypes.sizeof(T))] + [(f[0], getattr(T, f[0]).offset) for f in T._fields_]
+        assert printed[name] == want, name
+        # and the program names every field the header declares, in its order (a new field is not skipped by both sides)
+        body = re.search(r"typedef struct \{([^}]*)\} %s;" % name, header).group(1)
+        declared = [d.split()[-1].lstrip("*") for stmt in body.split(";") if stmt.strip() for d in stmt.split(",")]
+        assert declared == [f for f, _ in want[1:]], name
+
+
 def test_ctypes_binding_matches_the_header():
     """coral_amd/_lib.py: every argtypes list is as long as the header's prototype."""
     from coral_amd import _lib

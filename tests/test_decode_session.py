@@ -1,7 +1,8 @@
-"""coral_amd/decode_session.py without a GPU: open_handle's choice among the five coral_bamgpu_open_request* entry points, against
-the library itself (an open does no GPU work), and the order in which a DecodeSession calls the library and the device, against a
-stub that records the calls.  The session's two device operations (_alloc, _drain) are overridden and nothing else; what the
-session references is observed through weak references, never through its private attributes."""
+"""coral_amd/decode_session.py without a GPU: the coral_bam_sink_t that open_handle hands to coral_bamgpu_open_request for each kind
+of sink, against the library itself (an open does no GPU work) and against a stub that records what it was given, and the order in
+which a DecodeSession calls the library and the device, against that stub.  The session's two device operations (_alloc, _drain)
+are overridden and nothing else; what the session references is observed through weak references, never through its private
+attributes."""
 import ctypes as C
 import gc
 import os
@@ -16,11 +17,11 @@ from tests.bamfile import M
 from tests.decode_support import CORAL_ERR_ARG, CORAL_OK
 
 CORAL_ERR_HIP = -2
-NEEDS_A_DEVICE = ("coral_bamgpu_open_request_ordered", "coral_bamgpu_open_request_to_runs")
+NEEDS_A_DEVICE = ("no sink, coordinate order", "runs")
 RECORDS, FASTQ, SORTED = (0, None, None, 2), (0, None, None, 1), (0, None, None, 2, 1)
 
 
-# ---- which entry point --------------------------------------------------------------------------------------------------------
+# ---- which sink ---------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def small(tmp_path_factory):
     d = tmp_path_factory.mktemp("decode_session")
@@ -29,10 +30,15 @@ def small(tmp_path_factory):
     return dict(dir=d, path=path, header=bam.bam_header_bytes(path))
 
 
-def direct(L, name, path, request, *args, n_threads=1, batch_bytes=1 << 20):
-    """The entry point ``name`` called as include/coral_hip.h declares it -> (rc, handle granted, ws_bytes, message); closed."""
+def direct(L, path, request, fields, order=None, n_threads=1, batch_bytes=1 << 20):
+    """coral_bamgpu_open_request called as include/coral_hip.h declares it, with the coral_bam_sink_t of ``fields`` = (kind, path,
+    header, header_bytes, chunk_blocks), or NULL for None, and ``order`` (None: as ``request`` has it) in the request's reads_order
+    -> (rc, handle granted, ws_bytes, message); closed."""
     req, h, ws = _lib.bam_request(**request), C.c_void_p(), C.c_int64(0)
-    rc = getattr(L, name)(path.encode(), n_threads, batch_bytes, C.byref(req), *args, C.byref(h), C.byref(ws))
+    if order is not None:
+        req.reads_order = order
+    to = None if fields is None else _lib.coral_bam_sink_t(*fields)
+    rc = L.coral_bamgpu_open_request(path.encode(), n_threads, batch_bytes, C.byref(req), to, C.byref(h), C.byref(ws))
     message = L.coral_bam_last_error().decode()
     if h.value is not None:
         L.coral_bamgpu_close(h)
@@ -49,56 +55,99 @@ def through_open_handle(L, path, request, sink, n_threads=1, batch_bytes=1 << 20
 
 
 def cases(small, sub):
-    """name -> (request, sink, entry point, its own arguments); every sink's file in the directory ``sub``"""
+    """name -> (request, sink, the sink struct's fields: kind, path, header, header_bytes, chunk_blocks, the request's reads_order
+    in the call); every sink's file in the directory ``sub``"""
     out = lambda name: str(sub / name)
     head = small["header"]
     head_ptr = C.cast(C.c_char_p(head), C.c_void_p)
     return {
-        "no sink": (dict(), None, "coral_bamgpu_open_request", ()),
-        "no sink, coordinate order": (dict(reads=SORTED), None, "coral_bamgpu_open_request_ordered", (1,)),
-        "text file": (dict(reads=FASTQ), TextFile(out("x.fastq")), "coral_bamgpu_open_request_to_text", (os.fsencode(out("x.fastq")),)),
-        "BAM file": (dict(reads=RECORDS), BamFile(out("x.bam"), head, 3), "coral_bamgpu_open_request_to_file", (os.fsencode(out("x.bam")), head_ptr, len(head), 3)),
-        "runs": (dict(reads=RECORDS), Runs(out("x.runs.tmp"), 3), "coral_bamgpu_open_request_to_runs", (os.fsencode(out("x.runs.tmp")), 3)),
+        "no sink": (dict(), None, None, 0),
+        "no sink, coordinate order": (dict(reads=SORTED), None, None, 1),
+        "text file": (dict(reads=FASTQ), TextFile(out("x.fastq")), (_lib.SINK_TEXT, os.fsencode(out("x.fastq")), None, 0, 0), 0),
+        "BAM file": (dict(reads=RECORDS), BamFile(out("x.bam"), head, 3), (_lib.SINK_BAM, os.fsencode(out("x.bam")), head_ptr, len(head), 3), 0),
+        "runs": (dict(reads=RECORDS), Runs(out("x.runs.tmp"), 3), (_lib.SINK_RUNS, os.fsencode(out("x.runs.tmp")), None, 0, 3), 1),      # (the sink asks for the order)
     }
 
 
 def test_open_handle_grants_what_the_entry_point_grants(small, tmp_path):
-    """(_ordered and _to_runs size hipcub's sort at open: without a device the library answers CORAL_ERR_HIP, to the direct call
-    and to open_handle alike - the plain entry point would have granted the same request; with a device they are granted like the
-    others.)"""
+    """(reads_order = 1 sizes hipcub's sort at open: without a device the library answers CORAL_ERR_HIP, to the direct call and to
+    open_handle alike - the same request in file order would have been granted; with a device they are granted like the others.)"""
     L, sizes = _lib.lib(), {}
-    for name, (request, sink, entry, args) in cases(small, tmp_path).items():
-        want = direct(L, entry, small["path"], request, *args)
+    for name, (request, sink, fields, order) in cases(small, tmp_path).items():
+        want = direct(L, small["path"], request, fields, order)
         got = through_open_handle(L, small["path"], request, sink)
         if want[0] == CORAL_ERR_HIP and not torch.cuda.is_available():
-            assert entry in NEEDS_A_DEVICE and "sort" in want[3], (name, want)
+            assert name in NEEDS_A_DEVICE and "sort" in want[3], (name, want)
         else:
             assert want[:2] == (CORAL_OK, True) and want[2] > 0, (name, want)
             sizes[name] = got[2]
         assert got == want, name
-    # they carve differently: a call that went to another entry point would not have returned this size
+    # they carve differently: a call that described another sink would not have returned this size
     assert sizes["no sink"] < sizes["BAM file"] and len(set(sizes.values())) == len(sizes) >= 3, sizes
 
 
 def test_open_handle_refuses_what_the_entry_point_refuses(small, tmp_path):
     L, c = _lib.lib(), cases(small, tmp_path)
     path = small["path"]
+    text, bam_file, runs = c["text file"][2], c["BAM file"][2], c["runs"][2]
     bad = {                                                      # the case's request or sink with one thing wrong -> a word of the message
-        "no sink": (dict(rank=2, world=2), None, (), "rank"),
-        "no sink, coordinate order": (dict(reads=FASTQ + (1,)), None, (1,), "reads_order"),          # (the plain entry point grants it)
-        "text file": (dict(reads=RECORDS), c["text file"][1], c["text file"][3], "want_reads"),
-        "BAM file": (dict(reads=RECORDS), c["BAM file"][1]._replace(header=None), (c["BAM file"][3][0], None, 0, 3), "header"),
-        "runs": (dict(reads=RECORDS), c["runs"][1]._replace(chunk_blocks=16385), (c["runs"][3][0], 16385), "chunk_blocks"),
-        "runs, no path": (dict(reads=RECORDS), Runs(None, 3), (None, 3), "path"),
+        "no sink": (dict(rank=2, world=2), None, None, 0, "rank"),
+        "no sink, coordinate order": (dict(reads=FASTQ + (1,)), None, None, 1, "reads_order"),       # (in file order it is granted)
+        "text file": (dict(reads=RECORDS), c["text file"][1], text, 0, "want_reads"),
+        "BAM file": (dict(reads=RECORDS), c["BAM file"][1]._replace(header=None), bam_file[:2] + (None, 0, 3), 0, "header"),
+        "runs": (dict(reads=RECORDS), c["runs"][1]._replace(chunk_blocks=16385), runs[:4] + (16385,), 1, "chunk_blocks"),
+        "runs, no path": (dict(reads=RECORDS), Runs(None, 3), (_lib.SINK_RUNS, None, None, 0, 3), 1, "path"),
     }
-    for name, (request, sink, args, word) in bad.items():
-        entry = c[name.split(",")[0] if name.startswith("runs") else name][2]
-        want = direct(L, entry, path, request, *args)
+    for name, (request, sink, fields, order, word) in bad.items():
+        want = direct(L, path, request, fields, order)
         got = through_open_handle(L, path, request, sink)
         assert want[:3] == (CORAL_ERR_ARG, False, 0) and word in want[3], (name, want)
         assert got == want, name
     with pytest.raises(TypeError):
         open_handle(L, path, 1, 0, _lib.bam_request(), (str(tmp_path / "x"), None, 0))       # (the tuple of before is not a sink)
+
+
+def test_the_one_open_call_refuses_before_any_device_call(small, tmp_path):
+    """The rules of reads_order and of the sink kinds, on both pipelines where both have them; nothing is created, no handle is given."""
+    L, path = _lib.lib(), small["path"]
+    out = os.fsencode(str(tmp_path / "never"))
+    head = C.cast(C.c_char_p(small["header"]), C.c_void_p)
+    assert direct(L, path, dict(reads=RECORDS), (7, out, head, len(small["header"]), 0))[:3] == (CORAL_ERR_ARG, False, 0)       # an unknown kind
+    assert direct(L, path, dict(reads=RECORDS), (-1, out, None, 0, 0))[:3] == (CORAL_ERR_ARG, False, 0)
+    for request in (dict(reads=RECORDS + (2,)), dict(reads=FASTQ + (1,)), dict()):          # reads_order = 2; = 1 without want_reads = 2
+        req, h = _lib.bam_request(**request), C.c_void_p()
+        if not request:
+            req.reads_order = 1
+        assert L.coral_bam_decode_request(path.encode(), 1, C.byref(req), C.byref(h)) == CORAL_ERR_ARG and h.value is None, request
+        assert "reads_order" in L.coral_bam_last_error().decode(), request
+        ws = C.c_int64(0)
+        assert L.coral_bamgpu_open_request(path.encode(), 1, 0, C.byref(req), None, C.byref(h), C.byref(ws)) == CORAL_ERR_ARG and h.value is None, request
+        assert "reads_order" in L.coral_bam_last_error().decode() and ws.value == 0, request
+    got = direct(L, path, dict(reads=SORTED), (_lib.SINK_BAM, out, head, len(small["header"]), 0))       # a BAM file is written in file order
+    assert got[:3] == (CORAL_ERR_ARG, False, 0) and "reads_order must be 0" in got[3], got
+    got = direct(L, path, dict(reads=RECORDS), (_lib.SINK_RUNS, out, None, 0, 0))                          # runs are sorted
+    assert got[:3] == (CORAL_ERR_ARG, False, 0) and "reads_order must be 1" in got[3], got
+    assert not os.path.exists(out)
+    # the host kind reads none of the other fields: garbage there opens like NULL
+    plain = direct(L, path, dict(reads=RECORDS), None)
+    assert plain[:2] == (CORAL_OK, True) and direct(L, path, dict(reads=RECORDS), (_lib.SINK_HOST, b"/no/such/dir/x", 0x10, -5, 99999)) == plain
+    assert not os.path.exists(out)
+
+
+def test_open_handle_fills_the_sink_struct(small, tmp_path):
+    """What the one call is given: the fs-encoded path, the header's bytes and length, chunk_blocks, and the order in the request."""
+    head = small["header"]
+    for name, (request, sink, fields, order) in cases(small, tmp_path).items():
+        stub = StubLib()
+        rc, h, ws = open_handle(stub, small["path"], 2, 1 << 20, _lib.bam_request(**request), sink)
+        assert (rc, h.value, ws) == (CORAL_OK, 0x1000, WS_BYTES) and stub.opened[:3] == (small["path"].encode(), 2, 1 << 20), name
+        assert stub.opened[3] == order, name
+        if fields is None:
+            assert stub.opened[4] is None, name
+        else:
+            kind, path, header, header_bytes, chunk_blocks = stub.opened[4]
+            assert (kind, path, header_bytes, chunk_blocks) == (fields[0], fields[1], fields[3], fields[4]), name
+            assert header == (head if fields[2] is not None else None), name
 
 
 # ---- the call order -----------------------------------------------------------------------------------------------------------
@@ -121,8 +170,10 @@ class StubLib:
     def coral_bam_last_error(self):
         return b"the stub says no"
 
-    def coral_bamgpu_open_request(self, path, n_threads, batch_bytes, req, h, ws_bytes):
+    def coral_bamgpu_open_request(self, path, n_threads, batch_bytes, req, sink, h, ws_bytes):
         rc = self.rc("open")
+        to = None if sink is None else (sink.kind, sink.path, None if not sink.header else C.string_at(sink.header, sink.header_bytes), sink.header_bytes, sink.chunk_blocks)
+        self.opened = (path, n_threads, batch_bytes, req._obj.reads_order, to)
         if rc == CORAL_OK:
             h._obj.value, ws_bytes._obj.value = 0x1000, WS_BYTES
         return rc

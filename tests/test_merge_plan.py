@@ -158,21 +158,22 @@ def test_native_program(tmp_path):
 
 def test_the_library_exports_the_new_calls():
     L = _lib.lib()
-    for name in ("coral_bamgpu_open_request_to_runs", "coral_bamgpu_run_table", "coral_bamgpu_merge_workspace_bytes", "coral_bamgpu_merge_runs",
+    for name in ("coral_bamgpu_open_request", "coral_bamgpu_run_table", "coral_bamgpu_merge_workspace_bytes", "coral_bamgpu_merge_runs",
                  "coral_bamgpu_merge_stats", "coral_merge_plan"):
         assert getattr(L, name).argtypes is not None, name
     with open(os.path.join(ROOT, "include", "coral_hip.h")) as fp:
         header = fp.read()
-    for name in ("coral_bamgpu_open_request_to_runs(", "coral_bamgpu_run_table(", "coral_bamgpu_merge_workspace_bytes(", "coral_bamgpu_merge_runs(",
+    for name in ("coral_bamgpu_open_request(", "CORAL_SINK_RUNS", "coral_bamgpu_run_table(", "coral_bamgpu_merge_workspace_bytes(", "coral_bamgpu_merge_runs(",
                  "coral_bamgpu_merge_stats(", "coral_merge_plan("):
         assert name in header, name
     # neither call needs a GPU to refuse a handle that is none
-    assert L.coral_bamgpu_merge_workspace_bytes(None, 0) == CORAL_ERR_ARG and "coral_bamgpu_open_request_to_runs" in L.coral_bam_last_error().decode()
+    assert L.coral_bamgpu_merge_workspace_bytes(None, 0) == CORAL_ERR_ARG and "coral_bamgpu_open_request (runs sink)" in L.coral_bam_last_error().decode()
     assert L.coral_bamgpu_merge_runs(None, b"x", None, 0, None, 0, 0, None) == CORAL_ERR_ARG
     assert L.coral_bamgpu_run_table(None, 0, None, (C.c_int64 * 3)()) == CORAL_ERR_ARG
 
 
-def test_open_to_runs_refuses_what_open_to_file_refuses(tmp_path):
+def test_the_runs_sink_refuses_what_the_bam_sink_refuses(tmp_path):
+    """(the runs sink of coral_bamgpu_open_request and its BAM sink)"""
     from tests.test_sort_records import raw_record
     from tests.test_extract_reads import write_raw
     header = b"BAM\x01" + (0).to_bytes(4, "little") + (1).to_bytes(4, "little") + (5).to_bytes(4, "little") + b"chr1\0" + (1000).to_bytes(4, "little")
@@ -182,11 +183,12 @@ def test_open_to_runs_refuses_what_open_to_file_refuses(tmp_path):
 
     def open_runs(req, spill_path=spill, chunk_blocks=0):
         h, ws = C.c_void_p(), C.c_int64(0)
-        rc = L.coral_bamgpu_open_request_to_runs(path.encode(), 1, 0, C.byref(req), None if spill_path is None else os.fsencode(spill_path), chunk_blocks, C.byref(h), C.byref(ws))
+        to = _lib.coral_bam_sink_t(_lib.SINK_RUNS, None if spill_path is None else os.fsencode(spill_path), None, 0, chunk_blocks)
+        rc = L.coral_bamgpu_open_request(path.encode(), 1, 0, C.byref(req), to, C.byref(h), C.byref(ws))
         if h.value is not None:
             L.coral_bamgpu_close(h)
         return rc, L.coral_bam_last_error().decode()
-    records = lambda **kw: _lib.bam_request(reads=(0, None, None, 2), **kw)
+    records = lambda **kw: _lib.bam_request(reads=(0, None, None, 2, 1), **kw)
     for req, kw, word in ((_lib.bam_request(reads=(0, None, None, 1)), {}, "want_reads"), (_lib.bam_request(), {}, "want_reads"),
                           (records(rank=1, world=2), {}, "world"), (records(), dict(spill_path=None), "spill path"),
                           (records(), dict(chunk_blocks=-1), "chunk_blocks"), (records(), dict(chunk_blocks=16385), "chunk_blocks"),

@@ -1,5 +1,5 @@
 """Coordinate order during the BAM decode (bam.extract_records(order="coordinate"), bam.sort_bam, the `sort` mode; reads_order = 1
-of coral_bam_decode_request_ordered / coral_bamgpu_open_request_ordered; coral_bam_records_merge), on both pipelines.
+of the request, coral_bam_decode_request / coral_bamgpu_open_request; coral_bam_records_merge), on both pipelines.
 
 The contract is one key and stability:
     key = (uint32)tid << 32 | (uint32)(pos + 1) << 1 | (flag >> 4 & 1)
@@ -336,15 +336,16 @@ def test_both_entry_points_refuse_a_bad_order(case):
     path = case["path"].encode()
     for name, (kw, order) in BAD_ORDERS.items():
         req, h, ws = _lib.bam_request(**kw), C.c_void_p(), C.c_int64(0)
-        assert L.coral_bam_decode_request_ordered(path, 1, C.byref(req), order, C.byref(h)) == CORAL_ERR_ARG and h.value is None, name
+        req.reads_order = order
+        assert L.coral_bam_decode_request(path, 1, C.byref(req), C.byref(h)) == CORAL_ERR_ARG and h.value is None, name
         assert "reads_order" in L.coral_bam_last_error().decode(), (name, L.coral_bam_last_error().decode())
-        assert L.coral_bamgpu_open_request_ordered(path, 1, 0, C.byref(req), order, C.byref(h), C.byref(ws)) == CORAL_ERR_ARG, name
+        assert L.coral_bamgpu_open_request(path, 1, 0, C.byref(req), None, C.byref(h), C.byref(ws)) == CORAL_ERR_ARG, name
         assert h.value is None and ws.value == 0 and "reads_order" in L.coral_bam_last_error().decode(), name
-    # the rules of the request itself still come first, and order 0 is what the old entry points ask for
-    req, h = _lib.bam_request(reads=(0, None, None, 3)), C.c_void_p()
-    assert L.coral_bam_decode_request_ordered(path, 1, C.byref(req), 1, C.byref(h)) == CORAL_ERR_ARG and "want_reads" in L.coral_bam_last_error().decode()
+    # the other rules of the request still come first, and order 0 is what a zeroed field asks for
+    req, h = _lib.bam_request(reads=(0, None, None, 3, 1)), C.c_void_p()
+    assert L.coral_bam_decode_request(path, 1, C.byref(req), C.byref(h)) == CORAL_ERR_ARG and "want_reads" in L.coral_bam_last_error().decode()
     req = _lib.bam_request(reads=(0, None, [b"tie_a", b"tie_b"], 2))
-    assert L.coral_bam_decode_request_ordered(path, 2, C.byref(req), 0, C.byref(h)) == CORAL_OK
+    assert L.coral_bam_decode_request(path, 2, C.byref(req), C.byref(h)) == CORAL_OK
     sz = (C.c_int64 * 2)()
     assert L.coral_bam_reads_sizes(h, sz) == CORAL_OK and sz[0] == 2
     L.coral_bam_decode_close(h)
@@ -357,12 +358,12 @@ def test_both_entry_points_refuse_a_bad_order(case):
 
 
 @pytest.mark.gpu
-def test_only_an_ordered_request_carves_the_sort_arrays(case):
+def test_only_coordinate_order_carves_the_sort_arrays(case):
     L = _lib.lib()
     sizes = {}
     for order in (0, 1):
-        req, h, ws = _lib.bam_request(reads=(0, None, None, 2)), C.c_void_p(), C.c_int64(0)
-        assert L.coral_bamgpu_open_request_ordered(case["path"].encode(), 1, 0, C.byref(req), order, C.byref(h), C.byref(ws)) == CORAL_OK
+        req, h, ws = _lib.bam_request(reads=(0, None, None, 2, order)), C.c_void_p(), C.c_int64(0)
+        assert L.coral_bamgpu_open_request(case["path"].encode(), 1, 0, C.byref(req), None, C.byref(h), C.byref(ws)) == CORAL_OK
         L.coral_bamgpu_close(h)
         sizes[order] = ws.value
     assert sizes[0] == gpu_open_only(case["path"], reads=(0, None, None, 2))[2] < sizes[1]

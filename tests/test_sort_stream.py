@@ -1,4 +1,4 @@
-"""The streamed coordinate sort (bam.sort_bam_stream, bam.sort_bam(stream=True), `sort --stream`; coral_bamgpu_open_request_to_runs,
+"""The streamed coordinate sort (bam.sort_bam_stream, bam.sort_bam(stream=True), `sort --stream`; the CORAL_SINK_RUNS sink of coral_bamgpu_open_request,
 coral_bamgpu_merge_runs): sorted runs spilled to disk while the file is decoded, merged on the GPU.
 
 Every expected byte comes from tests/bamfile.parse, the selection rule restated in test_extract_records and Python's stable
@@ -88,7 +88,7 @@ def plan_inputs(runs):
 # ---- the C ABI: phase 1 alone, and the merge on its handle ---------------------------------------------------------------------------
 @contextlib.contextmanager
 def runs_decode(path, spill, batch_bytes=SMALL_BATCH, chunk_blocks=0, exclude_flags=0, record_filter=None):
-    """open_request_to_runs, the batches and `finish`; yields the DecodeSession (L, h, stream, dev, dh) with the run table (rows of
+    """open_request with a runs sink, the batches and `finish`; yields the DecodeSession (L, h, stream, dev, dh) with the run table (rows of
     first record, records, inflated bytes, file offset) and counts (runs, records, spill bytes).  Closed on every way out."""
     with gpu_decode(path, 2, batch_bytes, Runs(spill, chunk_blocks), keep=record_filter, reads=(exclude_flags, None, None, 2)) as d:
         L, counts = d.L, (C.c_int64 * 3)()
@@ -331,14 +331,14 @@ def test_the_other_entry_points_carve_what_they_carved(case, tmp_path):
 
     def sizes():
         got = {}
-        req = lambda: _lib.bam_request(reads=(0, None, None, 2))
+        head = C.cast(C.c_char_p(b"BAM\x01"), C.c_void_p)
         h, ws = C.c_void_p(), C.c_int64(0)
         got["plain"] = gpu_open_only(case["path"], reads=(0, None, None, 2))[2]
-        for name, call in (("ordered", lambda r: L.coral_bamgpu_open_request_ordered(path, 1, 0, C.byref(r), 1, C.byref(h), C.byref(ws))),
-                           ("to_file", lambda r: L.coral_bamgpu_open_request_to_file(path, 1, 0, C.byref(r), os.fsencode(str(tmp_path / "f.bam")), b"BAM\x01", 4, 5, C.byref(h),
-                                                                                      C.byref(ws))),
-                           ("to_runs", lambda r: L.coral_bamgpu_open_request_to_runs(path, 1, 0, C.byref(r), os.fsencode(str(tmp_path / "r.tmp")), 5, C.byref(h), C.byref(ws)))):
-            assert call(req()) == CORAL_OK, L.coral_bam_last_error().decode()
+        for name, order, to in (("ordered", 1, None),
+                                ("to_file", 0, _lib.coral_bam_sink_t(_lib.SINK_BAM, os.fsencode(str(tmp_path / "f.bam")), head, 4, 5)),
+                                ("to_runs", 1, _lib.coral_bam_sink_t(_lib.SINK_RUNS, os.fsencode(str(tmp_path / "r.tmp")), None, 0, 5))):
+            req = _lib.bam_request(reads=(0, None, None, 2, order))
+            assert L.coral_bamgpu_open_request(path, 1, 0, C.byref(req), to, C.byref(h), C.byref(ws)) == CORAL_OK, L.coral_bam_last_error().decode()
             L.coral_bamgpu_close(h)
             got[name] = ws.value
         return got

@@ -1,4 +1,4 @@
-"""bam.view_bam / coral_bamgpu_open_request_to_file: the selected records of a BAM file streamed to a BAM file while the decode
+"""bam.view_bam / the CORAL_SINK_BAM sink of coral_bamgpu_open_request: the selected records of a BAM file streamed to a BAM file while the decode
 runs, each batch's records deflated on the device.  Expected bytes are restated from the parsed fixture (tests/bamfile.py, the
 rule of tests/test_extract_records.py) and checked through gzip.decompress - which checks every member's CRC -, never taken from
 the code under test; the byte-identity partner is extract_records(...).write(device=gpu), the in-memory path."""
@@ -301,8 +301,8 @@ def view_of(src, out, *args, **kw):
 
 
 # ---- 8. nothing is kept on the host (the C ABI) ----------------------------------------------------------------------------------
-def open_to_file(path, out_path, header, chunk_blocks=0, batch_bytes=SMALL_BATCH, **request):
-    """coral_bamgpu_open_request_to_file alone -> (rc, handle, ws_bytes, message, the request - it owns the arrays)."""
+def open_bam_sink(path, out_path, header, chunk_blocks=0, batch_bytes=SMALL_BATCH, **request):
+    """coral_bamgpu_open_request with a BAM sink alone -> (rc, handle, ws_bytes, message, the request - it owns the arrays)."""
     L, req = _lib.lib(), _lib.bam_request(**request)
     rc, h, ws_bytes = open_handle(L, path, 2, batch_bytes, req, BamFile(out_path, header, chunk_blocks))
     return rc, h, ws_bytes, L.coral_bam_last_error().decode(), req
@@ -330,13 +330,13 @@ def test_the_c_abi_keeps_nothing_on_the_host(case, tmp_path):
 
 # ---- 9. refusals at open (no GPU work) -------------------------------------------------------------------------------------------
 def test_open_refuses(case, tmp_path):
-    # (reads_order = 1 cannot be asked for: the entry point takes no reads_order, file order is all there is)
     L, out = _lib.lib(), str(tmp_path / "refused.bam")
     records = (0, None, None, 2)
     bad = {
         "want_reads = 0": (dict(), {}, "want_reads"),
         "want_reads = 1": (dict(reads=(0, None, None, 1)), {}, "want_reads"),
         "with an index request": (dict(reads=records, index=True), {}, "want_reads"),
+        "coordinate order": (dict(reads=records + (1,)), {}, "reads_order"),
         "a byte range": (dict(reads=records, rank=0, world=2), {}, "world"),
         "chunk_blocks = -1": (dict(reads=records), dict(chunk_blocks=-1), "chunk_blocks"),
         "chunk_blocks = 16 385": (dict(reads=records), dict(chunk_blocks=16385), "chunk_blocks"),
@@ -347,7 +347,7 @@ def test_open_refuses(case, tmp_path):
     for name, (request, args, word) in bad.items():
         a = dict(out_path=out, header=case["header"])
         a.update(args)
-        rc, h, ws_bytes, message, keep = open_to_file(case["path"], a["out_path"], a["header"], a.get("chunk_blocks", 0), **request)
+        rc, h, ws_bytes, message, keep = open_bam_sink(case["path"], a["out_path"], a["header"], a.get("chunk_blocks", 0), **request)
         assert rc == CORAL_ERR_ARG and h.value is None and ws_bytes == 0, name
         assert word in message, (name, message)
         assert not os.path.exists(out), name                     # nothing is created for a request that is refused
@@ -356,16 +356,16 @@ def test_open_refuses(case, tmp_path):
 
 
 def test_a_request_without_a_sink_carves_what_it_carved(case, tmp_path):
-    """The sink's arrays are part of the workspace only for a sink request (and the older entry points are the new one without one)."""
+    """The sink's arrays are part of the workspace only for a sink request (NULL and CORAL_SINK_HOST are the same: no sink)."""
     L = _lib.lib()
     req, h, plain = _lib.bam_request(reads=(0, None, None, 2)), C.c_void_p(), C.c_int64(0)
-    assert L.coral_bamgpu_open_request(case["path"].encode(), 1, SMALL_BATCH, C.byref(req), C.byref(h), C.byref(plain)) == CORAL_OK
+    assert L.coral_bamgpu_open_request(case["path"].encode(), 1, SMALL_BATCH, C.byref(req), None, C.byref(h), C.byref(plain)) == CORAL_OK
     stats = (C.c_int64 * 4)()
     assert L.coral_bamgpu_sink_stats(h, stats) == CORAL_ERR_ARG and "no file" in L.coral_bam_last_error().decode()
     L.coral_bamgpu_close(h)
     sizes = {}
     for chunk in (1, 8):
-        rc, h, ws_bytes, message, keep = open_to_file(case["path"], str(tmp_path / "x.bam"), case["header"], chunk, reads=(0, None, None, 2))
+        rc, h, ws_bytes, message, keep = open_bam_sink(case["path"], str(tmp_path / "x.bam"), case["header"], chunk, reads=(0, None, None, 2))
         assert rc == CORAL_OK, message
         L.coral_bamgpu_close(h)
         sizes[chunk] = ws_bytes
