@@ -11,7 +11,8 @@ caller starts from), `fastq` (selected reads as FASTQ, by regions or read names)
 the records themselves, with its index on request) and `sort` (the kept records in coordinate order as a BAM file, with its
 index on request: lines 42-50 of the reference's scripts/align_nanopore_reads.sh from one decode) and `import` (the mapper's
 SAM text as the BAM file `sort` opens: line 38 of that script) and `cnv` (the .cns of segmented copy number and the seed
-intervals that `reconstruct` starts from: scripts/call_cnvs.sh and the seed mode, from the binned depth); the other modes of the
+intervals that `reconstruct` starts from: scripts/call_cnvs.sh and the seed mode, from the binned depth) and `kmers` (the
+reference genome's repetitive k-mers, the list the mapper takes with -W: lines 29-30 of that script); the other modes of the
 reference (seed, plot, cycle2bed) are untouched and are delegated to the reference's own modules when they are
 importable (set CORAL_REFERENCE_SRC to the reference's src/ directory).  The cycle-decomposition step after the graph build is the
 reference's (Gurobi); it runs on the object this module returns.
@@ -168,6 +169,18 @@ def build_parser():
     cp.add_argument("--min_seed_size", help="Minimum summed length of a seed.", type=int, default=99999)
     cp.add_argument("--max_seg_gap", help="Maximum gap between the segments of one seed.", type=int, default=300001)
     cp.add_argument("--device", help="GPU to use ('cpu': the host backend).", default="cuda:0")
+    kp = sub.add_parser("kmers", help="Count a reference's k-mers and write the repetitive ones (the mapper's -W list) from its FASTA file.")
+    kp.add_argument("--ref", help="Reference genome, FASTA (a name ending in .gz is inflated on the host).", required=True)
+    kp.add_argument("--output", help="Name of the output file (KMER<tab>COUNT lines).", required=True)
+    kp.add_argument("--k", help="K-mer size, 1..16.", type=int, default=15)
+    cut = kp.add_mutually_exclusive_group()
+    cut.add_argument("--distinct", help="Write the k-mers above the count that this fraction of the distinct k-mers stays at or below (default 0.9998).")
+    cut.add_argument("--greater_than", help="Write the k-mers with a count above this, in place of --distinct.", type=int)
+    kp.add_argument("--forward", help="Count every k-mer as it stands, not under the smaller of itself and its reverse complement.", action='store_true')
+    kp.add_argument("--both_strands", help="Write every k-mer's reverse complement behind it.", action='store_true')
+    kp.add_argument("--histogram", help="Also write the histogram (count<tab>kmers lines) to this file.")
+    kp.add_argument("--chunk_bytes", help="Bytes of the FASTA file per piece.", type=int, default=64 << 20)
+    kp.add_argument("--device", help="GPU to use ('cpu': the host backend, one thread).", default="cuda:0")
     for p in (rp, hp, qp, pp, dp, fp, vp, sp, mp, cp):
         add_filter_arguments(p)
     for mode in ("seed", "plot", "cycle2bed"):
@@ -387,6 +400,20 @@ def cnv_mode(args):
     return args.output
 
 
+def kmers_mode(args):
+    """The repetitive k-mers of --ref (kmers.repetitive_kmers): lines 29-30 of the reference's scripts/align_nanopore_reads.sh, the
+    file the mapper takes with -W."""
+    from coral_amd import kmers
+    kc = kmers.repetitive_kmers(args.ref, args.output, args.k, args.distinct, args.greater_than, canonical=not args.forward, both_strands=args.both_strands,
+                                device=args.device, chunk_bytes=args.chunk_bytes)
+    print("n_sequences: %d\nn_bases: %d\ntotal: %d\ndistinct: %d\nthreshold: %d" % (kc.n_sequences, kc.n_bases, kc.total, kc.distinct, kc.threshold_used))
+    print("Wrote %s (%d lines)" % (args.output, kc.lines_written))
+    if args.histogram:
+        print("Wrote %s (%d lines)" % (args.histogram, kc.write_histogram(args.histogram)))
+    kc.close()
+    return args.output
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     if argv and argv[0] in ("seed", "plot", "cycle2bed"):
@@ -428,6 +455,8 @@ def main(argv=None):
         return import_mode(args)
     if args.mode == "cnv":
         return cnv_mode(args)
+    if args.mode == "kmers":
+        return kmers_mode(args)
     parser.print_help()
     return None
 

@@ -218,6 +218,18 @@ def lib():
     L.coral_cn_segment_gpu.argtypes = [C.c_int32] + L.coral_cn_segment_host.argtypes + [P, C.c_int64, P, P]
     L.coral_cn_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64]
     L.coral_cn_workspace_bytes.restype = C.c_int64
+    L.coral_kmer_table_bytes.argtypes = [C.c_int32]
+    L.coral_kmer_table_bytes.restype = C.c_int64
+    L.coral_kmer_workspace_bytes.argtypes = [C.c_int32, C.c_int64]
+    L.coral_kmer_workspace_bytes.restype = C.c_int64
+    L.coral_kmer_geometry.argtypes = [P]
+    L.coral_kmer_open.argtypes = [C.c_int32, C.c_int32, C.c_int32, P, C.c_int64, P, C.c_int64, P, C.c_int64, C.POINTER(C.c_void_p)]
+    L.coral_kmer_feed.argtypes = [C.c_void_p, P, C.c_int64]
+    L.coral_kmer_finish.argtypes = [C.c_void_p, P, P]
+    L.coral_kmer_histogram.argtypes = [C.c_void_p, C.c_int64, P, P]
+    L.coral_kmer_select.argtypes = [C.c_void_p, C.c_int64, C.c_int64, P, P, C.POINTER(C.c_int64)]
+    L.coral_kmer_lookup.argtypes = [C.c_void_p, P, C.c_int64, P]
+    L.coral_kmer_close.argtypes = [C.c_void_p]
     for name in ("coral_bgzf_deflate_scratch_bytes", "coral_bgzf_pack_scratch_bytes"):
         getattr(L, name).argtypes = [C.c_int32]
         getattr(L, name).restype = C.c_int64

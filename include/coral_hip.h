@@ -1007,6 +1007,68 @@ int coral_cn_segment_gpu(int32_t device, int32_t n_contigs, const int64_t *bin_o
                          void *stream, double *seconds);
 int64_t coral_cn_workspace_bytes(int64_t n_bins, int32_t n_contigs, int32_t levels, int32_t has_reference, int64_t row_cap);
 
+/* ------------------------------------------------------------------------------------------------
+ * The k-mers of a reference genome (`kmers`): what lines 29-30 of the reference's scripts/align_nanopore_reads.sh get from
+ * `meryl count k=15 output merylDB ref.fa` and `meryl print greater-than distinct=0.9998 merylDB > repetitive_k15.txt`, the
+ * list the mapper takes with -W.  Parity with meryl's rounding of distinct=, its choice between a k-mer and its reverse
+ * complement and its print order is not claimed (meryl was not available); the rule (coral_kmer_core.h) is what
+ * both backends compute, exactly:
+ *   text      FASTA bytes, fed in pieces of any size; the result does not depend on the cuts.  A line starts at the first byte
+ *             and behind every '\n'; a line whose first byte is '>' is a header: its '>' is one break, the rest up to and
+ *             including its '\n' is skipped.  '\n' and '\r' are skipped anywhere; ACGTacgt are the bases 0..3; any other byte
+ *             is a break.
+ *   k-mers    every window of k consecutive bases without a break, 1 <= k <= 16, as a 2k-bit integer with the first base in
+ *             the top bits; canonical != 0: the smaller of the window and its reverse complement.
+ *   table     4^k uint32 counters (coral_kmer_table_bytes), index = the k-mer, the caller's memory, zeroed by the caller (or
+ *             holding an earlier count of bases_before bases to add to).  2^32 bases or more in all: CORAL_ERR_CAPACITY, so no
+ *             counter wraps.
+ * A session, so that the caller owns the reading of the file:
+ *   open      (lines 29-30: the count) device < 0: the host backend, one thread, `table` in host memory; staging_bytes,
+ *             workspace and stream are ignored.  device >= 0: `table` and `workspace` (coral_kmer_workspace_bytes(k,
+ *             staging_bytes); the library allocates no device memory) are device memory, the kernels run on `stream`; the session
+ *             owns two pinned staging buffers of staging_bytes (16 .. 2^30) and a copy stream.
+ *   feed      (line 29) the next n bytes.  Device: copied into a staging buffer (waiting only for that buffer's use two pieces
+ *             earlier), header lines found on the host (memchr), uploaded on the copy stream beside the kernels of the piece
+ *             before; then on `stream`: scan of the keep flags, k_kmer_scatter, k_kmer_count (one no-return atomicAdd per run
+ *             of equal indices of a thread's 32 symbols), k_kmer_carry.  No host wait for the kernels.
+ *   finish    (line 30: what `distinct=` is computed from) waits; stats[0..5] (8 entries) = n_sequences (header lines), n_bases,
+ *             total (k-mers counted), distinct (non-zero entries), the number of different count values, the largest count.
+ *             seconds[0..3] (or NULL) = upload, classify + compact, count (host: the whole feed), statistics.
+ *   histogram (line 30) the exact histogram, rising: values[i] = a count, numbers[i] = the distinct k-mers with it; capacity
+ *             below stats[4]: CORAL_ERR_CAPACITY.
+ *   select    (line 30: `print greater-than`) the entries with a count above greater_than in table order: kmers[i], counts[i];
+ *             *n = how many there are; *n > capacity: CORAL_ERR_CAPACITY with the first `capacity` written - ask again with *n.
+ *             Device sessions: kmers and counts are device memory; a count per 4 096-entry tile, a scan, a ranked write.
+ *   lookup    (line 30) counts[i] = table[indices[i]] (0 for an index outside the table); device sessions: device memory.
+ *   close     frees the session (never the table or the workspace).
+ * coral_kmer_geometry (lines 29-30: the kernels of both) -> geometry[0..7] = symbols per thread and threads per workgroup of
+ *   k_kmer_count, entries per workgroup tile and threads of the table passes (k_kmer_stats, k_kmer_sel_*), the symbols carried
+ *   between pieces, bytes per workgroup of k_kmer_scatter, the histogram bins kept in LDS, the first count that is listed
+ *   rather than binned.
+ * Errors go to coral_bam_last_error.
+ * ------------------------------------------------------------------------------------------------ */
+/* lines 29-30 of scripts/align_nanopore_reads.sh: the bytes of meryl's count table for k */
+int64_t coral_kmer_table_bytes(int32_t k);
+/* line 29: the device scratch of a counting session */
+int64_t coral_kmer_workspace_bytes(int32_t k, int64_t staging_bytes);
+/* lines 29-30: the launch geometry of the kernels behind both */
+int coral_kmer_geometry(int32_t *geometry);
+/* line 29 (`meryl count k=15 output merylDB ref.fa`): a counting session */
+int coral_kmer_open(int32_t k, int32_t canonical, int32_t device, void *table, int64_t staging_bytes, void *workspace,
+                    int64_t workspace_bytes, void *stream, int64_t bases_before, void **handle);
+/* line 29: the next bytes of ref.fa */
+int coral_kmer_feed(void *handle, const uint8_t *bytes, int64_t n);
+/* line 30 (`distinct=0.9998` needs them): the statistics of the finished count */
+int coral_kmer_finish(void *handle, int64_t *stats, double *seconds);
+/* line 30: the histogram `distinct=` is resolved against (`meryl histogram`) */
+int coral_kmer_histogram(void *handle, int64_t capacity, int64_t *values, int64_t *numbers);
+/* line 30 (`meryl print greater-than`): the k-mers above a count */
+int coral_kmer_select(void *handle, int64_t greater_than, int64_t capacity, uint64_t *kmers, uint32_t *counts, int64_t *n);
+/* line 30: the counts of given k-mers */
+int coral_kmer_lookup(void *handle, const uint64_t *indices, int64_t n, uint32_t *counts);
+/* lines 29-30: the end of the session (merylDB has no counterpart: nothing is left on disk) */
+int coral_kmer_close(void *handle);
+
 #ifdef __cplusplus
 }
 #endif
