@@ -12,7 +12,9 @@ the records themselves, with its index on request) and `sort` (the kept records 
 index on request: lines 42-50 of the reference's scripts/align_nanopore_reads.sh from one decode) and `import` (the mapper's
 SAM text as the BAM file `sort` opens: line 38 of that script) and `cnv` (the .cns of segmented copy number and the seed
 intervals that `reconstruct` starts from: scripts/call_cnvs.sh and the seed mode, from the binned depth) and `kmers` (the
-reference genome's repetitive k-mers, the list the mapper takes with -W: lines 29-30 of that script); the other modes of the
+reference genome's repetitive k-mers, the list the mapper takes with -W: lines 29-30 of that script) and `composition` (the
+reference genome's G/C, A/T and soft-masked bases per depth bin, which `cnv --ref / --composition` corrects the GC bias with: the
+gc and rmask columns of the reference table of scripts/call_cnvs.sh); the other modes of the
 reference (seed, plot, cycle2bed) are untouched and are delegated to the reference's own modules when they are
 importable (set CORAL_REFERENCE_SRC to the reference's src/ directory).  The cycle-decomposition step after the graph build is the
 reference's (Gurobi); it runs on the object this module returns.
@@ -169,6 +171,12 @@ def build_parser():
     cp.add_argument("--min_seed_size", help="Minimum summed length of a seed.", type=int, default=99999)
     cp.add_argument("--max_seg_gap", help="Maximum gap between the segments of one seed.", type=int, default=300001)
     cp.add_argument("--device", help="GPU to use ('cpu': the host backend).", default="cuda:0")
+    comp = cp.add_mutually_exclusive_group()
+    comp.add_argument("--ref", help="Reference genome, FASTA: its composition is counted at the depth's bin size, for the GC correction and the uncalled-base mask.")
+    comp.add_argument("--composition", help="Per-bin composition table written by the composition mode, in place of --ref.")
+    cp.add_argument("--gc_strata", help="With --ref / --composition: steps of the GC fraction, 1..1000.", type=int, default=100)
+    cp.add_argument("--gc_min_bins", help="With --ref / --composition: bins a stratum's bias is the median of (neighbouring strata are pooled up to it).", type=int, default=256)
+    cp.add_argument("--min_called", help="With --ref / --composition: smallest fraction of a bin's bases that are A, C, G or T, in [0, 1].", type=float, default=0.5)
     kp = sub.add_parser("kmers", help="Count a reference's k-mers and write the repetitive ones (the mapper's -W list) from its FASTA file.")
     kp.add_argument("--ref", help="Reference genome, FASTA (a name ending in .gz is inflated on the host).", required=True)
     kp.add_argument("--output", help="Name of the output file (KMER<tab>COUNT lines).", required=True)
@@ -181,6 +189,12 @@ def build_parser():
     kp.add_argument("--histogram", help="Also write the histogram (count<tab>kmers lines) to this file.")
     kp.add_argument("--chunk_bytes", help="Bytes of the FASTA file per piece.", type=int, default=64 << 20)
     kp.add_argument("--device", help="GPU to use ('cpu': the host backend, one thread).", default="cuda:0")
+    gp = sub.add_parser("composition", help="Count a reference's G/C, A/T and soft-masked bases per bin (the table `cnv --composition` takes) from its FASTA file.")
+    gp.add_argument("--ref", help="Reference genome, FASTA (a name ending in .gz is inflated on the host).", required=True)
+    gp.add_argument("--output", help="Name of the output file (tab-separated, one row per bin).", required=True)
+    gp.add_argument("--bin_size", help="Bases per bin: the binned depth's.", type=int, default=1000)
+    gp.add_argument("--chunk_bytes", help="Bytes of the FASTA file per piece.", type=int, default=64 << 20)
+    gp.add_argument("--device", help="GPU to use ('cpu': the host backend, one thread).", default="cuda:0")
     for p in (rp, hp, qp, pp, dp, fp, vp, sp, mp, cp):
         add_filter_arguments(p)
     for mode in ("seed", "plot", "cycle2bed"):
@@ -384,14 +398,28 @@ def cnv_mode(args):
         raise ValueError("--seeds needs --centromeres: a bed file of the centromeres' p and q rows (none is shipped)")
     if args.seeds and not args.output.endswith(".cns"):
         raise ValueError("--seeds reads --output back as a .cns: its name must end in .cns, got %r" % (args.output,))
+    cnv._check_gc_arguments(args.gc_strata, args.gc_min_bins, args.min_called)
     reference = bam.BinnedDepth.read(args.reference_cnn) if args.reference_cnn else None
     if args.depth:
         depth = bam.BinnedDepth.read(args.depth)
     else:
         depth = bam.binned_depth(args.lr_bam, args.bin_size, device=args.device, record_filter=record_filter_of(args))
-    seg = cnv.segment_depth(depth, reference, args.levels, args.fdr_q, device=args.device)
+    comp = None
+    if args.composition:
+        from coral_amd import composition
+        comp = composition.Composition.read(args.composition)
+    elif args.ref:
+        from coral_amd import composition
+        comp = composition.reference_composition(args.ref, depth.bin_size, device=args.device)
+    seg = cnv.segment_depth(depth, reference, args.levels, args.fdr_q, device=args.device, composition=comp, gc_strata=args.gc_strata, gc_min_bins=args.gc_min_bins,
+                            min_called=args.min_called)
     seg.write(args.output)
     print("Wrote %s (%d segments of %d bins)" % (args.output, len(seg), seg.counts.get("kept", 0)))
+    if comp is not None:
+        used = seg.gc_bias["stratum_bins"] > 0
+        span = seg.gc_bias["bias"][used]
+        print("GC correction: %d strata in use, bias %.4f .. %.4f (log2), %d bins masked as uncalled" % (
+            int(used.sum()), float(span.min()) if len(span) else 0.0, float(span.max()) if len(span) else 0.0, seg.counts["uncalled"]))
     if args.seeds:
         sizes = args.chrom_sizes if args.chrom_sizes else dict(zip(depth.chroms, depth.lengths))
         seeds = cnv.find_seeds(args.output, args.centromeres, sizes, args.gain, args.min_seed_size, args.max_seg_gap)
@@ -411,6 +439,17 @@ def kmers_mode(args):
     if args.histogram:
         print("Wrote %s (%d lines)" % (args.histogram, kc.write_histogram(args.histogram)))
     kc.close()
+    return args.output
+
+
+def composition_mode(args):
+    """The G/C, A/T and soft-masked bases of --ref per bin (composition.reference_composition): the gc and rmask columns of the
+    reference table that the reference's scripts/call_cnvs.sh hands to CNVkit, for `cnv --composition`."""
+    from coral_amd import composition
+    comp = composition.reference_composition(args.ref, args.bin_size, device=args.device, chunk_bytes=args.chunk_bytes)
+    comp.write(args.output)
+    print("contigs: %d\npositions: %d\nbins: %d\ngc_fraction: %.6f" % (len(comp.chroms), comp.positions, comp.n_bins, comp.genome_gc()))
+    print("Wrote %s (%d rows)" % (args.output, comp.n_bins))
     return args.output
 
 
@@ -457,6 +496,8 @@ def main(argv=None):
         return cnv_mode(args)
     if args.mode == "kmers":
         return kmers_mode(args)
+    if args.mode == "composition":
+        return composition_mode(args)
     parser.print_help()
     return None
 

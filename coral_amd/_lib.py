@@ -218,6 +218,11 @@ def lib():
     L.coral_cn_segment_gpu.argtypes = [C.c_int32] + L.coral_cn_segment_host.argtypes + [P, C.c_int64, P, P]
     L.coral_cn_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64]
     L.coral_cn_workspace_bytes.restype = C.c_int64
+    gc_args = [P, P, C.c_int32, C.c_int64, C.c_int32, P, P]
+    L.coral_cn_segment_gc_host.argtypes = L.coral_cn_segment_host.argtypes + gc_args
+    L.coral_cn_segment_gc_gpu.argtypes = L.coral_cn_segment_gpu.argtypes + gc_args
+    L.coral_cn_workspace_gc_bytes.argtypes = L.coral_cn_workspace_bytes.argtypes + [C.c_int32, C.c_int32]
+    L.coral_cn_workspace_gc_bytes.restype = C.c_int64
     L.coral_kmer_table_bytes.argtypes = [C.c_int32]
     L.coral_kmer_table_bytes.restype = C.c_int64
     L.coral_kmer_workspace_bytes.argtypes = [C.c_int32, C.c_int64]
@@ -230,6 +235,14 @@ def lib():
     L.coral_kmer_select.argtypes = [C.c_void_p, C.c_int64, C.c_int64, P, P, C.POINTER(C.c_int64)]
     L.coral_kmer_lookup.argtypes = [C.c_void_p, P, C.c_int64, P]
     L.coral_kmer_close.argtypes = [C.c_void_p]
+    L.coral_comp_workspace_bytes.argtypes = [C.c_int64]
+    L.coral_comp_workspace_bytes.restype = C.c_int64
+    L.coral_comp_geometry.argtypes = [P]
+    L.coral_comp_open.argtypes = [C.c_int64, C.c_int32, P, P, P, C.c_int64, C.c_int64, P, C.c_int64, P, C.POINTER(C.c_void_p)]
+    L.coral_comp_feed.argtypes = [C.c_void_p, P, C.c_int64]
+    L.coral_comp_finish.argtypes = [C.c_void_p, P, P]
+    L.coral_comp_contigs.argtypes = [C.c_void_p, C.c_int64, P, C.c_int64, P, P]
+    L.coral_comp_close.argtypes = [C.c_void_p]
     for name in ("coral_bgzf_deflate_scratch_bytes", "coral_bgzf_pack_scratch_bytes"):
         getattr(L, name).argtypes = [C.c_int32]
         getattr(L, name).restype = C.c_int64

@@ -20,20 +20,24 @@ from . import _lib
 
 _AUTOSOME = re.compile(r"^(chr)?([1-9]|1[0-9]|2[0-2])$")
 LAST_SEGMENT = {}                    # seconds of the last GPU segment_depth, by stage (coral_cn_segment_gpu)
-_STAGES = ("upload", "signal", "noise", "levels", "cuts_host", "unify_rows")
+_STAGES = ("upload", "signal", "noise", "levels", "cuts_host", "unify_rows", "gc")
 
 
 class CopyNumberSegments:
     """The rows of a segmentation, one per segment in contig and position order: ``chrom`` (list of str), ``start`` / ``end``
     int64 (the first kept bin's start, the last one's end), ``probes`` int64 (kept bins), ``log2`` float64 (the mean log2 ratio
     against the centre: ``sum_s / (probes * 65536)`` of the integers both backends compute) and ``depth`` float64 (mean depth,
-    ``sum_bases / (probes * bin_size)``).  ``counts``: rows, kept bins, centre, reference centre, breakpoints."""
+    ``sum_bases / (probes * bin_size)``).  ``counts``: rows, kept bins, centre, reference centre, breakpoints, uncalled (the
+    candidates lost to the called-base mask).  ``gc_bias``: None without a composition, else a dict of ``strata`` (G),
+    ``stratum_bins`` (int64 [G + 1]: the centring contigs' kept bins per GC stratum) and ``bias`` (float64 [G + 1]: what was
+    subtracted from the signal per stratum, in log2 units; ``bias_q16`` holds the integers)."""
 
-    def __init__(self, chroms, bin_size, contig, start, end, probes, sum_s, sum_bases, counts=None):
+    def __init__(self, chroms, bin_size, contig, start, end, probes, sum_s, sum_bases, counts=None, gc_bias=None):
         self.chroms, self.bin_size = list(chroms), int(bin_size)
         self.contig = np.ascontiguousarray(contig, dtype=np.int32)
         self.start, self.end, self.probes, self.sum_s, self.sum_bases = (np.ascontiguousarray(a, dtype=np.int64) for a in (start, end, probes, sum_s, sum_bases))
         self.counts = dict(counts or {})
+        self.gc_bias = gc_bias
 
     def __len__(self) -> int:
         return len(self.contig)
@@ -71,6 +75,17 @@ def default_centre_contigs(chroms: Sequence[str]):
     return auto if auto else list(chroms)
 
 
+def _check_gc_arguments(gc_strata, gc_min_bins, min_called):
+    """-> min_called in permille.  ``ValueError``: gc_strata outside 1..1000, gc_min_bins below 1, min_called outside [0, 1]."""
+    if isinstance(gc_strata, bool) or not isinstance(gc_strata, numbers.Integral) or not 1 <= gc_strata <= 1000:
+        raise ValueError("gc_strata must be an integer in 1..1000, got %r" % (gc_strata,))
+    if isinstance(gc_min_bins, bool) or not isinstance(gc_min_bins, numbers.Integral) or gc_min_bins < 1:
+        raise ValueError("gc_min_bins must be an integer of at least 1, got %r" % (gc_min_bins,))
+    if isinstance(min_called, bool) or not isinstance(min_called, numbers.Real) or not 0.0 <= min_called <= 1.0:
+        raise ValueError("min_called must lie in [0, 1], got %r" % (min_called,))
+    return int(round(float(min_called) * 1000))
+
+
 def _check_arguments(depth, reference, levels, fdr_q, centre_contigs):
     if isinstance(levels, bool) or not isinstance(levels, numbers.Integral) or not 1 <= levels <= 20:
         raise ValueError("levels must be an integer in 1..20, got %r" % (levels,))
@@ -87,7 +102,8 @@ def _check_arguments(depth, reference, levels, fdr_q, centre_contigs):
     return np.array([c in wanted for c in depth.chroms], dtype=np.uint8)
 
 
-def segment_depth(depth, reference=None, levels: int = 5, fdr_q: float = 1e-4, centre_contigs=None, device="cuda:0") -> CopyNumberSegments:
+def segment_depth(depth, reference=None, levels: int = 5, fdr_q: float = 1e-4, centre_contigs=None, device="cuda:0", composition=None, gc_strata: int = 100,
+                  gc_min_bins: int = 256, min_called: float = 0.5) -> CopyNumberSegments:
     """Segments the binned depth ``depth`` (a ``bam.BinnedDepth``) into runs of equal copy number -> ``CopyNumberSegments``.
 
     Bins of the full size with depth are candidates; the centre is the lower median of their ``bases`` over ``centre_contigs``
@@ -97,10 +113,24 @@ def segment_depth(depth, reference=None, levels: int = 5, fdr_q: float = 1e-4, c
     dyadic scales, local peaks, a Benjamini-Hochberg cut at ``fdr_q`` per contig and level against a MAD noise estimate, and
     the levels' breakpoints unified fine to coarse.  The rule is integer arithmetic except for the cut (coral_cn_core.h), so the
     GPU ``device`` (coral_cn_segment_gpu: kernels k_cn_*, k_haar_*) and ``device="cpu"`` (coral_cn_segment_host) give the same
-    rows.  ``ValueError`` before any work: ``levels`` outside 1..20, ``fdr_q`` not in (0, 1), a reference with other bins, an
-    unknown centring contig."""
+    rows.  With ``composition`` - a ``composition.Composition`` of the reference genome at the depth's bin size - bins with fewer
+    called (A C G T) bases than ``min_called`` of the bin are masked as well, and the GC bias is taken out of the signal in
+    front of the details: a kept bin's stratum is its GC fraction in ``gc_strata`` steps, a stratum's bias is the lower median
+    of the signal over the centring contigs' kept bins of the nearest strata that together hold ``gc_min_bins`` bins, and every
+    kept bin's signal has its stratum's bias subtracted (``CopyNumberSegments.gc_bias``).  ``ValueError`` before any work:
+    ``levels`` outside 1..20, ``fdr_q`` not in (0, 1), a reference with other bins, an unknown centring contig, ``gc_strata``
+    outside 1..1000, ``gc_min_bins`` below 1, ``min_called`` outside [0, 1], a composition that does not fit the depth's
+    contigs and bin size (``Composition.for_depth``)."""
     import torch
     centre = _check_arguments(depth, reference, levels, fdr_q, centre_contigs)
+    permille = _check_gc_arguments(gc_strata, gc_min_bins, min_called)
+    gc = at = None
+    if composition is not None:
+        gc, at, _masked = composition.for_depth(depth)
+        gc, at = np.ascontiguousarray(gc, dtype=np.uint32), np.ascontiguousarray(at, dtype=np.uint32)
+    G = int(gc_strata)
+    bias, stratum_bins = np.zeros(G + 1, dtype=np.int64), np.zeros(G + 1, dtype=np.int64)
+    gc_args = [None, None, 0, 0, 0, None, None] if gc is None else [gc.ctypes.data, at.ctypes.data, G, int(gc_min_bins), permille, bias.ctypes.data, stratum_bins.ctypes.data]
     L = _lib.lib()
     n_contigs, n_bins = len(depth.chroms), depth.n_bins
     lengths = np.array(depth.lengths, dtype=np.int64)
@@ -115,20 +145,20 @@ def segment_depth(depth, reference=None, levels: int = 5, fdr_q: float = 1e-4, c
         if on_gpu:
             dev = torch.device(device)
             torch.cuda.set_device(dev)
-            ws_bytes = int(L.coral_cn_workspace_bytes(n_bins, n_contigs, int(levels), int(ref is not None), cap))
+            ws_bytes = int(L.coral_cn_workspace_gc_bytes(n_bins, n_contigs, int(levels), int(ref is not None), cap, int(gc is not None), G))
             if ws_bytes < 0:
-                raise _lib.CoralHipError("coral_cn_workspace_bytes failed (%d)" % ws_bytes)
+                raise _lib.CoralHipError("coral_cn_workspace_gc_bytes failed (%d)" % ws_bytes)
             ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
             stream = torch.cuda.current_stream(dev)
             stream.synchronize()                                 # (the block may be a recycled one)
-            secs = (C.c_double * 6)()
-            rc = L.coral_cn_segment_gpu(dev.index or 0, *common, ws.data_ptr(), ws_bytes, stream.cuda_stream, secs)
+            secs = (C.c_double * 7)()
+            rc = L.coral_cn_segment_gc_gpu(dev.index or 0, *common, ws.data_ptr(), ws_bytes, stream.cuda_stream, secs, *gc_args)
             stream.synchronize()
             del ws
             LAST_SEGMENT.clear()
             LAST_SEGMENT.update(zip(_STAGES, (float(s) for s in secs)), workspace_bytes=ws_bytes)
         else:
-            rc = L.coral_cn_segment_host(*common)
+            rc = L.coral_cn_segment_gc_host(*common, *gc_args)
         if rc == -3 and cap < n_bins:                            # CORAL_ERR_CAPACITY: counts[0] rows suffice
             cap = min(n_bins, max(int(counts[0]), cap + 1))
             continue
@@ -136,20 +166,24 @@ def segment_depth(depth, reference=None, levels: int = 5, fdr_q: float = 1e-4, c
     if rc != 0:
         raise _lib.CoralHipError("coral_cn_segment_%s failed (%d): %s" % ("gpu" if on_gpu else "host", rc, L.coral_bam_last_error().decode()))
     n = int(counts[0])
-    names = ("rows", "kept", "centre", "ref_centre", "breakpoints")
-    return CopyNumberSegments(depth.chroms, depth.bin_size, *(a[:n].copy() for a in rows), counts={k: int(counts[i]) for i, k in enumerate(names)})
+    names = ("rows", "kept", "centre", "ref_centre", "breakpoints", "uncalled")
+    gc_bias = None if gc is None else dict(strata=G, stratum_bins=stratum_bins, bias_q16=bias, bias=bias.astype(np.float64) / 65536.0)
+    return CopyNumberSegments(depth.chroms, depth.bin_size, *(a[:n].copy() for a in rows), counts={k: int(counts[i]) for i, k in enumerate(names)}, gc_bias=gc_bias)
 
 
 def call_copy_number(bam_path: str, bin_size: int = 1000, min_mapq: int = 0, exclude_flags: int = 0x704, count_deletions: bool = True, *, reference=None,
-                     levels: int = 5, fdr_q: float = 1e-4, centre_contigs=None, record_filter=None, device="cuda:0") -> CopyNumberSegments:
+                     levels: int = 5, fdr_q: float = 1e-4, centre_contigs=None, record_filter=None, device="cuda:0", composition=None, gc_strata: int = 100,
+                     gc_min_bins: int = 256, min_called: float = 0.5) -> CopyNumberSegments:
     """``bam.binned_depth`` of ``bam_path`` (one decode), then ``segment_depth``; the arguments are theirs."""
     from . import bam
     if isinstance(levels, bool) or not isinstance(levels, numbers.Integral) or not 1 <= levels <= 20:
         raise ValueError("levels must be an integer in 1..20, got %r" % (levels,))
     if isinstance(fdr_q, bool) or not isinstance(fdr_q, numbers.Real) or not 0.0 < fdr_q < 1.0:
         raise ValueError("fdr_q must lie in (0, 1), got %r" % (fdr_q,))
+    _check_gc_arguments(gc_strata, gc_min_bins, min_called)
     depth = bam.binned_depth(bam_path, bin_size, min_mapq, exclude_flags, count_deletions, device=device, record_filter=record_filter)
-    return segment_depth(depth, reference, levels, fdr_q, centre_contigs, device=device)
+    return segment_depth(depth, reference, levels, fdr_q, centre_contigs, device=device, composition=composition, gc_strata=gc_strata, gc_min_bins=gc_min_bins,
+                         min_called=min_called)
 
 
 # ----------------------------------------------------------------------------------------------

@@ -9,6 +9,9 @@
 //   - the signal of a kept bin is s = L(bases) - L(C) [- (L(ref) - L(C_ref))], L = log2 in Q16 by repeated squaring (log2_q16);
 //   - per contig, over its n kept bins x[0..n) with mirror padding, the Haar detail of half-size h at k = 1..n-1 is
 //     sum x[k..k+h-1] - sum x[k-h..k-1], taken from the contig's prefix sums (haar_detail); c[0] = c[n] = 0; peaks by peak_mag.
+//   - with the reference's composition per bin (gc, at) a candidate also needs enough called bases, and the lower median of s over
+//     the centring contigs' kept bins of its GC stratum (pooled with the nearest strata up to gc_min_bins) is subtracted from
+//     every kept bin's s in front of the details (called_enough, gc_stratum, gc_pool below);
 // The cut (fdr_cut) is the one floating-point step: a host function, called by both backends on the sorted magnitudes.
 // No HIP in this header beyond the host / device markers.
 #ifndef CORAL_CN_CORE_H
@@ -63,6 +66,34 @@ CORAL_CN_HD int64_t bin_end(int64_t b, int64_t bin_size, int64_t length) { const
 CORAL_CN_HD bool candidate(bool full, int64_t bases, bool has_ref, int64_t ref_bases) { return full && bases > 0 && (!has_ref || ref_bases > 0); }
 // bases * 32 >= C without the product: bases >= ceil(C / 32).  C == 0 (no candidate in the centring contigs): nothing is kept.
 CORAL_CN_HD bool above_floor(int64_t bases, int64_t C) { return C > 0 && bases >= (C + 31) / 32; }
+
+// ---- with the reference's composition per bin (gc, at: G/C and A/T bases of the bin): the uncalled-base mask and the GC bias -----
+//   - a candidate must also have acgt = gc + at > 0 and acgt * 1000 >= bin_size * min_called_permille;
+//   - a kept bin's stratum is g = gc * G / acgt in 0..G (G = gc_strata);
+//   - over P, the kept bins of the centring contigs: for each g the smallest w >= 0 whose strata [max(0, g - w), min(G, g + w)]
+//     hold at least min(gc_min_bins, |P|) bins of P (gc_pool); bias[g] = the lower median of s over those bins;
+//   - s' = s - bias[g] for every kept bin of every contig; detail, noise, cut, unify and rows run on s'.
+constexpr int32_t MAX_GC_STRATA = 1000;
+
+CORAL_CN_HD bool gc_params_ok(int32_t strata, int64_t min_bins, int32_t min_called_permille) {
+    return strata >= 1 && strata <= MAX_GC_STRATA && min_bins >= 1 && min_called_permille >= 0 && min_called_permille <= 1000;
+}
+CORAL_CN_HD bool called_enough(uint32_t gc, uint32_t at, int64_t bin_size, int32_t min_called_permille) {
+    const int64_t acgt = (int64_t)gc + (int64_t)at;
+    return acgt > 0 && acgt * 1000 >= bin_size * (int64_t)min_called_permille;
+}
+CORAL_CN_HD int32_t gc_stratum(uint32_t gc, uint32_t at, int32_t strata) { return (int32_t)((uint64_t)gc * (uint64_t)strata / ((uint64_t)gc + (uint64_t)at)); }
+// start[g] = the bins of P in the strata below g, g = 0..G + 1.  The pool of stratum g: strata lo..hi.
+CORAL_CN_HD void gc_pool(const int64_t *start, int32_t strata, int32_t g, int64_t need, int32_t &lo, int32_t &hi) {
+    for (int32_t w = 0;; ++w) {
+        lo = g - w < 0 ? 0 : g - w;
+        hi = g + w > strata ? strata : g + w;
+        if (start[hi + 1] - start[lo] >= need || (lo == 0 && hi == strata)) return;
+    }
+}
+// the order-preserving 32-bit key of a signal, and back
+CORAL_CN_HD uint32_t signal_key(int32_t s) { return (uint32_t)s ^ 0x80000000u; }
+CORAL_CN_HD int32_t key_signal(uint32_t k) { return (int32_t)(k ^ 0x80000000u); }
 
 // the contig of bin b: the last c with bin_off[c] <= b (empty contigs share an offset; the last of them holds the bin)
 CORAL_CN_HD int32_t contig_of(const int64_t *bin_off, int32_t n_contigs, int64_t b) {

@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <functional>
+#include <utility>
 #include <vector>
 
 #include "coral_cn_core.h"
@@ -20,6 +21,10 @@ struct Table {                       // a BinnedDepth, and optionally a second o
     const int64_t *bases;            // bin_off[n_contigs]
     const int64_t *ref_bases;        // the same, or null
     const uint8_t *centre;           // n_contigs: 1 = a centring contig
+    const uint32_t *gc = nullptr, *at = nullptr;         // the reference's G/C and A/T bases per bin, or both null
+    int32_t gc_strata = 100;
+    int64_t gc_min_bins = 256;
+    int32_t min_called_permille = 500;
 };
 
 struct Rows {
@@ -28,7 +33,11 @@ struct Rows {
     size_t size() const { return contig.size(); }
 };
 
-struct Counts { int64_t rows = 0, kept = 0, centre = 0, ref_centre = 0, breakpoints = 0; };
+struct Counts { int64_t rows = 0, kept = 0, centre = 0, ref_centre = 0, breakpoints = 0, uncalled = 0; };
+
+struct GcBias {                      // per stratum 0..gc_strata: the bias in Q16 and the bins of P (empty without a composition)
+    std::vector<int64_t> bias, stratum_bins;
+};
 
 inline bool table_ok(const Table &T, int32_t levels, double q) {
     if (T.n_contigs < 0 || !T.bin_off || T.bin_size < 1 || levels < 1 || levels > MAX_LEVELS || !(q > 0 && q < 1)) return false;
@@ -39,6 +48,8 @@ inline bool table_ok(const Table &T, int32_t levels, double q) {
         if (T.bin_off[c + 1] - T.bin_off[c] != (len + T.bin_size - 1) / T.bin_size) return false;
     }
     const int64_t n = T.bin_off[T.n_contigs];
+    if ((T.gc != nullptr) != (T.at != nullptr)) return false;
+    if (T.gc && (!gc_params_ok(T.gc_strata, T.gc_min_bins, T.min_called_permille) || T.bin_size > 0x7fffffff)) return false;
     return n <= MAX_BINS && (n == 0 || T.bases);
 }
 
@@ -55,36 +66,81 @@ inline int64_t level_cut(const int64_t *mags_desc, int64_t M, int64_t n, int32_t
     return fdr_cut(mags_desc, M, h, sigma_of(d), q);
 }
 
-inline void segment_host(const Table &T, int32_t levels, double q, Rows &R, Counts &X) {
-    const bool has_ref = T.ref_bases != nullptr;
+// bias[g] and stratum_bins[g] from P's (stratum, signal) pairs
+inline void gc_bias_host(std::vector<std::pair<int32_t, int32_t>> &P, int32_t strata, int64_t min_bins, GcBias &out) {
+    out.bias.assign((size_t)strata + 1, 0);
+    out.stratum_bins.assign((size_t)strata + 1, 0);
+    std::sort(P.begin(), P.end());
+    std::vector<int64_t> start((size_t)strata + 2, 0), pool;
+    for (const auto &p : P) ++out.stratum_bins[(size_t)p.first];
+    for (int32_t g = 0; g <= strata; ++g) start[(size_t)g + 1] = start[(size_t)g] + out.stratum_bins[(size_t)g];
+    const int64_t need = std::min<int64_t>(min_bins, (int64_t)P.size());
+    for (int32_t g = 0; g <= strata; ++g) {
+        int32_t lo, hi;
+        gc_pool(start.data(), strata, g, need, lo, hi);
+        pool.clear();
+        for (int64_t i = start[(size_t)lo]; i < start[(size_t)hi + 1]; ++i) pool.push_back(P[(size_t)i].second);
+        if (!pool.empty()) out.bias[(size_t)g] = lower_median(pool);
+    }
+}
+
+inline void segment_host(const Table &T, int32_t levels, double q, Rows &R, Counts &X, GcBias *gc_out = nullptr) {
+    const bool has_ref = T.ref_bases != nullptr, has_gc = T.gc != nullptr;
+    // today's candidate test, then the called-base mask: 0 = no candidate, 1 = a candidate, 2 = one lost to the mask
+    auto cand = [&](int32_t c, int64_t b) {
+        if (!candidate(full_bin(b - T.bin_off[c], T.bin_size, T.lengths[c]), T.bases[b], has_ref, has_ref ? T.ref_bases[b] : 0)) return 0;
+        return !has_gc || called_enough(T.gc[b], T.at[b], T.bin_size, T.min_called_permille) ? 1 : 2;
+    };
     std::vector<int64_t> mid, ref_mid;
     for (int32_t c = 0; c < T.n_contigs; ++c) {
-        if (!T.centre[c]) continue;
-        for (int64_t b = T.bin_off[c]; b < T.bin_off[c + 1]; ++b)
-            if (candidate(full_bin(b - T.bin_off[c], T.bin_size, T.lengths[c]), T.bases[b], has_ref, has_ref ? T.ref_bases[b] : 0)) {
+        for (int64_t b = T.bin_off[c]; b < T.bin_off[c + 1]; ++b) {
+            const int k = cand(c, b);
+            X.uncalled += k == 2;
+            if (k == 1 && T.centre[c]) {
                 mid.push_back(T.bases[b]);
                 if (has_ref) ref_mid.push_back(T.ref_bases[b]);
             }
+        }
     }
+    if (has_gc && gc_out) { gc_out->bias.assign((size_t)T.gc_strata + 1, 0); gc_out->stratum_bins.assign((size_t)T.gc_strata + 1, 0); }
     if (mid.empty()) return;
     const int64_t C = X.centre = lower_median(mid);
     const int64_t Cr = X.ref_centre = has_ref ? lower_median(ref_mid) : 0;
     const int32_t LC = log2_q16((uint64_t)C), LCr = has_ref ? log2_q16((uint64_t)Cr) : 0;
 
-    std::vector<int64_t> bin, P, B, a1, mags, set, add;
+    // the kept bins of every contig back to back: bin within the contig, signal, bases, stratum
+    std::vector<int64_t> kbin, ks, kv, koff((size_t)T.n_contigs + 1, 0);
+    std::vector<int32_t> kg;
     for (int32_t c = 0; c < T.n_contigs; ++c) {
-        bin.clear(); P.assign(1, 0); B.assign(1, 0);
         for (int64_t b = T.bin_off[c]; b < T.bin_off[c + 1]; ++b) {
             const int64_t v = T.bases[b], r = has_ref ? T.ref_bases[b] : 0;
-            if (!candidate(full_bin(b - T.bin_off[c], T.bin_size, T.lengths[c]), v, has_ref, r) || !above_floor(v, C) || (has_ref && !above_floor(r, Cr))) continue;
+            if (cand(c, b) != 1 || !above_floor(v, C) || (has_ref && !above_floor(r, Cr))) continue;
             int64_t s = (int64_t)log2_q16((uint64_t)v) - LC;
             if (has_ref) s -= (int64_t)log2_q16((uint64_t)r) - LCr;
-            bin.push_back(b - T.bin_off[c]);
-            P.push_back(P.back() + s);
-            B.push_back(B.back() + v);
+            kbin.push_back(b - T.bin_off[c]);
+            ks.push_back(s);
+            kv.push_back(v);
+            if (has_gc) kg.push_back(gc_stratum(T.gc[b], T.at[b], T.gc_strata));
         }
-        const int64_t n = (int64_t)bin.size();
+        koff[(size_t)c + 1] = (int64_t)kbin.size();
+    }
+    if (has_gc) {
+        std::vector<std::pair<int32_t, int32_t>> P;
+        for (int32_t c = 0; c < T.n_contigs; ++c)
+            if (T.centre[c]) for (int64_t i = koff[(size_t)c]; i < koff[(size_t)c + 1]; ++i) P.emplace_back(kg[(size_t)i], (int32_t)ks[(size_t)i]);
+        GcBias local;
+        GcBias &G = gc_out ? *gc_out : local;
+        gc_bias_host(P, T.gc_strata, T.gc_min_bins, G);
+        for (size_t i = 0; i < ks.size(); ++i) ks[i] -= G.bias[(size_t)kg[i]];
+    }
+
+    std::vector<int64_t> P, B, a1, mags, set, add;
+    for (int32_t c = 0; c < T.n_contigs; ++c) {
+        const int64_t *bin = kbin.data() + koff[(size_t)c];
+        const int64_t n = koff[(size_t)c + 1] - koff[(size_t)c];
         if (n == 0) continue;
+        P.assign(1, 0); B.assign(1, 0);
+        for (int64_t i = koff[(size_t)c]; i < koff[(size_t)c + 1]; ++i) { P.push_back(P.back() + ks[(size_t)i]); B.push_back(B.back() + kv[(size_t)i]); }
         X.kept += n;
         set.clear();
         if (n >= 2) {

@@ -1006,6 +1006,33 @@ int coral_cn_segment_gpu(int32_t device, int32_t n_contigs, const int64_t *bin_o
                          int64_t *row_sum_s, int64_t *row_sum_bases, int64_t *counts, void *workspace, int64_t workspace_bytes,
                          void *stream, double *seconds);
 int64_t coral_cn_workspace_bytes(int64_t n_bins, int32_t n_contigs, int32_t levels, int32_t has_reference, int64_t row_cap);
+/* The same with the reference's composition per bin (coral_comp_*: the gc and rmask columns of the reference table of the
+ * reference's scripts/call_cnvs.sh:12-17), which takes the GC bias and the uncalled bases out in front of the cut.  gc, at:
+ * uint32 per bin of the table (NULL, both: no composition - the rows and counts of the entry points above, bit for bit).
+ *   mask      a candidate must also have acgt = gc + at > 0 and acgt * 1000 >= bin_size * min_called_permille (0..1000);
+ *             counts[5] = the candidates lost to this.  C, the 1/32 test and s are as above, over these candidates.
+ *   stratum   g = gc * gc_strata / acgt in 64-bit integers, 0..gc_strata (gc_strata in 1..1000).
+ *   bias      P = the kept bins of the centring contigs; for each g the smallest w >= 0 whose strata [max(0, g - w),
+ *             min(gc_strata, g + w)] hold at least min(gc_min_bins, |P|) bins of P (gc_min_bins >= 1); bias[g] = the lower median
+ *             of s over those bins (0 without any).  stratum_bins[g] = the bins of P in stratum g.  gc_strata + 1 entries each.
+ *   apply     s' = s - bias[g] for every kept bin of every contig; detail, noise, cut, unify and rows run on s' (sum_s too).
+ * Device: one stable radix sort of (g << 32 | biased s) over P, the strata's starts by binary search, k_cn_gc_bias (a wave per
+ * stratum; the pooled median by bisection on the value), k_cn_gc_apply; no host wait is added.  seconds[0..6]: the six stages
+ * above, then gc.  coral_cn_workspace_gc_bytes sizes the workspace. */
+int coral_cn_segment_gc_host(int32_t n_contigs, const int64_t *bin_off, const int64_t *lengths, int64_t bin_size,
+                             const int64_t *bases, const int64_t *ref_bases, const uint8_t *centre, int32_t levels, double fdr_q,
+                             int64_t row_cap, int32_t *row_contig, int64_t *row_start, int64_t *row_end, int64_t *row_probes,
+                             int64_t *row_sum_s, int64_t *row_sum_bases, int64_t *counts, const uint32_t *gc, const uint32_t *at,
+                             int32_t gc_strata, int64_t gc_min_bins, int32_t min_called_permille, int64_t *bias,
+                             int64_t *stratum_bins);
+int coral_cn_segment_gc_gpu(int32_t device, int32_t n_contigs, const int64_t *bin_off, const int64_t *lengths, int64_t bin_size,
+                            const int64_t *bases, const int64_t *ref_bases, const uint8_t *centre, int32_t levels, double fdr_q,
+                            int64_t row_cap, int32_t *row_contig, int64_t *row_start, int64_t *row_end, int64_t *row_probes,
+                            int64_t *row_sum_s, int64_t *row_sum_bases, int64_t *counts, void *workspace, int64_t workspace_bytes,
+                            void *stream, double *seconds, const uint32_t *gc, const uint32_t *at, int32_t gc_strata,
+                            int64_t gc_min_bins, int32_t min_called_permille, int64_t *bias, int64_t *stratum_bins);
+int64_t coral_cn_workspace_gc_bytes(int64_t n_bins, int32_t n_contigs, int32_t levels, int32_t has_reference, int64_t row_cap,
+                                    int32_t has_composition, int32_t gc_strata);
 
 /* ------------------------------------------------------------------------------------------------
  * The k-mers of a reference genome (`kmers`): what lines 29-30 of the reference's scripts/align_nanopore_reads.sh get from
@@ -1068,6 +1095,57 @@ int coral_kmer_select(void *handle, int64_t greater_than, int64_t capacity, uint
 int coral_kmer_lookup(void *handle, const uint64_t *indices, int64_t n, uint32_t *counts);
 /* lines 29-30: the end of the session (merylDB has no counterpart: nothing is left on disk) */
 int coral_kmer_close(void *handle);
+
+/* ------------------------------------------------------------------------------------------------
+ * The composition of a reference genome per bin (`composition`): the GC and repeat-mask columns of the reference table that
+ * the reference's scripts/call_cnvs.sh:12-17 hands to `cnvkit.py batch --seq-method wgs --reference hg38full_ref_5k.cnn`,
+ * counted from the FASTA file.  Parity with `cnvkit.py reference` is not claimed; the rule (coral_comp_core.h)
+ * is what both backends compute, exactly:
+ *   text      FASTA bytes, fed in pieces of any size; the result does not depend on the cuts.  Lines are the k-mer counter's:
+ *             a line starts at the first byte and behind every '\n'; a line whose first byte is '>' is a header and starts a
+ *             contig, named by the bytes behind '>' up to the first blank, tab, '\r' or '\n' (an empty name: CORAL_ERR_FORMAT).
+ *             '\n' and '\r' are skipped anywhere; every other byte of a line that is no header is one position of the contig
+ *             (`samtools faidx` coordinates: N, IUPAC codes, '*' and '-' too); one in front of the first header:
+ *             CORAL_ERR_FORMAT.  A contig of length 0, consecutive headers, CR LF and a last line without '\n' are legal.
+ *   classes   gc: GCgc; at: ATat; masked: a..z; uncalled = length - gc - at.
+ *   tables    contig c has ceil(length[c] / bin_size) bins, the last one short, in file order (the bins of the binned depth);
+ *             gc, at, masked: uint32 per bin, `capacity` bins each, the caller's memory, zeroed by the caller.  1 <= bin_size <=
+ *             2^31 - 1; at most 2^28 bins.
+ * A session, so that the caller owns the reading of the file:
+ *   open      device < 0: the host backend, one thread, tables in host memory; staging_bytes, workspace and stream are ignored.
+ *             device >= 0: the tables and `workspace` (coral_comp_workspace_bytes(staging_bytes); the library allocates no
+ *             device memory) are device memory, the kernels run on `stream`; the session owns two pinned staging buffers of
+ *             staging_bytes (16 .. 2^30) and a copy stream.
+ *   feed      the next n bytes.  Device: header lines found in the caller's bytes (memchr) and blanked to '\n' in the pinned copy,
+ *             which goes up with the headers' byte offsets on the copy stream beside the kernels of the piece before (a piece
+ *             with more headers than geometry[3] is fed as several); then on `stream`: scan of the is-position flags,
+ *             k_comp_walk (closes the contigs, carries the open one), k_comp_count (one no-return atomicAdd per table and run of
+ *             lanes in the same bin).  No host wait for the kernels.
+ *   finish    waits; stats[0..6] (8 entries) = contigs, positions, bins, gc, at and masked in all, the bytes of the names.
+ *             seconds[0..3] (or NULL) = upload, ordinals + contigs, count (host: the whole feed), 0.  More bins than the
+ *             capacity: CORAL_ERR_CAPACITY, stats filled (stats[2] bins suffice), nothing written behind the capacity.
+ *   contigs   lengths[c], and names[name_off[c] .. name_off[c + 1]) (name_off: contigs + 1 entries), host arrays.
+ *   close     frees the session (never the tables or the workspace).
+ * coral_comp_geometry -> geometry[0..6] = bytes per thread and threads per workgroup of k_comp_count, lanes per wave, the
+ *   header lines one piece holds, threads of k_comp_walk, the smallest staging size, the bytes of one load.
+ * Errors go to coral_bam_last_error.
+ * ------------------------------------------------------------------------------------------------ */
+/* scripts/call_cnvs.sh:12-17 (the reference table's gc and rmask columns): the device scratch of a counting session */
+int64_t coral_comp_workspace_bytes(int64_t staging_bytes);
+/* scripts/call_cnvs.sh:12-17: the launch geometry of the kernels behind the count */
+int coral_comp_geometry(int32_t *geometry);
+/* scripts/call_cnvs.sh:12-17 (`--reference hg38full_ref_5k.cnn`): a counting session over the genome's FASTA */
+int coral_comp_open(int64_t bin_size, int32_t device, void *gc, void *at, void *masked, int64_t capacity, int64_t staging_bytes,
+                    void *workspace, int64_t workspace_bytes, void *stream, void **handle);
+/* scripts/call_cnvs.sh:12-17: the next bytes of the FASTA */
+int coral_comp_feed(void *handle, const uint8_t *bytes, int64_t n);
+/* scripts/call_cnvs.sh:12-17: the statistics of the finished count */
+int coral_comp_finish(void *handle, int64_t *stats, double *seconds);
+/* scripts/call_cnvs.sh:12-17 (the table's chromosome, start and end columns): the contigs' lengths and names */
+int coral_comp_contigs(void *handle, int64_t n_contigs, int64_t *lengths, int64_t names_capacity, uint8_t *names,
+                       int64_t *name_off);
+/* scripts/call_cnvs.sh:12-17: the end of the session */
+int coral_comp_close(void *handle);
 
 #ifdef __cplusplus
 }
