@@ -273,10 +273,11 @@ class PairSearch:
 
     def stats(self) -> dict:
         """Counters of the handle (coral_search_stats)."""
-        out = np.zeros(8, dtype=np.int64)
+        out = np.zeros(12, dtype=np.int64)
         self._lib.check(self._L.coral_search_stats(self._h, out.ctypes.data, len(out)), "coral_search_stats")
-        return dict(zip(("attached", "fill_ready_at_attach", "queued", "queued_before_bfs", "inline_steps", "workers", "helpers"),
-                        (int(v) for v in out[:7])))
+        return dict(zip(("attached", "fill_ready_at_attach", "queued", "queued_before_bfs", "inline_steps", "workers", "helpers",
+                         "spec_queued", "spec_asked", "spec_ready_when_asked", "spec_unused", "steps_done"),
+                        (int(v) for v in out)))
 
     def close(self):
         if self._h:

@@ -165,6 +165,9 @@ struct Entry {                                            // one (possibly pendi
     int64_t key[5];
     double t_queued = 0, t_start = 0, t_end = 0;          // CORAL_SEARCH_PROFILE=2: when it was asked for / computed
     int who = -1;                                         // -1 a worker, 0 the caller
+    // speculation (see "Exploring ahead" below): born_spec never changes; spec = the caller has not asked for it yet and
+    // step_seen = coral_search_step has met it (both under the handle's qm)
+    bool born_spec = false, spec = false, step_seen = false;
 };
 
 struct KeyHash {
@@ -191,7 +194,7 @@ struct TaskPool {
     struct Task { std::function<void()> *fn; std::atomic<int> *left; };
     std::mutex m;
     std::condition_variable cv;
-    std::deque<Task> q;
+    std::deque<Task> q, q_low;                            // q_low: batches of speculative steps, taken when q is empty
     bool stop = false;
     std::vector<std::thread> th;                          // (grow / shutdown: under Threads::life)
     std::atomic<int> n_alive{0};
@@ -202,10 +205,11 @@ struct TaskPool {
                     Task t;
                     {
                         std::unique_lock<std::mutex> lk(m);
-                        cv.wait(lk, [&] { return stop || !q.empty(); });
-                        if (q.empty()) return;
-                        t = q.front();
-                        q.pop_front();
+                        cv.wait(lk, [&] { return stop || !q.empty() || !q_low.empty(); });
+                        std::deque<Task> &from = q.empty() ? q_low : q;
+                        if (from.empty()) return;
+                        t = from.front();
+                        from.pop_front();
                     }
                     (*t.fn)();
                     t.left->fetch_sub(1, std::memory_order_acq_rel);
@@ -227,12 +231,14 @@ struct TaskPool {
         std::lock_guard<std::mutex> lk(m);
         stop = false;
     }
-    void run(std::vector<std::function<void()>> &tasks) {
+    // low: the batch of a speculative step — it goes behind every batch of a real step, and only a caller that waits for a
+    // low batch of its own helps with low tasks (a real step never waits behind a guess)
+    void run(std::vector<std::function<void()>> &tasks, bool low = false) {
         if (tasks.empty()) return;
         std::atomic<int> left((int)tasks.size());
         {
             std::lock_guard<std::mutex> lk(m);
-            for (size_t k = 1; k < tasks.size(); ++k) q.push_back(Task{&tasks[k], &left});
+            for (size_t k = 1; k < tasks.size(); ++k) (low ? q_low : q).push_back(Task{&tasks[k], &left});
         }
         cv.notify_all();
         tasks[0]();
@@ -242,6 +248,7 @@ struct TaskPool {
             {
                 std::lock_guard<std::mutex> lk(m);
                 if (!q.empty()) { t = q.front(); q.pop_front(); }
+                else if (low && !q_low.empty()) { t = q_low.front(); q_low.pop_front(); }
             }
             if (t.fn) {
                 (*t.fn)();
@@ -324,6 +331,14 @@ struct Search {
     std::unordered_map<std::array<int64_t, 5>, std::shared_ptr<Entry>, KeyHash> cache;
     std::shared_ptr<Entry> tail_job[2], tail_out[2];      // [0] small deletions, [1] pair filter: asked ahead / last collected (under qm)
     int64_t stat_tail[4] = {0, 0, 0, 0};                  // jobs queued, served from a queued job, computed on demand, of the served: by the caller
+    // exploring ahead (CORAL_SEARCH_SPECULATE): `active` is the running coral_search_bfs, under spec_m — which the search thread
+    // holds whenever it changes its interval / breakpoint lists, and a shadow pass while it reads them
+    bool speculate = false;                               // CORAL_SEARCH_SPECULATE
+    int64_t spec_max = 64;                                // speculative entries per coral_search_bfs (CORAL_SEARCH_SPECULATE_MAX)
+    std::mutex spec_m;
+    const struct ActiveBfs *active = nullptr;
+    int64_t spec_in_bfs = 0;                              // speculative entries of the running search (under qm)
+    int64_t stat_spec[3] = {0, 0, 0}, stat_done = 0;      // queued; asked for afterwards; of those done when the step came; steps computed (under qm)
     char err[256] = "";
     // CORAL_SEARCH_PROFILE=1: seconds per phase and work counters over all steps, printed when the handle is freed
     bool profile = false, profile_steps = false;
@@ -348,7 +363,8 @@ struct Threads {
     std::mutex life;                                      // grow / shutdown, one at a time
     std::mutex m;                                         // queue, stop, every handle's `inflight`
     std::condition_variable cv, idle_cv;
-    std::deque<std::shared_ptr<Entry>> queue;
+    std::deque<std::shared_ptr<Entry>> queue, spec_queue; // spec_queue: guesses, taken when `queue` is empty, by at most n_workers - 1
+    int spec_running = 0;                                 // workers computing an entry taken from spec_queue (under m)
     bool stop = false;
     std::vector<std::thread> workers;                     // (under `life`)
     std::atomic<int> n_workers{0};
@@ -373,6 +389,7 @@ struct Threads {
             std::lock_guard<std::mutex> lq(m);
             stop = true;
             queue.clear();                                // (their handles compute them themselves when they are asked for)
+            spec_queue.clear();
         }
         cv.notify_all();
         for (std::thread &t : workers) t.join();
@@ -481,7 +498,7 @@ void run_calls(const Search &S, const int64_t *cand, int64_t n, Calls &c) {
     run_calls_with(S.min_cluster_cutoff, S.bp_distance_cutoff, S.match_cutoff, S.accept_floor, 0, cand, n, c);
 }
 
-void compute_step(Search &S, Scratch &T, const int64_t key[5], StepResult &R) {
+void compute_step(Search &S, Scratch &T, const int64_t key[5], StepResult &R, bool low = false) {
     const int64_t tid = key[0], s = key[1], e = key[2], si = key[3], ei = key[4];
     TaskPool *const pool = helper_pool(S);
     R.clear();
@@ -609,7 +626,7 @@ void compute_step(Search &S, Scratch &T, const int64_t key[5], StepResult &R) {
     if (pooled && n_runs > 1) {
         std::vector<std::function<void()>> tasks;
         for (size_t g = 0; g < n_runs; ++g) tasks.emplace_back([&, g]() { stage_a(g); });
-        pool->run(tasks);
+        pool->run(tasks, low);
     } else {
         for (size_t g = 0; g < n_runs; ++g) stage_a(g);
     }
@@ -639,7 +656,7 @@ void compute_step(Search &S, Scratch &T, const int64_t key[5], StepResult &R) {
                 Scratch sc;                                  // (pairs_between only uses the `used` marks: a few bytes)
                 stage_b(chunks[c], sc);
             });
-        pool->run(tasks);
+        pool->run(tasks, low);
     } else {
         for (Chunk &ch : chunks) stage_b(ch, T);
     }
@@ -672,7 +689,7 @@ void compute_step(Search &S, Scratch &T, const int64_t key[5], StepResult &R) {
         if (pooled && n_big > 1) {
             std::vector<std::function<void()>> tasks;
             for (size_t g = 0; g < n_runs; ++g) tasks.emplace_back([&, g]() { run_calls(S, R.cand.data() + 13 * at[g], at[g + 1] - at[g], R.calls[g]); });
-            pool->run(tasks);
+            pool->run(tasks, low);
         } else {
             for (size_t g = 0; g < n_runs; ++g) run_calls(S, R.cand.data() + 13 * at[g], at[g + 1] - at[g], R.calls[g]);
         }
@@ -718,18 +735,29 @@ std::vector<int> cpus_of_my_node() {
 }
 
 void compute_tail(const Search &S, Entry &e);
+void shadow_after_step(Search &S, const std::shared_ptr<Entry> &e);
 
 void worker_main(Threads *G) {
     Scratch T;                                            // (serves every handle in turn: see Scratch)
     for (;;) {
         std::shared_ptr<Entry> e;
         Search *S;
+        bool guess = false;                               // taken from the speculative lane
         {
             std::unique_lock<std::mutex> lk(G->m);
-            G->cv.wait(lk, [&] { return G->stop || !G->queue.empty(); });
+            // a guess is taken only when no real entry waits, and one worker always stays free for the next real one
+            auto may_guess = [&] { return !G->spec_queue.empty() && G->spec_running < G->n_workers.load() - 1; };
+            G->cv.wait(lk, [&] { return G->stop || !G->queue.empty() || may_guess(); });
             if (G->stop) return;
-            e = G->queue.front();
-            G->queue.pop_front();
+            if (!G->queue.empty()) {
+                e = G->queue.front();
+                G->queue.pop_front();
+            } else {
+                e = G->spec_queue.front();
+                G->spec_queue.pop_front();
+                guess = true;
+                ++G->spec_running;
+            }
             S = e->owner;
             ++S->inflight;                               // from here to the decrement below coral_search_free waits for us
         }
@@ -741,7 +769,7 @@ void worker_main(Threads *G) {
         }
         if (mine) {
             e->t_start = now_s();
-            if (e->kind == 0) compute_step(*S, T, e->key, e->res);
+            if (e->kind == 0) compute_step(*S, T, e->key, e->res, guess);
             else compute_tail(*S, *e);
             e->t_end = now_s();
             {
@@ -749,11 +777,14 @@ void worker_main(Threads *G) {
                 e->done = true;
             }
             e->cv.notify_all();
+            if (e->kind == 0) shadow_after_step(*S, e);   // (the handle is alive: it counts us as in flight)
         }
         {
             std::lock_guard<std::mutex> lk(G->m);
             --S->inflight;                               // (the handle may be gone the moment the lock is released)
+            if (guess) --G->spec_running;
         }
+        if (guess) G->cv.notify_one();                    // (a guess another worker was not allowed to take may be taken now)
         G->idle_cv.notify_all();
     }
 }
@@ -801,23 +832,17 @@ struct BfsParams {
 
 enum { BFS_ERR_KEY_CHROM = -10, BFS_ERR_KEY_CHRIDX = -11, BFS_ERR_INDEX = -12 };
 
-struct BfsRun {
-    Search &S;
-    const BfsParams &P;
-    BfsOut &O;
-    BfsRun(Search &s, const BfsParams &p, BfsOut &o) : S(s), P(p), O(o) {}
-    struct MemoHash {
-        size_t operator()(const std::array<int64_t, 3> &k) const {
-            uint64_t h = (uint64_t)k[0] * 0x9E3779B97F4A7C15ull;
-            h ^= ((uint64_t)k[1] + 0x7F4A7C15ull) * 0xBF58476D1CE4E5B9ull;
-            h ^= ((uint64_t)k[2] + 0x94D049BBull) * 0x94D049BB133111EBull;
-            return (size_t)(h ^ (h >> 29));
-        }
-    };
-    std::vector<std::shared_ptr<Entry>> held;
-    std::unordered_map<std::array<int64_t, 3>, std::array<int64_t, 2>, MemoHash> chunk_memo;     // (step result, run, call) -> chunk
-    double t_steps = 0;                                      // CORAL_SEARCH_PROFILE: seconds inside coral_search_step (waits included)
+// The running coral_search_bfs of a handle, as a shadow pass sees it (Search::active, under Search::spec_m).
+struct ActiveBfs {
+    const BfsParams *P;
+    const BfsOut *O;
+};
 
+// The CN-segment tables and the parameters that the refinement reads; nothing of the search's own state.
+struct Geom {
+    const Search &S;
+    const BfsParams &P;
+    Geom(const Search &s, const BfsParams &p) : S(s), P(p) {}
     int64_t nseg(int64_t t) const { return S.seg_off[t + 1] - S.seg_off[t]; }
     int64_t sstart(int64_t t, int64_t k) const { return S.seg_start[S.seg_off[t] + k]; }
     int64_t send(int64_t t, int64_t k) const { return S.seg_end[S.seg_off[t] + k]; }
@@ -832,13 +857,201 @@ struct BfsRun {
         return -1;
     }
     bool pos2cni_any(int64_t t, int64_t pos) const { return pos2cni(t, pos) >= 0; }
+    static bool overlap(int64_t at, int64_t a1, int64_t a2, int64_t bt, int64_t b1, int64_t b2) {
+        return at == bt && a1 <= b2 && b1 <= a2;             // interval_overlap (bu:11-15)
+    }
+};
+
+// A refined target interval of one search step (ibg:459-612): contig, [l, r], whether `l` holds a comparison result (Q2),
+// and the breakpoints (indices into the list `bp_of` reads) that an `inside` run is made of.
+struct Ref { int64_t t, l, r; bool l_bool; std::vector<int64_t> bps; };
+struct Part { int64_t s, e; };
+
+// The inside / outside refinement of one run of a step (ibg:459-612): `found` are the breakpoints the run's calls were merged
+// into, bp_of(k) gives f[0..5] of breakpoint k, `here` is the interval being searched, (c, ns, ne) the run's segments.  Appends
+// to `refined`; ev3() is called where the reference logs its "neither end here" line.  Reads the lists it is given and the
+// tables of `G` only, so the search runs it on its own lists and a shadow pass on a copy.
+template <class BpOf, class Ev3>
+int refine_group(const Geom &G, BpOf bp_of, const std::vector<int64_t> &found, int64_t here_t, int64_t here_s, int64_t here_e, int64_t c,
+                 int64_t ns, int64_t ne, std::vector<Ref> &refined, int64_t *err_tid, Ev3 ev3) {
+    const Search &S = G.S;
+    const BfsParams &P = G.P;
+    const int64_t half = (int64_t)((double)S.max_seq_len / 2.0);
+    const int64_t D = P.D;
+    const double gain = P.cn_gain;
+    auto overlap = Geom::overlap;
+    auto nseg = [&](int64_t t) { return G.nseg(t); };
+    auto sstart = [&](int64_t t, int64_t k) { return G.sstart(t, k); };
+    auto send = [&](int64_t t, int64_t k) { return G.send(t, k); };
+    auto scn = [&](int64_t t, int64_t k) { return G.scn(t, k); };
+    auto pos2cni = [&](int64_t t, int64_t pos) { return G.pos2cni(t, pos); };
+    auto pos2cni_any = [&](int64_t t, int64_t pos) { return G.pos2cni_any(t, pos); };
+    struct In { int64_t cni, pos, k; };
+    struct Out { int64_t t, cni, pos, k; };
+    std::vector<In> inside;
+    std::vector<Out> outside;
+    for (int64_t k : found) {
+        const int64_t *bp = bp_of(k);
+        const int64_t t1 = bp[0], p1 = bp[1], t2 = bp[3], p2 = bp[4];
+        // (an IndexError / KeyError of pos2cni(..)[0] ends this breakpoint's turn — what was appended before stays)
+        if (overlap(t1, p1, p1, here_t, here_s, here_e) && overlap(t2, p2, p2, c, ns, ne)) {
+            const int64_t q = pos2cni(t2, p2);
+            if (q >= 0) inside.push_back({q, p2, k});
+        } else if (overlap(t2, p2, p2, here_t, here_s, here_e) && overlap(t1, p1, p1, c, ns, ne)) {
+            const int64_t q = pos2cni(t1, p1);
+            if (q >= 0) inside.push_back({q, p1, k});
+        } else {
+            ev3();
+            const bool o1 = overlap(t1, p1, p1, c, ns, ne), o2 = overlap(t2, p2, p2, c, ns, ne);
+            const int64_t q1 = pos2cni(t1, p1);
+            if (q1 < 0) continue;
+            if (o1) inside.push_back({q1, p1, k}); else outside.push_back({t1, q1, p1, k});
+            const int64_t q2 = pos2cni(t2, p2);
+            if (q2 < 0) continue;
+            if (o2) inside.push_back({q2, p2, k}); else outside.push_back({t2, q2, p2, k});
+        }
+    }
+    if (found.empty()) return CORAL_OK;
+    std::stable_sort(inside.begin(), inside.end(), [](const In &a, const In &b) { return a.cni != b.cni ? a.cni < b.cni : a.pos < b.pos; });
+    for (const Out &o : outside)
+        if (o.t < 0 || o.t >= S.n_tid || P.chr_rank[o.t] < 0) { *err_tid = o.t; return BFS_ERR_KEY_CHRIDX; }
+    std::stable_sort(outside.begin(), outside.end(), [&](const Out &a, const Out &b) {
+        const int32_t ra = P.chr_rank[a.t], rb = P.chr_rank[b.t];
+        if (ra != rb) return ra < rb;
+        if (a.cni != b.cni) return a.cni < b.cni;
+        return a.pos < b.pos;
+    });
+    const int64_t n_c_seg = nseg(c);
+    auto seg_ok = [&](int64_t t, int64_t k) { return k >= 0 && k < nseg(t); };
+    for (const In &x : inside) if (!seg_ok(c, x.cni)) return BFS_ERR_INDEX;
+    for (const Out &x : outside) if (!seg_ok(x.t, x.cni)) return BFS_ERR_INDEX;
+    if (n_c_seg == 0) return BFS_ERR_INDEX;
+    // ---- runs of `inside` breakpoints -> refined intervals on contig c (ibg:484-546)
+    auto split_inside = [&](size_t k) {
+        const int64_t nil = sstart(c, inside[k + 1].cni), lir = send(c, inside[k].cni);
+        const double ncn = scn(c, inside[k + 1].cni), lcn = scn(c, inside[k].cni);
+        const bool amp = ncn >= gain || lcn >= gain;
+        const int64_t dpos = inside[k + 1].pos - inside[k].pos;
+        return inside[k + 1].cni - inside[k].cni > 2 || (double)(nil - lir) > (double)S.max_seq_len / 2.0 || dpos > S.max_seq_len ||
+               (!amp && nil - lir > 2 * D) || (!amp && dpos > 3 * D);
+    };
+    size_t first = 0;
+    for (size_t k = 0; k + 1 < inside.size(); ++k) {
+        if (!split_inside(k)) continue;
+        const In &f = inside[first], &z = inside[k];
+        const int64_t lir = send(c, z.cni);
+        int64_t l = std::max((!(scn(c, f.cni) >= gain) ? f.pos : sstart(c, f.cni)) - D, sstart(c, 0));
+        int64_t r = std::min((!(scn(c, z.cni) >= gain) ? z.pos : lir) + D, send(c, n_c_seg - 1));
+        const double fcn = scn(c, f.cni);
+        if ((fcn != 0.0) && f.pos - half > l) l = f.pos - half;                 // Q3: the CN value as a truth value (NaN is true)
+        if (z.pos + half < r) r = z.pos + half;
+        if (!pos2cni_any(c, l)) l = sstart(c, f.cni);
+        if (!pos2cni_any(c, r)) r = lir;
+        Ref ref{c, l, r, false, {}};
+        for (size_t j = first; j <= k; ++j) ref.bps.push_back(inside[j].k);
+        refined.push_back(std::move(ref));
+        first = k + 1;
+    }
+    if (!inside.empty()) {
+        const In &f = inside[first], &z = inside.back();
+        int64_t l = std::max((!(scn(c, f.cni) >= gain) ? f.pos : sstart(c, f.cni)) - D, sstart(c, 0));
+        int64_t r = std::min((!(scn(c, z.cni) >= gain) ? z.pos : send(c, z.cni)) + D, send(c, n_c_seg - 1));
+        bool l_bool = false;
+        if (f.pos - half > l) { l = (f.pos - half > l) ? 1 : 0; l_bool = true; }          // Q2: the comparison result is stored
+        if (z.pos + half < r) r = z.pos + half;
+        if (!pos2cni_any(c, l)) { l = sstart(c, f.cni); l_bool = false; }
+        if (!pos2cni_any(c, r)) r = send(c, z.cni);
+        Ref ref{c, l, r, l_bool, {}};
+        for (size_t j = first; j < inside.size(); ++j) ref.bps.push_back(inside[j].k);
+        refined.push_back(std::move(ref));
+    }
+    // ---- runs of `outside` ends -> refined intervals on their own contigs (ibg:548-612)
+    auto split_outside = [&](size_t k) {
+        const Out &a = outside[k], &b = outside[k + 1];
+        const int64_t nil = sstart(b.t, b.cni), lir = send(a.t, a.cni);
+        const double ncn = scn(b.t, b.cni), lcn = scn(a.t, a.cni);
+        const bool amp = ncn >= gain || lcn >= gain;
+        return b.t != a.t || b.cni - a.cni > 2 || (double)(nil - lir) > (double)S.max_seq_len / 2.0 || b.pos - a.pos > S.max_seq_len ||
+               (!amp && nil - lir > 2 * D) || (!amp && b.pos - a.pos > 3 * D);
+    };
+    first = 0;
+    for (size_t k = 0; k + 1 < outside.size(); ++k) {
+        if (!split_outside(k)) continue;
+        const Out &f = outside[first], &z = outside[k];
+        const int64_t lir = send(z.t, z.cni);
+        int64_t l = std::max((!(scn(f.t, f.cni) >= gain) ? f.pos : sstart(f.t, f.cni)) - D, sstart(f.t, 0));
+        int64_t r = std::min((!(scn(z.t, z.cni) >= gain) ? z.pos : lir) + D, send(z.t, nseg(z.t) - 1));
+        if (f.pos - half > l) l = f.pos - half;
+        if (z.pos + half < r) r = z.pos + half;
+        if (!pos2cni_any(f.t, l)) l = sstart(f.t, f.cni);
+        if (!pos2cni_any(z.t, r)) r = lir;
+        refined.push_back(Ref{f.t, l, r, false, {}});
+        first = k + 1;
+    }
+    if (!outside.empty()) {
+        const Out &f = outside[first], &z = outside.back();
+        int64_t l = std::max((!(scn(f.t, f.cni) >= gain) ? f.pos : sstart(f.t, f.cni)) - D, sstart(f.t, 0));
+        int64_t r = std::min((!(scn(z.t, z.cni) >= gain) ? z.pos : send(z.t, z.cni)) + D, send(z.t, nseg(z.t) - 1));
+        if (f.pos - half > l) l = f.pos - half;
+        if (z.pos + half < r) r = z.pos + half;
+        if (!pos2cni_any(f.t, l)) l = sstart(f.t, f.cni);
+        if (!pos2cni_any(f.t, r)) {
+            if (!seg_ok(f.t, z.cni)) return BFS_ERR_INDEX;
+            r = send(f.t, z.cni);                                            // (by[f[0]][z[1]]: the FIRST end's contig, as written)
+        }
+        refined.push_back(Ref{f.t, l, r, false, {}});
+    }
+    return CORAL_OK;
+}
+
+// interval_exclusive (bu:54-67) of a refined interval against an interval list iv [n][5]: the parts of the candidate that the
+// list does not cover, and the list's intervals it overlaps in the iteration order of the reference's (CPython) set.
+void exclusive_parts(const Ref &ref, const std::vector<int64_t> &iv, std::vector<Part> &parts, std::vector<int64_t> &hits) {
+    PySetEmu hit;
+    parts.assign(1, Part{ref.l, ref.r});
+    hits.clear();
+    const int64_t n_iv = (int64_t)(iv.size() / 5);
+    for (int64_t k = 0; k < n_iv; ++k) {
+        const int64_t bt = iv[5 * k], bs = iv[5 * k + 1], be = iv[5 * k + 2];
+        for (int64_t j = (int64_t)parts.size() - 1; j >= 0; --j) {
+            const Part p = parts[(size_t)j];
+            if (Geom::overlap(ref.t, p.s, p.e, bt, bs, be)) {
+                hit.add((int32_t)k, (int64_t)k);
+                parts.erase(parts.begin() + j);
+                if (p.s < bs) parts.push_back({p.s, bs - 1});
+                if (p.e > be) parts.push_back({be + 1, p.e});
+            }
+        }
+    }
+    for (size_t slot = 0; slot <= hit.mask; ++slot)
+        if (hit.key[slot] >= 0) hits.push_back(hit.key[slot]);
+}
+
+// addbp's matching rule (ibg:326-340) on f[0..5]: the same ends within 200 bp
+inline bool same_bp(const int64_t *b, const int64_t *f) {
+    return b[0] == f[0] && b[3] == f[3] && b[2] == f[2] && b[5] == f[5] && llabs(b[1] - f[1]) < 200 && llabs(b[4] - f[4]) < 200;
+}
+
+struct BfsRun : Geom {
+    Search &Sm;                                          // the handle again, to change it (Geom::S reads it)
+    BfsOut &O;
+    BfsRun(Search &s, const BfsParams &p, BfsOut &o) : Geom(s, p), Sm(s), O(o) {}
+    struct MemoHash {
+        size_t operator()(const std::array<int64_t, 3> &k) const {
+            uint64_t h = (uint64_t)k[0] * 0x9E3779B97F4A7C15ull;
+            h ^= ((uint64_t)k[1] + 0x7F4A7C15ull) * 0xBF58476D1CE4E5B9ull;
+            h ^= ((uint64_t)k[2] + 0x94D049BBull) * 0x94D049BB133111EBull;
+            return (size_t)(h ^ (h >> 29));
+        }
+    };
+    std::vector<std::shared_ptr<Entry>> held;
+    std::unordered_map<std::array<int64_t, 3>, std::array<int64_t, 2>, MemoHash> chunk_memo;     // (step result, run, call) -> chunk
+    double t_steps = 0;                                      // CORAL_SEARCH_PROFILE: seconds inside coral_search_step (waits included)
+
     void event(int64_t ty, int64_t a = 0, int64_t b = 0, int64_t c = 0, int64_t d = 0, int64_t e = 0) {
         if (!P.log_events) return;
         const int64_t row[6] = {ty, a, b, c, d, e};
         O.events.insert(O.events.end(), row, row + 6);
-    }
-    static bool overlap(int64_t at, int64_t a1, int64_t a2, int64_t bt, int64_t b1, int64_t b2) {
-        return at == bt && a1 <= b2 && b1 <= a2;             // interval_overlap (bu:11-15)
     }
     int64_t conn_index(int64_t a, int64_t b, bool create) {
         for (size_t k = 0; k < O.conn_key.size(); ++k)
@@ -858,14 +1071,13 @@ struct BfsRun {
         const int64_t si = pos2cni(t, s), ei = pos2cni(t, e);
         if (si < 0 || ei < 0) return CORAL_OK;
         if (!P.tid_has_rows[t]) return CORAL_OK;
-        return coral_search_prefetch(&S, t, s, e, si, ei);
+        return coral_search_prefetch(&Sm, t, s, e, si, ei);
     }
 
     // addbp (ibg:326-340): merge into the first breakpoint with the same ends within 200 bp, else append
     int64_t addbp(const int64_t f[11], const double stats[6], int32_t flags, int64_t ccid, const std::array<int64_t, 2> &chunk) {
         for (size_t k = 0; k < O.bps.size(); ++k) {
-            const int64_t *b = O.bps[k].f;
-            if (b[0] == f[0] && b[3] == f[3] && b[2] == f[2] && b[5] == f[5] && llabs(b[1] - f[1]) < 200 && llabs(b[4] - f[4]) < 200) {
+            if (same_bp(O.bps[k].f, f)) {
                 O.bps[k].chunks.push_back(chunk);
                 return (int64_t)k;
             }
@@ -881,10 +1093,9 @@ struct BfsRun {
     }
 
     int bfs_from(int64_t ai, int64_t ccid) {
-        const int64_t half = (int64_t)((double)S.max_seq_len / 2.0);
-        const int64_t D = P.D;
-        const double gain = P.cn_gain;
         std::deque<int64_t> queue{ai};
+        // (shadow passes read O.iv / O.bps under spec_m: held here whenever the lists may change, i.e. always but in a step)
+        std::unique_lock<std::mutex> lists(Sm.spec_m);
         while (!queue.empty()) {
             const int64_t cur = queue.front();
             queue.pop_front();
@@ -896,7 +1107,9 @@ struct BfsRun {
             if (si < 0 || ei < 0) continue;
             if (!P.tid_has_rows[tid]) { O.err_tid = tid; return BFS_ERR_KEY_CHROM; }
             const double ts0 = S.profile ? now_s() : 0.0;
-            int rc = coral_search_step(&S, tid, s, e, si, ei);
+            lists.unlock();
+            int rc = coral_search_step(&Sm, tid, s, e, si, ei);
+            lists.lock();
             if (S.profile) t_steps += now_s() - ts0;
             if (rc != CORAL_OK) return rc;
             if (S.current_entry) held.push_back(S.current_entry);      // (step results stay alive: chunk_memo is keyed by their address)
@@ -904,7 +1117,6 @@ struct BfsRun {
             const StepResult &R = *S.current;
             const size_t ng = R.groups.size() / 4;
             const int64_t here_t = tid, here_s = s, here_e = e;      // `here` is not modified before all groups are done
-            struct Ref { int64_t t, l, r; bool l_bool; std::vector<int64_t> bps; };
             std::vector<Ref> refined;
             int64_t cand_at = 0;
             for (size_t gi = 0; gi < ng; ++gi) {
@@ -948,144 +1160,16 @@ struct BfsRun {
                     const int64_t k = addbp(f, calls.stats.data() + 6 * (size_t)q, calls.flags[(size_t)q], ccid, chunk);
                     if (std::find(found.begin(), found.end(), k) == found.end()) found.push_back(k);
                 }
-                struct In { int64_t cni, pos, k; };
-                struct Out { int64_t t, cni, pos, k; };
-                std::vector<In> inside;
-                std::vector<Out> outside;
-                for (int64_t k : found) {
-                    const int64_t *bp = O.bps[(size_t)k].f;
-                    const int64_t t1 = bp[0], p1 = bp[1], t2 = bp[3], p2 = bp[4];
-                    // (an IndexError / KeyError of pos2cni(..)[0] ends this breakpoint's turn — what was appended before stays)
-                    if (overlap(t1, p1, p1, here_t, here_s, here_e) && overlap(t2, p2, p2, c, ns, ne)) {
-                        const int64_t q = pos2cni(t2, p2);
-                        if (q >= 0) inside.push_back({q, p2, k});
-                    } else if (overlap(t2, p2, p2, here_t, here_s, here_e) && overlap(t1, p1, p1, c, ns, ne)) {
-                        const int64_t q = pos2cni(t1, p1);
-                        if (q >= 0) inside.push_back({q, p1, k});
-                    } else {
-                        event(3);
-                        const bool o1 = overlap(t1, p1, p1, c, ns, ne), o2 = overlap(t2, p2, p2, c, ns, ne);
-                        const int64_t q1 = pos2cni(t1, p1);
-                        if (q1 < 0) continue;
-                        if (o1) inside.push_back({q1, p1, k}); else outside.push_back({t1, q1, p1, k});
-                        const int64_t q2 = pos2cni(t2, p2);
-                        if (q2 < 0) continue;
-                        if (o2) inside.push_back({q2, p2, k}); else outside.push_back({t2, q2, p2, k});
-                    }
-                }
-                if (found.empty()) continue;
-                std::stable_sort(inside.begin(), inside.end(), [](const In &a, const In &b) { return a.cni != b.cni ? a.cni < b.cni : a.pos < b.pos; });
-                for (const Out &o : outside)
-                    if (o.t < 0 || o.t >= S.n_tid || P.chr_rank[o.t] < 0) { O.err_tid = o.t; return BFS_ERR_KEY_CHRIDX; }
-                std::stable_sort(outside.begin(), outside.end(), [&](const Out &a, const Out &b) {
-                    const int32_t ra = P.chr_rank[a.t], rb = P.chr_rank[b.t];
-                    if (ra != rb) return ra < rb;
-                    if (a.cni != b.cni) return a.cni < b.cni;
-                    return a.pos < b.pos;
-                });
-                const int64_t n_c_seg = nseg(c);
-                auto seg_ok = [&](int64_t t, int64_t k) { return k >= 0 && k < nseg(t); };
-                for (const In &x : inside) if (!seg_ok(c, x.cni)) return BFS_ERR_INDEX;
-                for (const Out &x : outside) if (!seg_ok(x.t, x.cni)) return BFS_ERR_INDEX;
-                if (n_c_seg == 0) return BFS_ERR_INDEX;
-                // ---- runs of `inside` breakpoints -> refined intervals on contig c (ibg:484-546)
-                auto split_inside = [&](size_t k) {
-                    const int64_t nil = sstart(c, inside[k + 1].cni), lir = send(c, inside[k].cni);
-                    const double ncn = scn(c, inside[k + 1].cni), lcn = scn(c, inside[k].cni);
-                    const bool amp = ncn >= gain || lcn >= gain;
-                    const int64_t dpos = inside[k + 1].pos - inside[k].pos;
-                    return inside[k + 1].cni - inside[k].cni > 2 || (double)(nil - lir) > (double)S.max_seq_len / 2.0 || dpos > S.max_seq_len ||
-                           (!amp && nil - lir > 2 * D) || (!amp && dpos > 3 * D);
-                };
-                size_t first = 0;
-                for (size_t k = 0; k + 1 < inside.size(); ++k) {
-                    if (!split_inside(k)) continue;
-                    const In &f = inside[first], &z = inside[k];
-                    const int64_t lir = send(c, z.cni);
-                    int64_t l = std::max((!(scn(c, f.cni) >= gain) ? f.pos : sstart(c, f.cni)) - D, sstart(c, 0));
-                    int64_t r = std::min((!(scn(c, z.cni) >= gain) ? z.pos : lir) + D, send(c, n_c_seg - 1));
-                    const double fcn = scn(c, f.cni);
-                    if ((fcn != 0.0) && f.pos - half > l) l = f.pos - half;                 // Q3: the CN value as a truth value (NaN is true)
-                    if (z.pos + half < r) r = z.pos + half;
-                    if (!pos2cni_any(c, l)) l = sstart(c, f.cni);
-                    if (!pos2cni_any(c, r)) r = lir;
-                    Ref ref{c, l, r, false, {}};
-                    for (size_t j = first; j <= k; ++j) ref.bps.push_back(inside[j].k);
-                    refined.push_back(std::move(ref));
-                    first = k + 1;
-                }
-                if (!inside.empty()) {
-                    const In &f = inside[first], &z = inside.back();
-                    int64_t l = std::max((!(scn(c, f.cni) >= gain) ? f.pos : sstart(c, f.cni)) - D, sstart(c, 0));
-                    int64_t r = std::min((!(scn(c, z.cni) >= gain) ? z.pos : send(c, z.cni)) + D, send(c, n_c_seg - 1));
-                    bool l_bool = false;
-                    if (f.pos - half > l) { l = (f.pos - half > l) ? 1 : 0; l_bool = true; }          // Q2: the comparison result is stored
-                    if (z.pos + half < r) r = z.pos + half;
-                    if (!pos2cni_any(c, l)) { l = sstart(c, f.cni); l_bool = false; }
-                    if (!pos2cni_any(c, r)) r = send(c, z.cni);
-                    Ref ref{c, l, r, l_bool, {}};
-                    for (size_t j = first; j < inside.size(); ++j) ref.bps.push_back(inside[j].k);
-                    refined.push_back(std::move(ref));
-                }
-                // ---- runs of `outside` ends -> refined intervals on their own contigs (ibg:548-612)
-                auto split_outside = [&](size_t k) {
-                    const Out &a = outside[k], &b = outside[k + 1];
-                    const int64_t nil = sstart(b.t, b.cni), lir = send(a.t, a.cni);
-                    const double ncn = scn(b.t, b.cni), lcn = scn(a.t, a.cni);
-                    const bool amp = ncn >= gain || lcn >= gain;
-                    return b.t != a.t || b.cni - a.cni > 2 || (double)(nil - lir) > (double)S.max_seq_len / 2.0 || b.pos - a.pos > S.max_seq_len ||
-                           (!amp && nil - lir > 2 * D) || (!amp && b.pos - a.pos > 3 * D);
-                };
-                first = 0;
-                for (size_t k = 0; k + 1 < outside.size(); ++k) {
-                    if (!split_outside(k)) continue;
-                    const Out &f = outside[first], &z = outside[k];
-                    const int64_t lir = send(z.t, z.cni);
-                    int64_t l = std::max((!(scn(f.t, f.cni) >= gain) ? f.pos : sstart(f.t, f.cni)) - D, sstart(f.t, 0));
-                    int64_t r = std::min((!(scn(z.t, z.cni) >= gain) ? z.pos : lir) + D, send(z.t, nseg(z.t) - 1));
-                    if (f.pos - half > l) l = f.pos - half;
-                    if (z.pos + half < r) r = z.pos + half;
-                    if (!pos2cni_any(f.t, l)) l = sstart(f.t, f.cni);
-                    if (!pos2cni_any(z.t, r)) r = lir;
-                    refined.push_back(Ref{f.t, l, r, false, {}});
-                    first = k + 1;
-                }
-                if (!outside.empty()) {
-                    const Out &f = outside[first], &z = outside.back();
-                    int64_t l = std::max((!(scn(f.t, f.cni) >= gain) ? f.pos : sstart(f.t, f.cni)) - D, sstart(f.t, 0));
-                    int64_t r = std::min((!(scn(z.t, z.cni) >= gain) ? z.pos : send(z.t, z.cni)) + D, send(z.t, nseg(z.t) - 1));
-                    if (f.pos - half > l) l = f.pos - half;
-                    if (z.pos + half < r) r = z.pos + half;
-                    if (!pos2cni_any(f.t, l)) l = sstart(f.t, f.cni);
-                    if (!pos2cni_any(f.t, r)) {
-                        if (!seg_ok(f.t, z.cni)) return BFS_ERR_INDEX;
-                        r = send(f.t, z.cni);                                            // (by[f[0]][z[1]]: the FIRST end's contig, as written)
-                    }
-                    refined.push_back(Ref{f.t, l, r, false, {}});
-                }
+                const int rcg = refine_group(*this, [&](int64_t k) { return (const int64_t *)O.bps[(size_t)k].f; }, found, here_t, here_s, here_e, c, ns, ne,
+                                             refined, &O.err_tid, [&] { event(3); });
+                if (rcg != CORAL_OK) return rcg;
             }
             // ---- the refined intervals against the interval list (ibg:614-673)
             for (const Ref &ref : refined) {
                 // interval_exclusive (bu:54-67): parts of the candidate not covered by the list + the (CPython) set of intervals it overlaps
-                PySetEmu hit;
-                struct Part { int64_t s, e; };
-                std::vector<Part> parts{{ref.l, ref.r}};
-                const int64_t n_iv = (int64_t)(O.iv.size() / 5);
-                for (int64_t k = 0; k < n_iv; ++k) {
-                    const int64_t bt = O.iv[5 * k], bs = O.iv[5 * k + 1], be = O.iv[5 * k + 2];
-                    for (int64_t j = (int64_t)parts.size() - 1; j >= 0; --j) {
-                        const Part p = parts[(size_t)j];
-                        if (overlap(ref.t, p.s, p.e, bt, bs, be)) {
-                            hit.add((int32_t)k, (int64_t)k);
-                            parts.erase(parts.begin() + j);
-                            if (p.s < bs) parts.push_back({p.s, bs - 1});
-                            if (p.e > be) parts.push_back({be + 1, p.e});
-                        }
-                    }
-                }
+                std::vector<Part> parts;
                 std::vector<int64_t> hits;
-                for (size_t slot = 0; slot <= hit.mask; ++slot)
-                    if (hit.key[slot] >= 0) hits.push_back(hit.key[slot]);
+                exclusive_parts(ref, O.iv, parts, hits);
                 auto bp_touches = [&](const int64_t *bp, int64_t o, bool first_end) {
                     const int64_t t = first_end ? bp[0] : bp[3], p = first_end ? bp[1] : bp[4];
                     return overlap(t, p, p, O.iv[5 * o], O.iv[5 * o + 1], O.iv[5 * o + 2]);
@@ -1132,6 +1216,113 @@ struct BfsRun {
         return CORAL_OK;
     }
 };
+
+// ---------------------------------------------------------------------------------------------
+// Exploring ahead (CORAL_SEARCH_SPECULATE).  The search above walks its queue serially and asks for an interval's step the
+// moment the parent's step has been consumed, so it waits for nearly every step off a seed — while the seeds' own steps, queued
+// when the handle was attached, sit finished and the other workers idle.  A step is a pure function of its key and the cache
+// is keyed by exactly that, so a thread that holds a FINISHED step may work out which intervals the search will probably derive
+// from it and queue those keys as speculative entries: a right guess is a cache hit, a wrong one is work of an idle thread, and
+// nothing the search computes can change — a shadow pass writes to no list of the search, logs nothing, and a guess that
+// would raise is not made.  The guess replays the search's own code (addbp's matching rule, refine_group, exclusive_parts,
+// enqueue's segment lookup) against the search's lists as they stand when the guess is made; it differs from the real request
+// where the real lists have grown by then.
+// ---------------------------------------------------------------------------------------------
+void spec_queue_key(Search &S, const std::array<int64_t, 5> &key) {
+    std::shared_ptr<Entry> ent;
+    {
+        std::lock_guard<std::mutex> lk(S.qm);
+        if (S.spec_in_bfs >= S.spec_max || S.cache.find(key) != S.cache.end()) return;
+        ent = std::make_shared<Entry>();
+        memcpy(ent->key, key.data(), sizeof(ent->key));
+        ent->owner = &S;
+        ent->t_queued = now_s();
+        ent->born_spec = ent->spec = true;
+        S.cache.emplace(key, ent);
+        ++S.spec_in_bfs;
+        ++S.stat_spec[0];
+    }
+    Threads *G = threads_if_any();                        // (a worker is one of its threads; no thread is started for a guess)
+    if (!G) return;
+    {
+        std::lock_guard<std::mutex> lk(G->m);
+        G->spec_queue.push_back(ent);
+    }
+    G->cv.notify_one();
+}
+
+// The keys a finished step implies.  Called with S.spec_m held and S.active set.
+void shadow_keys(Search &S, const Entry &e, std::vector<std::array<int64_t, 5>> &keys) {
+    const ActiveBfs &A = *S.active;
+    const BfsParams &P = *A.P;
+    const BfsOut &O = *A.O;
+    const StepResult &R = e.res;
+    if (R.rc != CORAL_OK) return;
+    const Geom G(S, P);
+    const int64_t here_t = e.key[0], here_s = e.key[1], here_e = e.key[2];
+    const size_t n_real = O.bps.size();
+    std::vector<std::array<int64_t, 6>> extra;            // breakpoints the real addbp would append
+    auto bp_of = [&](int64_t k) { return (size_t)k < n_real ? (const int64_t *)O.bps[(size_t)k].f : (const int64_t *)extra[(size_t)k - n_real].data(); };
+    std::vector<Ref> refined;
+    const size_t ng = R.groups.size() / 4;
+    int64_t cand_at = 0, err_tid = -1;
+    for (size_t gi = 0; gi < ng; ++gi) {
+        const int64_t c = R.groups[4 * gi], b0 = R.groups[4 * gi + 1], b1 = R.groups[4 * gi + 2], n_c = R.groups[4 * gi + 3];
+        const int64_t *cand = R.cand.data() + 13 * cand_at;
+        cand_at += n_c;
+        if (c < 0 || c >= S.n_tid || b0 < 0 || b1 < 0 || b0 >= G.nseg(c) || b1 >= G.nseg(c) || gi >= R.calls.size()) return;
+        const int64_t ns = G.sstart(c, b0), ne = G.send(c, b1);
+        const Calls &calls = R.calls[gi];
+        std::vector<int64_t> found;
+        for (int32_t q = 0; q < calls.n_calls; ++q) {
+            const int64_t *h = cand + 13 * calls.head[(size_t)q];
+            const std::array<int64_t, 6> f = {h[0], calls.p1[(size_t)q], h[2], h[3], calls.p2[(size_t)q], h[5]};
+            int64_t k = -1;
+            for (size_t j = 0; j < n_real + extra.size() && k < 0; ++j)
+                if (same_bp(bp_of((int64_t)j), f.data())) k = (int64_t)j;
+            if (k < 0) { extra.push_back(f); k = (int64_t)(n_real + extra.size()) - 1; }
+            if (std::find(found.begin(), found.end(), k) == found.end()) found.push_back(k);
+        }
+        if (refine_group(G, bp_of, found, here_t, here_s, here_e, c, ns, ne, refined, &err_tid, [] {}) != CORAL_OK) return;
+    }
+    if (refined.empty()) return;
+    // the parts against a copy of the search's list, which grows by the parts as the search's own would
+    std::vector<int64_t> iv(O.iv);
+    std::vector<Part> parts;
+    std::vector<int64_t> hits;
+    for (const Ref &ref : refined) {
+        exclusive_parts(ref, iv, parts, hits);
+        for (const Part &part : parts) {
+            const int64_t row[5] = {ref.t, part.s, part.e, -1, 0};
+            iv.insert(iv.end(), row, row + 5);
+            const int64_t si = G.pos2cni(ref.t, part.s), ei = G.pos2cni(ref.t, part.e);       // as BfsRun::enqueue
+            if (si < 0 || ei < 0 || !P.tid_has_rows[ref.t]) continue;
+            keys.push_back({ref.t, part.s, part.e, si, ei});
+        }
+    }
+}
+
+// The guesses are queued with spec_m still held, i.e. while the search is known to be running: coral_search_bfs clears `active`
+// under spec_m BEFORE it takes its guesses out of the queue, so none can arrive behind that sweep — nor, the search having
+// returned, behind the one of coral_search_free.  (Order of the locks: spec_m, then qm, then Threads::m, as on the search thread.)
+void shadow_pass(Search &S, const Entry &e) {
+    try {
+        std::lock_guard<std::mutex> lk(S.spec_m);
+        if (!S.active) return;
+        std::vector<std::array<int64_t, 5>> keys;
+        shadow_keys(S, e, keys);
+        for (const auto &k : keys) spec_queue_key(S, k);
+    } catch (...) {                                       // (out of memory in a guess: the guess is not made)
+    }
+}
+
+void shadow_after_step(Search &S, const std::shared_ptr<Entry> &e) {
+    {
+        std::lock_guard<std::mutex> lk(S.qm);
+        ++S.stat_done;
+    }
+    if (S.speculate) shadow_pass(S, *e);
+}
 }  // namespace
 
 // The part of a handle that needs the chimeric table and the pair table only: both are on the host while the build still
@@ -1183,6 +1374,9 @@ extern "C" void *coral_search_create_early(int64_t n_reads, int64_t n_rows, cons
     S->profile = pe && (pe[0] == '1' || pe[0] == '2');
     S->profile_steps = pe && pe[0] == '2';
     if (const char *pm = getenv("CORAL_SEARCH_PAR_MIN")) S->par_min_reads = S->par_min_cands = atoll(pm);
+    if (const char *sp = getenv("CORAL_SEARCH_SPECULATE")) S->speculate = sp[0] != '0';
+    else S->speculate = true;
+    if (const char *sp = getenv("CORAL_SEARCH_SPECULATE_MAX")) S->spec_max = std::max<int64_t>(0, atoll(sp));
     S->main_result.clear();
     S->current = &S->main_result;
     return S;
@@ -1334,8 +1528,8 @@ extern "C" int coral_search_free(void *h) {
         if (Threads *G = threads_if_any()) {
             // no thread is joined: what is still queued for this handle is dropped, what a worker holds is waited for
             std::unique_lock<std::mutex> lk(G->m);
-            auto &q = G->queue;
-            q.erase(std::remove_if(q.begin(), q.end(), [&](const std::shared_ptr<Entry> &e) { return e->owner == &S; }), q.end());
+            for (auto *q : {&G->queue, &G->spec_queue})
+                q->erase(std::remove_if(q->begin(), q->end(), [&](const std::shared_ptr<Entry> &e) { return e->owner == &S; }), q->end());
             G->idle_cv.wait(lk, [&] { return S.inflight == 0; });
         }
     S.pack.give_back();                                   // (the next handle's pack: PackBuf)
@@ -1358,20 +1552,36 @@ extern "C" int coral_search_prefetch(void *h, int64_t tid, int64_t s, int64_t e,
     if (S.n_threads == 0) return CORAL_OK;
     const std::array<int64_t, 5> key = {tid, s, e, si, ei};
     std::shared_ptr<Entry> ent;
+    bool guessed = false;                                 // the key is there as a guess nobody has asked for yet
     {
         std::lock_guard<std::mutex> lk(S.qm);
-        if (S.cache.find(key) != S.cache.end()) return CORAL_OK;
-        ent = std::make_shared<Entry>();
-        memcpy(ent->key, key.data(), sizeof(ent->key));
-        ent->owner = &S;
-        ent->t_queued = now_s();
-        S.cache.emplace(key, ent);
+        auto it = S.cache.find(key);
+        if (it != S.cache.end()) {
+            if (!it->second->spec) return CORAL_OK;
+            ent = it->second;                            // the caller asks for it now: it counts as queued by the caller, once
+            ent->spec = false;
+            guessed = true;
+            ++S.stat_spec[1];
+        } else {
+            ent = std::make_shared<Entry>();
+            memcpy(ent->key, key.data(), sizeof(ent->key));
+            ent->owner = &S;
+            ent->t_queued = now_s();
+            S.cache.emplace(key, ent);
+        }
         ++S.stat_queued;
     }
     Threads &G = threads();
     G.ensure(S.n_threads, S.n_helpers);                  // (there since coral_search_params, unless shut down or forked since)
     {
+        // a real request goes behind the real ones and so in front of every guess; one that is still in the lane of guesses
+        // moves over (if a worker has it already, or it is done, there is nothing to move)
         std::lock_guard<std::mutex> lk(G.m);
+        if (guessed) {
+            auto at = std::find(G.spec_queue.begin(), G.spec_queue.end(), ent);
+            if (at == G.spec_queue.end()) return CORAL_OK;
+            G.spec_queue.erase(at);
+        }
         G.queue.push_back(ent);
     }
     G.cv.notify_one();
@@ -1380,7 +1590,11 @@ extern "C" int coral_search_prefetch(void *h, int64_t tid, int64_t s, int64_t e,
 
 // Counters of a handle, for tests and traces: out[0] attached, out[1] the pack fill was complete when coral_search_attach
 // began, out[2] steps queued in all, out[3] steps already queued when the last coral_search_bfs began (-1: none yet), out[4]
-// steps computed by the caller, out[5] / out[6] look-ahead and helper threads alive in the process.
+// steps computed by the caller, out[5] / out[6] look-ahead and helper threads alive in the process.  out[2] counts each distinct
+// key the CALLER asked to have queued, once, whether or not a guess had queued it first.  With n_out >= 12 also the counters of
+// CORAL_SEARCH_SPECULATE: out[7] speculative entries queued, out[8] of the keys the caller asked for those a guess had queued
+// first, out[9] of those the ones already computed when their step was asked for, out[10] speculative entries never asked for,
+// out[11] steps computed so far (by anyone).
 extern "C" int coral_search_stats(void *h, int64_t *out, int32_t n_out) {
     if (!h || !out || n_out < 7) return CORAL_ERR_ARG;
     Search &S = *(Search *)h;
@@ -1388,6 +1602,10 @@ extern "C" int coral_search_stats(void *h, int64_t *out, int32_t n_out) {
     std::lock_guard<std::mutex> lk(S.qm);
     out[0] = S.attached ? 1 : 0; out[1] = S.stat_fill_ready; out[2] = S.stat_queued; out[3] = S.stat_queued_at_bfs;
     out[4] = S.n_inline; out[5] = G ? G->n_workers.load() : 0; out[6] = G ? G->helpers.n_alive.load() : 0;
+    if (n_out >= 12) {
+        out[7] = S.stat_spec[0]; out[8] = S.stat_spec[1]; out[9] = S.stat_spec[2]; out[10] = S.stat_spec[0] - S.stat_spec[1];
+        out[11] = S.stat_done;
+    }
     return CORAL_OK;
 }
 
@@ -1397,10 +1615,16 @@ extern "C" int coral_search_step(void *h, int64_t tid, int64_t s, int64_t e, int
     if (!S.attached) return not_attached(S, "search_step");
     const std::array<int64_t, 5> key = {tid, s, e, si, ei};
     std::shared_ptr<Entry> ent;
+    bool first_ask = false;                               // of an entry a guess made
     {
         std::lock_guard<std::mutex> lk(S.qm);
         auto it = S.cache.find(key);
-        if (it != S.cache.end()) ent = it->second;
+        if (it != S.cache.end()) {
+            ent = it->second;
+            if (ent->spec) { ent->spec = false; ++S.stat_spec[1]; }           // (a step asked for without a prefetch)
+            first_ask = ent->born_spec && !ent->step_seen;
+            ent->step_seen = true;
+        }
     }
     S.current_entry.reset();
     if (ent) {
@@ -1408,6 +1632,11 @@ extern "C" int coral_search_step(void *h, int64_t tid, int64_t s, int64_t e, int
         {
             std::unique_lock<std::mutex> lk(ent->m);
             if (!ent->taken) { ent->taken = true; mine = true; }           // still queued: do it here, the worker will skip it
+            if (first_ask && ent->done) {
+                lk.unlock();
+                std::lock_guard<std::mutex> lq(S.qm);
+                ++S.stat_spec[2];
+            }
         }
         const double t_ask = now_s();
         if (mine) {
@@ -1415,9 +1644,13 @@ extern "C" int coral_search_step(void *h, int64_t tid, int64_t s, int64_t e, int
             ent->who = 0;
             compute_step(S, S.main_scratch, ent->key, ent->res);
             ent->t_end = now_s();
-            std::lock_guard<std::mutex> lk(ent->m);
-            ent->done = true;
+            {
+                std::lock_guard<std::mutex> lk(ent->m);
+                ent->done = true;
+            }
             ++S.n_inline;
+            std::lock_guard<std::mutex> lq(S.qm);
+            ++S.stat_done;
         } else {
             const double w0 = S.profile ? now_s() : 0.0;
             std::unique_lock<std::mutex> lk(ent->m);
@@ -1425,9 +1658,9 @@ extern "C" int coral_search_step(void *h, int64_t tid, int64_t s, int64_t e, int
             if (S.profile) S.t_wait += now_s() - w0;
         }
         if (S.profile_steps)
-            fprintf(stderr, "  step contig %lld [%lld, %lld]: queued %.2f ms before it was asked for, compute %.2f ms (%s), asked -> ready %.2f ms; "
+            fprintf(stderr, "  step contig %lld [%lld, %lld]: queued %s%.2f ms before it was asked for, compute %.2f ms (%s), asked -> ready %.2f ms; "
                     "%zu runs, %zu candidates, %zu reads in the runs; reach %.2f union %.2f candidates %.2f calls %.2f ms\n", (long long)key[0], (long long)key[1], (long long)key[2],
-                    (t_ask - ent->t_queued) * 1e3, (ent->t_end - ent->t_start) * 1e3, ent->who == 0 ? "caller" : "worker", (now_s() - t_ask) * 1e3,
+                    ent->born_spec ? "by a guess " : "", (t_ask - ent->t_queued) * 1e3, (ent->t_end - ent->t_start) * 1e3, ent->who == 0 ? "caller" : "worker", (now_s() - t_ask) * 1e3,
                     ent->res.groups.size() / 4, ent->res.cand.size() / 13, (size_t)ent->res.order_off.back(),ent->res.t_phase[0] * 1e3, ent->res.t_phase[1] * 1e3,
                     ent->res.t_phase[2] * 1e3, ent->res.t_phase[3] * 1e3);
         S.current_entry = ent;
@@ -1598,12 +1831,60 @@ extern "C" int coral_search_bfs(void *h, int32_t n_seed, const int64_t *iv, cons
     int rc = CORAL_OK;
     if (S.n_reads > 0)
         for (int32_t ai = 0; ai < n_seed && rc == CORAL_OK; ++ai) rc = run.enqueue(ai);
+    // exploring ahead: from here to the end of the search a worker that finishes a step guesses what follows from it; the steps
+    // that are finished already (the seeds', queued when the handle was attached) are looked at here
+    const ActiveBfs active{&P, &O};
+    const bool explore = S.speculate && S.n_threads > 0 && S.n_reads > 0 && rc == CORAL_OK;
+    if (explore) {
+        std::vector<std::shared_ptr<Entry>> ready;
+        {
+            std::lock_guard<std::mutex> lk(S.qm);
+            S.spec_in_bfs = 0;
+            for (const auto &kv : S.cache) ready.push_back(kv.second);
+        }
+        {
+            std::lock_guard<std::mutex> lk(S.spec_m);
+            S.active = &active;
+        }
+        // (in key order: the cache's own order depends on the hash of the keys, the guesses' counters should not)
+        std::sort(ready.begin(), ready.end(), [](const std::shared_ptr<Entry> &a, const std::shared_ptr<Entry> &b) {
+            return std::lexicographical_compare(a->key, a->key + 5, b->key, b->key + 5);
+        });
+        for (const auto &e : ready) {
+            bool done;
+            {
+                std::lock_guard<std::mutex> lk(e->m);
+                done = e->done;
+            }
+            if (done) shadow_pass(S, *e);                    // (one that finishes from now on: its worker does it)
+        }
+    }
     int64_t ccid = 0;
     for (int32_t ai = 0; ai < n_seed && rc == CORAL_OK; ++ai)
         if (O.iv[5 * (size_t)ai + 3] == -1) {
             rc = run.bfs_from(ai, ccid);
             ++ccid;
         }
+    if (explore) {
+        {
+            std::lock_guard<std::mutex> lk(S.spec_m);       // (a shadow pass that is reading P / O ends first)
+            S.active = nullptr;
+        }
+        // guesses nobody took: out of the queue, so that what the caller queues next (the tail jobs) never waits behind them,
+        // and out of the cache (a later request for the key starts afresh)
+        if (Threads *G = threads_if_any()) {
+            std::vector<std::shared_ptr<Entry>> dropped;
+            {
+                std::lock_guard<std::mutex> lk(G->m);
+                auto &q = G->spec_queue;
+                for (const auto &e : q) if (e->owner == &S) dropped.push_back(e);
+                q.erase(std::remove_if(q.begin(), q.end(), [&](const std::shared_ptr<Entry> &e) { return e->owner == &S; }), q.end());
+            }
+            std::lock_guard<std::mutex> lk(S.qm);
+            for (const auto &e : dropped)                  // (still in the lane: no thread has begun them, nobody asked for them)
+                if (e->spec) S.cache.erase(std::array<int64_t, 5>{e->key[0], e->key[1], e->key[2], e->key[3], e->key[4]});
+        }
+    }
     if (S.profile) fprintf(stderr, "coral_search_bfs: %.2f ms in all, %.2f ms of it inside coral_search_step (waits for steps included), %zu support triples kept\n",
                            (now_s() - t_bfs0) * 1e3, run.t_steps * 1e3, O.chunk_read.size());
     if (rc == BFS_ERR_KEY_CHROM) snprintf(S.err, sizeof(S.err), "search_bfs: KeyError contig %lld has no hashed alignments", (long long)O.err_tid);

@@ -269,6 +269,12 @@ int coral_bp_pair_table(int32_t n_reads, int32_t n_rows, const int32_t *off, con
  * coral_search_shutdown joins the threads (idempotent; a later prefetch starts them again; after fork() the child starts
  * its own).  coral_search_stats: out int64[>= 7] = attached, pack fill complete when attach began, steps queued in all, steps
  * already queued when the last coral_search_bfs began (-1: none), steps computed by the caller, look-ahead / helper threads alive.
+ * "Steps queued" counts each distinct key the CALLER asked for, once.  While coral_search_bfs runs, a look-ahead thread that
+ * finishes a step also queues, as speculative entries behind every real one, the steps of the intervals the search will
+ * probably derive from it (CORAL_SEARCH_SPECULATE=0: never; at most CORAL_SEARCH_SPECULATE_MAX per search); results never
+ * depend on it.  With n_out >= 12 also: out[7] speculative entries queued, out[8] keys the caller asked for that a guess had
+ * queued first, out[9] of those the ones computed already when their step was asked for, out[10] speculative entries never
+ * asked for, out[11] steps computed so far by any thread.
  * ------------------------------------------------------------------------------------------------ */
 void *coral_search_create_early(int64_t n_reads, int64_t n_rows, const int64_t *off, const int64_t *row_read,
                                 const int64_t *row_tid, const int64_t *ra, const int64_t *rb, const int64_t *read_name,

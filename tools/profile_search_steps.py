@@ -68,6 +68,10 @@ for i in range(8):
     nb = None
     t2 = time.perf_counter()
     os.environ.pop("CORAL_SEARCH_PROFILE", None)
+    ctx = getattr(b, "_search_ctx", None)
+    if i >= 4 and ctx is not None and getattr(ctx, "_h", None):
+        # (CORAL_SEARCH_SPECULATE: how many steps were guessed, asked for, and ready when asked for)
+        print("   search counters: " + "  ".join("%s %d" % kv for kv in ctx.stats().items()), flush=True)
     if i >= 4:
         print("   inside: " + "  ".join("%s %.1f" % (k, v * 1e3) for k, v in sorted(acc.items())) + "   | phases: " +
               " ".join("%s %.1f" % (k[:10], v * 1e3) for k, v in ph.items()), flush=True)
