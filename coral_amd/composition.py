@@ -11,13 +11,11 @@ from __future__ import annotations
 
 import ctypes as C
 import numbers
-import os
 import time
 
 import numpy as np
 
-from . import _lib
-from .kmers import _pieces
+from . import _lib, fasta_stream
 
 LAST_COMPOSITION = {}                # seconds of the last reference_composition, by stage
 MAX_BINS = 1 << 28
@@ -144,20 +142,6 @@ class Composition:
         return pick(self.gc), pick(self.at), pick(self.masked)
 
 
-def _stream_size(fasta):
-    """The bytes still to come from ``fasta`` (None: not known without reading) and a function that starts it over."""
-    if hasattr(fasta, "read"):
-        try:
-            at = fasta.tell()
-            end = fasta.seek(0, os.SEEK_END)
-            fasta.seek(at)
-            return end - at, lambda: fasta.seek(at)
-        except (OSError, AttributeError, ValueError):
-            return None, None
-    path = os.fspath(fasta)
-    return (None if path.endswith(".gz") else os.path.getsize(path)), lambda: None
-
-
 def reference_composition(fasta, bin_size: int = 1000, device="cuda:0", chunk_bytes: int = 64 << 20, _capacity=None) -> Composition:
     """Counts G/C, A/T and soft-masked positions per bin of ``bin_size`` along every contig of the FASTA ``fasta`` - a path (one
     ending in .gz is read through Python's ``gzip`` on the host) or an open binary file -> ``Composition``.
@@ -175,7 +159,7 @@ def reference_composition(fasta, bin_size: int = 1000, device="cuda:0", chunk_by
     L = _lib.lib()
     on_gpu = torch.device(device).type == "cuda"
     staging = min(int(chunk_bytes), 1 << 30)
-    size, rewind = _stream_size(fasta)
+    size, rewind = fasta_stream.stream_size(fasta)
     if size is not None:
         staging = max(16, min(staging, size))                    # (a small file needs no large pinned buffers)
     capacity = int(_capacity) if _capacity is not None else min(MAX_BINS, (size if size is not None else 1 << 30) // int(bin_size) + 4096)
@@ -185,31 +169,17 @@ def reference_composition(fasta, bin_size: int = 1000, device="cuda:0", chunk_by
         handle = C.c_void_p()
         if on_gpu:
             dev = torch.device(device)
-            torch.cuda.set_device(dev)
-            ws_bytes = int(L.coral_comp_workspace_bytes(staging))
-            if ws_bytes < 0:
-                raise _lib.CoralHipError("coral_comp_workspace_bytes failed (%d)" % ws_bytes)
             tables = torch.zeros((3, capacity), dtype=torch.int32, device=dev)
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-            stream = torch.cuda.current_stream(dev)
-            stream.synchronize()                                     # (the blocks may be recycled ones)
-            rc = L.coral_comp_open(int(bin_size), dev.index or 0, tables[0].data_ptr(), tables[1].data_ptr(), tables[2].data_ptr(), capacity, staging, ws.data_ptr(), ws_bytes,
+            ws, stream = fasta_stream.gpu_side(dev, int(L.coral_comp_workspace_bytes(staging)), "coral_comp_workspace_bytes")
+            rc = L.coral_comp_open(int(bin_size), dev.index or 0, tables[0].data_ptr(), tables[1].data_ptr(), tables[2].data_ptr(), capacity, staging, ws.data_ptr(), ws.numel(),
                                    stream.cuda_stream, C.byref(handle))
         else:
             tables = np.zeros((3, capacity), dtype=np.uint32)
             rc = L.coral_comp_open(int(bin_size), -1, tables[0].ctypes.data, tables[1].ctypes.data, tables[2].ctypes.data, capacity, 0, None, 0, None, C.byref(handle))
-        if rc != 0:
-            raise _lib.CoralHipError("coral_comp_open failed (%d): %s" % (rc, L.coral_bam_last_error().decode()))
+        fasta_stream.check(rc, "coral_comp_open")
         stats, secs = (C.c_int64 * 8)(), (C.c_double * 4)()
         try:
-            pieces, read_s = _pieces(fasta, int(chunk_bytes))
-            feed_s = 0.0
-            for piece, n in pieces:
-                t0 = time.perf_counter()
-                rc = L.coral_comp_feed(handle, piece.ctypes.data if isinstance(piece, np.ndarray) else piece, n)
-                feed_s += time.perf_counter() - t0
-                if rc != 0:
-                    raise _lib.CoralHipError("coral_comp_feed failed (%d): %s" % (rc, L.coral_bam_last_error().decode()))
+            read_s, feed_s = fasta_stream.feed_all(L.coral_comp_feed, handle, fasta, chunk_bytes)
             t0 = time.perf_counter()
             rc = L.coral_comp_finish(handle, stats, secs)
             finish_s = time.perf_counter() - t0
@@ -218,12 +188,9 @@ def reference_composition(fasta, bin_size: int = 1000, device="cuda:0", chunk_by
                 capacity = bins
                 rewind()
                 continue
-            if rc != 0:
-                raise _lib.CoralHipError("coral_comp_finish failed (%d): %s" % (rc, L.coral_bam_last_error().decode()))
+            fasta_stream.check(rc, "coral_comp_finish")
             lengths, name_off, blob = np.zeros(n_contigs, dtype=np.int64), np.zeros(n_contigs + 1, dtype=np.int64), np.zeros(max(names_bytes, 1), dtype=np.uint8)
-            rc = L.coral_comp_contigs(handle, n_contigs, lengths.ctypes.data, names_bytes, blob.ctypes.data, name_off.ctypes.data)
-            if rc != 0:
-                raise _lib.CoralHipError("coral_comp_contigs failed (%d): %s" % (rc, L.coral_bam_last_error().decode()))
+            fasta_stream.check(L.coral_comp_contigs(handle, n_contigs, lengths.ctypes.data, names_bytes, blob.ctypes.data, name_off.ctypes.data), "coral_comp_contigs")
         finally:
             L.coral_comp_close(handle)
         break
@@ -231,7 +198,7 @@ def reference_composition(fasta, bin_size: int = 1000, device="cuda:0", chunk_by
     host = tables[:, :bins].cpu().numpy().view(np.uint32) if on_gpu else tables[:, :bins]
     text = blob.tobytes()
     chroms = [text[name_off[c]:name_off[c + 1]].decode("utf-8", "surrogateescape") for c in range(n_contigs)]
-    LAST_COMPOSITION.update(read=read_s[0], feed=feed_s, finish_wait=finish_s, upload=float(secs[0]), ordinals=float(secs[1]), count=float(secs[2]),
+    LAST_COMPOSITION.update(read=read_s, feed=feed_s, finish_wait=finish_s, upload=float(secs[0]), ordinals=float(secs[1]), count=float(secs[2]),
                             download=time.perf_counter() - t0, attempts=attempt + 1, wall=time.perf_counter() - t_all)
     out = Composition(chroms, lengths.tolist(), bin_size, host[0], host[1], host[2])
     out.totals = dict(contigs=n_contigs, positions=positions, bins=bins, gc=int(stats[3]), at=int(stats[4]), masked=int(stats[5]))

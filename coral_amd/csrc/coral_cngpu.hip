@@ -34,6 +34,7 @@
 
 #include "../../include/coral_hip.h"
 #include "coral_cn_host.h"
+#include "coral_stream_gpu.h"
 
 namespace coral_bam { void set_error(const std::string &msg); }      // coral_bam_last_error() of the calling thread (coral_bam.cpp)
 
@@ -312,13 +313,8 @@ __global__ __launch_bounds__(CN_BLOCK) void k_cn_segments(CnTable T, const int32
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------
-inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-struct Carver {                      // hands the workspace out in 256-byte steps (p == 0: only the size is counted)
-    uintptr_t p;
-    size_t used = 0;
-    template <class T> T *take(size_t n) { used += up256(n * sizeof(T)); return (T *)(p + used - up256(n * sizeof(T))); }
-};
+using coral_stream::Carver;          // hands the workspace out in 256-byte steps
+using coral_stream::up256;
 
 // hipcub's temporary storage for the largest of the calls below
 size_t cub_tmp_bytes(long long n_bins, int32_t n_contigs) {

@@ -1,6 +1,6 @@
 // coral_comp.hip - the device backend of `composition`: the kernels behind coral_comp_open .. coral_comp_close (include/coral_hip.h)
 // for a device session.  The rule is coral_comp_core.h's, the same functions the host backend (coral_comp_host.h) loops over.  The
-// three tables and the workspace are the caller's; the session owns two pinned staging buffers, a copy stream and its events.  It
+// three tables and the workspace are the caller's; the staging of the pieces is coral_stream_gpu.h's PieceStager.  It
 // stands in for the GC and repeat-mask columns of the reference table of the reference's scripts/call_cnvs.sh:12-17.
 //
 // Per fed piece of at most `staging` bytes and at most MAX_BOUND header lines (a piece with more is fed as several), stream-ordered,
@@ -14,7 +14,7 @@
 //   k_comp_count    each thread takes COUNT_SPT consecutive bytes in aligned 16-byte loads, finds its stretch by a search in the
 //                   headers' offsets, sums runs of equal bin and leaves its last bin to the wave: lanes with the same bin are
 //                   neighbours (positions ascend), the run's first lane issues one no-return atomicAdd per table
-// The closed contigs' lengths come down behind k_comp_walk and are read when the staging buffer is next used.
+// The closed contigs' lengths come down behind k_comp_walk, into the piece's pinned buffer, and are read when it is next used.
 // Plain C++ atomics and vector stores only.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
@@ -25,10 +25,12 @@
 
 #include "../../include/coral_hip.h"
 #include "coral_comp_gpu.h"
+#include "coral_stream_gpu.h"
 
 namespace {
 
 using namespace coral_comp;
+using namespace coral_stream;
 
 constexpr int WAVE = 64;
 constexpr int COUNT_SPT = 64;                    // bytes per thread of k_comp_count: four 16-byte loads
@@ -57,11 +59,6 @@ struct Segs {                                    // a piece's stretches: stretch
     uint32_t start[MAX_BOUND + 1], ord[MAX_BOUND + 1];      // first byte; the ordinal of that byte
     unsigned long long bin[MAX_BOUND + 1];       // the first bin of the stretch's contig
 };
-
-struct KeepOp {
-    __host__ __device__ uint32_t operator()(const uint8_t &c) const { return is_position(c); }
-};
-using KeepIter = hipcub::TransformInputIterator<uint32_t, KeepOp, const uint8_t *>;
 
 __global__ __launch_bounds__(WALK_BLOCK) void k_comp_walk(const PieceHead *__restrict__ H, const uint8_t *__restrict__ raw, const uint32_t *__restrict__ pos,
                                                            unsigned long long bin_size, Carry *__restrict__ C, Segs *__restrict__ S, unsigned long long *__restrict__ closed) {
@@ -196,20 +193,6 @@ __global__ __launch_bounds__(COUNT_BLOCK) void k_comp_count(const uint8_t *__res
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------
-inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-struct Carver {                      // hands the workspace out in 256-byte steps (p == 0: only the size is counted)
-    uintptr_t p;
-    size_t used = 0;
-    template <class T> T *take(size_t n) { used += up256(n * sizeof(T)); return (T *)(p + used - up256(n * sizeof(T))); }
-};
-
-size_t cub_tmp_bytes(int64_t staging) {
-    size_t b = 0;
-    if (hipcub::DeviceScan::ExclusiveSum(nullptr, b, KeepIter(nullptr, KeepOp()), (uint32_t *)nullptr, (int)staging) != hipSuccess) b = 0;
-    return b + 256;
-}
-
 struct Workspace {
     uint8_t *raw[2];                 // PieceHead (HEAD_BYTES), then the piece
     uint32_t *pos;
@@ -236,8 +219,6 @@ struct Workspace {
 
 namespace coral_comp_gpu {
 
-enum { EV_UP0, EV_UP1, EV_K0, EV_K1, EV_DONE, N_EV };
-
 struct Device {
     int device = 0;
     bool finished = false, started = false;
@@ -245,26 +226,21 @@ struct Device {
     uint64_t bin_size = 0, capacity = 0;
     uint32_t *gc = nullptr, *at = nullptr, *masked = nullptr;
     int64_t staging = 0;
-    hipStream_t stream = nullptr, copy = nullptr;
     Workspace W{nullptr, 16, 0};
-    uint8_t *pinned[2] = {nullptr, nullptr};
-    unsigned long long *closed_host[2] = {nullptr, nullptr};
+    PieceStager st;                  // a pinned buffer: PieceHead (HEAD_BYTES), the piece, and from closed_at on the lengths that come down
+    size_t closed_at = 0;
     uint32_t n_closed[2] = {0, 0};
     bool open_before[2] = {false, false};
-    hipEvent_t ev[2][N_EV] = {};
-    bool used[2] = {false, false};
-    int next = 0;
     LineState line;
     Names names;
     std::vector<int64_t> lengths;
     std::vector<uint32_t> bounds;
     std::vector<std::pair<uint32_t, uint32_t>> blanks;
-    double seconds[4] = {0, 0, 0, 0};
 };
 
 int64_t workspace_bytes(int64_t staging_bytes) {
     if (staging_bytes < MIN_STAGING || staging_bytes > MAX_STAGING) return CORAL_ERR_ARG;
-    const Workspace W(nullptr, staging_bytes, cub_tmp_bytes(staging_bytes));
+    const Workspace W(nullptr, staging_bytes, keep_scan_tmp_bytes(staging_bytes) + 256);
     return (int64_t)W.bytes + 256;
 }
 
@@ -273,23 +249,10 @@ void geometry(int32_t *out) {
     for (int i = 0; i < 8; ++i) out[i] = g[i];
 }
 
-static bool hip_ok(hipError_t e, const char *what, std::string &err) {
-    if (e == hipSuccess) return true;
-    if (err.empty()) err = std::string(what) + ": " + hipGetErrorString(e);
-    return false;
-}
-
 void close(Device *d) {
     if (!d) return;
     (void)hipSetDevice(d->device);
-    if (d->copy) (void)hipStreamSynchronize(d->copy);
-    (void)hipStreamSynchronize(d->stream);
-    for (int b = 0; b < 2; ++b) {
-        for (hipEvent_t e : d->ev[b]) if (e) (void)hipEventDestroy(e);
-        if (d->pinned[b]) (void)hipHostFree(d->pinned[b]);
-        if (d->closed_host[b]) (void)hipHostFree(d->closed_host[b]);
-    }
-    if (d->copy) (void)hipStreamDestroy(d->copy);
+    d->st.close();
     delete d;
 }
 
@@ -300,52 +263,37 @@ int open(int64_t bin_size, int device, uint32_t *gc, uint32_t *at, uint32_t *mas
         return CORAL_ERR_ARG;
     }
     if (!hip_ok(hipSetDevice(device), "hipSetDevice", err)) return CORAL_ERR_HIP;
-    const size_t cub_bytes = cub_tmp_bytes(staging_bytes);
+    const size_t cub_bytes = keep_scan_tmp_bytes(staging_bytes) + 256;
     const Workspace sized(nullptr, staging_bytes, cub_bytes);
     if (!workspace || ws_bytes < (int64_t)sized.bytes + 256) { err = "the workspace is smaller than coral_comp_workspace_bytes"; return CORAL_ERR_ARG; }
     Device *d = new Device();
     d->device = device; d->bin_size = (uint64_t)bin_size; d->capacity = (uint64_t)capacity; d->gc = gc; d->at = at; d->masked = masked; d->staging = staging_bytes;
-    d->stream = (hipStream_t)stream;
     d->W = Workspace((void *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255), staging_bytes, cub_bytes);
-    bool good = hip_ok(hipStreamCreateWithFlags(&d->copy, hipStreamNonBlocking), "hipStreamCreateWithFlags", err);
-    for (int b = 0; b < 2 && good; ++b) {
-        good = hip_ok(hipHostMalloc((void **)&d->pinned[b], HEAD_BYTES + (size_t)staging_bytes, hipHostMallocDefault), "hipHostMalloc", err) &&
-               hip_ok(hipHostMalloc((void **)&d->closed_host[b], (size_t)MAX_BOUND * 8, hipHostMallocDefault), "hipHostMalloc", err);
-        for (int e = 0; e < N_EV && good; ++e) good = hip_ok(hipEventCreate(&d->ev[b][e]), "hipEventCreate", err);
-    }
-    good = good && hip_ok(hipMemsetAsync(d->W.carry, 0, sizeof(Carry), d->stream), "hipMemsetAsync", err) &&
-           hip_ok(hipStreamSynchronize(d->stream), "hipStreamSynchronize", err);      // (the copy stream writes into the workspace: nothing earlier may still use it)
+    d->closed_at = up256(HEAD_BYTES + (size_t)staging_bytes);
+    d->st.retired = [d](int b) {                         // a piece that is through leaves the lengths of the contigs it closed
+        const unsigned long long *closed = (const unsigned long long *)(d->st.pinned[b] + d->closed_at);
+        for (uint32_t j = d->open_before[b] ? 0 : 1; j < d->n_closed[b]; ++j) d->lengths.push_back((int64_t)closed[j]);
+        d->n_closed[b] = 0;
+    };
+    const bool good = hip_ok(hipMemsetAsync(d->W.carry, 0, sizeof(Carry), (hipStream_t)stream), "hipMemsetAsync", err) &&
+                      d->st.open((hipStream_t)stream, d->closed_at + (size_t)MAX_BOUND * 8, err);
     if (!good) { close(d); return CORAL_ERR_HIP; }
     *out = d;
     return CORAL_OK;
 }
 
-// the staging buffer's earlier piece is through: its stage times and the lengths of the contigs it closed are read
-static bool retire(Device *d, int b, std::string &err) {
-    if (!d->used[b]) return true;
-    if (!hip_ok(hipEventSynchronize(d->ev[b][EV_DONE]), "hipEventSynchronize", err)) return false;
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, d->ev[b][EV_UP0], d->ev[b][EV_UP1]) == hipSuccess) d->seconds[0] += ms * 1e-3;
-    if (hipEventElapsedTime(&ms, d->ev[b][EV_K0], d->ev[b][EV_K1]) == hipSuccess) d->seconds[1] += ms * 1e-3;
-    if (hipEventElapsedTime(&ms, d->ev[b][EV_K1], d->ev[b][EV_DONE]) == hipSuccess) d->seconds[2] += ms * 1e-3;
-    for (uint32_t j = d->open_before[b] ? 0 : 1; j < d->n_closed[b]; ++j) d->lengths.push_back((int64_t)d->closed_host[b][j]);
-    d->used[b] = false;
-    d->n_closed[b] = 0;
-    return true;
-}
-
 // the next piece: at most `n` bytes of it; *taken = how many it was
 static int feed_piece(Device *d, const uint8_t *bytes, uint32_t n, uint32_t *taken, std::string &err) {
-    const int b = d->next;
-    d->next ^= 1;
-    if (!retire(d, b, err)) return CORAL_ERR_HIP;
+    PieceStager &st = d->st;
+    const int b = st.acquire(err);
+    if (b < 0) return CORAL_ERR_HIP;
     const bool open_before = d->started;
     int fe = COMP_OK;
     const uint32_t m = (uint32_t)scan_piece(d->line, d->names, d->started, bytes, n, MAX_BOUND, d->bounds, d->blanks, &fe);
     if (fe != COMP_OK) { d->format_error = fe; err = format_text(fe); return CORAL_ERR_FORMAT; }
     *taken = m;
-    PieceHead *head = (PieceHead *)d->pinned[b];
-    uint8_t *text = d->pinned[b] + HEAD_BYTES;
+    PieceHead *head = (PieceHead *)st.pinned[b];
+    uint8_t *text = st.pinned[b] + HEAD_BYTES;
     const uint32_t nb = (uint32_t)d->bounds.size();
     head->n_bytes = m; head->n_bounds = nb; head->open_before = open_before; head->pad = 0;
     if (nb) memcpy(head->bounds, d->bounds.data(), (size_t)nb * 4);
@@ -354,34 +302,27 @@ static int feed_piece(Device *d, const uint8_t *bytes, uint32_t n, uint32_t *tak
     const Workspace &W = d->W;
     const PieceHead *dev_head = (const PieceHead *)W.raw[b];
     const uint8_t *dev_text = W.raw[b] + HEAD_BYTES;
-    hipEvent_t *ev = d->ev[b];
-    bool good = hip_ok(hipEventRecord(ev[EV_UP0], d->copy), "hipEventRecord", err) &&
-                hip_ok(hipMemcpyAsync(W.raw[b], d->pinned[b], HEAD_BYTES + m, hipMemcpyHostToDevice, d->copy), "hipMemcpyAsync", err) &&
-                hip_ok(hipEventRecord(ev[EV_UP1], d->copy), "hipEventRecord", err) && hip_ok(hipStreamWaitEvent(d->stream, ev[EV_UP1], 0), "hipStreamWaitEvent", err) &&
-                hip_ok(hipEventRecord(ev[EV_K0], d->stream), "hipEventRecord", err);
+    bool good = st.upload(b, W.raw[b], HEAD_BYTES + m, err);
     if (good) {
-        d->used[b] = true;                               // (from here on the buffer is the device's until EV_DONE)
         size_t tb = W.tmp_bytes;
-        good = hip_ok(hipcub::DeviceScan::ExclusiveSum(W.tmp, tb, KeepIter(dev_text, KeepOp()), W.pos, (int)m, d->stream), "scan of the position flags", err);
+        good = hip_ok(keep_scan(W.tmp, tb, dev_text, W.pos, m, st.stream), "scan of the position flags", err);
     }
     if (good) {
-        hipLaunchKernelGGL(k_comp_walk, dim3(1), dim3(WALK_BLOCK), 0, d->stream, dev_head, dev_text, W.pos, (unsigned long long)d->bin_size, W.carry, W.segs, W.closed);
+        hipLaunchKernelGGL(k_comp_walk, dim3(1), dim3(WALK_BLOCK), 0, st.stream, dev_head, dev_text, W.pos, (unsigned long long)d->bin_size, W.carry, W.segs, W.closed);
         good = hip_ok(hipGetLastError(), "k_comp_walk", err);
         if (good && nb) {
-            good = hip_ok(hipMemcpyAsync(d->closed_host[b], W.closed, (size_t)nb * 8, hipMemcpyDeviceToHost, d->stream), "hipMemcpyAsync", err);
+            good = hip_ok(hipMemcpyAsync(st.pinned[b] + d->closed_at, W.closed, (size_t)nb * 8, hipMemcpyDeviceToHost, st.stream), "hipMemcpyAsync", err);
             if (good) { d->n_closed[b] = nb; d->open_before[b] = open_before; }
         }
-        good = good && hip_ok(hipEventRecord(ev[EV_K1], d->stream), "hipEventRecord", err);
+        good = good && st.mark_k1(b, err);
     }
     if (good) {
         const unsigned blocks = (unsigned)(((long long)m + COUNT_TILE - 1) / COUNT_TILE);
-        hipLaunchKernelGGL(k_comp_count, dim3(blocks), dim3(COUNT_BLOCK), 0, d->stream, dev_text, W.pos, W.segs, (unsigned long long)d->bin_size, (unsigned long long)d->capacity, d->gc,
+        hipLaunchKernelGGL(k_comp_count, dim3(blocks), dim3(COUNT_BLOCK), 0, st.stream, dev_text, W.pos, W.segs, (unsigned long long)d->bin_size, (unsigned long long)d->capacity, d->gc,
                            d->at, d->masked, W.carry);
         good = hip_ok(hipGetLastError(), "k_comp_count", err);
     }
-    // the event goes in whatever happened, so that the buffer's next use (or close) has something to wait for
-    if (d->used[b]) good = hip_ok(hipEventRecord(ev[EV_DONE], d->stream), "hipEventRecord", err) && good;
-    return good ? CORAL_OK : CORAL_ERR_HIP;
+    return st.done(b, good, err) ? CORAL_OK : CORAL_ERR_HIP;
 }
 
 int feed(Device *d, const uint8_t *bytes, int64_t n, std::string &err) {
@@ -402,9 +343,9 @@ int finish(Device *d, coral_comp::Stats &st, std::vector<int64_t> &lengths, cora
     if (d->format_error != COMP_OK) { err = format_text(d->format_error); return CORAL_ERR_FORMAT; }
     if (!hip_ok(hipSetDevice(d->device), "hipSetDevice", err)) return CORAL_ERR_HIP;
     d->finished = true;
-    if (!retire(d, d->next, err) || !retire(d, d->next ^ 1, err)) return CORAL_ERR_HIP;          // (the older piece first: its contigs come first)
+    if (!d->st.drain(err)) return CORAL_ERR_HIP;          // (the older piece first: its contigs come first)
     Carry c{};
-    if (!hip_ok(hipMemcpyAsync(&c, d->W.carry, sizeof(c), hipMemcpyDeviceToHost, d->stream), "hipMemcpyAsync", err) || !hip_ok(hipStreamSynchronize(d->stream), "hipStreamSynchronize", err))
+    if (!hip_ok(hipMemcpyAsync(&c, d->W.carry, sizeof(c), hipMemcpyDeviceToHost, d->st.stream), "hipMemcpyAsync", err) || !hip_ok(hipStreamSynchronize(d->st.stream), "hipStreamSynchronize", err))
         return CORAL_ERR_HIP;
     if (d->names.in_line && !d->names.close_line()) { d->format_error = COMP_FORMAT_EMPTY_NAME; err = format_text(d->format_error); return CORAL_ERR_FORMAT; }
     st = coral_comp::Stats();
@@ -414,7 +355,7 @@ int finish(Device *d, coral_comp::Stats &st, std::vector<int64_t> &lengths, cora
     st.positions = c.positions; st.gc = c.gc; st.at = c.at; st.masked = c.masked;
     lengths = d->lengths;
     names = d->names;
-    if (seconds) for (int i = 0; i < 4; ++i) seconds[i] = d->seconds[i];
+    if (seconds) for (int i = 0; i < 4; ++i) seconds[i] = d->st.seconds[i];
     return CORAL_OK;
 }
 

@@ -3,8 +3,7 @@
 // It stands in for the GC and repeat-mask columns of the reference table that the reference's scripts/call_cnvs.sh:12-17 hands to
 // `cnvkit.py batch --reference hg38full_ref_5k.cnn`; DESIGN.md §4 states the rule in words.
 //
-//   - lines are coral_kmer_core.h's: a line starts at the stream's first byte and behind every '\n'; a line whose first byte is
-//     '>' is a header line and starts a contig; '\n' and '\r' are skipped wherever they stand.
+//   - lines are coral_fasta_core.h's; a header line starts a contig; '\n' and '\r' are skipped wherever they stand.
 //   - every other byte of a line that is no header is one position of the current contig (`samtools faidx` coordinates: N,
 //     IUPAC codes, '*' and '-' are positions too).
 //   - a position is gc (GCgc), at (ATat) or neither (uncalled), and masked when its byte is a..z.
@@ -16,22 +15,22 @@
 
 #include <stdint.h>
 
-#include "coral_kmer_core.h"
+#include "coral_fasta_core.h"
 
 namespace coral_comp {
 
-using coral_kmer::LineState;
+using namespace coral_fasta;
 
 constexpr int64_t MAX_BIN_SIZE = 0x7fffffff;
 constexpr int64_t MAX_BINS = (int64_t)1 << 28;
 constexpr uint32_t CLS_GC = 1, CLS_AT = 2, CLS_MASKED = 4;
 enum Kind : uint8_t { KIND_OPEN, KIND_HEADER, KIND_SKIP, KIND_POSITION };      // a header's '>', the rest of its line, '\n' / '\r', a position
 
-CORAL_KMER_HD bool bin_size_ok(int64_t bin_size) { return bin_size >= 1 && bin_size <= MAX_BIN_SIZE; }
-CORAL_KMER_HD bool is_position(uint8_t c) { return c != '\n' && c != '\r'; }      // of a byte outside a header line
+CORAL_FASTA_HD bool bin_size_ok(int64_t bin_size) { return bin_size >= 1 && bin_size <= MAX_BIN_SIZE; }
+CORAL_FASTA_HD bool is_position(uint8_t c) { return kept(c); }                    // of a byte outside a header line
 
 // the classes of a position's byte
-CORAL_KMER_HD uint32_t classes(uint8_t c) {
+CORAL_FASTA_HD uint32_t classes(uint8_t c) {
     const uint32_t masked = c >= 'a' && c <= 'z' ? CLS_MASKED : 0;
     switch (c | 0x20) {                                // (only a letter's two cases map onto it)
         case 'g': case 'c': return CLS_GC | masked;
@@ -40,20 +39,16 @@ CORAL_KMER_HD uint32_t classes(uint8_t c) {
     }
 }
 
-// the next byte of the stream -> what it is (coral_kmer_core.h's next_symbol decides the lines)
-CORAL_KMER_HD Kind next_kind(LineState &s, uint8_t c) {
-    const bool inside = s.in_header != 0;
-    bool header;
-    const uint8_t sym = coral_kmer::next_symbol(s, c, &header);
-    if (header) return KIND_OPEN;
-    if (inside) return KIND_HEADER;
-    return sym == coral_kmer::SYM_SKIP ? KIND_SKIP : KIND_POSITION;
+// the next byte of the stream -> what it is
+CORAL_FASTA_HD Kind next_kind(LineState &s, uint8_t c) {
+    const Line l = line_step(s, c);
+    return l == LINE_OPEN ? KIND_OPEN : l == LINE_HEADER ? KIND_HEADER : is_position(c) ? KIND_POSITION : KIND_SKIP;
 }
 
-CORAL_KMER_HD uint64_t bins_of(uint64_t length, uint64_t bin_size) { return (length + bin_size - 1) / bin_size; }
+CORAL_FASTA_HD uint64_t bins_of(uint64_t length, uint64_t bin_size) { return (length + bin_size - 1) / bin_size; }
 
 // a byte that ends a contig's name inside its header line
-CORAL_KMER_HD bool ends_name(uint8_t c) { return c == ' ' || c == '\t' || c == '\r' || c == '\n'; }
+CORAL_FASTA_HD bool ends_name(uint8_t c) { return c == ' ' || c == '\t' || c == '\r' || c == '\n'; }
 
 }  // namespace coral_comp
 #endif /* CORAL_COMP_CORE_H */

@@ -1,7 +1,7 @@
 // coral_comp_host.h - the host backend of the reference's per-bin composition: a straight loop over coral_comp_core.h with a small
 // state carried between feeds, and the same tables as the device.  It is what the kernels (coral_comp.hip) are compared against
-// and `device="cpu"` of coral_amd/composition.py.  scan_piece is the host's share of the device path: it finds the header lines
-// of a piece and takes the contigs' names from them.  It stands in for the GC and repeat-mask columns of the reference table of
+// and `device="cpu"` of coral_amd/composition.py.  scan_piece is the host's share of the device path: it takes the contigs'
+// names from the header lines of a piece, which coral_fasta_host.h finds, and says what to blank.  It stands in for the GC and repeat-mask columns of the reference table of
 // the reference's scripts/call_cnvs.sh:12-17.  No HIP: g++ alone builds it (tests/native/comp_host.cpp).
 #ifndef CORAL_COMP_HOST_H
 #define CORAL_COMP_HOST_H
@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "coral_comp_core.h"
+#include "coral_fasta_host.h"
 
 namespace coral_comp {
 
@@ -114,7 +115,7 @@ struct HostComposer {
     }
 };
 
-// The header lines of the next piece of the stream, found with memchr before the piece is copied: `bounds` gets the byte offset of
+// The header lines of the next piece of the stream, found before the piece is copied: `bounds` gets the byte offset of
 // every header line that opens in the piece (its '>'), `blanks` the ranges [a, b) of header bytes ('>' included, the line's '\n'
 // not) for the caller to overwrite with '\n', `names` the contigs' names.  At most max_bounds headers are taken: the piece ends in
 // front of the next one.  `s` and `started` (a header line has been seen) are the state in front of the piece and become the
@@ -124,44 +125,22 @@ inline size_t scan_piece(LineState &s, Names &names, bool &started, const uint8_
     bounds.clear();
     blanks.clear();
     *error = COMP_OK;
-    if (n == 0) return 0;
+    if (!started) {                                      // only '\n' and '\r' may stand in front of the first header line (none is open yet)
+        size_t i = 0;
+        while (i < n && !is_position(src[i])) ++i;
+        if (i < n && (src[i] != '>' || !(i == 0 ? s.line_start != 0 : src[i - 1] == '\n'))) { *error = COMP_FORMAT_BEFORE_HEADER; return n; }
+    }
     size_t pos = 0;
-    if (s.in_header) {
-        const uint8_t *q = (const uint8_t *)memchr(src, '\n', n);
-        const size_t end = q ? (size_t)(q - src) : n;
-        if (!names.bytes(src, end)) { *error = COMP_FORMAT_EMPTY_NAME; return n; }
-        if (end) blanks.emplace_back(0u, (uint32_t)end);
-        if (!q) return n;
-        if (!names.close_line()) { *error = COMP_FORMAT_EMPTY_NAME; return n; }
-        pos = end + 1;
-        s.in_header = 0;
-        s.line_start = 1;
+    for (HeaderLine h; next_header_line(s, src, n, pos, h);) {
+        if (!h.carried) {
+            if (bounds.size() == max_bounds) { s.in_header = 0; s.line_start = 1; return h.begin; }      // the piece ends in front of this line
+            bounds.push_back((uint32_t)h.begin);
+            started = true;
+            names.open();
+        }
+        if (h.end > h.begin) blanks.emplace_back((uint32_t)h.begin, (uint32_t)h.end);
+        if (!names.bytes(src + h.body, h.end - h.body) || (h.closed && !names.close_line())) { *error = COMP_FORMAT_EMPTY_NAME; return n; }
     }
-    if (!started) {                                      // only '\n' and '\r' may stand in front of the first header line
-        while (pos < n && !is_position(src[pos])) ++pos;
-        if (pos == n) { s.line_start = src[n - 1] == '\n'; return n; }
-        const bool first = pos == 0 ? s.line_start != 0 : src[pos - 1] == '\n';
-        if (src[pos] != '>' || !first) { *error = COMP_FORMAT_BEFORE_HEADER; return n; }
-    }
-    while (pos < n) {
-        const uint8_t *p = (const uint8_t *)memchr(src + pos, '>', n - pos);
-        if (!p) break;
-        const size_t i = (size_t)(p - src);
-        const bool first = i == 0 ? s.line_start != 0 : src[i - 1] == '\n';
-        if (!first) { pos = i + 1; continue; }
-        if (bounds.size() == max_bounds) { s.line_start = 1; return i; }
-        bounds.push_back((uint32_t)i);
-        started = true;
-        names.open();
-        const uint8_t *q = (const uint8_t *)memchr(src + i + 1, '\n', n - i - 1);
-        const size_t end = q ? (size_t)(q - src) : n;
-        blanks.emplace_back((uint32_t)i, (uint32_t)end);
-        if (!names.bytes(src + i + 1, end - i - 1)) { *error = COMP_FORMAT_EMPTY_NAME; return n; }
-        if (!q) { s.in_header = 1; s.line_start = 0; return n; }
-        if (!names.close_line()) { *error = COMP_FORMAT_EMPTY_NAME; return n; }
-        pos = end + 1;
-    }
-    s.line_start = src[n - 1] == '\n';
     return n;
 }
 

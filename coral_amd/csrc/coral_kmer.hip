@@ -1,6 +1,6 @@
 // coral_kmer.hip - the device backend of `kmers`: the kernels behind coral_kmer_open .. coral_kmer_close (include/coral_hip.h) for a
 // device session.  The rule is coral_kmer_core.h's, the same functions the host backend (coral_kmer_host.h) loops over.  The table
-// (4^k uint32) and the workspace are the caller's; the session owns two pinned staging buffers, a copy stream and its events.
+// (4^k uint32) and the workspace are the caller's; the staging of the pieces is coral_stream_gpu.h's PieceStager.
 //
 // Per fed piece of at most `staging` bytes, stream-ordered, no host wait but the one for the staging buffer's earlier use:
 //   host            copy into a pinned buffer; mask_headers turns every header line's body into '\n' (the '>' stays: one break)
@@ -26,10 +26,12 @@
 
 #include "../../include/coral_hip.h"
 #include "coral_kmer_gpu.h"
+#include "coral_stream_gpu.h"
 
 namespace {
 
 using namespace coral_kmer;
+using namespace coral_stream;
 
 constexpr int PRE = 16;                          // symbols carried in front of a piece's (>= MAX_K - 1, and keeps the runs 16-byte aligned)
 constexpr int COUNT_SPT = 32;                    // symbols per thread of k_kmer_count
@@ -48,11 +50,6 @@ struct Scalars {                                 // what stays in device memory 
     unsigned long long n_bases, total, distinct;
     uint32_t m, pad;                             // kept symbols of the current piece
 };
-
-struct KeepOp {
-    __host__ __device__ uint32_t operator()(const uint8_t &c) const { return classify(c) != SYM_SKIP; }
-};
-using KeepIter = hipcub::TransformInputIterator<uint32_t, KeepOp, const uint8_t *>;
 
 // four bytes a thread: symbols to dense[pos]; the thread of the last byte leaves the number of kept symbols
 __global__ __launch_bounds__(SCATTER_BLOCK) void k_kmer_scatter(const uint8_t *__restrict__ raw, const uint32_t *__restrict__ pos, uint32_t n, uint8_t *__restrict__ dense,
@@ -222,19 +219,10 @@ __global__ void k_kmer_lookup(const uint32_t *__restrict__ table, unsigned long 
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------
-inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-struct Carver {                      // hands the workspace out in 256-byte steps (p == 0: only the size is counted)
-    uintptr_t p;
-    size_t used = 0;
-    template <class T> T *take(size_t n) { used += up256(n * sizeof(T)); return (T *)(p + used - up256(n * sizeof(T))); }
-};
-
 long long table_tiles(int k) { return (long long)((table_entries(k) + TABLE_TILE - 1) / TABLE_TILE); }
 
 size_t cub_tmp_bytes(int k, int64_t staging) {
-    size_t need = 0, b = 0;
-    if (hipcub::DeviceScan::ExclusiveSum(nullptr, b, KeepIter(nullptr, KeepOp()), (uint32_t *)nullptr, (int)staging) == hipSuccess) need = std::max(need, b);
+    size_t need = keep_scan_tmp_bytes(staging), b = 0;
     if (hipcub::DeviceScan::ExclusiveSum(nullptr, b, (unsigned long long *)nullptr, (unsigned long long *)nullptr, (int)(table_tiles(k) + 1)) == hipSuccess) need = std::max(need, b);
     return need + 256;
 }
@@ -269,23 +257,16 @@ unsigned grid_of(long long items, int per_block) { return (unsigned)std::max<lon
 
 namespace coral_kmer_gpu {
 
-enum { EV_UP0, EV_UP1, EV_K0, EV_K1, EV_DONE, N_EV };
-
 struct Device {
     int k = 0, device = 0;
     bool canonical = true, finished = false;
     uint32_t *table = nullptr;
     int64_t staging = 0;
     uint64_t bases_before = 0;
-    hipStream_t stream = nullptr, copy = nullptr;
     Workspace W{nullptr, 1, 16, 0};
-    uint8_t *pinned[2] = {nullptr, nullptr};
-    hipEvent_t ev[2][N_EV] = {};
-    bool used[2] = {false, false};
-    int next = 0;
+    PieceStager st;
     LineState line;
     uint64_t n_sequences = 0;
-    double seconds[4] = {0, 0, 0, 0};
 };
 
 int64_t workspace_bytes(int k, int64_t staging_bytes) {
@@ -299,21 +280,10 @@ void geometry(int32_t *out) {
     for (int i = 0; i < 8; ++i) out[i] = g[i];
 }
 
-static bool hip_ok(hipError_t e, const char *what, std::string &err) {
-    if (e == hipSuccess) return true;
-    if (err.empty()) err = std::string(what) + ": " + hipGetErrorString(e);
-    return false;
-}
-
 void close(Device *d) {
     if (!d) return;
     (void)hipSetDevice(d->device);
-    if (d->stream || d->copy) { if (d->copy) (void)hipStreamSynchronize(d->copy); (void)hipStreamSynchronize(d->stream); }
-    for (int b = 0; b < 2; ++b) {
-        for (hipEvent_t e : d->ev[b]) if (e) (void)hipEventDestroy(e);
-        if (d->pinned[b]) (void)hipHostFree(d->pinned[b]);
-    }
-    if (d->copy) (void)hipStreamDestroy(d->copy);
+    d->st.close();
     delete d;
 }
 
@@ -326,63 +296,38 @@ int open(int k, bool canonical, int device, uint32_t *table, int64_t staging_byt
     if (!workspace || ws_bytes < (int64_t)sized.bytes + 256) { err = "the workspace is smaller than coral_kmer_workspace_bytes"; return CORAL_ERR_ARG; }
     Device *d = new Device();
     d->k = k; d->device = device; d->canonical = canonical; d->table = table; d->staging = staging_bytes; d->bases_before = bases_before;
-    d->stream = (hipStream_t)stream;
     d->W = Workspace((void *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255), k, staging_bytes, cub_bytes);
-    bool good = hip_ok(hipStreamCreateWithFlags(&d->copy, hipStreamNonBlocking), "hipStreamCreateWithFlags", err);
-    for (int b = 0; b < 2 && good; ++b) {
-        good = hip_ok(hipHostMalloc((void **)&d->pinned[b], (size_t)staging_bytes, hipHostMallocDefault), "hipHostMalloc", err);
-        for (int e = 0; e < N_EV && good; ++e) good = hip_ok(hipEventCreate(&d->ev[b][e]), "hipEventCreate", err);
-    }
-    good = good && hip_ok(hipMemsetAsync(d->W.dense, SYM_BREAK, PRE, d->stream), "hipMemsetAsync", err) &&
-           hip_ok(hipMemsetAsync(d->W.scal, 0, sizeof(Scalars), d->stream), "hipMemsetAsync", err) &&
-           hip_ok(hipStreamSynchronize(d->stream), "hipStreamSynchronize", err);      // (the copy stream writes into the workspace: nothing earlier may still use it)
+    const hipStream_t s = (hipStream_t)stream;
+    const bool good = hip_ok(hipMemsetAsync(d->W.dense, SYM_BREAK, PRE, s), "hipMemsetAsync", err) && hip_ok(hipMemsetAsync(d->W.scal, 0, sizeof(Scalars), s), "hipMemsetAsync", err) &&
+                      d->st.open(s, (size_t)staging_bytes, err);
     if (!good) { close(d); return CORAL_ERR_HIP; }
     *out = d;
     return CORAL_OK;
 }
 
-// the staging buffer's earlier piece is through: its stage times are read
-static bool retire(Device *d, int b, std::string &err) {
-    if (!d->used[b]) return true;
-    if (!hip_ok(hipEventSynchronize(d->ev[b][EV_DONE]), "hipEventSynchronize", err)) return false;
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, d->ev[b][EV_UP0], d->ev[b][EV_UP1]) == hipSuccess) d->seconds[0] += ms * 1e-3;
-    if (hipEventElapsedTime(&ms, d->ev[b][EV_K0], d->ev[b][EV_K1]) == hipSuccess) d->seconds[1] += ms * 1e-3;
-    if (hipEventElapsedTime(&ms, d->ev[b][EV_K1], d->ev[b][EV_DONE]) == hipSuccess) d->seconds[2] += ms * 1e-3;
-    d->used[b] = false;
-    return true;
-}
-
 static int feed_piece(Device *d, const uint8_t *bytes, uint32_t n, std::string &err) {
-    const int b = d->next;
-    d->next ^= 1;
-    if (!retire(d, b, err)) return CORAL_ERR_HIP;
-    memcpy(d->pinned[b], bytes, n);
-    d->n_sequences += mask_headers(d->line, d->pinned[b], n);
+    PieceStager &st = d->st;
+    const int b = st.acquire(err);
+    if (b < 0) return CORAL_ERR_HIP;
+    memcpy(st.pinned[b], bytes, n);
+    d->n_sequences += mask_headers(d->line, st.pinned[b], n);
     const Workspace &W = d->W;
-    hipEvent_t *ev = d->ev[b];
-    bool good = hip_ok(hipEventRecord(ev[EV_UP0], d->copy), "hipEventRecord", err) &&
-                hip_ok(hipMemcpyAsync(W.raw[b], d->pinned[b], n, hipMemcpyHostToDevice, d->copy), "hipMemcpyAsync", err) &&
-                hip_ok(hipEventRecord(ev[EV_UP1], d->copy), "hipEventRecord", err) && hip_ok(hipStreamWaitEvent(d->stream, ev[EV_UP1], 0), "hipStreamWaitEvent", err) &&
-                hip_ok(hipEventRecord(ev[EV_K0], d->stream), "hipEventRecord", err);
+    bool good = st.upload(b, W.raw[b], n, err);
     if (good) {
-        d->used[b] = true;                               // (from here on the buffer is the device's until EV_DONE)
         size_t tb = W.tmp_bytes;
-        good = hip_ok(hipcub::DeviceScan::ExclusiveSum(W.tmp, tb, KeepIter(W.raw[b], KeepOp()), W.pos, (int)n, d->stream), "scan of the keep flags", err);
+        good = hip_ok(keep_scan(W.tmp, tb, W.raw[b], W.pos, n, st.stream), "scan of the keep flags", err);
     }
     if (good) {
-        hipLaunchKernelGGL(k_kmer_scatter, dim3(grid_of(((long long)n + 3) / 4, SCATTER_BLOCK)), dim3(SCATTER_BLOCK), 0, d->stream, W.raw[b], W.pos, n, W.dense + PRE, W.scal);
-        good = hip_ok(hipGetLastError(), "k_kmer_scatter", err) && hip_ok(hipEventRecord(ev[EV_K1], d->stream), "hipEventRecord", err);
+        hipLaunchKernelGGL(k_kmer_scatter, dim3(grid_of(((long long)n + 3) / 4, SCATTER_BLOCK)), dim3(SCATTER_BLOCK), 0, st.stream, W.raw[b], W.pos, n, W.dense + PRE, W.scal);
+        good = hip_ok(hipGetLastError(), "k_kmer_scatter", err) && st.mark_k1(b, err);
     }
     if (good) {
         const unsigned blocks = (unsigned)(((long long)n + COUNT_TILE - 1) / COUNT_TILE);      // (enough for n kept symbols; a thread past m leaves)
-        hipLaunchKernelGGL(k_kmer_count, dim3(blocks), dim3(COUNT_BLOCK), 0, d->stream, W.dense, W.scal, d->k, (int)d->canonical, d->table);
-        hipLaunchKernelGGL(k_kmer_carry, dim3(1), dim3(64), 0, d->stream, W.dense, W.scal);
+        hipLaunchKernelGGL(k_kmer_count, dim3(blocks), dim3(COUNT_BLOCK), 0, st.stream, W.dense, W.scal, d->k, (int)d->canonical, d->table);
+        hipLaunchKernelGGL(k_kmer_carry, dim3(1), dim3(64), 0, st.stream, W.dense, W.scal);
         good = hip_ok(hipGetLastError(), "k_kmer_count", err);
     }
-    // the event goes in whatever happened, so that the buffer's next use (or close) has something to wait for
-    if (d->used[b]) good = hip_ok(hipEventRecord(ev[EV_DONE], d->stream), "hipEventRecord", err) && good;
-    return good ? CORAL_OK : CORAL_ERR_HIP;
+    return st.done(b, good, err) ? CORAL_OK : CORAL_ERR_HIP;
 }
 
 int feed(Device *d, const uint8_t *bytes, int64_t n, std::string &err) {
@@ -403,18 +348,18 @@ static bool select_pass(Device *d, uint64_t greater_than, int64_t capacity, uint
     if (greater_than >= 0xffffffffull) { *n = 0; return true; }      // (no uint32 is above)
     const uint32_t t = (uint32_t)greater_than;
     const unsigned grid = grid_of(tiles, 1);
-    bool good = hip_ok(hipMemsetAsync(W.tile_cnt + tiles, 0, 8, d->stream), "hipMemsetAsync", err);
+    bool good = hip_ok(hipMemsetAsync(W.tile_cnt + tiles, 0, 8, d->st.stream), "hipMemsetAsync", err);
     if (!good) return false;
-    hipLaunchKernelGGL(k_kmer_sel_count, dim3(grid), dim3(TABLE_BLOCK), 0, d->stream, d->table, n4, tiles, t, W.tile_cnt);
+    hipLaunchKernelGGL(k_kmer_sel_count, dim3(grid), dim3(TABLE_BLOCK), 0, d->st.stream, d->table, n4, tiles, t, W.tile_cnt);
     size_t tb = W.tmp_bytes;
-    good = hip_ok(hipGetLastError(), "k_kmer_sel_count", err) && hip_ok(hipcub::DeviceScan::ExclusiveSum(W.tmp, tb, W.tile_cnt, W.tile_off, (int)(tiles + 1), d->stream), "scan of the tiles", err);
+    good = hip_ok(hipGetLastError(), "k_kmer_sel_count", err) && hip_ok(hipcub::DeviceScan::ExclusiveSum(W.tmp, tb, W.tile_cnt, W.tile_off, (int)(tiles + 1), d->st.stream), "scan of the tiles", err);
     if (!good) return false;
     if (capacity > 0) {
-        hipLaunchKernelGGL(k_kmer_sel_write, dim3(grid), dim3(TABLE_BLOCK), 0, d->stream, d->table, n4, tiles, t, W.tile_off, (unsigned long long)capacity, kmers, counts);
+        hipLaunchKernelGGL(k_kmer_sel_write, dim3(grid), dim3(TABLE_BLOCK), 0, d->st.stream, d->table, n4, tiles, t, W.tile_off, (unsigned long long)capacity, kmers, counts);
         if (!hip_ok(hipGetLastError(), "k_kmer_sel_write", err)) return false;
     }
     unsigned long long total = 0;
-    good = hip_ok(hipMemcpyAsync(&total, W.tile_off + tiles, 8, hipMemcpyDeviceToHost, d->stream), "hipMemcpyAsync", err) && hip_ok(hipStreamSynchronize(d->stream), "hipStreamSynchronize", err);
+    good = hip_ok(hipMemcpyAsync(&total, W.tile_off + tiles, 8, hipMemcpyDeviceToHost, d->st.stream), "hipMemcpyAsync", err) && hip_ok(hipStreamSynchronize(d->st.stream), "hipStreamSynchronize", err);
     *n = (int64_t)total;
     return good;
 }
@@ -424,10 +369,10 @@ int finish(Device *d, coral_kmer::Stats &st, std::map<uint64_t, uint64_t> &hist,
     if (!hip_ok(hipSetDevice(d->device), "hipSetDevice", err)) return CORAL_ERR_HIP;
     d->finished = true;
     const Workspace &W = d->W;
-    if (!retire(d, 0, err) || !retire(d, 1, err) || !hip_ok(hipStreamSynchronize(d->stream), "hipStreamSynchronize", err)) return CORAL_ERR_HIP;
+    if (!d->st.drain(err) || !hip_ok(hipStreamSynchronize(d->st.stream), "hipStreamSynchronize", err)) return CORAL_ERR_HIP;
     Scalars s{};
-    hipEvent_t *ev = d->ev[0];                           // (both buffers are retired: their events are free)
-    bool good = hip_ok(hipMemcpyAsync(&s, W.scal, sizeof(s), hipMemcpyDeviceToHost, d->stream), "hipMemcpyAsync", err) && hip_ok(hipStreamSynchronize(d->stream), "hipStreamSynchronize", err);
+    hipEvent_t *ev = d->st.ev[0];                        // (both buffers are retired: their events are free)
+    bool good = hip_ok(hipMemcpyAsync(&s, W.scal, sizeof(s), hipMemcpyDeviceToHost, d->st.stream), "hipMemcpyAsync", err) && hip_ok(hipStreamSynchronize(d->st.stream), "hipStreamSynchronize", err);
     if (!good) return CORAL_ERR_HIP;
     st = coral_kmer::Stats();
     st.n_sequences = d->n_sequences;
@@ -435,26 +380,26 @@ int finish(Device *d, coral_kmer::Stats &st, std::map<uint64_t, uint64_t> &hist,
     st.total = s.total;
     if (st.n_bases >= MAX_BASES) { err = "the stream has 2^32 bases or more: a counter may have wrapped"; return CORAL_ERR_CAPACITY; }
     const long long tiles = table_tiles(d->k);
-    good = hip_ok(hipEventRecord(ev[EV_K0], d->stream), "hipEventRecord", err) && hip_ok(hipMemsetAsync(W.hist, 0, (size_t)HIST_DIRECT * 4, d->stream), "hipMemsetAsync", err);
+    good = hip_ok(hipEventRecord(ev[EV_K0], d->st.stream), "hipEventRecord", err) && hip_ok(hipMemsetAsync(W.hist, 0, (size_t)HIST_DIRECT * 4, d->st.stream), "hipMemsetAsync", err);
     if (!good) return CORAL_ERR_HIP;
-    hipLaunchKernelGGL(k_kmer_stats, dim3(grid_of(tiles, 1)), dim3(TABLE_BLOCK), 0, d->stream, d->table, (unsigned long long)(table_entries(d->k) / 4), tiles, W.hist, W.scal);
+    hipLaunchKernelGGL(k_kmer_stats, dim3(grid_of(tiles, 1)), dim3(TABLE_BLOCK), 0, d->st.stream, d->table, (unsigned long long)(table_entries(d->k) / 4), tiles, W.hist, W.scal);
     if (!hip_ok(hipGetLastError(), "k_kmer_stats", err)) return CORAL_ERR_HIP;
     int64_t n_tail = 0;
     if (!select_pass(d, HIST_DIRECT - 1, TAIL_CAP, W.tail_kmers, W.tail_counts, &n_tail, err)) return CORAL_ERR_HIP;
     if (n_tail >= TAIL_CAP) { err = "more than 65 535 counts of 65 536 and more"; return CORAL_ERR_HIP; }
     std::vector<uint32_t> direct(HIST_DIRECT), tail((size_t)n_tail);
-    good = hip_ok(hipMemcpyAsync(direct.data(), W.hist, (size_t)HIST_DIRECT * 4, hipMemcpyDeviceToHost, d->stream), "hipMemcpyAsync", err) &&
-           (n_tail == 0 || hip_ok(hipMemcpyAsync(tail.data(), W.tail_counts, (size_t)n_tail * 4, hipMemcpyDeviceToHost, d->stream), "hipMemcpyAsync", err)) &&
-           hip_ok(hipMemcpyAsync(&s, W.scal, sizeof(s), hipMemcpyDeviceToHost, d->stream), "hipMemcpyAsync", err) && hip_ok(hipEventRecord(ev[EV_K1], d->stream), "hipEventRecord", err) &&
-           hip_ok(hipStreamSynchronize(d->stream), "hipStreamSynchronize", err);
+    good = hip_ok(hipMemcpyAsync(direct.data(), W.hist, (size_t)HIST_DIRECT * 4, hipMemcpyDeviceToHost, d->st.stream), "hipMemcpyAsync", err) &&
+           (n_tail == 0 || hip_ok(hipMemcpyAsync(tail.data(), W.tail_counts, (size_t)n_tail * 4, hipMemcpyDeviceToHost, d->st.stream), "hipMemcpyAsync", err)) &&
+           hip_ok(hipMemcpyAsync(&s, W.scal, sizeof(s), hipMemcpyDeviceToHost, d->st.stream), "hipMemcpyAsync", err) && hip_ok(hipEventRecord(ev[EV_K1], d->st.stream), "hipEventRecord", err) &&
+           hip_ok(hipStreamSynchronize(d->st.stream), "hipStreamSynchronize", err);
     if (!good) return CORAL_ERR_HIP;
     float ms = 0;
-    if (hipEventElapsedTime(&ms, ev[EV_K0], ev[EV_K1]) == hipSuccess) d->seconds[3] = ms * 1e-3;
+    if (hipEventElapsedTime(&ms, ev[EV_K0], ev[EV_K1]) == hipSuccess) d->st.seconds[3] = ms * 1e-3;
     st.distinct = s.distinct;
     hist.clear();
     for (uint32_t c = 1; c < HIST_DIRECT; ++c) if (direct[c]) { hist[c] = direct[c]; st.max_count = c; }
     for (uint32_t c : tail) { ++hist[c]; if (c > st.max_count) st.max_count = c; }
-    if (seconds) for (int i = 0; i < 4; ++i) seconds[i] = d->seconds[i];
+    if (seconds) for (int i = 0; i < 4; ++i) seconds[i] = d->st.seconds[i];
     return CORAL_OK;
 }
 
@@ -470,8 +415,8 @@ int lookup(Device *d, const uint64_t *indices, int64_t n, uint32_t *counts, std:
     if (!d || !d->finished || n < 0 || (n > 0 && (!indices || !counts))) { err = "no finished session, or a missing array"; return CORAL_ERR_ARG; }
     if (n == 0) return CORAL_OK;
     if (!hip_ok(hipSetDevice(d->device), "hipSetDevice", err)) return CORAL_ERR_HIP;
-    hipLaunchKernelGGL(k_kmer_lookup, dim3(grid_of(n, 256)), dim3(256), 0, d->stream, d->table, (unsigned long long)table_entries(d->k), indices, (long long)n, counts);
-    const bool good = hip_ok(hipGetLastError(), "k_kmer_lookup", err) && hip_ok(hipStreamSynchronize(d->stream), "hipStreamSynchronize", err);
+    hipLaunchKernelGGL(k_kmer_lookup, dim3(grid_of(n, 256)), dim3(256), 0, d->st.stream, d->table, (unsigned long long)table_entries(d->k), indices, (long long)n, counts);
+    const bool good = hip_ok(hipGetLastError(), "k_kmer_lookup", err) && hip_ok(hipStreamSynchronize(d->st.stream), "hipStreamSynchronize", err);
     return good ? CORAL_OK : CORAL_ERR_HIP;
 }
 

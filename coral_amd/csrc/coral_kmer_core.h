@@ -3,8 +3,7 @@
 // lines 29-30 of the reference's scripts/align_nanopore_reads.sh (`meryl count k=15`, `meryl print greater-than distinct=0.9998`);
 // DESIGN.md §4 states the rule in words and says what is not pinned against meryl.
 //
-//   - FASTA text is a stream of bytes.  A line starts at the stream's first byte and behind every '\n'.  A line whose first byte
-//     is '>' is a header line: its '>' is one break, the rest of it up to and including its '\n' is skipped.
+//   - lines are coral_fasta_core.h's.  A header line's '>' is one break, the rest of it up to and including its '\n' is skipped.
 //   - '\n' and '\r' are skipped wherever they stand; A C G T a c g t are the bases 0..3; every other byte is a break.
 //   - a k-mer is a window of k consecutive bases without a break, 1 <= k <= 16, as a 2k-bit integer, first base in the top bits;
 //     canonical: the smaller of the window and its reverse complement.
@@ -15,24 +14,22 @@
 
 #include <stdint.h>
 
-#if defined(__HIPCC__)
-#define CORAL_KMER_HD __host__ __device__ inline
-#else
-#define CORAL_KMER_HD inline
-#endif
+#include "coral_fasta_core.h"
 
 namespace coral_kmer {
+
+using namespace coral_fasta;
 
 constexpr int MAX_K = 16;
 constexpr uint64_t MAX_BASES = (uint64_t)1 << 32;      // a stream with this many bases or more is refused
 constexpr uint32_t HIST_DIRECT = 65536;                // counts below it have a histogram bin of their own; the others are listed
 constexpr uint8_t SYM_BREAK = 4, SYM_SKIP = 5;         // beside the bases 0..3
 
-CORAL_KMER_HD bool k_ok(int k) { return k >= 1 && k <= MAX_K; }
-CORAL_KMER_HD uint64_t table_entries(int k) { return (uint64_t)1 << (2 * k); }
+CORAL_FASTA_HD bool k_ok(int k) { return k >= 1 && k <= MAX_K; }
+CORAL_FASTA_HD uint64_t table_entries(int k) { return (uint64_t)1 << (2 * k); }
 
 // a byte of a sequence line (or a header's '>') -> base, break or skip
-CORAL_KMER_HD uint8_t classify(uint8_t c) {
+CORAL_FASTA_HD uint8_t classify(uint8_t c) {
     switch (c) {
         case 'A': case 'a': return 0;
         case 'C': case 'c': return 1;
@@ -43,22 +40,11 @@ CORAL_KMER_HD uint8_t classify(uint8_t c) {
     }
 }
 
-// where the stream stands between two bytes
-struct LineState {
-    uint8_t line_start = 1, in_header = 0;
-};
-
 // the next byte of the stream -> its symbol; *header is set when the byte opens a header line
-CORAL_KMER_HD uint8_t next_symbol(LineState &s, uint8_t c, bool *header) {
-    *header = false;
-    if (s.in_header) {
-        if (c == '\n') { s.in_header = 0; s.line_start = 1; }
-        return SYM_SKIP;
-    }
-    const bool first = s.line_start != 0;
-    s.line_start = c == '\n';
-    if (first && c == '>') { s.in_header = 1; *header = true; return SYM_BREAK; }
-    return classify(c);
+CORAL_FASTA_HD uint8_t next_symbol(LineState &s, uint8_t c, bool *header) {
+    const Line l = line_step(s, c);
+    *header = l == LINE_OPEN;
+    return l == LINE_OPEN ? SYM_BREAK : l == LINE_HEADER ? SYM_SKIP : classify(c);
 }
 
 // the rolling window: the last min(run, k) bases, forward and as the reverse complement
@@ -68,7 +54,7 @@ struct Roll {
 };
 
 // pushes a kept symbol (a base or a break); true when a window of k bases is complete
-CORAL_KMER_HD bool roll_push(Roll &r, uint8_t sym, int k) {
+CORAL_FASTA_HD bool roll_push(Roll &r, uint8_t sym, int k) {
     if (sym > 3) { r.run = 0; r.fwd = 0; r.rev = 0; return false; }
     const uint64_t mask = table_entries(k) - 1;
     r.fwd = ((r.fwd << 2) | sym) & mask;
@@ -77,9 +63,9 @@ CORAL_KMER_HD bool roll_push(Roll &r, uint8_t sym, int k) {
     return r.run == (uint32_t)k;
 }
 
-CORAL_KMER_HD uint64_t roll_index(const Roll &r, bool canonical) { return canonical && r.rev < r.fwd ? r.rev : r.fwd; }
+CORAL_FASTA_HD uint64_t roll_index(const Roll &r, bool canonical) { return canonical && r.rev < r.fwd ? r.rev : r.fwd; }
 
-CORAL_KMER_HD uint64_t reverse_complement(uint64_t kmer, int k) {
+CORAL_FASTA_HD uint64_t reverse_complement(uint64_t kmer, int k) {
     uint64_t out = 0;
     for (int i = 0; i < k; ++i) { out = (out << 2) | (3 - (kmer & 3)); kmer >>= 2; }
     return out;

@@ -1,7 +1,7 @@
 // coral_kmer_host.h - the k-mer counter's host backend: a straight loop over coral_kmer_core.h with a small state carried between
 // feeds, and the same table layout as the device.  It is what the kernels (coral_kmer.hip) are compared against and `device="cpu"`
-// of coral_amd/kmers.py.  mask_headers is the host's share of the device path: it finds the header lines of a piece.
-// No HIP: g++ alone builds it (tests/native/kmer_host.cpp).
+// of coral_amd/kmers.py.  mask_headers is the host's share of the device path: it blanks the header lines of a piece, which
+// coral_fasta_host.h finds.  No HIP: g++ alone builds it (tests/native/kmer_host.cpp).
 #ifndef CORAL_KMER_HOST_H
 #define CORAL_KMER_HOST_H
 
@@ -11,6 +11,7 @@
 #include <map>
 #include <vector>
 
+#include "coral_fasta_host.h"
 #include "coral_kmer_core.h"
 
 namespace coral_kmer {
@@ -45,39 +46,14 @@ struct HostCounter {
 
 // The header lines of a piece, for a consumer that classifies byte by byte (coral_kmer_core.h's classify): every byte of a header
 // line behind its '>' becomes '\n' in place, so that the '>' is the one break and the rest is skipped.  `s` is the state in front
-// of the piece and becomes the one behind it; returns the number of header lines that open in the piece.  '>' is searched with
-// memchr and tested for a line start; headers are few, so this costs little beside the copy into the staging buffer.
+// of the piece and becomes the one behind it; returns the number of header lines that open in the piece.
 inline uint64_t mask_headers(LineState &s, uint8_t *buf, size_t n) {
     uint64_t opened = 0;
     size_t pos = 0;
-    if (n == 0) return 0;
-    const bool ends_line = buf[n - 1] == '\n';
-    if (s.in_header) {
-        uint8_t *q = (uint8_t *)memchr(buf, '\n', n);
-        if (!q) { memset(buf, '\n', n); return 0; }
-        memset(buf, '\n', (size_t)(q - buf));
-        pos = (size_t)(q - buf) + 1;
-        s.in_header = 0;
-        s.line_start = 1;
+    for (HeaderLine h; next_header_line(s, buf, n, pos, h);) {
+        opened += !h.carried;
+        memset(buf + h.body, '\n', h.end - h.body);
     }
-    while (pos < n) {
-        uint8_t *p = (uint8_t *)memchr(buf + pos, '>', n - pos);
-        if (!p) break;
-        const size_t i = (size_t)(p - buf);
-        const bool first = i == 0 ? s.line_start != 0 : buf[i - 1] == '\n';
-        if (!first) { pos = i + 1; continue; }
-        ++opened;
-        uint8_t *q = (uint8_t *)memchr(buf + i + 1, '\n', n - i - 1);
-        if (!q) {
-            memset(buf + i + 1, '\n', n - i - 1);
-            s.in_header = 1;
-            s.line_start = 0;
-            return opened;
-        }
-        memset(buf + i + 1, '\n', (size_t)(q - (buf + i + 1)));
-        pos = (size_t)(q - buf) + 1;
-    }
-    s.line_start = ends_line;
     return opened;
 }
 

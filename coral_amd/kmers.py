@@ -13,13 +13,12 @@ from __future__ import annotations
 
 import ctypes as C
 import numbers
-import os
 import re
 import time
 
 import numpy as np
 
-from . import _lib
+from . import _lib, fasta_stream
 
 LAST_COUNT = {}                      # seconds of the last count_kmers / select / write, by stage
 _FIRST_SELECT = 1 << 16              # rows the first coral_kmer_select makes room for
@@ -233,41 +232,6 @@ class KmerCounts:
         return len(values)
 
 
-def _pieces(fasta, chunk_bytes):
-    """The stream's pieces as (array or bytes, length), and the seconds spent reading them (a one-entry list, filled as it goes)."""
-    spent = [0.0]
-
-    def gen(fp):
-        buf = np.empty(chunk_bytes, dtype=np.uint8)
-        into = getattr(fp, "readinto", None)
-        while True:
-            t0 = time.perf_counter()
-            if into is not None:
-                n = into(memoryview(buf))
-                piece = buf
-            else:
-                piece = fp.read(chunk_bytes)
-                n = len(piece)
-            spent[0] += time.perf_counter() - t0
-            if not n:
-                return
-            yield piece, n
-
-    def opened():
-        if hasattr(fasta, "read"):
-            yield from gen(fasta)
-            return
-        path = os.fspath(fasta)
-        if path.endswith(".gz"):                                  # inflated by Python's gzip on the host: slow, not the hot path
-            import gzip
-            with gzip.open(path, "rb") as fp:
-                yield from gen(fp)
-        else:
-            with open(path, "rb", buffering=0) as fp:
-                yield from gen(fp)
-    return opened(), spent
-
-
 def count_kmers(fasta, k: int = 15, canonical: bool = True, device="cuda:0", chunk_bytes: int = 64 << 20, _bases_before: int = 0) -> KmerCounts:
     """Counts every k-mer of the FASTA ``fasta`` - a path (one ending in .gz is read through Python's ``gzip`` on the host, which is
     slow and not the hot path) or an open binary file - into a table of 4^k uint32 counters -> ``KmerCounts``.
@@ -290,44 +254,28 @@ def count_kmers(fasta, k: int = 15, canonical: bool = True, device="cuda:0", chu
     t_all = time.perf_counter()
     if on_gpu:
         dev = torch.device(device)
-        torch.cuda.set_device(dev)
-        ws_bytes = int(L.coral_kmer_workspace_bytes(k, staging))
-        if ws_bytes < 0:
-            raise _lib.CoralHipError("coral_kmer_workspace_bytes failed (%d)" % ws_bytes)
         table = torch.zeros(entries, dtype=torch.int32, device=dev)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        stream = torch.cuda.current_stream(dev)
-        stream.synchronize()                                     # (the blocks may be recycled ones)
+        ws, stream = fasta_stream.gpu_side(dev, int(L.coral_kmer_workspace_bytes(k, staging)), "coral_kmer_workspace_bytes")
         keep = (table, ws)
-        rc = L.coral_kmer_open(k, int(bool(canonical)), dev.index or 0, table.data_ptr(), staging, ws.data_ptr(), ws_bytes, stream.cuda_stream, int(_bases_before),
+        rc = L.coral_kmer_open(k, int(bool(canonical)), dev.index or 0, table.data_ptr(), staging, ws.data_ptr(), ws.numel(), stream.cuda_stream, int(_bases_before),
                                C.byref(handle))
     else:
         dev = None
         table = np.zeros(entries, dtype=np.uint32)
         keep = (table,)
         rc = L.coral_kmer_open(k, int(bool(canonical)), -1, table.ctypes.data, 0, None, 0, None, int(_bases_before), C.byref(handle))
-    if rc != 0:
-        raise _lib.CoralHipError("coral_kmer_open failed (%d): %s" % (rc, L.coral_bam_last_error().decode()))
+    fasta_stream.check(rc, "coral_kmer_open")
     LAST_COUNT["zero_table"] = time.perf_counter() - t_all
     stats, secs = (C.c_int64 * 8)(), (C.c_double * 4)()
     try:
-        pieces, read_s = _pieces(fasta, int(chunk_bytes))
-        feed_s = 0.0
-        for piece, n in pieces:
-            t0 = time.perf_counter()
-            rc = L.coral_kmer_feed(handle, piece.ctypes.data if isinstance(piece, np.ndarray) else piece, n)
-            feed_s += time.perf_counter() - t0
-            if rc != 0:
-                raise _lib.CoralHipError("coral_kmer_feed failed (%d): %s" % (rc, L.coral_bam_last_error().decode()))
+        read_s, feed_s = fasta_stream.feed_all(L.coral_kmer_feed, handle, fasta, chunk_bytes)
         t0 = time.perf_counter()
-        rc = L.coral_kmer_finish(handle, stats, secs)
-        if rc != 0:
-            raise _lib.CoralHipError("coral_kmer_finish failed (%d): %s" % (rc, L.coral_bam_last_error().decode()))
+        fasta_stream.check(L.coral_kmer_finish(handle, stats, secs), "coral_kmer_finish")
         finish_s = time.perf_counter() - t0
     except BaseException:
         L.coral_kmer_close(handle)
         raise
-    LAST_COUNT.update(read=read_s[0], feed=feed_s, finish_wait=finish_s, upload=float(secs[0]), classify_compact=float(secs[1]), count=float(secs[2]),
+    LAST_COUNT.update(read=read_s, feed=feed_s, finish_wait=finish_s, upload=float(secs[0]), classify_compact=float(secs[1]), count=float(secs[2]),
                       statistics=float(secs[3]), wall=time.perf_counter() - t_all)
     return KmerCounts(handle, k, canonical, dev, stats, keep)
 

@@ -156,6 +156,28 @@ def test_more_selected_k_mers_than_the_first_capacity():
     assert L.coral_kmer_select(dev._handle, 0, 0, None, None, C.byref(n)) == -3 and n.value == len(want[0])
 
 
+def test_a_session_closed_with_pieces_in_flight():
+    """Through the C ABI: a device session at staging 16 is fed five pieces in one call - both staging buffers are retired and used
+    again - and closed without coral_kmer_finish.  Close has to wait for what is in flight; a count of the same text afterwards
+    equals the host backend's."""
+    import torch
+    L = _lib.lib()
+    data = b">one\nACGTTGCAGGATTACAGATTACACGT\n>two\nGGGATCCNNACGTACGTTTGACCATGCAGGCTAAT\nACGTAG\n"
+    assert len(data) == 80
+    table = torch.zeros(4 ** 3, dtype=torch.int32, device=GPU)
+    ws_bytes = L.coral_kmer_workspace_bytes(3, 16)
+    assert ws_bytes > 0
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=GPU)
+    stream = torch.cuda.current_stream(GPU)
+    stream.synchronize()
+    handle = C.c_void_p()
+    assert L.coral_kmer_open(3, 1, 0, table.data_ptr(), 16, ws.data_ptr(), ws_bytes, stream.cuda_stream, 0, C.byref(handle)) == 0
+    assert L.coral_kmer_feed(handle, data, len(data)) == 0
+    L.coral_kmer_close(handle)
+    assert device_results(data, 3, True, 16) == host_results(data, 3, True)
+    assert host_results(data, 3, True)[2]["n_sequences"] == 2
+
+
 def test_kmers_mode_on_both_devices(tmp_path, capsys):
     fasta = str(tmp_path / "ref.fa")
     with open(fasta, "wb") as fp:
