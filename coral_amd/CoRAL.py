@@ -5,7 +5,7 @@
         --skip_cycle_decomp
 
 The `reconstruct` mode and the `hsr` mode (§8(f) item 3) run on the MI355X path, and so do `index`, `qc`
-(the reference's scripts/report_nanopore_qc.py, from one decode of the aligned BAM), `pileup` (the bases per position of
+(the reference's scripts/report_nanopore_qc.py, from one decode of the aligned BAM or, with --fastq, from the reads' FASTQ), `pileup` (the bases per position of
 regions, pysam's count_coverage as a table) and `depth` (read depth per fixed-size bin of every contig, the table a copy-number
 caller starts from), `fastq` (selected reads as FASTQ, by regions or read names), `view` (the same selection as a BAM file of
 the records themselves, with its index on request) and `sort` (the kept records in coordinate order as a BAM file, with its
@@ -14,7 +14,8 @@ SAM text as the BAM file `sort` opens: line 38 of that script) and `cnv` (the .c
 intervals that `reconstruct` starts from: scripts/call_cnvs.sh and the seed mode, from the binned depth) and `kmers` (the
 reference genome's repetitive k-mers, the list the mapper takes with -W: lines 29-30 of that script) and `composition` (the
 reference genome's G/C, A/T and soft-masked bases per depth bin, which `cnv --ref / --composition` corrects the GC bias with: the
-gc and rmask columns of the reference table of scripts/call_cnvs.sh); the other modes of the
+gc and rmask columns of the reference table of scripts/call_cnvs.sh) and `filter` (the reads of a FASTQ file that are long and
+good enough, written as they were read: the "Quality filter reads" that scripts/report_nanopore_qc.py announces); the other modes of the
 reference (seed, plot, cycle2bed) are untouched and are delegated to the reference's own modules when they are
 importable (set CORAL_REFERENCE_SRC to the reference's src/ directory).  The cycle-decomposition step after the graph build is the
 reference's (Gurobi); it runs on the object this module returns.
@@ -88,8 +89,10 @@ def build_parser():
     ip.add_argument("--lr_bam", help="Sorted (long read) bam file.", required=True)
     ip.add_argument("--index", help="Name of the index file (default: <lr_bam>.bai).")
     ip.add_argument("--device", help="GPU to use ('cpu': the host pipeline).", default="cuda:0")
-    qp = sub.add_parser("qc", help="Report read length and base quality statistics of a (long read) bam file.")
-    qp.add_argument("--lr_bam", help="(Long read) bam file.", required=True)
+    qp = sub.add_parser("qc", help="Report read length and base quality statistics of a (long read) bam file, or of the reads' FASTQ file.")
+    qp.add_argument("--lr_bam", help="(Long read) bam file.")
+    qp.add_argument("--fastq", help="FASTQ file of the reads, in place of --lr_bam (a name ending in .gz is inflated on the host).")
+    qp.add_argument("--chunk_bytes", help="With --fastq: bytes of the FASTQ file per piece.", type=int, default=64 << 20)
     qp.add_argument("--output_dir", help="Where to write the summary and the plots.", required=True)
     qp.add_argument("--device", help="GPU to use ('cpu': the host pipeline).", default="cuda:0")
     qp.add_argument("--no_plots", help="If specified, write no histogram images.", action='store_true')
@@ -195,6 +198,14 @@ def build_parser():
     gp.add_argument("--bin_size", help="Bases per bin: the binned depth's.", type=int, default=1000)
     gp.add_argument("--chunk_bytes", help="Bytes of the FASTA file per piece.", type=int, default=64 << 20)
     gp.add_argument("--device", help="GPU to use ('cpu': the host backend, one thread).", default="cuda:0")
+    lp = sub.add_parser("filter", help="Write the reads of a FASTQ file that are long and good enough, from one pass over it.")
+    lp.add_argument("--fastq", help="FASTQ file of the reads (a name ending in .gz is inflated on the host).", required=True)
+    lp.add_argument("--output", help="Name of the FASTQ file of the kept reads.", required=True)
+    lp.add_argument("--min_length", help="Drop reads with fewer bases.", type=int, default=0)
+    lp.add_argument("--max_length", help="Drop reads with more bases (0: no limit).", type=int, default=0)
+    lp.add_argument("--min_mean_quality", help="Drop reads whose mean base quality (the arithmetic mean of the Phred values) is lower.", type=float, default=0.0)
+    lp.add_argument("--chunk_bytes", help="Bytes of the FASTQ file per piece.", type=int, default=64 << 20)
+    lp.add_argument("--device", help="GPU to use ('cpu': the host backend, one thread).", default="cuda:0")
     for p in (rp, hp, qp, pp, dp, fp, vp, sp, mp, cp):
         add_filter_arguments(p)
     for mode in ("seed", "plot", "cycle2bed"):
@@ -228,7 +239,15 @@ def qc_mode(args):
     histograms (lines 54-68, plain matplotlib) and read_qc.json (counters, summary, base-quality histogram)."""
     import json
     from coral_amd import bam
-    qc = bam.read_qc(args.lr_bam, device=args.device, record_filter=record_filter_of(args))
+    if (args.lr_bam is None) == (getattr(args, "fastq", None) is None):
+        raise SystemExit("qc: give exactly one of --lr_bam and --fastq")
+    if args.lr_bam is None:
+        if record_filter_of(args).active:
+            raise SystemExit("qc: the --filter_* arguments test bam records and cannot be given with --fastq (the filter mode drops reads of a FASTQ file)")
+        from coral_amd import fastq
+        qc = fastq.read_qc(args.fastq, device=args.device, chunk_bytes=args.chunk_bytes)
+    else:
+        qc = bam.read_qc(args.lr_bam, device=args.device, record_filter=record_filter_of(args))
     os.makedirs(args.output_dir, exist_ok=True)
     wrote = [qc.write_summary(os.path.join(args.output_dir, "quality_control_summary.tsv"))]
     summary = qc.summary()
@@ -453,6 +472,17 @@ def composition_mode(args):
     return args.output
 
 
+def filter_mode(args):
+    """The reads of --fastq that are long and good enough (fastq.read_qc with an output): what the "Quality filter reads" of the
+    reference's scripts/report_nanopore_qc.py promises.  The kept records are written exactly as they were read."""
+    from coral_amd import fastq
+    qc = fastq.read_qc(args.fastq, device=args.device, chunk_bytes=args.chunk_bytes, min_length=args.min_length, max_length=args.max_length,
+                       min_mean_quality=args.min_mean_quality, output=args.output)
+    print("records: %d\nreads: %d\nbases: %d\nkept_records: %d\nkept_bases: %d" % (qc.n_records, qc.n_reads, qc.total_bases, qc.n_kept, qc.kept_bases))
+    print("Wrote %s" % args.output)
+    return args.output
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     if argv and argv[0] in ("seed", "plot", "cycle2bed"):
@@ -498,6 +528,8 @@ def main(argv=None):
         return kmers_mode(args)
     if args.mode == "composition":
         return composition_mode(args)
+    if args.mode == "filter":
+        return filter_mode(args)
     parser.print_help()
     return None
 

@@ -243,6 +243,14 @@ def lib():
     L.coral_comp_finish.argtypes = [C.c_void_p, P, P]
     L.coral_comp_contigs.argtypes = [C.c_void_p, C.c_int64, P, C.c_int64, P, P]
     L.coral_comp_close.argtypes = [C.c_void_p]
+    L.coral_fastq_workspace_bytes.argtypes = [C.c_int64]
+    L.coral_fastq_workspace_bytes.restype = C.c_int64
+    L.coral_fastq_geometry.argtypes = [P]
+    L.coral_fastq_open.argtypes = [C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int64, P, P, C.c_int64, P, C.POINTER(C.c_void_p)]
+    L.coral_fastq_feed.argtypes = [C.c_void_p, P, C.c_int64]
+    L.coral_fastq_finish.argtypes = [C.c_void_p, P, P]
+    L.coral_fastq_rows.argtypes = [C.c_void_p, C.c_int64, P, P, P]
+    L.coral_fastq_close.argtypes = [C.c_void_p]
     for name in ("coral_bgzf_deflate_scratch_bytes", "coral_bgzf_pack_scratch_bytes"):
         getattr(L, name).argtypes = [C.c_int32]
         getattr(L, name).restype = C.c_int64

@@ -1,6 +1,7 @@
-// coral_stream_gpu.h - what the device sessions that stream FASTA text in pieces share (coral_kmer.hip, coral_comp.hip): the
-// double-buffered staging of the pieces and the scan that gives every kept byte of a piece its ordinal; and, for every session that
-// carves a caller's workspace (coral_cngpu.hip too), up256 and the typed Carver.
+// coral_stream_gpu.h - what the device sessions that stream text in pieces share (FASTA: coral_kmer.hip, coral_comp.hip; FASTQ:
+// coral_fastq.hip, the first whose per-piece results come down again, through `retired`): the double-buffered staging of the
+// pieces and the scan that gives every kept byte of a FASTA piece its ordinal; and, for every session that carves a caller's
+// workspace (coral_cngpu.hip too), up256 and the typed Carver.
 //
 // A PieceStager owns two pinned buffers, a non-blocking copy stream and five events a buffer.  Per piece, with no host wait but the
 // one for the buffer's earlier use:

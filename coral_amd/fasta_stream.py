@@ -1,6 +1,6 @@
-"""What the modes that stream a reference FASTA through a native session share (`kmers`: kmers.py, `composition`: composition.py):
-the file's pieces, the GPU side of a session and the timed loop over a ``*_feed`` entry point.  The native counterpart is
-coral_stream_gpu.h."""
+"""What the modes that stream a text file through a native session share (a reference FASTA: `kmers`: kmers.py, `composition`:
+composition.py; the reads' FASTQ: `qc --fastq` and `filter`: fastq.py): the file's pieces, the GPU side of a session and the timed
+loop over a ``*_feed`` entry point.  The native counterpart is coral_stream_gpu.h."""
 from __future__ import annotations
 
 import os

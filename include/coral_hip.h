@@ -1153,6 +1153,65 @@ int coral_comp_contigs(void *handle, int64_t n_contigs, int64_t *lengths, int64_
 /* scripts/call_cnvs.sh:12-17: the end of the session */
 int coral_comp_close(void *handle);
 
+/* ------------------------------------------------------------------------------------------------
+ * Read QC and a read filter from the FASTQ itself (`qc --fastq`, `filter`): what the reference's scripts/report_nanopore_qc.py:35-48
+ * collects through `pysam.FastxFile` - `len(sequence)` and `np.mean(quality)` of every record that has a sequence - and the
+ * filter that its argument parser promises ("Quality filter reads") and that it lacks.  pysam and kseq were not available to
+ * compare with; the rule (coral_fastq_core.h) is what both backends compute, exactly:
+ *   text      FASTQ bytes, fed in pieces of any size; the result does not depend on the cuts.  A line starts at the first byte
+ *             and behind every '\n'; line k has phase k mod 4; four lines are one record: name, sequence, separator, quality.  A
+ *             phase-0 line must start with '@', a phase-2 line with '+'; the rest of either is not looked at.  '\r' is skipped
+ *             anywhere in a phase-1 or phase-3 line; every other byte of a phase-1 line is one base (length <= 2^31 - 1), every
+ *             other byte of a phase-3 line one quality character q, 33 <= q <= 126: qual_sum += q - 33, hist[q - 33] += 1.  A
+ *             record's quality count must equal its length.  A last line without '\n' is legal; the stream may end at a record
+ *             boundary, inside a phase-3 line or right behind the '\n' of a phase-2 line (either closes the record); an empty
+ *             stream is zero records.
+ *   refusals  everything else is CORAL_ERR_FORMAT, with the stream offset of the first offending byte in stats[6]: a wrong first
+ *             byte (blank lines, FASTA records and wrapped records are refused so) and a quality character out of range at that
+ *             byte; counts that differ at the byte that closes the record (its quality line's '\n', or the end of the stream);
+ *             a stream that ends inside lines 0-2 at its end.  (kseq would skip blank lines and accept wrapped records.)
+ *   rows      a record of length 0 is counted (stats[2]) and not listed; every other one is a read with length, qual_sum and kept.
+ *   filter    kept iff length >= min_length, (max_length == 0 or length <= max_length) and 100 * qual_sum >= min_mean_q100 *
+ *             length in 64-bit integers: the arithmetic mean of the Phred values in hundredths, not a mean of error
+ *             probabilities.  No thresholds: every record is kept.  With output_fd >= 0 the bytes of every kept record go to
+ *             it exactly as they were read (CR LF and a missing last '\n' included), consecutive kept records in one write.
+ * A session, so that the caller owns the reading of the file:
+ *   open      device < 0: the host backend, one thread, `hist` (256 zeroed uint64) in host memory; staging_bytes, workspace and
+ *             stream are ignored.  device >= 0: `hist` and `workspace` (coral_fastq_workspace_bytes(staging_bytes); the library
+ *             allocates no device memory) are device memory, the kernels run on `stream`; the session owns two pinned staging
+ *             buffers of staging_bytes (16 .. 2^30) and a copy stream.  min_mean_q100: 0 .. 9300.
+ *   feed      the next n bytes.  Device: the '\n' bytes are counted in the caller's bytes (memchr), which says how many records
+ *             the piece closes and where (a piece that would close more than geometry[3] is fed as several); the pinned copy goes
+ *             up on the copy stream beside the kernels of the piece before; then on `stream`: scan of the is-newline flags,
+ *             k_fastq_accum (one no-return atomicAdd per row column and run of lanes in the same record, the histogram through
+ *             a 256-bin LDS table), k_fastq_walk (closes the records, carries the open one) and the copy of the closed rows down
+ *             into the pinned buffer, where they are taken - and the kept records' bytes written - when the buffer is next
+ *             used.  No host wait for the kernels; uncompressed text never comes back from the device.
+ *   finish    waits; stats[0..6] (8 entries) = records, reads, records without sequence, bases, kept records (those without
+ *             sequence included), kept bases, the offending offset or -1.  seconds[0..3] (or NULL) = upload, scan + walk,
+ *             accumulate (host: the whole feed), write.  A refused text: CORAL_ERR_FORMAT from feed or finish, stats[6] filled.
+ *   rows      length, qual_sum and kept of the listed reads in file order, host arrays of stats[1] entries.
+ *   close     frees the session (never the histogram or the workspace, and the descriptor stays open).
+ * coral_fastq_geometry -> geometry[0..6] = bytes per thread and threads per workgroup of k_fastq_accum, lanes per wave, the
+ *   records one piece closes, the smallest staging size, the bytes of one load, threads of k_fastq_walk.
+ * Errors go to coral_bam_last_error; a bad argument or an output that cannot be written is CORAL_ERR_ARG.
+ * ------------------------------------------------------------------------------------------------ */
+/* scripts/report_nanopore_qc.py:35-48 (`pysam.FastxFile(fastq_file)`): the device scratch of a session over the FASTQ */
+int64_t coral_fastq_workspace_bytes(int64_t staging_bytes);
+/* scripts/report_nanopore_qc.py:35-48: the launch geometry of the kernels behind the loop over the records */
+int coral_fastq_geometry(int32_t *geometry);
+/* scripts/report_nanopore_qc.py:35-48 (and the "Quality filter reads" of its line 85): a session over the FASTQ */
+int coral_fastq_open(int32_t device, int64_t min_length, int64_t max_length, int64_t min_mean_q100, int32_t output_fd,
+                     int64_t staging_bytes, void *hist, void *workspace, int64_t workspace_bytes, void *stream, void **handle);
+/* scripts/report_nanopore_qc.py:35-48: the next bytes of the FASTQ */
+int coral_fastq_feed(void *handle, const uint8_t *bytes, int64_t n);
+/* scripts/report_nanopore_qc.py:35-48: the end of the stream and the counters */
+int coral_fastq_finish(void *handle, int64_t *stats, double *seconds);
+/* scripts/report_nanopore_qc.py:43-48 (`mean_lengths`, `mean_qualities`): length, quality sum and kept flag of every read */
+int coral_fastq_rows(void *handle, int64_t n_reads, int32_t *length, int64_t *qual_sum, uint8_t *kept);
+/* scripts/report_nanopore_qc.py:35-48: the end of the session */
+int coral_fastq_close(void *handle);
+
 #ifdef __cplusplus
 }
 #endif
