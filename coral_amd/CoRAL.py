@@ -15,7 +15,8 @@ intervals that `reconstruct` starts from: scripts/call_cnvs.sh and the seed mode
 reference genome's repetitive k-mers, the list the mapper takes with -W: lines 29-30 of that script) and `composition` (the
 reference genome's G/C, A/T and soft-masked bases per depth bin, which `cnv --ref / --composition` corrects the GC bias with: the
 gc and rmask columns of the reference table of scripts/call_cnvs.sh) and `filter` (the reads of a FASTQ file that are long and
-good enough, written as they were read: the "Quality filter reads" that scripts/report_nanopore_qc.py announces); the other modes of the
+good enough, written as they were read: the "Quality filter reads" that scripts/report_nanopore_qc.py announces) and `sketch` (the
+reference genome's window minimizers sorted by hash, the mapper's first stage: line 34 of scripts/align_nanopore_reads.sh); the other modes of the
 reference (seed, plot, cycle2bed) are untouched and are delegated to the reference's own modules when they are
 importable (set CORAL_REFERENCE_SRC to the reference's src/ directory).  The cycle-decomposition step after the graph build is the
 reference's (Gurobi); it runs on the object this module returns.
@@ -198,6 +199,14 @@ def build_parser():
     gp.add_argument("--bin_size", help="Bases per bin: the binned depth's.", type=int, default=1000)
     gp.add_argument("--chunk_bytes", help="Bytes of the FASTA file per piece.", type=int, default=64 << 20)
     gp.add_argument("--device", help="GPU to use ('cpu': the host backend, one thread).", default="cuda:0")
+    xp = sub.add_parser("sketch", help="Sketch a reference's window minimizers and write its seed index (the mapper's first stage) from its FASTA file.")
+    xp.add_argument("--ref", help="Reference genome, FASTA (a name ending in .gz is inflated on the host).", required=True)
+    xp.add_argument("--output", help="Name of the output file (an uncompressed .npz).", required=True)
+    xp.add_argument("--weights", help="Repetitive k-mers to down-weight: the output of the kmers mode at the same k (the mapper's -W list).")
+    xp.add_argument("--k", help="K-mer size, 1..16.", type=int, default=15)
+    xp.add_argument("--w", help="Window size in k-mer positions, 1..256.", type=int, default=50)
+    xp.add_argument("--chunk_bytes", help="Bytes of the FASTA file per piece.", type=int, default=64 << 20)
+    xp.add_argument("--device", help="GPU to use ('cpu': the host backend, one thread).", default="cuda:0")
     lp = sub.add_parser("filter", help="Write the reads of a FASTQ file that are long and good enough, from one pass over it.")
     lp.add_argument("--fastq", help="FASTQ file of the reads (a name ending in .gz is inflated on the host).", required=True)
     lp.add_argument("--output", help="Name of the FASTQ file of the kept reads.", required=True)
@@ -472,6 +481,18 @@ def composition_mode(args):
     return args.output
 
 
+def sketch_mode(args):
+    """The minimizer index of --ref (minimizers.write_index): the first stage of the mapper of line 34 of the reference's
+    scripts/align_nanopore_reads.sh, with --weights the list its -W takes."""
+    from coral_amd import minimizers
+    idx = minimizers.write_index(args.ref, args.output, args.k, args.w, args.weights, device=args.device, chunk_bytes=args.chunk_bytes)
+    print("contigs: %d\nbases: %d\nminimizers: %d\ndensity: %.6f" % (len(idx.contig_names), idx.positions, idx.n, idx.n / idx.positions if idx.positions else 0.0))
+    print("seconds: " + " ".join("%s=%.3f" % (name, minimizers.LAST_SKETCH[name]) for name in ("open", "read", "feed", "upload", "symbols", "sketch", "sort", "write", "wall")))
+    print("Wrote %s (%d entries)" % (args.output, idx.n))
+    idx.close()
+    return args.output
+
+
 def filter_mode(args):
     """The reads of --fastq that are long and good enough (fastq.read_qc with an output): what the "Quality filter reads" of the
     reference's scripts/report_nanopore_qc.py promises.  The kept records are written exactly as they were read."""
@@ -528,6 +549,8 @@ def main(argv=None):
         return kmers_mode(args)
     if args.mode == "composition":
         return composition_mode(args)
+    if args.mode == "sketch":
+        return sketch_mode(args)
     if args.mode == "filter":
         return filter_mode(args)
     parser.print_help()

@@ -251,6 +251,19 @@ def lib():
     L.coral_fastq_finish.argtypes = [C.c_void_p, P, P]
     L.coral_fastq_rows.argtypes = [C.c_void_p, C.c_int64, P, P, P]
     L.coral_fastq_close.argtypes = [C.c_void_p]
+    for name, args in (("coral_sketch_bitmap_bytes", [C.c_int32]), ("coral_sketch_workspace_bytes", [C.c_int64]), ("coral_sketch_sort_workspace_bytes", [C.c_int64]),
+                       ("coral_sketch_anchors_workspace_bytes", [C.c_int64])):
+        getattr(L, name).argtypes = args
+        getattr(L, name).restype = C.c_int64
+    L.coral_sketch_geometry.argtypes = [P]
+    L.coral_sketch_open.argtypes = [C.c_int32, C.c_int32, C.c_int32, P, P, P, C.c_int64, C.c_int64, P, C.c_int64, P, C.POINTER(C.c_void_p)]
+    L.coral_sketch_feed.argtypes = [C.c_void_p, P, C.c_int64]
+    L.coral_sketch_finish.argtypes = [C.c_void_p, P, P]
+    L.coral_sketch_contigs.argtypes = [C.c_void_p, C.c_int64, P, C.c_int64, P, P]
+    L.coral_sketch_close.argtypes = [C.c_void_p]
+    L.coral_sketch_sort.argtypes = [C.c_int32, P, P, C.c_int64, C.c_int32, P, C.c_int64, P]
+    L.coral_sketch_lookup.argtypes = [C.c_int32, P, C.c_int64, P, C.c_int64, P, P, P]
+    L.coral_sketch_anchors.argtypes = [C.c_int32, P, P, C.c_int64, P, P, P, P, C.c_int64, C.c_int64, C.c_int64, P, P, P, C.c_int64, P, C.POINTER(C.c_int64)]
     for name in ("coral_bgzf_deflate_scratch_bytes", "coral_bgzf_pack_scratch_bytes"):
         getattr(L, name).argtypes = [C.c_int32]
         getattr(L, name).restype = C.c_int64

@@ -36,17 +36,10 @@ constexpr int WAVE = 64;
 constexpr int COUNT_SPT = 64;                    // bytes per thread of k_comp_count: four 16-byte loads
 constexpr int COUNT_BLOCK = 256;
 constexpr int COUNT_TILE = COUNT_SPT * COUNT_BLOCK;
-constexpr int MAX_BOUND = 1024;                  // header lines of one piece
-constexpr int WALK_BLOCK = 256;
+constexpr int WALK_BLOCK = 256;                  // (MAX_BOUND, the header lines of one piece, and PieceHead are coral_stream_gpu.h's)
 constexpr int WALK_ITEMS = MAX_BOUND / WALK_BLOCK;
 constexpr int64_t MIN_STAGING = 16, MAX_STAGING = (int64_t)1 << 30;
 constexpr uint32_t NO_BIN = 0xffffffffu;
-
-struct PieceHead {                               // in front of a piece's bytes, in the pinned buffer and on the device
-    uint32_t n_bytes, n_bounds, open_before, pad;
-    uint32_t bounds[MAX_BOUND];                  // byte offsets of the header lines that open in the piece, rising
-};
-constexpr size_t HEAD_BYTES = (sizeof(PieceHead) + 255) & ~(size_t)255;
 
 struct Carry {                                   // what stays in device memory between the pieces
     unsigned long long cur_len, bin_base;        // the open contig's positions so far; the bins in front of it

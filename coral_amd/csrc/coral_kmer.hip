@@ -54,20 +54,7 @@ struct Scalars {                                 // what stays in device memory 
 // four bytes a thread: symbols to dense[pos]; the thread of the last byte leaves the number of kept symbols
 __global__ __launch_bounds__(SCATTER_BLOCK) void k_kmer_scatter(const uint8_t *__restrict__ raw, const uint32_t *__restrict__ pos, uint32_t n, uint8_t *__restrict__ dense,
                                                                  Scalars *__restrict__ S) {
-    const uint32_t words = (n + 3) / 4;
-    for (uint32_t w = blockIdx.x * SCATTER_BLOCK + threadIdx.x; w < words; w += gridDim.x * SCATTER_BLOCK) {
-        const uint32_t bytes = ((const uint32_t *)raw)[w];           // (both arrays are allocated in whole words of four)
-        const uint4 p = ((const uint4 *)pos)[w];
-        const uint32_t at[4] = {p.x, p.y, p.z, p.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const uint32_t i = w * 4 + j;
-            if (i >= n) break;
-            const uint8_t sym = classify((uint8_t)(bytes >> (8 * j)));
-            if (sym != SYM_SKIP) dense[at[j]] = sym;
-            if (i == n - 1) S->m = at[j] + (sym != SYM_SKIP);
-        }
-    }
+    scatter_symbols<SCATTER_BLOCK>(raw, pos, n, dense, &S->m, [](uint8_t c) { return classify(c); }, SYM_SKIP);
 }
 
 // `dense` starts at the PRE carried symbols; the piece's m symbols follow

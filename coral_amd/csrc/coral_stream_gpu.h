@@ -50,6 +50,37 @@ inline size_t keep_scan_tmp_bytes(int64_t n) {
     return keep_scan(nullptr, b, nullptr, nullptr, n, nullptr) == hipSuccess ? b : 0;
 }
 
+// The body of a scatter kernel (k_kmer_scatter, k_sketch_scatter): four bytes a thread, the kept bytes' symbols to dense[pos];
+// the thread of the last byte leaves the number of kept symbols in *m.  `symbol`: byte -> symbol, `skip` the symbol of a byte that
+// is not kept.
+template <int BLOCK, class Symbol>
+__device__ __forceinline__ void scatter_symbols(const uint8_t *__restrict__ raw, const uint32_t *__restrict__ pos, uint32_t n, uint8_t *__restrict__ dense, uint32_t *__restrict__ m,
+                                                const Symbol &symbol, uint8_t skip) {
+    const uint32_t words = (n + 3) / 4;
+    for (uint32_t w = blockIdx.x * BLOCK + threadIdx.x; w < words; w += gridDim.x * BLOCK) {
+        const uint32_t bytes = ((const uint32_t *)raw)[w];           // (both arrays are allocated in whole words of four)
+        const uint4 p = ((const uint4 *)pos)[w];
+        const uint32_t at[4] = {p.x, p.y, p.z, p.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const uint32_t i = w * 4 + j;
+            if (i >= n) break;
+            const uint8_t sym = symbol((uint8_t)(bytes >> (8 * j)));
+            if (sym != skip) dense[at[j]] = sym;
+            if (i == n - 1) *m = at[j] + (sym != skip);
+        }
+    }
+}
+
+// In front of a piece's bytes, in the pinned buffer and on the device, for the sessions that follow the contigs (coral_comp.hip,
+// coral_sketch.hip): the header lines that open in the piece, at most MAX_BOUND of them (a piece with more is fed as several).
+constexpr int MAX_BOUND = 1024;
+struct PieceHead {
+    uint32_t n_bytes, n_bounds, open_before, pad;
+    uint32_t bounds[MAX_BOUND];                  // byte offsets of the header lines that open in the piece, rising
+};
+constexpr size_t HEAD_BYTES = (sizeof(PieceHead) + 255) & ~(size_t)255;
+
 enum { EV_UP0, EV_UP1, EV_K0, EV_K1, EV_DONE, N_EV };
 
 struct PieceStager {

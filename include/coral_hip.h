@@ -1212,6 +1212,88 @@ int coral_fastq_rows(void *handle, int64_t n_reads, int32_t *length, int64_t *qu
 /* scripts/report_nanopore_qc.py:35-48: the end of the session */
 int coral_fastq_close(void *handle);
 
+/* ------------------------------------------------------------------------------------------------
+ * The minimizer sketch of a reference genome and its seed index (`sketch`): the first stage of `winnowmap -W repetitive_k15.txt
+ * -ax map-ont` of the reference's scripts/align_nanopore_reads.sh:34, and the only use repetitive_k15.txt has.  Neither winnowmap
+ * nor minimap2 was available to compare with; the rule (coral_sketch_core.h) is what both backends compute, exactly:
+ *   text      FASTA bytes, fed in pieces of any size; the result does not depend on the cuts.  Lines, contigs, names and the
+ *             refusals (CORAL_ERR_FORMAT) are the composition session's.  Every byte of a sequence line but '\n' and '\r' is one
+ *             position of its contig; ACGTacgt are the bases, any other byte is a non-base in its place.  A contig of 2^31
+ *             positions or more, or 2^32 contigs or more: CORAL_ERR_CAPACITY.
+ *   k-mer     1 <= k <= 16; the k bases from position p on; fwd / rev as the k-mer counter's.  Invalid with a non-base in it or
+ *             with fwd == rev.  strand = rev < fwd, canon = min(fwd, rev), key = hash64(canon) | repetitive(canon) << 2k, hash64
+ *             the invertible integer hash, every step taken & (4^k - 1).  `weights`: one bit per canonical k-mer, 4^k bits in
+ *             uint32 words (coral_sketch_bitmap_bytes(k)), bit (canon & 31) of word canon >> 5; NULL: no k-mer is repetitive.
+ *   windows   1 <= w <= 256.  A contig with n >= 1 k-mer positions has the windows of min(w, n) consecutive positions inside it;
+ *             an invalid k-mer keeps its place with the key +infinity.  Position p is a minimizer iff its k-mer is valid and its
+ *             key is the minimum of at least one window that holds p; tied minima all count.
+ *   output    keys[i], values[i] = contig << 32 | pos << 1 | strand, uint64, in (contig, pos) order, `capacity` entries each, the
+ *             caller's memory.
+ * A session, so that the caller owns the reading of the file:
+ *   open      device < 0: the host backend, one thread, arrays in host memory; staging_bytes, workspace and stream are ignored.
+ *             device >= 0: `weights`, the arrays and `workspace` (coral_sketch_workspace_bytes(staging_bytes); the library
+ *             allocates no device memory) are device memory, the kernels run on `stream`; the session owns two pinned staging
+ *             buffers of staging_bytes (16 .. 2^30) and a copy stream.
+ *   feed      the next n bytes.  Device: header lines found in the caller's bytes (memchr) and blanked in the pinned copy but for
+ *             their '>', which goes up with the headers' byte offsets on the copy stream beside the kernels of the piece before (a
+ *             piece with more headers than geometry[4] is fed as several); then on `stream`: scan of the keep flags,
+ *             k_sketch_scatter (symbols behind the geometry[1] carried ones), k_sketch_walk (the table of contig starts, the
+ *             decided positions), k_sketch_tile twice with a scan between (count, write: a workgroup per geometry[0] positions,
+ *             keys with halos in LDS, two sliding passes), k_sketch_carry.  No host wait for the kernels.
+ *   finish    waits; stats[0..6] (8 entries) = contigs, positions, minimizers, minimizers written, 0, 0, the bytes of the names.
+ *             seconds[0..3] (or NULL) = upload, symbols + contig table, sketch (host: the whole feed), the last tile.  More
+ *             minimizers than the capacity: CORAL_ERR_CAPACITY, stats filled (stats[2] entries suffice), nothing written
+ *             behind the capacity.
+ *   contigs   lengths[c], and names[name_off[c] .. name_off[c + 1]) (name_off: contigs + 1 entries), host arrays.
+ *   close     frees the session (never the arrays, the weights or the workspace).
+ * The index, over the two arrays (device < 0: host arrays; else device arrays, and the call waits for `stream`):
+ *   sort      by key, stably, so that ties keep their (contig, pos) order; device: one radix sort over the key's 2k + 1 bits in
+ *             `workspace` (coral_sketch_sort_workspace_bytes(n)).
+ *   lookup    first[i], count[i] = the entries of query_keys[i] in the sorted keys (first = the insertion point for count 0).
+ *   anchors   query minimizers (query, qpos, qstrand, qkey), n_queries of them: a key with more than max_occ entries is dropped,
+ *             every other one gives per entry anchor_query = query << 32 | qpos and anchor_ref = the entry's value with its
+ *             strand bit ^ qstrand; query order, then index order; count, scan, write in `workspace`
+ *             (coral_sketch_anchors_workspace_bytes(n_queries)).  *n_anchors = how many there are; more than the capacity:
+ *             CORAL_ERR_CAPACITY with the first `capacity` written - ask again with *n_anchors.
+ * coral_sketch_geometry -> geometry[0..7] = positions per tile of k_sketch_tile, symbols carried between pieces, threads per
+ *   workgroup, positions per thread, the header lines one piece holds, the entries of the contig table, the smallest staging size,
+ *   the largest w.
+ * Errors go to coral_bam_last_error.
+ * ------------------------------------------------------------------------------------------------ */
+/* scripts/align_nanopore_reads.sh:34 (`-W repetitive_k15.txt`): the bytes of the weights' bitmap at k */
+int64_t coral_sketch_bitmap_bytes(int32_t k);
+/* scripts/align_nanopore_reads.sh:34: the device scratch of a sketching session */
+int64_t coral_sketch_workspace_bytes(int64_t staging_bytes);
+/* scripts/align_nanopore_reads.sh:34: the launch geometry of the kernels behind the sketch */
+int coral_sketch_geometry(int32_t *geometry);
+/* scripts/align_nanopore_reads.sh:34 (`winnowmap -W ... ref.fa`, the mapper's indexing of the reference): a sketching session */
+int coral_sketch_open(int32_t k, int32_t w, int32_t device, const void *weights, void *keys, void *values, int64_t capacity,
+                      int64_t staging_bytes, void *workspace, int64_t workspace_bytes, void *stream, void **handle);
+/* scripts/align_nanopore_reads.sh:34: the next bytes of the FASTA */
+int coral_sketch_feed(void *handle, const uint8_t *bytes, int64_t n);
+/* scripts/align_nanopore_reads.sh:34: the end of the stream and the counts */
+int coral_sketch_finish(void *handle, int64_t *stats, double *seconds);
+/* scripts/align_nanopore_reads.sh:34 (the @SQ lines of the mapper's output): the contigs' lengths and names */
+int coral_sketch_contigs(void *handle, int64_t n_contigs, int64_t *lengths, int64_t names_capacity, uint8_t *names,
+                         int64_t *name_off);
+/* scripts/align_nanopore_reads.sh:34: the end of the session */
+int coral_sketch_close(void *handle);
+/* scripts/align_nanopore_reads.sh:34 (the mapper's hash table of the reference's minimizers): the device scratch of the sort */
+int64_t coral_sketch_sort_workspace_bytes(int64_t n);
+/* scripts/align_nanopore_reads.sh:34: the pairs sorted by key */
+int coral_sketch_sort(int32_t device, void *keys, void *values, int64_t n, int32_t k, void *workspace, int64_t workspace_bytes,
+                      void *stream);
+/* scripts/align_nanopore_reads.sh:34 (a read minimizer's look-up in the table): the entries of given keys */
+int coral_sketch_lookup(int32_t device, const void *sorted_keys, int64_t n, const void *query_keys, int64_t n_queries,
+                        int64_t *first, int64_t *count, void *stream);
+/* scripts/align_nanopore_reads.sh:34: the device scratch of the expansion */
+int64_t coral_sketch_anchors_workspace_bytes(int64_t n_queries);
+/* scripts/align_nanopore_reads.sh:34 (the seeds that the mapper chains): read minimizers expanded into anchors */
+int coral_sketch_anchors(int32_t device, const void *sorted_keys, const void *values, int64_t n, const uint32_t *query,
+                         const uint32_t *qpos, const uint8_t *qstrand, const void *qkey, int64_t n_queries, int64_t max_occ,
+                         int64_t capacity, void *anchor_query, void *anchor_ref, void *workspace, int64_t workspace_bytes,
+                         void *stream, int64_t *n_anchors);
+
 #ifdef __cplusplus
 }
 #endif
