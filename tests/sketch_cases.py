@@ -1,8 +1,9 @@
 """The minimizer sketch's rule restated in plain Python by brute force, O(n w), straight from its definition - split the text into
 contigs, give every position of a contig its key or +infinity, list the windows, take every position whose key is the minimum of a
 window that holds it - and the table of FASTA byte strings that the CPU tests (tests/test_sketch_core.py: the host backend against
-this restatement) and the GPU tests (tests/test_sketch_gpu.py: the device against the host backend) share.  Nothing here calls the
-library but ``feed_in_pieces``."""
+this restatement) and the GPU tests (tests/test_sketch_gpu.py and tests/test_sketch_limits_gpu.py: the device against the host
+backend) share.  Nothing here calls the library but ``geometry`` and ``feed_in_pieces``, which runs a session on the host or, with
+guard entries behind its arrays and its workspace, on a GPU."""
 import ctypes as C
 import functools
 
@@ -11,6 +12,11 @@ import numpy as np
 from tests import kmer_cases
 
 KW = ((5, 4), (8, 1), (11, 5), (15, 50), (3, 256))
+EDGE_KW = ((16, 256), (16, 255), (16, 1), (16, 50), (1, 1), (1, 256), (2, 3))      # the limits of k and w; kept out of KW, which multiplies the whole case table
+MANY_HEADERS_KW = ((3, 4), (16, 256), (1, 1))        # of the texts with more header lines than a device piece holds
+GUARD = 64                           # untouched entries asked for behind every device output array,
+WS_GUARD = 4096                      # and bytes of GUARD_BYTE behind every device workspace
+SENTINEL, GUARD_BYTE = 0x5A5A5A5A5A5A5A5A, 0xA5
 INF = float("inf")
 REFUSED = "refused"                  # what `restate` gives for a text with a sequence byte in front of the first header line
 _CODE = {65: 0, 67: 1, 71: 2, 84: 3, 97: 0, 99: 1, 103: 2, 116: 3}
@@ -112,14 +118,57 @@ def canonical(seq: bytes) -> int:
 
 
 # ---- the library, fed in pieces ---------------------------------------------------------------------------------------------------
-def feed_in_pieces(data: bytes, k: int, w: int, piece: int, capacity: int, bitmap=None):
-    """The host backend through the C ABI, ``piece`` bytes a feed (0: the whole text at once) -> (rc of the first call that failed
-    or of finish, stats list, rows, names, lengths)."""
+WHOLE = 2 << 20                      # a staging size that holds every text here
+
+
+def guarded(n: int, device):
+    """A device int64 tensor of n + GUARD entries, every one SENTINEL: an output array of n entries with its guard behind it."""
+    import torch
+    return torch.full((n + GUARD,), SENTINEL, dtype=torch.int64, device=device)
+
+
+def guarded_workspace(n_bytes: int, device):
+    """A device workspace of n_bytes + WS_GUARD bytes, every one GUARD_BYTE (the library is told of n_bytes)."""
+    import torch
+    assert n_bytes >= 0
+    return torch.full((n_bytes + WS_GUARD,), GUARD_BYTE, dtype=torch.uint8, device=device)
+
+
+def assert_untouched(array, n: int, what=""):
+    """Everything from entry n on of a ``guarded`` array is still SENTINEL."""
+    assert bool((array[n:] == SENTINEL).all()), "entries behind the first %d were written: %s" % (n, what)
+
+
+def assert_workspace_guard(ws, n_bytes: int, what=""):
+    assert ws.numel() == n_bytes + WS_GUARD and bool((ws[n_bytes:] == GUARD_BYTE).all()), "bytes behind the workspace were written: %s" % (what,)
+
+
+def feed_in_pieces(data: bytes, k: int, w: int, piece: int, capacity: int, bitmap=None, device=None):
+    """One session through the C ABI, ``piece`` bytes a feed (0: the whole text at once) -> (rc of the first call that failed or of
+    finish, stats list, rows, names, lengths).  ``device`` None: the host backend.  Else the same session on that GPU at staging
+    ``piece or WHOLE``: the arrays have GUARD entries behind the capacity and hold SENTINEL, the workspace has WS_GUARD bytes of
+    GUARD_BYTE behind it, and after finish nothing behind the written entries and behind the workspace has changed.  Capacity 0: no
+    arrays."""
     from coral_amd import _lib
     L = _lib.lib()
-    keys, values = np.zeros(max(capacity, 1), dtype=np.uint64), np.zeros(max(capacity, 1), dtype=np.uint64)
     h = C.c_void_p()
-    assert L.coral_sketch_open(k, w, -1, bitmap.ctypes.data if bitmap is not None else None, keys.ctypes.data, values.ctypes.data, capacity, 0, None, 0, None, C.byref(h)) == 0
+    if device is None:
+        keys, values = np.zeros(max(capacity, 1), dtype=np.uint64), np.zeros(max(capacity, 1), dtype=np.uint64)
+        assert L.coral_sketch_open(k, w, -1, bitmap.ctypes.data if bitmap is not None else None, keys.ctypes.data if capacity else None, values.ctypes.data if capacity else None, capacity,
+                                   0, None, 0, None, C.byref(h)) == 0
+    else:
+        import torch
+        dev = torch.device(device)
+        torch.cuda.set_device(dev)
+        staging = piece or WHOLE
+        dkeys, dvalues = guarded(capacity, dev), guarded(capacity, dev)
+        ws_bytes = int(L.coral_sketch_workspace_bytes(staging))
+        ws = guarded_workspace(ws_bytes, dev)
+        dbitmap = torch.from_numpy(bitmap.view(np.int32)).to(dev) if bitmap is not None else None
+        stream = torch.cuda.current_stream(dev)
+        stream.synchronize()
+        assert L.coral_sketch_open(k, w, dev.index or 0, dbitmap.data_ptr() if dbitmap is not None else None, dkeys.data_ptr() if capacity else None, dvalues.data_ptr() if capacity else None,
+                                   capacity, staging, ws.data_ptr(), ws_bytes, stream.cuda_stream, C.byref(h)) == 0
     stats = (C.c_int64 * 8)()
     try:
         buf = np.frombuffer(data, dtype=np.uint8) if data else np.zeros(1, dtype=np.uint8)
@@ -137,6 +186,14 @@ def feed_in_pieces(data: bytes, k: int, w: int, piece: int, capacity: int, bitma
             assert L.coral_sketch_contigs(h, n_contigs, lengths.ctypes.data, names_bytes, blob.ctypes.data, name_off.ctypes.data) == 0
     finally:
         L.coral_sketch_close(h)
+    if device is not None:
+        torch.cuda.synchronize(dev)
+        what = (k, w, piece, capacity)
+        assert 0 <= stats[3] <= capacity
+        assert_untouched(dkeys, int(stats[3]), what)
+        assert_untouched(dvalues, int(stats[3]), what)
+        assert_workspace_guard(ws, ws_bytes, what)
+        keys, values = dkeys.cpu().numpy().view(np.uint64), dvalues.cpu().numpy().view(np.uint64)
     text = blob.tobytes()
     names = [text[name_off[c]:name_off[c + 1]].decode() for c in range(n_contigs)]
     return rc, list(stats), rows_of(keys[:stats[3]], values[:stats[3]]), names, lengths.tolist()
@@ -195,6 +252,77 @@ def six_records() -> bytes:
     seq[15000:15600] = bytes(seq[15000:15600]).lower()
     cuts = [0, 40, 3000, 3049, 11000, 11064, 20_000]
     return b"".join(b">rec%d words\n" % i + kmer_cases.wrap(bytes(seq[a:b]), 60) for i, (a, b) in enumerate(zip(cuts, cuts[1:])))
+
+
+@functools.lru_cache(maxsize=None)
+def limits_text() -> bytes:
+    """One contig of 6 000 random bases with an N at 2000 and 300 x AC from 4000 on, in lines of 60: the text of the extreme k and w
+    (EDGE_KW), short enough for the O(n w) restatement at w = 256."""
+    seq = bytearray(kmer_cases.random_bases(np.random.RandomState(31), 6000))
+    seq[2000:2001] = b"N"
+    seq[4000:4600] = b"AC" * 300
+    return b">limits\n" + kmer_cases.wrap(bytes(seq), 60)
+
+
+def many_headers_text(geometry) -> bytes:
+    """More header lines than one piece of the device session holds, several times over, sized from coral_sketch_geometry
+    (``geometry``: its 8 entries): 3 max_bound + 928 empty contigs of one name, a contig of 300 bases, max_bound + 476 empty contigs,
+    and a contig of 8 bases without a final newline.  Fed whole, the device cuts a piece at every max_bound header lines; the
+    second piece finds the carry full of contig starts and adds max_bound of its own, which fills the contig table as far as it
+    is ever filled (1 + carry + max_bound entries)."""
+    max_bound, carry = int(geometry[4]), int(geometry[1])
+    assert max_bound > carry                             # (the first piece ends on more than `carry` empty contigs)
+    return _many_headers_text(max_bound)
+
+
+@functools.lru_cache(maxsize=None)
+def _many_headers_text(max_bound: int) -> bytes:
+    rng = np.random.RandomState(32)
+    return b">x\n" * (3 * max_bound + 928) + b">last\n" + kmer_cases.random_bases(rng, 300) + b"\n" + b">y\n" * (max_bound + 476) + b">z\nACGTTGCA"
+
+
+@functools.lru_cache(maxsize=None)
+def one_base_contigs() -> bytes:
+    """3 000 contigs of one random base each: contig boundaries and bases alternate in everything the device carries."""
+    bases = kmer_cases.random_bases(np.random.RandomState(33), 3000)
+    return b"".join(b">s\n%c\n" % c for c in bases)
+
+
+@functools.lru_cache(maxsize=None)
+def poly_a_6200() -> bytes:
+    """6 200 x A in lines of 61: at (k, w) = (5, 4) every one of its 6 196 k-mer positions is a minimizer, so output rank r is
+    contig position r - the text of the capacity tests."""
+    return b">p\n" + kmer_cases.wrap(b"A" * 6200, 61)
+
+
+def geometry() -> tuple:
+    """coral_sketch_geometry's 8 entries: tile, carry, block, items, max_bound, table_cap, the smallest staging size, the largest w."""
+    from coral_amd import _lib
+    g = (C.c_int32 * 8)()
+    assert _lib.lib().coral_sketch_geometry(g) == 0
+    return tuple(g)
+
+
+@functools.lru_cache(maxsize=None)
+def k16_weights_case():
+    """-> (text, k, w, listed): limits_text() at (16, 50) and three canonical k-mers to list as repetitive.  The one of the
+    smallest key outside the tandem: it is a minimizer, so listing it changes or removes its row.  The two of the
+    AC tandem at 4000: the windows inside the tandem are repetitive as a whole and still yield their minimum, so rows with the
+    repetitive bit - bit 32 at k = 16 - stay in the sketch."""
+    data, k, w = limits_text(), 16, 50
+    seq = contigs_of(data)[0][1]
+    _key, _contig, pos, _strand = min(r for r in restate(data, k, w)[2] if not 4000 <= r[2] <= 4600 - k)
+    listed = frozenset([canonical(seq[pos:pos + k]), canonical(b"AC" * 8), canonical(b"CA" * 8)])
+    assert len(listed) == 3 and seq[4000:4600] == b"AC" * 300
+    return data, k, w, listed
+
+
+def assert_bit_32_marks_the_listed(data: bytes, rows, listed, k: int = 16):
+    """In a sketch at k = 16 some rows carry bit 32, and they are exactly the rows of the listed k-mers."""
+    seq = contigs_of(data)[0][1]
+    marked = [r for r in rows if r[0] >> 32]
+    assert len(marked) > 100 and all(r[0] >> 32 == 1 for r in marked)
+    assert marked == [r for r in rows if canonical(seq[r[2]:r[2] + k]) in listed]
 
 
 @functools.lru_cache(maxsize=None)

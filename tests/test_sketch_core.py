@@ -1,6 +1,7 @@
 """The minimizer sketch on the CPU: coral_sketch_core.h through the host backend (coral_sketch_host.h, coral_sketch.cpp) against the
-brute-force restatement of tests/sketch_cases.py, the sorted index with its lookup and anchors, the weights, the capacity retry and
-the saved file.  Every result is integers: every comparison is exact."""
+brute-force restatement of tests/sketch_cases.py - at the limits of k and w and with more header lines than a device piece holds
+too -, the sorted index with its lookup and anchors, the weights, the capacities around the number of minimizers, the capacity
+retry and the saved file.  Every result is integers: every comparison is exact."""
 import io
 
 import numpy as np
@@ -62,6 +63,41 @@ def test_host_backend_equals_the_restatement(name, k, w):
     assert stats[:4] == [len(want[0]), sum(want[1]), len(want[2]), len(want[2])]
 
 
+@pytest.mark.parametrize("k,w", SC.EDGE_KW)
+def test_host_backend_equals_the_restatement_at_the_limits_of_k_and_w(k, w):
+    """k = 16 (the mask is 2^32 - 1, the repetitive bit is bit 32), k = 1 and 2 (every second 2-mer can be a palindrome), w = 1 and
+    w = 256, and the pair (16, 256) that the device's carry and LDS arrays are sized for."""
+    texts = [SC.limits_text()] + ([SC.cases()["contigs_around_k_and_w"]] if (k, w) == (16, 256) else [])
+    for data in texts:
+        names, lengths, want = SC.restate(data, k, w)
+        assert len(want) > 0
+        for piece in (0, 17):
+            rc, stats, rows, got_names, got_lengths = SC.feed_in_pieces(data, k, w, piece, 1 << 13)
+            assert rc == 0 and (got_names, got_lengths) == (names, lengths)
+            assert rows == want
+            assert stats[:4] == [len(names), sum(lengths), len(want), len(want)]
+    if (k, w) == (16, 1):                                            # every valid position is chosen: keys that need all 32 bits
+        assert max(key for key, *_ in SC.restate(SC.limits_text(), k, w)[2]) >= 1 << 31
+
+
+@pytest.mark.parametrize("k,w", SC.MANY_HEADERS_KW)
+@pytest.mark.parametrize("text", ("many_headers", "one_base_contigs"))
+def test_more_header_lines_than_a_device_piece_holds(text, k, w):
+    g = SC.geometry()
+    data = SC.many_headers_text(g) if text == "many_headers" else SC.one_base_contigs()
+    names, lengths, want = SC.restate(data, k, w)
+    if text == "many_headers":
+        assert (len(names), sum(lengths)) == (4 * g[4] + 1406, 308)
+        assert len(want) == {(3, 4): 131, (16, 256): 1, (1, 1): 308}[k, w]      # recorded from the restatement: pins the text's generator
+    else:
+        assert (len(names), sum(lengths)) == (3000, 3000) and len(want) == (3000 if k == 1 else 0)      # a minimizer a contig, or no k-mer at all
+    for piece in (0, 16, 3073):
+        rc, stats, rows, got_names, got_lengths = SC.feed_in_pieces(data, k, w, piece, 1 << 12)
+        assert rc == 0 and (got_names, got_lengths) == (names, lengths)
+        assert rows == want
+        assert stats[:4] == [len(names), sum(lengths), len(want), len(want)]
+
+
 def test_expected_densities_of_the_table():
     """poly-A: every k-mer position; AC tandem: its two k-mers alternate, so every second position (every one at w = 1); ACGT
     tandem at k = 8, w = 1: the k-mers at even positions are their own reverse complements and invalid, the odd ones are chosen."""
@@ -115,6 +151,18 @@ def test_an_all_repetitive_window_still_yields_its_minimum():
     assert len(poly) == 36 and all(key == (minimizers.hash64(0, k) | 1 << 2 * k) for key, *_ in poly)
 
 
+def test_a_repetitive_kmer_at_k16_carries_bit_32():
+    """The widest key: at k = 16 the repetitive bit is bit 32 and the bitmap has 4^16 bits (512 MiB)."""
+    data, k, w, listed = SC.k16_weights_case()
+    plain, want = SC.restate(data, k, w)[2], SC.restate(data, k, w, listed)[2]
+    assert want != plain and not any(key >> 32 for key, *_ in plain)
+    SC.assert_bit_32_marks_the_listed(data, want, listed)            # the windows inside the AC tandem: all repetitive, their minimum is chosen
+    assert _lib.lib().coral_sketch_bitmap_bytes(16) == 512 << 20
+    rc, stats, rows, _names, _lengths = SC.feed_in_pieces(data, k, w, 0, 1 << 13, bitmap=SC.bitmap_of(listed, k))
+    assert rc == 0 and rows == want
+    SC.assert_bit_32_marks_the_listed(data, rows, listed)
+
+
 def test_the_bitmap_is_built_from_a_kmers_file(tmp_path):
     from coral_amd import kmers
     k = 8
@@ -146,6 +194,20 @@ def test_capacity_overflow_reports_the_needed_size_and_the_retry_succeeds():
     assert rc == -3 and stats[2] == len(want) and stats[3] == 100 and rows == want[:100]      # CORAL_ERR_CAPACITY; nothing behind the capacity
     idx = host_index(data, 5, 4, _capacity=100)
     assert minimizers.LAST_SKETCH["attempts"] == 2 and SC.index_rows(idx) == SC.sorted_rows(want)
+
+
+@pytest.mark.parametrize("piece", (0, 1031))
+def test_capacities_around_the_number_of_minimizers(piece):
+    """CORAL_ERR_CAPACITY below n and success from n on, stats[2] = n, stats[3] = the written ones, and they are the first ones."""
+    data = SC.poly_a_6200()
+    want = SC.restate(data, 5, 4)[2]
+    n = len(want)
+    assert n == 6196 and [r[2] for r in want] == list(range(n))
+    for cap in (0, 1, 64, n - 1, n, n + 1):
+        rc, stats, rows, _names, _lengths = SC.feed_in_pieces(data, 5, 4, piece, cap)
+        assert rc == (-3 if cap < n else 0), cap
+        assert (stats[2], stats[3]) == (n, min(cap, n)), cap
+        assert rows == want[:cap], cap
 
 
 def test_a_stream_that_cannot_be_started_over_raises():

@@ -77,14 +77,14 @@ def edge_texts(k, w):
         out["ties_start", at] = b">a\n" + rb(rng, i) + b"A" * (2 * w + k) + tail + b"\n"
         out["ties_end", at] = b">a\n" + rb(rng, i - (2 * w + k) + 1) + b"A" * (2 * w + k) + tail + b"\n"
         out["ties_across", at] = b">a\n" + rb(rng, i - w) + b"AC" * (w + k) + tail + b"\n"
-        short = k + w - 3                                            # w - 2 k-mers: the clipped single window
+        short = max(k + w - 3, 0)                                    # w - 2 k-mers: the clipped single window (w = 1: no base at all)
         out["short_contig_ends", at] = b">a\n" + rb(rng, i - short - 1) + b"\n>s\n" + rb(rng, short) + b"\n>b\n" + tail + b"\n"
         out["short_contig_starts", at] = b">a\n" + rb(rng, i - 1) + b"\n>s\n" + rb(rng, short) + b"\n>b\n" + tail + b"\n"
         out["short_contig_across", at] = b">a\n" + rb(rng, i - 1 - short // 2) + b"\n>s\n" + rb(rng, short) + b"\n>b\n" + tail + b"\n"
     return out
 
 
-@pytest.mark.parametrize("k,w", ((15, 50), (11, 5), (3, 256)))
+@pytest.mark.parametrize("k,w", ((15, 50), (11, 5), (3, 256), (16, 256), (1, 1)))
 def test_contig_ends_starts_n_runs_and_ties_at_the_tile_edges(k, w):
     for (what, at), data in edge_texts(k, w).items():
         want = host_rows(data, k, w)
